@@ -8,7 +8,7 @@ solve.  Workload at every N: the configuration the metric is quoted on, "Venice-
 (SURVEY.md F7), so it is the seeded dense SBA-like generator of SURVEY.md §8d with n = 1778 cameras
 (tests/xm_testlib.py:gen_dense).  For N > 1 the same problem is row-partitioned over the ranks (strong scaling).
 
-Launch: python bench.py [--gpus N --steps K --warmup W].
+Launch: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR].
   * under torch.distributed.run (one rank per GPU, what the driver does): one process per GPU, RCCL all-gathers inside the solver;
   * plain `python bench.py --gpus N`: NO launcher -- the library's single-process multi-GPU mode (xm_problem_t.n_gpus: one host thread
     per GPU, direct peer-write exchange fused into the tCG).  When the box has fewer than N GPUs the N ranks are "virtual devices" on
@@ -71,7 +71,6 @@ else:
 os.environ.setdefault("GLOO_SOCKET_IFNAME", "lo")              # control-plane rendezvous on loopback (hostname may not resolve)
 os.environ.setdefault("NCCL_SOCKET_IFNAME", "lo")              # RCCL bootstrap of the single-node communicator likewise
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC: required by RCCL on this driver (multi-process runs)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")           # virtual devices (N ranks on one GPU) need a hardware queue per rank's stream (8 ranks: 16 queues)
 if "WORLD_SIZE" not in os.environ and _argv_gpus() != "1":   # single-process multi-GPU, possibly N virtual devices on ONE GPU:
     os.environ.setdefault("HSA_ENABLE_SDMA", "0")                                # their streams must not share the copy engine's in-order queue (copies become kernels)
 # cpu_baseline (rank 0 of a 1-GPU run only): OpenMP threads stay where they first touched their share of Q, spread over the L3 slices /
@@ -332,6 +331,28 @@ def kkt_pair(tl, xmamd_mod, budget_s):
 _JSON_FD = [1]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, R, s, info):
+    """--dump-outputs DIR: what the last timed solve handed its caller, as float64 DIR/<name>.npy -- R (3n x rank), s (n) and
+    `solve`, the outcome [rank, status, primal, dual, min_eig, tcg_iters, outer_iters].  The inputs are seeded, so two builds run
+    with the same arguments can be compared file by file.  An array beyond its share of the 64 MB budget is stored as a fixed,
+    seeded sample of its rows, their indices in DIR/<name>_rows.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {"R": np.asarray(R, dtype=np.float64), "s": np.asarray(s, dtype=np.float64),
+              "solve": np.array([info[k] for k in ("rank", "status", "primal", "dual", "min_eig", "tcg_iters", "outer_iters")], dtype=np.float64)}
+    share = DUMP_LIMIT_BYTES // (2 * len(arrays))          # per array, with room for the row indices of a sample
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            row_bytes = a.nbytes // a.shape[0]
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=share // row_bytes, replace=False)).astype(np.int64)
+            np.save(os.path.join(d, name + "_rows.npy"), rows)
+            a = a[rows]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def _claim_stdout():
     """The contract is ONE JSON line on stdout.  Libraries loaded during the run write there too (RCCL's "Librccl path : ..." banner sits in
     libc's buffer until the process exits, i.e. AFTER the line): from here on file descriptor 1 is stderr for everybody, and the JSON line
@@ -382,7 +403,7 @@ def _arm_guards(rank, ngp, args, workload_desc):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=6)
+    ap.add_argument("--steps", type=int, default=6, help="timed solves (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="venice1778")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg (0 = skip)")
@@ -411,7 +432,11 @@ def main():
                     "kernel (xm_tuning_t.sym_min_rows; 0 = the library's measured default)")
     ap.add_argument("--stream-policy", type=int, default=None, help="measurement aid (include/xm_bench.h: xm_bench_dense_policy): cache policy of the matrix "
                     "streams forced -- 0 all cacheable, 1 all non-temporal, >= 2 a cacheable prefix of that many MB; default: the library's size rules")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed solve returned (R, s, the solve's outcome) as float64 DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     _claim_stdout()
 
     import torch
@@ -604,6 +629,8 @@ def _run(args, wl, tl, t0, Q, tkw, team, gpu_map, ngp, retr, rank, world, torch,
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     _PHASE[0] = "after the timed solves (secondary legs)"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last_sol)
     barrier()
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64)

@@ -16,7 +16,6 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "xm-code_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import numpy as np            # noqa: E402
 import xmamd                  # noqa: E402
 import xm_testlib as tl       # noqa: E402  (the seeded view-graph generator of SURVEY 8d)

@@ -4,7 +4,6 @@ import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 code = f"""
 import os, sys, ctypes as C
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, {os.path.join(ROOT, 'xm-code_amd')!r})
 import xmamd
 us = C.c_double()

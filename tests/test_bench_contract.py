@@ -84,3 +84,26 @@ def test_first_multi_gpu_run_script_commands_parse():
             assert fl in h.stdout, (script, fl)
     d = subprocess.run([sys.executable, os.path.join(root, "scripts", "multi_gpu_probe.py"), "--dry-run", "--gpus", "8"], capture_output=True, text=True, cwd=root)
     assert d.returncode == 0 and '"gpus": 8' in d.stdout
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_budget(tmp_path):
+    """--dump-outputs DIR: R, s and the solve's outcome as float64 .npy files; an array beyond its share of the budget becomes the same
+    seeded sample of its rows in every run, with the row indices beside it"""
+    import numpy as np
+    r = _run(f"""
+        import numpy as np, bench
+        R = np.arange(3 * 50 * 4, dtype=np.float64).reshape(150, 4); s = np.linspace(1, 2, 50)
+        info = dict(rank=4, status=1, primal=1.5, dual=1.5, min_eig=-1e-9, tcg_iters=77, outer_iters=9)
+        bench.dump_outputs({str(tmp_path / 'a')!r}, R, s, info)
+        bench.DUMP_LIMIT_BYTES = 6 * 4 * 8 * 10                       # share per array: 10 rows of R
+        bench.dump_outputs({str(tmp_path / 'b')!r}, R, s, info)
+        bench.dump_outputs({str(tmp_path / 'c')!r}, R, s, info)
+    """)
+    assert r.returncode == 0, r.stderr
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("R", "s", "solve")}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["R"].shape == (150, 4) and a["s"].shape == (50,) and a["solve"].tolist() == [4, 1, 1.5, 1.5, -1e-9, 77, 9]
+    rows = np.load(tmp_path / "b" / "R_rows.npy")
+    assert len(rows) == 10 and np.array_equal(np.load(tmp_path / "b" / "R.npy"), a["R"][rows])
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "R_rows.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) < 6 * 4 * 8 * 10 + 6 * 128

@@ -1081,7 +1081,7 @@ def test_bench_two_ranks_flow(xmamd, transport):
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, XM_BENCH_SINGLE_DEVICE="1", GPU_MAX_HW_QUEUES="16", **({"XM_BENCH_SHM": "1"} if transport == "shm" else {"XM_BENCH_IPC": "1"}))
+    env = dict(os.environ, XM_BENCH_SINGLE_DEVICE="1", **({"XM_BENCH_SHM": "1"} if transport == "shm" else {"XM_BENCH_IPC": "1"}))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"]
     if transport == "ipc":
@@ -1117,7 +1117,8 @@ def test_bench_plain_command_needs_no_launcher(xmamd):
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(line) == 1
     d = json.loads(line[0])
-    assert d["n_gpus"] == 2 and d["solve"]["status"] == 1 and d["value"] > 0 and d["solve"]["exchange"] == 2
+    assert d["n_gpus"] == 2 and d["solve"]["status"] == 1 and d["value"] > 0
+    assert d["solve"]["exchange"] == (2 if xmamd.device_count() >= 2 or tl.virtual_ranks_wait_on_device(2) else 1)
     assert d["solve"]["primal"] == pytest.approx(0.2844696774, rel=1e-8)
     assert "ONE process" in d["config"]["parallelism"]
     assert d["transport"].startswith("direct peer writes") and d["fallback"] is None

@@ -410,7 +410,7 @@ def test_single_process_multi_gpu_equals_the_multi_process_run(xmamd, tmp_path, 
     stores, and in its release-fence form xm_tuning_t.exchange_fence) and with the un-fused peer all-gather between the launches
     (xm_tuning_t.exchange = 1)."""
     code = _team_worker_code()
-    env = dict(os.environ, XM_SHM_TIMEOUT="60", GPU_MAX_HW_QUEUES="16", XM_WATCHDOG_S="60")
+    env = dict(os.environ, XM_SHM_TIMEOUT="60", XM_WATCHDOG_S="60")
     tn = dict(sell=1) if case in ("sell", "sell_esc") else {}
     env["XMT_TUNING"] = json.dumps(tn)
     name = "/xm_t3_" + uuid.uuid4().hex[:12]
@@ -428,7 +428,7 @@ def test_single_process_multi_gpu_equals_the_multi_process_run(xmamd, tmp_path, 
         out = str(tmp_path / f"team{k}.npz")
         _run(code, ["team", world, out, case], dict(env, XMT_TUNING=json.dumps(dict(tn, exchange=ex, **extra))))
         t = np.load(out)
-        assert int(t["n_gpus"]) == world and int(t["exchange"]) == (2 if ex == 2 else 1)
+        assert int(t["n_gpus"]) == world and int(t["exchange"]) == (2 if ex == 2 and tl.virtual_ranks_wait_on_device(world) else 1)
         assert int(t["rank"]) == int(ref["rank"]) and int(t["status"]) == int(ref["status"]) == 1 and int(t["tcg"]) == int(ref["tcg"])
         assert np.array_equal(t["trace"], ref["trace"])
         assert np.array_equal(t["R"], ref["R"]) and np.array_equal(t["s"], ref["s"])
@@ -441,7 +441,7 @@ def test_one_process_per_gpu_over_ipc_handles_equals_the_single_process_team(xma
     directory, maps the peers' and runs the very kernels of the single-process team (push + epoch flag + bounded wait inside
     cg_step).  Here `world` processes share the one GPU of the box.  Every rank must reproduce the team run bit for bit."""
     code = _team_worker_code()
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="16", XM_WATCHDOG_S="60")
+    env = dict(os.environ, XM_WATCHDOG_S="60")
     if case == "sell_esc":
         env["XMT_TUNING"] = '{"sell": 1}'
     ref_out = str(tmp_path / "team.npz")
@@ -458,7 +458,7 @@ def test_one_process_per_gpu_over_ipc_handles_equals_the_single_process_team(xma
     assert all(p.returncode == 0 for p in procs), "\n".join(l[-1500:] for l in logs)
     for r in range(world):
         t = np.load(outs[r])
-        assert int(t["exchange"]) == 2 and int(ref["exchange"]) == 2
+        assert int(t["exchange"]) == 2 and int(ref["exchange"]) == (2 if tl.virtual_ranks_wait_on_device(world) else 1)
         assert int(t["rank"]) == int(ref["rank"]) and int(t["status"]) == int(ref["status"]) == 1 and int(t["tcg"]) == int(ref["tcg"])
         assert np.array_equal(t["trace"], ref["trace"])
         assert np.array_equal(t["R"], ref["R"]) and np.array_equal(t["s"], ref["s"])
@@ -468,14 +468,14 @@ def test_one_process_per_gpu_over_ipc_handles_equals_the_single_process_team(xma
 def test_eight_virtual_gpus(xmamd, tmp_path, case):
     """the node's real shape, N = 8, as virtual devices: 8 host threads, 8-way partition with padding cameras (dense: 41 cameras -> 6
     per rank, the last rank holds 5 inert ones; view graph with hubs: ranges balanced by stored blocks, + the XM^2 calls), 7 peers per
-    exchange.  Same certified optimum as one GPU.  (Each rank's stream needs a hardware queue of its own -- GPU_MAX_HW_QUEUES=16, set
-    by the binding before the runtime starts -- and a fresh process: a spinning wait that shares a queue with the push it waits for
-    ends in the bounded wait's XM_ERR_COMM, which is what a second 8-rank context in the same process ran into.  The ranks of one
+    exchange.  Same certified optimum as one GPU.  (More than four ranks on one device synchronise their collectives through the host,
+    and each 8-rank context gets a fresh process: a spinning wait that shares a queue with the push it waits for ends in the bounded
+    wait's XM_ERR_COMM, which is what a second 8-rank context in the same process ran into.  The ranks of one
     process on one device also share the copy engine's in-order queue: HSA_ENABLE_SDMA=0 makes every copy a kernel on the rank's own
     stream -- with the engine, rank A's device-to-host copy behind its wait kernel blocked rank B's copy in front of the push A was
     waiting for (found here: deterministic stall at the first all-gather after the certificate).)"""
     code = _team_worker_code()
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="16", HSA_ENABLE_SDMA="0", XM_WATCHDOG_S="60")
+    env = dict(os.environ, HSA_ENABLE_SDMA="0", XM_WATCHDOG_S="60")
     if case == "vg":
         env["XMT_TUNING"] = '{"sell": 1}'
     one, eight = str(tmp_path / "one.npz"), str(tmp_path / "eight.npz")
@@ -499,7 +499,7 @@ def test_symmetric_window_product_under_the_row_partition(xmamd, tmp_path, world
     arithmetic, fixed summation orders) and both the single-GPU optimum (rank escalation included: o = 4, 5, 6 fall back to the general
     kernel above sym_max_o)."""
     code = _team_worker_code()
-    env = dict(os.environ, XM_SHM_TIMEOUT="60", GPU_MAX_HW_QUEUES="16", XM_WATCHDOG_S="60", XMT_TUNING='{"sym": 1}')
+    env = dict(os.environ, XM_SHM_TIMEOUT="60", XM_WATCHDOG_S="60", XMT_TUNING='{"sym": 1}')
     name = "/xm_t4s_" + uuid.uuid4().hex[:12]
     outs = [str(tmp_path / f"shm{r}.npz") for r in range(world)]
     procs = [subprocess.Popen([sys.executable, "-c", code, f"shm{r}", str(world), outs[r], "dense_sym", name], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
@@ -525,7 +525,7 @@ def test_matrix_free_context_under_the_row_partition(xmamd, tmp_path, case, worl
     the reduced camera Laplacian's inverse, the ranks all-gather x_cam, and the chain's last kernel + epilogue run for the rank's cameras.
     Same certified optimum as the single-GPU context (rotations <= 1e-6), at test size and at Final-13682 size (6.4 M observations)."""
     code = _team_worker_code()
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="16", HSA_ENABLE_SDMA="0", XM_WATCHDOG_S="120")
+    env = dict(os.environ, HSA_ENABLE_SDMA="0", XM_WATCHDOG_S="120")
     one, team = str(tmp_path / "one.npz"), str(tmp_path / "team.npz")
     _run(code, ["single", 1, one, case], env, timeout=900)
     _run(code, ["team", world, team, case], env, timeout=900)
@@ -543,7 +543,7 @@ def test_rome13682_dense_storage_on_virtual_ranks_vs_recorded_oracle(xmamd, tmp_
     window's edge strips), the oracle's recorded optimum to 1e-9, rotations within 1e-6"""
     c = json.load(open(os.path.join(G, "synth", "rome13682_oracle.json")))
     out = str(tmp_path / "team.npz")
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="16", HSA_ENABLE_SDMA="0", XM_WATCHDOG_S="120")
+    env = dict(os.environ, HSA_ENABLE_SDMA="0", XM_WATCHDOG_S="120")
     _run(_team_worker_code(), ["team", world, out, "rome_dense"], env, timeout=900)
     t = np.load(out)
     assert int(t["n_gpus"]) == world and int(t["sym"]) == 1 and int(t["rank"]) == 3 and int(t["status"]) == 1
@@ -563,10 +563,10 @@ def test_multi_rank_baseline_sizes_vs_recorded_oracle(xmamd, tmp_path, case, wor
     fj, fr = {"venice": ("venice1778_oracle.json", "venice1778_oracle_rot.npy"), "rome_bsr": ("rome13682_oracle.json", "rome13682_oracle_rot.npy")}[case]
     c = json.load(open(os.path.join(G, "synth", fj)))
     out = str(tmp_path / "team.npz")
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="16", HSA_ENABLE_SDMA="0", XM_WATCHDOG_S="120")
+    env = dict(os.environ, HSA_ENABLE_SDMA="0", XM_WATCHDOG_S="120")
     _run(_team_worker_code(), ["team", world, out, case], env, timeout=900)
     t = np.load(out)
-    assert int(t["n_gpus"]) == world and int(t["exchange"]) == (2 if world <= 4 else 1)
+    assert int(t["n_gpus"]) == world and int(t["exchange"]) == (2 if tl.virtual_ranks_wait_on_device(world) else 1)
     assert int(t["rank"]) == c.get("rank", 3) and int(t["status"]) == 1
     assert float(t["primal"]) == pytest.approx(c["f"], rel=1e-8)
     rot, _ = tl.recover_rotations(t["R"], t["s"])
@@ -600,7 +600,7 @@ def test_single_process_multi_gpu_viewgraph_hubs_and_xm2(xmamd, tmp_path):
     quaternion-compressed sliced ELL is forced on.  The certified optimum equals the single-GPU one, and so does the XM^2 round
     (residuals, re-weighting, warm re-solve) that fans out to the ranks."""
     code = _team_worker_code()
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="16", XMT_TUNING='{"sell": 1}', XM_WATCHDOG_S="60")
+    env = dict(os.environ, XMT_TUNING='{"sell": 1}', XM_WATCHDOG_S="60")
     one = str(tmp_path / "one.npz")
     _run(code, ["single", 1, one, "vg"], env)
     a = np.load(one)
@@ -638,7 +638,7 @@ def test_file_surface_on_two_virtual_gpus(xmamd, tmp_path):
         XM.solve({str(d)!r}, 3, 1e-16, 0.0, 1000)
     """)
     env = {k: v for k, v in os.environ.items() if k != "XM_QUIET"}         # an earlier test of the session may have silenced the progress lines
-    out = _run(code, [], dict(env, XM_GPUS="2", XM_GPU_MAP="1", GPU_MAX_HW_QUEUES="16", XM_WATCHDOG_S="60"))
+    out = _run(code, [], dict(env, XM_GPUS="2", XM_GPU_MAP="1", XM_WATCHDOG_S="60"))
     assert "BM finished with rank 3" in out or "Terminate" in out
     R = tl.load_bin(str(d / "R.bin")); s = tl.load_bin(str(d / "s.bin")).reshape(-1)
     exp = json.load(open(os.path.join(G, "simple1", "expected.json")))
@@ -651,27 +651,45 @@ def test_file_surface_on_two_virtual_gpus(xmamd, tmp_path):
 def test_a_dead_peer_becomes_an_error_not_a_hang(xmamd, tmp_path):
     """every device-side wait of the peer exchange is bounded: with the group's spin limit at 2 s (a third of the host watchdog) and one
     rank made to skip its push (xm_tuning_t.debug_peer_mute) the solve must come back with XM_ERR_COMM, promptly, and the GPU must still work
-    afterwards"""
+    afterwards.  The two ranks are threads of one process where its hardware queues let them wait on the device, else two processes over
+    IPC handles (xm_comm_init_ipc): virtual ranks without the queues for it synchronise through the host and never wait on the device."""
+    in_process = tl.virtual_ranks_wait_on_device(2)
     code = textwrap.dedent(f"""
         import sys, os, time
         sys.path.insert(0, {os.path.join(ROOT, 'xm-code_amd')!r}); sys.path.insert(0, {os.path.join(ROOT, 'tests')!r})
         import numpy as np, xmamd, xm_testlib as tl
         P = tl.gen_vg(41, deg=3, sigma=1.5, seed=40)
-        ctx = xmamd.Context(Q=P["Q"], n_gpus=2, gpu_map=1, tuning=dict(debug_peer_mute=1))
+        if sys.argv[1] == "team":
+            ctx = xmamd.Context(Q=P["Q"], n_gpus=2, gpu_map=1, tuning=dict(debug_peer_mute=1))
+        else:
+            xmamd._chk(xmamd.lib().xm_comm_init_ipc(int(sys.argv[1]), 2, 0, sys.argv[2].encode(), 2.0))
+            ctx = xmamd.Context(Q=P["Q"], tuning=dict(debug_peer_mute=1))
         t0 = time.time()
         try:
             ctx.solve(6, 1e-9, 3.0)
             print("NO ERROR")
         except xmamd.XmError as e:
             print("ERR", time.time() - t0, e)
-        ctx.close()
+        try:                                                       # the peer may have left already: its teardown is not under test
+            ctx.close()
+            if sys.argv[1] != "team":
+                xmamd.lib().xm_comm_finalize()
+        except xmamd.XmError as e:
+            print("CLOSE", e)
         R, s, info = xmamd.solve_dense(P["Q"], 6, 1e-9, 3.0)
         print("AFTER", info["status"])
     """)
-    out = _run(code, [], dict(os.environ, GPU_MAX_HW_QUEUES="16", XM_WATCHDOG_S="6"), timeout=300)
-    err = [l for l in out.splitlines() if l.startswith("ERR")]
-    assert err and "-4" in err[0] and float(err[0].split()[1]) < 60.0, out[-800:]
-    assert "AFTER 1" in out
+    env = dict(os.environ, XM_WATCHDOG_S="6")
+    if in_process:
+        outs = [_run(code, ["team"], env, timeout=300)]
+    else:
+        name = "/xm_t3m_" + uuid.uuid4().hex[:12]
+        procs = [subprocess.Popen([sys.executable, "-c", code, str(r), name], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(2)]
+        outs = [p.communicate(timeout=300)[0].decode() for p in procs]
+        assert all(p.returncode == 0 for p in procs), "\n".join(o[-1500:] for o in outs)
+    err = [l for l in outs[0].splitlines() if l.startswith("ERR")]        # rank 0 waits for the muted rank 1
+    assert err and "-4" in err[0] and float(err[0].split()[1]) < 60.0, outs[0][-800:]
+    assert all("AFTER 1" in o for o in outs)
 
 
 # ---------------------------------------------------------------------------------------------- XM^2 with the reference's definitions

@@ -498,6 +498,15 @@ def schur_residuals_numpy(cam, lm, p, w, U):
     return np.sum((pu - xc[cam] + xl[lm]) ** 2, axis=1)
 
 
+def virtual_ranks_wait_on_device(ranks):
+    """does a single-process team of `ranks` virtual devices on one GPU fuse its tCG exchange (xm_problem_t.exchange 2)?  The rule of
+    PeerComm::device_waits: at most four ranks per device, and four of the runtime's hardware queues per rank of this process (the
+    queue count is read from the environment the way the HIP runtime reads it; unset means four)"""
+    v = os.environ.get("GPU_MAX_HW_QUEUES", "").strip()
+    q = int(v) if v.isdigit() and int(v) > 0 else 4
+    return ranks == 1 or (ranks <= 4 and 4 * ranks <= q)
+
+
 def env_tuning():
     """xm_tuning_t fields for a worker process of a test, handed over as JSON in XMT_TUNING (a variable of the TESTS: the library itself
     selects no kernel or layout through the environment) -> dict for xmamd.Context(tuning=...), or None"""

@@ -558,6 +558,17 @@ __global__ __launch_bounds__(256) void peer_wait_kernel(PeerPtrs pp, double *__r
         if (i < own0 || i >= own1) buf[i] = plain ? src[i] : __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// hardware queues the HIP runtime opens per device in this process (streams beyond that share them); the runtime's default when its
+// variable is unset is four
+int hw_queues_per_process() {
+    static const int n = [] {
+        const char *v = std::getenv("GPU_MAX_HW_QUEUES");
+        const int q = v ? std::atoi(v) : 0;
+        return q > 0 ? q : 4;
+    }();
+    return n;
+}
+
 struct PeerComm : Comm {
     std::shared_ptr<PeerGroup> g;
     char *arena = nullptr;
@@ -577,7 +588,13 @@ struct PeerComm : Comm {
     int kind() const override { return g->kind(); }
     bool peer() const override { return true; }
     int ranks_on_my_device() const override { return g->ranks_on_device_of(rank); }
-    bool device_waits() const override { return g->ranks_on_device_of(rank) <= 4; }
+    bool device_waits() const override {
+        const int r = g->ranks_on_device_of(rank);
+        if (r > 4) return false;
+        // threads of ONE process on one device share the process's hardware queues (see hw_queues_per_process): a waiting kernel
+        // blocks whatever is queued behind it, the peer's push included.  Device-side waits were proven with four queues per rank.
+        return g->kind() != 3 || r == 1 || 4 * r <= hw_queues_per_process();
+    }
     unsigned long long *flags_of(int r) const { return reinterpret_cast<unsigned long long *>(parena[r]); }
     unsigned long long *tickets() const { return reinterpret_cast<unsigned long long *>(arena) + kFlagWords; }
     double *stage_of(int r) const { return reinterpret_cast<double *>(static_cast<char *>(parena[r]) + kArenaHead); }

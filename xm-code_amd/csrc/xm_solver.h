@@ -76,7 +76,8 @@ struct Comm {
     virtual int ranks_on_my_device() const { return 1; }
     // may a kernel of this rank wait for its peers ON THE DEVICE?  Not when more than four ranks share one GPU (a test vehicle): a waiting
     // kernel holds its hardware queue, and the queues of eight ranks' pushes and waits are more than the device keeps active at once --
-    // the collectives are then synchronised through the host and the tCG exchange is not fused into cg_step
+    // the collectives are then synchronised through the host and the tCG exchange is not fused into cg_step.  Nor when several ranks of
+    // ONE process share a device with fewer than four hardware queues each (the runtime's GPU_MAX_HW_QUEUES): see PeerComm::device_waits
     virtual bool device_waits() const { return true; }
     virtual void set_exchange_fence(bool on) { (void)on; }   // peer transports: release fence instead of write-through stores in the collectives
     std::string fallback_note;   // why a faster transport was given up for this one (empty: first choice)
