@@ -120,7 +120,12 @@ typedef struct {
     int32_t schur_pcg_first;   /* XM_STORAGE_SCHUR, CG form: iterations enqueued in the first batch of the first product (0 = 26; tests force top-up batches) */
     int32_t schur_pcg_hess_digits; /* ... relative residual 10^-d of the inner solve inside Hessian products: 0 = 9, 6 .. 13 (13 = as tight as the
                                   gradient / cost / certificate products always are) */
-    int32_t reserved[2];
+    int32_t hess_f32;          /* 1: the Hessian products of the truncated CG read an fp32 copy of Q (rounded to nearest, made on the device at
+                                  creation; loaded as fp32, accumulated in f64).  Gradient, cost, certificate, escalation line search and Lanczos stay
+                                  on the f64 Q, so the stop test and the certificate are unchanged; only the tCG steps see the rounded operator.
+                                  Dense storage on one rank only: any other storage, n_gpus > 1, a communicator, or an entry of Q that is not
+                                  finite in fp32 gives XM_ERR_ARG.  0 (default): off */
+    int32_t reserved[1];
 } xm_tuning_t;
 
 typedef struct {
@@ -239,7 +244,8 @@ typedef struct {
     int32_t outer_on_device;   /* trust regions (rank levels) of this solve whose outer iteration was driven by the device (0: all by the host --
                                   XM_FLAG_HOST_OUTER, dense products without XM_FLAG_DEVICE_OUTER, or a configuration the device-driven form does not
                                   cover); appended in round 6 */
-    int32_t reserved_;
+    int32_t hess_f32;          /* 1 when the tCG Hessian products of the final rank read the fp32 copy of Q (xm_tuning_t.hess_f32); qw_bytes and
+                                  qw_stream_bytes then count the fp32 bytes */
 } xm_result_t;
 #define XM_CERT_EIG_NOT_CONVERGED 1   /* Lanczos hit its iteration cap: min_eig is only an upper bound, the certificate was NOT accepted on it */
 #define XM_CERT_EIG_EXACT 2           /* small problem (3n <= cert_dense_rows, default 384): the Krylov space of S was EXHAUSTED (3n steps, or an
@@ -336,6 +342,14 @@ int xm_dense_from_bsr3(const int64_t *rowptr, const int32_t *colidx, const doubl
 int xm_qw_dense(const double *dq, int64_t n, int o, const double *dW, double *dOut, double alpha, void *stream);
 /* the same product reading only the upper block triangle of a SYMMETRIC Q (o in 1, 3..5; allocates its scratch per call) */
 int xm_qw_dense_sym(const double *dq, int64_t n, int o, const double *dW, double *dOut, double alpha, void *stream);
+/* fp32 copy of a device matrix in the padded layout above (*dq32 allocated here, free with xm_dev_free): 3n rows of xm_dense_ld(n) floats,
+ * the SAME leading dimension in elements (row pitch 4 * xm_dense_ld(n) bytes), each element rounded to nearest (subnormals kept).
+ * XM_ERR_ARG when an element is not finite in fp32 (the copy is made either way). */
+int xm_dense_to_f32(const double *dq, int64_t n, float **dq32);
+/* out = alpha * Q32 * W with Q32 from xm_dense_to_f32: Q loaded as fp32 and accumulated in f64 (o in 1, 3..10); dW, dOut as for xm_qw_dense */
+int xm_qw_dense_f32(const float *dq32, int64_t n, int o, const double *dW, double *dOut, double alpha, void *stream);
+/* the half-traffic symmetric pair on the fp32 copy (o in 3..5; allocates its scratch per call) */
+int xm_qw_dense_sym_f32(const float *dq32, int64_t n, int o, const double *dW, double *dOut, double alpha, void *stream);
 /* same product from 3x3-block CSR (device arrays; blocks row-major 9 doubles) */
 int xm_qw_bsr3(const int64_t *d_rowptr, const int32_t *d_colidx, const double *d_blocks, int64_t n, int o,
                const double *dW, double *dOut, double alpha, void *stream);

@@ -17,6 +17,9 @@ const char *xm_bench_last_error(void);
 int xm_qw_dense_time(const double *dq, int64_t n, int o, const double *dW, double *dOut, int reps, double *ms_avg);
 /* the half-traffic symmetric product (xm_qw_dense_sym), scratch allocated once */
 int xm_qw_dense_sym_time(const double *dq, int64_t n, int o, const double *dW, double *dOut, int reps, double *ms_avg);
+/* the same two timings on the fp32 copy of xm_dense_to_f32 (xm_qw_dense_f32 / xm_qw_dense_sym_f32, o = 3..5 for the latter) */
+int xm_qw_dense_f32_time(const float *dq32, int64_t n, int o, const double *dW, double *dOut, int reps, double *ms_avg);
+int xm_qw_dense_sym_f32_time(const float *dq32, int64_t n, int o, const double *dW, double *dOut, int reps, double *ms_avg);
 /* micro-benchmark settings of the symmetric sweep: k > 0 overrides the chunk length of the plan (0 = the plan's own; set it BEFORE a context
  * or a timing call sizes its partial-result buffers); alternate = 0: xm_qw_dense_sym_time / xm_qw_dense_time walk the matrix in the same direction in every
  * launch instead of alternating it between consecutive products as the solver does; kf > 0 (with k > 0): the last quarter of the grid rows is cut

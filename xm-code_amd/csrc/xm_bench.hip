@@ -78,6 +78,29 @@ int xm_qw_dense_sym_time(const double *dq, int64_t n, int o, const double *dW, d
     return XM_OK;
     XM_CATCH
 }
+int xm_qw_dense_f32_time(const float *dq32, int64_t n, int o, const double *dW, double *dOut, int reps, double *ms_avg) {
+    XM_TRY
+    xm::CamArgs a = plain_args(n, dOut);
+    const int64_t ld = xm::dense_ld(n);
+    int it = 0;
+    const double ms = time_launches(3, reps, [&] { a.rev = g_sym_alternate ? (it++ & 1) : 0; xm::launch_qw_dense_f32(o, xm::EPI_PLAIN, dq32, nullptr, ld, dW, 1.0, a, nullptr); });
+    if (ms_avg) *ms_avg = ms;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_qw_dense_sym_f32_time(const float *dq32, int64_t n, int o, const double *dW, double *dOut, int reps, double *ms_avg) {
+    XM_TRY
+    const int64_t ld = xm::dense_ld(n);
+    xm::DevBuf<double> prow, pcol;
+    prow.alloc(xm::sym_prow_count((int)n, ld, o));
+    pcol.alloc(xm::sym_pcol_count((int)n, ld, o), false);
+    const xm::CamArgs a = plain_args(n, dOut);
+    int it = 0;
+    const double ms = time_launches(3, reps, [&] { xm::launch_qw_sym_f32(o, xm::EPI_PLAIN, dq32, nullptr, ld, dW, 1.0, a, prow.p, pcol.p, nullptr, g_sym_alternate ? (it++ & 1) : 0); });
+    if (ms_avg) *ms_avg = ms;
+    return XM_OK;
+    XM_CATCH
+}
 int xm_bench_symv_k(int k, int alternate, int kf) {
     xm::symv_bench_k(k, kf);
     g_sym_alternate = alternate;

@@ -362,6 +362,43 @@ int xm_qw_dense_sym(const double *dq, int64_t n, int o, const double *dW, double
     return XM_OK;
     XM_CATCH
 }
+int xm_dense_to_f32(const double *dq, int64_t n, float **dq32) {
+    XM_TRY
+    require_device();
+    if (!dq || !dq32 || n < 1) throw xm::Error(XM_ERR_ARG, "bad argument");
+    const int64_t ld = xm::dense_ld(n), rows = 3 * n;
+    float *out = nullptr;
+    XM_HIP_CHECK(hipMalloc((void **)&out, (size_t)rows * ld * sizeof(float)));
+    xm::DevBuf<unsigned int> bad;
+    bad.alloc(1);
+    unsigned int h = 0;
+    try {
+        xm::launch_dense_to_f32(dq, out, rows, ld, bad.p, nullptr);
+        XM_HIP_CHECK(hipMemcpy(&h, bad.p, sizeof(h), hipMemcpyDeviceToHost));
+    } catch (...) { (void)hipFree(out); throw; }
+    *dq32 = out;
+    if (h) throw xm::Error(XM_ERR_ARG, std::to_string(h) + " entries of Q are not finite in fp32");
+    return XM_OK;
+    XM_CATCH
+}
+int xm_qw_dense_f32(const float *dq32, int64_t n, int o, const double *dW, double *dOut, double alpha, void *stream) {
+    XM_TRY
+    xm::launch_qw_dense_f32(o, xm::EPI_PLAIN, dq32, nullptr, xm::dense_ld(n), dW, alpha, plain_args(n, dOut), (hipStream_t)stream);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_qw_dense_sym_f32(const float *dq32, int64_t n, int o, const double *dW, double *dOut, double alpha, void *stream) {
+    XM_TRY
+    const int64_t ld = xm::dense_ld(n);
+    if (o < 3 || o > 5) throw xm::Error(XM_ERR_ARG, "fp32 symmetric product: o in 3..5");
+    xm::DevBuf<double> prow, pcol;
+    prow.alloc(xm::sym_prow_count((int)n, ld, o));
+    pcol.alloc(xm::sym_pcol_count((int)n, ld, o), false);
+    xm::launch_qw_sym_f32(o, xm::EPI_PLAIN, dq32, nullptr, ld, dW, alpha, plain_args(n, dOut), prow.p, pcol.p, (hipStream_t)stream);
+    XM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return XM_OK;
+    XM_CATCH
+}
 int xm_qw_bsr3(const int64_t *rp, const int32_t *ci, const double *bl, int64_t n, int o, const double *dW, double *dOut, double alpha,
                void *stream) {
     XM_TRY

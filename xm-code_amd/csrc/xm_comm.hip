@@ -70,6 +70,8 @@ Settings Settings::resolve(const xm_tuning_t *t) {
     s.schur_pcg_first = z.schur_pcg_first > 0 ? z.schur_pcg_first : 0;
     if (z.schur_pcg_hess_digits != 0 && (z.schur_pcg_hess_digits < 6 || z.schur_pcg_hess_digits > 13)) throw Error(XM_ERR_ARG, "xm_tuning_t.schur_pcg_hess_digits must be 0 or 6..13");
     s.schur_pcg_hess_digits = z.schur_pcg_hess_digits;
+    if (z.hess_f32 < 0 || z.hess_f32 > 1) throw Error(XM_ERR_ARG, "xm_tuning_t.hess_f32 must be 0 or 1");
+    s.hess_f32 = z.hess_f32;
     s.debug_drop_finalize = z.debug_drop_finalize > 0 ? z.debug_drop_finalize : -1;
     s.debug_peer_mute = z.debug_peer_mute;
     return s;

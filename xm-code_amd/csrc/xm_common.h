@@ -232,6 +232,14 @@ void symv_plan_get(int nloc, int64_t ld, int out[4]);   // K, Kf, ysplit, nchunk
 void launch_qw_sym(int o, int epi, const double *Q, int64_t ld, const double *W, double alpha, const CamArgs &a, double *Prow,
                    double *Pcol, hipStream_t st, int rev = 0);   // rev: sweep direction, alternated by the caller between consecutive products
 void launch_asym(const double *Q, int64_t ld, int64_t m, double *out, int grid, hipStream_t st);
+// fp32 copy of a dense Q for the Hessian products of the truncated CG (xm_tuning_t.hess_f32): same shape (rows x ld, ld a multiple of 4), round to
+// nearest; *bad (device) receives the number of elements that are not finite in fp32
+void launch_dense_to_f32(const double *src, float *dst, int64_t rows, int64_t ld, unsigned int *bad, hipStream_t st);
+// the products from it: Q loaded as fp32, accumulated in f64.  Epilogues: plain, Hessian, and EPI_AUTO, whose gradient role reads Qd (f64)
+void launch_qw_dense_f32(int o, int epi, const float *Qf, const double *Qd, int64_t ld, const double *W, double alpha, const CamArgs &a, hipStream_t st);
+void launch_qw_sym_f32(int o, int epi, const float *Qf, const double *Qd, int64_t ld, const double *W, double alpha, const CamArgs &a, double *Prow,
+                       double *Pcol, hipStream_t st, int rev = 0);   // o = 3..5; Prow / Pcol as for launch_qw_sym
+
 // exact symmetry check of a row-partitioned matrix: this strip's (rows row0 .. row0 + nrows of the m x m matrix) share of a sum modulo 2^64
 // that vanishes over all strips iff the matrix is symmetric (xm_kernels.hip: symhash_kernel); out: 2 * grid words
 void launch_symhash(const double *Q, int64_t ld, int64_t row0, int64_t nrows, int64_t m, unsigned long long *out, int grid, hipStream_t st);

@@ -2974,4 +2974,449 @@ void launch_edge_residual(int64_t ne, const int32_t *ei, const int32_t *ej, cons
     check_launch("edge_residual");
 }
 
+// ----------------------------------------------------------------------------------------------------------------
+// fp32 STORAGE of a dense Q for the Hessian products of the truncated CG (xm_tuning_t.hess_f32)
+// ----------------------------------------------------------------------------------------------------------------
+// The copy keeps the f64 layout's shape: 3 nloc rows of ld = dense_ld(n) floats (row pitch 4 ld bytes, a multiple of 512), padding zero.
+// Both products load Q as fp32, widen it in registers and accumulate in f64; W, the partial sums and the fused epilogues stay f64, so the
+// only approximation is the rounding of each element of Q to fp32 (exactly symmetric when Q is).
+// Geometry, chosen for the fp32 byte count ("fp32 Hessian products"):
+//   load width   16 bytes (global_load_dwordx4) as in the f64 loops: a lane now covers FOUR columns per row instead of two, so a wavefront
+//                request spans 256 columns (1 KB of one row);
+//   general      one wavefront per camera as in qw_dense_kernel; NSUB = 2 sub-tiles of 256 columns per W tile for o <= 5 (six 16-byte
+//                requests in flight per lane, like the f64 loop's two sub-tiles of 128) -- a W tile of 512 columns is 24..40 KB of LDS
+//                double-buffered; o >= 6 keeps one sub-tile so that the W tile stays <= 44 KB;
+//   symmetric    the vertical sweep of qw_symv_kernel on the SAME strips of 256 columns (a lane: one float4 per row), so its partial sums
+//                have the f64 layout and symv_reduce_kernel / symv_plan serve unchanged: 6 requests per step instead of 12;
+//   cache policy the rule of the f64 stream (qw_resident_bytes) applied to the fp32 bytes: the Venice-size copy (114 MB, 57 MB triangle)
+//                stays cacheable as a whole; a copy beyond 310 MB keeps a 220 MB prefix resident and streams the rest non-temporally.
+// EPI_AUTO (device-driven outer iteration): one launch serves the Hessian role (PH_TCG: fp32 copy) and the gradient role at the candidate
+// point (PH_CAND: f64 Q, never approximated); the phase is read before the first Q request, and the launch streams the matrix its role needs.
+__device__ __forceinline__ float4 nt_load16f(const float4 *p) {
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    const f4v v = __builtin_nontemporal_load(reinterpret_cast<const f4v *>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+// four consecutive columns of one row of Q as loaded: one float4 (fp32 copy) or two double2 (f64 matrix, gradient role of EPI_AUTO)
+template <typename T> struct QFrag4;
+template <> struct QFrag4<float> {
+    float4 v;
+    template <bool NT> __device__ __forceinline__ void load(const float *p) {
+        v = NT ? nt_load16f(reinterpret_cast<const float4 *>(p)) : *reinterpret_cast<const float4 *>(p);
+    }
+    __device__ __forceinline__ double at(int i) const { return (double)(i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w); }
+};
+template <> struct QFrag4<double> {
+    double2 a, b;
+    template <bool NT> __device__ __forceinline__ void load(const double *p) {
+        const double2 *q = reinterpret_cast<const double2 *>(p);
+        a = NT ? nt_load16(q) : q[0];
+        b = NT ? nt_load16(q + 1) : q[1];
+    }
+    __device__ __forceinline__ double at(int i) const { return i == 0 ? a.x : i == 1 ? a.y : i == 2 ? b.x : b.y; }
+};
+
+// f64 -> fp32, round to nearest even, subnormals kept (the translation unit does not flush fp32 denormals); counts elements that are not
+// finite in fp32 (NaN, +-inf, or finite f64 beyond the fp32 range) into *bad.  n4: groups of four elements.
+__global__ __launch_bounds__(256) void dense_to_f32_kernel(const double *__restrict__ src, float *__restrict__ dst, size_t n4, unsigned int *bad) {
+    unsigned int nbad = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const double2 a = reinterpret_cast<const double2 *>(src)[2 * i], b = reinterpret_cast<const double2 *>(src)[2 * i + 1];
+        const float4 f = make_float4((float)a.x, (float)a.y, (float)b.x, (float)b.y);
+        nbad += !isfinite(f.x) + !isfinite(f.y) + !isfinite(f.z) + !isfinite(f.w);
+        reinterpret_cast<float4 *>(dst)[i] = f;
+    }
+    if (nbad) atomicAdd(bad, nbad);
+}
+
+constexpr int f32_nsub(int o) { return o <= 5 ? 2 : 1; }
+template <int O, int EPI>
+__global__ __launch_bounds__(256) void qw_dense_f32_kernel(const float *__restrict__ Qf, const double *__restrict__ Qd, int64_t ld,
+                                                            const double *__restrict__ W, double alpha, CamArgs a) {
+    constexpr int OP = pitch_of(O);
+    constexpr int NSUB = f32_nsub(O);
+    constexpr int TILE = NSUB * 256;                 // columns per tile (a lane: 4 columns per sub-tile)
+    constexpr int TILE2 = TILE * OP / 2;
+    constexpr int NST = (TILE2 + 255) / 256;
+    int role = EPI;
+    __shared__ __attribute__((aligned(16))) double wt[2][TILE * OP];
+    __shared__ double red[kQwWaves][3];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int cam = blockIdx.x * kQwWaves + wave;
+    const bool active = cam < a.nloc;
+    const bool nt = (int)(blockIdx.x * kQwWaves) >= a.nt_cam0;
+    const size_t row0 = (size_t)(active ? cam : 0) * 3 * (size_t)ld;
+    const int ntiles = (int)((ld + TILE - 1) / TILE);
+    auto tile_at = [&](int i) -> int { return a.rev ? ntiles - 1 - i : i; };
+
+    double acc[3][O];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int k = 0; k < O; ++k) acc[r][k] = 0.0;
+    EpiOps eops;
+    double2 ws[NST];
+    auto load_w = [&](int t) {
+        const int64_t c0 = (int64_t)t * TILE;
+        const int64_t cols = (ld - c0 < TILE) ? (ld - c0) : TILE;   // W beyond ld is zero in LDS: the clamped Q loads below meet zeros
+        const int n2 = (int)(cols * OP / 2);
+        const double2 *src = reinterpret_cast<const double2 *>(W + (size_t)c0 * OP);
+#pragma unroll
+        for (int j = 0; j < NST; ++j) {
+            const int idx = threadIdx.x + j * 256;
+            ws[j] = (idx < n2) ? src[idx] : make_double2(0.0, 0.0);
+        }
+    };
+    auto store_w = [&](int buf) {
+        double2 *dst = reinterpret_cast<double2 *>(wt[buf]);
+#pragma unroll
+        for (int j = 0; j < NST; ++j) {
+            const int idx = threadIdx.x + j * 256;
+            if (idx < TILE2) dst[idx] = ws[j];
+        }
+    };
+    auto stream = [&](const auto *Q, auto ntag) -> bool {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(Q)>>;
+        constexpr bool NT = decltype(ntag)::value;
+        QFrag4<T> qn[NSUB][3];
+        auto load_q = [&](int t) {
+#pragma unroll
+            for (int u = 0; u < NSUB; ++u) {
+                int64_t c = (int64_t)t * TILE + u * 256 + 4 * lane;
+                c = (c < ld) ? c : ld - 4;   // ld is a multiple of 128: the last sub-tile may be half; its absent lanes re-read a valid fragment
+#pragma unroll
+                for (int r = 0; r < 3; ++r) qn[u][r].template load<NT>(Q + row0 + (size_t)r * ld + c);
+            }
+        };
+        load_q(tile_at(0));
+        if (EPI == EPI_HESS) {
+            if (a.scal->status != 0) return false;
+        }
+        store_w(0);
+        __syncthreads();
+        for (int t = 0; t < ntiles; ++t) {
+            QFrag4<T> q[NSUB][3];
+#pragma unroll
+            for (int u = 0; u < NSUB; ++u)
+#pragma unroll
+                for (int r = 0; r < 3; ++r) q[u][r] = qn[u][r];
+            const bool more = (t + 1 < ntiles);
+            if (more) {
+                load_q(tile_at(t + 1));
+                load_w(tile_at(t + 1));
+            } else if (EPI != EPI_AUTO) {
+                epi_prefetch<O, EPI>(eops, cam, lane, active, a, (int)EPI);
+            }
+            const double2 *wbase = reinterpret_cast<const double2 *>(wt[t & 1]);
+#pragma unroll
+            for (int u = 0; u < NSUB; ++u) {
+                const double2 *wp = wbase + (size_t)(u * 64 + lane) * 2 * OP;   // the lane's four columns: 4 OP contiguous doubles
+                double wv[4 * OP];
+#pragma unroll
+                for (int j = 0; j < 2 * OP; ++j) {
+                    const double2 tt = wp[j];
+                    wv[2 * j] = tt.x;
+                    wv[2 * j + 1] = tt.y;
+                }
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const double q0 = q[u][r].at(0), q1 = q[u][r].at(1), q2 = q[u][r].at(2), q3 = q[u][r].at(3);
+#pragma unroll
+                    for (int k = 0; k < O; ++k) acc[r][k] += (q0 * wv[k] + q1 * wv[OP + k]) + (q2 * wv[2 * OP + k] + q3 * wv[3 * OP + k]);
+                }
+            }
+            if (more) store_w((t + 1) & 1);
+            __syncthreads();
+        }
+        return true;
+    };
+    load_w(tile_at(0));
+    bool alive;
+    if constexpr (EPI == EPI_AUTO) {
+        const int ph = a.scal->phase;
+        if (ph >= PH_STOP) return;
+        role = (ph == PH_CAND) ? EPI_GRAD : EPI_HESS;
+        if (role == EPI_GRAD) alive = nt ? stream(Qd, std::true_type{}) : stream(Qd, std::false_type{});
+        else alive = nt ? stream(Qf, std::true_type{}) : stream(Qf, std::false_type{});
+    } else {
+        alive = nt ? stream(Qf, std::true_type{}) : stream(Qf, std::false_type{});
+    }
+    if (!alive) return;
+    if (EPI == EPI_AUTO) epi_prefetch<O, EPI>(eops, cam, lane, active, a, role);
+    qw_finish<O, EPI, 64, kQwWaves>(cam, lane, wave, active, acc, alpha, a, eops, red, (EPI == EPI_AUTO) ? role : (int)EPI);
+}
+
+// Symmetric half-traffic sweep from the fp32 copy: qw_symv_kernel's strips, chunks, folded grid and partial-sum layout (Prow / Pcol, read by
+// symv_reduce_kernel), with a lane on four adjacent columns c0 + 4 lane .. + 3 of its strip -- column pair h (0, 1) = columns c0 + 4 lane + 2 h,
+// + 1 -- and one float4 per row and step.  A strip that ends after its first 128 columns: lanes 32..63 re-read the first half and meet
+// w_col = 0; their column sums are not written.  EPI_AUTO (by_phase): PH_TCG streams the fp32 copy, PH_CAND the f64 matrix (two double2 per row).
+template <int O, bool AUTO>
+__global__ __launch_bounds__(256) void qw_symv_f32_kernel(const float *__restrict__ Qf, const double *__restrict__ Qd, int64_t ld, const double *__restrict__ W,
+                                                           int nloc, int Kc, int Kf, int ysplit, int nt_step0, const TcgScal *__restrict__ scal,
+                                                           double *__restrict__ Prow, double *__restrict__ Pcol, int rev) {
+    constexpr int OP = pitch_of(O), V = 6 * O;
+    __shared__ __attribute__((aligned(16))) double lds[4][V * 64];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nsteps = (nloc + 1) >> 1, nrows = 3 * nloc;
+    const int nstrips = (int)((ld + kSvStrip - 1) / kSvStrip);
+    const int K = ((int)blockIdx.y >= ysplit) ? Kf : Kc;
+    int s = blockIdx.y, sc = blockIdx.x;
+    {
+        int jA = (int)(((int64_t)s * kSvStrip + kSvStrip + 5) / 6);
+        if (jA > nsteps) jA = nsteps;
+        const int nA = (jA + 4 * K - 1) / (4 * K);
+        if (sc >= nA) {
+            if (nstrips - 1 - s == s) return;
+            s = nstrips - 1 - s; sc -= nA;
+        }
+    }
+    const int64_t c0 = (int64_t)s * kSvStrip;
+    int jend = (int)((c0 + kSvStrip + 5) / 6);
+    if (jend > nsteps) jend = nsteps;
+    if (sc * 4 * K >= jend) return;
+    const int jb = (sc * 4 + wave) * K;
+    const int je = (jb + K < jend) ? jb + K : jend;
+    const int jfull = (int)(c0 / 6);
+    const bool lane_ok = (c0 + 4 * lane) < ld;                   // false only in the absent half of a half strip
+    const int64_t R = (int64_t)6 * nsteps;
+    double *L = lds[wave];
+    const int64_t cA = lane_ok ? c0 + 4 * lane : c0 + 4 * (lane - 32);
+    const int64_t wlim = (int64_t)nrows * OP - 1;
+
+    double wc[2][2][O], ca[2][2][O];
+    auto sweep = [&](const auto *Q, auto ntag) __attribute__((always_inline)) -> bool {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(Q)>>;
+        constexpr bool NT = decltype(ntag)::value;
+        auto load_q = [&](int j, QFrag4<T> (&q)[6], double &wl) __attribute__((always_inline)) {
+            const int64_t r0 = (int64_t)6 * j;
+            {
+                const int64_t wi = r0 * OP + (lane < 6 * OP ? lane : 0);
+                wl = W[wi < wlim ? wi : wlim];
+            }
+#pragma unroll
+            for (int r = 0; r < 6; ++r) {
+                const int64_t rr = (r0 + r < nrows) ? r0 + r : nrows - 1;
+                q[r].template load<NT>(Q + (size_t)rr * (size_t)ld + cA);
+            }
+        };
+        auto step = [&](int j, const QFrag4<T> (&q)[6], const double wl, auto masked) __attribute__((always_inline)) {
+            constexpr bool MASK = decltype(masked)::value;
+            const int64_t r0 = (int64_t)6 * j;
+            double mr[2] = {1.0, 1.0}, mc[2] = {1.0, 1.0};
+            if constexpr (MASK) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {   // both columns of a pair fall on the same side (all bounds are even)
+                    mr[h] = (cA + 2 * h >= r0) ? 1.0 : 0.0;
+                    mc[h] = (cA + 2 * h >= r0 + 6) ? 1.0 : 0.0;
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 6; ++r) {
+                double wr[O];
+                const bool ok = r0 + r < nrows;
+#pragma unroll
+                for (int k = 0; k < O; ++k) {
+                    const int lo = __builtin_amdgcn_readlane(__double2loint(wl), r * OP + k), hi = __builtin_amdgcn_readlane(__double2hiint(wl), r * OP + k);
+                    wr[k] = ok ? __hiloint2double(hi, lo) : 0.0;
+                }
+                double qr[2][2], qc[2][2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const double x = q[r].at(2 * h + e);
+                        qr[h][e] = MASK ? x * mr[h] : x;
+                        qc[h][e] = MASK ? x * mc[h] : x;
+                    }
+#pragma unroll
+                for (int k = 0; k < O; ++k) {
+                    double t = qr[0][0] * wc[0][0][k];
+                    t = fma(qr[0][1], wc[0][1][k], t);
+                    t = fma(qr[1][0], wc[1][0][k], t);
+                    t = fma(qr[1][1], wc[1][1][k], t);
+                    L[(r * O + k) * 64 + lane] = t;
+#pragma unroll
+                    for (int h = 0; h < 2; ++h)
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) ca[h][e][k] = fma(qc[h][e], wr[k], ca[h][e][k]);
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const int g = lane >> 4, jl = lane & 15;
+#pragma unroll
+            for (int v0 = 0; v0 < V; v0 += 4) {
+                const int v = v0 + g;
+                double t = 0.0;
+                if (v < V) {
+                    const double2 x = *reinterpret_cast<const double2 *>(L + v * 64 + 4 * jl), y = *reinterpret_cast<const double2 *>(L + v * 64 + 4 * jl + 2);
+                    t = (x.x + x.y) + (y.x + y.y);
+                }
+                t = group_sum<16>(t);
+                if (jl == 0 && v < V) Prow[((size_t)s * (size_t)R + (size_t)r0) * O + v] = t;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        };
+        auto run = [&](int j, const QFrag4<T> (&q)[6], const double wl) __attribute__((always_inline)) {
+            if (j < jfull) step(j, q, wl, std::false_type{});
+            else step(j, q, wl, std::true_type{});
+        };
+        QFrag4<T> qA[6], qB[6];
+        double wA = 0.0, wB = 0.0;
+        if (jb < je) load_q(rev ? je - 1 : jb, qA, wA);
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+#pragma unroll
+                for (int k = 0; k < O; ++k) {
+                    const double t = W[(size_t)(cA + 2 * h + e) * OP + k];
+                    wc[h][e][k] = lane_ok ? t : 0.0;
+                    ca[h][e][k] = 0.0;
+                }
+        if (!AUTO && scal != nullptr) {
+            if (scal->status != 0) return false;
+        }
+        auto at = [&](int i) __attribute__((always_inline)) { return rev ? je - 1 - i : jb + i; };
+        const int cnt = je - jb;
+        if (cnt > 0) {
+            int i = 0;
+            while (i + 2 < cnt) {
+                load_q(at(i + 1), qB, wB);
+                run(at(i), qA, wA);
+                load_q(at(i + 2), qA, wA);
+                run(at(i + 1), qB, wB);
+                i += 2;
+            }
+            if (i + 1 < cnt) {
+                load_q(at(i + 1), qB, wB);
+                run(at(i), qA, wA);
+                run(at(i + 1), qB, wB);
+            } else {
+                run(at(i), qA, wA);
+            }
+        }
+        return true;
+    };
+    bool alive;
+    const bool nt = jb >= nt_step0;
+    if constexpr (AUTO) {
+        const int ph = scal->phase;
+        if (ph >= PH_STOP) return;
+        if (ph == PH_CAND) alive = nt ? sweep(Qd, std::true_type{}) : sweep(Qd, std::false_type{});
+        else alive = nt ? sweep(Qf, std::true_type{}) : sweep(Qf, std::false_type{});
+    } else {
+        alive = nt ? sweep(Qf, std::true_type{}) : sweep(Qf, std::false_type{});
+    }
+    if (!alive) return;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+#pragma unroll
+            for (int k = 0; k < O; ++k) L[((h * 2 + e) * O + k) * 64 + lane] = ca[h][e][k];
+    __syncthreads();
+    if (wave < 2 && lane_ok) {   // wavefront h writes the column pair h of every lane
+        double *pc = Pcol + ((size_t)sc * (size_t)ld + (size_t)(cA + 2 * wave)) * O;
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+#pragma unroll
+            for (int k = 0; k < O; ++k) {
+                const int idx = ((wave * 2 + e) * O + k) * 64 + lane;
+                pc[e * O + k] = ((lds[0][idx] + lds[1][idx]) + lds[2][idx]) + lds[3][idx];
+            }
+    }
+}
+
+// bad: device counter of elements that are not finite in fp32, zeroed here; the caller reads it after the stream has run
+void launch_dense_to_f32(const double *src, float *dst, int64_t rows, int64_t ld, unsigned int *bad, hipStream_t st) {
+    if (ld % 4 != 0) throw Error(-2, "fp32 copy: leading dimension must be a multiple of 4");
+    const size_t n4 = (size_t)rows * (size_t)ld / 4;
+    XM_HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(unsigned int), st));
+    if (n4 == 0) return;
+    const int grid = (int)std::min<size_t>(4096, (n4 + 255) / 256);
+    hipLaunchKernelGGL(dense_to_f32_kernel, dim3(grid), dim3(256), 0, st, src, dst, n4, bad);
+    check_launch("dense_to_f32");
+}
+
+template <int O>
+static void qw_dense_f32_epi(int epi, const float *Qf, const double *Qd, int64_t ld, const double *W, double alpha, const CamArgs &a0, hipStream_t st) {
+    const dim3 g(qw_grid(a0.nloc)), b(256);
+    CamArgs a = a0;
+    {
+        const size_t row3 = (size_t)3 * (size_t)ld * sizeof(float);
+        a.nt_cam0 = (int)std::min<int64_t>(a.nloc, qw_resident_bytes((size_t)a.nloc * row3) / (int64_t)row3);
+    }
+    switch (epi) {
+        case EPI_PLAIN: hipLaunchKernelGGL((qw_dense_f32_kernel<O, EPI_PLAIN>), g, b, 0, st, Qf, Qd, ld, W, alpha, a); break;
+        case EPI_HESS: hipLaunchKernelGGL((qw_dense_f32_kernel<O, EPI_HESS>), g, b, 0, st, Qf, Qd, ld, W, alpha, a); break;
+        case EPI_AUTO:
+            if constexpr (O >= 3) {
+                if (!Qd) throw Error(-2, "fp32 product in the device-driven role needs the f64 matrix too");
+                hipLaunchKernelGGL((qw_dense_f32_kernel<O, EPI_AUTO>), g, b, 0, st, Qf, Qd, ld, W, alpha, a);
+                break;
+            }
+            throw Error(-2, "bad epilogue");
+        default: throw Error(-2, "fp32 dense product: plain, Hessian or device-driven epilogue only");
+    }
+}
+void launch_qw_dense_f32(int o, int epi, const float *Qf, const double *Qd, int64_t ld, const double *W, double alpha, const CamArgs &a, hipStream_t st) {
+    if (a.nloc <= 0) return;
+    XM_DISPATCH_O(o, (qw_dense_f32_epi<O_>(epi, Qf, Qd, ld, W, alpha, a, st)));
+    check_launch("qw_dense_f32");
+}
+template <int O>
+static void qw_symv_f32_epi(int epi, const float *Qf, const double *Qd, int64_t ld, const double *W, double alpha, const CamArgs &a, double *Prow,
+                            double *Pcol, hipStream_t st, int rev) {
+    const SymvPlan pl = symv_plan(a.nloc, ld);
+    const int nstrips = (int)((ld + kSvStrip - 1) / kSvStrip);
+    const int rK = 4 * pl.K, rKf = 4 * pl.Kf, ys = pl.ysplit;
+    const dim3 gs(pl.gx, pl.gy), g(qw_grid(a.nloc)), b(256);
+    // load policy: the f64 rule on the fp32 triangle's bytes (the sweep of the candidate's gradient under EPI_AUTO reads the f64 matrix with
+    // the f64 rule's first non-temporal step)
+    int nt0;
+    {
+        const double m = 3.0 * a.nloc, tri = 4.0 * m * (m + 6.0) / 2.0;
+        const int64_t res = qw_resident_bytes((size_t)tri);
+        const int nsteps = (a.nloc + 1) / 2;
+        if ((double)res >= tri) nt0 = nsteps + 1;
+        else {
+            const double r = m - std::sqrt(std::max(0.0, m * m - 2.0 * (double)res / 4.0));
+            nt0 = (int)std::min<double>(nsteps + 1, std::max(0.0, r / 6.0));
+        }
+    }
+    switch (epi) {
+        case EPI_PLAIN:
+            hipLaunchKernelGGL((qw_symv_f32_kernel<O, false>), gs, b, 0, st, Qf, Qd, ld, W, a.nloc, pl.K, pl.Kf, ys, nt0, (const TcgScal *)nullptr, Prow, Pcol, rev);
+            hipLaunchKernelGGL((symv_reduce_kernel<O, EPI_PLAIN>), g, b, 0, st, Prow, Pcol, ld, nstrips, rK, rKf, ys, alpha, a);
+            break;
+        case EPI_HESS:
+            hipLaunchKernelGGL((qw_symv_f32_kernel<O, false>), gs, b, 0, st, Qf, Qd, ld, W, a.nloc, pl.K, pl.Kf, ys, nt0, a.scal, Prow, Pcol, rev);
+            hipLaunchKernelGGL((symv_reduce_kernel<O, EPI_HESS>), g, b, 0, st, Prow, Pcol, ld, nstrips, rK, rKf, ys, alpha, a);
+            break;
+        case EPI_AUTO:
+            if constexpr (O >= 3) {
+                if (!Qd) throw Error(-2, "fp32 product in the device-driven role needs the f64 matrix too");
+                const int nt64 = symv_nt_step0(a.nloc, ld);
+                hipLaunchKernelGGL((qw_symv_f32_kernel<O, true>), gs, b, 0, st, Qf, Qd, ld, W, a.nloc, pl.K, pl.Kf, ys, std::min(nt0, nt64), a.scal, Prow, Pcol, rev);
+                hipLaunchKernelGGL((symv_reduce_kernel<O, EPI_AUTO>), g, b, 0, st, Prow, Pcol, ld, nstrips, rK, rKf, ys, alpha, a);
+                break;
+            }
+            throw Error(-2, "bad epilogue");
+        default: throw Error(-2, "fp32 symmetric product: plain, Hessian or device-driven epilogue only");
+    }
+}
+void launch_qw_sym_f32(int o, int epi, const float *Qf, const double *Qd, int64_t ld, const double *W, double alpha, const CamArgs &a, double *Prow,
+                       double *Pcol, hipStream_t st, int rev) {
+    if (a.nloc <= 0) return;
+    switch (o) {
+        case 3: qw_symv_f32_epi<3>(epi, Qf, Qd, ld, W, alpha, a, Prow, Pcol, st, rev & 1); break;
+        case 4: qw_symv_f32_epi<4>(epi, Qf, Qd, ld, W, alpha, a, Prow, Pcol, st, rev & 1); break;
+        case 5: qw_symv_f32_epi<5>(epi, Qf, Qd, ld, W, alpha, a, Prow, Pcol, st, rev & 1); break;
+        default: throw Error(-2, "fp32 symmetric product is instantiated for o = 3..5");
+    }
+    check_launch("qw_symv_f32");
+}
+
 }  // namespace xm

@@ -4,6 +4,7 @@
 //   XM.solve_rank3(dataset_path, max_rank, tol, lam, max_time)    -> None
 // Additive (not in the reference): the same solve on arrays, without the Q.bin / R.bin round trip
 //   XM.solve_array(Q, max_rank, tol, lam, max_time, mode=0, s_ini=None, flags=0, R_ini=None)      -> (R, s, info)
+//                  (also hess_f32=0: 1 = the truncated CG's Hessian products read an fp32 copy of Q, xm_tuning_t.hess_f32)
 //   XM.solve_bsr(rowptr, colidx, blocks, max_rank, tol, lam, max_time, mode=0, s_ini=None, flags=0) -> (R, s, info)
 // both take n_gpus=1, gpu_map=0, retraction=0: the single-process row partition over several GPUs (include/xm_amd.h) and the polar
 // retraction; the file functions take the GPU count from the environment (XM_GPUS=8 python 1_test_solve.py).
@@ -92,15 +93,20 @@ static py::tuple solve_problem(xm_problem_t &prob, unsigned int max_rank, double
     info["min_eig"] = res.min_eig; info["gap"] = res.gap; info["tcg_iters"] = res.tcg_iters; info["outer_iters"] = res.outer_iters;
     info["qw_products"] = res.qw_products; info["lanczos_iters"] = res.lanczos_iters; info["seconds"] = res.seconds;
     info["cert_flags"] = res.cert_flags; info["eig_residual"] = res.eig_residual; info["n_gpus"] = res.n_gpus; info["exchange"] = res.exchange;
+    info["hess_f32"] = res.hess_f32; info["sym_product"] = res.sym_product;
     return py::make_tuple(Rout, sout, info);
 }
 static py::tuple solve_array(darr Q, unsigned int max_rank, double tol, double lam, double max_time, int mode, py::object s_ini,
-                             unsigned int flags, py::object R_ini, int n_gpus, int gpu_map, int retraction) {
+                             unsigned int flags, py::object R_ini, int n_gpus, int gpu_map, int retraction, int hess_f32) {
     if (Q.ndim() != 2 || Q.shape(0) != Q.shape(1) || Q.shape(0) % 3 != 0 || Q.shape(0) < 3)
         throw std::invalid_argument("Q must be 3n x 3n");
     xm_problem_t prob;
     std::memset(&prob, 0, sizeof(prob));
     prob.n = Q.shape(0) / 3; prob.storage = XM_STORAGE_DENSE; prob.q = Q.data(); prob.ldq = Q.shape(0);
+    xm_tuning_t tun;
+    std::memset(&tun, 0, sizeof(tun));
+    tun.hess_f32 = hess_f32;
+    if (hess_f32) prob.tuning = &tun;
     return solve_problem(prob, max_rank, tol, lam, max_time, mode, s_ini, flags, R_ini, n_gpus, gpu_map, retraction);
 }
 static py::tuple solve_bsr(py::array_t<int64_t, py::array::c_style | py::array::forcecast> rowptr,
@@ -124,7 +130,7 @@ PYBIND11_MODULE(XM, m) {
     m.def("solve_rank3", &solve_rank3, "XM main function for rank 3 only");
     m.def("solve_array", &solve_array, "in-memory solve of a dense symmetric Q -> (R, s, info)", py::arg("Q"), py::arg("max_rank"),
           py::arg("tol"), py::arg("lam"), py::arg("max_time"), py::arg("mode") = 0, py::arg("s_ini") = py::none(), py::arg("flags") = 0u,
-          py::arg("R_ini") = py::none(), py::arg("n_gpus") = 1, py::arg("gpu_map") = 0, py::arg("retraction") = 0);
+          py::arg("R_ini") = py::none(), py::arg("n_gpus") = 1, py::arg("gpu_map") = 0, py::arg("retraction") = 0, py::arg("hess_f32") = 0);
     m.def("solve_bsr", &solve_bsr, "in-memory solve of a 3x3-block CSR Q -> (R, s, info)", py::arg("rowptr"), py::arg("colidx"),
           py::arg("blocks"), py::arg("max_rank"), py::arg("tol"), py::arg("lam"), py::arg("max_time"), py::arg("mode") = 0,
           py::arg("s_ini") = py::none(), py::arg("flags") = 0u, py::arg("R_ini") = py::none(), py::arg("n_gpus") = 1, py::arg("gpu_map") = 0,

@@ -43,6 +43,7 @@ struct Settings {
     int schur_pcg_first = 0, schur_pcg_hess_digits = 0;   // CG form of the matrix-free storage (xm_schur.h: SchurSettings)
     int schur_solver = 0;                 // 0 by size | 1 dense inverse of the reduced camera Laplacian | 2 preconditioned CG inside the product
     int64_t schur_dense_max = 20000;
+    int hess_f32 = 0;                     // 1: the tCG Hessian products of a dense single-rank context read an fp32 copy of Q (dQ32_)
     static Settings resolve(const xm_tuning_t *t);
 };
 
@@ -216,6 +217,8 @@ private:
     int storage_ = XM_STORAGE_DENSE;
     double *dQ_ = nullptr; // dense: 3*nloc rows x ld, row-major
     bool ownQ_ = false;
+    float *dQ32_ = nullptr; // xm_tuning_t.hess_f32: fp32 copy of dQ_ (same shape), read by the Hessian products of the truncated CG only
+    void refresh_q32();     // (re)makes dQ32_ from dQ_: XM_ERR_ARG when an entry is not finite in fp32
     DevBuf<double> Afull_;   // multi-rank tCG: replicated image of the residual (cg_step_kernel)
     DevBuf<int64_t> rowptr_;
     DevBuf<int32_t> colidx_;

@@ -100,6 +100,8 @@ void Context::release_raw() {
     ev_pool_.clear();
     if (ownQ_ && dQ_) (void)hipFree(dQ_);
     dQ_ = nullptr;
+    if (dQ32_) (void)hipFree(dQ32_);
+    dQ32_ = nullptr;
     if (hstat_) (void)hipHostFree(hstat_);
     hstat_ = nullptr;
     if (hpin_) (void)hipHostFree(hpin_);
@@ -225,6 +227,10 @@ void Context::init(const xm_problem_t &prob_in) {
     if (3 * prob.n > 2000000000LL) throw Error(XM_ERR_ARG, "n too large");
     n_ = prob.n;
     storage_ = prob.storage;
+    if (cfg_.hess_f32) {   // (before anything is allocated)
+        if (storage_ != XM_STORAGE_DENSE) throw Error(XM_ERR_ARG, "xm_tuning_t.hess_f32 needs XM_STORAGE_DENSE (storage " + std::to_string(storage_) + ")");
+        if (world > 1 || comm_->active()) throw Error(XM_ERR_ARG, "xm_tuning_t.hess_f32 needs a single-rank context (no communicator, n_gpus <= 1)");
+    }
     XM_HIP_CHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
 
     // view-graph storage: the edge list becomes 3x3-block CSR on the host (and is attached for the XM^2 calls further down)
@@ -381,6 +387,7 @@ void Context::init(const xm_problem_t &prob_in) {
             sym_ok_ = force ? (da <= 1e-9 * mx) : (da == 0.0);
         }
     }
+    if (cfg_.hess_f32) refresh_q32();
     // Several ranks: every rank streams half of its row strip through a cyclic half window (xm_symw.h) -- the upper triangle cut into row
     // strips would leave rank 0 with almost its whole strip.  Whether Q is symmetric cannot be seen from one strip.  The policy is the
     // single-GPU one: automatic (sym = 0) only for an EXACTLY symmetric matrix -- an order-independent checksum modulo 2^64 over the
@@ -644,7 +651,12 @@ void Context::product(int epi, int o, double alpha, const CamArgs &a) {
         }
         flush_gather();
     }
-    if (storage_ == XM_STORAGE_DENSE) {
+    if (storage_ == XM_STORAGE_DENSE && dQ32_ && o == o_ && (epi == EPI_HESS || epi == EPI_AUTO)) {
+        // xm_tuning_t.hess_f32: the Hessian products of the tCG read the fp32 copy -- the symmetric pair wherever the f64 path takes it
+        // (EPI_AUTO: the same launch computes the candidate's gradient from the f64 Q when the device-driven outer iteration asks for it)
+        if (sym_ok_ && o >= 3 && o <= sym_max_o_ && Pcol_.p) launch_qw_sym_f32(o, epi, dQ32_, dQ_, ld_, W_.p, alpha, a, Prow_.p, Pcol_.p, st_, sym_rev_);
+        else { CamArgs ar = a; ar.rev = sym_rev_; launch_qw_dense_f32(o, epi, dQ32_, dQ_, ld_, W_.p, alpha, ar, st_); }
+    } else if (storage_ == XM_STORAGE_DENSE) {
         if (symw_ && o == o_ && o >= 3 && o <= sym_max_o_ && epi != EPI_CERT) product_symw(epi, o, alpha, a);
         else if (sym_ok_ && o == o_ && o >= 3 && o <= sym_max_o_ && epi != EPI_CERT && Pcol_.p) launch_qw_sym(o, epi, dQ_, ld_, W_.p, alpha, a, Prow_.p, Pcol_.p, st_, sym_rev_);
         else { CamArgs ar = a; ar.rev = sym_rev_; launch_qw_dense(o, epi, dQ_, ld_, W_.p, alpha, ar, st_); }
@@ -1807,6 +1819,19 @@ bool Context::schur_info(int64_t out[3], double *relres) const {
     return true;
 }
 
+// fp32 copy of the dense Q for the tCG's Hessian products, made on the device (nothing crosses the host link, also for a q_on_device context)
+void Context::refresh_q32() {
+    const size_t rows = (size_t)3 * nloc_;
+    if (!dQ32_) XM_HIP_CHECK(hipMalloc((void **)&dQ32_, rows * (size_t)ld_ * sizeof(float)));
+    DevBuf<unsigned int> bad;
+    bad.alloc(1);
+    launch_dense_to_f32(dQ_, dQ32_, (int64_t)rows, ld_, bad.p, st_);
+    unsigned int h = 0;
+    XM_HIP_CHECK(hipMemcpyAsync(&h, bad.p, sizeof(h), hipMemcpyDeviceToHost, st_));
+    XM_HIP_CHECK(hipStreamSynchronize(st_));
+    if (h) throw Error(XM_ERR_ARG, "xm_tuning_t.hess_f32: " + std::to_string(h) + " entries of Q are not finite in fp32");
+}
+
 void Context::set_edge_weights(const double *w) {
     if (storage_ == XM_STORAGE_SCHUR) {
         schur_->set_weights(w, st_);
@@ -1821,6 +1846,7 @@ void Context::set_edge_weights(const double *w) {
     launch_edge_write(dense, ne_, ei_.p, ej_.p, eM_.p, ew_.p, cam0_, nloc_, inc_ptr_.p, inc_edge_.p, pos_ij_.p, pos_ji_.p, pos_d_.p,
                       dense ? nullptr : blocks_.p, dense ? dQ_ : nullptr, ld_, st_);
     if (sell_) sell_->refill(colidx_.p, blocks_.p, st_);   // the sliced-ELL copy follows the CSR values
+    if (dQ32_) refresh_q32();                              // and the fp32 copy the dense values
     XM_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
@@ -1925,10 +1951,12 @@ void Context::solve(const xm_options_t &opt, xm_result_t &res) {
     // algorithmic bytes of one tCG product at the final rank
     const int of = std::max(3, std::min(out_rank, (int)opt.max_rank));
     res.sym_product = ((sym_ok_ || symw_) && storage_ == XM_STORAGE_DENSE) ? 1 : 0;
-    if (storage_ == XM_STORAGE_DENSE) res.qw_bytes = 8LL * (3 * n_) * (3 * n_) + 2LL * 8 * 3 * n_ * of;
+    res.hess_f32 = dQ32_ ? 1 : 0;
+    const int64_t qel = dQ32_ ? 4 : 8;   // bytes per element of the matrix the tCG products read
+    if (storage_ == XM_STORAGE_DENSE) res.qw_bytes = qel * (3 * n_) * (3 * n_) + 2LL * 8 * 3 * n_ * of;
     else if (storage_ == XM_STORAGE_SCHUR) res.qw_bytes = schur_->bytes_per_product(of);
     else res.qw_bytes = 76LL * nb_loc_ + 4LL * (n_ + 1) + 2LL * 8 * 3 * n_ * of;
-    res.qw_stream_bytes = (storage_ == XM_STORAGE_DENSE) ? (symw_ ? symw_->stream_bytes() : (res.sym_product ? 4LL : 8LL) * (3 * n_) * (3 * n_))
+    res.qw_stream_bytes = (storage_ == XM_STORAGE_DENSE) ? (symw_ ? symw_->stream_bytes() : (res.sym_product ? qel / 2 : qel) * (3 * n_) * (3 * n_))
                           : (storage_ == XM_STORAGE_BSR3) ? ((sell_ && sell_supports(of)) ? sell_->stream_bytes() : 76LL * nb_loc_) : 0;
     res.n_gpus = comm_->world;
     res.exchange = !comm_->active() ? 0 : (xchg_.world > 1 ? 2 : 1);

@@ -33,9 +33,10 @@ EXPORTS = [
     "xm_comm_unique_id", "xm_comm_init", "xm_comm_init_shm", "xm_comm_init_ipc", "xm_comm_finalize", "xm_partition", "xm_partition_blocks",
     "xm_symv_plan", "xm_sell_layout", "xm_sell_locality", "xm_sell_create", "xm_sell_create2", "xm_sell_quat_roundtrip", "xm_sell_destroy", "xm_qw_sell", "xm_qw_sell_padded",
     "xm_ctx_attach_edges", "xm_ctx_edge_residuals", "xm_ctx_edge_residuals_recovered", "xm_ctx_xm2_filter", "xm_ctx_xm2_round", "xm_ctx_set_edge_weights", "xm_ctx_recover_tp", "xm_ctx_schur_info", "xm_ctx_qw", "xm_spd_inverse", "xm_ctx_transport", "xm_ctx_sell_wpad", "xm_ctx_product_kind", "xm_symw_plan", "xm_symw_use",
+    "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
-BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
+BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
                  "xm_retract_variant", "xm_recover_rotations_variant", "xm_peer_allgather_bench", "xm_qw_symw_time", "xm_bench_grid_barrier"]
 PRODUCT_KINDS = {0: "dense", 1: "dense_sym", 2: "bsr3", 3: "sell", 4: "sell_quat", 5: "schur"}
 
@@ -49,7 +50,7 @@ class Tuning(C.Structure):
                                          "overlap_min_mb", "cert_dense_rows", "lanczos_mmax", "lanczos_restarts", "watchdog_s", "balance",
                                          "exchange", "split_k", "sell_wpad", "exchange_fence", "schur_host_assembly", "schur_trace",
                                          "schur_solver", "schur_dense_max", "debug_drop_finalize", "debug_peer_mute", "schur_pcg_first",
-                                         "schur_pcg_hess_digits")] + [("reserved", C.c_int32 * 2)]
+                                         "schur_pcg_hess_digits", "hess_f32")] + [("reserved", C.c_int32 * 1)]
 
 
 class Problem(C.Structure):
@@ -76,7 +77,7 @@ class Result(C.Structure):
                 ("qw_bytes", C.c_int64), ("trace_len", C.c_int32), ("last_stop_reason", C.c_int32),
                 ("sym_product", C.c_int32), ("cert_flags", C.c_int32), ("eig_residual", C.c_double),
                 ("n_gpus", C.c_int32), ("exchange", C.c_int32), ("qw_stream_bytes", C.c_int64),
-                ("outer_on_device", C.c_int32), ("reserved_", C.c_int32)]
+                ("outer_on_device", C.c_int32), ("hess_f32", C.c_int32)]
 
 
 class Xm2Info(C.Structure):
@@ -134,6 +135,11 @@ def lib():
         L.xm_dense_from_bsr3.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
         L.xm_qw_dense.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
         L.xm_qw_dense_sym.argtypes = L.xm_qw_dense.argtypes
+        L.xm_dense_to_f32.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+        L.xm_qw_dense_f32.argtypes = L.xm_qw_dense.argtypes
+        L.xm_qw_dense_sym_f32.argtypes = L.xm_qw_dense.argtypes
+        L.xm_qw_dense_f32_time.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+        L.xm_qw_dense_sym_f32_time.argtypes = L.xm_qw_dense_f32_time.argtypes
         L.xm_qw_dense_sym_time.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double)]
         L.xm_bench_symv_k.argtypes = [C.c_int, C.c_int, C.c_int]
         L.xm_qw_dense_sym_trace.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int)]
@@ -289,6 +295,38 @@ def qw_dense(Q, W, alpha=1.0, dq=None, sym=False):
     _chk(lib().xm_dev_sync())
     out = from_rm(dO.get(), 3 * n, o)
     for b in (dW, dO) + ((dq,) if own else ()):
+        b.free()
+    return out
+
+
+def dense_to_f32(dq, n):
+    """fp32 copy of a device matrix in the padded layout (xm_dense_to_f32): 3n rows of dense_ld(n) floats; .get(np.float32) reads it back"""
+    p = C.c_void_p()
+    rc = lib().xm_dense_to_f32(dq.ptr, n, C.byref(p))
+    d = DevArray.__new__(DevArray)
+    d.ptr, d.nbytes = p, 3 * n * dense_ld(n) * 4
+    if rc != 0:
+        d.free()
+        _chk(rc)
+    return d
+
+
+def qw_dense_f32(Q, W, alpha=1.0, sym=False):
+    """alpha * fp32(Q) @ W on the GPU, Q read from its fp32 copy and accumulated in f64 (xm_qw_dense_f32; sym=True: xm_qw_dense_sym_f32)"""
+    require_gpu()
+    W = np.asarray(W, dtype=np.float64)
+    n, o = W.shape[0] // 3, W.shape[1]
+    dq = dense_upload(Q)
+    try:
+        d32 = dense_to_f32(dq, n)
+    finally:
+        dq.free()
+    dW = DevArray(to_rm(W, rows=dense_ld(n)))
+    dO = DevArray(nbytes=3 * n * pitch_of(o) * 8)
+    _chk((lib().xm_qw_dense_sym_f32 if sym else lib().xm_qw_dense_f32)(d32.ptr, n, o, dW.ptr, dO.ptr, alpha, None))
+    _chk(lib().xm_dev_sync())
+    out = from_rm(dO.get(), 3 * n, o)
+    for b in (d32, dW, dO):
         b.free()
     return out
 
