@@ -157,7 +157,8 @@ def test_stream_cache_policy_never_changes_a_result(xmamd):
     between); in the sliced-ELL and block-CSR kernels the two policies are two compiled copies of the loop under a uniform branch.  The test
     matrices are small, so the rule never reaches the non-temporal copies: force every policy (xm_bench_dense_policy) -- all cacheable, all
     non-temporal, a prefix that cuts the stream in the middle -- and compare bit for bit with the default.  Sliced ELL with full blocks and
-    with the quaternion codec, block CSR, dense (general kernel with a resident prefix)"""
+    with the quaternion codec, block CSR, dense (general kernel with a resident prefix), and the f64 symmetric sweep in both directions (a
+    prefix of whole steps from the top of the upper triangle)"""
     import ctypes as C
     L = xmamd.lib()
     P = tl.gen_vg(3000, deg=24, sigma=0.3, seed=31)
@@ -176,17 +177,31 @@ def test_stream_cache_policy_never_changes_a_result(xmamd):
         out.append(xmamd.from_rm(dO.get(), 9000, 3))
         for b in (drp, dci, dbl, dW, dO): b.free()
         out.append(xmamd.qw_dense(D["Q"], Wd, 1.0))
+        # the symmetric sweep: top-down (functional entry) and bottom-up (the timing hook's last launch: warm-ups rev 0 1 0, timed rev 1)
+        out.append(xmamd.qw_dense(D["Q"], Wd, 1.0, dq=dD, sym=True))
+        dW = xmamd.DevArray(xmamd.to_rm(Wd, rows=xmamd.dense_ld(300))); dO = xmamd.DevArray(np.full(900 * 3, np.nan))
+        xmamd._chk(L.xm_qw_dense_sym_time(dD.ptr, 300, 3, dW.ptr, dO.ptr, 1, C.byref(ms)))
+        out.append(xmamd.from_rm(dO.get(), 900, 3))
+        dW.free(); dO.free()
         return out
+    dD = xmamd.dense_upload(D["Q"])
     try:
         ref = products()
-        for pol in (0, 1, -1024, -3000):     # (the sliced-ELL streams are ~9 MB / ~5 MB, the dense matrix 9 MB)
+        # the sliced-ELL streams are ~9 MB / ~5 MB, the dense matrix 9 MB (general kernel: 24 KB per camera, prefixes of 42 / 125 of 300
+        # cameras).  The f64 sweep streams the triangle 8 m (m + 6) / 2 = 3.26 MB (m = 900 rows); a prefix of P bytes holds its rows
+        # r = m - sqrt(m^2 - 2 P / 8): 160 rows (1 024 KB) and 695 rows (3 000 KB), so the first non-temporal step is 26 and 115 of 150
+        # (chunks of K = 4 steps: both policies run in one launch)
+        for pol in (0, 1, -1024, -3000):
             xmamd._chk(L.xm_bench_dense_policy(pol))
             got = products()
-            for a, b in zip(ref, got):
-                assert np.array_equal(a, b), pol
+            for i, (a, b) in enumerate(zip(ref, got)):
+                assert np.array_equal(a, b), (pol, i)
     finally:
         xmamd._chk(L.xm_bench_dense_policy(-1))
+        dD.free()
     assert tl.rel_fro(ref[0], tl.bsr_to_dense(3000, P["rowptr"], P["colidx"], P["blocks"]) @ W) < 1e-13
+    Dw = D["Q"] @ Wd
+    assert tl.rel_fro(ref[-3], Dw) < 1e-13 and tl.rel_fro(ref[-2], Dw) < 1e-13 and tl.rel_fro(ref[-1], Dw) < 1e-13
 
 
 def test_qw_sell_skewed_degrees_and_unsorted_rows(xmamd):
