@@ -113,7 +113,10 @@ typedef struct {
     int32_t schur_host_assembly; /* XM_STORAGE_SCHUR: 1 = assemble the reduced camera Laplacian on the host (the reference's route, utils/creatematrix.py:137-260) */
     int32_t schur_trace;       /* XM_STORAGE_SCHUR: 1 = set-up phase times on stderr */
     int32_t schur_solver;      /* XM_STORAGE_SCHUR: how the reduced camera Laplacian is applied inside the product: 0 auto (dense inverse up to
-                                  schur_dense_max cameras, preconditioned CG above), 1 dense inverse, 2 preconditioned CG (xm-code_amd/csrc/xm_schur.h) */
+                                  schur_dense_max cameras, preconditioned CG above), 1 dense inverse, 2 preconditioned CG (Jacobi;
+                                  xm-code_amd/csrc/xm_schur.h), 3 CG with the two-level preconditioner: exact blocks of VT on aggregates of
+                                  64 cameras in breadth-first order plus the coarse operator P^T VT P (sequential captures, where Jacobi needs
+                                  O(N) iterations); single GPU, at most 4096 aggregates (262 144 cameras).  Auto never picks 3. */
     int32_t schur_dense_max;   /* 0 = 20000 */
     int32_t debug_drop_finalize; /* tests: the k-th outer iteration loses its result kernel (the host must come back with XM_ERR_HIP) */
     int32_t debug_peer_mute;   /* tests: rank 1 never publishes its tCG epoch (a dead peer: the bounded waits must expire) */
@@ -322,6 +325,9 @@ int xm_ctx_recover_tp(xm_ctx_t *ctx, const double *rot, const double *scale, dou
  * preconditioned CG on the matrix-free VT (no N^2 array) -- and, for the CG form, stats = {products so far, inner CG iterations
  * so far, products that stopped at the iteration cap instead of at the tolerance 1e-13} and the relative residual of the last product. */
 int xm_ctx_schur_info(xm_ctx_t *ctx, int *uses_cg, int64_t stats[3], double *last_relres);
+/* ... and the preconditioner of the CG form: *kind = -1 no CG form (dense inverse, or not a matrix-free context), 0 Jacobi (schur_solver 2 or
+ * auto), 1 two-level (schur_solver 3; *aggregates = their number n_c, *block = cameras per aggregate).  aggregates / block may be NULL. */
+int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int *block);
 
 /* ================================================================== 3. kernel-level entry points (device pointers) */
 /* device memory helpers so that callers need no other GPU runtime */
@@ -369,6 +375,11 @@ int xm_symv_plan(int64_t n, int32_t plan[4]);
  * predicate "row step t uses block (t, u)" of a matrix of T steps. */
 int xm_symw_plan(int64_t ntot, int nloc, int cam0, int K, int32_t geom[8], int32_t *items);
 int xm_symw_use(int T, int t, int u);
+/* Aggregates of the two-level preconditioner (xm_tuning_t.schur_solver = 3) for an observation list, host-only (CPU test): the cameras
+ * 1..n-1 in breadth-first order over the camera-landmark graph from camera 0 (landmarks seen more than 64 times are not expanded), unreached
+ * cameras appended, cut into runs of B (1..64; the solver uses 64).  agg_of_camera[n]: aggregate of every camera, -1 for camera 0.  More
+ * than 4096 aggregates: XM_ERR_ARG. */
+int xm_schur_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int32_t *lm, int B, int32_t *agg_of_camera);
 /* Large block-sparse Q: "sliced ELL over per-XCD column slabs" (xm-code_amd/csrc/xm_sell.h).  Same product as xm_qw_bsr3
  * (the reference has no sparse product: Dense/matmul.h:42-87 on a dense Q); the matrix is described on the HOST as 3x3-block CSR
  * (rows n, global columns in [0, ncols)) and re-laid on the device.  slabs in {1,2,4,8}; lmax = longest virtual row (hub

@@ -276,6 +276,17 @@ int xm_ctx_schur_info(xm_ctx_t *ctx, int *uses_cg, int64_t stats[3], double *las
     return XM_OK;
     XM_CATCH
 }
+int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int *block) {
+    XM_TRY
+    if (!ctx || !ctx->impl || !kind) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_precond_info: single-GPU context and a non-null output needed");
+    int64_t na = 0;
+    int b = 0;
+    *kind = ctx->impl->schur_precond(&na, &b);
+    if (aggregates) *aggregates = na;
+    if (block) *block = b;
+    return XM_OK;
+    XM_CATCH
+}
 int xm_ctx_set_edge_weights(xm_ctx_t *ctx, const double *w) {
     XM_TRY
     if (!ctx) throw xm::Error(XM_ERR_ARG, "null argument");
@@ -746,6 +757,18 @@ int xm_symw_plan(int64_t ntot, int nloc, int cam0, int K, int32_t geom[8], int32
     }
     if (items)
         for (size_t i = 0; i < p.items.size(); ++i) { items[3 * i] = p.items[i].s; items[3 * i + 1] = p.items[i].jb; items[3 * i + 2] = p.items[i].je; }
+    return XM_OK;
+    XM_CATCH
+}
+// host-only view of the two-level preconditioner's aggregates (xm_schur.h) for the CPU test: agg_of_camera[i] = aggregate of camera i, -1 for the
+// anchor camera 0
+int xm_schur_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int32_t *lm, int B, int32_t *agg_of_camera) {
+    XM_TRY
+    if (!agg_of_camera) throw xm::Error(XM_ERR_ARG, "xm_schur_aggregate_plan: null output");
+    std::vector<int32_t> order;
+    xm::schur_aggregate_plan(n, nobs, cam, lm, B, order);
+    agg_of_camera[0] = -1;
+    for (size_t k = 0; k < order.size(); ++k) agg_of_camera[order[k]] = (int32_t)(k / (size_t)B);
     return XM_OK;
     XM_CATCH
 }

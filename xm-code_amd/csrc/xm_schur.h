@@ -25,6 +25,14 @@
 namespace xm {
 
 constexpr int64_t kSchurMaxCams = 40000;   // (N-1)^2 inverse + workspace = 3 x 8 N^2 bytes during set-up: 38 GB at the limit
+constexpr int kSchurAggCams = 64;          // two-level preconditioner of the CG form: cameras per aggregate (one wavefront, a lane per camera)
+constexpr int64_t kSchurMaxAggregates = 4096;   // ... and its coarse operator: the n_c x n_c inverse is at most 134 MB
+
+// Aggregates of the two-level preconditioner (host; xm_schur_aggregate_plan): the cameras 1..n-1 in the order of a breadth-first search over
+// the bipartite camera-landmark graph from camera 0 (landmarks with more than kSchurHeavy observations are not expanded: they carry no
+// locality), cameras it never reaches appended in index order, cut into runs of B.  order[k] = the camera at position k (aggregate k / B).
+// More than kSchurMaxAggregates runs: XM_ERR_ARG.
+void schur_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int32_t *lm, int B, std::vector<int32_t> &order);
 
 // A (device, column-major n x n, lower triangle read) -> Cholesky factor; X <- the LOWER triangle of A^-1 (above the diagonal: scratch).
 // false: not positive definite
@@ -39,6 +47,7 @@ struct SchurSettings {          // from xm_tuning_t (Settings::resolve)
     int64_t sym_min_rows = 4096; // VT^-1 is applied with the half-traffic symmetric kernel from this many rows on
     bool trace = false;         // set-up phase times on stderr (scripts/kbench_schur.py)
     int solver = 0;             // reduced camera system inside the product: 0 by size (dense inverse up to dense_max cameras, CG above) | 1 dense inverse | 2 preconditioned CG
+                                // (Jacobi) | 3 CG with the two-level preconditioner (aggregate blocks + coarse operator; xm_schur.hip)
     int64_t dense_max = 20000;  // (the dense inverse costs 8 (N-1)^2 bytes -- 3.2 GB here -- and an O(N^3) set-up; the CG form nothing but the observation lists)
     int pcg_first = 0;          // CG form: iterations of the first batch of a context's first product (0 = 26; tests force top-up batches with a small one)
     int pcg_hess_digits = 0;    // CG form: relative residual 10^-digits of the inner solve inside HESSIAN products (0 = 9; gradient, cost and certificate products: 13)
@@ -70,6 +79,8 @@ public:
     // and the relative residual of the last one
     bool uses_pcg() const { return pcg_; }
     void pcg_stats(int64_t out[3], double *relres) const { out[0] = pcg_products_; out[1] = pcg_iters_total_; out[2] = pcg_unconverged_; if (relres) *relres = pcg_last_relres_; }
+    bool two_level() const { return tl_; }
+    int64_t aggregates() const { return tl_nagg_; }
 
 private:
     int64_t n_ = 0, m_ = 0, nobs_ = 0, nred_ = 0, ldv_ = 0;   // nred = cameras of the padded (N-1) system / 3
@@ -114,7 +125,20 @@ private:
     int pcg_grid_ = 1, pcg_last_iters_[2] = {24, 24}, pcg_max_iters_ = 1000;   // [0] products at the tight tolerance, [1] Hessian products
     double pcg_tol_[2] = {1e-13, 1e-9}, pcg_last_relres_ = 0.0;
     int64_t pcg_products_ = 0, pcg_iters_total_ = 0, pcg_unconverged_ = 0;
-    template <int O> void pcg_solve(const SchurLm &L, const struct TcgScal *sc, hipStream_t st, int kind);
+    template <int O, bool TL> void pcg_solve(const SchurLm &L, const struct TcgScal *sc, hipStream_t st, int kind);
+    // two-level preconditioner M^-1 r = blockdiag(VT_aa)^-1 r + P A_c^-1 P^T r (cfg.solver == 3).  Structure (fixed): the aggregates and, per
+    // aggregate, its "groups" -- the observations of one landmark whose cameras fall in the aggregate, by landmark slot -- and the coarse
+    // entries with their lists of group pairs (light landmarks; heavy ones are rank-1 terms).  Weight-dependent: the block inverses and A_c^-1.
+    bool tl_ = false;
+    int64_t tl_nagg_ = 0, tl_ngroups_ = 0, tl_nentries_ = 0;
+    DevBuf<int32_t> tl_perm_;                 // position (aggregate * kSchurAggCams + row) -> reduced camera (camera - 1), -1 = padding
+    DevBuf<int64_t> tl_gptr_, tl_eptr_, tl_eobs_, tl_cptr_;
+    DevBuf<int32_t> tl_gslot_, tl_eloc_, tl_cab_, tl_cpair_;
+    DevBuf<double> tl_u_, tl_binv_, tl_ainv_, tl_g_, tl_z_;
+    DevBuf<int32_t> tl_fail_;
+    std::vector<int32_t> tl_agg_of_;          // camera -> aggregate (-1: camera 0)
+    void two_level_build(int64_t nobs, const int32_t *cam, const int32_t *lm);
+    void two_level_set_weights(const double *w, hipStream_t st);
 public:
     ~SchurOp();
     SchurOp(const SchurOp &) = delete;

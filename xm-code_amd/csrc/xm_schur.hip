@@ -250,7 +250,10 @@ struct PcgArgs {
     int grid;                 // workgroups of the flat kernels == partial sums per column
     double tol2;              // (relative residual)^2 to reach
     const double *b;          // right-hand side r_ (pitch OP)
-    const double *dinv;       // 1 / diag(VT), n1
+    union {
+        const double *dinv;   // 1 / diag(VT), n1
+        const double *z;      // two-level preconditioner (TL kernels): z = M^-1 r, pitch OP, written by pcg_block_kernel / pcg_coarse_kernel
+    };
     const double *q2;         // Q2 per camera (index cam)
     double *x, *r, *p, *Ap;   // pitch OP, n1 records
     double *prz[2], *prr, *pbb;   // per-workgroup partial sums of <r,z> (by iteration parity), |r|^2, |b|^2: grid * O each (column-major: [k][workgroup])
@@ -271,8 +274,9 @@ __device__ __forceinline__ void pcg_store_partials(const double (&acc)[O], doubl
         if (threadIdx.x == 0) parts[(size_t)k * grid + blockIdx.x] = t;
     }
 }
-// x = 0, r = b, p = z = dinv .* r; partials of <r, z> (parity 0) and |b|^2
-template <int O>
+// x = 0, r = b, p = z = dinv .* r; partials of <r, z> (parity 0) and |b|^2.  TL (two-level preconditioner): x = 0, r = b and |b|^2 only --
+// z, p = z and <r, z> come from pcg_block_kernel + pcg_coarse_kernel behind this launch
+template <int O, bool TL = false>
 __global__ __launch_bounds__(256) void pcg_init_kernel(PcgArgs a, const TcgScal *__restrict__ scal) {
     constexpr int OP = pitch_of(O);
     __shared__ double sh[4];
@@ -284,20 +288,29 @@ __global__ __launch_bounds__(256) void pcg_init_kernel(PcgArgs a, const TcgScal 
 #pragma unroll
     for (int k = 0; k < O; ++k) rz[k] = bb[k] = 0.0;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < a.n1; i += gridDim.x * 256) {
-        const double di = a.dinv[i];
+        if constexpr (TL) {
 #pragma unroll
-        for (int k = 0; k < O; ++k) {
-            const double v = a.b[(size_t)i * OP + k], z = di * v;
-            a.x[(size_t)i * OP + k] = 0.0; a.r[(size_t)i * OP + k] = v; a.p[(size_t)i * OP + k] = z;
-            rz[k] += v * z; bb[k] += v * v;
+            for (int k = 0; k < O; ++k) {
+                const double v = a.b[(size_t)i * OP + k];
+                a.x[(size_t)i * OP + k] = 0.0; a.r[(size_t)i * OP + k] = v;
+                bb[k] += v * v;
+            }
+        } else {
+            const double di = a.dinv[i];
+#pragma unroll
+            for (int k = 0; k < O; ++k) {
+                const double v = a.b[(size_t)i * OP + k], z = di * v;
+                a.x[(size_t)i * OP + k] = 0.0; a.r[(size_t)i * OP + k] = v; a.p[(size_t)i * OP + k] = z;
+                rz[k] += v * z; bb[k] += v * v;
+            }
         }
     }
-    pcg_store_partials<O>(rz, a.prz[0], a.grid, sh);
+    if constexpr (!TL) pcg_store_partials<O>(rz, a.prz[0], a.grid, sh);
     pcg_store_partials<O>(bb, a.pbb, a.grid, sh);
     if (blockIdx.x == 0 && threadIdx.x == 0) { a.st->done = 0; a.st->iters = 0; a.st->relres = 1.0; }
 }
 // iteration it >= 1: beta = <r,z>_new / <r,z>_old per column, p = z + beta p; decides whether the previous update reached the tolerance
-template <int O>
+template <int O, bool TL = false>
 __global__ __launch_bounds__(256) void pcg_dir_kernel(PcgArgs a, int it) {
     constexpr int OP = pitch_of(O);
     __shared__ double sh[4];
@@ -328,9 +341,14 @@ __global__ __launch_bounds__(256) void pcg_dir_kernel(PcgArgs a, int it) {
 #pragma unroll
     for (int k = 0; k < O; ++k) beta[k] = (rzo[k] > 0.0) ? rzn[k] / rzo[k] : 0.0;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < a.n1; i += gridDim.x * 256) {
-        const double di = a.dinv[i];
+        if constexpr (TL) {
 #pragma unroll
-        for (int k = 0; k < O; ++k) a.p[(size_t)i * OP + k] = di * a.r[(size_t)i * OP + k] + beta[k] * a.p[(size_t)i * OP + k];
+            for (int k = 0; k < O; ++k) a.p[(size_t)i * OP + k] = a.z[(size_t)i * OP + k] + beta[k] * a.p[(size_t)i * OP + k];
+        } else {
+            const double di = a.dinv[i];
+#pragma unroll
+            for (int k = 0; k < O; ++k) a.p[(size_t)i * OP + k] = di * a.r[(size_t)i * OP + k] + beta[k] * a.p[(size_t)i * OP + k];
+        }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) { a.st->iters = it; a.st->relres = sqrt(worst); }
 }
@@ -415,8 +433,9 @@ __global__ __launch_bounds__(256) void pcg_cam_kernel(int n, const int64_t *__re
         }
     }
 }
-// alpha = <r,z> / <p,Ap> per column; x += alpha p, r -= alpha Ap; partials of the new <r,z> (other parity) and |r|^2
-template <int O>
+// alpha = <r,z> / <p,Ap> per column; x += alpha p, r -= alpha Ap; partials of the new <r,z> (other parity) and |r|^2.  TL: |r|^2 only (the
+// new <r,z> is pcg_coarse_kernel's)
+template <int O, bool TL = false>
 __global__ __launch_bounds__(256) void pcg_upd_kernel(PcgArgs a, int it) {
     constexpr int OP = pitch_of(O);
     __shared__ double sh[4];
@@ -430,17 +449,28 @@ __global__ __launch_bounds__(256) void pcg_upd_kernel(PcgArgs a, int it) {
 #pragma unroll
     for (int k = 0; k < O; ++k) rzn[k] = rr[k] = 0.0;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < a.n1; i += gridDim.x * 256) {
-        const double di = a.dinv[i];
+        if constexpr (TL) {
 #pragma unroll
-        for (int k = 0; k < O; ++k) {
-            const size_t j = (size_t)i * OP + k;
-            a.x[j] += alpha[k] * a.p[j];
-            const double rn = a.r[j] - alpha[k] * a.Ap[j];
-            a.r[j] = rn;
-            rzn[k] += rn * rn * di; rr[k] += rn * rn;
+            for (int k = 0; k < O; ++k) {
+                const size_t j = (size_t)i * OP + k;
+                a.x[j] += alpha[k] * a.p[j];
+                const double rn = a.r[j] - alpha[k] * a.Ap[j];
+                a.r[j] = rn;
+                rr[k] += rn * rn;
+            }
+        } else {
+            const double di = a.dinv[i];
+#pragma unroll
+            for (int k = 0; k < O; ++k) {
+                const size_t j = (size_t)i * OP + k;
+                a.x[j] += alpha[k] * a.p[j];
+                const double rn = a.r[j] - alpha[k] * a.Ap[j];
+                a.r[j] = rn;
+                rzn[k] += rn * rn * di; rr[k] += rn * rn;
+            }
         }
     }
-    pcg_store_partials<O>(rzn, a.prz[(it & 1) ^ 1], a.grid, sh);
+    if constexpr (!TL) pcg_store_partials<O>(rzn, a.prz[(it & 1) ^ 1], a.grid, sh);
     pcg_store_partials<O>(rr, a.prr, a.grid, sh);
 }
 // 1 / diag(VT):  diag_i = Q2_i - sum_{obs of i} w^2 / Q3_l   (one wavefront per camera; set-up)
@@ -456,6 +486,183 @@ __global__ __launch_bounds__(256) void pcg_diag_kernel(int n, const int64_t *__r
         const double d = q2[cam] - acc;
         dinv[cam - 1] = (d > 0.0) ? 1.0 / d : 0.0;
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Two-level additive Schwarz preconditioner of the CG form (xm_tuning_t.schur_solver = 3):
+//      M^-1 r = blockdiag(VT_aa)^-1 r + P A_c^-1 P^T r
+// a: aggregates of at most kSchurAggCams cameras (schur_aggregate_plan: runs of a breadth-first order, so that an aggregate is a stretch of
+// the co-visibility graph), VT_aa: the exact principal block of VT, P: the 0/1 camera -> aggregate map, A_c = P^T VT P.  Both terms are SPD
+// when VT is, so plain PCG stays valid.  Jacobi's diag(VT)^-1 VT is well conditioned only on expander-like graphs (random co-visibility);
+// on a sequential capture VT is close to a path Laplacian and Jacobi needs O(N) iterations, the coarse term removes the smooth error
+// the blocks cannot see.  Two launches per iteration behind pcg_upd_kernel<O, true>; every sum in a fixed order (no atomics).
+// ------------------------------------------------------------------------------------------------------------------
+struct PcgTwoLevel {
+    int64_t nagg;
+    const int32_t *perm;      // nagg * kSchurAggCams: reduced camera (camera - 1) at each row of each aggregate, -1 = padding
+    const double *binv;       // nagg blocks of kSchurAggCams^2: VT_aa^-1, symmetric
+    const double *ainv;       // nagg x nagg: A_c^-1, symmetric
+    double *g;                // P^T r: nagg * O
+    double *z;                // M^-1 r (= PcgArgs.z)
+};
+// z_a = VT_aa^-1 r_a and g_a = sum_{i in a} r_i: one wavefront per aggregate, a lane per row; the block inverse is read by columns (coalesced)
+template <int O>
+__global__ __launch_bounds__(256) void pcg_block_kernel(PcgArgs a, PcgTwoLevel t) {
+    constexpr int OP = pitch_of(O), B = kSchurAggCams;
+    __shared__ double rs[kQwWaves][B][O];
+    if (a.st->done) return;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t ag = (int64_t)blockIdx.x * kQwWaves + wv;
+    if (ag >= t.nagg) return;   // wavefront-uniform; no workgroup barrier below
+    const int i = t.perm[ag * B + lane];
+    double ri[O];
+#pragma unroll
+    for (int k = 0; k < O; ++k) {
+        ri[k] = (i >= 0) ? a.r[(size_t)i * OP + k] : 0.0;
+        rs[wv][lane][k] = ri[k];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    double z[O];
+#pragma unroll
+    for (int k = 0; k < O; ++k) z[k] = 0.0;
+    const double *col = t.binv + (size_t)ag * B * B + lane;
+    for (int m = 0; m < B; ++m) {
+        const double bm = col[(size_t)m * B];
+#pragma unroll
+        for (int k = 0; k < O; ++k) z[k] += bm * rs[wv][m][k];
+    }
+    if (i >= 0) {
+#pragma unroll
+        for (int k = 0; k < O; ++k) t.z[(size_t)i * OP + k] = z[k];
+    }
+#pragma unroll
+    for (int k = 0; k < O; ++k) ri[k] = wave_sum(ri[k]);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < O; ++k) t.g[(size_t)ag * O + k] = ri[k];
+    }
+}
+// z_i += (A_c^-1 g)_{a(i)} (one wavefront per aggregate, grid-strided over the aggregates; the row of A_c^-1 lane-strided + DPP tree), init:
+// p = z as well; partials of <r, z> into parity `par` (grid: the flat kernels' -- pcg_dir_kernel sums them)
+template <int O>
+__global__ __launch_bounds__(256) void pcg_coarse_kernel(PcgArgs a, PcgTwoLevel t, int par, int init) {
+    constexpr int OP = pitch_of(O), B = kSchurAggCams;
+    __shared__ double sh[4];
+    if (a.st->done) return;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double rz[O];
+#pragma unroll
+    for (int k = 0; k < O; ++k) rz[k] = 0.0;
+    for (int64_t ag = (int64_t)blockIdx.x * kQwWaves + wv; ag < t.nagg; ag += (int64_t)gridDim.x * kQwWaves) {
+        double c[O];
+#pragma unroll
+        for (int k = 0; k < O; ++k) c[k] = 0.0;
+        const double *row = t.ainv + (size_t)ag * (size_t)t.nagg;
+        for (int64_t b = lane; b < t.nagg; b += 64) {
+            const double v = row[b];
+#pragma unroll
+            for (int k = 0; k < O; ++k) c[k] += v * t.g[(size_t)b * O + k];
+        }
+#pragma unroll
+        for (int k = 0; k < O; ++k) c[k] = wave_sum(c[k]);
+        const int i = t.perm[ag * B + lane];
+        if (i >= 0) {
+#pragma unroll
+            for (int k = 0; k < O; ++k) {
+                const size_t j = (size_t)i * OP + k;
+                const double zz = t.z[j] + c[k];
+                t.z[j] = zz;
+                if (init) a.p[j] = zz;
+                rz[k] += a.r[j] * zz;
+            }
+        }
+    }
+    pcg_store_partials<O>(rz, a.prz[par], a.grid, sh);
+}
+
+// set-up (every set_weights): U_g = the weights of group g's observations summed in list order (group: the observations of one landmark
+// whose cameras fall in one aggregate)
+__global__ __launch_bounds__(256) void tl_group_sum_kernel(int64_t ng, const int64_t *__restrict__ eptr, const int64_t *__restrict__ eobs,
+                                                            const double *__restrict__ w, double *__restrict__ u) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= ng) return;
+    double s = 0.0;
+    for (int64_t e = eptr[g]; e < eptr[g + 1]; ++e) s += w[eobs[e]];
+    u[g] = s;
+}
+// A_c entry (a, b), a >= b, one thread each: [a == b] sum_{i in a} Q2_i - sum over its group pairs (light landmarks in slot order) of
+// (1/Q3_l) U_g1 U_g2; written to both triangles (column-major).  Heavy landmarks follow as rank-1 terms (rank1_sub_device).
+__global__ __launch_bounds__(256) void tl_coarse_entries_kernel(int64_t nent, const int64_t *__restrict__ cptr, const int32_t *__restrict__ cab,
+                                                                 const int32_t *__restrict__ cpair, const int32_t *__restrict__ gslot,
+                                                                 const double *__restrict__ u, const double *__restrict__ q3inv,
+                                                                 const int32_t *__restrict__ perm, const double *__restrict__ q2, int64_t nagg,
+                                                                 double *__restrict__ A) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nent) return;
+    const int64_t a = cab[2 * k], b = cab[2 * k + 1];
+    double v = 0.0;
+    if (a == b)
+        for (int j = 0; j < kSchurAggCams; ++j) {
+            const int i = perm[a * kSchurAggCams + j];
+            if (i >= 0) v += q2[i + 1];
+        }
+    for (int64_t q = cptr[k]; q < cptr[k + 1]; ++q) {
+        const int32_t g1 = cpair[2 * q], g2 = cpair[2 * q + 1];
+        v -= q3inv[gslot[g1]] * u[g1] * u[g2];
+    }
+    A[(size_t)a + (size_t)b * nagg] = v;
+    A[(size_t)b + (size_t)a * nagg] = v;
+}
+// VT_aa^-1 for one aggregate per workgroup (one wavefront, lane j owns column j of the block in LDS): diag(Q2), then per group in slot order
+// -= (1/Q3_l) u u^T with u the group's weights by row (a row named twice sums: lane j's u_j, then every entry of the group into column j in
+// list order), then Gauss-Jordan inversion in place without pivoting -- on an SPD matrix every pivot is the diagonal of a Schur complement,
+// positive exactly when the block is positive definite (else *fail = 1) -- written out symmetrised.  Rows beyond the aggregate: identity.
+__global__ __launch_bounds__(64) void tl_block_inverse_kernel(const int32_t *__restrict__ perm, const int64_t *__restrict__ gptr,
+                                                               const int32_t *__restrict__ gslot, const int64_t *__restrict__ eptr,
+                                                               const int32_t *__restrict__ eloc, const int64_t *__restrict__ eobs,
+                                                               const double *__restrict__ w, const double *__restrict__ q3inv,
+                                                               const double *__restrict__ q2, double *__restrict__ binv, int32_t *__restrict__ fail) {
+    constexpr int B = kSchurAggCams;
+    __shared__ double A[B * B];   // A[i * B + j]: row i, column j
+    __shared__ double colk[B];
+    const int j = threadIdx.x;
+    const int64_t ag = blockIdx.x;
+    const int cj = perm[ag * B + j];
+    for (int i = 0; i < B; ++i) A[i * B + j] = (i == j) ? (cj >= 0 ? q2[cj + 1] : 1.0) : 0.0;
+    for (int64_t g = gptr[ag]; g < gptr[ag + 1]; ++g) {   // wavefront-uniform
+        const double q = q3inv[gslot[g]];
+        if (q == 0.0) continue;
+        double uj = 0.0;
+        for (int64_t e = eptr[g]; e < eptr[g + 1]; ++e)
+            if (eloc[e] == j) uj += w[eobs[e]];
+        if (uj == 0.0) continue;
+        const double qu = q * uj;
+        for (int64_t e = eptr[g]; e < eptr[g + 1]; ++e) A[eloc[e] * B + j] -= w[eobs[e]] * qu;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    bool ok = true;
+    for (int k = 0; k < B; ++k) {
+        const double piv = A[k * B + k];
+        colk[j] = A[j * B + k];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (!(piv > 0.0)) { ok = false; break; }   // (uniform)
+        const double akj = ((j == k) ? 1.0 : A[k * B + j]) / piv;
+        for (int i = 0; i < B; ++i) {
+            if (i == k) A[i * B + j] = akj;
+            else A[i * B + j] = ((j == k) ? 0.0 : A[i * B + j]) - colk[i] * akj;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (!ok) {
+        if (j == 0) *fail = 1;
+        return;
+    }
+    double *out = binv + (size_t)ag * B * B;
+    for (int i = 0; i < B; ++i) out[i * B + j] = 0.5 * (A[i * B + j] + A[j * B + i]);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -571,7 +778,8 @@ SchurOp::SchurOp(int64_t n, int64_t n_landmarks, int64_t nobs, const int32_t *ca
     if (n < 1 || n_landmarks < 1 || nobs < 1 || !cam || !lm || !p || !w) throw Error(XM_ERR_ARG, "matrix-free Q: bad observation list");
     // how VT^-1 is applied: the dense inverse (fast products, 8 (N-1)^2 bytes and an O(N^3) set-up) up to cfg.dense_max cameras, above that
     // preconditioned CG inside every product (no (N-1)^2 array at all); cfg.solver forces one of the two
-    pcg_ = cfg.solver == 2 || (cfg.solver == 0 && n > cfg.dense_max);
+    pcg_ = cfg.solver == 2 || cfg.solver == 3 || (cfg.solver == 0 && n > cfg.dense_max);
+    tl_ = cfg.solver == 3;
     if (pcg_ && comm_) throw Error(XM_ERR_ARG, "matrix-free Q: the CG form of the reduced camera system runs on one GPU (row-partitioned contexts use the dense inverse)");
     if (!pcg_ && n > kSchurMaxCams) throw Error(XM_ERR_ARG, "matrix-free Q: more than " + std::to_string(kSchurMaxCams) + " cameras need the CG form (xm_tuning_t.schur_solver)");
     n_ = n; m_ = n_landmarks; nobs_ = nobs;
@@ -697,6 +905,7 @@ SchurOp::SchurOp(int64_t n, int64_t n_landmarks, int64_t nobs, const int32_t *ca
         pcg_dinv_.alloc((size_t)std::max<int64_t>(mr, 1));
         XM_HIP_CHECK(hipHostMalloc((void **)&pcg_host_, sizeof(PcgState), hipHostMallocDefault));
         pcg_state_.alloc(sizeof(PcgState) / sizeof(int32_t) + 2);
+        if (tl_ && mr > 0) two_level_build(nobs, cam, lm);
     } else {
         vtinv_.alloc((size_t)3 * nred_pad_ * (size_t)ldv_);
     }
@@ -851,6 +1060,10 @@ void SchurOp::set_weights_device(const double *w, hipStream_t st) {
         for (double d : hd)
             if (!(d > 0.0) || !std::isfinite(d)) throw Error(XM_ERR_ARG, "matrix-free Q: a camera has no weight on the reduced camera Laplacian's diagonal (camera without observations?)");
         lap("Jacobi diagonal (device)");
+        if (tl_) {
+            two_level_set_weights(w, st);
+            lap("two-level preconditioner (device)");
+        }
         return;
     }
     DevBuf<double> tmp, inv;
@@ -898,6 +1111,182 @@ void SchurOp::set_weights_device(const double *w, hipStream_t st) {
     spd_inverse_layout((int)mr, inv.p, vtinv_.p, ldv_, st);
     XM_HIP_CHECK(hipStreamSynchronize(st));
     lap("layout of the inverse");
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// host: the two-level preconditioner's structure (once per context) and its weight-dependent parts (every set_weights)
+// ------------------------------------------------------------------------------------------------------------------
+void schur_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int32_t *lm, int B, std::vector<int32_t> &order) {
+    if (n < 2 || nobs < 1 || !cam || !lm) throw Error(XM_ERR_ARG, "aggregate plan: needs at least 2 cameras and 1 observation");
+    if (B < 1 || B > kSchurAggCams) throw Error(XM_ERR_ARG, "aggregate plan: cameras per aggregate must be 1.." + std::to_string(kSchurAggCams));
+    const int64_t nagg = (n - 1 + B - 1) / B;
+    if (nagg > kSchurMaxAggregates)
+        throw Error(XM_ERR_ARG, "two-level preconditioner: " + std::to_string(n - 1) + " cameras make " + std::to_string(nagg) + " aggregates of " +
+                                std::to_string(B) + ", more than the coarse operator's limit of " + std::to_string(kSchurMaxAggregates) +
+                                " (use xm_tuning_t.schur_solver = 2)");
+    int64_t M = 0;
+    for (int64_t e = 0; e < nobs; ++e) {
+        if (cam[e] < 0 || cam[e] >= n || lm[e] < 0) throw Error(XM_ERR_ARG, "aggregate plan: observation index out of range");
+        M = std::max<int64_t>(M, (int64_t)lm[e] + 1);
+    }
+    // the bipartite graph as two lists in input order (fixed visiting order)
+    std::vector<int64_t> cptr((size_t)n + 1, 0), lptr((size_t)M + 1, 0);
+    for (int64_t e = 0; e < nobs; ++e) { cptr[(size_t)cam[e] + 1]++; lptr[(size_t)lm[e] + 1]++; }
+    for (int64_t i = 0; i < n; ++i) cptr[(size_t)i + 1] += cptr[(size_t)i];
+    for (int64_t l = 0; l < M; ++l) lptr[(size_t)l + 1] += lptr[(size_t)l];
+    std::vector<int32_t> c_l((size_t)nobs), l_c((size_t)nobs);
+    {
+        std::vector<int64_t> nc(cptr.begin(), cptr.end() - 1), nl(lptr.begin(), lptr.end() - 1);
+        for (int64_t e = 0; e < nobs; ++e) { c_l[(size_t)nc[(size_t)cam[e]]++] = lm[e]; l_c[(size_t)nl[(size_t)lm[e]]++] = cam[e]; }
+    }
+    std::vector<char> cseen((size_t)n, 0), lseen((size_t)M, 0);
+    std::vector<int32_t> queue;
+    queue.reserve((size_t)n);
+    queue.push_back(0); cseen[0] = 1;
+    for (size_t h = 0; h < queue.size(); ++h) {
+        const int32_t c = queue[h];
+        for (int64_t q = cptr[(size_t)c]; q < cptr[(size_t)c + 1]; ++q) {
+            const int32_t l = c_l[(size_t)q];
+            if (lseen[(size_t)l] || lptr[(size_t)l + 1] - lptr[(size_t)l] > kSchurHeavy) continue;   // heavy landmarks carry no locality
+            lseen[(size_t)l] = 1;
+            for (int64_t q2 = lptr[(size_t)l]; q2 < lptr[(size_t)l + 1]; ++q2) {
+                const int32_t c2 = l_c[(size_t)q2];
+                if (!cseen[(size_t)c2]) { cseen[(size_t)c2] = 1; queue.push_back(c2); }
+            }
+        }
+    }
+    order.assign(queue.begin() + 1, queue.end());
+    for (int64_t i = 1; i < n; ++i)
+        if (!cseen[(size_t)i]) order.push_back((int32_t)i);
+}
+
+void SchurOp::two_level_build(int64_t nobs, const int32_t *cam, const int32_t *lm) {
+    constexpr int B = kSchurAggCams;
+    std::vector<int32_t> order;
+    schur_aggregate_plan(n_, nobs, cam, lm, B, order);
+    const int64_t nagg = (n_ - 1 + B - 1) / B;
+    tl_nagg_ = nagg;
+    std::vector<int32_t> perm((size_t)nagg * B, -1), loc((size_t)n_, -1);
+    tl_agg_of_.assign((size_t)n_, -1);
+    for (size_t k = 0; k < order.size(); ++k) {
+        perm[k] = order[k] - 1;
+        tl_agg_of_[(size_t)order[k]] = (int32_t)(k / B);
+        loc[(size_t)order[k]] = (int32_t)(k % B);
+    }
+    // groups: the observations of cameras >= 1 by (aggregate, landmark slot, input order)
+    std::vector<int64_t> aptr((size_t)nagg + 1, 0);
+    for (int64_t e = 0; e < nobs; ++e)
+        if (cam[e] != 0) aptr[(size_t)tl_agg_of_[(size_t)cam[e]] + 1]++;
+    for (int64_t a = 0; a < nagg; ++a) aptr[(size_t)a + 1] += aptr[(size_t)a];
+    std::vector<int64_t> obs((size_t)aptr[(size_t)nagg]);
+    {
+        std::vector<int64_t> na(aptr.begin(), aptr.end() - 1);
+        for (int64_t e = 0; e < nobs; ++e)
+            if (cam[e] != 0) obs[(size_t)na[(size_t)tl_agg_of_[(size_t)cam[e]]]++] = e;
+    }
+    for (int64_t a = 0; a < nagg; ++a)
+        std::stable_sort(obs.begin() + aptr[(size_t)a], obs.begin() + aptr[(size_t)a + 1],
+                         [&](int64_t x, int64_t y) { return slot_of_[(size_t)lm[x]] < slot_of_[(size_t)lm[y]]; });
+    std::vector<int64_t> gptr((size_t)nagg + 1, 0), eptr(1, 0);
+    std::vector<int32_t> gslot, gagg, eloc((size_t)obs.size());
+    for (int64_t a = 0; a < nagg; ++a) {
+        for (int64_t q = aptr[(size_t)a]; q < aptr[(size_t)a + 1]; ++q) {
+            const int32_t sl = slot_of_[(size_t)lm[obs[(size_t)q]]];
+            if (q == aptr[(size_t)a] || sl != gslot.back()) {
+                if (q != aptr[(size_t)a]) eptr.push_back(q);
+                gslot.push_back(sl); gagg.push_back((int32_t)a);
+            }
+            eloc[(size_t)q] = loc[(size_t)cam[obs[(size_t)q]]];
+        }
+        if (aptr[(size_t)a + 1] > aptr[(size_t)a]) eptr.push_back(aptr[(size_t)a + 1]);
+        gptr[(size_t)a + 1] = (int64_t)gslot.size();
+    }
+    const int64_t ng = (int64_t)gslot.size();
+    tl_ngroups_ = ng;
+    // coarse entries (a, b), a >= b, with their group pairs: light landmarks in slot order (the groups of one landmark are in aggregate order);
+    // every diagonal entry exists.  A heavy landmark (more than kSchurHeavy observations) would add up to n_c^2 pairs: a rank-1 term instead.
+    std::vector<int64_t> sptr((size_t)m_ + 1, 0);
+    for (int64_t g = 0; g < ng; ++g) sptr[(size_t)gslot[(size_t)g] + 1]++;
+    for (int64_t sl = 0; sl < m_; ++sl) sptr[(size_t)sl + 1] += sptr[(size_t)sl];
+    std::vector<int32_t> by_slot((size_t)ng);
+    {
+        std::vector<int64_t> ns(sptr.begin(), sptr.end() - 1);
+        for (int64_t g = 0; g < ng; ++g) by_slot[(size_t)ns[(size_t)gslot[(size_t)g]]++] = (int32_t)g;
+    }
+    struct Pair { int64_t key; int32_t g1, g2; };
+    std::vector<Pair> pairs;
+    for (int64_t a = 0; a < nagg; ++a) pairs.push_back({a * nagg + a, -1, -1});
+    for (int64_t sl = nheavy_; sl < m_; ++sl)
+        for (int64_t x = sptr[(size_t)sl]; x < sptr[(size_t)sl + 1]; ++x)
+            for (int64_t y = sptr[(size_t)sl]; y <= x; ++y) {
+                const int32_t g1 = by_slot[(size_t)x], g2 = by_slot[(size_t)y];
+                pairs.push_back({(int64_t)gagg[(size_t)g1] * nagg + gagg[(size_t)g2], g1, g2});
+            }
+    std::stable_sort(pairs.begin(), pairs.end(), [](const Pair &x, const Pair &y) { return x.key < y.key; });
+    std::vector<int64_t> cptr(1, 0);
+    std::vector<int32_t> cab, cpair;
+    for (size_t q = 0; q < pairs.size(); ++q) {
+        if (q == 0 || pairs[q].key != pairs[q - 1].key) {
+            if (q != 0) cptr.push_back((int64_t)cpair.size() / 2);
+            cab.push_back((int32_t)(pairs[q].key / nagg)); cab.push_back((int32_t)(pairs[q].key % nagg));
+        }
+        if (pairs[q].g1 >= 0) { cpair.push_back(pairs[q].g1); cpair.push_back(pairs[q].g2); }
+    }
+    cptr.push_back((int64_t)cpair.size() / 2);
+    tl_nentries_ = (int64_t)cab.size() / 2;
+    auto up = [&](auto &buf, const auto &v) {
+        buf.alloc(std::max<size_t>(v.size(), 1), false);
+        if (!v.empty()) XM_HIP_CHECK(hipMemcpy(buf.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
+    };
+    up(tl_perm_, perm); up(tl_gptr_, gptr); up(tl_gslot_, gslot); up(tl_eptr_, eptr); up(tl_eloc_, eloc); up(tl_eobs_, obs);
+    up(tl_cptr_, cptr); up(tl_cab_, cab); up(tl_cpair_, cpair);
+    tl_u_.alloc((size_t)std::max<int64_t>(ng, 1), false);
+    tl_binv_.alloc((size_t)nagg * B * B, false);
+    tl_ainv_.alloc((size_t)nagg * nagg, false);
+    tl_fail_.alloc(1);
+}
+
+// the blocks VT_aa^-1 and A_c^-1 from the current weights (w_in_ / q2_ / q3inv_ already on the device: set_weights_device)
+void SchurOp::two_level_set_weights(const double *w, hipStream_t st) {
+    const int64_t nagg = tl_nagg_;
+    hipLaunchKernelGGL(tl_group_sum_kernel, dim3((unsigned)std::max<int64_t>(1, (tl_ngroups_ + 255) / 256)), dim3(256), 0, st, tl_ngroups_, tl_eptr_.p, tl_eobs_.p,
+                       w_in_.p, tl_u_.p);
+    XM_HIP_CHECK(hipMemsetAsync(tl_fail_.p, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(tl_block_inverse_kernel, dim3((unsigned)nagg), dim3(kSchurAggCams), 0, st, tl_perm_.p, tl_gptr_.p, tl_gslot_.p, tl_eptr_.p,
+                       tl_eloc_.p, tl_eobs_.p, w_in_.p, q3inv_.p, q2_.p, tl_binv_.p, tl_fail_.p);
+    DevBuf<double> A, X;
+    A.alloc((size_t)nagg * nagg, false); X.alloc((size_t)nagg * nagg, false);
+    XM_HIP_CHECK(hipMemsetAsync(A.p, 0, (size_t)nagg * nagg * sizeof(double), st));
+    hipLaunchKernelGGL(tl_coarse_entries_kernel, dim3((unsigned)((tl_nentries_ + 255) / 256)), dim3(256), 0, st, tl_nentries_, tl_cptr_.p, tl_cab_.p,
+                       tl_cpair_.p, tl_gslot_.p, tl_u_.p, q3inv_.p, tl_perm_.p, q2_.p, nagg, A.p);
+    check_launch("schur set-up (two-level preconditioner)");
+    int32_t fail = 0;
+    XM_HIP_CHECK(hipMemcpyAsync(&fail, tl_fail_.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    XM_HIP_CHECK(hipStreamSynchronize(st));
+    if (fail) throw Error(XM_ERR_ARG, "matrix-free Q: the reduced camera Laplacian is not positive definite (observation graph not connected?): a block of the two-level preconditioner");
+    if (nheavy_ > 0) {   // heavy landmarks in slot order (fixed): A_c -= (1/Q3_l) U U^T, U = the weights of l's observations by aggregate
+        std::vector<double> q3h((size_t)nheavy_);
+        XM_HIP_CHECK(hipMemcpyAsync(q3h.data(), q3inv_.p, (size_t)nheavy_ * sizeof(double), hipMemcpyDeviceToHost, st));
+        XM_HIP_CHECK(hipStreamSynchronize(st));
+        DevBuf<double> du;
+        du.alloc((size_t)nagg, false);
+        std::vector<double> u((size_t)nagg);
+        for (int64_t h = 0; h < nheavy_; ++h) {
+            if (q3h[(size_t)h] == 0.0) continue;
+            std::fill(u.begin(), u.end(), 0.0);
+            for (int64_t k = hub_obs_ptr_[(size_t)h]; k < hub_obs_ptr_[(size_t)h + 1]; ++k) {
+                const int64_t e = hub_obs_[(size_t)k];
+                if (hcam_[(size_t)e] != 0) u[(size_t)tl_agg_of_[(size_t)hcam_[(size_t)e]]] += w[e];
+            }
+            XM_HIP_CHECK(hipMemcpyAsync(du.p, u.data(), (size_t)nagg * sizeof(double), hipMemcpyHostToDevice, st));
+            rank1_sub_device((int)nagg, A.p, du.p, q3h[(size_t)h], st);
+            XM_HIP_CHECK(hipStreamSynchronize(st));   // u is reused
+        }
+    }
+    if (!spd_inverse_device((int)nagg, A.p, X.p, st))
+        throw Error(XM_ERR_ARG, "matrix-free Q: the reduced camera Laplacian is not positive definite (observation graph not connected?): the coarse operator of the two-level preconditioner");
+    spd_inverse_layout((int)nagg, X.p, tl_ainv_.p, nagg, st);
+    XM_HIP_CHECK(hipStreamSynchronize(st));
 }
 
 // residual of every observation at the point whose scaled rows are U (camera records of 3 * pitch_of(o) doubles):
@@ -977,6 +1366,7 @@ void SchurOp::ensure(int o) {
         pcg_r_.alloc(v); pcg_p_.alloc(v); pcg_ap_.alloc(v);
         pcg_grid_ = flat_grid(std::max<int64_t>(n_ - 1, 1));
         pcg_parts_.alloc(((size_t)4 * pcg_grid_ + (size_t)qw_grid((int)n_)) * (size_t)o + 16);
+        if (tl_) { tl_z_.alloc(v); tl_g_.alloc((size_t)std::max<int64_t>(tl_nagg_, 1) * o + 2); }
     }
     // VT^-1 is symmetric: from xm_tuning_t.sym_min_rows rows on (default 4096, the measured threshold of the dense solver) the chain applies it
     // with the half-traffic kernel (upper triangle only; o = 3, 4)
@@ -992,7 +1382,9 @@ void SchurOp::ensure(int o) {
 int64_t SchurOp::bytes_per_product(int o) const {
     // observation arrays are streamed twice by camera (w, landmark index; w, p, landmark index) and twice by landmark, VT^{-1} once
     // CG form: every iteration streams both observation lists once more (w + index each way); counted with the iterations of the last product
-    const int64_t inner = pcg_ ? (int64_t)std::max(1, pcg_last_iters_[1]) * (2 * nobs_ * (8 + 4)) : 8 * (n_ - 1) * (n_ - 1);
+    // (two-level preconditioner: + the block inverses and A_c^-1 once per iteration)
+    const int64_t tl_iter = tl_ ? tl_nagg_ * kSchurAggCams * kSchurAggCams * 8 + tl_nagg_ * tl_nagg_ * 8 : 0;
+    const int64_t inner = pcg_ ? (int64_t)std::max(1, pcg_last_iters_[1]) * (2 * nobs_ * (8 + 4) + tl_iter) : 8 * (n_ - 1) * (n_ - 1);
     return nobs_ * (8 + 4) + nobs_ * (8 + 24 + 4) + nobs_ * (8 + 24 + 4) + nobs_ * (8 + 4) + inner + 2LL * 8 * 3 * n_ * o;
 }
 
@@ -1051,7 +1443,10 @@ void SchurOp::product(int o, int epi, const double *W, double alpha, const CamAr
     // inner tolerance by the kind of product: the truncated CG tolerates a Hessian applied to 1e-9 (its own stop rule is a RELATIVE residual of
     // 1e-1 .. 1e-6, its recurrences never look at the true residual), the gradient that decides convergence and the certificate do not
     const int kind = (epi == EPI_HESS) ? 1 : 0;
-    if (pcg_) pcg = [&](const TcgScal *sc) { XM_DISPATCH_O(o, (pcg_solve<O_>(L, sc, st, kind))); };
+    if (pcg_) pcg = [&](const TcgScal *sc) {
+        if (tl_) { XM_DISPATCH_O(o, (pcg_solve<O_, true>(L, sc, st, kind))); }
+        else { XM_DISPATCH_O(o, (pcg_solve<O_, false>(L, sc, st, kind))); }
+    };
     XM_DISPATCH_O(o, (schur_product_o<O_>(epi, n_, nobs_, L, cam_ptr_.p, cam_lm_.p, cam_w_.p, cam_p_.p, Q1_.p,
                                          c_.p, q3inv_.p, vtinv_.p, nred_, ldv_, h_.p, r_.p, xc_.p, xl_.p, W, alpha, a, (vt_sym_ && !comm_) ? sym_prow_.p : (double *)nullptr, sym_pcol_.p, st,
                                          comm_, nred_loc_, pcg)));
@@ -1061,13 +1456,14 @@ void SchurOp::product(int o, int epi, const double *W, double alpha, const CamAr
 // x_cam = VT^-1 r by preconditioned CG (kernels above).  The iterations are enqueued in batches without looking at the device: as many as
 // the previous product needed (+ 2), then the host reads the state word and tops up in steps of 8 -- one host round trip per product in
 // the steady state, where consecutive right-hand sides of a truncated CG need the same number of iterations to within a few.
-template <int O>
+template <int O, bool TL>
 void SchurOp::pcg_solve(const SchurLm &L, const TcgScal *sc, hipStream_t st, int kind) {
     constexpr int OP = pitch_of(O);
     const int n1 = (int)(n_ - 1);
     PcgArgs a;
     a.n1 = n1; a.grid = pcg_grid_; a.tol2 = pcg_tol_[kind] * pcg_tol_[kind];
-    a.b = r_.p; a.dinv = pcg_dinv_.p; a.q2 = q2_.p;
+    a.b = r_.p; a.q2 = q2_.p;
+    if (TL) a.z = tl_z_.p; else a.dinv = pcg_dinv_.p;
     a.x = xc_.p; a.r = pcg_r_.p; a.p = pcg_p_.p; a.Ap = pcg_ap_.p;
     const size_t seg = (size_t)pcg_grid_ * O;
     a.prz[0] = pcg_parts_.p; a.prz[1] = pcg_parts_.p + seg; a.prr = pcg_parts_.p + 2 * seg; a.pbb = pcg_parts_.p + 3 * seg;
@@ -1076,18 +1472,29 @@ void SchurOp::pcg_solve(const SchurLm &L, const TcgScal *sc, hipStream_t st, int
     const dim3 b(256), gf(pcg_grid_), gc(a.cam_grid);
     const int64_t nlight = L.m - L.nheavy;
     const dim3 glm((unsigned)(L.nheavy + (nlight + kSchurHeavyThreads - 1) / kSchurHeavyThreads)), blm(kSchurHeavyThreads);
-    hipLaunchKernelGGL((pcg_init_kernel<O>), gf, b, 0, st, a, sc);
+    PcgTwoLevel t;
+    t.nagg = tl_nagg_; t.perm = tl_perm_.p; t.binv = tl_binv_.p; t.ainv = tl_ainv_.p; t.g = tl_g_.p; t.z = tl_z_.p;
+    const dim3 gb((unsigned)std::max<int64_t>(1, (tl_nagg_ + kQwWaves - 1) / kQwWaves));
+    auto precond = [&](int par, int init) {   // z = M^-1 r, <r, z> into parity par (init: p = z)
+        if constexpr (TL) {
+            hipLaunchKernelGGL((pcg_block_kernel<O>), gb, b, 0, st, a, t);
+            hipLaunchKernelGGL((pcg_coarse_kernel<O>), gf, b, 0, st, a, t, par, init);
+        }
+    };
+    hipLaunchKernelGGL((pcg_init_kernel<O, TL>), gf, b, 0, st, a, sc);
+    precond(0, 1);
     int it = 0, dir_applied = 0;   // dir_applied: the iteration whose direction update is already in the queue (iteration 0 needs none)
     auto enqueue = [&](int upto) {
         for (; it < upto; ++it) {
-            if (it != dir_applied) hipLaunchKernelGGL((pcg_dir_kernel<O>), gf, b, 0, st, a, it);
+            if (it != dir_applied) hipLaunchKernelGGL((pcg_dir_kernel<O, TL>), gf, b, 0, st, a, it);
             hipLaunchKernelGGL((pcg_lm_kernel<O>), glm, blm, 0, st, L, q3inv_.p, (const double *)a.p, (const PcgState *)a.st, xl_.p);
             hipLaunchKernelGGL((pcg_cam_kernel<O>), gc, b, 0, st, (int)n_, cam_ptr_.p, cam_lm_.p, cam_w_.p, (const double *)xl_.p, a);
-            hipLaunchKernelGGL((pcg_upd_kernel<O>), gf, b, 0, st, a, it);
+            hipLaunchKernelGGL((pcg_upd_kernel<O, TL>), gf, b, 0, st, a, it);
+            precond((it & 1) ^ 1, 0);
         }
         // the convergence test of the last update (no-op once done).  When the test fails the same launch IS the direction update of iteration
         // `it`: a following batch must not repeat it (p = z + beta (z + beta p) is no conjugate direction -- ADVICE r5)
-        hipLaunchKernelGGL((pcg_dir_kernel<O>), gf, b, 0, st, a, it);
+        hipLaunchKernelGGL((pcg_dir_kernel<O, TL>), gf, b, 0, st, a, it);
         dir_applied = it;
     };
     int target = std::min(pcg_max_iters_, std::max(4, pcg_last_iters_[kind] + 2));

@@ -42,6 +42,7 @@ struct Settings {
     bool schur_host_assembly = false, schur_trace = false;   // matrix-free storage (xm_schur.h: SchurSettings)
     int schur_pcg_first = 0, schur_pcg_hess_digits = 0;   // CG form of the matrix-free storage (xm_schur.h: SchurSettings)
     int schur_solver = 0;                 // 0 by size | 1 dense inverse of the reduced camera Laplacian | 2 preconditioned CG inside the product
+                                          // (Jacobi) | 3 CG with the two-level preconditioner
     int64_t schur_dense_max = 20000;
     int hess_f32 = 0;                     // 1: the tCG Hessian products of a dense single-rank context read an fp32 copy of Q (dQ32_)
     static Settings resolve(const xm_tuning_t *t);
@@ -204,6 +205,7 @@ public:
     const std::vector<double> &weights() const { return w_cur_; }
     int64_t n_landmarks() const;
     bool schur_info(int64_t out[3], double *relres) const;   // matrix-free storage with the CG form: products, inner iterations, products at the cap
+    int schur_precond(int64_t *aggregates, int *block) const; // its preconditioner: -1 no CG form, 0 Jacobi, 1 two-level (aggregates, cameras per aggregate)
 
 private:
     // ---- problem ------------------------------------------------------------------------------------------------

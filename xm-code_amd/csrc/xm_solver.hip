@@ -1818,6 +1818,13 @@ bool Context::schur_info(int64_t out[3], double *relres) const {
     schur_->pcg_stats(out, relres);
     return true;
 }
+int Context::schur_precond(int64_t *aggregates, int *block) const {
+    *aggregates = 0; *block = 0;
+    if (!schur_ || !schur_->uses_pcg()) return -1;
+    if (!schur_->two_level()) return 0;
+    *aggregates = schur_->aggregates(); *block = kSchurAggCams;
+    return 1;
+}
 
 // fp32 copy of the dense Q for the tCG's Hessian products, made on the device (nothing crosses the host link, also for a q_on_device context)
 void Context::refresh_q32() {

@@ -33,6 +33,7 @@ EXPORTS = [
     "xm_comm_unique_id", "xm_comm_init", "xm_comm_init_shm", "xm_comm_init_ipc", "xm_comm_finalize", "xm_partition", "xm_partition_blocks",
     "xm_symv_plan", "xm_sell_layout", "xm_sell_locality", "xm_sell_create", "xm_sell_create2", "xm_sell_quat_roundtrip", "xm_sell_destroy", "xm_qw_sell", "xm_qw_sell_padded",
     "xm_ctx_attach_edges", "xm_ctx_edge_residuals", "xm_ctx_edge_residuals_recovered", "xm_ctx_xm2_filter", "xm_ctx_xm2_round", "xm_ctx_set_edge_weights", "xm_ctx_recover_tp", "xm_ctx_schur_info", "xm_ctx_qw", "xm_spd_inverse", "xm_ctx_transport", "xm_ctx_sell_wpad", "xm_ctx_product_kind", "xm_symw_plan", "xm_symw_use",
+    "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
@@ -119,6 +120,8 @@ def lib():
         L.xm_ctx_recover_tp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_transport.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
         L.xm_ctx_schur_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_double)]
+        L.xm_ctx_schur_precond_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+        L.xm_schur_aggregate_plan.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.xm_ctx_sell_wpad.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.xm_ctx_product_kind.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.xm_bench_last_error.restype = C.c_char_p
@@ -406,6 +409,17 @@ def sell_locality(rowptr, colidx, ncols=None, slabs=4, lmax=64):
     return tuple(int(x) for x in out)
 
 
+def schur_aggregate_plan(cam, lm, n=None, B=64):
+    """aggregate of every camera in the two-level preconditioner of the matrix-free CG form (xm_tuning_t.schur_solver = 3), -1 for the
+    anchor camera 0 -- host only"""
+    cam = np.ascontiguousarray(cam, dtype=np.int32); lm = np.ascontiguousarray(lm, dtype=np.int32)
+    n = int(cam.max()) + 1 if n is None else int(n)
+    out = np.zeros(n, dtype=np.int32)
+    _chk(lib().xm_schur_aggregate_plan(n, cam.size, cam.ctypes.data_as(C.c_void_p), lm.ctypes.data_as(C.c_void_p), int(B),
+                                       out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 def symw_plan(ntot, nloc, cam0, K=0):
     """work list of one rank of the multi-rank symmetric window product (xm_symw.h) -- host only"""
     geom = np.zeros(8, dtype=np.int32)
@@ -565,10 +579,14 @@ class Context:
         return PRODUCT_KINDS.get(k.value, "?")
 
     def schur_info(self):
-        """matrix-free contexts: dict(cg=bool, products, inner_iters, capped, last_relres) (xm_ctx_schur_info)"""
+        """matrix-free contexts: dict(cg=bool, products, inner_iters, capped, last_relres, precond, aggregates) (xm_ctx_schur_info,
+        xm_ctx_schur_precond_info); precond: "jacobi" / "two-level" for the CG form, None otherwise"""
         u = C.c_int(0); st = (C.c_int64 * 3)(); rr = C.c_double(0.0)
         _chk(lib().xm_ctx_schur_info(self.h, C.byref(u), st, C.byref(rr)))
-        return dict(cg=bool(u.value), products=int(st[0]), inner_iters=int(st[1]), capped=int(st[2]), last_relres=rr.value)
+        kind = C.c_int(-1); na = C.c_int64(0); blk = C.c_int(0)
+        _chk(lib().xm_ctx_schur_precond_info(self.h, C.byref(kind), C.byref(na), C.byref(blk)))
+        return dict(cg=bool(u.value), products=int(st[0]), inner_iters=int(st[1]), capped=int(st[2]), last_relres=rr.value,
+                    precond={0: "jacobi", 1: "two-level"}.get(kind.value), aggregates=int(na.value))
 
     def sell_wpad(self):
         """True when the tCG of the last solved rank read its product input at the 128-byte record pitch (xm_ctx_sell_wpad)"""
