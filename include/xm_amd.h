@@ -329,6 +329,54 @@ int xm_ctx_schur_info(xm_ctx_t *ctx, int *uses_cg, int64_t stats[3], double *las
  * auto), 1 two-level (schur_solver 3; *aggregates = their number n_c, *block = cameras per aggregate).  aggregates / block may be NULL. */
 int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int *block);
 
+/* ---- reprojection bundle adjustment of a recovered solution (the reference's Ceres refinement, 5_test_ceres.py:610-616,
+ * utils/ceresforXM.py), on the device over the observation lists of an XM_STORAGE_SCHUR context.
+ *   parameters  camera i: Rcw_i = R_i^T, tcw_i = -R_i^T t_i (rot: 3 x 3n column-major, t: 3 x n, as xm_recover_rotations /
+ *               xm_ctx_recover_tp return them); landmark l: world point P_l (p: 3 x n_landmarks).  Host arrays, updated in place.
+ *   residual    r_e = pi(Rcw_i P_l + tcw_i) - (p_e0 / p_e2, p_e1 / p_e2), pi(X) = (X0 / X2, X1 / X2) (SIMPLE_PINHOLE, f = 1, c = 0),
+ *               cost F = 1/2 sum |r_e|^2 (unweighted) over the USED observations: current weight > 0 (XM^2-filtered ones drop out)
+ *               and p_e2 > 0.  Cameras and landmarks without a used observation come back bit-identical.
+ *   update      Rcw <- Exp(dtheta) Rcw (rotation vector, left), tcw += dt, P += dP; the gauge is free (no anchor, no scale).
+ *   step        Levenberg-Marquardt with Ceres's rules: (J^T J + mu D) d = -J^T r, D = diag(J^T J) clamped to [1e-6, 1e32], mu = 1 / radius,
+ *               radius 1e4 at the start; accepted when rho = (F - F_new) / model decrease > 1e-3 (radius /= max(1/3, 1 - (2 rho - 1)^3));
+ *               rejected: radius /= nu, nu *= 2.  Landmarks eliminated, the reduced camera system solved by PCG from zero with the
+ *               inverted diagonal camera blocks as preconditioner (ITERATIVE_SCHUR + SCHUR_JACOBI) to relative residual eta or 500
+ *               iterations.  Deviations from Ceres: monotonic steps only, no Jacobi scaling, no robust loss.
+ *   stops       |dF| / F <= function_tol on an accepted step; |J^T r|_inf <= gradient_tol (tangent coordinates); |d| <= parameter_tol
+ *               (|x| + parameter_tol) with |x|^2 = sum over used cameras of (1 for a free rotation + |tcw|^2) + sum |P|^2; max_iters; max_time
+ *               (seconds); radius < 1e-32.
+ * Options: struct_size = sizeof(xm_ba_options_t); max_iters, max_time, function_tol, gradient_tol, parameter_tol: 0 = the defaults
+ * (1000, 300, 1e-6, 1e-10, 1e-8); eta is required and lies in (0, 1) (Ceres's is 0.1).  trace: trace_cap x 6 doubles, one record per LM
+ * iteration: cost, candidate cost, mu, accepted (0 / 1), PCG iterations, PCG relative residual.
+ * XM_ERR_ARG (context unchanged and usable): not XM_STORAGE_SCHUR, several ranks or a communicator, a struct_size other than the
+ * library's, null arrays, non-finite input, eta outside (0, 1), negative settings, unknown flags.  The call reads the context and changes
+ * nothing in it (Q, weights, solver workspace). */
+#define XM_BA_FIX_ROTATIONS 1u          /* the reference's only_landmarks = True: rotations constant (bit-identical), t and P free */
+#define XM_BA_NO_CONVERGENCE       0
+#define XM_BA_CONVERGED_FUNCTION   1
+#define XM_BA_CONVERGED_GRADIENT   2
+#define XM_BA_CONVERGED_PARAMETER  3
+#define XM_BA_MAX_ITERATIONS       4
+#define XM_BA_TIME_LIMIT           5
+#define XM_BA_NO_PROGRESS          6    /* the trust-region radius fell below 1e-32 */
+typedef struct {
+    uint32_t struct_size;
+    int32_t max_iters;
+    double max_time, eta, function_tol, gradient_tol, parameter_tol;
+    uint32_t flags;            /* XM_BA_* */
+    int32_t trace_cap;
+    double *trace;
+} xm_ba_options_t;
+typedef struct {
+    uint32_t struct_size;
+    int32_t status;            /* XM_BA_* */
+    int32_t iters, accepted;   /* LM iterations, accepted steps */
+    int64_t pcg_iters, n_used; /* PCG iterations over all steps; observations in the cost */
+    double initial_cost, final_cost, gradient_max, seconds;
+    int32_t trace_len;
+} xm_ba_result_t;
+int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, xm_ba_result_t *res);
+
 /* ================================================================== 3. kernel-level entry points (device pointers) */
 /* device memory helpers so that callers need no other GPU runtime */
 int xm_dev_count(int *count);

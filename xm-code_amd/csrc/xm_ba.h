@@ -1,0 +1,49 @@
+// xm_ba.h — reprojection bundle adjustment of a recovered XM solution on the matrix-free storage.
+//
+// The reference refines the XM solution with Ceres (5_test_ceres.py:610-616, utils/ceresforXM.py): SIMPLE_PINHOLE with f = 1, c = 0,
+// one residual per observation r_e = pi(Rcw_i P_l + tcw_i) - (p_e0 / p_e2, p_e1 / p_e2), trivial loss, Levenberg-Marquardt with
+// ITERATIVE_SCHUR + SCHUR_JACOBI.  Here the same problem runs on the device over the observation lists the SchurOp already holds
+// (SchurLists): nothing of the observation structure is copied, only the per-observation Jacobians are stored (in both list orders).
+//
+// Per LM iteration (host loop, xm_ba.hip):
+//   eval        r_e, J_e = [J_c | J_P] at the current point (after an accepted step only)
+//   landmarks   V_l = sum J_P^T J_P, g_l = sum J_P^T r, (V_l + mu D_l)^-1                 thread per light landmark, workgroup per heavy one
+//   cameras     U_i, g_i, S_ii = U*_i - sum W V*^-1 W^T, its Cholesky inverse, b_i = -g_i + sum W V*^-1 g_l      wavefront per camera
+//   PCG         S dc = b from zero, S applied as U* x - sum W V*^-1 W^T x through the two lists, block-Jacobi preconditioner, batches that
+//               run ahead of the host and are polled through a state word (as SchurOp::pcg_solve)
+//   back-subst  dP_l = -V*_l^-1 (g_l + sum W^T dc)
+//   candidate   Rcw <- Exp(dtheta) Rcw, tcw += dt, P += dP; its cost and the model decrease; ONE read of the scalars by the host
+// Every sum over observations is a fixed-order sum (lane-strided lists + DPP trees, per-workgroup partials added in a fixed order): two
+// calls give the same bits.  f64 throughout.
+//
+// Deliberate deviations from Ceres: steps are monotonic only (the reference sets use_nonmonotonic_steps); no Jacobi column scaling of J;
+// no robust loss.  The rotation is the left-multiplied rotation vector (Ceres's quaternion Plus turns by 2|delta|: only the meaning of
+// gradient_tol differs).  |x| in the parameter tolerance counts 1 per free rotation (a unit quaternion) plus |tcw|^2 and |P|^2.
+#pragma once
+
+#include <cstdint>
+
+#include "xm_solver.h"
+
+namespace xm {
+
+class SchurOp;
+
+struct BaSettings {
+    int max_iters = 1000;
+    double max_time = 300.0, eta = 0.1, function_tol = 1e-6, gradient_tol = 1e-10, parameter_tol = 1e-8;
+    bool fix_rotations = false;   // XM_BA_FIX_ROTATIONS: camera blocks are the translation only (3 x 3)
+    int trace_cap = 0;
+    double *trace = nullptr;      // trace_cap x 6 row-major: cost, candidate cost, mu, accepted, PCG iterations, PCG relative residual
+    double watchdog_s = 600.0;    // host waits give up after this long
+};
+struct BaOutcome {
+    int status = 0, iters = 0, accepted = 0, trace_len = 0;
+    int64_t pcg_iters = 0, n_used = 0;
+    double initial_cost = 0, final_cost = 0, gradient_max = 0, seconds = 0;
+};
+
+// rot: 3 x 3n column-major (R_i, camera-to-world), t: 3 x n, p: 3 x m (host, updated in place).  The SchurOp is only read.
+void bundle_adjust(const SchurOp &S, const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out, hipStream_t st);
+
+}  // namespace xm

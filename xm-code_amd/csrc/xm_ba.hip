@@ -1,0 +1,863 @@
+// xm_ba.hip — reprojection bundle adjustment on the lists of the matrix-free storage (design: xm_ba.h).  CD = 6 (rotation vector +
+// translation per camera) or 3 (XM_BA_FIX_ROTATIONS: translation only).
+#include "xm_ba.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "xm_device.h"
+#include "xm_schur.h"
+
+namespace xm {
+
+namespace {
+
+constexpr int kBaHeavyThreads = 1024;   // a landmark with more than 64 observations: a workgroup of its own (as schur_lm_*)
+constexpr int kBaMaxPcgIters = 500;     // Ceres's max_linear_solver_iterations
+
+// per-observation record, one plane of `stride` doubles per entry: J_c (2 x CD, row-major), J_P (2 x 3), r (2)
+template <int CD> constexpr int ba_planes() { return 2 * CD + 8; }
+template <int CD> constexpr int ba_jp() { return 2 * CD; }
+template <int CD> constexpr int ba_res() { return 2 * CD + 6; }
+
+struct BaState {              // device-resident; the host reads it whole
+    int32_t done, iters;      // PCG: 1 = reached the tolerance; iterations performed
+    double relres;            // PCG: |r| / |b| when it stopped
+    double cost, used, gmax;  // at the current point: F, used observations, |J^T r|_inf
+    double cost_new, model;   // candidate: F, sum r.Jd + |Jd|^2 / 2
+    double step2[2], x2[2];   // |d|^2, |x|^2: cameras, landmarks
+};
+
+__device__ __forceinline__ double clamp_diag(double d) { return fmin(fmax(d, 1e-6), 1e32); }
+
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+template <int T>
+__device__ __forceinline__ double block_max(double v, double *sh) {   // result valid in thread 0
+    v = wave_max(v);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double m = 0.0;
+    if (threadIdx.x == 0)
+        for (int q = 0; q < T / 64; ++q) m = fmax(m, sh[q]);
+    return m;
+}
+// sum of K values over a heavy landmark's workgroup: DPP tree per wavefront, the 16 wavefront sums in a fixed order; valid in thread 0
+template <int K>
+__device__ __forceinline__ bool heavy_sum(double (&acc)[K]) {
+    __shared__ double part[kBaHeavyThreads / 64][K];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = wave_sum(acc[k]);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) part[wv][k] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return false;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double t = 0.0;
+        for (int q = 0; q < kBaHeavyThreads / 64; ++q) t += part[q][k];
+        acc[k] = t;
+    }
+    return true;
+}
+// the observations of landmark slot l in the by-landmark lists (heavy: workgroup-strided, light: the packed 64-wide group)
+struct LmRange {
+    int64_t l, e, e_end, step;
+    bool heavy, active;
+};
+__device__ __forceinline__ LmRange lm_range(const SchurLists &S) {
+    LmRange r;
+    r.heavy = (int64_t)blockIdx.x < S.nheavy;
+    r.active = true;
+    if (r.heavy) {
+        r.l = blockIdx.x; r.e = S.lm_ptr[r.l] + threadIdx.x; r.e_end = S.lm_ptr[r.l + 1]; r.step = kBaHeavyThreads;
+    } else {
+        const int64_t t = ((int64_t)blockIdx.x - S.nheavy) * kBaHeavyThreads + threadIdx.x;
+        r.l = S.nheavy + t; r.step = 64;
+        r.active = r.l < S.m;
+        r.e = r.active ? S.gbase[t >> 6] + (t & 63) : 0;
+        r.e_end = r.active ? r.e + (int64_t)64 * S.deg[r.l] : 0;
+    }
+    return r;
+}
+__device__ __forceinline__ bool obs_used(const double (&v)[6]) { return v[0] != 0.0 || v[1] != 0.0 || v[2] != 0.0; }   // J_P row 0 (never 0 when used)
+
+// ---- residuals and Jacobians at (Rcw, tcw, P), written in both list orders; partial sums of the cost and of the used observations
+template <int CD>
+__global__ __launch_bounds__(256) void ba_eval_kernel(SchurLists S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
+                                                      const double *__restrict__ P, double *__restrict__ Jc, double *__restrict__ Jl,
+                                                      double *__restrict__ parts) {
+    constexpr int NP = ba_planes<CD>(), JP = ba_jp<CD>(), RS = ba_res<CD>();
+    __shared__ double sh[4];
+    double cost = 0.0, used = 0.0;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < S.nobs; e += (int64_t)gridDim.x * 256) {
+        const int64_t pc = S.pos_c[e], pl = S.dpos_l[e];
+        const double w = S.cam_w[pc], q0 = S.obs_p[3 * e], q1 = S.obs_p[3 * e + 1], q2 = S.obs_p[3 * e + 2];
+        double v[NP];
+#pragma unroll
+        for (int k = 0; k < NP; ++k) v[k] = 0.0;
+        if (w > 0.0 && q2 > 0.0) {
+            const double *R = Rcw + (size_t)9 * S.obs_cam[e], *T = tcw + (size_t)3 * S.obs_cam[e], *X3 = P + (size_t)3 * S.obs_lm[e];
+            double Y[3], X[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                Y[a] = R[3 * a] * X3[0] + R[3 * a + 1] * X3[1] + R[3 * a + 2] * X3[2];
+                X[a] = Y[a] + T[a];
+            }
+            const double iz = 1.0 / X[2], u0 = X[0] / X[2], u1 = X[1] / X[2];
+            const double d[2][3] = {{iz, 0.0, -u0 * iz}, {0.0, iz, -u1 * iz}};   // d pi / d X
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) v[JP + 3 * r + k] = d[r][0] * R[k] + d[r][1] * R[3 + k] + d[r][2] * R[6 + k];   // d pi / dX . Rcw
+                if constexpr (CD == 6) {   // X = Exp(th) Y + t: dX / dth = -[Y]x
+                    v[6 * r + 0] = -d[r][1] * Y[2] + d[r][2] * Y[1];
+                    v[6 * r + 1] = d[r][0] * Y[2] - d[r][2] * Y[0];
+                    v[6 * r + 2] = -d[r][0] * Y[1] + d[r][1] * Y[0];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) v[6 * r + 3 + k] = d[r][k];
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) v[3 * r + k] = d[r][k];
+                }
+            }
+            v[RS] = u0 - q0 / q2;
+            v[RS + 1] = u1 - q1 / q2;
+            cost += 0.5 * (v[RS] * v[RS] + v[RS + 1] * v[RS + 1]);
+            used += 1.0;
+        }
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            Jc[(size_t)k * S.nobs + pc] = v[k];
+            Jl[(size_t)k * S.lm_total + pl] = v[k];
+        }
+    }
+    cost = block_sum256(cost, sh);
+    used = block_sum256(used, sh);
+    if (threadIdx.x == 0) { parts[blockIdx.x] = cost; parts[gridDim.x + blockIdx.x] = used; }
+}
+
+// ---- landmark pass: V_l, g_l, (V_l + mu D_l)^-1 (6 entries of the symmetric inverse), used flag; per-workgroup max of |g_l|_inf
+template <int CD>
+__global__ __launch_bounds__(kBaHeavyThreads) void ba_lm_kernel(SchurLists S, const double *__restrict__ Jl, double mu, double *__restrict__ vinv,
+                                                                double *__restrict__ gl, int32_t *__restrict__ lused, double *__restrict__ gpart) {
+    constexpr int JP = ba_jp<CD>(), RS = ba_res<CD>();
+    __shared__ double sh[kBaHeavyThreads / 64];
+    const LmRange q = lm_range(S);
+    double acc[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) acc[k] = 0.0;
+    for (int64_t e = q.e; e < q.e_end; e += q.step) {
+        double j[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) j[k] = Jl[(size_t)(JP + k) * S.lm_total + e];
+        const double r0 = Jl[(size_t)RS * S.lm_total + e], r1 = Jl[(size_t)(RS + 1) * S.lm_total + e];
+        acc[0] += j[0] * j[0] + j[3] * j[3]; acc[1] += j[0] * j[1] + j[3] * j[4]; acc[2] += j[0] * j[2] + j[3] * j[5];
+        acc[3] += j[1] * j[1] + j[4] * j[4]; acc[4] += j[1] * j[2] + j[4] * j[5]; acc[5] += j[2] * j[2] + j[5] * j[5];
+        acc[6] += j[0] * r0 + j[3] * r1; acc[7] += j[1] * r0 + j[4] * r1; acc[8] += j[2] * r0 + j[5] * r1;
+        acc[9] += obs_used(j) ? 1.0 : 0.0;
+    }
+    bool writer = q.active;
+    if (q.heavy) writer = heavy_sum<10>(acc);
+    double gabs = 0.0;
+    if (writer) {
+        const int64_t l = q.l;
+        const double a00 = acc[0] + mu * clamp_diag(acc[0]), a11 = acc[3] + mu * clamp_diag(acc[3]), a22 = acc[5] + mu * clamp_diag(acc[5]);
+        const double a01 = acc[1], a02 = acc[2], a12 = acc[4];
+        const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
+        const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
+        const double id = 1.0 / (a00 * c00 + a01 * c01 + a02 * c02);
+        double *vi = vinv + (size_t)6 * l;
+        vi[0] = c00 * id; vi[1] = c01 * id; vi[2] = c02 * id; vi[3] = c11 * id; vi[4] = c12 * id; vi[5] = c22 * id;
+        gl[3 * l] = acc[6]; gl[3 * l + 1] = acc[7]; gl[3 * l + 2] = acc[8];
+        lused[l] = acc[9] > 0.0 ? 1 : 0;
+        gabs = fmax(fabs(acc[6]), fmax(fabs(acc[7]), fabs(acc[8])));
+    }
+    if (q.heavy) {
+        if (writer) gpart[blockIdx.x] = gabs;
+        return;
+    }
+    const double m = block_max<kBaHeavyThreads>(gabs, sh);
+    if (threadIdx.x == 0) gpart[blockIdx.x] = m;
+}
+
+__device__ __forceinline__ void sym3(const double *vi, double (&V)[3][3]) {
+    V[0][0] = vi[0]; V[0][1] = V[1][0] = vi[1]; V[0][2] = V[2][0] = vi[2];
+    V[1][1] = vi[3]; V[1][2] = V[2][1] = vi[4]; V[2][2] = vi[5];
+}
+__device__ __forceinline__ constexpr int tri(int a, int b) { return a <= b ? b * (b + 1) / 2 + a : a * (a + 1) / 2 + b; }
+
+// A (CD x CD, symmetric positive definite) -> its inverse by Cholesky; not positive definite: the inverse of the diagonal
+template <int CD>
+__device__ void chol_inverse(const double (&A)[CD][CD], double *out) {
+    double L[CD][CD], Li[CD][CD];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < CD; ++j) {
+        double s = A[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
+        if (!(s > 0.0)) { ok = false; s = 1.0; }
+        L[j][j] = sqrt(s);
+#pragma unroll
+        for (int i = j + 1; i < CD; ++i) {
+            double t = A[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k];
+            L[i][j] = t / L[j][j];
+        }
+    }
+    if (!ok) {
+#pragma unroll
+        for (int i = 0; i < CD; ++i)
+#pragma unroll
+            for (int j = 0; j < CD; ++j) out[CD * i + j] = (i == j && A[i][i] > 0.0) ? 1.0 / A[i][i] : 0.0;
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < CD; ++j) {
+        Li[j][j] = 1.0 / L[j][j];
+#pragma unroll
+        for (int i = j + 1; i < CD; ++i) {
+            double t = 0.0;
+#pragma unroll
+            for (int k = j; k < i; ++k) t += L[i][k] * Li[k][j];
+            Li[i][j] = -t / L[i][i];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < CD; ++i)
+#pragma unroll
+        for (int j = 0; j < CD; ++j) {
+            double t = 0.0;
+#pragma unroll
+            for (int k = (i > j ? i : j); k < CD; ++k) t += Li[k][i] * Li[k][j];
+            out[CD * i + j] = t;
+        }
+}
+
+// ---- camera pass (a wavefront per camera): U_i, g_i; S_ii = U*_i - sum W V*^-1 W^T and its inverse; b_i = -g_i + sum W V*^-1 g_l
+template <int CD>
+__global__ __launch_bounds__(256) void ba_cam_kernel(SchurLists S, const double *__restrict__ Jc, const double *__restrict__ vinv,
+                                                     const double *__restrict__ gl, double mu, double *__restrict__ ustar, double *__restrict__ sinv,
+                                                     double *__restrict__ b, int32_t *__restrict__ cused, double *__restrict__ gpart) {
+    constexpr int JP = ba_jp<CD>(), RS = ba_res<CD>(), NU = CD * (CD + 1) / 2, NA = 2 * NU + 2 * CD + 1;
+    __shared__ double red[kQwWaves];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t cam = (int64_t)blockIdx.x * kQwWaves + wv;
+    const bool on = cam < S.n;
+    double acc[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k) acc[k] = 0.0;
+    if (on)
+        for (int64_t e = S.cam_ptr[cam] + lane; e < S.cam_ptr[cam + 1]; e += 64) {
+            double jc[2 * CD], jp[6];
+#pragma unroll
+            for (int k = 0; k < 2 * CD; ++k) jc[k] = Jc[(size_t)k * S.nobs + e];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) jp[k] = Jc[(size_t)(JP + k) * S.nobs + e];
+            const double r0 = Jc[(size_t)RS * S.nobs + e], r1 = Jc[(size_t)(RS + 1) * S.nobs + e];
+            const int64_t l = S.cam_lm[e];
+            double V[3][3], W[CD][3], WV[CD][3];
+            sym3(vinv + (size_t)6 * l, V);
+            const double g0 = gl[3 * l], g1 = gl[3 * l + 1], g2 = gl[3 * l + 2];
+#pragma unroll
+            for (int k = 0; k < CD; ++k)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) W[k][c] = jc[k] * jp[c] + jc[CD + k] * jp[3 + c];
+#pragma unroll
+            for (int k = 0; k < CD; ++k)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) WV[k][c] = W[k][0] * V[0][c] + W[k][1] * V[1][c] + W[k][2] * V[2][c];
+#pragma unroll
+            for (int j = 0; j < CD; ++j)
+#pragma unroll
+                for (int k = 0; k <= j; ++k) {
+                    acc[tri(k, j)] += jc[k] * jc[j] + jc[CD + k] * jc[CD + j];
+                    acc[NU + tri(k, j)] += WV[k][0] * W[j][0] + WV[k][1] * W[j][1] + WV[k][2] * W[j][2];
+                }
+#pragma unroll
+            for (int k = 0; k < CD; ++k) {
+                acc[2 * NU + k] += jc[k] * r0 + jc[CD + k] * r1;
+                acc[2 * NU + CD + k] += WV[k][0] * g0 + WV[k][1] * g1 + WV[k][2] * g2;
+            }
+            acc[NA - 1] += obs_used(jp) ? 1.0 : 0.0;
+        }
+#pragma unroll
+    for (int k = 0; k < NA; ++k) acc[k] = wave_sum(acc[k]);
+    double gabs = 0.0;
+    if (on && lane == 0) {
+        double Us[CD][CD], Sm[CD][CD];
+#pragma unroll
+        for (int j = 0; j < CD; ++j)
+#pragma unroll
+            for (int k = 0; k < CD; ++k) {
+                const double u = acc[tri(k, j)];
+                Us[j][k] = (j == k) ? u + mu * clamp_diag(u) : u;
+                Sm[j][k] = Us[j][k] - acc[NU + tri(k, j)];
+            }
+        double *us = ustar + (size_t)CD * CD * cam;
+#pragma unroll
+        for (int j = 0; j < CD; ++j)
+#pragma unroll
+            for (int k = 0; k < CD; ++k) us[CD * j + k] = Us[j][k];
+        chol_inverse<CD>(Sm, sinv + (size_t)CD * CD * cam);
+#pragma unroll
+        for (int k = 0; k < CD; ++k) {
+            b[(size_t)CD * cam + k] = -acc[2 * NU + k] + acc[2 * NU + CD + k];
+            gabs = fmax(gabs, fabs(acc[2 * NU + k]));
+        }
+        cused[cam] = acc[NA - 1] > 0.0 ? 1 : 0;
+    }
+    if (lane == 0) red[wv] = gabs;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double m = 0.0;
+        for (int q = 0; q < kQwWaves; ++q) m = fmax(m, red[q]);
+        gpart[blockIdx.x] = m;
+    }
+}
+
+// ---- PCG on S dc = b (vectors: CD per camera).  Same scheme as SchurOp::pcg_solve: per-workgroup partials, every workgroup of the flat
+// kernels sums them in the same fixed order, the direction kernel decides convergence and publishes it through the state word
+struct BaPcg {
+    int64_t n;
+    int grid, cgrid;
+    double tol2;
+    const double *b, *sinv, *ustar;
+    double *x, *r, *z, *p, *Ap;
+    double *prz[2], *prr, *pbb, *ppap;
+    BaState *st;
+};
+template <int CD>
+__device__ __forceinline__ void block_matvec(const double *M, const double *v, double (&out)[CD]) {
+#pragma unroll
+    for (int j = 0; j < CD; ++j) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < CD; ++k) t += M[CD * j + k] * v[k];
+        out[j] = t;
+    }
+}
+template <int CD>
+__global__ __launch_bounds__(256) void ba_pcg_init_kernel(BaPcg a) {
+    __shared__ double sh[4];
+    double rz = 0.0, bb = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
+        double v[CD], z[CD];
+#pragma unroll
+        for (int k = 0; k < CD; ++k) v[k] = a.b[CD * i + k];
+        block_matvec<CD>(a.sinv + (size_t)CD * CD * i, v, z);
+#pragma unroll
+        for (int k = 0; k < CD; ++k) {
+            a.x[CD * i + k] = 0.0; a.r[CD * i + k] = v[k]; a.z[CD * i + k] = z[k]; a.p[CD * i + k] = z[k];
+            rz += v[k] * z[k]; bb += v[k] * v[k];
+        }
+    }
+    rz = block_sum256(rz, sh);
+    bb = block_sum256(bb, sh);
+    if (threadIdx.x == 0) { a.prz[0][blockIdx.x] = rz; a.pbb[blockIdx.x] = bb; a.prr[blockIdx.x] = bb; }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { a.st->done = 0; a.st->iters = 0; a.st->relres = 1.0; }
+}
+// iteration it >= 1: convergence test of the last update, else beta = <r,z>_new / <r,z>_old and p = z + beta p
+template <int CD>
+__global__ __launch_bounds__(256) void ba_pcg_dir_kernel(BaPcg a, int it) {
+    __shared__ double sh[4];
+    __shared__ int was_done;
+    if (threadIdx.x == 0) was_done = a.st->done;
+    __syncthreads();
+    if (was_done) return;
+    const double rzn = sum_partials256(a.prz[it & 1], a.grid, sh), rzo = sum_partials256(a.prz[(it & 1) ^ 1], a.grid, sh);
+    const double rr = sum_partials256(a.prr, a.grid, sh), bb = sum_partials256(a.pbb, a.grid, sh);
+    const double q = bb > 0.0 ? rr / bb : 0.0;
+    if (q <= a.tol2) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { a.st->done = 1; a.st->iters = it; a.st->relres = sqrt(q); }
+        return;
+    }
+    const double beta = rzo > 0.0 ? rzn / rzo : 0.0;
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < a.n * CD; j += (int64_t)gridDim.x * 256) a.p[j] = a.z[j] + beta * a.p[j];
+    if (blockIdx.x == 0 && threadIdx.x == 0) { a.st->iters = it; a.st->relres = sqrt(q); }
+}
+// landmark side of S x (and of the back-substitution): y_l = sgn V*_l^-1 (g_l + sum_{obs of l} J_P^T J_c x_i)   (g: optional)
+template <int CD>
+__global__ __launch_bounds__(kBaHeavyThreads) void ba_lmx_kernel(SchurLists S, const double *__restrict__ Jl, const double *__restrict__ vinv,
+                                                                 const double *__restrict__ gl, double sgn, const int32_t *__restrict__ lused,
+                                                                 const double *__restrict__ x, const BaState *__restrict__ st, double *__restrict__ y) {
+    constexpr int JP = ba_jp<CD>();
+    if (st != nullptr && st->done) return;
+    const LmRange q = lm_range(S);
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int64_t e = q.e; e < q.e_end; e += q.step) {
+        double jc[2 * CD], jp[6];
+#pragma unroll
+        for (int k = 0; k < 2 * CD; ++k) jc[k] = Jl[(size_t)k * S.lm_total + e];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) jp[k] = Jl[(size_t)(JP + k) * S.lm_total + e];
+        const double *xi = x + (size_t)CD * S.lm_cam[e];
+        double u0 = 0.0, u1 = 0.0;
+#pragma unroll
+        for (int k = 0; k < CD; ++k) { u0 += jc[k] * xi[k]; u1 += jc[CD + k] * xi[k]; }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += jp[c] * u0 + jp[3 + c] * u1;
+    }
+    bool writer = q.active;
+    if (q.heavy) writer = heavy_sum<3>(acc);
+    if (!writer) return;
+    const int64_t l = q.l;
+    if (!lused[l]) { y[3 * l] = y[3 * l + 1] = y[3 * l + 2] = 0.0; return; }
+    if (gl != nullptr) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += gl[3 * l + c];
+    }
+    double V[3][3];
+    sym3(vinv + (size_t)6 * l, V);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) y[3 * l + c] = sgn * (V[c][0] * acc[0] + V[c][1] * acc[1] + V[c][2] * acc[2]);
+}
+// camera side: Ap_i = U*_i p_i - sum_{obs of i} J_c^T J_P y_l (a wavefront per camera); per-workgroup partials of <p, Ap>
+template <int CD>
+__global__ __launch_bounds__(256) void ba_camx_kernel(SchurLists S, const double *__restrict__ Jc, const double *__restrict__ y, BaPcg a) {
+    constexpr int JP = ba_jp<CD>();
+    __shared__ double red[kQwWaves];
+    if (a.st->done) return;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t cam = (int64_t)blockIdx.x * kQwWaves + wv;
+    const bool on = cam < S.n;
+    double acc[CD];
+#pragma unroll
+    for (int k = 0; k < CD; ++k) acc[k] = 0.0;
+    if (on)
+        for (int64_t e = S.cam_ptr[cam] + lane; e < S.cam_ptr[cam + 1]; e += 64) {
+            double jc[2 * CD], jp[6];
+#pragma unroll
+            for (int k = 0; k < 2 * CD; ++k) jc[k] = Jc[(size_t)k * S.nobs + e];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) jp[k] = Jc[(size_t)(JP + k) * S.nobs + e];
+            const double *yl = y + (size_t)3 * S.cam_lm[e];
+            const double v0 = jp[0] * yl[0] + jp[1] * yl[1] + jp[2] * yl[2], v1 = jp[3] * yl[0] + jp[4] * yl[1] + jp[5] * yl[2];
+#pragma unroll
+            for (int k = 0; k < CD; ++k) acc[k] += jc[k] * v0 + jc[CD + k] * v1;
+        }
+#pragma unroll
+    for (int k = 0; k < CD; ++k) acc[k] = wave_sum(acc[k]);
+    double pap = 0.0;
+    if (on && lane == 0) {
+        double up[CD];
+        block_matvec<CD>(a.ustar + (size_t)CD * CD * cam, a.p + (size_t)CD * cam, up);
+#pragma unroll
+        for (int k = 0; k < CD; ++k) {
+            const double v = up[k] - acc[k];
+            a.Ap[CD * cam + k] = v;
+            pap += a.p[CD * cam + k] * v;
+        }
+    }
+    if (lane == 0) red[wv] = pap;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int q = 0; q < kQwWaves; ++q) t += red[q];
+        a.ppap[blockIdx.x] = t;
+    }
+}
+// alpha = <r,z> / <p,Ap>; x += alpha p, r -= alpha Ap, z = S_ii^-1 r; partials of the new <r,z> (other parity) and |r|^2
+template <int CD>
+__global__ __launch_bounds__(256) void ba_pcg_upd_kernel(BaPcg a, int it) {
+    __shared__ double sh[4];
+    if (a.st->done) return;
+    const double rz = sum_partials256(a.prz[it & 1], a.grid, sh), pap = sum_partials256(a.ppap, a.cgrid, sh);
+    const double alpha = (pap > 0.0 && rz > 0.0) ? rz / pap : 0.0;
+    double rzn = 0.0, rr = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
+        double rn[CD], z[CD];
+#pragma unroll
+        for (int k = 0; k < CD; ++k) {
+            const size_t j = (size_t)CD * i + k;
+            a.x[j] += alpha * a.p[j];
+            rn[k] = a.r[j] - alpha * a.Ap[j];
+            a.r[j] = rn[k];
+        }
+        block_matvec<CD>(a.sinv + (size_t)CD * CD * i, rn, z);
+#pragma unroll
+        for (int k = 0; k < CD; ++k) {
+            a.z[CD * i + k] = z[k];
+            rzn += rn[k] * z[k]; rr += rn[k] * rn[k];
+        }
+    }
+    rzn = block_sum256(rzn, sh);
+    rr = block_sum256(rr, sh);
+    if (threadIdx.x == 0) { a.prz[(it & 1) ^ 1][blockIdx.x] = rzn; a.prr[blockIdx.x] = rr; }
+}
+
+// ---- candidate point.  Cameras: Rcw <- Exp(dtheta) Rcw (Rodrigues), tcw += dt; cameras without a used observation are copied.
+template <int CD>
+__global__ __launch_bounds__(256) void ba_cand_cam_kernel(int64_t n, const double *__restrict__ Rcw, const double *__restrict__ tcw,
+                                                          const double *__restrict__ dc, const int32_t *__restrict__ cused, double *__restrict__ Rn,
+                                                          double *__restrict__ tn, double *__restrict__ parts) {
+    __shared__ double sh[4];
+    double s2 = 0.0, x2 = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double *R = Rcw + 9 * i, *T = tcw + 3 * i, *d = dc + CD * i;
+        if (!cused[i]) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) Rn[9 * i + k] = R[k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) tn[3 * i + k] = T[k];
+            continue;
+        }
+        const double *dt = d + (CD == 6 ? 3 : 0);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { tn[3 * i + k] = T[k] + dt[k]; x2 += T[k] * T[k]; }
+#pragma unroll
+        for (int k = 0; k < CD; ++k) s2 += d[k] * d[k];
+        if constexpr (CD == 6) {
+            x2 += 1.0;   // the unit quaternion of the rotation
+            const double w0 = d[0], w1 = d[1], w2 = d[2], th2 = w0 * w0 + w1 * w1 + w2 * w2;
+            double A, B;
+            if (th2 < 1e-16) { A = 1.0 - th2 / 6.0; B = 0.5 - th2 / 24.0; }
+            else { const double th = sqrt(th2); A = sin(th) / th; B = (1.0 - cos(th)) / th2; }
+            const double K[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
+            double E[3][3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) E[a][c] = (a == c ? 1.0 : 0.0) + A * K[a][c] + B * (K[a][0] * K[0][c] + K[a][1] * K[1][c] + K[a][2] * K[2][c]);
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) Rn[9 * i + 3 * a + c] = E[a][0] * R[c] + E[a][1] * R[3 + c] + E[a][2] * R[6 + c];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) Rn[9 * i + k] = R[k];
+        }
+    }
+    s2 = block_sum256(s2, sh);
+    x2 = block_sum256(x2, sh);
+    if (threadIdx.x == 0) { parts[blockIdx.x] = s2; parts[gridDim.x + blockIdx.x] = x2; }
+}
+__global__ __launch_bounds__(256) void ba_cand_lm_kernel(int64_t m, const double *__restrict__ P, const double *__restrict__ dP,
+                                                         const int32_t *__restrict__ lused, double *__restrict__ Pn, double *__restrict__ parts) {
+    __shared__ double sh[4];
+    double s2 = 0.0, x2 = 0.0;
+    for (int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x; l < m; l += (int64_t)gridDim.x * 256) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double v = P[3 * l + k];
+            if (lused[l]) { Pn[3 * l + k] = v + dP[3 * l + k]; s2 += dP[3 * l + k] * dP[3 * l + k]; x2 += v * v; }
+            else Pn[3 * l + k] = v;
+        }
+    }
+    s2 = block_sum256(s2, sh);
+    x2 = block_sum256(x2, sh);
+    if (threadIdx.x == 0) { parts[blockIdx.x] = s2; parts[gridDim.x + blockIdx.x] = x2; }
+}
+// cost at the candidate and the linear model's terms sum r.(J d) + |J d|^2 / 2 (J, r: the current point, by-camera order)
+template <int CD>
+__global__ __launch_bounds__(256) void ba_cost_kernel(SchurLists S, const double *__restrict__ Rn, const double *__restrict__ tn,
+                                                      const double *__restrict__ Pn, const double *__restrict__ Jc, const double *__restrict__ dc,
+                                                      const double *__restrict__ dP, double *__restrict__ parts) {
+    constexpr int JP = ba_jp<CD>(), RS = ba_res<CD>();
+    __shared__ double sh[4];
+    double cost = 0.0, model = 0.0;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < S.nobs; e += (int64_t)gridDim.x * 256) {
+        const int64_t pc = S.pos_c[e];
+        const double w = S.cam_w[pc], q0 = S.obs_p[3 * e], q1 = S.obs_p[3 * e + 1], q2 = S.obs_p[3 * e + 2];
+        if (!(w > 0.0 && q2 > 0.0)) continue;
+        const int64_t i = S.obs_cam[e], l = S.obs_lm[e];
+        const double *R = Rn + 9 * i, *T = tn + 3 * i, *X3 = Pn + 3 * l;
+        double X[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) X[a] = R[3 * a] * X3[0] + R[3 * a + 1] * X3[1] + R[3 * a + 2] * X3[2] + T[a];
+        const double e0 = X[0] / X[2] - q0 / q2, e1 = X[1] / X[2] - q1 / q2;
+        cost += 0.5 * (e0 * e0 + e1 * e1);
+        double jd0 = 0.0, jd1 = 0.0;
+#pragma unroll
+        for (int k = 0; k < CD; ++k) {
+            jd0 += Jc[(size_t)k * S.nobs + pc] * dc[CD * i + k];
+            jd1 += Jc[(size_t)(CD + k) * S.nobs + pc] * dc[CD * i + k];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            jd0 += Jc[(size_t)(JP + c) * S.nobs + pc] * dP[3 * l + c];
+            jd1 += Jc[(size_t)(JP + 3 + c) * S.nobs + pc] * dP[3 * l + c];
+        }
+        const double r0 = Jc[(size_t)RS * S.nobs + pc], r1 = Jc[(size_t)(RS + 1) * S.nobs + pc];
+        model += r0 * jd0 + r1 * jd1 + 0.5 * (jd0 * jd0 + jd1 * jd1);
+    }
+    cost = block_sum256(cost, sh);
+    model = block_sum256(model, sh);
+    if (threadIdx.x == 0) { parts[blockIdx.x] = cost; parts[gridDim.x + blockIdx.x] = model; }
+}
+// scalars of the state word from the partials, in a fixed order (one workgroup): up to 6 sums and one max
+constexpr int kBaSums = 6;
+struct BaReduce {
+    const double *sum_p[kBaSums];
+    int sum_n[kBaSums];
+    double *sum_out[kBaSums];
+    const double *max_p;
+    int max_n;
+    double *max_out;
+};
+__global__ __launch_bounds__(256) void ba_reduce_kernel(BaReduce r) {
+    __shared__ double sh[4];
+    __shared__ double shm[4];
+    for (int k = 0; k < kBaSums; ++k) {
+        if (r.sum_out[k] == nullptr) continue;
+        const double v = sum_partials256(r.sum_p[k], r.sum_n[k], sh);
+        if (threadIdx.x == 0) *r.sum_out[k] = v;
+    }
+    if (r.max_out != nullptr) {
+        double m = 0.0;
+        for (int i = threadIdx.x; i < r.max_n; i += 256) m = fmax(m, r.max_p[i]);
+        m = block_max<256>(m, shm);
+        if (threadIdx.x == 0) *r.max_out = m;
+    }
+}
+
+double secs_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); }
+
+// host wait on the stream, bounded by the watchdog
+void wait_stream(hipStream_t st, double limit, const char *what) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+        const hipError_t q = hipStreamQuery(st);
+        if (q == hipSuccess) return;
+        if (q != hipErrorNotReady) {
+            (void)hipGetLastError();
+            throw Error(XM_ERR_HIP, std::string("bundle adjustment: device error while waiting for ") + what + ": " + hipGetErrorString(q));
+        }
+        if (secs_since(t0) > limit)
+            throw Error(XM_ERR_HIP, std::string("bundle adjustment: watchdog: no progress for ") + std::to_string((int)limit) + " s while waiting for " + what);
+        std::this_thread::yield();
+    }
+}
+
+struct PinnedState {
+    BaState *h = nullptr;
+    PinnedState() { XM_HIP_CHECK(hipHostMalloc((void **)&h, sizeof(BaState), hipHostMallocDefault)); }
+    ~PinnedState() { if (h) (void)hipHostFree(h); }
+};
+
+template <int CD>
+void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out, hipStream_t st) {
+    const auto t_start = std::chrono::steady_clock::now();
+    const SchurLists S = SO.lists();
+    const std::vector<int32_t> &slot_of = SO.slot_of();
+    const int64_t n = S.n, m = S.m, nobs = S.nobs;
+    constexpr int NP = ba_planes<CD>();
+    // ---- parameters on the device: Rcw = R_i^T (row-major), tcw = -R_i^T t_i, P by landmark slot
+    std::vector<double> hR((size_t)9 * n), hT((size_t)3 * n), hP((size_t)3 * m);
+    for (int64_t i = 0; i < n; ++i) {
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) hR[(size_t)9 * i + 3 * a + c] = rot[(size_t)c + 3 * ((size_t)3 * i + a)];
+        for (int a = 0; a < 3; ++a) {
+            double s = 0.0;
+            for (int c = 0; c < 3; ++c) s += hR[(size_t)9 * i + 3 * a + c] * t[(size_t)3 * i + c];
+            hT[(size_t)3 * i + a] = -s;
+        }
+    }
+    for (int64_t l = 0; l < m; ++l)
+        for (int a = 0; a < 3; ++a) hP[(size_t)3 * slot_of[(size_t)l] + a] = p[(size_t)3 * l + a];
+    DevBuf<double> R[2], T[2], P[2];
+    for (int k = 0; k < 2; ++k) { R[k].alloc((size_t)9 * n, false); T[k].alloc((size_t)3 * n, false); P[k].alloc((size_t)3 * m, false); }
+    XM_HIP_CHECK(hipMemcpyAsync(R[0].p, hR.data(), hR.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    XM_HIP_CHECK(hipMemcpyAsync(T[0].p, hT.data(), hT.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    XM_HIP_CHECK(hipMemcpyAsync(P[0].p, hP.data(), hP.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    // ---- workspace (zero: the padding of the packed landmark lists stays 0 in every plane)
+    DevBuf<double> Jc, Jl, vinv, gl, ustar, sinv, b, x, r, z, pv, Ap, y, dP, parts;
+    DevBuf<int32_t> lused, cused, state_buf;
+    Jc.alloc((size_t)NP * nobs); Jl.alloc((size_t)NP * S.lm_total);
+    vinv.alloc((size_t)6 * m); gl.alloc((size_t)3 * m); y.alloc((size_t)3 * m); dP.alloc((size_t)3 * m); lused.alloc((size_t)m);
+    ustar.alloc((size_t)CD * CD * n); sinv.alloc((size_t)CD * CD * n); cused.alloc((size_t)n);
+    for (DevBuf<double> *v : {&b, &x, &r, &z, &pv, &Ap}) v->alloc((size_t)CD * n);
+    state_buf.alloc(sizeof(BaState) / sizeof(int32_t) + 2);
+    BaState *dst = reinterpret_cast<BaState *>(state_buf.p);
+    PinnedState hs;
+    const int ge = flat_grid(nobs), gfc = flat_grid(n), gfl = flat_grid(m), gcam = qw_grid((int)n);
+    const int glm = (int)(S.nheavy + (m - S.nheavy + kBaHeavyThreads - 1) / kBaHeavyThreads);
+    // partials: eval (2 ge) | gmax (glm + gcam) | PCG (4 gfc + gcam) | candidate step / |x| (cameras then landmarks, 2 x (gfc + gfl)) | cost (2 ge)
+    const size_t o_eval = 0, o_gmax = o_eval + 2 * (size_t)ge, o_pcg = o_gmax + glm + gcam, o_cand = o_pcg + 4 * (size_t)gfc + gcam,
+                 o_cost = o_cand + 2 * ((size_t)gfc + gfl), n_parts = o_cost + 2 * (size_t)ge;
+    parts.alloc(n_parts);
+    double *pp = parts.p;
+    const dim3 b256(256), blm(kBaHeavyThreads);
+    auto reduce = [&](BaReduce rd) { hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), b256, 0, st, rd); };
+    auto read_state = [&](const char *what) {
+        check_launch(what);
+        XM_HIP_CHECK(hipMemcpyAsync(hs.h, dst, sizeof(BaState), hipMemcpyDeviceToHost, st));
+        wait_stream(st, cfg.watchdog_s, what);
+        return *hs.h;
+    };
+    int cur = 0;
+    auto eval = [&]() {
+        hipLaunchKernelGGL((ba_eval_kernel<CD>), dim3(ge), b256, 0, st, S, R[cur].p, T[cur].p, P[cur].p, Jc.p, Jl.p, pp + o_eval);
+        BaReduce rd{};
+        rd.sum_p[0] = pp + o_eval; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->cost;
+        rd.sum_p[1] = pp + o_eval + ge; rd.sum_n[1] = ge; rd.sum_out[1] = &dst->used;
+        reduce(rd);
+    };
+    auto passes = [&](double mu) {
+        hipLaunchKernelGGL((ba_lm_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, mu, vinv.p, gl.p, lused.p, pp + o_gmax);
+        hipLaunchKernelGGL((ba_cam_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)vinv.p, (const double *)gl.p, mu,
+                           ustar.p, sinv.p, b.p, cused.p, pp + o_gmax + glm);
+        BaReduce rd{};
+        rd.max_p = pp + o_gmax; rd.max_n = glm + gcam; rd.max_out = &dst->gmax;
+        reduce(rd);
+    };
+    BaPcg a;
+    a.n = n; a.grid = gfc; a.cgrid = gcam; a.tol2 = cfg.eta * cfg.eta;
+    a.b = b.p; a.sinv = sinv.p; a.ustar = ustar.p; a.x = x.p; a.r = r.p; a.z = z.p; a.p = pv.p; a.Ap = Ap.p;
+    a.prz[0] = pp + o_pcg; a.prz[1] = pp + o_pcg + gfc; a.prr = pp + o_pcg + 2 * gfc; a.pbb = pp + o_pcg + 3 * gfc; a.ppap = pp + o_pcg + 4 * gfc;
+    a.st = dst;
+    int pcg_last = 8;
+    // PCG from zero: batches enqueued ahead of the host (as many iterations as the last solve needed + 2, then steps of 8), one read per batch
+    auto pcg = [&](int &iters, double &relres) {
+        hipLaunchKernelGGL((ba_pcg_init_kernel<CD>), dim3(gfc), b256, 0, st, a);
+        int it = 0, dir_applied = 0;
+        auto enqueue = [&](int upto) {
+            for (; it < upto; ++it) {
+                if (it != dir_applied) hipLaunchKernelGGL((ba_pcg_dir_kernel<CD>), dim3(gfc), b256, 0, st, a, it);
+                hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)nullptr, 1.0,
+                                   (const int32_t *)lused.p, (const double *)pv.p, (const BaState *)dst, y.p);
+                hipLaunchKernelGGL((ba_camx_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)y.p, a);
+                hipLaunchKernelGGL((ba_pcg_upd_kernel<CD>), dim3(gfc), b256, 0, st, a, it);
+            }
+            hipLaunchKernelGGL((ba_pcg_dir_kernel<CD>), dim3(gfc), b256, 0, st, a, it);   // convergence test of the last update (or the next direction)
+            dir_applied = it;
+        };
+        int target = std::min(kBaMaxPcgIters, std::max(4, pcg_last + 2));
+        BaState s;
+        for (;;) {
+            enqueue(target);
+            s = read_state("the reduced camera PCG");
+            if (s.done || target >= kBaMaxPcgIters) break;
+            target = std::min(kBaMaxPcgIters, target + 8);
+        }
+        iters = s.done ? s.iters : target;
+        relres = s.relres;
+        if (s.done && s.iters > 0) pcg_last = s.iters;
+    };
+
+    double radius = 1e4, nu = 2.0, F = 0.0, gmax = 0.0;
+    int status = XM_BA_NO_CONVERGENCE, iters = 0, accepted = 0, tl = 0;
+    int64_t pcg_total = 0;
+    bool fresh = true, first = true;   // fresh: the point changed and its cost / gradient have not been read yet
+    eval();
+    for (;;) {
+        const double mu = 1.0 / radius;
+        passes(mu);
+        if (fresh) {
+            const BaState s = read_state("the cost and gradient");
+            F = s.cost; gmax = s.gmax;
+            if (first) {
+                if (!std::isfinite(F)) throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: the initial reprojection cost is not finite (a point on a camera's focal plane?)");
+                out.initial_cost = F; out.n_used = (int64_t)s.used;
+                first = false;
+            }
+            fresh = false;
+            if (gmax <= cfg.gradient_tol) { status = XM_BA_CONVERGED_GRADIENT; break; }
+        }
+        if (iters >= cfg.max_iters) { status = XM_BA_MAX_ITERATIONS; break; }
+        if (secs_since(t_start) >= cfg.max_time) { status = XM_BA_TIME_LIMIT; break; }
+        int pit = 0;
+        double relres = 0.0;
+        pcg(pit, relres);
+        pcg_total += pit;
+        // back-substitution dP = -V*^-1 (g + W^T dc), candidate, its cost and the model decrease
+        hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)gl.p, -1.0,
+                           (const int32_t *)lused.p, (const double *)x.p, (const BaState *)nullptr, dP.p);
+        const int nx = cur ^ 1;
+        hipLaunchKernelGGL((ba_cand_cam_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p, (const double *)x.p,
+                           (const int32_t *)cused.p, R[nx].p, T[nx].p, pp + o_cand);
+        hipLaunchKernelGGL(ba_cand_lm_kernel, dim3(gfl), b256, 0, st, m, (const double *)P[cur].p, (const double *)dP.p, (const int32_t *)lused.p,
+                           P[nx].p, pp + o_cand + 2 * (size_t)gfc);
+        hipLaunchKernelGGL((ba_cost_kernel<CD>), dim3(ge), b256, 0, st, S, (const double *)R[nx].p, (const double *)T[nx].p, (const double *)P[nx].p,
+                           (const double *)Jc.p, (const double *)x.p, (const double *)dP.p, pp + o_cost);
+        BaReduce rd{};
+        rd.sum_p[0] = pp + o_cost; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->cost_new;
+        rd.sum_p[1] = pp + o_cost + ge; rd.sum_n[1] = ge; rd.sum_out[1] = &dst->model;
+        rd.sum_p[2] = pp + o_cand; rd.sum_n[2] = gfc; rd.sum_out[2] = &dst->step2[0];
+        rd.sum_p[3] = pp + o_cand + gfc; rd.sum_n[3] = gfc; rd.sum_out[3] = &dst->x2[0];
+        rd.sum_p[4] = pp + o_cand + 2 * (size_t)gfc; rd.sum_n[4] = gfl; rd.sum_out[4] = &dst->step2[1];
+        rd.sum_p[5] = pp + o_cand + 2 * (size_t)gfc + gfl; rd.sum_n[5] = gfl; rd.sum_out[5] = &dst->x2[1];
+        reduce(rd);
+        const BaState s = read_state("the candidate's cost");
+        iters++;
+        const double step_norm = std::sqrt(s.step2[0] + s.step2[1]), x_norm = std::sqrt(s.x2[0] + s.x2[1]);
+        const double Fn = s.cost_new, model_dec = -s.model;
+        const bool valid = std::isfinite(Fn) && model_dec > 0.0;
+        const double rho = valid ? (F - Fn) / model_dec : -1.0;
+        const bool accept = valid && rho > 1e-3;
+        if (tl < cfg.trace_cap && cfg.trace) {
+            double *rec = cfg.trace + (size_t)6 * tl++;
+            rec[0] = F; rec[1] = Fn; rec[2] = mu; rec[3] = accept ? 1.0 : 0.0; rec[4] = pit; rec[5] = relres;
+        }
+        if (step_norm <= cfg.parameter_tol * (x_norm + cfg.parameter_tol)) { status = XM_BA_CONVERGED_PARAMETER; break; }
+        if (accept) {
+            accepted++;
+            radius = std::min(1e16, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3)));
+            nu = 2.0;
+            cur = nx;
+            const double Fold = F;
+            F = Fn;
+            eval();
+            fresh = true;
+            if (std::fabs(Fold - Fn) <= cfg.function_tol * Fold) { status = XM_BA_CONVERGED_FUNCTION; break; }
+        } else {
+            radius /= nu;
+            nu *= 2.0;
+            if (radius < 1e-32) { status = XM_BA_NO_PROGRESS; break; }
+        }
+    }
+    if (fresh) {   // the last accepted point: its gradient
+        passes(1.0 / radius);
+        const BaState s = read_state("the final gradient");
+        F = s.cost; gmax = s.gmax;
+    }
+    // ---- back to the caller's layouts; cameras / landmarks without a used observation are left as they came
+    std::vector<int32_t> cu((size_t)n), lu((size_t)m);
+    XM_HIP_CHECK(hipMemcpyAsync(hR.data(), R[cur].p, hR.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    XM_HIP_CHECK(hipMemcpyAsync(hT.data(), T[cur].p, hT.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    XM_HIP_CHECK(hipMemcpyAsync(hP.data(), P[cur].p, hP.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    XM_HIP_CHECK(hipMemcpyAsync(cu.data(), cused.p, cu.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    XM_HIP_CHECK(hipMemcpyAsync(lu.data(), lused.p, lu.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    wait_stream(st, cfg.watchdog_s, "the refined parameters");
+    for (int64_t i = 0; i < n; ++i) {
+        if (!cu[(size_t)i]) continue;
+        const double *Rc = &hR[(size_t)9 * i], *tc = &hT[(size_t)3 * i];
+        for (int a = 0; a < 3; ++a) {
+            for (int c = 0; c < 3; ++c) rot[(size_t)a + 3 * ((size_t)3 * i + c)] = Rc[3 * c + a];   // R_i = Rcw^T
+            t[(size_t)3 * i + a] = -(Rc[a] * tc[0] + Rc[3 + a] * tc[1] + Rc[6 + a] * tc[2]);     // t_i = -R_i tcw
+        }
+    }
+    for (int64_t l = 0; l < m; ++l) {
+        const int32_t sl = slot_of[(size_t)l];
+        if (!lu[(size_t)sl]) continue;
+        for (int a = 0; a < 3; ++a) p[(size_t)3 * l + a] = hP[(size_t)3 * sl + a];
+    }
+    out.status = status; out.iters = iters; out.accepted = accepted; out.pcg_iters = pcg_total;
+    out.final_cost = F; out.gradient_max = gmax; out.trace_len = tl;
+    out.seconds = secs_since(t_start);
+    (void)nobs;
+}
+
+}  // namespace
+
+void bundle_adjust(const SchurOp &S, const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out, hipStream_t st) {
+    out = BaOutcome();
+    if (cfg.fix_rotations) run<3>(S, cfg, rot, t, p, out, st);
+    else run<6>(S, cfg, rot, t, p, out, st);
+}
+
+}  // namespace xm

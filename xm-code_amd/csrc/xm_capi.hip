@@ -6,6 +6,7 @@
 #include <mutex>
 #include <vector>
 
+#include "xm_ba.h"
 #include "xm_schur.h"
 #include "xm_sell.h"
 #include "xm_symw.h"
@@ -284,6 +285,48 @@ int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int
     *kind = ctx->impl->schur_precond(&na, &b);
     if (aggregates) *aggregates = na;
     if (block) *block = b;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, xm_ba_result_t *res) {
+    XM_TRY
+    if (!ctx || !opt || !res || !rot || !t || !p) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: null argument");
+    if (opt->struct_size != sizeof(xm_ba_options_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: xm_ba_options_t.struct_size is not sizeof(xm_ba_options_t)");
+    if (res->struct_size != sizeof(xm_ba_result_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: xm_ba_result_t.struct_size is not sizeof(xm_ba_result_t)");
+    if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: single-GPU contexts only (not n_gpus > 1)");
+    if (ctx->impl->world() > 1) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: single-rank contexts only");
+    const xm_ba_options_t o = *opt;
+    auto bad = [](double v) { return !(v >= 0.0) || !std::isfinite(v); };
+    if (!(o.eta > 0.0 && o.eta < 1.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: eta must lie in (0, 1)");
+    if (o.max_iters < 0 || bad(o.max_time) || bad(o.function_tol) || bad(o.gradient_tol) || bad(o.parameter_tol))
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: negative or non-finite setting");
+    if (o.flags & ~XM_BA_FIX_ROTATIONS) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: unknown flag");
+    if (o.trace_cap < 0 || (o.trace_cap > 0 && !o.trace)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: trace_cap > 0 needs a trace array");
+    const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks();
+    for (int64_t k = 0; k < 9 * n; ++k)
+        if (!std::isfinite(rot[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: rotations are not finite");
+    for (int64_t k = 0; k < 3 * n; ++k)
+        if (!std::isfinite(t[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: translations are not finite");
+    for (int64_t k = 0; k < 3 * m; ++k)
+        if (!std::isfinite(p[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: landmarks are not finite");
+    xm::BaSettings c;
+    if (o.max_iters > 0) c.max_iters = o.max_iters;
+    if (o.max_time > 0.0) c.max_time = o.max_time;
+    if (o.function_tol > 0.0) c.function_tol = o.function_tol;
+    if (o.gradient_tol > 0.0) c.gradient_tol = o.gradient_tol;
+    if (o.parameter_tol > 0.0) c.parameter_tol = o.parameter_tol;
+    c.eta = o.eta;
+    c.fix_rotations = (o.flags & XM_BA_FIX_ROTATIONS) != 0;
+    c.trace_cap = o.trace_cap; c.trace = o.trace;
+    xm::BaOutcome r;
+    ctx->impl->bundle_adjust(c, rot, t, p, r);
+    xm_ba_result_t out;
+    std::memset(&out, 0, sizeof(out));
+    out.struct_size = sizeof(xm_ba_result_t);
+    out.status = r.status; out.iters = r.iters; out.accepted = r.accepted; out.pcg_iters = r.pcg_iters; out.n_used = r.n_used;
+    out.initial_cost = r.initial_cost; out.final_cost = r.final_cost; out.gradient_max = r.gradient_max; out.seconds = r.seconds;
+    out.trace_len = r.trace_len;
+    *res = out;
     return XM_OK;
     XM_CATCH
 }

@@ -54,6 +54,18 @@ struct SchurSettings {          // from xm_tuning_t (Settings::resolve)
 };
 struct SchurLm;                 // xm_schur.hip
 
+// The device lists of a SchurOp, read-only, for the kernels of other files (the bundle adjustment, xm_ba.h).  By camera: the observations of
+// camera i at [cam_ptr[i], cam_ptr[i+1]) with the landmark SLOT of each and its current weight.  By landmark slot: the first nheavy slots
+// have contiguous lists [lm_ptr[s], lm_ptr[s+1]); the others are packed 64 to a group (observation k of the group's lane j at
+// gbase[group] + 64 k + j, deg[s] of them); positions index arrays of lm_total entries, padding has weight 0.  Input order: camera, slot
+// and point (nobs x 3 row-major) of observation e, and where it sits in the two lists (pos_c, dpos_l).
+struct SchurLists {
+    int64_t n, m, nobs, nheavy, lm_total;
+    const int64_t *cam_ptr, *lm_ptr, *gbase, *pos_c, *dpos_l;
+    const int32_t *cam_lm, *lm_cam, *deg, *obs_cam, *obs_lm;
+    const double *cam_w, *lm_w, *obs_p;
+};
+
 class SchurOp {
 public:
     // cam / lm: 0-based indices of the nobs observations, p: nobs x 3 (row-major), w: nobs
@@ -81,6 +93,11 @@ public:
     void pcg_stats(int64_t out[3], double *relres) const { out[0] = pcg_products_; out[1] = pcg_iters_total_; out[2] = pcg_unconverged_; if (relres) *relres = pcg_last_relres_; }
     bool two_level() const { return tl_; }
     int64_t aggregates() const { return tl_nagg_; }
+    SchurLists lists() const {
+        return SchurLists{n_, m_, nobs_, nheavy_, ltotal_, cam_ptr_.p, lm_ptr_.p, gbase_.p, pos_c_dev_.p, dpos_l_dev_.p,
+                          cam_lm_.p, lm_cam_.p, ldeg_.p, obs_cam_.p, obs_lm_.p, cam_w_.p, lm_w_.p, obs_p_.p};
+    }
+    const std::vector<int32_t> &slot_of() const { return slot_of_; }   // landmark -> slot
 
 private:
     int64_t n_ = 0, m_ = 0, nobs_ = 0, nred_ = 0, ldv_ = 0;   // nred = cameras of the padded (N-1) system / 3

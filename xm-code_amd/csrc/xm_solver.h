@@ -157,6 +157,8 @@ int64_t equal_range_len(int64_t n, int world);   // cameras per rank of the equa
 class SellMatrix;   // xm_sell.h
 class SymwProduct;  // xm_symw.h
 class SchurOp;      // xm_schur.h
+struct BaSettings;  // xm_ba.h
+struct BaOutcome;
 
 struct PointState {  // everything the gradient epilogue writes for one point (R, s)
     DevBuf<double> G, egs, S0, rgR, rgs;
@@ -195,6 +197,8 @@ public:
     void edge_residuals(double *res);
     void set_edge_weights(const double *w);
     void recover_tp(const double *rot, const double *scale, double *t, double *p);   // matrix-free storage only
+    // reprojection bundle adjustment of a recovered solution (xm_ba.h): matrix-free storage, one rank; reads the context, changes nothing in it
+    void bundle_adjust(const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out);
     // XM^2 with the reference's residual definition (3_test_colmap_glomap.py:305-316): squared distance per edge / observation of the
     // RECOVERED solution (anchored rotations rot 3 x 3n column-major, scales) -- res: host, input order
     void edge_residuals_recovered(const double *rot, const double *scale, double *res);

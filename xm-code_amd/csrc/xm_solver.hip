@@ -13,6 +13,7 @@
 #include "xm_sell.h"
 #include "xm_symw.h"
 #include "xm_schur.h"
+#include "xm_ba.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1811,6 +1812,14 @@ double Context::xm2_filter(const double *rot, const double *scale, double pct, i
 void Context::recover_tp(const double *rot, const double *scale, double *t, double *p) {
     if (storage_ != XM_STORAGE_SCHUR || !schur_) throw Error(XM_ERR_ARG, "recover_tp: needs a matrix-free context (XM_STORAGE_SCHUR): the translations and landmarks are functions of the observations");
     schur_->recover_tp(rot, scale, t, p, st_);
+}
+void Context::bundle_adjust(const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out) {
+    if (storage_ != XM_STORAGE_SCHUR || !schur_)
+        throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: single-rank contexts only");
+    BaSettings c = cfg;
+    c.watchdog_s = cfg_.watchdog_s;
+    xm::bundle_adjust(*schur_, c, rot, t, p, out, st_);
 }
 int64_t Context::n_landmarks() const { return schur_ ? schur_->n_landmarks() : 0; }
 bool Context::schur_info(int64_t out[3], double *relres) const {

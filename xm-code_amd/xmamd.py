@@ -35,6 +35,7 @@ EXPORTS = [
     "xm_ctx_attach_edges", "xm_ctx_edge_residuals", "xm_ctx_edge_residuals_recovered", "xm_ctx_xm2_filter", "xm_ctx_xm2_round", "xm_ctx_set_edge_weights", "xm_ctx_recover_tp", "xm_ctx_schur_info", "xm_ctx_qw", "xm_spd_inverse", "xm_ctx_transport", "xm_ctx_sell_wpad", "xm_ctx_product_kind", "xm_symw_plan", "xm_symw_use",
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
+    "xm_ctx_bundle_adjust",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -87,6 +88,24 @@ class Xm2Info(C.Structure):
                 ("lam_used", C.c_double), ("rank3_tcg_iters", C.c_int64)]
 
 
+class BaOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_iters", C.c_int32), ("max_time", C.c_double), ("eta", C.c_double),
+                ("function_tol", C.c_double), ("gradient_tol", C.c_double), ("parameter_tol", C.c_double), ("flags", C.c_uint32),
+                ("trace_cap", C.c_int32), ("trace", C.c_void_p)]
+
+
+class BaResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_int32), ("iters", C.c_int32), ("accepted", C.c_int32),
+                ("pcg_iters", C.c_int64), ("n_used", C.c_int64), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("gradient_max", C.c_double), ("seconds", C.c_double), ("trace_len", C.c_int32)]
+
+
+BA_FIX_ROTATIONS = 1
+BA_STATUS = {0: "no_convergence", 1: "function_tolerance", 2: "gradient_tolerance", 3: "parameter_tolerance", 4: "max_iterations",
+             5: "time_limit", 6: "no_progress"}
+BA_CONVERGED = (1, 2, 3)
+
+
 _lib = None
 
 
@@ -118,6 +137,7 @@ def lib():
         L.xm_ctx_xm2_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p]
         L.xm_ctx_xm2_round.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Options), C.POINTER(Xm2Info), C.POINTER(Result)]
         L.xm_ctx_recover_tp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.xm_ctx_bundle_adjust.argtypes = [C.c_void_p, C.POINTER(BaOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaResult)]
         L.xm_ctx_transport.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
         L.xm_ctx_schur_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_double)]
         L.xm_ctx_schur_precond_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
@@ -622,6 +642,30 @@ class Context:
         _chk(lib().xm_ctx_recover_tp(self.h, rot.ctypes.data_as(C.c_void_p), scale.ctypes.data_as(C.c_void_p),
                                      t.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p)))
         return np.ascontiguousarray(t), np.ascontiguousarray(p)
+
+    def bundle_adjust(self, rot, t, P, fix_rotations=False, max_iters=1000, max_time=300.0, eta=0.1, function_tol=1e-6,
+                      gradient_tol=1e-10, parameter_tol=1e-8, trace=0):
+        """reprojection bundle adjustment of a recovered solution (the reference's Ceres refinement, xm_ctx_bundle_adjust): rot 3 x 3n
+        (R_i), t 3 x n, P 3 x m as recover_rotations / recover_tp return them -> refined (rot, t, P, info); matrix-free contexts only.
+        info: status (BA_STATUS), iters, accepted, pcg_iters, n_used, initial_cost, final_cost, gradient_max, seconds, and with trace > 0
+        "trace": one row per LM iteration (cost, candidate cost, mu, accepted, PCG iterations, PCG relative residual)"""
+        rot = np.array(rot, dtype=np.float64, order="F"); t = np.array(t, dtype=np.float64, order="F"); P = np.array(P, dtype=np.float64, order="F")
+        assert rot.shape == (3, 3 * self.n) and t.shape == (3, self.n) and P.shape == (3, self.n_landmarks)
+        opt = BaOptions(); res = BaResult()
+        opt.struct_size, res.struct_size = C.sizeof(BaOptions), C.sizeof(BaResult)
+        opt.max_iters, opt.max_time, opt.eta = int(max_iters), float(max_time), float(eta)
+        opt.function_tol, opt.gradient_tol, opt.parameter_tol = float(function_tol), float(gradient_tol), float(parameter_tol)
+        opt.flags = BA_FIX_ROTATIONS if fix_rotations else 0
+        tr = None
+        if trace:
+            tr = np.zeros((int(trace), 6)); opt.trace_cap = int(trace); opt.trace = tr.ctypes.data_as(C.c_void_p)
+        _chk(lib().xm_ctx_bundle_adjust(self.h, C.byref(opt), rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                        P.ctypes.data_as(C.c_void_p), C.byref(res)))
+        info = {k: getattr(res, k) for k, _ in BaResult._fields_ if k != "struct_size"}
+        info["status_name"] = BA_STATUS.get(res.status, "?")
+        if tr is not None:
+            info["trace"] = tr[: res.trace_len].copy()
+        return rot, t, P, info
 
     def edge_residuals_recovered(self, rot, scale):
         """squared distance per edge / observation of a RECOVERED solution (rot 3 x 3n, scale n): the reference's XM^2 residual"""
