@@ -8,7 +8,11 @@ solve.  Workload at every N: the configuration the metric is quoted on, "Venice-
 (SURVEY.md F7), so it is the seeded dense SBA-like generator of SURVEY.md §8d with n = 1778 cameras
 (tests/xm_testlib.py:gen_dense).  For N > 1 the same problem is row-partitioned over the ranks (strong scaling).
 
-Launch: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR].
+Launch: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full].
+A plain run does what the headline needs and nothing more: set-up, W warm-up solves, K timed solves, the dump, the JSON line.  --full
+adds the legs beside the headline, each a run of its own after the timed solves: the Rome-scale (13682-camera) solves, the HBM-bound
+run of the dense kernel, the same-node CPU baseline and GPU / CPU wall-clock-to-KKT pair with the parity against the recorded oracle,
+and with several ranks the RCCL leg and the replica throughput.  The --no-* / --cpu-* options below select among those legs.
   * under torch.distributed.run (one rank per GPU, what the driver does): one process per GPU, RCCL all-gathers inside the solver;
   * plain `python bench.py --gpus N`: NO launcher -- the library's single-process multi-GPU mode (xm_problem_t.n_gpus: one host thread
     per GPU, direct peer-write exchange fused into the tCG).  When the box has fewer than N GPUs the N ranks are "virtual devices" on
@@ -406,7 +410,10 @@ def main():
     ap.add_argument("--steps", type=int, default=6, help="timed solves (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="venice1778")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the legs beside it (Rome-scale solves, HBM-bound kernel run, CPU baseline and KKT pair, "
+                         "RCCL leg and replicas with several ranks); a plain run prints the headline alone")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg (--full; 0 = skip)")
     ap.add_argument("--storage", default="dense", choices=["dense", "bsr", "vg"],
                     help="storage of view-graph workloads: dense, 3x3-block CSR, or the edge list (XM_STORAGE_VIEWGRAPH: compressed sliced ELL)")
     ap.add_argument("--retraction", default="qr", choices=["qr", "polar"])
@@ -420,7 +427,7 @@ def main():
     ap.add_argument("--exchange", default="auto", choices=["auto", "peer", "rccl"],
                     help="multi-GPU tCG exchange: auto = direct peer writes when the transport passes its self-test, else RCCL (the library's ladder); "
                          "peer = direct peer writes or an error; rccl = the RCCL all-gather north_star prescribes even where peer writes work. "
-                         "With auto and --gpus N > 1 a second, RCCL-timed leg follows the default one (rccl_leg)")
+                         "With auto, --gpus N > 1 and --full a second, RCCL-timed leg follows the default one (rccl_leg)")
     ap.add_argument("--no-rccl-leg", action="store_true", help="skip the second (RCCL) leg of a multi-GPU run")
     ap.add_argument("--sell", default="auto", choices=["auto", "on", "off"], help="sliced-ELL copy of block-sparse storage (xm_tuning_t.sell)")
     ap.add_argument("--model-recurrence", action="store_true", help="xm_options_t.flags |= XM_FLAG_MODEL_RECURRENCE: the tCG keeps no accumulated H v (default off: last bits of the model value differ)")
@@ -714,12 +721,13 @@ def _run(args, wl, tl, t0, Q, tkw, team, gpu_map, ngp, retr, rank, world, torch,
                      "streamed": ({"bytes_per_product": traffic, "GBs": traffic / (traced_us * 1e-6) / 1e9, "frac": traffic / (traced_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
                                    "traced_frac_algorithmic": alg_bytes / (traced_us * 1e-6) / 1e9 / HBM_PEAK_GBS} if (traffic and traced_us) else None),
                      "note": "HIP events around every 64th tCG Q*W launch inside the timed solves (no-op samples dropped); " + (
-                             "per-rank Q is %.0f MB, inside the 256 MB Infinity Cache: the figure is cache-assisted, see roofline_hbm for the "
+                             "per-rank Q is %.0f MB, inside the 256 MB Infinity Cache: the figure is cache-assisted, see roofline_hbm (--full) for the "
                              "HBM-bound run of the same kernel" % (alg_bytes / 1e6) if alg_bytes < 250e6 else
                              "per-rank Q is %.0f MB, beyond the 256 MB Infinity Cache: HBM-bound" % (alg_bytes / 1e6))},
     }
     ctx.close()
-    if not args.no_rome and args.workload == "venice1778":
+    # the headline ends here: what follows are the legs beside it, each a run of its own, and only with --full
+    if args.full and not args.no_rome and args.workload == "venice1778":
         # BASELINE.json north_star: "end-to-end solve of a Rome-scale (>= 10k-camera) Q reported as iters/s and wall-clock at
         # 1, 2, 4 and 8 GPUs" — a secondary leg at every N (same rules: warmup, barrier-bracketed, max over ranks); the headline
         # `value` above stays the Venice-1778 metric.
@@ -776,7 +784,7 @@ def _run(args, wl, tl, t0, Q, tkw, team, gpu_map, ngp, retr, rank, world, torch,
                                        "primal": di["primal"], "sym_product": di.get("sym_product"), "hess_launch_ms": dq_ms,
                                        **dict(zip(("hess_traffic", "hess_traffic_source", "hess_traced_us"), recorded_traffic("rome_dense", ngp))),
                                        "hess_algorithmic_GBs": db / (dq_ms * 1e-3) / 1e9 if dq_ms > 0 else None}
-    if rank == 0 and ngp == 1 and not args.no_hbm_check and wl["kind"] == "dense":
+    if args.full and rank == 0 and ngp == 1 and not args.no_hbm_check and wl["kind"] == "dense":
         # same kernel, matrix far beyond every cache: 13682 cameras = 13.5 GB of random f64 generated on the device
         nb_, o_ = 13682, 3
         ld_ = xmamd.dense_ld(nb_)
@@ -795,13 +803,14 @@ def _run(args, wl, tl, t0, Q, tkw, team, gpu_map, ngp, retr, rank, world, torch,
                                "algorithmic_bytes_per_launch": by, "kernel": "qw_dense_kernel<3, EPI_PLAIN>",
                                "workload": "same kernel on a 13682-camera (Final-13682-size) 13.5 GB random matrix, 20 launches"}
         del Qbig, Wbig, Obig
-    if rank == 0 and ngp == 1 and args.cpu_seconds > 0 and bound_mask is not None:
+    cpu_legs = args.full and rank == 0 and ngp == 1 and args.cpu_seconds > 0
+    if cpu_legs and bound_mask is not None:
         os.sched_setaffinity(0, bound_mask)   # the host leg: this thread is OpenMP thread 0 again, on its place
-    if rank == 0 and ngp == 1 and args.cpu_seconds > 0 and not args.no_kkt_pair and args.workload == "venice1778":
+    if cpu_legs and not args.no_kkt_pair and args.workload == "venice1778":
         out["kkt_pair"] = kkt_pair(tl, xmamd, args.cpu_seconds)
-    if rank == 0 and ngp == 1 and args.cpu_seconds > 0 and Q is not None:
+    if cpu_legs and Q is not None:
         out["cpu_baseline"] = cpu_baseline(Q, wl, args.cpu_seconds)
-    elif rank == 0 and ngp == 1 and args.cpu_seconds > 0 and wl["kind"] == "vg" and args.storage in ("bsr", "vg"):
+    elif cpu_legs and wl["kind"] == "vg" and args.storage in ("bsr", "vg"):
         out["cpu_baseline"] = cpu_baseline(None, wl, args.cpu_seconds, bsr=(P["rowptr"], P["colidx"], P["blocks"]))
     if rank == 0 and ngp == 1 and "cpu_baseline" in out and Q is not None and last_sol is not None and args.workload == "venice1778":
         if args.cpu_kkt_seconds > 0:
@@ -819,7 +828,7 @@ def _run(args, wl, tl, t0, Q, tkw, team, gpu_map, ngp, retr, rank, world, torch,
             out["cpu_baseline"]["recorded_wallclock_to_kkt_s"] = par["cpu_wallclock_to_kkt_s"]       # ANOTHER machine and thread count than `value`:
             out["cpu_baseline"]["recorded_wallclock_to_kkt_threads"] = par["cpu_threads"]            # see kkt_pair for a same-node pair
             out["cpu_baseline"]["recorded_wallclock_to_kkt_provenance"] = par["cpu_wallclock_provenance"]
-    if ngp > 1 and args.exchange == "auto" and not args.no_rccl_leg:
+    if args.full and ngp > 1 and args.exchange == "auto" and not args.no_rccl_leg:
         # north_star prescribes "an RCCL all-gather of Y over xGMI each iteration"; the library's default is the direct peer exchange.  One
         # driver run yields both curves: the same workload again with the RCCL rung of the ladder forced (xm_tuning_t.exchange = 3 in the
         # single-process mode; XM_COMM_PEER=0 + a fresh xm_comm_init with one process per GPU).  A refusal (RCCL does not put two ranks
@@ -833,8 +842,8 @@ def _run(args, wl, tl, t0, Q, tkw, team, gpu_map, ngp, retr, rank, world, torch,
         xmamd.lib().xm_comm_finalize()
         # Replica throughput: what N GPUs deliver on N INDEPENDENT Venice-size scenes (no data-path communication; the row
         # partition above is latency-bound at this size: 28 MB of Q per GPU at N = 8 against two collectives per iteration).
-        # Reported next to the partitioned headline, never instead of it.
-        cx = xmamd.Context(Q=Q) if Q is not None else None
+        # Reported next to the partitioned headline (--full), never instead of it.
+        cx = xmamd.Context(Q=Q) if (args.full and Q is not None) else None
         if cx is not None:
             cx.solve(wl["max_rank"], wl["tol"], wl["lam"])
             barrier()

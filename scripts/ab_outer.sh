@@ -4,7 +4,7 @@
 rounds=${1:-2}
 for r in $(seq 1 $rounds); do for o in host device; do
   echo -n "$o: "
-  timeout 300 python bench.py --outer $o --steps 6 --warmup 1 --no-hbm-check --no-kkt-pair --cpu-kkt-seconds 0 --cpu-seconds 0 --no-rome-dense 2>/dev/null | python -c "
+  timeout 300 python bench.py --outer $o --steps 6 --warmup 1 --no-hbm-check --no-kkt-pair --cpu-kkt-seconds 0 --cpu-seconds 0 --no-rome-dense --full 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['rome_scale']

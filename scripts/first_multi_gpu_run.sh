@@ -24,13 +24,13 @@ run() {   # run <log name> <timeout s> <command ...>
 cd $R
 run probe 900 python scripts/multi_gpu_probe.py --gpus $N --rungs peer rccl procs
 run pytest_multi 2400 python -m pytest tests -m gpu -q --timeout 900 -k "ipc or virtual or two_ranks or multi_gpu or multi_rank or rccl"
-run bench_team 1200 python bench.py --gpus $N --steps 3 --warmup 1 --cpu-seconds 0
-run bench_team_peer 900 python bench.py --gpus $N --steps 3 --warmup 1 --cpu-seconds 0 --exchange peer --no-rccl-leg
-run bench_team_rccl 900 python bench.py --gpus $N --steps 3 --warmup 1 --cpu-seconds 0 --exchange rccl
-run bench_procs 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus $N --steps 3 --warmup 1 --cpu-seconds 0
-run bench_procs_rccl 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((PORT+1)) bench.py --gpus $N --steps 3 --warmup 1 --cpu-seconds 0 --exchange rccl
+run bench_team 1200 python bench.py --gpus $N --steps 3 --warmup 1 --cpu-seconds 0 --full
+run bench_team_peer 900 python bench.py --gpus $N --steps 3 --warmup 1 --cpu-seconds 0 --exchange peer --no-rccl-leg --full
+run bench_team_rccl 900 python bench.py --gpus $N --steps 3 --warmup 1 --cpu-seconds 0 --exchange rccl --full
+run bench_procs 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus $N --steps 3 --warmup 1 --cpu-seconds 0 --full
+run bench_procs_rccl 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((PORT+1)) bench.py --gpus $N --steps 3 --warmup 1 --cpu-seconds 0 --exchange rccl --full
 for n in 1 2 4 8; do
-  [ $n -le $N ] && [ $n -gt 1 ] && run scale_$n 1500 python bench.py --gpus $n --steps 3 --warmup 1 --cpu-seconds 0 --no-rccl-leg
+  [ $n -le $N ] && [ $n -gt 1 ] && run scale_$n 1500 python bench.py --gpus $n --steps 3 --warmup 1 --cpu-seconds 0 --no-rccl-leg --full
 done
 run kbench_symw 900 python scripts/kbench_symw.py 13682 --worlds 2 $N
 run kbench_multi 600 python scripts/kbench_multi.py 1778 --o 3

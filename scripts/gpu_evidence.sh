@@ -26,12 +26,12 @@ for i in 1 2 3; do
 done
 timeout 3000 python scripts/pmc_legs.py $TAG venice hbm13682 rome_dense rome_bsr vg100k_vg vg100k_bsr > $O/${TAG}_pmc_legs.out 2>&1
 mkdir -p profiles; cp $O/${TAG}_pmc_fetch_*.json profiles/ 2>/dev/null     # bench.py quotes them (same box, same sources)
-timeout 900 python bench.py --steps 6 --warmup 1 2>/dev/null | tail -1 > $O/${TAG}_bench_venice1778.json
-timeout 600 python bench.py --workload vg100k --storage vg --steps 6 --warmup 1 --no-rome --no-hbm-check --cpu-seconds 10 2>/dev/null | tail -1 > $O/${TAG}_bench_vg100k_vg.json
+timeout 900 python bench.py --steps 6 --warmup 1 --full 2>/dev/null | tail -1 > $O/${TAG}_bench_venice1778.json
+timeout 600 python bench.py --workload vg100k --storage vg --steps 6 --warmup 1 --no-rome --no-hbm-check --cpu-seconds 10 --full 2>/dev/null | tail -1 > $O/${TAG}_bench_vg100k_vg.json
 timeout 600 python bench.py --workload vg100k --storage bsr --steps 6 --warmup 1 --no-rome --no-hbm-check --cpu-seconds 0 2>/dev/null | tail -1 > $O/${TAG}_bench_vg100k_bsr.json
 timeout 600 python bench.py --workload final13682 --storage bsr --steps 6 --warmup 1 --no-hbm-check --cpu-seconds 0 2>/dev/null | tail -1 > $O/${TAG}_bench_rome_bsr.json
-timeout 900 python bench.py --gpus 2 --steps 3 --warmup 1 --cpu-seconds 0 2>/dev/null | tail -1 > $O/${TAG}_bench_2gpu_virtual.json
-timeout 900 python bench.py --gpus 8 --steps 2 --warmup 1 --no-rome-dense --cpu-seconds 0 2>/dev/null | tail -1 > $O/${TAG}_bench_8gpu_virtual.json
+timeout 900 python bench.py --gpus 2 --steps 3 --warmup 1 --cpu-seconds 0 --full 2>/dev/null | tail -1 > $O/${TAG}_bench_2gpu_virtual.json
+timeout 900 python bench.py --gpus 8 --steps 2 --warmup 1 --no-rome-dense --cpu-seconds 0 --full 2>/dev/null | tail -1 > $O/${TAG}_bench_8gpu_virtual.json
 cd /tmp
 for leg in "venice1778:--steps 3 --warmup 1 --cpu-seconds 0 --no-hbm-check --no-rome" \
            "vg100k_vg:--workload vg100k --storage vg --steps 2 --warmup 1 --no-rome --no-hbm-check --cpu-seconds 0" \

@@ -15,9 +15,9 @@ LEGS = {
                "Hessian products of the headline solve (dense products: outer iteration on the host, EPI_HESS = 2): qw_symv_kernel + "
                "symv_reduce_kernel<o, EPI_HESS> at rank 3 / 4 (half-traffic symmetric pair; the main launch also serves the few gradient products), "
                "qw_dense_kernel<5, EPI_HESS> at rank 5"),
-    "hbm13682": (["--steps", "1", "--warmup", "0", "--cpu-seconds", "0", "--no-rome"],
+    "hbm13682": (["--steps", "1", "--warmup", "0", "--cpu-seconds", "0", "--no-rome", "--full"],
                  {"plain": ["qw_dense_kernel<3, 0, 2, false"]}, "roofline_hbm leg: qw_dense_kernel<3, EPI_PLAIN> on the 13.5 GB matrix (220 MB prefix cacheable, the rest a non-temporal stream)"),
-    "rome_dense": (["--steps", "1", "--warmup", "0", "--cpu-seconds", "0", "--no-hbm-check"],
+    "rome_dense": (["--steps", "1", "--warmup", "0", "--cpu-seconds", "0", "--no-hbm-check", "--full"],
                    {"main": ["qw_symv_kernel<3"], "reduce": ["symv_reduce_kernel<3, 2"]},
                    "rome_scale_dense leg: Hessian products of the 13.5 GB dense Q through the half-traffic symmetric path (main + reduce launch)"),
     "rome_bsr": (["--workload", "final13682", "--storage", "bsr", "--steps", "1", "--warmup", "0", "--no-hbm-check", "--cpu-seconds", "0"],

@@ -1098,7 +1098,7 @@ def test_bench_two_ranks_flow(xmamd, transport):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, XM_BENCH_SINGLE_DEVICE="1", **({"XM_BENCH_SHM": "1"} if transport == "shm" else {"XM_BENCH_IPC": "1"}))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--full"]
     if transport == "ipc":
         env["XM_BENCH_IPC_SPIN"] = "60"       # bound of the device-side waits in this run
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)   # a hard gate: no retry, no skip (see Context::tcg_blocks)
@@ -1137,6 +1137,7 @@ def test_bench_plain_command_needs_no_launcher(xmamd):
     assert d["solve"]["primal"] == pytest.approx(0.2844696774, rel=1e-8)
     assert "ONE process" in d["config"]["parallelism"]
     assert d["transport"].startswith("direct peer writes") and d["fallback"] is None
+    assert not {"rome_scale", "rome_scale_dense", "rccl_leg", "replicas"} & set(d)     # a plain run: the headline alone (legs: --full)
     if xmamd.device_count() < 2:
         assert "VIRTUAL devices" in d["config"]["devices"]
 
