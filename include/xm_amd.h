@@ -341,17 +341,41 @@ int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int
  *               radius 1e4 at the start; accepted when rho = (F - F_new) / model decrease > 1e-3 (radius /= max(1/3, 1 - (2 rho - 1)^3));
  *               rejected: radius /= nu, nu *= 2.  Landmarks eliminated, the reduced camera system solved by PCG from zero with the
  *               inverted diagonal camera blocks as preconditioner (ITERATIVE_SCHUR + SCHUR_JACOBI) to relative residual eta or 500
- *               iterations.  Deviations from Ceres: monotonic steps only, no Jacobi scaling, no robust loss.
+ *               iterations.  Deviation from Ceres: no Jacobi scaling (with block-Jacobi PCG and mu diag(J^T J) damping it changes
+ *               only the clamp of D and the norm of the PCG's stop test).
+ *   loss        loss (XM_BA_LOSS_*) with scale a = loss_scale in the normalised image units of r (pixels / focal length); Ceres's
+ *               definitions (loss_function.cc) at s = |r_e|^2:  Huber  rho = s (s <= a^2), 2 a sqrt(s) - a^2;  SoftL1  2 b (sqrt(1 + s / b)
+ *               - 1);  Cauchy  b log(1 + s / b);  Arctan  a atan2(s, a)  (b = a^2); rho' clamped below at the smallest normal double.  The
+ *               cost is F = 1/2 sum rho(s_e) (initial_cost, final_cost and the trace report it); r_e and J_e are scaled by sqrt(rho'(s_e)),
+ *               which is Ceres's Corrector for these losses (rho'' <= 0).  Which observations are used does not depend on the loss.
+ *   steps       XM_BA_NONMONOTONIC: Ceres's non-monotonic steps (use_nonmonotonic_steps = true, the reference's configuration): step
+ *               quality rho = max((F - F_new) / dm, (F_ref - F_new) / (dm_ref + dm)) with the reference cost F_ref reset after
+ *               max_nonmonotonic (0 = 5) accepted steps without a new minimum (Conn, Gould & Toint, Algorithm 10.1.2); the call returns
+ *               the point of least cost, and final_cost and gradient_max are those of that point.  Without the flag every accepted
+ *               step decreases F.
  *   stops       |dF| / F <= function_tol on an accepted step; |J^T r|_inf <= gradient_tol (tangent coordinates); |d| <= parameter_tol
  *               (|x| + parameter_tol) with |x|^2 = sum over used cameras of (1 for a free rotation + |tcw|^2) + sum |P|^2; max_iters; max_time
  *               (seconds); radius < 1e-32.
- * Options: struct_size = sizeof(xm_ba_options_t); max_iters, max_time, function_tol, gradient_tol, parameter_tol: 0 = the defaults
- * (1000, 300, 1e-6, 1e-10, 1e-8); eta is required and lies in (0, 1) (Ceres's is 0.1).  trace: trace_cap x 6 doubles, one record per LM
- * iteration: cost, candidate cost, mu, accepted (0 / 1), PCG iterations, PCG relative residual.
- * XM_ERR_ARG (context unchanged and usable): not XM_STORAGE_SCHUR, several ranks or a communicator, a struct_size other than the
- * library's, null arrays, non-finite input, eta outside (0, 1), negative settings, unknown flags.  The call reads the context and changes
- * nothing in it (Q, weights, solver workspace). */
+ * Options: struct_size = sizeof(xm_ba_options_t), or XM_BA_OPTIONS_SIZE_V1 (64: the fields through trace, as the first version of this
+ * struct had them; it means the trivial loss and monotonic steps); max_iters, max_time, function_tol, gradient_tol, parameter_tol: 0 = the
+ * defaults (1000, 300, 1e-6, 1e-10, 1e-8); eta is required and lies in (0, 1) (Ceres's is 0.1).  trace: trace_cap x 6 doubles, one record
+ * per LM iteration: cost, candidate cost, mu, accepted (0 / 1), PCG iterations, PCG relative residual.
+ * XM_ERR_ARG (context unchanged and usable): not XM_STORAGE_SCHUR, several ranks or a communicator, a struct_size other than those two,
+ * null arrays, non-finite input, eta outside (0, 1), negative settings, unknown flags, an unknown loss, a robust loss whose loss_scale is
+ * not finite and > 0, loss_scale != 0 with the trivial loss, max_nonmonotonic < 0.  The call reads the context and changes nothing in it
+ * (Q, weights, solver workspace).
+ * xm_ctx_reprojection_errors: sqerr[e] = |r_e|^2 (unrobustified) of every observation e in input order at (rot, t, p) (the layouts, context
+ * and refusals of xm_ctx_bundle_adjust), -1 for an observation the adjustment does not use (current weight <= 0 or p_e2 <= 0); computed on
+ * the device with the context's current weights, nothing in the context changes.  For choosing the loss scale before an adjustment and for
+ * finding the outliers after it (xm_ctx_set_edge_weights can then drop them before the next solve). */
 #define XM_BA_FIX_ROTATIONS 1u          /* the reference's only_landmarks = True: rotations constant (bit-identical), t and P free */
+#define XM_BA_NONMONOTONIC  2u          /* Ceres's non-monotonic steps (see above) */
+#define XM_BA_LOSS_TRIVIAL  0
+#define XM_BA_LOSS_HUBER    1
+#define XM_BA_LOSS_SOFT_L1  2
+#define XM_BA_LOSS_CAUCHY   3
+#define XM_BA_LOSS_ARCTAN   4
+#define XM_BA_OPTIONS_SIZE_V1 64u       /* struct_size of callers built before loss, max_nonmonotonic and loss_scale */
 #define XM_BA_NO_CONVERGENCE       0
 #define XM_BA_CONVERGED_FUNCTION   1
 #define XM_BA_CONVERGED_GRADIENT   2
@@ -366,6 +390,9 @@ typedef struct {
     uint32_t flags;            /* XM_BA_* */
     int32_t trace_cap;
     double *trace;
+    int32_t loss;              /* XM_BA_LOSS_* */
+    int32_t max_nonmonotonic;  /* Ceres's max_consecutive_nonmonotonic_steps; 0 = 5 */
+    double loss_scale;         /* Ceres's a; 0 with the trivial loss */
 } xm_ba_options_t;
 typedef struct {
     uint32_t struct_size;
@@ -376,6 +403,7 @@ typedef struct {
     int32_t trace_len;
 } xm_ba_result_t;
 int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, xm_ba_result_t *res);
+int xm_ctx_reprojection_errors(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, double *sqerr);
 
 /* ================================================================== 3. kernel-level entry points (device pointers) */
 /* device memory helpers so that callers need no other GPU runtime */

@@ -3,7 +3,8 @@ streams (a model of the kernels' loads and stores), at two sizes:
    SIMPLE2 (tests/golden/simple2: the reference's own recovered solution as the start, what its Ceres step would get)
    a scene of gen_scene Final-13682 size (13 682 cameras, 800 000 landmarks, 8 random views each + 3 landmarks seen by every camera) whose
    cameras sit on a sphere looking at the landmark cloud, so every depth is positive
-   python scripts/kbench_ba.py [--out profiles/<name>.txt] [--iters K]
+   python scripts/kbench_ba.py [--out profiles/<name>.txt] [--iters K] [--loss NAME --scale A] [--nonmonotonic]
+(--loss: one of xmamd.BA_LOSS with its scale A in normalised image units; --nonmonotonic: Ceres's non-monotonic steps.)
 Per LM iteration: runs of exactly K LM iterations (stop tolerances 1e-300) at eta = 0.1 and 1e-4.  Per PCG iteration: ONE LM iteration
 from the same start at eta = 0.1 and at eta = 1e-10 (identical work apart from the PCG), best of three each; (time difference) / (PCG
 iteration difference)."""
@@ -24,6 +25,7 @@ def arg(name, default):
 
 K = int(arg("--iters", 10))
 out_path = arg("--out", None)
+LOSS = dict(loss=arg("--loss", "trivial"), loss_scale=float(arg("--scale", 0.0)), nonmonotonic="--nonmonotonic" in sys.argv)
 lines = []
 
 
@@ -64,19 +66,19 @@ def pcg_bytes(n, m, nobs, cd=6):
 
 def bench(name, obs, n, m, rot0, t0, P0):
     ctx = xmamd.Context(obs=obs, n=n)
-    ctx.bundle_adjust(rot0, t0, P0, max_iters=1)      # warm-up: code objects, allocations
+    ctx.bundle_adjust(rot0, t0, P0, max_iters=1, **LOSS)      # warm-up: code objects, allocations
     r = {}
     for eta in (0.1, 1e-4):
         t = time.time()
         _, _, _, info = ctx.bundle_adjust(rot0, t0, P0, max_iters=K, eta=eta, trace=K, function_tol=1e-300, gradient_tol=1e-300,
-                                             parameter_tol=1e-300)
+                                             parameter_tol=1e-300, **LOSS)
         r[eta] = (time.time() - t, info)
     one = {}
     for eta in (0.1, 1e-10):
         best = None
         for _ in range(3):
             t = time.time()
-            _, _, _, info = ctx.bundle_adjust(rot0, t0, P0, max_iters=1, eta=eta)
+            _, _, _, info = ctx.bundle_adjust(rot0, t0, P0, max_iters=1, eta=eta, **LOSS)
             dt = time.time() - t
             best = (dt, info) if best is None or dt < best[0] else best
         one[eta] = best
@@ -95,7 +97,8 @@ def bench(name, obs, n, m, rot0, t0, P0):
         f"{by / max(per_pcg, 1e-12) / 1e9:7.1f} GB/s")
 
 
-log(f"kbench_ba: {time.strftime('%Y-%m-%d %H:%M:%S')}  K = {K} LM iterations per run")
+log(f"kbench_ba: {time.strftime('%Y-%m-%d %H:%M:%S')}  K = {K} LM iterations per run; loss {LOSS['loss']} (scale {LOSS['loss_scale']:g})"
+    f"{', non-monotonic steps' if LOSS['nonmonotonic'] else ''}")
 G = os.path.join(ROOT, "tests", "golden", "simple2")
 Z = np.load(os.path.join(G, "obs.npz"))
 ref = np.load(os.path.join(G, "tp.npz"))

@@ -16,9 +16,13 @@
 // Every sum over observations is a fixed-order sum (lane-strided lists + DPP trees, per-workgroup partials added in a fixed order): two
 // calls give the same bits.  f64 throughout.
 //
-// Deliberate deviations from Ceres: steps are monotonic only (the reference sets use_nonmonotonic_steps); no Jacobi column scaling of J;
-// no robust loss.  The rotation is the left-multiplied rotation vector (Ceres's quaternion Plus turns by 2|delta|: only the meaning of
-// gradient_tol differs).  |x| in the parameter tolerance counts 1 per free rotation (a unit quaternion) plus |tcw|^2 and |P|^2.
+// Robust losses (Huber, SoftL1, Cauchy, Arctan; Ceres's definitions): the eval kernel stores sqrt(rho') r and sqrt(rho') J (Ceres's
+// Corrector when rho'' <= 0) and the cost 1/2 sum rho(|r|^2), so every later pass is the same.  Non-monotonic steps (the reference's
+// use_nonmonotonic_steps): Ceres's TrustRegionStepEvaluator on the host, the least-cost point is returned.
+// Deliberate deviation from Ceres: no Jacobi column scaling of J (with block-Jacobi PCG and the damping mu diag(J^T J) it changes only the
+// clamp of D and the norm of the PCG's stop test).  The rotation is the left-multiplied rotation vector (Ceres's quaternion Plus turns by
+// 2|delta|: only the meaning of gradient_tol differs).  |x| in the parameter tolerance counts 1 per free rotation (a unit quaternion) plus
+// |tcw|^2 and |P|^2.
 #pragma once
 
 #include <cstdint>
@@ -33,6 +37,10 @@ struct BaSettings {
     int max_iters = 1000;
     double max_time = 300.0, eta = 0.1, function_tol = 1e-6, gradient_tol = 1e-10, parameter_tol = 1e-8;
     bool fix_rotations = false;   // XM_BA_FIX_ROTATIONS: camera blocks are the translation only (3 x 3)
+    int loss = XM_BA_LOSS_TRIVIAL;
+    double loss_scale = 0.0;      // Ceres's a (normalised image units); robust losses only
+    bool nonmonotonic = false;    // XM_BA_NONMONOTONIC
+    int max_nonmonotonic = 5;     // Ceres's max_consecutive_nonmonotonic_steps
     int trace_cap = 0;
     double *trace = nullptr;      // trace_cap x 6 row-major: cost, candidate cost, mu, accepted, PCG iterations, PCG relative residual
     double watchdog_s = 600.0;    // host waits give up after this long
@@ -45,5 +53,7 @@ struct BaOutcome {
 
 // rot: 3 x 3n column-major (R_i, camera-to-world), t: 3 x n, p: 3 x m (host, updated in place).  The SchurOp is only read.
 void bundle_adjust(const SchurOp &S, const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out, hipStream_t st);
+// sqerr[e] = |r_e|^2 (unrobustified) of observation e in input order at (rot, t, p), -1 where it is not used (weight <= 0 or p_e2 <= 0)
+void reprojection_errors(const SchurOp &S, const double *rot, const double *t, const double *p, double *sqerr, double watchdog_s, hipStream_t st);
 
 }  // namespace xm

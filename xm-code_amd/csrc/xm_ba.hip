@@ -93,11 +93,58 @@ __device__ __forceinline__ LmRange lm_range(const SchurLists &S) {
 }
 __device__ __forceinline__ bool obs_used(const double (&v)[6]) { return v[0] != 0.0 || v[1] != 0.0 || v[2] != 0.0; }   // J_P row 0 (never 0 when used)
 
-// ---- residuals and Jacobians at (Rcw, tcw, P), written in both list orders; partial sums of the cost and of the used observations
-template <int CD>
+// ---- robust losses: Ceres's definitions (loss_function.cc) of rho(s) and rho'(s) at s = |r|^2 for the scale a, rho' clamped below at the
+// smallest normal double as Ceres does.  rho'' <= 0 everywhere for these four, so Ceres's Corrector reduces to scaling r and J by
+// sqrt(rho'(s)): the eval kernel stores the scaled records and every later pass reads them as they are.  Since rho' >= DBL_MIN, sqrt(rho')
+// >= 2^-511 and the first row of a used observation's J_P (of norm >= 1 / |X2|) stays non-zero: obs_used does not depend on the loss.
+template <int LOSS>
+__device__ __forceinline__ double ba_rho(double s, double a, double &rho1) {
+    constexpr double kMinNormal = 2.2250738585072014e-308;
+    if constexpr (LOSS == XM_BA_LOSS_HUBER) {
+        const double b = a * a;
+        if (s > b) {
+            const double r = sqrt(s);
+            rho1 = fmax(kMinNormal, a / r);
+            return 2.0 * a * r - b;
+        }
+        rho1 = 1.0;
+        return s;
+    } else if constexpr (LOSS == XM_BA_LOSS_SOFT_L1) {
+        const double b = a * a, sum = 1.0 + s * (1.0 / b), tmp = sqrt(sum);
+        rho1 = fmax(kMinNormal, 1.0 / tmp);
+        return 2.0 * b * (tmp - 1.0);
+    } else if constexpr (LOSS == XM_BA_LOSS_CAUCHY) {
+        const double b = a * a, sum = 1.0 + s * (1.0 / b);
+        rho1 = fmax(kMinNormal, 1.0 / sum);
+        return b * log(sum);
+    } else {
+        static_assert(LOSS == XM_BA_LOSS_ARCTAN, "unknown loss");
+        const double sum = 1.0 + s * s * (1.0 / (a * a));
+        rho1 = fmax(kMinNormal, 1.0 / sum);
+        return a * atan2(s, a);
+    }
+}
+// Scale: the loss scale a (one double) for a robust LOSS, nothing for the trivial one, whose argument list and code are those it had before
+template <int LOSS, class... Scale>
+constexpr bool ba_loss_args() { return sizeof...(Scale) == (LOSS == XM_BA_LOSS_TRIVIAL ? 0 : 1); }
+
+// Y = Rcw P, X = Y + tcw: the camera-frame point of an observation, the eval kernel's expression (written out there, so that its trivial
+// instantiations keep the code they had before the losses)
+__device__ __forceinline__ void ba_point(const double *R, const double *T, const double *X3, double (&Y)[3], double (&X)[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        Y[a] = R[3 * a] * X3[0] + R[3 * a + 1] * X3[1] + R[3 * a + 2] * X3[2];
+        X[a] = Y[a] + T[a];
+    }
+}
+
+// ---- residuals and Jacobians at (Rcw, tcw, P), written in both list orders (scaled by sqrt(rho') under a robust loss); partial sums of
+// the cost 1/2 sum rho(|r|^2) and of the used observations
+template <int CD, int LOSS = XM_BA_LOSS_TRIVIAL, class... Scale>
 __global__ __launch_bounds__(256) void ba_eval_kernel(SchurLists S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
                                                       const double *__restrict__ P, double *__restrict__ Jc, double *__restrict__ Jl,
-                                                      double *__restrict__ parts) {
+                                                      double *__restrict__ parts, Scale... scale) {
+    static_assert(ba_loss_args<LOSS, Scale...>(), "a robust loss takes its scale, the trivial one nothing");
     constexpr int NP = ba_planes<CD>(), JP = ba_jp<CD>(), RS = ba_res<CD>();
     __shared__ double sh[4];
     double cost = 0.0, used = 0.0;
@@ -134,7 +181,15 @@ __global__ __launch_bounds__(256) void ba_eval_kernel(SchurLists S, const double
             }
             v[RS] = u0 - q0 / q2;
             v[RS + 1] = u1 - q1 / q2;
-            cost += 0.5 * (v[RS] * v[RS] + v[RS + 1] * v[RS + 1]);
+            if constexpr (LOSS == XM_BA_LOSS_TRIVIAL) {
+                cost += 0.5 * (v[RS] * v[RS] + v[RS + 1] * v[RS + 1]);
+            } else {
+                double rho1;
+                cost += 0.5 * ba_rho<LOSS>(v[RS] * v[RS] + v[RS + 1] * v[RS + 1], scale..., rho1);
+                const double c = sqrt(rho1);
+#pragma unroll
+                for (int k = 0; k < NP; ++k) v[k] *= c;
+            }
             used += 1.0;
         }
 #pragma unroll
@@ -562,11 +617,13 @@ __global__ __launch_bounds__(256) void ba_cand_lm_kernel(int64_t m, const double
     x2 = block_sum256(x2, sh);
     if (threadIdx.x == 0) { parts[blockIdx.x] = s2; parts[gridDim.x + blockIdx.x] = x2; }
 }
-// cost at the candidate and the linear model's terms sum r.(J d) + |J d|^2 / 2 (J, r: the current point, by-camera order)
-template <int CD>
+// cost 1/2 sum rho(|r|^2) at the candidate (the eval kernel's expression) and the linear model's terms sum r.(J d) + |J d|^2 / 2 (J, r: the
+// stored records of the current point, by-camera order)
+template <int CD, int LOSS = XM_BA_LOSS_TRIVIAL, class... Scale>
 __global__ __launch_bounds__(256) void ba_cost_kernel(SchurLists S, const double *__restrict__ Rn, const double *__restrict__ tn,
                                                       const double *__restrict__ Pn, const double *__restrict__ Jc, const double *__restrict__ dc,
-                                                      const double *__restrict__ dP, double *__restrict__ parts) {
+                                                      const double *__restrict__ dP, double *__restrict__ parts, Scale... scale) {
+    static_assert(ba_loss_args<LOSS, Scale...>(), "a robust loss takes its scale, the trivial one nothing");
     constexpr int JP = ba_jp<CD>(), RS = ba_res<CD>();
     __shared__ double sh[4];
     double cost = 0.0, model = 0.0;
@@ -580,7 +637,12 @@ __global__ __launch_bounds__(256) void ba_cost_kernel(SchurLists S, const double
 #pragma unroll
         for (int a = 0; a < 3; ++a) X[a] = R[3 * a] * X3[0] + R[3 * a + 1] * X3[1] + R[3 * a + 2] * X3[2] + T[a];
         const double e0 = X[0] / X[2] - q0 / q2, e1 = X[1] / X[2] - q1 / q2;
-        cost += 0.5 * (e0 * e0 + e1 * e1);
+        if constexpr (LOSS == XM_BA_LOSS_TRIVIAL) {
+            cost += 0.5 * (e0 * e0 + e1 * e1);
+        } else {
+            double rho1;
+            cost += 0.5 * ba_rho<LOSS>(e0 * e0 + e1 * e1, scale..., rho1);
+        }
         double jd0 = 0.0, jd1 = 0.0;
 #pragma unroll
         for (int k = 0; k < CD; ++k) {
@@ -598,6 +660,21 @@ __global__ __launch_bounds__(256) void ba_cost_kernel(SchurLists S, const double
     cost = block_sum256(cost, sh);
     model = block_sum256(model, sh);
     if (threadIdx.x == 0) { parts[blockIdx.x] = cost; parts[gridDim.x + blockIdx.x] = model; }
+}
+// |r_e|^2 per observation in input order at (Rcw, tcw, P) (the eval kernel's projection, unrobustified); -1 where the observation is not used
+__global__ __launch_bounds__(256) void ba_sqerr_kernel(SchurLists S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
+                                                       const double *__restrict__ P, double *__restrict__ sqerr) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < S.nobs; e += (int64_t)gridDim.x * 256) {
+        const double w = S.cam_w[S.pos_c[e]], q0 = S.obs_p[3 * e], q1 = S.obs_p[3 * e + 1], q2 = S.obs_p[3 * e + 2];
+        double sq = -1.0;
+        if (w > 0.0 && q2 > 0.0) {
+            double Y[3], X[3];
+            ba_point(Rcw + (size_t)9 * S.obs_cam[e], tcw + (size_t)3 * S.obs_cam[e], P + (size_t)3 * S.obs_lm[e], Y, X);
+            const double r0 = X[0] / X[2] - q0 / q2, r1 = X[1] / X[2] - q1 / q2;
+            sq = r0 * r0 + r1 * r1;
+        }
+        sqerr[e] = sq;
+    }
 }
 // scalars of the state word from the partials, in a fixed order (one workgroup): up to 6 sums and one max
 constexpr int kBaSums = 6;
@@ -649,15 +726,38 @@ struct PinnedState {
     ~PinnedState() { if (h) (void)hipHostFree(h); }
 };
 
+// the eval and cost kernels of the chosen loss (the trivial instantiations take no scale)
 template <int CD>
-void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out, hipStream_t st) {
-    const auto t_start = std::chrono::steady_clock::now();
-    const SchurLists S = SO.lists();
+void launch_eval(int loss, double a, int grid, hipStream_t st, const SchurLists &S, const double *R, const double *T, const double *P, double *Jc,
+                 double *Jl, double *parts) {
+    const dim3 g(grid), b(256);
+    switch (loss) {
+    case XM_BA_LOSS_HUBER: hipLaunchKernelGGL((ba_eval_kernel<CD, XM_BA_LOSS_HUBER, double>), g, b, 0, st, S, R, T, P, Jc, Jl, parts, a); break;
+    case XM_BA_LOSS_SOFT_L1: hipLaunchKernelGGL((ba_eval_kernel<CD, XM_BA_LOSS_SOFT_L1, double>), g, b, 0, st, S, R, T, P, Jc, Jl, parts, a); break;
+    case XM_BA_LOSS_CAUCHY: hipLaunchKernelGGL((ba_eval_kernel<CD, XM_BA_LOSS_CAUCHY, double>), g, b, 0, st, S, R, T, P, Jc, Jl, parts, a); break;
+    case XM_BA_LOSS_ARCTAN: hipLaunchKernelGGL((ba_eval_kernel<CD, XM_BA_LOSS_ARCTAN, double>), g, b, 0, st, S, R, T, P, Jc, Jl, parts, a); break;
+    default: hipLaunchKernelGGL((ba_eval_kernel<CD>), g, b, 0, st, S, R, T, P, Jc, Jl, parts);
+    }
+}
+template <int CD>
+void launch_cost(int loss, double a, int grid, hipStream_t st, const SchurLists &S, const double *Rn, const double *Tn, const double *Pn,
+                 const double *Jc, const double *dc, const double *dP, double *parts) {
+    const dim3 g(grid), b(256);
+    switch (loss) {
+    case XM_BA_LOSS_HUBER: hipLaunchKernelGGL((ba_cost_kernel<CD, XM_BA_LOSS_HUBER, double>), g, b, 0, st, S, Rn, Tn, Pn, Jc, dc, dP, parts, a); break;
+    case XM_BA_LOSS_SOFT_L1: hipLaunchKernelGGL((ba_cost_kernel<CD, XM_BA_LOSS_SOFT_L1, double>), g, b, 0, st, S, Rn, Tn, Pn, Jc, dc, dP, parts, a); break;
+    case XM_BA_LOSS_CAUCHY: hipLaunchKernelGGL((ba_cost_kernel<CD, XM_BA_LOSS_CAUCHY, double>), g, b, 0, st, S, Rn, Tn, Pn, Jc, dc, dP, parts, a); break;
+    case XM_BA_LOSS_ARCTAN: hipLaunchKernelGGL((ba_cost_kernel<CD, XM_BA_LOSS_ARCTAN, double>), g, b, 0, st, S, Rn, Tn, Pn, Jc, dc, dP, parts, a); break;
+    default: hipLaunchKernelGGL((ba_cost_kernel<CD>), g, b, 0, st, S, Rn, Tn, Pn, Jc, dc, dP, parts);
+    }
+}
+
+// the caller's parameters in the device layouts: Rcw = R_i^T (row-major), tcw = -R_i^T t_i, P by landmark slot
+void to_device_layout(const SchurOp &SO, const double *rot, const double *t, const double *p, std::vector<double> &hR, std::vector<double> &hT,
+                      std::vector<double> &hP) {
     const std::vector<int32_t> &slot_of = SO.slot_of();
-    const int64_t n = S.n, m = S.m, nobs = S.nobs;
-    constexpr int NP = ba_planes<CD>();
-    // ---- parameters on the device: Rcw = R_i^T (row-major), tcw = -R_i^T t_i, P by landmark slot
-    std::vector<double> hR((size_t)9 * n), hT((size_t)3 * n), hP((size_t)3 * m);
+    const int64_t n = SO.lists().n, m = SO.lists().m;
+    hR.assign((size_t)9 * n, 0.0); hT.assign((size_t)3 * n, 0.0); hP.assign((size_t)3 * m, 0.0);
     for (int64_t i = 0; i < n; ++i) {
         for (int a = 0; a < 3; ++a)
             for (int c = 0; c < 3; ++c) hR[(size_t)9 * i + 3 * a + c] = rot[(size_t)c + 3 * ((size_t)3 * i + a)];
@@ -669,8 +769,21 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
     }
     for (int64_t l = 0; l < m; ++l)
         for (int a = 0; a < 3; ++a) hP[(size_t)3 * slot_of[(size_t)l] + a] = p[(size_t)3 * l + a];
-    DevBuf<double> R[2], T[2], P[2];
-    for (int k = 0; k < 2; ++k) { R[k].alloc((size_t)9 * n, false); T[k].alloc((size_t)3 * n, false); P[k].alloc((size_t)3 * m, false); }
+}
+
+template <int CD>
+void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out, hipStream_t st) {
+    const auto t_start = std::chrono::steady_clock::now();
+    const SchurLists S = SO.lists();
+    const std::vector<int32_t> &slot_of = SO.slot_of();
+    const int64_t n = S.n, m = S.m, nobs = S.nobs;
+    constexpr int NP = ba_planes<CD>();
+    // ---- parameters on the device; three sets with non-monotonic steps (current, candidate, least cost so far), two otherwise
+    std::vector<double> hR, hT, hP;
+    to_device_layout(SO, rot, t, p, hR, hT, hP);
+    const bool nonmono = cfg.nonmonotonic;
+    DevBuf<double> R[3], T[3], P[3];
+    for (int k = 0; k < (nonmono ? 3 : 2); ++k) { R[k].alloc((size_t)9 * n, false); T[k].alloc((size_t)3 * n, false); P[k].alloc((size_t)3 * m, false); }
     XM_HIP_CHECK(hipMemcpyAsync(R[0].p, hR.data(), hR.size() * sizeof(double), hipMemcpyHostToDevice, st));
     XM_HIP_CHECK(hipMemcpyAsync(T[0].p, hT.data(), hT.size() * sizeof(double), hipMemcpyHostToDevice, st));
     XM_HIP_CHECK(hipMemcpyAsync(P[0].p, hP.data(), hP.size() * sizeof(double), hipMemcpyHostToDevice, st));
@@ -699,9 +812,9 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         wait_stream(st, cfg.watchdog_s, what);
         return *hs.h;
     };
-    int cur = 0;
+    int cur = 0, best = 0;   // the current point and the one of least cost so far (the same one without non-monotonic steps)
     auto eval = [&]() {
-        hipLaunchKernelGGL((ba_eval_kernel<CD>), dim3(ge), b256, 0, st, S, R[cur].p, T[cur].p, P[cur].p, Jc.p, Jl.p, pp + o_eval);
+        launch_eval<CD>(cfg.loss, cfg.loss_scale, ge, st, S, R[cur].p, T[cur].p, P[cur].p, Jc.p, Jl.p, pp + o_eval);
         BaReduce rd{};
         rd.sum_p[0] = pp + o_eval; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->cost;
         rd.sum_p[1] = pp + o_eval + ge; rd.sum_n[1] = ge; rd.sum_out[1] = &dst->used;
@@ -751,6 +864,11 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
 
     double radius = 1e4, nu = 2.0, F = 0.0, gmax = 0.0;
     int status = XM_BA_NO_CONVERGENCE, iters = 0, accepted = 0, tl = 0;
+    // non-monotonic steps: Ceres's TrustRegionStepEvaluator (Conn, Gould & Toint, Trust-Region Methods, Algorithm 10.1.2).  Costs of the
+    // minimum, the reference and the candidate point, the model decreases accumulated since the reference and the candidate, and the
+    // accepted steps since the last new minimum
+    double ev_min = 0.0, ev_ref = 0.0, ev_cand = 0.0, ev_dm_ref = 0.0, ev_dm_cand = 0.0;
+    int ev_steps = 0;
     int64_t pcg_total = 0;
     bool fresh = true, first = true;   // fresh: the point changed and its cost / gradient have not been read yet
     eval();
@@ -763,6 +881,7 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
             if (first) {
                 if (!std::isfinite(F)) throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: the initial reprojection cost is not finite (a point on a camera's focal plane?)");
                 out.initial_cost = F; out.n_used = (int64_t)s.used;
+                ev_min = ev_ref = ev_cand = F;
                 first = false;
             }
             fresh = false;
@@ -777,13 +896,13 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         // back-substitution dP = -V*^-1 (g + W^T dc), candidate, its cost and the model decrease
         hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)gl.p, -1.0,
                            (const int32_t *)lused.p, (const double *)x.p, (const BaState *)nullptr, dP.p);
-        const int nx = cur ^ 1;
+        int nx = 0;   // the candidate's parameter set: neither the current one nor the least-cost one (without non-monotonic steps: cur ^ 1)
+        while (nx == cur || nx == best) ++nx;
         hipLaunchKernelGGL((ba_cand_cam_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p, (const double *)x.p,
                            (const int32_t *)cused.p, R[nx].p, T[nx].p, pp + o_cand);
         hipLaunchKernelGGL(ba_cand_lm_kernel, dim3(gfl), b256, 0, st, m, (const double *)P[cur].p, (const double *)dP.p, (const int32_t *)lused.p,
                            P[nx].p, pp + o_cand + 2 * (size_t)gfc);
-        hipLaunchKernelGGL((ba_cost_kernel<CD>), dim3(ge), b256, 0, st, S, (const double *)R[nx].p, (const double *)T[nx].p, (const double *)P[nx].p,
-                           (const double *)Jc.p, (const double *)x.p, (const double *)dP.p, pp + o_cost);
+        launch_cost<CD>(cfg.loss, cfg.loss_scale, ge, st, S, R[nx].p, T[nx].p, P[nx].p, Jc.p, x.p, dP.p, pp + o_cost);
         BaReduce rd{};
         rd.sum_p[0] = pp + o_cost; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->cost_new;
         rd.sum_p[1] = pp + o_cost + ge; rd.sum_n[1] = ge; rd.sum_out[1] = &dst->model;
@@ -797,7 +916,8 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         const double step_norm = std::sqrt(s.step2[0] + s.step2[1]), x_norm = std::sqrt(s.x2[0] + s.x2[1]);
         const double Fn = s.cost_new, model_dec = -s.model;
         const bool valid = std::isfinite(Fn) && model_dec > 0.0;
-        const double rho = valid ? (F - Fn) / model_dec : -1.0;
+        double rho = valid ? (F - Fn) / model_dec : -1.0;
+        if (valid && nonmono) rho = std::max(rho, (ev_ref - Fn) / (ev_dm_ref + model_dec));   // Ceres's StepQuality
         const bool accept = valid && rho > 1e-3;
         if (tl < cfg.trace_cap && cfg.trace) {
             double *rec = cfg.trace + (size_t)6 * tl++;
@@ -809,6 +929,19 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
             radius = std::min(1e16, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3)));
             nu = 2.0;
             cur = nx;
+            if (!nonmono) {
+                best = cur;
+            } else {   // Ceres's StepAccepted
+                ev_dm_cand += model_dec; ev_dm_ref += model_dec;
+                if (Fn < ev_min) {
+                    ev_min = ev_cand = Fn; ev_dm_cand = 0.0; ev_steps = 0;
+                    best = cur;
+                } else {
+                    ++ev_steps;
+                    if (Fn > ev_cand) { ev_cand = Fn; ev_dm_cand = 0.0; }
+                }
+                if (ev_steps == cfg.max_nonmonotonic) { ev_ref = ev_cand; ev_dm_ref = ev_dm_cand; }
+            }
             const double Fold = F;
             F = Fn;
             eval();
@@ -819,6 +952,11 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
             nu *= 2.0;
             if (radius < 1e-32) { status = XM_BA_NO_PROGRESS; break; }
         }
+    }
+    if (best != cur) {   // non-monotonic steps: the caller gets the point of least cost, and its cost and gradient
+        cur = best;
+        eval();
+        fresh = true;
     }
     if (fresh) {   // the last accepted point: its gradient
         passes(1.0 / radius);
@@ -858,6 +996,23 @@ void bundle_adjust(const SchurOp &S, const BaSettings &cfg, double *rot, double 
     out = BaOutcome();
     if (cfg.fix_rotations) run<3>(S, cfg, rot, t, p, out, st);
     else run<6>(S, cfg, rot, t, p, out, st);
+}
+
+void reprojection_errors(const SchurOp &SO, const double *rot, const double *t, const double *p, double *sqerr, double watchdog_s, hipStream_t st) {
+    const SchurLists S = SO.lists();
+    std::vector<double> hR, hT, hP;
+    to_device_layout(SO, rot, t, p, hR, hT, hP);
+    DevBuf<double> R, T, P, out;
+    R.alloc(hR.size(), false); T.alloc(hT.size(), false); P.alloc(hP.size(), false); out.alloc((size_t)std::max<int64_t>(S.nobs, 1), false);
+    XM_HIP_CHECK(hipMemcpyAsync(R.p, hR.data(), hR.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    XM_HIP_CHECK(hipMemcpyAsync(T.p, hT.data(), hT.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    XM_HIP_CHECK(hipMemcpyAsync(P.p, hP.data(), hP.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    if (S.nobs > 0) {
+        hipLaunchKernelGGL(ba_sqerr_kernel, dim3(flat_grid(S.nobs)), dim3(256), 0, st, S, (const double *)R.p, (const double *)T.p, (const double *)P.p, out.p);
+        check_launch("the reprojection errors");
+        XM_HIP_CHECK(hipMemcpyAsync(sqerr, out.p, (size_t)S.nobs * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    wait_stream(st, watchdog_s, "the reprojection errors");
 }
 
 }  // namespace xm

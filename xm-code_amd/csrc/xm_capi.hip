@@ -1,6 +1,7 @@
 // xm_capi.hip — extern "C" boundary (include/xm_amd.h).  No exceptions cross it.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <fstream>
 #include <mutex>
@@ -291,16 +292,26 @@ int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int
 int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, xm_ba_result_t *res) {
     XM_TRY
     if (!ctx || !opt || !res || !rot || !t || !p) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: null argument");
-    if (opt->struct_size != sizeof(xm_ba_options_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: xm_ba_options_t.struct_size is not sizeof(xm_ba_options_t)");
+    static_assert(offsetof(xm_ba_options_t, loss) == XM_BA_OPTIONS_SIZE_V1, "the first version of xm_ba_options_t ends at trace");
+    if (opt->struct_size != sizeof(xm_ba_options_t) && opt->struct_size != XM_BA_OPTIONS_SIZE_V1)
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: xm_ba_options_t.struct_size is neither sizeof(xm_ba_options_t) nor XM_BA_OPTIONS_SIZE_V1");
     if (res->struct_size != sizeof(xm_ba_result_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: xm_ba_result_t.struct_size is not sizeof(xm_ba_result_t)");
     if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: single-GPU contexts only (not n_gpus > 1)");
     if (ctx->impl->world() > 1) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: single-rank contexts only");
-    const xm_ba_options_t o = *opt;
+    xm_ba_options_t o;   // a caller of the first version: the fields it does not have are 0 (trivial loss, monotonic steps)
+    std::memset(&o, 0, sizeof(o));
+    std::memcpy(&o, opt, opt->struct_size);
     auto bad = [](double v) { return !(v >= 0.0) || !std::isfinite(v); };
     if (!(o.eta > 0.0 && o.eta < 1.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: eta must lie in (0, 1)");
     if (o.max_iters < 0 || bad(o.max_time) || bad(o.function_tol) || bad(o.gradient_tol) || bad(o.parameter_tol))
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: negative or non-finite setting");
-    if (o.flags & ~XM_BA_FIX_ROTATIONS) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: unknown flag");
+    if (o.flags & ~(XM_BA_FIX_ROTATIONS | XM_BA_NONMONOTONIC)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: unknown flag");
+    if (o.loss < XM_BA_LOSS_TRIVIAL || o.loss > XM_BA_LOSS_ARCTAN) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: unknown loss");
+    if (o.loss == XM_BA_LOSS_TRIVIAL && o.loss_scale != 0.0)
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: loss_scale is given but the loss is trivial");
+    if (o.loss != XM_BA_LOSS_TRIVIAL && !(std::isfinite(o.loss_scale) && o.loss_scale > 0.0))
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: a robust loss needs a finite loss_scale > 0");
+    if (o.max_nonmonotonic < 0) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: max_nonmonotonic is negative");
     if (o.trace_cap < 0 || (o.trace_cap > 0 && !o.trace)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: trace_cap > 0 needs a trace array");
     const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks();
     for (int64_t k = 0; k < 9 * n; ++k)
@@ -317,6 +328,9 @@ int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot,
     if (o.parameter_tol > 0.0) c.parameter_tol = o.parameter_tol;
     c.eta = o.eta;
     c.fix_rotations = (o.flags & XM_BA_FIX_ROTATIONS) != 0;
+    c.loss = o.loss; c.loss_scale = o.loss_scale;
+    c.nonmonotonic = (o.flags & XM_BA_NONMONOTONIC) != 0;
+    if (o.max_nonmonotonic > 0) c.max_nonmonotonic = o.max_nonmonotonic;
     c.trace_cap = o.trace_cap; c.trace = o.trace;
     xm::BaOutcome r;
     ctx->impl->bundle_adjust(c, rot, t, p, r);
@@ -327,6 +341,22 @@ int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot,
     out.initial_cost = r.initial_cost; out.final_cost = r.final_cost; out.gradient_max = r.gradient_max; out.seconds = r.seconds;
     out.trace_len = r.trace_len;
     *res = out;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_ctx_reprojection_errors(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, double *sqerr) {
+    XM_TRY
+    if (!ctx || !rot || !t || !p || !sqerr) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: null argument");
+    if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: single-GPU contexts only (not n_gpus > 1)");
+    if (ctx->impl->world() > 1) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: single-rank contexts only");
+    const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks();
+    for (int64_t k = 0; k < 9 * n; ++k)
+        if (!std::isfinite(rot[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: rotations are not finite");
+    for (int64_t k = 0; k < 3 * n; ++k)
+        if (!std::isfinite(t[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: translations are not finite");
+    for (int64_t k = 0; k < 3 * m; ++k)
+        if (!std::isfinite(p[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: landmarks are not finite");
+    ctx->impl->reprojection_errors(rot, t, p, sqerr);
     return XM_OK;
     XM_CATCH
 }

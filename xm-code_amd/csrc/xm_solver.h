@@ -199,6 +199,7 @@ public:
     void recover_tp(const double *rot, const double *scale, double *t, double *p);   // matrix-free storage only
     // reprojection bundle adjustment of a recovered solution (xm_ba.h): matrix-free storage, one rank; reads the context, changes nothing in it
     void bundle_adjust(const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out);
+    void reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr);   // per observation, input order (xm_ba.h)
     // XM^2 with the reference's residual definition (3_test_colmap_glomap.py:305-316): squared distance per edge / observation of the
     // RECOVERED solution (anchored rotations rot 3 x 3n column-major, scales) -- res: host, input order
     void edge_residuals_recovered(const double *rot, const double *scale, double *res);

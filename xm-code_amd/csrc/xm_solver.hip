@@ -1821,6 +1821,12 @@ void Context::bundle_adjust(const BaSettings &cfg, double *rot, double *t, doubl
     c.watchdog_s = cfg_.watchdog_s;
     xm::bundle_adjust(*schur_, c, rot, t, p, out, st_);
 }
+void Context::reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr) {
+    if (storage_ != XM_STORAGE_SCHUR || !schur_)
+        throw Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: single-rank contexts only");
+    xm::reprojection_errors(*schur_, rot, t, p, sqerr, cfg_.watchdog_s, st_);
+}
 int64_t Context::n_landmarks() const { return schur_ ? schur_->n_landmarks() : 0; }
 bool Context::schur_info(int64_t out[3], double *relres) const {
     if (!schur_ || !schur_->uses_pcg()) return false;

@@ -35,7 +35,7 @@ EXPORTS = [
     "xm_ctx_attach_edges", "xm_ctx_edge_residuals", "xm_ctx_edge_residuals_recovered", "xm_ctx_xm2_filter", "xm_ctx_xm2_round", "xm_ctx_set_edge_weights", "xm_ctx_recover_tp", "xm_ctx_schur_info", "xm_ctx_qw", "xm_spd_inverse", "xm_ctx_transport", "xm_ctx_sell_wpad", "xm_ctx_product_kind", "xm_symw_plan", "xm_symw_use",
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
-    "xm_ctx_bundle_adjust",
+    "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -91,7 +91,7 @@ class Xm2Info(C.Structure):
 class BaOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_iters", C.c_int32), ("max_time", C.c_double), ("eta", C.c_double),
                 ("function_tol", C.c_double), ("gradient_tol", C.c_double), ("parameter_tol", C.c_double), ("flags", C.c_uint32),
-                ("trace_cap", C.c_int32), ("trace", C.c_void_p)]
+                ("trace_cap", C.c_int32), ("trace", C.c_void_p), ("loss", C.c_int32), ("max_nonmonotonic", C.c_int32), ("loss_scale", C.c_double)]
 
 
 class BaResult(C.Structure):
@@ -101,6 +101,9 @@ class BaResult(C.Structure):
 
 
 BA_FIX_ROTATIONS = 1
+BA_NONMONOTONIC = 2
+BA_LOSS = {"trivial": 0, "huber": 1, "soft_l1": 2, "cauchy": 3, "arctan": 4}
+BA_OPTIONS_SIZE_V1 = 64        # struct_size of callers built before loss, max_nonmonotonic and loss_scale (include/xm_amd.h)
 BA_STATUS = {0: "no_convergence", 1: "function_tolerance", 2: "gradient_tolerance", 3: "parameter_tolerance", 4: "max_iterations",
              5: "time_limit", 6: "no_progress"}
 BA_CONVERGED = (1, 2, 3)
@@ -138,6 +141,7 @@ def lib():
         L.xm_ctx_xm2_round.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Options), C.POINTER(Xm2Info), C.POINTER(Result)]
         L.xm_ctx_recover_tp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_bundle_adjust.argtypes = [C.c_void_p, C.POINTER(BaOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaResult)]
+        L.xm_ctx_reprojection_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_transport.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
         L.xm_ctx_schur_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_double)]
         L.xm_ctx_schur_precond_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
@@ -644,18 +648,25 @@ class Context:
         return np.ascontiguousarray(t), np.ascontiguousarray(p)
 
     def bundle_adjust(self, rot, t, P, fix_rotations=False, max_iters=1000, max_time=300.0, eta=0.1, function_tol=1e-6,
-                      gradient_tol=1e-10, parameter_tol=1e-8, trace=0):
+                      gradient_tol=1e-10, parameter_tol=1e-8, trace=0, loss="trivial", loss_scale=0.0, nonmonotonic=False, max_nonmonotonic=0):
         """reprojection bundle adjustment of a recovered solution (the reference's Ceres refinement, xm_ctx_bundle_adjust): rot 3 x 3n
         (R_i), t 3 x n, P 3 x m as recover_rotations / recover_tp return them -> refined (rot, t, P, info); matrix-free contexts only.
+        loss: a BA_LOSS name with its scale loss_scale (Ceres's a, in normalised image units: pixels / focal length); nonmonotonic=True:
+        Ceres's non-monotonic steps (the reference's configuration), reference cost reset after max_nonmonotonic (0 = 5) steps without a
+        new minimum, the least-cost point returned.
         info: status (BA_STATUS), iters, accepted, pcg_iters, n_used, initial_cost, final_cost, gradient_max, seconds, and with trace > 0
-        "trace": one row per LM iteration (cost, candidate cost, mu, accepted, PCG iterations, PCG relative residual)"""
+        "trace": one row per LM iteration (cost, candidate cost, mu, accepted, PCG iterations, PCG relative residual); costs are
+        1/2 sum rho(|r|^2)"""
         rot = np.array(rot, dtype=np.float64, order="F"); t = np.array(t, dtype=np.float64, order="F"); P = np.array(P, dtype=np.float64, order="F")
         assert rot.shape == (3, 3 * self.n) and t.shape == (3, self.n) and P.shape == (3, self.n_landmarks)
+        if loss not in BA_LOSS:
+            raise XmError(f"unknown loss {loss!r} (one of {', '.join(BA_LOSS)})")
         opt = BaOptions(); res = BaResult()
         opt.struct_size, res.struct_size = C.sizeof(BaOptions), C.sizeof(BaResult)
         opt.max_iters, opt.max_time, opt.eta = int(max_iters), float(max_time), float(eta)
         opt.function_tol, opt.gradient_tol, opt.parameter_tol = float(function_tol), float(gradient_tol), float(parameter_tol)
-        opt.flags = BA_FIX_ROTATIONS if fix_rotations else 0
+        opt.flags = (BA_FIX_ROTATIONS if fix_rotations else 0) | (BA_NONMONOTONIC if nonmonotonic else 0)
+        opt.loss, opt.loss_scale, opt.max_nonmonotonic = BA_LOSS[loss], float(loss_scale), int(max_nonmonotonic)
         tr = None
         if trace:
             tr = np.zeros((int(trace), 6)); opt.trace_cap = int(trace); opt.trace = tr.ctypes.data_as(C.c_void_p)
@@ -666,6 +677,17 @@ class Context:
         if tr is not None:
             info["trace"] = tr[: res.trace_len].copy()
         return rot, t, P, info
+
+    def reprojection_errors(self, rot, t, P):
+        """|r_e|^2 (unrobustified) of every observation in input order at (rot, t, P) -- the layouts of bundle_adjust -- with the
+        context's current weights, -1 where the adjustment does not use the observation (weight <= 0 or p_e2 <= 0): an (nobs,) array"""
+        rot = np.asfortranarray(np.asarray(rot, dtype=np.float64)); t = np.asfortranarray(np.asarray(t, dtype=np.float64))
+        P = np.asfortranarray(np.asarray(P, dtype=np.float64))
+        assert rot.shape == (3, 3 * self.n) and t.shape == (3, self.n) and P.shape == (3, self.n_landmarks)
+        out = np.zeros(self.ne)
+        _chk(lib().xm_ctx_reprojection_errors(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p),
+                                              out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def edge_residuals_recovered(self, rot, scale):
         """squared distance per edge / observation of a RECOVERED solution (rot 3 x 3n, scale n): the reference's XM^2 residual"""
