@@ -360,6 +360,14 @@ int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int
  * struct had them; it means the trivial loss and monotonic steps); max_iters, max_time, function_tol, gradient_tol, parameter_tol: 0 = the
  * defaults (1000, 300, 1e-6, 1e-10, 1e-8); eta is required and lies in (0, 1) (Ceres's is 0.1).  trace: trace_cap x 6 doubles, one record
  * per LM iteration: cost, candidate cost, mu, accepted (0 / 1), PCG iterations, PCG relative residual.
+ * XM_BA_DENSE_SCHUR (Ceres's linear_solver_type = DENSE_SCHUR): every LM iteration solves the reduced camera system (U* - sum W V*^-1 W^T)
+ * dc = b exactly over all CD n rows instead of by PCG: S is assembled densely on the device (the lower block triangle, fixed-order sums, no
+ * atomics), factored by Cholesky and solved by two triangular substitutions; everything else in the iteration is unchanged, and eta is
+ * validated but not read.  A camera without a used observation has the block mu 1e-6 I and right-hand side 0 (its step is 0).  A pivot
+ * that is not positive or a non-finite solution makes the step invalid (radius /= nu, nu *= 2, as a step without model decrease).
+ * pcg_iters = 0; trace column 4 = 0 and column 5 = |b - S dc| / |b| with S applied matrix-free (a check of assembly and solve; -1 after a
+ * failed factorisation).  The CD n x CD n matrix is allocated inside the call and freed before it returns: CD n > XM_BA_DENSE_MAX_ROWS is
+ * XM_ERR_ARG, a failed allocation XM_ERR_NOMEM (both leave the context unchanged and usable).
  * XM_ERR_ARG (context unchanged and usable): not XM_STORAGE_SCHUR, several ranks or a communicator, a struct_size other than those two,
  * null arrays, non-finite input, eta outside (0, 1), negative settings, unknown flags, an unknown loss, a robust loss whose loss_scale is
  * not finite and > 0, loss_scale != 0 with the trivial loss, max_nonmonotonic < 0.  The call reads the context and changes nothing in it
@@ -370,6 +378,8 @@ int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int
  * finding the outliers after it (xm_ctx_set_edge_weights can then drop them before the next solve). */
 #define XM_BA_FIX_ROTATIONS 1u          /* the reference's only_landmarks = True: rotations constant (bit-identical), t and P free */
 #define XM_BA_NONMONOTONIC  2u          /* Ceres's non-monotonic steps (see above) */
+#define XM_BA_DENSE_SCHUR   16u         /* Ceres's DENSE_SCHUR (see below) instead of ITERATIVE_SCHUR; 4 and 8 are not flags */
+#define XM_BA_DENSE_MAX_ROWS 32768      /* XM_BA_DENSE_SCHUR: largest CD n (CD = 6, or 3 with XM_BA_FIX_ROTATIONS): an 8.6 GB matrix */
 #define XM_BA_LOSS_TRIVIAL  0
 #define XM_BA_LOSS_HUBER    1
 #define XM_BA_LOSS_SOFT_L1  2
@@ -440,6 +450,10 @@ int xm_qw_bsr3(const int64_t *d_rowptr, const int32_t *d_colidx, const double *d
  * (blocked Cholesky + triangular solves, xm-code_amd/csrc/xm_dense_la.hip): the set-up step of XM_STORAGE_SCHUR, which the reference
  * does on the host with scipy.linalg.solve (utils/creatematrix.py:260). */
 int xm_spd_inverse(int64_t n, double *A);
+/* B (host, column-major n x k) is overwritten by A^-1 B for A (host, column-major n x n, symmetric positive definite; only the lower
+ * triangle is read), by the Cholesky factorisation and the two triangular substitutions of the dense Schur solver of xm_ctx_bundle_adjust
+ * (xm_dense_la.hip).  XM_ERR_ARG: n outside [1, 46000], k < 1, null arrays, a pivot that is not positive or a non-finite solution. */
+int xm_spd_solve(int64_t n, int64_t k, const double *A, double *B);
 
 /* Work decomposition of the half-traffic symmetric dense product (xm_qw_dense_sym, vertical sweep) for n cameras, host-only (CPU
  * test of the index arithmetic, tests/test_symv_layout.py): plan = { K steps (of two cameras) per chunk, Kf for the strip groups

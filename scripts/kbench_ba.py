@@ -7,7 +7,11 @@ streams (a model of the kernels' loads and stores), at two sizes:
 (--loss: one of xmamd.BA_LOSS with its scale A in normalised image units; --nonmonotonic: Ceres's non-monotonic steps.)
 Per LM iteration: runs of exactly K LM iterations (stop tolerances 1e-300) at eta = 0.1 and 1e-4.  Per PCG iteration: ONE LM iteration
 from the same start at eta = 0.1 and at eta = 1e-10 (identical work apart from the PCG), best of three each; (time difference) / (PCG
-iteration difference)."""
+iteration difference).
+   python scripts/kbench_ba.py --solver dense [--seq 500,1000,2000,5000] [--iters K] [--no-converge] [--out ...]
+compares the dense Schur solver (linear_solver="dense_schur") with the PCG at eta 0.1 and 1e-6 on SIMPLE2 and on sequential captures
+(xm_ba_numpy.sequential_scene, seeds 62 / 63 as in the tests) instead: time per LM iteration over K iterations, then LM iterations, wall
+time and final cost of a run to function_tol 1e-8 (at most 200 iterations or 120 s).  The sphere scene is above XM_BA_DENSE_MAX_ROWS."""
 import os
 import sys
 import time
@@ -97,11 +101,46 @@ def bench(name, obs, n, m, rot0, t0, P0):
         f"{by / max(per_pcg, 1e-12) / 1e9:7.1f} GB/s")
 
 
+SOLVERS = [("dense", dict(linear_solver="dense_schur")), ("eta 0.1", dict(eta=0.1)), ("eta 1e-6", dict(eta=1e-6))]
+
+
+def bench_solvers(name, obs, n, m, rot0, t0, P0):
+    ctx = xmamd.Context(obs=obs, n=n)
+    log(f"{name}: {n} cameras ({6 * n} rows in the reduced camera system), {m} landmarks, {obs[0].size} observations")
+    for label, kw in SOLVERS:
+        ctx.bundle_adjust(rot0, t0, P0, max_iters=1, **kw, **LOSS)      # warm-up: code objects, allocations
+        t = time.time()
+        _, _, _, inf = ctx.bundle_adjust(rot0, t0, P0, max_iters=K, trace=K, function_tol=1e-300, gradient_tol=1e-300, parameter_tol=1e-300,
+                                         **kw, **LOSS)
+        tt = time.time() - t
+        log(f"  {label:9s} K = {inf['iters']}: {inf['seconds'] * 1e3 / max(1, inf['iters']):9.3f} ms per LM iteration ({tt * 1e3:9.2f} ms wall), "
+            f"{inf['pcg_iters']} PCG iterations, max per step {int(inf['trace'][:, 4].max())}, largest |b - S dc| / |b| {inf['trace'][:, 5].max():.2e}")
+    if "--no-converge" not in sys.argv:
+        for label, kw in SOLVERS:
+            t = time.time()
+            _, _, _, inf = ctx.bundle_adjust(rot0, t0, P0, max_iters=200, max_time=120.0, function_tol=1e-8, **kw, **LOSS)
+            tt = time.time() - t
+            log(f"  {label:9s} to function_tol 1e-8: {inf['iters']:4d} LM iterations ({inf['accepted']} accepted), {tt:8.3f} s wall, "
+                f"{inf['pcg_iters']} PCG iterations, cost {inf['initial_cost']:.6e} -> {inf['final_cost']:.12e} ({inf['status_name']})")
+    ctx.close()
+
+
 log(f"kbench_ba: {time.strftime('%Y-%m-%d %H:%M:%S')}  K = {K} LM iterations per run; loss {LOSS['loss']} (scale {LOSS['loss_scale']:g})"
     f"{', non-monotonic steps' if LOSS['nonmonotonic'] else ''}")
 G = os.path.join(ROOT, "tests", "golden", "simple2")
 Z = np.load(os.path.join(G, "obs.npz"))
 ref = np.load(os.path.join(G, "tp.npz"))
+if arg("--solver", "iterative") == "dense":
+    bench_solvers("SIMPLE2 (the reference's R_real, t_est, p_est)", (Z["cam"], Z["lm"], Z["p"], Z["w"].reshape(-1)), ref["t_est"].shape[1],
+                  ref["p_est"].shape[1], ref["R_real"], ref["t_est"], ref["p_est"])
+    for nc in [int(v) for v in arg("--seq", "500,1000,2000,5000").split(",") if v]:
+        S = ba.sequential_scene(n_cams=nc, seed=62, noise=1e-3)
+        rot0, t0, P0 = ba.perturb(S["rot"], S["t"], S["P"], seed=63, deg=0.5, rel=2e-4)
+        bench_solvers(f"sequential capture of {nc} cameras", (S["cam"], S["lm"], S["p"], S["w"]), S["n"], S["m"], rot0, t0, P0)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 bench("SIMPLE2 (the reference's R_real, t_est, p_est)", (Z["cam"], Z["lm"], Z["p"], Z["w"].reshape(-1)), ref["t_est"].shape[1], ref["p_est"].shape[1],
       ref["R_real"], ref["t_est"], ref["p_est"])
 t = time.time()

@@ -11,6 +11,9 @@
 //   cameras     U_i, g_i, S_ii = U*_i - sum W V*^-1 W^T, its Cholesky inverse, b_i = -g_i + sum W V*^-1 g_l      wavefront per camera
 //   PCG         S dc = b from zero, S applied as U* x - sum W V*^-1 W^T x through the two lists, block-Jacobi preconditioner, batches that
 //               run ahead of the host and are polled through a state word (as SchurOp::pcg_solve)
+//   or dense    (XM_BA_DENSE_SCHUR) S assembled as a dense lower block triangle (wavefront per block row), Cholesky factor and two
+//               triangular substitutions (xm_dense_la.hip); a pivot that is not positive or a non-finite solution makes the step invalid
+//               (flag in the state word, read with the candidate's scalars); |b - S dc| / |b| through the matrix-free product for the trace
 //   back-subst  dP_l = -V*_l^-1 (g_l + sum W^T dc)
 //   candidate   Rcw <- Exp(dtheta) Rcw, tcw += dt, P += dP; its cost and the model decrease; ONE read of the scalars by the host
 // Every sum over observations is a fixed-order sum (lane-strided lists + DPP trees, per-workgroup partials added in a fixed order): two
@@ -41,8 +44,10 @@ struct BaSettings {
     double loss_scale = 0.0;      // Ceres's a (normalised image units); robust losses only
     bool nonmonotonic = false;    // XM_BA_NONMONOTONIC
     int max_nonmonotonic = 5;     // Ceres's max_consecutive_nonmonotonic_steps
+    bool dense_schur = false;     // XM_BA_DENSE_SCHUR: the reduced camera system assembled densely and solved by Cholesky (eta unused)
     int trace_cap = 0;
     double *trace = nullptr;      // trace_cap x 6 row-major: cost, candidate cost, mu, accepted, PCG iterations, PCG relative residual
+                                  // (dense Schur: 0 and |b - S dc| / |b| with S applied matrix-free, -1 after a failed factorisation)
     double watchdog_s = 600.0;    // host waits give up after this long
 };
 struct BaOutcome {

@@ -31,6 +31,8 @@ struct BaState {              // device-resident; the host reads it whole
     double cost, used, gmax;  // at the current point: F, used observations, |J^T r|_inf
     double cost_new, model;   // candidate: F, sum r.Jd + |Jd|^2 / 2
     double step2[2], x2[2];   // |d|^2, |x|^2: cameras, landmarks
+    double res2[2];           // dense Schur: |b - S dc|^2, |b|^2
+    int32_t fail, pad;        // dense Schur: 1 = the factorisation or a substitution failed (cleared before each factorisation)
 };
 
 __device__ __forceinline__ double clamp_diag(double d) { return fmin(fmax(d, 1e-6), 1e32); }
@@ -555,6 +557,103 @@ __global__ __launch_bounds__(256) void ba_pcg_upd_kernel(BaPcg a, int it) {
     if (threadIdx.x == 0) { a.prz[(it & 1) ^ 1][blockIdx.x] = rzn; a.prr[blockIdx.x] = rr; }
 }
 
+// ---- dense reduced camera system (XM_BA_DENSE_SCHUR): the lower block triangle of
+//   S_ij = delta_ij U*_i - sum_l (sum_{e in (i,l)} W_e) V*_l^-1 (sum_{f in (j,l)} W_f)^T,   j <= i,
+// column-major with leading dimension ld = CD n, into a matrix the caller has zeroed.  A wavefront per block row i: it writes U*_i, then walks
+// camera i's list in list order; for observation e of landmark l the lanes run over l's list (the packed group of a light landmark, the
+// contiguous list of a heavy one, 64 at a time) and lane f subtracts (W_e V*_l^-1) W_f^T from block (i, camera of f).  Every pair (e, f) of a
+// landmark is taken, so a (camera, landmark) pair named twice brings its cross terms.  Two lanes of one batch on the same block (such a pair
+// again) write one after the other, in lane order, behind a workgroup fence each time: the additions to every entry come in a fixed order
+// and no floating-point atomics are used.  Only this wavefront writes row i, so nothing else orders them.
+template <int CD>
+__global__ __launch_bounds__(256) void ba_schur_dense_kernel(SchurLists S, const double *__restrict__ Jc, const double *__restrict__ Jl,
+                                                             const double *__restrict__ vinv, const double *__restrict__ ustar, double *__restrict__ Sd,
+                                                             int64_t ld) {
+    constexpr int JP = ba_jp<CD>();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t i = (int64_t)blockIdx.x * kQwWaves + wv;
+    if (i >= S.n) return;
+    double *row = Sd + (size_t)CD * i;   // entry (CD i + a, c) at row[a + c ld]
+    if (lane < CD * CD) row[lane / CD + ((size_t)CD * i + lane % CD) * ld] = ustar[(size_t)CD * CD * i + lane];
+    __threadfence_block();
+    for (int64_t e = S.cam_ptr[i]; e < S.cam_ptr[i + 1]; ++e) {
+        double jc[2 * CD], jp[6];
+#pragma unroll
+        for (int k = 0; k < 2 * CD; ++k) jc[k] = Jc[(size_t)k * S.nobs + e];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) jp[k] = Jc[(size_t)(JP + k) * S.nobs + e];
+        if (!obs_used(jp)) continue;
+        const int64_t l = S.cam_lm[e];
+        double V[3][3], X[CD][3];
+        sym3(vinv + (size_t)6 * l, V);
+#pragma unroll
+        for (int k = 0; k < CD; ++k) {
+            double w[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) w[c] = jc[k] * jp[c] + jc[CD + k] * jp[3 + c];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) X[k][c] = w[0] * V[0][c] + w[1] * V[1][c] + w[2] * V[2][c];
+        }
+        int64_t f0, cnt, stride;
+        if (l < S.nheavy) { f0 = S.lm_ptr[l]; cnt = S.lm_ptr[l + 1] - f0; stride = 1; }
+        else { const int64_t t = l - S.nheavy; f0 = S.gbase[t >> 6] + (t & 63); cnt = S.deg[l]; stride = 64; }
+        for (int64_t k0 = 0; k0 < cnt; k0 += 64) {
+            const int nb = (int)(cnt - k0 < 64 ? cnt - k0 : 64);
+            int j = -1;
+            double C[CD][CD];
+            if (lane < nb) {
+                const size_t f = (size_t)(f0 + (k0 + lane) * stride);
+                double jc2[2 * CD], jp2[6];
+#pragma unroll
+                for (int k = 0; k < 2 * CD; ++k) jc2[k] = Jl[(size_t)k * S.lm_total + f];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) jp2[k] = Jl[(size_t)(JP + k) * S.lm_total + f];
+                const int jf = S.lm_cam[f];
+                if (jf <= i && obs_used(jp2)) {
+                    j = jf;
+#pragma unroll
+                    for (int b = 0; b < CD; ++b) {
+                        double w[3];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) w[c] = jc2[b] * jp2[c] + jc2[CD + b] * jp2[3 + c];
+#pragma unroll
+                        for (int a = 0; a < CD; ++a) C[a][b] = X[a][0] * w[0] + X[a][1] * w[1] + X[a][2] * w[2];
+                    }
+                }
+            }
+            int rank = 0;   // earlier lanes of this batch on the same block
+            for (int q = 0; q < nb; ++q) {
+                const int jq = __builtin_amdgcn_readlane(j, q);
+                rank += (q < lane && jq >= 0 && jq == j) ? 1 : 0;
+            }
+            const int rmax = (int)wave_max((double)rank);
+            for (int r = 0; r <= rmax; ++r) {
+                if (j >= 0 && rank == r) {
+                    double *blk = row + (size_t)CD * j * ld;
+#pragma unroll
+                    for (int b = 0; b < CD; ++b)
+#pragma unroll
+                        for (int a = 0; a < CD; ++a) blk[a + (size_t)b * ld] -= C[a][b];
+                }
+                __threadfence_block();
+            }
+        }
+    }
+}
+// per-workgroup partials of |b - S dc|^2 and |b|^2 (S dc from the matrix-free product)
+template <int CD>
+__global__ __launch_bounds__(256) void ba_dense_res_kernel(int64_t n, const double *__restrict__ b, const double *__restrict__ sx, double *__restrict__ parts) {
+    __shared__ double sh[4];
+    double rr = 0.0, bb = 0.0;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n * CD; k += (int64_t)gridDim.x * 256) {
+        const double d = b[k] - sx[k];
+        rr += d * d; bb += b[k] * b[k];
+    }
+    rr = block_sum256(rr, sh);
+    bb = block_sum256(bb, sh);
+    if (threadIdx.x == 0) { parts[blockIdx.x] = rr; parts[gridDim.x + blockIdx.x] = bb; }
+}
+
 // ---- candidate point.  Cameras: Rcw <- Exp(dtheta) Rcw (Rodrigues), tcw += dt; cameras without a used observation are copied.
 template <int CD>
 __global__ __launch_bounds__(256) void ba_cand_cam_kernel(int64_t n, const double *__restrict__ Rcw, const double *__restrict__ tcw,
@@ -833,6 +932,41 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
     a.b = b.p; a.sinv = sinv.p; a.ustar = ustar.p; a.x = x.p; a.r = r.p; a.z = z.p; a.p = pv.p; a.Ap = Ap.p;
     a.prz[0] = pp + o_pcg; a.prz[1] = pp + o_pcg + gfc; a.prr = pp + o_pcg + 2 * gfc; a.pbb = pp + o_pcg + 3 * gfc; a.ppap = pp + o_pcg + 4 * gfc;
     a.st = dst;
+    // dense Schur: the CD n x CD n matrix, allocated here and freed on return; the substitutions' scratch vector
+    const int64_t nd = (int64_t)CD * n;
+    DevBuf<double> Sd, ysub;
+    if (cfg.dense_schur) {
+        if (nd > XM_BA_DENSE_MAX_ROWS) throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: the dense Schur system has more than XM_BA_DENSE_MAX_ROWS rows");
+        const size_t elems = (size_t)nd * (size_t)nd;
+        if (hipMalloc((void **)&Sd.p, elems * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            Sd.p = nullptr;
+            throw Error(XM_ERR_NOMEM, "xm_ctx_bundle_adjust: no device memory for the dense Schur system (" + std::to_string(elems * 8 >> 20) + " MB)");
+        }
+        Sd.count = Sd.capacity = elems;
+        ysub.alloc((size_t)nd);
+    }
+    // S dc = b exactly: assembly, Cholesky, substitutions (dc -> x); then |b - S dc|^2 and |b|^2 with S applied through the matrix-free
+    // kernels of the PCG (the state word's done flag is never set on this path).  Nothing is read by the host here.
+    auto dense_solve = [&]() {
+        XM_HIP_CHECK(hipMemsetAsync(Sd.p, 0, Sd.count * sizeof(double), st));
+        XM_HIP_CHECK(hipMemsetAsync(&dst->fail, 0, sizeof(int32_t), st));
+        hipLaunchKernelGGL((ba_schur_dense_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)Jl.p, (const double *)vinv.p,
+                           (const double *)ustar.p, Sd.p, nd);
+        spd_cholesky_device((int)nd, Sd.p, nd, &dst->fail, st);
+        XM_HIP_CHECK(hipMemcpyAsync(x.p, b.p, (size_t)nd * sizeof(double), hipMemcpyDeviceToDevice, st));
+        spd_substitute_device((int)nd, Sd.p, nd, x.p, ysub.p, nd, 1, &dst->fail, st);
+        BaPcg ar = a;
+        ar.p = x.p;
+        hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)nullptr, 1.0,
+                           (const int32_t *)lused.p, (const double *)x.p, (const BaState *)nullptr, y.p);
+        hipLaunchKernelGGL((ba_camx_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)y.p, ar);
+        hipLaunchKernelGGL((ba_dense_res_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)b.p, (const double *)Ap.p, pp + o_pcg);
+        BaReduce rd{};
+        rd.sum_p[0] = pp + o_pcg; rd.sum_n[0] = gfc; rd.sum_out[0] = &dst->res2[0];
+        rd.sum_p[1] = pp + o_pcg + gfc; rd.sum_n[1] = gfc; rd.sum_out[1] = &dst->res2[1];
+        reduce(rd);
+    };
     int pcg_last = 8;
     // PCG from zero: batches enqueued ahead of the host (as many iterations as the last solve needed + 2, then steps of 8), one read per batch
     auto pcg = [&](int &iters, double &relres) {
@@ -891,7 +1025,8 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         if (secs_since(t_start) >= cfg.max_time) { status = XM_BA_TIME_LIMIT; break; }
         int pit = 0;
         double relres = 0.0;
-        pcg(pit, relres);
+        if (cfg.dense_schur) dense_solve();
+        else pcg(pit, relres);
         pcg_total += pit;
         // back-substitution dP = -V*^-1 (g + W^T dc), candidate, its cost and the model decrease
         hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)gl.p, -1.0,
@@ -915,7 +1050,9 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         iters++;
         const double step_norm = std::sqrt(s.step2[0] + s.step2[1]), x_norm = std::sqrt(s.x2[0] + s.x2[1]);
         const double Fn = s.cost_new, model_dec = -s.model;
-        const bool valid = std::isfinite(Fn) && model_dec > 0.0;
+        const bool solved = !(cfg.dense_schur && s.fail);   // a failed factorisation: an invalid step, as one without a model decrease
+        if (cfg.dense_schur) relres = solved ? (s.res2[1] > 0.0 ? std::sqrt(s.res2[0] / s.res2[1]) : 0.0) : -1.0;
+        const bool valid = solved && std::isfinite(Fn) && model_dec > 0.0;
         double rho = valid ? (F - Fn) / model_dec : -1.0;
         if (valid && nonmono) rho = std::max(rho, (ev_ref - Fn) / (ev_dm_ref + model_dec));   // Ceres's StepQuality
         const bool accept = valid && rho > 1e-3;
@@ -923,7 +1060,7 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
             double *rec = cfg.trace + (size_t)6 * tl++;
             rec[0] = F; rec[1] = Fn; rec[2] = mu; rec[3] = accept ? 1.0 : 0.0; rec[4] = pit; rec[5] = relres;
         }
-        if (step_norm <= cfg.parameter_tol * (x_norm + cfg.parameter_tol)) { status = XM_BA_CONVERGED_PARAMETER; break; }
+        if (solved && step_norm <= cfg.parameter_tol * (x_norm + cfg.parameter_tol)) { status = XM_BA_CONVERGED_PARAMETER; break; }
         if (accept) {
             accepted++;
             radius = std::min(1e16, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3)));

@@ -305,7 +305,7 @@ int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot,
     if (!(o.eta > 0.0 && o.eta < 1.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: eta must lie in (0, 1)");
     if (o.max_iters < 0 || bad(o.max_time) || bad(o.function_tol) || bad(o.gradient_tol) || bad(o.parameter_tol))
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: negative or non-finite setting");
-    if (o.flags & ~(XM_BA_FIX_ROTATIONS | XM_BA_NONMONOTONIC)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: unknown flag");
+    if (o.flags & ~(XM_BA_FIX_ROTATIONS | XM_BA_NONMONOTONIC | XM_BA_DENSE_SCHUR)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: unknown flag");
     if (o.loss < XM_BA_LOSS_TRIVIAL || o.loss > XM_BA_LOSS_ARCTAN) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: unknown loss");
     if (o.loss == XM_BA_LOSS_TRIVIAL && o.loss_scale != 0.0)
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: loss_scale is given but the loss is trivial");
@@ -314,6 +314,8 @@ int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot,
     if (o.max_nonmonotonic < 0) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: max_nonmonotonic is negative");
     if (o.trace_cap < 0 || (o.trace_cap > 0 && !o.trace)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: trace_cap > 0 needs a trace array");
     const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks();
+    if ((o.flags & XM_BA_DENSE_SCHUR) && ((o.flags & XM_BA_FIX_ROTATIONS) ? 3 : 6) * n > XM_BA_DENSE_MAX_ROWS)
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: XM_BA_DENSE_SCHUR with more than XM_BA_DENSE_MAX_ROWS rows in the reduced camera system");
     for (int64_t k = 0; k < 9 * n; ++k)
         if (!std::isfinite(rot[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: rotations are not finite");
     for (int64_t k = 0; k < 3 * n; ++k)
@@ -330,6 +332,7 @@ int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot,
     c.fix_rotations = (o.flags & XM_BA_FIX_ROTATIONS) != 0;
     c.loss = o.loss; c.loss_scale = o.loss_scale;
     c.nonmonotonic = (o.flags & XM_BA_NONMONOTONIC) != 0;
+    c.dense_schur = (o.flags & XM_BA_DENSE_SCHUR) != 0;
     if (o.max_nonmonotonic > 0) c.max_nonmonotonic = o.max_nonmonotonic;
     c.trace_cap = o.trace_cap; c.trace = o.trace;
     xm::BaOutcome r;
@@ -519,6 +522,28 @@ int xm_spd_inverse(int64_t n, double *A) {
     xm::spd_inverse_layout((int)n, x.p, a.p, n, nullptr);   // full symmetric matrix from the computed lower triangle (a is free now)
     XM_HIP_CHECK(hipDeviceSynchronize());
     XM_HIP_CHECK(hipMemcpy(A, a.p, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost));
+    return XM_OK;
+    XM_CATCH
+}
+
+// A^-1 B by the factorisation and substitutions of the dense Schur solver (xm_dense_la.hip)
+int xm_spd_solve(int64_t n, int64_t k, const double *A, double *B) {
+    XM_TRY
+    require_device();
+    if (n < 1 || n > 46000 || k < 1 || k > (int64_t)1 << 20 || !A || !B) throw xm::Error(XM_ERR_ARG, "bad argument");
+    xm::DevBuf<double> a, x, y;
+    xm::DevBuf<int> info;
+    a.alloc((size_t)n * n, false); x.alloc((size_t)n * k, false); y.alloc((size_t)n * k, false); info.alloc(1);
+    XM_HIP_CHECK(hipMemcpy(a.p, A, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
+    XM_HIP_CHECK(hipMemcpy(x.p, B, (size_t)n * k * sizeof(double), hipMemcpyHostToDevice));
+    xm::spd_cholesky_device((int)n, a.p, n, info.p, nullptr);
+    xm::spd_substitute_device((int)n, a.p, n, x.p, y.p, n, (int)k, info.p, nullptr);
+    xm::check_launch("spd_solve");
+    XM_HIP_CHECK(hipDeviceSynchronize());
+    int h = 0;
+    XM_HIP_CHECK(hipMemcpy(&h, info.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (h) throw xm::Error(XM_ERR_ARG, "matrix is not positive definite");
+    XM_HIP_CHECK(hipMemcpy(B, x.p, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost));
     return XM_OK;
     XM_CATCH
 }

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "xm_device.h"
 #include "xm_solver.h"
 
 namespace xm {
@@ -202,6 +203,94 @@ static void gemm_sub(int m, int n, int k, const double *A, int64_t lda, int ta, 
     hipLaunchKernelGGL(la_gemm_sub_kernel, g, dim3(256), 0, st, m, n, k, A, lda, ta, B, ldb, tb, C, ldc, lower_only);
 }
 
+// A (device, column-major n x n, leading dimension ld, lower triangle read) is overwritten by its Cholesky factor L (lower; zeros above the
+// diagonal inside the 64 x 64 diagonal blocks, the other upper blocks untouched).  *info (device) is set to 1 when a pivot is not positive;
+// it is never cleared here.  Enqueued on st only: no host synchronisation.
+void spd_cholesky_device(int n, double *A, int64_t ld, int *info, hipStream_t st) {
+    for (int k = 0; k < n; k += kLaB) {
+        const int b = std::min(kLaB, n - k), m = n - k - b;
+        double *A11 = A + (size_t)k + (size_t)k * ld;
+        hipLaunchKernelGGL(la_potrf_kernel, dim3(1), dim3(256), 0, st, b, A11, ld, info);
+        if (m > 0) {
+            double *A21 = A11 + b;
+            hipLaunchKernelGGL(la_trsm_right_kernel, dim3((m + 255) / 256), dim3(256), 0, st, m, b, A11, ld, A21, ld);
+            gemm_sub(m, m, b, A21, ld, 0, A21, ld, 1, A11 + b + (size_t)b * ld, ld, 1, st);   // A22 -= A21 A21^T (lower tiles)
+        }
+    }
+}
+
+// ---- substitutions L y = b, L^T x = y for a few right-hand sides, 64 rows per launch.  The 64 x 64 MFMA tile of la_gemm_sub_kernel would
+// waste 63 / 64 of itself on one column, so a step is GEMV-shaped: every workgroup solves the diagonal block (the same bits in each; only
+// workgroup 0 stores the result) and then updates its share of the rows not yet solved with it.  Forward (trans = 0): rows below the
+// block, a thread per row (column-major L read coalesced); backward (trans = 1): rows above it, a wavefront per row with the lanes along the
+// block's 64 entries of that column of L (contiguous), summed by the DPP tree.  Each entry is updated by one thread in a fixed order: two
+// runs give the same bits.  src is read in the block's rows and updated outside them, dst is written in the block's rows only, so no
+// launch reads what it writes.  A non-finite solution entry sets *info (an infinite pivot slips past la_potrf_kernel's test).
+constexpr int kLaTrsvRowsPerWave = 16;
+__global__ __launch_bounds__(256) void la_trsv_step_kernel(int n, int k0, int b, const double *__restrict__ Lm, int64_t ld, int trans, int nrhs,
+                                                           double *__restrict__ src, double *__restrict__ dst, int64_t ldx, int *info) {
+    __shared__ double L[kLaB][kLaB + 1];
+    __shared__ double xs[kLaB];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int e = threadIdx.x; e < b * b; e += 256) L[e % b][e / b] = Lm[(size_t)(k0 + e % b) + (size_t)(k0 + e / b) * ld];
+    __syncthreads();
+    for (int q = 0; q < nrhs; ++q) {
+        double *s = src + (size_t)q * ldx, *d = dst + (size_t)q * ldx;
+        if (wave == 0) {   // lane i holds row k0 + i of the block; the pivots in order, each broadcast to the rows it updates
+            double y = lane < b ? s[k0 + lane] : 0.0, x = 0.0;
+            if (!trans) {
+                for (int j = 0; j < b; ++j) {
+                    if (lane == j) x = y / L[j][j];
+                    const double xj = __shfl(x, j);
+                    if (lane > j && lane < b) y -= L[lane][j] * xj;
+                }
+            } else {
+                for (int j = b - 1; j >= 0; --j) {
+                    if (lane == j) x = y / L[j][j];
+                    const double xj = __shfl(x, j);
+                    if (lane < j) y -= L[j][lane] * xj;
+                }
+            }
+            if (lane < b) {
+                xs[lane] = x;
+                if (blockIdx.x == 0) {
+                    d[k0 + lane] = x;
+                    if (!isfinite(x)) *info = 1;
+                }
+            }
+        }
+        __syncthreads();
+        if (!trans) {
+            const int r = k0 + b + blockIdx.x * 256 + threadIdx.x;
+            if (r < n) {
+                double t = 0.0;
+                for (int c = 0; c < b; ++c) t += Lm[(size_t)r + (size_t)(k0 + c) * ld] * xs[c];
+                s[r] -= t;
+            }
+        } else {
+            const int r0 = (blockIdx.x * 4 + wave) * kLaTrsvRowsPerWave;
+            for (int r = r0; r < r0 + kLaTrsvRowsPerWave && r < k0; ++r) {
+                const double v = wave_sum(lane < b ? Lm[(size_t)(k0 + lane) + (size_t)r * ld] * xs[lane] : 0.0);
+                if (lane == 0) s[r] -= v;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// X (device, n x nrhs, leading dimension ldx) <- A^-1 X with L from spd_cholesky_device; Y (the same shape) is scratch.  Enqueued on st only.
+void spd_substitute_device(int n, const double *L, int64_t ld, double *X, double *Y, int64_t ldx, int nrhs, int *info, hipStream_t st) {
+    if (n <= 0 || nrhs <= 0) return;
+    for (int k0 = 0; k0 < n; k0 += kLaB) {   // L Y = X (X is consumed)
+        const int b = std::min(kLaB, n - k0), below = n - k0 - b;
+        hipLaunchKernelGGL(la_trsv_step_kernel, dim3((unsigned)std::max(1, (below + 255) / 256)), dim3(256), 0, st, n, k0, b, L, ld, 0, nrhs, X, Y, ldx, info);
+    }
+    for (int k0 = ((n - 1) / kLaB) * kLaB; k0 >= 0; k0 -= kLaB) {   // L^T X = Y
+        const int b = std::min(kLaB, n - k0), per = 4 * kLaTrsvRowsPerWave;
+        hipLaunchKernelGGL(la_trsv_step_kernel, dim3((unsigned)std::max(1, (k0 + per - 1) / per)), dim3(256), 0, st, n, k0, b, L, ld, 1, nrhs, Y, X, ldx, info);
+    }
+}
+
 // A (device, column-major n x n, ld = n, lower triangle read) is overwritten by its Cholesky factor; X (device, n x n) receives the LOWER
 // triangle of A^-1 (rows >= columns; what lies above the diagonal is scratch): Y = L^-1 is lower triangular, and of X = L^-T Y only the
 // lower triangle is computed -- both substitutions then touch the columns [0, i + b) of block row i only, half the flops of the full
@@ -212,16 +301,7 @@ bool spd_inverse_device(int n, double *A, double *X, hipStream_t st, bool trace)
     const int64_t ld = n;
     DevBuf<int> info;
     info.alloc(1);
-    for (int k = 0; k < n; k += kLaB) {
-        const int b = std::min(kLaB, n - k), m = n - k - b;
-        double *A11 = A + (size_t)k + (size_t)k * ld;
-        hipLaunchKernelGGL(la_potrf_kernel, dim3(1), dim3(256), 0, st, b, A11, ld, info.p);
-        if (m > 0) {
-            double *A21 = A11 + b;
-            hipLaunchKernelGGL(la_trsm_right_kernel, dim3((m + 255) / 256), dim3(256), 0, st, m, b, A11, ld, A21, ld);
-            gemm_sub(m, m, b, A21, ld, 0, A21, ld, 1, A11 + b + (size_t)b * ld, ld, 1, st);   // A22 -= A21 A21^T (lower tiles)
-        }
-    }
+    spd_cholesky_device(n, A, ld, info.p, st);
     check_launch("spd_inverse(cholesky)");
     auto t0 = std::chrono::steady_clock::now();
     int h = 0;

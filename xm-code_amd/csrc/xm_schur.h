@@ -37,6 +37,12 @@ void schur_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int
 // A (device, column-major n x n, lower triangle read) -> Cholesky factor; X <- the LOWER triangle of A^-1 (above the diagonal: scratch).
 // false: not positive definite
 bool spd_inverse_device(int n, double *A, double *X, hipStream_t st, bool trace = false);   // trace: phase times on stderr
+// A (device, column-major n x n, leading dimension ld, lower triangle read) -> its Cholesky factor, the launches of spd_inverse_device; *info
+// (device) <- 1 when a pivot is not positive (never cleared).  No host synchronisation.
+void spd_cholesky_device(int n, double *A, int64_t ld, int *info, hipStream_t st);
+// X (device, n x nrhs, leading dimension ldx) <- A^-1 X from that factor by two blocked substitutions; Y: scratch of X's shape; *info <- 1
+// when a solution entry is not finite.  No host synchronisation.
+void spd_substitute_device(int n, const double *L, int64_t ld, double *X, double *Y, int64_t ldx, int nrhs, int *info, hipStream_t st);
 // dst (row-major n x n, leading dimension ldd) <- the full symmetric inverse from X's lower triangle
 void spd_inverse_layout(int n, const double *X, double *dst, int64_t ldd, hipStream_t st);
 // A (device, column-major n x n) -= q * u u^T  (u: device, n doubles)

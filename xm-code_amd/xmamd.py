@@ -35,7 +35,7 @@ EXPORTS = [
     "xm_ctx_attach_edges", "xm_ctx_edge_residuals", "xm_ctx_edge_residuals_recovered", "xm_ctx_xm2_filter", "xm_ctx_xm2_round", "xm_ctx_set_edge_weights", "xm_ctx_recover_tp", "xm_ctx_schur_info", "xm_ctx_qw", "xm_spd_inverse", "xm_ctx_transport", "xm_ctx_sell_wpad", "xm_ctx_product_kind", "xm_symw_plan", "xm_symw_use",
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
-    "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors",
+    "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -102,6 +102,9 @@ class BaResult(C.Structure):
 
 BA_FIX_ROTATIONS = 1
 BA_NONMONOTONIC = 2
+BA_DENSE_SCHUR = 16            # Ceres's DENSE_SCHUR for the reduced camera system (include/xm_amd.h)
+BA_DENSE_MAX_ROWS = 32768      # ... up to this many rows (6 per camera, 3 with fixed rotations)
+BA_LINEAR_SOLVERS = {"iterative_schur": 0, "dense_schur": BA_DENSE_SCHUR}
 BA_LOSS = {"trivial": 0, "huber": 1, "soft_l1": 2, "cauchy": 3, "arctan": 4}
 BA_OPTIONS_SIZE_V1 = 64        # struct_size of callers built before loss, max_nonmonotonic and loss_scale (include/xm_amd.h)
 BA_STATUS = {0: "no_convergence", 1: "function_tolerance", 2: "gradient_tolerance", 3: "parameter_tolerance", 4: "max_iterations",
@@ -132,6 +135,7 @@ def lib():
         L.xm_ctx_destroy.argtypes = [C.c_void_p]
         L.xm_ctx_destroy.restype = None
         L.xm_spd_inverse.argtypes = [C.c_int64, C.c_void_p]
+        L.xm_spd_solve.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
         L.xm_ctx_qw.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double]
         L.xm_ctx_attach_edges.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_edge_residuals.argtypes = [C.c_void_p, C.c_void_p]
@@ -397,6 +401,18 @@ def spd_inverse(A):
     return np.ascontiguousarray(A)
 
 
+def spd_solve(A, B):
+    """A^-1 B on the GPU for a symmetric positive definite A (only its lower triangle is read; xm_spd_solve): B of shape (n,) or (n, k)"""
+    require_gpu()
+    A = np.asfortranarray(np.array(A, dtype=np.float64))
+    B = np.array(B, dtype=np.float64)
+    vec = B.ndim == 1
+    X = np.asfortranarray(B.reshape(B.shape[0], -1))
+    assert A.ndim == 2 and A.shape[0] == A.shape[1] == X.shape[0]
+    _chk(lib().xm_spd_solve(A.shape[0], X.shape[1], A.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p)))
+    return X[:, 0].copy() if vec else np.ascontiguousarray(X)
+
+
 def quat_roundtrip(block):
     """host-only: (stored quaternion, block rebuilt by the product kernel) of a 3x3 block -w * rotation"""
     b = np.ascontiguousarray(block, dtype=np.float64).reshape(9)
@@ -648,12 +664,14 @@ class Context:
         return np.ascontiguousarray(t), np.ascontiguousarray(p)
 
     def bundle_adjust(self, rot, t, P, fix_rotations=False, max_iters=1000, max_time=300.0, eta=0.1, function_tol=1e-6,
-                      gradient_tol=1e-10, parameter_tol=1e-8, trace=0, loss="trivial", loss_scale=0.0, nonmonotonic=False, max_nonmonotonic=0):
+                      gradient_tol=1e-10, parameter_tol=1e-8, trace=0, loss="trivial", loss_scale=0.0, nonmonotonic=False, max_nonmonotonic=0,
+                      linear_solver="iterative_schur"):
         """reprojection bundle adjustment of a recovered solution (the reference's Ceres refinement, xm_ctx_bundle_adjust): rot 3 x 3n
         (R_i), t 3 x n, P 3 x m as recover_rotations / recover_tp return them -> refined (rot, t, P, info); matrix-free contexts only.
         loss: a BA_LOSS name with its scale loss_scale (Ceres's a, in normalised image units: pixels / focal length); nonmonotonic=True:
         Ceres's non-monotonic steps (the reference's configuration), reference cost reset after max_nonmonotonic (0 = 5) steps without a
-        new minimum, the least-cost point returned.
+        new minimum, the least-cost point returned.  linear_solver: "iterative_schur" (block-Jacobi PCG to eta, Ceres's ITERATIVE_SCHUR) or
+        "dense_schur" (the reduced camera system assembled densely and solved by Cholesky, Ceres's DENSE_SCHUR; up to BA_DENSE_MAX_ROWS rows).
         info: status (BA_STATUS), iters, accepted, pcg_iters, n_used, initial_cost, final_cost, gradient_max, seconds, and with trace > 0
         "trace": one row per LM iteration (cost, candidate cost, mu, accepted, PCG iterations, PCG relative residual); costs are
         1/2 sum rho(|r|^2)"""
@@ -661,11 +679,13 @@ class Context:
         assert rot.shape == (3, 3 * self.n) and t.shape == (3, self.n) and P.shape == (3, self.n_landmarks)
         if loss not in BA_LOSS:
             raise XmError(f"unknown loss {loss!r} (one of {', '.join(BA_LOSS)})")
+        if linear_solver not in BA_LINEAR_SOLVERS:
+            raise XmError(f"unknown linear solver {linear_solver!r} (one of {', '.join(BA_LINEAR_SOLVERS)})")
         opt = BaOptions(); res = BaResult()
         opt.struct_size, res.struct_size = C.sizeof(BaOptions), C.sizeof(BaResult)
         opt.max_iters, opt.max_time, opt.eta = int(max_iters), float(max_time), float(eta)
         opt.function_tol, opt.gradient_tol, opt.parameter_tol = float(function_tol), float(gradient_tol), float(parameter_tol)
-        opt.flags = (BA_FIX_ROTATIONS if fix_rotations else 0) | (BA_NONMONOTONIC if nonmonotonic else 0)
+        opt.flags = (BA_FIX_ROTATIONS if fix_rotations else 0) | (BA_NONMONOTONIC if nonmonotonic else 0) | BA_LINEAR_SOLVERS[linear_solver]
         opt.loss, opt.loss_scale, opt.max_nonmonotonic = BA_LOSS[loss], float(loss_scale), int(max_nonmonotonic)
         tr = None
         if trace:
