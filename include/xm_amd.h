@@ -368,6 +368,18 @@ int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int
  * pcg_iters = 0; trace column 4 = 0 and column 5 = |b - S dc| / |b| with S applied matrix-free (a check of assembly and solve; -1 after a
  * failed factorisation).  The CD n x CD n matrix is allocated inside the call and freed before it returns: CD n > XM_BA_DENSE_MAX_ROWS is
  * XM_ERR_ARG, a failed allocation XM_ERR_NOMEM (both leave the context unchanged and usable).
+ * XM_BA_PRECOND_TWO_LEVEL / XM_BA_PRECOND_BLOCKS (opt-in; for sequential captures, whose reduced camera system is close to a path graph and
+ * takes block-Jacobi PCG to its 500-iteration cap): the PCG's preconditioner becomes M^-1 = blockdiag(S_aa)^-1 + P A_c^-1 P^T (TWO_LEVEL) or
+ * its first term alone (BLOCKS, Ceres's CLUSTER_JACOBI in spirit); S, the stop rule, the start from zero and everything outside the PCG
+ * are unchanged.  Aggregates a: the cameras with a used observation in breadth-first order over the camera-landmark graph
+ * (xm_ba_aggregate_plan), cut into runs of XM_BA_AGG_CAMS; S_aa (16 CD square) is assembled and inverted on the device every LM iteration.
+ * P: per aggregate the seven rigid-plus-scale motions X -> X + w x (X - c) + v + s (X - c) of its cameras about the centroid c of their
+ * centres, in the tangent coordinates above (with XM_BA_FIX_ROTATIONS the four columns v, s of the translation rows), columns of unit
+ * norm, recomputed after every accepted step; a column of norm 0 (all centres coincide) is dropped; a last aggregate of one camera shares
+ * its predecessor's columns.  A_c = P^T S P is assembled (fixed-order sums, no atomics) and inverted every LM iteration; when it cannot be
+ * (a pivot that is not positive, a non-finite entry) that iteration runs with the blocks alone and coarse_fallbacks counts it.  Both flags
+ * together, either with XM_BA_DENSE_SCHUR, or more than XM_BA_MAX_AGGREGATES aggregates: XM_ERR_ARG.  The workspace is allocated inside
+ * the call and freed before it returns (a failed allocation: XM_ERR_NOMEM).  Two calls give the same bits.
  * XM_ERR_ARG (context unchanged and usable): not XM_STORAGE_SCHUR, several ranks or a communicator, a struct_size other than those two,
  * null arrays, non-finite input, eta outside (0, 1), negative settings, unknown flags, an unknown loss, a robust loss whose loss_scale is
  * not finite and > 0, loss_scale != 0 with the trivial loss, max_nonmonotonic < 0.  The call reads the context and changes nothing in it
@@ -379,6 +391,10 @@ int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int
 #define XM_BA_FIX_ROTATIONS 1u          /* the reference's only_landmarks = True: rotations constant (bit-identical), t and P free */
 #define XM_BA_NONMONOTONIC  2u          /* Ceres's non-monotonic steps (see above) */
 #define XM_BA_DENSE_SCHUR   16u         /* Ceres's DENSE_SCHUR (see below) instead of ITERATIVE_SCHUR; 4 and 8 are not flags */
+#define XM_BA_PRECOND_TWO_LEVEL 32u     /* PCG preconditioner: aggregate blocks + rigid-motion coarse operator (see below) */
+#define XM_BA_PRECOND_BLOCKS    64u     /* PCG preconditioner: the aggregate blocks alone (the ablation of the above) */
+#define XM_BA_AGG_CAMS          16      /* cameras per aggregate */
+#define XM_BA_MAX_AGGREGATES    4096    /* at most this many aggregates (65 536 cameras): A_c has up to 28 672 rows */
 #define XM_BA_DENSE_MAX_ROWS 32768      /* XM_BA_DENSE_SCHUR: largest CD n (CD = 6, or 3 with XM_BA_FIX_ROTATIONS): an 8.6 GB matrix */
 #define XM_BA_LOSS_TRIVIAL  0
 #define XM_BA_LOSS_HUBER    1
@@ -411,6 +427,7 @@ typedef struct {
     int64_t pcg_iters, n_used; /* PCG iterations over all steps; observations in the cost */
     double initial_cost, final_cost, gradient_max, seconds;
     int32_t trace_len;
+    int32_t coarse_fallbacks;  /* XM_BA_PRECOND_TWO_LEVEL: LM iterations that ran with the blocks alone (in what was tail padding) */
 } xm_ba_result_t;
 int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, xm_ba_result_t *res);
 int xm_ctx_reprojection_errors(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, double *sqerr);
@@ -470,6 +487,13 @@ int xm_symw_use(int T, int t, int u);
  * cameras appended, cut into runs of B (1..64; the solver uses 64).  agg_of_camera[n]: aggregate of every camera, -1 for camera 0.  More
  * than 4096 aggregates: XM_ERR_ARG. */
 int xm_schur_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int32_t *lm, int B, int32_t *agg_of_camera);
+/* Aggregates of xm_ctx_bundle_adjust's opt-in preconditioners, host-only (CPU test): the cameras with a used observation (used[e] != 0; NULL =
+ * every observation) in breadth-first order over the graph of the used observations from camera 0 (landmarks with more than 64 of them are
+ * not expanded) -- or, when camera 0 is not an end of the capture, from the camera that search reaches last: the search is repeated from
+ * there and kept unless camera 0 lies in its last level, so that the order runs along a trajectory on one front, not outwards from its
+ * middle on two -- the members never reached appended in index order, cut into runs of B (1..64; the solver uses XM_BA_AGG_CAMS).  agg_of_camera[n]: the
+ * aggregate of every camera, -1 for one without a used observation.  More than XM_BA_MAX_AGGREGATES aggregates: XM_ERR_ARG. */
+int xm_ba_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int32_t *lm, const uint8_t *used, int B, int32_t *agg_of_camera);
 /* Large block-sparse Q: "sliced ELL over per-XCD column slabs" (xm-code_amd/csrc/xm_sell.h).  Same product as xm_qw_bsr3
  * (the reference has no sparse product: Dense/matmul.h:42-87 on a dense Q); the matrix is described on the HOST as 3x3-block CSR
  * (rows n, global columns in [0, ncols)) and re-laid on the device.  slabs in {1,2,4,8}; lmax = longest virtual row (hub

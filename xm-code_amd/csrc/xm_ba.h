@@ -16,6 +16,12 @@
 //               (flag in the state word, read with the candidate's scalars); |b - S dc| / |b| through the matrix-free product for the trace
 //   back-subst  dP_l = -V*_l^-1 (g_l + sum W^T dc)
 //   candidate   Rcw <- Exp(dtheta) Rcw, tcw += dt, P += dP; its cost and the model decrease; ONE read of the scalars by the host
+//   precond     (XM_BA_PRECOND_BLOCKS / XM_BA_PRECOND_TWO_LEVEL, opt-in) M^-1 = blockdiag(S_aa)^-1 [+ P A_c^-1 P^T] in place of the inverted camera
+//               blocks: aggregates of XM_BA_AGG_CAMS cameras along a breadth-first order (host, once per call); per LM iteration a workgroup
+//               per aggregate assembles S_aa in LDS and inverts it there, a wavefront per aggregate assembles its rows of A_c = P^T S P
+//               (P: the 7 rigid-plus-scale motions of each aggregate, 4 with fixed rotations; recomputed after every accepted step), and
+//               A_c is inverted by spd_inverse_device; per PCG iteration two launches (update + block GEMVs + P^T r; coarse GEMV +
+//               combination + <r, z>) replace the update kernel
 // Every sum over observations is a fixed-order sum (lane-strided lists + DPP trees, per-workgroup partials added in a fixed order): two
 // calls give the same bits.  f64 throughout.
 //
@@ -29,6 +35,7 @@
 #pragma once
 
 #include <cstdint>
+#include <vector>
 
 #include "xm_solver.h"
 
@@ -45,6 +52,7 @@ struct BaSettings {
     bool nonmonotonic = false;    // XM_BA_NONMONOTONIC
     int max_nonmonotonic = 5;     // Ceres's max_consecutive_nonmonotonic_steps
     bool dense_schur = false;     // XM_BA_DENSE_SCHUR: the reduced camera system assembled densely and solved by Cholesky (eta unused)
+    int precond = 0;              // PCG preconditioner: 0 the inverted camera blocks | 1 XM_BA_PRECOND_BLOCKS | 2 XM_BA_PRECOND_TWO_LEVEL
     int trace_cap = 0;
     double *trace = nullptr;      // trace_cap x 6 row-major: cost, candidate cost, mu, accepted, PCG iterations, PCG relative residual
                                   // (dense Schur: 0 and |b - S dc| / |b| with S applied matrix-free, -1 after a failed factorisation)
@@ -52,9 +60,18 @@ struct BaSettings {
 };
 struct BaOutcome {
     int status = 0, iters = 0, accepted = 0, trace_len = 0;
+    int coarse_fallbacks = 0;     // two-level preconditioner: LM iterations whose coarse operator could not be inverted (blocks alone)
     int64_t pcg_iters = 0, n_used = 0;
     double initial_cost = 0, final_cost = 0, gradient_max = 0, seconds = 0;
 };
+
+// Aggregates of the PCG's opt-in preconditioners (host; xm_ba_aggregate_plan): the cameras with a used observation (used == nullptr: every
+// observation counts) in the order of a breadth-first search over the camera-landmark graph of the used observations from camera 0
+// (landmarks with more than 64 of them are not expanded) -- repeated from the camera reached last, and that order kept unless camera 0 lies in
+// its last level (camera 0 in the middle of a trajectory would give every aggregate two distant stretches) --, the members it never reaches
+// appended in index order; aggregate = position / B.
+// More than XM_BA_MAX_AGGREGATES aggregates: XM_ERR_ARG.
+void ba_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int32_t *lm, const uint8_t *used, int B, std::vector<int32_t> &order);
 
 // rot: 3 x 3n column-major (R_i, camera-to-world), t: 3 x n, p: 3 x m (host, updated in place).  The SchurOp is only read.
 void bundle_adjust(const SchurOp &S, const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out, hipStream_t st);

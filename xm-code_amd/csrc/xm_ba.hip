@@ -801,6 +801,451 @@ __global__ __launch_bounds__(256) void ba_reduce_kernel(BaReduce r) {
     }
 }
 
+// ---- opt-in preconditioners of the PCG (XM_BA_PRECOND_BLOCKS, XM_BA_PRECOND_TWO_LEVEL): M^-1 = blockdiag(S_aa)^-1 [+ P A_c^-1 P^T].
+// Aggregates: runs of kBaAgg members of the host's breadth-first order (ba_aggregate_plan); members are the cameras with a used observation,
+// the others keep z = 0 (their right-hand side and residual are 0).  A last aggregate of one member has a block of its own but shares the
+// coarse columns of its predecessor: nagg blocks, ncoarse = nagg or nagg - 1 coarse aggregates.  The coarse space of an aggregate: the
+// first-order effect on its members' (dtheta, dtcw) of the world motion X -> X + w x (X - c) + v + s (X - c) about the centroid c of their
+// centres C_i = -Rcw_i^T tcw_i -- 7 columns (w, v, s), or the 4 columns (v, s) of the dtcw rows with fixed rotations -- scaled to unit norm.
+constexpr int kBaAgg = XM_BA_AGG_CAMS;
+template <int CD> constexpr int ba_nc() { return CD == 6 ? 7 : 4; }
+struct BaTl {
+    int32_t nagg, ncoarse, nmem, use_coarse;
+    const int32_t *order;    // the members in plan order: block a = positions [a kBaAgg, min(nmem, (a + 1) kBaAgg))
+    const int32_t *agg_of;   // camera -> block aggregate, -1: not a member
+    const double *binv;      // nagg blocks S_aa^-1, (kBaAgg CD)^2 each, symmetric
+    const double *Pm;        // per camera CD x NC (row-major), the scaled columns of its coarse aggregate
+    const double *ainv;      // A_c^-1, (NC ncoarse)^2, symmetric
+    double *gpart;           // P^T r by block aggregate: nagg x NC
+};
+__device__ __forceinline__ void coarse_range(const BaTl &t, int ca, int &k0, int &k1) {
+    k0 = ca * kBaAgg;
+    k1 = (ca == t.ncoarse - 1) ? t.nmem : k0 + kBaAgg;
+}
+// the CD x NC rows of camera (R, T) for the motion about c, unscaled
+template <int CD>
+__device__ __forceinline__ void tl_cam_basis(const double *R, const double *T, const double (&c)[3], double (&blk)[CD][ba_nc<CD>()]) {
+    constexpr int NC = ba_nc<CD>();
+    double C[3], d[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { C[a] = -(R[a] * T[0] + R[3 + a] * T[1] + R[6 + a] * T[2]); d[a] = C[a] - c[a]; }
+#pragma unroll
+    for (int r = 0; r < CD; ++r)
+#pragma unroll
+        for (int k = 0; k < NC; ++k) blk[r][k] = 0.0;
+    constexpr int T0 = CD == 6 ? 3 : 0, V0 = CD == 6 ? 3 : 0;   // first dtcw row; first column of v
+    if constexpr (CD == 6) {
+        // dtheta = -R w;  dtcw = R ([d]x - [C]x) w
+        const double K[3][3] = {{0.0, -(d[2] - C[2]), d[1] - C[1]}, {d[2] - C[2], 0.0, -(d[0] - C[0])}, {-(d[1] - C[1]), d[0] - C[0], 0.0}};
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                blk[a][b] = -R[3 * a + b];
+                blk[3 + a][b] = R[3 * a] * K[0][b] + R[3 * a + 1] * K[1][b] + R[3 * a + 2] * K[2][b];
+            }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int b = 0; b < 3; ++b) blk[T0 + a][V0 + b] = -R[3 * a + b];
+        blk[T0 + a][V0 + 3] = -(R[3 * a] * d[0] + R[3 * a + 1] * d[1] + R[3 * a + 2] * d[2]);
+    }
+}
+// P at the current point, a thread per coarse aggregate (at most 17 members): centroid, column norms, scaled rows; drop[NC ca + k] = 1 for
+// a column of norm 0 (all members at one centre: the scale column, and with one member the rotation about it)
+template <int CD>
+__global__ __launch_bounds__(256) void ba_tl_basis_kernel(BaTl t, const double *__restrict__ Rcw, const double *__restrict__ tcw, double *__restrict__ Pm,
+                                                          double *__restrict__ drop) {
+    constexpr int NC = ba_nc<CD>();
+    const int ca = blockIdx.x * 256 + threadIdx.x;
+    if (ca >= t.ncoarse) return;
+    int k0, k1;
+    coarse_range(t, ca, k0, k1);
+    double c[3] = {0.0, 0.0, 0.0};
+    for (int k = k0; k < k1; ++k) {
+        const double *R = Rcw + (size_t)9 * t.order[k], *T = tcw + (size_t)3 * t.order[k];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) c[a] += -(R[a] * T[0] + R[3 + a] * T[1] + R[6 + a] * T[2]);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) c[a] /= (double)(k1 - k0);
+    double nrm[NC], blk[CD][NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) nrm[k] = 0.0;
+    for (int k = k0; k < k1; ++k) {
+        tl_cam_basis<CD>(Rcw + (size_t)9 * t.order[k], tcw + (size_t)3 * t.order[k], c, blk);
+#pragma unroll
+        for (int r = 0; r < CD; ++r)
+#pragma unroll
+            for (int q = 0; q < NC; ++q) nrm[q] += blk[r][q] * blk[r][q];
+    }
+#pragma unroll
+    for (int q = 0; q < NC; ++q) {
+        const bool ok = nrm[q] > 0.0 && isfinite(nrm[q]);
+        drop[(size_t)NC * ca + q] = ok ? 0.0 : 1.0;
+        nrm[q] = ok ? 1.0 / sqrt(nrm[q]) : 0.0;
+    }
+    for (int k = k0; k < k1; ++k) {
+        const int i = t.order[k];
+        tl_cam_basis<CD>(Rcw + (size_t)9 * i, tcw + (size_t)3 * i, c, blk);
+#pragma unroll
+        for (int r = 0; r < CD; ++r)
+#pragma unroll
+            for (int q = 0; q < NC; ++q) Pm[((size_t)CD * i + r) * NC + q] = blk[r][q] * nrm[q];
+    }
+}
+
+// the observations of landmark slot l in the by-landmark lists: f0 + k stride, k < cnt
+__device__ __forceinline__ void lm_list(const SchurLists &S, int64_t l, int64_t &f0, int64_t &cnt, int64_t &stride) {
+    if (l < S.nheavy) { f0 = S.lm_ptr[l]; cnt = S.lm_ptr[l + 1] - f0; stride = 1; }
+    else { const int64_t q = l - S.nheavy; f0 = S.gbase[q >> 6] + (q & 63); cnt = S.deg[l]; stride = 64; }
+}
+__device__ __forceinline__ constexpr int ltri(int i, int j) { return i * (i + 1) / 2 + j; }   // packed lower triangle, j <= i
+
+// S_aa^-1 of every aggregate, a workgroup each.  Assembly: thread (li, lj), lj <= li, holds block (member li, member lj) of
+//   S_ij = delta_ij U*_i - sum_l (sum_{e in (i,l)} W_e) V*_l^-1 (sum_{f in (j,l)} W_f)^T
+// in registers: it walks camera i's list and, for each used observation, the list of its landmark for the observations of camera j (the pair
+// walk of ba_schur_dense_kernel restricted to one partner; the 16 threads of a row read the same records) -- one writer per entry, sums in
+// list order.  The lower triangle goes to LDS packed (NB (NB + 1) / 2 doubles: 37 KB at NB = 96), is factored there (Cholesky, right-looking),
+// the factor inverted in place (column by column from the last) and S_aa^-1 = L^-T L^-1 written to global memory as a full symmetric block.
+// Rows of absent members (a last, shorter aggregate) are identity.  A pivot that is not positive: the inverse of the diagonal (as chol_inverse).
+template <int CD>
+__global__ __launch_bounds__(256) void ba_tl_block_kernel(SchurLists S, BaTl t, const double *__restrict__ Jc, const double *__restrict__ Jl,
+                                                          const double *__restrict__ vinv, const double *__restrict__ ustar, double *__restrict__ binv) {
+    constexpr int JP = ba_jp<CD>(), NB = kBaAgg * CD, NT = NB * (NB + 1) / 2;
+    static_assert(kBaAgg == 16, "thread (li, lj) = (threadIdx.x / 16, threadIdx.x % 16)");
+    __shared__ double A[NT];
+    __shared__ double dg[NB], colv[NB];
+    const int tid = threadIdx.x, li = tid >> 4, lj = tid & 15;
+    const int k0 = blockIdx.x * kBaAgg, nm = min(kBaAgg, t.nmem - k0);
+    if (lj <= li) {
+        double acc[CD][CD];
+#pragma unroll
+        for (int a = 0; a < CD; ++a)
+#pragma unroll
+            for (int b = 0; b < CD; ++b) acc[a][b] = (li == lj && a == b && li >= nm) ? 1.0 : 0.0;
+        if (li < nm) {
+            const int i = t.order[k0 + li], j = t.order[k0 + lj];
+            if (li == lj) {
+#pragma unroll
+                for (int a = 0; a < CD; ++a)
+#pragma unroll
+                    for (int b = 0; b < CD; ++b) acc[a][b] = ustar[(size_t)CD * CD * i + CD * a + b];
+            }
+            for (int64_t e = S.cam_ptr[i]; e < S.cam_ptr[i + 1]; ++e) {
+                double jp[6];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) jp[k] = Jc[(size_t)(JP + k) * S.nobs + e];
+                if (!obs_used(jp)) continue;
+                const int64_t l = S.cam_lm[e];
+                int64_t f0, cnt, stride;
+                lm_list(S, l, f0, cnt, stride);
+                bool have = false;
+                double X[CD][3];
+                for (int64_t k = 0; k < cnt; ++k) {
+                    const size_t f = (size_t)(f0 + k * stride);
+                    if (S.lm_cam[f] != j) continue;
+                    double jc2[2 * CD], jp2[6];
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) jp2[q] = Jl[(size_t)(JP + q) * S.lm_total + f];
+                    if (!obs_used(jp2)) continue;
+                    if (!have) {
+                        double V[3][3];
+                        sym3(vinv + (size_t)6 * l, V);
+#pragma unroll
+                        for (int a = 0; a < CD; ++a) {
+                            const double j0 = Jc[(size_t)a * S.nobs + e], j1 = Jc[(size_t)(CD + a) * S.nobs + e];
+                            double w[3];
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) w[c] = j0 * jp[c] + j1 * jp[3 + c];
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) X[a][c] = w[0] * V[0][c] + w[1] * V[1][c] + w[2] * V[2][c];
+                        }
+                        have = true;
+                    }
+#pragma unroll
+                    for (int q = 0; q < 2 * CD; ++q) jc2[q] = Jl[(size_t)q * S.lm_total + f];
+#pragma unroll
+                    for (int b = 0; b < CD; ++b) {
+                        double w[3];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) w[c] = jc2[b] * jp2[c] + jc2[CD + b] * jp2[3 + c];
+#pragma unroll
+                        for (int a = 0; a < CD; ++a) acc[a][b] -= X[a][0] * w[0] + X[a][1] * w[1] + X[a][2] * w[2];
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < CD; ++a)
+#pragma unroll
+            for (int b = 0; b < CD; ++b) {
+                const int row = CD * li + a, col = CD * lj + b;
+                if (col <= row) A[ltri(row, col)] = acc[a][b];
+            }
+    }
+    __syncthreads();
+    if (tid < NB) dg[tid] = A[ltri(tid, tid)];
+    __syncthreads();
+    const int tx = tid & 15, ty = tid >> 4;
+    bool ok = true;
+    for (int j = 0; j < NB; ++j) {   // Cholesky; every thread sees the same pivots
+        double d = A[ltri(j, j)];
+        if (!(d > 0.0) || !isfinite(d)) { ok = false; break; }
+        d = sqrt(d);
+        __syncthreads();
+        if (tid < NB - j - 1) A[ltri(j + 1 + tid, j)] /= d;
+        if (tid == 255) A[ltri(j, j)] = d;
+        __syncthreads();
+        for (int i = j + 1 + ty; i < NB; i += 16) {
+            const double lij = A[ltri(i, j)];
+            for (int k = j + 1 + tx; k <= i; k += 16) A[ltri(i, k)] -= lij * A[ltri(k, j)];
+        }
+        __syncthreads();
+    }
+    double *out = binv + (size_t)NB * NB * blockIdx.x;
+    if (!ok) {
+        for (int q = tid; q < NB * NB; q += 256) out[q] = (q / NB == q % NB && dg[q / NB] > 0.0) ? 1.0 / dg[q / NB] : 0.0;
+        return;
+    }
+    for (int j = NB - 1; j >= 0; --j) {   // L -> L^-1 in place: column j from the inverted trailing block
+        const double ajj = 1.0 / A[ltri(j, j)];
+        __syncthreads();
+        if (tid < NB - j - 1) colv[tid] = A[ltri(j + 1 + tid, j)];
+        if (tid == 255) A[ltri(j, j)] = ajj;
+        __syncthreads();
+        if (tid < NB - j - 1) {
+            const int i = j + 1 + tid;
+            double s = 0.0;
+            for (int k = j + 1; k <= i; ++k) s += A[ltri(i, k)] * colv[k - j - 1];
+            A[ltri(i, j)] = -ajj * s;
+        }
+    }
+    __syncthreads();
+    for (int i = ty; i < NB; i += 16)
+        for (int j = tx; j <= i; j += 16) {
+            double s = 0.0;
+            for (int k = i; k < NB; ++k) s += A[ltri(k, i)] * A[ltri(k, j)];
+            out[(size_t)NB * i + j] = s;
+            out[(size_t)NB * j + i] = s;
+        }
+}
+
+// A_c = P^T S P, the lower block triangle, column-major with leading dimension ld = NC ncoarse, into a matrix the caller has zeroed.  A
+// wavefront per coarse aggregate a owns block row a: it writes sum_i P_i^T U*_i P_i (and 1 on the diagonal of a dropped column), then walks
+// its members' lists in order; for observation e of landmark l the lanes run over l's list, 64 at a time: lane f forms T_f = J_P,f^T J_c,f
+// P_cam(f) (3 x NC), the first lane of every coarse aggregate b <= a in the batch adds those of the later lanes of b in lane order and
+// subtracts (P_i^T W_e V*_l^-1) T from block (a, b).  One writer per entry, a workgroup fence between batches: fixed order, no atomics.
+template <int CD>
+__global__ __launch_bounds__(256) void ba_tl_coarse_kernel(SchurLists S, BaTl t, const double *__restrict__ Jc, const double *__restrict__ Jl,
+                                                           const double *__restrict__ vinv, const double *__restrict__ ustar,
+                                                           const double *__restrict__ drop, double *__restrict__ Ac, int64_t ld) {
+    constexpr int JP = ba_jp<CD>(), NC = ba_nc<CD>();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int ca = blockIdx.x * kQwWaves + wv;
+    if (ca >= t.ncoarse) return;
+    int k0, k1;
+    coarse_range(t, ca, k0, k1);
+    double *row = Ac + (size_t)NC * ca;   // entry (NC ca + r, c) at row[r + c ld]
+    if (lane < NC * NC) {
+        const int r = lane / NC, c = lane % NC;
+        double s = 0.0;
+        for (int k = k0; k < k1; ++k) {
+            const int i = t.order[k];
+            const double *Pi = t.Pm + (size_t)CD * NC * i, *U = ustar + (size_t)CD * CD * i;
+            for (int x = 0; x < CD; ++x) {
+                double u = 0.0;
+                for (int y = 0; y < CD; ++y) u += U[CD * x + y] * Pi[NC * y + c];
+                s += Pi[NC * x + r] * u;
+            }
+        }
+        if (r == c && drop[(size_t)NC * ca + r] != 0.0) s += 1.0;
+        row[r + ((size_t)NC * ca + c) * ld] = s;
+    }
+    __threadfence_block();
+    for (int km = k0; km < k1; ++km) {
+        const int i = t.order[km];
+        const double *Pi = t.Pm + (size_t)CD * NC * i;
+        for (int64_t e = S.cam_ptr[i]; e < S.cam_ptr[i + 1]; ++e) {
+            double jc[2 * CD], jp[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) jp[k] = Jc[(size_t)(JP + k) * S.nobs + e];
+            if (!obs_used(jp)) continue;
+#pragma unroll
+            for (int k = 0; k < 2 * CD; ++k) jc[k] = Jc[(size_t)k * S.nobs + e];
+            const int64_t l = S.cam_lm[e];
+            double V[3][3], X[NC][3];
+            sym3(vinv + (size_t)6 * l, V);
+#pragma unroll
+            for (int r = 0; r < NC; ++r) {
+                double u0 = 0.0, u1 = 0.0, w[3];
+#pragma unroll
+                for (int k = 0; k < CD; ++k) { u0 += jc[k] * Pi[NC * k + r]; u1 += jc[CD + k] * Pi[NC * k + r]; }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) w[c] = u0 * jp[c] + u1 * jp[3 + c];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) X[r][c] = w[0] * V[0][c] + w[1] * V[1][c] + w[2] * V[2][c];
+            }
+            int64_t f0, cnt, stride;
+            lm_list(S, l, f0, cnt, stride);
+            for (int64_t kb = 0; kb < cnt; kb += 64) {
+                const int nb = (int)(cnt - kb < 64 ? cnt - kb : 64);
+                int b = -1;
+                double T[3][NC];
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) T[k][c] = 0.0;
+                if (lane < nb) {
+                    const size_t f = (size_t)(f0 + (kb + lane) * stride);
+                    double jp2[6];
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) jp2[k] = Jl[(size_t)(JP + k) * S.lm_total + f];
+                    const int jf = S.lm_cam[f], af = t.agg_of[jf];
+                    const int bf = af < t.ncoarse ? af : t.ncoarse - 1;
+                    if (obs_used(jp2) && af >= 0 && bf <= ca) {
+                        b = bf;
+                        const double *Pj = t.Pm + (size_t)CD * NC * jf;
+                        double jc2[2 * CD];
+#pragma unroll
+                        for (int k = 0; k < 2 * CD; ++k) jc2[k] = Jl[(size_t)k * S.lm_total + f];
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) {
+                            double u0 = 0.0, u1 = 0.0;
+#pragma unroll
+                            for (int k = 0; k < CD; ++k) { u0 += jc2[k] * Pj[NC * k + c]; u1 += jc2[CD + k] * Pj[NC * k + c]; }
+#pragma unroll
+                            for (int k = 0; k < 3; ++k) T[k][c] = jp2[k] * u0 + jp2[3 + k] * u1;
+                        }
+                    }
+                }
+                int rank = 0;   // earlier lanes of this batch with the same coarse aggregate
+                for (int q = 0; q < nb; ++q) {
+                    const int bq = __builtin_amdgcn_readlane(b, q);
+                    rank += (q < lane && bq >= 0 && bq == b) ? 1 : 0;
+                }
+                for (int q = 1; q < nb; ++q) {   // followers in lane order into the first lane of their aggregate
+                    const int bq = __builtin_amdgcn_readlane(b, q), rq = __builtin_amdgcn_readlane(rank, q);
+                    if (bq < 0 || rq == 0) continue;
+                    const bool take = rank == 0 && b == bq;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) {
+                            const double v = __shfl(T[k][c], q);
+                            if (take) T[k][c] += v;
+                        }
+                }
+                if (b >= 0 && rank == 0) {
+                    double *blk = row + (size_t)NC * b * ld;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c)
+#pragma unroll
+                        for (int r = 0; r < NC; ++r) blk[r + (size_t)c * ld] -= X[r][0] * T[0][c] + X[r][1] * T[1][c] + X[r][2] * T[2][c];
+                }
+                __threadfence_block();
+            }
+        }
+    }
+}
+// *flag <- 1 when an entry of the n x n matrix is not finite
+__global__ __launch_bounds__(256) void ba_tl_finite_kernel(int64_t count, const double *__restrict__ A, int32_t *__restrict__ flag) {
+    bool bad = false;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < count; k += (int64_t)gridDim.x * 256) bad = bad || !isfinite(A[k]);
+    if (bad) *flag = 1;
+}
+
+// ---- the preconditioner inside the PCG: two launches in place of ba_pcg_upd_kernel (and, with init, of ba_pcg_init_kernel).
+// A workgroup per block aggregate: alpha as the update kernel forms it; x += alpha p, r -= alpha Ap for its members (init: x = 0, r = b);
+// z = S_aa^-1 r (the block is symmetric: thread k reads column k, coalesced) and the aggregate's part of P^T r.
+template <int CD>
+__global__ __launch_bounds__(256) void ba_tl_apply_block_kernel(BaPcg a, BaTl t, int it, int init) {
+    constexpr int NB = kBaAgg * CD, NC = ba_nc<CD>();
+    __shared__ double sh[4];
+    __shared__ double rs[NB];
+    if (!init && a.st->done) return;
+    double alpha = 0.0;
+    if (!init) {
+        const double rz = sum_partials256(a.prz[it & 1], a.grid, sh), pap = sum_partials256(a.ppap, a.cgrid, sh);
+        alpha = (pap > 0.0 && rz > 0.0) ? rz / pap : 0.0;
+    }
+    const int tid = threadIdx.x, k0 = blockIdx.x * kBaAgg, nm = min(kBaAgg, t.nmem - k0);
+    size_t j = 0;
+    const bool mine = tid < NB && tid / CD < nm;
+    if (tid < NB) {
+        double rn = 0.0;
+        if (mine) {
+            j = (size_t)CD * t.order[k0 + tid / CD] + tid % CD;
+            if (init) { rn = a.b[j]; a.x[j] = 0.0; }
+            else { a.x[j] += alpha * a.p[j]; rn = a.r[j] - alpha * a.Ap[j]; }
+            a.r[j] = rn;
+        }
+        rs[tid] = rn;
+    }
+    __syncthreads();
+    if (mine) {
+        const double *Bk = t.binv + (size_t)NB * NB * blockIdx.x + tid;
+        double z = 0.0;
+        for (int k = 0; k < CD * nm; ++k) z += Bk[(size_t)NB * k] * rs[k];
+        a.z[j] = z;
+    }
+    if (t.use_coarse && tid >= 128 && tid < 128 + NC) {
+        const int q = tid - 128;
+        double s = 0.0;
+        for (int k = 0; k < CD * nm; ++k) s += t.Pm[((size_t)CD * t.order[k0 + k / CD] + k % CD) * NC + q] * rs[k];
+        t.gpart[(size_t)NC * blockIdx.x + q] = s;
+    }
+    if (init && blockIdx.x == 0 && tid == 0) { a.st->done = 0; a.st->iters = 0; a.st->relres = 1.0; }
+}
+// A workgroup per coarse aggregate: y = its NC rows of A_c^-1 (P^T r) (the partials of a merged last block added to its predecessor's),
+// z += P y for its members, and the partials of <r, z> and |r|^2 (init: also p = z and |b|^2)
+template <int CD>
+__global__ __launch_bounds__(256) void ba_tl_apply_coarse_kernel(BaPcg a, BaTl t, int it, int init) {
+    constexpr int NC = ba_nc<CD>();
+    __shared__ double sh[4];
+    __shared__ double ys[NC];
+    if (!init && a.st->done) return;
+    const int tid = threadIdx.x, ca = blockIdx.x;
+    int k0, k1;
+    coarse_range(t, ca, k0, k1);
+    if (t.use_coarse) {
+        const int nct = NC * t.ncoarse;
+        const bool merged = t.nagg != t.ncoarse;
+        for (int q = 0; q < NC; ++q) {
+            const double *row = t.ainv + (size_t)(NC * ca + q) * nct;
+            double v = 0.0;
+            for (int c = tid; c < nct; c += 256) {
+                double g = t.gpart[c];
+                if (merged && c >= nct - NC) g += t.gpart[c + NC];
+                v += row[c] * g;
+            }
+            v = block_sum256(v, sh);
+            if (tid == 0) ys[q] = v;
+        }
+        __syncthreads();
+    }
+    double rz = 0.0, rr = 0.0;
+    if (tid < (k1 - k0) * CD) {
+        const size_t j = (size_t)CD * t.order[k0 + tid / CD] + tid % CD;
+        double z = a.z[j];
+        if (t.use_coarse) {
+#pragma unroll
+            for (int q = 0; q < NC; ++q) z += t.Pm[j * NC + q] * ys[q];
+            a.z[j] = z;
+        }
+        if (init) a.p[j] = z;
+        const double r = a.r[j];
+        rz = r * z; rr = r * r;
+    }
+    rz = block_sum256(rz, sh);
+    rr = block_sum256(rr, sh);
+    if (tid == 0) {
+        if (init) { a.prz[0][ca] = rz; a.pbb[ca] = rr; a.prr[ca] = rr; }
+        else { a.prz[(it & 1) ^ 1][ca] = rz; a.prr[ca] = rr; }
+    }
+}
+
 double secs_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); }
 
 // host wait on the stream, bounded by the watchdog
@@ -932,6 +1377,92 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
     a.b = b.p; a.sinv = sinv.p; a.ustar = ustar.p; a.x = x.p; a.r = r.p; a.z = z.p; a.p = pv.p; a.Ap = Ap.p;
     a.prz[0] = pp + o_pcg; a.prz[1] = pp + o_pcg + gfc; a.prr = pp + o_pcg + 2 * gfc; a.pbb = pp + o_pcg + 3 * gfc; a.ppap = pp + o_pcg + 4 * gfc;
     a.st = dst;
+    // opt-in preconditioners: the plan from the used observations (host, once), the blocks and the coarse operator (device, allocated here
+    // and freed on return).  atl: the PCG's arguments with the partial sums of <r, z>, |r|^2 and |b|^2 by coarse aggregate
+    constexpr int NC = ba_nc<CD>(), NB = kBaAgg * CD;
+    bool tlmode = cfg.precond != 0;
+    BaTl tl{};
+    BaPcg atl = a;
+    DevBuf<int32_t> tl_order, tl_agg, tl_flag;
+    DevBuf<double> tl_binv, tl_P, tl_drop, tl_gpart, tl_parts, tl_A, tl_X;
+    int64_t nct = 0;
+    if (tlmode) {
+        std::vector<int32_t> hc((size_t)nobs), hl((size_t)nobs), order;
+        std::vector<int64_t> hpos((size_t)nobs);
+        std::vector<double> hw((size_t)nobs), hp3((size_t)3 * nobs);
+        XM_HIP_CHECK(hipMemcpyAsync(hc.data(), S.obs_cam, (size_t)nobs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        XM_HIP_CHECK(hipMemcpyAsync(hl.data(), S.obs_lm, (size_t)nobs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        XM_HIP_CHECK(hipMemcpyAsync(hpos.data(), S.pos_c, (size_t)nobs * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        XM_HIP_CHECK(hipMemcpyAsync(hw.data(), S.cam_w, (size_t)nobs * sizeof(double), hipMemcpyDeviceToHost, st));
+        XM_HIP_CHECK(hipMemcpyAsync(hp3.data(), S.obs_p, (size_t)3 * nobs * sizeof(double), hipMemcpyDeviceToHost, st));
+        wait_stream(st, cfg.watchdog_s, "the observation lists");
+        std::vector<uint8_t> used((size_t)nobs);
+        for (int64_t e = 0; e < nobs; ++e) used[(size_t)e] = (hw[(size_t)hpos[(size_t)e]] > 0.0 && hp3[(size_t)3 * e + 2] > 0.0) ? 1 : 0;
+        ba_aggregate_plan(n, nobs, hc.data(), hl.data(), used.data(), kBaAgg, order);
+        const int64_t nmem = (int64_t)order.size();
+        if (nmem == 0) tlmode = false;   // no used observation: nothing to precondition (b = 0, the PCG stops at once)
+        else {
+            const int64_t nagg = (nmem + kBaAgg - 1) / kBaAgg, ncoarse = (nagg > 1 && nmem - (nagg - 1) * kBaAgg < 2) ? nagg - 1 : nagg;
+            nct = NC * ncoarse;
+            std::vector<int32_t> agg((size_t)n, -1);
+            for (int64_t k = 0; k < nmem; ++k) agg[(size_t)order[(size_t)k]] = (int32_t)(k / kBaAgg);
+            auto try_alloc = [&](DevBuf<double> &buf, size_t elems, const char *what) {
+                if (hipMalloc((void **)&buf.p, elems * sizeof(double)) != hipSuccess) {
+                    (void)hipGetLastError();
+                    buf.p = nullptr;
+                    throw Error(XM_ERR_NOMEM, std::string("xm_ctx_bundle_adjust: no device memory for ") + what + " (" + std::to_string(elems * 8 >> 20) + " MB)");
+                }
+                buf.count = buf.capacity = elems;
+            };
+            tl_order.alloc((size_t)nmem, false); tl_agg.alloc((size_t)n, false); tl_flag.alloc(1);
+            XM_HIP_CHECK(hipMemcpyAsync(tl_order.p, order.data(), (size_t)nmem * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            XM_HIP_CHECK(hipMemcpyAsync(tl_agg.p, agg.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            wait_stream(st, cfg.watchdog_s, "the aggregate plan");
+            try_alloc(tl_binv, (size_t)nagg * NB * NB, "the preconditioner's blocks");
+            tl_parts.alloc(4 * (size_t)ncoarse);
+            if (cfg.precond == 2) {
+                tl_P.alloc((size_t)n * CD * NC); tl_drop.alloc((size_t)nct); tl_gpart.alloc((size_t)(nagg + 1) * NC);
+                try_alloc(tl_A, (size_t)nct * nct, "the coarse operator");
+                try_alloc(tl_X, (size_t)nct * nct, "the coarse operator's inverse");
+            }
+            tl.nagg = (int32_t)nagg; tl.ncoarse = (int32_t)ncoarse; tl.nmem = (int32_t)nmem; tl.use_coarse = 0;
+            tl.order = tl_order.p; tl.agg_of = tl_agg.p; tl.binv = tl_binv.p; tl.Pm = tl_P.p; tl.ainv = tl_A.p; tl.gpart = tl_gpart.p;
+            atl.grid = (int)ncoarse;
+            atl.prz[0] = tl_parts.p; atl.prz[1] = tl_parts.p + ncoarse; atl.prr = tl_parts.p + 2 * ncoarse; atl.pbb = tl_parts.p + 3 * ncoarse;
+        }
+    }
+    bool basis_stale = true;   // P belongs to the current point: recomputed after every accepted step
+    int coarse_fallbacks = 0;
+    // every LM iteration (S changes with mu): the block inverses; two-level: A_c = P^T S P and its inverse.  A_c that cannot be inverted (a
+    // pivot that is not positive, an entry that is not finite): this iteration's PCG runs with the blocks alone
+    auto precond_setup = [&]() {
+        hipLaunchKernelGGL((ba_tl_block_kernel<CD>), dim3((unsigned)tl.nagg), b256, 0, st, S, tl, (const double *)Jc.p, (const double *)Jl.p,
+                           (const double *)vinv.p, (const double *)ustar.p, tl_binv.p);
+        tl.use_coarse = 0;
+        if (cfg.precond != 2) return;
+        if (basis_stale) {
+            hipLaunchKernelGGL((ba_tl_basis_kernel<CD>), dim3((unsigned)((tl.ncoarse + 255) / 256)), b256, 0, st, tl, (const double *)R[cur].p,
+                               (const double *)T[cur].p, tl_P.p, tl_drop.p);
+            basis_stale = false;
+        }
+        XM_HIP_CHECK(hipMemsetAsync(tl_A.p, 0, tl_A.count * sizeof(double), st));
+        XM_HIP_CHECK(hipMemsetAsync(tl_flag.p, 0, sizeof(int32_t), st));
+        hipLaunchKernelGGL((ba_tl_coarse_kernel<CD>), dim3((unsigned)((tl.ncoarse + kQwWaves - 1) / kQwWaves)), b256, 0, st, S, tl, (const double *)Jc.p,
+                           (const double *)Jl.p, (const double *)vinv.p, (const double *)ustar.p, (const double *)tl_drop.p, tl_A.p, nct);
+        check_launch("the two-level preconditioner");
+        bool ok = spd_inverse_device((int)nct, tl_A.p, tl_X.p, st);
+        if (ok) {
+            spd_inverse_layout((int)nct, tl_X.p, tl_A.p, nct, st);
+            hipLaunchKernelGGL(ba_tl_finite_kernel, dim3((unsigned)std::min<int64_t>(1024, (nct * nct + 255) / 256)), b256, 0, st, nct * nct, (const double *)tl_A.p,
+                               tl_flag.p);
+            int32_t bad = 0;
+            XM_HIP_CHECK(hipMemcpyAsync(&bad, tl_flag.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            wait_stream(st, cfg.watchdog_s, "the coarse operator's inverse");
+            ok = bad == 0;
+        }
+        if (ok) tl.use_coarse = 1;
+        else coarse_fallbacks++;
+    };
     // dense Schur: the CD n x CD n matrix, allocated here and freed on return; the substitutions' scratch vector
     const int64_t nd = (int64_t)CD * n;
     DevBuf<double> Sd, ysub;
@@ -969,8 +1500,15 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
     };
     int pcg_last = 8;
     // PCG from zero: batches enqueued ahead of the host (as many iterations as the last solve needed + 2, then steps of 8), one read per batch
+    const BaPcg &a_jacobi = a;
     auto pcg = [&](int &iters, double &relres) {
-        hipLaunchKernelGGL((ba_pcg_init_kernel<CD>), dim3(gfc), b256, 0, st, a);
+        const BaPcg &a = tlmode ? atl : a_jacobi;
+        auto precond = [&](int it, int init) {   // the update of iteration it (or the start) with M^-1 = blocks [+ coarse]
+            hipLaunchKernelGGL((ba_tl_apply_block_kernel<CD>), dim3((unsigned)tl.nagg), b256, 0, st, a, tl, it, init);
+            hipLaunchKernelGGL((ba_tl_apply_coarse_kernel<CD>), dim3((unsigned)tl.ncoarse), b256, 0, st, a, tl, it, init);
+        };
+        if (tlmode) precond(0, 1);
+        else hipLaunchKernelGGL((ba_pcg_init_kernel<CD>), dim3(gfc), b256, 0, st, a);
         int it = 0, dir_applied = 0;
         auto enqueue = [&](int upto) {
             for (; it < upto; ++it) {
@@ -978,7 +1516,8 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
                 hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)nullptr, 1.0,
                                    (const int32_t *)lused.p, (const double *)pv.p, (const BaState *)dst, y.p);
                 hipLaunchKernelGGL((ba_camx_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)y.p, a);
-                hipLaunchKernelGGL((ba_pcg_upd_kernel<CD>), dim3(gfc), b256, 0, st, a, it);
+                if (tlmode) precond(it, 0);
+                else hipLaunchKernelGGL((ba_pcg_upd_kernel<CD>), dim3(gfc), b256, 0, st, a, it);
             }
             hipLaunchKernelGGL((ba_pcg_dir_kernel<CD>), dim3(gfc), b256, 0, st, a, it);   // convergence test of the last update (or the next direction)
             dir_applied = it;
@@ -997,7 +1536,7 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
     };
 
     double radius = 1e4, nu = 2.0, F = 0.0, gmax = 0.0;
-    int status = XM_BA_NO_CONVERGENCE, iters = 0, accepted = 0, tl = 0;
+    int status = XM_BA_NO_CONVERGENCE, iters = 0, accepted = 0, trace_n = 0;
     // non-monotonic steps: Ceres's TrustRegionStepEvaluator (Conn, Gould & Toint, Trust-Region Methods, Algorithm 10.1.2).  Costs of the
     // minimum, the reference and the candidate point, the model decreases accumulated since the reference and the candidate, and the
     // accepted steps since the last new minimum
@@ -1026,7 +1565,10 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         int pit = 0;
         double relres = 0.0;
         if (cfg.dense_schur) dense_solve();
-        else pcg(pit, relres);
+        else {
+            if (tlmode) precond_setup();
+            pcg(pit, relres);
+        }
         pcg_total += pit;
         // back-substitution dP = -V*^-1 (g + W^T dc), candidate, its cost and the model decrease
         hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)gl.p, -1.0,
@@ -1056,8 +1598,8 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         double rho = valid ? (F - Fn) / model_dec : -1.0;
         if (valid && nonmono) rho = std::max(rho, (ev_ref - Fn) / (ev_dm_ref + model_dec));   // Ceres's StepQuality
         const bool accept = valid && rho > 1e-3;
-        if (tl < cfg.trace_cap && cfg.trace) {
-            double *rec = cfg.trace + (size_t)6 * tl++;
+        if (trace_n < cfg.trace_cap && cfg.trace) {
+            double *rec = cfg.trace + (size_t)6 * trace_n++;
             rec[0] = F; rec[1] = Fn; rec[2] = mu; rec[3] = accept ? 1.0 : 0.0; rec[4] = pit; rec[5] = relres;
         }
         if (solved && step_norm <= cfg.parameter_tol * (x_norm + cfg.parameter_tol)) { status = XM_BA_CONVERGED_PARAMETER; break; }
@@ -1066,6 +1608,7 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
             radius = std::min(1e16, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3)));
             nu = 2.0;
             cur = nx;
+            basis_stale = true;
             if (!nonmono) {
                 best = cur;
             } else {   // Ceres's StepAccepted
@@ -1122,12 +1665,76 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         for (int a = 0; a < 3; ++a) p[(size_t)3 * l + a] = hP[(size_t)3 * sl + a];
     }
     out.status = status; out.iters = iters; out.accepted = accepted; out.pcg_iters = pcg_total;
-    out.final_cost = F; out.gradient_max = gmax; out.trace_len = tl;
+    out.final_cost = F; out.gradient_max = gmax; out.trace_len = trace_n;
+    out.coarse_fallbacks = coarse_fallbacks;
     out.seconds = secs_since(t_start);
     (void)nobs;
 }
 
 }  // namespace
+
+void ba_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int32_t *lm, const uint8_t *used, int B, std::vector<int32_t> &order) {
+    if (n < 1 || nobs < 0 || (nobs > 0 && (!cam || !lm))) throw Error(XM_ERR_ARG, "aggregate plan: needs at least 1 camera and the observation arrays");
+    if (B < 1 || B > 64) throw Error(XM_ERR_ARG, "aggregate plan: cameras per aggregate must be 1..64");
+    int64_t M = 0;
+    for (int64_t e = 0; e < nobs; ++e) {
+        if (cam[e] < 0 || cam[e] >= n || lm[e] < 0) throw Error(XM_ERR_ARG, "aggregate plan: observation index out of range");
+        M = std::max<int64_t>(M, (int64_t)lm[e] + 1);
+    }
+    // the bipartite graph of the used observations as two lists in input order (fixed visiting order)
+    auto on = [&](int64_t e) { return used == nullptr || used[e] != 0; };
+    std::vector<int64_t> cptr((size_t)n + 1, 0), lptr((size_t)M + 1, 0);
+    for (int64_t e = 0; e < nobs; ++e)
+        if (on(e)) { cptr[(size_t)cam[e] + 1]++; lptr[(size_t)lm[e] + 1]++; }
+    for (int64_t i = 0; i < n; ++i) cptr[(size_t)i + 1] += cptr[(size_t)i];
+    for (int64_t l = 0; l < M; ++l) lptr[(size_t)l + 1] += lptr[(size_t)l];
+    const int64_t nused = cptr[(size_t)n];
+    std::vector<int32_t> c_l((size_t)nused), l_c((size_t)nused);
+    {
+        std::vector<int64_t> nc(cptr.begin(), cptr.end() - 1), nl(lptr.begin(), lptr.end() - 1);
+        for (int64_t e = 0; e < nobs; ++e)
+            if (on(e)) { c_l[(size_t)nc[(size_t)cam[e]]++] = lm[e]; l_c[(size_t)nl[(size_t)lm[e]]++] = cam[e]; }
+    }
+    int64_t nmem = 0;
+    for (int64_t i = 0; i < n; ++i) nmem += cptr[(size_t)i + 1] > cptr[(size_t)i] ? 1 : 0;
+    if ((nmem + B - 1) / B > XM_BA_MAX_AGGREGATES)
+        throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: " + std::to_string(nmem) + " cameras make more than XM_BA_MAX_AGGREGATES aggregates of " +
+                                std::to_string(B) + " (use the default preconditioner)");
+    // breadth-first order from `start` with the level (camera-to-camera hops) of every camera reached
+    std::vector<char> cseen, lseen;
+    std::vector<int32_t> level;
+    auto bfs = [&](int32_t start, std::vector<int32_t> &out) {
+        cseen.assign((size_t)n, 0); lseen.assign((size_t)M, 0); level.assign((size_t)n, -1);
+        out.clear();
+        out.push_back(start); cseen[(size_t)start] = 1; level[(size_t)start] = 0;
+        for (size_t h = 0; h < out.size(); ++h) {
+            const int32_t c = out[h];
+            for (int64_t q = cptr[(size_t)c]; q < cptr[(size_t)c + 1]; ++q) {
+                const int32_t l = c_l[(size_t)q];
+                if (lseen[(size_t)l] || lptr[(size_t)l + 1] - lptr[(size_t)l] > 64) continue;   // heavy landmarks carry no locality
+                lseen[(size_t)l] = 1;
+                for (int64_t q2 = lptr[(size_t)l]; q2 < lptr[(size_t)l + 1]; ++q2) {
+                    const int32_t c2 = l_c[(size_t)q2];
+                    if (!cseen[(size_t)c2]) { cseen[(size_t)c2] = 1; level[(size_t)c2] = level[(size_t)c] + 1; out.push_back(c2); }
+                }
+            }
+        }
+    };
+    order.clear();
+    if (nmem == 0) return;
+    int32_t start = 0;
+    while (cptr[(size_t)start + 1] == cptr[(size_t)start]) ++start;   // camera 0, or the first member when camera 0 is none
+    // From a camera in the middle of a trajectory the search advances on two fronts and every aggregate would hold two distant stretches.
+    // So the search is repeated from the camera reached last; it replaces the first one unless the start lies in its last level (the start
+    // is then an end of the trajectory itself and the order from it stands)
+    std::vector<int32_t> first;
+    bfs(start, first);
+    const int32_t far = first.back();
+    bfs(far, order);   // reaches the component of the first search: the same cameras, so cseen ends as that search left it
+    if (level[(size_t)start] == level[(size_t)order.back()]) order.swap(first);
+    for (int64_t i = 0; i < n; ++i)
+        if (!cseen[(size_t)i] && cptr[(size_t)i + 1] > cptr[(size_t)i]) order.push_back((int32_t)i);
+}
 
 void bundle_adjust(const SchurOp &S, const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out, hipStream_t st) {
     out = BaOutcome();

@@ -305,7 +305,12 @@ int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot,
     if (!(o.eta > 0.0 && o.eta < 1.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: eta must lie in (0, 1)");
     if (o.max_iters < 0 || bad(o.max_time) || bad(o.function_tol) || bad(o.gradient_tol) || bad(o.parameter_tol))
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: negative or non-finite setting");
-    if (o.flags & ~(XM_BA_FIX_ROTATIONS | XM_BA_NONMONOTONIC | XM_BA_DENSE_SCHUR)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: unknown flag");
+    if (o.flags & ~(XM_BA_FIX_ROTATIONS | XM_BA_NONMONOTONIC | XM_BA_DENSE_SCHUR | XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS))
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: unknown flag");
+    if ((o.flags & XM_BA_PRECOND_TWO_LEVEL) && (o.flags & XM_BA_PRECOND_BLOCKS))
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: XM_BA_PRECOND_TWO_LEVEL and XM_BA_PRECOND_BLOCKS exclude each other");
+    if ((o.flags & XM_BA_DENSE_SCHUR) && (o.flags & (XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS)))
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: a PCG preconditioner is given but XM_BA_DENSE_SCHUR does not run the PCG");
     if (o.loss < XM_BA_LOSS_TRIVIAL || o.loss > XM_BA_LOSS_ARCTAN) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: unknown loss");
     if (o.loss == XM_BA_LOSS_TRIVIAL && o.loss_scale != 0.0)
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: loss_scale is given but the loss is trivial");
@@ -333,6 +338,7 @@ int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot,
     c.loss = o.loss; c.loss_scale = o.loss_scale;
     c.nonmonotonic = (o.flags & XM_BA_NONMONOTONIC) != 0;
     c.dense_schur = (o.flags & XM_BA_DENSE_SCHUR) != 0;
+    c.precond = (o.flags & XM_BA_PRECOND_TWO_LEVEL) ? 2 : (o.flags & XM_BA_PRECOND_BLOCKS) ? 1 : 0;
     if (o.max_nonmonotonic > 0) c.max_nonmonotonic = o.max_nonmonotonic;
     c.trace_cap = o.trace_cap; c.trace = o.trace;
     xm::BaOutcome r;
@@ -342,7 +348,7 @@ int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot,
     out.struct_size = sizeof(xm_ba_result_t);
     out.status = r.status; out.iters = r.iters; out.accepted = r.accepted; out.pcg_iters = r.pcg_iters; out.n_used = r.n_used;
     out.initial_cost = r.initial_cost; out.final_cost = r.final_cost; out.gradient_max = r.gradient_max; out.seconds = r.seconds;
-    out.trace_len = r.trace_len;
+    out.trace_len = r.trace_len; out.coarse_fallbacks = r.coarse_fallbacks;
     *res = out;
     return XM_OK;
     XM_CATCH
@@ -866,6 +872,17 @@ int xm_schur_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const i
     std::vector<int32_t> order;
     xm::schur_aggregate_plan(n, nobs, cam, lm, B, order);
     agg_of_camera[0] = -1;
+    for (size_t k = 0; k < order.size(); ++k) agg_of_camera[order[k]] = (int32_t)(k / (size_t)B);
+    return XM_OK;
+    XM_CATCH
+}
+// host-only view of the aggregates of the bundle adjustment's preconditioners (xm_ba.h) for the CPU test
+int xm_ba_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int32_t *lm, const uint8_t *used, int B, int32_t *agg_of_camera) {
+    XM_TRY
+    if (!agg_of_camera) throw xm::Error(XM_ERR_ARG, "xm_ba_aggregate_plan: null output");
+    std::vector<int32_t> order;
+    xm::ba_aggregate_plan(n, nobs, cam, lm, used, B, order);
+    for (int64_t i = 0; i < n; ++i) agg_of_camera[i] = -1;
     for (size_t k = 0; k < order.size(); ++k) agg_of_camera[order[k]] = (int32_t)(k / (size_t)B);
     return XM_OK;
     XM_CATCH

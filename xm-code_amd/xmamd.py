@@ -35,7 +35,7 @@ EXPORTS = [
     "xm_ctx_attach_edges", "xm_ctx_edge_residuals", "xm_ctx_edge_residuals_recovered", "xm_ctx_xm2_filter", "xm_ctx_xm2_round", "xm_ctx_set_edge_weights", "xm_ctx_recover_tp", "xm_ctx_schur_info", "xm_ctx_qw", "xm_spd_inverse", "xm_ctx_transport", "xm_ctx_sell_wpad", "xm_ctx_product_kind", "xm_symw_plan", "xm_symw_use",
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
-    "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve",
+    "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_ba_aggregate_plan",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -97,7 +97,7 @@ class BaOptions(C.Structure):
 class BaResult(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("status", C.c_int32), ("iters", C.c_int32), ("accepted", C.c_int32),
                 ("pcg_iters", C.c_int64), ("n_used", C.c_int64), ("initial_cost", C.c_double), ("final_cost", C.c_double),
-                ("gradient_max", C.c_double), ("seconds", C.c_double), ("trace_len", C.c_int32)]
+                ("gradient_max", C.c_double), ("seconds", C.c_double), ("trace_len", C.c_int32), ("coarse_fallbacks", C.c_int32)]
 
 
 BA_FIX_ROTATIONS = 1
@@ -105,6 +105,11 @@ BA_NONMONOTONIC = 2
 BA_DENSE_SCHUR = 16            # Ceres's DENSE_SCHUR for the reduced camera system (include/xm_amd.h)
 BA_DENSE_MAX_ROWS = 32768      # ... up to this many rows (6 per camera, 3 with fixed rotations)
 BA_LINEAR_SOLVERS = {"iterative_schur": 0, "dense_schur": BA_DENSE_SCHUR}
+BA_PRECOND_TWO_LEVEL = 32      # PCG preconditioner: aggregate blocks + rigid-motion coarse operator (include/xm_amd.h)
+BA_PRECOND_BLOCKS = 64         # ... the aggregate blocks alone
+BA_AGG_CAMS = 16               # cameras per aggregate
+BA_MAX_AGGREGATES = 4096
+BA_PRECONDITIONERS = {"jacobi": 0, "blocks": BA_PRECOND_BLOCKS, "two_level": BA_PRECOND_TWO_LEVEL}
 BA_LOSS = {"trivial": 0, "huber": 1, "soft_l1": 2, "cauchy": 3, "arctan": 4}
 BA_OPTIONS_SIZE_V1 = 64        # struct_size of callers built before loss, max_nonmonotonic and loss_scale (include/xm_amd.h)
 BA_STATUS = {0: "no_convergence", 1: "function_tolerance", 2: "gradient_tolerance", 3: "parameter_tolerance", 4: "max_iterations",
@@ -150,6 +155,7 @@ def lib():
         L.xm_ctx_schur_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_double)]
         L.xm_ctx_schur_precond_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
         L.xm_schur_aggregate_plan.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.xm_ba_aggregate_plan.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.xm_ctx_sell_wpad.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.xm_ctx_product_kind.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.xm_bench_last_error.restype = C.c_char_p
@@ -460,6 +466,20 @@ def schur_aggregate_plan(cam, lm, n=None, B=64):
     return out
 
 
+def ba_aggregate_plan(cam, lm, n=None, used=None, B=BA_AGG_CAMS):
+    """aggregate of every camera in the opt-in preconditioners of Context.bundle_adjust ("blocks", "two_level"), -1 for a camera without
+    a used observation (used: one flag per observation, None = all) -- host only"""
+    cam = np.ascontiguousarray(cam, dtype=np.int32); lm = np.ascontiguousarray(lm, dtype=np.int32)
+    n = int(cam.max()) + 1 if n is None else int(n)
+    u = None if used is None else np.ascontiguousarray(np.asarray(used) != 0, dtype=np.uint8)
+    if cam.size != lm.size or (u is not None and u.size != cam.size):
+        raise XmError("ba_aggregate_plan: cam, lm and used must have one entry per observation")
+    out = np.zeros(n, dtype=np.int32)
+    _chk(lib().xm_ba_aggregate_plan(n, cam.size, cam.ctypes.data_as(C.c_void_p), lm.ctypes.data_as(C.c_void_p),
+                                    None if u is None else u.ctypes.data_as(C.c_void_p), int(B), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 def symw_plan(ntot, nloc, cam0, K=0):
     """work list of one rank of the multi-rank symmetric window product (xm_symw.h) -- host only"""
     geom = np.zeros(8, dtype=np.int32)
@@ -665,13 +685,17 @@ class Context:
 
     def bundle_adjust(self, rot, t, P, fix_rotations=False, max_iters=1000, max_time=300.0, eta=0.1, function_tol=1e-6,
                       gradient_tol=1e-10, parameter_tol=1e-8, trace=0, loss="trivial", loss_scale=0.0, nonmonotonic=False, max_nonmonotonic=0,
-                      linear_solver="iterative_schur"):
+                      linear_solver="iterative_schur", preconditioner="jacobi"):
         """reprojection bundle adjustment of a recovered solution (the reference's Ceres refinement, xm_ctx_bundle_adjust): rot 3 x 3n
         (R_i), t 3 x n, P 3 x m as recover_rotations / recover_tp return them -> refined (rot, t, P, info); matrix-free contexts only.
         loss: a BA_LOSS name with its scale loss_scale (Ceres's a, in normalised image units: pixels / focal length); nonmonotonic=True:
         Ceres's non-monotonic steps (the reference's configuration), reference cost reset after max_nonmonotonic (0 = 5) steps without a
         new minimum, the least-cost point returned.  linear_solver: "iterative_schur" (block-Jacobi PCG to eta, Ceres's ITERATIVE_SCHUR) or
         "dense_schur" (the reduced camera system assembled densely and solved by Cholesky, Ceres's DENSE_SCHUR; up to BA_DENSE_MAX_ROWS rows).
+        preconditioner (of the PCG): "jacobi" (the inverted camera blocks, Ceres's SCHUR_JACOBI), "blocks" (inverted blocks of BA_AGG_CAMS
+        cameras along a breadth-first order) or "two_level" (those blocks plus a coarse operator on the rigid-plus-scale motions of every
+        aggregate: for sequential captures, where the default runs into its iteration cap); info["coarse_fallbacks"]: LM iterations
+        whose coarse operator could not be inverted and that ran with the blocks alone.
         info: status (BA_STATUS), iters, accepted, pcg_iters, n_used, initial_cost, final_cost, gradient_max, seconds, and with trace > 0
         "trace": one row per LM iteration (cost, candidate cost, mu, accepted, PCG iterations, PCG relative residual); costs are
         1/2 sum rho(|r|^2)"""
@@ -681,11 +705,14 @@ class Context:
             raise XmError(f"unknown loss {loss!r} (one of {', '.join(BA_LOSS)})")
         if linear_solver not in BA_LINEAR_SOLVERS:
             raise XmError(f"unknown linear solver {linear_solver!r} (one of {', '.join(BA_LINEAR_SOLVERS)})")
+        if preconditioner not in BA_PRECONDITIONERS:
+            raise XmError(f"unknown preconditioner {preconditioner!r} (one of {', '.join(BA_PRECONDITIONERS)})")
         opt = BaOptions(); res = BaResult()
         opt.struct_size, res.struct_size = C.sizeof(BaOptions), C.sizeof(BaResult)
         opt.max_iters, opt.max_time, opt.eta = int(max_iters), float(max_time), float(eta)
         opt.function_tol, opt.gradient_tol, opt.parameter_tol = float(function_tol), float(gradient_tol), float(parameter_tol)
         opt.flags = (BA_FIX_ROTATIONS if fix_rotations else 0) | (BA_NONMONOTONIC if nonmonotonic else 0) | BA_LINEAR_SOLVERS[linear_solver]
+        opt.flags |= BA_PRECONDITIONERS[preconditioner]
         opt.loss, opt.loss_scale, opt.max_nonmonotonic = BA_LOSS[loss], float(loss_scale), int(max_nonmonotonic)
         tr = None
         if trace:
