@@ -494,6 +494,41 @@ int xm_schur_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const i
  * middle on two -- the members never reached appended in index order, cut into runs of B (1..64; the solver uses XM_BA_AGG_CAMS).  agg_of_camera[n]: the
  * aggregate of every camera, -1 for one without a used observation.  More than XM_BA_MAX_AGGREGATES aggregates: XM_ERR_ARG. */
 int xm_ba_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int32_t *lm, const uint8_t *used, int B, int32_t *agg_of_camera);
+/* One linearisation of xm_ctx_bundle_adjust, a test export (tests/test_gpu_ba_stages.py): at the point (rot, t, p) (the layouts, context and
+ * refusals of xm_ctx_bundle_adjust) and the damping mu > 0 it runs one eval + landmark pass + camera pass with the kernels, grids and
+ * arguments of the LM loop (one workspace class serves both) and fills the scalars and every array whose pointer is not null; arrays per
+ * landmark come by input index, CD = 3 with XM_BA_FIX_ROTATIONS, else 6; NC = 4 or 7.  flags: XM_BA_FIX_ROTATIONS, XM_BA_PRECOND_BLOCKS,
+ * XM_BA_PRECOND_TWO_LEVEL (the others: XM_ERR_ARG); loss, loss_scale as in xm_ba_options_t.
+ *   cost, n_used, gmax                       the state word after the passes
+ *   b (CD n), g_l (3 m), vinv (6 m: the entries 00 01 02 11 12 22 of (V + mu D)^-1), ustar, sinv (CD CD n, row-major blocks), cused (n), lused (m)
+ *   X (CD n x k, column-major, input) -> SX = S X by the matrix-free product, MX = M^-1 X for the selected preconditioner through the PCG's
+ *                                            start (b := X_j, the init launch or launches, z read back)
+ *   Sdense (CD n square, column-major)       the assembled lower block triangle before factorisation, the rest 0; CD n >
+ *                                            XM_BA_PROBE_DENSE_MAX_ROWS: XM_ERR_ARG
+ *   XM_BA_PRECOND_TWO_LEVEL: Pm (CD n x NC, row-major: every camera's rows of its coarse aggregate's scaled columns), dropped (NC ncoarse,
+ *                                            1 = a column of norm 0), Ac (NC ncoarse square, column-major, the lower block triangle as assembled,
+ *                                            before inversion; the caller sizes both for ncoarse <= ceil(n / XM_BA_AGG_CAMS)), coarse_ok (A_c was
+ *                                            inverted); nagg, ncoarse (0 without the coarse space)
+ *   dc (CD n, input) -> dP (3 m) = -V*^-1 (g_l + W^T dc), the candidate rot1, t1, p1 in the caller's layouts (members without a used
+ *                                            observation: the input bits), cost1, model = sum r.(J d) + |J d|^2 / 2, step2, x2 (cameras, landmarks)
+ * The context is only read.  Allocates and frees its workspace per call. */
+#define XM_BA_PROBE_DENSE_MAX_ROWS 4096  /* a 134 MB matrix copied to the host */
+typedef struct {
+    uint32_t struct_size;
+    uint32_t flags;
+    int32_t loss, pad;
+    double loss_scale, mu;
+    int64_t k;
+    const double *X, *dc;
+    double cost, gmax, cost1, model, step2[2], x2[2];
+    int64_t n_used;
+    int32_t nagg, ncoarse, coarse_ok, pad2;
+    double *b, *g_l, *vinv, *ustar, *sinv;
+    int32_t *cused, *lused;
+    double *SX, *Sdense, *MX, *Pm, *dropped, *Ac;
+    double *dP, *rot1, *t1, *p1;
+} xm_ba_probe_t;
+int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_ba_probe_t *probe);
 /* Large block-sparse Q: "sliced ELL over per-XCD column slabs" (xm-code_amd/csrc/xm_sell.h).  Same product as xm_qw_bsr3
  * (the reference has no sparse product: Dense/matmul.h:42-87 on a dense Q); the matrix is described on the HOST as 3x3-block CSR
  * (rows n, global columns in [0, ncols)) and re-laid on the device.  slabs in {1,2,4,8}; lmax = longest virtual row (hub

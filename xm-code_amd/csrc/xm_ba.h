@@ -8,7 +8,8 @@
 // Per LM iteration (host loop, xm_ba.hip):
 //   eval        r_e, J_e = [J_c | J_P] at the current point (after an accepted step only)
 //   landmarks   V_l = sum J_P^T J_P, g_l = sum J_P^T r, (V_l + mu D_l)^-1                 thread per light landmark, workgroup per heavy one
-//   cameras     U_i, g_i, S_ii = U*_i - sum W V*^-1 W^T, its Cholesky inverse, b_i = -g_i + sum W V*^-1 g_l      wavefront per camera
+//   cameras     U_i, g_i, S_ii = U*_i - sum_l (sum_e W_e) V*^-1 (sum_f W_f)^T (e, f: the observations of (i, l), one unless a pair is named
+//               twice), its Cholesky inverse, b_i = -g_i + sum W V*^-1 g_l                                             wavefront per camera
 //   PCG         S dc = b from zero, S applied as U* x - sum W V*^-1 W^T x through the two lists, block-Jacobi preconditioner, batches that
 //               run ahead of the host and are polled through a state word (as SchurOp::pcg_solve)
 //   or dense    (XM_BA_DENSE_SCHUR) S assembled as a dense lower block triangle (wavefront per block row), Cholesky factor and two
@@ -19,6 +20,7 @@
 //   precond     (XM_BA_PRECOND_BLOCKS / XM_BA_PRECOND_TWO_LEVEL, opt-in) M^-1 = blockdiag(S_aa)^-1 [+ P A_c^-1 P^T] in place of the inverted camera
 //               blocks: aggregates of XM_BA_AGG_CAMS cameras along a breadth-first order (host, once per call); per LM iteration a workgroup
 //               per aggregate assembles S_aa in LDS and inverts it there, a wavefront per aggregate assembles its rows of A_c = P^T S P
+//               (a compensated sum: thousands of small terms meet P^T U* P in every entry)
 //               (P: the 7 rigid-plus-scale motions of each aggregate, 4 with fixed rotations; recomputed after every accepted step), and
 //               A_c is inverted by spd_inverse_device; per PCG iteration two launches (update + block GEMVs + P^T r; coarse GEMV +
 //               combination + <r, z>) replace the update kernel
@@ -73,8 +75,25 @@ struct BaOutcome {
 // More than XM_BA_MAX_AGGREGATES aggregates: XM_ERR_ARG.
 void ba_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int32_t *lm, const uint8_t *used, int B, std::vector<int32_t> &order);
 
+// One linearisation for the test export xm_ctx_ba_probe (include/xm_amd.h): inputs and host output arrays, each written only when its pointer
+// is not null.  Per-landmark arrays come back by input index.
+struct BaProbe {
+    double mu = 0.0;
+    int64_t k = 0;
+    const double *X = nullptr, *dc = nullptr;   // CD n x k column-major; CD n
+    double cost = 0, gmax = 0, cost1 = 0, model = 0, step2[2] = {0, 0}, x2[2] = {0, 0};
+    int64_t n_used = 0;
+    int32_t nagg = 0, ncoarse = 0, coarse_ok = 0;
+    double *b = nullptr, *g_l = nullptr, *vinv = nullptr, *ustar = nullptr, *sinv = nullptr;
+    int32_t *cused = nullptr, *lused = nullptr;
+    double *SX = nullptr, *Sdense = nullptr, *MX = nullptr, *Pm = nullptr, *dropped = nullptr, *Ac = nullptr;
+    double *dP = nullptr, *rot1 = nullptr, *t1 = nullptr, *p1 = nullptr;
+};
+
 // rot: 3 x 3n column-major (R_i, camera-to-world), t: 3 x n, p: 3 x m (host, updated in place).  The SchurOp is only read.
 void bundle_adjust(const SchurOp &S, const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out, hipStream_t st);
+// cfg: fix_rotations, loss, loss_scale, precond and watchdog_s are read.  The launches are those of bundle_adjust (one workspace class serves both).
+void ba_probe(const SchurOp &S, const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q, hipStream_t st);
 // sqerr[e] = |r_e|^2 (unrobustified) of observation e in input order at (rot, t, p), -1 where it is not used (weight <= 0 or p_e2 <= 0)
 void reprojection_errors(const SchurOp &S, const double *rot, const double *t, const double *p, double *sqerr, double watchdog_s, hipStream_t st);
 

@@ -304,7 +304,8 @@ __device__ void chol_inverse(const double (&A)[CD][CD], double *out) {
         }
 }
 
-// ---- camera pass (a wavefront per camera): U_i, g_i; S_ii = U*_i - sum W V*^-1 W^T and its inverse; b_i = -g_i + sum W V*^-1 g_l
+// ---- camera pass (a wavefront per camera): U_i, g_i; S_ii = U*_i - sum_l (sum_e W_e) V*_l^-1 (sum_f W_f)^T over the observations e, f of
+// (i, l) and its inverse; b_i = -g_i + sum W V*^-1 g_l
 template <int CD>
 __global__ __launch_bounds__(256) void ba_cam_kernel(SchurLists S, const double *__restrict__ Jc, const double *__restrict__ vinv,
                                                      const double *__restrict__ gl, double mu, double *__restrict__ ustar, double *__restrict__ sinv,
@@ -350,6 +351,22 @@ __global__ __launch_bounds__(256) void ba_cam_kernel(SchurLists S, const double 
                 acc[2 * NU + CD + k] += WV[k][0] * g0 + WV[k][1] * g1 + WV[k][2] * g2;
             }
             acc[NA - 1] += obs_used(jp) ? 1.0 : 0.0;
+            // a (camera, landmark) pair named more than once: S_ii holds (sum_e W_e) V*^-1 (sum_f W_f)^T, so every other observation f of the
+            // pair brings W_e V*^-1 W_f^T.  The list is sorted by landmark: they are this entry's neighbours (none in an ordinary scene)
+            for (int dir = -1; dir <= 1; dir += 2)
+                for (int64_t f = e + dir; f >= S.cam_ptr[cam] && f < S.cam_ptr[cam + 1] && S.cam_lm[f] == l; f += dir) {
+                    double Wf[CD][3];
+#pragma unroll
+                    for (int k = 0; k < CD; ++k)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c)
+                            Wf[k][c] = Jc[(size_t)k * S.nobs + f] * Jc[(size_t)(JP + c) * S.nobs + f] +
+                                       Jc[(size_t)(CD + k) * S.nobs + f] * Jc[(size_t)(JP + 3 + c) * S.nobs + f];
+#pragma unroll
+                    for (int j = 0; j < CD; ++j)
+#pragma unroll
+                        for (int k = 0; k <= j; ++k) acc[NU + tri(k, j)] += WV[k][0] * Wf[j][0] + WV[k][1] * Wf[j][1] + WV[k][2] * Wf[j][2];
+                }
         }
 #pragma unroll
     for (int k = 0; k < NA; ++k) acc[k] = wave_sum(acc[k]);
@@ -1037,10 +1054,13 @@ __global__ __launch_bounds__(256) void ba_tl_block_kernel(SchurLists S, BaTl t, 
 // its members' lists in order; for observation e of landmark l the lanes run over l's list, 64 at a time: lane f forms T_f = J_P,f^T J_c,f
 // P_cam(f) (3 x NC), the first lane of every coarse aggregate b <= a in the batch adds those of the later lanes of b in lane order and
 // subtracts (P_i^T W_e V*_l^-1) T from block (a, b).  One writer per entry, a workgroup fence between batches: fixed order, no atomics.
+// Every addition's rounding error (two-sum) is collected in a second matrix lo of the same shape and added once at the end: without it an
+// entry lost about sqrt(additions) ulp of P^T U* P, which A_c's own entries can be far below (rigid motions are S's near-null vectors).
 template <int CD>
 __global__ __launch_bounds__(256) void ba_tl_coarse_kernel(SchurLists S, BaTl t, const double *__restrict__ Jc, const double *__restrict__ Jl,
                                                            const double *__restrict__ vinv, const double *__restrict__ ustar,
-                                                           const double *__restrict__ drop, double *__restrict__ Ac, int64_t ld) {
+                                                           const double *__restrict__ drop, double *__restrict__ Ac, double *__restrict__ lo,
+                                                           int64_t ld) {
     constexpr int JP = ba_jp<CD>(), NC = ba_nc<CD>();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int ca = blockIdx.x * kQwWaves + wv;
@@ -1048,6 +1068,7 @@ __global__ __launch_bounds__(256) void ba_tl_coarse_kernel(SchurLists S, BaTl t,
     int k0, k1;
     coarse_range(t, ca, k0, k1);
     double *row = Ac + (size_t)NC * ca;   // entry (NC ca + r, c) at row[r + c ld]
+    double *lrow = lo + (size_t)NC * ca;  // the rounding errors of the additions to that entry (zeroed by the caller), added at the end
     if (lane < NC * NC) {
         const int r = lane / NC, c = lane % NC;
         double s = 0.0;
@@ -1138,15 +1159,24 @@ __global__ __launch_bounds__(256) void ba_tl_coarse_kernel(SchurLists S, BaTl t,
                         }
                 }
                 if (b >= 0 && rank == 0) {
-                    double *blk = row + (size_t)NC * b * ld;
+                    double *blk = row + (size_t)NC * b * ld, *lob = lrow + (size_t)NC * b * ld;
 #pragma unroll
                     for (int c = 0; c < NC; ++c)
 #pragma unroll
-                        for (int r = 0; r < NC; ++r) blk[r + (size_t)c * ld] -= X[r][0] * T[0][c] + X[r][1] * T[1][c] + X[r][2] * T[2][c];
+                        for (int r = 0; r < NC; ++r) {   // an entry takes thousands of small terms next to P^T U* P: the sum is compensated
+                            const double u = -(X[r][0] * T[0][c] + X[r][1] * T[1][c] + X[r][2] * T[2][c]), h = blk[r + (size_t)c * ld];
+                            const double s = h + u, v = s - h;
+                            blk[r + (size_t)c * ld] = s;
+                            lob[r + (size_t)c * ld] += (h - (s - v)) + (u - v);
+                        }
                 }
                 __threadfence_block();
             }
         }
+    }
+    for (int q = lane; q < NC * NC * (ca + 1); q += 64) {
+        const size_t at = (size_t)(q % NC) + (size_t)(q / NC) * ld;
+        row[at] += lrow[at];
     }
 }
 // *flag <- 1 when an entry of the n x n matrix is not finite
@@ -1315,78 +1345,88 @@ void to_device_layout(const SchurOp &SO, const double *rot, const double *t, con
         for (int a = 0; a < 3; ++a) hP[(size_t)3 * slot_of[(size_t)l] + a] = p[(size_t)3 * l + a];
 }
 
+// One linearisation's device state and the launches on it: the workspace, the eval / landmark / camera passes, the preconditioner's
+// set-up, the product S x, the dense assembly, the PCG's start and the candidate block.  run() (the LM loop) and probe() (the test export
+// xm_ctx_ba_probe) both go through these members, so the probe launches what the loop launches: same kernels, grids and arguments.
 template <int CD>
-void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out, hipStream_t st) {
-    const auto t_start = std::chrono::steady_clock::now();
-    const SchurLists S = SO.lists();
-    const std::vector<int32_t> &slot_of = SO.slot_of();
-    const int64_t n = S.n, m = S.m, nobs = S.nobs;
-    constexpr int NP = ba_planes<CD>();
-    // ---- parameters on the device; three sets with non-monotonic steps (current, candidate, least cost so far), two otherwise
+struct BaWork {
+    static constexpr int NP = ba_planes<CD>(), NC = ba_nc<CD>(), NB = kBaAgg * CD;
+    const SchurOp &SO;
+    const BaSettings &cfg;
+    hipStream_t st;
+    const SchurLists S;
+    const int64_t n, m, nobs;
     std::vector<double> hR, hT, hP;
-    to_device_layout(SO, rot, t, p, hR, hT, hP);
-    const bool nonmono = cfg.nonmonotonic;
+    // ---- parameters on the device; three sets with non-monotonic steps (current, candidate, least cost so far), two otherwise
     DevBuf<double> R[3], T[3], P[3];
-    for (int k = 0; k < (nonmono ? 3 : 2); ++k) { R[k].alloc((size_t)9 * n, false); T[k].alloc((size_t)3 * n, false); P[k].alloc((size_t)3 * m, false); }
-    XM_HIP_CHECK(hipMemcpyAsync(R[0].p, hR.data(), hR.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    XM_HIP_CHECK(hipMemcpyAsync(T[0].p, hT.data(), hT.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    XM_HIP_CHECK(hipMemcpyAsync(P[0].p, hP.data(), hP.size() * sizeof(double), hipMemcpyHostToDevice, st));
     // ---- workspace (zero: the padding of the packed landmark lists stays 0 in every plane)
     DevBuf<double> Jc, Jl, vinv, gl, ustar, sinv, b, x, r, z, pv, Ap, y, dP, parts;
     DevBuf<int32_t> lused, cused, state_buf;
-    Jc.alloc((size_t)NP * nobs); Jl.alloc((size_t)NP * S.lm_total);
-    vinv.alloc((size_t)6 * m); gl.alloc((size_t)3 * m); y.alloc((size_t)3 * m); dP.alloc((size_t)3 * m); lused.alloc((size_t)m);
-    ustar.alloc((size_t)CD * CD * n); sinv.alloc((size_t)CD * CD * n); cused.alloc((size_t)n);
-    for (DevBuf<double> *v : {&b, &x, &r, &z, &pv, &Ap}) v->alloc((size_t)CD * n);
-    state_buf.alloc(sizeof(BaState) / sizeof(int32_t) + 2);
-    BaState *dst = reinterpret_cast<BaState *>(state_buf.p);
+    BaState *dst = nullptr;
     PinnedState hs;
-    const int ge = flat_grid(nobs), gfc = flat_grid(n), gfl = flat_grid(m), gcam = qw_grid((int)n);
-    const int glm = (int)(S.nheavy + (m - S.nheavy + kBaHeavyThreads - 1) / kBaHeavyThreads);
-    // partials: eval (2 ge) | gmax (glm + gcam) | PCG (4 gfc + gcam) | candidate step / |x| (cameras then landmarks, 2 x (gfc + gfl)) | cost (2 ge)
-    const size_t o_eval = 0, o_gmax = o_eval + 2 * (size_t)ge, o_pcg = o_gmax + glm + gcam, o_cand = o_pcg + 4 * (size_t)gfc + gcam,
-                 o_cost = o_cand + 2 * ((size_t)gfc + gfl), n_parts = o_cost + 2 * (size_t)ge;
-    parts.alloc(n_parts);
-    double *pp = parts.p;
-    const dim3 b256(256), blm(kBaHeavyThreads);
-    auto reduce = [&](BaReduce rd) { hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), b256, 0, st, rd); };
-    auto read_state = [&](const char *what) {
-        check_launch(what);
-        XM_HIP_CHECK(hipMemcpyAsync(hs.h, dst, sizeof(BaState), hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, what);
-        return *hs.h;
-    };
+    int ge = 0, gfc = 0, gfl = 0, gcam = 0, glm = 0;
+    size_t o_eval = 0, o_gmax = 0, o_pcg = 0, o_cand = 0, o_cost = 0;
+    double *pp = nullptr;
+    const dim3 b256{256}, blm{kBaHeavyThreads};
     int cur = 0, best = 0;   // the current point and the one of least cost so far (the same one without non-monotonic steps)
-    auto eval = [&]() {
-        launch_eval<CD>(cfg.loss, cfg.loss_scale, ge, st, S, R[cur].p, T[cur].p, P[cur].p, Jc.p, Jl.p, pp + o_eval);
-        BaReduce rd{};
-        rd.sum_p[0] = pp + o_eval; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->cost;
-        rd.sum_p[1] = pp + o_eval + ge; rd.sum_n[1] = ge; rd.sum_out[1] = &dst->used;
-        reduce(rd);
-    };
-    auto passes = [&](double mu) {
-        hipLaunchKernelGGL((ba_lm_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, mu, vinv.p, gl.p, lused.p, pp + o_gmax);
-        hipLaunchKernelGGL((ba_cam_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)vinv.p, (const double *)gl.p, mu,
-                           ustar.p, sinv.p, b.p, cused.p, pp + o_gmax + glm);
-        BaReduce rd{};
-        rd.max_p = pp + o_gmax; rd.max_n = glm + gcam; rd.max_out = &dst->gmax;
-        reduce(rd);
-    };
     BaPcg a;
-    a.n = n; a.grid = gfc; a.cgrid = gcam; a.tol2 = cfg.eta * cfg.eta;
-    a.b = b.p; a.sinv = sinv.p; a.ustar = ustar.p; a.x = x.p; a.r = r.p; a.z = z.p; a.p = pv.p; a.Ap = Ap.p;
-    a.prz[0] = pp + o_pcg; a.prz[1] = pp + o_pcg + gfc; a.prr = pp + o_pcg + 2 * gfc; a.pbb = pp + o_pcg + 3 * gfc; a.ppap = pp + o_pcg + 4 * gfc;
-    a.st = dst;
     // opt-in preconditioners: the plan from the used observations (host, once), the blocks and the coarse operator (device, allocated here
-    // and freed on return).  atl: the PCG's arguments with the partial sums of <r, z>, |r|^2 and |b|^2 by coarse aggregate
-    constexpr int NC = ba_nc<CD>(), NB = kBaAgg * CD;
-    bool tlmode = cfg.precond != 0;
+    // and freed with the workspace).  atl: the PCG's arguments with the partial sums of <r, z>, |r|^2 and |b|^2 by coarse aggregate
+    bool tlmode = false;
     BaTl tl{};
-    BaPcg atl = a;
+    BaPcg atl;
     DevBuf<int32_t> tl_order, tl_agg, tl_flag;
     DevBuf<double> tl_binv, tl_P, tl_drop, tl_gpart, tl_parts, tl_A, tl_X;
     int64_t nct = 0;
-    if (tlmode) {
+    bool basis_stale = true;   // P belongs to the current point: recomputed after every accepted step
+    int coarse_fallbacks = 0;
+    double *ac_copy = nullptr;   // probe only: A_c as assembled (device, nct x nct), copied before it is inverted in place
+    // dense Schur: the CD n x CD n matrix, allocated here and freed with the workspace; the substitutions' scratch vector
+    const int64_t nd;
+    DevBuf<double> Sd, ysub;
+
+    BaWork(const SchurOp &SO_, const BaSettings &cfg_, const double *rot, const double *t, const double *p, hipStream_t st_, bool dense)
+        : SO(SO_), cfg(cfg_), st(st_), S(SO_.lists()), n(S.n), m(S.m), nobs(S.nobs), nd((int64_t)CD * S.n) {
+        to_device_layout(SO, rot, t, p, hR, hT, hP);
+        const bool nonmono = cfg.nonmonotonic;
+        for (int k = 0; k < (nonmono ? 3 : 2); ++k) { R[k].alloc((size_t)9 * n, false); T[k].alloc((size_t)3 * n, false); P[k].alloc((size_t)3 * m, false); }
+        XM_HIP_CHECK(hipMemcpyAsync(R[0].p, hR.data(), hR.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        XM_HIP_CHECK(hipMemcpyAsync(T[0].p, hT.data(), hT.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        XM_HIP_CHECK(hipMemcpyAsync(P[0].p, hP.data(), hP.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        Jc.alloc((size_t)NP * nobs); Jl.alloc((size_t)NP * S.lm_total);
+        vinv.alloc((size_t)6 * m); gl.alloc((size_t)3 * m); y.alloc((size_t)3 * m); dP.alloc((size_t)3 * m); lused.alloc((size_t)m);
+        ustar.alloc((size_t)CD * CD * n); sinv.alloc((size_t)CD * CD * n); cused.alloc((size_t)n);
+        for (DevBuf<double> *v : {&b, &x, &r, &z, &pv, &Ap}) v->alloc((size_t)CD * n);
+        state_buf.alloc(sizeof(BaState) / sizeof(int32_t) + 2);
+        dst = reinterpret_cast<BaState *>(state_buf.p);
+        ge = flat_grid(nobs); gfc = flat_grid(n); gfl = flat_grid(m); gcam = qw_grid((int)n);
+        glm = (int)(S.nheavy + (m - S.nheavy + kBaHeavyThreads - 1) / kBaHeavyThreads);
+        // partials: eval (2 ge) | gmax (glm + gcam) | PCG (4 gfc + gcam) | candidate step / |x| (cameras then landmarks, 2 x (gfc + gfl)) | cost (2 ge)
+        o_eval = 0; o_gmax = o_eval + 2 * (size_t)ge; o_pcg = o_gmax + glm + gcam; o_cand = o_pcg + 4 * (size_t)gfc + gcam;
+        o_cost = o_cand + 2 * ((size_t)gfc + gfl);
+        const size_t n_parts = o_cost + 2 * (size_t)ge;
+        parts.alloc(n_parts);
+        pp = parts.p;
+        a.n = n; a.grid = gfc; a.cgrid = gcam; a.tol2 = cfg.eta * cfg.eta;
+        a.b = b.p; a.sinv = sinv.p; a.ustar = ustar.p; a.x = x.p; a.r = r.p; a.z = z.p; a.p = pv.p; a.Ap = Ap.p;
+        a.prz[0] = pp + o_pcg; a.prz[1] = pp + o_pcg + gfc; a.prr = pp + o_pcg + 2 * gfc; a.pbb = pp + o_pcg + 3 * gfc; a.ppap = pp + o_pcg + 4 * gfc;
+        a.st = dst;
+        tlmode = cfg.precond != 0;
+        atl = a;
+        if (tlmode) plan_aggregates();
+        if (dense) {
+            if (nd > XM_BA_DENSE_MAX_ROWS) throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: the dense Schur system has more than XM_BA_DENSE_MAX_ROWS rows");
+            const size_t elems = (size_t)nd * (size_t)nd;
+            if (hipMalloc((void **)&Sd.p, elems * sizeof(double)) != hipSuccess) {
+                (void)hipGetLastError();
+                Sd.p = nullptr;
+                throw Error(XM_ERR_NOMEM, "xm_ctx_bundle_adjust: no device memory for the dense Schur system (" + std::to_string(elems * 8 >> 20) + " MB)");
+            }
+            Sd.count = Sd.capacity = elems;
+            ysub.alloc((size_t)nd);
+        }
+    }
+    void plan_aggregates() {
         std::vector<int32_t> hc((size_t)nobs), hl((size_t)nobs), order;
         std::vector<int64_t> hpos((size_t)nobs);
         std::vector<double> hw((size_t)nobs), hp3((size_t)3 * nobs);
@@ -1400,42 +1440,60 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         for (int64_t e = 0; e < nobs; ++e) used[(size_t)e] = (hw[(size_t)hpos[(size_t)e]] > 0.0 && hp3[(size_t)3 * e + 2] > 0.0) ? 1 : 0;
         ba_aggregate_plan(n, nobs, hc.data(), hl.data(), used.data(), kBaAgg, order);
         const int64_t nmem = (int64_t)order.size();
-        if (nmem == 0) tlmode = false;   // no used observation: nothing to precondition (b = 0, the PCG stops at once)
-        else {
-            const int64_t nagg = (nmem + kBaAgg - 1) / kBaAgg, ncoarse = (nagg > 1 && nmem - (nagg - 1) * kBaAgg < 2) ? nagg - 1 : nagg;
-            nct = NC * ncoarse;
-            std::vector<int32_t> agg((size_t)n, -1);
-            for (int64_t k = 0; k < nmem; ++k) agg[(size_t)order[(size_t)k]] = (int32_t)(k / kBaAgg);
-            auto try_alloc = [&](DevBuf<double> &buf, size_t elems, const char *what) {
-                if (hipMalloc((void **)&buf.p, elems * sizeof(double)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    buf.p = nullptr;
-                    throw Error(XM_ERR_NOMEM, std::string("xm_ctx_bundle_adjust: no device memory for ") + what + " (" + std::to_string(elems * 8 >> 20) + " MB)");
-                }
-                buf.count = buf.capacity = elems;
-            };
-            tl_order.alloc((size_t)nmem, false); tl_agg.alloc((size_t)n, false); tl_flag.alloc(1);
-            XM_HIP_CHECK(hipMemcpyAsync(tl_order.p, order.data(), (size_t)nmem * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            XM_HIP_CHECK(hipMemcpyAsync(tl_agg.p, agg.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            wait_stream(st, cfg.watchdog_s, "the aggregate plan");
-            try_alloc(tl_binv, (size_t)nagg * NB * NB, "the preconditioner's blocks");
-            tl_parts.alloc(4 * (size_t)ncoarse);
-            if (cfg.precond == 2) {
-                tl_P.alloc((size_t)n * CD * NC); tl_drop.alloc((size_t)nct); tl_gpart.alloc((size_t)(nagg + 1) * NC);
-                try_alloc(tl_A, (size_t)nct * nct, "the coarse operator");
-                try_alloc(tl_X, (size_t)nct * nct, "the coarse operator's inverse");
+        if (nmem == 0) { tlmode = false; return; }   // no used observation: nothing to precondition (b = 0, the PCG stops at once)
+        const int64_t nagg = (nmem + kBaAgg - 1) / kBaAgg, ncoarse = (nagg > 1 && nmem - (nagg - 1) * kBaAgg < 2) ? nagg - 1 : nagg;
+        nct = NC * ncoarse;
+        std::vector<int32_t> agg((size_t)n, -1);
+        for (int64_t k = 0; k < nmem; ++k) agg[(size_t)order[(size_t)k]] = (int32_t)(k / kBaAgg);
+        auto try_alloc = [&](DevBuf<double> &buf, size_t elems, const char *what) {
+            if (hipMalloc((void **)&buf.p, elems * sizeof(double)) != hipSuccess) {
+                (void)hipGetLastError();
+                buf.p = nullptr;
+                throw Error(XM_ERR_NOMEM, std::string("xm_ctx_bundle_adjust: no device memory for ") + what + " (" + std::to_string(elems * 8 >> 20) + " MB)");
             }
-            tl.nagg = (int32_t)nagg; tl.ncoarse = (int32_t)ncoarse; tl.nmem = (int32_t)nmem; tl.use_coarse = 0;
-            tl.order = tl_order.p; tl.agg_of = tl_agg.p; tl.binv = tl_binv.p; tl.Pm = tl_P.p; tl.ainv = tl_A.p; tl.gpart = tl_gpart.p;
-            atl.grid = (int)ncoarse;
-            atl.prz[0] = tl_parts.p; atl.prz[1] = tl_parts.p + ncoarse; atl.prr = tl_parts.p + 2 * ncoarse; atl.pbb = tl_parts.p + 3 * ncoarse;
+            buf.count = buf.capacity = elems;
+        };
+        tl_order.alloc((size_t)nmem, false); tl_agg.alloc((size_t)n, false); tl_flag.alloc(1);
+        XM_HIP_CHECK(hipMemcpyAsync(tl_order.p, order.data(), (size_t)nmem * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        XM_HIP_CHECK(hipMemcpyAsync(tl_agg.p, agg.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        wait_stream(st, cfg.watchdog_s, "the aggregate plan");
+        try_alloc(tl_binv, (size_t)nagg * NB * NB, "the preconditioner's blocks");
+        tl_parts.alloc(4 * (size_t)ncoarse);
+        if (cfg.precond == 2) {
+            tl_P.alloc((size_t)n * CD * NC); tl_drop.alloc((size_t)nct); tl_gpart.alloc((size_t)(nagg + 1) * NC);
+            try_alloc(tl_A, (size_t)nct * nct, "the coarse operator");
+            try_alloc(tl_X, (size_t)nct * nct, "the coarse operator's inverse");
         }
+        tl.nagg = (int32_t)nagg; tl.ncoarse = (int32_t)ncoarse; tl.nmem = (int32_t)nmem; tl.use_coarse = 0;
+        tl.order = tl_order.p; tl.agg_of = tl_agg.p; tl.binv = tl_binv.p; tl.Pm = tl_P.p; tl.ainv = tl_A.p; tl.gpart = tl_gpart.p;
+        atl.grid = (int)ncoarse;
+        atl.prz[0] = tl_parts.p; atl.prz[1] = tl_parts.p + ncoarse; atl.prr = tl_parts.p + 2 * ncoarse; atl.pbb = tl_parts.p + 3 * ncoarse;
     }
-    bool basis_stale = true;   // P belongs to the current point: recomputed after every accepted step
-    int coarse_fallbacks = 0;
+    void reduce(BaReduce rd) { hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), b256, 0, st, rd); }
+    BaState read_state(const char *what) {
+        check_launch(what);
+        XM_HIP_CHECK(hipMemcpyAsync(hs.h, dst, sizeof(BaState), hipMemcpyDeviceToHost, st));
+        wait_stream(st, cfg.watchdog_s, what);
+        return *hs.h;
+    }
+    void eval() {
+        launch_eval<CD>(cfg.loss, cfg.loss_scale, ge, st, S, R[cur].p, T[cur].p, P[cur].p, Jc.p, Jl.p, pp + o_eval);
+        BaReduce rd{};
+        rd.sum_p[0] = pp + o_eval; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->cost;
+        rd.sum_p[1] = pp + o_eval + ge; rd.sum_n[1] = ge; rd.sum_out[1] = &dst->used;
+        reduce(rd);
+    }
+    void passes(double mu) {
+        hipLaunchKernelGGL((ba_lm_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, mu, vinv.p, gl.p, lused.p, pp + o_gmax);
+        hipLaunchKernelGGL((ba_cam_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)vinv.p, (const double *)gl.p, mu,
+                           ustar.p, sinv.p, b.p, cused.p, pp + o_gmax + glm);
+        BaReduce rd{};
+        rd.max_p = pp + o_gmax; rd.max_n = glm + gcam; rd.max_out = &dst->gmax;
+        reduce(rd);
+    }
     // every LM iteration (S changes with mu): the block inverses; two-level: A_c = P^T S P and its inverse.  A_c that cannot be inverted (a
     // pivot that is not positive, an entry that is not finite): this iteration's PCG runs with the blocks alone
-    auto precond_setup = [&]() {
+    void precond_setup() {
         hipLaunchKernelGGL((ba_tl_block_kernel<CD>), dim3((unsigned)tl.nagg), b256, 0, st, S, tl, (const double *)Jc.p, (const double *)Jl.p,
                            (const double *)vinv.p, (const double *)ustar.p, tl_binv.p);
         tl.use_coarse = 0;
@@ -1446,10 +1504,12 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
             basis_stale = false;
         }
         XM_HIP_CHECK(hipMemsetAsync(tl_A.p, 0, tl_A.count * sizeof(double), st));
+        XM_HIP_CHECK(hipMemsetAsync(tl_X.p, 0, tl_X.count * sizeof(double), st));   // the assembly's error terms; the inverse is written over them
         XM_HIP_CHECK(hipMemsetAsync(tl_flag.p, 0, sizeof(int32_t), st));
         hipLaunchKernelGGL((ba_tl_coarse_kernel<CD>), dim3((unsigned)((tl.ncoarse + kQwWaves - 1) / kQwWaves)), b256, 0, st, S, tl, (const double *)Jc.p,
-                           (const double *)Jl.p, (const double *)vinv.p, (const double *)ustar.p, (const double *)tl_drop.p, tl_A.p, nct);
+                           (const double *)Jl.p, (const double *)vinv.p, (const double *)ustar.p, (const double *)tl_drop.p, tl_A.p, tl_X.p, nct);
         check_launch("the two-level preconditioner");
+        if (ac_copy) XM_HIP_CHECK(hipMemcpyAsync(ac_copy, tl_A.p, tl_A.count * sizeof(double), hipMemcpyDeviceToDevice, st));
         bool ok = spd_inverse_device((int)nct, tl_A.p, tl_X.p, st);
         if (ok) {
             spd_inverse_layout((int)nct, tl_X.p, tl_A.p, nct, st);
@@ -1462,61 +1522,90 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         }
         if (ok) tl.use_coarse = 1;
         else coarse_fallbacks++;
-    };
-    // dense Schur: the CD n x CD n matrix, allocated here and freed on return; the substitutions' scratch vector
-    const int64_t nd = (int64_t)CD * n;
-    DevBuf<double> Sd, ysub;
-    if (cfg.dense_schur) {
-        if (nd > XM_BA_DENSE_MAX_ROWS) throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: the dense Schur system has more than XM_BA_DENSE_MAX_ROWS rows");
-        const size_t elems = (size_t)nd * (size_t)nd;
-        if (hipMalloc((void **)&Sd.p, elems * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            Sd.p = nullptr;
-            throw Error(XM_ERR_NOMEM, "xm_ctx_bundle_adjust: no device memory for the dense Schur system (" + std::to_string(elems * 8 >> 20) + " MB)");
-        }
-        Sd.count = Sd.capacity = elems;
-        ysub.alloc((size_t)nd);
     }
-    // S dc = b exactly: assembly, Cholesky, substitutions (dc -> x); then |b - S dc|^2 and |b|^2 with S applied through the matrix-free
-    // kernels of the PCG (the state word's done flag is never set on this path).  Nothing is read by the host here.
-    auto dense_solve = [&]() {
+    // ar.Ap = S ar.p through the two lists (the PCG's product; gate: the state word whose done flag skips the landmark side, or null)
+    void sx(const BaPcg &ar, const BaState *gate) {
+        hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)nullptr, 1.0,
+                           (const int32_t *)lused.p, (const double *)ar.p, gate, y.p);
+        hipLaunchKernelGGL((ba_camx_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)y.p, ar);
+    }
+    // the dense lower block triangle of S into Sd (zeroed here), the failure flag cleared
+    void dense_assemble() {
         XM_HIP_CHECK(hipMemsetAsync(Sd.p, 0, Sd.count * sizeof(double), st));
         XM_HIP_CHECK(hipMemsetAsync(&dst->fail, 0, sizeof(int32_t), st));
         hipLaunchKernelGGL((ba_schur_dense_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)Jl.p, (const double *)vinv.p,
                            (const double *)ustar.p, Sd.p, nd);
+    }
+    // S dc = b exactly: assembly, Cholesky, substitutions (dc -> x); then |b - S dc|^2 and |b|^2 with S applied through the matrix-free
+    // kernels of the PCG (the state word's done flag is never set on this path).  Nothing is read by the host here.
+    void dense_solve() {
+        dense_assemble();
         spd_cholesky_device((int)nd, Sd.p, nd, &dst->fail, st);
         XM_HIP_CHECK(hipMemcpyAsync(x.p, b.p, (size_t)nd * sizeof(double), hipMemcpyDeviceToDevice, st));
         spd_substitute_device((int)nd, Sd.p, nd, x.p, ysub.p, nd, 1, &dst->fail, st);
         BaPcg ar = a;
         ar.p = x.p;
-        hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)nullptr, 1.0,
-                           (const int32_t *)lused.p, (const double *)x.p, (const BaState *)nullptr, y.p);
-        hipLaunchKernelGGL((ba_camx_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)y.p, ar);
+        sx(ar, nullptr);
         hipLaunchKernelGGL((ba_dense_res_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)b.p, (const double *)Ap.p, pp + o_pcg);
         BaReduce rd{};
         rd.sum_p[0] = pp + o_pcg; rd.sum_n[0] = gfc; rd.sum_out[0] = &dst->res2[0];
         rd.sum_p[1] = pp + o_pcg + gfc; rd.sum_n[1] = gfc; rd.sum_out[1] = &dst->res2[1];
         reduce(rd);
-    };
-    int pcg_last = 8;
-    // PCG from zero: batches enqueued ahead of the host (as many iterations as the last solve needed + 2, then steps of 8), one read per batch
-    const BaPcg &a_jacobi = a;
-    auto pcg = [&](int &iters, double &relres) {
-        const BaPcg &a = tlmode ? atl : a_jacobi;
-        auto precond = [&](int it, int init) {   // the update of iteration it (or the start) with M^-1 = blocks [+ coarse]
-            hipLaunchKernelGGL((ba_tl_apply_block_kernel<CD>), dim3((unsigned)tl.nagg), b256, 0, st, a, tl, it, init);
-            hipLaunchKernelGGL((ba_tl_apply_coarse_kernel<CD>), dim3((unsigned)tl.ncoarse), b256, 0, st, a, tl, it, init);
-        };
+    }
+    const BaPcg &pcg_args() const { return tlmode ? atl : a; }
+    // the update of iteration it (or the start) with M^-1 = blocks [+ coarse]
+    void precond(int it, int init) {
+        hipLaunchKernelGGL((ba_tl_apply_block_kernel<CD>), dim3((unsigned)tl.nagg), b256, 0, st, atl, tl, it, init);
+        hipLaunchKernelGGL((ba_tl_apply_coarse_kernel<CD>), dim3((unsigned)tl.ncoarse), b256, 0, st, atl, tl, it, init);
+    }
+    // the PCG's start: x = 0, r = b, z = M^-1 b, p = z and the first partial sums
+    void pcg_start() {
         if (tlmode) precond(0, 1);
         else hipLaunchKernelGGL((ba_pcg_init_kernel<CD>), dim3(gfc), b256, 0, st, a);
+    }
+    // back-substitution dP = -V*^-1 (g + W^T dc), candidate (parameter set nx), its cost and the model decrease; the scalars to the state word
+    void candidate(int nx, const double *dc) {
+        hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)gl.p, -1.0,
+                           (const int32_t *)lused.p, dc, (const BaState *)nullptr, dP.p);
+        hipLaunchKernelGGL((ba_cand_cam_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p, dc,
+                           (const int32_t *)cused.p, R[nx].p, T[nx].p, pp + o_cand);
+        hipLaunchKernelGGL(ba_cand_lm_kernel, dim3(gfl), b256, 0, st, m, (const double *)P[cur].p, (const double *)dP.p, (const int32_t *)lused.p,
+                           P[nx].p, pp + o_cand + 2 * (size_t)gfc);
+        launch_cost<CD>(cfg.loss, cfg.loss_scale, ge, st, S, R[nx].p, T[nx].p, P[nx].p, Jc.p, dc, dP.p, pp + o_cost);
+        BaReduce rd{};
+        rd.sum_p[0] = pp + o_cost; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->cost_new;
+        rd.sum_p[1] = pp + o_cost + ge; rd.sum_n[1] = ge; rd.sum_out[1] = &dst->model;
+        rd.sum_p[2] = pp + o_cand; rd.sum_n[2] = gfc; rd.sum_out[2] = &dst->step2[0];
+        rd.sum_p[3] = pp + o_cand + gfc; rd.sum_n[3] = gfc; rd.sum_out[3] = &dst->x2[0];
+        rd.sum_p[4] = pp + o_cand + 2 * (size_t)gfc; rd.sum_n[4] = gfl; rd.sum_out[4] = &dst->step2[1];
+        rd.sum_p[5] = pp + o_cand + 2 * (size_t)gfc + gfl; rd.sum_n[5] = gfl; rd.sum_out[5] = &dst->x2[1];
+        reduce(rd);
+    }
+};
+
+template <int CD>
+void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out, hipStream_t st) {
+    const auto t_start = std::chrono::steady_clock::now();
+    BaWork<CD> W(SO, cfg, rot, t, p, st, cfg.dense_schur);
+    const std::vector<int32_t> &slot_of = SO.slot_of();
+    const int64_t n = W.n, m = W.m;
+    const bool nonmono = cfg.nonmonotonic;
+    std::vector<double> &hR = W.hR, &hT = W.hT, &hP = W.hP;
+    int &cur = W.cur, &best = W.best;
+    BaState *const dst = W.dst;
+    const int gfc = W.gfc;
+    const dim3 b256 = W.b256;
+    int pcg_last = 8;
+    // PCG from zero: batches enqueued ahead of the host (as many iterations as the last solve needed + 2, then steps of 8), one read per batch
+    auto pcg = [&](int &iters, double &relres) {
+        const BaPcg &a = W.pcg_args();
+        W.pcg_start();
         int it = 0, dir_applied = 0;
         auto enqueue = [&](int upto) {
             for (; it < upto; ++it) {
                 if (it != dir_applied) hipLaunchKernelGGL((ba_pcg_dir_kernel<CD>), dim3(gfc), b256, 0, st, a, it);
-                hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)nullptr, 1.0,
-                                   (const int32_t *)lused.p, (const double *)pv.p, (const BaState *)dst, y.p);
-                hipLaunchKernelGGL((ba_camx_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)y.p, a);
-                if (tlmode) precond(it, 0);
+                W.sx(a, dst);
+                if (W.tlmode) W.precond(it, 0);
                 else hipLaunchKernelGGL((ba_pcg_upd_kernel<CD>), dim3(gfc), b256, 0, st, a, it);
             }
             hipLaunchKernelGGL((ba_pcg_dir_kernel<CD>), dim3(gfc), b256, 0, st, a, it);   // convergence test of the last update (or the next direction)
@@ -1526,7 +1615,7 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         BaState s;
         for (;;) {
             enqueue(target);
-            s = read_state("the reduced camera PCG");
+            s = W.read_state("the reduced camera PCG");
             if (s.done || target >= kBaMaxPcgIters) break;
             target = std::min(kBaMaxPcgIters, target + 8);
         }
@@ -1544,12 +1633,12 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
     int ev_steps = 0;
     int64_t pcg_total = 0;
     bool fresh = true, first = true;   // fresh: the point changed and its cost / gradient have not been read yet
-    eval();
+    W.eval();
     for (;;) {
         const double mu = 1.0 / radius;
-        passes(mu);
+        W.passes(mu);
         if (fresh) {
-            const BaState s = read_state("the cost and gradient");
+            const BaState s = W.read_state("the cost and gradient");
             F = s.cost; gmax = s.gmax;
             if (first) {
                 if (!std::isfinite(F)) throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: the initial reprojection cost is not finite (a point on a camera's focal plane?)");
@@ -1564,31 +1653,16 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         if (secs_since(t_start) >= cfg.max_time) { status = XM_BA_TIME_LIMIT; break; }
         int pit = 0;
         double relres = 0.0;
-        if (cfg.dense_schur) dense_solve();
+        if (cfg.dense_schur) W.dense_solve();
         else {
-            if (tlmode) precond_setup();
+            if (W.tlmode) W.precond_setup();
             pcg(pit, relres);
         }
         pcg_total += pit;
-        // back-substitution dP = -V*^-1 (g + W^T dc), candidate, its cost and the model decrease
-        hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)gl.p, -1.0,
-                           (const int32_t *)lused.p, (const double *)x.p, (const BaState *)nullptr, dP.p);
         int nx = 0;   // the candidate's parameter set: neither the current one nor the least-cost one (without non-monotonic steps: cur ^ 1)
         while (nx == cur || nx == best) ++nx;
-        hipLaunchKernelGGL((ba_cand_cam_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p, (const double *)x.p,
-                           (const int32_t *)cused.p, R[nx].p, T[nx].p, pp + o_cand);
-        hipLaunchKernelGGL(ba_cand_lm_kernel, dim3(gfl), b256, 0, st, m, (const double *)P[cur].p, (const double *)dP.p, (const int32_t *)lused.p,
-                           P[nx].p, pp + o_cand + 2 * (size_t)gfc);
-        launch_cost<CD>(cfg.loss, cfg.loss_scale, ge, st, S, R[nx].p, T[nx].p, P[nx].p, Jc.p, x.p, dP.p, pp + o_cost);
-        BaReduce rd{};
-        rd.sum_p[0] = pp + o_cost; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->cost_new;
-        rd.sum_p[1] = pp + o_cost + ge; rd.sum_n[1] = ge; rd.sum_out[1] = &dst->model;
-        rd.sum_p[2] = pp + o_cand; rd.sum_n[2] = gfc; rd.sum_out[2] = &dst->step2[0];
-        rd.sum_p[3] = pp + o_cand + gfc; rd.sum_n[3] = gfc; rd.sum_out[3] = &dst->x2[0];
-        rd.sum_p[4] = pp + o_cand + 2 * (size_t)gfc; rd.sum_n[4] = gfl; rd.sum_out[4] = &dst->step2[1];
-        rd.sum_p[5] = pp + o_cand + 2 * (size_t)gfc + gfl; rd.sum_n[5] = gfl; rd.sum_out[5] = &dst->x2[1];
-        reduce(rd);
-        const BaState s = read_state("the candidate's cost");
+        W.candidate(nx, W.x.p);
+        const BaState s = W.read_state("the candidate's cost");
         iters++;
         const double step_norm = std::sqrt(s.step2[0] + s.step2[1]), x_norm = std::sqrt(s.x2[0] + s.x2[1]);
         const double Fn = s.cost_new, model_dec = -s.model;
@@ -1608,7 +1682,7 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
             radius = std::min(1e16, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3)));
             nu = 2.0;
             cur = nx;
-            basis_stale = true;
+            W.basis_stale = true;
             if (!nonmono) {
                 best = cur;
             } else {   // Ceres's StepAccepted
@@ -1624,7 +1698,7 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
             }
             const double Fold = F;
             F = Fn;
-            eval();
+            W.eval();
             fresh = true;
             if (std::fabs(Fold - Fn) <= cfg.function_tol * Fold) { status = XM_BA_CONVERGED_FUNCTION; break; }
         } else {
@@ -1635,21 +1709,21 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
     }
     if (best != cur) {   // non-monotonic steps: the caller gets the point of least cost, and its cost and gradient
         cur = best;
-        eval();
+        W.eval();
         fresh = true;
     }
     if (fresh) {   // the last accepted point: its gradient
-        passes(1.0 / radius);
-        const BaState s = read_state("the final gradient");
+        W.passes(1.0 / radius);
+        const BaState s = W.read_state("the final gradient");
         F = s.cost; gmax = s.gmax;
     }
     // ---- back to the caller's layouts; cameras / landmarks without a used observation are left as they came
     std::vector<int32_t> cu((size_t)n), lu((size_t)m);
-    XM_HIP_CHECK(hipMemcpyAsync(hR.data(), R[cur].p, hR.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    XM_HIP_CHECK(hipMemcpyAsync(hT.data(), T[cur].p, hT.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    XM_HIP_CHECK(hipMemcpyAsync(hP.data(), P[cur].p, hP.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    XM_HIP_CHECK(hipMemcpyAsync(cu.data(), cused.p, cu.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    XM_HIP_CHECK(hipMemcpyAsync(lu.data(), lused.p, lu.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    XM_HIP_CHECK(hipMemcpyAsync(hR.data(), W.R[cur].p, hR.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    XM_HIP_CHECK(hipMemcpyAsync(hT.data(), W.T[cur].p, hT.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    XM_HIP_CHECK(hipMemcpyAsync(hP.data(), W.P[cur].p, hP.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    XM_HIP_CHECK(hipMemcpyAsync(cu.data(), W.cused.p, cu.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    XM_HIP_CHECK(hipMemcpyAsync(lu.data(), W.lused.p, lu.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     wait_stream(st, cfg.watchdog_s, "the refined parameters");
     for (int64_t i = 0; i < n; ++i) {
         if (!cu[(size_t)i]) continue;
@@ -1666,9 +1740,115 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
     }
     out.status = status; out.iters = iters; out.accepted = accepted; out.pcg_iters = pcg_total;
     out.final_cost = F; out.gradient_max = gmax; out.trace_len = trace_n;
-    out.coarse_fallbacks = coarse_fallbacks;
+    out.coarse_fallbacks = W.coarse_fallbacks;
     out.seconds = secs_since(t_start);
-    (void)nobs;
+}
+
+// The test export xm_ctx_ba_probe: one eval + landmark pass + camera pass at (rot, t, p) with the damping mu, then whatever the caller
+// asked for, every array brought back in the caller's index order.  Only BaWork's members launch kernels here.
+template <int CD>
+void probe(const SchurOp &SO, const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q, hipStream_t st) {
+    constexpr int NC = ba_nc<CD>();
+    BaWork<CD> W(SO, cfg, rot, t, p, st, q.Sdense != nullptr);
+    const std::vector<int32_t> &slot_of = SO.slot_of();
+    const int64_t n = W.n, m = W.m, nd = W.nd;
+    auto d2h = [&](void *dstp, const void *src, size_t bytes) { XM_HIP_CHECK(hipMemcpyAsync(dstp, src, bytes, hipMemcpyDeviceToHost, st)); };
+    auto sync = [&](const char *what) { check_launch(what); wait_stream(st, cfg.watchdog_s, what); };
+    // per-landmark arrays: device slot order -> input order
+    std::vector<double> tmp;
+    auto lm_out = [&](const double *dev, int w, double *outp) {
+        if (!outp) return;
+        tmp.resize((size_t)w * m);
+        d2h(tmp.data(), dev, tmp.size() * sizeof(double));
+        sync("a landmark array");
+        for (int64_t l = 0; l < m; ++l)
+            for (int k = 0; k < w; ++k) outp[(size_t)w * l + k] = tmp[(size_t)w * slot_of[(size_t)l] + k];
+    };
+    W.eval();
+    W.passes(q.mu);
+    const BaState s0 = W.read_state("the probe's passes");
+    q.cost = s0.cost; q.n_used = (int64_t)s0.used; q.gmax = s0.gmax;
+    if (q.b) d2h(q.b, W.b.p, (size_t)nd * sizeof(double));
+    if (q.ustar) d2h(q.ustar, W.ustar.p, (size_t)CD * nd * sizeof(double));
+    if (q.sinv) d2h(q.sinv, W.sinv.p, (size_t)CD * nd * sizeof(double));
+    if (q.cused) d2h(q.cused, W.cused.p, (size_t)n * sizeof(int32_t));
+    sync("the camera arrays");
+    lm_out(W.gl.p, 3, q.g_l);
+    lm_out(W.vinv.p, 6, q.vinv);
+    if (q.lused) {
+        std::vector<int32_t> lu((size_t)m);
+        d2h(lu.data(), W.lused.p, (size_t)m * sizeof(int32_t));
+        sync("the landmark flags");
+        for (int64_t l = 0; l < m; ++l) q.lused[l] = lu[(size_t)slot_of[(size_t)l]];
+    }
+    // S X: column j into the PCG's direction vector, the product pair, A p back (the state word's done flag is 0: nothing has set it)
+    if (q.SX)
+        for (int64_t j = 0; j < q.k; ++j) {
+            XM_HIP_CHECK(hipMemcpyAsync(W.pv.p, q.X + (size_t)nd * j, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
+            W.sx(W.pcg_args(), W.dst);
+            d2h(q.SX + (size_t)nd * j, W.Ap.p, (size_t)nd * sizeof(double));
+            sync("the product S x");
+        }
+    if (q.Sdense) {
+        W.dense_assemble();
+        d2h(q.Sdense, W.Sd.p, (size_t)nd * nd * sizeof(double));
+        sync("the dense Schur matrix");
+    }
+    // the preconditioner's set-up as the loop runs it before the PCG, then M^-1 X through the PCG's start: b := X_j, z read back
+    DevBuf<double> ac;
+    if (W.tlmode) {
+        if (cfg.precond == 2 && q.Ac) { ac.alloc((size_t)W.nct * W.nct); W.ac_copy = ac.p; }
+        W.precond_setup();
+        q.nagg = W.tl.nagg; q.ncoarse = cfg.precond == 2 ? W.tl.ncoarse : 0; q.coarse_ok = W.tl.use_coarse;
+        if (cfg.precond == 2) {
+            if (q.Pm) d2h(q.Pm, W.tl_P.p, (size_t)nd * NC * sizeof(double));
+            if (q.dropped) d2h(q.dropped, W.tl_drop.p, (size_t)W.nct * sizeof(double));
+            if (q.Ac) d2h(q.Ac, ac.p, (size_t)W.nct * W.nct * sizeof(double));
+            sync("the coarse space");
+        }
+    }
+    if (q.MX && q.k > 0) {
+        DevBuf<double> keep;
+        keep.alloc((size_t)nd, false);
+        XM_HIP_CHECK(hipMemcpyAsync(keep.p, W.b.p, (size_t)nd * sizeof(double), hipMemcpyDeviceToDevice, st));
+        for (int64_t j = 0; j < q.k; ++j) {
+            XM_HIP_CHECK(hipMemcpyAsync(W.b.p, q.X + (size_t)nd * j, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
+            XM_HIP_CHECK(hipMemsetAsync(W.z.p, 0, (size_t)nd * sizeof(double), st));   // as the loop's first start finds it: cameras that are no members keep 0
+            W.pcg_start();
+            d2h(q.MX + (size_t)nd * j, W.z.p, (size_t)nd * sizeof(double));
+            sync("the preconditioner");
+        }
+        XM_HIP_CHECK(hipMemcpyAsync(W.b.p, keep.p, (size_t)nd * sizeof(double), hipMemcpyDeviceToDevice, st));
+        wait_stream(st, cfg.watchdog_s, "the right-hand side");
+    }
+    if (q.dc) {
+        XM_HIP_CHECK(hipMemcpyAsync(W.x.p, q.dc, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
+        W.candidate(1, W.x.p);
+        const BaState s = W.read_state("the probe's candidate");
+        q.cost1 = s.cost_new; q.model = s.model;
+        q.step2[0] = s.step2[0]; q.step2[1] = s.step2[1]; q.x2[0] = s.x2[0]; q.x2[1] = s.x2[1];
+        lm_out(W.dP.p, 3, q.dP);
+        lm_out(W.P[1].p, 3, q.p1);
+        if (q.rot1 || q.t1) {   // as the loop returns them: cameras without a used observation keep the caller's bits
+            std::vector<double> hR((size_t)9 * n), hT((size_t)3 * n);
+            std::vector<int32_t> cu((size_t)n);
+            d2h(hR.data(), W.R[1].p, hR.size() * sizeof(double));
+            d2h(hT.data(), W.T[1].p, hT.size() * sizeof(double));
+            d2h(cu.data(), W.cused.p, cu.size() * sizeof(int32_t));
+            sync("the candidate cameras");
+            if (q.rot1) std::memcpy(q.rot1, rot, (size_t)9 * n * sizeof(double));
+            if (q.t1) std::memcpy(q.t1, t, (size_t)3 * n * sizeof(double));
+            for (int64_t i = 0; i < n; ++i) {
+                if (!cu[(size_t)i]) continue;
+                const double *Rc = &hR[(size_t)9 * i], *tc = &hT[(size_t)3 * i];
+                for (int a = 0; a < 3; ++a) {
+                    if (q.rot1)
+                        for (int c = 0; c < 3; ++c) q.rot1[(size_t)a + 3 * ((size_t)3 * i + c)] = Rc[3 * c + a];   // R_i = Rcw^T
+                    if (q.t1) q.t1[(size_t)3 * i + a] = -(Rc[a] * tc[0] + Rc[3 + a] * tc[1] + Rc[6 + a] * tc[2]);   // t_i = -R_i tcw
+                }
+            }
+        }
+    }
 }
 
 }  // namespace
@@ -1740,6 +1920,11 @@ void bundle_adjust(const SchurOp &S, const BaSettings &cfg, double *rot, double 
     out = BaOutcome();
     if (cfg.fix_rotations) run<3>(S, cfg, rot, t, p, out, st);
     else run<6>(S, cfg, rot, t, p, out, st);
+}
+
+void ba_probe(const SchurOp &S, const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q, hipStream_t st) {
+    if (cfg.fix_rotations) probe<3>(S, cfg, rot, t, p, q, st);
+    else probe<6>(S, cfg, rot, t, p, q, st);
 }
 
 void reprojection_errors(const SchurOp &SO, const double *rot, const double *t, const double *p, double *sqerr, double watchdog_s, hipStream_t st) {

@@ -369,6 +369,50 @@ int xm_ctx_reprojection_errors(xm_ctx_t *ctx, const double *rot, const double *t
     return XM_OK;
     XM_CATCH
 }
+int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_ba_probe_t *pr) {
+    XM_TRY
+    if (!ctx || !rot || !t || !p || !pr) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: null argument");
+    if (pr->struct_size != sizeof(xm_ba_probe_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: xm_ba_probe_t.struct_size is not sizeof(xm_ba_probe_t)");
+    if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: single-GPU contexts only (not n_gpus > 1)");
+    if (ctx->impl->world() > 1) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: single-rank contexts only");
+    if (!(pr->mu > 0.0) || !std::isfinite(pr->mu)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: mu must be finite and > 0");
+    if (pr->flags & ~(XM_BA_FIX_ROTATIONS | XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: unknown flag");
+    if ((pr->flags & XM_BA_PRECOND_TWO_LEVEL) && (pr->flags & XM_BA_PRECOND_BLOCKS))
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: XM_BA_PRECOND_TWO_LEVEL and XM_BA_PRECOND_BLOCKS exclude each other");
+    if (pr->loss < XM_BA_LOSS_TRIVIAL || pr->loss > XM_BA_LOSS_ARCTAN) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: unknown loss");
+    if (pr->loss == XM_BA_LOSS_TRIVIAL && pr->loss_scale != 0.0) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: loss_scale is given but the loss is trivial");
+    if (pr->loss != XM_BA_LOSS_TRIVIAL && !(std::isfinite(pr->loss_scale) && pr->loss_scale > 0.0))
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: a robust loss needs a finite loss_scale > 0");
+    if (pr->k < 0 || (pr->k > 0 && !pr->X)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: k > 0 needs X");
+    const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks(), cd = (pr->flags & XM_BA_FIX_ROTATIONS) ? 3 : 6;
+    if (pr->Sdense && cd * n > XM_BA_PROBE_DENSE_MAX_ROWS) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: Sdense with more than XM_BA_PROBE_DENSE_MAX_ROWS rows");
+    for (int64_t k = 0; k < 9 * n; ++k)
+        if (!std::isfinite(rot[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: rotations are not finite");
+    for (int64_t k = 0; k < 3 * n; ++k)
+        if (!std::isfinite(t[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: translations are not finite");
+    for (int64_t k = 0; k < 3 * m; ++k)
+        if (!std::isfinite(p[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: landmarks are not finite");
+    for (int64_t k = 0; k < cd * n * pr->k; ++k)
+        if (!std::isfinite(pr->X[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: X is not finite");
+    if (pr->dc)
+        for (int64_t k = 0; k < cd * n; ++k)
+            if (!std::isfinite(pr->dc[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: dc is not finite");
+    xm::BaSettings c;
+    c.fix_rotations = (pr->flags & XM_BA_FIX_ROTATIONS) != 0;
+    c.loss = pr->loss; c.loss_scale = pr->loss_scale;
+    c.precond = (pr->flags & XM_BA_PRECOND_TWO_LEVEL) ? 2 : (pr->flags & XM_BA_PRECOND_BLOCKS) ? 1 : 0;
+    xm::BaProbe q;
+    q.mu = pr->mu; q.k = pr->k; q.X = pr->X; q.dc = pr->dc;
+    q.b = pr->b; q.g_l = pr->g_l; q.vinv = pr->vinv; q.ustar = pr->ustar; q.sinv = pr->sinv; q.cused = pr->cused; q.lused = pr->lused;
+    q.SX = pr->SX; q.Sdense = pr->Sdense; q.MX = pr->MX; q.Pm = pr->Pm; q.dropped = pr->dropped; q.Ac = pr->Ac;
+    q.dP = pr->dP; q.rot1 = pr->rot1; q.t1 = pr->t1; q.p1 = pr->p1;
+    ctx->impl->ba_probe(c, rot, t, p, q);
+    pr->cost = q.cost; pr->gmax = q.gmax; pr->cost1 = q.cost1; pr->model = q.model; pr->n_used = q.n_used;
+    pr->step2[0] = q.step2[0]; pr->step2[1] = q.step2[1]; pr->x2[0] = q.x2[0]; pr->x2[1] = q.x2[1];
+    pr->nagg = q.nagg; pr->ncoarse = q.ncoarse; pr->coarse_ok = q.coarse_ok;
+    return XM_OK;
+    XM_CATCH
+}
 int xm_ctx_set_edge_weights(xm_ctx_t *ctx, const double *w) {
     XM_TRY
     if (!ctx) throw xm::Error(XM_ERR_ARG, "null argument");

@@ -159,6 +159,7 @@ class SymwProduct;  // xm_symw.h
 class SchurOp;      // xm_schur.h
 struct BaSettings;  // xm_ba.h
 struct BaOutcome;
+struct BaProbe;
 
 struct PointState {  // everything the gradient epilogue writes for one point (R, s)
     DevBuf<double> G, egs, S0, rgR, rgs;
@@ -199,6 +200,7 @@ public:
     void recover_tp(const double *rot, const double *scale, double *t, double *p);   // matrix-free storage only
     // reprojection bundle adjustment of a recovered solution (xm_ba.h): matrix-free storage, one rank; reads the context, changes nothing in it
     void bundle_adjust(const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out);
+    void ba_probe(const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q);   // test export
     void reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr);   // per observation, input order (xm_ba.h)
     // XM^2 with the reference's residual definition (3_test_colmap_glomap.py:305-316): squared distance per edge / observation of the
     // RECOVERED solution (anchored rotations rot 3 x 3n column-major, scales) -- res: host, input order

@@ -1821,6 +1821,14 @@ void Context::bundle_adjust(const BaSettings &cfg, double *rot, double *t, doubl
     c.watchdog_s = cfg_.watchdog_s;
     xm::bundle_adjust(*schur_, c, rot, t, p, out, st_);
 }
+void Context::ba_probe(const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q) {
+    if (storage_ != XM_STORAGE_SCHUR || !schur_)
+        throw Error(XM_ERR_ARG, "xm_ctx_ba_probe: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_ba_probe: single-rank contexts only");
+    BaSettings c = cfg;
+    c.watchdog_s = cfg_.watchdog_s;
+    xm::ba_probe(*schur_, c, rot, t, p, q, st_);
+}
 void Context::reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr) {
     if (storage_ != XM_STORAGE_SCHUR || !schur_)
         throw Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");

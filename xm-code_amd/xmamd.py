@@ -35,7 +35,7 @@ EXPORTS = [
     "xm_ctx_attach_edges", "xm_ctx_edge_residuals", "xm_ctx_edge_residuals_recovered", "xm_ctx_xm2_filter", "xm_ctx_xm2_round", "xm_ctx_set_edge_weights", "xm_ctx_recover_tp", "xm_ctx_schur_info", "xm_ctx_qw", "xm_spd_inverse", "xm_ctx_transport", "xm_ctx_sell_wpad", "xm_ctx_product_kind", "xm_symw_plan", "xm_symw_use",
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
-    "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_ba_aggregate_plan",
+    "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_ba_aggregate_plan", "xm_ctx_ba_probe",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -100,6 +100,16 @@ class BaResult(C.Structure):
                 ("gradient_max", C.c_double), ("seconds", C.c_double), ("trace_len", C.c_int32), ("coarse_fallbacks", C.c_int32)]
 
 
+class BaProbe(C.Structure):   # xm_ba_probe_t, the test export xm_ctx_ba_probe
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("loss", C.c_int32), ("pad", C.c_int32), ("loss_scale", C.c_double),
+                ("mu", C.c_double), ("k", C.c_int64), ("X", C.c_void_p), ("dc", C.c_void_p), ("cost", C.c_double), ("gmax", C.c_double),
+                ("cost1", C.c_double), ("model", C.c_double), ("step2", C.c_double * 2), ("x2", C.c_double * 2), ("n_used", C.c_int64),
+                ("nagg", C.c_int32), ("ncoarse", C.c_int32), ("coarse_ok", C.c_int32), ("pad2", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("b", "g_l", "vinv", "ustar", "sinv", "cused", "lused", "SX", "Sdense", "MX", "Pm", "dropped", "Ac",
+                                          "dP", "rot1", "t1", "p1")]
+
+
+BA_PROBE_DENSE_MAX_ROWS = 4096
 BA_FIX_ROTATIONS = 1
 BA_NONMONOTONIC = 2
 BA_DENSE_SCHUR = 16            # Ceres's DENSE_SCHUR for the reduced camera system (include/xm_amd.h)
@@ -150,6 +160,7 @@ def lib():
         L.xm_ctx_xm2_round.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Options), C.POINTER(Xm2Info), C.POINTER(Result)]
         L.xm_ctx_recover_tp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_bundle_adjust.argtypes = [C.c_void_p, C.POINTER(BaOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaResult)]
+        L.xm_ctx_ba_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaProbe)]
         L.xm_ctx_reprojection_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_transport.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
         L.xm_ctx_schur_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_double)]
@@ -724,6 +735,55 @@ class Context:
         if tr is not None:
             info["trace"] = tr[: res.trace_len].copy()
         return rot, t, P, info
+
+    def ba_probe(self, rot, t, P, mu, fix_rotations=False, loss="trivial", loss_scale=0.0, preconditioner="jacobi", X=None, dc=None, dense=False):
+        """one linearisation of bundle_adjust at (rot, t, P) with the damping mu (the test export xm_ctx_ba_probe; include/xm_amd.h): a dict
+        of cost, n_used, gmax, b (n x CD), g_l (m x 3), vinv (m x 6), ustar, sinv (n x CD x CD), cused, lused; with X (CD n x k): SX and MX
+        (M^-1 X for the preconditioner); dense=True: Sdense (the lower block triangle); preconditioner "two_level": Pm (CD n x NC), dropped,
+        Ac (lower block triangle), coarse_ok, nagg, ncoarse; with dc (CD n): dP (m x 3), rot1, t1, p1, cost1, model, step2, x2.  Landmark
+        arrays by input index."""
+        rot = np.asfortranarray(np.asarray(rot, dtype=np.float64)); t = np.asfortranarray(np.asarray(t, dtype=np.float64))
+        P = np.asfortranarray(np.asarray(P, dtype=np.float64))
+        n, m = self.n, self.n_landmarks
+        assert rot.shape == (3, 3 * n) and t.shape == (3, n) and P.shape == (3, m)
+        if loss not in BA_LOSS:
+            raise XmError(f"unknown loss {loss!r} (one of {', '.join(BA_LOSS)})")
+        if preconditioner not in BA_PRECONDITIONERS:
+            raise XmError(f"unknown preconditioner {preconditioner!r} (one of {', '.join(BA_PRECONDITIONERS)})")
+        cd, nc = (3, 4) if fix_rotations else (6, 7)
+        nd = cd * n
+        q = BaProbe()
+        q.struct_size = C.sizeof(BaProbe)
+        q.flags = (BA_FIX_ROTATIONS if fix_rotations else 0) | BA_PRECONDITIONERS[preconditioner]
+        q.loss, q.loss_scale, q.mu = BA_LOSS[loss], float(loss_scale), float(mu)
+        out = dict(b=np.zeros((n, cd)), g_l=np.zeros((m, 3)), vinv=np.zeros((m, 6)), ustar=np.zeros((n, cd, cd)), sinv=np.zeros((n, cd, cd)),
+                   cused=np.zeros(n, dtype=np.int32), lused=np.zeros(m, dtype=np.int32))
+        if X is not None:
+            X = np.asfortranarray(np.asarray(X, dtype=np.float64).reshape(nd, -1))
+            q.k, q.X = X.shape[1], X.ctypes.data_as(C.c_void_p)
+            out["SX"] = np.zeros(X.shape, order="F"); out["MX"] = np.zeros(X.shape, order="F")
+        if dense:
+            if nd > BA_PROBE_DENSE_MAX_ROWS:
+                raise XmError("ba_probe: Sdense with more than BA_PROBE_DENSE_MAX_ROWS rows")
+            out["Sdense"] = np.zeros((nd, nd), order="F")
+        ncmax = nc * ((n + BA_AGG_CAMS - 1) // BA_AGG_CAMS)
+        if preconditioner == "two_level":
+            out["Pm"] = np.zeros((nd, nc)); out["dropped"] = np.zeros(ncmax); out["Ac"] = np.zeros(ncmax * ncmax)
+        if dc is not None:
+            dc = np.ascontiguousarray(np.asarray(dc, dtype=np.float64).reshape(nd))
+            q.dc = dc.ctypes.data_as(C.c_void_p)
+            out.update(dP=np.zeros((m, 3)), rot1=np.zeros((3, 3 * n), order="F"), t1=np.zeros((3, n), order="F"), p1=np.zeros((3, m), order="F"))
+        for k, v in out.items():
+            setattr(q, k, v.ctypes.data_as(C.c_void_p))
+        _chk(lib().xm_ctx_ba_probe(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p), C.byref(q)))
+        out.update(cost=q.cost, n_used=q.n_used, gmax=q.gmax, nagg=q.nagg, ncoarse=q.ncoarse, coarse_ok=q.coarse_ok)
+        if preconditioner == "two_level":
+            k = nc * q.ncoarse
+            out["dropped"] = out["dropped"][:k].copy()
+            out["Ac"] = out["Ac"][:k * k].reshape(k, k).T.copy()   # column-major with leading dimension NC ncoarse
+        if dc is not None:
+            out.update(cost1=q.cost1, model=q.model, step2=np.array(q.step2[:]), x2=np.array(q.x2[:]))
+        return out
 
     def reprojection_errors(self, rot, t, P):
         """|r_e|^2 (unrobustified) of every observation in input order at (rot, t, P) -- the layouts of bundle_adjust -- with the
