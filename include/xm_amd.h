@@ -290,7 +290,8 @@ int xm_ctx_set_edge_weights(xm_ctx_t *ctx, const double *w);
  *              contexts: |s_i R_i - M_e s_j R_j|_F^2.  Host array, input order.  Single-GPU contexts.
  *   xm2_filter: error = w .* res on the device, threshold = np.percentile(error, pct) (linear interpolation between two order
  *              statistics found by a device radix select, :321), weights of everything above it set to 0 and Q rebuilt (:323-338,
- *              without the reference's re-indexing of emptied landmarks / cameras: checklandmarks is upstream data cleaning).
+ *              without the reference's re-indexing of emptied landmarks / cameras: that is xm_ctx_clean_observations below, which
+ *              answers for the filtered list without an upload).
  *   xm2_round: filter at `percentile` (0 -> 90), then the reference's second pass (:339-351): solve_rank3 at lam = 0, statistics of its
  *              scales; |mean(s[1:]) - 1| > 2 std(s[1:]) or more than 10 scales < 0.1  ->  lam = kept edges / n, else lam = 0; final solve
  *              with opt->max_rank / tol / max_time / flags (XM_FLAG_WARM_R in opt->flags: start it from the rank-3 result instead of the
@@ -313,6 +314,55 @@ int xm_ctx_xm2_filter(xm_ctx_t *ctx, const double *rot, const double *scale, dou
                       double *w_out /* optional: the new weights */);
 int xm_ctx_xm2_round(xm_ctx_t *ctx, const double *R, const double *s, int r, const xm_options_t *opt, xm_xm2_info_t *info,
                      xm_result_t *res);
+/* ---- Cleaning an observation list: the reference's utils/checkconnection.py:checklandmarks (run before the first create_matrix and again
+ * between the XM^2 filter and the second solve, 5_test_ceres.py:482 / :578; 2_test_creatematrix.py:85-144 is the same sequence with the
+ * thresholds 0 and 1) as a query on the device.  A list whose graph is not connected cannot become an XM_STORAGE_SCHUR context ("not
+ * positive definite"); this call says which observations to drop and how the survivors are renumbered.
+ * Input: n cameras, m landmarks, nobs observations (cam[e], lm[e]), 0-based, in input order; a weight per observation.  An observation is
+ * LIVE when its weight is > 0 (w == NULL: all are live; the reference deletes filtered rows, so weight 0 means deleted there).  One pass,
+ * not a fixed point; every count counts observations, a (camera, landmark) pair named twice counts twice (np.bincount):
+ *   1. d1[c] = live observations of camera c.  Camera c survives when d1[c] > min_cam_obs.  first = the lowest c with the largest d1.
+ *   2. among the live observations of surviving cameras d2[l] = observations of landmark l; l survives when d2[l] > min_lm_obs.
+ *   3. a camera with no observation left is dropped (one that step 2 pushed to <= min_cam_obs but > 0 stays).
+ *   4. of the connected components of the bipartite graph of the remaining observations (nodes: the cameras and landmarks that still have
+ *      one) the one with the most nodes, cameras plus landmarks, stays; among several of that size the one that holds the earliest
+ *      remaining observation in input order (max(nx.connected_components(G), key=len) for the reference's insertion order).
+ * Output (host arrays): keep[nobs] (1 = the observation stays); lm_index[m] = rank of l among the kept landmarks in original order, -1 when
+ * dropped; cam_index[n] = the reference's indices_all: the stage-1 index is the rank among the stage-1 survivors in original order; then
+ * `first` takes index 0 and the camera that had index 0 takes first's index (not with XM_CLEAN_NO_SWAP: the reference calls the exchange
+ * optional); the final index is the number of kept cameras with a smaller stage-1 index, -1 when dropped.  Nothing survives: XM_OK, every
+ * index -1, keep all 0, zero counts.  min_cam_obs / min_lm_obs are literal (0 is a value, not "default"): checklandmarks is 10 and 1.
+ * On the device: degrees by integer atomics, components by hooking (atomicMin on the parent's label) and pointer jumping over int32 labels
+ * of the n + m vertices, a round being two launches and the host reading one word per few rounds; the labels' fixed point is unique, so
+ * every output is the same on every call -- only `rounds` depends on the order in which the atomics arrive.  More than 1024 rounds:
+ * XM_ERR_HIP.  n + m >= 2^31 or an index out of range: XM_ERR_ARG.
+ * xm_clean_observations needs no context (creating one on a disconnected list fails): host arrays, uploaded inside the call.
+ * xm_ctx_clean_observations: the list and the CURRENT weights of an XM_STORAGE_SCHUR context, so after xm_ctx_xm2_filter /
+ * xm_ctx_set_edge_weights it answers for the filtered list with no upload of observations; nothing in the context changes (a solve after
+ * it gives the bits of one without it).  XM_ERR_ARG (context unchanged and usable): another storage, several ranks or a communicator, a
+ * struct_size that is not sizeof, negative thresholds, unknown flags, null outputs. */
+#define XM_CLEAN_NO_SWAP 1u
+typedef struct {
+    uint32_t struct_size;
+    int32_t min_cam_obs, min_lm_obs;
+    uint32_t flags;            /* XM_CLEAN_NO_SWAP */
+} xm_clean_options_t;
+typedef struct {
+    uint32_t struct_size;
+    int32_t rounds;            /* hooking rounds until no label changed (the round that found nothing to change included) */
+    int64_t nobs_live, n_new, m_new, nobs_new;
+    int64_t components;        /* of the graph after stage 3 */
+    int64_t cams_weak;         /* cameras that fail stage 1 (unobserved ones included) */
+    int64_t lms_weak;          /* landmarks that fail stage 2 (unobserved ones included) */
+    int64_t cams_emptied;      /* stage-1 survivors that stage 2 left without an observation */
+    int64_t cams_off_component, lms_off_component;   /* nodes of the stage-3 graph outside the component that stays */
+    int32_t first_camera;      /* `first` of stage 1 (-1: n = 0) */
+    int32_t reserved;
+} xm_clean_result_t;
+int xm_clean_observations(int64_t n, int64_t m, int64_t nobs, const int32_t *cam, const int32_t *lm, const double *w /* NULL: all live */,
+                          const xm_clean_options_t *opt, uint8_t *keep, int32_t *cam_index, int32_t *lm_index, xm_clean_result_t *res);
+int xm_ctx_clean_observations(xm_ctx_t *ctx, const xm_clean_options_t *opt, uint8_t *keep, int32_t *cam_index, int32_t *lm_index,
+                              xm_clean_result_t *res);
 /* Translations and landmarks of a solution: the last step of utils/recoversolution.py:recover_XM (lines 77-86,
  * ybar_est = Abar @ sR_real.T; t_est = [0 | first N-1 columns], p_est = the rest) for an XM_STORAGE_SCHUR context.  The reference
  * needs the dense (N-1+M) x 3N matrix Abar.bin that create_matrix writes (creatematrix.py:283-311; 80 GB at Final-13682 with 800 k

@@ -2,12 +2,14 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <mutex>
 #include <vector>
 
 #include "xm_ba.h"
+#include "xm_clean.h"
 #include "xm_schur.h"
 #include "xm_sell.h"
 #include "xm_symw.h"
@@ -410,6 +412,56 @@ int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const dou
     pr->cost = q.cost; pr->gmax = q.gmax; pr->cost1 = q.cost1; pr->model = q.model; pr->n_used = q.n_used;
     pr->step2[0] = q.step2[0]; pr->step2[1] = q.step2[1]; pr->x2[0] = q.x2[0]; pr->x2[1] = q.x2[1];
     pr->nagg = q.nagg; pr->ncoarse = q.ncoarse; pr->coarse_ok = q.coarse_ok;
+    return XM_OK;
+    XM_CATCH
+}
+namespace {
+void clean_settings(const char *who, const xm_clean_options_t *opt, const uint8_t *keep, const int32_t *cam_index, const int32_t *lm_index,
+                    const xm_clean_result_t *res, xm::CleanSettings &c) {
+    const std::string w(who);
+    if (!opt || !keep || !cam_index || !lm_index || !res) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (opt->struct_size != sizeof(xm_clean_options_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_clean_options_t.struct_size is not sizeof(xm_clean_options_t)");
+    if (res->struct_size != sizeof(xm_clean_result_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_clean_result_t.struct_size is not sizeof(xm_clean_result_t)");
+    if (opt->min_cam_obs < 0 || opt->min_lm_obs < 0) throw xm::Error(XM_ERR_ARG, w + ": negative threshold");
+    if (opt->flags & ~XM_CLEAN_NO_SWAP) throw xm::Error(XM_ERR_ARG, w + ": unknown flag");
+    c.min_cam_obs = opt->min_cam_obs; c.min_lm_obs = opt->min_lm_obs; c.swap_first = !(opt->flags & XM_CLEAN_NO_SWAP);
+}
+void give_clean(xm_clean_result_t *res, const xm::CleanOutcome &r) {
+    xm_clean_result_t out;
+    std::memset(&out, 0, sizeof(out));
+    out.struct_size = sizeof(xm_clean_result_t);
+    out.rounds = r.rounds; out.nobs_live = r.nobs_live; out.n_new = r.n_new; out.m_new = r.m_new; out.nobs_new = r.nobs_new;
+    out.components = r.components; out.cams_weak = r.cams_weak; out.lms_weak = r.lms_weak; out.cams_emptied = r.cams_emptied;
+    out.cams_off_component = r.cams_off_component; out.lms_off_component = r.lms_off_component; out.first_camera = r.first_camera;
+    *res = out;
+}
+}  // namespace
+int xm_clean_observations(int64_t n, int64_t m, int64_t nobs, const int32_t *cam, const int32_t *lm, const double *w, const xm_clean_options_t *opt,
+                          uint8_t *keep, int32_t *cam_index, int32_t *lm_index, xm_clean_result_t *res) {
+    XM_TRY
+    xm::CleanSettings c;
+    clean_settings("xm_clean_observations", opt, keep, cam_index, lm_index, res, c);
+    if (n < 0 || m < 0 || nobs < 0) throw xm::Error(XM_ERR_ARG, "xm_clean_observations: negative size");
+    if (n + m >= ((int64_t)1 << 31)) throw xm::Error(XM_ERR_ARG, "xm_clean_observations: cameras + landmarks must stay below 2^31");
+    if (nobs > 0 && (!cam || !lm)) throw xm::Error(XM_ERR_ARG, "xm_clean_observations: null observation arrays");
+    require_device();
+    if (const char *e = std::getenv("XM_WATCHDOG_S")) { const double v = std::atof(e); if (v > 0) c.watchdog_s = v; }
+    xm::CleanOutcome r;
+    xm::clean_observations_host(n, m, nobs, cam, lm, w, c, keep, cam_index, lm_index, r);
+    give_clean(res, r);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_ctx_clean_observations(xm_ctx_t *ctx, const xm_clean_options_t *opt, uint8_t *keep, int32_t *cam_index, int32_t *lm_index, xm_clean_result_t *res) {
+    XM_TRY
+    if (!ctx) throw xm::Error(XM_ERR_ARG, "xm_ctx_clean_observations: null argument");
+    xm::CleanSettings c;
+    clean_settings("xm_ctx_clean_observations", opt, keep, cam_index, lm_index, res, c);
+    if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_clean_observations: single-GPU contexts only (not n_gpus > 1)");
+    if (ctx->impl->world() > 1) throw xm::Error(XM_ERR_ARG, "xm_ctx_clean_observations: single-rank contexts only");
+    xm::CleanOutcome r;
+    ctx->impl->clean_observations(c, keep, cam_index, lm_index, r);
+    give_clean(res, r);
     return XM_OK;
     XM_CATCH
 }

@@ -160,6 +160,8 @@ class SchurOp;      // xm_schur.h
 struct BaSettings;  // xm_ba.h
 struct BaOutcome;
 struct BaProbe;
+struct CleanSettings;  // xm_clean.h
+struct CleanOutcome;
 
 struct PointState {  // everything the gradient epilogue writes for one point (R, s)
     DevBuf<double> G, egs, S0, rgR, rgs;
@@ -202,6 +204,8 @@ public:
     void bundle_adjust(const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out);
     void ba_probe(const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q);   // test export
     void reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr);   // per observation, input order (xm_ba.h)
+    // which observations, cameras and landmarks of the list survive cleaning at the current weights (xm_clean.h); changes nothing here
+    void clean_observations(const CleanSettings &cfg, uint8_t *keep, int32_t *cam_index, int32_t *lm_index, CleanOutcome &out);
     // XM^2 with the reference's residual definition (3_test_colmap_glomap.py:305-316): squared distance per edge / observation of the
     // RECOVERED solution (anchored rotations rot 3 x 3n column-major, scales) -- res: host, input order
     void edge_residuals_recovered(const double *rot, const double *scale, double *res);

@@ -14,6 +14,7 @@
 #include "xm_symw.h"
 #include "xm_schur.h"
 #include "xm_ba.h"
+#include "xm_clean.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1834,6 +1835,14 @@ void Context::reprojection_errors(const double *rot, const double *t, const doub
         throw Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
     if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: single-rank contexts only");
     xm::reprojection_errors(*schur_, rot, t, p, sqerr, cfg_.watchdog_s, st_);
+}
+void Context::clean_observations(const CleanSettings &cfg, uint8_t *keep, int32_t *cam_index, int32_t *lm_index, CleanOutcome &out) {
+    if (storage_ != XM_STORAGE_SCHUR || !schur_)
+        throw Error(XM_ERR_ARG, "xm_ctx_clean_observations: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no observations");
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_clean_observations: single-rank contexts only");
+    CleanSettings c = cfg;
+    c.watchdog_s = cfg_.watchdog_s;
+    xm::clean_observations(*schur_, c, keep, cam_index, lm_index, out, st_);
 }
 int64_t Context::n_landmarks() const { return schur_ ? schur_->n_landmarks() : 0; }
 bool Context::schur_info(int64_t out[3], double *relres) const {

@@ -36,6 +36,7 @@ EXPORTS = [
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
     "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_ba_aggregate_plan", "xm_ctx_ba_probe",
+    "xm_clean_observations", "xm_ctx_clean_observations",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -109,6 +110,17 @@ class BaProbe(C.Structure):   # xm_ba_probe_t, the test export xm_ctx_ba_probe
                                           "dP", "rot1", "t1", "p1")]
 
 
+class CleanOptions(C.Structure):   # xm_clean_options_t
+    _fields_ = [("struct_size", C.c_uint32), ("min_cam_obs", C.c_int32), ("min_lm_obs", C.c_int32), ("flags", C.c_uint32)]
+
+
+class CleanResult(C.Structure):    # xm_clean_result_t
+    _fields_ = [("struct_size", C.c_uint32), ("rounds", C.c_int32)] + \
+               [(k, C.c_int64) for k in ("nobs_live", "n_new", "m_new", "nobs_new", "components", "cams_weak", "lms_weak", "cams_emptied",
+                                         "cams_off_component", "lms_off_component")] + [("first_camera", C.c_int32), ("reserved", C.c_int32)]
+
+
+CLEAN_NO_SWAP = 1
 BA_PROBE_DENSE_MAX_ROWS = 4096
 BA_FIX_ROTATIONS = 1
 BA_NONMONOTONIC = 2
@@ -161,6 +173,9 @@ def lib():
         L.xm_ctx_recover_tp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_bundle_adjust.argtypes = [C.c_void_p, C.POINTER(BaOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaResult)]
         L.xm_ctx_ba_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaProbe)]
+        L.xm_clean_observations.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CleanOptions), C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.POINTER(CleanResult)]
+        L.xm_ctx_clean_observations.argtypes = [C.c_void_p, C.POINTER(CleanOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CleanResult)]
         L.xm_ctx_reprojection_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_transport.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
         L.xm_ctx_schur_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_double)]
@@ -491,6 +506,64 @@ def ba_aggregate_plan(cam, lm, n=None, used=None, B=BA_AGG_CAMS):
     return out
 
 
+class CleanPlan:
+    """what clean_observations / Context.clean_observations found: keep (bool per observation), cam_index (n) and lm_index (m) -- the new
+    number of every camera (the reference's indices_all) and landmark, -1 when dropped -- and info, the fields of xm_clean_result_t"""
+
+    def __init__(self, keep, cam_index, lm_index, info):
+        self.keep, self.cam_index, self.lm_index, self.info = keep, cam_index, lm_index, info
+
+    def apply(self, cam, lm, *per_observation):
+        """the compacted, re-indexed list on the host: (cam, lm, *arrays) of the kept observations in input order -- the reference's
+        edges - 1, landmarks, weights, rgbs, ready for Context(obs=...)"""
+        cam = np.asarray(cam); lm = np.asarray(lm)
+        if cam.shape != self.keep.shape or lm.shape != self.keep.shape:
+            raise XmError("CleanPlan.apply: cam and lm must have one entry per observation of the cleaned list")
+        k = self.keep
+        out = [self.cam_index[cam[k]], self.lm_index[lm[k]]]
+        for a in per_observation:
+            a = np.asarray(a)
+            if a.shape[:1] != k.shape:
+                raise XmError("CleanPlan.apply: a per-observation array has another length than the cleaned list")
+            out.append(a[k])
+        return tuple(out)
+
+
+def _clean_options(min_cam_obs, min_lm_obs, swap_first):
+    if int(min_cam_obs) < 0 or int(min_lm_obs) < 0:
+        raise XmError("clean_observations: negative threshold")
+    opt = CleanOptions(); res = CleanResult()
+    opt.struct_size, res.struct_size = C.sizeof(CleanOptions), C.sizeof(CleanResult)
+    opt.min_cam_obs, opt.min_lm_obs, opt.flags = int(min_cam_obs), int(min_lm_obs), 0 if swap_first else CLEAN_NO_SWAP
+    return opt, res
+
+
+def _clean_plan(keep, ci, li, res):
+    return CleanPlan(keep.astype(bool), ci, li, {k: getattr(res, k) for k, _ in CleanResult._fields_ if k not in ("struct_size", "reserved")})
+
+
+def clean_observations(cam, lm, w=None, n=None, m=None, min_cam_obs=10, min_lm_obs=1, swap_first=True):
+    """the reference's checklandmarks on the device for a host list (xm_clean_observations; include/xm_amd.h has the definition): cam, lm
+    0-based per observation, w: weights (an observation with w <= 0 counts as deleted; None: all live), n / m: cameras / landmarks (None:
+    largest index + 1).  Thresholds are literal: (10, 1) is checklandmarks, (0, 1) the sequence of 2_test_creatematrix.py.  -> CleanPlan"""
+    cam = np.ascontiguousarray(cam, dtype=np.int32).reshape(-1); lm = np.ascontiguousarray(lm, dtype=np.int32).reshape(-1)
+    if cam.size != lm.size:
+        raise XmError("clean_observations: cam and lm must have one entry per observation")
+    if w is not None:
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if w.size != cam.size:
+            raise XmError("clean_observations: w must have one entry per observation")
+    n = (int(cam.max()) + 1 if cam.size else 0) if n is None else int(n)
+    m = (int(lm.max()) + 1 if lm.size else 0) if m is None else int(m)
+    opt, res = _clean_options(min_cam_obs, min_lm_obs, swap_first)
+    require_gpu()
+    keep = np.zeros(cam.size, dtype=np.uint8); ci = np.full(max(n, 0), -1, dtype=np.int32); li = np.full(max(m, 0), -1, dtype=np.int32)
+    _chk(lib().xm_clean_observations(n, m, cam.size, cam.ctypes.data_as(C.c_void_p), lm.ctypes.data_as(C.c_void_p),
+                                     None if w is None else w.ctypes.data_as(C.c_void_p), C.byref(opt), keep.ctypes.data_as(C.c_void_p),
+                                     ci.ctypes.data_as(C.c_void_p), li.ctypes.data_as(C.c_void_p), C.byref(res)))
+    return _clean_plan(keep, ci, li, res)
+
+
 def symw_plan(ntot, nloc, cam0, K=0):
     """work list of one rank of the multi-rank symmetric window product (xm_symw.h) -- host only"""
     geom = np.zeros(8, dtype=np.int32)
@@ -795,6 +868,18 @@ class Context:
         _chk(lib().xm_ctx_reprojection_errors(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p),
                                               out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def clean_observations(self, min_cam_obs=10, min_lm_obs=1, swap_first=True):
+        """the reference's checklandmarks for this context's list at its CURRENT weights (after xm2_filter / set_edge_weights: the filtered
+        list; xm_ctx_clean_observations), matrix-free contexts only; nothing in the context changes.  -> CleanPlan; plan.apply(cam, lm, p, w)
+        gives the arguments of the next Context(obs=...)"""
+        opt, res = _clean_options(min_cam_obs, min_lm_obs, swap_first)
+        # (a context of another storage has no observations: sized for nothing, the library refuses it)
+        keep = np.zeros(getattr(self, "ne", 0), dtype=np.uint8); ci = np.full(self.n, -1, dtype=np.int32)
+        li = np.full(getattr(self, "n_landmarks", 0), -1, dtype=np.int32)
+        _chk(lib().xm_ctx_clean_observations(self.h, C.byref(opt), keep.ctypes.data_as(C.c_void_p), ci.ctypes.data_as(C.c_void_p),
+                                             li.ctypes.data_as(C.c_void_p), C.byref(res)))
+        return _clean_plan(keep, ci, li, res)
 
     def edge_residuals_recovered(self, rot, scale):
         """squared distance per edge / observation of a RECOVERED solution (rot 3 x 3n, scale n): the reference's XM^2 residual"""
