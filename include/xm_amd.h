@@ -579,6 +579,54 @@ typedef struct {
     double *dP, *rot1, *t1, *p1;
 } xm_ba_probe_t;
 int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_ba_probe_t *probe);
+/* The trust region's kernels stage by stage, a test export (tests/test_gpu_rtr_stages.py): at the point (R: 3n x o column-major, s: n; s[0] is
+ * forced to 1 as in a solve) and with lam, the stages below run through the context's own setup for rank o, its product dispatch and the
+ * launchers, grids and arguments of a solve -- the kernels are those the storage and xm_tuning_t select (product_kind: XM_PRODUCT_*; split_k: slices of
+ * the column-split dense product in effect at this rank, 1 = not split; sell_gather: gather mode of the sliced-ELL kernels, 0 a record per lane | 1 LDS-transposed, -1 without that layout).  Every
+ * array whose pointer is not null is filled; matrices are 3n x o column-major, vectors n.  Single-rank contexts only (XM_ERR_ARG otherwise, and
+ * for o outside 3..10 (a point needs three orthonormal rows), non-finite input, a wrong struct_size, XM_RTR_PROBE_AUTO where the device-driven outer iteration does not apply).
+ *   grad (always)      scale_rows, the EPI_GRAD product, outer_finalize -> f, rr = <rg,rg>, G = 2 Q sR, egs, S0 (9 n, row-major blocks), rgR, rgs
+ *   hess (pR, ps given; rR, rs optional = 0)   W = s.*pR + ps.*R (anchor's ps taken as 0, written by the tCG's own start kernel), the EPI_HESS
+ *                      product -> HpR, Hps and pHp = <p,Hp>, rHp = <r,Hp>, HpHp = <Hp,Hp>: the per-workgroup partial sums (nA each) added by
+ *                      the summation tree cg_step_kernel uses.  hess_f32 contexts: the fp32 launch
+ *   XM_RTR_PROBE_AUTO  both stages through the role-switching EPI_AUTO instantiation (TcgScal.phase = PH_CAND / PH_TCG)
+ *   XM_RTR_PROBE_TCG_INIT  tcg_init_kernel from the grad stage's rg and rr with scal_in.delta -> init_* (init_W / init_Wpad: the product input
+ *                      at its native pitch / at the 16-double record pitch (16 n); w_native / wpad say which of the two this context's tCG keeps)
+ *   XM_RTR_PROBE_CG_STEP (needs hess)  one cg_step_kernel launch from scal_in (rr, vv, vp, pp, delta, gradnorm, model, iter; status 0), p, r,
+ *                      v = (vR, vs), Hv = (HvR, Hvs; none with XM_RTR_PROBE_MODEL_REC = XM_FLAG_MODEL_RECURRENCE), Hp and the three sums as
+ *                      the hess stage left them on the device, and for scal_in.iter > 0 partsB_in (partsB_in_count == nB partial sums of
+ *                      |r|^2, as partsB_out of the launch before) -> scal_out, out_* (arrays a branch does not write come back with their
+ *                      input bits), partsB_out (up to 1024 doubles, nB used) and rr_parts, their sum by the same tree
+ *   XM_RTR_PROBE_CERT  cert_prepare_kernel at the point -> Lam (9 n), dz (n), dual[2] = the two sums (y0 + y3 + y5 of the anchor; lam sum(1 - xii^2));
+ *                      with X (3n x k column-major): SX = S X, column by column through the EPI_CERT product
+ * Solver state: the next solve on the context gives the bits it would have given without the call (the workspace is re-created by every
+ * solve); the resident end point of an earlier solve is gone (as after xm_ctx_qw).  Allocates only the grow-only workspace of a solve at rank o. */
+#define XM_RTR_PROBE_AUTO      1u
+#define XM_RTR_PROBE_MODEL_REC 2u
+#define XM_RTR_PROBE_TCG_INIT  4u
+#define XM_RTR_PROBE_CG_STEP   8u
+#define XM_RTR_PROBE_CERT      16u
+typedef struct {
+    double rr, vv, vp, pp, delta, gradnorm, last_step, model;
+    int32_t status, iter;
+} xm_rtr_scal_t;
+typedef struct {
+    uint32_t struct_size;
+    uint32_t flags;
+    int32_t o, k;
+    double lam;
+    const double *R, *s, *pR, *ps, *rR, *rs, *vR, *vs, *HvR, *Hvs, *partsB_in, *X;
+    int32_t partsB_in_count, pad;
+    xm_rtr_scal_t scal_in;
+    int32_t product_kind, nA, nB, w_native, wpad, split_k, sell_gather, pad2;
+    double f, rr, pHp, rHp, HpHp, rr_parts, dual[2];
+    xm_rtr_scal_t init_scal, scal_out;
+    double *G, *egs, *S0, *rgR, *rgs, *HpR, *Hps;
+    double *init_rR, *init_rs, *init_pR, *init_ps, *init_vR, *init_vs, *init_HvR, *init_Hvs, *init_W, *init_Wpad;
+    double *out_vR, *out_vs, *out_HvR, *out_Hvs, *out_rR, *out_rs, *out_pR, *out_ps, *out_W, *out_Wpad, *partsB_out;
+    double *Lam, *dz, *SX;
+} xm_rtr_probe_t;
+int xm_ctx_rtr_probe(xm_ctx_t *ctx, xm_rtr_probe_t *probe);
 /* Large block-sparse Q: "sliced ELL over per-XCD column slabs" (xm-code_amd/csrc/xm_sell.h).  Same product as xm_qw_bsr3
  * (the reference has no sparse product: Dense/matmul.h:42-87 on a dense Q); the matrix is described on the HOST as 3x3-block CSR
  * (rows n, global columns in [0, ncols)) and re-laid on the device.  slabs in {1,2,4,8}; lmax = longest virtual row (hub

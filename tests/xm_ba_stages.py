@@ -20,12 +20,15 @@ KINDS = ("jacobi", "blocks", "two_level")
 MAX_E_REF = 1e-8          # a scene whose reference is worse than this for a compared quantity is not a scene to judge a kernel on
 
 
-def err(x, xe):
-    """(error, index of the worst block); x, xe: (blocks, ...)"""
+def err(x, xe, scale=None):
+    """(error, index of the worst block); x, xe: (blocks, ...); scale (per block, optional): a lower limit of the denominator -- the magnitude
+    of the terms the block is formed from, where the exact block itself may cancel to nothing (xm_rtr_exact.py)"""
     xe = np.asarray(xe, dtype=LD)
     xe = xe.reshape(xe.shape[0] if xe.ndim else 1, -1)
     x = np.asarray(x, dtype=LD).reshape(xe.shape)
     num, den = np.abs(x - xe).max(axis=1), np.abs(xe).max(axis=1)
+    if scale is not None:
+        den = np.maximum(den, np.asarray(scale, dtype=LD).reshape(-1))
     e = np.where(den > 0, num / np.where(den > 0, den, 1), np.where(num > 0, np.inf, 0))
     return float(e.max()), int(e.argmax())
 

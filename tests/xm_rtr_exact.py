@@ -1,0 +1,376 @@
+"""The quantities of the Riemannian trust region on St(3,o)^n x R+^(n-1), stage by stage, restated in plain numpy from the reference's
+trustregion.h and checkeig.h (line numbers in the comments).  Every function is written once over a dtype: dt = np.longdouble gives the
+reference the GPU stage tests compare with (tests/test_gpu_rtr_stages.py), dt = np.float64 the restatement whose own error against it sets
+their bound (xm_rtr_stages.py).  Imports nothing from the library or the oracle.
+
+Layout: R is 3n x o (camera i = rows 3i..3i+2, orthonormal rows), s is n with s[0] = 1 (the anchor, trustregion.h:125-127); a tangent
+vector is (pR, ps) with sym(R_i pR_i^T) = 0 and ps[0] = 0; the metric is <u, v> = sum(uR vR) + sum(us vs / s^2) (ProductManifoldInner with
+the scale parts divided by s, trustregion.h:565-566, 625-626).
+
+Next to every array the functions return, under the key "<name>~", the magnitude of the terms its blocks are formed from (per camera, or
+a scalar): the products' terms are bounded through |Q| |W|, and what is built from them inherits that.  An error is judged against the larger of
+the exact block's maximum and this magnitude -- at a critical point, where the exact gradient is 0, the first alone would compare one round-off
+with another.
+
+damage= (f64 runs of tests/test_rtr_exact.py only) plants one deliberate fault; the names are those of FAULTS."""
+import numpy as np
+
+LD = np.longdouble
+FAULTS = ("no_S0", "no_ps_s_egs", "anchor_egs", "anchor_rhs", "anchor_ps", "nosym", "lam_s2", "rr_est_no_cross", "tau_root", "vp_no_beta", "lam5",
+          "dz_row")
+MAX_INNER = 1000   # trustregion.h:416
+
+
+class Op:
+    """W -> Q W for a dense matrix, in any dtype; absolute() is the same for |Q| (the magnitude of the product's terms)"""
+
+    def __init__(self, Q):
+        self.Q = np.asarray(Q)
+        self._cache = {}
+
+    def _as(self, dt, absolute=False):
+        key = (np.dtype(dt).name, absolute)
+        if key not in self._cache:
+            M = self.Q.astype(dt)
+            self._cache[key] = np.abs(M) if absolute else M
+        return self._cache[key]
+
+    def __call__(self, W, dt):
+        return self._as(dt) @ W.astype(dt)
+
+    def absolute(self, W, dt):
+        return self._as(dt, True) @ np.abs(W).astype(dt)
+
+
+class BlockOp:
+    """the same for a 3x3-block CSR matrix (rows too many to densify)"""
+
+    def __init__(self, rowptr, colidx, blocks):
+        self.rows = np.repeat(np.arange(len(rowptr) - 1), np.diff(rowptr))
+        self.cols = np.asarray(colidx, dtype=np.int64)
+        self.blocks = np.asarray(blocks).reshape(-1, 3, 3)
+        self.n = len(rowptr) - 1
+
+    def _apply(self, B, W, dt):
+        Wb = W.astype(dt).reshape(self.n, 3, -1)
+        out = np.zeros(Wb.shape, dtype=dt)
+        np.add.at(out, self.rows, np.einsum("bac,bck->bak", B.astype(dt), Wb[self.cols]))
+        return out.reshape(W.shape)
+
+    def __call__(self, W, dt):
+        return self._apply(self.blocks, W, dt)
+
+    def absolute(self, W, dt):
+        return self._apply(np.abs(self.blocks), np.abs(W), dt)
+
+
+def blk(A, n):
+    return A.reshape(n, 3, -1)
+
+
+def sym3(M):
+    return (M + np.swapaxes(M, 1, 2)) / 2
+
+
+def inner(uR, us, vR, vs, s):
+    """the product metric: trustregion.h:565-566 (ProductManifoldInner with one scale part over s^2)"""
+    return (uR * vR).sum() + (us * vs / (s * s)).sum()
+
+
+def tangent(R, Z, zs):
+    """projection of (Z, zs) onto the tangent space at R (trustregion.h:307-317 without the metric factor of the scale part), anchor masked"""
+    n = R.shape[0] // 3
+    Rb, Zb = blk(R, n), blk(Z, n)
+    P = Zb - np.einsum("iab,ibk->iak", sym3(np.einsum("iak,ibk->iab", Rb, Zb)), Rb)
+    ps = np.array(zs, dtype=Z.dtype)
+    ps[0] = 0
+    return P.reshape(R.shape), ps
+
+
+def point(R, s, dt):
+    R = np.asarray(R).astype(dt)
+    s = np.asarray(s).astype(dt).copy()
+    s[0] = 1                                               # trustregion.h:125-127
+    return R, s
+
+
+def cost(op, R, s, lam, dt=LD):
+    """objc, trustregion.h:162-170: <sR, Q sR> + lam sum_{i>=1} (s_i^2 - 1)^2"""
+    R, s = point(R, s, dt)
+    sR = R * np.repeat(s, 3)[:, None]
+    q = s[1:] * s[1:] - 1
+    return (sR * op(sR, dt)).sum() + dt(lam) * (q * q).sum()
+
+
+def grad_stage(op, R, s, lam, dt=LD, damage=None):
+    """objc :162-170, grad :186-194, projection :307-317; rr = <rg, rg> (:483-484)"""
+    R, s = point(R, s, dt)
+    n, lam = s.size, dt(lam)
+    s3 = np.repeat(s, 3)[:, None]
+    sR = R * s3
+    G = 2 * op(sR, dt)                                     # dfdsR, :187
+    aG = 2 * op.absolute(sR, dt)
+    q = s * s - 1
+    anchor = np.arange(n) == 0
+    f = (G * sR).sum() / 2 + lam * (q[1:] * q[1:]).sum()
+    af = (aG * np.abs(sR)).sum() / 2 + lam * (q[1:] * q[1:]).sum()
+    Rb, Gb, aGb = blk(R, n), blk(G, n), blk(aG, n)
+    lamterm = 4 * lam * q * s                              # GradLambdaKernal + :191-192
+    egs = (Gb * Rb).sum(axis=(1, 2)) + lamterm             # :189
+    aegs = (aGb * np.abs(Rb)).sum(axis=(1, 2)) + np.abs(lamterm)
+    if damage != "anchor_egs":
+        egs = np.where(anchor, 0, egs)
+    aegs = np.where(anchor, 0, aegs)
+    eg = Gb * s[:, None, None]                             # grad_r, :188
+    aeg = (aGb * s[:, None, None]).max(axis=(1, 2))
+    M = np.einsum("iak,ibk->iab", Rb, eg)                  # :310
+    S0 = M if damage == "nosym" else sym3(M)               # :311
+    rgR = eg - np.einsum("iab,ibk->iak", S0, Rb)           # :312-314
+    rgs = egs * s * s                                      # :315
+    rr = (rgR * rgR).sum() + ((rgs / s) ** 2).sum()
+    o = R.shape[1]
+    arr = (3 * o * aeg * aeg).sum() + ((aegs * s) ** 2).sum()
+    return {"f": f, "f~": af, "rr": rr, "rr~": arr, "G": Gb, "G~": aGb.max(axis=(1, 2)), "egs": egs, "egs~": aegs, "S0": S0, "S0~": aeg,
+            "rgR": rgR, "rgR~": aeg, "rgs": rgs, "rgs~": aegs * s * s, "_aG": aGb, "_R": Rb, "_s": s}
+
+
+def hess_stage(op, g, pR, ps, rR, rs, lam, dt=LD, damage=None):
+    """ehess :227-255, ehess2rhess :277-295 at the point of the gradient stage g (op: the operator of the Hessian products, which the fp32 option
+    rounds to fp32; G, egs, S0 come from g), and the three inner products the truncated CG takes from it (:565-566, :625-626)"""
+    Rb, s = g["_R"], g["_s"]
+    n, lam = s.size, dt(lam)
+    anchor = np.arange(n) == 0
+    Pb, rb = blk(np.asarray(pR).astype(dt), n), blk(np.asarray(rR).astype(dt), n)
+    ps, rs = np.asarray(ps).astype(dt).copy(), np.asarray(rs).astype(dt).copy()
+    pse = ps.copy()                                        # the scale part as the epilogue sees it: a direction is given with anything at the anchor
+    ps[0] = 0                                              # su_ex = [0; su], :204
+    rs[0] = 0
+    if damage != "anchor_ps":
+        pse[0] = 0
+    G, aG, egs = g["G"].astype(dt), g["_aG"].astype(dt), g["egs"].astype(dt)
+    W = Pb * s[:, None, None] + Rb * ps[:, None, None]     # sRu + suR, :229-234
+    aW = np.abs(Pb) * s[:, None, None] + np.abs(Rb) * np.abs(ps)[:, None, None]
+    h = blk(2 * op(W.reshape(3 * n, -1), dt), n)           # CsRu, :237
+    ah = blk(2 * op.absolute(aW.reshape(3 * n, -1), dt), n)
+    c = (s * s - 1) if damage == "lam_s2" else (3 * s * s - 1)
+    lamterm = 4 * lam * c * ps                             # HessLambdaKernal, :250-254
+    hs = (h * Rb).sum(axis=(1, 2)) + (G * Pb).sum(axis=(1, 2)) + lamterm   # :244-248
+    ahs = (ah * np.abs(Rb)).sum(axis=(1, 2)) + (aG * np.abs(Pb)).sum(axis=(1, 2)) + np.abs(lamterm)
+    if damage != "anchor_rhs":
+        hs = np.where(anchor, 0, hs)
+    eh = h * s[:, None, None] + G * pse[:, None, None]     # hr = sCsRu + suCsR, :238-242
+    aeh = (ah * s[:, None, None] + aG * np.abs(ps)[:, None, None]).max(axis=(1, 2))
+    S0 = g["S0"].astype(dt)
+    aS0 = g["S0~"].astype(dt)
+    rh = eh if damage == "no_S0" else eh - np.einsum("iab,ibk->iak", S0, Pb)   # :279-283
+    M = np.einsum("iak,ibk->iab", Rb, rh)                  # :285
+    S1 = M if damage == "nosym" else sym3(M)               # :286
+    HpR = rh - np.einsum("iab,ibk->iak", S1, Rb)           # :287
+    aHpR = aeh + 3 * aS0 * np.abs(Pb).max(axis=(1, 2))
+    Hps = hs * s * s                                       # :288
+    if damage != "no_ps_s_egs":
+        Hps = Hps + ps * s * egs                           # :289-293
+    aHps = ahs * s * s + np.abs(ps) * s * g["egs~"].astype(dt)
+    if damage != "anchor_rhs":
+        Hps = np.where(anchor, 0, Hps)
+    aHps = np.where(anchor, 0, aHps)
+    o = Rb.shape[2]
+    pHp = (Pb * HpR).sum() + (ps * Hps / (s * s)).sum()
+    rHp = (rb * HpR).sum() + (rs * Hps / (s * s)).sum()
+    HpHp = (HpR * HpR).sum() + ((Hps / s) ** 2).sum()
+    apHp = (np.abs(Pb).sum(axis=(1, 2)) * aHpR).sum() + (np.abs(ps) * aHps / (s * s)).sum()
+    arHp = (np.abs(rb).sum(axis=(1, 2)) * aHpR).sum() + (np.abs(rs) * aHps / (s * s)).sum()
+    aHH = (3 * o * aHpR * aHpR).sum() + ((aHps / s) ** 2).sum()
+    return {"HpR": HpR, "HpR~": aHpR, "Hps": Hps, "Hps~": aHps, "pHp": pHp, "pHp~": apHp, "rHp": rHp, "rHp~": arHp, "HpHp": HpHp, "HpHp~": aHH,
+            "W": W, "W~": aW.max(axis=(1, 2))}
+
+
+def tcg_init_stage(g, delta, dt=LD):
+    """start of the truncated CG, trustregion.h:454-458, 476-485: r = rg, p = -rg, v = Hv = 0, the first product input (:229-234)"""
+    Rb, s = g["_R"], g["_s"]
+    rR, rs = g["rgR"].astype(dt), g["rgs"].astype(dt)
+    z, zs = np.zeros(rR.shape, dtype=dt), np.zeros(rs.shape, dtype=dt)
+    W = -rR * s[:, None, None] + Rb * (-rs)[:, None, None]
+    rr = dt(g["rr"])
+    scal = dict(rr=rr, vv=dt(0), vp=dt(0), pp=rr, delta=dt(delta), gradnorm=np.sqrt(rr), last_step=dt(0), model=dt(0), status=0, iter=0)
+    return {"rR": rR, "rs": rs, "pR": -rR, "ps": -rs, "vR": z, "vs": zs, "HvR": z, "Hvs": zs, "W": W, "scal": scal}
+
+
+def cg_step_stage(sc, sums, Hp, p, r, v, Hv, R, s, dt=LD, damage=None, model_rec=False, pHp_scale=None):
+    """one iteration of the truncated CG's body, trustregion.h:565-644, from its scalar state sc (rr, vv, vp, pp, delta, gradnorm, model, iter),
+    sums = (<p,Hp>, <r,Hp>, <Hp,Hp>, |r|^2 as summed by the previous iteration or None at iter 0) and the vectors.  The residual norm after
+    the step is the expansion <r,r> + 2 step <r,Hp> + step^2 <Hp,Hp> of :626; the model value follows m -= step <r,r> - step^2 <p,Hp> / 2.
+    Returns the outputs, the branch taken and, under "margins", the relative distance of every comparison a branch depends on (the sign of
+    alpha is the sign of <p,Hp>: judged against pHp_scale, the magnitude of that sum's terms)."""
+    R, s = point(R, s, dt)
+    n = s.size
+    Rb = blk(R, n)
+    cv = lambda a: np.asarray(a).astype(dt)
+    HpR, Hps, pR, ps, rR, rs, vR, vs = blk(cv(Hp[0]), n), cv(Hp[1]), blk(cv(p[0]), n), cv(p[1]), blk(cv(r[0]), n), cv(r[1]), blk(cv(v[0]), n), cv(v[1])
+    HvR, Hvs = (None, None) if model_rec else (blk(cv(Hv[0]), n), cv(Hv[1]))
+    pHp, rHp, HpHp = (dt(x) for x in sums[:3])
+    rr = dt(sc["rr"]) if sc["iter"] == 0 else dt(sums[3])
+    vv, vp, pp, delta, gradnorm, model = (dt(sc[k]) for k in ("vv", "vp", "pp", "delta", "gradnorm", "model"))
+    out = dict(vR=vR, vs=vs, HvR=HvR, Hvs=Hvs, rR=rR, rs=rs, pR=pR, ps=ps, W=None, rr_parts=None)
+    bmax = lambda a: np.abs(a).max(axis=(1, 2))
+    nx = dict(rr=rr, vv=vv, vp=vp, pp=pp, delta=delta, gradnorm=gradnorm, last_step=dt(0), model=model, status=0, iter=int(sc["iter"]))
+    rel = lambda a, b: float(abs(a - b) / max(abs(a), abs(b))) if max(abs(a), abs(b)) > 0 else 0.0
+    margins = {"rr<1e-15": rel(rr, dt(1e-15))}
+    if rr < dt(1e-15):                                     # :572-576
+        nx["status"] = 5
+        return dict(out, scal=nx, branch=5, margins=margins, step=dt(0))
+    alpha = rr / pHp                                       # :566
+    margins["alpha>0"] = float(abs(pHp) / max(abs(pHp), dt(pHp_scale or 0)))
+    vnew2 = vv + 2 * alpha * vp + alpha * alpha * pp       # :589
+    neg = alpha <= 0                                       # :577
+    if not neg:
+        margins["inside"] = rel(vnew2, delta * delta)
+    boundary = neg or vnew2 > delta * delta
+    if boundary:                                           # :578-579, 590-591
+        sq = np.sqrt(vp * vp + pp * (delta * delta - vv))
+        step = ((-vp - sq) if damage == "tau_root" else (-vp + sq)) / pp
+    else:
+        step = alpha
+    nx["last_step"] = step
+    if model_rec:
+        nx["model"] = model - step * rr + step * step * pHp / 2
+    out["vR"], out["vs"] = vR + step * pR, vs + step * ps                         # :582-583, 594-595, 605-606
+    out["vR~"], out["vs~"] = bmax(vR) + abs(step) * bmax(pR), np.abs(vs) + abs(step) * np.abs(ps)
+    out["model~"] = abs(model) + abs(step * rr) + abs(step * step * pHp / 2)
+    if not model_rec:
+        out["HvR"], out["Hvs"] = HvR + step * HpR, Hvs + step * Hps               # :584-585, 596-597, 609-610
+        out["HvR~"], out["Hvs~"] = bmax(HvR) + abs(step) * bmax(HpR), np.abs(Hvs) + abs(step) * np.abs(Hps)
+    if boundary:
+        nx["status"] = 1 if neg else 2                     # :586, 598
+        return dict(out, scal=nx, branch=nx["status"], margins=margins, step=step)
+    rRn, rsn = rR + step * HpR, rs + step * Hps            # :607-608
+    out["rR"], out["rs"] = rRn, rsn
+    out["rR~"], out["rs~"] = bmax(rR) + abs(step) * bmax(HpR), np.abs(rs) + abs(step) * np.abs(Hps)
+    out.update({"rr~": rr + abs(2 * step * rHp) + step * step * HpHp, "vv~": vv + abs(2 * alpha * vp) + alpha * alpha * pp})
+    out["rr_parts"] = (rRn * rRn).sum() + ((rsn / s) ** 2).sum()                  # :625-626, summed directly: <r,r> of the next iteration
+    rr_est = rr + step * step * HpHp
+    if damage != "rr_est_no_cross":
+        rr_est = rr_est + 2 * step * rHp
+    rr_est = max(rr_est, dt(0))
+    stop = gradnorm * min(gradnorm, dt(0.1))               # :627
+    margins["converged"] = rel(np.sqrt(rr_est), stop)
+    beta = rr_est / rr                                     # :634
+    nx["rr"] = rr_est
+    nx["vv"] = vnew2                                       # :642
+    nx["vp"] = (vp + step * pp) if damage == "vp_no_beta" else beta * (vp + step * pp)   # :643
+    nx["pp"] = beta * beta * pp + rr_est                   # :644
+    out["vp~"] = beta * (abs(vp) + abs(step) * pp)
+    if np.sqrt(rr_est) < stop:
+        nx["status"] = 3                                   # :628
+        return dict(out, scal=nx, branch=3, margins=margins, step=step)
+    pRn, psn = beta * pR - rRn, beta * ps - rsn            # :635-638
+    out["pR"], out["ps"] = pRn, psn
+    out["pR~"], out["ps~"] = beta * bmax(pR) + out["rR~"], beta * np.abs(ps) + out["rs~"]
+    out["W~"] = out["pR~"] * s + out["ps~"]
+    out["W"] = pRn * s[:, None, None] + Rb * psn[:, None, None]                   # the next :229-234
+    nx["iter"] = int(sc["iter"]) + 1
+    nx["status"] = 6 if nx["iter"] >= MAX_INNER else 0     # :559
+    return dict(out, scal=nx, branch=nx["status"], margins=margins, step=step)
+
+
+def gj_solve(N, b):
+    """N y = b for a batch of small SPD systems, Gauss-Jordan without pivoting (N = <A_g B, A_h B> with B B^T = s^2 I: near diagonal)"""
+    N, b = N.copy(), b.copy()
+    m = N.shape[1]
+    for c in range(m):
+        d = N[:, c, c].copy()
+        N[:, c, :] /= d[:, None]
+        b[:, c] /= d
+        for r in range(m):
+            if r != c:
+                f = N[:, r, c].copy()
+                N[:, r, :] -= f[:, None] * N[:, c, :]
+                b[:, r] -= f * b[:, c]
+    return b
+
+
+def generators(anchor, dt):
+    """constraint matrices of one camera, checkeig.h:71-98 (anchor: the six symmetric unit matrices) and :100-161 (the others: two traceless
+    diagonal and three off-diagonal ones)"""
+    E = lambda a, b: np.outer(np.eye(3)[a], np.eye(3)[b]).astype(dt)
+    h = dt(1) / 2
+    if anchor:
+        return np.stack([E(0, 0), h * (E(0, 1) + E(1, 0)), h * (E(0, 2) + E(2, 0)), E(1, 1), h * (E(1, 2) + E(2, 1)), E(2, 2)])
+    return np.stack([h * (E(0, 0) - E(1, 1)), h * (E(1, 1) - E(2, 2)), h * (E(0, 1) + E(1, 0)), h * (E(0, 2) + E(2, 0)), h * (E(1, 2) + E(2, 1))])
+
+
+def cert_stage(op, R, s, lam, X=None, dt=LD, damage=None):
+    """the dual certificate's multipliers and operator, checkeig.h:56-368: Z = Q + 2 lam (|row 3i of sR|^2 - 1) on the diagonal entries 3i
+    (:173-182), y = least squares of [A_g sR] y = Z sR camera by camera (:190-214; the columns of different cameras are orthogonal), Lam_i =
+    sum y_g A_g (:263-299), dual = y0 + y3 + y5 + lam sum(1 - xii^2) (:322-332), and S X = Z X - Lam X"""
+    R, s = point(R, s, dt)
+    n, lam = s.size, dt(lam)
+    sR = R * np.repeat(s, 3)[:, None]
+    B = blk(sR, n)
+    row = 1 if damage == "dz_row" else 0
+    xii = (B[:, 0, :] ** 2).sum(axis=1)                    # :324-329
+    dz = 2 * lam * (xii - 1)
+    adz = 2 * lam * (xii + 1)
+    Right = blk(op(sR, dt), n).copy()                      # :181-182
+    aRight = blk(op.absolute(sR, dt), n).copy()
+    Right[:, row, :] += dz[:, None] * B[:, row, :]
+    aRight[:, 0, :] += adz[:, None] * np.abs(B[:, 0, :])
+    Lam = np.zeros((n, 3, 3), dtype=dt)
+    Mm = np.einsum("iak,ibk->iab", Right, B)
+    Pm = np.einsum("iak,ibk->iab", B, B)
+    y_anchor = None
+    for anchor in (True, False):
+        idx = np.array([0]) if anchor else np.arange(1, n)
+        if idx.size == 0:
+            continue
+        A = generators(anchor and damage != "lam5", dt)
+        rhs = np.einsum("gab,iab->ig", A, Mm[idx])
+        N = np.einsum("gab,ibc,hac->igh", A, Pm[idx], A)
+        y = gj_solve(N, rhs)
+        Lam[idx] = np.einsum("ig,gab->iab", y, A)
+        if anchor:
+            y_anchor = y[0]
+    aLam = aRight.max(axis=(1, 2)) / s
+    if damage == "lam5":
+        dual0 = dt(0)
+    else:
+        dual0 = y_anchor[0] + y_anchor[3] + y_anchor[5]     # :322
+    dual1 = lam * (1 - xii * xii).sum()                    # :330-332
+    out = {"Lam": Lam, "Lam~": aLam, "dz": dz, "dz~": adz, "dual0": dual0, "dual0~": 3 * aLam[0], "dual1": dual1, "dual1~": lam * (1 + xii * xii).sum()}
+    if X is not None:
+        X = np.asarray(X).astype(dt)
+        Xb = blk(X, n)
+        SX = blk(op(X, dt), n) - np.einsum("iab,ibk->iak", Lam, Xb)
+        SX[:, row, :] += dz[:, None] * Xb[:, row, :]
+        aSX = blk(op.absolute(X, dt), n).max(axis=(1, 2)) + adz * np.abs(Xb[:, 0, :]).max(axis=1) + 3 * aLam * np.abs(Xb).max(axis=(1, 2))
+        out.update({"SX": SX, "SX~": aSX})
+    return out
+
+
+def polar_rows(M):
+    """the closest matrices with orthonormal rows to a batch of 3 x o blocks: Newton's iteration X <- (X + (X X^T)^-1 X) / 2, the 3x3 inverses
+    by cofactors (numpy's factorisations do not work in longdouble)"""
+    X = M.copy()
+    for _ in range(60):
+        A = np.einsum("iak,ibk->iab", X, X)
+        C = np.empty_like(A)
+        for a in range(3):
+            for b in range(3):
+                a1, a2, b1, b2 = (a + 1) % 3, (a + 2) % 3, (b + 1) % 3, (b + 2) % 3
+                C[:, b, a] = A[:, a1, b1] * A[:, a2, b2] - A[:, a1, b2] * A[:, a2, b1]
+        det = (A[:, 0, :] * C[:, :, 0]).sum(axis=1)
+        Xn = (X + np.einsum("iab,ibk->iak", C / det[:, None, None], X)) / 2
+        if np.abs(Xn - X).max() == 0:
+            break
+        X = Xn
+    return X
+
+
+def curve(R, s, pR, ps, t, dt=LD):
+    """a second-order curve through (R, s) with velocity (pR, ps): the polar retraction of R + t pR and the geodesic s exp(t ps / s) of the
+    metric ds^2 / s^2 (trustregion.h:19-24)"""
+    R, s = point(R, s, dt)
+    n, t = s.size, dt(t)
+    Rt = polar_rows(blk(R + t * np.asarray(pR).astype(dt), n)).reshape(R.shape)
+    st = s * np.exp(t * np.asarray(ps).astype(dt) / s)
+    return Rt, st

@@ -415,6 +415,43 @@ int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const dou
     return XM_OK;
     XM_CATCH
 }
+int xm_ctx_rtr_probe(xm_ctx_t *ctx, xm_rtr_probe_t *pr) {
+    XM_TRY
+    if (!ctx || !pr) throw xm::Error(XM_ERR_ARG, "xm_ctx_rtr_probe: null argument");
+    if (pr->struct_size != sizeof(xm_rtr_probe_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_rtr_probe: xm_rtr_probe_t.struct_size is not sizeof(xm_rtr_probe_t)");
+    if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_rtr_probe: single-GPU contexts only (not n_gpus > 1)");
+    if (ctx->impl->world() > 1 || ctx->impl->comm_kind() != 0) throw xm::Error(XM_ERR_ARG, "xm_ctx_rtr_probe: single-rank contexts only");
+    if (pr->o < 3 || pr->o > 10) throw xm::Error(XM_ERR_ARG, "xm_ctx_rtr_probe: rank o must be in 3..10");
+    if (pr->flags & ~(XM_RTR_PROBE_AUTO | XM_RTR_PROBE_MODEL_REC | XM_RTR_PROBE_TCG_INIT | XM_RTR_PROBE_CG_STEP | XM_RTR_PROBE_CERT))
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_rtr_probe: unknown flag");
+    if (!pr->R || !pr->s) throw xm::Error(XM_ERR_ARG, "xm_ctx_rtr_probe: the point (R, s) is missing");
+    if ((pr->pR == nullptr) != (pr->ps == nullptr)) throw xm::Error(XM_ERR_ARG, "xm_ctx_rtr_probe: pR and ps go together");
+    if (pr->k < 0 || (pr->k > 0 && !pr->X)) throw xm::Error(XM_ERR_ARG, "xm_ctx_rtr_probe: k > 0 needs X");
+    const int64_t n = ctx->impl->cameras(), mat = 3 * n * pr->o;
+    auto finite = [](const double *x, int64_t len, const char *what) {
+        if (!x) return;
+        for (int64_t k = 0; k < len; ++k)
+            if (!std::isfinite(x[k])) throw xm::Error(XM_ERR_ARG, std::string("xm_ctx_rtr_probe: ") + what + " is not finite");
+    };
+    if (!std::isfinite(pr->lam)) throw xm::Error(XM_ERR_ARG, "xm_ctx_rtr_probe: lam is not finite");
+    finite(pr->R, mat, "R"); finite(pr->s, n, "s"); finite(pr->pR, mat, "pR"); finite(pr->ps, n, "ps"); finite(pr->rR, mat, "rR"); finite(pr->rs, n, "rs");
+    finite(pr->X, 3 * n * pr->k, "X");
+    if (pr->flags & XM_RTR_PROBE_CG_STEP) {
+        finite(pr->vR, mat, "vR"); finite(pr->vs, n, "vs");
+        if (!(pr->flags & XM_RTR_PROBE_MODEL_REC)) { finite(pr->HvR, mat, "HvR"); finite(pr->Hvs, n, "Hvs"); }
+        if (pr->scal_in.iter > 0) finite(pr->partsB_in, pr->partsB_in_count, "partsB_in");
+        const xm_rtr_scal_t &sc = pr->scal_in;
+        const double v[7] = {sc.rr, sc.vv, sc.vp, sc.pp, sc.delta, sc.gradnorm, sc.model};
+        finite(v, 7, "scal_in");
+        if (sc.iter < 0 || sc.iter >= 1000) throw xm::Error(XM_ERR_ARG, "xm_ctx_rtr_probe: scal_in.iter must be in 0..999");
+    }
+    if ((pr->flags & XM_RTR_PROBE_TCG_INIT) && !std::isfinite(pr->scal_in.delta)) throw xm::Error(XM_ERR_ARG, "xm_ctx_rtr_probe: scal_in.delta is not finite");
+    for (int64_t i = 0; i < n; ++i)
+        if (!(pr->s[i] > 0.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_rtr_probe: scales must be positive");
+    ctx->impl->rtr_probe(*pr);
+    return XM_OK;
+    XM_CATCH
+}
 namespace {
 void clean_settings(const char *who, const xm_clean_options_t *opt, const uint8_t *keep, const int32_t *cam_index, const int32_t *lm_index,
                     const xm_clean_result_t *res, xm::CleanSettings &c) {

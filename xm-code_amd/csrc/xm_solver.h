@@ -203,6 +203,7 @@ public:
     // reprojection bundle adjustment of a recovered solution (xm_ba.h): matrix-free storage, one rank; reads the context, changes nothing in it
     void bundle_adjust(const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out);
     void ba_probe(const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q);   // test export
+    void rtr_probe(xm_rtr_probe_t &q);   // test export (include/xm_amd.h: xm_ctx_rtr_probe): the trust region's kernels stage by stage
     void reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr);   // per observation, input order (xm_ba.h)
     // which observations, cameras and landmarks of the list survive cleaning at the current weights (xm_clean.h); changes nothing here
     void clean_observations(const CleanSettings &cfg, uint8_t *keep, int32_t *cam_index, int32_t *lm_index, CleanOutcome &out);
@@ -346,6 +347,7 @@ private:
     unsigned int outer_run_ = 0;         // run number in the progress word (hstat_[24])
     CertResult certificate(int o, double primal, std::vector<double> &v_out);
     int lanczos_min(std::vector<double> &x_out, double &theta, int &iters, double &resid);   // 0 converged, 1 not
+    void cert_product(const double *vj, const CamArgs &a, int j);   // a.out = S vj for a replicated vector of pitch 1 (EPI_CERT; j: sweep direction of the symmetric pair)
     void log(const char *fmt, ...) const;
 };
 

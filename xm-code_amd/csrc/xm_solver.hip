@@ -1422,6 +1422,14 @@ static void tridiag_min(const std::vector<double> &a, const std::vector<double> 
 // Replaces cusolverDnXsyevd on the 3n x 3n certificate matrix (checkeig.h:303-318, Dense/eig.h:35-73), O((3n)^3),
 // by products with the same Q*W kernel (rank-1 input).  Lam_/dz live in ps_[cur^1].S0 / .egs (free at this point).
 // ------------------------------------------------------------------------------------------------------------------
+void Context::cert_product(const double *vj, const CamArgs &a, int j) {
+    if (storage_ == XM_STORAGE_DENSE && sym_ok_ && Pcol_.p) launch_qw_sym(1, EPI_CERT, dQ_, ld_, vj, 1.0, a, Prow_.p, Pcol_.p, st_, j);
+    else if (storage_ == XM_STORAGE_DENSE) launch_qw_dense(1, EPI_CERT, dQ_, ld_, vj, 1.0, a, st_);
+    else if (storage_ == XM_STORAGE_SCHUR) schur_->product(1, EPI_CERT, vj, 1.0, a, st_);
+    else if (sell_) launch_qw_sell(1, EPI_CERT, *sell_, vj, 1.0, a, 0, st_);
+    else launch_qw_bsr3(1, EPI_CERT, rowptr_.p, colidx_.p, blocks_.p, vj, 1.0, a, st_, nb_loc_, rowinfo_.p);
+}
+
 int Context::lanczos_min(std::vector<double> &x_out, double &theta_out, int &iters_out, double &resid_out) {
     const int64_t len = ld_;           // vectors are replicated, full length, zero beyond 3n
     const int64_t m3 = 3 * n_;
@@ -1482,11 +1490,7 @@ int Context::lanczos_min(std::vector<double> &x_out, double &theta_out, int &ite
                 // w = S v_j : the product input is v_j itself (pitch 1); output rows land in w at this rank's offset
                 a.Wloc = vj + (size_t)cam0_ * 3;
                 a.out = w.p + (size_t)cam0_ * 3;
-                if (storage_ == XM_STORAGE_DENSE && sym_ok_ && Pcol_.p) launch_qw_sym(1, EPI_CERT, dQ_, ld_, vj, 1.0, a, Prow_.p, Pcol_.p, st_, j);
-                else if (storage_ == XM_STORAGE_DENSE) launch_qw_dense(1, EPI_CERT, dQ_, ld_, vj, 1.0, a, st_);
-                else if (storage_ == XM_STORAGE_SCHUR) schur_->product(1, EPI_CERT, vj, 1.0, a, st_);
-                else if (sell_) launch_qw_sell(1, EPI_CERT, *sell_, vj, 1.0, a, 0, st_);
-                else launch_qw_bsr3(1, EPI_CERT, rowptr_.p, colidx_.p, blocks_.p, vj, 1.0, a, st_, nb_loc_, rowinfo_.p);
+                cert_product(vj, a, j);
                 res_->qw_products++;
                 if (comm_->active()) comm_->allgather(w.p, (size_t)nloc_ * 3, st_);
                 // classical Gram-Schmidt twice against V(:,0..j); alpha_j = c1[j] + c2[j]; beta_j = |w|; v_{j+1} = w / beta_j
@@ -1625,6 +1629,209 @@ void Context::apply(int o, const double *Wh, double *out, double alpha) {
         for (int k = 0; k < o; ++k) out[r + (size_t)k * m] = res[r * OP_ + k];
     opt_ = nullptr;
     solved_ = false;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The trust region's kernels stage by stage (test export xm_ctx_rtr_probe, include/xm_amd.h): the context's own setup for rank o, cam_args(),
+// product() and the launchers with the grids and arguments of trust_region() / tcg_enqueue_iteration() / trust_region_device() / certificate().
+// Nothing a later solve reads survives: setup_rank() re-creates the workspace, the progress words are not touched (hstat = nullptr, seq 0), and
+// the result block's sequence number only ever has to grow.
+// ------------------------------------------------------------------------------------------------------------------
+void Context::rtr_probe(xm_rtr_probe_t &q) {
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_rtr_probe: single-rank contexts only");
+    const int o = q.o;
+    const bool aut = (q.flags & XM_RTR_PROBE_AUTO) != 0, model_rec = (q.flags & XM_RTR_PROBE_MODEL_REC) != 0;
+    const bool want_hess = q.pR && q.ps, want_init = (q.flags & XM_RTR_PROBE_TCG_INIT) != 0, want_step = (q.flags & XM_RTR_PROBE_CG_STEP) != 0;
+    const bool want_cert = (q.flags & XM_RTR_PROBE_CERT) != 0;
+    if (want_step && !want_hess) throw Error(XM_ERR_ARG, "xm_ctx_rtr_probe: XM_RTR_PROBE_CG_STEP needs pR and ps (the hess stage)");
+    if (want_step && !(q.vR && q.vs && (model_rec || (q.HvR && q.Hvs)))) throw Error(XM_ERR_ARG, "xm_ctx_rtr_probe: XM_RTR_PROBE_CG_STEP needs v (and Hv unless XM_RTR_PROBE_MODEL_REC)");
+    xm_options_t opt;
+    std::memset(&opt, 0, sizeof(opt));
+    opt.lam = q.lam;
+    opt.max_rank = (unsigned)o;
+    opt.flags = (aut ? XM_FLAG_DEVICE_OUTER : 0u) | (model_rec ? XM_FLAG_MODEL_RECURRENCE : 0u);
+    struct Leave { Context *c; ~Leave() { c->opt_ = nullptr; c->sym_rev_ = 1; c->solved_ = false; } } leave{this};
+    opt_ = &opt;
+    grouping_ = 0;
+    setup_rank(o);
+    const int nA = prod_grid(), nB = tcg_blocks();
+    q.product_kind = product_kind(o); q.nA = nA; q.nB = nB; q.wpad = wpad() ? 1 : 0; q.w_native = wpad() ? 0 : 1;
+    q.split_k = ks_; q.sell_gather = (sell_ && sell_supports(o)) ? sell_gm_ : -1;
+    if (aut && !device_outer_applies(o)) throw Error(XM_ERR_ARG, "xm_ctx_rtr_probe: XM_RTR_PROBE_AUTO, but the device-driven outer iteration does not apply to this context at this rank");
+    if (want_step && q.scal_in.iter > 0 && (!q.partsB_in || q.partsB_in_count != nB))
+        throw Error(XM_ERR_ARG, "xm_ctx_rtr_probe: scal_in.iter > 0 needs partsB_in with nB = " + std::to_string(nB) + " partial sums");
+    const size_t n = (size_t)n_, m3 = 3 * n, mat = (size_t)nloc_ * 3 * OP_;
+    std::vector<double> hm(mat), hv((size_t)nloc_);
+    auto up_mat = [&](double *dst, const double *src, double sign) {   // host column-major -> device rows of pitch OP (nullptr: zeros)
+        std::fill(hm.begin(), hm.end(), 0.0);
+        if (src)
+            for (size_t c = 0; c < n; ++c)
+                for (int a = 0; a < 3; ++a)
+                    for (int k = 0; k < o; ++k) hm[(c * 3 + a) * OP_ + k] = sign * src[(3 * c + a) + (size_t)k * m3];
+        to_dev(dst, hm.data(), mat * sizeof(double));
+    };
+    auto up_vec = [&](double *dst, const double *src, double sign, bool zero_anchor) {
+        std::fill(hv.begin(), hv.end(), 0.0);
+        if (src)
+            for (size_t c = 0; c < n; ++c) hv[c] = sign * src[c];
+        if (zero_anchor) hv[0] = 0.0;
+        to_dev(dst, hv.data(), hv.size() * sizeof(double));
+    };
+    auto down_mat = [&](double *dst, const double *src) {
+        if (!dst) return;
+        to_host(hm.data(), src, mat * sizeof(double));
+        for (size_t c = 0; c < n; ++c)
+            for (int a = 0; a < 3; ++a)
+                for (int k = 0; k < o; ++k) dst[(3 * c + a) + (size_t)k * m3] = hm[(c * 3 + a) * OP_ + k];
+    };
+    auto down_vec = [&](double *dst, const double *src, size_t per = 1) {
+        if (dst) to_host(dst, src, n * per * sizeof(double));
+    };
+    auto scal_out = [](const TcgScal &sc, xm_rtr_scal_t &out) {
+        out.rr = sc.rr; out.vv = sc.vv; out.vp = sc.vp; out.pp = sc.pp; out.delta = sc.delta; out.gradnorm = sc.gradnorm; out.last_step = sc.last_step;
+        out.model = sc.model; out.status = sc.status; out.iter = sc.iter;
+    };
+    double *hres_dev = reinterpret_cast<double *>(hstat_dev_) + 8;
+    double *Wloc = W_.p + (size_t)cam0_ * 3 * OP_;
+    double *Wtcg = wpad() ? nullptr : Wloc;   // as run_tcg: with the padded copy on, the tCG's kernels do not write the native-pitch input
+    const PointState &P = ps_[cur_];
+
+    // ---- grad: trust_region()'s first cost / gradient
+    upload_point(std::vector<double>(q.R, q.R + m3 * (size_t)o), o, std::vector<double>(q.s, q.s + n));
+    launch_scale_rows(o, nloc_, R_.p, s_.p, Wloc, st_);
+    double f = 0, rr = 0;
+    if (!aut) {
+        eval_point(cur_, R_.p, s_.p, f, rr);
+    } else {   // the role-switching launch in its candidate role: trust_region_device()'s enqueue_slot with the candidate's buffers = this point's
+        TcgScal sc;
+        std::memset(&sc, 0, sizeof(sc));
+        sc.phase = PH_CAND;
+        to_dev(scal_.p, &sc, sizeof(sc));
+        CamArgs a = cam_args(cur_);
+        a.scal = scal_.p;
+        a.partials = partsB_.p;
+        a.cand.R = R_.p; a.cand.s = s_.p;
+        a.cand.G = P.G.p; a.cand.egs = P.egs.p; a.cand.S0 = P.S0.p; a.cand.rgR = P.rgR.p; a.cand.rgs = P.rgs.p;
+        a.cand.partials = partsA_.p;
+        product(EPI_AUTO, o_, 2.0, a);
+        launch_outer_finalize(partsA_.p, nA, 1, partsM_.p, 0, scal_.p, hres_dev, ++outer_seq_, 0, st_);
+        volatile double *hres = wait_outer_result();
+        f = hres[0]; rr = hres[1];
+    }
+    q.f = f; q.rr = rr;
+    down_mat(q.G, P.G.p); down_vec(q.egs, P.egs.p); down_vec(q.S0, P.S0.p, 9); down_mat(q.rgR, P.rgR.p); down_vec(q.rgs, P.rgs.p);
+
+    // ---- tcg_init: run_tcg()'s start from the gradient state
+    if (want_init) {
+        launch_tcg_init(o, nloc_, P.rgR.p, P.rgs.p, R_.p, s_.p, rR_.p, rs_.p, pR_.p, psA_.p, vR_.p, vs_.p, HvR_.p, Hvs_.p, Wtcg, scal_.p, rr, q.scal_in.delta,
+                        nullptr, st_, wpad(), 0);
+        down_mat(q.init_rR, rR_.p); down_vec(q.init_rs, rs_.p); down_mat(q.init_pR, pR_.p); down_vec(q.init_ps, psA_.p);
+        down_mat(q.init_vR, vR_.p); down_vec(q.init_vs, vs_.p); down_mat(q.init_HvR, HvR_.p); down_vec(q.init_Hvs, Hvs_.p);
+        if (Wtcg) down_mat(q.init_W, Wloc);
+        if (wpad()) down_vec(q.init_Wpad, wpad(), 16);
+        TcgScal sc;
+        to_host(&sc, scal_.p, sizeof(sc));
+        scal_out(sc, q.init_scal);
+    }
+
+    // ---- hess: tcg_enqueue_iteration()'s product (trust_region_device()'s in the tCG role)
+    if (want_hess) {
+        const int par = want_step ? (q.scal_in.iter & 1) : 0;
+        double *ps_cur = par ? psB_.p : psA_.p, *ps_next = par ? psA_.p : psB_.p, *rs_cur = par ? rsB_.p : rs_.p, *rs_next = par ? rs_.p : rsB_.p;
+        // the product input W = s.*pR + ps.*R, and its padded copy where the context keeps one, by the kernel that writes them in a solve: the tCG's
+        // start from "rg" = -p (the anchor's scale part is 0 in every direction a solve forms)
+        up_mat(D_.p, q.pR, -1.0);
+        up_vec(sc_.p, q.ps, -1.0, true);
+        launch_tcg_init(o, nloc_, D_.p, sc_.p, R_.p, s_.p, rR_.p, rs_.p, pR_.p, psA_.p, vR_.p, vs_.p, HvR_.p, Hvs_.p, Wtcg, scal_.p, 0.0, 0.0, nullptr, st_, wpad(), 0);
+        up_mat(pR_.p, q.pR, 1.0); up_vec(ps_cur, q.ps, 1.0, false);   // the vectors as given: what they hold at the anchor must not get through
+        up_mat(rR_.p, q.rR, 1.0); up_vec(rs_cur, q.rs, 1.0, false);
+        TcgScal sc;
+        std::memset(&sc, 0, sizeof(sc));
+        if (want_step) {
+            sc.rr = q.scal_in.rr; sc.vv = q.scal_in.vv; sc.vp = q.scal_in.vp; sc.pp = q.scal_in.pp; sc.delta = q.scal_in.delta; sc.gradnorm = q.scal_in.gradnorm;
+            sc.model = q.scal_in.model; sc.iter = q.scal_in.iter;
+        }
+        sc.phase = PH_TCG;
+        to_dev(scal_.p + par, &sc, sizeof(sc));
+        const size_t chunk = (size_t)3 * nA + nB;
+        double *pcur = partsB_.p + (size_t)par * chunk, *pnext = partsB_.p + (size_t)(par ^ 1) * chunk;
+        CamArgs a = cam_args(cur_);
+        a.scal = scal_.p + par;
+        a.ps = ps_cur;
+        a.rs = rs_cur;
+        a.partials = pcur;
+        if (aut) {
+            const PointState &Pn = ps_[cur_ ^ 1];
+            a.cand.R = Rc_.p; a.cand.s = sc_.p;
+            a.cand.G = Pn.G.p; a.cand.egs = Pn.egs.p; a.cand.S0 = Pn.S0.p; a.cand.rgR = Pn.rgR.p; a.cand.rgs = Pn.rgs.p;
+            a.cand.partials = partsA_.p;
+        }
+        sym_rev_ = par;
+        product(aut ? EPI_AUTO : EPI_HESS, o_, 2.0, a);
+        sym_rev_ = 1;
+        // the three sums by the summation tree of cg_step_kernel (sum_partials256: the same tree in every kernel that adds partial sums)
+        launch_outer_finalize(pcur, nA, 1, pcur + (size_t)2 * nA, nA, scal_.p + par, hres_dev, ++outer_seq_, 0, st_);
+        volatile double *hres = wait_outer_result();
+        q.pHp = hres[0]; q.rHp = hres[1]; q.HpHp = hres[2];
+        down_mat(q.HpR, HpR_.p); down_vec(q.Hps, Hps_.p);
+
+        // ---- cg_step: tcg_enqueue_iteration()'s second launch
+        if (want_step) {
+            up_mat(vR_.p, q.vR, 1.0); up_vec(vs_.p, q.vs, 1.0, false);
+            if (!model_rec) { up_mat(HvR_.p, q.HvR, 1.0); up_vec(Hvs_.p, q.Hvs, 1.0, false); }
+            up_vec(ps_next, q.ps, 1.0, false); up_vec(rs_next, q.rs, 1.0, false);   // a branch that leaves them alone returns the input
+            if (q.scal_in.iter > 0) to_dev(pcur + (size_t)3 * nA, q.partsB_in, (size_t)nB * sizeof(double));
+            XM_HIP_CHECK(hipMemsetAsync(pnext + (size_t)3 * nA, 0, (size_t)nB * sizeof(double), st_));
+            launch_cg_step(o_, nloc_, scal_.p + par, scal_.p + (par ^ 1), pcur, nA, nB, 1, HpR_.p, Hps_.p, R_.p, s_.p, pR_.p, ps_cur, ps_next, vR_.p, vs_.p,
+                           model_rec ? nullptr : HvR_.p, model_rec ? nullptr : Hvs_.p, rR_.p, rs_cur, rs_next, Wtcg, pnext + (size_t)3 * nA, nullptr, 0,
+                           (int64_t)mat, nullptr, W_.p, 0, PeerXchg(), st_, wpad());
+            launch_outer_finalize(partsA_.p, 0, 1, pnext + (size_t)3 * nA, nB, scal_.p + (par ^ 1), hres_dev, ++outer_seq_, 0, st_);
+            hres = wait_outer_result();
+            q.rr_parts = hres[2];
+            TcgScal nx;
+            to_host(&nx, scal_.p + (par ^ 1), sizeof(nx));
+            scal_out(nx, q.scal_out);
+            down_mat(q.out_vR, vR_.p); down_vec(q.out_vs, vs_.p);
+            if (!model_rec) { down_mat(q.out_HvR, HvR_.p); down_vec(q.out_Hvs, Hvs_.p); }
+            down_mat(q.out_rR, rR_.p); down_vec(q.out_rs, rs_next); down_mat(q.out_pR, pR_.p); down_vec(q.out_ps, ps_next);
+            if (Wtcg) down_mat(q.out_W, Wloc);
+            if (wpad()) down_vec(q.out_Wpad, wpad(), 16);
+            if (q.partsB_out) to_host(q.partsB_out, pnext + (size_t)3 * nA, (size_t)nB * sizeof(double));
+        }
+    }
+
+    // ---- cert: certificate()'s right-hand side, multipliers and operator
+    if (want_cert) {
+        launch_scale_rows(o, nloc_, R_.p, s_.p, Wloc, st_);
+        CamArgs a = cam_args(cur_);
+        a.out = HpR_.p;
+        product(EPI_PLAIN, o, 1.0, a);
+        const int g = (nloc_ + 255) / 256;
+        double *Lam = ps_[cur_ ^ 1].S0.p, *dz = ps_[cur_ ^ 1].egs.p;
+        launch_cert_prepare(o, nloc_, cam0_, q.lam, HpR_.p, R_.p, s_.p, Lam, dz, partsM_.p, st_);
+        std::vector<double> parts((size_t)2 * g);
+        to_host(parts.data(), partsM_.p, parts.size() * sizeof(double));
+        q.dual[0] = q.dual[1] = 0.0;
+        for (int i = 0; i < g; ++i) { q.dual[0] += parts[(size_t)i]; q.dual[1] += parts[(size_t)g + i]; }   // in sum_parts()'s order
+        down_vec(q.Lam, Lam, 9); down_vec(q.dz, dz);
+        if (q.X && q.SX && q.k > 0) {
+            CamArgs c = cam_args(cur_);
+            c.Lam = Lam; c.dz = dz;
+            std::vector<double> x((size_t)ld_), y(m3);
+            for (int j = 0; j < q.k; ++j) {   // as a Lanczos vector: replicated, pitch 1, zero beyond 3n
+                std::fill(x.begin(), x.end(), 0.0);
+                std::copy(q.X + (size_t)j * m3, q.X + (size_t)(j + 1) * m3, x.begin());
+                to_dev(W_.p, x.data(), x.size() * sizeof(double));
+                c.Wloc = W_.p + (size_t)cam0_ * 3;
+                c.out = HpR_.p;
+                cert_product(W_.p, c, j);
+                to_host(y.data(), HpR_.p, m3 * sizeof(double));
+                std::copy(y.begin(), y.end(), q.SX + (size_t)j * m3);
+            }
+        }
+        XM_HIP_CHECK(hipMemsetAsync(W_.p, 0, W_.count * sizeof(double), st_));
+    }
+    XM_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -36,7 +36,7 @@ EXPORTS = [
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
     "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_ba_aggregate_plan", "xm_ctx_ba_probe",
-    "xm_clean_observations", "xm_ctx_clean_observations",
+    "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -110,6 +110,27 @@ class BaProbe(C.Structure):   # xm_ba_probe_t, the test export xm_ctx_ba_probe
                                           "dP", "rot1", "t1", "p1")]
 
 
+class RtrScal(C.Structure):    # xm_rtr_scal_t: the truncated CG's scalar block as the test export xm_ctx_rtr_probe passes it
+    _fields_ = [(k, C.c_double) for k in ("rr", "vv", "vp", "pp", "delta", "gradnorm", "last_step", "model")] + [("status", C.c_int32), ("iter", C.c_int32)]
+
+
+RTR_IN = ("R", "s", "pR", "ps", "rR", "rs", "vR", "vs", "HvR", "Hvs", "partsB_in", "X")
+RTR_OUT = ("G", "egs", "S0", "rgR", "rgs", "HpR", "Hps", "init_rR", "init_rs", "init_pR", "init_ps", "init_vR", "init_vs", "init_HvR", "init_Hvs", "init_W",
+           "init_Wpad", "out_vR", "out_vs", "out_HvR", "out_Hvs", "out_rR", "out_rs", "out_pR", "out_ps", "out_W", "out_Wpad", "partsB_out", "Lam", "dz", "SX")
+
+
+class RtrProbe(C.Structure):   # xm_rtr_probe_t, the test export xm_ctx_rtr_probe
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("o", C.c_int32), ("k", C.c_int32), ("lam", C.c_double)] + \
+               [(k, C.c_void_p) for k in RTR_IN] + [("partsB_in_count", C.c_int32), ("pad", C.c_int32), ("scal_in", RtrScal)] + \
+               [(k, C.c_int32) for k in ("product_kind", "nA", "nB", "w_native", "wpad", "split_k", "sell_gather", "pad2")] + \
+               [(k, C.c_double) for k in ("f", "rr", "pHp", "rHp", "HpHp", "rr_parts")] + [("dual", C.c_double * 2), ("init_scal", RtrScal), ("scal_out", RtrScal)] + \
+               [(k, C.c_void_p) for k in RTR_OUT]
+
+
+RTR_PROBE_AUTO, RTR_PROBE_MODEL_REC, RTR_PROBE_TCG_INIT, RTR_PROBE_CG_STEP, RTR_PROBE_CERT = 1, 2, 4, 8, 16
+RTR_SCAL_IN = ("rr", "vv", "vp", "pp", "delta", "gradnorm", "model", "iter")
+
+
 class CleanOptions(C.Structure):   # xm_clean_options_t
     _fields_ = [("struct_size", C.c_uint32), ("min_cam_obs", C.c_int32), ("min_lm_obs", C.c_int32), ("flags", C.c_uint32)]
 
@@ -173,6 +194,7 @@ def lib():
         L.xm_ctx_recover_tp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_bundle_adjust.argtypes = [C.c_void_p, C.POINTER(BaOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaResult)]
         L.xm_ctx_ba_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaProbe)]
+        L.xm_ctx_rtr_probe.argtypes = [C.c_void_p, C.POINTER(RtrProbe)]
         L.xm_clean_observations.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CleanOptions), C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.POINTER(CleanResult)]
         L.xm_ctx_clean_observations.argtypes = [C.c_void_p, C.POINTER(CleanOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CleanResult)]
@@ -857,6 +879,64 @@ class Context:
         if dc is not None:
             out.update(cost1=q.cost1, model=q.model, step2=np.array(q.step2[:]), x2=np.array(q.x2[:]))
         return out
+
+    def rtr_probe(self, o, lam, R, s, p=None, r=None, auto=False, tcg_init=False, delta=1.0, cg_step=None, model_recurrence=False, cert=False, X=None):
+        """the trust region's kernels stage by stage at the point (R: 3n x o, s: n) (the test export xm_ctx_rtr_probe; include/xm_amd.h): a dict of
+        f, rr, G, egs, S0 (n x 3 x 3), rgR, rgs, product_kind, nA, nB, wpad, w_native; with p = (pR, ps) [and r = (rR, rs)]: HpR, Hps, pHp, rHp,
+        HpHp; split_k, sell_gather: the column split and the sliced-ELL gather mode in effect; auto=True: both through the role-switching launch; tcg_init=True (radius delta): init_* and init_scal; cg_step = dict(rr, vv, vp,
+        pp, delta, gradnorm, model, iter, v=(vR, vs), Hv=(HvR, Hvs), partsB=array for iter > 0): one cg_step launch -> scal_out, out_*,
+        partsB_out, rr_parts (model_recurrence=True: no Hv); cert=True: Lam (n x 3 x 3), dz, dual (2), and SX for X (3n x k)."""
+        n, o = self.n, int(o)
+        f64 = lambda a, shape: np.asfortranarray(np.asarray(a, dtype=np.float64).reshape(shape))
+        q = RtrProbe()
+        q.struct_size = C.sizeof(RtrProbe)
+        q.o, q.lam = o, float(lam)
+        q.flags = (RTR_PROBE_AUTO if auto else 0) | (RTR_PROBE_MODEL_REC if model_recurrence else 0) | (RTR_PROBE_TCG_INIT if tcg_init else 0) | \
+                  (RTR_PROBE_CG_STEP if cg_step is not None else 0) | (RTR_PROBE_CERT if cert else 0)
+        q.scal_in.delta = float(delta)
+        ins = dict(R=f64(R, (3 * n, o)), s=f64(s, (n,)))
+        mat = lambda: np.zeros((3 * n, o), order="F")
+        out = dict(G=mat(), egs=np.zeros(n), S0=np.zeros((n, 3, 3)), rgR=mat(), rgs=np.zeros(n))
+        if p is not None:
+            ins.update(pR=f64(p[0], (3 * n, o)), ps=f64(p[1], (n,)))
+            out.update(HpR=mat(), Hps=np.zeros(n))
+        if r is not None:
+            ins.update(rR=f64(r[0], (3 * n, o)), rs=f64(r[1], (n,)))
+        if tcg_init:
+            out.update({"init_" + k: (np.zeros(n) if k.endswith("s") else mat()) for k in ("rR", "rs", "pR", "ps", "vR", "vs", "HvR", "Hvs")})
+            out.update(init_W=mat(), init_Wpad=np.zeros((n, 16)))
+        if cg_step is not None:
+            for k in RTR_SCAL_IN:
+                setattr(q.scal_in, k, (int if k == "iter" else float)(cg_step[k]))
+            ins.update(vR=f64(cg_step["v"][0], (3 * n, o)), vs=f64(cg_step["v"][1], (n,)))
+            if not model_recurrence:
+                ins.update(HvR=f64(cg_step["Hv"][0], (3 * n, o)), Hvs=f64(cg_step["Hv"][1], (n,)))
+            if cg_step.get("partsB") is not None:
+                ins["partsB_in"] = f64(cg_step["partsB"], (-1,))
+                q.partsB_in_count = ins["partsB_in"].size
+            out.update({"out_" + k: (np.zeros(n) if k.endswith("s") else mat()) for k in ("vR", "vs", "HvR", "Hvs", "rR", "rs", "pR", "ps")})
+            out.update(out_W=mat(), out_Wpad=np.zeros((n, 16)), partsB_out=np.zeros(1024))
+        if cert:
+            out.update(Lam=np.zeros((n, 3, 3)), dz=np.zeros(n))
+            if X is not None:
+                ins["X"] = f64(X, (3 * n, -1))
+                q.k = ins["X"].shape[1]
+                out["SX"] = np.zeros(ins["X"].shape, order="F")
+        for k, v in list(ins.items()) + list(out.items()):
+            setattr(q, k, v.ctypes.data_as(C.c_void_p))
+        _chk(lib().xm_ctx_rtr_probe(self.h, C.byref(q)))
+        scal = lambda sc: {k: getattr(sc, k) for k, _ in RtrScal._fields_}
+        out.update(f=q.f, rr=q.rr, product_kind=PRODUCT_KINDS.get(q.product_kind, "?"), nA=q.nA, nB=q.nB, wpad=bool(q.wpad), w_native=bool(q.w_native),
+                   split_k=q.split_k, sell_gather=q.sell_gather)
+        if p is not None:
+            out.update(pHp=q.pHp, rHp=q.rHp, HpHp=q.HpHp)
+        if tcg_init:
+            out["init_scal"] = scal(q.init_scal)
+        if cg_step is not None:
+            out.update(scal_out=scal(q.scal_out), rr_parts=q.rr_parts, partsB_out=out["partsB_out"][:q.nB].copy())
+        if cert:
+            out["dual"] = np.array(q.dual[:])
+        return {k: (np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v) for k, v in out.items()}
 
     def reprojection_errors(self, rot, t, P):
         """|r_e|^2 (unrobustified) of every observation in input order at (rot, t, P) -- the layouts of bundle_adjust -- with the
