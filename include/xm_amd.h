@@ -126,9 +126,19 @@ typedef struct {
     int32_t hess_f32;          /* 1: the Hessian products of the truncated CG read an fp32 copy of Q (rounded to nearest, made on the device at
                                   creation; loaded as fp32, accumulated in f64).  Gradient, cost, certificate, escalation line search and Lanczos stay
                                   on the f64 Q, so the stop test and the certificate are unchanged; only the tCG steps see the rounded operator.
-                                  Dense storage on one rank only: any other storage, n_gpus > 1, a communicator, or an entry of Q that is not
-                                  finite in fp32 gives XM_ERR_ARG.  0 (default): off */
+                                  Dense storage on one rank only (or XM_STORAGE_SCHUR with schur_dense_q = 1): any other storage, n_gpus > 1, a
+                                  communicator, or an entry of Q that is not finite in fp32 gives XM_ERR_ARG.  0 (default): off */
+    union {                    /* (anonymous: the slot keeps its old name reserved[0] as an alias, so callers that zero it by name still compile) */
+    int32_t schur_dense_q;     /* XM_STORAGE_SCHUR: 1 = the context also builds the dense 3n x 3n Q of utils/creatematrix.py on the device from its
+                                  observation lists (xm-code_amd/csrc/xm_schur_dense.hip) and EVERY product (xm_ctx_qw, the solve, the certificate)
+                                  goes through the dense dispatch: the general kernel, the half-traffic symmetric sweep by the usual rule (the
+                                  matrix is symmetric bit for bit), XM_FLAG_DEVICE_OUTER, and hess_f32 = 1, which is accepted together with it.
+                                  The lists stay: residuals, xm_ctx_recover_tp, the XM^2 calls, cleaning and bundle adjustment work unchanged, and
+                                  xm_ctx_set_edge_weights / xm_ctx_xm2_filter / xm_ctx_xm2_round rebuild Q (and the fp32 copy) on the device.
+                                  XM_ERR_ARG: the CG forms (schur_solver 2 or 3), n_gpus > 1, a communicator, more than 20000 cameras (28.8 GB of Q),
+                                  or a list that names a (camera, landmark) pair twice.  0 (default): off, nothing changes.  */
     int32_t reserved[1];
+    };
 } xm_tuning_t;
 
 typedef struct {
@@ -370,6 +380,19 @@ int xm_ctx_clean_observations(xm_ctx_t *ctx, const xm_clean_options_t *opt, uint
  * N^2).  rot: 3 x 3n column-major and scale: n as returned by xm_recover_rotations; t: 3 x n column-major (t[:, 0] = 0, the
  * anchor), p: 3 x n_landmarks column-major.  Uses the context's CURRENT observation weights. */
 int xm_ctx_recover_tp(xm_ctx_t *ctx, const double *rot, const double *scale, double *t, double *p);
+/* xm_tuning_t.schur_dense_q contexts: the context's CURRENT dense Q (after a re-weighting: the rebuilt one) to a host array, column-major,
+ * ldq >= 3n.  XM_ERR_ARG for a context that did not build one. */
+int xm_ctx_dense_q(xm_ctx_t *ctx, double *q, int64_t ldq);
+/* The reference's create_matrix (utils/creatematrix.py:51-339) in one call from host arrays, on the device, without solver state: cam / lm
+ * 0-based indices of the nobs observations, p nobs x 3 row-major camera-frame points, w weights (the arguments of an XM_STORAGE_SCHUR
+ * problem).  Q: 3n x 3n column-major, ldq >= 3n, symmetric bit for bit.  Abar (NULL: not wanted): (n-1+m) x 3n column-major, the matrix
+ * recover_XM multiplies with (camera rows -VT^-1 G^T, then one row per landmark, produced on the device 2048 landmarks at a time).  The limits
+ * of xm_tuning_t.schur_dense_q apply (20000 cameras, no (camera, landmark) pair named twice). */
+int xm_create_matrix(int64_t n, int64_t m, int64_t nobs, const int32_t *cam, const int32_t *lm, const double *p, const double *w, double *Q,
+                     int64_t ldq, double *Abar /* NULL: not wanted; (n-1+m) x 3n column-major */);
+/* constants of the device build: out[0] = cameras per LDS column window of the assembly kernel, out[1] = landmarks per panel of Abar,
+ * out[2] = the camera cap (host-only; tests derive their window-edge and multi-panel cases from them) */
+int xm_schur_dense_limits(int64_t out[3]);
 /* XM_STORAGE_SCHUR: how the reduced camera Laplacian VT = Q2_bar - V3_bar Q3^-1 V3_bar^T (utils/creatematrix.py:150-166) is applied inside a
  * product -- *uses_cg = 0: through its dense inverse (set-up O(N^3), 8 (N-1)^2 bytes; up to xm_tuning_t.schur_dense_max cameras), 1: by
  * preconditioned CG on the matrix-free VT (no N^2 array) -- and, for the CG form, stats = {products so far, inner CG iterations

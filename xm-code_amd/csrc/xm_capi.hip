@@ -269,6 +269,51 @@ int xm_ctx_recover_tp(xm_ctx_t *ctx, const double *rot, const double *scale, dou
     return XM_OK;
     XM_CATCH
 }
+int xm_ctx_dense_q(xm_ctx_t *ctx, double *q, int64_t ldq) {
+    XM_TRY
+    if (!ctx || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_dense_q: single-GPU contexts only");
+    ctx->impl->dense_q(q, ldq);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_create_matrix(int64_t n, int64_t m, int64_t nobs, const int32_t *cam, const int32_t *lm, const double *p, const double *w, double *Q,
+                     int64_t ldq, double *Abar) {
+    XM_TRY
+    if (!Q || ldq < 3 * n) throw xm::Error(XM_ERR_ARG, "xm_create_matrix: null Q or ldq < 3n");
+    if (n > xm::kSchurDenseQMaxCams) throw xm::Error(XM_ERR_ARG, "xm_create_matrix: more than " + std::to_string(xm::kSchurDenseQMaxCams) + " cameras");
+    require_device();
+    hipStream_t st = nullptr;
+    XM_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    double *dq = nullptr;
+    try {
+        xm::SchurSettings sc;
+        sc.solver = 1;
+        xm::SchurOp op(n, m, nobs, cam, lm, p, w, st, nullptr, sc);
+        if (op.names_a_pair_twice()) throw xm::Error(XM_ERR_ARG, "xm_create_matrix: the observation list names a (camera, landmark) pair twice");
+        const int64_t ld = xm_dense_ld(n);
+        XM_HIP_CHECK(hipMalloc((void **)&dq, (size_t)3 * n * (size_t)ld * sizeof(double)));
+        XM_HIP_CHECK(hipMemsetAsync(dq, 0, (size_t)3 * n * (size_t)ld * sizeof(double), st));
+        op.build_dense_q(dq, ld, Abar, st);
+        XM_HIP_CHECK(hipMemcpy2DAsync(Q, (size_t)ldq * sizeof(double), dq, (size_t)ld * sizeof(double), (size_t)3 * n * sizeof(double), (size_t)3 * n,
+                                      hipMemcpyDeviceToHost, st));
+        XM_HIP_CHECK(hipStreamSynchronize(st));
+    } catch (...) {
+        if (dq) (void)hipFree(dq);
+        (void)hipStreamDestroy(st);
+        throw;
+    }
+    (void)hipFree(dq);
+    (void)hipStreamDestroy(st);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_schur_dense_limits(int64_t out[3]) {
+    XM_TRY
+    if (!out) throw xm::Error(XM_ERR_ARG, "xm_schur_dense_limits: null output");
+    out[0] = xm::kSchurDenseQWinCams; out[1] = xm::kSchurAbarPanel; out[2] = xm::kSchurDenseQMaxCams;
+    return XM_OK;
+    XM_CATCH
+}
 int xm_ctx_schur_info(xm_ctx_t *ctx, int *uses_cg, int64_t stats[3], double *last_relres) {
     XM_TRY
     if (!ctx || !ctx->impl || !uses_cg) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_info: single-GPU context and a non-null output needed");

@@ -72,6 +72,8 @@ Settings Settings::resolve(const xm_tuning_t *t) {
     s.schur_pcg_hess_digits = z.schur_pcg_hess_digits;
     if (z.hess_f32 < 0 || z.hess_f32 > 1) throw Error(XM_ERR_ARG, "xm_tuning_t.hess_f32 must be 0 or 1");
     s.hess_f32 = z.hess_f32;
+    if (z.schur_dense_q < 0 || z.schur_dense_q > 1) throw Error(XM_ERR_ARG, "xm_tuning_t.schur_dense_q must be 0 or 1");
+    s.schur_dense_q = z.schur_dense_q;
     s.debug_drop_finalize = z.debug_drop_finalize > 0 ? z.debug_drop_finalize : -1;
     s.debug_peer_mute = z.debug_peer_mute;
     return s;

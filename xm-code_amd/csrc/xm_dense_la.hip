@@ -203,6 +203,12 @@ static void gemm_sub(int m, int n, int k, const double *A, int64_t lda, int ta, 
     hipLaunchKernelGGL(la_gemm_sub_kernel, g, dim3(256), 0, st, m, n, k, A, lda, ta, B, ldb, tb, C, ldc, lower_only);
 }
 
+void gemm_sub_device(int m, int n, int k, const double *A, int64_t lda, int ta, const double *B, int64_t ldb, int tb, double *C, int64_t ldc,
+                     int lower_only, hipStream_t st) {
+    gemm_sub(m, n, k, A, lda, ta, B, ldb, tb, C, ldc, lower_only, st);
+    check_launch("gemm_sub");
+}
+
 // A (device, column-major n x n, leading dimension ld, lower triangle read) is overwritten by its Cholesky factor L (lower; zeros above the
 // diagonal inside the 64 x 64 diagonal blocks, the other upper blocks untouched).  *info (device) is set to 1 when a pivot is not positive;
 // it is never cleared here.  Enqueued on st only: no host synchronisation.

@@ -25,6 +25,15 @@
 namespace xm {
 
 constexpr int64_t kSchurMaxCams = 40000;   // (N-1)^2 inverse + workspace = 3 x 8 N^2 bytes during set-up: 38 GB at the limit
+// Dense Q built on the device from the observation list (xm_tuning_t.schur_dense_q, xm_create_matrix; xm_schur_dense.hip).  At the cap the
+// padded 3N x 3N matrix is 28.8 GB, the two 3N x (N-1) work arrays (G^T and the camera rows of Abar) 9.6 GB each and VT^-1 3.2 GB: 51 GB
+// while Q is built, 32 GB afterwards (+ 14.4 GB for an fp32 copy)
+constexpr int64_t kSchurDenseQMaxCams = 20000;
+constexpr int kSchurDenseQWinCams = 512;   // column window of the assembly kernel in cameras: 12 doubles of LDS per camera (a 3 x 3 block of B D B^T
+                                           // and a 3-vector of G for each of the strip's three rows) = 48 KB per wavefront, three wavefronts on a CU's
+                                           // 160 KB.  Every window walks the camera's list again; measured at 8000 cameras / 5.4 M observations:
+                                           // 1024 cameras (one wavefront per CU) 113 ms, 512 cameras 66 ms
+constexpr int kSchurAbarPanel = 2048;      // landmark rows of Abar are produced and copied out this many at a time (a panel of 3N doubles per landmark)
 constexpr int kSchurAggCams = 64;          // two-level preconditioner of the CG form: cameras per aggregate (one wavefront, a lane per camera)
 constexpr int64_t kSchurMaxAggregates = 4096;   // ... and its coarse operator: the n_c x n_c inverse is at most 134 MB
 
@@ -47,6 +56,10 @@ void spd_substitute_device(int n, const double *L, int64_t ld, double *X, double
 void spd_inverse_layout(int n, const double *X, double *dst, int64_t ldd, hipStream_t st);
 // A (device, column-major n x n) -= q * u u^T  (u: device, n doubles)
 void rank1_sub_device(int n, double *A, const double *u, double q, hipStream_t st);
+// C[m x n] -= opA(A)[m x k] * opB(B)[k x n] on the f64 matrix cores (la_gemm_sub_kernel; ta / tb: 1 = transposed; lower_only: the tiles on and
+// below the diagonal).  Column-major, enqueued on st only.
+void gemm_sub_device(int m, int n, int k, const double *A, int64_t lda, int ta, const double *B, int64_t ldb, int tb, double *C, int64_t ldc,
+                     int lower_only, hipStream_t st);
 
 struct SchurSettings {          // from xm_tuning_t (Settings::resolve)
     bool host_assembly = false; // assemble the reduced camera Laplacian on the host (the reference's route, utils/creatematrix.py:137-260; tests)
@@ -104,6 +117,11 @@ public:
                           cam_lm_.p, lm_cam_.p, ldeg_.p, obs_cam_.p, obs_lm_.p, cam_w_.p, lm_w_.p, obs_p_.p};
     }
     const std::vector<int32_t> &slot_of() const { return slot_of_; }   // landmark -> slot
+    // The dense Q of the CURRENT weights (xm_schur_dense.hip): Q (device, zero-filled padding, 3n rows of ldq doubles) <- the symmetric 3N x 3N
+    // matrix in the dense kernels' layout, bit-for-bit symmetric.  abar (host, may be null): the (n-1+m) x 3n column-major matrix of
+    // utils/creatematrix.py:283-311.  Needs the dense inverse of VT (not the CG form) and a list without a (camera, landmark) pair named twice.
+    void build_dense_q(double *Q, int64_t ldq, double *abar, hipStream_t st);
+    bool names_a_pair_twice() const { return has_dup_; }
 
 private:
     int64_t n_ = 0, m_ = 0, nobs_ = 0, nred_ = 0, ldv_ = 0;   // nred = cameras of the padded (N-1) system / 3
@@ -136,7 +154,8 @@ private:
     // weight-dependent factors assembled on the device (set_weights_device); the host version serves lists with duplicate (camera, landmark) pairs
     DevBuf<int64_t> pos_c_dev_, dpos_l_dev_;
     DevBuf<double> w_in_, q2_;
-    bool dup_pairs_ = false;
+    bool dup_pairs_ = false, has_dup_ = false;   // has_dup_: what the list says; dup_pairs_: the host path is taken (also forced by host_assembly)
+    DevBuf<int32_t> slot_dev_;                   // landmark -> slot on the device (build_dense_q with abar)
     SchurSettings cfg_;
     std::vector<int64_t> hub_lm_, hub_obs_ptr_, hub_obs_;
     void set_weights_device(const double *w, hipStream_t st);

@@ -874,6 +874,7 @@ SchurOp::SchurOp(int64_t n, int64_t n_landmarks, int64_t nobs, const int32_t *ca
                 if (seen[(size_t)b] == l) { dup_pairs_ = true; break; }
                 seen[(size_t)b] = l;
             }
+        has_dup_ = dup_pairs_;
         if (cfg_.host_assembly) dup_pairs_ = true;
     }
     hub_lm_.clear(); hub_obs_ptr_.assign(1, 0); hub_obs_.clear();   // heavy landmarks: their observations (input indices), for the rank-1 terms

@@ -44,6 +44,7 @@ struct Settings {
     int schur_solver = 0;                 // 0 by size | 1 dense inverse of the reduced camera Laplacian | 2 preconditioned CG inside the product
                                           // (Jacobi) | 3 CG with the two-level preconditioner
     int64_t schur_dense_max = 20000;
+    int schur_dense_q = 0;                // 1: a matrix-free context also builds the dense Q on the device and multiplies with it (xm_schur_dense.hip)
     int hess_f32 = 0;                     // 1: the tCG Hessian products of a dense single-rank context read an fp32 copy of Q (dQ32_)
     static Settings resolve(const xm_tuning_t *t);
 };
@@ -216,6 +217,7 @@ public:
     double xm2_filter(const double *rot, const double *scale, double pct, int64_t *removed, double *w_out);
     const std::vector<double> &weights() const { return w_cur_; }
     int64_t n_landmarks() const;
+    void dense_q(double *q, int64_t ldq);   // xm_tuning_t.schur_dense_q: the current dense Q -> host, column-major
     bool schur_info(int64_t out[3], double *relres) const;   // matrix-free storage with the CG form: products, inner iterations, products at the cap
     int schur_precond(int64_t *aggregates, int *block) const; // its preconditioner: -1 no CG form, 0 Jacobi, 1 two-level (aggregates, cameras per aggregate)
 
@@ -242,6 +244,7 @@ private:
     std::unique_ptr<SellMatrix> sell_;   // large block-sparse Q: sliced-ELL layout (xm_sell.h); the CSR arrays stay for the fallback kernels
     int sell_gm_ = 0;
     std::unique_ptr<SchurOp> schur_;     // XM_STORAGE_SCHUR: matrix-free Q (xm_schur.h)
+    bool schur_dense_ = false;           // xm_tuning_t.schur_dense_q: dQ_ was built from schur_'s lists and storage_ is XM_STORAGE_DENSE for the products
     // XM^2 edge description (attach_edges)
     int64_t ne_ = 0;
     DevBuf<int32_t> ei_, ej_, inc_edge_;

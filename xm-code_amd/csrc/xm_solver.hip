@@ -229,8 +229,17 @@ void Context::init(const xm_problem_t &prob_in) {
     if (3 * prob.n > 2000000000LL) throw Error(XM_ERR_ARG, "n too large");
     n_ = prob.n;
     storage_ = prob.storage;
+    schur_dense_ = false;
+    if (cfg_.schur_dense_q && storage_ == XM_STORAGE_SCHUR) {   // the dense Q built on the device from the observation list (xm_schur_dense.hip)
+        if (cfg_.schur_solver == 2 || cfg_.schur_solver == 3)
+            throw Error(XM_ERR_ARG, "xm_tuning_t.schur_dense_q needs the dense inverse of the reduced camera Laplacian (schur_solver 0 or 1, not the CG forms)");
+        if (world > 1 || comm_->active()) throw Error(XM_ERR_ARG, "xm_tuning_t.schur_dense_q needs a single-rank context (no communicator, n_gpus <= 1)");
+        if (n_ > kSchurDenseQMaxCams || n_ > cfg_.schur_dense_max)
+            throw Error(XM_ERR_ARG, "xm_tuning_t.schur_dense_q: more than " + std::to_string(std::min<int64_t>(kSchurDenseQMaxCams, cfg_.schur_dense_max)) + " cameras");
+        schur_dense_ = true;
+    }
     if (cfg_.hess_f32) {   // (before anything is allocated)
-        if (storage_ != XM_STORAGE_DENSE) throw Error(XM_ERR_ARG, "xm_tuning_t.hess_f32 needs XM_STORAGE_DENSE (storage " + std::to_string(storage_) + ")");
+        if (storage_ != XM_STORAGE_DENSE && !schur_dense_) throw Error(XM_ERR_ARG, "xm_tuning_t.hess_f32 needs XM_STORAGE_DENSE (storage " + std::to_string(storage_) + ")");
         if (world > 1 || comm_->active()) throw Error(XM_ERR_ARG, "xm_tuning_t.hess_f32 needs a single-rank context (no communicator, n_gpus <= 1)");
     }
     XM_HIP_CHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
@@ -354,6 +363,17 @@ void Context::init(const xm_problem_t &prob_in) {
         sc.pcg_first = cfg_.schur_pcg_first; sc.pcg_hess_digits = cfg_.schur_pcg_hess_digits;
         schur_.reset(new SchurOp(n_, prob.n_landmarks, prob.nobs, prob.obs_cam, prob.obs_lm, prob.obs_p, prob.obs_w, st_, comm_.get(), sc));
         w_cur_.assign(prob.obs_w, prob.obs_w + prob.nobs);
+        if (schur_dense_) {   // the context keeps its SchurOp (lists, residuals, recovery, cleaning, bundle adjustment) and owns the dense Q beside it:
+                              // from here on every product takes the dense dispatch
+            if (schur_->names_a_pair_twice())
+                throw Error(XM_ERR_ARG, "xm_tuning_t.schur_dense_q: the observation list names a (camera, landmark) pair twice (the device assembly assumes a landmark names a camera once)");
+            const size_t rows = (size_t)3 * nloc_;
+            XM_HIP_CHECK(hipMalloc((void **)&dQ_, rows * (size_t)ld_ * sizeof(double)));
+            ownQ_ = true;
+            XM_HIP_CHECK(hipMemsetAsync(dQ_, 0, rows * (size_t)ld_ * sizeof(double), st_));
+            schur_->build_dense_q(dQ_, ld_, nullptr, st_);
+            storage_ = XM_STORAGE_DENSE;
+        }
     } else {
         throw Error(XM_ERR_ARG, "unknown storage");
     }
@@ -1880,7 +1900,7 @@ void Context::attach_edges(int64_t ne, const int32_t *ei, const int32_t *ej, con
 }
 
 void Context::edge_residuals(double *res) {
-    if (storage_ == XM_STORAGE_SCHUR) {   // matrix-free: the observations are the edges (one residual per observation, input order)
+    if (schur_) {   // matrix-free: the observations are the edges (one residual per observation, input order)
         if (!solved_) throw Error(XM_ERR_ARG, "edge_residuals: the context holds no solution yet");
         if (!res) throw Error(XM_ERR_ARG, "edge_residuals: null output");
         xm_options_t opt;
@@ -1913,7 +1933,7 @@ void Context::edge_residuals(double *res) {
 // residuals of a RECOVERED rank-3 solution on the device: the product input is W_i = s_i * R_i^T (camera i's 3 x 3 record)
 const double *Context::residuals_recovered_device(const double *rot, const double *scale) {
     if (!rot || !scale) throw Error(XM_ERR_ARG, "edge_residuals_recovered: null argument");
-    if (storage_ != XM_STORAGE_SCHUR && !ei_.p) throw Error(XM_ERR_ARG, "edge_residuals_recovered: no edges attached");
+    if (!schur_ && !ei_.p) throw Error(XM_ERR_ARG, "edge_residuals_recovered: no edges attached");
     // Under a row partition every rank holds the whole edge list and gets the whole recovered solution from the caller: each
     // evaluates all residuals (and, in xm2_filter, the same order statistic) itself -- identical numbers everywhere, no exchange.
     constexpr int OP = pitch_of(3);
@@ -1927,7 +1947,7 @@ const double *Context::residuals_recovered_device(const double *rot, const doubl
     DevBuf<double> &dW = recW_;
     if (dW.count < hW.size()) dW.alloc(hW.size());
     to_dev(dW.p, hW.data(), hW.size() * sizeof(double));
-    if (storage_ == XM_STORAGE_SCHUR) {
+    if (schur_) {
         xm_options_t opt;
         std::memset(&opt, 0, sizeof(opt));
         const xm_options_t *keep = opt_;
@@ -1947,7 +1967,7 @@ const double *Context::residuals_recovered_device(const double *rot, const doubl
 void Context::edge_residuals_recovered(const double *rot, const double *scale, double *res) {
     if (!res) throw Error(XM_ERR_ARG, "edge_residuals_recovered: null output");
     const double *r = residuals_recovered_device(rot, scale);
-    const int64_t ne = (storage_ == XM_STORAGE_SCHUR) ? schur_->nobs() : ne_;
+    const int64_t ne = schur_ ? schur_->nobs() : ne_;
     if (ne > 0) to_host(res, r, (size_t)ne * sizeof(double));
     XM_HIP_CHECK(hipStreamSynchronize(st_));
     if (comm_->active()) comm_->host_barrier();   // nobody runs ahead into a collective while a peer still (re)allocates here
@@ -1979,7 +1999,7 @@ static double radix_select(const double *x, int64_t n, int64_t k, unsigned int *
 
 double Context::xm2_filter(const double *rot, const double *scale, double pct, int64_t *removed, double *w_out) {
     if (!(pct >= 0.0 && pct <= 100.0)) throw Error(XM_ERR_ARG, "xm2_filter: percentile must be in [0, 100]");
-    const int64_t ne = (storage_ == XM_STORAGE_SCHUR) ? schur_->nobs() : ne_;
+    const int64_t ne = schur_ ? schur_->nobs() : ne_;
     if ((int64_t)w_cur_.size() != ne || ne < 1) throw Error(XM_ERR_ARG, "xm2_filter: the context does not know its edge weights (view-graph / matrix-free storage, or call xm_ctx_set_edge_weights first)");
     const double *res = residuals_recovered_device(rot, scale);
     if (ew_.count < (size_t)ne) ew_.alloc((size_t)ne);
@@ -2018,11 +2038,11 @@ double Context::xm2_filter(const double *rot, const double *scale, double pct, i
 }
 
 void Context::recover_tp(const double *rot, const double *scale, double *t, double *p) {
-    if (storage_ != XM_STORAGE_SCHUR || !schur_) throw Error(XM_ERR_ARG, "recover_tp: needs a matrix-free context (XM_STORAGE_SCHUR): the translations and landmarks are functions of the observations");
+    if (!schur_) throw Error(XM_ERR_ARG, "recover_tp: needs a matrix-free context (XM_STORAGE_SCHUR): the translations and landmarks are functions of the observations");
     schur_->recover_tp(rot, scale, t, p, st_);
 }
 void Context::bundle_adjust(const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out) {
-    if (storage_ != XM_STORAGE_SCHUR || !schur_)
+    if (!schur_)
         throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
     if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: single-rank contexts only");
     BaSettings c = cfg;
@@ -2030,7 +2050,7 @@ void Context::bundle_adjust(const BaSettings &cfg, double *rot, double *t, doubl
     xm::bundle_adjust(*schur_, c, rot, t, p, out, st_);
 }
 void Context::ba_probe(const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q) {
-    if (storage_ != XM_STORAGE_SCHUR || !schur_)
+    if (!schur_)
         throw Error(XM_ERR_ARG, "xm_ctx_ba_probe: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
     if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_ba_probe: single-rank contexts only");
     BaSettings c = cfg;
@@ -2038,18 +2058,26 @@ void Context::ba_probe(const BaSettings &cfg, const double *rot, const double *t
     xm::ba_probe(*schur_, c, rot, t, p, q, st_);
 }
 void Context::reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr) {
-    if (storage_ != XM_STORAGE_SCHUR || !schur_)
+    if (!schur_)
         throw Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
     if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: single-rank contexts only");
     xm::reprojection_errors(*schur_, rot, t, p, sqerr, cfg_.watchdog_s, st_);
 }
 void Context::clean_observations(const CleanSettings &cfg, uint8_t *keep, int32_t *cam_index, int32_t *lm_index, CleanOutcome &out) {
-    if (storage_ != XM_STORAGE_SCHUR || !schur_)
+    if (!schur_)
         throw Error(XM_ERR_ARG, "xm_ctx_clean_observations: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no observations");
     if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_clean_observations: single-rank contexts only");
     CleanSettings c = cfg;
     c.watchdog_s = cfg_.watchdog_s;
     xm::clean_observations(*schur_, c, keep, cam_index, lm_index, out, st_);
+}
+void Context::dense_q(double *q, int64_t ldq) {
+    if (!schur_dense_ || !dQ_) throw Error(XM_ERR_ARG, "xm_ctx_dense_q: the context holds no dense Q built from observations (xm_tuning_t.schur_dense_q)");
+    if (!q || ldq < 3 * n_) throw Error(XM_ERR_ARG, "xm_ctx_dense_q: null output or ldq < 3n");
+    // symmetric bit for bit: the row-major device matrix is its own column-major image
+    XM_HIP_CHECK(hipMemcpy2DAsync(q, (size_t)ldq * sizeof(double), dQ_, (size_t)ld_ * sizeof(double), (size_t)3 * n_ * sizeof(double), (size_t)3 * n_,
+                                  hipMemcpyDeviceToHost, st_));
+    XM_HIP_CHECK(hipStreamSynchronize(st_));
 }
 int64_t Context::n_landmarks() const { return schur_ ? schur_->n_landmarks() : 0; }
 bool Context::schur_info(int64_t out[3], double *relres) const {
@@ -2079,9 +2107,13 @@ void Context::refresh_q32() {
 }
 
 void Context::set_edge_weights(const double *w) {
-    if (storage_ == XM_STORAGE_SCHUR) {
+    if (schur_) {
         schur_->set_weights(w, st_);
         w_cur_.assign(w, w + schur_->nobs());
+        if (schur_dense_) {   // Q follows the factors on the device; nothing is uploaded
+            schur_->build_dense_q(dQ_, ld_, nullptr, st_);
+            if (dQ32_) refresh_q32();
+        }
         return;
     }
     if (!ei_.p) throw Error(XM_ERR_ARG, "set_edge_weights: no edges attached");

@@ -106,6 +106,8 @@ Team::Team(const xm_problem_t &prob, int n_gpus, int gpu_map) : p_(new Impl) {
     for (int r = 0; r < n_gpus; ++r) t.device[(size_t)r] = (gpu_map == 1) ? 0 : r;
     const Settings cfg = Settings::resolve(prob.tuning);
     if (cfg.hess_f32) throw Error(XM_ERR_ARG, "xm_tuning_t.hess_f32 needs a single-rank context (n_gpus = " + std::to_string(n_gpus) + ")");
+    if (prob.storage == XM_STORAGE_SCHUR && cfg.schur_dense_q)
+        throw Error(XM_ERR_ARG, "xm_tuning_t.schur_dense_q needs a single-rank context (n_gpus = " + std::to_string(n_gpus) + ")");
     if (prob.storage == XM_STORAGE_SCHUR && cfg.schur_solver == 3)
         throw Error(XM_ERR_ARG, "xm_tuning_t.schur_solver = 3 (two-level preconditioner of the CG form) needs a single-rank context (n_gpus = " + std::to_string(n_gpus) + ")");
     // device-side waits give up after min(watchdog / 3, 30 s): long enough for a peer that lags, short enough not to look hung, and well

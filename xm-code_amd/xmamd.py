@@ -37,6 +37,7 @@ EXPORTS = [
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
     "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_ba_aggregate_plan", "xm_ctx_ba_probe",
     "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe",
+    "xm_ctx_dense_q", "xm_create_matrix", "xm_schur_dense_limits",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -53,7 +54,7 @@ class Tuning(C.Structure):
                                          "overlap_min_mb", "cert_dense_rows", "lanczos_mmax", "lanczos_restarts", "watchdog_s", "balance",
                                          "exchange", "split_k", "sell_wpad", "exchange_fence", "schur_host_assembly", "schur_trace",
                                          "schur_solver", "schur_dense_max", "debug_drop_finalize", "debug_peer_mute", "schur_pcg_first",
-                                         "schur_pcg_hess_digits", "hess_f32")] + [("reserved", C.c_int32 * 1)]
+                                         "schur_pcg_hess_digits", "hess_f32", "schur_dense_q")]
 
 
 class Problem(C.Structure):
@@ -200,6 +201,9 @@ def lib():
         L.xm_ctx_clean_observations.argtypes = [C.c_void_p, C.POINTER(CleanOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CleanResult)]
         L.xm_ctx_reprojection_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_transport.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
+        L.xm_ctx_dense_q.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.xm_create_matrix.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.xm_schur_dense_limits.argtypes = [C.c_void_p]
         L.xm_ctx_schur_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_double)]
         L.xm_ctx_schur_precond_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
         L.xm_schur_aggregate_plan.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -670,6 +674,50 @@ def recover_rotations(R, s, variant=None, reps=0):
     return (np.ascontiguousarray(rot), sc, neg.value) + ((ms.value,) if reps > 0 else ())
 
 
+def schur_dense_limits():
+    """(cameras per LDS column window of the assembly kernel, landmarks per panel of Abar, camera cap) of the device build of the dense Q"""
+    out = (C.c_int64 * 3)()
+    _chk(lib().xm_schur_dense_limits(out))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def create_matrix_arrays(cam, lm, p, w, n=None, m=None, abar=True):
+    """dense Q (3n x 3n) and, with abar=True, Abar ((n-1+m) x 3n) of the reference's create_matrix from 0-based observation arrays, built on
+    the device (xm_create_matrix).  Returns (Q, Abar or None)."""
+    require_gpu()
+    cam = np.ascontiguousarray(cam, dtype=np.int32).reshape(-1); lm = np.ascontiguousarray(lm, dtype=np.int32).reshape(-1)
+    p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3); w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+    assert cam.size == lm.size == w.size == p.shape[0]
+    n = int(cam.max()) + 1 if n is None else int(n)
+    m = int(lm.max()) + 1 if m is None else int(m)
+    Q = np.zeros((3 * n, 3 * n), order="F")
+    A = np.zeros((n - 1 + m, 3 * n), order="F") if abar else None
+    _chk(lib().xm_create_matrix(n, m, cam.size, cam.ctypes.data_as(C.c_void_p), lm.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p),
+                                w.ctypes.data_as(C.c_void_p), Q.ctypes.data_as(C.c_void_p), 3 * n, A.ctypes.data_as(C.c_void_p) if abar else None))
+    return Q, A
+
+
+def _write_bin(fn, M):
+    """the reference's .bin matrix (utils/io.py): int32 rows, int32 cols, float64 column-major"""
+    M = np.asfortranarray(M, dtype=np.float64)
+    with open(fn, "wb") as f:
+        np.array(M.shape, dtype=np.int32).tofile(f)
+        f.write(M.tobytes(order="F"))
+
+
+def create_matrix(weight, edges, landmarks, output_path, abar=True):
+    """drop-in for the reference's utils/creatematrix.py:create_matrix on the device: weight (nobs), edges (nobs x 2, 1-based camera and
+    landmark), landmarks (nobs x 3 camera-frame points); writes Q.bin and (abar=True) Abar.bin into output_path in the reference's format and
+    returns (Q, Abar or None)."""
+    edges = np.asarray(edges)
+    Q, A = create_matrix_arrays(edges[:, 0].astype(np.int64) - 1, edges[:, 1].astype(np.int64) - 1, landmarks, weight, abar=abar)
+    os.makedirs(output_path, exist_ok=True)
+    _write_bin(os.path.join(output_path, "Q.bin"), Q)
+    if abar:
+        _write_bin(os.path.join(output_path, "Abar.bin"), A)
+    return Q, A
+
+
 # ------------------------------------------------------------------------------------------------ context API
 class Context:
     """Q resident in HBM; solve() == the reference's staircase (XM_main.cu:180 / :312 / :35)."""
@@ -753,6 +801,12 @@ class Context:
         _chk(lib().xm_ctx_schur_precond_info(self.h, C.byref(kind), C.byref(na), C.byref(blk)))
         return dict(cg=bool(u.value), products=int(st[0]), inner_iters=int(st[1]), capped=int(st[2]), last_relres=rr.value,
                     precond={0: "jacobi", 1: "two-level"}.get(kind.value), aggregates=int(na.value))
+
+    def dense_q(self):
+        """the context's current dense Q (3n x 3n) built on the device from its observation lists (tuning schur_dense_q=1; xm_ctx_dense_q)"""
+        Q = np.zeros((3 * self.n, 3 * self.n), order="F")
+        _chk(lib().xm_ctx_dense_q(self.h, Q.ctypes.data_as(C.c_void_p), 3 * self.n))
+        return Q
 
     def sell_wpad(self):
         """True when the tCG of the last solved rank read its product input at the 128-byte record pitch (xm_ctx_sell_wpad)"""
