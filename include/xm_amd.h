@@ -373,6 +373,85 @@ int xm_clean_observations(int64_t n, int64_t m, int64_t nobs, const int32_t *cam
                           const xm_clean_options_t *opt, uint8_t *keep, int32_t *cam_index, int32_t *lm_index, xm_clean_result_t *res);
 int xm_ctx_clean_observations(xm_ctx_t *ctx, const xm_clean_options_t *opt, uint8_t *keep, int32_t *cam_index, int32_t *lm_index,
                               xm_clean_result_t *res);
+/* ---- Flagging observations that disagree with pairwise relative rotations: the block the reference's last pipeline script marks "YOUR OWN
+ * FILTER HERE" (5_test_ceres.py:316-431), which runs in front of checklandmarks and create_matrix, as a query on the device.
+ * Input: n cameras, m landmarks, nobs observations in input order: cam[e], lm[e] 0-based, p[e] = 3 doubles, the camera-frame point; npairs
+ * pairs (pi[k], pj[k], R_k), R_k a 3x3 rotation, row-major (9 doubles per pair).
+ * Per pair (i, j, R), with src the points of camera i and dst those of camera j on their common landmarks, in increasing landmark order
+ * (k of them):
+ *   1. fewer than min_joint (20) common landmarks (or none at all): the pair is skipped.
+ *   2. src_avg, dst_avg = the trimmed mean of every coordinate, `trim` = 0.05 cut from each end: scipy.stats.trim_mean, lo = int(trim * k),
+ *      the mean of the sorted values [lo, k - lo).
+ *   3. src_dis, dst_dis = the distances to those means.
+ *   4. keep = src_dis < P(src_dis, dist_pct = 90) & dst_dis < P(dst_dis, dist_pct).  P is numpy's default percentile: position
+ *      (k - 1) * (q / 100) in the sorted values, a + (b - a) t between the two neighbours, b - (b - a)(1 - t) for t >= 1/2 (numpy's _lerp).
+ *      With t = 0 the threshold is an order statistic itself, bit for bit: the decision is a rank.
+ *   5. src_avg, dst_avg again over the kept points.
+ *   6. scale1 = the trimmed mean of |dst_n - dst_avg| over the kept points, scale2 likewise for src.
+ *   7. src <- src / scale2 * scale1, all k points.
+ *   8. translation = the trimmed mean, per coordinate, of dst - R src.
+ *   9. err = |R src + translation - dst| / scale1.
+ *  10. thr = max(mad_factor * median(err), P(err, err_pct = 95)); a point with err - thr > 0 is flagged at BOTH of its observations.
+ * Output (host arrays): count[e] = the number of pairs that flagged observation e (a pair listed twice counts twice; (j, i, R^T) next to
+ * (i, j, R) is a pair of its own); outlier[e] = count[e] >= min_flags (the reference: error_sum > 0, min_flags = 1).  stats (npairs entries
+ * or NULL): what the pair found.  The option fields are literal (0 is a value): XM_PAIR_OPTIONS_INIT holds the reference's constants.
+ * Where this differs from the reference, on purpose:
+ *   (a) the reference stores ROW NUMBERS as the values of its sparse visibility matrix and tests them for truth, so observation row 0 never
+ *       takes part in any pair.  Here it takes part; XM_PAIR_SKIP_ROW0 reproduces the reference.
+ *   (b) a (camera, landmark) pair named twice is summed into a wrong row number by the reference's coo_matrix -> csr; here it is XM_ERR_ARG.
+ *   (c) the reference computes error_angle and percentage and uses neither; percentage (the share of points with err < 0.05) is kept as a
+ *       diagnostic of the pair.
+ *   (d) the front end's translation of a pair is never read by the reference, so it is not an input.
+ *   (e) the reference visits the pairs i < j of its pose table; here every listed pair is visited, in any order.
+ * A pair with scale2 == 0, no kept point or a value that is not finite (scale1, scale2, translation, any err) flags nothing and has status
+ * XM_PAIR_DEGENERATE.  XM_ERR_ARG: a pair with pi == pj, an index out of range, nobs >= 2^31, a struct_size that is not sizeof, a negative
+ * option, a percentile above 100, trim >= 0.5, unknown flags, null arrays.
+ * On the device: the list is indexed by camera on the host inside the call; one workgroup per pair intersects the two sorted lists, and
+ * every order statistic comes from a sort in LDS, every sum from a fixed tree over the sorted range, all in f64: two calls give the same
+ * bits in every output, and count does not depend on the order of the input list.  Joint sets above xm_pair_filter_limits()[0] points take
+ * the same code through a global-memory workspace.  Needs no context (it runs before the list is clean enough to create one). */
+#define XM_PAIR_SKIP_ROW0   1u
+#define XM_PAIR_USED        0
+#define XM_PAIR_TOO_FEW     1
+#define XM_PAIR_DEGENERATE  2
+typedef struct {
+    uint32_t struct_size;
+    int32_t min_joint;         /* 20 */
+    int32_t min_flags;         /* 1 */
+    uint32_t flags;            /* XM_PAIR_SKIP_ROW0 */
+    double trim;               /* 0.05 */
+    double dist_pct;           /* 90 */
+    double err_pct;            /* 95 */
+    double mad_factor;         /* 3 */
+} xm_pair_options_t;
+#define XM_PAIR_OPTIONS_INIT { (uint32_t)sizeof(xm_pair_options_t), 20, 1, 0u, 0.05, 90.0, 95.0, 3.0 }
+typedef struct {
+    int32_t n_joint;           /* common landmarks */
+    int32_t n_kept;            /* points that pass step 4 */
+    int32_t n_flagged;         /* points flagged (each at two observations) */
+    int32_t status;            /* XM_PAIR_USED / XM_PAIR_TOO_FEW / XM_PAIR_DEGENERATE */
+    double scale1, scale2;
+    double translation[3];
+    double median, p95;        /* of err (p95: at err_pct) */
+    double percentage;         /* share of the points with err < 0.05 */
+} xm_pair_stat_t;
+typedef struct {
+    uint32_t struct_size;
+    uint32_t reserved;
+    int64_t pairs_used, pairs_skipped /* too few */, pairs_degenerate;
+    int64_t nobs_flagged;      /* observations with outlier[e] = 1 */
+    int64_t max_joint;         /* largest number of common landmarks over the listed pairs */
+    int64_t pairs_on_workspace_path;
+    double seconds_index;      /* host: index + upload */
+    double seconds_kernels;
+    double seconds_download;
+} xm_pair_result_t;
+int xm_pair_filter(int64_t n, int64_t m, int64_t nobs, const int32_t *cam, const int32_t *lm, const double *p, int64_t npairs, const int32_t *pi,
+                   const int32_t *pj, const double *R /* 9 per pair */, const xm_pair_options_t *opt, int32_t *count, uint8_t *outlier,
+                   xm_pair_stat_t *stats /* npairs or NULL */, xm_pair_result_t *res);
+/* out[0]: largest joint set that is sorted in LDS; out[1]: threads per workgroup; out[2]: workgroups of the workspace path; out[3]: largest
+ * joint set of the small LDS instantiation (every pair starts there) */
+int xm_pair_filter_limits(int64_t out[4]);
 /* Translations and landmarks of a solution: the last step of utils/recoversolution.py:recover_XM (lines 77-86,
  * ybar_est = Abar @ sR_real.T; t_est = [0 | first N-1 columns], p_est = the rest) for an XM_STORAGE_SCHUR context.  The reference
  * needs the dense (N-1+M) x 3N matrix Abar.bin that create_matrix writes (creatematrix.py:283-311; 80 GB at Final-13682 with 800 k

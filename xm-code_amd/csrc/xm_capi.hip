@@ -10,6 +10,7 @@
 
 #include "xm_ba.h"
 #include "xm_clean.h"
+#include "xm_pair.h"
 #include "xm_schur.h"
 #include "xm_sell.h"
 #include "xm_symw.h"
@@ -544,6 +545,48 @@ int xm_ctx_clean_observations(xm_ctx_t *ctx, const xm_clean_options_t *opt, uint
     xm::CleanOutcome r;
     ctx->impl->clean_observations(c, keep, cam_index, lm_index, r);
     give_clean(res, r);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_pair_filter(int64_t n, int64_t m, int64_t nobs, const int32_t *cam, const int32_t *lm, const double *p, int64_t npairs, const int32_t *pi,
+                   const int32_t *pj, const double *R, const xm_pair_options_t *opt, int32_t *count, uint8_t *outlier, xm_pair_stat_t *stats,
+                   xm_pair_result_t *res) {
+    XM_TRY
+    const std::string w("xm_pair_filter");
+    if (!opt || !res) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (opt->struct_size != sizeof(xm_pair_options_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_pair_options_t.struct_size is not sizeof(xm_pair_options_t)");
+    if (res->struct_size != sizeof(xm_pair_result_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_pair_result_t.struct_size is not sizeof(xm_pair_result_t)");
+    if (opt->min_joint < 0 || opt->min_flags < 0 || !(opt->trim >= 0.0) || !(opt->dist_pct >= 0.0) || !(opt->err_pct >= 0.0) || !(opt->mad_factor >= 0.0))
+        throw xm::Error(XM_ERR_ARG, w + ": negative option");
+    if (!(opt->trim < 0.5)) throw xm::Error(XM_ERR_ARG, w + ": trim must stay below 0.5");
+    if (!(opt->dist_pct <= 100.0) || !(opt->err_pct <= 100.0)) throw xm::Error(XM_ERR_ARG, w + ": a percentile above 100");
+    if (opt->flags & ~XM_PAIR_SKIP_ROW0) throw xm::Error(XM_ERR_ARG, w + ": unknown flag");
+    if (n < 0 || m < 0 || nobs < 0 || npairs < 0) throw xm::Error(XM_ERR_ARG, w + ": negative size");
+    if (n >= ((int64_t)1 << 31) || m >= ((int64_t)1 << 31) || nobs >= ((int64_t)1 << 31) || npairs >= ((int64_t)1 << 31))
+        throw xm::Error(XM_ERR_ARG, w + ": cameras, landmarks, observations and pairs must each stay below 2^31");
+    if (nobs > 0 && (!cam || !lm || !p || !count || !outlier)) throw xm::Error(XM_ERR_ARG, w + ": null observation or output arrays");
+    if (npairs > 0 && (!pi || !pj || !R)) throw xm::Error(XM_ERR_ARG, w + ": null pair arrays");
+    xm::PairSettings c;
+    c.min_joint = opt->min_joint; c.min_flags = opt->min_flags; c.skip_row0 = (opt->flags & XM_PAIR_SKIP_ROW0) != 0;
+    c.trim = opt->trim; c.dist_pct = opt->dist_pct; c.err_pct = opt->err_pct; c.mad_factor = opt->mad_factor;
+    require_device();
+    if (const char *e = std::getenv("XM_WATCHDOG_S")) { const double v = std::atof(e); if (v > 0) c.watchdog_s = v; }
+    xm::PairOutcome r;
+    xm::pair_filter_host(n, m, nobs, cam, lm, p, npairs, pi, pj, R, c, count, outlier, stats, r);
+    xm_pair_result_t out;
+    std::memset(&out, 0, sizeof(out));
+    out.struct_size = sizeof(xm_pair_result_t);
+    out.pairs_used = r.pairs_used; out.pairs_skipped = r.pairs_skipped; out.pairs_degenerate = r.pairs_degenerate; out.nobs_flagged = r.nobs_flagged;
+    out.max_joint = r.max_joint; out.pairs_on_workspace_path = r.pairs_on_workspace_path;
+    out.seconds_index = r.seconds_index; out.seconds_kernels = r.seconds_kernels; out.seconds_download = r.seconds_download;
+    *res = out;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_pair_filter_limits(int64_t out[4]) {
+    XM_TRY
+    if (!out) throw xm::Error(XM_ERR_ARG, "xm_pair_filter_limits: null output");
+    out[0] = xm::kPairLdsJoint; out[1] = xm::kPairThreads; out[2] = xm::kPairWsGroups; out[3] = xm::kPairSmallJoint;
     return XM_OK;
     XM_CATCH
 }

@@ -38,6 +38,7 @@ EXPORTS = [
     "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_ba_aggregate_plan", "xm_ctx_ba_probe",
     "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe",
     "xm_ctx_dense_q", "xm_create_matrix", "xm_schur_dense_limits",
+    "xm_pair_filter", "xm_pair_filter_limits",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -142,6 +143,29 @@ class CleanResult(C.Structure):    # xm_clean_result_t
                                          "cams_off_component", "lms_off_component")] + [("first_camera", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PairOptions(C.Structure):    # xm_pair_options_t; the defaults are the reference's constants (XM_PAIR_OPTIONS_INIT)
+    _fields_ = [("struct_size", C.c_uint32), ("min_joint", C.c_int32), ("min_flags", C.c_int32), ("flags", C.c_uint32), ("trim", C.c_double),
+                ("dist_pct", C.c_double), ("err_pct", C.c_double), ("mad_factor", C.c_double)]
+
+    def __init__(self, min_joint=20, min_flags=1, flags=0, trim=0.05, dist_pct=90.0, err_pct=95.0, mad_factor=3.0):
+        super().__init__(C.sizeof(PairOptions), min_joint, min_flags, flags, trim, dist_pct, err_pct, mad_factor)
+
+
+class PairStat(C.Structure):       # xm_pair_stat_t
+    _fields_ = [(k, C.c_int32) for k in ("n_joint", "n_kept", "n_flagged", "status")] + [("scale1", C.c_double), ("scale2", C.c_double),
+               ("translation", C.c_double * 3), ("median", C.c_double), ("p95", C.c_double), ("percentage", C.c_double)]
+
+
+class PairResult(C.Structure):     # xm_pair_result_t
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + \
+               [(k, C.c_int64) for k in ("pairs_used", "pairs_skipped", "pairs_degenerate", "nobs_flagged", "max_joint", "pairs_on_workspace_path")] + \
+               [(k, C.c_double) for k in ("seconds_index", "seconds_kernels", "seconds_download")]
+
+
+PAIR_STAT_DTYPE = np.dtype([("n_joint", "<i4"), ("n_kept", "<i4"), ("n_flagged", "<i4"), ("status", "<i4"), ("scale1", "<f8"), ("scale2", "<f8"),
+                            ("translation", "<f8", (3,)), ("median", "<f8"), ("p95", "<f8"), ("percentage", "<f8")])
+PAIR_SKIP_ROW0 = 1
+PAIR_USED, PAIR_TOO_FEW, PAIR_DEGENERATE = 0, 1, 2
 CLEAN_NO_SWAP = 1
 BA_PROBE_DENSE_MAX_ROWS = 4096
 BA_FIX_ROTATIONS = 1
@@ -199,6 +223,9 @@ def lib():
         L.xm_clean_observations.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CleanOptions), C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.POINTER(CleanResult)]
         L.xm_ctx_clean_observations.argtypes = [C.c_void_p, C.POINTER(CleanOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CleanResult)]
+        L.xm_pair_filter.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(PairOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PairResult)]
+        L.xm_pair_filter_limits.argtypes = [C.c_void_p]
         L.xm_ctx_reprojection_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_transport.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
         L.xm_ctx_dense_q.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -588,6 +615,66 @@ def clean_observations(cam, lm, w=None, n=None, m=None, min_cam_obs=10, min_lm_o
                                      None if w is None else w.ctypes.data_as(C.c_void_p), C.byref(opt), keep.ctypes.data_as(C.c_void_p),
                                      ci.ctypes.data_as(C.c_void_p), li.ctypes.data_as(C.c_void_p), C.byref(res)))
     return _clean_plan(keep, ci, li, res)
+
+
+class PairFilterPlan:
+    """what pair_filter found: count (int32 per observation: the pairs that flagged it), outlier (bool per observation), stats (a structured
+    array with one xm_pair_stat_t per pair) and info, the fields of xm_pair_result_t"""
+
+    def __init__(self, count, outlier, stats, info):
+        self.count, self.outlier, self.stats, self.info = count, outlier, stats, info
+
+    def apply(self, *per_observation):
+        """the rows of the observations that are no outliers, in input order, of every array given (cam, lm, p, w, ...): what the reference
+        hands to checklandmarks (5_test_ceres.py:423-426)"""
+        k = ~self.outlier
+        out = []
+        for a in per_observation:
+            a = np.asarray(a)
+            if a.shape[:1] != k.shape:
+                raise XmError("PairFilterPlan.apply: a per-observation array has another length than the filtered list")
+            out.append(a[k])
+        return tuple(out)
+
+
+def pair_filter_limits():
+    """-> dict(lds_joint: the largest joint set of a pair that is sorted in LDS (larger ones take the workspace path), threads: per workgroup,
+    workspace_groups: workgroups of the workspace path, small_joint: the largest joint set of the small LDS instantiation)"""
+    out = np.zeros(4, dtype=np.int64)
+    _chk(lib().xm_pair_filter_limits(out.ctypes.data_as(C.c_void_p)))
+    return dict(lds_joint=int(out[0]), threads=int(out[1]), workspace_groups=int(out[2]), small_joint=int(out[3]))
+
+
+def pair_filter(cam, lm, p, pairs_i, pairs_j, R, n=None, m=None, min_joint=20, trim=0.05, dist_pct=90, err_pct=95, mad_factor=3.0, min_flags=1,
+                skip_row0=False):
+    """the reference's pairwise relative-rotation filter (5_test_ceres.py:316-431) on the device (xm_pair_filter; include/xm_amd.h has the
+    definition): cam, lm 0-based per observation, p nobs x 3 camera-frame points; pairs_i, pairs_j the cameras of every pair and R (npairs x
+    3 x 3) its relative rotation, dst ~ R src for src in camera pairs_i and dst in camera pairs_j.  The options are literal; the defaults are
+    the reference's constants.  skip_row0: the reference's quirk that observation row 0 never takes part.  -> PairFilterPlan"""
+    cam = np.ascontiguousarray(cam, dtype=np.int32).reshape(-1); lm = np.ascontiguousarray(lm, dtype=np.int32).reshape(-1)
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    if cam.size != lm.size or p.shape != (cam.size, 3):
+        raise XmError("pair_filter: cam, lm and p (nobs x 3) must have one entry per observation")
+    pi = np.ascontiguousarray(pairs_i, dtype=np.int32).reshape(-1); pj = np.ascontiguousarray(pairs_j, dtype=np.int32).reshape(-1)
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    if pi.size != pj.size or R.size != 9 * pi.size or (pi.size and R.shape[-2:] != (3, 3)):
+        raise XmError("pair_filter: pairs_i, pairs_j and R (npairs x 3 x 3) must have one entry per pair")
+    if int(min_joint) < 0 or int(min_flags) < 0 or not trim >= 0 or not dist_pct >= 0 or not err_pct >= 0 or not mad_factor >= 0:
+        raise XmError("pair_filter: negative option")
+    if not trim < 0.5:
+        raise XmError("pair_filter: trim must stay below 0.5")
+    if dist_pct > 100 or err_pct > 100:
+        raise XmError("pair_filter: a percentile above 100")
+    n = (int(cam.max()) + 1 if cam.size else 0) if n is None else int(n)
+    m = (int(lm.max()) + 1 if lm.size else 0) if m is None else int(m)
+    opt = PairOptions(int(min_joint), int(min_flags), PAIR_SKIP_ROW0 if skip_row0 else 0, float(trim), float(dist_pct), float(err_pct), float(mad_factor))
+    res = PairResult(); res.struct_size = C.sizeof(PairResult)
+    require_gpu()
+    count = np.zeros(cam.size, dtype=np.int32); outlier = np.zeros(cam.size, dtype=np.uint8); stats = np.zeros(pi.size, dtype=PAIR_STAT_DTYPE)
+    P = lambda a: a.ctypes.data_as(C.c_void_p)
+    _chk(lib().xm_pair_filter(n, m, cam.size, P(cam), P(lm), P(p), pi.size, P(pi), P(pj), P(R), C.byref(opt), P(count), P(outlier), P(stats),
+                              C.byref(res)))
+    return PairFilterPlan(count, outlier.astype(bool), stats, {k: getattr(res, k) for k, _ in PairResult._fields_ if k not in ("struct_size", "reserved")})
 
 
 def symw_plan(ntot, nloc, cam0, K=0):
