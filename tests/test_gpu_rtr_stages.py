@@ -128,6 +128,58 @@ def test_stage_outputs_against_the_longdouble_reference(xmamd, pid):
     assert not bad, bad
 
 
+SYMV_MK, SYMV_TUNING = ("dense", 128, 0), dict(sym=1, sym_min_rows=1)   # ld = 384: two strips, 64 steps
+
+
+def _symv_plan(xmamd, n):
+    plan = (C.c_int32 * 4)()
+    xmamd._chk(xmamd.lib().xm_symv_plan(n, plan))
+    return tuple(plan)
+
+
+@pytest.mark.parametrize("f32", [False, True], ids=["f64", "hess_f32"])
+def test_symv_plan_does_not_move_under_a_live_context(xmamd, f32):
+    """the symmetric pair's chunk plan belongs to the workspace it sized: xm_bench_symv_k between two probes of one context changes no byte of
+    any output (gradient, Hessian product -- the fp32 sweep with hess_f32 --, the certificate's o = 1 launch on the same workspace).  The
+    override only moves to LONGER chunks here (4 records per column allocated, 2 asked for)."""
+    L = xmamd.lib()
+    n = rs.matrix(*SYMV_MK)["n"]
+    assert _symv_plan(xmamd, n) == (4, 4, 1, 4)            # the default the test stands on: K = Kf = 4, no finer cut, nchunks = 4
+    pt, E, e_ref, lam = rs.reference(SYMV_MK, 3, False, False)
+    path = dict(auto=False)
+    try:
+        ctx = _ctx(xmamd, SYMV_MK, dict(SYMV_TUNING, hess_f32=1) if f32 else SYMV_TUNING)
+        first = _probe(ctx, path, 3, pt, lam, tcg_init=True, delta=2.5, cert=True, X=pt["X"])
+        assert first["product_kind"] == "dense_sym"
+        xmamd._chk(L.xm_bench_symv_k(8, 1, 8))
+        assert _symv_plan(xmamd, n)[:2] == (8, 8) and _symv_plan(xmamd, n)[3] == 2   # what a workspace made now would get
+        again = _probe(ctx, path, 3, pt, lam, tcg_init=True, delta=2.5, cert=True, X=pt["X"])
+        for k, v in first.items():
+            same = v.tobytes() == again[k].tobytes() if isinstance(v, np.ndarray) else v == again[k]
+            assert same, k
+        ctx.close()
+    finally:
+        xmamd._chk(L.xm_bench_symv_k(0, 1, 0))
+
+
+def test_symv_workspace_made_under_the_override_uses_it(xmamd):
+    """a context created after xm_bench_symv_k runs the forced plan: the bounds of the path sym-finer-cut"""
+    L = xmamd.lib()
+    n = rs.matrix(*SYMV_MK)["n"]
+    pt, E, e_ref, lam = rs.reference(SYMV_MK, 3, False, False)
+    try:
+        xmamd._chk(L.xm_bench_symv_k(8, 1, 8))
+        ctx = _ctx(xmamd, SYMV_MK, SYMV_TUNING)
+        got = _probe(ctx, dict(auto=False), 3, pt, lam)
+        assert got["product_kind"] == "dense_sym"
+        bad = rs.compare("sym-override-8-8-o3", got, E, e_ref, rs.GRAD_KEYS + rs.HESS_KEYS)
+        assert _symv_plan(xmamd, n)[:2] == (8, 8)
+        ctx.close()
+    finally:
+        xmamd._chk(L.xm_bench_symv_k(0, 1, 0))
+    assert not bad, bad
+
+
 CONS = ["dense-n86", "sym-n87", "f32-sym-n86", "bsr-n200", "sell-n200-g1-c2-w1", "schur-n40", "auto-bsr-n17", "split8-n683"]
 
 

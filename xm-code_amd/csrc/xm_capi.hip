@@ -668,10 +668,9 @@ int xm_qw_dense(const double *dq, int64_t n, int o, const double *dW, double *dO
 int xm_qw_dense_sym(const double *dq, int64_t n, int o, const double *dW, double *dOut, double alpha, void *stream) {
     XM_TRY
     const int64_t ld = xm::dense_ld(n);
-    xm::DevBuf<double> prow, pcol;
-    prow.alloc(xm::sym_prow_count((int)n, ld, o));
-    pcol.alloc(xm::sym_pcol_count((int)n, ld, o), false);
-    xm::launch_qw_sym(o, xm::EPI_PLAIN, dq, ld, dW, alpha, plain_args(n, dOut), prow.p, pcol.p, (hipStream_t)stream);
+    xm::SymvWork work;
+    work.ensure((int)n, ld, o);
+    xm::launch_qw_sym(o, xm::EPI_PLAIN, dq, ld, dW, alpha, plain_args(n, dOut), work, (hipStream_t)stream);
     XM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     return XM_OK;
     XM_CATCH
@@ -705,10 +704,9 @@ int xm_qw_dense_sym_f32(const float *dq32, int64_t n, int o, const double *dW, d
     XM_TRY
     const int64_t ld = xm::dense_ld(n);
     if (o < 3 || o > 5) throw xm::Error(XM_ERR_ARG, "fp32 symmetric product: o in 3..5");
-    xm::DevBuf<double> prow, pcol;
-    prow.alloc(xm::sym_prow_count((int)n, ld, o));
-    pcol.alloc(xm::sym_pcol_count((int)n, ld, o), false);
-    xm::launch_qw_sym_f32(o, xm::EPI_PLAIN, dq32, nullptr, ld, dW, alpha, plain_args(n, dOut), prow.p, pcol.p, (hipStream_t)stream);
+    xm::SymvWork work;
+    work.ensure((int)n, ld, o);
+    xm::launch_qw_sym_f32(o, xm::EPI_PLAIN, dq32, nullptr, ld, dW, alpha, plain_args(n, dOut), work, (hipStream_t)stream);
     XM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     return XM_OK;
     XM_CATCH

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <stdexcept>
@@ -23,6 +24,49 @@ struct Error : std::runtime_error {
             throw ::xm::Error(-3, std::string("HIP error: ") + hipGetErrorString(_e) + " at " +       \
                                       __FILE__ + ":" + std::to_string(__LINE__) + " (" #expr ")");    \
     } while (0)
+
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t count = 0;
+    size_t capacity = 0;   // elements allocated (>= count): ensure() reuses the allocation
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        count = 0;
+        capacity = 0;
+    }
+    void alloc(size_t n, bool zero = true) {
+        release();
+        count = n;
+        capacity = n ? n : 1;
+        XM_HIP_CHECK(hipMalloc((void **)&p, (n ? n : 1) * sizeof(T)));
+        if (zero) {
+            // hipMemset runs on the NULL stream and may return before it has executed; the solver works on its own NON-BLOCKING
+            // stream, which is not ordered against the NULL stream -> wait here, or a late memset could wipe data that kernels on
+            // the solver stream have already written (seen with two processes time-slicing one GPU).
+            XM_HIP_CHECK(hipMemset(p, 0, (n ? n : 1) * sizeof(T)));
+            XM_HIP_CHECK(hipStreamSynchronize(nullptr));
+        }
+    }
+    // n zero-filled elements for work on stream `st`: the allocation is kept when it is large enough (a memset enqueued on `st`, no
+    // hipFree / hipMalloc / device synchronisation -- a staircase solve sets its workspace up once per rank level, ~45 buffers each
+    // time); `reserve` (>= n) is what a NEW allocation is sized for, so that later rank levels fit
+    void ensure(size_t n, hipStream_t st, size_t reserve = 0) {
+        if (p && n <= capacity) {
+            count = n;
+            XM_HIP_CHECK(hipMemsetAsync(p, 0, (n ? n : 1) * sizeof(T), st));
+            return;
+        }
+        const size_t want = std::max(n, reserve);
+        alloc(want);
+        count = n;
+    }
+};
 
 // Row pitch of every device "3n x o" matrix: o rounded up to an odd number.  An odd pitch makes the
 // per-lane ds_read_b128 of two consecutive W rows bank-conflict free (lane stride 4*OP dwords, OP odd).
@@ -221,24 +265,36 @@ void launch_qw_dense_split(int o, int epi, const double *Q, int64_t ld, const do
 int qw_dense_tile_cols();
 int qw_dense_split_k(int nloc, int64_t ld);   // column split the small-strip policy picks for `nloc` cameras (1 = none)
 int bsr_grid(int nloc);   // workgroups (= partial sums per epilogue slot) of the BSR3 kernels
-size_t sym_prow_count(int nloc, int64_t ld, int o);
-size_t sym_pcol_count(int nloc, int64_t ld, int o);
 void qw_bench_nt(int nt);                                  // micro-benchmark override of the load policy: -1 by size, 0 default, 1 non-temporal
-void symv_bench_k(int k, int kf);                                  // micro-benchmark override of the chunk length (xm_bench.h)
+void symv_bench_k(int k, int kf);                                  // micro-benchmark override of the chunk length (xm_bench.h): read when a SymvWork is made, never by a launch
 int symv_trace_slots();
-void launch_qw_sym_traced(int o, const double *Q, int64_t ld, const double *W, const CamArgs &a, double *Prow, double *Pcol, unsigned long long *trace,
-                          int grid[2], hipStream_t st);
-void symv_plan_get(int nloc, int64_t ld, int out[4]);   // K, Kf, ysplit, nchunks of the vertical-sweep symmetric product
-void launch_qw_sym(int o, int epi, const double *Q, int64_t ld, const double *W, double alpha, const CamArgs &a, double *Prow,
-                   double *Pcol, hipStream_t st, int rev = 0);   // rev: sweep direction, alternated by the caller between consecutive products
+// Chunk plan of the vertical-sweep symmetric product.  K: steps per chunk (a wavefront); Kf: the same in the grid rows >= ysplit (dispatched last: cut
+// finer when the sweep takes several residency rounds); nchunks: upper bound of column-sum records per column (sizes pcol); gx, gy: the folded grid
+struct SymvPlan { int K, Kf, ysplit, nchunks, gx, gy; };
+void symv_plan_get(int nloc, int64_t ld, int out[4]);   // host-only view: K, Kf, ysplit, nchunks a workspace made now would get
+// Workspace of the symmetric product for (nloc, ld) and ranks up to o: the plan and the two buffers it sizes, made together.  The sweep writes its
+// column sums where the plan says and the reducer reads them there, so the launchers take the plan from here and nowhere else.
+struct SymvWork {
+    int nloc = 0, o = 0;
+    int64_t ld = 0;
+    SymvPlan plan{};
+    DevBuf<double> prow, pcol;                  // row results (zero-filled) and per-workgroup column partials
+    void ensure(int nloc, int64_t ld, int o);   // plans from the override as it stands NOW and allocates anew, also when (nloc, ld, o) repeat
+    void release();
+    explicit operator bool() const { return pcol.p != nullptr; }
+};
+// symmetric half-traffic products.  Every launcher throws XM_ERR_ARG unless `work` is allocated for a.nloc, ld and a rank >= o.
+void launch_qw_sym_traced(int o, const double *Q, int64_t ld, const double *W, const CamArgs &a, SymvWork &work, unsigned long long *trace, hipStream_t st);
+void launch_qw_sym(int o, int epi, const double *Q, int64_t ld, const double *W, double alpha, const CamArgs &a, SymvWork &work, hipStream_t st,
+                   int rev = 0);   // rev: sweep direction, alternated by the caller between consecutive products
 void launch_asym(const double *Q, int64_t ld, int64_t m, double *out, int grid, hipStream_t st);
 // fp32 copy of a dense Q for the Hessian products of the truncated CG (xm_tuning_t.hess_f32): same shape (rows x ld, ld a multiple of 4), round to
 // nearest; *bad (device) receives the number of elements that are not finite in fp32
 void launch_dense_to_f32(const double *src, float *dst, int64_t rows, int64_t ld, unsigned int *bad, hipStream_t st);
 // the products from it: Q loaded as fp32, accumulated in f64.  Epilogues: plain, Hessian, and EPI_AUTO, whose gradient role reads Qd (f64)
 void launch_qw_dense_f32(int o, int epi, const float *Qf, const double *Qd, int64_t ld, const double *W, double alpha, const CamArgs &a, hipStream_t st);
-void launch_qw_sym_f32(int o, int epi, const float *Qf, const double *Qd, int64_t ld, const double *W, double alpha, const CamArgs &a, double *Prow,
-                       double *Pcol, hipStream_t st, int rev = 0);   // o = 3..5; Prow / Pcol as for launch_qw_sym
+void launch_qw_sym_f32(int o, int epi, const float *Qf, const double *Qd, int64_t ld, const double *W, double alpha, const CamArgs &a, SymvWork &work,
+                       hipStream_t st, int rev = 0);   // o = 3..5; work as for launch_qw_sym
 
 // exact symmetry check of a row-partitioned matrix: this strip's (rows row0 .. row0 + nrows of the m x m matrix) share of a sum modulo 2^64
 // that vanishes over all strips iff the matrix is symmetric (xm_kernels.hip: symhash_kernel); out: 2 * grid words

@@ -2437,24 +2437,21 @@ int flat_grid(int64_t elems) {
 constexpr int kQwResidentMB = 220;
 static int g_qw_nt_override = -1;
 void qw_bench_nt(int nt) { g_qw_nt_override = nt; }
-static int64_t qw_resident_bytes(size_t total_bytes) {      // bytes of the stream that stay cacheable; >= total: all of it
+static int64_t resident_bytes(int64_t by_size) {            // the override, else what the stream's own rule found by its size
     if (g_qw_nt_override == 0) return INT64_MAX;
     if (g_qw_nt_override == 1) return 0;
     if (g_qw_nt_override >= 2) return (int64_t)g_qw_nt_override << 20;
     if (g_qw_nt_override <= -2) return (int64_t)(-g_qw_nt_override) << 10;   // (KB: mixed policies on the small matrices of the tests)
-    return total_bytes <= ((size_t)310 << 20) ? INT64_MAX : (int64_t)kQwResidentMB << 20;
+    return by_size;
+}
+static int64_t qw_resident_bytes(size_t total_bytes) {      // bytes of the stream that stay cacheable; >= total: all of it
+    return resident_bytes(total_bytes <= ((size_t)310 << 20) ? INT64_MAX : (int64_t)kQwResidentMB << 20);
 }
 // sliced-ELL stream (xm_sell.hip): bytes of its prefix that stay cacheable when an iteration moves `other` bytes besides it
 constexpr int64_t kSellCacheBudgetMB = 230;
-int64_t sell_resident_bytes(int64_t stream, int64_t other) {
-    if (g_qw_nt_override == 0) return INT64_MAX;
-    if (g_qw_nt_override == 1) return 0;
-    if (g_qw_nt_override >= 2) return (int64_t)g_qw_nt_override << 20;
-    if (g_qw_nt_override <= -2) return (int64_t)(-g_qw_nt_override) << 10;
-    return std::max<int64_t>(0, (kSellCacheBudgetMB << 20) - other);
-}
-static int qw_nt_cam0(int nloc, int64_t ld) {
-    const size_t row3 = (size_t)3 * (size_t)ld * sizeof(double);
+int64_t sell_resident_bytes(int64_t stream, int64_t other) { return resident_bytes(std::max<int64_t>(0, (kSellCacheBudgetMB << 20) - other)); }
+static int qw_nt_cam0(int nloc, int64_t ld, size_t elem_bytes) {   // elem_bytes: 8 (f64 matrix) or 4 (its fp32 copy)
+    const size_t row3 = (size_t)3 * (size_t)ld * elem_bytes;
     const int64_t res = qw_resident_bytes((size_t)nloc * row3);
     return (int)std::min<int64_t>(nloc, res / (int64_t)row3);
 }
@@ -2462,7 +2459,7 @@ template <int O, int NSUB>
 static void qw_dense_epi(int epi, const double *Q, int64_t ld, const double *W, double alpha, const CamArgs &a0, hipStream_t st) {
     const dim3 g(qw_grid(a0.nloc)), b(256);
     CamArgs a = a0;
-    a.nt_cam0 = qw_nt_cam0(a.nloc, ld);
+    a.nt_cam0 = qw_nt_cam0(a.nloc, ld, sizeof(double));
     switch (epi) {
         case EPI_PLAIN: hipLaunchKernelGGL((qw_dense_kernel<O, EPI_PLAIN, NSUB>), g, b, 0, st, Q, ld, W, alpha, a); break;
         case EPI_GRAD: hipLaunchKernelGGL((qw_dense_kernel<O, EPI_GRAD, NSUB>), g, b, 0, st, Q, ld, W, alpha, a); break;
@@ -2478,7 +2475,7 @@ template <int O>
 static void qw_dense_split_o(int epi, const double *Q, int64_t ld, const double *W, double alpha, const CamArgs &a0, hipStream_t st) {
     const dim3 g(qw_grid(a0.nloc)), b(256);
     CamArgs a = a0;
-    a.nt_cam0 = qw_nt_cam0(a.nloc, ld);
+    a.nt_cam0 = qw_nt_cam0(a.nloc, ld, sizeof(double));
     if (epi == EPI_PLAIN) hipLaunchKernelGGL((qw_dense_kernel<O, EPI_PLAIN, 2, true>), g, b, 0, st, Q, ld, W, alpha, a);
     else if (epi == EPI_GRAD) hipLaunchKernelGGL((qw_dense_kernel<O, EPI_GRAD, 2, true>), g, b, 0, st, Q, ld, W, alpha, a);
     else throw Error(-2, "split dense product: plain or gradient epilogue only");
@@ -2520,7 +2517,7 @@ void launch_qw_dense(int o, int epi, const double *Q, int64_t ld, const double *
     if (epi == EPI_CERT) {
         if (o != 1) throw Error(-2, "certificate operator needs o == 1");
         CamArgs ac = a;
-        ac.nt_cam0 = qw_nt_cam0(a.nloc, ld);
+        ac.nt_cam0 = qw_nt_cam0(a.nloc, ld, sizeof(double));
         hipLaunchKernelGGL((qw_dense_kernel<1, EPI_CERT, 2>), dim3(qw_grid(a.nloc)), dim3(256), 0, st, Q, ld, W, alpha, ac);
     } else {
         XM_DISPATCH_O(o, (qw_dense_epi<O_, kQwNsub>(epi, Q, ld, W, alpha, a, st)));
@@ -2554,7 +2551,6 @@ int symv_k(int nloc, int64_t ld) {
     }
     return (int)k;
 }
-size_t sym_prow_count(int nloc, int64_t ld, int o) { return (size_t)((ld + kSvStrip - 1) / kSvStrip) * 6 * (size_t)((nloc + 1) / 2) * o; }
 // The launch's tail: workgroups are dispatched strip group by strip group (left to right) and a chunk of K = 64 steps is a quarter
 // of a millisecond at 13.5 GB with only ~4.5 chunks per resident workgroup, so with equal chunks the last "round" runs part empty.
 // The strip groups dispatched last (the rightmost 13 %, a quarter of the work) are cut four times finer -- guided self-scheduling by
@@ -2564,9 +2560,7 @@ size_t sym_prow_count(int nloc, int64_t ld, int o) { return (size_t)((ld + kSvSt
 // of this kind: it repeats on a box.
 static int g_symv_k = 0, g_symv_kf = 0;                   // micro-benchmark / test override of the chunk lengths (xm_bench.h: xm_bench_symv_k)
 void symv_bench_k(int k, int kf) { g_symv_k = k; g_symv_kf = kf; }
-// K: steps per chunk (a wavefront); Kf: the same in the grid rows >= ysplit (dispatched last: cut finer when the sweep takes several residency
-// rounds); nchunks: upper bound of column-sum records per column (sizes Pcol); gx, gy: the folded grid
-struct SymvPlan { int K, Kf, ysplit, nchunks, gx, gy; };
+// the plan (xm_common.h: SymvPlan) under the override as it stands: called when a workspace is made (SymvWork::ensure) and by the host-only view
 static SymvPlan symv_plan(int nloc, int64_t ld) {
     SymvPlan p;
     p.K = g_symv_k > 0 ? g_symv_k : symv_k(nloc, ld);
@@ -2594,74 +2588,88 @@ void symv_plan_get(int nloc, int64_t ld, int out[4]) {   // host-only view of th
     const SymvPlan p = symv_plan(nloc, ld);
     out[0] = p.K; out[1] = p.Kf; out[2] = p.ysplit; out[3] = p.nchunks;
 }
-size_t sym_pcol_count(int nloc, int64_t ld, int o) { return (size_t)symv_plan(nloc, ld).nchunks * (size_t)ld * o; }
+// One plan per allocation: the plan is fixed here, sizes pcol here, and every launch on this workspace takes it from here -- a later
+// xm_bench_symv_k reaches the workspaces made after it and no sweep that writes into this one.
+void SymvWork::ensure(int nloc_new, int64_t ld_new, int o_new) {
+    release();
+    const SymvPlan p = symv_plan(nloc_new, ld_new);
+    prow.alloc((size_t)((ld_new + kSvStrip - 1) / kSvStrip) * 6 * (size_t)((nloc_new + 1) / 2) * o_new);
+    pcol.alloc((size_t)p.nchunks * (size_t)ld_new * o_new, false);
+    nloc = nloc_new; ld = ld_new; o = o_new; plan = p;
+}
+void SymvWork::release() {
+    prow.release(); pcol.release();
+    nloc = 0; ld = 0; o = 0; plan = SymvPlan{};
+}
+// what both sweeps and the reducer take from the plan: the folded grid; steps per column-sum record (4 K: one record per workgroup), the same in
+// the finer cut, and the grid row from which it applies.  Refuses a workspace that was not made for this product, before anything is launched.
+struct SymvGeom { dim3 gs; int rK, rKf, ys, nstrips; };
+static SymvGeom symv_geom(const SymvWork &w, int nloc, int64_t ld, int o) {
+    if (!w || nloc != w.nloc || ld != w.ld || o > w.o) throw Error(-2, "symmetric product: the workspace was not made for this size and rank");
+    return {dim3(w.plan.gx, w.plan.gy), 4 * w.plan.K, 4 * w.plan.Kf, w.plan.ysplit, (int)((ld + kSvStrip - 1) / kSvStrip)};
+}
 
 // first step (two cameras, six rows) of the symmetric sweep that streams non-temporally: the upper triangle's rows above it hold the resident bytes
-static int symv_nt_step0(int nloc, int64_t ld) {
+static int symv_nt_step0(int nloc, double elem_bytes) {     // elem_bytes: 8 (f64 matrix) or 4 (its fp32 copy)
     const double m = 3.0 * nloc;
-    const double tri = 8.0 * m * (m + 6.0) / 2.0;            // bytes the sweep streams (triangle incl. the 6-wide diagonal blocks)
+    const double tri = elem_bytes * m * (m + 6.0) / 2.0;     // bytes the sweep streams (triangle incl. the 6-wide diagonal blocks)
     const int64_t res = qw_resident_bytes((size_t)tri);
     const int nsteps = (nloc + 1) / 2;
     if ((double)res >= tri) return nsteps + 1;
-    // rows [0, r) of the triangle hold 8 (r m - r^2 / 2) bytes
-    const double disc = m * m - 2.0 * (double)res / 8.0;
+    // rows [0, r) of the triangle hold elem_bytes (r m - r^2 / 2) bytes
+    const double disc = m * m - 2.0 * (double)res / elem_bytes;
     const double r = m - std::sqrt(std::max(0.0, disc));
     return (int)std::min<double>(nsteps + 1, std::max(0.0, r / 6.0));
 }
 template <int O>
-static void qw_symv_epi(int epi, const double *Q, int64_t ld, const double *W, double alpha, const CamArgs &a, double *Prow, double *Pcol,
+static void qw_symv_epi(int epi, const double *Q, int64_t ld, const double *W, double alpha, const CamArgs &a, SymvWork &work,
                         hipStream_t st, int rev, unsigned long long *trace = nullptr) {
-    const SymvPlan pl = symv_plan(a.nloc, ld);
-    const int nstrips = (int)((ld + kSvStrip - 1) / kSvStrip);
+    const auto [gs, rK, rKf, ys, nstrips] = symv_geom(work, a.nloc, ld, O);
+    const SymvPlan &pl = work.plan;
+    double *const Prow = work.prow.p, *const Pcol = work.pcol.p;
     const TcgScal *sc = (epi == EPI_HESS || epi == EPI_AUTO) ? a.scal : (const TcgScal *)nullptr;
     const int by_phase = (epi == EPI_AUTO) ? 1 : 0;
-    // the per-camera sum needs: steps per column-sum record (4 K: one record per workgroup), grid row from which the finer cut applies
-    const int ys = pl.ysplit, rK = 4 * pl.K, rKf = 4 * pl.Kf, rys = ys;
-    const dim3 gs(pl.gx, pl.gy);
-    const int nt0 = symv_nt_step0(a.nloc, ld);
+    const int nt0 = symv_nt_step0(a.nloc, sizeof(double));
     if (trace) {
         if constexpr (O == 3 || O == 4) hipLaunchKernelGGL((qw_symv_kernel<O, true>), gs, dim3(256), 0, st, Q, ld, W, a.nloc, pl.K, pl.Kf, ys, nt0, sc, Prow, Pcol, trace, rev, by_phase);
     } else hipLaunchKernelGGL((qw_symv_kernel<O>), gs, dim3(256), 0, st, Q, ld, W, a.nloc, pl.K, pl.Kf, ys, nt0, sc, Prow, Pcol, trace, rev, by_phase);
     const dim3 g(qw_grid(a.nloc)), b(256);
     switch (epi) {
-        case EPI_PLAIN: hipLaunchKernelGGL((symv_reduce_kernel<O, EPI_PLAIN>), g, b, 0, st, Prow, Pcol, ld, nstrips, rK, rKf, rys, alpha, a); break;
-        case EPI_GRAD: hipLaunchKernelGGL((symv_reduce_kernel<O, EPI_GRAD>), g, b, 0, st, Prow, Pcol, ld, nstrips, rK, rKf, rys, alpha, a); break;
-        case EPI_HESS: hipLaunchKernelGGL((symv_reduce_kernel<O, EPI_HESS>), g, b, 0, st, Prow, Pcol, ld, nstrips, rK, rKf, rys, alpha, a); break;
+        case EPI_PLAIN: hipLaunchKernelGGL((symv_reduce_kernel<O, EPI_PLAIN>), g, b, 0, st, Prow, Pcol, ld, nstrips, rK, rKf, ys, alpha, a); break;
+        case EPI_GRAD: hipLaunchKernelGGL((symv_reduce_kernel<O, EPI_GRAD>), g, b, 0, st, Prow, Pcol, ld, nstrips, rK, rKf, ys, alpha, a); break;
+        case EPI_HESS: hipLaunchKernelGGL((symv_reduce_kernel<O, EPI_HESS>), g, b, 0, st, Prow, Pcol, ld, nstrips, rK, rKf, ys, alpha, a); break;
         case EPI_AUTO:
-            if constexpr (O >= 3) { hipLaunchKernelGGL((symv_reduce_kernel<O, EPI_AUTO>), g, b, 0, st, Prow, Pcol, ld, nstrips, rK, rKf, rys, alpha, a); break; }
+            if constexpr (O >= 3) { hipLaunchKernelGGL((symv_reduce_kernel<O, EPI_AUTO>), g, b, 0, st, Prow, Pcol, ld, nstrips, rK, rKf, ys, alpha, a); break; }
             throw Error(-2, "bad epilogue");
         case EPI_CERT:   // certificate operator (rank-1 input): the Lanczos products of a large dense Q at half the traffic too
-            if constexpr (O == 1) { hipLaunchKernelGGL((symv_reduce_kernel<1, EPI_CERT>), g, b, 0, st, Prow, Pcol, ld, nstrips, rK, rKf, rys, alpha, a); break; }
+            if constexpr (O == 1) { hipLaunchKernelGGL((symv_reduce_kernel<1, EPI_CERT>), g, b, 0, st, Prow, Pcol, ld, nstrips, rK, rKf, ys, alpha, a); break; }
             throw Error(-2, "certificate operator needs o == 1");
         default: throw Error(-2, "bad epilogue");
     }
 }
 int symv_trace_slots() { return kSvTraceSlots; }
-// micro-benchmark: one traced product (o = 3 or 4); trace = [grid.y * grid.x * 4 wavefronts][kSvTraceSlots] timestamps, grid returned
-void launch_qw_sym_traced(int o, const double *Q, int64_t ld, const double *W, const CamArgs &a, double *Prow, double *Pcol, unsigned long long *trace,
-                          int grid[2], hipStream_t st) {
-    const SymvPlan pl = symv_plan(a.nloc, ld);
-    grid[0] = pl.gx; grid[1] = pl.gy;
-    if (trace == nullptr) return;
-    if (o == 3) qw_symv_epi<3>(EPI_PLAIN, Q, ld, W, 1.0, a, Prow, Pcol, st, 0, trace);
-    else if (o == 4) qw_symv_epi<4>(EPI_PLAIN, Q, ld, W, 1.0, a, Prow, Pcol, st, 0, trace);
+// micro-benchmark: one traced product (o = 3 or 4); trace = [work.plan.gy * work.plan.gx * 4 wavefronts][kSvTraceSlots] timestamps
+void launch_qw_sym_traced(int o, const double *Q, int64_t ld, const double *W, const CamArgs &a, SymvWork &work, unsigned long long *trace, hipStream_t st) {
+    if (trace == nullptr) throw Error(-2, "traced symmetric product: no trace buffer");
+    if (o == 3) qw_symv_epi<3>(EPI_PLAIN, Q, ld, W, 1.0, a, work, st, 0, trace);
+    else if (o == 4) qw_symv_epi<4>(EPI_PLAIN, Q, ld, W, 1.0, a, work, st, 0, trace);
     else throw Error(-2, "traced symmetric product: o = 3 or 4");
     check_launch("qw_symv traced");
 }
 
-// symmetric half-traffic product (o in 1, 3..5); Prow: sym_prow_count() doubles, Pcol: sym_pcol_count() doubles.  rev (0 / 1): the direction
+// symmetric half-traffic product (o in 1, 3..5) on a workspace made for this (a.nloc, ld) and a rank >= o.  rev (0 / 1): the direction
 // of the sweep inside every chunk.  A launch that starts with the steps the previous launch ended with finds them in the XCDs' L2 (4 MB each:
 // a quarter of a Venice-size sweep; block b runs on XCD b mod 8 in every launch), so callers alternate it between consecutive products --
 // by a number both runs of the same solve agree on (the tCG iteration, the Lanczos step), never by a launch count that run-ahead no-ops would shift:
 // the direction changes the order of the column sums, i.e. the last bits.
-void launch_qw_sym(int o, int epi, const double *Q, int64_t ld, const double *W, double alpha, const CamArgs &a, double *Prow,
-                   double *Pcol, hipStream_t st, int rev) {
+void launch_qw_sym(int o, int epi, const double *Q, int64_t ld, const double *W, double alpha, const CamArgs &a, SymvWork &work, hipStream_t st,
+                   int rev) {
     if (a.nloc <= 0) return;
     switch (o) {
-        case 1: qw_symv_epi<1>(epi, Q, ld, W, alpha, a, Prow, Pcol, st, rev & 1); break;
-        case 3: qw_symv_epi<3>(epi, Q, ld, W, alpha, a, Prow, Pcol, st, rev & 1); break;
-        case 4: qw_symv_epi<4>(epi, Q, ld, W, alpha, a, Prow, Pcol, st, rev & 1); break;
-        case 5: qw_symv_epi<5>(epi, Q, ld, W, alpha, a, Prow, Pcol, st, rev & 1); break;
+        case 1: qw_symv_epi<1>(epi, Q, ld, W, alpha, a, work, st, rev & 1); break;
+        case 3: qw_symv_epi<3>(epi, Q, ld, W, alpha, a, work, st, rev & 1); break;
+        case 4: qw_symv_epi<4>(epi, Q, ld, W, alpha, a, work, st, rev & 1); break;
+        case 5: qw_symv_epi<5>(epi, Q, ld, W, alpha, a, work, st, rev & 1); break;
         default: throw Error(-2, "symmetric product is instantiated for o = 1, 3..5");
     }
     check_launch("qw_symv");
@@ -3344,10 +3352,7 @@ template <int O>
 static void qw_dense_f32_epi(int epi, const float *Qf, const double *Qd, int64_t ld, const double *W, double alpha, const CamArgs &a0, hipStream_t st) {
     const dim3 g(qw_grid(a0.nloc)), b(256);
     CamArgs a = a0;
-    {
-        const size_t row3 = (size_t)3 * (size_t)ld * sizeof(float);
-        a.nt_cam0 = (int)std::min<int64_t>(a.nloc, qw_resident_bytes((size_t)a.nloc * row3) / (int64_t)row3);
-    }
+    a.nt_cam0 = qw_nt_cam0(a.nloc, ld, sizeof(float));
     switch (epi) {
         case EPI_PLAIN: hipLaunchKernelGGL((qw_dense_f32_kernel<O, EPI_PLAIN>), g, b, 0, st, Qf, Qd, ld, W, alpha, a); break;
         case EPI_HESS: hipLaunchKernelGGL((qw_dense_f32_kernel<O, EPI_HESS>), g, b, 0, st, Qf, Qd, ld, W, alpha, a); break;
@@ -3367,25 +3372,15 @@ void launch_qw_dense_f32(int o, int epi, const float *Qf, const double *Qd, int6
     check_launch("qw_dense_f32");
 }
 template <int O>
-static void qw_symv_f32_epi(int epi, const float *Qf, const double *Qd, int64_t ld, const double *W, double alpha, const CamArgs &a, double *Prow,
-                            double *Pcol, hipStream_t st, int rev) {
-    const SymvPlan pl = symv_plan(a.nloc, ld);
-    const int nstrips = (int)((ld + kSvStrip - 1) / kSvStrip);
-    const int rK = 4 * pl.K, rKf = 4 * pl.Kf, ys = pl.ysplit;
-    const dim3 gs(pl.gx, pl.gy), g(qw_grid(a.nloc)), b(256);
+static void qw_symv_f32_epi(int epi, const float *Qf, const double *Qd, int64_t ld, const double *W, double alpha, const CamArgs &a, SymvWork &work,
+                            hipStream_t st, int rev) {
+    const auto [gs, rK, rKf, ys, nstrips] = symv_geom(work, a.nloc, ld, O);
+    const SymvPlan &pl = work.plan;
+    double *const Prow = work.prow.p, *const Pcol = work.pcol.p;
+    const dim3 g(qw_grid(a.nloc)), b(256);
     // load policy: the f64 rule on the fp32 triangle's bytes (the sweep of the candidate's gradient under EPI_AUTO reads the f64 matrix with
     // the f64 rule's first non-temporal step)
-    int nt0;
-    {
-        const double m = 3.0 * a.nloc, tri = 4.0 * m * (m + 6.0) / 2.0;
-        const int64_t res = qw_resident_bytes((size_t)tri);
-        const int nsteps = (a.nloc + 1) / 2;
-        if ((double)res >= tri) nt0 = nsteps + 1;
-        else {
-            const double r = m - std::sqrt(std::max(0.0, m * m - 2.0 * (double)res / 4.0));
-            nt0 = (int)std::min<double>(nsteps + 1, std::max(0.0, r / 6.0));
-        }
-    }
+    const int nt0 = symv_nt_step0(a.nloc, sizeof(float));
     switch (epi) {
         case EPI_PLAIN:
             hipLaunchKernelGGL((qw_symv_f32_kernel<O, false>), gs, b, 0, st, Qf, Qd, ld, W, a.nloc, pl.K, pl.Kf, ys, nt0, (const TcgScal *)nullptr, Prow, Pcol, rev);
@@ -3398,7 +3393,7 @@ static void qw_symv_f32_epi(int epi, const float *Qf, const double *Qd, int64_t 
         case EPI_AUTO:
             if constexpr (O >= 3) {
                 if (!Qd) throw Error(-2, "fp32 product in the device-driven role needs the f64 matrix too");
-                const int nt64 = symv_nt_step0(a.nloc, ld);
+                const int nt64 = symv_nt_step0(a.nloc, sizeof(double));
                 hipLaunchKernelGGL((qw_symv_f32_kernel<O, true>), gs, b, 0, st, Qf, Qd, ld, W, a.nloc, pl.K, pl.Kf, ys, std::min(nt0, nt64), a.scal, Prow, Pcol, rev);
                 hipLaunchKernelGGL((symv_reduce_kernel<O, EPI_AUTO>), g, b, 0, st, Prow, Pcol, ld, nstrips, rK, rKf, ys, alpha, a);
                 break;
@@ -3407,13 +3402,13 @@ static void qw_symv_f32_epi(int epi, const float *Qf, const double *Qd, int64_t 
         default: throw Error(-2, "fp32 symmetric product: plain, Hessian or device-driven epilogue only");
     }
 }
-void launch_qw_sym_f32(int o, int epi, const float *Qf, const double *Qd, int64_t ld, const double *W, double alpha, const CamArgs &a, double *Prow,
-                       double *Pcol, hipStream_t st, int rev) {
+void launch_qw_sym_f32(int o, int epi, const float *Qf, const double *Qd, int64_t ld, const double *W, double alpha, const CamArgs &a, SymvWork &work,
+                       hipStream_t st, int rev) {
     if (a.nloc <= 0) return;
     switch (o) {
-        case 3: qw_symv_f32_epi<3>(epi, Qf, Qd, ld, W, alpha, a, Prow, Pcol, st, rev & 1); break;
-        case 4: qw_symv_f32_epi<4>(epi, Qf, Qd, ld, W, alpha, a, Prow, Pcol, st, rev & 1); break;
-        case 5: qw_symv_f32_epi<5>(epi, Qf, Qd, ld, W, alpha, a, Prow, Pcol, st, rev & 1); break;
+        case 3: qw_symv_f32_epi<3>(epi, Qf, Qd, ld, W, alpha, a, work, st, rev & 1); break;
+        case 4: qw_symv_f32_epi<4>(epi, Qf, Qd, ld, W, alpha, a, work, st, rev & 1); break;
+        case 5: qw_symv_f32_epi<5>(epi, Qf, Qd, ld, W, alpha, a, work, st, rev & 1); break;
         default: throw Error(-2, "fp32 symmetric product is instantiated for o = 3..5");
     }
     check_launch("qw_symv_f32");

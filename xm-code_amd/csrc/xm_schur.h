@@ -141,7 +141,7 @@ private:
     DevBuf<double> Q1_, c_, q3inv_;
     DevBuf<double> vtinv_;                     // (N-1)^2 inverse in the dense kernel's padded row-major layout
     DevBuf<double> h_, r_, xc_, xl_, res_;
-    DevBuf<double> sym_prow_, sym_pcol_;       // partial sums of the half-traffic product with VT^-1 (large N only)
+    SymvWork sym_work_;                        // plan and partial sums of the half-traffic product with VT^-1 (large N only)
     bool vt_sym_ = false;
     DevBuf<int32_t> obs_cam_, obs_lm_;        // the observations in input order (residual kernel)
     DevBuf<double> obs_p_;

@@ -1372,11 +1372,7 @@ void SchurOp::ensure(int o) {
     // VT^-1 is symmetric: from xm_tuning_t.sym_min_rows rows on (default 4096, the measured threshold of the dense solver) the chain applies it
     // with the half-traffic kernel (upper triangle only; o = 3, 4)
     vt_sym_ = !pcg_ && 3 * nred_ >= cfg_.sym_min_rows;
-    if (vt_sym_ && o >= 3) {
-        const int os = std::min(o, 4);
-        sym_prow_.alloc(sym_prow_count((int)nred_, ldv_, os));
-        sym_pcol_.alloc(sym_pcol_count((int)nred_, ldv_, os), false);
-    }
+    if (vt_sym_ && o >= 3) sym_work_.ensure((int)nred_, ldv_, std::min(o, 4));
     o_alloc_ = o;
 }
 
@@ -1393,7 +1389,7 @@ template <int O>
 static void schur_product_o(int epi, int64_t n, int64_t nobs, const SchurLm &L, const int64_t *cam_ptr, const int32_t *cam_lm, const double *cam_w, const double *cam_p,
                             const double *Q1,
                             const double *c, const double *q3inv, const double *vtinv, int64_t nred, int64_t ldv, double *h, double *r,
-                            double *xc, double *xl, const double *W, double alpha, const CamArgs &a, double *sym_prow, double *sym_pcol, hipStream_t st,
+                            double *xc, double *xl, const double *W, double alpha, const CamArgs &a, SymvWork *sym_work, hipStream_t st,
                             Comm *comm, int64_t nred_loc, const std::function<void(const TcgScal *)> &solve_pcg) {
     const TcgScal *sc = (epi == EPI_HESS) ? a.scal : (const TcgScal *)nullptr;
     const int64_t nheavy = L.nheavy, nlight = L.m - L.nheavy;
@@ -1415,7 +1411,7 @@ static void schur_product_o(int epi, int64_t n, int64_t nobs, const SchurLm &L, 
             comm->allgather(xc, (size_t)3 * nred_loc * OPc, st);
         } else {
             pa.nloc = (int)nred; pa.out = xc;
-            if (sym_prow && (O == 3 || O == 4)) launch_qw_sym(O, EPI_PLAIN, vtinv, ldv, r, 1.0, pa, sym_prow, sym_pcol, st);
+            if (sym_work && (O == 3 || O == 4)) launch_qw_sym(O, EPI_PLAIN, vtinv, ldv, r, 1.0, pa, *sym_work, st);
             else launch_qw_dense(O, EPI_PLAIN, vtinv, ldv, r, 1.0, pa, st);
         }
     }
@@ -1449,7 +1445,7 @@ void SchurOp::product(int o, int epi, const double *W, double alpha, const CamAr
         else { XM_DISPATCH_O(o, (pcg_solve<O_, false>(L, sc, st, kind))); }
     };
     XM_DISPATCH_O(o, (schur_product_o<O_>(epi, n_, nobs_, L, cam_ptr_.p, cam_lm_.p, cam_w_.p, cam_p_.p, Q1_.p,
-                                         c_.p, q3inv_.p, vtinv_.p, nred_, ldv_, h_.p, r_.p, xc_.p, xl_.p, W, alpha, a, (vt_sym_ && !comm_) ? sym_prow_.p : (double *)nullptr, sym_pcol_.p, st,
+                                         c_.p, q3inv_.p, vtinv_.p, nred_, ldv_, h_.p, r_.p, xc_.p, xl_.p, W, alpha, a, (vt_sym_ && !comm_ && sym_work_) ? &sym_work_ : nullptr, st,
                                          comm_, nred_loc_, pcg)));
     check_launch("schur_product");
 }

@@ -106,49 +106,6 @@ std::shared_ptr<Comm> rccl_comm_create(int rank, int world, const unsigned char 
 void peer_group_abort(const std::shared_ptr<PeerGroup> &g);
 double peer_allgather_bench(int world, int gpu_map, int64_t count, int reps);   // microseconds per collective (xm_team.hip)                               // wakes every host-side wait with an error
 
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t count = 0;
-    size_t capacity = 0;   // elements allocated (>= count): ensure() reuses the allocation
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        count = 0;
-        capacity = 0;
-    }
-    void alloc(size_t n, bool zero = true) {
-        release();
-        count = n;
-        capacity = n ? n : 1;
-        XM_HIP_CHECK(hipMalloc((void **)&p, (n ? n : 1) * sizeof(T)));
-        if (zero) {
-            // hipMemset runs on the NULL stream and may return before it has executed; the solver works on its own NON-BLOCKING
-            // stream, which is not ordered against the NULL stream -> wait here, or a late memset could wipe data that kernels on
-            // the solver stream have already written (seen with two processes time-slicing one GPU).
-            XM_HIP_CHECK(hipMemset(p, 0, (n ? n : 1) * sizeof(T)));
-            XM_HIP_CHECK(hipStreamSynchronize(nullptr));
-        }
-    }
-    // n zero-filled elements for work on stream `st`: the allocation is kept when it is large enough (a memset enqueued on `st`, no
-    // hipFree / hipMalloc / device synchronisation -- a staircase solve sets its workspace up once per rank level, ~45 buffers each
-    // time); `reserve` (>= n) is what a NEW allocation is sized for, so that later rank levels fit
-    void ensure(size_t n, hipStream_t st, size_t reserve = 0) {
-        if (p && n <= capacity) {
-            count = n;
-            XM_HIP_CHECK(hipMemsetAsync(p, 0, (n ? n : 1) * sizeof(T), st));
-            return;
-        }
-        const size_t want = std::max(n, reserve);
-        alloc(want);
-        count = n;
-    }
-};
-
 void partition_cuts(int64_t n, int world, const int64_t *weights, std::vector<int64_t> &cuts);   // xm_solver.hip
 // solution recovery behind xm_recover_rotations (xm_capi.hip); variant 1 = the wavefront-per-camera projection kernel, timed when reps > 0
 void recover_rotations(int64_t n, int r, const double *R, const double *s, double *rot, double *scale, int *n_negative_det, int variant,
@@ -278,7 +235,7 @@ private:
     int cur_ = 0;
     DevBuf<double> rR_, rs_, rsB_, pR_, psA_, psB_, vR_, vs_, HvR_, Hvs_, HpR_, Hps_;
     DevBuf<double> partsA_, partsB_, partsM_;
-    DevBuf<double> Prow_, Pcol_;               // symmetric product: row results and per-workgroup column partials
+    SymvWork symv_;                            // symmetric product: its chunk plan, row results and per-workgroup column partials
     DevBuf<double> ksum_;                      // column-split dense product of a small strip: partial sums per (slice, camera)
     DevBuf<unsigned int> kcount_;              //   arrival counters per camera group
     int ks_ = 1;

@@ -541,12 +541,10 @@ void Context::setup_rank(int o) {
     }
     if (comm_->active()) Afull_.ensure(mat * world, st_, mat_top * world); else Afull_.release();
     partsM_.ensure((size_t)std::max(std::max(nB_, flat_grid((int64_t)mat_top) * world), 4 * ((nloc_ + 255) / 256) * world), st_);   // (device-driven outer iteration: one model partial per wavefront of 64 cameras)
-    if (sym_ok_ && o >= 3 && o <= sym_max_o_) {
-        Prow_.alloc(sym_prow_count(nloc_, ld_, o));
-        Pcol_.alloc(sym_pcol_count(nloc_, ld_, o), false);
-    } else {
-        Prow_.release(); Pcol_.release();
-    }
+    // the symmetric product's workspace is made when the rank changes and kept, with the chunk plan it was made under, while it repeats: every
+    // entry the reducer reads is written by the sweep in front of it, so nothing of an earlier run gets through
+    if (!(sym_ok_ && o >= 3 && o <= sym_max_o_)) symv_.release();
+    else if (!symv_ || symv_.nloc != nloc_ || symv_.ld != ld_ || symv_.o != o) symv_.ensure(nloc_, ld_, o);
     // column-split product for small strips (xm_kernels.hip:qw_dense_ks_kernel): multi-rank dense storage by default
     ks_ = 1;
     if (storage_ == XM_STORAGE_DENSE && !sym_ok_ && cfg_.split_k >= 0) {
@@ -676,11 +674,11 @@ void Context::product(int epi, int o, double alpha, const CamArgs &a) {
     if (storage_ == XM_STORAGE_DENSE && dQ32_ && o == o_ && (epi == EPI_HESS || epi == EPI_AUTO)) {
         // xm_tuning_t.hess_f32: the Hessian products of the tCG read the fp32 copy -- the symmetric pair wherever the f64 path takes it
         // (EPI_AUTO: the same launch computes the candidate's gradient from the f64 Q when the device-driven outer iteration asks for it)
-        if (sym_ok_ && o >= 3 && o <= sym_max_o_ && Pcol_.p) launch_qw_sym_f32(o, epi, dQ32_, dQ_, ld_, W_.p, alpha, a, Prow_.p, Pcol_.p, st_, sym_rev_);
+        if (sym_ok_ && o >= 3 && o <= sym_max_o_ && symv_) launch_qw_sym_f32(o, epi, dQ32_, dQ_, ld_, W_.p, alpha, a, symv_, st_, sym_rev_);
         else { CamArgs ar = a; ar.rev = sym_rev_; launch_qw_dense_f32(o, epi, dQ32_, dQ_, ld_, W_.p, alpha, ar, st_); }
     } else if (storage_ == XM_STORAGE_DENSE) {
         if (symw_ && o == o_ && o >= 3 && o <= sym_max_o_ && epi != EPI_CERT) product_symw(epi, o, alpha, a);
-        else if (sym_ok_ && o == o_ && o >= 3 && o <= sym_max_o_ && epi != EPI_CERT && Pcol_.p) launch_qw_sym(o, epi, dQ_, ld_, W_.p, alpha, a, Prow_.p, Pcol_.p, st_, sym_rev_);
+        else if (sym_ok_ && o == o_ && o >= 3 && o <= sym_max_o_ && epi != EPI_CERT && symv_) launch_qw_sym(o, epi, dQ_, ld_, W_.p, alpha, a, symv_, st_, sym_rev_);
         else { CamArgs ar = a; ar.rev = sym_rev_; launch_qw_dense(o, epi, dQ_, ld_, W_.p, alpha, ar, st_); }
     } else if (storage_ == XM_STORAGE_SCHUR) {
         schur_->product(o, epi, W_.p, alpha, a, st_);
@@ -1443,7 +1441,7 @@ static void tridiag_min(const std::vector<double> &a, const std::vector<double> 
 // by products with the same Q*W kernel (rank-1 input).  Lam_/dz live in ps_[cur^1].S0 / .egs (free at this point).
 // ------------------------------------------------------------------------------------------------------------------
 void Context::cert_product(const double *vj, const CamArgs &a, int j) {
-    if (storage_ == XM_STORAGE_DENSE && sym_ok_ && Pcol_.p) launch_qw_sym(1, EPI_CERT, dQ_, ld_, vj, 1.0, a, Prow_.p, Pcol_.p, st_, j);
+    if (storage_ == XM_STORAGE_DENSE && sym_ok_ && symv_) launch_qw_sym(1, EPI_CERT, dQ_, ld_, vj, 1.0, a, symv_, st_, j);
     else if (storage_ == XM_STORAGE_DENSE) launch_qw_dense(1, EPI_CERT, dQ_, ld_, vj, 1.0, a, st_);
     else if (storage_ == XM_STORAGE_SCHUR) schur_->product(1, EPI_CERT, vj, 1.0, a, st_);
     else if (sell_) launch_qw_sell(1, EPI_CERT, *sell_, vj, 1.0, a, 0, st_);
