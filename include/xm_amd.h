@@ -729,6 +729,72 @@ typedef struct {
     double *Lam, *dz, *SX;
 } xm_rtr_probe_t;
 int xm_ctx_rtr_probe(xm_ctx_t *ctx, xm_rtr_probe_t *probe);
+/* The other half of an outer iteration stage by stage, a test export (tests/test_gpu_outer_stages.py): the retraction with the model decrease
+ * it delivers, and one step launch of the device-driven outer iteration.  As xm_ctx_rtr_probe: the context's own setup for rank o, its product
+ * dispatch, the launchers, grids and arguments of a solve (the step launch's arguments come from the function a solve takes them from);
+ * matrices 3n x o column-major, vectors n; every array whose pointer is not null is filled; single-rank contexts only (XM_ERR_ARG otherwise, and
+ * for o outside 3..10, non-finite input, a wrong struct_size, XM_OUTER_PROBE_STEP where the device-driven outer iteration does not apply).
+ * The gradient stage runs first at (R, s) as in xm_ctx_rtr_probe (through the EPI_AUTO launch with XM_OUTER_PROBE_AUTO and with
+ * XM_OUTER_PROBE_STEP) -> f, rr, rgR, rgs.  The retraction is the context's (that of its last solve), or XM_OUTER_PROBE_POLAR / _MGS; polar says which.
+ *   XM_OUTER_PROBE_RETRACT     launch_retract_model of the step v = (vR, vs; vs[0] taken as 0) with Hv = (HvR, Hvs) and the gradient stage's rg,
+ *                      then outer_finalize_kernel -> ret_Rc, ret_sc, ret_W (native pitch) and ret_Wpad (16 n; w_native / wpad say which the
+ *                      context keeps), ret_partsM (up to 1024, nM used), model = the sum the result kernel hands to the host.
+ *                      With XM_OUTER_PROBE_MODEL_REC the launch runs without Hv: ret_partsM keeps what the caller put there, model = scal_in.model
+ *   XM_OUTER_PROBE_RETRACT_LS  launch_retract(D, no ds, t, no sout): the line search's form -> ls_Rc, ls_W
+ *   XM_OUTER_PROBE_STEP        one outer_step_kernel launch from scal_in (all fields), os_in, delta_bar, gradtol, max_outer, stop_req and the tCG
+ *                      vectors p, r, v, Hv (none with _MODEL_REC); slot: the launch pair's index (its parity picks the parity copies and the sweep direction).
+ *                      scal_in.phase 0 (PH_TCG): the EPI_AUTO Hessian product of p first -> HpR, Hps, pHp, rHp, HpHp; scal_in.iter > 0 needs
+ *                      partsB_in (nB).  1 (PH_CAND): the candidate (Rc, sc) and partsM_in (one partial per wavefront of 64 cameras) are given;
+ *                      the EPI_AUTO product in its gradient role at the candidate first -> cand_G .. cand_rgs, f_cand, rr_cand (the two sums by
+ *                      the result kernel's tree) and m_cand (the partials regrouped four by four and summed by the same tree; scal_in.model with
+ *                      _MODEL_REC).  3 (PH_INIT), 2 (PH_STOP): the launch alone.
+ *                      -> scal_out, os_out, progress (run: the run number in it), trace (record os_in.k + 1; trace_written says whether the launch
+ *                      wrote it), grid, nwave, and out_*: every array the launch may write (those a role leaves alone come back with their
+ *                      input bits; the candidate's buffers start as a copy of the point unless given)
+ * Pad columns (even ranks: the pitch is o + 1): before a retraction the pad column of every copy it writes holds ones; ret_pad / ls_pad / out_pad
+ * (scal_in.phase 0 only) count the entries that are not zero afterwards in Rc, W and the padded copy (-1: the context keeps no such copy).
+ * Solver state: as after xm_ctx_rtr_probe. */
+#define XM_OUTER_PROBE_RETRACT    1u
+#define XM_OUTER_PROBE_MODEL_REC  2u
+#define XM_OUTER_PROBE_RETRACT_LS 4u
+#define XM_OUTER_PROBE_STEP       8u
+#define XM_OUTER_PROBE_POLAR      16u
+#define XM_OUTER_PROBE_MGS        32u
+#define XM_OUTER_PROBE_AUTO       64u
+typedef struct {
+    double rr, vv, vp, pp, delta, gradnorm, last_step, model;
+    int32_t status, iter, seq, phase;
+} xm_outer_tcg_t;
+typedef struct {
+    double loss, rr_point;
+    int64_t totalite;
+    int32_t shrink_count, k, stop_reason, time_up, slots, pad;
+} xm_outer_scal_t;
+typedef struct {
+    uint32_t struct_size;
+    uint32_t flags;
+    int32_t o, slot;
+    double lam, t;
+    const double *R, *s, *vR, *vs, *HvR, *Hvs, *D, *pR, *ps, *rR, *rs, *Rc, *sc, *partsB_in, *partsM_in;
+    int32_t partsB_in_count, partsM_in_count;
+    xm_outer_tcg_t scal_in;
+    xm_outer_scal_t os_in;
+    double delta_bar, gradtol;
+    int32_t max_outer, stop_req;
+    int32_t product_kind, nA, nB, nM, w_native, wpad, polar, grid, nwave, trace_written;
+    uint32_t run, pad;
+    int32_t ret_pad[3], ls_pad[2], out_pad[2], pad2;
+    double f, rr, model, pHp, rHp, HpHp, f_cand, rr_cand, m_cand;
+    uint64_t progress;
+    xm_outer_tcg_t scal_out;
+    xm_outer_scal_t os_out;
+    double trace[6];
+    double *rgR, *rgs, *ret_Rc, *ret_sc, *ret_W, *ret_Wpad, *ret_partsM, *ls_Rc, *ls_W, *HpR, *Hps;
+    double *cand_G, *cand_egs, *cand_S0, *cand_rgR, *cand_rgs;
+    double *out_R, *out_s, *out_Rc, *out_sc, *out_vR, *out_vs, *out_HvR, *out_Hvs, *out_rR, *out_rs, *out_pR, *out_ps, *out_W, *out_Wpad;
+    double *out_partsB, *out_partsM, *out_G, *out_egs, *out_S0, *out_rgR, *out_rgs;
+} xm_outer_probe_t;
+int xm_ctx_outer_probe(xm_ctx_t *ctx, xm_outer_probe_t *probe);
 /* Large block-sparse Q: "sliced ELL over per-XCD column slabs" (xm-code_amd/csrc/xm_sell.h).  Same product as xm_qw_bsr3
  * (the reference has no sparse product: Dense/matmul.h:42-87 on a dense Q); the matrix is described on the HOST as 3x3-block CSR
  * (rows n, global columns in [0, ncols)) and re-laid on the device.  slabs in {1,2,4,8}; lmax = longest virtual row (hub

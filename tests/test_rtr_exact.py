@@ -87,10 +87,19 @@ def test_f64_run_agrees_with_longdouble_on_every_gpu_case():
         assert F["branch"] == E["branch"] and F["scal"]["iter"] == E["scal"]["iter"]
         for k, e in _cg_errors(F, E).items():
             assert e <= rs.MAX_E_REF, (c["id"], o, name, k, e)
+    # the outer iteration's other half (test_gpu_outer_stages.py): both retractions, the line search's form and the model decrease
+    worst = {}
+    for c in rs.OUTER_CONTEXTS:
+        for o in rs.RETRACT_RANKS:
+            for name, errs in rs.retract_case(c["mk"], o)["e_ref"].items():
+                for k, v in errs.items():
+                    assert v <= rs.MAX_E_REF, (c["id"], o, name, k, v)
+                    worst[name + "." + k] = max(worst.get(name + "." + k, 0.0), v)
+    print("E_REF worst per quantity of the retraction: " + ", ".join(f"{k} {v:.1e}" for k, v in worst.items()))
 
 
-def _cg_cases():
-    for c in rs.CG_CONTEXTS:
+def _cg_cases(contexts=None):
+    for c in contexts or rs.CG_CONTEXTS + rs.STEP_CONTEXTS:
         for o in c["ranks"]:
             for name in c["names"]:
                 mk = c["mk_neg"] if name == "negative" else c["mk"]
@@ -135,6 +144,39 @@ def test_cg_step_cases_take_their_branch_with_a_margin():
 
 
 FAULT_CASES = [("dense-n5", 3), ("dense-n43", 4), ("dense-n86", 5), ("bsr-n17", 3), ("sym-n9", 3)]
+OUTER_FAULTS = ("m_no_scale", "m_metric_s", "anchor_scale", "mgs_raw_row", "rou_sign", "double_any")
+
+
+def _decide_inputs(b, f=7.25, m=-0.8, rr_new=3.0):
+    """the decision's inputs for one branch of rs.decide_branches around given sums: the loss is placed so that rho hits the branch's target"""
+    m = 0.3 if b["rho"] is None else m
+    loss = f + 1.0 if b["rho"] is None else f - b["rho"] * m
+    sc = dict(delta=b["delta"], status=b["status"], iter=b["iter"], phase=ex.PH_CAND, seq=5)
+    os_ = dict(loss=loss, rr_point=4.0, totalite=11, shrink_count=b["shrink"], k=b["k"], time_up=b["time_up"], slots=9)
+    return sc, os_, (f, rr_new, m, b["delta_bar"], b["gradtol"], b["max_outer"] or 1000, b["stop_req"])
+
+
+def _outer_faults(fault):
+    """the new faults in the f64 run: the retraction's and the model's against the longdouble reference with the bound, the decision's (plain f64
+    code compared exactly) as any output that differs"""
+    broken = []
+    for c in rs.OUTER_CONTEXTS[:3]:
+        for o in (3, 4):
+            case = rs.retract_case(c["mk"], o)
+            pt, E, e_ref = case["pt"], case["E"], case["e_ref"]
+            ds = case["v"][1]                              # (0.9 at the anchor)
+            F = ex.retract_stage(pt["R"], pt["s"], case["v"][0], ds, 1.0, False, np.float64, fault)
+            broken += [(c["id"], o, k, rs.error(F[k], E["mgs"], k)[0]) for k in rs.RETRACT_KEYS if rs.error(F[k], E["mgs"], k)[0] > st.bound(e_ref["mgs"][k])]
+            g = ex.grad_stage(ex.Op(rs.matrix(*c["mk"])["Q"]) if rs.matrix(*c["mk"])["Q"] is not None else rs.matrix(*c["mk"])["op"], pt["R"], pt["s"], case["lam"], np.float64)
+            Fm = ex.model_stage(case["v"], case["Hv"], (g["rgR"], g["rgs"]), pt["s"], np.float64, fault)
+            e = rs.error(Fm["m"], E["model"], "m")[0]
+            if e > st.bound(e_ref["model"]["m"]):
+                broken.append((c["id"], o, "m", e))
+    for b in rs.decide_branches():
+        sc, os_, rest = _decide_inputs(b)
+        good, bad = ex.outer_decide_stage(sc, os_, *rest), ex.outer_decide_stage(sc, os_, *rest, damage=fault)
+        broken += [("decide-" + b["name"], 0, k, 1.0) for k in good if good[k] != bad[k]]
+    return broken
 
 
 @pytest.mark.parametrize("fault", ex.FAULTS + (None,))
@@ -142,17 +184,20 @@ def test_every_deliberate_fault_breaks_the_bound(fault):
     """the faults a trust region survives (it converges to the same certified optimum, only more slowly) planted in the f64 run: no S0 term; no
     ps s egs; the anchor not masked in egs, in hs and rhs, in the direction's scale part; sym replaced by the unsymmetrised product; s^2 - 1 for
     3 s^2 - 1; rr_est without its cross term; tau's other root; the vp recurrence without beta; the anchor's multipliers from five generators;
-    dz on the wrong row.  (The masks of hs and of rs at the anchor are each covered by a second one -- rhs is masked as well, and rs only ever
+    dz on the wrong row; the scale term of the model decrease dropped; its metric 1 / s for 1 / s^2; the anchor's scale moved by the retraction;
+    the second Gram-Schmidt projection against the unnormalised row; rho with the sign of m flipped; the radius doubled whatever ended the tCG.  (The masks of hs and of rs at the anchor are each covered by a second one -- rhs is masked as well, and rs only ever
     multiplies rhs -- so one of them missing alone changes no output: they are planted together with the mask that covers them.)"""
     broken = []
+    if fault in OUTER_FAULTS or fault is None:
+        broken += _outer_faults(fault)
     if fault in ("rr_est_no_cross", "tau_root", "vp_no_beta", None):
-        for c, o, name, case in _cg_cases():
+        for c, o, name, case in _cg_cases(rs.CG_CONTEXTS):
             if c["id"] != "cg-dense":
                 continue
             E = case["expect"]
             e_ref, e = _cg_errors(_cg_run(case, np.float64), E), _cg_errors(_cg_run(case, np.float64, fault), E)
             broken += [(name, o, k, e[k]) for k in e if e[k] > st.bound(e_ref[k])]
-    if fault not in ("rr_est_no_cross", "tau_root", "vp_no_beta"):
+    if fault not in ("rr_est_no_cross", "tau_root", "vp_no_beta") + OUTER_FAULTS:
         by_id = {p["id"]: p for p in rs.PATHS}
         for pid, o in FAULT_CASES:
             p = by_id[pid]
@@ -169,3 +214,80 @@ def test_every_deliberate_fault_breaks_the_bound(fault):
                     broken.append((pid, o, k, e))
     print(f"FAULT {fault}: " + ", ".join(f"{a}-o{b} {k} {e:.1e}" for a, b, k, e in broken[:6]))
     assert (not broken) if fault is None else broken, (fault, broken[:6])    # None: the control -- the same loop without a fault reports nothing
+
+
+def test_f_above_loss_in_the_reject_test_changes_nothing():
+    """`f > loss` of trustregion.h:702 cannot be reached alone: the test is only looked at with m < 0, where f > loss gives rho = (f - loss) / m
+    <= -0 < 0.1.  So the fault "f > loss dropped" (ex.EQUIVALENT_FAULTS) breaks no output, here over every branch and a grid of sums that
+    includes f a hair above the loss, equal to it and far from it, and m from tiny to huge -- it is listed apart from ex.FAULTS for that reason,
+    and no GPU case can exist for "reject by f > loss with rho >= 0.1"."""
+    assert ex.EQUIVALENT_FAULTS == ("no_f_gt_loss",) and not set(ex.EQUIVALENT_FAULTS) & set(ex.FAULTS)
+    count = 0
+    for b in rs.decide_branches():
+        for m in (-1e-300, -1e-12, -0.8, -1e12, -1e300):
+            for gap in (0.0, 5e-324, 1e-300, 2.0 ** -52, 1e-3, 1.0, 1e300, -1e-3, -2.0 ** -52):
+                sc, os_, rest = _decide_inputs(b)
+                os_["loss"] = 7.25
+                f = np.nextafter(7.25, np.inf) if gap == 2.0 ** -52 else np.nextafter(7.25, -np.inf) if gap == -2.0 ** -52 else 7.25 + gap
+                rest = (f, rest[1], m) + rest[3:]
+                with np.errstate(over="ignore"):            # (rho = -inf at the corners of the grid)
+                    assert ex.outer_decide_stage(sc, os_, *rest) == ex.outer_decide_stage(sc, os_, *rest, damage="no_f_gt_loss"), (b["name"], m, gap)
+                count += 1
+    assert count > 500
+
+
+def test_decision_branches_are_reached_with_a_margin():
+    """every branch of rs.decide_branches comes out as listed from the plain f64 restatement, and every target rho keeps a relative distance
+    of more than MARGIN from the thresholds 0.1, 0.25 and 0.75, so the kernel's own sums (a few round-offs from any others) take the same branch"""
+    for rho in rs.RHO_TARGETS:
+        assert min(abs(rho - t) / t for t in (0.1, 0.25, 0.75)) > 1e3 * rs.MARGIN
+    seen = set()
+    for b in rs.decide_branches():
+        sc, os_, rest = _decide_inputs(b)
+        out = ex.outer_decide_stage(sc, os_, *rest)
+        for k, v in b["expect"].items():
+            assert out[k] == v, (b["name"], k, out[k], v)
+        assert (out["trace"] is None) == (out["stop_reason"] in (12, 13, 14)), b["name"]
+        assert out["phase"] == (ex.PH_TCG if out["start"] else ex.PH_STOP)
+        seen.add(out["stop_reason"])
+    assert seen == {0, 5, 10, 11, 12, 13, 14}
+    init = ex.outer_decide_stage(dict(delta=2.0, status=0, iter=0, phase=ex.PH_INIT, seq=3), dict(loss=1.0, rr_point=4.0, totalite=0, shrink_count=0, k=0, time_up=0), 0, 0, 0, 1, 0, 1000, 0)
+    assert (init["phase"], init["rr"], init["gradnorm"], init["delta"], init["k"], init["accept"], init["start"], init["trace"]) == (ex.PH_TCG, 4.0, 2.0, 2.0, 0, False, True, None)
+    assert ex.outer_decide_stage(dict(phase=ex.PH_STOP), {}, 0, 0, 0, 1, 0, 1000, 0)["passed"]
+
+
+@pytest.mark.parametrize("n,o,polar", [(5, 3, False), (20, 4, True), (43, 10, False), (43, 5, True)])
+def test_the_retraction_is_a_retraction(n, o, polar):
+    """Rn Rn^T = I to longdouble round-off, the anchor's scale stays, and d/dt at 0 is the tangent step: central differences at two step
+    sizes, the error quartering (the curve is smooth), for the rows and for s exp(t ds / s)"""
+    case = rs.retract_case(("dense", n, 0), o)
+    pt, v = case["pt"], case["v"]
+    E = ex.retract_stage(pt["R"], pt["s"], v[0], v[1], 1.0, polar, LD)
+    gram = np.einsum("iak,ibk->iab", E["Rc"], E["Rc"]) - np.eye(3)
+    assert float(np.abs(gram).max()) <= 64 * float(np.finfo(LD).eps)
+    assert E["sc"][0] == 1 and float(np.abs(E["W"] - E["Rc"] * E["sc"][:, None, None]).max()) == 0.0
+    R1 = ex.polar_rows(ex.blk(pt["R"].astype(LD), n)).reshape(3 * n, o)     # on the manifold to longdouble precision, and v tangent there
+    vR, vs = ex.tangent(R1, v[0].astype(LD), v[1].astype(LD))
+    errs = []
+    for h in (1e-3, 5e-4):
+        P, Mn = (ex.retract_stage(R1, pt["s"], vR, vs, t, polar, LD) for t in (h, -h))
+        dR, ds = (P["Rc"] - Mn["Rc"]) / (2 * LD(h)), (P["sc"] - Mn["sc"]) / (2 * LD(h))
+        errs.append((float(np.abs(dR - ex.blk(vR, n)).max()), float(np.abs(ds - vs).max())))
+    for e1, e2 in zip(*errs):
+        assert e2 <= 1e-4 and 3.5 <= e1 / e2 <= 4.5, errs
+
+
+@pytest.mark.parametrize("n,o,lam", [(5, 3, 10.0), (20, 4, 1000.0), (43, 7, 0.0)])
+def test_model_decrease_is_the_second_order_expansion_of_the_cost(n, o, lam):
+    """m(v) = <v, rg> + <v, Hv> / 2 with Hv from hess_stage against D1 + D2 / 2, the central first and second differences of the cost along
+    curve() with velocity v: within the scheme's truncation error estimated from two step sizes, as in the test of the derivatives above"""
+    op, pt, g, p, u = _fd_case(n, o, lam, 53 * n + o)
+    H = ex.hess_stage(op, g, *p, *u, lam, LD)
+    m = ex.model_stage(p, (H["HpR"].reshape(3 * n, o), H["Hps"]), (g["rgR"].reshape(3 * n, o), g["rgs"]), pt["s"], LD)
+    assert abs(float(m["m"] - m["m_cam"].sum())) == 0.0
+    h = 1e-3
+    (a1, a2), (b1, b2) = _differences(op, pt, lam, p, h), _differences(op, pt, lam, p, h / 2)
+    e1, e2 = float(abs(a1 + a2 / 2 - m["m"])), float(abs(b1 + b2 / 2 - m["m"]))
+    print(f"FD model n={n} o={o}: {e1 / float(abs(m['m'])):.2e} at h, {e2 / float(abs(m['m'])):.2e} at h/2, ratio {e1 / e2:.3f}")
+    assert e2 <= 1.5 * (float(abs(a1 - b1)) + float(abs(a2 - b2)) / 2) / 3
+    assert e2 <= 1e-4 * float(m["m~"])

@@ -17,8 +17,12 @@ import numpy as np
 
 LD = np.longdouble
 FAULTS = ("no_S0", "no_ps_s_egs", "anchor_egs", "anchor_rhs", "anchor_ps", "nosym", "lam_s2", "rr_est_no_cross", "tau_root", "vp_no_beta", "lam5",
-          "dz_row")
+          "dz_row") + ("m_no_scale", "m_metric_s", "anchor_scale", "mgs_raw_row", "rou_sign", "double_any")
+# a fault that changes no output, kept apart: `f > loss` dropped from the reject test of trustregion.h:702.  With m < 0 (the only way to the test)
+# f > loss makes rou = (f - loss) / m negative (or -0), so rou < 0.1 rejects as well; tests/test_rtr_exact.py pins that over a grid.
+EQUIVALENT_FAULTS = ("no_f_gt_loss",)
 MAX_INNER = 1000   # trustregion.h:416
+PH_TCG, PH_CAND, PH_STOP, PH_INIT = 0, 1, 2, 3   # what a (product, step) pair of the device-driven outer iteration does (xm_common.h: Phase)
 
 
 class Op:
@@ -374,3 +378,110 @@ def curve(R, s, pR, ps, t, dt=LD):
     Rt = polar_rows(blk(R + t * np.asarray(pR).astype(dt), n)).reshape(R.shape)
     st = s * np.exp(t * np.asarray(ps).astype(dt) / s)
     return Rt, st
+
+
+def mgs_rows(M, damage=None):
+    """rows of a batch of 3 x o blocks by modified Gram-Schmidt in the order of Dense/batchedQR.h:42-67: normalise row i, then take its
+    component out of every later row"""
+    q = M.copy()
+    for i in range(3):
+        raw = q[:, i, :].copy()
+        q[:, i, :] = raw / np.sqrt((raw * raw).sum(axis=1))[:, None]
+        for j in range(i + 1, 3):
+            a = raw if (damage == "mgs_raw_row" and i == 1) else q[:, i, :]
+            uu = (a * q[:, j, :]).sum(axis=1)
+            q[:, j, :] = q[:, j, :] - uu[:, None] * a
+    return q
+
+
+def retract_stage(R, s, D, ds, t, polar, dt=LD, damage=None):
+    """the retraction of trustregion.h:667-678 (and of its line search with ds = None): Rn = rows of R + t D by modified Gram-Schmidt or the
+    polar factor, sn = s exp(t ds / s) with the anchor left alone (trustregion.h:19-24), the next product input W = sn .* Rn (:677)"""
+    R, s = point(R, s, dt)
+    n, t = s.size, dt(t)
+    M = blk(R + t * np.asarray(D).astype(dt), n)
+    Rn = polar_rows(M) if polar else mgs_rows(M, damage)
+    if ds is None:
+        sn = s.copy()
+    else:
+        sn = s * np.exp(t * np.asarray(ds).astype(dt) / s)
+        if damage != "anchor_scale":
+            sn[0] = s[0]
+    one = np.ones(n, dtype=dt)
+    return {"Rc": Rn, "Rc~": one, "sc": sn, "sc~": sn, "W": Rn * sn[:, None, None], "W~": sn}
+
+
+def model_stage(v, Hv, rg, s, dt=LD, damage=None):
+    """the model decrease of the step v, m = <v, Hv> / 2 + <v, rg> in the product metric (trustregion.h:667-668), per camera and summed; the
+    anchor's scale part of a step is 0.  Hv = None: no such sum is formed (XM_FLAG_MODEL_RECURRENCE)"""
+    cv = lambda a: np.asarray(a).astype(dt)
+    s = cv(s).copy(); s[0] = 1
+    n = s.size
+    vR, vs, HvR, Hvs, rgR, rgs = blk(cv(v[0]), n), cv(v[1]).copy(), blk(cv(Hv[0]), n), cv(Hv[1]), blk(cv(rg[0]), n), cv(rg[1])
+    vs[0] = 0
+    metric = s if damage == "m_metric_s" else s * s
+    mR = (vR * (HvR / 2 + rgR)).sum(axis=(1, 2))
+    ms = vs / metric * (Hvs / 2 + rgs)
+    if damage == "m_no_scale":
+        ms = ms * 0
+    am = (np.abs(vR) * (np.abs(HvR) / 2 + np.abs(rgR))).sum(axis=(1, 2)) + np.abs(vs) / (s * s) * (np.abs(Hvs) / 2 + np.abs(rgs))
+    return {"m_cam": mR + ms, "m": (mR + ms).sum(), "m~": am.sum()}
+
+
+def outer_decide_stage(sc, os, f, rr_new, m, delta_bar, gradtol, max_outer, time_up, damage=None):
+    """what the step launch of the device-driven outer iteration decides between two truncated CGs, in plain f64 scalar code: the trust-region
+    update of trustregion.h:680-708 and the stop tests of :527-543 as Context::trust_region has them.  sc: the tCG's scalar block (delta, status,
+    iter, phase), os: the trust region's (loss, rr_point, totalite, shrink_count, k, time_up, slots), f / rr_new / m: the candidate's cost and
+    squared gradient norm and the model decrease, time_up: the host's stop-request word.  PH_INIT starts the first tCG and decides nothing,
+    PH_STOP passes both blocks on.  Returns the next blocks' fields, stop_reason, accept, start and the trace record (None if none is written)."""
+    F = np.float64
+    phase = int(sc["phase"])
+    if phase == PH_STOP:
+        return dict(phase=PH_STOP, passed=True, accept=False, start=False, trace=None)
+    loss, rr, delta = F(os["loss"]), F(os["rr_point"]), F(sc["delta"])
+    shrink, k, totalite, stop = int(os["shrink_count"]), int(os["k"]), int(os["totalite"]), 0
+    accept, start, trace = False, True, None
+    if phase == PH_CAND:
+        f, rr_new, m = F(f), F(rr_new), F(m)
+        endreason = 6 if int(sc["status"]) == 0 else int(sc["status"])
+        inner_print, trstatus = int(sc["iter"]) + 1, 4
+        totalite += int(sc["iter"]) + 1
+        if m >= 0:                                         # "loss_qu is larger than 0": the point stays
+            stop, start = 12, False
+        else:
+            rou = (f - loss) / (-m if damage == "rou_sign" else m)    # :680
+            if rou < 0.25:
+                delta, trstatus, shrink = delta * F(0.25), 1, shrink + 1
+            elif rou > 0.75 and (endreason <= 2 or damage == "double_any"):
+                delta, trstatus, shrink = min(delta * 2, F(delta_bar)), 2, 0
+            else:
+                shrink = 0
+            stop_delta = False
+            if shrink > 3:                                 # :692-700
+                delta, shrink = delta * F(1e-3), 0
+                stop_delta = bool(delta < 1e-20)
+            reject = bool((f > loss and damage != "no_f_gt_loss") or rou < 0.1)   # :702
+            accept = stop_delta or not reject
+            if stop_delta:                                 # the reference leaves the new point in place but reports loss[k]
+                stop, start = 13, False
+            else:
+                if not reject:
+                    loss, rr = f, rr_new
+                else:
+                    trstatus = 3
+                k += 1
+                if k >= int(max_outer):
+                    stop, start = 14, False
+                else:
+                    trace = (float(loss), float(np.sqrt(rr)), float(inner_print), float(endreason), float(trstatus), float(delta))
+                    if endreason == 5:
+                        stop = 5
+                    elif np.sqrt(rr) < F(gradtol):
+                        stop = 10
+                    elif int(os["time_up"]):
+                        stop = 11
+                    start = stop == 0
+    return dict(rr=float(rr), pp=float(rr), delta=float(delta), gradnorm=float(np.sqrt(rr)), vv=0.0, vp=0.0, last_step=0.0, model=0.0, status=0, iter=0,
+                seq=int(sc.get("seq", 0)), phase=PH_TCG if start else PH_STOP, loss=float(loss), rr_point=float(rr), totalite=totalite, shrink_count=shrink,
+                k=k, stop_reason=stop, time_up=int(os["time_up"]) | int(time_up), slots=int(os.get("slots", 0)) + (1 if phase == PH_CAND else 0),
+                accept=accept, start=start, trace=trace, passed=False)

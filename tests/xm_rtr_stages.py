@@ -298,3 +298,93 @@ def cg_inputs(c, nB):
     w = 1.0 + 0.5 * np.cos(np.arange(nB))
     parts = c["rr_total"] * w / w.sum() if c["sc"]["iter"] > 0 else None
     return dict(p=c["pt"]["p"], r=c["r"], cg_step=dict(c["sc"], v=c["v"], Hv=c["Hv"], partsB=parts), model_recurrence=c["model_rec"]), parts
+
+
+# ---------------------------------------------------------------------------------------------------------------- the outer iteration's other half
+# retract_kernel's shapes: 43 cameras = one partly filled wavefront; 131 = three wavefronts (outer_decide's group of four has an absent member);
+# 321 = two workgroups, six wavefronts (two partsM entries, the second with two absent members); ranks with and without the pad column
+RETRACT_RANKS = (3, 4, 5, 10)
+RETRACTIONS = ("mgs", "polar")
+OUTER_CONTEXTS = tuple(dict(id=f"{kind}-n{n}", mk=mk, tuning=tuning, kind=pk)
+                       for n in (43, 131, 321)
+                       for kind, mk, tuning, pk in (("dense", ("dense", n, 0), dict(sym=-1), "dense"),
+                                                    ("sym", ("dense", n, 0), dict(sym=1, sym_min_rows=1), "dense_sym"),
+                                                    ("bsr", ("vg", n, 6), dict(sell=-1), "bsr3")))
+OUTER_IDS = [c["id"] for c in OUTER_CONTEXTS]
+RETRACT_KEYS = ("Rc", "sc", "W")
+LS_T = -0.37              # the line search retracts R - alpha D
+
+
+@functools.lru_cache(maxsize=None)
+def retract_case(mk, o):
+    """a point, a tangent step v whose scale part has t ds / s spread over -5 .. 5 (the exp is nowhere near 1), H v and a line-search direction D;
+    for a tangent D the Gram matrix of a block of R + D is I + D D^T: every block is well conditioned.  -> the longdouble quantities of the
+    gradient, the two retractions, the line search's form and the model decrease, and the f64 run's error per quantity"""
+    M = matrix(*mk)
+    n, lam = M["n"], lam_of(M["n"], o)
+    pt = make_point(n, o, 3000 * n + o)
+    rng = np.random.default_rng(3100 * n + o)
+    s1 = pt["s"].copy(); s1[0] = 1.0
+    v = ex.tangent(pt["R"], 0.4 * rng.standard_normal((3 * n, o)), s1 * rng.uniform(-5.0, 5.0, n))
+    v[1][0] = 0.9                                          # what a caller leaves at the anchor must not get through
+    Hv = ex.tangent(pt["R"], rng.standard_normal((3 * n, o)), rng.standard_normal(n) * s1)
+    D = ex.tangent(pt["R"], rng.standard_normal((3 * n, o)), np.zeros(n))[0]
+    op64 = ex.Op(M["Q"]) if M["Q"] is not None else M["op"]
+    runs = []
+    for dt, op in ((LD, M["op"]), (np.float64, op64)):
+        g = ex.grad_stage(op, pt["R"], pt["s"], lam, dt)
+        E = dict(grad=g, model=ex.model_stage(v, Hv, (g["rgR"], g["rgs"]), pt["s"], dt))
+        for name in RETRACTIONS:
+            E[name] = ex.retract_stage(pt["R"], pt["s"], v[0], v[1], 1.0, name == "polar", dt)
+            E["ls-" + name] = ex.retract_stage(pt["R"], pt["s"], D, None, LS_T, name == "polar", dt)
+        runs.append(E)
+    E, F = runs
+    e_ref = {name: {k: error(F[name][k], E[name], k)[0] for k in RETRACT_KEYS} for name in E if name not in ("grad", "model")}
+    e_ref["model"] = {"m": error(F["model"]["m"], E["model"], "m")[0]}
+    return dict(pt=pt, v=v, Hv=Hv, D=D, lam=lam, E=E, e_ref=e_ref)
+
+
+def regroup4(w):
+    """per-wavefront partial sums four by four in block_sum256's order (w0 + w1) + (w2 + w3), absent members 0: retract_kernel's per-workgroup sums"""
+    w = np.concatenate([np.asarray(w, dtype=np.float64), np.zeros(-len(w) % 4)]).reshape(-1, 4)
+    return (w[:, 0] + w[:, 1]) + (w[:, 2] + w[:, 3])
+
+
+# the step launch: (context, the indefinite matrix of the negative-curvature branch, ranks); the last is the one size at which the tCG-ending role's
+# loop over wavefronts takes a second trip (more than 1024 x 64 cameras)
+STEP_CG = ("interior0", "interior7", "interior0-model")
+STEP_END = ("converged", "boundary", "negative", "tiny", "cap", "boundary-model")
+STEP_CONTEXTS = (dict(id="step-dense-n43", mk=("dense", 43, 0), mk_neg=("dense", 43, 2), tuning=dict(sym=-1), ranks=(3, 4), names=STEP_CG + STEP_END),
+                 dict(id="step-sym-n131", mk=("dense", 131, 0), mk_neg=("dense", 131, 2), tuning=dict(sym=1, sym_min_rows=1), ranks=(4, 5), names=STEP_CG + STEP_END),
+                 dict(id="step-bsr-n321", mk=("vg", 321, 6), mk_neg=("vg_neg", 321, 6), tuning=dict(sell=-1), ranks=(3, 10), names=STEP_CG + STEP_END),
+                 dict(id="step-bsr-n65600", mk=("vg", 65600, 2), mk_neg=None, tuning=dict(sell=-1), ranks=(3,), names=("boundary",)))
+STEP_IDS = [c["id"] for c in STEP_CONTEXTS]
+DECIDE_CONTEXTS = (dict(id="decide-dense-n43", mk=("dense", 43, 0), tuning=dict(sym=-1), o=4), dict(id="decide-bsr-n131", mk=("vg", 131, 6), tuning=dict(sell=-1), o=3),
+                   dict(id="decide-sym-n321", mk=("dense", 321, 0), tuning=dict(sym=1, sym_min_rows=1), o=5))
+RHO_TARGETS = (0.05, 0.2, 0.5, 0.9)                      # each keeps a relative distance > MARGIN from 0.1, 0.25 and 0.75
+
+
+def decide_branches(delta=2.0):
+    """(name, changes to the decision's inputs, what must come out): rho = the target the loss is placed for (None: m >= 0), then the tCG's exit
+    status and iteration count, the radius, the state of the trust region and the limits"""
+    B = []
+    add = lambda name, rho, expect, **kw: B.append(dict(dict(name=name, rho=rho, status=2, iter=4, delta=delta, delta_bar=1e3, gradtol=0.0, max_outer=0, shrink=0,
+                                                             k=3, time_up=0, stop_req=0), expect=expect, **kw))
+    add("reject", 0.05, dict(accept=False, start=True, stop_reason=0, shrink_count=1))
+    add("shrink-accept", 0.2, dict(accept=True, start=True, stop_reason=0, shrink_count=1))
+    add("accept", 0.5, dict(accept=True, start=True, stop_reason=0, shrink_count=0), shrink=2)
+    add("double", 0.9, dict(accept=True, start=True, stop_reason=0, shrink_count=0, delta=2 * delta))
+    add("no-double-at-tolerance", 0.9, dict(accept=True, start=True, stop_reason=0, delta=delta), status=3)
+    add("delta-bar-cap", 0.9, dict(accept=True, start=True, stop_reason=0, delta=1.5 * delta), delta_bar=1.5 * delta)
+    add("fourth-shrink", 0.2, dict(accept=True, start=True, stop_reason=0, shrink_count=0, delta=delta * 0.25 * 1e-3), shrink=3)
+    add("fourth-shrink-reject", 0.05, dict(accept=False, start=True, stop_reason=0, shrink_count=0, delta=delta * 0.25 * 1e-3), shrink=3)
+    add("stop13", 0.05, dict(accept=True, start=False, stop_reason=13), shrink=3, delta=1e-18)
+    add("stop12", None, dict(accept=False, start=False, stop_reason=12))
+    add("stop14", 0.5, dict(accept=True, start=False, stop_reason=14), k=6, max_outer=7)
+    add("stop14-solve-cap", 0.5, dict(accept=True, start=False, stop_reason=14), k=999)
+    add("stop5", 0.5, dict(accept=True, start=False, stop_reason=5), status=5)
+    add("stop10", 0.5, dict(accept=True, start=False, stop_reason=10), gradtol=1e30)
+    add("stop11", 0.5, dict(accept=True, start=False, stop_reason=11), time_up=1)
+    add("time-request-is-passed-on", 0.5, dict(accept=True, start=True, stop_reason=0, time_up=1), stop_req=1)
+    add("max-iterations", 0.9, dict(accept=True, start=True, stop_reason=0, delta=delta), status=0, iter=999)
+    return B

@@ -498,6 +498,59 @@ int xm_ctx_rtr_probe(xm_ctx_t *ctx, xm_rtr_probe_t *pr) {
     return XM_OK;
     XM_CATCH
 }
+int xm_ctx_outer_probe(xm_ctx_t *ctx, xm_outer_probe_t *pr) {
+    XM_TRY
+    if (!ctx || !pr) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: null argument");
+    if (pr->struct_size != sizeof(xm_outer_probe_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: xm_outer_probe_t.struct_size is not sizeof(xm_outer_probe_t)");
+    if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: single-GPU contexts only (not n_gpus > 1)");
+    if (ctx->impl->world() > 1 || ctx->impl->comm_kind() != 0) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: single-rank contexts only");
+    if (pr->o < 3 || pr->o > 10) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: rank o must be in 3..10");
+    const uint32_t known = XM_OUTER_PROBE_RETRACT | XM_OUTER_PROBE_MODEL_REC | XM_OUTER_PROBE_RETRACT_LS | XM_OUTER_PROBE_STEP | XM_OUTER_PROBE_POLAR |
+                           XM_OUTER_PROBE_MGS | XM_OUTER_PROBE_AUTO;
+    if (pr->flags & ~known) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: unknown flag");
+    if ((pr->flags & XM_OUTER_PROBE_POLAR) && (pr->flags & XM_OUTER_PROBE_MGS)) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: one retraction at a time");
+    if (!pr->R || !pr->s) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: the point (R, s) is missing");
+    const bool ret = pr->flags & XM_OUTER_PROBE_RETRACT, ls = pr->flags & XM_OUTER_PROBE_RETRACT_LS, step = pr->flags & XM_OUTER_PROBE_STEP;
+    const bool rec = pr->flags & XM_OUTER_PROBE_MODEL_REC;
+    if ((ret || step) && !(pr->vR && pr->vs && (rec || (pr->HvR && pr->Hvs))))
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: the retraction and the step launch need v (and Hv unless XM_OUTER_PROBE_MODEL_REC)");
+    if (ls && !pr->D) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: XM_OUTER_PROBE_RETRACT_LS needs D");
+    if (step && !(pr->pR && pr->ps && pr->rR && pr->rs)) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: XM_OUTER_PROBE_STEP needs p and r");
+    if ((pr->Rc == nullptr) != (pr->sc == nullptr)) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: Rc and sc go together");
+    const int64_t n = ctx->impl->cameras(), mat = 3 * n * pr->o;
+    auto finite = [](const double *x, int64_t len, const char *what) {
+        if (!x) return;
+        for (int64_t k = 0; k < len; ++k)
+            if (!std::isfinite(x[k])) throw xm::Error(XM_ERR_ARG, std::string("xm_ctx_outer_probe: ") + what + " is not finite");
+    };
+    const double sv[2] = {pr->lam, pr->t};
+    finite(sv, 2, "lam or t");
+    finite(pr->R, mat, "R"); finite(pr->s, n, "s"); finite(pr->vR, mat, "vR"); finite(pr->vs, n, "vs"); finite(pr->HvR, mat, "HvR"); finite(pr->Hvs, n, "Hvs");
+    finite(pr->D, mat, "D"); finite(pr->pR, mat, "pR"); finite(pr->ps, n, "ps"); finite(pr->rR, mat, "rR"); finite(pr->rs, n, "rs");
+    finite(pr->Rc, mat, "Rc"); finite(pr->sc, n, "sc");
+    if (pr->partsB_in_count < 0 || pr->partsM_in_count < 0) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: a negative count");
+    finite(pr->partsB_in, pr->partsB_in_count, "partsB_in"); finite(pr->partsM_in, pr->partsM_in_count, "partsM_in");
+    if (ret || step) {
+        const xm_outer_tcg_t &sc = pr->scal_in;
+        const double v[8] = {sc.rr, sc.vv, sc.vp, sc.pp, sc.delta, sc.gradnorm, sc.last_step, sc.model};
+        finite(v, 8, "scal_in");
+    }
+    if (step) {
+        const xm_outer_tcg_t &sc = pr->scal_in;
+        if (sc.iter < 0 || sc.iter >= 1000) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: scal_in.iter must be in 0..999");
+        if (sc.phase < 0 || sc.phase > 3) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: scal_in.phase must be 0 (tCG), 1 (candidate), 2 (stop) or 3 (init)");
+        if (pr->slot < 0) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: slot must not be negative");
+        const double w[4] = {pr->os_in.loss, pr->os_in.rr_point, pr->delta_bar, pr->gradtol};
+        finite(w, 4, "os_in, delta_bar or gradtol");
+        if (pr->os_in.k < 0 || pr->os_in.k >= 1000 || pr->max_outer < 0) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: os_in.k must be in 0..999 and max_outer >= 0");
+    }
+    for (const double *sp : {pr->s, pr->sc})
+        for (int64_t i = 0; sp && i < n; ++i)
+            if (!(sp[i] > 0.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_outer_probe: scales must be positive");
+    ctx->impl->outer_probe(*pr);
+    return XM_OK;
+    XM_CATCH
+}
 namespace {
 void clean_settings(const char *who, const xm_clean_options_t *opt, const uint8_t *keep, const int32_t *cam_index, const int32_t *lm_index,
                     const xm_clean_result_t *res, xm::CleanSettings &c) {

@@ -161,6 +161,7 @@ public:
     // reprojection bundle adjustment of a recovered solution (xm_ba.h): matrix-free storage, one rank; reads the context, changes nothing in it
     void bundle_adjust(const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out);
     void ba_probe(const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q);   // test export
+    void outer_probe(xm_outer_probe_t &q);   // test export (xm_ctx_outer_probe): the retraction and the device-driven step launch stage by stage
     void rtr_probe(xm_rtr_probe_t &q);   // test export (include/xm_amd.h: xm_ctx_rtr_probe): the trust region's kernels stage by stage
     void reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr);   // per observation, input order (xm_ba.h)
     // which observations, cameras and landmarks of the list survive cleaning at the current weights (xm_clean.h); changes nothing here
@@ -301,6 +302,7 @@ private:
     // and watches a progress word; entered from trust_region() after the first cost / gradient (f, rr at the starting point)
     bool device_outer_applies(int o) const;
     TrResult trust_region_device(int o, double &gradtol, double f, double rr, double delta, double delta_bar, double max_time);
+    OuterStepArgs outer_step_args(int slot, bool model_rec, double delta_bar, double gradtol, unsigned int runid) const;
     DevBuf<double> trace_dev_;           // device copy of the outer-iteration trace (kMaxOuter records)
     DevBuf<int> stop_req_;               // set by the host when its time limit has expired
     DevBuf<OuterScal> oscal_;            // trust-region state of the device-driven outer iteration, two parity copies next to scal_

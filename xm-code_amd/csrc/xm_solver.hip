@@ -1182,12 +1182,43 @@ bool Context::device_outer_applies(int o) const {
     return true;
 }
 
+// The step launch's arguments for launch pair `slot` of run `runid` (trust_region_device() and the test export outer_probe() take them from here).
+OuterStepArgs Context::outer_step_args(int slot, bool model_rec, double delta_bar, double gradtol, unsigned int runid) const {
+    const int nA = prod_grid(), nB = tcg_blocks(), nM = retract_grid(nloc_);
+    const size_t chunk = (size_t)3 * nA + nB;
+    const PointState &Pc = ps_[cur_], &Pn = ps_[cur_ ^ 1];
+    const int par = slot & 1;
+    OuterStepArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.nloc = nloc_; A.cam0 = cam0_;
+    A.scal_cur = scal_.p + par; A.scal_next = scal_.p + (par ^ 1);
+    A.os_cur = oscal_.p + par; A.os_next = oscal_.p + (par ^ 1);
+    A.parts = partsB_.p + (size_t)par * chunk;
+    A.partsB_out = partsB_.p + (size_t)(par ^ 1) * chunk + (size_t)3 * nA;
+    A.nA = nA; A.nB = nB;
+    A.HpR = HpR_.p; A.Hps = Hps_.p;
+    A.R = R_.p; A.s = s_.p; A.Rc = Rc_.p; A.sc = sc_.p;
+    A.pR = pR_.p; A.ps_cur = par ? psB_.p : psA_.p; A.ps_next = par ? psA_.p : psB_.p;
+    A.vR = vR_.p; A.vs = vs_.p; A.HvR = model_rec ? nullptr : HvR_.p; A.Hvs = model_rec ? nullptr : Hvs_.p; A.rR = rR_.p;
+    A.rs_cur = par ? rsB_.p : rs_.p; A.rs_next = par ? rs_.p : rsB_.p;
+    A.Wloc = W_.p + (size_t)cam0_ * 3 * OP_; A.Wpad = nullptr;
+    A.cur = {Pc.G.p, Pc.egs.p, Pc.S0.p, Pc.rgR.p, Pc.rgs.p};
+    A.cand = {Pn.G.p, Pn.egs.p, Pn.S0.p, Pn.rgR.p, Pn.rgs.p};
+    A.partsA = partsA_.p; A.partsM = partsM_.p; A.nM = nM;
+    A.delta_bar = delta_bar; A.gradtol = gradtol; A.max_outer = kMaxOuter;
+    A.trace = trace_dev_.p; A.trace_cap = kMaxOuter;
+    A.stop_req = stop_req_.p;
+    A.hprog = hstat_dev_ + 24;
+    A.run = runid; A.slot = slot; A.grp = grouping_;
+    return A;
+}
+
 TrResult Context::trust_region_device(int o, double &gradtol, double f, double rr, double delta, double delta_bar, double max_time) {
     TrResult out;
     const auto start = clk::now();
     const bool profile = (opt_->flags & XM_FLAG_PROFILE_QW) != 0;
     const bool model_rec = (opt_->flags & XM_FLAG_MODEL_RECURRENCE) != 0;
-    const int nA = prod_grid(), nB = tcg_blocks(), nM = retract_grid(nloc_);
+    const int nA = prod_grid(), nB = tcg_blocks();
     double loss = f;
     int stop_reason = 14, k = 0;
     long long totalite = 0;
@@ -1233,34 +1264,8 @@ TrResult Context::trust_region_device(int o, double &gradtol, double f, double r
         volatile unsigned long long *hp = hstat_ + 24;
         *hp = 0;
         const size_t chunk = (size_t)3 * nA + nB;
-        double *Wloc = W_.p + (size_t)cam0_ * 3 * OP_;
-        const PointState &Pc = ps_[cur_], &Pn = ps_[cur_ ^ 1];
-        auto step_args = [&](int slot) {
-            const int par = slot & 1;
-            OuterStepArgs A;
-            std::memset(&A, 0, sizeof(A));
-            A.nloc = nloc_; A.cam0 = cam0_;
-            A.scal_cur = scal_.p + par; A.scal_next = scal_.p + (par ^ 1);
-            A.os_cur = oscal_.p + par; A.os_next = oscal_.p + (par ^ 1);
-            A.parts = partsB_.p + (size_t)par * chunk;
-            A.partsB_out = partsB_.p + (size_t)(par ^ 1) * chunk + (size_t)3 * nA;
-            A.nA = nA; A.nB = nB;
-            A.HpR = HpR_.p; A.Hps = Hps_.p;
-            A.R = R_.p; A.s = s_.p; A.Rc = Rc_.p; A.sc = sc_.p;
-            A.pR = pR_.p; A.ps_cur = par ? psB_.p : psA_.p; A.ps_next = par ? psA_.p : psB_.p;
-            A.vR = vR_.p; A.vs = vs_.p; A.HvR = model_rec ? nullptr : HvR_.p; A.Hvs = model_rec ? nullptr : Hvs_.p; A.rR = rR_.p;
-            A.rs_cur = par ? rsB_.p : rs_.p; A.rs_next = par ? rs_.p : rsB_.p;
-            A.Wloc = Wloc; A.Wpad = nullptr;
-            A.cur = {Pc.G.p, Pc.egs.p, Pc.S0.p, Pc.rgR.p, Pc.rgs.p};
-            A.cand = {Pn.G.p, Pn.egs.p, Pn.S0.p, Pn.rgR.p, Pn.rgs.p};
-            A.partsA = partsA_.p; A.partsM = partsM_.p; A.nM = nM;
-            A.delta_bar = delta_bar; A.gradtol = gradtol; A.max_outer = kMaxOuter;
-            A.trace = trace_dev_.p; A.trace_cap = kMaxOuter;
-            A.stop_req = stop_req_.p;
-            A.hprog = hstat_dev_ + 24;
-            A.run = runid; A.slot = slot; A.grp = grouping_;
-            return A;
-        };
+        const PointState &Pn = ps_[cur_ ^ 1];
+        auto step_args = [&](int slot) { return outer_step_args(slot, model_rec, delta_bar, gradtol, runid); };
         const int polar = retraction_ == XM_RETRACT_POLAR ? 1 : 0;
         auto enqueue_slot = [&](int slot) {
             const int par = slot & 1;
@@ -1848,6 +1853,287 @@ void Context::rtr_probe(xm_rtr_probe_t &q) {
             }
         }
         XM_HIP_CHECK(hipMemsetAsync(W_.p, 0, W_.count * sizeof(double), st_));
+    }
+    XM_HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The other half of an outer iteration stage by stage (test export xm_ctx_outer_probe, include/xm_amd.h): the retraction launches of
+// trust_region() and its line search, and one step launch of trust_region_device() with the arguments outer_step_args() gives a solve.
+// What a later solve reads is re-created as after rtr_probe(); the progress word of the device-driven form carries a run number of its own.
+// ------------------------------------------------------------------------------------------------------------------
+void Context::outer_probe(xm_outer_probe_t &q) {
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_outer_probe: single-rank contexts only");
+    const int o = q.o;
+    const bool want_ret = (q.flags & XM_OUTER_PROBE_RETRACT) != 0, want_ls = (q.flags & XM_OUTER_PROBE_RETRACT_LS) != 0;
+    const bool want_step = (q.flags & XM_OUTER_PROBE_STEP) != 0, model_rec = (q.flags & XM_OUTER_PROBE_MODEL_REC) != 0;
+    const bool aut = want_step || (q.flags & XM_OUTER_PROBE_AUTO) != 0;
+    xm_options_t opt;
+    std::memset(&opt, 0, sizeof(opt));
+    opt.lam = q.lam;
+    opt.max_rank = (unsigned)o;
+    opt.flags = (aut ? XM_FLAG_DEVICE_OUTER : 0u) | (model_rec ? XM_FLAG_MODEL_RECURRENCE : 0u);
+    struct Leave { Context *c; ~Leave() { c->opt_ = nullptr; c->sym_rev_ = 1; c->solved_ = false; } } leave{this};
+    opt_ = &opt;
+    grouping_ = 0;
+    setup_rank(o);
+    const int nA = prod_grid(), nB = tcg_blocks(), nM = retract_grid(nloc_), nwave = (nloc_ + 63) >> 6;
+    const int polar = (q.flags & XM_OUTER_PROBE_POLAR) ? 1 : (q.flags & XM_OUTER_PROBE_MGS) ? 0 : (retraction_ == XM_RETRACT_POLAR ? 1 : 0);
+    const int phase = q.scal_in.phase;
+    q.product_kind = product_kind(o); q.nA = nA; q.nB = nB; q.nM = nM; q.wpad = wpad() ? 1 : 0; q.w_native = wpad() ? 0 : 1; q.polar = polar;
+    q.grid = nB; q.nwave = nwave; q.trace_written = 0; q.run = 0; q.progress = 0;
+    for (int k = 0; k < 3; ++k) q.ret_pad[k] = -1;
+    q.ls_pad[0] = q.ls_pad[1] = q.out_pad[0] = q.out_pad[1] = -1;
+    if (aut && !device_outer_applies(o))
+        throw Error(XM_ERR_ARG, "xm_ctx_outer_probe: XM_OUTER_PROBE_STEP / _AUTO, but the device-driven outer iteration does not apply to this context at this rank");
+    if (want_step && phase == PH_TCG && q.scal_in.iter > 0 && (!q.partsB_in || q.partsB_in_count != nB))
+        throw Error(XM_ERR_ARG, "xm_ctx_outer_probe: scal_in.iter > 0 needs partsB_in with nB = " + std::to_string(nB) + " partial sums");
+    if (want_step && phase == PH_CAND && !model_rec && (!q.partsM_in || q.partsM_in_count != nwave))
+        throw Error(XM_ERR_ARG, "xm_ctx_outer_probe: the candidate role needs partsM_in with one partial sum per wavefront: " + std::to_string(nwave));
+    const size_t n = (size_t)n_, m3 = 3 * n, mat = (size_t)nloc_ * 3 * OP_;
+    std::vector<double> hm(mat), hv((size_t)nloc_);
+    auto up_mat = [&](double *dst, const double *src, double sign) {   // host column-major -> device rows of pitch OP (nullptr: zeros)
+        std::fill(hm.begin(), hm.end(), 0.0);
+        if (src)
+            for (size_t c = 0; c < n; ++c)
+                for (int a = 0; a < 3; ++a)
+                    for (int k = 0; k < o; ++k) hm[(c * 3 + a) * OP_ + k] = sign * src[(3 * c + a) + (size_t)k * m3];
+        to_dev(dst, hm.data(), mat * sizeof(double));
+    };
+    auto up_vec = [&](double *dst, const double *src, double sign, bool zero_anchor) {
+        std::fill(hv.begin(), hv.end(), 0.0);
+        if (src)
+            for (size_t c = 0; c < n; ++c) hv[c] = sign * src[c];
+        if (zero_anchor) hv[0] = 0.0;
+        to_dev(dst, hv.data(), hv.size() * sizeof(double));
+    };
+    auto down_mat = [&](double *dst, const double *src) {
+        if (!dst) return;
+        to_host(hm.data(), src, mat * sizeof(double));
+        for (size_t c = 0; c < n; ++c)
+            for (int a = 0; a < 3; ++a)
+                for (int k = 0; k < o; ++k) dst[(3 * c + a) + (size_t)k * m3] = hm[(c * 3 + a) * OP_ + k];
+    };
+    auto down_vec = [&](double *dst, const double *src, size_t per = 1) {
+        if (dst) to_host(dst, src, n * per * sizeof(double));
+    };
+    // pad columns of an even rank: ones into a matrix the next launch writes as a whole (its other entries: zeros), and the count of what is left
+    const bool padded = OP_ > o;
+    auto poison_mat = [&](double *dst) {
+        if (!padded) return;
+        std::fill(hm.begin(), hm.end(), 0.0);
+        for (size_t r = 0; r < (size_t)nloc_ * 3; ++r) hm[r * OP_ + o] = 1.0;
+        to_dev(dst, hm.data(), mat * sizeof(double));
+    };
+    auto poison_pad_only = [&](double *dst) {   // the same for a matrix whose other entries must stay
+        if (!padded) return;
+        to_host(hm.data(), dst, mat * sizeof(double));
+        for (size_t r = 0; r < (size_t)nloc_ * 3; ++r) hm[r * OP_ + o] = 1.0;
+        to_dev(dst, hm.data(), mat * sizeof(double));
+    };
+    auto count_pad = [&](const double *src) {
+        if (!padded) return 0;
+        to_host(hm.data(), src, mat * sizeof(double));
+        int bad = 0;
+        for (size_t r = 0; r < (size_t)nloc_ * 3; ++r) bad += hm[r * OP_ + o] != 0.0;
+        return bad;
+    };
+    std::vector<double> hw;
+    auto poison_wpad = [&]() {   // only the pad column inside a record: what lies behind 3 OP doubles is never written by anybody
+        if (!wpad() || !padded) return;
+        hw.assign((size_t)nloc_ * 16, 0.0);
+        for (size_t c = 0; c < (size_t)nloc_; ++c)
+            for (int a = 0; a < 3; ++a) hw[c * 16 + a * OP_ + o] = 1.0;
+        to_dev(wpad(), hw.data(), hw.size() * sizeof(double));
+    };
+    auto count_wpad = [&]() {
+        if (!wpad()) return -1;
+        if (!padded) return 0;
+        hw.assign((size_t)nloc_ * 16, 0.0);
+        to_host(hw.data(), wpad(), hw.size() * sizeof(double));
+        int bad = 0;
+        for (size_t c = 0; c < (size_t)nloc_; ++c)
+            for (int a = 0; a < 3; ++a) bad += hw[c * 16 + a * OP_ + o] != 0.0;
+        return bad;
+    };
+    auto tcg_in = [](const xm_outer_tcg_t &in) {
+        TcgScal sc;
+        std::memset(&sc, 0, sizeof(sc));
+        sc.rr = in.rr; sc.vv = in.vv; sc.vp = in.vp; sc.pp = in.pp; sc.delta = in.delta; sc.gradnorm = in.gradnorm; sc.last_step = in.last_step;
+        sc.model = in.model; sc.status = in.status; sc.iter = in.iter; sc.seq = in.seq; sc.phase = in.phase;
+        return sc;
+    };
+    auto tcg_out = [](const TcgScal &sc, xm_outer_tcg_t &out) {
+        out.rr = sc.rr; out.vv = sc.vv; out.vp = sc.vp; out.pp = sc.pp; out.delta = sc.delta; out.gradnorm = sc.gradnorm; out.last_step = sc.last_step;
+        out.model = sc.model; out.status = sc.status; out.iter = sc.iter; out.seq = sc.seq; out.phase = sc.phase;
+    };
+    double *hres_dev = reinterpret_cast<double *>(hstat_dev_) + 8;
+    double *Wloc = W_.p + (size_t)cam0_ * 3 * OP_;
+    const PointState &P = ps_[cur_], &Pn = ps_[cur_ ^ 1];
+
+    // ---- grad: as rtr_probe()
+    upload_point(std::vector<double>(q.R, q.R + m3 * (size_t)o), o, std::vector<double>(q.s, q.s + n));
+    launch_scale_rows(o, nloc_, R_.p, s_.p, Wloc, st_);
+    double f = 0, rr = 0;
+    if (!aut) {
+        eval_point(cur_, R_.p, s_.p, f, rr);
+    } else {
+        TcgScal sc;
+        std::memset(&sc, 0, sizeof(sc));
+        sc.phase = PH_CAND;
+        to_dev(scal_.p, &sc, sizeof(sc));
+        CamArgs a = cam_args(cur_);
+        a.scal = scal_.p;
+        a.partials = partsB_.p;
+        a.cand.R = R_.p; a.cand.s = s_.p;
+        a.cand.G = P.G.p; a.cand.egs = P.egs.p; a.cand.S0 = P.S0.p; a.cand.rgR = P.rgR.p; a.cand.rgs = P.rgs.p;
+        a.cand.partials = partsA_.p;
+        product(EPI_AUTO, o_, 2.0, a);
+        launch_outer_finalize(partsA_.p, nA, 1, partsM_.p, 0, scal_.p, hres_dev, ++outer_seq_, 0, st_);
+        volatile double *hres = wait_outer_result();
+        f = hres[0]; rr = hres[1];
+    }
+    q.f = f; q.rr = rr;
+    down_mat(q.rgR, P.rgR.p); down_vec(q.rgs, P.rgs.p);
+
+    // ---- retract: trust_region()'s retraction of the step with its model decrease, and the result kernel behind it
+    if (want_ret) {
+        up_mat(vR_.p, q.vR, 1.0); up_vec(vs_.p, q.vs, 1.0, true);
+        if (!model_rec) { up_mat(HvR_.p, q.HvR, 1.0); up_vec(Hvs_.p, q.Hvs, 1.0, false); }
+        if (q.ret_partsM) to_dev(partsM_.p, q.ret_partsM, (size_t)nM * sizeof(double));   // what the launch must leave alone without Hv
+        TcgScal sc = tcg_in(q.scal_in);
+        sc.phase = 0;
+        to_dev(scal_.p, &sc, sizeof(sc));
+        poison_mat(Rc_.p); poison_mat(Wloc); poison_wpad();
+        launch_retract_model(o, nloc_, cam0_, R_.p, s_.p, vR_.p, vs_.p, Rc_.p, sc_.p, Wloc, wpad(), model_rec ? nullptr : HvR_.p, Hvs_.p, P.rgR.p, P.rgs.p,
+                             partsM_.p, st_, polar);
+        launch_outer_finalize(partsA_.p, 0, 1, partsM_.p, model_rec ? 0 : nM, scal_.p, hres_dev, ++outer_seq_, grouping_, st_);
+        volatile double *hres = wait_outer_result();
+        q.model = hres[2];
+        down_mat(q.ret_Rc, Rc_.p); down_vec(q.ret_sc, sc_.p); down_mat(q.ret_W, Wloc);
+        if (wpad()) down_vec(q.ret_Wpad, wpad(), 16);
+        if (q.ret_partsM) to_host(q.ret_partsM, partsM_.p, (size_t)nM * sizeof(double));
+        q.ret_pad[0] = count_pad(Rc_.p); q.ret_pad[1] = count_pad(Wloc); q.ret_pad[2] = count_wpad();
+    }
+
+    // ---- retract_ls: the line search's form (trust_region(): no scale step, no scales out)
+    if (want_ls) {
+        up_mat(D_.p, q.D, 1.0);
+        poison_mat(Rc_.p); poison_mat(Wloc);
+        launch_retract(o, nloc_, cam0_, R_.p, s_.p, D_.p, nullptr, q.t, Rc_.p, nullptr, Wloc, st_, polar);
+        down_mat(q.ls_Rc, Rc_.p); down_mat(q.ls_W, Wloc);
+        q.ls_pad[0] = count_pad(Rc_.p); q.ls_pad[1] = count_pad(Wloc);
+    }
+
+    // ---- step: one (product, step) pair of trust_region_device() in the role scal_in.phase names
+    if (want_step) {
+        const int par = q.slot & 1;
+        double *ps_cur = par ? psB_.p : psA_.p, *ps_next = par ? psA_.p : psB_.p, *rs_cur = par ? rsB_.p : rs_.p, *rs_next = par ? rs_.p : rsB_.p;
+        if (trace_dev_.count < (size_t)kMaxOuter * 6) trace_dev_.alloc((size_t)kMaxOuter * 6);
+        if (stop_req_.count < 1) stop_req_.alloc(1);
+        if (oscal_.count < 2) oscal_.alloc(2);
+        const int stop_word = q.stop_req;
+        to_dev(stop_req_.p, &stop_word, sizeof(int));
+        const unsigned int runid = ++outer_run_;
+        q.run = runid;
+        volatile unsigned long long *hp = hstat_ + 24;
+        *hp = 0;
+        const size_t chunk = (size_t)3 * nA + nB;
+        double *pcur = partsB_.p + (size_t)par * chunk, *pnext = partsB_.p + (size_t)(par ^ 1) * chunk;
+        if (phase == PH_TCG) {   // the product input W = s.*pR + ps.*R by the kernel that writes it in a solve, as rtr_probe()
+            up_mat(D_.p, q.pR, -1.0);
+            up_vec(Hps_.p, q.ps, -1.0, true);
+            launch_tcg_init(o, nloc_, D_.p, Hps_.p, R_.p, s_.p, rR_.p, rs_.p, pR_.p, psA_.p, vR_.p, vs_.p, HvR_.p, Hvs_.p, Wloc, scal_.p, 0.0, 0.0, nullptr, st_, nullptr, 0);
+        }
+        up_mat(pR_.p, q.pR, 1.0); up_vec(ps_cur, q.ps, 1.0, false); up_vec(ps_next, q.ps, 1.0, false);
+        up_mat(rR_.p, q.rR, 1.0); up_vec(rs_cur, q.rs, 1.0, false); up_vec(rs_next, q.rs, 1.0, false);
+        up_mat(vR_.p, q.vR, 1.0); up_vec(vs_.p, q.vs, 1.0, false);
+        up_mat(HvR_.p, q.HvR, 1.0); up_vec(Hvs_.p, q.Hvs, 1.0, false);
+        if (q.Rc && q.sc) { up_mat(Rc_.p, q.Rc, 1.0); up_vec(sc_.p, q.sc, 1.0, false); }
+        else {
+            XM_HIP_CHECK(hipMemcpyAsync(Rc_.p, R_.p, mat * sizeof(double), hipMemcpyDeviceToDevice, st_));
+            XM_HIP_CHECK(hipMemcpyAsync(sc_.p, s_.p, (size_t)nloc_ * sizeof(double), hipMemcpyDeviceToDevice, st_));
+        }
+        for (DevBuf<double> *b : {&ps_[cur_ ^ 1].G, &ps_[cur_ ^ 1].egs, &ps_[cur_ ^ 1].S0, &ps_[cur_ ^ 1].rgR, &ps_[cur_ ^ 1].rgs})
+            XM_HIP_CHECK(hipMemsetAsync(b->p, 0, b->count * sizeof(double), st_));
+        TcgScal sc = tcg_in(q.scal_in), sc_zero;
+        std::memset(&sc_zero, 0, sizeof(sc_zero));
+        to_dev(scal_.p + par, &sc, sizeof(sc));
+        to_dev(scal_.p + (par ^ 1), &sc_zero, sizeof(sc_zero));
+        OuterScal os, os_zero;
+        std::memset(&os, 0, sizeof(os));
+        std::memset(&os_zero, 0, sizeof(os_zero));
+        os.loss = q.os_in.loss; os.rr_point = q.os_in.rr_point; os.totalite = q.os_in.totalite; os.shrink_count = q.os_in.shrink_count; os.k = q.os_in.k;
+        os.stop_reason = q.os_in.stop_reason; os.time_up = q.os_in.time_up; os.slots = q.os_in.slots;
+        to_dev(oscal_.p + par, &os, sizeof(os));
+        to_dev(oscal_.p + (par ^ 1), &os_zero, sizeof(os_zero));
+        XM_HIP_CHECK(hipMemsetAsync(partsB_.p, 0, 2 * chunk * sizeof(double), st_));
+        XM_HIP_CHECK(hipMemsetAsync(partsM_.p, 0, (size_t)std::max(nwave, nM) * sizeof(double), st_));
+        if (q.partsM_in && q.partsM_in_count == nwave) to_dev(partsM_.p, q.partsM_in, (size_t)nwave * sizeof(double));
+        const int krec = q.os_in.k + 1;
+        const bool rec_ok = krec >= 1 && krec < kMaxOuter;
+        if (rec_ok) XM_HIP_CHECK(hipMemsetAsync(trace_dev_.p + (size_t)krec * 6, 0xff, 6 * sizeof(double), st_));
+        CamArgs a = cam_args(cur_);   // trust_region_device()'s enqueue_slot
+        a.scal = scal_.p + par;
+        a.ps = ps_cur;
+        a.rs = rs_cur;
+        a.partials = pcur;
+        a.cand.R = Rc_.p; a.cand.s = sc_.p;
+        a.cand.G = Pn.G.p; a.cand.egs = Pn.egs.p; a.cand.S0 = Pn.S0.p; a.cand.rgR = Pn.rgR.p; a.cand.rgs = Pn.rgs.p;
+        a.cand.partials = partsA_.p;
+        if (phase == PH_TCG) {
+            sym_rev_ = par;
+            product(EPI_AUTO, o_, 2.0, a);
+            sym_rev_ = 1;
+            launch_outer_finalize(pcur, nA, 1, pcur + (size_t)2 * nA, nA, scal_.p + par, hres_dev, ++outer_seq_, 0, st_);
+            volatile double *hres = wait_outer_result();
+            q.pHp = hres[0]; q.rHp = hres[1]; q.HpHp = hres[2];
+            down_mat(q.HpR, HpR_.p); down_vec(q.Hps, Hps_.p);
+            if (q.scal_in.iter > 0) to_dev(pcur + (size_t)3 * nA, q.partsB_in, (size_t)nB * sizeof(double));
+            poison_pad_only(Rc_.p); poison_pad_only(Wloc);
+        } else if (phase == PH_CAND) {
+            launch_scale_rows(o, nloc_, Rc_.p, sc_.p, Wloc, st_);   // what the retraction of the tCG's last launch leaves as the product input
+            sym_rev_ = par;
+            product(EPI_AUTO, o_, 2.0, a);
+            sym_rev_ = 1;
+            // the three sums the decision takes: f and <rg,rg> by the result kernel's tree, m of the partials regrouped as outer_decide regroups them
+            std::vector<double> grouped((size_t)nM, 0.0);
+            if (!model_rec)
+                for (int i = 0; i < nM; ++i) {
+                    auto w = [&](int j) { return j < nwave ? q.partsM_in[j] : 0.0; };
+                    grouped[(size_t)i] = (w(4 * i) + w(4 * i + 1)) + (w(4 * i + 2) + w(4 * i + 3));
+                }
+            to_dev(D_.p, grouped.data(), grouped.size() * sizeof(double));
+            launch_outer_finalize(partsA_.p, nA, 1, D_.p, model_rec ? 0 : nM, scal_.p + par, hres_dev, ++outer_seq_, grouping_, st_);
+            volatile double *hres = wait_outer_result();
+            q.f_cand = hres[0]; q.rr_cand = hres[1]; q.m_cand = hres[2];
+            down_mat(q.cand_G, Pn.G.p); down_vec(q.cand_egs, Pn.egs.p); down_vec(q.cand_S0, Pn.S0.p, 9); down_mat(q.cand_rgR, Pn.rgR.p); down_vec(q.cand_rgs, Pn.rgs.p);
+        }
+        OuterStepArgs A = outer_step_args(q.slot, model_rec, q.delta_bar, q.gradtol, runid);
+        if (q.max_outer > 0) A.max_outer = q.max_outer;   // (a solve's is kMaxOuter)
+        launch_outer_step(o_, polar, A, nB, st_);
+        XM_HIP_CHECK(hipStreamSynchronize(st_));
+        q.progress = *hp;
+        TcgScal nx;
+        OuterScal on;
+        to_host(&nx, scal_.p + (par ^ 1), sizeof(nx));
+        to_host(&on, oscal_.p + (par ^ 1), sizeof(on));
+        tcg_out(nx, q.scal_out);
+        q.os_out.loss = on.loss; q.os_out.rr_point = on.rr_point; q.os_out.totalite = on.totalite; q.os_out.shrink_count = on.shrink_count; q.os_out.k = on.k;
+        q.os_out.stop_reason = on.stop_reason; q.os_out.time_up = on.time_up; q.os_out.slots = on.slots; q.os_out.pad = 0;
+        if (rec_ok) {
+            to_host(q.trace, trace_dev_.p + (size_t)krec * 6, 6 * sizeof(double));
+            q.trace_written = std::isnan(q.trace[0]) ? 0 : 1;
+        }
+        down_mat(q.out_R, R_.p); down_vec(q.out_s, s_.p); down_mat(q.out_Rc, Rc_.p); down_vec(q.out_sc, sc_.p);
+        down_mat(q.out_vR, vR_.p); down_vec(q.out_vs, vs_.p); down_mat(q.out_HvR, HvR_.p); down_vec(q.out_Hvs, Hvs_.p);
+        down_mat(q.out_rR, rR_.p); down_vec(q.out_rs, rs_next); down_mat(q.out_pR, pR_.p); down_vec(q.out_ps, ps_next);
+        down_mat(q.out_W, Wloc);
+        if (wpad()) down_vec(q.out_Wpad, wpad(), 16);
+        if (q.out_partsB) to_host(q.out_partsB, pnext + (size_t)3 * nA, (size_t)nB * sizeof(double));
+        if (q.out_partsM) to_host(q.out_partsM, partsM_.p, (size_t)nwave * sizeof(double));
+        down_mat(q.out_G, P.G.p); down_vec(q.out_egs, P.egs.p); down_vec(q.out_S0, P.S0.p, 9); down_mat(q.out_rgR, P.rgR.p); down_vec(q.out_rgs, P.rgs.p);
+        if (phase == PH_TCG) { q.out_pad[0] = count_pad(Rc_.p); q.out_pad[1] = count_pad(Wloc); }
     }
     XM_HIP_CHECK(hipStreamSynchronize(st_));
 }

@@ -36,7 +36,7 @@ EXPORTS = [
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
     "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_ba_aggregate_plan", "xm_ctx_ba_probe",
-    "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe",
+    "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe", "xm_ctx_outer_probe",
     "xm_ctx_dense_q", "xm_create_matrix", "xm_schur_dense_limits",
     "xm_pair_filter", "xm_pair_filter_limits",
 ]
@@ -133,6 +133,43 @@ RTR_PROBE_AUTO, RTR_PROBE_MODEL_REC, RTR_PROBE_TCG_INIT, RTR_PROBE_CG_STEP, RTR_
 RTR_SCAL_IN = ("rr", "vv", "vp", "pp", "delta", "gradnorm", "model", "iter")
 
 
+class OuterTcg(C.Structure):   # xm_outer_tcg_t: the truncated CG's scalar block with the fields the device-driven outer iteration adds
+    _fields_ = [(k, C.c_double) for k in ("rr", "vv", "vp", "pp", "delta", "gradnorm", "last_step", "model")] + \
+               [(k, C.c_int32) for k in ("status", "iter", "seq", "phase")]
+
+
+class OuterScal(C.Structure):  # xm_outer_scal_t: the trust-region state of the device-driven outer iteration
+    _fields_ = [("loss", C.c_double), ("rr_point", C.c_double), ("totalite", C.c_int64)] + \
+               [(k, C.c_int32) for k in ("shrink_count", "k", "stop_reason", "time_up", "slots", "pad")]
+
+
+OUTER_IN = ("R", "s", "vR", "vs", "HvR", "Hvs", "D", "pR", "ps", "rR", "rs", "Rc", "sc", "partsB_in", "partsM_in")
+OUTER_MATS = ("rgR", "ret_Rc", "ret_W", "ls_Rc", "ls_W", "HpR", "cand_G", "cand_rgR", "out_R", "out_Rc", "out_vR", "out_HvR", "out_rR", "out_pR", "out_W",
+              "out_G", "out_rgR")
+OUTER_OUT = ("rgR", "rgs", "ret_Rc", "ret_sc", "ret_W", "ret_Wpad", "ret_partsM", "ls_Rc", "ls_W", "HpR", "Hps", "cand_G", "cand_egs", "cand_S0", "cand_rgR",
+             "cand_rgs", "out_R", "out_s", "out_Rc", "out_sc", "out_vR", "out_vs", "out_HvR", "out_Hvs", "out_rR", "out_rs", "out_pR", "out_ps", "out_W",
+             "out_Wpad", "out_partsB", "out_partsM", "out_G", "out_egs", "out_S0", "out_rgR", "out_rgs")
+
+
+class OuterProbe(C.Structure):   # xm_outer_probe_t, the test export xm_ctx_outer_probe
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("o", C.c_int32), ("slot", C.c_int32), ("lam", C.c_double), ("t", C.c_double)] + \
+               [(k, C.c_void_p) for k in OUTER_IN] + [("partsB_in_count", C.c_int32), ("partsM_in_count", C.c_int32), ("scal_in", OuterTcg), ("os_in", OuterScal),
+                                                      ("delta_bar", C.c_double), ("gradtol", C.c_double), ("max_outer", C.c_int32), ("stop_req", C.c_int32)] + \
+               [(k, C.c_int32) for k in ("product_kind", "nA", "nB", "nM", "w_native", "wpad", "polar", "grid", "nwave", "trace_written")] + \
+               [("run", C.c_uint32), ("pad", C.c_uint32), ("ret_pad", C.c_int32 * 3), ("ls_pad", C.c_int32 * 2), ("out_pad", C.c_int32 * 2), ("pad2", C.c_int32)] + \
+               [(k, C.c_double) for k in ("f", "rr", "model", "pHp", "rHp", "HpHp", "f_cand", "rr_cand", "m_cand")] + \
+               [("progress", C.c_uint64), ("scal_out", OuterTcg), ("os_out", OuterScal), ("trace", C.c_double * 6)] + [(k, C.c_void_p) for k in OUTER_OUT]
+
+
+OUTER_PROBE_RETRACT, OUTER_PROBE_MODEL_REC, OUTER_PROBE_RETRACT_LS, OUTER_PROBE_STEP, OUTER_PROBE_POLAR, OUTER_PROBE_MGS, OUTER_PROBE_AUTO = 1, 2, 4, 8, 16, 32, 64
+PH_TCG, PH_CAND, PH_STOP, PH_INIT = 0, 1, 2, 3
+
+
+def pack_prog(run, slots, phase):
+    """the progress word of the device-driven outer iteration: [run : 32 | launch pairs done : 24 | phase : 8]"""
+    return (int(run) << 32) | ((int(slots) & 0xffffff) << 8) | (int(phase) & 0xff)
+
+
 class CleanOptions(C.Structure):   # xm_clean_options_t
     _fields_ = [("struct_size", C.c_uint32), ("min_cam_obs", C.c_int32), ("min_lm_obs", C.c_int32), ("flags", C.c_uint32)]
 
@@ -220,6 +257,7 @@ def lib():
         L.xm_ctx_bundle_adjust.argtypes = [C.c_void_p, C.POINTER(BaOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaResult)]
         L.xm_ctx_ba_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaProbe)]
         L.xm_ctx_rtr_probe.argtypes = [C.c_void_p, C.POINTER(RtrProbe)]
+        L.xm_ctx_outer_probe.argtypes = [C.c_void_p, C.POINTER(OuterProbe)]
         L.xm_clean_observations.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CleanOptions), C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.POINTER(CleanResult)]
         L.xm_ctx_clean_observations.argtypes = [C.c_void_p, C.POINTER(CleanOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CleanResult)]
@@ -1078,6 +1116,82 @@ class Context:
         if cert:
             out["dual"] = np.array(q.dual[:])
         return {k: (np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v) for k, v in out.items()}
+
+    def outer_probe(self, o, lam, R, s, v=None, Hv=None, retract=False, model_recurrence=False, retraction=None, auto=False, model=0.0, partsM_fill=None,
+                    ls=None, step=None):
+        """the other half of an outer iteration stage by stage at the point (R: 3n x o, s: n) (the test export xm_ctx_outer_probe; include/xm_amd.h): a
+        dict of f, rr, rgR, rgs, product_kind, nA, nB, nM, nwave, grid, wpad, w_native, polar.  retract=True with v = (vR, vs), Hv = (HvR, Hvs):
+        ret_Rc, ret_sc, ret_W, ret_Wpad, ret_partsM (nM), model, ret_pad; model_recurrence=True: no Hv, ret_partsM keeps partsM_fill and model is
+        the given one.  retraction: None the context's | "polar" | "mgs".  auto=True: the gradient through the role-switching launch.
+        ls = (D, t): ls_Rc, ls_W, ls_pad.  step = dict(scal=dict of xm_outer_tcg_t fields, os=dict of xm_outer_scal_t fields, delta_bar, gradtol,
+        max_outer, stop_req, slot, p=(pR, ps), r=(rR, rs), cand=(Rc, sc), partsB, partsM) with v, Hv: one outer_step_kernel launch -> scal_out,
+        os_out, progress, run, trace (None unless written), out_* and, by role, HpR, Hps, pHp, rHp, HpHp / cand_*, f_cand, rr_cand, m_cand."""
+        n, o = self.n, int(o)
+        f64 = lambda a, shape: np.asfortranarray(np.asarray(a, dtype=np.float64).reshape(shape))
+        q = OuterProbe()
+        q.struct_size = C.sizeof(OuterProbe)
+        q.o, q.lam = o, float(lam)
+        q.flags = (OUTER_PROBE_RETRACT if retract else 0) | (OUTER_PROBE_MODEL_REC if model_recurrence else 0) | (OUTER_PROBE_RETRACT_LS if ls is not None else 0) | \
+                  (OUTER_PROBE_STEP if step is not None else 0) | (OUTER_PROBE_AUTO if auto else 0) | \
+                  {None: 0, "polar": OUTER_PROBE_POLAR, "mgs": OUTER_PROBE_MGS}[retraction]
+        q.scal_in.model = float(model)
+        ins = dict(R=f64(R, (3 * n, o)), s=f64(s, (n,)))
+        mat = lambda: np.zeros((3 * n, o), order="F")
+        nwave = (n + 63) // 64
+        shapes = dict(ret_Wpad=(n, 16), out_Wpad=(n, 16), ret_partsM=(1024,), out_partsB=(1024,), out_partsM=(max(1024, nwave),), cand_S0=(n, 3, 3), out_S0=(n, 3, 3))
+        new = lambda k: mat() if k in OUTER_MATS else np.zeros(shapes.get(k, (n,)))
+        out = {k: new(k) for k in ("rgR", "rgs")}
+        if v is not None:
+            ins.update(vR=f64(v[0], (3 * n, o)), vs=f64(v[1], (n,)))
+        if Hv is not None and not model_recurrence:
+            ins.update(HvR=f64(Hv[0], (3 * n, o)), Hvs=f64(Hv[1], (n,)))
+        if retract:
+            out.update({k: new(k) for k in OUTER_OUT if k.startswith("ret_")})
+            if partsM_fill is not None:
+                out["ret_partsM"][:] = partsM_fill
+        if ls is not None:
+            ins["D"] = f64(ls[0], (3 * n, o))
+            q.t = float(ls[1])
+            out.update(ls_Rc=mat(), ls_W=mat())
+        if step is not None:
+            for k, val in step["scal"].items():
+                setattr(q.scal_in, k, float(val) if k in RTR_SCAL_IN[:7] + ("last_step",) else int(val))
+            for k, val in step.get("os", {}).items():
+                setattr(q.os_in, k, float(val) if k in ("loss", "rr_point") else int(val))
+            q.delta_bar, q.gradtol = float(step.get("delta_bar", 1e30)), float(step.get("gradtol", 0.0))
+            q.max_outer, q.stop_req, q.slot = int(step.get("max_outer", 0)), int(step.get("stop_req", 0)), int(step.get("slot", 0))
+            ins.update(pR=f64(step["p"][0], (3 * n, o)), ps=f64(step["p"][1], (n,)), rR=f64(step["r"][0], (3 * n, o)), rs=f64(step["r"][1], (n,)))
+            if step.get("cand") is not None:
+                ins.update(Rc=f64(step["cand"][0], (3 * n, o)), sc=f64(step["cand"][1], (n,)))
+            for k in ("partsB", "partsM"):
+                if step.get(k) is not None:
+                    ins[k + "_in"] = f64(step[k], (-1,))
+                    setattr(q, k + "_in_count", ins[k + "_in"].size)
+            phase = int(step["scal"].get("phase", PH_TCG))
+            out.update({k: new(k) for k in OUTER_OUT if k.startswith("out_")})
+            if phase == PH_TCG:
+                out.update(HpR=mat(), Hps=np.zeros(n))
+            if phase == PH_CAND:
+                out.update({k: new(k) for k in OUTER_OUT if k.startswith("cand_")})
+        for k, val in list(ins.items()) + list(out.items()):
+            setattr(q, k, val.ctypes.data_as(C.c_void_p))
+        _chk(lib().xm_ctx_outer_probe(self.h, C.byref(q)))
+        fields = lambda sc: {k: getattr(sc, k) for k, _ in sc._fields_ if k != "pad"}
+        out.update(f=q.f, rr=q.rr, product_kind=PRODUCT_KINDS.get(q.product_kind, "?"), nA=q.nA, nB=q.nB, nM=q.nM, nwave=q.nwave, grid=q.grid, wpad=bool(q.wpad),
+                   w_native=bool(q.w_native), polar=bool(q.polar))
+        if retract:
+            out.update(model=q.model, ret_partsM=out["ret_partsM"][:q.nM].copy(), ret_pad=tuple(q.ret_pad))
+        if ls is not None:
+            out["ls_pad"] = tuple(q.ls_pad)
+        if step is not None:
+            out.update(scal_out=fields(q.scal_out), os_out=fields(q.os_out), progress=int(q.progress), run=int(q.run), out_pad=tuple(q.out_pad),
+                       trace=np.array(q.trace[:]) if q.trace_written else None, out_partsB=out["out_partsB"][:q.nB].copy(),
+                       out_partsM=out["out_partsM"][:q.nwave].copy())
+            if phase == PH_TCG:
+                out.update(pHp=q.pHp, rHp=q.rHp, HpHp=q.HpHp)
+            if phase == PH_CAND:
+                out.update(f_cand=q.f_cand, rr_cand=q.rr_cand, m_cand=q.m_cand)
+        return {k: (np.ascontiguousarray(val) if isinstance(val, np.ndarray) else val) for k, val in out.items()}
 
     def reprojection_errors(self, rot, t, P):
         """|r_e|^2 (unrobustified) of every observation in input order at (rot, t, P) -- the layouts of bundle_adjust -- with the
