@@ -795,6 +795,40 @@ typedef struct {
     double *out_partsB, *out_partsM, *out_G, *out_egs, *out_S0, *out_rgR, *out_rgs;
 } xm_outer_probe_t;
 int xm_ctx_outer_probe(xm_ctx_t *ctx, xm_outer_probe_t *probe);
+/* The certificate's Lanczos eigen-solver, a test export (tests/test_gpu_cert_stages.py): at the point (R: 3n x o column-major, s: n; s[0] taken
+ * as 1) and with lam, the context's setup for rank o, the certificate's right-hand side and cert_prepare_kernel as in a solve (the code a solve
+ * runs), then Context::lanczos_min itself with cert_dense_rows, lanczos_mmax and lanczos_restarts of the context's xm_tuning_t.  Single-rank
+ * contexts only (XM_ERR_ARG otherwise, and for o outside 3..10, non-finite input, a wrong struct_size).
+ *   -> ret (lanczos_min's return value: 0 converged, 1 not), eig_exact (XM_CERT_EIG_EXACT would be set), theta, resid (the Ritz residual
+ *      |beta_{m-1} y_{m-1}|), iters (steps of all restart cycles), m_use (size of the tridiagonal matrix theta and y come from), cycles (restart
+ *      cycles run), mmax (steps a cycle can take: min(3n, max(2, lanczos_mmax))), steps_dev (steps the LAST cycle ran on the device: the host
+ *      looks every eight steps, so m_use <= steps_dev), steps_fused / steps_unfused (steps of all cycles through the two forms of a step),
+ *      len (length of the replicated vectors, >= 3n) and nseg (segments a dot product over len is cut into), product_kind (XM_PRODUCT_*),
+ *      Lam (9 n), dz (n), dual[2] as xm_ctx_rtr_probe
+ *   and, from what the last cycle left on the device, into arrays of the caller sized for cap steps (a null pointer skips one; XM_ERR_ARG, with
+ *   the scalars above filled, if mmax > cap and any array is given):
+ *      alpha, beta (mmax each; steps_dev filled), V (3n x (mmax + 1) column-major, columns 0..steps_dev filled, the padding rows dropped),
+ *      c1, c2 (mmax each: the Gram-Schmidt coefficients of the two passes of step steps_dev - 1, steps_dev filled), y (mmax; m_use filled:
+ *      the tridiagonal matrix's eigenvector as the Ritz vector's kernel read it), x (3n: the normalised Ritz vector in global camera order)
+ *   XM_CERT_PROBE_UNFUSED  every step takes the form a solve uses beyond 1024 Lanczos columns (no solve sets this)
+ * Solver state: as after xm_ctx_rtr_probe. */
+#define XM_CERT_PROBE_UNFUSED 1u
+typedef struct {
+    uint32_t struct_size;
+    uint32_t flags;
+    int32_t o, cap;
+    double lam;
+    const double *R, *s;
+    int32_t ret, eig_exact, iters, m_use, cycles, mmax, steps_dev, steps_fused, steps_unfused, nseg, product_kind, pad2;
+    int64_t len;
+    double theta, resid, dual[2];
+    double *Lam, *dz, *alpha, *beta, *V, *c1, *c2, *y, *x;
+} xm_cert_probe_t;
+int xm_ctx_cert_probe(xm_ctx_t *ctx, xm_cert_probe_t *probe);
+/* Smallest eigenpair of the symmetric tridiagonal matrix with diagonal a[0..m) and off-diagonal b[0..m-1), by the certificate's own host code
+ * (Sturm bisection to an interval of 4e-16 max(1, tmax), inverse iteration): *theta, y[0..m) (unit norm), *tmax = the Gershgorin bound of |T|.
+ * Host only, a test export (tests/test_tridiag_min.py). */
+int xm_tridiag_min(const double *a, const double *b, int m, double *theta, double *y, double *tmax);
 /* Large block-sparse Q: "sliced ELL over per-XCD column slabs" (xm-code_amd/csrc/xm_sell.h).  Same product as xm_qw_bsr3
  * (the reference has no sparse product: Dense/matmul.h:42-87 on a dense Q); the matrix is described on the HOST as 3x3-block CSR
  * (rows n, global columns in [0, ncols)) and re-laid on the device.  slabs in {1,2,4,8}; lmax = longest virtual row (hub

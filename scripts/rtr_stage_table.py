@@ -5,7 +5,7 @@
     python scripts/rtr_stage_table.py run.log > profiles/r14_rtr_stage_errors.txt
 
 A second argument names the test file of the run (the outer iteration's other half: tests/test_gpu_outer_stages.py ->
-profiles/r17_outer_stage_errors.txt).  One line per case with its worst quantity (the run prints one per case and quantity), the worst case per quantity, and the largest value of every
+profiles/r17_outer_stage_errors.txt; the certificate's eigen-solver: tests/test_gpu_cert_stages.py -> profiles/r18_cert_stage_errors.txt).  One line per case with its worst quantity (the run prints one per case and quantity), the worst case per quantity, and the largest value of every
 consistency check."""
 import collections
 import re
@@ -38,7 +38,8 @@ for line in open(sys.argv[1]):
         elif kind == "CONS":
             loose.append(f"{label} {rest}")
 tests = sys.argv[2] if len(sys.argv) > 2 else "tests/test_gpu_rtr_stages.py"
-print(f"Stage errors of the trust region's kernels on one MI355X (gfx950): python -m pytest {tests} -m gpu -s ({tail}),")
+what = "the certificate's eigen-solver" if "cert" in tests else "the trust region's kernels"
+print(f"Stage errors of {what} on one MI355X (gfx950): python -m pytest {tests} -m gpu -s ({tail}),")
 print("condensed by scripts/rtr_stage_table.py.  e_ref = error of the f64 run of tests/xm_rtr_exact.py against its longdouble run, e_gpu = error of the")
 print("kernel's output against the same longdouble values, ratio = e_gpu / max(16 e_ref, 64 eps_f64) (the bound: <= 1).  Errors per camera block against")
 print(f"the larger of the exact block's maximum and the magnitude of the terms it is formed from.  The run printed {n_err} STAGE_ERR lines.")

@@ -291,3 +291,147 @@ def test_model_decrease_is_the_second_order_expansion_of_the_cost(n, o, lam):
     print(f"FD model n={n} o={o}: {e1 / float(abs(m['m'])):.2e} at h, {e2 / float(abs(m['m'])):.2e} at h/2, ratio {e1 / e2:.3f}")
     assert e2 <= 1.5 * (float(abs(a1 - b1)) + float(abs(a2 - b2)) / 2) / 3
     assert e2 <= 1e-4 * float(m["m~"])
+
+
+# ---------------------------------------------------------------------------------------------------------------- the certificate's eigen-solver
+import xm_cert_stages as cs
+
+EPS_LD = float(np.finfo(LD).eps)
+
+
+@pytest.mark.parametrize("cid", ["single-n5", "single-n43", "single-n43-optimum"])
+def test_lanczos_reference_tridiagonalises_S(cid):
+    """the whole run in longdouble, taken through all 3n steps (or to an invariant subspace): V^T V = I (column 0 is normalised in f64 as the
+    solver's start vector is: 4 eps_f64 on its diagonal entry; everything else to longdouble round-off), S V_m = V_m T_m + beta_{m-1} v_m e_m^T
+    entry by entry against the magnitude of the terms, and theta = the smallest eigenvalue of S (numpy's eigvalsh of the f64 matrix, whose own
+    error is a few eps |S|; theta is the midpoint of an interval of 4e-16 max(1, tmax))"""
+    S = cs.setup(cid)
+    n = S["n"]
+    E = ex.lanczos_stage(S["op"], S["C"], LD, **cs.run_settings(cs.BY_ID[cid]))
+    m, V = E["m_use"], E["V"]
+    G = V[:, :m].T @ V[:, :m] - np.eye(m)
+    assert abs(float(G[0, 0])) <= 4 * st.EPS
+    G[0, 0] = 0
+    assert float(np.abs(G).max()) <= 64 * m * EPS_LD, float(np.abs(G).max())
+    Sd = cs.dense_S(S, LD)
+    T = np.diag(E["alpha"]) + np.diag(E["beta"][:m - 1], 1) + np.diag(E["beta"][:m - 1], -1)
+    D = Sd @ V[:, :m] - V[:, :m] @ T
+    D[:, m - 1] -= E["beta"][m - 1] * V[:, m]
+    scale = np.abs(Sd) @ np.abs(V[:, :m]) + np.abs(V[:, :m + 1]) @ np.abs(np.vstack([T, np.eye(m)[m - 1:] * E["beta"][m - 1]]))
+    assert float((np.abs(D) / scale).max()) <= 64 * m * EPS_LD
+    assert E["eig_exact"] and E["ret"] == 0
+    ev = np.linalg.eigvalsh(Sd.astype(np.float64))
+    unit = max(1.0, float(E["tmax"]))
+    assert abs(float(E["theta"]) - ev[0]) <= 8e-16 * unit + 16 * st.EPS * np.abs(ev).max()
+    x = E["x"]
+    r = Sd @ x - E["theta"] * x
+    assert float(np.sqrt(r @ r)) <= 1e-6 * unit            # (inverse iteration with a shift 1e-14 away: the vector is far better than theta)
+
+
+def _critical_point(n, o, lam, seed):
+    """a matrix Q for which a random point (R, s) is a critical point of the cost with multipliers that are not zero: Q = L - dz + P A P with
+    L block diagonal and symmetric (traceless blocks for every camera but the anchor: the scale's stationarity), dz the diagonal term of the
+    certificate, P the projector onto the complement of the columns of s R and A any symmetric matrix; then Z sR = L sR, and S = P A P"""
+    rng = np.random.default_rng(seed)
+    R, s = cs.make_point(n, o, seed)
+    R, s = ex.point(R, s, LD)
+    R = ex.polar_rows(ex.blk(R, n)).reshape(3 * n, o)
+    Y = R * np.repeat(s, 3)[:, None]
+    L = np.zeros((3 * n, 3 * n), dtype=LD)
+    for i in range(n):
+        B = rng.standard_normal((3, 3)).astype(LD)
+        B = (B + B.T) / 2
+        if i > 0:
+            B -= np.eye(3) * np.trace(B) / 3
+        L[3 * i:3 * i + 3, 3 * i:3 * i + 3] = B
+    dz = np.zeros(3 * n, dtype=LD)
+    dz[0::3] = 2 * LD(lam) * (s * s - 1)
+    P = np.eye(3 * n, dtype=LD) - Y @ rs.solve_ld(Y.T @ Y, Y.T)
+    A = rng.standard_normal((3 * n, 3 * n)).astype(LD)
+    Q = L - np.diag(dz) + P @ ((A + A.T) / 2) @ P
+    return ex.Op((Q + Q.T) / 2), R, s, L
+
+
+@pytest.mark.parametrize("n,o,lam,polar", [(6, 4, 10.0, False), (9, 3, 1000.0, True), (5, 5, 0.0, False)])
+def test_ritz_vector_is_the_escape_direction_the_staircase_uses(n, o, lam, polar):
+    """at a critical point of rank o, with v = x / s in a new last column, the cost along the line search's retraction of [R 0] + t [0 v] is
+    f + t^2 x^T S x + O(t^3) -- for the Ritz pair of the reference's whole run, t^2 theta.  Central second differences at h and h / 2: the
+    value at h / 2 within the scheme's truncation error estimated from the two, and the error quartering (ratio 3.5 .. 4.5).  The critical
+    point is built, not found: _critical_point."""
+    op, R, s, L = _critical_point(n, o, lam, 90 + n)
+    C = ex.cert_stage(op, R, s, lam, None, LD)
+    assert float(np.abs(C["Lam"] - np.stack([L[3 * i:3 * i + 3, 3 * i:3 * i + 3] for i in range(n)])).max()) <= 1e4 * EPS_LD * float(np.abs(L).max())
+    E = ex.lanczos_stage(op, C, LD)
+    assert E["eig_exact"] and float(E["theta"]) < -0.1     # a direction of descent
+    x, theta = E["x"], E["theta"]
+    Rp = np.concatenate([R, np.zeros((3 * n, 1), dtype=LD)], axis=1)
+    D = np.zeros_like(Rp)
+    D[:, o] = x / np.repeat(s, 3)
+    f = lambda t: ex.cost(op, ex.retract_stage(Rp, s, D, None, t, polar, LD)["Rc"].reshape(3 * n, o + 1), s, lam)
+    f0 = ex.cost(op, R, s, lam)
+    assert abs(float(f(0.0) - f0)) <= 1e3 * EPS_LD * abs(float(f0))
+    d2 = [(f(h) - 2 * f0 + f(-h)) / (LD(h) * LD(h)) / 2 for h in (1e-2, 5e-3)]
+    e1, e2 = (float(abs(d - theta)) for d in d2)
+    print(f"FD escape n={n} o={o}: {e1 / abs(float(theta)):.2e} at h, {e2 / abs(float(theta)):.2e} at h/2, ratio {e1 / e2:.3f}")
+    assert e2 <= 1.5 * float(abs(d2[0] - d2[1])) / 3 and 3.5 <= e1 / e2 <= 4.5
+    assert e2 <= 1e-3 * abs(float(theta))
+
+
+LZ_FAULT_CASES = ("single-n43", "dense-n130", "seg2-n2731", "restarts-n130")
+
+
+def _lz_fault_run(cid, fault):
+    case = cs.BY_ID[cid]
+    S = cs.setup(cid)
+    n = S["n"]
+    pos = np.roll(np.arange(n), 1)                         # a partition that moves every camera (one rank keeps the identity)
+    F = ex.lanczos_stage(S["op64"], S["C64"], np.float64, damage=fault, pos=pos, **cs.run_settings(case))
+    return cs.compare_run(f"{cid}-{fault}", S, cs.as_run(F), case, who="f64", e_ref_run=cs.as_run(S["F"]))
+
+
+@pytest.mark.parametrize("fault", ex.LZ_FAULTS + (None,))
+def test_every_deliberate_lanczos_fault_breaks_the_bound(fault):
+    """the faults a certificate survives, planted in the f64 whole run and judged as the GPU's run is (xm_cert_stages.compare_run): the second
+    Gram-Schmidt pass dropped; the last column left out of the subtraction; alpha from the first pass alone; beta without the square root; one
+    segment's terms dropped from the first pass's dots; y reversed in the Ritz vector; the Ritz vector left in the partition's order.  None: the
+    control.  alpha from the first pass alone differs from alpha by c2[j], which from an orthonormal basis is one round-off of the terms: from
+    the run's own basis it stays under the bound, so it is planted in the step form as well, from a basis that is orthonormal to 1e-6 only --
+    there it must break alpha and nothing else."""
+    broken = []
+    for cid in LZ_FAULT_CASES:
+        broken += _lz_fault_run(cid, fault)
+    if fault in ("lz_alpha_pass1", None):
+        S = cs.setup("dense-n130")
+        rng = np.random.default_rng(5)
+        V = np.asarray(S["F"]["V"][:, :9]) + 1e-6 * rng.standard_normal((3 * S["n"], 9))
+        E = ex.lanczos_stage(S["op"], S["C"], LD, V=V)
+        F, Fd = (ex.lanczos_stage(S["op64"], S["C64"], np.float64, V=V, damage=d) for d in (None, fault))
+        hit = [k for k in ex.LZ_STEP_KEYS if rs.error(Fd[k], E, k)[0] > st.bound(rs.error(F[k], E, k)[0])]
+        assert hit == (["alpha"] if fault else []), hit
+        broken += hit
+    print(f"FAULT {fault}: " + "; ".join(broken[:6]))
+    assert (not broken) if fault is None else broken, (fault, broken[:6])
+
+
+def test_lanczos_cases_end_as_the_gpu_tests_expect():
+    """the f64 run of the reference ends every case the way tests/test_gpu_cert_stages.py asserts for the GPU, with a margin at each threshold
+    the ending depends on: the exhaustion cases stop at m = 2 with beta_1 a factor 10 under 1e-13 max(1, tmax) and beta_0 far above; the run that
+    is cut short keeps its residual a factor 1e3 above the convergence limit; the segment counts are those listed"""
+    for case in cs.CASES:
+        S = cs.setup(case["id"])
+        F = S["F"]
+        for k, v in case.get("expect", {}).items():
+            if k in F:
+                assert int(F[k]) == v, (case["id"], k, F[k])
+        assert ex.dots_segments(-(-3 * S["n"] // 128) * 128)[0] == case["nseg"], case["id"]
+        unit = max(1.0, float(F["tmax"]))
+        if case.get("exhaust"):
+            assert F["beta"][1] <= 1e-14 * unit and F["beta"][0] >= 1e-3 * unit, (case["id"], F["beta"])
+            assert abs(float(F["theta"])) <= 64 * st.EPS * S["n"]
+        if case["id"] == "cut-short-n130":
+            assert float(F["resid"]) >= 1e-3 * unit
+        if case.get("restarts"):
+            assert F["cycles"] > 1
+    nseg, seg = ex.dots_segments(262272)
+    assert (nseg, seg) == (64, 4352) and sum(1 for q in range(64) if q * seg >= 262272) == 3      # the last three segments are empty
+    assert ex.dots_segments(8320) == (2, 4352) and ex.dots_segments(12416)[0] == 3

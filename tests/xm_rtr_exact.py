@@ -12,7 +12,8 @@ a scalar): the products' terms are bounded through |Q| |W|, and what is built fr
 the exact block's maximum and this magnitude -- at a critical point, where the exact gradient is 0, the first alone would compare one round-off
 with another.
 
-damage= (f64 runs of tests/test_rtr_exact.py only) plants one deliberate fault; the names are those of FAULTS."""
+damage= (f64 runs of tests/test_rtr_exact.py only) plants one deliberate fault; the names are those of FAULTS and, for the certificate's
+eigen-solver, LZ_FAULTS."""
 import numpy as np
 
 LD = np.longdouble
@@ -342,13 +343,203 @@ def cert_stage(op, R, s, lam, X=None, dt=LD, damage=None):
     dual1 = lam * (1 - xii * xii).sum()                    # :330-332
     out = {"Lam": Lam, "Lam~": aLam, "dz": dz, "dz~": adz, "dual0": dual0, "dual0~": 3 * aLam[0], "dual1": dual1, "dual1~": lam * (1 + xii * xii).sum()}
     if X is not None:
-        X = np.asarray(X).astype(dt)
-        Xb = blk(X, n)
-        SX = blk(op(X, dt), n) - np.einsum("iab,ibk->iak", Lam, Xb)
-        SX[:, row, :] += dz[:, None] * Xb[:, row, :]
-        aSX = blk(op.absolute(X, dt), n).max(axis=(1, 2)) + adz * np.abs(Xb[:, 0, :]).max(axis=1) + 3 * aLam * np.abs(Xb).max(axis=(1, 2))
-        out.update({"SX": SX, "SX~": aSX})
+        out.update(cert_operator(op, out, X, dt, damage))
     return out
+
+
+def cert_operator(op, C, X, dt=LD, damage=None):
+    """S X = Z X - Lam X (checkeig.h:303-318) from the multipliers C = cert_stage(...) of the point"""
+    Lam, dz, adz, aLam = C["Lam"].astype(dt), C["dz"].astype(dt), C["dz~"].astype(dt), C["Lam~"].astype(dt)
+    n = dz.size
+    row = 1 if damage == "dz_row" else 0
+    X = np.asarray(X).astype(dt)
+    Xb = blk(X, n)
+    SX = blk(op(X, dt), n) - np.einsum("iab,ibk->iak", Lam, Xb)
+    SX[:, row, :] += dz[:, None] * Xb[:, row, :]
+    aSX = blk(op.absolute(X, dt), n).max(axis=(1, 2)) + adz * np.abs(Xb[:, 0, :]).max(axis=1) + 3 * aLam * np.abs(Xb).max(axis=(1, 2))
+    return {"SX": SX, "SX~": aSX}
+
+
+# ---------------------------------------------------------------------------------------------------------------- the certificate's eigen-solver
+# Context::lanczos_min restated: Lanczos on S with two classical Gram-Schmidt passes against every earlier column, the smallest eigenpair of the
+# tridiagonal matrix by Sturm bisection and inverse iteration, restart cycles from the Ritz vector.  Vectors are in global camera order throughout
+# (the device keeps them in the partition's position order, which is the same on one rank).
+LZ_FAULTS = ("lz_no_pass2", "lz_skip_last", "lz_alpha_pass1", "lz_beta_no_sqrt", "lz_drop_segment", "lz_y_reversed", "lz_no_unmap")
+LZ_STEP_KEYS = ("c1", "c2", "alpha", "beta", "w")
+
+
+def lanczos_start(n):
+    """the start vector, bit for bit: a 64-bit linear congruential generator drawn in global order, 53 bits each, minus 1/2, the squares summed in
+    order, every entry divided by the root of the sum (all in f64, whatever dtype the run continues in)"""
+    state, mask = 0x9E3779B97F4A7C15, (1 << 64) - 1
+    v = np.empty(3 * n)
+    for i in range(3 * n):
+        state = (state * 6364136223846793005 + 1442695040888963407) & mask
+        v[i] = (state >> 11) / 9007199254740992.0 - 0.5
+    return v / np.sqrt(np.cumsum(v * v)[-1])               # (cumsum adds in order; sum would add pairwise)
+
+
+def dots_segments(length):
+    """(segments, elements per segment) of a dot product over `length` elements: dots_multi_segments and the launchers' segment length"""
+    nseg = min(64, max(1, length // 4096))
+    return nseg, (-(-length // nseg) + 255) // 256 * 256
+
+
+def lanczos_step(op, C, V, dt=LD, damage=None, length=None, scales=True):
+    """one step from the columns V[:, 0..j] as given (3n x (j + 1)): w = S v_j, two classical Gram-Schmidt passes against all j + 1 columns with the
+    coefficients c1 and c2, alpha_j = c1[j] + c2[j], beta_j = |w|; w is returned un-normalised (n x 3).  Magnitudes: S v_j's from cert_operator
+    (per camera) for w; that, summed through |V|, for the coefficients and alpha; its 2-norm for beta.  length: elements of the device's vectors
+    (3n rounded up; only the fault "one segment's terms dropped" reads it)"""
+    V = np.asarray(V).astype(dt, copy=False)
+    j, n = V.shape[1] - 1, C["dz"].size
+    o = cert_operator(op, C, V[:, j:j + 1], dt)
+    w, a3 = o["SX"].reshape(-1), np.repeat(o["SX~"], 3)
+    keep = np.ones(3 * n, dtype=bool)
+    if damage == "lz_drop_segment":                        # in every dot product of the step, as a fault of their kernel would; a vector of one segment is left alone
+        nseg, seg = dots_segments(length or -(-3 * n // 128) * 128)
+        if nseg > 1:
+            keep[(nseg - 1) * seg:] = False                # the last segment that holds anything (the short one)
+    cols = slice(0, j) if damage == "lz_skip_last" else slice(0, j + 1)
+    c1 = V.T @ np.where(keep, w, 0)
+    w = w - V[:, cols] @ c1[cols]
+    if damage == "lz_no_pass2":
+        c2 = np.zeros(j + 1, dtype=dt)
+    else:
+        c2 = V.T @ np.where(keep, w, 0)
+        w = w - V[:, cols] @ c2[cols]
+    alpha = c1[j] if damage == "lz_alpha_pass1" else c1[j] + c2[j]
+    ww = w @ np.where(keep, w, 0)
+    beta = ww if damage == "lz_beta_no_sqrt" else np.sqrt(ww)
+    ac = np.abs(V).T @ a3 if scales else np.zeros(j + 1, dtype=dt)
+    return {"w": w.reshape(n, 3), "w~": o["SX~"], "c1": c1, "c1~": ac, "c2": c2, "c2~": ac, "alpha": alpha, "alpha~": ac[j], "beta": beta,
+            "beta~": np.sqrt(a3 @ a3)}
+
+
+def sturm_count(a, b, x):
+    """eigenvalues below x of the tridiagonal matrix (diagonal a, off-diagonal b)"""
+    d = a[0] - x
+    cnt = int(d < 0)
+    for i in range(1, len(a)):
+        if d == 0:
+            d = type(d)(1e-300)
+        d = (a[i] - x) - b[i - 1] * b[i - 1] / d
+        cnt += int(d < 0)
+    return cnt
+
+
+def tridiag_bounds(a, b):
+    """Gershgorin interval of the tridiagonal matrix and tmax = the larger of its ends' magnitudes"""
+    a, b = np.asarray(a), np.asarray(b)[:len(a) - 1]
+    r = np.zeros(len(a), dtype=a.dtype)
+    r[:-1] += np.abs(b)
+    r[1:] += np.abs(b)
+    lo, hi = (a - r).min(), (a + r).max()
+    return lo, hi, max(abs(lo), abs(hi))
+
+
+def tridiag_min(a, b, dt=LD):
+    """tridiag_min of xm_solver.hip restated over a dtype: bisection on the Sturm count down to an interval of 4e-16 max(1, tmax), its midpoint
+    theta, then three rounds of inverse iteration with the shift theta - 1e-14 max(1, tmax) from the constant vector (here through a dense solve
+    in place of the pivoted tridiagonal elimination: the same equations).  -> theta, y (unit norm), tmax"""
+    a, b = np.asarray(a).astype(dt), np.asarray(b).astype(dt)[:len(a) - 1]
+    m = len(a)
+    lo, hi, tmax = tridiag_bounds(a, b)
+    unit = max(dt(1), tmax)
+    for _ in range(200):
+        if not hi - lo > dt(4e-16) * unit:
+            break
+        mid = (lo + hi) / 2
+        if sturm_count(a, b, mid) >= 1:
+            hi = mid
+        else:
+            lo = mid
+    theta = (lo + hi) / 2
+    if m == 1:
+        return theta, np.ones(1, dtype=dt), tmax
+    y = np.full(m, 1 / np.sqrt(dt(m)), dtype=dt)
+    d, e = a - (theta - dt(1e-14) * unit), b.copy()
+    for _ in range(3):
+        y = tridiag_solve(d, e, y)
+        y = y / np.sqrt(y @ y)
+    return theta, y, tmax
+
+
+def tridiag_solve(d, e, rhs):
+    """(tridiagonal with diagonal d, off-diagonal e) x = rhs by elimination with partial pivoting, in the arrays' dtype"""
+    m = len(d)
+    dd, du, du2, dl, x = d.copy(), np.append(e, 0), np.zeros(m, dtype=d.dtype), np.append(e, 0), rhs.copy()
+    for i in range(m - 1):
+        if abs(dd[i]) >= abs(dl[i]):
+            f = dl[i] / dd[i]
+            dd[i + 1] -= f * du[i]
+            x[i + 1] -= f * x[i]
+        else:
+            f = dd[i] / dl[i]
+            t_dd, t_du = dd[i + 1], du[i + 1]
+            dd[i], old_du = dl[i], du[i]
+            du[i] = t_dd
+            du2[i] = t_du if i < m - 2 else 0
+            dd[i + 1] = old_du - f * t_dd
+            if i < m - 2:
+                du[i + 1] = -f * t_du
+            x[i], x[i + 1] = x[i + 1], x[i] - f * x[i + 1]
+    x[m - 1] = x[m - 1] / dd[m - 1]
+    x[m - 2] = (x[m - 2] - du[m - 2] * x[m - 1]) / dd[m - 2]
+    for i in range(m - 3, -1, -1):
+        x[i] = (x[i] - du[i] * x[i + 1] - du2[i] * x[i + 2]) / dd[i]
+    return x
+
+
+def lanczos_stage(op, C, dt=LD, mmax=400, restarts=12, dense_rows=384, damage=None, pos=None, length=None, V=None):
+    """V given: lanczos_step, one step from those columns.  Otherwise the whole run of Context::lanczos_min from lanczos_start with its stop rules:
+    a cycle takes up to min(3n, max(2, mmax)) steps; with 3n <= dense_rows and 3n <= mmax ("exact") it ends only when the Krylov space is
+    exhausted (3n steps, or beta < 1e-13 max(1, tmax)), otherwise also at a Ritz residual |beta_{m-1} y_{m-1}| <= 1e-9 max(1, tmax); the Ritz
+    vector starts the next of up to `restarts` cycles; converged (ret 0) means a residual <= 1e-6 max(1, tmax).  pos (camera -> position; only
+    the fault "not mapped back" reads it).  -> alpha, beta, V (3n x (m_use + 1)), y, x, theta, resid, ret, eig_exact, m_use, cycles, iters, tmax, c1 and c2 of the last step"""
+    if V is not None:
+        return lanczos_step(op, C, V, dt, damage, length)
+    n = C["dz"].size
+    m3 = 3 * n
+    mmax = min(m3, max(2, mmax))
+    exact = m3 <= dense_rows and m3 <= mmax
+    x = lanczos_start(n).astype(dt)
+    eig_exact, iters, resid, theta, tmax = False, 0, dt(1e300), dt(0), dt(1)
+    for cycle in range(max(1, restarts)):
+        V = np.zeros((m3, mmax + 1), dtype=dt)
+        V[:, 0] = x
+        al, be, done, m_use, y = [], [], False, 0, None
+        for j in range(mmax):
+            st = step = lanczos_step(op, C, V[:, :j + 1], dt, damage, length, scales=False)
+            iters += 1
+            al.append(st["alpha"])
+            beta = st["beta"]
+            V[:, j + 1] = st["w"].reshape(-1) / beta if beta > 0 else 0
+            m_use = m = j + 1
+            tmax = tridiag_bounds(np.array(al, dtype=dt), np.array(be + [dt(0)], dtype=dt))[2]
+            exhausted = m == m3 or beta < dt(1e-13) * max(dt(1), tmax)
+            y = None
+            if not exact or exhausted or j == mmax - 1:        # (an exact run looks at the residual only when it ends)
+                theta, y, tmax = tridiag_min(al, be + [dt(0)], dt)
+                resid = abs(beta * y[m - 1])
+            if exact and exhausted and np.isfinite(beta):
+                eig_exact = True
+            if (not exact and resid <= dt(1e-9) * max(dt(1), tmax)) or exhausted or not np.isfinite(beta):
+                done = True
+                break
+            be.append(beta)
+        yy = y[::-1] if damage == "lz_y_reversed" else y
+        x = V[:, :m_use] @ yy
+        x = x / np.sqrt(x @ x)
+        if done:
+            break
+    be = (be + [beta])[:m_use]
+    xo = x
+    if damage == "lz_no_unmap" and pos is not None:
+        xo = np.empty_like(x)
+        xo.reshape(n, 3)[np.asarray(pos)] = x.reshape(n, 3)
+    return dict(alpha=np.array(al, dtype=dt), beta=np.array(be, dtype=dt), V=V[:, :m_use + 1], y=y, x=xo, theta=theta, resid=resid,
+                ret=0 if resid <= dt(1e-6) * max(dt(1), tmax) else 1, eig_exact=eig_exact, m_use=m_use, cycles=cycle + 1, iters=iters, tmax=tmax,
+                c1=step["c1"], c2=step["c2"])
 
 
 def polar_rows(M):

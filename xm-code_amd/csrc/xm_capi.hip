@@ -551,6 +551,32 @@ int xm_ctx_outer_probe(xm_ctx_t *ctx, xm_outer_probe_t *pr) {
     return XM_OK;
     XM_CATCH
 }
+int xm_ctx_cert_probe(xm_ctx_t *ctx, xm_cert_probe_t *pr) {
+    XM_TRY
+    if (!ctx || !pr) throw xm::Error(XM_ERR_ARG, "xm_ctx_cert_probe: null argument");
+    if (pr->struct_size != sizeof(xm_cert_probe_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_cert_probe: xm_cert_probe_t.struct_size is not sizeof(xm_cert_probe_t)");
+    if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_cert_probe: single-GPU contexts only (not n_gpus > 1)");
+    if (ctx->impl->world() > 1 || ctx->impl->comm_kind() != 0) throw xm::Error(XM_ERR_ARG, "xm_ctx_cert_probe: single-rank contexts only");
+    if (pr->o < 3 || pr->o > 10) throw xm::Error(XM_ERR_ARG, "xm_ctx_cert_probe: rank o must be in 3..10");
+    if (pr->flags & ~XM_CERT_PROBE_UNFUSED) throw xm::Error(XM_ERR_ARG, "xm_ctx_cert_probe: unknown flag");
+    if (!pr->R || !pr->s) throw xm::Error(XM_ERR_ARG, "xm_ctx_cert_probe: the point (R, s) is missing");
+    const int64_t n = ctx->impl->cameras();
+    if (!std::isfinite(pr->lam)) throw xm::Error(XM_ERR_ARG, "xm_ctx_cert_probe: lam is not finite");
+    for (int64_t k = 0; k < 3 * n * pr->o; ++k)
+        if (!std::isfinite(pr->R[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_cert_probe: R is not finite");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(pr->s[i]) || !(pr->s[i] > 0.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_cert_probe: scales must be finite and positive");
+    ctx->impl->cert_probe(*pr);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_tridiag_min(const double *a, const double *b, int m, double *theta, double *y, double *tmax) {
+    XM_TRY
+    if (!a || !theta || !y || !tmax || m < 1 || (m > 1 && !b)) throw xm::Error(XM_ERR_ARG, "xm_tridiag_min: null argument or m < 1");
+    xm::tridiag_min_export(a, b, m, theta, y, tmax);
+    return XM_OK;
+    XM_CATCH
+}
 namespace {
 void clean_settings(const char *who, const xm_clean_options_t *opt, const uint8_t *keep, const int32_t *cam_index, const int32_t *lm_index,
                     const xm_clean_result_t *res, xm::CleanSettings &c) {

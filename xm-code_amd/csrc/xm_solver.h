@@ -163,6 +163,7 @@ public:
     void ba_probe(const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q);   // test export
     void outer_probe(xm_outer_probe_t &q);   // test export (xm_ctx_outer_probe): the retraction and the device-driven step launch stage by stage
     void rtr_probe(xm_rtr_probe_t &q);   // test export (include/xm_amd.h: xm_ctx_rtr_probe): the trust region's kernels stage by stage
+    void cert_probe(xm_cert_probe_t &q); // test export (xm_ctx_cert_probe): the certificate's Lanczos eigen-solver
     void reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr);   // per observation, input order (xm_ba.h)
     // which observations, cameras and landmarks of the list survive cleaning at the current weights (xm_clean.h); changes nothing here
     void clean_observations(const CleanSettings &cfg, uint8_t *keep, int32_t *cam_index, int32_t *lm_index, CleanOutcome &out);
@@ -308,12 +309,17 @@ private:
     DevBuf<OuterScal> oscal_;            // trust-region state of the device-driven outer iteration, two parity copies next to scal_
     unsigned int outer_run_ = 0;         // run number in the progress word (hstat_[24])
     CertResult certificate(int o, double primal, std::vector<double> &v_out);
+    int cert_multipliers(int o, double lam);   // Lam, dz and the dual value's partial sums at the point in R_ / s_; returns the partial count per rank and sum
     int lanczos_min(std::vector<double> &x_out, double &theta, int &iters, double &resid);   // 0 converged, 1 not
+    int lz_m_use_ = 0, lz_cycles_ = 0;   // of the last lanczos_min(): size of the tridiagonal matrix behind theta, restart cycles run (cert_probe())
+    bool lz_unfused_ = false;            // cert_probe() only, false in every solve: every Lanczos step takes the form used beyond lz_fused_ok()
     void cert_product(const double *vj, const CamArgs &a, int j);   // a.out = S vj for a replicated vector of pitch 1 (EPI_CERT; j: sweep direction of the symmetric pair)
     void log(const char *fmt, ...) const;
 };
 
 // single-process multi-GPU driver (xm_team.hip): `n_gpus` Contexts, one host thread and one device each, joined by a peer group
+void tridiag_min_export(const double *a, const double *b, int m, double *theta, double *y, double *tmax);   // xm_tridiag_min (host only)
+
 class Team {
 public:
     Team(const xm_problem_t &prob, int n_gpus, int gpu_map);

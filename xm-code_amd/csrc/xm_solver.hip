@@ -1517,7 +1517,7 @@ int Context::lanczos_min(std::vector<double> &x_out, double &theta_out, int &ite
                 res_->qw_products++;
                 if (comm_->active()) comm_->allgather(w.p, (size_t)nloc_ * 3, st_);
                 // classical Gram-Schmidt twice against V(:,0..j); alpha_j = c1[j] + c2[j]; beta_j = |w|; v_{j+1} = w / beta_j
-                if (lz_fused_ok(j + 1)) {   // seven launches per step: the sums of the partial dots are taken by the kernels that use them (same bits)
+                if (lz_fused_ok(j + 1) && !lz_unfused_) {   // seven launches per step: the sums of the partial dots are taken by the kernels that use them (same bits)
                     launch_dots_multi_parts(V.p, len, j + 1, w.p, len, dscr.p, st_);
                     launch_sub_vc_fin(w.p, V.p, len, dscr.p, j + 1, len, c.p, nullptr, nullptr, st_);
                     launch_dots_multi_parts(V.p, len, j + 1, w.p, len, dscr.p, st_);
@@ -1551,8 +1551,9 @@ int Context::lanczos_min(std::vector<double> &x_out, double &theta_out, int &ite
         }
         // Ritz vector x = V(:,0..m_use-1) y
         if ((int)y.size() != m_use) tridiag_min(al, be, m_use, theta, y, tmax);
-        to_dev(c.p, y.data(), (size_t)m_use * sizeof(double));
-        launch_gemv_n(w.p, V.p, len, c.p, m_use, len, st_);
+        lz_m_use_ = m_use; lz_cycles_ = restart + 1;   // read by the test export cert_probe() only
+        to_dev(dscr.p, y.data(), (size_t)m_use * sizeof(double));   // into the dots' scratch (free here, >= mmax + 1 doubles): c1 / c2 keep the last step's coefficients
+        launch_gemv_n(w.p, V.p, len, dscr.p, m_use, len, st_);
         to_host(x.data(), w.p, (size_t)len * sizeof(double));
         double nn = 0;
         for (int64_t i = 0; i < len; ++i) nn += x[(size_t)i] * x[(size_t)i];
@@ -1571,11 +1572,9 @@ int Context::lanczos_min(std::vector<double> &x_out, double &theta_out, int &ite
 // ------------------------------------------------------------------------------------------------------------------
 // dual certificate (checkeig.h:42-368)
 // ------------------------------------------------------------------------------------------------------------------
-CertResult Context::certificate(int o, double primal, std::vector<double> &v_out) {
-    CertResult cr;
-    const auto t0 = clk::now();
-    int64_t pst0[3] = {0, 0, 0};
-    const int64_t pcg_unconverged_at_start = schur_info(pst0, nullptr) ? pst0[2] : 0;
+// The certificate's multipliers at the point in R_ / s_ (certificate() and the test export cert_probe()): Lam -> ps_[cur_ ^ 1].S0, dz -> .egs, and the
+// dual value's partial sums in partsM_, 2 g per rank with g = (nloc_ + 255) / 256, all-gathered.  Returns g.
+int Context::cert_multipliers(int o, double lam) {
     double *Wloc = W_.p + (size_t)cam0_ * 3 * OP_;
     // Right-hand side pieces: C * sR  (checkeig.h:182 with the diagonal term folded into cert_prepare)
     launch_scale_rows(o, nloc_, R_.p, s_.p, Wloc, st_);
@@ -1585,8 +1584,17 @@ CertResult Context::certificate(int o, double primal, std::vector<double> &v_out
     product(EPI_PLAIN, o, 1.0, a);
     const int g = (nloc_ + 255) / 256;
     double *Lam = ps_[cur_ ^ 1].S0.p, *dz = ps_[cur_ ^ 1].egs.p;
-    launch_cert_prepare(o, nloc_, cam0_, opt_->lam, HpR_.p, R_.p, s_.p, Lam, dz, partsM_.p + (size_t)comm_->rank * 2 * g, st_);
+    launch_cert_prepare(o, nloc_, cam0_, lam, HpR_.p, R_.p, s_.p, Lam, dz, partsM_.p + (size_t)comm_->rank * 2 * g, st_);
     if (comm_->active()) comm_->allgather(partsM_.p, (size_t)2 * g, st_);
+    return g;
+}
+
+CertResult Context::certificate(int o, double primal, std::vector<double> &v_out) {
+    CertResult cr;
+    const auto t0 = clk::now();
+    int64_t pst0[3] = {0, 0, 0};
+    const int64_t pcg_unconverged_at_start = schur_info(pst0, nullptr) ? pst0[2] : 0;
+    const int g = cert_multipliers(o, opt_->lam);
     const double dual = sum_parts(partsM_.p, 2 * g * comm_->world);   // y0+y3+y5 + lam*sum(1 - xii^2)  (checkeig.h:322-332)
     // lambda_min(S) and its eigenvector
     XM_HIP_CHECK(hipMemsetAsync(W_.p, 0, W_.count * sizeof(double), st_));
@@ -1652,6 +1660,76 @@ void Context::apply(int o, const double *Wh, double *out, double alpha) {
         for (int k = 0; k < o; ++k) out[r + (size_t)k * m] = res[r * OP_ + k];
     opt_ = nullptr;
     solved_ = false;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The certificate's eigen-solver (test export xm_ctx_cert_probe, include/xm_amd.h): setup_rank(), cert_multipliers() and lanczos_min() as
+// certificate() runs them, then what the last restart cycle left in the Lanczos workspace.  Solver state as after rtr_probe().
+// ------------------------------------------------------------------------------------------------------------------
+void tridiag_min_export(const double *a, const double *b, int m, double *theta, double *y, double *tmax) {
+    std::vector<double> av(a, a + m), bv(b, b + std::max(0, m - 1)), yv;
+    tridiag_min(av, bv, m, *theta, yv, *tmax);
+    std::copy(yv.begin(), yv.end(), y);
+}
+
+void Context::cert_probe(xm_cert_probe_t &q) {
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_cert_probe: single-rank contexts only");
+    const int o = q.o;
+    xm_options_t opt;
+    std::memset(&opt, 0, sizeof(opt));
+    opt.lam = q.lam;
+    opt.max_rank = (unsigned)o;
+    xm_result_t res;
+    std::memset(&res, 0, sizeof(res));
+    struct Leave { Context *c; ~Leave() { c->opt_ = nullptr; c->res_ = nullptr; c->lz_unfused_ = false; c->solved_ = false; } } leave{this};
+    opt_ = &opt;
+    res_ = &res;
+    grouping_ = 0;
+    lz_unfused_ = (q.flags & XM_CERT_PROBE_UNFUSED) != 0;
+    setup_rank(o);
+    const size_t n = (size_t)n_, m3 = 3 * n;
+    upload_point(std::vector<double>(q.R, q.R + m3 * (size_t)o), o, std::vector<double>(q.s, q.s + n));
+    const int g = cert_multipliers(o, q.lam);
+    std::vector<double> parts((size_t)2 * g);
+    to_host(parts.data(), partsM_.p, parts.size() * sizeof(double));
+    q.dual[0] = q.dual[1] = 0.0;
+    for (int i = 0; i < g; ++i) { q.dual[0] += parts[(size_t)i]; q.dual[1] += parts[(size_t)g + i]; }   // in sum_parts()'s order
+    if (q.Lam) to_host(q.Lam, ps_[cur_ ^ 1].S0.p, n * 9 * sizeof(double));
+    if (q.dz) to_host(q.dz, ps_[cur_ ^ 1].egs.p, n * sizeof(double));
+    XM_HIP_CHECK(hipMemsetAsync(W_.p, 0, W_.count * sizeof(double), st_));
+    std::vector<double> x;
+    double theta = 0, resid = 0;
+    int its = 0;
+    lz_m_use_ = lz_cycles_ = 0;
+    q.ret = lanczos_min(x, theta, its, resid);
+    const int64_t len = ld_;
+    const int mmax = (int)std::min<int64_t>((int64_t)m3, std::max(2, cfg_.lanczos_mmax));   // as lanczos_min()
+    const int m_use = lz_m_use_, cycles = lz_cycles_, steps_dev = its - (cycles - 1) * mmax;   // a cycle that is not the last runs all mmax steps
+    q.eig_exact = eig_exact_ ? 1 : 0; q.iters = its; q.m_use = m_use; q.cycles = cycles; q.mmax = mmax; q.steps_dev = steps_dev;
+    auto fused = [&](int steps) { int k = 0; for (int j = 0; j < steps; ++j) k += (lz_fused_ok(j + 1) && !lz_unfused_) ? 1 : 0; return k; };   // lanczos_min()'s test
+    q.steps_fused = fused(steps_dev) + (cycles - 1) * fused(mmax);
+    q.steps_unfused = its - q.steps_fused;
+    q.nseg = dots_multi_segments(len); q.len = len; q.product_kind = product_kind(o);
+    q.theta = theta; q.resid = resid;
+    if (mmax > q.cap && (q.alpha || q.beta || q.V || q.c1 || q.c2 || q.y))
+        throw Error(XM_ERR_ARG, "xm_ctx_cert_probe: the arrays hold cap = " + std::to_string(q.cap) + " steps, a cycle of this context takes " + std::to_string(mmax));
+    if (steps_dev < m_use || steps_dev > mmax || cycles < 1) throw Error(XM_ERR_HIP, "xm_ctx_cert_probe: the step counts of lanczos_min() do not add up");
+    std::vector<double> hab((size_t)2 * (mmax + 1));
+    to_host(hab.data(), lzab_.p, hab.size() * sizeof(double));
+    if (q.alpha) std::copy(hab.begin(), hab.begin() + steps_dev, q.alpha);
+    if (q.beta) std::copy(hab.begin() + (mmax + 1), hab.begin() + (mmax + 1) + steps_dev, q.beta);
+    if (q.c1) to_host(q.c1, lzc_.p, (size_t)steps_dev * sizeof(double));
+    if (q.c2) to_host(q.c2, lzc2_.p, (size_t)steps_dev * sizeof(double));
+    if (q.y) to_host(q.y, lzscr_.p, (size_t)m_use * sizeof(double));
+    if (q.V) {
+        std::vector<double> col((size_t)len);
+        for (int j = 0; j <= steps_dev; ++j) {
+            to_host(col.data(), lzV_.p + (size_t)j * len, (size_t)len * sizeof(double));
+            for (size_t i = 0; i < m3; ++i) q.V[(size_t)j * m3 + i] = col[(size_t)(3 * pos_of((int64_t)(i / 3))) + i % 3];
+        }
+    }
+    if (q.x) std::copy(x.begin(), x.end(), q.x);
+    XM_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -36,7 +36,7 @@ EXPORTS = [
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
     "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_ba_aggregate_plan", "xm_ctx_ba_probe",
-    "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe", "xm_ctx_outer_probe",
+    "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe", "xm_ctx_outer_probe", "xm_ctx_cert_probe", "xm_tridiag_min",
     "xm_ctx_dense_q", "xm_create_matrix", "xm_schur_dense_limits",
     "xm_pair_filter", "xm_pair_filter_limits",
 ]
@@ -165,6 +165,32 @@ OUTER_PROBE_RETRACT, OUTER_PROBE_MODEL_REC, OUTER_PROBE_RETRACT_LS, OUTER_PROBE_
 PH_TCG, PH_CAND, PH_STOP, PH_INIT = 0, 1, 2, 3
 
 
+CERT_OUT = ("Lam", "dz", "alpha", "beta", "V", "c1", "c2", "y", "x")
+CERT_INTS = ("ret", "eig_exact", "iters", "m_use", "cycles", "mmax", "steps_dev", "steps_fused", "steps_unfused", "nseg", "product_kind")
+
+
+class CertProbe(C.Structure):   # xm_cert_probe_t, the test export xm_ctx_cert_probe
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("o", C.c_int32), ("cap", C.c_int32), ("lam", C.c_double), ("R", C.c_void_p), ("s", C.c_void_p)] + \
+               [(k, C.c_int32) for k in CERT_INTS + ("pad2",)] + [("len", C.c_int64), ("theta", C.c_double), ("resid", C.c_double), ("dual", C.c_double * 2)] + \
+               [(k, C.c_void_p) for k in CERT_OUT]
+
+
+CERT_PROBE_UNFUSED = 1
+
+
+def tridiag_min(a, b):
+    """smallest eigenpair of the symmetric tridiagonal matrix (diagonal a[0..m), off-diagonal b[0..m-1)) by the certificate's host code
+    (xm_tridiag_min; no GPU): theta, y, tmax"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    if a.ndim != 1 or a.size < 1 or b.shape != (a.size - 1,):
+        raise ValueError("tridiag_min: a is the diagonal (m >= 1), b the m - 1 off-diagonal entries")
+    theta, tmax, y = C.c_double(), C.c_double(), np.zeros(a.size)
+    bp = b.ctypes.data_as(C.c_void_p) if b.size else None
+    _chk(lib().xm_tridiag_min(a.ctypes.data_as(C.c_void_p), bp, int(a.size), C.byref(theta), y.ctypes.data_as(C.c_void_p), C.byref(tmax)))
+    return theta.value, y, tmax.value
+
+
 def pack_prog(run, slots, phase):
     """the progress word of the device-driven outer iteration: [run : 32 | launch pairs done : 24 | phase : 8]"""
     return (int(run) << 32) | ((int(slots) & 0xffffff) << 8) | (int(phase) & 0xff)
@@ -258,6 +284,8 @@ def lib():
         L.xm_ctx_ba_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaProbe)]
         L.xm_ctx_rtr_probe.argtypes = [C.c_void_p, C.POINTER(RtrProbe)]
         L.xm_ctx_outer_probe.argtypes = [C.c_void_p, C.POINTER(OuterProbe)]
+        L.xm_ctx_cert_probe.argtypes = [C.c_void_p, C.POINTER(CertProbe)]
+        L.xm_tridiag_min.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.POINTER(C.c_double)]
         L.xm_clean_observations.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CleanOptions), C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.POINTER(CleanResult)]
         L.xm_ctx_clean_observations.argtypes = [C.c_void_p, C.POINTER(CleanOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CleanResult)]
@@ -1116,6 +1144,32 @@ class Context:
         if cert:
             out["dual"] = np.array(q.dual[:])
         return {k: (np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v) for k, v in out.items()}
+
+    def cert_probe(self, o, lam, R, s, unfused=False, mmax=None, want_V=True):
+        """the certificate's Lanczos eigen-solver at the point (R: 3n x o, s: n) (the test export xm_ctx_cert_probe; include/xm_amd.h): a dict of
+        ret, eig_exact, theta, resid, iters, m_use, cycles, mmax, steps_dev, steps_fused, steps_unfused, nseg, len, product_kind, Lam (n x 3 x 3), dz,
+        dual (2), alpha, beta, c1, c2 (steps_dev each), y (m_use), x (3n) and V (3n x (steps_dev + 1)) from the last restart cycle.  mmax: the
+        context's lanczos_mmax (None: its default, 400), which sizes the arrays; unfused=True: XM_CERT_PROBE_UNFUSED."""
+        n, o = self.n, int(o)
+        cap = min(3 * n, max(2, int(mmax) if mmax else 400))
+        q = CertProbe()
+        q.struct_size = C.sizeof(CertProbe)
+        q.o, q.cap, q.lam, q.flags = o, cap, float(lam), (CERT_PROBE_UNFUSED if unfused else 0)
+        ins = dict(R=np.asfortranarray(np.asarray(R, dtype=np.float64).reshape(3 * n, o)), s=np.ascontiguousarray(np.asarray(s, dtype=np.float64).reshape(n)))
+        out = dict(Lam=np.zeros((n, 3, 3)), dz=np.zeros(n), alpha=np.zeros(cap), beta=np.zeros(cap), c1=np.zeros(cap), c2=np.zeros(cap), y=np.zeros(cap),
+                   x=np.zeros(3 * n))
+        if want_V:
+            out["V"] = np.zeros((3 * n, cap + 1), order="F")
+        for k, v in list(ins.items()) + list(out.items()):
+            setattr(q, k, v.ctypes.data_as(C.c_void_p))
+        _chk(lib().xm_ctx_cert_probe(self.h, C.byref(q)))
+        k = q.steps_dev
+        out.update(alpha=out["alpha"][:k].copy(), beta=out["beta"][:k].copy(), c1=out["c1"][:k].copy(), c2=out["c2"][:k].copy(), y=out["y"][:q.m_use].copy())
+        if want_V:
+            out["V"] = np.ascontiguousarray(out["V"][:, :k + 1])
+        out.update({f: getattr(q, f) for f in CERT_INTS if f != "product_kind"})
+        out.update(product_kind=PRODUCT_KINDS.get(q.product_kind, "?"), len=q.len, theta=q.theta, resid=q.resid, dual=np.array(q.dual[:]))
+        return out
 
     def outer_probe(self, o, lam, R, s, v=None, Hv=None, retract=False, model_recurrence=False, retraction=None, auto=False, model=0.0, partsM_fill=None,
                     ls=None, step=None):
