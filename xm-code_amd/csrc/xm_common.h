@@ -247,6 +247,46 @@ struct OuterStepArgs {
 };
 void launch_outer_step(int o, int polar, const OuterStepArgs &A, int grid, hipStream_t st);
 
+// The two-copy buffers of the truncated CG as iteration (or slot) parity `par` sees them (Context::tcg_parity: the one place that picks a copy).
+// A parity's partial sums are `world` chunks, one per rank, gathered in place; a chunk is
+//   [this rank's rows of the image of Hp (b_off doubles; multi-rank only) | 3 nA Hessian-epilogue partials | nB |r|^2 partials]
+struct TcgParity {
+    TcgScal *scal_cur, *scal_next;
+    double *ps_cur, *ps_next, *rs_cur, *rs_next;
+    size_t chunk, b_off;
+    double *pcur;         // gather base of this parity: what cg_step reads its sums from
+    double *parts;        // this rank's [3 nA | nB] inside it: the Hessian epilogue writes the first part
+    double *Bout;         // this rank's image rows inside it (nullptr: single rank)
+    double *partsB_out;   // this rank's |r|^2 partials in the OTHER parity: written by the step that ends this iteration
+};
+
+// Host-side arguments of tcg_init_kernel and cg_step_kernel: Context::tcg_init_args / cg_step_args build them for a solve, the launchers unpack
+// them into the kernels' positional parameters.
+struct TcgInitArgs {
+    int nloc;
+    const double *rgR, *rgs, *R, *s;   // the gradient the tCG starts from, the point
+    double *rR, *rs, *pR, *ps, *vR, *vs, *HvR, *Hvs;
+    double *Wloc, *Wpad;               // product input at the native pitch / at the 128-byte record pitch (either may be nullptr)
+    TcgScal *scal0;
+    double rr, delta;
+    unsigned long long *hstat;         // host-mapped progress word (nullptr: none), stamped with run number seq
+    int seq;
+    const SpecCtl *spec;               // start only if spec->go, with spec->rr / spec->delta (else leave scal0 dormant); nullptr: a regular start
+};
+struct CgStepArgs {
+    int nloc;
+    TcgParity v;                       // scal, ps, rs cur -> next; sums read at v.pcur, |r|^2 partials written to v.partsB_out
+    int nA, nB, world;                 // partial counts per rank; grid = nB
+    const double *HpR, *Hps, *R, *s;
+    double *pR, *vR, *vs, *HvR, *Hvs, *rR;   // HvR == nullptr: XM_FLAG_MODEL_RECURRENCE
+    double *Wloc, *Wpad;               // Wpad: single rank only
+    unsigned long long *hstat;
+    int64_t mat;
+    double *Afull, *Wfull;             // multi-rank: replicated image of the residual / the whole product input
+    int grouping;
+    PeerXchg xchg;
+};
+
 // ---- launchers implemented in xm_kernels.hip -------------------------------------------------------------------
 // Q*W products.  grid = ceil(nloc / kQwWaves).  Q rows are the local cameras' rows; W has `ld` rows (all cameras).
 void launch_qw_dense(int o, int epi, const double *Q, int64_t ld, const double *W, double alpha, const CamArgs &a,
@@ -309,15 +349,8 @@ void launch_dense_from_bsr(const int64_t *rowptr, const int32_t *colidx, const d
 // flat / per-camera kernels
 int flat_grid(int64_t elems);
 void launch_scale_rows(int o, int nloc, const double *R, const double *s, double *Wloc, hipStream_t st);
-void launch_tcg_init(int o, int nloc, const double *rgR, const double *rgs, const double *R, const double *s, double *rR,
-                     double *rs, double *pR, double *ps, double *vR, double *vs, double *HvR, double *Hvs, double *Wloc,
-                     TcgScal *scal0, double rr, double delta, unsigned long long *hstat, hipStream_t st, double *Wpad = nullptr, int seq = 0,
-                     const SpecCtl *spec = nullptr);   // spec: start only if spec->go, with spec->rr / spec->delta (else leave scal0 dormant)
-void launch_cg_step(int o, int nloc, const TcgScal *scal_cur, TcgScal *scal_next, const double *parts, int nA_loc, int nB_loc, int world,
-                    const double *HpR, const double *Hps, const double *R, const double *s, double *pR,
-                    const double *ps_cur, double *ps_next, double *vR, double *vs, double *HvR, double *Hvs, double *rR, const double *rs_cur,
-                    double *rs_next, double *Wloc, double *partsB_out, unsigned long long *hstat, int b_off, int64_t mat, double *Afull,
-                    double *Wfull, int grouping, const struct PeerXchg &xchg, hipStream_t st, double *Wpad = nullptr);   // Wpad: single-rank only
+void launch_tcg_init(int o, const TcgInitArgs &a, hipStream_t st);
+void launch_cg_step(int o, const CgStepArgs &a, hipStream_t st);
 // trust-region numbers of the iteration that ends (what the host holds when it enqueues this launch); spec_out: see SpecCtl (nullptr: none)
 struct OuterArgs { double loss, delta, delta_bar, gradtol; int shrink_count, last_iter; };
 void launch_outer_finalize(const double *partsA, int nA_loc, int world, const double *partsM, int nM, const TcgScal *scal, double *hres,

@@ -1033,7 +1033,7 @@ __global__ __launch_bounds__(256) void tcg_init_kernel(int nloc, const double *_
         const double g = rgR[i], gs = rgs[cam];
         rR[i] = g; pR[i] = -g; vR[i] = 0.0; HvR[i] = 0.0;
         const double wv = s[cam] * (-g) + (-gs) * R[i];
-        if (Wloc) Wloc[i] = wv;   // (nullptr: the products of this tCG read the padded copy only, Context::run_tcg)
+        if (Wloc) Wloc[i] = wv;   // (nullptr: the products of this tCG read the padded copy only, Context::tcg_init_args)
         if (Wpad) Wpad[(size_t)cam * 16 + (i - (int64_t)cam * (3 * OP))] = wv;   // copy at a 128-byte record pitch for the sliced-ELL gather (xm_sell.h)
         if (i % (3 * OP) == 0) { rs[cam] = gs; ps[cam] = -gs; vs[cam] = 0.0; Hvs[cam] = 0.0; }
     }
@@ -2798,22 +2798,18 @@ void launch_scale_rows(int o, int nloc, const double *R, const double *s, double
                                         nloc, R, s, Wloc));
     check_launch("scale_rows");
 }
-void launch_tcg_init(int o, int nloc, const double *rgR, const double *rgs, const double *R, const double *s, double *rR, double *rs,
-                     double *pR, double *ps, double *vR, double *vs, double *HvR, double *Hvs, double *Wloc, TcgScal *scal0,
-                     double rr, double delta, unsigned long long *hstat, hipStream_t st, double *Wpad, int seq, const SpecCtl *spec) {
-    XM_DISPATCH_O(o, hipLaunchKernelGGL((tcg_init_kernel<O_>), dim3(flat_grid((int64_t)nloc * 3 * pitch_of(O_))), dim3(256), 0, st,
-                                        nloc, rgR, rgs, R, s, rR, rs, pR, ps, vR, vs, HvR, Hvs, Wloc, scal0, rr, delta, hstat, Wpad, seq, spec));
+void launch_tcg_init(int o, const TcgInitArgs &a, hipStream_t st) {
+    XM_DISPATCH_O(o, hipLaunchKernelGGL((tcg_init_kernel<O_>), dim3(flat_grid((int64_t)a.nloc * 3 * pitch_of(O_))), dim3(256), 0, st,
+                                        a.nloc, a.rgR, a.rgs, a.R, a.s, a.rR, a.rs, a.pR, a.ps, a.vR, a.vs, a.HvR, a.Hvs, a.Wloc, a.scal0, a.rr, a.delta,
+                                        a.hstat, a.Wpad, a.seq, a.spec));
     check_launch("tcg_init");
 }
-void launch_cg_step(int o, int nloc, const TcgScal *scal_cur, TcgScal *scal_next, const double *parts, int nA_loc, int nB_loc, int world,
-                    const double *HpR, const double *Hps, const double *R, const double *s, double *pR,
-                    const double *ps_cur, double *ps_next, double *vR, double *vs, double *HvR, double *Hvs, double *rR, const double *rs_cur,
-                    double *rs_next, double *Wloc, double *partsB_out, unsigned long long *hstat, int b_off, int64_t mat, double *Afull,
-                    double *Wfull, int grouping, const PeerXchg &xchg, hipStream_t st, double *Wpad) {
-    // grid = nB_loc: one |r|^2 partial sum per workgroup (Context::tcg_blocks: capped when the launch waits for its peers inside the kernel)
-    XM_DISPATCH_O(o, hipLaunchKernelGGL((cg_step_kernel<O_>), dim3(nB_loc), dim3(256), 0, st, nloc,
-                                        scal_cur, scal_next, parts, nA_loc, nB_loc, world, HpR, Hps, R, s, pR, ps_cur, ps_next, vR,
-                                        vs, HvR, Hvs, rR, rs_cur, rs_next, Wloc, partsB_out, hstat, b_off, mat, Afull, Wfull, grouping, xchg, Wpad));
+void launch_cg_step(int o, const CgStepArgs &a, hipStream_t st) {
+    // grid = nB: one |r|^2 partial sum per workgroup (Context::tcg_blocks: capped when the launch waits for its peers inside the kernel)
+    XM_DISPATCH_O(o, hipLaunchKernelGGL((cg_step_kernel<O_>), dim3(a.nB), dim3(256), 0, st, a.nloc,
+                                        a.v.scal_cur, a.v.scal_next, a.v.pcur, a.nA, a.nB, a.world, a.HpR, a.Hps, a.R, a.s, a.pR, a.v.ps_cur, a.v.ps_next, a.vR,
+                                        a.vs, a.HvR, a.Hvs, a.rR, a.v.rs_cur, a.v.rs_next, a.Wloc, a.v.partsB_out, a.hstat, (int)a.v.b_off, a.mat, a.Afull,
+                                        a.Wfull, a.grouping, a.xchg, a.Wpad));
     check_launch("cg_step");
 }
 void launch_outer_finalize(const double *partsA, int nA_loc, int world, const double *partsM, int nM, const TcgScal *scal, double *hres,

@@ -287,9 +287,17 @@ private:
     bool overlap_applies() const;
     void eval_point(int state, const double *Rp, const double *sp, double &f, double &rr);
     double sum_parts(const double *dparts, int count);
-    int run_tcg(double rr, double delta, TcgScal &fin, int adopted = 0);   // adopted: iterations of THIS tCG already enqueued speculatively (enqueue_spec_tcg)
+    int run_tcg(double rr, double delta, int adopted = 0);   // adopted: iterations of THIS tCG already enqueued speculatively (enqueue_spec_tcg)
     int enqueue_spec_tcg();      // single GPU: tcg_init + the first iteration(s) of the next tCG from the CANDIDATE point, gated on the device (SpecCtl)
     void tcg_enqueue_iteration(int i, bool profile);   // one iteration = Hessian product (+ exchange) + cg_step
+    // What the solver's two forms AND the test exports (rtr_probe, outer_probe) launch the tCG's kernels with: a probe overrides single fields, never rebuilds.
+    TcgParity tcg_parity(int par) const;   // single rank on partsB_ | communicator with a lockstep gather | fused peer exchange on partsB_peer_
+    void cand_role(CamArgs &a, const PointState &P, const double *R, const double *s) const;   // CamArgs::cand: the gradient role of an EPI_AUTO product at (R, s)
+    CamArgs tcg_cam_args(const TcgParity &v, bool cand) const;   // product of a tCG slot: cam_args(cur_) + v (+ the candidate point's role)
+    void tcg_product(int epi, const CamArgs &a, int par, bool profile);   // sweep direction by parity, sampled HIP events, hess_launches_
+    TcgInitArgs tcg_init_args(double rr, double delta, const SpecCtl *spec) const;   // start of run tcg_seq_ from the gradient of ps_[cur_]
+    CgStepArgs cg_step_args(int i) const;
+    void probe_grad(bool aut, double &f, double &rr);   // first stage of both probes: cost / gradient at the uploaded point
     bool spec_applies() const;
     DevBuf<SpecCtl> spec_;
     unsigned int tcg_seq_ = 0;   // sequence number of the current truncated-CG run (TcgScal.seq, progress word)
@@ -304,6 +312,9 @@ private:
     bool device_outer_applies(int o) const;
     TrResult trust_region_device(int o, double &gradtol, double f, double rr, double delta, double delta_bar, double max_time);
     OuterStepArgs outer_step_args(int slot, bool model_rec, double delta_bar, double gradtol, unsigned int runid) const;
+    void progress_line(int k, int inner, double loss, double gradnorm, int endreason, int trstatus) const;   // the reference's line per outer iteration
+    // the end of either form: stop-reason message, totals, the result's counters (and the reference's gradtol /= 10 after stop reason 10)
+    TrResult close_trust_region(int stop_reason, double &gradtol, long long totalite, int k, double loss, std::chrono::steady_clock::time_point start);
     DevBuf<double> trace_dev_;           // device copy of the outer-iteration trace (kMaxOuter records)
     DevBuf<int> stop_req_;               // set by the host when its time limit has expired
     DevBuf<OuterScal> oscal_;            // trust-region state of the device-driven outer iteration, two parity copies next to scal_

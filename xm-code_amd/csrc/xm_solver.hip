@@ -837,40 +837,81 @@ void Context::finish_profile() {
 // ------------------------------------------------------------------------------------------------------------------
 // one tCG iteration on the stream: the Hessian product of iteration i, the lockstep all-gather when the exchange is not fused, cg_step
 void Context::tcg_enqueue_iteration(int i, bool profile) {
-    const int nA_loc = prod_grid(), nB_loc = tcg_blocks();
-    const int rank = comm_->rank;
-    const bool fused = xchg_.world > 1;
-    const bool lockstep = comm_->active() && !fused;
-    double *Wloc = wpad() ? nullptr : W_.p + (size_t)cam0_ * 3 * OP_;   // (see run_tcg)
-    const int par = i & 1;
+    const CgStepArgs S = cg_step_args(i);
+    tcg_product(EPI_HESS, tcg_cam_args(S.v, false), i & 1, profile);
+    if (comm_->active() && xchg_.world <= 1) comm_->allgather(S.v.pcur, S.v.chunk, st_);   // lockstep: the exchange is not fused into cg_step
+    launch_cg_step(o_, S, st_);
+}
+
+// tCG partial sums travel in ONE all-gather per iteration: chunk = [Hessian-epilogue partials of this iteration | |r|^2 partials the previous
+// cg_step left in this parity's buffer] and, with more than one rank, in front of them this rank's rows of the image of Hp (see cg_step_kernel):
+// the product input of the next iteration then follows from replicated data and needs no all-gather of its own.
+TcgParity Context::tcg_parity(int par) const {
+    const size_t nA = (size_t)prod_grid(), world = (size_t)comm_->world, rank = (size_t)comm_->rank;
+    TcgParity v;
+    v.scal_cur = scal_.p + par; v.scal_next = scal_.p + (par ^ 1);
+    v.ps_cur = par ? psB_.p : psA_.p; v.ps_next = par ? psA_.p : psB_.p;
+    v.rs_cur = par ? rsB_.p : rs_.p; v.rs_next = par ? rs_.p : rsB_.p;
+    v.b_off = comm_->active() ? (size_t)nloc_ * 3 * OP_ : 0;
+    v.chunk = v.b_off + 3 * nA + (size_t)tcg_blocks();
+    double *pB = xchg_.world > 1 ? partsB_peer_ : partsB_.p;   // fused peer exchange: the sums live in peer-addressable memory
+    v.pcur = pB + (size_t)par * v.chunk * world;
+    v.parts = v.pcur + rank * v.chunk + v.b_off;
+    v.Bout = comm_->active() ? v.pcur + rank * v.chunk : nullptr;
+    v.partsB_out = pB + (size_t)(par ^ 1) * v.chunk * world + rank * v.chunk + v.b_off + 3 * nA;
+    return v;
+}
+
+void Context::cand_role(CamArgs &a, const PointState &P, const double *R, const double *s) const {
+    a.cand = {R, s, P.G.p, P.egs.p, P.S0.p, P.rgR.p, P.rgs.p, partsA_.p};
+}
+
+CamArgs Context::tcg_cam_args(const TcgParity &v, bool cand) const {
     CamArgs a = cam_args(cur_);
-    a.scal = scal_.p + par;
-    a.ps = par ? psB_.p : psA_.p;
-    a.rs = par ? rsB_.p : rs_.p;
-    // tCG partial sums travel in ONE all-gather per iteration: chunk = [Hessian-epilogue partials of this iteration |
-    // |r|^2 partials the previous cg_step left in this parity's buffer]
-    // and, with more than one rank, in front of them this rank's rows of the image of Hp (see cg_step_kernel): the product
-    // input of the next iteration then follows from replicated data and needs no all-gather of its own.
-    const size_t mat = (size_t)nloc_ * 3 * OP_;
-    const size_t b_off = comm_->active() ? mat : 0;
-    const size_t chunk = b_off + (size_t)3 * nA_loc + nB_loc;
-    double *pB = fused ? partsB_peer_ : partsB_.p;
-    double *pcur = pB + (size_t)par * chunk * comm_->world, *pnext = pB + (size_t)(par ^ 1) * chunk * comm_->world;
-    a.partials = pcur + (size_t)rank * chunk + b_off;
-    a.Bout = comm_->active() ? pcur + (size_t)rank * chunk : nullptr;
+    a.scal = v.scal_cur; a.ps = v.ps_cur; a.rs = v.rs_cur;
+    a.partials = v.parts; a.Bout = v.Bout;
+    if (cand) cand_role(a, ps_[cur_ ^ 1], Rc_.p, sc_.p);
+    return a;
+}
+
+// Every product of a tCG slot.  Sampled by HIP events when `profile` (a launch that turns out an enqueued-ahead no-op is dropped by finish_profile()).
+void Context::tcg_product(int epi, const CamArgs &a, int par, bool profile) {
     const bool timed = profile && (hess_launches_ % kProfileStride == 0) && ev_used_ < ev_pool_.size();
     if (timed) XM_HIP_CHECK(hipEventRecord(ev_pool_[ev_used_].first, st_));
-    const bool model_rec = opt_ && (opt_->flags & XM_FLAG_MODEL_RECURRENCE);
     sym_rev_ = par;        // consecutive tCG iterations sweep the symmetric matrix in opposite directions (launch_qw_sym)
-    product(EPI_HESS, o_, 2.0, a);
+    product(epi, o_, 2.0, a);
     sym_rev_ = 1;          // every other product (gradient, cost): bottom-up, the direction iteration 0 of a tCG does not use
     if (timed) { XM_HIP_CHECK(hipEventRecord(ev_pool_[ev_used_].second, st_)); ev_used_++; }
     hess_launches_++;
-    if (lockstep) comm_->allgather(pcur, chunk, st_);
-    launch_cg_step(o_, nloc_, scal_.p + par, scal_.p + (par ^ 1), pcur, nA_loc, nB_loc, comm_->world, HpR_.p, Hps_.p, R_.p,
-                   s_.p, pR_.p, par ? psB_.p : psA_.p, par ? psA_.p : psB_.p, vR_.p, vs_.p, model_rec ? nullptr : HvR_.p, model_rec ? nullptr : Hvs_.p, rR_.p,
-                   par ? rsB_.p : rs_.p, par ? rs_.p : rsB_.p, Wloc, pnext + (size_t)rank * chunk + b_off + 3 * nA_loc, hstat_dev_,
-                   (int)b_off, (int64_t)mat, comm_->active() ? Afull_.p : nullptr, W_.p, grouping_, xchg_, st_, wpad());
+}
+
+// With the padded copy on (single rank, sliced ELL) nothing reads the native-pitch product input inside the tCG: the main launch gathers from
+// the copy and the second launch rebuilds the diagonal term from its own operands -- the kernels skip those 7.2 MB of stores per iteration at
+// 100 k cameras (Wloc == nullptr).
+TcgInitArgs Context::tcg_init_args(double rr, double delta, const SpecCtl *spec) const {
+    const PointState &P = ps_[cur_];
+    TcgInitArgs a;
+    a.nloc = nloc_;
+    a.rgR = P.rgR.p; a.rgs = P.rgs.p; a.R = R_.p; a.s = s_.p;
+    a.rR = rR_.p; a.rs = rs_.p; a.pR = pR_.p; a.ps = psA_.p; a.vR = vR_.p; a.vs = vs_.p; a.HvR = HvR_.p; a.Hvs = Hvs_.p;
+    a.Wloc = wpad() ? nullptr : W_.p + (size_t)cam0_ * 3 * OP_; a.Wpad = wpad();
+    a.scal0 = scal_.p; a.rr = rr; a.delta = delta;
+    a.hstat = hstat_dev_; a.seq = (int)tcg_seq_; a.spec = spec;
+    return a;
+}
+
+CgStepArgs Context::cg_step_args(int i) const {
+    const bool model_rec = opt_ && (opt_->flags & XM_FLAG_MODEL_RECURRENCE);
+    CgStepArgs a;
+    a.nloc = nloc_; a.v = tcg_parity(i & 1);
+    a.nA = prod_grid(); a.nB = tcg_blocks(); a.world = comm_->world;
+    a.HpR = HpR_.p; a.Hps = Hps_.p; a.R = R_.p; a.s = s_.p;
+    a.pR = pR_.p; a.vR = vR_.p; a.vs = vs_.p; a.HvR = model_rec ? nullptr : HvR_.p; a.Hvs = model_rec ? nullptr : Hvs_.p; a.rR = rR_.p;
+    a.Wloc = wpad() ? nullptr : W_.p + (size_t)cam0_ * 3 * OP_; a.Wpad = wpad();
+    a.hstat = hstat_dev_; a.mat = (int64_t)nloc_ * 3 * OP_;
+    a.Afull = comm_->active() ? Afull_.p : nullptr; a.Wfull = W_.p;
+    a.grouping = grouping_; a.xchg = xchg_;
+    return a;
 }
 
 // May the start of the next truncated CG be enqueued behind outer_finalize_kernel before the host knows how the outer iteration ended?
@@ -886,11 +927,8 @@ int Context::enqueue_spec_tcg() {
     std::swap(R_.p, Rc_.p);
     std::swap(s_.p, sc_.p);
     cur_ ^= 1;
-    const PointState &P = ps_[cur_];
-    double *Wloc = wpad() ? nullptr : W_.p + (size_t)cam0_ * 3 * OP_;
     ++tcg_seq_;
-    launch_tcg_init(o_, nloc_, P.rgR.p, P.rgs.p, R_.p, s_.p, rR_.p, rs_.p, pR_.p, psA_.p, vR_.p, vs_.p, HvR_.p, Hvs_.p, Wloc,
-                    scal_.p, 0.0, 0.0, hstat_dev_, st_, wpad(), (int)tcg_seq_, spec_.p);
+    launch_tcg_init(o_, tcg_init_args(0.0, 0.0, spec_.p), st_);
     // ONE iteration behind tcg_init, and a run-ahead of two in run_tcg: measured against 2 / 3 on one box at Final-13682 size in block CSR
     // (profiles/r05_ab_rome.txt: 27.8 against 28.8 ms per solve; fewer launches that turn out to be no-ops when the tCG ends after ~5
     // iterations) and equal at Venice size
@@ -902,19 +940,13 @@ int Context::enqueue_spec_tcg() {
     return n_spec;
 }
 
-int Context::run_tcg(double rr, double delta, TcgScal &fin, int adopted) {
+int Context::run_tcg(double rr, double delta, int adopted) {
     const bool stepped = (opt_->flags & XM_FLAG_HOST_STEPPED) != 0;
     const bool profile = (opt_->flags & XM_FLAG_PROFILE_QW) != 0;
-    // with the padded copy on (single rank, sliced ELL) nothing reads the native-pitch product input inside the tCG: the main launch
-    // gathers from the copy and the second launch rebuilds the diagonal term from its own operands -- the kernels skip those 7.2 MB of
-    // stores per iteration at 100 k cameras
-    double *Wloc = wpad() ? nullptr : W_.p + (size_t)cam0_ * 3 * OP_;
-    const PointState &P = ps_[cur_];
     if (comm_->active()) comm_->note("tcg_start", rr, delta);
     if (adopted == 0) {
         ++tcg_seq_;
-        launch_tcg_init(o_, nloc_, P.rgR.p, P.rgs.p, R_.p, s_.p, rR_.p, rs_.p, pR_.p, psA_.p, vR_.p, vs_.p, HvR_.p, Hvs_.p, Wloc,
-                        scal_.p, rr, delta, hstat_dev_, st_, wpad(), (int)tcg_seq_);
+        launch_tcg_init(o_, tcg_init_args(rr, delta, nullptr), st_);
         gather_W();
     }
     // Iterations in flight ahead of the last one seen finished; the excess become no-op launches.  With a communicator the
@@ -979,7 +1011,6 @@ int Context::run_tcg(double rr, double delta, TcgScal &fin, int adopted) {
         const int T = (fin_status == 6) ? fin_iter - 1 : fin_iter;   // iteration in which the tCG ended
         while (it < std::min(kMaxInner, T + 2)) enqueue(it++);      // no-ops, but the same collectives on every rank
     }
-    (void)fin;
     return it;  // the final scalar block is scal_[it & 1]; the caller fetches it together with the other results
 }
 
@@ -1049,28 +1080,19 @@ TrResult Context::trust_region(int o, double &gradtol, double linesearch_step, c
     const auto start = clk::now();
     for (k = 0; k < kMaxOuter; ++k) {
         const double gradnorm = std::sqrt(rr);
-        if (verbose_) {
-            static const char *trn[] = {"", "TR- ", "TR+ ", "REJ ", "TR "};
-            if (k > 0) log("%s", trn[trstatus]);
-            log("%d   %d   %1.3e   %1.3e", k, inner_print, loss, gradnorm);
-            if (k > 0) {
-                const char *er = endreason == 1 ? "nagative curvature" : endreason == 2 ? "exceed trust region"
-                               : endreason == 3 ? "reached norm tolerance" : endreason == 5 ? "numerical issue" : "max iteration";
-                log("   %s\n", er);
-            } else log("\n");
-        }
+        progress_line(k, inner_print, loss, gradnorm, endreason, trstatus);
         if (opt_->trace && res_->trace_len < opt_->trace_cap) {
             double *tr = opt_->trace + (size_t)res_->trace_len * 6;
             tr[0] = loss; tr[1] = gradnorm; tr[2] = inner_print; tr[3] = endreason; tr[4] = trstatus; tr[5] = delta;
             res_->trace_len++;
         }
-        if (endreason == 5) { stop_reason = 5; log("Terminate because of rdotr touched machine precise\n"); break; }
-        if (gradnorm < gradtol) { log("Terminate because of small gradient norm\n"); gradtol /= 10; stop_reason = 10; break; }
-        if (agree_any((double)(long long)secs_since(start) > max_time)) { log("Terminate because of time limit\n"); stop_reason = 11; break; }
+        if (endreason == 5) { stop_reason = 5; break; }   // (close_trust_region() prints why)
+        if (gradnorm < gradtol) { stop_reason = 10; break; }
+        if (agree_any((double)(long long)secs_since(start) > max_time)) { stop_reason = 11; break; }
         endreason = 6; trstatus = 4;
 
         TcgScal fin;
-        const int enq = run_tcg(rr, delta, fin, adopted);
+        const int enq = run_tcg(rr, delta, adopted);
         adopted = 0;
 
         // model decrease, retraction and the candidate's cost/gradient are enqueued right behind the tCG and fetched with
@@ -1118,7 +1140,7 @@ TrResult Context::trust_region(int o, double &gradtol, double linesearch_step, c
         inner_print = fin.iter + 1;
         totalite += fin.iter + 1;
         if (opt_->flags & XM_FLAG_PROFILE_QW) drain_events();
-        if (loss_qu >= 0) { log("error! loss_qu is larger than 0\n"); stop_reason = 12; break; }
+        if (loss_qu >= 0) { stop_reason = 12; break; }
         const double rou = (f_new - loss) / loss_qu;  // trustregion.h:680-701
         if (rou < 0.25) { delta *= 0.25; trstatus = 1; shrink_count++; }
         else if (rou > 0.75 && endreason <= 2) { delta = std::min(delta * 2, delta_bar); trstatus = 2; shrink_count = 0; }
@@ -1127,7 +1149,7 @@ TrResult Context::trust_region(int o, double &gradtol, double linesearch_step, c
         if (shrink_count > 3) {
             delta *= 1e-3; shrink_count = 0;
             log("delta shrinked to %1.3e\n", delta);
-            if (delta < 1e-20) { log("delta is too small, BM stopped!\n"); stop_delta = true; }
+            if (delta < 1e-20) stop_delta = true;
         }
         const bool reject = (f_new > loss || rou < 0.1);  // trustregion.h:702
         if (stop_delta || !reject) {
@@ -1148,6 +1170,25 @@ TrResult Context::trust_region(int o, double &gradtol, double linesearch_step, c
         // padded copy), which every later user re-creates before reading (certificate and line search rebuild W; tcg_seq_ guards the progress word).
         if (n_spec > 0 && adopted != n_spec && res_) res_->qw_products -= n_spec;
     }
+    return close_trust_region(stop_reason, gradtol, totalite, k, loss, start);
+}
+
+// XM_FLAG_VERBOSE: the reference's progress line of outer iteration k (trustregion.h:504-525)
+void Context::progress_line(int k, int inner, double loss, double gradnorm, int endreason, int trstatus) const {
+    static const char *trn[] = {"", "TR- ", "TR+ ", "REJ ", "TR "};
+    if (k > 0) log("%s", trn[(trstatus >= 0 && trstatus <= 4) ? trstatus : 0]);
+    log("%d   %d   %1.3e   %1.3e", k, inner, loss, gradnorm);
+    if (k > 0) log("   %s\n", endreason == 1 ? "nagative curvature" : endreason == 2 ? "exceed trust region" : endreason == 3 ? "reached norm tolerance"
+                              : endreason == 5 ? "numerical issue" : "max iteration");
+    else log("\n");
+}
+
+TrResult Context::close_trust_region(int stop_reason, double &gradtol, long long totalite, int k, double loss, clk::time_point start) {
+    if (stop_reason == 5) log("Terminate because of rdotr touched machine precise\n");
+    else if (stop_reason == 10) { log("Terminate because of small gradient norm\n"); gradtol /= 10; }
+    else if (stop_reason == 11) log("Terminate because of time limit\n");
+    else if (stop_reason == 12) log("error! loss_qu is larger than 0\n");
+    else if (stop_reason == 13) log("delta is too small, BM stopped!\n");
     log("\nTotal iteration:     %lld\n", totalite);
     const double secs = secs_since(start);
     log("Time taken by function1: %lld ms\n", (long long)(secs * 1e3));
@@ -1155,9 +1196,8 @@ TrResult Context::trust_region(int o, double &gradtol, double linesearch_step, c
     res_->outer_iters += k;
     res_->tr_seconds += secs;
     res_->last_stop_reason = stop_reason;
-    out.primal = loss;
-    out.outer_iters = k;
-    out.stop_reason = stop_reason;
+    TrResult out;
+    out.primal = loss; out.outer_iters = k; out.stop_reason = stop_reason;
     return out;
 }
 
@@ -1184,27 +1224,25 @@ bool Context::device_outer_applies(int o) const {
 
 // The step launch's arguments for launch pair `slot` of run `runid` (trust_region_device() and the test export outer_probe() take them from here).
 OuterStepArgs Context::outer_step_args(int slot, bool model_rec, double delta_bar, double gradtol, unsigned int runid) const {
-    const int nA = prod_grid(), nB = tcg_blocks(), nM = retract_grid(nloc_);
-    const size_t chunk = (size_t)3 * nA + nB;
     const PointState &Pc = ps_[cur_], &Pn = ps_[cur_ ^ 1];
     const int par = slot & 1;
+    const TcgParity v = tcg_parity(par);
     OuterStepArgs A;
     std::memset(&A, 0, sizeof(A));
     A.nloc = nloc_; A.cam0 = cam0_;
-    A.scal_cur = scal_.p + par; A.scal_next = scal_.p + (par ^ 1);
+    A.scal_cur = v.scal_cur; A.scal_next = v.scal_next;
     A.os_cur = oscal_.p + par; A.os_next = oscal_.p + (par ^ 1);
-    A.parts = partsB_.p + (size_t)par * chunk;
-    A.partsB_out = partsB_.p + (size_t)(par ^ 1) * chunk + (size_t)3 * nA;
-    A.nA = nA; A.nB = nB;
+    A.parts = v.parts; A.partsB_out = v.partsB_out;
+    A.nA = prod_grid(); A.nB = tcg_blocks();
     A.HpR = HpR_.p; A.Hps = Hps_.p;
     A.R = R_.p; A.s = s_.p; A.Rc = Rc_.p; A.sc = sc_.p;
-    A.pR = pR_.p; A.ps_cur = par ? psB_.p : psA_.p; A.ps_next = par ? psA_.p : psB_.p;
+    A.pR = pR_.p; A.ps_cur = v.ps_cur; A.ps_next = v.ps_next;
     A.vR = vR_.p; A.vs = vs_.p; A.HvR = model_rec ? nullptr : HvR_.p; A.Hvs = model_rec ? nullptr : Hvs_.p; A.rR = rR_.p;
-    A.rs_cur = par ? rsB_.p : rs_.p; A.rs_next = par ? rs_.p : rsB_.p;
+    A.rs_cur = v.rs_cur; A.rs_next = v.rs_next;
     A.Wloc = W_.p + (size_t)cam0_ * 3 * OP_; A.Wpad = nullptr;
     A.cur = {Pc.G.p, Pc.egs.p, Pc.S0.p, Pc.rgR.p, Pc.rgs.p};
     A.cand = {Pn.G.p, Pn.egs.p, Pn.S0.p, Pn.rgR.p, Pn.rgs.p};
-    A.partsA = partsA_.p; A.partsM = partsM_.p; A.nM = nM;
+    A.partsA = partsA_.p; A.partsM = partsM_.p; A.nM = retract_grid(nloc_);
     A.delta_bar = delta_bar; A.gradtol = gradtol; A.max_outer = kMaxOuter;
     A.trace = trace_dev_.p; A.trace_cap = kMaxOuter;
     A.stop_req = stop_req_.p;
@@ -1214,35 +1252,21 @@ OuterStepArgs Context::outer_step_args(int slot, bool model_rec, double delta_ba
 }
 
 TrResult Context::trust_region_device(int o, double &gradtol, double f, double rr, double delta, double delta_bar, double max_time) {
-    TrResult out;
     const auto start = clk::now();
     const bool profile = (opt_->flags & XM_FLAG_PROFILE_QW) != 0;
     const bool model_rec = (opt_->flags & XM_FLAG_MODEL_RECURRENCE) != 0;
-    const int nA = prod_grid(), nB = tcg_blocks();
+    const int nB = tcg_blocks();
     double loss = f;
     int stop_reason = 14, k = 0;
     long long totalite = 0;
-    int trace0 = res_->trace_len;   // the trace of this trust region starts here (the staircase appends stage after stage)
     if (opt_->trace && res_->trace_len < opt_->trace_cap) {
         double *tr = opt_->trace + (size_t)res_->trace_len * 6;
         tr[0] = loss; tr[1] = std::sqrt(rr); tr[2] = 1; tr[3] = 6; tr[4] = 4; tr[5] = delta;
         res_->trace_len++;
     }
-    // XM_FLAG_VERBOSE: the reference's progress lines (trustregion.h:504-525) are printed from the trace records -- the same text, but a
-    // stage's lines appear together when its trust region has ended instead of one by one
-    auto progress_line = [&](int kk, const double *rec, double delta_prev) {
-        static const char *trn[] = {"", "TR- ", "TR+ ", "REJ ", "TR "};
-        const int er = (int)rec[3], ts = (int)rec[4];
-        if (kk > 0 && rec[5] < delta_prev * 0.25 * 0.5) log("delta shrinked to %1.3e\n", rec[5]);   // (the 1e-3 cut after four shrinks in a row)
-        if (kk > 0) log("%s", trn[(ts >= 0 && ts <= 4) ? ts : 0]);
-        log("%d   %d   %1.3e   %1.3e", kk, (int)rec[2], rec[0], rec[1]);
-        if (kk > 0) log("   %s\n", er == 1 ? "nagative curvature" : er == 2 ? "exceed trust region" : er == 3 ? "reached norm tolerance" : er == 5 ? "numerical issue" : "max iteration");
-        else log("\n");
-    };
-    {
-        const double rec0[6] = {loss, std::sqrt(rr), 1, 6, 4, delta};
-        progress_line(0, rec0, delta);
-    }
+    // XM_FLAG_VERBOSE: the reference's progress lines are printed from the trace records -- the same text, but a stage's lines appear together
+    // when its trust region has ended instead of one by one
+    progress_line(0, 1, loss, std::sqrt(rr), 6, 4);
     bool run = true;
     if (std::sqrt(rr) < gradtol) { stop_reason = 10; run = false; }
     else if ((double)(long long)secs_since(start) > max_time) { stop_reason = 11; run = false; }
@@ -1263,29 +1287,12 @@ TrResult Context::trust_region_device(int o, double &gradtol, double f, double r
         const unsigned int runid = ++outer_run_;
         volatile unsigned long long *hp = hstat_ + 24;
         *hp = 0;
-        const size_t chunk = (size_t)3 * nA + nB;
-        const PointState &Pn = ps_[cur_ ^ 1];
         auto step_args = [&](int slot) { return outer_step_args(slot, model_rec, delta_bar, gradtol, runid); };
         const int polar = retraction_ == XM_RETRACT_POLAR ? 1 : 0;
         auto enqueue_slot = [&](int slot) {
-            const int par = slot & 1;
-            CamArgs a = cam_args(cur_);
-            a.scal = scal_.p + par;
-            a.ps = par ? psB_.p : psA_.p;
-            a.rs = par ? rsB_.p : rs_.p;
-            a.partials = partsB_.p + (size_t)par * chunk;
-            a.cand.R = Rc_.p; a.cand.s = sc_.p;
-            a.cand.G = Pn.G.p; a.cand.egs = Pn.egs.p; a.cand.S0 = Pn.S0.p; a.cand.rgR = Pn.rgR.p; a.cand.rgs = Pn.rgs.p;
-            a.cand.partials = partsA_.p;
             // sampled like the host-driven loop's Hessian launches; a pair in the gradient role moves the same bytes, a drained pair after the
             // end is dropped by finish_profile() like a run-ahead no-op
-            const bool timed = profile && (hess_launches_ % kProfileStride == 0) && ev_used_ < ev_pool_.size();
-            if (timed) XM_HIP_CHECK(hipEventRecord(ev_pool_[ev_used_].first, st_));
-            sym_rev_ = par;
-            product(EPI_AUTO, o_, 2.0, a);
-            sym_rev_ = 1;
-            if (timed) { XM_HIP_CHECK(hipEventRecord(ev_pool_[ev_used_].second, st_)); ev_used_++; }
-            hess_launches_++;
+            tcg_product(EPI_AUTO, tcg_cam_args(tcg_parity(slot & 1), true), slot & 1, profile);
             launch_outer_step(o_, polar, step_args(slot), nB, st_);
         };
         launch_outer_step(o_, polar, step_args(-1), nB, st_);
@@ -1339,30 +1346,18 @@ TrResult Context::trust_region_device(int o, double &gradtol, double f, double r
             std::vector<double> recs((size_t)last_rec * 6);
             to_host(recs.data(), trace_dev_.p + 6, recs.size() * sizeof(double));
             double dprev = delta;
-            for (int kk = 1; kk <= last_rec; ++kk) { progress_line(kk, &recs[(size_t)(kk - 1) * 6], dprev); dprev = recs[(size_t)(kk - 1) * 6 + 5]; }
+            for (int kk = 1; kk <= last_rec; ++kk) {
+                const double *rec = &recs[(size_t)(kk - 1) * 6];
+                if (rec[5] < dprev * 0.25 * 0.5) log("delta shrinked to %1.3e\n", rec[5]);   // (the 1e-3 cut after four shrinks in a row)
+                progress_line(kk, (int)rec[2], rec[0], rec[1], (int)rec[3], (int)rec[4]);
+                dprev = rec[5];
+            }
         }
         if (profile) drain_events();
         res_->qw_products -= (slots_enq - slots_live);   // pairs drained after the end were no products
     }
-    (void)trace0;
-    if (stop_reason == 5) log("Terminate because of rdotr touched machine precise\n");
-    else if (stop_reason == 10) log("Terminate because of small gradient norm\n");
-    else if (stop_reason == 11) log("Terminate because of time limit\n");
-    else if (stop_reason == 12) log("error! loss_qu is larger than 0\n");
-    else if (stop_reason == 13) log("delta is too small, BM stopped!\n");
-    log("\nTotal iteration:     %lld\n", totalite);
-    log("Time taken by function1: %lld ms\n", (long long)(secs_since(start) * 1e3));
-    if (stop_reason == 10) gradtol /= 10;
-    const double secs = secs_since(start);
     res_->outer_on_device++;
-    res_->tcg_iters += totalite;
-    res_->outer_iters += k;
-    res_->tr_seconds += secs;
-    res_->last_stop_reason = stop_reason;
-    out.primal = loss;
-    out.outer_iters = k;
-    out.stop_reason = stop_reason;
-    return out;
+    return close_trust_region(stop_reason, gradtol, totalite, k, loss, start);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1732,6 +1727,23 @@ void Context::cert_probe(xm_cert_probe_t &q) {
     XM_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
+// First stage of rtr_probe() and outer_probe(): cost and gradient at the uploaded point, by trust_region()'s eval_point or (aut) by the role-switching
+// launch in its candidate role: trust_region_device()'s enqueue_slot with the candidate's buffers = this point's
+void Context::probe_grad(bool aut, double &f, double &rr) {
+    launch_scale_rows(o_, nloc_, R_.p, s_.p, W_.p + (size_t)cam0_ * 3 * OP_, st_);
+    if (!aut) return eval_point(cur_, R_.p, s_.p, f, rr);
+    TcgScal sc;
+    std::memset(&sc, 0, sizeof(sc));
+    sc.phase = PH_CAND;
+    to_dev(scal_.p, &sc, sizeof(sc));
+    CamArgs a = tcg_cam_args(tcg_parity(0), false);
+    cand_role(a, ps_[cur_], R_.p, s_.p);
+    product(EPI_AUTO, o_, 2.0, a);   // (swept as a first cost / gradient, not by slot parity)
+    launch_outer_finalize(partsA_.p, prod_grid(), 1, partsM_.p, 0, scal_.p, reinterpret_cast<double *>(hstat_dev_) + 8, ++outer_seq_, 0, st_);
+    volatile double *hres = wait_outer_result();
+    f = hres[0]; rr = hres[1];
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // The trust region's kernels stage by stage (test export xm_ctx_rtr_probe, include/xm_amd.h): the context's own setup for rank o, cam_args(),
 // product() and the launchers with the grids and arguments of trust_region() / tcg_enqueue_iteration() / trust_region_device() / certificate().
@@ -1799,33 +1811,16 @@ void Context::rtr_probe(xm_rtr_probe_t &q) {
 
     // ---- grad: trust_region()'s first cost / gradient
     upload_point(std::vector<double>(q.R, q.R + m3 * (size_t)o), o, std::vector<double>(q.s, q.s + n));
-    launch_scale_rows(o, nloc_, R_.p, s_.p, Wloc, st_);
     double f = 0, rr = 0;
-    if (!aut) {
-        eval_point(cur_, R_.p, s_.p, f, rr);
-    } else {   // the role-switching launch in its candidate role: trust_region_device()'s enqueue_slot with the candidate's buffers = this point's
-        TcgScal sc;
-        std::memset(&sc, 0, sizeof(sc));
-        sc.phase = PH_CAND;
-        to_dev(scal_.p, &sc, sizeof(sc));
-        CamArgs a = cam_args(cur_);
-        a.scal = scal_.p;
-        a.partials = partsB_.p;
-        a.cand.R = R_.p; a.cand.s = s_.p;
-        a.cand.G = P.G.p; a.cand.egs = P.egs.p; a.cand.S0 = P.S0.p; a.cand.rgR = P.rgR.p; a.cand.rgs = P.rgs.p;
-        a.cand.partials = partsA_.p;
-        product(EPI_AUTO, o_, 2.0, a);
-        launch_outer_finalize(partsA_.p, nA, 1, partsM_.p, 0, scal_.p, hres_dev, ++outer_seq_, 0, st_);
-        volatile double *hres = wait_outer_result();
-        f = hres[0]; rr = hres[1];
-    }
+    probe_grad(aut, f, rr);
     q.f = f; q.rr = rr;
     down_mat(q.G, P.G.p); down_vec(q.egs, P.egs.p); down_vec(q.S0, P.S0.p, 9); down_mat(q.rgR, P.rgR.p); down_vec(q.rgs, P.rgs.p);
 
     // ---- tcg_init: run_tcg()'s start from the gradient state
     if (want_init) {
-        launch_tcg_init(o, nloc_, P.rgR.p, P.rgs.p, R_.p, s_.p, rR_.p, rs_.p, pR_.p, psA_.p, vR_.p, vs_.p, HvR_.p, Hvs_.p, Wtcg, scal_.p, rr, q.scal_in.delta,
-                        nullptr, st_, wpad(), 0);
+        TcgInitArgs I = tcg_init_args(rr, q.scal_in.delta, nullptr);
+        I.hstat = nullptr; I.seq = 0;   // no host progress word (nor a run number for it)
+        launch_tcg_init(o, I, st_);
         down_mat(q.init_rR, rR_.p); down_vec(q.init_rs, rs_.p); down_mat(q.init_pR, pR_.p); down_vec(q.init_ps, psA_.p);
         down_mat(q.init_vR, vR_.p); down_vec(q.init_vs, vs_.p); down_mat(q.init_HvR, HvR_.p); down_vec(q.init_Hvs, Hvs_.p);
         if (Wtcg) down_mat(q.init_W, Wloc);
@@ -1837,15 +1832,18 @@ void Context::rtr_probe(xm_rtr_probe_t &q) {
 
     // ---- hess: tcg_enqueue_iteration()'s product (trust_region_device()'s in the tCG role)
     if (want_hess) {
-        const int par = want_step ? (q.scal_in.iter & 1) : 0;
-        double *ps_cur = par ? psB_.p : psA_.p, *ps_next = par ? psA_.p : psB_.p, *rs_cur = par ? rsB_.p : rs_.p, *rs_next = par ? rs_.p : rsB_.p;
+        const int iter = want_step ? q.scal_in.iter : 0, par = iter & 1;
+        const TcgParity v = tcg_parity(par);
         // the product input W = s.*pR + ps.*R, and its padded copy where the context keeps one, by the kernel that writes them in a solve: the tCG's
         // start from "rg" = -p (the anchor's scale part is 0 in every direction a solve forms)
         up_mat(D_.p, q.pR, -1.0);
         up_vec(sc_.p, q.ps, -1.0, true);
-        launch_tcg_init(o, nloc_, D_.p, sc_.p, R_.p, s_.p, rR_.p, rs_.p, pR_.p, psA_.p, vR_.p, vs_.p, HvR_.p, Hvs_.p, Wtcg, scal_.p, 0.0, 0.0, nullptr, st_, wpad(), 0);
-        up_mat(pR_.p, q.pR, 1.0); up_vec(ps_cur, q.ps, 1.0, false);   // the vectors as given: what they hold at the anchor must not get through
-        up_mat(rR_.p, q.rR, 1.0); up_vec(rs_cur, q.rs, 1.0, false);
+        TcgInitArgs I = tcg_init_args(0.0, 0.0, nullptr);
+        I.rgR = D_.p; I.rgs = sc_.p;    // "rg" = -p
+        I.hstat = nullptr; I.seq = 0;   // no host progress word (nor a run number for it)
+        launch_tcg_init(o, I, st_);
+        up_mat(pR_.p, q.pR, 1.0); up_vec(v.ps_cur, q.ps, 1.0, false);   // the vectors as given: what they hold at the anchor must not get through
+        up_mat(rR_.p, q.rR, 1.0); up_vec(v.rs_cur, q.rs, 1.0, false);
         TcgScal sc;
         std::memset(&sc, 0, sizeof(sc));
         if (want_step) {
@@ -1853,25 +1851,10 @@ void Context::rtr_probe(xm_rtr_probe_t &q) {
             sc.model = q.scal_in.model; sc.iter = q.scal_in.iter;
         }
         sc.phase = PH_TCG;
-        to_dev(scal_.p + par, &sc, sizeof(sc));
-        const size_t chunk = (size_t)3 * nA + nB;
-        double *pcur = partsB_.p + (size_t)par * chunk, *pnext = partsB_.p + (size_t)(par ^ 1) * chunk;
-        CamArgs a = cam_args(cur_);
-        a.scal = scal_.p + par;
-        a.ps = ps_cur;
-        a.rs = rs_cur;
-        a.partials = pcur;
-        if (aut) {
-            const PointState &Pn = ps_[cur_ ^ 1];
-            a.cand.R = Rc_.p; a.cand.s = sc_.p;
-            a.cand.G = Pn.G.p; a.cand.egs = Pn.egs.p; a.cand.S0 = Pn.S0.p; a.cand.rgR = Pn.rgR.p; a.cand.rgs = Pn.rgs.p;
-            a.cand.partials = partsA_.p;
-        }
-        sym_rev_ = par;
-        product(aut ? EPI_AUTO : EPI_HESS, o_, 2.0, a);
-        sym_rev_ = 1;
+        to_dev(v.scal_cur, &sc, sizeof(sc));
+        tcg_product(aut ? EPI_AUTO : EPI_HESS, tcg_cam_args(v, aut), par, false);
         // the three sums by the summation tree of cg_step_kernel (sum_partials256: the same tree in every kernel that adds partial sums)
-        launch_outer_finalize(pcur, nA, 1, pcur + (size_t)2 * nA, nA, scal_.p + par, hres_dev, ++outer_seq_, 0, st_);
+        launch_outer_finalize(v.parts, nA, 1, v.parts + (size_t)2 * nA, nA, v.scal_cur, hres_dev, ++outer_seq_, 0, st_);
         volatile double *hres = wait_outer_result();
         q.pHp = hres[0]; q.rHp = hres[1]; q.HpHp = hres[2];
         down_mat(q.HpR, HpR_.p); down_vec(q.Hps, Hps_.p);
@@ -1880,24 +1863,26 @@ void Context::rtr_probe(xm_rtr_probe_t &q) {
         if (want_step) {
             up_mat(vR_.p, q.vR, 1.0); up_vec(vs_.p, q.vs, 1.0, false);
             if (!model_rec) { up_mat(HvR_.p, q.HvR, 1.0); up_vec(Hvs_.p, q.Hvs, 1.0, false); }
-            up_vec(ps_next, q.ps, 1.0, false); up_vec(rs_next, q.rs, 1.0, false);   // a branch that leaves them alone returns the input
-            if (q.scal_in.iter > 0) to_dev(pcur + (size_t)3 * nA, q.partsB_in, (size_t)nB * sizeof(double));
-            XM_HIP_CHECK(hipMemsetAsync(pnext + (size_t)3 * nA, 0, (size_t)nB * sizeof(double), st_));
-            launch_cg_step(o_, nloc_, scal_.p + par, scal_.p + (par ^ 1), pcur, nA, nB, 1, HpR_.p, Hps_.p, R_.p, s_.p, pR_.p, ps_cur, ps_next, vR_.p, vs_.p,
-                           model_rec ? nullptr : HvR_.p, model_rec ? nullptr : Hvs_.p, rR_.p, rs_cur, rs_next, Wtcg, pnext + (size_t)3 * nA, nullptr, 0,
-                           (int64_t)mat, nullptr, W_.p, 0, PeerXchg(), st_, wpad());
-            launch_outer_finalize(partsA_.p, 0, 1, pnext + (size_t)3 * nA, nB, scal_.p + (par ^ 1), hres_dev, ++outer_seq_, 0, st_);
+            up_vec(v.ps_next, q.ps, 1.0, false); up_vec(v.rs_next, q.rs, 1.0, false);   // a branch that leaves them alone returns the input
+            if (q.scal_in.iter > 0) to_dev(v.parts + (size_t)3 * nA, q.partsB_in, (size_t)nB * sizeof(double));
+            XM_HIP_CHECK(hipMemsetAsync(v.partsB_out, 0, (size_t)nB * sizeof(double), st_));
+            CgStepArgs S = cg_step_args(iter);
+            S.hstat = nullptr;       // no host progress word
+            S.xchg = PeerXchg();     // no peer exchange
+            S.grouping = 0;          // grouping 0
+            launch_cg_step(o_, S, st_);
+            launch_outer_finalize(partsA_.p, 0, 1, v.partsB_out, nB, v.scal_next, hres_dev, ++outer_seq_, 0, st_);
             hres = wait_outer_result();
             q.rr_parts = hres[2];
             TcgScal nx;
-            to_host(&nx, scal_.p + (par ^ 1), sizeof(nx));
+            to_host(&nx, v.scal_next, sizeof(nx));
             scal_out(nx, q.scal_out);
             down_mat(q.out_vR, vR_.p); down_vec(q.out_vs, vs_.p);
             if (!model_rec) { down_mat(q.out_HvR, HvR_.p); down_vec(q.out_Hvs, Hvs_.p); }
-            down_mat(q.out_rR, rR_.p); down_vec(q.out_rs, rs_next); down_mat(q.out_pR, pR_.p); down_vec(q.out_ps, ps_next);
+            down_mat(q.out_rR, rR_.p); down_vec(q.out_rs, v.rs_next); down_mat(q.out_pR, pR_.p); down_vec(q.out_ps, v.ps_next);
             if (Wtcg) down_mat(q.out_W, Wloc);
             if (wpad()) down_vec(q.out_Wpad, wpad(), 16);
-            if (q.partsB_out) to_host(q.partsB_out, pnext + (size_t)3 * nA, (size_t)nB * sizeof(double));
+            if (q.partsB_out) to_host(q.partsB_out, v.partsB_out, (size_t)nB * sizeof(double));
         }
     }
 
@@ -2051,26 +2036,8 @@ void Context::outer_probe(xm_outer_probe_t &q) {
 
     // ---- grad: as rtr_probe()
     upload_point(std::vector<double>(q.R, q.R + m3 * (size_t)o), o, std::vector<double>(q.s, q.s + n));
-    launch_scale_rows(o, nloc_, R_.p, s_.p, Wloc, st_);
     double f = 0, rr = 0;
-    if (!aut) {
-        eval_point(cur_, R_.p, s_.p, f, rr);
-    } else {
-        TcgScal sc;
-        std::memset(&sc, 0, sizeof(sc));
-        sc.phase = PH_CAND;
-        to_dev(scal_.p, &sc, sizeof(sc));
-        CamArgs a = cam_args(cur_);
-        a.scal = scal_.p;
-        a.partials = partsB_.p;
-        a.cand.R = R_.p; a.cand.s = s_.p;
-        a.cand.G = P.G.p; a.cand.egs = P.egs.p; a.cand.S0 = P.S0.p; a.cand.rgR = P.rgR.p; a.cand.rgs = P.rgs.p;
-        a.cand.partials = partsA_.p;
-        product(EPI_AUTO, o_, 2.0, a);
-        launch_outer_finalize(partsA_.p, nA, 1, partsM_.p, 0, scal_.p, hres_dev, ++outer_seq_, 0, st_);
-        volatile double *hres = wait_outer_result();
-        f = hres[0]; rr = hres[1];
-    }
+    probe_grad(aut, f, rr);
     q.f = f; q.rr = rr;
     down_mat(q.rgR, P.rgR.p); down_vec(q.rgs, P.rgs.p);
 
@@ -2106,7 +2073,7 @@ void Context::outer_probe(xm_outer_probe_t &q) {
     // ---- step: one (product, step) pair of trust_region_device() in the role scal_in.phase names
     if (want_step) {
         const int par = q.slot & 1;
-        double *ps_cur = par ? psB_.p : psA_.p, *ps_next = par ? psA_.p : psB_.p, *rs_cur = par ? rsB_.p : rs_.p, *rs_next = par ? rs_.p : rsB_.p;
+        const TcgParity v = tcg_parity(par);
         if (trace_dev_.count < (size_t)kMaxOuter * 6) trace_dev_.alloc((size_t)kMaxOuter * 6);
         if (stop_req_.count < 1) stop_req_.alloc(1);
         if (oscal_.count < 2) oscal_.alloc(2);
@@ -2116,15 +2083,17 @@ void Context::outer_probe(xm_outer_probe_t &q) {
         q.run = runid;
         volatile unsigned long long *hp = hstat_ + 24;
         *hp = 0;
-        const size_t chunk = (size_t)3 * nA + nB;
-        double *pcur = partsB_.p + (size_t)par * chunk, *pnext = partsB_.p + (size_t)(par ^ 1) * chunk;
         if (phase == PH_TCG) {   // the product input W = s.*pR + ps.*R by the kernel that writes it in a solve, as rtr_probe()
             up_mat(D_.p, q.pR, -1.0);
             up_vec(Hps_.p, q.ps, -1.0, true);
-            launch_tcg_init(o, nloc_, D_.p, Hps_.p, R_.p, s_.p, rR_.p, rs_.p, pR_.p, psA_.p, vR_.p, vs_.p, HvR_.p, Hvs_.p, Wloc, scal_.p, 0.0, 0.0, nullptr, st_, nullptr, 0);
+            TcgInitArgs I = tcg_init_args(0.0, 0.0, nullptr);
+            I.rgR = D_.p; I.rgs = Hps_.p;   // "rg" = -p
+            I.hstat = nullptr; I.seq = 0;   // no host progress word (nor a run number for it)
+            I.Wloc = Wloc; I.Wpad = nullptr;   // the native-pitch input only, as outer_step_args() (the device-driven form keeps no padded copy)
+            launch_tcg_init(o, I, st_);
         }
-        up_mat(pR_.p, q.pR, 1.0); up_vec(ps_cur, q.ps, 1.0, false); up_vec(ps_next, q.ps, 1.0, false);
-        up_mat(rR_.p, q.rR, 1.0); up_vec(rs_cur, q.rs, 1.0, false); up_vec(rs_next, q.rs, 1.0, false);
+        up_mat(pR_.p, q.pR, 1.0); up_vec(v.ps_cur, q.ps, 1.0, false); up_vec(v.ps_next, q.ps, 1.0, false);
+        up_mat(rR_.p, q.rR, 1.0); up_vec(v.rs_cur, q.rs, 1.0, false); up_vec(v.rs_next, q.rs, 1.0, false);
         up_mat(vR_.p, q.vR, 1.0); up_vec(vs_.p, q.vs, 1.0, false);
         up_mat(HvR_.p, q.HvR, 1.0); up_vec(Hvs_.p, q.Hvs, 1.0, false);
         if (q.Rc && q.sc) { up_mat(Rc_.p, q.Rc, 1.0); up_vec(sc_.p, q.sc, 1.0, false); }
@@ -2136,8 +2105,8 @@ void Context::outer_probe(xm_outer_probe_t &q) {
             XM_HIP_CHECK(hipMemsetAsync(b->p, 0, b->count * sizeof(double), st_));
         TcgScal sc = tcg_in(q.scal_in), sc_zero;
         std::memset(&sc_zero, 0, sizeof(sc_zero));
-        to_dev(scal_.p + par, &sc, sizeof(sc));
-        to_dev(scal_.p + (par ^ 1), &sc_zero, sizeof(sc_zero));
+        to_dev(v.scal_cur, &sc, sizeof(sc));
+        to_dev(v.scal_next, &sc_zero, sizeof(sc_zero));
         OuterScal os, os_zero;
         std::memset(&os, 0, sizeof(os));
         std::memset(&os_zero, 0, sizeof(os_zero));
@@ -2145,35 +2114,24 @@ void Context::outer_probe(xm_outer_probe_t &q) {
         os.stop_reason = q.os_in.stop_reason; os.time_up = q.os_in.time_up; os.slots = q.os_in.slots;
         to_dev(oscal_.p + par, &os, sizeof(os));
         to_dev(oscal_.p + (par ^ 1), &os_zero, sizeof(os_zero));
-        XM_HIP_CHECK(hipMemsetAsync(partsB_.p, 0, 2 * chunk * sizeof(double), st_));
+        XM_HIP_CHECK(hipMemsetAsync(partsB_.p, 0, 2 * v.chunk * sizeof(double), st_));
         XM_HIP_CHECK(hipMemsetAsync(partsM_.p, 0, (size_t)std::max(nwave, nM) * sizeof(double), st_));
         if (q.partsM_in && q.partsM_in_count == nwave) to_dev(partsM_.p, q.partsM_in, (size_t)nwave * sizeof(double));
         const int krec = q.os_in.k + 1;
         const bool rec_ok = krec >= 1 && krec < kMaxOuter;
         if (rec_ok) XM_HIP_CHECK(hipMemsetAsync(trace_dev_.p + (size_t)krec * 6, 0xff, 6 * sizeof(double), st_));
-        CamArgs a = cam_args(cur_);   // trust_region_device()'s enqueue_slot
-        a.scal = scal_.p + par;
-        a.ps = ps_cur;
-        a.rs = rs_cur;
-        a.partials = pcur;
-        a.cand.R = Rc_.p; a.cand.s = sc_.p;
-        a.cand.G = Pn.G.p; a.cand.egs = Pn.egs.p; a.cand.S0 = Pn.S0.p; a.cand.rgR = Pn.rgR.p; a.cand.rgs = Pn.rgs.p;
-        a.cand.partials = partsA_.p;
+        const CamArgs a = tcg_cam_args(v, true);   // trust_region_device()'s enqueue_slot
         if (phase == PH_TCG) {
-            sym_rev_ = par;
-            product(EPI_AUTO, o_, 2.0, a);
-            sym_rev_ = 1;
-            launch_outer_finalize(pcur, nA, 1, pcur + (size_t)2 * nA, nA, scal_.p + par, hres_dev, ++outer_seq_, 0, st_);
+            tcg_product(EPI_AUTO, a, par, false);
+            launch_outer_finalize(v.parts, nA, 1, v.parts + (size_t)2 * nA, nA, v.scal_cur, hres_dev, ++outer_seq_, 0, st_);
             volatile double *hres = wait_outer_result();
             q.pHp = hres[0]; q.rHp = hres[1]; q.HpHp = hres[2];
             down_mat(q.HpR, HpR_.p); down_vec(q.Hps, Hps_.p);
-            if (q.scal_in.iter > 0) to_dev(pcur + (size_t)3 * nA, q.partsB_in, (size_t)nB * sizeof(double));
+            if (q.scal_in.iter > 0) to_dev(v.parts + (size_t)3 * nA, q.partsB_in, (size_t)nB * sizeof(double));
             poison_pad_only(Rc_.p); poison_pad_only(Wloc);
         } else if (phase == PH_CAND) {
             launch_scale_rows(o, nloc_, Rc_.p, sc_.p, Wloc, st_);   // what the retraction of the tCG's last launch leaves as the product input
-            sym_rev_ = par;
-            product(EPI_AUTO, o_, 2.0, a);
-            sym_rev_ = 1;
+            tcg_product(EPI_AUTO, a, par, false);
             // the three sums the decision takes: f and <rg,rg> by the result kernel's tree, m of the partials regrouped as outer_decide regroups them
             std::vector<double> grouped((size_t)nM, 0.0);
             if (!model_rec)
@@ -2182,7 +2140,7 @@ void Context::outer_probe(xm_outer_probe_t &q) {
                     grouped[(size_t)i] = (w(4 * i) + w(4 * i + 1)) + (w(4 * i + 2) + w(4 * i + 3));
                 }
             to_dev(D_.p, grouped.data(), grouped.size() * sizeof(double));
-            launch_outer_finalize(partsA_.p, nA, 1, D_.p, model_rec ? 0 : nM, scal_.p + par, hres_dev, ++outer_seq_, grouping_, st_);
+            launch_outer_finalize(partsA_.p, nA, 1, D_.p, model_rec ? 0 : nM, v.scal_cur, hres_dev, ++outer_seq_, grouping_, st_);
             volatile double *hres = wait_outer_result();
             q.f_cand = hres[0]; q.rr_cand = hres[1]; q.m_cand = hres[2];
             down_mat(q.cand_G, Pn.G.p); down_vec(q.cand_egs, Pn.egs.p); down_vec(q.cand_S0, Pn.S0.p, 9); down_mat(q.cand_rgR, Pn.rgR.p); down_vec(q.cand_rgs, Pn.rgs.p);
@@ -2194,7 +2152,7 @@ void Context::outer_probe(xm_outer_probe_t &q) {
         q.progress = *hp;
         TcgScal nx;
         OuterScal on;
-        to_host(&nx, scal_.p + (par ^ 1), sizeof(nx));
+        to_host(&nx, v.scal_next, sizeof(nx));
         to_host(&on, oscal_.p + (par ^ 1), sizeof(on));
         tcg_out(nx, q.scal_out);
         q.os_out.loss = on.loss; q.os_out.rr_point = on.rr_point; q.os_out.totalite = on.totalite; q.os_out.shrink_count = on.shrink_count; q.os_out.k = on.k;
@@ -2205,10 +2163,10 @@ void Context::outer_probe(xm_outer_probe_t &q) {
         }
         down_mat(q.out_R, R_.p); down_vec(q.out_s, s_.p); down_mat(q.out_Rc, Rc_.p); down_vec(q.out_sc, sc_.p);
         down_mat(q.out_vR, vR_.p); down_vec(q.out_vs, vs_.p); down_mat(q.out_HvR, HvR_.p); down_vec(q.out_Hvs, Hvs_.p);
-        down_mat(q.out_rR, rR_.p); down_vec(q.out_rs, rs_next); down_mat(q.out_pR, pR_.p); down_vec(q.out_ps, ps_next);
+        down_mat(q.out_rR, rR_.p); down_vec(q.out_rs, v.rs_next); down_mat(q.out_pR, pR_.p); down_vec(q.out_ps, v.ps_next);
         down_mat(q.out_W, Wloc);
         if (wpad()) down_vec(q.out_Wpad, wpad(), 16);
-        if (q.out_partsB) to_host(q.out_partsB, pnext + (size_t)3 * nA, (size_t)nB * sizeof(double));
+        if (q.out_partsB) to_host(q.out_partsB, v.partsB_out, (size_t)nB * sizeof(double));
         if (q.out_partsM) to_host(q.out_partsM, partsM_.p, (size_t)nwave * sizeof(double));
         down_mat(q.out_G, P.G.p); down_vec(q.out_egs, P.egs.p); down_vec(q.out_S0, P.S0.p, 9); down_mat(q.out_rgR, P.rgR.p); down_vec(q.out_rgs, P.rgs.p);
         if (phase == PH_TCG) { q.out_pad[0] = count_pad(Rc_.p); q.out_pad[1] = count_pad(Wloc); }
