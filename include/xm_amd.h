@@ -825,6 +825,44 @@ typedef struct {
     double *Lam, *dz, *alpha, *beta, *V, *c1, *c2, *y, *x;
 } xm_cert_probe_t;
 int xm_ctx_cert_probe(xm_ctx_t *ctx, xm_cert_probe_t *probe);
+/* The matrix-free Q (XM_STORAGE_SCHUR) stage by stage, a test export (tests/test_gpu_schur_stages.py): the layout of the packed landmark
+ * lists, the set-up factors as the last set_weights left them, what one product leaves behind in every stage of the factor chain, and the
+ * pieces of the inner CG.  Single-GPU, single-rank XM_STORAGE_SCHUR contexts only (XM_ERR_ARG otherwise, and for a wrong struct_size, flags
+ * != 0, non-finite input, o or k outside 0, 1, 3..10 -- the ranks the kernels are instantiated for --, an array the context's form does not
+ * have: dinv, VX, pAp, MX without the CG form, VTinv with it, perm, binv, ainv without the two-level preconditioner).  Every array whose
+ * pointer is not null is filled; arrays per landmark come by INPUT landmark index (the device numbers landmarks by degree), matrices are
+ * column-major, n1 = n - 1 (the reduced cameras 1..n-1), m landmarks.
+ *   layout   nheavy (landmarks with more than 64 observations: a workgroup each), lm_total (entries of the packed by-landmark arrays, padding
+ *            included), deg (m: observations per landmark as the device holds them), uses_cg, two_level, nagg (aggregates of 64 cameras),
+ *            dup_pairs (1: set_weights takes the host assembly -- a (camera, landmark) pair named twice, or xm_tuning_t.schur_host_assembly)
+ *   set-up   Q1 (9 n, row-major 3 x 3 blocks: sum w p p^T), c (3 n: sum w p), q2 (n: sum w), q3inv (m: 1 / sum w, 0 for a landmark without
+ *            weight); CG form: dinv (n1: 1 / diag VT); dense form: VTinv (n1 x n1, from the padded layout the product reads; n1 >
+ *            XM_SCHUR_PROBE_DENSE_MAX_ROWS: XM_ERR_ARG); two-level: perm (64 nagg: reduced camera at each row of each aggregate, -1 = padding),
+ *            binv (64 x 64 x nagg: VT_aa^-1, padding rows the identity), ainv (nagg x nagg: (P^T VT P)^-1)
+ *   chain    W (3n x o, input; o = 0: none) -> one SchurOp::product with the plain epilogue and alpha, then the scratch vectors it wrote:
+ *            h (m x o), r (n1 x o), xc (n1 x o), xl (m x o), and Y (3n x o) = alpha Q W.  CG form: pcg_done, pcg_iters, pcg_relres (the state
+ *            word the product's inner solve ended with), pcg_tol and pcg_cap (the relative residual it asks for, the iteration cap)
+ *   CG form  X (n1 x k, input; k = 0: none) -> MX = M^-1 X through the PCG's start (b := X; the init launch, then for the two-level form the block
+ *            and coarse launches; p read back), VX = VT X through the operator's two launches with p := X, pAp (k) = <p, VT p>: the camera
+ *            pass's per-workgroup partial sums added by the tree pcg_upd_kernel uses.  All through the functions the product's solve calls.
+ * The context is only read: the factors are untouched, the statistics of xm_ctx_schur_info are restored, and a later product or solve gives the
+ * bits it would have given without the call.  Allocates the grow-only scratch of a product at o and k columns. */
+#define XM_SCHUR_PROBE_DENSE_MAX_ROWS 4096  /* a 134 MB matrix copied to the host */
+typedef struct {
+    uint32_t struct_size;
+    uint32_t flags;
+    int32_t o, k;
+    double alpha;
+    const double *W, *X;
+    int64_t nheavy, lm_total, nagg;
+    int32_t uses_cg, two_level, dup_pairs, pcg_done, pcg_iters, pcg_cap;
+    double pcg_relres, pcg_tol;
+    int32_t *deg, *perm;
+    double *Q1, *c, *q2, *q3inv, *dinv, *VTinv, *binv, *ainv;
+    double *h, *r, *xc, *xl, *Y;
+    double *VX, *pAp, *MX;
+} xm_schur_probe_t;
+int xm_ctx_schur_probe(xm_ctx_t *ctx, xm_schur_probe_t *probe);
 /* Smallest eigenpair of the symmetric tridiagonal matrix with diagonal a[0..m) and off-diagonal b[0..m-1), by the certificate's own host code
  * (Sturm bisection to an interval of 4e-16 max(1, tmax), inverse iteration): *theta, y[0..m) (unit norm), *tmax = the Gershgorin bound of |T|.
  * Host only, a test export (tests/test_tridiag_min.py). */

@@ -461,6 +461,29 @@ int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const dou
     return XM_OK;
     XM_CATCH
 }
+int xm_ctx_schur_probe(xm_ctx_t *ctx, xm_schur_probe_t *pr) {
+    XM_TRY
+    if (!ctx || !pr) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_probe: null argument");
+    if (pr->struct_size != sizeof(xm_schur_probe_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_probe: xm_schur_probe_t.struct_size is not sizeof(xm_schur_probe_t)");
+    if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_probe: single-GPU contexts only (not n_gpus > 1)");
+    if (ctx->impl->world() > 1 || ctx->impl->comm_kind() != 0) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_probe: single-rank contexts only");
+    if (pr->flags != 0) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_probe: unknown flag");
+    auto cols = [](int v) { return v == 0 || v == 1 || (v >= 3 && v <= 10); };
+    if (!cols(pr->o) || !cols(pr->k)) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_probe: o and k must be 0, 1 or 3..10");
+    if ((pr->o > 0) != (pr->W != nullptr)) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_probe: o > 0 and W go together");
+    if ((pr->k > 0) != (pr->X != nullptr)) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_probe: k > 0 and X go together");
+    if (pr->o == 0 && (pr->h || pr->r || pr->xc || pr->xl || pr->Y)) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_probe: the chain stages need W");
+    if (pr->k == 0 && (pr->VX || pr->pAp || pr->MX)) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_probe: VX, pAp and MX need X");
+    const int64_t n = ctx->impl->cameras();
+    if (pr->o > 0 && !std::isfinite(pr->alpha)) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_probe: alpha is not finite");
+    for (int64_t k = 0; k < 3 * n * pr->o; ++k)
+        if (!std::isfinite(pr->W[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_probe: W is not finite");
+    for (int64_t k = 0; k < (n - 1) * pr->k; ++k)
+        if (!std::isfinite(pr->X[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_probe: X is not finite");
+    ctx->impl->schur_probe(*pr);
+    return XM_OK;
+    XM_CATCH
+}
 int xm_ctx_rtr_probe(xm_ctx_t *ctx, xm_rtr_probe_t *pr) {
     XM_TRY
     if (!ctx || !pr) throw xm::Error(XM_ERR_ARG, "xm_ctx_rtr_probe: null argument");

@@ -72,6 +72,9 @@ struct SchurSettings {          // from xm_tuning_t (Settings::resolve)
     int pcg_hess_digits = 0;    // CG form: relative residual 10^-digits of the inner solve inside HESSIAN products (0 = 9; gradient, cost and certificate products: 13)
 };
 struct SchurLm;                 // xm_schur.hip
+struct PcgArgs;
+struct PcgTwoLevel;
+struct PcgGrids;
 
 // The device lists of a SchurOp, read-only, for the kernels of other files (the bundle adjustment, xm_ba.h).  By camera: the observations of
 // camera i at [cam_ptr[i], cam_ptr[i+1]) with the landmark SLOT of each and its current weight.  By landmark slot: the first nheavy slots
@@ -122,6 +125,10 @@ public:
     // utils/creatematrix.py:283-311.  Needs the dense inverse of VT (not the CG form) and a list without a (camera, landmark) pair named twice.
     void build_dense_q(double *Q, int64_t ldq, double *abar, hipStream_t st);
     bool names_a_pair_twice() const { return has_dup_; }
+    // The test export xm_ctx_schur_probe (include/xm_amd.h): the layout, the set-up factors as the last set_weights left them, the stages of one
+    // product() of q.W and the pieces of the inner CG for q.X, the latter through the members pcg_solve() calls.  Leaves the statistics of the CG
+    // form and the scratch vectors' clean padding as a product expects them.
+    void probe(xm_schur_probe_t &q, hipStream_t st);
 
 private:
     int64_t n_ = 0, m_ = 0, nobs_ = 0, nred_ = 0, ldv_ = 0;   // nred = cameras of the padded (N-1) system / 3
@@ -168,6 +175,15 @@ private:
     double pcg_tol_[2] = {1e-13, 1e-9}, pcg_last_relres_ = 0.0;
     int64_t pcg_products_ = 0, pcg_iters_total_ = 0, pcg_unconverged_ = 0;
     template <int O, bool TL> void pcg_solve(const SchurLm &L, const struct TcgScal *sc, hipStream_t st, int kind);
+    // the pieces of pcg_solve (the probe calls the same): arguments and grids at o columns; x = 0, r = b and z = p = M^-1 b; VT p (+ <p, VT p>
+    // partial sums); z = M^-1 r with <r, z> into parity par (Jacobi: nothing to launch, the flat kernels apply the diagonal themselves)
+    void pcg_setup(int o, int kind, const SchurLm &L, PcgArgs &a, PcgTwoLevel &t, PcgGrids &g);
+    template <int O, bool TL> void pcg_start(const PcgArgs &a, const PcgTwoLevel &t, const PcgGrids &g, const struct TcgScal *sc, hipStream_t st);
+    template <int O> void pcg_operator(const SchurLm &L, const PcgArgs &a, const PcgGrids &g, hipStream_t st);
+    template <int O, bool TL> void pcg_precond(const PcgArgs &a, const PcgTwoLevel &t, const PcgGrids &g, int par, int init, hipStream_t st);
+    template <int O> void probe_chain(xm_schur_probe_t &q, hipStream_t st);
+    template <int O, bool TL> void probe_pcg(xm_schur_probe_t &q, const SchurLm &L, hipStream_t st);
+    SchurLm lm_lists() const;
     // two-level preconditioner M^-1 r = blockdiag(VT_aa)^-1 r + P A_c^-1 P^T r (cfg.solver == 3).  Structure (fixed): the aggregates and, per
     // aggregate, its "groups" -- the observations of one landmark whose cameras fall in the aggregate, by landmark slot -- and the coarse
     // entries with their lists of group pairs (light landmarks; heavy ones are rank-1 terms).  Weight-dependent: the block inverses and A_c^-1.

@@ -990,7 +990,7 @@ void SchurOp::set_weights(const double *w, hipStream_t st) {
     auto put = [&](DevBuf<double> &buf, const std::vector<double> &v) {
         if (!v.empty()) XM_HIP_CHECK(hipMemcpy(buf.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
     };
-    put(cam_w_, c_w); put(lm_w_, d_lw); put(Q1_, Q1); put(c_, c); put(q3inv_, q3inv_slot);
+    put(cam_w_, c_w); put(lm_w_, d_lw); put(Q1_, Q1); put(c_, c); put(q2_, Q2); put(q3inv_, q3inv_slot);
     if (mr > 0) {   // invert on the device (blocked Cholesky, xm_dense_la.hip), then lay the inverse out like a dense Q
         DevBuf<double> tmp, inv;
         tmp.alloc((size_t)mr * mr, false); inv.alloc((size_t)mr * mr, false);
@@ -1042,8 +1042,7 @@ void SchurOp::set_weights_device(const double *w, hipStream_t st) {
                        cam_w_.p, lm_w_.p);
     hipLaunchKernelGGL(schur_cam_sums_kernel, dim3((unsigned)((N + kQwWaves - 1) / kQwWaves)), dim3(256), 0, st, N, nobs, cam_ptr_.p, cam_w_.p, cam_p_.p,
                        Q1_.p, c_.p, q2_.p);
-    SchurLm L;
-    L.m = m_; L.nheavy = nheavy_; L.total = ltotal_; L.ptr = lm_ptr_.p; L.gbase = gbase_.p; L.deg = ldeg_.p; L.cam = lm_cam_.p; L.w = lm_w_.p; L.p = lm_p_.p;
+    const SchurLm L = lm_lists();
     const int64_t nlight = M - nheavy_;
     hipLaunchKernelGGL(schur_lm_q3_kernel, dim3((unsigned)(nheavy_ + (nlight + kSchurHeavyThreads - 1) / kSchurHeavyThreads)), dim3(kSchurHeavyThreads), 0, st, L,
                        q3inv_.p);
@@ -1434,8 +1433,7 @@ void SchurOp::product(int o, int epi, const double *W, double alpha, const CamAr
         XM_HIP_CHECK(hipMemsetAsync(xc_.p, 0, xc_.count * sizeof(double), st));
         o_last_ = o;
     }
-    SchurLm L;
-    L.m = m_; L.nheavy = nheavy_; L.total = ltotal_; L.ptr = lm_ptr_.p; L.gbase = gbase_.p; L.deg = ldeg_.p; L.cam = lm_cam_.p; L.w = lm_w_.p; L.p = lm_p_.p;
+    const SchurLm L = lm_lists();
     std::function<void(const TcgScal *)> pcg;
     // inner tolerance by the kind of product: the truncated CG tolerates a Hessian applied to 1e-9 (its own stop rule is a RELATIVE residual of
     // 1e-1 .. 1e-6, its recurrences never look at the true residual), the gradient that decides convergence and the certificate do not
@@ -1453,45 +1451,57 @@ void SchurOp::product(int o, int epi, const double *W, double alpha, const CamAr
 // x_cam = VT^-1 r by preconditioned CG (kernels above).  The iterations are enqueued in batches without looking at the device: as many as
 // the previous product needed (+ 2), then the host reads the state word and tops up in steps of 8 -- one host round trip per product in
 // the steady state, where consecutive right-hand sides of a truncated CG need the same number of iterations to within a few.
-template <int O, bool TL>
-void SchurOp::pcg_solve(const SchurLm &L, const TcgScal *sc, hipStream_t st, int kind) {
-    constexpr int OP = pitch_of(O);
-    const int n1 = (int)(n_ - 1);
-    PcgArgs a;
-    a.n1 = n1; a.grid = pcg_grid_; a.tol2 = pcg_tol_[kind] * pcg_tol_[kind];
+struct PcgGrids { dim3 b, gf, gc, glm, blm, gb; };   // flat kernels, camera pass, landmark pass, aggregate blocks
+void SchurOp::pcg_setup(int o, int kind, const SchurLm &L, PcgArgs &a, PcgTwoLevel &t, PcgGrids &g) {
+    a.n1 = (int)(n_ - 1); a.grid = pcg_grid_; a.tol2 = pcg_tol_[kind] * pcg_tol_[kind];
     a.b = r_.p; a.q2 = q2_.p;
-    if (TL) a.z = tl_z_.p; else a.dinv = pcg_dinv_.p;
+    if (tl_) a.z = tl_z_.p; else a.dinv = pcg_dinv_.p;
     a.x = xc_.p; a.r = pcg_r_.p; a.p = pcg_p_.p; a.Ap = pcg_ap_.p;
-    const size_t seg = (size_t)pcg_grid_ * O;
+    const size_t seg = (size_t)pcg_grid_ * o;
     a.prz[0] = pcg_parts_.p; a.prz[1] = pcg_parts_.p + seg; a.prr = pcg_parts_.p + 2 * seg; a.pbb = pcg_parts_.p + 3 * seg;
     a.ppap = pcg_parts_.p + 4 * seg; a.cam_grid = qw_grid((int)n_);
     a.st = reinterpret_cast<PcgState *>(pcg_state_.p);
-    const dim3 b(256), gf(pcg_grid_), gc(a.cam_grid);
     const int64_t nlight = L.m - L.nheavy;
-    const dim3 glm((unsigned)(L.nheavy + (nlight + kSchurHeavyThreads - 1) / kSchurHeavyThreads)), blm(kSchurHeavyThreads);
-    PcgTwoLevel t;
+    g.b = dim3(256); g.gf = dim3(pcg_grid_); g.gc = dim3(a.cam_grid);
+    g.glm = dim3((unsigned)(L.nheavy + (nlight + kSchurHeavyThreads - 1) / kSchurHeavyThreads)); g.blm = dim3(kSchurHeavyThreads);
     t.nagg = tl_nagg_; t.perm = tl_perm_.p; t.binv = tl_binv_.p; t.ainv = tl_ainv_.p; t.g = tl_g_.p; t.z = tl_z_.p;
-    const dim3 gb((unsigned)std::max<int64_t>(1, (tl_nagg_ + kQwWaves - 1) / kQwWaves));
-    auto precond = [&](int par, int init) {   // z = M^-1 r, <r, z> into parity par (init: p = z)
-        if constexpr (TL) {
-            hipLaunchKernelGGL((pcg_block_kernel<O>), gb, b, 0, st, a, t);
-            hipLaunchKernelGGL((pcg_coarse_kernel<O>), gf, b, 0, st, a, t, par, init);
-        }
-    };
-    hipLaunchKernelGGL((pcg_init_kernel<O, TL>), gf, b, 0, st, a, sc);
-    precond(0, 1);
+    g.gb = dim3((unsigned)std::max<int64_t>(1, (tl_nagg_ + kQwWaves - 1) / kQwWaves));
+}
+template <int O, bool TL>
+void SchurOp::pcg_precond(const PcgArgs &a, const PcgTwoLevel &t, const PcgGrids &g, int par, int init, hipStream_t st) {   // z = M^-1 r, <r, z> into parity par (init: p = z)
+    if constexpr (TL) {
+        hipLaunchKernelGGL((pcg_block_kernel<O>), g.gb, g.b, 0, st, a, t);
+        hipLaunchKernelGGL((pcg_coarse_kernel<O>), g.gf, g.b, 0, st, a, t, par, init);
+    }
+}
+template <int O, bool TL>
+void SchurOp::pcg_start(const PcgArgs &a, const PcgTwoLevel &t, const PcgGrids &g, const TcgScal *sc, hipStream_t st) {
+    hipLaunchKernelGGL((pcg_init_kernel<O, TL>), g.gf, g.b, 0, st, a, sc);
+    pcg_precond<O, TL>(a, t, g, 0, 1, st);
+}
+template <int O>
+void SchurOp::pcg_operator(const SchurLm &L, const PcgArgs &a, const PcgGrids &g, hipStream_t st) {   // Ap = VT p through the two lists (y_l in xl_)
+    hipLaunchKernelGGL((pcg_lm_kernel<O>), g.glm, g.blm, 0, st, L, q3inv_.p, (const double *)a.p, (const PcgState *)a.st, xl_.p);
+    hipLaunchKernelGGL((pcg_cam_kernel<O>), g.gc, g.b, 0, st, (int)n_, cam_ptr_.p, cam_lm_.p, cam_w_.p, (const double *)xl_.p, a);
+}
+template <int O, bool TL>
+void SchurOp::pcg_solve(const SchurLm &L, const TcgScal *sc, hipStream_t st, int kind) {
+    PcgArgs a;
+    PcgTwoLevel t;
+    PcgGrids g;
+    pcg_setup(O, kind, L, a, t, g);
+    pcg_start<O, TL>(a, t, g, sc, st);
     int it = 0, dir_applied = 0;   // dir_applied: the iteration whose direction update is already in the queue (iteration 0 needs none)
     auto enqueue = [&](int upto) {
         for (; it < upto; ++it) {
-            if (it != dir_applied) hipLaunchKernelGGL((pcg_dir_kernel<O, TL>), gf, b, 0, st, a, it);
-            hipLaunchKernelGGL((pcg_lm_kernel<O>), glm, blm, 0, st, L, q3inv_.p, (const double *)a.p, (const PcgState *)a.st, xl_.p);
-            hipLaunchKernelGGL((pcg_cam_kernel<O>), gc, b, 0, st, (int)n_, cam_ptr_.p, cam_lm_.p, cam_w_.p, (const double *)xl_.p, a);
-            hipLaunchKernelGGL((pcg_upd_kernel<O, TL>), gf, b, 0, st, a, it);
-            precond((it & 1) ^ 1, 0);
+            if (it != dir_applied) hipLaunchKernelGGL((pcg_dir_kernel<O, TL>), g.gf, g.b, 0, st, a, it);
+            pcg_operator<O>(L, a, g, st);
+            hipLaunchKernelGGL((pcg_upd_kernel<O, TL>), g.gf, g.b, 0, st, a, it);
+            pcg_precond<O, TL>(a, t, g, (it & 1) ^ 1, 0, st);
         }
         // the convergence test of the last update (no-op once done).  When the test fails the same launch IS the direction update of iteration
         // `it`: a following batch must not repeat it (p = z + beta (z + beta p) is no conjugate direction -- ADVICE r5)
-        hipLaunchKernelGGL((pcg_dir_kernel<O, TL>), gf, b, 0, st, a, it);
+        hipLaunchKernelGGL((pcg_dir_kernel<O, TL>), g.gf, g.b, 0, st, a, it);
         dir_applied = it;
     };
     int target = std::min(pcg_max_iters_, std::max(4, pcg_last_iters_[kind] + 2));
@@ -1508,7 +1518,161 @@ void SchurOp::pcg_solve(const SchurLm &L, const TcgScal *sc, hipStream_t st, int
     pcg_products_++;
     pcg_iters_total_ += pcg_host_->done ? pcg_host_->iters : target;
     if (!pcg_host_->done) pcg_unconverged_++;
-    (void)OP;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The test export xm_ctx_schur_probe (include/xm_amd.h)
+// ------------------------------------------------------------------------------------------------------------------
+// <p, VT p> per column from the camera pass's partial sums, by the tree pcg_upd_kernel adds them with
+template <int O>
+__global__ __launch_bounds__(256) void pcg_probe_pap_kernel(PcgArgs a, double *__restrict__ out) {
+    __shared__ double sh[4];
+    double pap[O];
+    pcg_sums<O>(a.ppap, a.cam_grid, pap, sh);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < O; ++k) out[k] = pap[k];
+    }
+}
+namespace {
+template <class T>
+std::vector<T> probe_fetch(const T *dev, size_t count, hipStream_t st) {
+    std::vector<T> v(count);
+    if (count) XM_HIP_CHECK(hipMemcpyAsync(v.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost, st));
+    XM_HIP_CHECK(hipStreamSynchronize(st));
+    return v;
+}
+// records of `pitch` doubles (rows x o used) -> column-major rows x o; row_of: the record of output row i (null: i)
+void probe_unpack(const std::vector<double> &rec, int64_t rows, int o, int pitch, const int32_t *row_of, double *out) {
+    for (int64_t i = 0; i < rows; ++i) {
+        const size_t s = (size_t)(row_of ? row_of[i] : i) * pitch;
+        for (int k = 0; k < o; ++k) out[(size_t)i + (size_t)k * rows] = rec[s + k];
+    }
+}
+std::vector<double> probe_pack(const double *in, int64_t rows, int o, int pitch, size_t count) {
+    std::vector<double> rec(count, 0.0);
+    for (int64_t i = 0; i < rows; ++i)
+        for (int k = 0; k < o; ++k) rec[(size_t)i * pitch + k] = in[(size_t)i + (size_t)k * rows];
+    return rec;
+}
+}  // namespace
+
+template <int O>
+void SchurOp::probe_chain(xm_schur_probe_t &q, hipStream_t st) {
+    constexpr int OP = pitch_of(O);
+    const int64_t n1 = n_ - 1;
+    DevBuf<double> dW, dY;
+    const std::vector<double> hW = probe_pack(q.W, 3 * n_, O, OP, (size_t)(n_ + kColPad) * 3 * OP);
+    dW.alloc(hW.size(), false); dY.alloc((size_t)n_ * 3 * OP + 2);
+    XM_HIP_CHECK(hipMemcpyAsync(dW.p, hW.data(), hW.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    CamArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.nloc = (int)n_; a.out = dY.p;
+    product(O, EPI_PLAIN, dW.p, q.alpha, a, st);
+    if (q.h) probe_unpack(probe_fetch(h_.p, (size_t)m_ * OP, st), m_, O, OP, slot_of_.data(), q.h);
+    if (q.xl) probe_unpack(probe_fetch(xl_.p, (size_t)m_ * OP, st), m_, O, OP, slot_of_.data(), q.xl);
+    if (q.r) probe_unpack(probe_fetch(r_.p, (size_t)n1 * OP, st), n1, O, OP, nullptr, q.r);
+    if (q.xc) probe_unpack(probe_fetch(xc_.p, (size_t)n1 * OP, st), n1, O, OP, nullptr, q.xc);
+    if (q.Y) probe_unpack(probe_fetch(dY.p, (size_t)n_ * 3 * OP, st), 3 * n_, O, OP, nullptr, q.Y);
+    XM_HIP_CHECK(hipStreamSynchronize(st));
+    if (pcg_ && n1 > 0) { q.pcg_done = pcg_host_->done; q.pcg_iters = pcg_host_->iters; q.pcg_relres = pcg_host_->relres; }
+}
+
+template <int O, bool TL>
+void SchurOp::probe_pcg(xm_schur_probe_t &q, const SchurLm &L, hipStream_t st) {
+    constexpr int OP = pitch_of(O);
+    const int64_t n1 = n_ - 1;
+    ensure(O);
+    PcgArgs a;
+    PcgTwoLevel t;
+    PcgGrids g;
+    pcg_setup(O, 0, L, a, t, g);
+    const std::vector<double> hX = probe_pack(q.X, n1, O, OP, (size_t)n1 * OP);
+    // b := X (the rows beyond n1 of r_ stay as they are; product() clears the vector again: o_last_ below)
+    XM_HIP_CHECK(hipMemcpyAsync(r_.p, hX.data(), hX.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    pcg_start<O, TL>(a, t, g, nullptr, st);
+    check_launch("schur probe (M^-1 X)");
+    if (q.MX) probe_unpack(probe_fetch(pcg_p_.p, (size_t)n1 * OP, st), n1, O, OP, nullptr, q.MX);
+    // p := X; the state word says "not done" since the init launch
+    XM_HIP_CHECK(hipMemcpyAsync(pcg_p_.p, hX.data(), hX.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    pcg_operator<O>(L, a, g, st);
+    DevBuf<double> dpap;
+    dpap.alloc(O);
+    hipLaunchKernelGGL((pcg_probe_pap_kernel<O>), dim3(1), dim3(256), 0, st, a, dpap.p);
+    check_launch("schur probe (VT X)");
+    if (q.VX) probe_unpack(probe_fetch(pcg_ap_.p, (size_t)n1 * OP, st), n1, O, OP, nullptr, q.VX);
+    if (q.pAp) {
+        const std::vector<double> v = probe_fetch(dpap.p, O, st);
+        std::copy(v.begin(), v.end(), q.pAp);
+    }
+    XM_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+SchurLm SchurOp::lm_lists() const {
+    SchurLm L;
+    L.m = m_; L.nheavy = nheavy_; L.total = ltotal_; L.ptr = lm_ptr_.p; L.gbase = gbase_.p; L.deg = ldeg_.p; L.cam = lm_cam_.p; L.w = lm_w_.p; L.p = lm_p_.p;
+    return L;
+}
+
+void SchurOp::probe(xm_schur_probe_t &q, hipStream_t st) {
+    if (comm_) throw Error(XM_ERR_ARG, "xm_ctx_schur_probe: single-rank contexts only");
+    const int64_t n1 = n_ - 1;
+    const bool cg = pcg_ && n1 > 0, tl = tl_ && n1 > 0;
+    if (!pcg_ && (q.dinv || q.VX || q.pAp || q.MX || q.k > 0)) throw Error(XM_ERR_ARG, "xm_ctx_schur_probe: dinv, X, VX, pAp and MX need the CG form (xm_tuning_t.schur_solver 2 or 3)");
+    if (pcg_ && q.VTinv) throw Error(XM_ERR_ARG, "xm_ctx_schur_probe: the CG form keeps no VTinv");
+    if (!tl_ && (q.perm || q.binv || q.ainv)) throw Error(XM_ERR_ARG, "xm_ctx_schur_probe: perm, binv and ainv need the two-level preconditioner (xm_tuning_t.schur_solver 3)");
+    if (q.VTinv && n1 > XM_SCHUR_PROBE_DENSE_MAX_ROWS) throw Error(XM_ERR_ARG, "xm_ctx_schur_probe: VTinv with more than XM_SCHUR_PROBE_DENSE_MAX_ROWS rows");
+    q.nheavy = nheavy_; q.lm_total = ltotal_; q.nagg = tl ? tl_nagg_ : 0;
+    q.uses_cg = pcg_ ? 1 : 0; q.two_level = tl_ ? 1 : 0; q.dup_pairs = dup_pairs_ ? 1 : 0;
+    q.pcg_done = 0; q.pcg_iters = 0; q.pcg_relres = 0.0; q.pcg_tol = pcg_ ? pcg_tol_[0] : 0.0; q.pcg_cap = pcg_ ? pcg_max_iters_ : 0;
+    XM_HIP_CHECK(hipStreamSynchronize(st));
+    auto by_landmark = [&](const auto &slot_vals, auto *out) {
+        for (int64_t l = 0; l < m_; ++l) out[l] = slot_vals[(size_t)slot_of_[(size_t)l]];
+    };
+    auto copy_out = [&](const double *dev, size_t count, double *out) {
+        const std::vector<double> v = probe_fetch(dev, count, st);
+        std::copy(v.begin(), v.end(), out);
+    };
+    if (q.deg) by_landmark(probe_fetch(ldeg_.p, (size_t)m_, st), q.deg);
+    if (q.q3inv) by_landmark(probe_fetch(q3inv_.p, (size_t)m_, st), q.q3inv);
+    if (q.Q1) copy_out(Q1_.p, (size_t)n_ * 9, q.Q1);
+    if (q.c) copy_out(c_.p, (size_t)n_ * 3, q.c);
+    if (q.q2) copy_out(q2_.p, (size_t)n_, q.q2);
+    if (q.dinv && cg) copy_out(pcg_dinv_.p, (size_t)n1, q.dinv);
+    if (q.VTinv && n1 > 0) {   // row i of the padded row-major layout -> column-major n1 x n1
+        std::vector<double> v((size_t)n1 * n1);
+        XM_HIP_CHECK(hipMemcpy2DAsync(v.data(), (size_t)n1 * sizeof(double), vtinv_.p, (size_t)ldv_ * sizeof(double), (size_t)n1 * sizeof(double), (size_t)n1,
+                                      hipMemcpyDeviceToHost, st));
+        XM_HIP_CHECK(hipStreamSynchronize(st));
+        for (int64_t i = 0; i < n1; ++i)
+            for (int64_t j = 0; j < n1; ++j) q.VTinv[(size_t)i + (size_t)j * n1] = v[(size_t)i * n1 + j];
+    }
+    if (tl) {
+        if (q.perm) {
+            const std::vector<int32_t> v = probe_fetch(tl_perm_.p, (size_t)tl_nagg_ * kSchurAggCams, st);
+            std::copy(v.begin(), v.end(), q.perm);
+        }
+        if (q.binv) copy_out(tl_binv_.p, (size_t)tl_nagg_ * kSchurAggCams * kSchurAggCams, q.binv);
+        if (q.ainv) copy_out(tl_ainv_.p, (size_t)tl_nagg_ * tl_nagg_, q.ainv);
+    }
+    // the statistics of the CG form and its batch sizes are the products' own: put back behind the probe's launches
+    const int64_t s_products = pcg_products_, s_iters = pcg_iters_total_, s_unconv = pcg_unconverged_;
+    const int s_last[2] = {pcg_last_iters_[0], pcg_last_iters_[1]};
+    const double s_relres = pcg_last_relres_;
+    struct Leave {
+        std::function<void()> f;
+        ~Leave() { f(); }
+    } leave{[&] {
+        pcg_products_ = s_products; pcg_iters_total_ = s_iters; pcg_unconverged_ = s_unconv;
+        pcg_last_iters_[0] = s_last[0]; pcg_last_iters_[1] = s_last[1]; pcg_last_relres_ = s_relres;
+        o_last_ = 0;   // the next product starts from clean padding in r_ and xc_ (the CG pieces wrote X into r_)
+    }};
+    if (q.o > 0) { XM_DISPATCH_O(q.o, (probe_chain<O_>(q, st))); }
+    if (q.k > 0 && cg) {
+        const SchurLm L = lm_lists();
+        if (tl_) { XM_DISPATCH_O(q.k, (probe_pcg<O_, true>(q, L, st))); }
+        else { XM_DISPATCH_O(q.k, (probe_pcg<O_, false>(q, L, st))); }
+    }
 }
 
 }  // namespace xm

@@ -163,6 +163,7 @@ public:
     void ba_probe(const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q);   // test export
     void outer_probe(xm_outer_probe_t &q);   // test export (xm_ctx_outer_probe): the retraction and the device-driven step launch stage by stage
     void rtr_probe(xm_rtr_probe_t &q);   // test export (include/xm_amd.h: xm_ctx_rtr_probe): the trust region's kernels stage by stage
+    void schur_probe(xm_schur_probe_t &q);   // test export (xm_ctx_schur_probe): the matrix-free Q's factors, chain stages and inner-CG pieces
     void cert_probe(xm_cert_probe_t &q); // test export (xm_ctx_cert_probe): the certificate's Lanczos eigen-solver
     void reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr);   // per observation, input order (xm_ba.h)
     // which observations, cameras and landmarks of the list survive cleaning at the current weights (xm_clean.h); changes nothing here

@@ -2377,6 +2377,12 @@ void Context::ba_probe(const BaSettings &cfg, const double *rot, const double *t
     c.watchdog_s = cfg_.watchdog_s;
     xm::ba_probe(*schur_, c, rot, t, p, q, st_);
 }
+void Context::schur_probe(xm_schur_probe_t &q) {
+    if (!schur_ || schur_dense_)
+        throw Error(XM_ERR_ARG, "xm_ctx_schur_probe: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages keep no factors");
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_schur_probe: single-rank contexts only");
+    schur_->probe(q, st_);
+}
 void Context::reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr) {
     if (!schur_)
         throw Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");

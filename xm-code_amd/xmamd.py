@@ -36,7 +36,7 @@ EXPORTS = [
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
     "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_ba_aggregate_plan", "xm_ctx_ba_probe",
-    "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe", "xm_ctx_outer_probe", "xm_ctx_cert_probe", "xm_tridiag_min",
+    "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe", "xm_ctx_outer_probe", "xm_ctx_cert_probe", "xm_tridiag_min", "xm_ctx_schur_probe",
     "xm_ctx_dense_q", "xm_create_matrix", "xm_schur_dense_limits",
     "xm_pair_filter", "xm_pair_filter_limits",
 ]
@@ -177,6 +177,20 @@ class CertProbe(C.Structure):   # xm_cert_probe_t, the test export xm_ctx_cert_p
 
 CERT_PROBE_UNFUSED = 1
 
+SCHUR_PROBE_INTS = ("uses_cg", "two_level", "dup_pairs", "pcg_done", "pcg_iters", "pcg_cap")
+SCHUR_PROBE_OUT = ("deg", "perm", "Q1", "c", "q2", "q3inv", "dinv", "VTinv", "binv", "ainv", "h", "r", "xc", "xl", "Y", "VX", "pAp", "MX")
+
+
+class SchurProbe(C.Structure):   # xm_schur_probe_t, the test export xm_ctx_schur_probe
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("o", C.c_int32), ("k", C.c_int32), ("alpha", C.c_double), ("W", C.c_void_p),
+                ("X", C.c_void_p), ("nheavy", C.c_int64), ("lm_total", C.c_int64), ("nagg", C.c_int64)] + \
+               [(k, C.c_int32) for k in SCHUR_PROBE_INTS] + [("pcg_relres", C.c_double), ("pcg_tol", C.c_double)] + \
+               [(k, C.c_void_p) for k in SCHUR_PROBE_OUT]
+
+
+SCHUR_PROBE_DENSE_MAX_ROWS = 4096
+SCHUR_AGG_CAMS = 64
+
 
 def tridiag_min(a, b):
     """smallest eigenpair of the symmetric tridiagonal matrix (diagonal a[0..m), off-diagonal b[0..m-1)) by the certificate's host code
@@ -285,6 +299,7 @@ def lib():
         L.xm_ctx_rtr_probe.argtypes = [C.c_void_p, C.POINTER(RtrProbe)]
         L.xm_ctx_outer_probe.argtypes = [C.c_void_p, C.POINTER(OuterProbe)]
         L.xm_ctx_cert_probe.argtypes = [C.c_void_p, C.POINTER(CertProbe)]
+        L.xm_ctx_schur_probe.argtypes = [C.c_void_p, C.POINTER(SchurProbe)]
         L.xm_tridiag_min.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.POINTER(C.c_double)]
         L.xm_clean_observations.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CleanOptions), C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.POINTER(CleanResult)]
@@ -1144,6 +1159,44 @@ class Context:
         if cert:
             out["dual"] = np.array(q.dual[:])
         return {k: (np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v) for k, v in out.items()}
+
+    def schur_probe(self, W=None, alpha=1.0, X=None, dense=False):
+        """the matrix-free Q stage by stage (the test export xm_ctx_schur_probe; include/xm_amd.h): a dict of the layout (nheavy, lm_total, nagg,
+        uses_cg, two_level, dup_pairs, deg), the set-up factors (Q1 n x 3 x 3, c n x 3, q2, q3inv; CG form: dinv; dense=True: VTinv; two-level:
+        perm nagg x 64, binv nagg x 64 x 64, ainv); with W (3n x o): h, r, xc, xl, Y of one product alpha Q W and, for the CG form, pcg_done,
+        pcg_iters, pcg_relres, pcg_tol, pcg_cap; with X (n - 1 x k, CG form): MX, VX, pAp.  Landmark arrays by input index."""
+        n, m = self.n, self.n_landmarks
+        n1 = n - 1
+        info = self.schur_info()
+        q = SchurProbe()
+        q.struct_size = C.sizeof(SchurProbe)
+        out = dict(deg=np.zeros(m, dtype=np.int32), Q1=np.zeros((n, 3, 3)), c=np.zeros((n, 3)), q2=np.zeros(n), q3inv=np.zeros(m))
+        if info["cg"]:
+            out["dinv"] = np.zeros(n1)
+        elif dense:
+            if n1 > SCHUR_PROBE_DENSE_MAX_ROWS:
+                raise XmError("schur_probe: VTinv with more than SCHUR_PROBE_DENSE_MAX_ROWS rows")
+            out["VTinv"] = np.zeros((n1, n1), order="F")
+        if info["precond"] == "two-level" and n1 > 0:
+            na = info["aggregates"]
+            out.update(perm=np.zeros((na, SCHUR_AGG_CAMS), dtype=np.int32), binv=np.zeros((na, SCHUR_AGG_CAMS, SCHUR_AGG_CAMS)), ainv=np.zeros((na, na), order="F"))
+        if W is not None:
+            W = np.asfortranarray(np.asarray(W, dtype=np.float64).reshape(3 * n, -1))
+            o = W.shape[1]
+            q.o, q.W, q.alpha = o, W.ctypes.data_as(C.c_void_p), float(alpha)
+            out.update(h=np.zeros((m, o), order="F"), r=np.zeros((n1, o), order="F"), xc=np.zeros((n1, o), order="F"), xl=np.zeros((m, o), order="F"),
+                       Y=np.zeros((3 * n, o), order="F"))
+        if X is not None:
+            X = np.asfortranarray(np.asarray(X, dtype=np.float64).reshape(n1, -1))
+            k = X.shape[1]
+            q.k, q.X = k, X.ctypes.data_as(C.c_void_p)
+            out.update(MX=np.zeros((n1, k), order="F"), VX=np.zeros((n1, k), order="F"), pAp=np.zeros(k))
+        for key, v in out.items():
+            setattr(q, key, v.ctypes.data_as(C.c_void_p))
+        _chk(lib().xm_ctx_schur_probe(self.h, C.byref(q)))
+        out.update(nheavy=q.nheavy, lm_total=q.lm_total, nagg=q.nagg, pcg_relres=q.pcg_relres, pcg_tol=q.pcg_tol)
+        out.update({key: getattr(q, key) for key in SCHUR_PROBE_INTS})
+        return out
 
     def cert_probe(self, o, lam, R, s, unfused=False, mmax=None, want_V=True):
         """the certificate's Lanczos eigen-solver at the point (R: 3n x o, s: n) (the test export xm_ctx_cert_probe; include/xm_amd.h): a dict of
