@@ -452,6 +452,76 @@ int xm_pair_filter(int64_t n, int64_t m, int64_t nobs, const int32_t *cam, const
 /* out[0]: largest joint set that is sorted in LDS; out[1]: threads per workgroup; out[2]: workgroups of the workspace path; out[3]: largest
  * joint set of the small LDS instantiation (every pair starts there) */
 int xm_pair_filter_limits(int64_t out[4]);
+/* ---- The depth lift: from the front end's match table and every camera's depth and confidence map to the observation list, on the device
+ * (5_test_ceres.py:191-204, the de-duplication, and :244-296, the loop over the cameras; 4_test_unidepth.py:217-262 is the same loop with
+ * margin = 5).  It runs in front of xm_pair_filter, xm_clean_observations and xm_ctx_create (XM_STORAGE_SCHUR), which take its output as it
+ * is.  The maps are what a depth network leaves on the GPU: with XM_LIFT_MAPS_ON_DEVICE depth[i] and conf[i] are device pointers and no
+ * map travels (the reference copies every H x W map to the host to read a few thousand pixels of each).
+ * Input: n cameras, m tracks, nrows rows of the match table in input order: cam[r], lm[r] 0-based, xy[r] = 2 doubles, the pixel position
+ * (x, y).  Per camera i: hw[2i], hw[2i + 1] = height and width of its maps; depth[i], conf[i]: f32, row-major, pitch = width.  depth[i] ==
+ * NULL: the camera has no map and yields nothing (the reference's `continue` at :253).  conf == NULL, or conf[i] == NULL: every weight (of
+ * that camera) is 1.  Kinv + 9i: the INVERSE intrinsics of camera i, row-major; nothing is inverted here (the reference inverts K at :284).
+ * Without XM_LIFT_MAPS_ON_DEVICE the maps are host memory: the call samples them on the host and uploads the samples only; everything
+ * behind the sampling is the same device code, so the two transports give the same bits.
+ *   1. Of the rows with the same (cam, lm) the earliest in input order stays (:194-198: a stable lexsort, then np.unique(...,
+ *      return_index), which names the first row of every group).
+ *   2. u = (int)x, v = (int)y, truncated toward zero (:261-262, astype(int)).  A row passes when margin <= u < w - margin and
+ *      margin <= v < h - margin (:265).
+ *   3. d = the f32 depth at (v, u), over all rows of the camera that passed 2., non-positive values included (:272).
+ *   4. threshold = P(d, depth_pct = 95) (:273): numpy's default percentile IN F64 ON THE WIDENED SAMPLES -- position (k - 1) * (q / 100)
+ *      in the sorted values, a + (b - a) t between the two neighbours, b - (b - a)(1 - t) for t >= 1/2 (numpy's _lerp), every product and
+ *      sum rounded on its own: the rule of xm_pair_filter's step 4.
+ *   5. A row survives when d > 0 && d < threshold (:275); so the largest depth of a camera never survives.
+ *   6. One NaN among a camera's d leaves the camera with nothing (numpy's percentile is NaN then); threshold[i] is NaN.
+ *   7. w = the f32 product c * c of the confidence at (v, u), widened to double (:281, :289: w ** 2 on a float32 array).
+ *   8. p = (Kinv (u, v, 1)^T) * (double)d, the sum of every row of Kinv as (K0 u + K1 v) + K2 (:282-285).
+ *   9. Output order: camera ascending, then track ascending (the order in which the reference walks its CSR rows).
+ * Output (host arrays of capacity nrows; *nout entries are written): out_cam, out_lm, out_p (3 doubles), out_w, and out_row = the input
+ * row every output came from (what carries the reference's rgbs, or anything else, along).  threshold (n entries or NULL): the camera's
+ * percentile, NaN for a camera the reference skips (no map, no row, no row inside the border) and for 6.  The option fields are literal
+ * (0 is a value); XM_LIFT_OPTIONS_INIT holds the constants of 5_test_ceres.py.
+ * Where this differs from the reference, on purpose: the script hands np.percentile the float32 array, and numpy then interpolates in
+ * float32 (with numpy 2.x the position as well), which depends on the numpy version.  The f64 rule above is the contract.  The two can
+ * differ only where the interpolated threshold rounds onto its lower neighbour in float32: 19 samples 1.0f and one nextafter(1.0f) give
+ * threshold == 1.0f in float32 and > 1 in f64, which decides the 19 rows.
+ * XM_ERR_ARG: an index out of range, a pixel position that is not finite or |x|, |y| >= 2^31, nrows (n, m) >= 2^31, more than 2^30 rows of
+ * one camera, a negative size or margin, a percentile outside [0, 100], h or w <= 0 with a non-null map, a struct_size that is not
+ * sizeof, unknown flags, null arrays (cam, lm, xy and the outputs with nrows > 0; hw, depth, Kinv with n > 0; opt, nout, res).
+ * On the device: the rows are binned by camera (a counting sort), one workgroup per camera sorts its (track, row) words and its sampled
+ * depths in LDS, an exclusive scan of the cameras' survivor counts gives their offsets and one more kernel writes the list.  No atomic
+ * decides an order or a value: two calls give the same bits in every output.  Cameras above xm_lift_limits()[0] rows take the same code
+ * through a global-memory workspace.  Needs no context. */
+#define XM_LIFT_MAPS_ON_DEVICE 1u
+typedef struct {
+    uint32_t struct_size;
+    int32_t margin;            /* 10 */
+    uint32_t flags;            /* XM_LIFT_MAPS_ON_DEVICE */
+    uint32_t reserved;
+    double depth_pct;          /* 95 */
+} xm_lift_options_t;
+#define XM_LIFT_OPTIONS_INIT { (uint32_t)sizeof(xm_lift_options_t), 10, 0u, 0u, 95.0 }
+typedef struct {
+    uint32_t struct_size;
+    uint32_t reserved;
+    int64_t rows_duplicate;    /* rows dropped by 1. */
+    int64_t rows_border;       /* ... by 2. */
+    int64_t rows_depth;        /* ... by 5. or 6. */
+    int64_t rows_no_map;       /* rows (after 1.) of cameras without a map; the four and *nout add up to nrows */
+    int64_t cams_no_map;       /* cameras with depth[i] == NULL */
+    int64_t cams_empty;        /* cameras with a map that yielded nothing */
+    int64_t cams_small, cams_large, cams_workspace;   /* cameras with at least one row, by the size of the kernel that handled them */
+    int64_t max_rows;          /* most rows of one camera */
+    double seconds_index;      /* host: checks, sampling of host maps, upload, binning */
+    double seconds_kernels;
+    double seconds_download;
+} xm_lift_result_t;
+int xm_lift_observations(int64_t n, int64_t m, int64_t nrows, const int32_t *cam, const int32_t *lm, const double *xy, const int32_t *hw,
+                         const float *const *depth, const float *const *conf /* or NULL */, const double *Kinv /* 9 per camera */,
+                         const xm_lift_options_t *opt, int32_t *out_cam, int32_t *out_lm, double *out_p, double *out_w, int32_t *out_row,
+                         int64_t *nout, double *threshold /* n or NULL */, xm_lift_result_t *res);
+/* out[0]: most rows of a camera that are sorted in LDS; out[1]: threads per workgroup; out[2]: workgroups of the workspace path; out[3]:
+ * most rows of a camera in the small LDS instantiation (every camera with that many rows or fewer runs there) */
+int xm_lift_limits(int64_t out[4]);
 /* Translations and landmarks of a solution: the last step of utils/recoversolution.py:recover_XM (lines 77-86,
  * ybar_est = Abar @ sR_real.T; t_est = [0 | first N-1 columns], p_est = the rest) for an XM_STORAGE_SCHUR context.  The reference
  * needs the dense (N-1+M) x 3N matrix Abar.bin that create_matrix writes (creatematrix.py:283-311; 80 GB at Final-13682 with 800 k

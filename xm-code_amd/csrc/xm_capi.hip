@@ -10,6 +10,7 @@
 
 #include "xm_ba.h"
 #include "xm_clean.h"
+#include "xm_lift.h"
 #include "xm_pair.h"
 #include "xm_schur.h"
 #include "xm_sell.h"
@@ -682,6 +683,47 @@ int xm_pair_filter(int64_t n, int64_t m, int64_t nobs, const int32_t *cam, const
     out.max_joint = r.max_joint; out.pairs_on_workspace_path = r.pairs_on_workspace_path;
     out.seconds_index = r.seconds_index; out.seconds_kernels = r.seconds_kernels; out.seconds_download = r.seconds_download;
     *res = out;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_lift_observations(int64_t n, int64_t m, int64_t nrows, const int32_t *cam, const int32_t *lm, const double *xy, const int32_t *hw,
+                         const float *const *depth, const float *const *conf, const double *Kinv, const xm_lift_options_t *opt, int32_t *out_cam,
+                         int32_t *out_lm, double *out_p, double *out_w, int32_t *out_row, int64_t *nout, double *threshold, xm_lift_result_t *res) {
+    XM_TRY
+    const std::string w("xm_lift_observations");
+    if (!opt || !res || !nout) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (opt->struct_size != sizeof(xm_lift_options_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_lift_options_t.struct_size is not sizeof(xm_lift_options_t)");
+    if (res->struct_size != sizeof(xm_lift_result_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_lift_result_t.struct_size is not sizeof(xm_lift_result_t)");
+    if (opt->margin < 0) throw xm::Error(XM_ERR_ARG, w + ": negative margin");
+    if (!(opt->depth_pct >= 0.0) || !(opt->depth_pct <= 100.0)) throw xm::Error(XM_ERR_ARG, w + ": a percentile outside [0, 100]");
+    if (opt->flags & ~XM_LIFT_MAPS_ON_DEVICE) throw xm::Error(XM_ERR_ARG, w + ": unknown flag");
+    if (n < 0 || m < 0 || nrows < 0) throw xm::Error(XM_ERR_ARG, w + ": negative size");
+    if (n >= ((int64_t)1 << 31) || m >= ((int64_t)1 << 31) || nrows >= ((int64_t)1 << 31))
+        throw xm::Error(XM_ERR_ARG, w + ": cameras, tracks and rows must each stay below 2^31");
+    if (nrows > 0 && (!cam || !lm || !xy || !out_cam || !out_lm || !out_p || !out_w || !out_row)) throw xm::Error(XM_ERR_ARG, w + ": null row or output arrays");
+    if (n > 0 && (!hw || !depth || !Kinv)) throw xm::Error(XM_ERR_ARG, w + ": null camera arrays");
+    xm::LiftSettings c;
+    c.margin = opt->margin; c.depth_pct = opt->depth_pct; c.maps_on_device = (opt->flags & XM_LIFT_MAPS_ON_DEVICE) != 0;
+    require_device();
+    if (const char *e = std::getenv("XM_WATCHDOG_S")) { const double v = std::atof(e); if (v > 0) c.watchdog_s = v; }
+    xm::LiftOutcome r;
+    xm::lift_observations_host(n, m, nrows, cam, lm, xy, hw, depth, conf, Kinv, c, out_cam, out_lm, out_p, out_w, out_row, threshold, r);
+    xm_lift_result_t out;
+    std::memset(&out, 0, sizeof(out));
+    out.struct_size = sizeof(xm_lift_result_t);
+    out.rows_duplicate = r.rows_duplicate; out.rows_border = r.rows_border; out.rows_depth = r.rows_depth; out.rows_no_map = r.rows_no_map;
+    out.cams_no_map = r.cams_no_map; out.cams_empty = r.cams_empty; out.cams_small = r.cams_small; out.cams_large = r.cams_large;
+    out.cams_workspace = r.cams_workspace; out.max_rows = r.max_rows;
+    out.seconds_index = r.seconds_index; out.seconds_kernels = r.seconds_kernels; out.seconds_download = r.seconds_download;
+    *nout = r.nout;
+    *res = out;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_lift_limits(int64_t out[4]) {
+    XM_TRY
+    if (!out) throw xm::Error(XM_ERR_ARG, "xm_lift_limits: null output");
+    out[0] = xm::kLiftLdsRows; out[1] = xm::kLiftThreads; out[2] = xm::kLiftWsGroups; out[3] = xm::kLiftSmallRows;
     return XM_OK;
     XM_CATCH
 }

@@ -13,12 +13,14 @@
 
 // every product and every sum below is rounded on its own: the residual that is sorted and the one compared with the threshold are the same bits
 #pragma clang fp contract(off)
+#include "xm_sortstat.h"   // after the pragma: its percentile is compiled without contraction too
 
 namespace xm {
 namespace {
 
 typedef unsigned long long u64;
 constexpr int kT = kPairThreads;
+static_assert(kT == kSortThreads, "the helpers of xm_sortstat.h are written for this workgroup size");
 constexpr int kCap = kPairLdsJoint;
 
 // slots of the device counter block
@@ -43,8 +45,6 @@ struct PairArgs {
     int32_t ws_cap;
 };
 
-__device__ inline int lane_id() { return (int)(threadIdx.x & 63u); }
-__device__ inline double inf_() { return __longlong_as_double(0x7ff0000000000000ll); }
 __device__ inline bool finite_(double x) { return (__double_as_longlong(x) & 0x7ff0000000000000ll) != 0x7ff0000000000000ll; }
 
 // position of key in the increasing array a[0 .. len), -1 when absent
@@ -56,35 +56,6 @@ __device__ inline int find_lm(const int32_t *a, int len, int key) {
     }
     return (lo < len && a[lo] == key) ? lo : -1;
 }
-// sum over the workgroup, valid in every thread; ired: 4 ints
-__device__ inline int block_sum_int(int v, int *ired) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();
-    if (lane_id() == 0) ired[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (ired[0] + ired[1]) + (ired[2] + ired[3]);
-}
-// ascending bitonic sort of S[0 .. KP), KP a power of two >= 2; ends with a barrier
-template <class P>
-__device__ inline void sort_values(P S, int KP) {
-    for (int size = 2; size <= KP; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = (int)threadIdx.x; t < (KP >> 1); t += kT) {
-                const int i = 2 * t - (t & (stride - 1)), j = i + stride;
-                const bool up = (i & size) == 0;
-                const double x = S[i], y = S[j];
-                if ((x > y) == up) { S[i] = y; S[j] = x; }
-            }
-            __syncthreads();
-        }
-}
-// S[q] = f(q) for q < k, +inf behind; then sorted
-template <class P, class F>
-__device__ inline void fill_sort(P S, int KP, int k, F f) {
-    for (int q = (int)threadIdx.x; q < KP; q += kT) S[q] = q < k ? f(q) : inf_();
-    __syncthreads();
-    sort_values(S, KP);
-}
 // scipy.stats.trim_mean of the cnt smallest values of the sorted S: the mean of [lo, cnt - lo), lo = int(trim * cnt); a fixed tree
 template <class P>
 __device__ inline double trimmed_mean(P S, int cnt, double trim, double *dred) {
@@ -94,15 +65,6 @@ __device__ inline double trimmed_mean(P S, int cnt, double trim, double *dred) {
     const double sum = block_sum256(v, dred);
     __syncthreads();   // dred is free again
     return sum / (double)(hi - lo);
-}
-// numpy.percentile (linear) of the k smallest values of the sorted S at the fraction q
-template <class P>
-__device__ inline double percentile(P S, int k, double q) {
-    const double pos = (double)(k - 1) * q;
-    const double fl = floor(pos), t = pos - fl;
-    const int i0 = (int)fl, i1 = i0 + 1 < k ? i0 + 1 : k - 1;
-    const double a = S[i0], b = S[i1], d = b - a;
-    return t >= 0.5 ? b - d * (1.0 - t) : a + d * t;
 }
 __device__ inline double norm3(double x, double y, double z) { return sqrt((x * x + y * y) + z * z); }
 

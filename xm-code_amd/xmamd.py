@@ -39,6 +39,7 @@ EXPORTS = [
     "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe", "xm_ctx_outer_probe", "xm_ctx_cert_probe", "xm_tridiag_min", "xm_ctx_schur_probe",
     "xm_ctx_dense_q", "xm_create_matrix", "xm_schur_dense_limits",
     "xm_pair_filter", "xm_pair_filter_limits",
+    "xm_lift_observations", "xm_lift_limits",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -239,6 +240,21 @@ class PairResult(C.Structure):     # xm_pair_result_t
                [(k, C.c_double) for k in ("seconds_index", "seconds_kernels", "seconds_download")]
 
 
+class LiftOptions(C.Structure):    # xm_lift_options_t; the defaults are the constants of 5_test_ceres.py (XM_LIFT_OPTIONS_INIT)
+    _fields_ = [("struct_size", C.c_uint32), ("margin", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32), ("depth_pct", C.c_double)]
+
+    def __init__(self, margin=10, flags=0, depth_pct=95.0):
+        super().__init__(C.sizeof(LiftOptions), margin, flags, 0, depth_pct)
+
+
+class LiftResult(C.Structure):     # xm_lift_result_t
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + \
+               [(k, C.c_int64) for k in ("rows_duplicate", "rows_border", "rows_depth", "rows_no_map", "cams_no_map", "cams_empty", "cams_small",
+                                         "cams_large", "cams_workspace", "max_rows")] + \
+               [(k, C.c_double) for k in ("seconds_index", "seconds_kernels", "seconds_download")]
+
+
+LIFT_MAPS_ON_DEVICE = 1
 PAIR_STAT_DTYPE = np.dtype([("n_joint", "<i4"), ("n_kept", "<i4"), ("n_flagged", "<i4"), ("status", "<i4"), ("scale1", "<f8"), ("scale2", "<f8"),
                             ("translation", "<f8", (3,)), ("median", "<f8"), ("p95", "<f8"), ("percentage", "<f8")])
 PAIR_SKIP_ROW0 = 1
@@ -307,6 +323,9 @@ def lib():
         L.xm_pair_filter.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.POINTER(PairOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PairResult)]
         L.xm_pair_filter_limits.argtypes = [C.c_void_p]
+        L.xm_lift_observations.argtypes = [C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7 + [C.POINTER(LiftOptions)] + [C.c_void_p] * 5 + \
+                                          [C.POINTER(C.c_int64), C.c_void_p, C.POINTER(LiftResult)]
+        L.xm_lift_limits.argtypes = [C.c_void_p]
         L.xm_ctx_reprojection_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_transport.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
         L.xm_ctx_dense_q.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -756,6 +775,107 @@ def pair_filter(cam, lm, p, pairs_i, pairs_j, R, n=None, m=None, min_joint=20, t
     _chk(lib().xm_pair_filter(n, m, cam.size, P(cam), P(lm), P(p), pi.size, P(pi), P(pj), P(R), C.byref(opt), P(count), P(outlier), P(stats),
                               C.byref(res)))
     return PairFilterPlan(count, outlier.astype(bool), stats, {k: getattr(res, k) for k, _ in PairResult._fields_ if k not in ("struct_size", "reserved")})
+
+
+class LiftPlan:
+    """what lift_observations returns: the observation list cam, lm (int32), p (nout x 3), w in camera-then-track order, row (the input
+    row of every output), threshold (per camera, NaN where the camera was skipped) and info, the fields of xm_lift_result_t"""
+
+    def __init__(self, cam, lm, p, w, row, threshold, info, nrows):
+        self.cam, self.lm, self.p, self.w, self.row, self.threshold, self.info, self.nrows = cam, lm, p, w, row, threshold, info, nrows
+
+    def carry(self, *per_row_arrays):
+        """the rows of every array given (colours, ...) that belong to the outputs, in output order"""
+        out = []
+        for a in per_row_arrays:
+            a = np.asarray(a)
+            if a.shape[:1] != (self.nrows,):
+                raise XmError("LiftPlan.carry: a per-row array has another length than the match table")
+            out.append(a[self.row])
+        return tuple(out)
+
+
+def lift_limits():
+    """-> dict(lds_rows: most rows of a camera that are sorted in LDS (larger cameras take the workspace path), threads: per workgroup,
+    workspace_groups: workgroups of the workspace path, small_rows: most rows of a camera in the small LDS instantiation)"""
+    out = np.zeros(4, dtype=np.int64)
+    _chk(lib().xm_lift_limits(out.ctypes.data_as(C.c_void_p)))
+    return dict(lds_rows=int(out[0]), threads=int(out[1]), workspace_groups=int(out[2]), small_rows=int(out[3]))
+
+
+def _lift_map(x, what, i):
+    """one entry of depth / conf -> (pointer, on_device, (h, w), the object that keeps the memory alive)"""
+    if x is None:
+        return 0, None, None, None
+    if isinstance(x, tuple) and len(x) == 3 and isinstance(x[0], DevArray):
+        d, h, w = x
+        if int(h) * int(w) * 4 > d.nbytes:
+            raise XmError(f"lift_observations: {what}[{i}]: the device buffer is smaller than h x w float32")
+        return int(d.ptr.value or 0), True, (int(h), int(w)), d
+    if isinstance(x, np.ndarray):
+        if x.ndim != 2 or x.dtype != np.float32:
+            raise XmError(f"lift_observations: {what}[{i}] must be a 2-D float32 array")
+        x = np.ascontiguousarray(x)
+        return x.ctypes.data, False, (int(x.shape[0]), int(x.shape[1])), x
+    if hasattr(x, "data_ptr") and hasattr(x, "shape") and hasattr(x, "is_cuda"):
+        if len(x.shape) != 2 or "float32" not in str(getattr(x, "dtype", "float32")):
+            raise XmError(f"lift_observations: {what}[{i}] must be a 2-D float32 tensor")
+        if hasattr(x, "is_contiguous") and not x.is_contiguous():
+            x = x.contiguous()
+        return int(x.data_ptr()), bool(x.is_cuda), (int(x.shape[0]), int(x.shape[1])), x
+    raise XmError(f"lift_observations: {what}[{i}] is none of None, a float32 array, (DevArray, h, w) or a tensor")
+
+
+def lift_observations(cam, lm, xy, depth, conf, K, n=None, m=None, margin=10, depth_pct=95.0):
+    """the reference's depth lift (5_test_ceres.py:191-204, :244-296) on the device (xm_lift_observations; include/xm_amd.h has the
+    definition): cam, lm 0-based per row of the match table, xy nrows x 2 pixel positions; depth, conf: one entry per camera -- None, a 2-D
+    float32 array (host), (DevArray, h, w), or an object with data_ptr(), shape and is_cuda (a torch tensor); conf may be None altogether
+    (every weight 1); K: n x 3 x 3 intrinsics, inverted here.  Host and device maps cannot be mixed.  -> LiftPlan"""
+    cam = np.ascontiguousarray(cam, dtype=np.int32).reshape(-1); lm = np.ascontiguousarray(lm, dtype=np.int32).reshape(-1)
+    xy = np.ascontiguousarray(xy, dtype=np.float64)
+    if cam.size != lm.size or xy.shape != (cam.size, 2):
+        raise XmError("lift_observations: cam, lm and xy (nrows x 2) must have one entry per row")
+    depth = list(depth)
+    n = len(depth) if n is None else int(n)
+    m = (int(lm.max()) + 1 if lm.size else 0) if m is None else int(m)
+    if len(depth) != n or (conf is not None and len(conf) != n):
+        raise XmError("lift_observations: depth and conf must have one entry per camera")
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape != (n, 3, 3):
+        raise XmError("lift_observations: K must be n x 3 x 3")
+    if int(margin) < 0:
+        raise XmError("lift_observations: negative margin")
+    if not (depth_pct >= 0 and depth_pct <= 100):
+        raise XmError("lift_observations: a percentile outside [0, 100]")
+    Kinv = np.ascontiguousarray(np.linalg.inv(K)) if n else np.zeros((0, 3, 3))
+    hw = np.zeros((n, 2), dtype=np.int32); dptr = np.zeros(n, dtype=np.uint64); cptr = np.zeros(n, dtype=np.uint64)
+    where = set(); alive = []
+    for i in range(n):
+        pd, on_d, shp, keep = _lift_map(depth[i], "depth", i)
+        pc, on_c, shc, keepc = _lift_map(None if conf is None else conf[i], "conf", i)
+        if pd == 0:
+            continue                                   # (no depth map: the camera's confidence map is not looked at)
+        if pc and shc != shp:
+            raise XmError(f"lift_observations: depth[{i}] and conf[{i}] differ in shape")
+        where.add(on_d)
+        if pc:
+            where.add(on_c)
+        hw[i] = shp; dptr[i] = pd; cptr[i] = pc; alive += [keep, keepc]
+    if len(where) > 1:
+        raise XmError("lift_observations: host and device maps are mixed in one call")
+    opt = LiftOptions(int(margin), LIFT_MAPS_ON_DEVICE if where == {True} else 0, float(depth_pct))
+    res = LiftResult(); res.struct_size = C.sizeof(LiftResult)
+    require_gpu()
+    nr = cam.size
+    ocam = np.zeros(nr, dtype=np.int32); olm = np.zeros(nr, dtype=np.int32); orow = np.zeros(nr, dtype=np.int32)
+    op = np.zeros((nr, 3)); ow = np.zeros(nr); thr = np.full(n, np.nan); nout = C.c_int64(0)
+    P = lambda a: a.ctypes.data_as(C.c_void_p)
+    _chk(lib().xm_lift_observations(n, m, nr, P(cam), P(lm), P(xy), P(hw), P(dptr), None if conf is None else P(cptr), P(Kinv), C.byref(opt), P(ocam),
+                                    P(olm), P(op), P(ow), P(orow), C.byref(nout), P(thr), C.byref(res)))
+    del alive
+    k = nout.value
+    info = {f: getattr(res, f) for f, _ in LiftResult._fields_ if f not in ("struct_size", "reserved")}
+    return LiftPlan(ocam[:k].copy(), olm[:k].copy(), op[:k].copy(), ow[:k].copy(), orow[:k].copy(), thr, info, nr)
 
 
 def symw_plan(ntot, nloc, cam0, K=0):
