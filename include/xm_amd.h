@@ -522,6 +522,106 @@ int xm_lift_observations(int64_t n, int64_t m, int64_t nrows, const int32_t *cam
 /* out[0]: most rows of a camera that are sorted in LDS; out[1]: threads per workgroup; out[2]: workgroups of the workspace path; out[3]:
  * most rows of a camera in the small LDS instantiation (every camera with that many rows or fewer runs there) */
 int xm_lift_limits(int64_t out[4]);
+/* ---- Feature tracks from pairwise matches, on the device: the stage that produces the match table the depth lift reads.  It stands for the
+ * track establishment of the reference's fork of GLOMAP (deps/glomap/glomap/controllers/track_establishment.cc: BlindConcatenation :19-63,
+ * TrackCollection :65-151, FindTracksForProblem :153-227, called from global_mapper.cc:113-156) with its modified union-find
+ * (deps/glomap/glomap/math/union_find.h, which refuses to merge two sets that share an image).  NOTHING HERE WAS COMPARED WITH THE
+ * REFERENCE'S COMPILED CODE (it needs COLMAP, Eigen and glog): parity rests on a line-cited sequential restatement
+ * (tests/xm_tracks_numpy.py) and on the argument of rule 3.  Needs no context; host arrays in, host arrays out.
+ * Input: n images; foff[n + 1], foff[0] = 0, non-decreasing: image i owns the global features foff[i] .. foff[i + 1] - 1, F = foff[n];
+ * xy: 2 doubles per feature; registered[n] (NULL: every image is registered); npairs pairs pi[k], pj[k] in any order and either
+ * orientation; moff[npairs + 1], moff[0] = 0, non-decreasing; f1[e], f2[e]: the feature index IN image pi[k] / pj[k] of every inlier match
+ * of every valid pair (the caller applies is_valid and the inlier mask, :28-36).
+ *   1. A feature takes part only if it is an endpoint of some match (union_find.h:18-25 creates a point in Find): it is "touched".  A match
+ *      listed twice, in both orientations, or in a pair listed twice changes nothing.
+ *   2. The connected components of the match graph over the touched features are computed.  A component's label is its smallest global
+ *      feature index.
+ *   3. A component is conflicted when it holds two features of one image.  A conflict-free component is a track as it is: no Union inside
+ *      it is ever refused, whatever the order of the pairs, so the fork, upstream GLOMAP and plain connected components agree on it, and
+ *      the check at :120-136 never fires for it.
+ *   4. Conflicted components have no order-independent statement in the reference (its result depends on the hash order of the pairs);
+ *      they follow `conflict`:
+ *      XM_TRACKS_DROP    the component yields nothing.
+ *      XM_TRACKS_GLOMAP  upstream GLOMAP, and :120-136 on the merged set: the component is discarded whole if any two of its features in
+ *                        one image have sqrt(dx*dx + dy*dy) > thres_inconsistency (every product and sum rounded on its own, strictly
+ *                        greater); otherwise it is kept with ALL its rows -- two rows of one image then carry one track, and
+ *                        xm_lift_observations' rule 1 keeps the earlier, the smaller feature index.
+ *      XM_TRACKS_SPLIT   the fork's refusal in an order that does not depend on the input: the distinct edges of the component, sorted as
+ *                        (smaller id, larger id) ascending, are visited one by one; the two roots are united when their image sets are
+ *                        disjoint, the larger root under the smaller.  The resulting sets are the tracks: none sees an image twice and
+ *                        every label is still the set's smallest member.  ON PURPOSE this departs from the fork: the fork puts the refused
+ *                        endpoint into the other endpoint's track all the same (:102-105), which :125-136 then discards or keeps with two
+ *                        rows of one image.  That step is not reproduced.  The split is sequential; it runs on the host over the edges of
+ *                        the conflicted components only (xm_tracks_split_host) and is timed on its own.
+ *   5. A track is dropped when its observation count (all images, :161, :163) is below min_views or above max_views, or when the number of
+ *      distinct REGISTERED images in it (:186-197) is below min_views.
+ *   6. If more than max_tracks + 1 tracks remain, the max_tracks + 1 longest stay (:219 breaks on `>`).  Ties go to the larger label; the
+ *      reference's tie order is its union-find root, which is arbitrary.
+ *   7. min_num_tracks_per_view >= 0 is the reference's sequential per-view greedy (:203-218).  The pipeline never sets it (-1 compared with
+ *      an unsigned counter: no limit), it is not offered and there is no such field.
+ *   8. Kept tracks are numbered 0 .. ntracks - 1 in ascending label (the reference's idx is hash order).
+ * Output (the four row arrays have capacity F; *nout rows are written): one row per touched feature of a registered image in a kept
+ * track, image ascending, then feature ascending: out_cam, out_feat (the index in the image), out_track, out_xy (the input's bits).
+ * label[F] or NULL: the track of every feature, or a negative XM_TRACK_* code.  A feature of an unregistered image in a kept track carries
+ * the track's number and has no row.  XM_TRACK_CONFLICT also stands for a GLOMAP discard.
+ * XM_ERR_ARG, nothing written: pi[k] == pj[k], an image or feature index out of range (feature indices are checked on the device and
+ * never used as an address when out of range), foff or moff not starting at 0 or decreasing, F, n, npairs or the number of matches
+ * >= 2^31, thres_inconsistency negative or not finite, min_views < 1, max_views < min_views, max_tracks < 0, an unknown policy, unknown
+ * flags, a struct_size that is not sizeof, null arrays where counts are positive.  n == 0 or no match: success with *nout = 0.
+ * On the device: one kernel expands moff into global endpoint ids, checks them and marks the touched features; hooking and pointer
+ * jumping on int32 labels (atomicMin), rounds enqueued four at a time, at most 1024 (XM_ERR_HIP beyond); one workgroup per image sorts
+ * the (label, feature) words of its touched features -- equal neighbours are the conflicts; integer atomics count rows and registered
+ * images per component; two prefix sums number the tracks and the rows; one kernel writes the rows.  No floating-point atomic, no atomic
+ * decides an order or a value: two calls, and any permutation of pairs, matches and orientations, give the same bits. */
+#define XM_TRACKS_DROP   0
+#define XM_TRACKS_GLOMAP 1
+#define XM_TRACKS_SPLIT  2
+#define XM_TRACK_UNTOUCHED      (-1)   /* label[]: the feature is in no match */
+#define XM_TRACK_SHORT          (-2)   /* fewer than min_views observations */
+#define XM_TRACK_LONG           (-3)   /* more than max_views observations */
+#define XM_TRACK_CONFLICT       (-4)   /* discarded by the conflict policy */
+#define XM_TRACK_FEW_REGISTERED (-5)   /* fewer than min_views distinct registered images */
+#define XM_TRACK_BEYOND_MAX     (-6)   /* not among the max_tracks + 1 longest */
+typedef struct {
+    uint32_t struct_size;
+    int32_t min_views;             /* 3 */
+    int32_t max_views;             /* 1000000 (5_test_ceres.py:127) */
+    int32_t conflict;              /* XM_TRACKS_SPLIT */
+    int64_t max_tracks;            /* 10000000 */
+    double thres_inconsistency;    /* 10.0 px; XM_TRACKS_GLOMAP only */
+    uint32_t flags;                /* none defined */
+    uint32_t reserved;
+} xm_tracks_options_t;
+#define XM_TRACKS_OPTIONS_INIT { (uint32_t)sizeof(xm_tracks_options_t), 3, 1000000, XM_TRACKS_SPLIT, 10000000, 10.0, 0u, 0u }
+typedef struct {
+    uint32_t struct_size;
+    int32_t rounds;                /* hooking rounds until the labels stood still */
+    int64_t ntracks;               /* kept tracks */
+    int64_t features_touched;
+    int64_t matches;               /* matches listed (duplicates included) */
+    int64_t components, components_conflicted;
+    int64_t rows_conflicted;       /* touched features in conflicted components */
+    int64_t tracks_short, tracks_long, tracks_conflict, tracks_few_registered, tracks_beyond_max;   /* by the first rule that dropped them */
+    int64_t images_small, images_large, images_workspace;   /* images with a touched feature, by the size of the kernel that sorted them */
+    int64_t max_touched;           /* most touched features of one image */
+    int64_t edges_split;           /* DISTINCT edges handed to the host splitter (XM_TRACKS_SPLIT) */
+    int64_t unions_refused;        /* ... of which it refused */
+    double seconds_index;          /* host: checks and upload */
+    double seconds_kernels;
+    double seconds_split;          /* XM_TRACKS_SPLIT: download of the conflicted edges, the host split, upload of the new labels */
+    double seconds_download;
+} xm_tracks_result_t;
+int xm_build_tracks(int64_t n, const int64_t *foff, const double *xy, const uint8_t *registered /* n or NULL */, int64_t npairs, const int32_t *pi,
+                    const int32_t *pj, const int64_t *moff, const int32_t *f1, const int32_t *f2, const xm_tracks_options_t *opt, int32_t *out_cam,
+                    int32_t *out_feat, int32_t *out_track, double *out_xy, int64_t *nout, int32_t *label /* F or NULL */, xm_tracks_result_t *res);
+/* out[0]: most touched features of an image that are sorted in LDS; out[1]: threads per workgroup; out[2]: workgroups of the workspace
+ * path; out[3]: most touched features of an image in the small LDS instantiation */
+int xm_tracks_limits(int64_t out[4]);
+/* Test export: rule 4's XM_TRACKS_SPLIT on the host, as xm_build_tracks runs it.  nedges edges eu[e], ev[e] (global feature indices, any
+ * order, duplicates allowed); label[F]: the smallest member of the set of every feature that is an endpoint, -1 for the others.  distinct,
+ * refused (or NULL): the distinct edges and the unions refused.  Needs no device. */
+int xm_tracks_split_host(int64_t n, const int64_t *foff, int64_t nedges, const int32_t *eu, const int32_t *ev, int32_t *label, int64_t *distinct,
+                         int64_t *refused);
 /* Translations and landmarks of a solution: the last step of utils/recoversolution.py:recover_XM (lines 77-86,
  * ybar_est = Abar @ sR_real.T; t_est = [0 | first N-1 columns], p_est = the rest) for an XM_STORAGE_SCHUR context.  The reference
  * needs the dense (N-1+M) x 3N matrix Abar.bin that create_matrix writes (creatematrix.py:283-311; 80 GB at Final-13682 with 800 k

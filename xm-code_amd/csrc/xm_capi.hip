@@ -11,6 +11,8 @@
 #include "xm_ba.h"
 #include "xm_clean.h"
 #include "xm_lift.h"
+#include "xm_tracks.h"
+#include "xm_tracks_split.h"
 #include "xm_pair.h"
 #include "xm_schur.h"
 #include "xm_sell.h"
@@ -724,6 +726,99 @@ int xm_lift_limits(int64_t out[4]) {
     XM_TRY
     if (!out) throw xm::Error(XM_ERR_ARG, "xm_lift_limits: null output");
     out[0] = xm::kLiftLdsRows; out[1] = xm::kLiftThreads; out[2] = xm::kLiftWsGroups; out[3] = xm::kLiftSmallRows;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_build_tracks(int64_t n, const int64_t *foff, const double *xy, const uint8_t *registered, int64_t npairs, const int32_t *pi, const int32_t *pj,
+                    const int64_t *moff, const int32_t *f1, const int32_t *f2, const xm_tracks_options_t *opt, int32_t *out_cam, int32_t *out_feat,
+                    int32_t *out_track, double *out_xy, int64_t *nout, int32_t *label, xm_tracks_result_t *res) {
+    XM_TRY
+    const std::string w("xm_build_tracks");
+    const int64_t lim = (int64_t)1 << 31;
+    if (!opt || !res || !nout) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (opt->struct_size != sizeof(xm_tracks_options_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_tracks_options_t.struct_size is not sizeof(xm_tracks_options_t)");
+    if (res->struct_size != sizeof(xm_tracks_result_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_tracks_result_t.struct_size is not sizeof(xm_tracks_result_t)");
+    if (opt->min_views < 1) throw xm::Error(XM_ERR_ARG, w + ": min_views below 1");
+    if (opt->max_views < opt->min_views) throw xm::Error(XM_ERR_ARG, w + ": max_views below min_views");
+    if (opt->max_tracks < 0) throw xm::Error(XM_ERR_ARG, w + ": negative max_tracks");
+    if (!(opt->thres_inconsistency >= 0.0) || !(opt->thres_inconsistency <= 1.7976931348623157e308))
+        throw xm::Error(XM_ERR_ARG, w + ": thres_inconsistency is negative or not finite");
+    if (opt->conflict != XM_TRACKS_DROP && opt->conflict != XM_TRACKS_GLOMAP && opt->conflict != XM_TRACKS_SPLIT)
+        throw xm::Error(XM_ERR_ARG, w + ": unknown conflict policy");
+    if (opt->flags) throw xm::Error(XM_ERR_ARG, w + ": unknown flag");
+    if (n < 0 || npairs < 0) throw xm::Error(XM_ERR_ARG, w + ": negative size");
+    if (n >= lim || npairs >= lim) throw xm::Error(XM_ERR_ARG, w + ": images and pairs must each stay below 2^31");
+    if (n > 0 && !foff) throw xm::Error(XM_ERR_ARG, w + ": null feature offsets");
+    if (npairs > 0 && (!pi || !pj || !moff)) throw xm::Error(XM_ERR_ARG, w + ": null pair arrays");
+    if (n > 0 && foff[0] != 0) throw xm::Error(XM_ERR_ARG, w + ": foff does not start at 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (foff[i + 1] < foff[i]) throw xm::Error(XM_ERR_ARG, w + ": foff decreases at image " + std::to_string(i));
+    const int64_t F = n > 0 ? foff[n] : 0;
+    if (F >= lim) throw xm::Error(XM_ERR_ARG, w + ": features must stay below 2^31");
+    if (npairs > 0 && moff[0] != 0) throw xm::Error(XM_ERR_ARG, w + ": moff does not start at 0");
+    for (int64_t k = 0; k < npairs; ++k) {
+        if (moff[k + 1] < moff[k]) throw xm::Error(XM_ERR_ARG, w + ": moff decreases at pair " + std::to_string(k));
+        if (pi[k] < 0 || pi[k] >= n || pj[k] < 0 || pj[k] >= n) throw xm::Error(XM_ERR_ARG, w + ": image index out of range at pair " + std::to_string(k));
+        if (pi[k] == pj[k]) throw xm::Error(XM_ERR_ARG, w + ": pair " + std::to_string(k) + " names one image twice");
+    }
+    const int64_t E = npairs > 0 ? moff[npairs] : 0;
+    if (E >= lim) throw xm::Error(XM_ERR_ARG, w + ": matches must stay below 2^31");
+    if (E > 0 && (!f1 || !f2)) throw xm::Error(XM_ERR_ARG, w + ": null match arrays");
+    if (F > 0 && (!xy || !out_cam || !out_feat || !out_track || !out_xy)) throw xm::Error(XM_ERR_ARG, w + ": null feature or output arrays");
+    xm::TracksSettings c;
+    c.min_views = opt->min_views; c.max_views = opt->max_views; c.conflict = opt->conflict; c.max_tracks = opt->max_tracks;
+    c.thres_inconsistency = opt->thres_inconsistency;
+    if (n > 0 && E > 0) require_device();
+    if (const char *e = std::getenv("XM_WATCHDOG_S")) { const double v = std::atof(e); if (v > 0) c.watchdog_s = v; }
+    xm::TracksOutcome r;
+    xm::build_tracks_host(n, foff, xy, registered, npairs, pi, pj, moff, f1, f2, c, out_cam, out_feat, out_track, out_xy, label, r);
+    xm_tracks_result_t out;
+    std::memset(&out, 0, sizeof(out));
+    out.struct_size = sizeof(xm_tracks_result_t);
+    out.rounds = r.rounds; out.ntracks = r.ntracks; out.features_touched = r.features_touched; out.matches = r.matches;
+    out.components = r.components; out.components_conflicted = r.components_conflicted; out.rows_conflicted = r.rows_conflicted;
+    out.tracks_short = r.tracks_short; out.tracks_long = r.tracks_long; out.tracks_conflict = r.tracks_conflict;
+    out.tracks_few_registered = r.tracks_few_registered; out.tracks_beyond_max = r.tracks_beyond_max;
+    out.images_small = r.images_small; out.images_large = r.images_large; out.images_workspace = r.images_workspace; out.max_touched = r.max_touched;
+    out.edges_split = r.edges_split; out.unions_refused = r.unions_refused;
+    out.seconds_index = r.seconds_index; out.seconds_kernels = r.seconds_kernels; out.seconds_split = r.seconds_split; out.seconds_download = r.seconds_download;
+    *nout = r.nout;
+    *res = out;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_tracks_limits(int64_t out[4]) {
+    XM_TRY
+    if (!out) throw xm::Error(XM_ERR_ARG, "xm_tracks_limits: null output");
+    out[0] = xm::kTracksLdsRows; out[1] = xm::kTracksThreads; out[2] = xm::kTracksWsGroups; out[3] = xm::kTracksSmallRows;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_tracks_split_host(int64_t n, const int64_t *foff, int64_t nedges, const int32_t *eu, const int32_t *ev, int32_t *label, int64_t *distinct,
+                         int64_t *refused) {
+    XM_TRY
+    const std::string w("xm_tracks_split_host");
+    if (n < 0 || nedges < 0) throw xm::Error(XM_ERR_ARG, w + ": negative size");
+    if (n > 0 && !foff) throw xm::Error(XM_ERR_ARG, w + ": null feature offsets");
+    if (n > 0 && foff[0] != 0) throw xm::Error(XM_ERR_ARG, w + ": foff does not start at 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (foff[i + 1] < foff[i]) throw xm::Error(XM_ERR_ARG, w + ": foff decreases at image " + std::to_string(i));
+    const int64_t F = n > 0 ? foff[n] : 0;
+    if (F >= ((int64_t)1 << 31)) throw xm::Error(XM_ERR_ARG, w + ": features must stay below 2^31");
+    if (nedges > 0 && (!eu || !ev)) throw xm::Error(XM_ERR_ARG, w + ": null edge arrays");
+    if (F > 0 && !label) throw xm::Error(XM_ERR_ARG, w + ": null label array");
+    std::vector<uint64_t> edges((size_t)nedges);
+    for (int64_t e = 0; e < nedges; ++e) {
+        if (eu[e] < 0 || eu[e] >= F || ev[e] < 0 || ev[e] >= F) throw xm::Error(XM_ERR_ARG, w + ": feature index out of range at edge " + std::to_string(e));
+        const uint32_t a = (uint32_t)std::min(eu[e], ev[e]), b = (uint32_t)std::max(eu[e], ev[e]);
+        edges[(size_t)e] = ((uint64_t)a << 32) | (uint64_t)b;
+    }
+    xm::TrackSplit sp;
+    xm::tracks_split(n, foff, edges, sp);
+    for (int64_t g = 0; g < F; ++g) label[g] = -1;
+    for (size_t v = 0; v < sp.feat.size(); ++v) label[sp.feat[v]] = sp.label[v];
+    if (distinct) *distinct = sp.distinct;
+    if (refused) *refused = sp.refused;
     return XM_OK;
     XM_CATCH
 }

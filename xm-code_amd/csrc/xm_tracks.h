@@ -1,0 +1,62 @@
+// xm_tracks.h — feature tracks from pairwise matches on the device (include/xm_amd.h: xm_build_tracks has the definition): the track
+// establishment of the reference's fork of GLOMAP (track_establishment.cc:19-227, union_find.h) as connected components of the match graph
+// plus an explicit policy for the components that hold two features of one image.
+//
+// Launches, all on the default stream and all deterministic in what they write:
+//   tracks_expand_kernel   one thread per match: the pair by binary search in moff, the two global feature ids (smaller first), the range
+//                          check of the feature indices (an index out of range is reported and never used as an address), touched marks
+//   tracks_feat_kernel     one thread per feature: its image by binary search in foff, label = itself, touched features per image
+//   tracks_hook_kernel /   FastSV hooking and pointer jumping on int32 labels as xm_clean.hip's (atomicMin; a component's final label is
+//   tracks_jump_kernel     its smallest member); kTracksBatch rounds are enqueued ahead of the host, which reads their "changed" words
+//   tracks_image_kernel    one workgroup of kTracksThreads per image: compacts (ballots) and sorts (xm_sortstat.h) the (label << 32 |
+//                          feature) words of its touched features; equal neighbouring labels are the image's conflicts: they set the
+//                          component's flag (atomicOr), count its duplicates in registered images (atomicAdd) and, under
+//                          XM_TRACKS_GLOMAP, run the distance test over the run.  Three sizes as xm_lift.hip: kTracksSmallRows words in
+//                          2 KB of LDS for every image, kTracksLdsRows in 32 KB for the images the host lists, a global workspace above
+//   tracks_size_kernel     rows and rows in registered images per component (integer atomicAdd)
+//   tracks_stats_kernel    components, conflicted components and their rows
+//   tracks_compact_kernel  XM_TRACKS_SPLIT: the edges of flagged components for the host splitter (xm_tracks_split.h).  Their order in
+//                          the list is arbitrary; the splitter sorts them first, so nothing depends on it
+//   tracks_relabel_kernel  the splitter's labels back into the label array
+//   tracks_decide_kernel   per component: kept, or the first rule that drops it
+//   tracks_scan_*          exclusive prefix sums (three launches, as xm_clean.hip's): track numbers over the labels, row offsets
+//   tracks_rows_kernel     label[] and the row flag of every feature
+//   tracks_emit_kernel     one thread per feature: a row at its offset
+#pragma once
+
+#include <cstdint>
+
+#include "../../include/xm_amd.h"
+#include "xm_solver.h"
+
+namespace xm {
+
+constexpr int kTracksThreads = 256;      // threads per workgroup (four wavefronts)
+constexpr int kTracksSmallRows = 256;    // most touched features of an image in the small instantiation
+constexpr int kTracksLdsRows = 4096;     // most touched features of an image that are sorted in LDS
+constexpr int kTracksWsGroups = 64;      // workgroups of the workspace path
+constexpr int kTracksMaxRounds = 1024;   // more hooking rounds than this: XM_ERR_HIP
+constexpr int kTracksBatch = 4;          // rounds enqueued between two looks at the changed words
+constexpr int kTracksScanTile = 1024;    // entries per workgroup of the prefix sums
+
+struct TracksSettings {
+    int32_t min_views = 3, max_views = 1000000, conflict = XM_TRACKS_SPLIT;
+    int64_t max_tracks = 10000000;
+    double thres_inconsistency = 10.0;
+    double watchdog_s = 600.0;           // host waits give up after this long
+};
+struct TracksOutcome {
+    int32_t rounds = 0;
+    int64_t nout = 0, ntracks = 0, features_touched = 0, matches = 0, components = 0, components_conflicted = 0, rows_conflicted = 0;
+    int64_t tracks_short = 0, tracks_long = 0, tracks_conflict = 0, tracks_few_registered = 0, tracks_beyond_max = 0;
+    int64_t images_small = 0, images_large = 0, images_workspace = 0, max_touched = 0, edges_split = 0, unions_refused = 0;
+    double seconds_index = 0.0, seconds_kernels = 0.0, seconds_split = 0.0, seconds_download = 0.0;
+};
+
+// host arrays.  Checks the offsets and the pairs on the host and the feature indices on the device (XM_ERR_ARG, nothing written), runs on
+// the default stream.  registered and label may be null.
+void build_tracks_host(int64_t n, const int64_t *foff, const double *xy, const uint8_t *registered, int64_t npairs, const int32_t *pi, const int32_t *pj,
+                       const int64_t *moff, const int32_t *f1, const int32_t *f2, const TracksSettings &cfg, int32_t *out_cam, int32_t *out_feat,
+                       int32_t *out_track, double *out_xy, int32_t *label, TracksOutcome &out);
+
+}  // namespace xm

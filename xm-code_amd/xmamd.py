@@ -40,6 +40,7 @@ EXPORTS = [
     "xm_ctx_dense_q", "xm_create_matrix", "xm_schur_dense_limits",
     "xm_pair_filter", "xm_pair_filter_limits",
     "xm_lift_observations", "xm_lift_limits",
+    "xm_build_tracks", "xm_tracks_limits", "xm_tracks_split_host",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -254,6 +255,25 @@ class LiftResult(C.Structure):     # xm_lift_result_t
                [(k, C.c_double) for k in ("seconds_index", "seconds_kernels", "seconds_download")]
 
 
+class TracksOptions(C.Structure):  # xm_tracks_options_t; the defaults are the pipeline's constants (XM_TRACKS_OPTIONS_INIT)
+    _fields_ = [("struct_size", C.c_uint32), ("min_views", C.c_int32), ("max_views", C.c_int32), ("conflict", C.c_int32), ("max_tracks", C.c_int64),
+                ("thres_inconsistency", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, min_views=3, max_views=1000000, conflict=2, max_tracks=10000000, thres_inconsistency=10.0, flags=0):
+        super().__init__(C.sizeof(TracksOptions), min_views, max_views, conflict, max_tracks, thres_inconsistency, flags, 0)
+
+
+class TracksResult(C.Structure):   # xm_tracks_result_t
+    _fields_ = [("struct_size", C.c_uint32), ("rounds", C.c_int32)] + \
+               [(k, C.c_int64) for k in ("ntracks", "features_touched", "matches", "components", "components_conflicted", "rows_conflicted",
+                                         "tracks_short", "tracks_long", "tracks_conflict", "tracks_few_registered", "tracks_beyond_max",
+                                         "images_small", "images_large", "images_workspace", "max_touched", "edges_split", "unions_refused")] + \
+               [(k, C.c_double) for k in ("seconds_index", "seconds_kernels", "seconds_split", "seconds_download")]
+
+
+TRACKS_DROP, TRACKS_GLOMAP, TRACKS_SPLIT = 0, 1, 2
+TRACKS_POLICIES = {"drop": TRACKS_DROP, "glomap": TRACKS_GLOMAP, "split": TRACKS_SPLIT}
+TRACK_UNTOUCHED, TRACK_SHORT, TRACK_LONG, TRACK_CONFLICT, TRACK_FEW_REGISTERED, TRACK_BEYOND_MAX = -1, -2, -3, -4, -5, -6
 LIFT_MAPS_ON_DEVICE = 1
 PAIR_STAT_DTYPE = np.dtype([("n_joint", "<i4"), ("n_kept", "<i4"), ("n_flagged", "<i4"), ("status", "<i4"), ("scale1", "<f8"), ("scale2", "<f8"),
                             ("translation", "<f8", (3,)), ("median", "<f8"), ("p95", "<f8"), ("percentage", "<f8")])
@@ -326,6 +346,10 @@ def lib():
         L.xm_lift_observations.argtypes = [C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7 + [C.POINTER(LiftOptions)] + [C.c_void_p] * 5 + \
                                           [C.POINTER(C.c_int64), C.c_void_p, C.POINTER(LiftResult)]
         L.xm_lift_limits.argtypes = [C.c_void_p]
+        L.xm_build_tracks.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(TracksOptions)] + \
+                                     [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.c_void_p, C.POINTER(TracksResult)]
+        L.xm_tracks_limits.argtypes = [C.c_void_p]
+        L.xm_tracks_split_host.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.xm_ctx_reprojection_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_transport.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
         L.xm_ctx_dense_q.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -876,6 +900,112 @@ def lift_observations(cam, lm, xy, depth, conf, K, n=None, m=None, margin=10, de
     k = nout.value
     info = {f: getattr(res, f) for f, _ in LiftResult._fields_ if f not in ("struct_size", "reserved")}
     return LiftPlan(ocam[:k].copy(), olm[:k].copy(), op[:k].copy(), ow[:k].copy(), orow[:k].copy(), thr, info, nr)
+
+
+class TrackTable:
+    """what build_tracks returns: one row per touched feature of a registered image in a kept track, image ascending, then feature
+    ascending: cam, feat (the index in the image), track (int32), xy (rows x 2, the input's bits); m, the number of tracks; label (per
+    global feature: its track or a negative TRACK_* code); info, the fields of xm_tracks_result_t; foff, the feature offsets.
+    lift_observations(t.cam, t.track, t.xy, depth, conf, K, n=n, m=t.m) takes it as it is"""
+
+    def __init__(self, cam, feat, track, xy, m, label, info, foff):
+        self.cam, self.feat, self.track, self.xy, self.m, self.label, self.info, self.foff = cam, feat, track, xy, m, label, info, foff
+
+    @property
+    def feature(self):
+        """the global feature index of every row"""
+        return self.foff[self.cam] + self.feat
+
+    def carry(self, *per_feature_arrays):
+        """the rows of every array given (colours, descriptors, ...; one entry per global feature) that belong to the table's rows"""
+        out = []
+        g = self.feature
+        for a in per_feature_arrays:
+            a = np.asarray(a)
+            if a.shape[:1] != (int(self.foff[-1]),):
+                raise XmError("TrackTable.carry: a per-feature array has another length than the feature list")
+            out.append(a[g])
+        return tuple(out)
+
+
+def tracks_limits():
+    """-> dict(lds_rows: most touched features of an image that are sorted in LDS (larger images take the workspace path), threads: per
+    workgroup, workspace_groups: workgroups of the workspace path, small_rows: most touched features of an image in the small LDS instantiation)"""
+    out = np.zeros(4, dtype=np.int64)
+    _chk(lib().xm_tracks_limits(out.ctypes.data_as(C.c_void_p)))
+    return dict(lds_rows=int(out[0]), threads=int(out[1]), workspace_groups=int(out[2]), small_rows=int(out[3]))
+
+
+def _tracks_foff(foff_or_counts, nfeat):
+    """feature offsets from either the offsets themselves (n + 1 entries, the last one the number of features) or the counts per image"""
+    a = np.ascontiguousarray(foff_or_counts, dtype=np.int64).reshape(-1)
+    if a.size and a[0] == 0 and a[-1] == nfeat and np.all(np.diff(a) >= 0):   # (an array that reads both ways, as [0, 0, 5] does, is the offsets)
+        return a
+    if int(a.sum()) != nfeat:
+        raise XmError("build_tracks: foff_or_counts is neither the offsets (n + 1 entries ending in the number of features) nor the counts per image")
+    return np.concatenate([[0], np.cumsum(a)]).astype(np.int64)
+
+
+def _tracks_matches(matches, npairs):
+    if isinstance(matches, tuple) and len(matches) == 3:
+        moff, f1, f2 = (np.ascontiguousarray(matches[0], dtype=np.int64).reshape(-1), np.ascontiguousarray(matches[1], dtype=np.int32).reshape(-1),
+                        np.ascontiguousarray(matches[2], dtype=np.int32).reshape(-1))
+    else:
+        per = [np.asarray(x, dtype=np.int32).reshape(-1, 2) for x in matches]
+        moff = np.concatenate([[0], np.cumsum([x.shape[0] for x in per])]).astype(np.int64)
+        cat = np.concatenate(per, axis=0) if per else np.zeros((0, 2), dtype=np.int32)
+        f1, f2 = np.ascontiguousarray(cat[:, 0]), np.ascontiguousarray(cat[:, 1])
+    if moff.size != npairs + 1 or f1.size != f2.size or (moff.size and int(moff[-1]) != f1.size):
+        raise XmError("build_tracks: matches must be (moff, f1, f2) with npairs + 1 offsets ending in the number of matches, or one (k, 2) array per pair")
+    return moff, f1, f2
+
+
+def build_tracks(foff_or_counts, xy, pi, pj, matches, registered=None, min_views=3, max_views=1000000, max_tracks=10000000,
+                 thres_inconsistency=10.0, conflict="split"):
+    """feature tracks from pairwise matches on the device (xm_build_tracks; include/xm_amd.h has the definition and where it departs from
+    the reference's fork of GLOMAP): foff_or_counts: the feature offsets (n + 1) or the feature counts (n) of the images; xy: features x 2;
+    pi, pj: the images of every pair, 0-based; matches: (moff, f1, f2) or one (k, 2) array of feature indices per pair; registered: per
+    image or None; conflict: "drop", "glomap" or "split".  -> TrackTable"""
+    xy = np.ascontiguousarray(xy, dtype=np.float64)
+    if xy.ndim != 2 or xy.shape[1] != 2:
+        raise XmError("build_tracks: xy must be features x 2")
+    foff = _tracks_foff(foff_or_counts, xy.shape[0])
+    n = foff.size - 1
+    pi = np.ascontiguousarray(pi, dtype=np.int32).reshape(-1); pj = np.ascontiguousarray(pj, dtype=np.int32).reshape(-1)
+    if pi.size != pj.size:
+        raise XmError("build_tracks: pi and pj must have one entry per pair")
+    moff, f1, f2 = _tracks_matches(matches, pi.size)
+    reg = None
+    if registered is not None:
+        reg = np.ascontiguousarray(np.asarray(registered) != 0, dtype=np.uint8).reshape(-1)
+        if reg.size != n:
+            raise XmError("build_tracks: registered must have one entry per image")
+    if isinstance(conflict, str) and conflict not in TRACKS_POLICIES:
+        raise XmError(f"build_tracks: conflict must be one of {sorted(TRACKS_POLICIES)} (or an XM_TRACKS_* number)")
+    opt = TracksOptions(int(min_views), int(max_views), int(TRACKS_POLICIES.get(conflict, conflict)), int(max_tracks), float(thres_inconsistency))
+    res = TracksResult(); res.struct_size = C.sizeof(TracksResult)
+    F = xy.shape[0]
+    ocam = np.zeros(F, dtype=np.int32); ofeat = np.zeros(F, dtype=np.int32); otrack = np.zeros(F, dtype=np.int32); oxy = np.zeros((F, 2))
+    label = np.full(F, TRACK_UNTOUCHED, dtype=np.int32); nout = C.c_int64(0)
+    P = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    _chk(lib().xm_build_tracks(n, P(foff), P(xy), P(reg), pi.size, P(pi), P(pj), P(moff), P(f1), P(f2), C.byref(opt), P(ocam), P(ofeat), P(otrack),
+                               P(oxy), C.byref(nout), P(label), C.byref(res)))
+    k = nout.value
+    info = {f: getattr(res, f) for f, _ in TracksResult._fields_ if f != "struct_size"}
+    return TrackTable(ocam[:k].copy(), ofeat[:k].copy(), otrack[:k].copy(), oxy[:k].copy(), int(res.ntracks), label, info, foff)
+
+
+def split_host(foff_or_counts, nfeat, eu, ev):
+    """the test export xm_tracks_split_host: rule 4's XM_TRACKS_SPLIT over the edges (eu, ev) of global feature indices, on the host.
+    -> (label per feature: the smallest member of its set, -1 for a feature in no edge; distinct edges; unions refused)"""
+    foff = _tracks_foff(foff_or_counts, int(nfeat))
+    eu = np.ascontiguousarray(eu, dtype=np.int32).reshape(-1); ev = np.ascontiguousarray(ev, dtype=np.int32).reshape(-1)
+    if eu.size != ev.size:
+        raise XmError("split_host: eu and ev must have one entry per edge")
+    label = np.full(int(nfeat), -1, dtype=np.int32); d = C.c_int64(0); r = C.c_int64(0)
+    P = lambda a: a.ctypes.data_as(C.c_void_p)
+    _chk(lib().xm_tracks_split_host(foff.size - 1, P(foff), eu.size, P(eu), P(ev), P(label), C.byref(d), C.byref(r)))
+    return label, d.value, r.value
 
 
 def symw_plan(ntot, nloc, cam0, K=0):
