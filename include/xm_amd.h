@@ -622,6 +622,123 @@ int xm_tracks_limits(int64_t out[4]);
  * refused (or NULL): the distinct edges and the unions refused.  Needs no device. */
 int xm_tracks_split_host(int64_t n, const int64_t *foff, int64_t nedges, const int32_t *eu, const int32_t *ev, int32_t *label, int64_t *distinct,
                          int64_t *refused);
+/* ---- Two-view match verification and view-graph pruning, on the device: the stage that produces what xm_build_tracks reads (the inlier
+ * matches of the valid pairs, and `registered`) and the pair list xm_pair_filter reads.  It stands for the block in front of track
+ * establishment in the reference's fork of GLOMAP, deps/glomap/glomap/controllers/global_mapper.cc:56-111: ImagePairsInlierCount
+ * (processors/image_pair_inliers.cc), FilterInlierNum / FilterInlierRatio / FilterRotations (processors/relpose_filter.cc),
+ * KeepLargestConnectedComponents (scene/view_graph.cc:9-46).  NOTHING HERE WAS COMPARED WITH THE REFERENCE'S COMPILED CODE (it needs
+ * COLMAP, Eigen and glog): parity rests on a line-cited sequential restatement in plain Python loops (tests/xm_viewgraph_numpy.py,
+ * restatement (a)) which the vectorised contract (run_numpy, restatement (b)) equals exactly.  Needs no context; host arrays in, host
+ * arrays out.  A pipeline calls it twice: pass A (XM_VG_SCORE, rot = NULL) scores, applies the number and ratio rules and prunes; pass B
+ * (no flag, rot given, fed with pass A's compacted matches, its pair validity and its registered_out) applies the rotation rule after a
+ * view-graph solve and prunes again.  Pass B's f1_out / f2_out / moff_out and registered_out go into xm_build_tracks as they are.
+ * Input: n images; foff[n + 1] and xy (2 doubles per feature, pixels) as xm_build_tracks; focal[n]; Kinv: 9 per image, row-major (nothing
+ * is inverted here); bearing: 3 doubles per feature or NULL -- if given it replaces rule 0 (cameras with distortion); npairs pairs pi, pj;
+ * model[npairs]: XM_VG_MODEL_*, the caller maps COLMAP's configuration (image_pair_inliers.cc:7-18: CALIBRATED -> E, UNCALIBRATED -> F,
+ * PLANAR / PANORAMIC / PLANAR_OR_PANORAMIC -> H, anything else -> NONE); Rrel: 9 per pair, row-major, the rotation of cam2_from_cam1;
+ * trel: 3 per pair, used as given (GLOMAP keeps it at unit length); FH: 9 per pair, row-major, F of an F pair and H of an H pair (NULL only
+ * if no pair is F or H); valid_in[npairs] or NULL (all valid); registered_in[n] or NULL (all registered); rot: 9 per image, row-major,
+ * cam_from_world, or NULL (rule 6 is off); moff[npairs + 1], f1, f2 as xm_build_tracks.
+ * Every product and every sum is rounded on its own (no fused multiply-add); a sum of three runs left to right, dot(a, b) =
+ * (a0*b0 + a1*b1) + a2*b2; division and square root are IEEE.  A NaN makes every comparison false.
+ *   0. Bearing (image_undistorter.cc:33-36; only without `bearing`, only E pairs read it): h_r = (K_r0*x + K_r1*y) + K_r2 over the rows of
+ *      Kinv, b = h / sqrt((h0*h0 + h1*h1) + h2*h2), component by component.
+ *   1. With XM_VG_SCORE a pair that is invalid at input gets no inliers and is not scored (image_pair_inliers.cc:205-212); a NONE pair
+ *      gets none (:17).  Without the flag every listed match of a valid pair is an inlier, and a pair invalid at input has none.
+ *   2. E pairs (:20-92).  E = [t]x R (two_view_geometry.cc:41-45): E_0c = t1*R_2c - t2*R_1c, E_1c = t2*R_0c - t0*R_2c, E_2c = t0*R_1c -
+ *      t1*R_0c.  thr = (max_epipolar_error_E*0.5)*(1/focal_i + 1/focal_j), sq = thr*thr.  Sampson error (:71-83): Ex1_r = dot(E_r, x1) /
+ *      (XM_VG_EPS + x1_2), Etx2_r = dot(E column r, x2) / (XM_VG_EPS + x2_2), C = dot(Ex1, x2), r2 = (C*C) / ((Ex1_0*Ex1_0 + Ex1_1*Ex1_1) +
+ *      (Etx2_0*Etx2_0 + Etx2_1*Etx2_1)).  CheckCheirality (:5-29): Rx1_r = dot(R_r, x1), a = -dot(Rx1, x2), b1 = -dot(Rx1, t), b2 =
+ *      dot(x2, t), l1 = b1 - a*b2, l2 = (-a)*b1 + b2, f = 1 - a*a; it holds when l1 and l2 are > XM_VG_MIN_DEPTH*f and < XM_VG_MAX_DEPTH*f.
+ *      e12 = t, e21_r = -dot(R column r, t), each negated when its z is negative (:26-31).  A match is an inlier when r2 < sq, the
+ *      cheirality holds, dot(x1, R^T x2) < XM_VG_COS_PARALLEL with (R^T x2)_r = dot(R column r, x2), dot(x1, e21) < XM_VG_COS_EPIPOLE and
+ *      dot(x2, e12) < XM_VG_COS_EPIPOLE.  The reference rotates by the pose's quaternion; here the rotation is the matrix Rrel.
+ *   3. F pairs (:94-164), on the pixels.  The epipole is F.row(0) x F.row(2) with cross(a, b) = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 -
+ *      a1*b0); if no component is > XM_VG_EPS or < -XM_VG_EPS it is F.row(1) x F.row(2).  Fx1_r = (F_r0*x1 + F_r1*y1) + F_r2, Ftx2_r =
+ *      (F_0r*x2 + F_1r*y2) + F_2r, C = (Fx1_0*x2 + Fx1_1*y2) + Fx1_2, r2 = (C*C) / ((Fx1_0^2 + Fx1_1^2) + (Ftx2_0^2 + Ftx2_1^2)) (:57-69);
+ *      pre-inliers have r2 < maxF*maxF.  Signum (:32-39): ((F_00*x2 + F_10*y2) + F_20) * (ep_1 - ep_2*y1), positive when > 0.  Equal
+ *      positive and negative counts over the pre-inliers (zero included): no inliers.  Otherwise the pre-inliers of the majority side.
+ *   4. H pairs (:166-198): Hx_r = (H_r0*x1 + H_r1*y1) + H_r2, d = XM_VG_EPS + Hx_2, u = Hx_0/d - x2, v = Hx_1/d - y2, u*u + v*v < maxH*maxH.
+ *   5. With XM_VG_SCORE (relpose_filter.cc:35-65): a valid pair with inliers < min_inlier_num becomes invalid (XM_VG_FEW_INLIERS); then a
+ *      valid pair with inliers / (double)matches < min_inlier_ratio becomes invalid (XM_VG_LOW_RATIO).  No matches: NaN, false, as there.
+ *   6. With rot (relpose_filter.cc:7-33, rigid3d.cc:7-15), for valid pairs with both images in registered_in: M_ab = dot(rot_j row a,
+ *      rot_i row b); s = the sum of M_ab*Rrel_ab in row-major order, starting from the first product; c = (s - 1)/2, set to 1 when > 1 and
+ *      to -1 when < -1; the pair becomes invalid (XM_VG_ROTATION) when c < cos_max_rotation_error.  ON PURPOSE the test is on the cosine and
+ *      from matrices: the reference takes acos of a quaternion product and compares degrees; the two differ only within the rounding of acos
+ *      at the boundary.
+ *   7. Largest component (view_graph.cc:9-46): the connected components of the images over the valid pairs; an image without a valid pair
+ *      forms none.  The largest wins, ties go to the component with the smallest image index (the reference's tie is hash order).
+ *      registered_out is membership in it; every valid pair with an unregistered end becomes invalid (XM_VG_OUTSIDE).  With no valid pair
+ *      the call succeeds with nothing registered and largest = 0 (the reference gives up there).
+ *   8. Output: inlier[e] (rules 1-4); pair_inliers[k]; pair_status[k], the first rule that dropped the pair; registered_out[n]; moff_out
+ *      [npairs + 1], f1_out, f2_out (capacity: the input's matches): the inliers of the pairs still valid, in input order.
+ * XM_ERR_ARG, nothing written, everything but the feature indices checked on the host before any device call: an image or feature index
+ * out of range (feature indices are checked on the device and never used as an address when out of range), pi[k] == pj[k], foff or moff
+ * not starting at 0 or decreasing, n, npairs, features or matches >= 2^31, an unknown model or flag, an F or H pair with FH == NULL, an E
+ * pair that is scored with neither Kinv nor bearing (or without focal), a negative or non-finite threshold, a negative min_inlier_num, a
+ * struct_size that is not sizeof, a null array where its count is positive.
+ * On the device: one kernel computes the bearings of the images E pairs touch; the scoring holds a pair's geometry in registers and
+ * streams its matches through a wavefront (pairs up to xm_view_graph_limits()[2] matches), a workgroup (up to [0]) or, above, workgroups
+ * over chunks of [0] matches whose counts meet in a workspace -- the F majority is known before the second sweep in every form; one
+ * kernel applies rules 5 and 6; hooking and pointer jumping on int32 image labels, rounds enqueued four at a time, at most 1024
+ * (XM_ERR_HIP beyond); integer atomics count the component sizes, one reduction takes the arg-max; a three-launch exclusive scan gives
+ * moff_out and one kernel writes the kept inliers through ballot prefixes.  No floating-point atomic, no atomic decides an order or a
+ * value: two calls give the same bits, and a permutation of the pairs permutes the per-pair outputs. */
+#define XM_VG_SCORE 1u                 /* flags: score the matches and apply rule 5 (pass A) */
+#define XM_VG_MODEL_NONE 0
+#define XM_VG_MODEL_E    1
+#define XM_VG_MODEL_F    2
+#define XM_VG_MODEL_H    3
+#define XM_VG_VALID       0            /* pair_status[] */
+#define XM_VG_INVALID_IN  1
+#define XM_VG_FEW_INLIERS 2
+#define XM_VG_LOW_RATIO   3
+#define XM_VG_ROTATION    4
+#define XM_VG_OUTSIDE     5
+/* the constants the reference hard-codes, as 17-digit literals */
+#define XM_VG_EPS          9.9999999999999998e-13   /* glomap/types.h: EPS = 1e-12 */
+#define XM_VG_MIN_DEPTH    1.0000000000000000e-02   /* image_pair_inliers.cc:65 */
+#define XM_VG_MAX_DEPTH    1.0000000000000000e+02
+#define XM_VG_COS_EPIPOLE  9.9863053475457386e-01   /* cos(3 deg) + 1e-6 (:54, :57) */
+#define XM_VG_COS_PARALLEL 1.0000009999999999e+00   /* 1 + 1e-6 (:55-56) */
+#define XM_VG_COS_10DEG    9.8480775301220802e-01   /* the default of cos_max_rotation_error: max_rotation_error = 10 degrees */
+typedef struct {
+    uint32_t struct_size;
+    uint32_t flags;                    /* XM_VG_SCORE */
+    double max_epipolar_error_E;       /* 1 (glomap/types.h:18-33) */
+    double max_epipolar_error_F;       /* 4 */
+    double max_epipolar_error_H;       /* 4 */
+    int32_t min_inlier_num;            /* 30 */
+    int32_t reserved;
+    double min_inlier_ratio;           /* 0.25 */
+    double cos_max_rotation_error;     /* XM_VG_COS_10DEG */
+} xm_vg_options_t;
+#define XM_VG_OPTIONS_INIT { (uint32_t)sizeof(xm_vg_options_t), XM_VG_SCORE, 1.0, 4.0, 4.0, 30, 0, 0.25, XM_VG_COS_10DEG }
+typedef struct {
+    uint32_t struct_size;
+    int32_t rounds;                    /* hooking rounds until the labels stood still */
+    int64_t matches;                   /* matches listed */
+    int64_t inliers;                   /* ... that are inliers (rules 1-4) */
+    int64_t matches_out;               /* ... that are written to f1_out / f2_out */
+    int64_t pairs_valid, pairs_invalid_in, pairs_few_inliers, pairs_low_ratio, pairs_rotation, pairs_outside;   /* by pair_status */
+    int64_t pairs_none, pairs_E, pairs_F, pairs_H;   /* listed pairs by model */
+    int64_t largest;                   /* images in the largest component */
+    int64_t components;
+    int64_t pairs_wave, pairs_group, pairs_workspace;   /* pairs with a match, by the form of the kernels that ran them */
+    int64_t max_matches;               /* most matches of one pair */
+    double seconds_index;              /* host: checks and upload */
+    double seconds_kernels;
+    double seconds_download;
+} xm_vg_result_t;
+int xm_view_graph_filter(int64_t n, const int64_t *foff, const double *xy, const double *focal, const double *Kinv,
+                         const double *bearing /* 3 per feature or NULL */, int64_t npairs, const int32_t *pi, const int32_t *pj,
+                         const int32_t *model, const double *Rrel, const double *trel, const double *FH, const uint8_t *valid_in /* or NULL */,
+                         const uint8_t *registered_in /* or NULL */, const double *rot /* 9 per image or NULL */, const int64_t *moff,
+                         const int32_t *f1, const int32_t *f2, const xm_vg_options_t *opt, uint8_t *inlier, int32_t *pair_inliers,
+                         int32_t *pair_status, uint8_t *registered_out, int64_t *moff_out, int32_t *f1_out, int32_t *f2_out, xm_vg_result_t *res);
+/* out[0]: most matches of a pair that one workgroup runs (and the chunk of the workspace form above it); out[1]: threads per workgroup;
+ * out[2]: most matches of a pair that one wavefront runs; out[3]: most hooking rounds */
+int xm_view_graph_limits(int64_t out[4]);
 /* Translations and landmarks of a solution: the last step of utils/recoversolution.py:recover_XM (lines 77-86,
  * ybar_est = Abar @ sR_real.T; t_est = [0 | first N-1 columns], p_est = the rest) for an XM_STORAGE_SCHUR context.  The reference
  * needs the dense (N-1+M) x 3N matrix Abar.bin that create_matrix writes (creatematrix.py:283-311; 80 GB at Final-13682 with 800 k

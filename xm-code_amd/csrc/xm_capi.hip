@@ -13,6 +13,7 @@
 #include "xm_lift.h"
 #include "xm_tracks.h"
 #include "xm_tracks_split.h"
+#include "xm_viewgraph.h"
 #include "xm_pair.h"
 #include "xm_schur.h"
 #include "xm_sell.h"
@@ -819,6 +820,85 @@ int xm_tracks_split_host(int64_t n, const int64_t *foff, int64_t nedges, const i
     for (size_t v = 0; v < sp.feat.size(); ++v) label[sp.feat[v]] = sp.label[v];
     if (distinct) *distinct = sp.distinct;
     if (refused) *refused = sp.refused;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_view_graph_filter(int64_t n, const int64_t *foff, const double *xy, const double *focal, const double *Kinv, const double *bearing, int64_t npairs,
+                         const int32_t *pi, const int32_t *pj, const int32_t *model, const double *Rrel, const double *trel, const double *FH,
+                         const uint8_t *valid_in, const uint8_t *registered_in, const double *rot, const int64_t *moff, const int32_t *f1, const int32_t *f2,
+                         const xm_vg_options_t *opt, uint8_t *inlier, int32_t *pair_inliers, int32_t *pair_status, uint8_t *registered_out, int64_t *moff_out,
+                         int32_t *f1_out, int32_t *f2_out, xm_vg_result_t *res) {
+    XM_TRY
+    const std::string w("xm_view_graph_filter");
+    const int64_t lim = (int64_t)1 << 31;
+    const double dmax = 1.7976931348623157e308;
+    if (!opt || !res) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (opt->struct_size != sizeof(xm_vg_options_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_vg_options_t.struct_size is not sizeof(xm_vg_options_t)");
+    if (res->struct_size != sizeof(xm_vg_result_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_vg_result_t.struct_size is not sizeof(xm_vg_result_t)");
+    if (opt->flags & ~XM_VG_SCORE) throw xm::Error(XM_ERR_ARG, w + ": unknown flag");
+    const double thr[5] = {opt->max_epipolar_error_E, opt->max_epipolar_error_F, opt->max_epipolar_error_H, opt->min_inlier_ratio, opt->cos_max_rotation_error};
+    const char *thr_name[5] = {"max_epipolar_error_E", "max_epipolar_error_F", "max_epipolar_error_H", "min_inlier_ratio", "cos_max_rotation_error"};
+    for (int x = 0; x < 5; ++x) {
+        const double lo = x == 4 ? -dmax : 0.0;   // (a cosine may be negative)
+        if (!(thr[x] >= lo) || !(thr[x] <= dmax)) throw xm::Error(XM_ERR_ARG, w + ": " + thr_name[x] + " is negative or not finite");
+    }
+    if (opt->min_inlier_num < 0) throw xm::Error(XM_ERR_ARG, w + ": negative min_inlier_num");
+    if (n < 0 || npairs < 0) throw xm::Error(XM_ERR_ARG, w + ": negative size");
+    if (n >= lim || npairs >= lim) throw xm::Error(XM_ERR_ARG, w + ": images and pairs must each stay below 2^31");
+    if (n > 0 && (!foff || !registered_out)) throw xm::Error(XM_ERR_ARG, w + ": null feature offsets or registered_out");
+    if (npairs > 0 && (!pi || !pj || !model || !moff || !pair_inliers || !pair_status || !moff_out)) throw xm::Error(XM_ERR_ARG, w + ": null pair arrays");
+    if (n > 0 && foff[0] != 0) throw xm::Error(XM_ERR_ARG, w + ": foff does not start at 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (foff[i + 1] < foff[i]) throw xm::Error(XM_ERR_ARG, w + ": foff decreases at image " + std::to_string(i));
+    const int64_t F = n > 0 ? foff[n] : 0;
+    if (F >= lim) throw xm::Error(XM_ERR_ARG, w + ": features must stay below 2^31");
+    if (npairs > 0 && moff[0] != 0) throw xm::Error(XM_ERR_ARG, w + ": moff does not start at 0");
+    const bool score = (opt->flags & XM_VG_SCORE) != 0;
+    bool any_E = false;
+    for (int64_t k = 0; k < npairs; ++k) {
+        if (moff[k + 1] < moff[k]) throw xm::Error(XM_ERR_ARG, w + ": moff decreases at pair " + std::to_string(k));
+        if (pi[k] < 0 || pi[k] >= n || pj[k] < 0 || pj[k] >= n) throw xm::Error(XM_ERR_ARG, w + ": image index out of range at pair " + std::to_string(k));
+        if (pi[k] == pj[k]) throw xm::Error(XM_ERR_ARG, w + ": pair " + std::to_string(k) + " names one image twice");
+        if (model[k] < XM_VG_MODEL_NONE || model[k] > XM_VG_MODEL_H) throw xm::Error(XM_ERR_ARG, w + ": unknown model at pair " + std::to_string(k));
+        if ((model[k] == XM_VG_MODEL_F || model[k] == XM_VG_MODEL_H) && !FH)
+            throw xm::Error(XM_ERR_ARG, w + ": pair " + std::to_string(k) + " is an F or H pair and FH is null");
+        if (model[k] == XM_VG_MODEL_E && score && (!valid_in || valid_in[k])) any_E = true;
+    }
+    if (any_E && ((!Kinv && !bearing) || !focal || !Rrel || !trel))
+        throw xm::Error(XM_ERR_ARG, w + ": an E pair is scored and Kinv and bearing are both null, or focal, Rrel or trel is null");
+    if (rot && npairs > 0 && !Rrel) throw xm::Error(XM_ERR_ARG, w + ": rot is given and Rrel is null");
+    const int64_t E = npairs > 0 ? moff[npairs] : 0;
+    if (E >= lim) throw xm::Error(XM_ERR_ARG, w + ": matches must stay below 2^31");
+    if (E > 0 && (!f1 || !f2 || !inlier || !f1_out || !f2_out)) throw xm::Error(XM_ERR_ARG, w + ": null match arrays");
+    if (F > 0 && !xy) throw xm::Error(XM_ERR_ARG, w + ": null feature positions");
+    xm::VgSettings c;
+    c.score = score; c.max_E = opt->max_epipolar_error_E; c.max_F = opt->max_epipolar_error_F; c.max_H = opt->max_epipolar_error_H;
+    c.min_inlier_num = opt->min_inlier_num; c.min_inlier_ratio = opt->min_inlier_ratio; c.cos_max_rotation_error = opt->cos_max_rotation_error;
+    if (npairs > 0) require_device();
+    if (const char *e = std::getenv("XM_WATCHDOG_S")) { const double v = std::atof(e); if (v > 0) c.watchdog_s = v; }
+    xm::VgOutcome r;
+    xm::view_graph_filter_host(n, foff, xy, focal, Kinv, bearing, npairs, pi, pj, model, Rrel, trel, FH, valid_in, registered_in, rot, moff, f1, f2, c, inlier,
+                               pair_inliers, pair_status, registered_out, moff_out, f1_out, f2_out, r);
+    xm_vg_result_t out;
+    std::memset(&out, 0, sizeof(out));
+    out.struct_size = sizeof(xm_vg_result_t);
+    out.rounds = r.rounds; out.matches = r.matches; out.inliers = r.inliers; out.matches_out = r.matches_out;
+    out.pairs_valid = r.pairs_by_status[XM_VG_VALID]; out.pairs_invalid_in = r.pairs_by_status[XM_VG_INVALID_IN];
+    out.pairs_few_inliers = r.pairs_by_status[XM_VG_FEW_INLIERS]; out.pairs_low_ratio = r.pairs_by_status[XM_VG_LOW_RATIO];
+    out.pairs_rotation = r.pairs_by_status[XM_VG_ROTATION]; out.pairs_outside = r.pairs_by_status[XM_VG_OUTSIDE];
+    out.pairs_none = r.pairs_by_model[XM_VG_MODEL_NONE]; out.pairs_E = r.pairs_by_model[XM_VG_MODEL_E]; out.pairs_F = r.pairs_by_model[XM_VG_MODEL_F];
+    out.pairs_H = r.pairs_by_model[XM_VG_MODEL_H];
+    out.largest = r.largest; out.components = r.components; out.pairs_wave = r.pairs_wave; out.pairs_group = r.pairs_group;
+    out.pairs_workspace = r.pairs_workspace; out.max_matches = r.max_matches;
+    out.seconds_index = r.seconds_index; out.seconds_kernels = r.seconds_kernels; out.seconds_download = r.seconds_download;
+    *res = out;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_view_graph_limits(int64_t out[4]) {
+    XM_TRY
+    if (!out) throw xm::Error(XM_ERR_ARG, "xm_view_graph_limits: null output");
+    out[0] = xm::kVgGroupMatches; out[1] = xm::kVgThreads; out[2] = xm::kVgWaveMatches; out[3] = xm::kVgMaxRounds;
     return XM_OK;
     XM_CATCH
 }

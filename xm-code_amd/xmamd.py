@@ -40,7 +40,7 @@ EXPORTS = [
     "xm_ctx_dense_q", "xm_create_matrix", "xm_schur_dense_limits",
     "xm_pair_filter", "xm_pair_filter_limits",
     "xm_lift_observations", "xm_lift_limits",
-    "xm_build_tracks", "xm_tracks_limits", "xm_tracks_split_host",
+    "xm_build_tracks", "xm_tracks_limits", "xm_tracks_split_host", "xm_view_graph_filter", "xm_view_graph_limits",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -271,6 +271,29 @@ class TracksResult(C.Structure):   # xm_tracks_result_t
                [(k, C.c_double) for k in ("seconds_index", "seconds_kernels", "seconds_split", "seconds_download")]
 
 
+class VgOptions(C.Structure):      # xm_vg_options_t; the defaults are those of glomap/types.h:18-33 (XM_VG_OPTIONS_INIT)
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("max_epipolar_error_E", C.c_double), ("max_epipolar_error_F", C.c_double),
+                ("max_epipolar_error_H", C.c_double), ("min_inlier_num", C.c_int32), ("reserved", C.c_int32), ("min_inlier_ratio", C.c_double),
+                ("cos_max_rotation_error", C.c_double)]
+
+    def __init__(self, flags=1, max_epipolar_error_E=1.0, max_epipolar_error_F=4.0, max_epipolar_error_H=4.0, min_inlier_num=30, min_inlier_ratio=0.25,
+                 cos_max_rotation_error=9.8480775301220802e-01):
+        super().__init__(C.sizeof(VgOptions), flags, max_epipolar_error_E, max_epipolar_error_F, max_epipolar_error_H, min_inlier_num, 0, min_inlier_ratio,
+                         cos_max_rotation_error)
+
+
+class VgResult(C.Structure):       # xm_vg_result_t
+    _fields_ = [("struct_size", C.c_uint32), ("rounds", C.c_int32)] + \
+               [(k, C.c_int64) for k in ("matches", "inliers", "matches_out", "pairs_valid", "pairs_invalid_in", "pairs_few_inliers", "pairs_low_ratio",
+                                         "pairs_rotation", "pairs_outside", "pairs_none", "pairs_E", "pairs_F", "pairs_H", "largest", "components",
+                                         "pairs_wave", "pairs_group", "pairs_workspace", "max_matches")] + \
+               [(k, C.c_double) for k in ("seconds_index", "seconds_kernels", "seconds_download")]
+
+
+VG_SCORE = 1
+VG_MODEL_NONE, VG_MODEL_E, VG_MODEL_F, VG_MODEL_H = 0, 1, 2, 3
+VG_MODELS = {"none": VG_MODEL_NONE, "E": VG_MODEL_E, "F": VG_MODEL_F, "H": VG_MODEL_H}
+VG_VALID, VG_INVALID_IN, VG_FEW_INLIERS, VG_LOW_RATIO, VG_ROTATION, VG_OUTSIDE = 0, 1, 2, 3, 4, 5
 TRACKS_DROP, TRACKS_GLOMAP, TRACKS_SPLIT = 0, 1, 2
 TRACKS_POLICIES = {"drop": TRACKS_DROP, "glomap": TRACKS_GLOMAP, "split": TRACKS_SPLIT}
 TRACK_UNTOUCHED, TRACK_SHORT, TRACK_LONG, TRACK_CONFLICT, TRACK_FEW_REGISTERED, TRACK_BEYOND_MAX = -1, -2, -3, -4, -5, -6
@@ -349,6 +372,9 @@ def lib():
         L.xm_build_tracks.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(TracksOptions)] + \
                                      [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.c_void_p, C.POINTER(TracksResult)]
         L.xm_tracks_limits.argtypes = [C.c_void_p]
+        L.xm_view_graph_filter.argtypes = [C.c_int64] + [C.c_void_p] * 5 + [C.c_int64] + [C.c_void_p] * 12 + [C.POINTER(VgOptions)] + [C.c_void_p] * 7 + \
+                                          [C.POINTER(VgResult)]
+        L.xm_view_graph_limits.argtypes = [C.c_void_p]
         L.xm_tracks_split_host.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.xm_ctx_reprojection_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_transport.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
@@ -1006,6 +1032,88 @@ def split_host(foff_or_counts, nfeat, eu, ev):
     P = lambda a: a.ctypes.data_as(C.c_void_p)
     _chk(lib().xm_tracks_split_host(foff.size - 1, P(foff), eu.size, P(eu), P(ev), P(label), C.byref(d), C.byref(r)))
     return label, d.value, r.value
+
+
+class ViewGraphPlan:
+    """what view_graph_filter returns: inlier (uint8 per listed match), pair_inliers (int32 per pair), pair_status (int32 per pair: VG_VALID,
+    VG_INVALID_IN, VG_FEW_INLIERS, VG_LOW_RATIO, VG_ROTATION or VG_OUTSIDE, the first rule that dropped the pair), valid (pair_status ==
+    VG_VALID), registered (uint8 per image: membership in the largest component), matches (moff, f1, f2: the inliers of the pairs still
+    valid, in input order, an entry of moff per listed pair), info (the fields of xm_vg_result_t).  matches and registered go into
+    build_tracks, and into a second view_graph_filter call with valid_in=plan.valid, as they are"""
+
+    def __init__(self, inlier, pair_inliers, pair_status, registered, matches, info, pi, pj, Rrel):
+        self.inlier, self.pair_inliers, self.pair_status, self.registered, self.matches, self.info = inlier, pair_inliers, pair_status, registered, matches, info
+        self.valid = (pair_status == VG_VALID).astype(np.uint8)
+        self._pi, self._pj, self._Rrel = pi, pj, Rrel
+
+    def pairs(self):
+        """-> pi, pj, Rrel (k x 3 x 3) of the valid pairs: what pair_filter takes"""
+        k = np.flatnonzero(self.valid)
+        return self._pi[k], self._pj[k], (None if self._Rrel is None else self._Rrel.reshape(-1, 3, 3)[k])
+
+
+def view_graph_limits():
+    """-> dict(group_matches: most matches of a pair that one workgroup runs (larger pairs run in chunks of this size over a workspace),
+    threads: per workgroup, wave_matches: most matches of a pair that one wavefront runs, max_rounds: most hooking rounds)"""
+    out = np.zeros(4, dtype=np.int64)
+    _chk(lib().xm_view_graph_limits(out.ctypes.data_as(C.c_void_p)))
+    return dict(group_matches=int(out[0]), threads=int(out[1]), wave_matches=int(out[2]), max_rounds=int(out[3]))
+
+
+def _vg_array(x, dtype, shape, what):
+    if x is None:
+        return None
+    a = np.ascontiguousarray(x, dtype=dtype)
+    if a.size != int(np.prod(shape)):
+        raise XmError(f"view_graph_filter: {what} must be {' x '.join(str(v) for v in shape)}")
+    return a.reshape(shape)
+
+
+def view_graph_filter(foff_or_counts, xy, pi, pj, model, matches, focal=None, Kinv=None, bearing=None, Rrel=None, trel=None, FH=None, valid_in=None,
+                      registered_in=None, rot=None, score=True, max_epipolar_error_E=1.0, max_epipolar_error_F=4.0, max_epipolar_error_H=4.0,
+                      min_inlier_num=30, min_inlier_ratio=0.25, max_rotation_error_deg=10.0, cos_max_rotation_error=None):
+    """two-view match verification and view-graph pruning on the device (xm_view_graph_filter; include/xm_amd.h has the definition and the
+    lines of the reference's fork of GLOMAP it stands for): foff_or_counts, xy, pi, pj, matches as build_tracks; model: per pair, VG_MODEL_* or
+    "none" / "E" / "F" / "H"; focal (n), Kinv (n x 3 x 3) or bearing (features x 3); Rrel (pairs x 3 x 3, cam2_from_cam1), trel (pairs x 3),
+    FH (pairs x 3 x 3); valid_in per pair, registered_in per image, rot (n x 3 x 3, cam_from_world) or None.  score=True is pass A (rules
+    1-5 and 7), score=False with rot is pass B (rules 6 and 7).  max_rotation_error_deg becomes the cosine the library compares with;
+    cos_max_rotation_error, if given, is passed as it is.  -> ViewGraphPlan"""
+    xy = np.ascontiguousarray(xy, dtype=np.float64)
+    if xy.ndim != 2 or xy.shape[1] != 2:
+        raise XmError("view_graph_filter: xy must be features x 2")
+    foff = _tracks_foff(foff_or_counts, xy.shape[0])
+    n, F = foff.size - 1, xy.shape[0]
+    pi = np.ascontiguousarray(pi, dtype=np.int32).reshape(-1); pj = np.ascontiguousarray(pj, dtype=np.int32).reshape(-1)
+    if pi.size != pj.size:
+        raise XmError("view_graph_filter: pi and pj must have one entry per pair")
+    npairs = pi.size
+    try:
+        model = np.ascontiguousarray([VG_MODELS.get(v, v) if isinstance(v, str) else v for v in np.asarray(model).reshape(-1).tolist()], dtype=np.int32)
+    except (TypeError, ValueError):
+        raise XmError(f"view_graph_filter: model must hold VG_MODEL_* numbers or the names {sorted(VG_MODELS)}") from None
+    if model.size != npairs:
+        raise XmError("view_graph_filter: model must have one entry per pair")
+    moff, f1, f2 = _tracks_matches(matches, npairs)
+    focal = _vg_array(focal, np.float64, (n,), "focal"); Kinv = _vg_array(Kinv, np.float64, (n, 3, 3), "Kinv")
+    bearing = _vg_array(bearing, np.float64, (F, 3), "bearing"); Rrel = _vg_array(Rrel, np.float64, (npairs, 3, 3), "Rrel")
+    trel = _vg_array(trel, np.float64, (npairs, 3), "trel"); FH = _vg_array(FH, np.float64, (npairs, 3, 3), "FH")
+    rot = _vg_array(rot, np.float64, (n, 3, 3), "rot")
+    valid_in = None if valid_in is None else _vg_array(np.asarray(valid_in) != 0, np.uint8, (npairs,), "valid_in")
+    registered_in = None if registered_in is None else _vg_array(np.asarray(registered_in) != 0, np.uint8, (n,), "registered_in")
+    cosmax = float(np.cos(np.radians(float(max_rotation_error_deg)))) if cos_max_rotation_error is None else float(cos_max_rotation_error)
+    opt = VgOptions(VG_SCORE if score else 0, float(max_epipolar_error_E), float(max_epipolar_error_F), float(max_epipolar_error_H), int(min_inlier_num),
+                    float(min_inlier_ratio), cosmax)
+    res = VgResult(); res.struct_size = C.sizeof(VgResult)
+    E = f1.size
+    inlier = np.zeros(E, dtype=np.uint8); pinl = np.zeros(npairs, dtype=np.int32); pst = np.zeros(npairs, dtype=np.int32)
+    regout = np.zeros(n, dtype=np.uint8); mo = np.zeros(npairs + 1, dtype=np.int64); o1 = np.zeros(E, dtype=np.int32); o2 = np.zeros(E, dtype=np.int32)
+    P = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    _chk(lib().xm_view_graph_filter(n, P(foff), P(xy), P(focal), P(Kinv), P(bearing), npairs, P(pi), P(pj), P(model), P(Rrel), P(trel), P(FH), P(valid_in),
+                                    P(registered_in), P(rot), P(moff), P(f1), P(f2), C.byref(opt), P(inlier), P(pinl), P(pst), P(regout), P(mo), P(o1), P(o2),
+                                    C.byref(res)))
+    k = int(mo[-1])
+    info = {f: getattr(res, f) for f, _ in VgResult._fields_ if f != "struct_size"}
+    return ViewGraphPlan(inlier, pinl, pst, regout, (mo, o1[:k].copy(), o2[:k].copy()), info, pi, pj, Rrel)
 
 
 def symw_plan(ntot, nloc, cam0, K=0):
