@@ -4,7 +4,7 @@ policies.  tests/test_tracks_numpy.py ties the restatement to the sequential res
 
 Shapes: the recorded SIMPLE2-derived case (64 549 features, 261 680 matches) and hand-made cases of a few features, except where the
 size is the point: chains of 1 500 images (hooking rounds) and images with limits[3], limits[3] + 1, limits[0], limits[0] + 1 touched
-features (the three kernel sizes)."""
+features (the three kernel sizes), and one image of 2^20 + 4 features (the second pass of the prefix sums' top kernel)."""
 import numpy as np
 import pytest
 
@@ -59,7 +59,7 @@ def cases(xmamd):
 
 
 NAMES = ("simple2", "one_image", "two_images", "triangle", "lengths", "chain", "chain_permuted", "sizes", "conflict_near", "conflict_far",
-         "conflict_chain", "duplicate_match", "duplicate_orientation", "duplicate_pair", "coverage", "unregistered", "max_tracks")
+         "conflict_chain", "duplicate_match", "duplicate_orientation", "duplicate_pair", "coverage", "unregistered", "max_tracks", "scan_second_pass")
 
 
 @pytest.mark.parametrize("name", NAMES)

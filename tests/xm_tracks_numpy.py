@@ -189,6 +189,10 @@ def gpu_cases(limits):
     P["unregistered"] = make_case([2, 2, 2, 1], [(0, 1, [(0, 0), (1, 1)]), (1, 2, [(0, 0)]), (1, 3, [(1, 0)]), (3, 2, [(0, 1)])], registered=[1, 1, 0, 1])
     # five tracks of 5, 4, 3, 3 and 3 observations, max_tracks = 2: three stay, the tie at the cut goes to the larger label
     P["max_tracks"] = make_case([5] * 5, [(k, k + 1, [(c, c) for c, L in enumerate((3, 5, 3, 4, 3)) if k + 1 < L]) for k in range(4)], max_tracks=2)
+    # more than 1024 x 1024 features: the prefix sums' top kernel makes a second pass over the tile sums.  Three tracks whose smallest
+    # features are the global ids 0, F0 - 3 and F0 + 2; the second and third are numbered and placed with the carry of the first pass
+    F0 = 2 ** 20 + 4
+    P["scan_second_pass"] = make_case([F0, 4, 4, 4], [(0, 1, [(0, 0), (F0 - 3, 1)]), (1, 2, [(0, 0), (1, 1), (2, 2)]), (2, 3, [(2, 2)]), (0, 2, [(0, 0)])])
     return P
 
 

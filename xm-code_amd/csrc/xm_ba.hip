@@ -7,11 +7,11 @@
 #include <cmath>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "xm_device.h"
 #include "xm_schur.h"
+#include "xm_stage.h"
 
 namespace xm {
 
@@ -1276,29 +1276,7 @@ __global__ __launch_bounds__(256) void ba_tl_apply_coarse_kernel(BaPcg a, BaTl t
     }
 }
 
-double secs_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); }
-
-// host wait on the stream, bounded by the watchdog
-void wait_stream(hipStream_t st, double limit, const char *what) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-        const hipError_t q = hipStreamQuery(st);
-        if (q == hipSuccess) return;
-        if (q != hipErrorNotReady) {
-            (void)hipGetLastError();
-            throw Error(XM_ERR_HIP, std::string("bundle adjustment: device error while waiting for ") + what + ": " + hipGetErrorString(q));
-        }
-        if (secs_since(t0) > limit)
-            throw Error(XM_ERR_HIP, std::string("bundle adjustment: watchdog: no progress for ") + std::to_string((int)limit) + " s while waiting for " + what);
-        std::this_thread::yield();
-    }
-}
-
-struct PinnedState {
-    BaState *h = nullptr;
-    PinnedState() { XM_HIP_CHECK(hipHostMalloc((void **)&h, sizeof(BaState), hipHostMallocDefault)); }
-    ~PinnedState() { if (h) (void)hipHostFree(h); }
-};
+constexpr const char *kStage = "bundle adjustment";
 
 // the eval and cost kernels of the chosen loss (the trivial instantiations take no scale)
 template <int CD>
@@ -1363,7 +1341,7 @@ struct BaWork {
     DevBuf<double> Jc, Jl, vinv, gl, ustar, sinv, b, x, r, z, pv, Ap, y, dP, parts;
     DevBuf<int32_t> lused, cused, state_buf;
     BaState *dst = nullptr;
-    PinnedState hs;
+    Pinned<BaState> hs;
     int ge = 0, gfc = 0, gfl = 0, gcam = 0, glm = 0;
     size_t o_eval = 0, o_gmax = 0, o_pcg = 0, o_cand = 0, o_cost = 0;
     double *pp = nullptr;
@@ -1435,7 +1413,7 @@ struct BaWork {
         XM_HIP_CHECK(hipMemcpyAsync(hpos.data(), S.pos_c, (size_t)nobs * sizeof(int64_t), hipMemcpyDeviceToHost, st));
         XM_HIP_CHECK(hipMemcpyAsync(hw.data(), S.cam_w, (size_t)nobs * sizeof(double), hipMemcpyDeviceToHost, st));
         XM_HIP_CHECK(hipMemcpyAsync(hp3.data(), S.obs_p, (size_t)3 * nobs * sizeof(double), hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, "the observation lists");
+        wait_stream(st, cfg.watchdog_s, kStage, "the observation lists");
         std::vector<uint8_t> used((size_t)nobs);
         for (int64_t e = 0; e < nobs; ++e) used[(size_t)e] = (hw[(size_t)hpos[(size_t)e]] > 0.0 && hp3[(size_t)3 * e + 2] > 0.0) ? 1 : 0;
         ba_aggregate_plan(n, nobs, hc.data(), hl.data(), used.data(), kBaAgg, order);
@@ -1456,7 +1434,7 @@ struct BaWork {
         tl_order.alloc((size_t)nmem, false); tl_agg.alloc((size_t)n, false); tl_flag.alloc(1);
         XM_HIP_CHECK(hipMemcpyAsync(tl_order.p, order.data(), (size_t)nmem * sizeof(int32_t), hipMemcpyHostToDevice, st));
         XM_HIP_CHECK(hipMemcpyAsync(tl_agg.p, agg.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        wait_stream(st, cfg.watchdog_s, "the aggregate plan");
+        wait_stream(st, cfg.watchdog_s, kStage, "the aggregate plan");
         try_alloc(tl_binv, (size_t)nagg * NB * NB, "the preconditioner's blocks");
         tl_parts.alloc(4 * (size_t)ncoarse);
         if (cfg.precond == 2) {
@@ -1473,7 +1451,7 @@ struct BaWork {
     BaState read_state(const char *what) {
         check_launch(what);
         XM_HIP_CHECK(hipMemcpyAsync(hs.h, dst, sizeof(BaState), hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, what);
+        wait_stream(st, cfg.watchdog_s, kStage, what);
         return *hs.h;
     }
     void eval() {
@@ -1517,7 +1495,7 @@ struct BaWork {
                                tl_flag.p);
             int32_t bad = 0;
             XM_HIP_CHECK(hipMemcpyAsync(&bad, tl_flag.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            wait_stream(st, cfg.watchdog_s, "the coarse operator's inverse");
+            wait_stream(st, cfg.watchdog_s, kStage, "the coarse operator's inverse");
             ok = bad == 0;
         }
         if (ok) tl.use_coarse = 1;
@@ -1724,7 +1702,7 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
     XM_HIP_CHECK(hipMemcpyAsync(hP.data(), W.P[cur].p, hP.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     XM_HIP_CHECK(hipMemcpyAsync(cu.data(), W.cused.p, cu.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     XM_HIP_CHECK(hipMemcpyAsync(lu.data(), W.lused.p, lu.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    wait_stream(st, cfg.watchdog_s, "the refined parameters");
+    wait_stream(st, cfg.watchdog_s, kStage, "the refined parameters");
     for (int64_t i = 0; i < n; ++i) {
         if (!cu[(size_t)i]) continue;
         const double *Rc = &hR[(size_t)9 * i], *tc = &hT[(size_t)3 * i];
@@ -1753,7 +1731,7 @@ void probe(const SchurOp &SO, const BaSettings &cfg, const double *rot, const do
     const std::vector<int32_t> &slot_of = SO.slot_of();
     const int64_t n = W.n, m = W.m, nd = W.nd;
     auto d2h = [&](void *dstp, const void *src, size_t bytes) { XM_HIP_CHECK(hipMemcpyAsync(dstp, src, bytes, hipMemcpyDeviceToHost, st)); };
-    auto sync = [&](const char *what) { check_launch(what); wait_stream(st, cfg.watchdog_s, what); };
+    auto sync = [&](const char *what) { check_launch(what); wait_stream(st, cfg.watchdog_s, kStage, what); };
     // per-landmark arrays: device slot order -> input order
     std::vector<double> tmp;
     auto lm_out = [&](const double *dev, int w, double *outp) {
@@ -1819,7 +1797,7 @@ void probe(const SchurOp &SO, const BaSettings &cfg, const double *rot, const do
             sync("the preconditioner");
         }
         XM_HIP_CHECK(hipMemcpyAsync(W.b.p, keep.p, (size_t)nd * sizeof(double), hipMemcpyDeviceToDevice, st));
-        wait_stream(st, cfg.watchdog_s, "the right-hand side");
+        wait_stream(st, cfg.watchdog_s, kStage, "the right-hand side");
     }
     if (q.dc) {
         XM_HIP_CHECK(hipMemcpyAsync(W.x.p, q.dc, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
@@ -1941,7 +1919,7 @@ void reprojection_errors(const SchurOp &SO, const double *rot, const double *t, 
         check_launch("the reprojection errors");
         XM_HIP_CHECK(hipMemcpyAsync(sqerr, out.p, (size_t)S.nobs * sizeof(double), hipMemcpyDeviceToHost, st));
     }
-    wait_stream(st, watchdog_s, "the reprojection errors");
+    wait_stream(st, watchdog_s, kStage, "the reprojection errors");
 }
 
 }  // namespace xm

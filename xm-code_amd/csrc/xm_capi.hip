@@ -19,6 +19,7 @@
 #include "xm_sell.h"
 #include "xm_symw.h"
 #include "xm_solver.h"
+#include "xm_stage.h"
 
 struct xm_ctx {
     std::unique_ptr<xm::Context> impl;   // one GPU (or one rank of a multi-process run)
@@ -898,7 +899,7 @@ int xm_view_graph_filter(int64_t n, const int64_t *foff, const double *xy, const
 int xm_view_graph_limits(int64_t out[4]) {
     XM_TRY
     if (!out) throw xm::Error(XM_ERR_ARG, "xm_view_graph_limits: null output");
-    out[0] = xm::kVgGroupMatches; out[1] = xm::kVgThreads; out[2] = xm::kVgWaveMatches; out[3] = xm::kVgMaxRounds;
+    out[0] = xm::kVgGroupMatches; out[1] = xm::kVgThreads; out[2] = xm::kVgWaveMatches; out[3] = xm::kMaxRounds;
     return XM_OK;
     XM_CATCH
 }

@@ -8,7 +8,8 @@
 // then every vertex jumps to the root of its tree.  Labels only fall and only to vertices of the same component, so the fixed point is
 // unique -- every vertex carries the smallest vertex of its component, which is a camera -- and all outputs are the same bits on every
 // call; only the number of rounds depends on the order in which the atomics arrive.  A round is two ordinary launches; the host enqueues
-// kCleanBatch rounds and reads their "changed" words in one copy.
+// kBatch rounds and reads their "changed" words in one copy.  The labelling (stage_labels_kernel, stage_hook_kernel<CleanEdge>,
+// stage_jump_kernel, label_components) and the prefix sums (stage_scan_*_kernel, exclusive_scan) are xm_stage.h's.
 #pragma once
 
 #include <cstdint>
@@ -16,10 +17,6 @@
 #include "xm_solver.h"
 
 namespace xm {
-
-constexpr int kCleanMaxRounds = 1024;   // more hooking rounds than this: XM_ERR_HIP ("did not converge")
-constexpr int kCleanBatch = 4;          // rounds enqueued between two looks at the changed words
-constexpr int kCleanScanTile = 1024;    // entries per workgroup of the prefix sums (256 threads x 4)
 
 struct CleanSettings {
     int32_t min_cam_obs = 10, min_lm_obs = 1;

@@ -1,20 +1,20 @@
 // xm_clean.hip — observation cleaning on the device (xm_clean.h; definition in include/xm_amd.h at xm_clean_observations).
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/xm_amd.h"
 #include "xm_clean.h"
 #include "xm_schur.h"
+#include "xm_stage.h"
 
 namespace xm {
 namespace {
 
-typedef unsigned long long u64;
 constexpr int kT = 256;   // threads per workgroup of every kernel here (four wavefronts)
+static_assert(kT == kStageThreads, "the helpers of xm_stage.h are written for this workgroup size");
+constexpr const char *kStage = "observation cleaning";
 
 // slots of the device counter block
 enum { C_LIVE = 0, C_OBS_NEW, C_CAMS_WEAK, C_CAMS_EMPTIED, C_CAMS_OFF, C_N_NEW, C_LMS_WEAK, C_LMS_OFF, C_M_NEW, C_COMPONENTS,
@@ -23,36 +23,7 @@ enum { C_LIVE = 0, C_OBS_NEW, C_CAMS_WEAK, C_CAMS_EMPTIED, C_CAMS_OFF, C_N_NEW, 
        C_BEST_OBS,    // earliest observation of the largest components
        C_N1, C_SCAN_B, C_SCAN_C, C_COUNT };
 
-__device__ inline int ldi(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ inline u64 ldu(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline int lane_id() { return (int)(threadIdx.x & 63u); }
-
-// dst[idx] += 1 for every active lane; the lanes that name the same entry as the first active lane share one atomic.  Called by whole
-// wavefronts (inactive lanes pass active = false).
-__device__ inline void wave_add_one(int32_t *dst, int idx, bool active) {
-    const u64 mask = __ballot(active);
-    if (!mask) return;
-    const int leader = __ffsll((long long)mask) - 1;
-    const int idx0 = __shfl(idx, leader);
-    const u64 same = __ballot(active && idx == idx0);
-    if (active && idx == idx0) {
-        if (lane_id() == leader) atomicAdd(dst + idx0, (int32_t)__popcll(same));
-    } else if (active) {
-        atomicAdd(dst + idx, 1);
-    }
-}
-// *dst += number of lanes with pred; whole wavefronts
-__device__ inline void wave_count(u64 *dst, bool pred) {
-    const u64 mask = __ballot(pred);
-    if (mask && lane_id() == __ffsll((long long)mask) - 1) atomicAdd(dst, (u64)__popcll(mask));
-}
-__device__ inline u64 wave_max(u64 v) {
-    for (int off = 32; off > 0; off >>= 1) {
-        const u64 o = __shfl_xor(v, off);
-        v = o > v ? o : v;
-    }
-    return v;
-}
 
 __device__ inline bool is_live(int64_t e, const uint8_t *live, const double *w, const int64_t *wpos) {
     if (live) return live[e] != 0;
@@ -109,34 +80,17 @@ __global__ __launch_bounds__(kT) void clean_deg3_kernel(int64_t nobs, const int3
     wave_add_one(d3, in ? cam[e] : 0, on);
 }
 
-// components: labels p over the vertices 0 .. n-1 (cameras), n .. n+m-1 (landmarks); p[v] <= v always
-__global__ __launch_bounds__(kT) void clean_labels_kernel(int nv, int32_t *p) {
-    const int v = (int)(blockIdx.x * kT + threadIdx.x);
-    if (v < nv) p[v] = v;
-}
-__global__ __launch_bounds__(kT) void clean_hook_kernel(int64_t nobs, int n, const int32_t *cam, const int32_t *lm, const uint8_t *act, int32_t *p,
-                                                        const int32_t *before, int32_t *changed) {
-    if (before && *before == 0) return;   // the round before this one changed nothing: the labels are final (rounds are enqueued ahead of the host)
-    const int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x;
-    if (e >= nobs || !act[e]) return;
-    const int u = cam[e], v = n + lm[e];
-    const int pu = ldi(p + u), pv = ldi(p + v);
-    const int gu = ldi(p + pu), gv = ldi(p + pv);
-    if (gu == gv) return;
-    // the smaller grandparent goes to the other end's parent (hooking) and to the other end itself
-    if (gv < gu) { atomicMin(p + pu, gv); atomicMin(p + u, gv); }
-    else { atomicMin(p + pv, gu); atomicMin(p + v, gu); }
-    *changed = 1;
-}
-__global__ __launch_bounds__(kT) void clean_jump_kernel(int nv, int32_t *p, const int32_t *before, int32_t *changed) {
-    if (before && *before == 0) return;
-    const int v = (int)(blockIdx.x * kT + threadIdx.x);
-    if (v >= nv) return;
-    const int p0 = ldi(p + v);
-    int r = p0, x = ldi(p + r);
-    while (x != r) { r = x; x = ldi(p + r); }   // labels fall strictly along the way: at most v steps
-    if (r != p0) { p[v] = r; *changed = 1; }
-}
+// components: labels p over the vertices 0 .. n-1 (cameras), n .. n+m-1 (landmarks); an observation that remains is an edge
+struct CleanEdge {
+    int n;
+    const int32_t *cam, *lm;
+    const uint8_t *act;
+    __device__ bool operator()(int64_t e, int &u, int &v) const {
+        if (!act[e]) return false;
+        u = cam[e]; v = n + lm[e];
+        return true;
+    }
+};
 
 // nodes per component (at its root, a camera) and its earliest observation
 __global__ __launch_bounds__(kT) void clean_sizes_kernel(int n, int m, const int32_t *d3, const int32_t *ls2, const int32_t *p, int32_t *size) {
@@ -210,62 +164,6 @@ __global__ __launch_bounds__(kT) void clean_keep_lm_kernel(int m, int n, const i
     wave_count(cnt + C_M_NEW, k);
 }
 
-// ---- exclusive prefix sum of int32 flags in three launches: sums per tile of kCleanScanTile, scan of the sums, add
-__device__ inline int block_scan_excl(int t, int *lds, int *total) {
-    const int tid = (int)threadIdx.x;
-    lds[tid] = t;
-    __syncthreads();
-    for (int off = 1; off < kT; off <<= 1) {
-        const int v = tid >= off ? lds[tid - off] : 0;
-        __syncthreads();
-        lds[tid] += v;
-        __syncthreads();
-    }
-    const int incl = lds[tid];
-    *total = lds[kT - 1];
-    __syncthreads();
-    return incl - t;
-}
-__global__ __launch_bounds__(kT) void clean_scan_sums_kernel(int n, const int32_t *flags, int32_t *sums) {
-    __shared__ int lds[kT];
-    const int base = (int)blockIdx.x * kCleanScanTile + (int)threadIdx.x * 4;
-    int t = 0;
-    for (int j = 0; j < 4; ++j)
-        if (base + j < n) t += flags[base + j];
-    int total;
-    block_scan_excl(t, lds, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(kT) void clean_scan_top_kernel(int nb, int32_t *sums, u64 *total_out) {
-    __shared__ int lds[kT];
-    int carry = 0;
-    for (int base = 0; base < nb; base += kCleanScanTile) {
-        const int i0 = base + (int)threadIdx.x * 4;
-        int v[4], t = 0;
-        for (int j = 0; j < 4; ++j) { v[j] = i0 + j < nb ? sums[i0 + j] : 0; t += v[j]; }
-        int total;
-        int ex = carry + block_scan_excl(t, lds, &total);
-        for (int j = 0; j < 4; ++j) {
-            if (i0 + j < nb) sums[i0 + j] = ex;
-            ex += v[j];
-        }
-        carry += total;
-    }
-    if (threadIdx.x == 0) *total_out = (u64)(uint32_t)carry;
-}
-__global__ __launch_bounds__(kT) void clean_scan_add_kernel(int n, const int32_t *flags, const int32_t *sums, int32_t *out) {
-    __shared__ int lds[kT];
-    const int base = (int)blockIdx.x * kCleanScanTile + (int)threadIdx.x * 4;
-    int v[4], t = 0;
-    for (int j = 0; j < 4; ++j) { v[j] = base + j < n ? flags[base + j] : 0; t += v[j]; }
-    int total;
-    int ex = sums[blockIdx.x] + block_scan_excl(t, lds, &total);
-    for (int j = 0; j < 4; ++j) {
-        if (base + j < n) out[base + j] = ex;
-        ex += v[j];
-    }
-}
-
 // stage-1 index after the exchange of `first` with the camera of index 0, and the final keep flag of every stage-1 POSITION
 __global__ __launch_bounds__(kT) void clean_swap_kernel(int n, const int32_t *cs1, const int32_t *idx1, const int32_t *ckeep, const u64 *cnt, int swap,
                                                         int32_t *idx1s, int32_t *posflag) {
@@ -292,48 +190,7 @@ __global__ __launch_bounds__(kT) void clean_lm_index_kernel(int m, const int32_t
     if (l < m) lm_index[l] = lkeep[l] ? before[l] : -1;
 }
 
-double secs_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); }
-
-// host wait on the stream, bounded by the watchdog
-void wait_stream(hipStream_t st, double limit, const char *what) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-        const hipError_t q = hipStreamQuery(st);
-        if (q == hipSuccess) return;
-        if (q != hipErrorNotReady) {
-            (void)hipGetLastError();
-            throw Error(XM_ERR_HIP, std::string("observation cleaning: device error while waiting for ") + what + ": " + hipGetErrorString(q));
-        }
-        if (secs_since(t0) > limit)
-            throw Error(XM_ERR_HIP, std::string("observation cleaning: watchdog: no progress for ") + std::to_string((int)limit) + " s while waiting for " + what);
-        std::this_thread::yield();
-    }
-}
-
-struct Pinned {   // what the host reads during a call
-    struct Block { int32_t changed[kCleanBatch]; u64 cnt[C_COUNT]; } *h = nullptr;
-    Pinned() { XM_HIP_CHECK(hipHostMalloc((void **)&h, sizeof(Block), hipHostMallocDefault)); }
-    ~Pinned() { if (h) (void)hipHostFree(h); }
-    Pinned(const Pinned &) = delete;
-    Pinned &operator=(const Pinned &) = delete;
-};
-
-inline unsigned grid_of(int64_t n) { return (unsigned)((n + kT - 1) / kT); }
-template <class T>
-void fresh(DevBuf<T> &b, size_t n, int byte, hipStream_t st) {   // n entries filled with `byte` on the stream
-    b.alloc(n, false);
-    XM_HIP_CHECK(hipMemsetAsync(b.p, byte, (n ? n : 1) * sizeof(T), st));
-}
-
-// out[i] = sum of flags[0 .. i); the total goes to *total (a counter slot)
-void exclusive_scan(int n, const int32_t *flags, int32_t *out, DevBuf<int32_t> &sums, u64 *total, hipStream_t st) {
-    if (n <= 0) return;
-    const int nb = (n + kCleanScanTile - 1) / kCleanScanTile;
-    hipLaunchKernelGGL(clean_scan_sums_kernel, dim3((unsigned)nb), dim3(kT), 0, st, n, flags, sums.p);
-    hipLaunchKernelGGL(clean_scan_top_kernel, dim3(1), dim3(kT), 0, st, nb, sums.p, total);
-    hipLaunchKernelGGL(clean_scan_add_kernel, dim3((unsigned)nb), dim3(kT), 0, st, n, flags, sums.p, out);
-    check_launch("clean_scan");
-}
+struct Block { int32_t changed[kBatch]; u64 cnt[C_COUNT]; };   // what the host reads during a call
 
 }  // namespace
 
@@ -345,7 +202,7 @@ void clean_observations_device(const CleanList &L, const CleanSettings &cfg, uin
     if (nobs >= ((int64_t)1 << 39)) throw Error(XM_ERR_ARG, "observation cleaning: more than 2^39 observations");
     const int n = (int)L.n, m = (int)L.m, nv = n + m;
     out = CleanOutcome();
-    Pinned pin;
+    Pinned<Block> pin;
     DevBuf<u64> cnt, firstobs;
     DevBuf<uint8_t> live, act, dkeep;
     DevBuf<int32_t> d1, d2, d3, cs1, ls2, p, size, ckeep, lkeep, idx1, idx1s, posflag, before, lmbefore, dcam_index, dlm_index, sums, changed, slot;
@@ -358,8 +215,8 @@ void clean_observations_device(const CleanList &L, const CleanSettings &cfg, uin
     fresh(posflag, (size_t)n, 0, st); before.alloc((size_t)n, false); dcam_index.alloc((size_t)n, false);
     ls2.alloc((size_t)m, false); lkeep.alloc((size_t)m, false); lmbefore.alloc((size_t)m, false); dlm_index.alloc((size_t)m, false);
     p.alloc((size_t)nv, false);
-    sums.alloc((size_t)(std::max(n, m) / kCleanScanTile + 1), false);
-    fresh(changed, (size_t)kCleanMaxRounds + kCleanBatch, 0, st);
+    sums.alloc((size_t)(std::max(n, m) / kScanTile + 1), false);
+    fresh(changed, (size_t)kMaxRounds + kBatch, 0, st);
     if (L.lm_slot && m > 0) {
         slot.alloc((size_t)m, false);
         XM_HIP_CHECK(hipMemcpyAsync(slot.p, L.lm_slot, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -373,30 +230,11 @@ void clean_observations_device(const CleanList &L, const CleanSettings &cfg, uin
     if (ge) hipLaunchKernelGGL(clean_deg2_kernel, dim3(ge), dim3(kT), 0, st, nobs, L.cam, L.lm, live.p, cs1.p, d2.p);
     if (gl) hipLaunchKernelGGL(clean_stage2_kernel, dim3(gl), dim3(kT), 0, st, m, d2.p, cfg.min_lm_obs, ls2.p, cnt.p);
     if (ge) hipLaunchKernelGGL(clean_deg3_kernel, dim3(ge), dim3(kT), 0, st, nobs, L.cam, L.lm, live.p, cs1.p, ls2.p, act.p, d3.p);
-    if (gv) hipLaunchKernelGGL(clean_labels_kernel, dim3(gv), dim3(kT), 0, st, nv, p.p);
+    identity_labels(nv, p.p, st);
     check_launch("clean_degrees");
 
-    // components: kCleanBatch rounds, then one look at their changed words
-    int rounds = 0;
-    bool converged = !(ge && gv);
-    while (!converged) {
-        if (rounds >= kCleanMaxRounds)
-            throw Error(XM_ERR_HIP, "observation cleaning: the component labels did not converge in " + std::to_string(kCleanMaxRounds) + " rounds");
-        for (int k = 0; k < kCleanBatch; ++k) {
-            int32_t *word = changed.p + rounds + k;
-            const int32_t *prev = rounds + k > 0 ? word - 1 : nullptr;   // the round before this one's word
-            hipLaunchKernelGGL(clean_hook_kernel, dim3(ge), dim3(kT), 0, st, nobs, n, L.cam, L.lm, act.p, p.p, prev, word);
-            hipLaunchKernelGGL(clean_jump_kernel, dim3(gv), dim3(kT), 0, st, nv, p.p, prev, word);
-        }
-        check_launch("clean_components");
-        XM_HIP_CHECK(hipMemcpyAsync(pin.h->changed, changed.p + rounds, kCleanBatch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, "the component labels");
-        for (int k = 0; k < kCleanBatch && !converged; ++k) {
-            ++rounds;
-            converged = pin.h->changed[k] == 0;
-        }
-    }
-    out.rounds = rounds;
+    const CleanEdge edge = {n, L.cam, L.lm, act.p};
+    out.rounds = label_components(nobs, nv, edge, p.p, changed.p, pin.h->changed, kStage, cfg.watchdog_s, st);
 
     // the largest component, the flags and the index maps
     if (gv) hipLaunchKernelGGL(clean_sizes_kernel, dim3(gv), dim3(kT), 0, st, n, m, d3.p, ls2.p, p.p, size.p);
@@ -419,7 +257,7 @@ void clean_observations_device(const CleanList &L, const CleanSettings &cfg, uin
     if (n) XM_HIP_CHECK(hipMemcpyAsync(cam_index, dcam_index.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (m) XM_HIP_CHECK(hipMemcpyAsync(lm_index, dlm_index.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     XM_HIP_CHECK(hipMemcpyAsync(pin.h->cnt, cnt.p, C_COUNT * sizeof(u64), hipMemcpyDeviceToHost, st));
-    wait_stream(st, cfg.watchdog_s, "the kept observations");
+    wait_stream(st, cfg.watchdog_s, kStage, "the kept observations");
     const u64 *c = pin.h->cnt;
     out.nobs_live = (int64_t)c[C_LIVE]; out.nobs_new = (int64_t)c[C_OBS_NEW]; out.n_new = (int64_t)c[C_N_NEW]; out.m_new = (int64_t)c[C_M_NEW];
     out.components = (int64_t)c[C_COMPONENTS]; out.cams_weak = (int64_t)c[C_CAMS_WEAK]; out.lms_weak = (int64_t)c[C_LMS_WEAK];

@@ -5,11 +5,11 @@
 #include <cstring>
 #include <limits>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "xm_lift.h"
 #include "xm_device.h"
+#include "xm_stage.h"
 
 // every product and every sum below is rounded on its own: the percentile is numpy's, and the point is the definition's three-term sum
 #pragma clang fp contract(off)
@@ -18,9 +18,9 @@
 namespace xm {
 namespace {
 
-typedef unsigned long long u64;
 constexpr int kT = kLiftThreads;
-static_assert(kT == kSortThreads, "the helpers of xm_sortstat.h are written for this workgroup size");
+static_assert(kT == kStageThreads && kT == kSortThreads, "the helpers of xm_stage.h and xm_sortstat.h are written for this workgroup size");
+constexpr const char *kStage = "lift";
 
 // what a slot's code says when it is negative; a code >= 0 is the row's rank among its camera's survivors
 enum { S_DUPLICATE = -1, S_BORDER = -2, S_DEPTH = -3, S_NO_MAP = -4 };
@@ -238,31 +238,6 @@ __global__ __launch_bounds__(kT) void lift_emit_kernel(int64_t nrows, LiftArgs a
     }
 }
 
-double secs_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); }
-
-// host wait on the stream, bounded by the watchdog
-void wait_stream(hipStream_t st, double limit, const char *what) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-        const hipError_t q = hipStreamQuery(st);
-        if (q == hipSuccess) return;
-        if (q != hipErrorNotReady) {
-            (void)hipGetLastError();
-            throw Error(XM_ERR_HIP, std::string("lift: device error while waiting for ") + what + ": " + hipGetErrorString(q));
-        }
-        if (secs_since(t0) > limit)
-            throw Error(XM_ERR_HIP, std::string("lift: watchdog: no progress for ") + std::to_string((int)limit) + " s while waiting for " + what);
-        std::this_thread::yield();
-    }
-}
-
-template <class T>
-void upload(DevBuf<T> &b, const T *src, size_t n, hipStream_t st) {
-    b.alloc(n, false);
-    if (n) XM_HIP_CHECK(hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, st));
-}
-unsigned grid_for(int64_t items) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + kT - 1) / kT, 2048)); }
-
 void run_device(int64_t n, int64_t nrows, const int32_t *cam, const int32_t *lm, const double *xy, const int32_t *hw, const float *const *depth,
                 const float *const *conf, const double *Kinv, const std::vector<float> &sd, const std::vector<float> &sc, const LiftSettings &cfg,
                 int32_t *out_cam, int32_t *out_lm, double *out_p, double *out_w, int32_t *out_row, double *threshold, LiftOutcome &out,
@@ -290,16 +265,16 @@ void run_device(int64_t n, int64_t nrows, const int32_t *cam, const int32_t *lm,
     dop.alloc((size_t)nrows * 3, false); dow.alloc((size_t)nrows, false);
     // binning: a counting sort of the rows by camera
     XM_HIP_CHECK(hipMemsetAsync(dcnt.p, 0, (size_t)n * sizeof(int32_t), st));
-    hipLaunchKernelGGL(lift_hist_kernel, dim3(grid_for(nrows)), dim3(kT), 0, st, nrows, dcam.p, dcnt.p);
+    hipLaunchKernelGGL(lift_hist_kernel, dim3(grid_for(nrows, 2048)), dim3(kT), 0, st, nrows, dcam.p, dcnt.p);
     check_launch("lift_hist_kernel");
     hipLaunchKernelGGL(lift_scan_kernel, dim3(1), dim3(kT), 0, st, dcnt.p, 1, dcamptr.p, (int)n);
     check_launch("lift_scan_kernel (rows)");
     XM_HIP_CHECK(hipMemcpyAsync(dcursor.p, dcamptr.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(lift_scatter_kernel, dim3(grid_for(nrows)), dim3(kT), 0, st, nrows, dcam.p, dcursor.p, dsrow.p);
+    hipLaunchKernelGGL(lift_scatter_kernel, dim3(grid_for(nrows, 2048)), dim3(kT), 0, st, nrows, dcam.p, dcursor.p, dsrow.p);
     check_launch("lift_scatter_kernel");
     std::vector<int32_t> camptr((size_t)n + 1);
     XM_HIP_CHECK(hipMemcpyAsync(camptr.data(), dcamptr.p, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    wait_stream(st, cfg.watchdog_s, "the binning");
+    wait_stream(st, cfg.watchdog_s, kStage, "the binning");
     if (camptr[(size_t)n] != nrows) throw Error(XM_ERR_HIP, "lift: the cameras' rows do not add up to the rows listed");
     // which cameras need a larger size than the one all of them start in
     std::vector<int32_t> large, wsl;
@@ -314,7 +289,7 @@ void run_device(int64_t n, int64_t nrows, const int32_t *cam, const int32_t *lm,
     out.cams_large = (int64_t)large.size(); out.cams_workspace = (int64_t)wsl.size();
     if (!large.empty()) upload(dlarge, large.data(), large.size(), st);
     if (!wsl.empty()) upload(dwsl, wsl.data(), wsl.size(), st);
-    wait_stream(st, cfg.watchdog_s, "the camera lists");
+    wait_stream(st, cfg.watchdog_s, kStage, "the camera lists");
     out.seconds_index = secs_since(t_start);
     const auto t_kernels = std::chrono::steady_clock::now();
 
@@ -341,13 +316,13 @@ void run_device(int64_t n, int64_t nrows, const int32_t *cam, const int32_t *lm,
     }
     hipLaunchKernelGGL(lift_scan_kernel, dim3(1), dim3(kT), 0, st, dcamcnt.p + N_KEPT, (int)N_COUNTS, doff.p, (int)n);
     check_launch("lift_scan_kernel (survivors)");
-    hipLaunchKernelGGL(lift_emit_kernel, dim3(grid_for(nrows)), dim3(kT), 0, st, nrows, a, doff.p, docam.p, dolm.p, dop.p, dow.p, dorow.p);
+    hipLaunchKernelGGL(lift_emit_kernel, dim3(grid_for(nrows, 2048)), dim3(kT), 0, st, nrows, a, doff.p, docam.p, dolm.p, dop.p, dow.p, dorow.p);
     check_launch("lift_emit_kernel");
     std::vector<int32_t> camcnt((size_t)n * N_COUNTS);
     int32_t total = 0;
     XM_HIP_CHECK(hipMemcpyAsync(camcnt.data(), dcamcnt.p, camcnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     XM_HIP_CHECK(hipMemcpyAsync(&total, doff.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    wait_stream(st, cfg.watchdog_s, "the cameras");
+    wait_stream(st, cfg.watchdog_s, kStage, "the cameras");
     out.seconds_kernels = secs_since(t_kernels);
     const auto t_down = std::chrono::steady_clock::now();
     if (total < 0 || total > nrows) throw Error(XM_ERR_HIP, "lift: more survivors than rows");
@@ -360,7 +335,7 @@ void run_device(int64_t n, int64_t nrows, const int32_t *cam, const int32_t *lm,
         XM_HIP_CHECK(hipMemcpyAsync(out_w, dow.p, no * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     if (threshold) XM_HIP_CHECK(hipMemcpyAsync(threshold, dthr.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    wait_stream(st, cfg.watchdog_s, "the download");
+    wait_stream(st, cfg.watchdog_s, kStage, "the download");
     out.seconds_download = secs_since(t_down);
     out.nout = total;
     int64_t accounted = total;

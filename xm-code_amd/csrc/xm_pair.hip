@@ -4,12 +4,12 @@
 #include <cmath>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <utility>
 #include <vector>
 
 #include "xm_pair.h"
 #include "xm_device.h"
+#include "xm_stage.h"
 
 // every product and every sum below is rounded on its own: the residual that is sorted and the one compared with the threshold are the same bits
 #pragma clang fp contract(off)
@@ -18,9 +18,9 @@
 namespace xm {
 namespace {
 
-typedef unsigned long long u64;
 constexpr int kT = kPairThreads;
 static_assert(kT == kSortThreads, "the helpers of xm_sortstat.h are written for this workgroup size");
+constexpr const char *kStage = "pair filter";
 constexpr int kCap = kPairLdsJoint;
 
 // slots of the device counter block
@@ -268,30 +268,6 @@ __global__ __launch_bounds__(kT) void pair_outlier_kernel(int64_t nobs, const in
     if (lane_id() == 0 && total) atomicAdd(cnt + C_FLAGGED, total);
 }
 
-double secs_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); }
-
-// host wait on the stream, bounded by the watchdog
-void wait_stream(hipStream_t st, double limit, const char *what) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-        const hipError_t q = hipStreamQuery(st);
-        if (q == hipSuccess) return;
-        if (q != hipErrorNotReady) {
-            (void)hipGetLastError();
-            throw Error(XM_ERR_HIP, std::string("pair filter: device error while waiting for ") + what + ": " + hipGetErrorString(q));
-        }
-        if (secs_since(t0) > limit)
-            throw Error(XM_ERR_HIP, std::string("pair filter: watchdog: no progress for ") + std::to_string((int)limit) + " s while waiting for " + what);
-        std::this_thread::yield();
-    }
-}
-
-template <class T>
-void upload(DevBuf<T> &b, const T *src, size_t n, hipStream_t st) {
-    b.alloc(n, false);
-    if (n) XM_HIP_CHECK(hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, st));
-}
-
 void run_device(int64_t n, int64_t nobs, const double *p, int64_t npairs, const int32_t *pi, const int32_t *pj, const double *R,
                 const std::vector<int32_t> &camptr, const std::vector<int32_t> &slm, const std::vector<int32_t> &srow, const std::vector<int32_t> &order,
                 const PairSettings &cfg, int32_t *count, uint8_t *outlier, xm_pair_stat_t *stats, PairOutcome &out,
@@ -314,7 +290,7 @@ void run_device(int64_t n, int64_t nobs, const double *p, int64_t npairs, const 
     XM_HIP_CHECK(hipMemsetAsync(dcount.p, 0, (size_t)(nobs ? nobs : 1) * sizeof(int32_t), st));
     XM_HIP_CHECK(hipMemsetAsync(dcnt.p, 0, C_COUNT * sizeof(uint32_t), st));
     if (stats) dstats.alloc((size_t)npairs, false);
-    wait_stream(st, cfg.watchdog_s, "the upload");
+    wait_stream(st, cfg.watchdog_s, kStage, "the upload");
     out.seconds_index = secs_since(t_start);
     const auto t_kernels = std::chrono::steady_clock::now();
 
@@ -329,14 +305,14 @@ void run_device(int64_t n, int64_t nobs, const double *p, int64_t npairs, const 
         hipLaunchKernelGGL(pair_lds_kernel<kPairSmallJoint>, dim3((unsigned)npairs), dim3(kT), 0, st, a);
         check_launch("pair_lds_kernel (small)");
         XM_HIP_CHECK(hipMemcpyAsync(hcnt, dcnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, "the pairs");
+        wait_stream(st, cfg.watchdog_s, kStage, "the pairs");
         if (hcnt[C_OVER_SMALL] > 0) {
             dover2.alloc((size_t)hcnt[C_OVER_SMALL], false);
             a.work = dover1.p; a.nwork = (int32_t)hcnt[C_OVER_SMALL]; a.overflow = dover2.p; a.over_slot = C_OVER_LDS; a.first = 0;
             hipLaunchKernelGGL(pair_lds_kernel<kCap>, dim3((unsigned)a.nwork), dim3(kT), 0, st, a);
             check_launch("pair_lds_kernel (large)");
             XM_HIP_CHECK(hipMemcpyAsync(hcnt, dcnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, st));
-            wait_stream(st, cfg.watchdog_s, "the larger pairs");
+            wait_stream(st, cfg.watchdog_s, kStage, "the larger pairs");
         }
         const int64_t nover = hcnt[C_OVER_LDS];
         out.pairs_on_workspace_path = nover;
@@ -355,7 +331,7 @@ void run_device(int64_t n, int64_t nobs, const double *p, int64_t npairs, const 
         check_launch("pair_outlier_kernel");
     }
     XM_HIP_CHECK(hipMemcpyAsync(hcnt, dcnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, st));
-    wait_stream(st, cfg.watchdog_s, "the flags");
+    wait_stream(st, cfg.watchdog_s, kStage, "the flags");
     out.seconds_kernels = secs_since(t_kernels);
     const auto t_down = std::chrono::steady_clock::now();
     if (nobs > 0) {
@@ -363,7 +339,7 @@ void run_device(int64_t n, int64_t nobs, const double *p, int64_t npairs, const 
         XM_HIP_CHECK(hipMemcpyAsync(outlier, doutlier.p, (size_t)nobs, hipMemcpyDeviceToHost, st));
     }
     if (stats && npairs > 0) XM_HIP_CHECK(hipMemcpyAsync(stats, dstats.p, (size_t)npairs * sizeof(xm_pair_stat_t), hipMemcpyDeviceToHost, st));
-    wait_stream(st, cfg.watchdog_s, "the download");
+    wait_stream(st, cfg.watchdog_s, kStage, "the download");
     out.seconds_download = secs_since(t_down);
     out.pairs_used = hcnt[C_USED]; out.pairs_skipped = hcnt[C_TOO_FEW]; out.pairs_degenerate = hcnt[C_DEGENERATE];
     out.nobs_flagged = hcnt[C_FLAGGED]; out.max_joint = hcnt[C_MAX_JOINT];

@@ -6,11 +6,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include "xm_stage.h"   // lane_id()
+
 namespace xm {
 
-constexpr int kSortThreads = 256;
+constexpr int kSortThreads = kStageThreads;
 
-__device__ inline int lane_id() { return (int)(threadIdx.x & 63u); }
 __device__ inline double inf_() { return __longlong_as_double(0x7ff0000000000000ll); }
 
 // sum over the workgroup, valid in every thread; ired: 4 ints

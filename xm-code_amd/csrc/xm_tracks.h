@@ -6,8 +6,8 @@
 //   tracks_expand_kernel   one thread per match: the pair by binary search in moff, the two global feature ids (smaller first), the range
 //                          check of the feature indices (an index out of range is reported and never used as an address), touched marks
 //   tracks_feat_kernel     one thread per feature: its image by binary search in foff, label = itself, touched features per image
-//   tracks_hook_kernel /   FastSV hooking and pointer jumping on int32 labels as xm_clean.hip's (atomicMin; a component's final label is
-//   tracks_jump_kernel     its smallest member); kTracksBatch rounds are enqueued ahead of the host, which reads their "changed" words
+//   stage_hook_kernel<TracksEdge> /  xm_stage.h's FastSV hooking and pointer jumping on int32 labels (atomicMin; a component's final
+//   stage_jump_kernel      label is its smallest member); kBatch rounds are enqueued ahead of the host, which reads their "changed" words
 //   tracks_image_kernel    one workgroup of kTracksThreads per image: compacts (ballots) and sorts (xm_sortstat.h) the (label << 32 |
 //                          feature) words of its touched features; equal neighbouring labels are the image's conflicts: they set the
 //                          component's flag (atomicOr), count its duplicates in registered images (atomicAdd) and, under
@@ -19,7 +19,7 @@
 //                          the list is arbitrary; the splitter sorts them first, so nothing depends on it
 //   tracks_relabel_kernel  the splitter's labels back into the label array
 //   tracks_decide_kernel   per component: kept, or the first rule that drops it
-//   tracks_scan_*          exclusive prefix sums (three launches, as xm_clean.hip's): track numbers over the labels, row offsets
+//   stage_scan_*_kernel    xm_stage.h's exclusive prefix sums (three launches): track numbers over the labels, row offsets
 //   tracks_rows_kernel     label[] and the row flag of every feature
 //   tracks_emit_kernel     one thread per feature: a row at its offset
 #pragma once
@@ -35,9 +35,6 @@ constexpr int kTracksThreads = 256;      // threads per workgroup (four wavefron
 constexpr int kTracksSmallRows = 256;    // most touched features of an image in the small instantiation
 constexpr int kTracksLdsRows = 4096;     // most touched features of an image that are sorted in LDS
 constexpr int kTracksWsGroups = 64;      // workgroups of the workspace path
-constexpr int kTracksMaxRounds = 1024;   // more hooking rounds than this: XM_ERR_HIP
-constexpr int kTracksBatch = 4;          // rounds enqueued between two looks at the changed words
-constexpr int kTracksScanTile = 1024;    // entries per workgroup of the prefix sums
 
 struct TracksSettings {
     int32_t min_views = 3, max_views = 1000000, conflict = XM_TRACKS_SPLIT;

@@ -5,12 +5,11 @@
 #include <cmath>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "xm_tracks.h"
 #include "xm_tracks_split.h"
-#include "xm_common.h"
+#include "xm_stage.h"
 
 // the distance test of XM_TRACKS_GLOMAP is sqrt(dx*dx + dy*dy) with every product and the sum rounded on its own
 #pragma clang fp contract(off)
@@ -19,46 +18,15 @@
 namespace xm {
 namespace {
 
-typedef unsigned long long u64;
 constexpr int kT = kTracksThreads;
-static_assert(kT == kSortThreads, "the helpers of xm_sortstat.h are written for this workgroup size");
+static_assert(kT == kStageThreads && kT == kSortThreads, "the helpers of xm_stage.h and xm_sortstat.h are written for this workgroup size");
 static_assert((kTracksSmallRows & (kTracksSmallRows - 1)) == 0 && (kTracksLdsRows & (kTracksLdsRows - 1)) == 0, "the sort pads to a power of two");
+constexpr const char *kStage = "tracks";
 
 // slots of the device counter block
 enum { C_TOUCHED = 0, C_COMPONENTS, C_CONFLICTED, C_ROWS_CONFLICTED, C_NSPLIT, C_SHORT, C_LONG, C_CONFLICT, C_FEW, C_NTRACKS, C_NOUT, C_COUNT };
 // a component's flag word
 enum { F_CONFLICT = 1, F_FAR = 2 };
-
-__device__ inline int ldi(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// dst[idx] += 1 for every active lane; the lanes that name the same entry as the first active lane share one atomic.  Whole wavefronts.
-__device__ inline void wave_add_one(int32_t *dst, int idx, bool active) {
-    const u64 mask = __ballot(active);
-    if (!mask) return;
-    const int leader = __ffsll((long long)mask) - 1;
-    const int idx0 = __shfl(idx, leader);
-    const u64 same = __ballot(active && idx == idx0);
-    if (active && idx == idx0) {
-        if (lane_id() == leader) atomicAdd(dst + idx0, (int32_t)__popcll(same));
-    } else if (active) {
-        atomicAdd(dst + idx, 1);
-    }
-}
-// *dst += v over the lanes with pred; whole wavefronts
-__device__ inline void wave_sum_to(u64 *dst, bool pred, u64 v) {
-    v = pred ? v : 0ull;
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if (lane_id() == 0 && v) atomicAdd(dst, v);
-}
-// the largest k in [0, count) with off[k] <= x (off[0] <= x): at most 32 steps
-__device__ inline int owner_of(const int64_t *off, int count, int64_t x) {
-    int lo = 0, hi = count;
-    while (hi - lo > 1) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // one thread per match: the endpoints as global feature ids, smaller first; -1, -1 and the match's number in *firstbad when an index is out of range
 __global__ __launch_bounds__(kT) void tracks_expand_kernel(int64_t E, int npairs, const int64_t *moff, const int32_t *pi, const int32_t *pj, const int64_t *foff,
@@ -88,30 +56,14 @@ __global__ __launch_bounds__(kT) void tracks_feat_kernel(int F, int n, const int
     }
 }
 
-// components: labels p over the features; p[v] <= v always (xm_clean.hip's scheme)
-__global__ __launch_bounds__(kT) void tracks_hook_kernel(int64_t E, const int32_t *eu, const int32_t *ev, int32_t *p, const int32_t *before, int32_t *changed) {
-    if (before && *before == 0) return;   // the round before this one changed nothing: the labels are final (rounds are enqueued ahead of the host)
-    const int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x;
-    if (e >= E) return;
-    const int u = eu[e], v = ev[e];
-    if (u < 0) return;
-    const int pu = ldi(p + u), pv = ldi(p + v);
-    const int gu = ldi(p + pu), gv = ldi(p + pv);
-    if (gu == gv) return;
-    // the smaller grandparent goes to the other end's parent (hooking) and to the other end itself
-    if (gv < gu) { atomicMin(p + pu, gv); atomicMin(p + u, gv); }
-    else { atomicMin(p + pv, gu); atomicMin(p + v, gu); }
-    *changed = 1;
-}
-__global__ __launch_bounds__(kT) void tracks_jump_kernel(int F, int32_t *p, const int32_t *before, int32_t *changed) {
-    if (before && *before == 0) return;
-    const int v = (int)(blockIdx.x * kT + threadIdx.x);
-    if (v >= F) return;
-    const int p0 = ldi(p + v);
-    int r = p0, x = ldi(p + r);
-    while (x != r) { r = x; x = ldi(p + r); }   // labels fall strictly along the way: at most v steps
-    if (r != p0) { p[v] = r; *changed = 1; }
-}
+// components: labels p over the features; a match whose indices are in range is an edge
+struct TracksEdge {
+    const int32_t *eu, *ev;
+    __device__ bool operator()(int64_t e, int &u, int &v) const {
+        u = eu[e]; v = ev[e];
+        return u >= 0;
+    }
+};
 
 struct ImgArgs {
     const int64_t *foff;
@@ -260,62 +212,6 @@ __global__ __launch_bounds__(kT) void tracks_decide_kernel(int F, const int32_t 
     wave_sum_to(cnt + C_FEW, root && code == XM_TRACK_FEW_REGISTERED, 1ull);
 }
 
-// ---- exclusive prefix sum of int32 flags in three launches (xm_clean.hip's): sums per tile of kTracksScanTile, scan of the sums, add
-__device__ inline int block_scan_excl(int t, int *lds, int *total) {
-    const int tid = (int)threadIdx.x;
-    lds[tid] = t;
-    __syncthreads();
-    for (int off = 1; off < kT; off <<= 1) {
-        const int v = tid >= off ? lds[tid - off] : 0;
-        __syncthreads();
-        lds[tid] += v;
-        __syncthreads();
-    }
-    const int incl = lds[tid];
-    *total = lds[kT - 1];
-    __syncthreads();
-    return incl - t;
-}
-__global__ __launch_bounds__(kT) void tracks_scan_sums_kernel(int n, const int32_t *flags, int32_t *sums) {
-    __shared__ int lds[kT];
-    const int base = (int)blockIdx.x * kTracksScanTile + (int)threadIdx.x * 4;
-    int t = 0;
-    for (int j = 0; j < 4; ++j)
-        if (base + j < n) t += flags[base + j];
-    int total;
-    block_scan_excl(t, lds, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(kT) void tracks_scan_top_kernel(int nb, int32_t *sums, u64 *total_out) {
-    __shared__ int lds[kT];
-    int carry = 0;
-    for (int base = 0; base < nb; base += kTracksScanTile) {
-        const int i0 = base + (int)threadIdx.x * 4;
-        int v[4], t = 0;
-        for (int j = 0; j < 4; ++j) { v[j] = i0 + j < nb ? sums[i0 + j] : 0; t += v[j]; }
-        int total;
-        int ex = carry + block_scan_excl(t, lds, &total);
-        for (int j = 0; j < 4; ++j) {
-            if (i0 + j < nb) sums[i0 + j] = ex;
-            ex += v[j];
-        }
-        carry += total;
-    }
-    if (threadIdx.x == 0) *total_out = (u64)(uint32_t)carry;
-}
-__global__ __launch_bounds__(kT) void tracks_scan_add_kernel(int n, const int32_t *flags, const int32_t *sums, int32_t *out) {
-    __shared__ int lds[kT];
-    const int base = (int)blockIdx.x * kTracksScanTile + (int)threadIdx.x * 4;
-    int v[4], t = 0;
-    for (int j = 0; j < 4; ++j) { v[j] = base + j < n ? flags[base + j] : 0; t += v[j]; }
-    int total;
-    int ex = sums[blockIdx.x] + block_scan_excl(t, lds, &total);
-    for (int j = 0; j < 4; ++j) {
-        if (base + j < n) out[base + j] = ex;
-        ex += v[j];
-    }
-}
-
 // label[] and the row flag of every feature
 __global__ __launch_bounds__(kT) void tracks_rows_kernel(int F, const int32_t *touched, const int32_t *p, const int32_t *fimg, const uint8_t *reg,
                                                          const int32_t *status, const int32_t *tnum, int32_t *label, int32_t *rowflag) {
@@ -339,60 +235,14 @@ __global__ __launch_bounds__(kT) void tracks_emit_kernel(int F, const int64_t *f
     oxy[2 * o] = xy[2 * (size_t)g]; oxy[2 * o + 1] = xy[2 * (size_t)g + 1];
 }
 
-double secs_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); }
-
-// host wait on the stream, bounded by the watchdog
-void wait_stream(hipStream_t st, double limit, const char *what) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-        const hipError_t q = hipStreamQuery(st);
-        if (q == hipSuccess) return;
-        if (q != hipErrorNotReady) {
-            (void)hipGetLastError();
-            throw Error(XM_ERR_HIP, std::string("tracks: device error while waiting for ") + what + ": " + hipGetErrorString(q));
-        }
-        if (secs_since(t0) > limit)
-            throw Error(XM_ERR_HIP, std::string("tracks: watchdog: no progress for ") + std::to_string((int)limit) + " s while waiting for " + what);
-        std::this_thread::yield();
-    }
-}
-
-struct Pinned {   // what the host reads during a call
-    struct Block { int32_t changed[kTracksBatch]; int32_t firstbad; u64 cnt[C_COUNT]; } *h = nullptr;
-    Pinned() { XM_HIP_CHECK(hipHostMalloc((void **)&h, sizeof(Block), hipHostMallocDefault)); }
-    ~Pinned() { if (h) (void)hipHostFree(h); }
-    Pinned(const Pinned &) = delete;
-    Pinned &operator=(const Pinned &) = delete;
-};
-
-template <class T>
-void upload(DevBuf<T> &b, const T *src, size_t n, hipStream_t st) {
-    b.alloc(n, false);
-    if (n) XM_HIP_CHECK(hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, st));
-}
-template <class T>
-void fresh(DevBuf<T> &b, size_t n, int byte, hipStream_t st) {   // n entries filled with `byte` on the stream
-    b.alloc(n, false);
-    XM_HIP_CHECK(hipMemsetAsync(b.p, byte, (n ? n : 1) * sizeof(T), st));
-}
-unsigned grid_of(int64_t items) { return (unsigned)((items + kT - 1) / kT); }
-unsigned grid_for(int64_t items) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + kT - 1) / kT, 4096)); }
-
-// out[i] = sum of flags[0 .. i); the total goes to *total (a counter slot)
-void exclusive_scan(int n, const int32_t *flags, int32_t *out, DevBuf<int32_t> &sums, u64 *total, hipStream_t st) {
-    const int nb = (n + kTracksScanTile - 1) / kTracksScanTile;
-    hipLaunchKernelGGL(tracks_scan_sums_kernel, dim3((unsigned)nb), dim3(kT), 0, st, n, flags, sums.p);
-    hipLaunchKernelGGL(tracks_scan_top_kernel, dim3(1), dim3(kT), 0, st, nb, sums.p, total);
-    hipLaunchKernelGGL(tracks_scan_add_kernel, dim3((unsigned)nb), dim3(kT), 0, st, n, flags, sums.p, out);
-    check_launch("tracks_scan");
-}
+struct Block { int32_t changed[kBatch]; int32_t firstbad; u64 cnt[C_COUNT]; };   // what the host reads during a call
 
 void run_device(int64_t n64, const int64_t *foff, const double *xy, const uint8_t *registered, int64_t npairs, const int32_t *pi, const int32_t *pj,
                 const int64_t *moff, const int32_t *f1, const int32_t *f2, const TracksSettings &cfg, int32_t *out_cam, int32_t *out_feat,
                 int32_t *out_track, double *out_xy, int32_t *label, TracksOutcome &out, std::chrono::steady_clock::time_point t_start, hipStream_t st) {
     const int n = (int)n64, F = (int)foff[n64];
     const int64_t E = moff[npairs];
-    Pinned pin;
+    Pinned<Block> pin;
     DevBuf<int64_t> dfoff, dmoff;
     DevBuf<double> dxy, doxy;
     DevBuf<uint8_t> dreg;
@@ -413,54 +263,35 @@ void run_device(int64_t n64, const int64_t *foff, const double *xy, const uint8_
     firstbad.alloc(1, false);
     pin.h->firstbad = INT32_MAX;   // (above every match number)
     XM_HIP_CHECK(hipMemcpyAsync(firstbad.p, &pin.h->firstbad, sizeof(int32_t), hipMemcpyHostToDevice, st));
-    fresh(changed, (size_t)kTracksMaxRounds + kTracksBatch, 0, st);
+    fresh(changed, (size_t)kMaxRounds + kBatch, 0, st);
     fresh(cflag, (size_t)F, 0, st); fresh(cdupreg, (size_t)F, 0, st); fresh(size, (size_t)F, 0, st); fresh(regc, (size_t)F, 0, st);
     fresh(status, (size_t)F, 0, st);
     fimg.alloc((size_t)F, false); p.alloc((size_t)F, false); keep.alloc((size_t)F, false); tnum.alloc((size_t)F, false);
     dlabel.alloc((size_t)F, false); rowflag.alloc((size_t)F, false); rowoff.alloc((size_t)F, false);
-    sums.alloc((size_t)(F / kTracksScanTile + 1), false);
+    sums.alloc((size_t)(F / kScanTile + 1), false);
     docam.alloc((size_t)F, false); dofeat.alloc((size_t)F, false); dotrack.alloc((size_t)F, false); doxy.alloc((size_t)F * 2, false);
-    wait_stream(st, cfg.watchdog_s, "the upload");
+    wait_stream(st, cfg.watchdog_s, kStage, "the upload");
     out.seconds_index = secs_since(t_start);
     const auto t_kernels = std::chrono::steady_clock::now();
     double seconds_aside = 0.0;   // the host split, which is timed on its own
 
-    const unsigned ge = grid_of(E), gf = grid_of(F);
-    hipLaunchKernelGGL(tracks_expand_kernel, dim3(grid_for(E)), dim3(kT), 0, st, E, (int)npairs, dmoff.p, dpi.p, dpj.p, dfoff.p, df1.p, df2.p, eu.p, ev.p,
+    const unsigned gf = grid_of(F);
+    hipLaunchKernelGGL(tracks_expand_kernel, dim3(grid_for(E, 4096)), dim3(kT), 0, st, E, (int)npairs, dmoff.p, dpi.p, dpj.p, dfoff.p, df1.p, df2.p, eu.p, ev.p,
                        touched.p, firstbad.p);
-    hipLaunchKernelGGL(tracks_feat_kernel, dim3(grid_for(F)), dim3(kT), 0, st, F, n, dfoff.p, touched.p, fimg.p, p.p, tcnt.p);
+    hipLaunchKernelGGL(tracks_feat_kernel, dim3(grid_for(F, 4096)), dim3(kT), 0, st, F, n, dfoff.p, touched.p, fimg.p, p.p, tcnt.p);
     check_launch("tracks_expand");
     std::vector<int32_t> tc((size_t)n);
     XM_HIP_CHECK(hipMemcpyAsync(tc.data(), tcnt.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     XM_HIP_CHECK(hipMemcpyAsync(&pin.h->firstbad, firstbad.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    wait_stream(st, cfg.watchdog_s, "the matches");
+    wait_stream(st, cfg.watchdog_s, kStage, "the matches");
     if ((int64_t)pin.h->firstbad < E) {
         const int64_t e = pin.h->firstbad;
         const int64_t k = (std::upper_bound(moff, moff + npairs + 1, e) - moff) - 1;
         throw Error(XM_ERR_ARG, "xm_build_tracks: feature index out of range at match " + std::to_string(e) + " (pair " + std::to_string(k) + ")");
     }
 
-    // components: kTracksBatch rounds, then one look at their changed words
-    int rounds = 0;
-    bool converged = false;
-    while (!converged) {
-        if (rounds >= kTracksMaxRounds)
-            throw Error(XM_ERR_HIP, "tracks: the component labels did not converge in " + std::to_string(kTracksMaxRounds) + " rounds");
-        for (int k = 0; k < kTracksBatch; ++k) {
-            int32_t *word = changed.p + rounds + k;
-            const int32_t *prev = rounds + k > 0 ? word - 1 : nullptr;   // the round before this one's word
-            hipLaunchKernelGGL(tracks_hook_kernel, dim3(ge), dim3(kT), 0, st, E, eu.p, ev.p, p.p, prev, word);
-            hipLaunchKernelGGL(tracks_jump_kernel, dim3(gf), dim3(kT), 0, st, F, p.p, prev, word);
-        }
-        check_launch("tracks_components");
-        XM_HIP_CHECK(hipMemcpyAsync(pin.h->changed, changed.p + rounds, kTracksBatch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, "the component labels");
-        for (int k = 0; k < kTracksBatch && !converged; ++k) {
-            ++rounds;
-            converged = pin.h->changed[k] == 0;
-        }
-    }
-    out.rounds = rounds;
+    const TracksEdge edge = {eu.p, ev.p};
+    out.rounds = label_components(E, F, edge, p.p, changed.p, pin.h->changed, kStage, cfg.watchdog_s, st);
 
     // the images by the size of the kernel that looks for their conflicts
     std::vector<int32_t> large, wsl;
@@ -500,20 +331,20 @@ void run_device(int64_t n64, const int64_t *foff, const double *xy, const uint8_
 
     if (cfg.conflict == XM_TRACKS_SPLIT) {
         XM_HIP_CHECK(hipMemcpyAsync(pin.h->cnt, cnt.p, sizeof(u64) * C_COUNT, hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, "the conflicts");
+        wait_stream(st, cfg.watchdog_s, kStage, "the conflicts");
         if (pin.h->cnt[C_CONFLICTED] > 0) {
             const auto t_split = std::chrono::steady_clock::now();
             sedges.alloc((size_t)E, false);
-            hipLaunchKernelGGL(tracks_compact_kernel, dim3(grid_for(E)), dim3(kT), 0, st, E, eu.p, ev.p, p.p, cflag.p, cnt.p, sedges.p);
+            hipLaunchKernelGGL(tracks_compact_kernel, dim3(grid_for(E, 4096)), dim3(kT), 0, st, E, eu.p, ev.p, p.p, cflag.p, cnt.p, sedges.p);
             check_launch("tracks_compact_kernel");
             XM_HIP_CHECK(hipMemcpyAsync(pin.h->cnt, cnt.p, sizeof(u64) * C_COUNT, hipMemcpyDeviceToHost, st));
-            wait_stream(st, cfg.watchdog_s, "the conflicted edges");
+            wait_stream(st, cfg.watchdog_s, kStage, "the conflicted edges");
             const u64 ns = pin.h->cnt[C_NSPLIT];
             if (ns > (u64)E) throw Error(XM_ERR_HIP, "tracks: more conflicted edges than matches");
             std::vector<uint64_t> edges((size_t)ns);
             static_assert(sizeof(uint64_t) == sizeof(u64), "the edge words are copied as they are");
             if (ns) XM_HIP_CHECK(hipMemcpyAsync(edges.data(), sedges.p, (size_t)ns * sizeof(u64), hipMemcpyDeviceToHost, st));
-            wait_stream(st, cfg.watchdog_s, "the conflicted edges");
+            wait_stream(st, cfg.watchdog_s, kStage, "the conflicted edges");
             TrackSplit sp;
             tracks_split(n64, foff, edges, sp);
             out.edges_split = sp.distinct; out.unions_refused = sp.refused;
@@ -528,7 +359,7 @@ void run_device(int64_t n64, const int64_t *foff, const double *xy, const uint8_
             XM_HIP_CHECK(hipMemsetAsync(regc.p, 0, (size_t)F * sizeof(int32_t), st));
             hipLaunchKernelGGL(tracks_size_kernel, dim3(gf), dim3(kT), 0, st, F, touched.p, p.p, fimg.p, reg, size.p, regc.p);
             check_launch("tracks_size_kernel (after the split)");
-            wait_stream(st, cfg.watchdog_s, "the split labels");   // (the splitter's arrays are read by the copies above)
+            wait_stream(st, cfg.watchdog_s, kStage, "the split labels");   // (the splitter's arrays are read by the copies above)
             seconds_aside = secs_since(t_split);
             out.seconds_split = seconds_aside;
         }
@@ -545,7 +376,7 @@ void run_device(int64_t n64, const int64_t *foff, const double *xy, const uint8_
                            dotrack.p, doxy.p);
         check_launch("tracks_emit_kernel");
         XM_HIP_CHECK(hipMemcpyAsync(pin.h->cnt, cnt.p, sizeof(u64) * C_COUNT, hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, "the rows");
+        wait_stream(st, cfg.watchdog_s, kStage, "the rows");
     };
     number_and_emit();
     if ((int64_t)pin.h->cnt[C_NTRACKS] - 1 > cfg.max_tracks) {   // (max_tracks + 1 could overflow)
@@ -554,7 +385,7 @@ void run_device(int64_t n64, const int64_t *foff, const double *xy, const uint8_
         XM_HIP_CHECK(hipMemcpyAsync(hsize.data(), size.p, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         XM_HIP_CHECK(hipMemcpyAsync(hkeep.data(), keep.p, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         XM_HIP_CHECK(hipMemcpyAsync(hstatus.data(), status.p, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, "the sizes");
+        wait_stream(st, cfg.watchdog_s, kStage, "the sizes");
         std::vector<uint64_t> order;   // (size << 32 | label): the larger word is the track that stays
         for (int g = 0; g < F; ++g)
             if (hkeep[(size_t)g]) order.push_back(((uint64_t)(uint32_t)hsize[(size_t)g] << 32) | (uint64_t)(uint32_t)g);
@@ -581,7 +412,7 @@ void run_device(int64_t n64, const int64_t *foff, const double *xy, const uint8_
         XM_HIP_CHECK(hipMemcpyAsync(out_xy, doxy.p, no * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     if (label) XM_HIP_CHECK(hipMemcpyAsync(label, dlabel.p, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    wait_stream(st, cfg.watchdog_s, "the download");
+    wait_stream(st, cfg.watchdog_s, kStage, "the download");
     out.seconds_download = secs_since(t_down);
     out.nout = (int64_t)no; out.ntracks = (int64_t)c[C_NTRACKS];
     out.features_touched = (int64_t)c[C_TOUCHED]; out.components = (int64_t)c[C_COMPONENTS];

@@ -12,12 +12,12 @@
 //   vg_score_chunk_kernel  pairs above kVgGroupMatches: one workgroup per chunk of kVgGroupMatches matches does the first sweep; the two
 //   vg_score_final_kernel  counts of every chunk go to a workspace; one workgroup per pair adds them in chunk order and does the second sweep
 //   vg_decide_kernel       one thread per pair: rules 5 and 6, the pair's status, the `linked` mark of its two images
-//   vg_hook_kernel /       FastSV hooking and pointer jumping on int32 image labels over the valid pairs as xm_tracks.hip's (atomicMin; a
-//   vg_jump_kernel         component's final label is its smallest image); kVgBatch rounds are enqueued ahead of the host
+//   stage_hook_kernel<VgEdge> /  xm_stage.h's FastSV hooking and pointer jumping on int32 image labels over the valid pairs (atomicMin;
+//   stage_jump_kernel      a component's final label is its smallest image); kBatch rounds are enqueued ahead of the host
 //   vg_size_kernel         images per component (integer atomicAdd)
 //   vg_largest_kernel      one workgroup: arg-max of (size, smallest label) and the number of components, by a fixed LDS reduction
 //   vg_prune_kernel        registered_out; OUTSIDE; the kept inlier count of every pair
-//   vg_scan_*              exclusive prefix sum of the kept counts (three launches, as xm_clean.hip's): moff_out
+//   stage_scan_*_kernel    xm_stage.h's exclusive prefix sum of the kept counts (three launches): moff_out
 //   vg_emit_kernel<TEAM>   one team per kept pair: its inliers in input order through a ballot prefix
 //   vg_stats_kernel        the counters per status and per model, inliers
 #pragma once
@@ -32,9 +32,6 @@ namespace xm {
 constexpr int kVgThreads = 256;          // threads per workgroup (four wavefronts)
 constexpr int kVgWaveMatches = 256;      // most matches of a pair that one wavefront runs
 constexpr int kVgGroupMatches = 8192;    // most matches of a pair that one workgroup runs; the chunk of the workspace form
-constexpr int kVgMaxRounds = 1024;       // more hooking rounds than this: XM_ERR_HIP
-constexpr int kVgBatch = 4;              // rounds enqueued between two looks at the changed words
-constexpr int kVgScanTile = 1024;        // entries per workgroup of the prefix sum
 
 struct VgSettings {
     bool score = true;

@@ -6,11 +6,10 @@
 #include <cmath>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "xm_viewgraph.h"
-#include "xm_common.h"
+#include "xm_stage.h"
 
 // every product and every sum of the contract is rounded on its own
 #pragma clang fp contract(off)
@@ -18,10 +17,10 @@
 namespace xm {
 namespace {
 
-typedef unsigned long long u64;
 constexpr int kT = kVgThreads;
 constexpr int kWaves = kT / 64;
-static_assert(kT == 256 && kVgGroupMatches % kT == 0 && kVgWaveMatches % 64 == 0, "the sweeps run whole tiles");
+static_assert(kT == kStageThreads && kVgGroupMatches % kT == 0 && kVgWaveMatches % 64 == 0, "the sweeps run whole tiles, the helpers of xm_stage.h this workgroup size");
+constexpr const char *kStage = "view graph";
 
 // what the scoring does with a pair (set on the host from the flag, valid_in and the model)
 enum { MD_ZERO = 0, MD_ONES, MD_E, MD_F, MD_H };
@@ -30,24 +29,7 @@ enum { C_STATUS = 0, C_MODEL = 6, C_INLIERS = 10, C_MOUT, C_COUNT };
 // slots of the result of vg_largest_kernel
 enum { B_LABEL = 0, B_SIZE, B_COMPONENTS, B_COUNT };
 
-__device__ inline int lane() { return (int)(threadIdx.x & 63u); }
-__device__ inline int ldi(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ inline double dot3(double a0, double a1, double a2, double b0, double b1, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
-// *dst += v over the lanes with pred; whole wavefronts
-__device__ inline void wave_sum_to(u64 *dst, bool pred, u64 v) {
-    v = pred ? v : 0ull;
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if (lane() == 0 && v) atomicAdd(dst, v);
-}
-// the largest k in [0, count) with off[k] <= x (off[0] <= x): at most 32 steps
-__device__ inline int owner_of(const int64_t *off, int count, int64_t x) {
-    int lo = 0, hi = count;
-    while (hi - lo > 1) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // rule 0, for the features of the images that a scored E pair touches
 __global__ __launch_bounds__(kT) void vg_bearing_kernel(int F, int n, const int64_t *foff, const uint8_t *needb, const double *xy, const double *Kinv,
@@ -212,7 +194,7 @@ __device__ inline int second_sweep(const ScoreArgs &a, const Geo &g, int64_t m0,
 // the four wavefronts' counts in wavefront order
 __device__ inline void group_sum2(int &x, int &y, int *lds) {
     const int w = (int)threadIdx.x >> 6;
-    if (lane() == 0) { lds[w] = x; lds[kWaves + w] = y; }
+    if (lane_id() == 0) { lds[w] = x; lds[kWaves + w] = y; }
     __syncthreads();
     x = ((lds[0] + lds[1]) + lds[2]) + lds[3];
     y = ((lds[kWaves] + lds[kWaves + 1]) + lds[kWaves + 2]) + lds[kWaves + 3];
@@ -225,7 +207,7 @@ __global__ __launch_bounds__(kT) void vg_score_kernel(ScoreArgs a) {
     constexpr int TEAM = GROUP ? kT : 64;
     const int item = GROUP ? (int)blockIdx.x : (int)blockIdx.x * kWaves + ((int)threadIdx.x >> 6);
     if (item >= a.nwork) return;   // (a whole team)
-    const int tid = GROUP ? (int)threadIdx.x : lane();
+    const int tid = GROUP ? (int)threadIdx.x : lane_id();
     const int k = a.work[item];
     const int64_t m0 = a.moff[k], m1 = a.moff[k + 1];
     if (m1 - m0 > (GROUP ? kVgGroupMatches : kVgWaveMatches)) return;   // (the host lists it for a larger form)
@@ -303,29 +285,15 @@ __global__ __launch_bounds__(kT) void vg_decide_kernel(DecideArgs a) {
     if (st == XM_VG_VALID) { a.linked[i] = 1; a.linked[j] = 1; }   // (every writer stores the same value)
 }
 
-// components: labels p over the images; p[v] <= v always (xm_tracks.hip's scheme)
-__global__ __launch_bounds__(kT) void vg_hook_kernel(int npairs, const int32_t *pi, const int32_t *pj, const int32_t *status, int32_t *p, const int32_t *before,
-                                                     int32_t *changed) {
-    if (before && *before == 0) return;   // the round before this one changed nothing: the labels are final
-    const int k = (int)(blockIdx.x * kT + threadIdx.x);
-    if (k >= npairs || status[k] != XM_VG_VALID) return;
-    const int u = pi[k], v = pj[k];
-    const int pu = ldi(p + u), pv = ldi(p + v);
-    const int gu = ldi(p + pu), gv = ldi(p + pv);
-    if (gu == gv) return;
-    if (gv < gu) { atomicMin(p + pu, gv); atomicMin(p + u, gv); }
-    else { atomicMin(p + pv, gu); atomicMin(p + v, gu); }
-    *changed = 1;
-}
-__global__ __launch_bounds__(kT) void vg_jump_kernel(int n, int32_t *p, const int32_t *before, int32_t *changed) {
-    if (before && *before == 0) return;
-    const int v = (int)(blockIdx.x * kT + threadIdx.x);
-    if (v >= n) return;
-    const int p0 = ldi(p + v);
-    int r = p0, x = ldi(p + r);
-    while (x != r) { r = x; x = ldi(p + r); }   // labels fall strictly along the way: at most v steps
-    if (r != p0) { p[v] = r; *changed = 1; }
-}
+// components: labels p over the images; a pair that is still valid is an edge
+struct VgEdge {
+    const int32_t *pi, *pj, *status;
+    __device__ bool operator()(int64_t k, int &u, int &v) const {
+        if (status[k] != XM_VG_VALID) return false;
+        u = pi[k]; v = pj[k];
+        return true;
+    }
+};
 __global__ __launch_bounds__(kT) void vg_size_kernel(int n, const int32_t *linked, const int32_t *p, int32_t *size) {
     const int i = (int)(blockIdx.x * kT + threadIdx.x);
     if (i < n && linked[i]) atomicAdd(size + p[i], 1);
@@ -380,62 +348,6 @@ __global__ __launch_bounds__(kT) void vg_stats_kernel(int npairs, const int32_t 
     wave_sum_to(cnt + C_INLIERS, in, in ? (u64)(uint32_t)pair_inliers[k] : 0ull);
 }
 
-// ---- exclusive prefix sum of int32 counts in three launches (a copy of xm_tracks.hip's)
-__device__ inline int block_scan_excl(int t, int *lds, int *total) {
-    const int tid = (int)threadIdx.x;
-    lds[tid] = t;
-    __syncthreads();
-    for (int off = 1; off < kT; off <<= 1) {
-        const int v = tid >= off ? lds[tid - off] : 0;
-        __syncthreads();
-        lds[tid] += v;
-        __syncthreads();
-    }
-    const int incl = lds[tid];
-    *total = lds[kT - 1];
-    __syncthreads();
-    return incl - t;
-}
-__global__ __launch_bounds__(kT) void vg_scan_sums_kernel(int n, const int32_t *flags, int32_t *sums) {
-    __shared__ int lds[kT];
-    const int base = (int)blockIdx.x * kVgScanTile + (int)threadIdx.x * 4;
-    int t = 0;
-    for (int j = 0; j < 4; ++j)
-        if (base + j < n) t += flags[base + j];
-    int total;
-    block_scan_excl(t, lds, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(kT) void vg_scan_top_kernel(int nb, int32_t *sums, u64 *total_out) {
-    __shared__ int lds[kT];
-    int carry = 0;
-    for (int base = 0; base < nb; base += kVgScanTile) {
-        const int i0 = base + (int)threadIdx.x * 4;
-        int v[4], t = 0;
-        for (int j = 0; j < 4; ++j) { v[j] = i0 + j < nb ? sums[i0 + j] : 0; t += v[j]; }
-        int total;
-        int ex = carry + block_scan_excl(t, lds, &total);
-        for (int j = 0; j < 4; ++j) {
-            if (i0 + j < nb) sums[i0 + j] = ex;
-            ex += v[j];
-        }
-        carry += total;
-    }
-    if (threadIdx.x == 0) *total_out = (u64)(uint32_t)carry;
-}
-__global__ __launch_bounds__(kT) void vg_scan_add_kernel(int n, const int32_t *flags, const int32_t *sums, int32_t *out) {
-    __shared__ int lds[kT];
-    const int base = (int)blockIdx.x * kVgScanTile + (int)threadIdx.x * 4;
-    int v[4], t = 0;
-    for (int j = 0; j < 4; ++j) { v[j] = base + j < n ? flags[base + j] : 0; t += v[j]; }
-    int total;
-    int ex = sums[blockIdx.x] + block_scan_excl(t, lds, &total);
-    for (int j = 0; j < 4; ++j) {
-        if (base + j < n) out[base + j] = ex;
-        ex += v[j];
-    }
-}
-
 // the inliers of a kept pair at its offset, in input order
 template <bool GROUP>
 __global__ __launch_bounds__(kT) void vg_emit_kernel(int nwork, const int32_t *work, const int64_t *moff, const uint8_t *inl, const int32_t *keepcnt,
@@ -444,7 +356,7 @@ __global__ __launch_bounds__(kT) void vg_emit_kernel(int nwork, const int32_t *w
     constexpr int TEAM = GROUP ? kT : 64;
     const int item = GROUP ? (int)blockIdx.x : (int)blockIdx.x * kWaves + ((int)threadIdx.x >> 6);
     if (item >= nwork) return;   // (a whole team)
-    const int tid = GROUP ? (int)threadIdx.x : lane();
+    const int tid = GROUP ? (int)threadIdx.x : lane_id();
     const int k = work[item];
     if (keepcnt[k] == 0) return;
     const int64_t m0 = moff[k], m1 = moff[k + 1];
@@ -453,10 +365,10 @@ __global__ __launch_bounds__(kT) void vg_emit_kernel(int nwork, const int32_t *w
         const int64_t e = base + tid;
         const bool on = e < m1 && inl[e] != 0;
         const u64 mask = __ballot(on);
-        int before = __popcll(mask & ((1ull << lane()) - 1ull)), tot = __popcll(mask);
+        int before = __popcll(mask & ((1ull << lane_id()) - 1ull)), tot = __popcll(mask);
         if (GROUP) {
             const int w = (int)threadIdx.x >> 6;
-            if (lane() == 0) wtot[w] = tot;
+            if (lane_id() == 0) wtot[w] = tot;
             __syncthreads();
             tot = 0;
             for (int x = 0; x < kWaves; ++x) { if (x < w) before += wtot[x]; tot += wtot[x]; }
@@ -467,44 +379,7 @@ __global__ __launch_bounds__(kT) void vg_emit_kernel(int nwork, const int32_t *w
     }
 }
 
-double secs_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); }
-
-// host wait on the stream, bounded by the watchdog
-void wait_stream(hipStream_t st, double limit, const char *what) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-        const hipError_t q = hipStreamQuery(st);
-        if (q == hipSuccess) return;
-        if (q != hipErrorNotReady) {
-            (void)hipGetLastError();
-            throw Error(XM_ERR_HIP, std::string("view graph: device error while waiting for ") + what + ": " + hipGetErrorString(q));
-        }
-        if (secs_since(t0) > limit)
-            throw Error(XM_ERR_HIP, std::string("view graph: watchdog: no progress for ") + std::to_string((int)limit) + " s while waiting for " + what);
-        std::this_thread::yield();
-    }
-}
-
-struct Pinned {   // what the host reads during a call
-    struct Block { int32_t changed[kVgBatch]; int32_t firstbad; int32_t best[B_COUNT]; u64 cnt[C_COUNT]; } *h = nullptr;
-    Pinned() { XM_HIP_CHECK(hipHostMalloc((void **)&h, sizeof(Block), hipHostMallocDefault)); }
-    ~Pinned() { if (h) (void)hipHostFree(h); }
-    Pinned(const Pinned &) = delete;
-    Pinned &operator=(const Pinned &) = delete;
-};
-
-template <class T>
-void upload(DevBuf<T> &b, const T *src, size_t n, hipStream_t st) {
-    b.alloc(n, false);
-    if (n) XM_HIP_CHECK(hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, st));
-}
-template <class T>
-void fresh(DevBuf<T> &b, size_t n, int byte, hipStream_t st) {   // n entries filled with `byte` on the stream
-    b.alloc(n, false);
-    XM_HIP_CHECK(hipMemsetAsync(b.p, byte, (n ? n : 1) * sizeof(T), st));
-}
-unsigned grid_of(int64_t items) { return (unsigned)((items + kT - 1) / kT); }
-unsigned grid_for(int64_t items) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + kT - 1) / kT, 4096)); }
+struct Block { int32_t changed[kBatch]; int32_t firstbad; int32_t best[B_COUNT]; u64 cnt[C_COUNT]; };   // what the host reads during a call
 
 void run_device(int n, const int64_t *foff, const double *xy, const double *focal, const double *Kinv, const double *bearing, int npairs, const int32_t *pi,
                 const int32_t *pj, const int32_t *model, const double *Rrel, const double *trel, const double *FH, const uint8_t *valid_in,
@@ -541,7 +416,7 @@ void run_device(int n, const int64_t *foff, const double *xy, const double *foca
     std::vector<int32_t> iota((size_t)n);
     for (int i = 0; i < n; ++i) iota[(size_t)i] = i;
 
-    Pinned pin;
+    Pinned<Block> pin;
     DevBuf<int64_t> dfoff, dmoff;
     DevBuf<double> dxy, dfocal, dKinv, dbear, dRrel, dtrel, dFH, drot;
     DevBuf<uint8_t> dvalid, dreg, dneedb, dcode, dregout;
@@ -582,20 +457,20 @@ void run_device(int n, const int64_t *foff, const double *xy, const double *foca
     dcode.alloc((size_t)E, false);
     fresh(dinl, (size_t)npairs, 0, st);   // (a pair without matches runs in no scoring kernel)
     dstatus.alloc((size_t)npairs, false); keepcnt.alloc((size_t)npairs, false); koff.alloc((size_t)npairs, false);
-    sums.alloc((size_t)(npairs / kVgScanTile + 1), false);
+    sums.alloc((size_t)(npairs / kScanTile + 1), false);
     fresh(linked, (size_t)n, 0, st); fresh(size, (size_t)n, 0, st); fresh(cnt, C_COUNT, 0, st);
-    fresh(changed, (size_t)kVgMaxRounds + kVgBatch, 0, st);
+    fresh(changed, (size_t)kMaxRounds + kBatch, 0, st);
     best.alloc(B_COUNT, false); dregout.alloc((size_t)n, false);
     do1.alloc((size_t)E, false); do2.alloc((size_t)E, false);
     firstbad.alloc(1, false);
     pin.h->firstbad = INT32_MAX;   // (above every match number)
     XM_HIP_CHECK(hipMemcpyAsync(firstbad.p, &pin.h->firstbad, sizeof(int32_t), hipMemcpyHostToDevice, st));
-    wait_stream(st, cfg.watchdog_s, "the upload");
+    wait_stream(st, cfg.watchdog_s, kStage, "the upload");
     out.seconds_index = secs_since(t_start);
     const auto t_kernels = std::chrono::steady_clock::now();
 
     if (any_E && !bearing) {
-        hipLaunchKernelGGL(vg_bearing_kernel, dim3(grid_for(F)), dim3(kT), 0, st, F, n, dfoff.p, dneedb.p, dxy.p, dKinv.p, dbear.p);
+        hipLaunchKernelGGL(vg_bearing_kernel, dim3(grid_for(F, 4096)), dim3(kT), 0, st, F, n, dfoff.p, dneedb.p, dxy.p, dKinv.p, dbear.p);
         check_launch("vg_bearing_kernel");
     }
     ScoreArgs a;
@@ -629,42 +504,20 @@ void run_device(int n, const int64_t *foff, const double *xy, const double *foca
     check_launch("vg_decide_kernel");
     XM_HIP_CHECK(hipMemcpyAsync(&pin.h->firstbad, firstbad.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
 
-    // components: kVgBatch rounds, then one look at their changed words
-    int rounds = 0;
-    bool converged = false;
-    while (!converged) {
-        if (rounds >= kVgMaxRounds)
-            throw Error(XM_ERR_HIP, "view graph: the component labels did not converge in " + std::to_string(kVgMaxRounds) + " rounds");
-        for (int k = 0; k < kVgBatch; ++k) {
-            int32_t *word = changed.p + rounds + k;
-            const int32_t *prev = rounds + k > 0 ? word - 1 : nullptr;   // the round before this one's word
-            hipLaunchKernelGGL(vg_hook_kernel, dim3(gp), dim3(kT), 0, st, npairs, dpi.p, dpj.p, dstatus.p, p.p, prev, word);
-            hipLaunchKernelGGL(vg_jump_kernel, dim3(gn), dim3(kT), 0, st, n, p.p, prev, word);
-        }
-        check_launch("vg_components");
-        XM_HIP_CHECK(hipMemcpyAsync(pin.h->changed, changed.p + rounds, kVgBatch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, "the component labels");
-        if (rounds == 0 && (int64_t)pin.h->firstbad < E) {
-            const int64_t e = pin.h->firstbad;
-            const int64_t k = (std::upper_bound(moff, moff + npairs + 1, e) - moff) - 1;
-            throw Error(XM_ERR_ARG, "xm_view_graph_filter: feature index out of range at match " + std::to_string(e) + " (pair " + std::to_string(k) + ")");
-        }
-        for (int k = 0; k < kVgBatch && !converged; ++k) {
-            ++rounds;
-            converged = pin.h->changed[k] == 0;
-        }
+    // the first wait is in label_components: firstbad, whose copy is enqueued above, is looked at behind it
+    const VgEdge edge = {dpi.p, dpj.p, dstatus.p};
+    out.rounds = label_components(npairs, n, edge, p.p, changed.p, pin.h->changed, kStage, cfg.watchdog_s, st);
+    if ((int64_t)pin.h->firstbad < E) {
+        const int64_t e = pin.h->firstbad;
+        const int64_t k = (std::upper_bound(moff, moff + npairs + 1, e) - moff) - 1;
+        throw Error(XM_ERR_ARG, "xm_view_graph_filter: feature index out of range at match " + std::to_string(e) + " (pair " + std::to_string(k) + ")");
     }
-    out.rounds = rounds;
 
     hipLaunchKernelGGL(vg_size_kernel, dim3(gn), dim3(kT), 0, st, n, linked.p, p.p, size.p);
     hipLaunchKernelGGL(vg_largest_kernel, dim3(1), dim3(kT), 0, st, n, linked.p, p.p, size.p, best.p);
     hipLaunchKernelGGL(vg_prune_kernel, dim3(std::max(gp, gn)), dim3(kT), 0, st, n, npairs, dpi.p, linked.p, p.p, best.p, dinl.p, dstatus.p, dregout.p, keepcnt.p);
     check_launch("vg_prune_kernel");
-    const int nb = (npairs + kVgScanTile - 1) / kVgScanTile;
-    hipLaunchKernelGGL(vg_scan_sums_kernel, dim3((unsigned)nb), dim3(kT), 0, st, npairs, keepcnt.p, sums.p);
-    hipLaunchKernelGGL(vg_scan_top_kernel, dim3(1), dim3(kT), 0, st, nb, sums.p, cnt.p + C_MOUT);
-    hipLaunchKernelGGL(vg_scan_add_kernel, dim3((unsigned)nb), dim3(kT), 0, st, npairs, keepcnt.p, sums.p, koff.p);
-    check_launch("vg_scan");
+    exclusive_scan(npairs, keepcnt.p, koff.p, sums, cnt.p + C_MOUT, st);
     if (!lwave.empty())
         hipLaunchKernelGGL(vg_emit_kernel<false>, dim3((unsigned)((lwave.size() + kWaves - 1) / kWaves)), dim3(kT), 0, st, (int)lwave.size(), dlwave.p, dmoff.p,
                            dcode.p, keepcnt.p, koff.p, df1.p, df2.p, do1.p, do2.p);
@@ -678,7 +531,7 @@ void run_device(int n, const int64_t *foff, const double *xy, const double *foca
     check_launch("vg_emit_kernel");
     XM_HIP_CHECK(hipMemcpyAsync(pin.h->cnt, cnt.p, sizeof(u64) * C_COUNT, hipMemcpyDeviceToHost, st));
     XM_HIP_CHECK(hipMemcpyAsync(pin.h->best, best.p, sizeof(int32_t) * B_COUNT, hipMemcpyDeviceToHost, st));
-    wait_stream(st, cfg.watchdog_s, "the kept matches");
+    wait_stream(st, cfg.watchdog_s, kStage, "the kept matches");
     out.seconds_kernels = secs_since(t_kernels);
     const auto t_down = std::chrono::steady_clock::now();
     const u64 *c = pin.h->cnt;
@@ -694,7 +547,7 @@ void run_device(int n, const int64_t *foff, const double *xy, const double *foca
         XM_HIP_CHECK(hipMemcpyAsync(f1_out, do1.p, no * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         XM_HIP_CHECK(hipMemcpyAsync(f2_out, do2.p, no * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
-    wait_stream(st, cfg.watchdog_s, "the download");
+    wait_stream(st, cfg.watchdog_s, kStage, "the download");
     for (int k = 0; k < npairs; ++k) moff_out[k] = hkoff[(size_t)k];
     moff_out[npairs] = (int64_t)no;
     out.seconds_download = secs_since(t_down);
