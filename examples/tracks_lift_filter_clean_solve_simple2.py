@@ -13,7 +13,9 @@ reference's pipeline hands on for assets/SIMPLE2 (tests/golden/simple2/obs.npz),
 projects to; the matches are generated from them (tests/xm_tracks_numpy.py, simple2_case: every co-visible pair of a landmark's features
 with probability 0.6, 0.1 % wrong matches); the maps are rendered as in lift_filter_clean_solve_simple2.py.  The same downstream stages
 run a second time from the TRUE tracks (the landmark numbers of obs.npz), which is the figure lift_filter_clean_solve_simple2.py prints
-without its duplicated rows, so the two rotation errors stand next to each other.  Needs an MI355X."""
+without its duplicated rows, so the two rotation errors stand next to each other.  Needs an MI355X.
+    --split-device   the conflicted components are split on the device (conflict="split_device", XM_TRACKS_SPLIT_DEVICE) instead of on the
+                     host: the same tracks bit for bit, so every number printed is the one of the plain run; only the times differ"""
 import os
 import sys
 
@@ -87,7 +89,8 @@ order = np.lexsort((lm, cam))
 case = tn.simple2_case()
 assert case["foff"][-1] == cam.size
 fxy = xy[order]
-for policy in ("split", "drop", "glomap"):
+SPLIT = "split_device" if "--split-device" in sys.argv[1:] else "split"
+for policy in (SPLIT, "drop", "glomap"):
     t = xmamd.build_tracks(case["foff"], fxy, case["pi"], case["pj"], (case["moff"], case["f1"], case["f2"]), conflict=policy)
     i = t.info
     # how the tracks sit on the true landmarks: a track is pure when all its rows carry one landmark
@@ -95,12 +98,12 @@ for policy in ("split", "drop", "glomap"):
     o = np.lexsort((true_lm, t.track))
     mixed = np.unique(t.track[o][1:][(t.track[o][1:] == t.track[o][:-1]) & (true_lm[o][1:] != true_lm[o][:-1])]).size
     print(f"tracks ({policy}): {i['matches']} matches over {i['features_touched']} of {cam.size} features -> {i['components']} components, "
-          f"{i['components_conflicted']} conflicted ({i['rows_conflicted']} features, {i['edges_split']} edges split on the host, {i['unions_refused']} unions refused); "
+          f"{i['components_conflicted']} conflicted ({i['rows_conflicted']} features, {i['edges_split']} edges split on the {'device' if policy == 'split_device' else 'host'}, {i['unions_refused']} unions refused); "
           f"{t.m} tracks, {t.cam.size} rows, {mixed} tracks mix landmarks; dropped: {i['tracks_short']} short, {i['tracks_conflict']} by the policy; "
           f"{i['rounds']} hooking rounds, images by kernel size {i['images_small']} / {i['images_large']} / {i['images_workspace']}; "
           f"{1e3 * (i['seconds_index'] + i['seconds_kernels'] + i['seconds_split'] + i['seconds_download']):.2f} ms "
-          f"({1e3 * i['seconds_kernels']:.2f} ms of kernels, {1e3 * i['seconds_split']:.2f} ms host split)")
-    if policy == "split":
+          f"({1e3 * i['seconds_kernels']:.2f} ms of kernels, {1e3 * i['seconds_split']:.2f} ms {'device' if policy == 'split_device' else 'host'} split)")
+    if policy == SPLIT:
         table = t
-downstream("from the matches (split)", table.cam, table.track, table.xy, table.m)
+downstream(f"from the matches ({SPLIT})", table.cam, table.track, table.xy, table.m)
 downstream("from the true tracks", cam[order], lm[order], fxy, m)

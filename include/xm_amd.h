@@ -552,7 +552,10 @@ int xm_lift_limits(int64_t out[4]);
  *                        every label is still the set's smallest member.  ON PURPOSE this departs from the fork: the fork puts the refused
  *                        endpoint into the other endpoint's track all the same (:102-105), which :125-136 then discards or keeps with two
  *                        rows of one image.  That step is not reproduced.  The split is sequential; it runs on the host over the edges of
- *                        the conflicted components only (xm_tracks_split_host) and is timed on its own.
+ *                        the conflicted components only (xm_tracks_split_host) and is timed on its own.  It is sequential only inside a
+ *                        component, and a union never crosses components: with XM_TRACKS_SPLIT_DEVICE in flags every conflicted
+ *                        component is split by a team of its own on the device, walking the component's distinct edges in the same
+ *                        ascending order, which gives the same sets and so the same bits (see the flag).
  *   5. A track is dropped when its observation count (all images, :161, :163) is below min_views or above max_views, or when the number of
  *      distinct REGISTERED images in it (:186-197) is below min_views.
  *   6. If more than max_tracks + 1 tracks remain, the max_tracks + 1 longest stay (:219 breaks on `>`).  Ties go to the larger label; the
@@ -576,6 +579,17 @@ int xm_lift_limits(int64_t out[4]);
 #define XM_TRACKS_DROP   0
 #define XM_TRACKS_GLOMAP 1
 #define XM_TRACKS_SPLIT  2
+/* xm_tracks_options_t.flags.  XM_TRACKS_SPLIT_DEVICE: rule 4's split runs on the device; valid with conflict == XM_TRACKS_SPLIT only
+ * (XM_ERR_ARG with another policy).  Opt-in: nothing chooses it automatically, and every output equals the host split's bit for bit.  The
+ * edge words of the conflicted components are counted per component (integer atomicAdd), placed into one segment per component (two
+ * prefix sums and an integer slot counter whose order nothing depends on) and handed to one team per component: a wavefront for at most
+ * 64 endpoints and 512 listed edges, a workgroup of 256 for at most 4 096 listed edges (xm_tracks_split_limits).  The team sorts the
+ * segment in LDS, drops equal neighbours, lists the distinct endpoints and walks the edges in order; every endpoint carries the smallest
+ * local index of its set, so no find is needed.  A component above the workgroup's cap goes to the host splitter as before; one call may
+ * use both.  No floating-point atomic, no atomic decides an order or a value, no workgroup waits on another, and the walk is bounded by
+ * the cap.  Bit 0 is left undefined ON PURPOSE: flags = 1 has always been refused as an unknown flag, callers rely on that refusal, and
+ * a later meaning for it would turn their error into a silent change. */
+#define XM_TRACKS_SPLIT_DEVICE 2u
 #define XM_TRACK_UNTOUCHED      (-1)   /* label[]: the feature is in no match */
 #define XM_TRACK_SHORT          (-2)   /* fewer than min_views observations */
 #define XM_TRACK_LONG           (-3)   /* more than max_views observations */
@@ -589,7 +603,7 @@ typedef struct {
     int32_t conflict;              /* XM_TRACKS_SPLIT */
     int64_t max_tracks;            /* 10000000 */
     double thres_inconsistency;    /* 10.0 px; XM_TRACKS_GLOMAP only */
-    uint32_t flags;                /* none defined */
+    uint32_t flags;                /* 0, or XM_TRACKS_SPLIT_DEVICE */
     uint32_t reserved;
 } xm_tracks_options_t;
 #define XM_TRACKS_OPTIONS_INIT { (uint32_t)sizeof(xm_tracks_options_t), 3, 1000000, XM_TRACKS_SPLIT, 10000000, 10.0, 0u, 0u }
@@ -604,11 +618,13 @@ typedef struct {
     int64_t tracks_short, tracks_long, tracks_conflict, tracks_few_registered, tracks_beyond_max;   /* by the first rule that dropped them */
     int64_t images_small, images_large, images_workspace;   /* images with a touched feature, by the size of the kernel that sorted them */
     int64_t max_touched;           /* most touched features of one image */
-    int64_t edges_split;           /* DISTINCT edges handed to the host splitter (XM_TRACKS_SPLIT) */
-    int64_t unions_refused;        /* ... of which it refused */
+    int64_t edges_split;           /* XM_TRACKS_SPLIT: DISTINCT edges of the conflicted components, whether the host or the device split them */
+    int64_t unions_refused;        /* ... of which the split refused */
     double seconds_index;          /* host: checks and upload */
-    double seconds_kernels;
-    double seconds_split;          /* XM_TRACKS_SPLIT: download of the conflicted edges, the host split, upload of the new labels */
+    double seconds_kernels;        /* without seconds_split */
+    double seconds_split;          /* XM_TRACKS_SPLIT: download of the conflicted edges, the host split, upload of the new labels; with
+                                      XM_TRACKS_SPLIT_DEVICE: from the first launch of the split until the labels are final, the host's
+                                      part for components above the cap included */
     double seconds_download;
 } xm_tracks_result_t;
 int xm_build_tracks(int64_t n, const int64_t *foff, const double *xy, const uint8_t *registered /* n or NULL */, int64_t npairs, const int32_t *pi,
@@ -622,6 +638,20 @@ int xm_tracks_limits(int64_t out[4]);
  * refused (or NULL): the distinct edges and the unions refused.  Needs no device. */
 int xm_tracks_split_host(int64_t n, const int64_t *foff, int64_t nedges, const int32_t *eu, const int32_t *ev, int32_t *label, int64_t *distinct,
                          int64_t *refused);
+/* Test export: the same on the device, with the split code xm_build_tracks runs under XM_TRACKS_SPLIT_DEVICE.  Arguments, checks and
+ * outputs as xm_tracks_split_host.  The components of the given edges are labelled on the device and every one is treated as one to
+ * split (nothing is ever refused inside a conflict-free one).  An index out of range: XM_ERR_ARG, nothing written.  No edge needs no device. */
+int xm_tracks_split_device(int64_t n, const int64_t *foff, int64_t nedges, const int32_t *eu, const int32_t *ev, int32_t *label, int64_t *distinct,
+                           int64_t *refused);
+/* The forms of the device split; needs no device.  out[0]: most endpoints of a component in the wavefront form; out[1]: most raw (listed)
+ * edges of a component in the wavefront form; out[2]: most raw edges of a component in the workgroup form (above: the host splitter);
+ * out[3]: threads per workgroup.  A form that is not built reports 0. */
+int xm_tracks_split_limits(int64_t out[4]);
+/* What the calling thread's most recent xm_build_tracks or xm_tracks_split_device did (thread-local as xm_last_error, zeroed when either
+ * call starts; needs no device).  out[0], out[1], out[2]: components split in the wavefront form, in the workgroup form, on the host;
+ * out[3], out[4]: raw edges given to the device forms, to the host; out[5]: distinct edges; out[6]: unions refused; out[7]: 0.  All 0
+ * without XM_TRACKS_SPLIT_DEVICE. */
+int xm_tracks_split_stats(int64_t out[8]);
 /* ---- Two-view match verification and view-graph pruning, on the device: the stage that produces what xm_build_tracks reads (the inlier
  * matches of the valid pairs, and `registered`) and the pair list xm_pair_filter reads.  It stands for the block in front of track
  * establishment in the reference's fork of GLOMAP, deps/glomap/glomap/controllers/global_mapper.cc:56-111: ImagePairsInlierCount

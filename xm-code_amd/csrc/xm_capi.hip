@@ -735,6 +735,7 @@ int xm_build_tracks(int64_t n, const int64_t *foff, const double *xy, const uint
                     const int64_t *moff, const int32_t *f1, const int32_t *f2, const xm_tracks_options_t *opt, int32_t *out_cam, int32_t *out_feat,
                     int32_t *out_track, double *out_xy, int64_t *nout, int32_t *label, xm_tracks_result_t *res) {
     XM_TRY
+    xm::tracks_split_stats_clear();
     const std::string w("xm_build_tracks");
     const int64_t lim = (int64_t)1 << 31;
     if (!opt || !res || !nout) throw xm::Error(XM_ERR_ARG, w + ": null argument");
@@ -747,7 +748,8 @@ int xm_build_tracks(int64_t n, const int64_t *foff, const double *xy, const uint
         throw xm::Error(XM_ERR_ARG, w + ": thres_inconsistency is negative or not finite");
     if (opt->conflict != XM_TRACKS_DROP && opt->conflict != XM_TRACKS_GLOMAP && opt->conflict != XM_TRACKS_SPLIT)
         throw xm::Error(XM_ERR_ARG, w + ": unknown conflict policy");
-    if (opt->flags) throw xm::Error(XM_ERR_ARG, w + ": unknown flag");
+    if (opt->flags & ~XM_TRACKS_SPLIT_DEVICE) throw xm::Error(XM_ERR_ARG, w + ": unknown flag");
+    if (opt->flags && opt->conflict != XM_TRACKS_SPLIT) throw xm::Error(XM_ERR_ARG, w + ": XM_TRACKS_SPLIT_DEVICE goes with XM_TRACKS_SPLIT only");
     if (n < 0 || npairs < 0) throw xm::Error(XM_ERR_ARG, w + ": negative size");
     if (n >= lim || npairs >= lim) throw xm::Error(XM_ERR_ARG, w + ": images and pairs must each stay below 2^31");
     if (n > 0 && !foff) throw xm::Error(XM_ERR_ARG, w + ": null feature offsets");
@@ -769,7 +771,7 @@ int xm_build_tracks(int64_t n, const int64_t *foff, const double *xy, const uint
     if (F > 0 && (!xy || !out_cam || !out_feat || !out_track || !out_xy)) throw xm::Error(XM_ERR_ARG, w + ": null feature or output arrays");
     xm::TracksSettings c;
     c.min_views = opt->min_views; c.max_views = opt->max_views; c.conflict = opt->conflict; c.max_tracks = opt->max_tracks;
-    c.thres_inconsistency = opt->thres_inconsistency;
+    c.thres_inconsistency = opt->thres_inconsistency; c.split_device = (opt->flags & XM_TRACKS_SPLIT_DEVICE) != 0;
     if (n > 0 && E > 0) require_device();
     if (const char *e = std::getenv("XM_WATCHDOG_S")) { const double v = std::atof(e); if (v > 0) c.watchdog_s = v; }
     xm::TracksOutcome r;
@@ -821,6 +823,56 @@ int xm_tracks_split_host(int64_t n, const int64_t *foff, int64_t nedges, const i
     for (size_t v = 0; v < sp.feat.size(); ++v) label[sp.feat[v]] = sp.label[v];
     if (distinct) *distinct = sp.distinct;
     if (refused) *refused = sp.refused;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_tracks_split_device(int64_t n, const int64_t *foff, int64_t nedges, const int32_t *eu, const int32_t *ev, int32_t *label, int64_t *distinct,
+                           int64_t *refused) {
+    XM_TRY
+    xm::tracks_split_stats_clear();
+    const std::string w("xm_tracks_split_device");
+    if (n < 0 || nedges < 0) throw xm::Error(XM_ERR_ARG, w + ": negative size");
+    if (n >= ((int64_t)1 << 31) || nedges >= ((int64_t)1 << 31)) throw xm::Error(XM_ERR_ARG, w + ": images and edges must each stay below 2^31");
+    if (n > 0 && !foff) throw xm::Error(XM_ERR_ARG, w + ": null feature offsets");
+    if (n > 0 && foff[0] != 0) throw xm::Error(XM_ERR_ARG, w + ": foff does not start at 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (foff[i + 1] < foff[i]) throw xm::Error(XM_ERR_ARG, w + ": foff decreases at image " + std::to_string(i));
+    const int64_t F = n > 0 ? foff[n] : 0;
+    if (F >= ((int64_t)1 << 31)) throw xm::Error(XM_ERR_ARG, w + ": features must stay below 2^31");
+    if (nedges > 0 && (!eu || !ev)) throw xm::Error(XM_ERR_ARG, w + ": null edge arrays");
+    if (F > 0 && !label) throw xm::Error(XM_ERR_ARG, w + ": null label array");
+    std::vector<int32_t> lo((size_t)nedges), hi((size_t)nedges);
+    for (int64_t e = 0; e < nedges; ++e) {
+        if (eu[e] < 0 || eu[e] >= F || ev[e] < 0 || ev[e] >= F) throw xm::Error(XM_ERR_ARG, w + ": feature index out of range at edge " + std::to_string(e));
+        lo[(size_t)e] = std::min(eu[e], ev[e]); hi[(size_t)e] = std::max(eu[e], ev[e]);
+    }
+    int64_t d = 0, r = 0;
+    if (nedges > 0) {
+        require_device();
+        double watchdog_s = xm::TracksSettings().watchdog_s;
+        if (const char *e = std::getenv("XM_WATCHDOG_S")) { const double v = std::atof(e); if (v > 0) watchdog_s = v; }
+        std::vector<int32_t> out((size_t)F);
+        xm::tracks_split_device_host(n, foff, nedges, lo.data(), hi.data(), out.data(), d, r, watchdog_s);
+        std::memcpy(label, out.data(), (size_t)F * sizeof(int32_t));
+    } else {
+        for (int64_t g = 0; g < F; ++g) label[g] = -1;
+    }
+    if (distinct) *distinct = d;
+    if (refused) *refused = r;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_tracks_split_limits(int64_t out[4]) {
+    XM_TRY
+    if (!out) throw xm::Error(XM_ERR_ARG, "xm_tracks_split_limits: null output");
+    out[0] = xm::kSplitWaveEnds; out[1] = xm::kSplitWaveEdges; out[2] = xm::kSplitGroupEdges; out[3] = xm::kTracksThreads;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_tracks_split_stats(int64_t out[8]) {
+    XM_TRY
+    if (!out) throw xm::Error(XM_ERR_ARG, "xm_tracks_split_stats: null output");
+    xm::tracks_split_stats_get(out);
     return XM_OK;
     XM_CATCH
 }

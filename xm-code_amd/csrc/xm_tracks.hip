@@ -21,6 +21,9 @@ namespace {
 constexpr int kT = kTracksThreads;
 static_assert(kT == kStageThreads && kT == kSortThreads, "the helpers of xm_stage.h and xm_sortstat.h are written for this workgroup size");
 static_assert((kTracksSmallRows & (kTracksSmallRows - 1)) == 0 && (kTracksLdsRows & (kTracksLdsRows - 1)) == 0, "the sort pads to a power of two");
+static_assert((kSplitWaveEdges & (kSplitWaveEdges - 1)) == 0 && (kSplitGroupEdges & (kSplitGroupEdges - 1)) == 0 && kSplitWaveEdges <= kSplitGroupEdges,
+              "the split's sorts pad to a power of two");
+static_assert(kSplitWaveEnds == 64, "the wavefront form keeps one endpoint per lane and one image per bit of a 64-bit word");
 constexpr const char *kStage = "tracks";
 
 // slots of the device counter block
@@ -190,6 +193,219 @@ __global__ __launch_bounds__(kT) void tracks_relabel_kernel(int k, const int32_t
     if (x < k) p[feat[x]] = lab[x];
 }
 
+// ---- XM_TRACKS_SPLIT_DEVICE: rule 4's split on the device.  A union never crosses components, so walking each component's distinct
+// edges in ascending (smaller id, larger id) order gives exactly the sets of the host splitter's global sorted walk.
+// slots of the split's counter block
+enum { S_COMPONENTS = 0, S_EDGES, S_DISTINCT, S_REFUSED, S_BROKEN, S_COUNT };
+
+// raw edges per flagged component, at its label
+__global__ __launch_bounds__(kT) void split_count_kernel(int64_t E, const int32_t *eu, const int32_t *p, const int32_t *cflag, int32_t *ecnt) {
+    for (int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x; e < E; e += (int64_t)gridDim.x * kT) {
+        const int u = eu[e];
+        if (u < 0) continue;
+        const int r = p[u];
+        if (cflag[r] != 0) atomicAdd(ecnt + r, 1);
+    }
+}
+__global__ __launch_bounds__(kT) void split_roots_kernel(int F, const int32_t *ecnt, int32_t *isroot) {
+    const int g = (int)(blockIdx.x * kT + threadIdx.x);
+    if (g < F) isroot[g] = ecnt[g] > 0 ? 1 : 0;
+}
+// the flagged roots in label order: (label, first word of its segment, raw edges, endpoints)
+__global__ __launch_bounds__(kT) void split_list_kernel(int F, const int32_t *ecnt, const int32_t *segoff, const int32_t *rpos, const int32_t *size, int cap,
+                                                        int4 *list) {
+    const int g = (int)(blockIdx.x * kT + threadIdx.x);
+    if (g >= F || ecnt[g] <= 0) return;
+    const int k = rpos[g];
+    if (k < cap) list[k] = make_int4(g, segoff[g], ecnt[g], size[g]);
+}
+// the edge words (smaller id << 32 | larger id) into their component's segment.  The slot counter gives an arbitrary order inside a
+// segment; the teams sort it, so nothing depends on it
+__global__ __launch_bounds__(kT) void split_scatter_kernel(int64_t E, const int32_t *eu, const int32_t *ev, const int32_t *p, const int32_t *cflag,
+                                                           const int32_t *ecnt, const int32_t *segoff, int32_t *slot, u64 *out) {
+    for (int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x; e < E; e += (int64_t)gridDim.x * kT) {
+        const int u = eu[e];
+        if (u < 0) continue;
+        const int r = p[u];
+        if (cflag[r] == 0) continue;
+        const int s = atomicAdd(slot + r, 1);
+        if (s < ecnt[r]) out[(size_t)segoff[r] + (size_t)s] = ((u64)(uint32_t)u << 32) | (u64)(uint32_t)ev[e];
+    }
+}
+__global__ __launch_bounds__(kT) void split_mark_kernel(int k, const int32_t *roots, int32_t *flag) {
+    const int x = (int)(blockIdx.x * kT + threadIdx.x);
+    if (x < k) flag[roots[x]] = 1;
+}
+
+struct SplitArgs {
+    const int2 *work;       // per team: first word of its segment, raw edges
+    int32_t nwork;
+    const u64 *edges;
+    const int64_t *foff;
+    const int32_t *fimg;
+    int32_t *p;
+    u64 *cnt;               // S_* slots
+};
+
+// ascending bitonic sort as sort_values of xm_sortstat.h, for a team of T threads (one workgroup)
+template <int T, class V>
+__device__ inline void team_sort(V *S, int KP) {
+    for (int size = 2; size <= KP; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = (int)threadIdx.x; t < (KP >> 1); t += T) {
+                const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+                const bool up = (i & size) == 0;
+                const V x = S[i], y = S[j];
+                if ((x > y) == up) { S[i] = y; S[j] = x; }
+            }
+            __syncthreads();
+        }
+}
+// the first index in V[0 .. n) whose value is not below x
+__device__ inline int first_not_below(const uint32_t *V, int n, uint32_t x) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (V[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// A team of T threads (one workgroup) and one component of N <= CAP raw edges at edges[off ..): K[0 .. N) becomes the sorted edges as
+// (local index of the smaller id << 32 | local index of the larger id), equal neighbours still in place; V[0 .. nv) the distinct
+// endpoints, ascending (so the smaller local index is the smaller id).  Returns nv; *distinct (per thread) sums to the distinct edges
+// over the team.  K: CAP words, V: 2 CAP words, wtot: T / 64 ints.  Ends with a barrier.
+template <int T, int CAP>
+__device__ inline int split_prepare(const SplitArgs &a, int off, int N, u64 *K, uint32_t *V, int *wtot, int *distinct) {
+    const int tid = (int)threadIdx.x;
+    int KP = 2;
+    while (KP < N) KP <<= 1;
+    for (int q = tid; q < KP; q += T) K[q] = q < N ? a.edges[(size_t)off + (size_t)q] : ~0ull;
+    __syncthreads();
+    team_sort<T>(K, KP);
+    int d = 0;
+    for (int q = tid; q < N; q += T) d += q == 0 || K[q] != K[q - 1] ? 1 : 0;
+    *distinct = d;
+    // both ends of every edge, sorted; ids stay below 2^31, so the padding sorts behind them
+    for (int q = tid; q < 2 * KP; q += T) {
+        const int e = q < KP ? q : q - KP;
+        V[q] = e < N ? (q < KP ? (uint32_t)(K[e] >> 32) : (uint32_t)(K[e] & 0xffffffffull)) : ~0u;
+    }
+    __syncthreads();
+    team_sort<T>(V, 2 * KP);
+    // the distinct values to the front, in place: a value moves to an index that is not above its own, and every entry of a chunk is
+    // read before the chunk's barrier.  V[c0 - 1] is still the value it was: an earlier chunk wrote there only if it kept everything
+    int nv = 0;
+    for (int c0 = 0; c0 < 2 * N; c0 += T) {
+        const int q = c0 + tid;
+        const uint32_t x = q < 2 * N ? V[q] : ~0u;
+        const bool on = q < 2 * N && (q == 0 || V[q - 1] != x);
+        const u64 mask = __ballot(on);
+        const int before = __popcll(mask & ((1ull << lane_id()) - 1ull));
+        if (lane_id() == 0) wtot[tid >> 6] = __popcll(mask);
+        __syncthreads();
+        int at = nv, tot = 0;
+#pragma unroll
+        for (int x2 = 0; x2 < T / 64; ++x2) { if (x2 < (tid >> 6)) at += wtot[x2]; tot += wtot[x2]; }
+        if (on) V[at + before] = x;
+        nv += tot;
+        __syncthreads();
+    }
+    for (int q = tid; q < N; q += T) {
+        const u64 w = K[q];
+        K[q] = ((u64)(uint32_t)first_not_below(V, nv, (uint32_t)(w >> 32)) << 32) | (u64)(uint32_t)first_not_below(V, nv, (uint32_t)(w & 0xffffffffull));
+    }
+    __syncthreads();
+    return nv;
+}
+// the local index of the first endpoint of endpoint g's image: one number per image of the component, below nv
+__device__ inline int image_slot(const SplitArgs &a, const uint32_t *V, int nv, uint32_t g) { return first_not_below(V, nv, (uint32_t)a.foff[a.fimg[g]]); }
+
+// One wavefront (a workgroup of 64) per component of at most kSplitWaveEnds endpoints and kSplitWaveEdges raw edges: lane i keeps
+// endpoint i's set label (the smallest local index of its set) and the set's images as a bit mask in registers; an edge is two
+// label reads, two mask reads and a compare.  8 KB of LDS
+__global__ __launch_bounds__(kSplitWaveEnds) void split_wave_kernel(SplitArgs a) {
+    constexpr int CAP = kSplitWaveEdges;
+    __shared__ u64 K[CAP];
+    __shared__ uint32_t V[2 * CAP];
+    __shared__ int wtot[1];
+    if ((int)blockIdx.x >= a.nwork) return;
+    const int2 w = a.work[blockIdx.x];
+    const int N = w.y;
+    if (N < 1 || N > CAP) { if (threadIdx.x == 0) atomicAdd(a.cnt + S_BROKEN, 1ull); return; }   // (the host lists it for a larger size)
+    int distinct;
+    const int nv = split_prepare<kSplitWaveEnds, CAP>(a, w.x, N, K, V, wtot, &distinct);
+    if (nv > kSplitWaveEnds) { if (threadIdx.x == 0) atomicAdd(a.cnt + S_BROKEN, 1ull); return; }
+    const int lane = (int)threadIdx.x;
+    const bool in = lane < nv;
+    const uint32_t id = in ? V[lane] : 0u;
+    int lab = in ? lane : -1;
+    u64 images = in ? 1ull << image_slot(a, V, nv, id) : 0ull;
+    int refused = 0;
+    u64 prev = ~0ull;
+    for (int q = 0; q < N; ++q) {
+        const u64 e = K[q];   // (the same word in every lane)
+        if (e == prev) continue;
+        prev = e;
+        const int x = __builtin_amdgcn_readfirstlane((int)(e >> 32)), y = __builtin_amdgcn_readfirstlane((int)(e & 0xffffffffull));
+        const int lx = __shfl(lab, x), ly = __shfl(lab, y);
+        if (lx == ly) continue;
+        const u64 mx = __shfl(images, x), my = __shfl(images, y);
+        if (mx & my) { refused += 1; continue; }
+        const int lo = lx < ly ? lx : ly, hi = lx < ly ? ly : lx;
+        if (lab == lo || lab == hi) images = mx | my;
+        if (lab == hi) lab = lo;
+    }
+    const uint32_t first = (uint32_t)__shfl((int)id, in ? lab : 0);
+    if (in) a.p[id] = (int32_t)first;
+    wave_sum_to(a.cnt + S_DISTINCT, true, (u64)distinct);
+    if (lane == 0 && refused) atomicAdd(a.cnt + S_REFUSED, (u64)refused);
+}
+
+// One workgroup per component of at most kSplitGroupEdges raw edges: set labels, image slots and the stamps in LDS.  Per edge that
+// joins two sets: the members of the one stamp mark[image slot] with the edge's number, a barrier, the members of the other look
+// theirs up (nothing is ever cleared), a barrier with the vote, the relabelling, a barrier.  112 KB of LDS
+__global__ __launch_bounds__(kT) void split_group_kernel(SplitArgs a) {
+    constexpr int CAP = kSplitGroupEdges;
+    __shared__ u64 K[CAP];
+    __shared__ uint32_t V[2 * CAP];
+    __shared__ int32_t lab[CAP + 1], slot[CAP + 1], mark[CAP + 1];
+    __shared__ int wtot[kT / 64];
+    if ((int)blockIdx.x >= a.nwork) return;
+    const int2 w = a.work[blockIdx.x];
+    const int N = w.y;
+    const int tid = (int)threadIdx.x;
+    if (N < 1 || N > CAP) { if (tid == 0) atomicAdd(a.cnt + S_BROKEN, 1ull); return; }   // (the host splits it)
+    int distinct;
+    const int nv = split_prepare<kT, CAP>(a, w.x, N, K, V, wtot, &distinct);
+    if (nv > CAP + 1) { if (tid == 0) atomicAdd(a.cnt + S_BROKEN, 1ull); return; }   // (a connected component has at most one endpoint more than edges)
+    for (int i = tid; i < nv; i += kT) { lab[i] = i; slot[i] = image_slot(a, V, nv, V[i]); mark[i] = 0; }
+    __syncthreads();
+    int refused = 0;
+    u64 prev = ~0ull;
+    for (int q = 0; q < N; ++q) {
+        const u64 e = K[q];   // (the same word in every thread: every branch below is taken by the whole workgroup)
+        if (e == prev) continue;
+        prev = e;
+        const int lx = lab[(int)(e >> 32)], ly = lab[(int)(e & 0xffffffffull)];
+        if (lx == ly) continue;
+        const int stamp = q + 1;
+        for (int i = tid; i < nv; i += kT)
+            if (lab[i] == lx) mark[slot[i]] = stamp;
+        __syncthreads();
+        int hit = 0;
+        for (int i = tid; i < nv; i += kT)
+            if (lab[i] == ly && mark[slot[i]] == stamp) hit = 1;
+        if (__syncthreads_or(hit)) { refused += 1; continue; }
+        const int lo = lx < ly ? lx : ly, hi = lx < ly ? ly : lx;
+        for (int i = tid; i < nv; i += kT)
+            if (lab[i] == hi) lab[i] = lo;
+        __syncthreads();
+    }
+    for (int i = tid; i < nv; i += kT) a.p[V[i]] = (int32_t)V[lab[i]];
+    wave_sum_to(a.cnt + S_DISTINCT, true, (u64)distinct);
+    if (tid == 0 && refused) atomicAdd(a.cnt + S_REFUSED, (u64)refused);
+}
+
 struct Rules { int32_t min_views, max_views, conflict; };
 // per component (at its label): status 0 = kept, or the code of the first rule that drops it
 __global__ __launch_bounds__(kT) void tracks_decide_kernel(int F, const int32_t *touched, const int32_t *p, const int32_t *size, const int32_t *regc,
@@ -235,7 +451,112 @@ __global__ __launch_bounds__(kT) void tracks_emit_kernel(int F, const int64_t *f
     oxy[2 * o] = xy[2 * (size_t)g]; oxy[2 * o + 1] = xy[2 * (size_t)g + 1];
 }
 
-struct Block { int32_t changed[kBatch]; int32_t firstbad; u64 cnt[C_COUNT]; };   // what the host reads during a call
+struct Block { int32_t changed[kBatch]; int32_t firstbad; u64 cnt[C_COUNT]; u64 scnt[S_COUNT]; };   // what the host reads during a call
+
+thread_local int64_t t_split_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // xm_tracks_split_stats
+
+// rule 4 on the host for the components whose label carries a flag: their edges come down, tracks_split walks them, the new labels go
+// up.  Everything is enqueued when it returns; hs stays alive until the caller has waited for the stream (the uploads read it)
+struct SplitHost {
+    DevBuf<u64> sedges;
+    DevBuf<int32_t> sfeat, slab;
+    TrackSplit sp;
+};
+void split_on_host(int64_t n64, const int64_t *foff, int64_t E, const int32_t *eu, const int32_t *ev, int32_t *p, const int32_t *flag, u64 *cnt,
+                   Pinned<Block> &pin, double watchdog_s, hipStream_t st, SplitHost &hs) {
+    hs.sedges.alloc((size_t)E, false);
+    hipLaunchKernelGGL(tracks_compact_kernel, dim3(grid_for(E, 4096)), dim3(kT), 0, st, E, eu, ev, p, flag, cnt, hs.sedges.p);
+    check_launch("tracks_compact_kernel");
+    XM_HIP_CHECK(hipMemcpyAsync(pin.h->cnt, cnt, sizeof(u64) * C_COUNT, hipMemcpyDeviceToHost, st));
+    wait_stream(st, watchdog_s, kStage, "the conflicted edges");
+    const u64 ns = pin.h->cnt[C_NSPLIT];
+    if (ns > (u64)E) throw Error(XM_ERR_HIP, "tracks: more conflicted edges than matches");
+    std::vector<uint64_t> edges((size_t)ns);
+    static_assert(sizeof(uint64_t) == sizeof(u64), "the edge words are copied as they are");
+    if (ns) XM_HIP_CHECK(hipMemcpyAsync(edges.data(), hs.sedges.p, (size_t)ns * sizeof(u64), hipMemcpyDeviceToHost, st));
+    wait_stream(st, watchdog_s, kStage, "the conflicted edges");
+    tracks_split(n64, foff, edges, hs.sp);
+    upload(hs.sfeat, hs.sp.feat.data(), hs.sp.feat.size(), st);
+    upload(hs.slab, hs.sp.label.data(), hs.sp.label.size(), st);
+    if (!hs.sp.feat.empty())
+        hipLaunchKernelGGL(tracks_relabel_kernel, dim3(grid_of((int64_t)hs.sp.feat.size())), dim3(kT), 0, st, (int)hs.sp.feat.size(), hs.sfeat.p, hs.slab.p, p);
+}
+
+// XM_TRACKS_SPLIT_DEVICE: rule 4 for the components whose label carries a flag in cflag (each has an edge), on the device; the
+// components above the workgroup form's cap go through split_on_host.  size: endpoints per component, at its label; ncap: no more
+// flagged components than this; sums: F / kScanTile + 1 entries.  Everything is enqueued when it returns, the copy of the counters
+// into pin.h->scnt included: the caller waits for the stream, then calls split_collect.  ds stays alive until then
+struct SplitDevice {
+    DevBuf<int32_t> ecnt, isroot, segoff, rpos, slot, hroots, hflag;
+    DevBuf<int4> list;
+    DevBuf<int2> wwork, gwork;
+    DevBuf<u64> scnt, segs;
+    std::vector<int2> wlist, glist;   // what wwork and gwork are uploaded from
+    std::vector<int32_t> hlist;
+    SplitHost hs;
+    int64_t wave = 0, group = 0, host = 0, edges_device = 0, edges_host = 0;
+};
+void split_on_device(int64_t n64, const int64_t *foff, const int64_t *dfoff, int F, int64_t E, const int32_t *eu, const int32_t *ev, int32_t *p,
+                     const int32_t *cflag, const int32_t *size, const int32_t *fimg, int64_t ncap, DevBuf<int32_t> &sums, u64 *cnt, Pinned<Block> &pin,
+                     double watchdog_s, hipStream_t st, SplitDevice &ds) {
+    fresh(ds.ecnt, (size_t)F, 0, st); fresh(ds.slot, (size_t)F, 0, st); fresh(ds.scnt, S_COUNT, 0, st);
+    ds.isroot.alloc((size_t)F, false); ds.segoff.alloc((size_t)F, false); ds.rpos.alloc((size_t)F, false);
+    ds.list.alloc((size_t)ncap, false); ds.segs.alloc((size_t)E, false);
+    const unsigned gf = grid_of(F), ge = grid_for(E, 4096);
+    hipLaunchKernelGGL(split_count_kernel, dim3(ge), dim3(kT), 0, st, E, eu, p, cflag, ds.ecnt.p);
+    exclusive_scan(F, ds.ecnt.p, ds.segoff.p, sums, ds.scnt.p + S_EDGES, st);
+    hipLaunchKernelGGL(split_roots_kernel, dim3(gf), dim3(kT), 0, st, F, ds.ecnt.p, ds.isroot.p);
+    exclusive_scan(F, ds.isroot.p, ds.rpos.p, sums, ds.scnt.p + S_COMPONENTS, st);
+    hipLaunchKernelGGL(split_list_kernel, dim3(gf), dim3(kT), 0, st, F, ds.ecnt.p, ds.segoff.p, ds.rpos.p, size, (int)ncap, ds.list.p);
+    hipLaunchKernelGGL(split_scatter_kernel, dim3(ge), dim3(kT), 0, st, E, eu, ev, p, cflag, ds.ecnt.p, ds.segoff.p, ds.slot.p, ds.segs.p);
+    check_launch("split_scatter_kernel");
+    std::vector<int4> list((size_t)ncap);
+    XM_HIP_CHECK(hipMemcpyAsync(pin.h->scnt, ds.scnt.p, sizeof(u64) * S_COUNT, hipMemcpyDeviceToHost, st));
+    if (ncap) XM_HIP_CHECK(hipMemcpyAsync(list.data(), ds.list.p, (size_t)ncap * sizeof(int4), hipMemcpyDeviceToHost, st));
+    wait_stream(st, watchdog_s, kStage, "the conflicted components");
+    const u64 nc = pin.h->scnt[S_COMPONENTS];
+    if (nc > (u64)ncap || pin.h->scnt[S_EDGES] > (u64)E) throw Error(XM_ERR_HIP, "tracks: more conflicted components or edges than there can be");
+    // the components by the form that splits them, in label order
+    std::vector<int2> &wwork = ds.wlist, &gwork = ds.glist;
+    std::vector<int32_t> &hroots = ds.hlist;
+    for (size_t k = 0; k < (size_t)nc; ++k) {
+        const int4 c = list[k];   // (label, first word, raw edges, endpoints)
+        if (c.z <= kSplitWaveEdges && c.w <= kSplitWaveEnds) { wwork.push_back(make_int2(c.y, c.z)); ds.edges_device += c.z; }
+        else if (c.z <= kSplitGroupEdges) { gwork.push_back(make_int2(c.y, c.z)); ds.edges_device += c.z; }
+        else { hroots.push_back(c.x); ds.edges_host += c.z; }
+    }
+    ds.wave = (int64_t)wwork.size(); ds.group = (int64_t)gwork.size(); ds.host = (int64_t)hroots.size();
+    SplitArgs a;
+    a.edges = ds.segs.p; a.foff = dfoff; a.fimg = fimg; a.p = p; a.cnt = ds.scnt.p;
+    if (!wwork.empty()) {
+        upload(ds.wwork, wwork.data(), wwork.size(), st);
+        a.work = ds.wwork.p; a.nwork = (int32_t)wwork.size();
+        hipLaunchKernelGGL(split_wave_kernel, dim3((unsigned)a.nwork), dim3(kSplitWaveEnds), 0, st, a);
+        check_launch("split_wave_kernel");
+    }
+    if (!gwork.empty()) {
+        upload(ds.gwork, gwork.data(), gwork.size(), st);
+        a.work = ds.gwork.p; a.nwork = (int32_t)gwork.size();
+        hipLaunchKernelGGL(split_group_kernel, dim3((unsigned)a.nwork), dim3(kT), 0, st, a);
+        check_launch("split_group_kernel");
+    }
+    if (!hroots.empty()) {
+        upload(ds.hroots, hroots.data(), hroots.size(), st);
+        fresh(ds.hflag, (size_t)F, 0, st);
+        hipLaunchKernelGGL(split_mark_kernel, dim3(grid_of((int64_t)hroots.size())), dim3(kT), 0, st, (int)hroots.size(), ds.hroots.p, ds.hflag.p);
+        check_launch("split_mark_kernel");
+        split_on_host(n64, foff, E, eu, ev, p, ds.hflag.p, cnt, pin, watchdog_s, st, ds.hs);
+    }
+    XM_HIP_CHECK(hipMemcpyAsync(pin.h->scnt, ds.scnt.p, sizeof(u64) * S_COUNT, hipMemcpyDeviceToHost, st));
+}
+// behind the caller's wait: the counts of both paths, and the calling thread's statistics
+void split_collect(Pinned<Block> &pin, const SplitDevice &ds, int64_t &distinct, int64_t &refused) {
+    if (pin.h->scnt[S_BROKEN]) throw Error(XM_ERR_HIP, "tracks: a component did not fit the form it was listed for");
+    distinct = (int64_t)pin.h->scnt[S_DISTINCT] + ds.hs.sp.distinct;
+    refused = (int64_t)pin.h->scnt[S_REFUSED] + ds.hs.sp.refused;
+    const int64_t s[8] = {ds.wave, ds.group, ds.host, ds.edges_device, ds.edges_host, distinct, refused, 0};
+    std::memcpy(t_split_stats, s, sizeof(s));
+}
 
 void run_device(int64_t n64, const int64_t *foff, const double *xy, const uint8_t *registered, int64_t npairs, const int32_t *pi, const int32_t *pj,
                 const int64_t *moff, const int32_t *f1, const int32_t *f2, const TracksSettings &cfg, int32_t *out_cam, int32_t *out_feat,
@@ -247,8 +568,8 @@ void run_device(int64_t n64, const int64_t *foff, const double *xy, const uint8_
     DevBuf<double> dxy, doxy;
     DevBuf<uint8_t> dreg;
     DevBuf<int32_t> dpi, dpj, df1, df2, eu, ev, touched, fimg, p, tcnt, firstbad, changed, cflag, cdupreg, size, regc, status, keep, tnum, dlabel, rowflag,
-        rowoff, sums, dlarge, dwsl, sfeat, slab, docam, dofeat, dotrack;
-    DevBuf<u64> cnt, ws, sedges;
+        rowoff, sums, dlarge, dwsl, docam, dofeat, dotrack;
+    DevBuf<u64> cnt, ws;
     upload(dfoff, foff, (size_t)n + 1, st);
     upload(dmoff, moff, (size_t)npairs + 1, st);
     upload(dxy, xy, (size_t)F * 2, st);
@@ -334,24 +655,13 @@ void run_device(int64_t n64, const int64_t *foff, const double *xy, const uint8_
         wait_stream(st, cfg.watchdog_s, kStage, "the conflicts");
         if (pin.h->cnt[C_CONFLICTED] > 0) {
             const auto t_split = std::chrono::steady_clock::now();
-            sedges.alloc((size_t)E, false);
-            hipLaunchKernelGGL(tracks_compact_kernel, dim3(grid_for(E, 4096)), dim3(kT), 0, st, E, eu.p, ev.p, p.p, cflag.p, cnt.p, sedges.p);
-            check_launch("tracks_compact_kernel");
-            XM_HIP_CHECK(hipMemcpyAsync(pin.h->cnt, cnt.p, sizeof(u64) * C_COUNT, hipMemcpyDeviceToHost, st));
-            wait_stream(st, cfg.watchdog_s, kStage, "the conflicted edges");
-            const u64 ns = pin.h->cnt[C_NSPLIT];
-            if (ns > (u64)E) throw Error(XM_ERR_HIP, "tracks: more conflicted edges than matches");
-            std::vector<uint64_t> edges((size_t)ns);
-            static_assert(sizeof(uint64_t) == sizeof(u64), "the edge words are copied as they are");
-            if (ns) XM_HIP_CHECK(hipMemcpyAsync(edges.data(), sedges.p, (size_t)ns * sizeof(u64), hipMemcpyDeviceToHost, st));
-            wait_stream(st, cfg.watchdog_s, kStage, "the conflicted edges");
-            TrackSplit sp;
-            tracks_split(n64, foff, edges, sp);
-            out.edges_split = sp.distinct; out.unions_refused = sp.refused;
-            upload(sfeat, sp.feat.data(), sp.feat.size(), st);
-            upload(slab, sp.label.data(), sp.label.size(), st);
-            if (!sp.feat.empty())
-                hipLaunchKernelGGL(tracks_relabel_kernel, dim3(grid_of((int64_t)sp.feat.size())), dim3(kT), 0, st, (int)sp.feat.size(), sfeat.p, slab.p, p.p);
+            SplitHost hs;
+            SplitDevice ds;
+            if (cfg.split_device)
+                split_on_device(n64, foff, dfoff.p, F, E, eu.p, ev.p, p.p, cflag.p, size.p, fimg.p, (int64_t)pin.h->cnt[C_CONFLICTED], sums, cnt.p, pin,
+                                cfg.watchdog_s, st, ds);
+            else
+                split_on_host(n64, foff, E, eu.p, ev.p, p.p, cflag.p, cnt.p, pin, cfg.watchdog_s, st, hs);
             // every track is free of conflicts now: the flags go, and the sizes are counted again under the new labels
             XM_HIP_CHECK(hipMemsetAsync(cflag.p, 0, (size_t)F * sizeof(int32_t), st));
             XM_HIP_CHECK(hipMemsetAsync(cdupreg.p, 0, (size_t)F * sizeof(int32_t), st));
@@ -360,6 +670,8 @@ void run_device(int64_t n64, const int64_t *foff, const double *xy, const uint8_
             hipLaunchKernelGGL(tracks_size_kernel, dim3(gf), dim3(kT), 0, st, F, touched.p, p.p, fimg.p, reg, size.p, regc.p);
             check_launch("tracks_size_kernel (after the split)");
             wait_stream(st, cfg.watchdog_s, kStage, "the split labels");   // (the splitter's arrays are read by the copies above)
+            if (cfg.split_device) split_collect(pin, ds, out.edges_split, out.unions_refused);
+            else { out.edges_split = hs.sp.distinct; out.unions_refused = hs.sp.refused; }
             seconds_aside = secs_since(t_split);
             out.seconds_split = seconds_aside;
         }
@@ -421,7 +733,61 @@ void run_device(int64_t n64, const int64_t *foff, const double *xy, const uint8_
     out.tracks_few_registered = (int64_t)c[C_FEW];
 }
 
+// one thread per edge: both ends are endpoints
+__global__ __launch_bounds__(kT) void split_ends_kernel(int64_t E, const int32_t *eu, const int32_t *ev, int32_t *touched) {
+    const int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x;
+    if (e < E) { touched[eu[e]] = 1; touched[ev[e]] = 1; }   // (every writer stores the same value)
+}
+
+void run_split_device(int64_t n64, const int64_t *foff, int64_t E, const int32_t *eu, const int32_t *ev, int32_t *label, int64_t &distinct, int64_t &refused,
+                      double watchdog_s, hipStream_t st) {
+    const int F = (int)foff[n64];
+    Pinned<Block> pin;
+    DevBuf<int64_t> dfoff;
+    DevBuf<int32_t> deu, dev, dfimg, p, touched, changed, cflag, size, regc, sums;
+    DevBuf<u64> cnt;
+    std::vector<int32_t> fimg((size_t)F), hp((size_t)F), ht((size_t)F);
+    for (int64_t i = 0; i < n64; ++i)
+        for (int64_t g = foff[i]; g < foff[i + 1]; ++g) fimg[(size_t)g] = (int32_t)i;
+    upload(dfoff, foff, (size_t)n64 + 1, st);
+    upload(deu, eu, (size_t)E, st);
+    upload(dev, ev, (size_t)E, st);
+    upload(dfimg, fimg.data(), (size_t)F, st);
+    fresh(touched, (size_t)F, 0, st); fresh(changed, (size_t)kMaxRounds + kBatch, 0, st); fresh(cnt, C_COUNT, 0, st);
+    fresh(cflag, (size_t)F, 1, st);   // (every byte 1: every component is one to split)
+    fresh(size, (size_t)F, 0, st); fresh(regc, (size_t)F, 0, st);
+    p.alloc((size_t)F, false); sums.alloc((size_t)(F / kScanTile + 1), false);
+    identity_labels(F, p.p, st);
+    hipLaunchKernelGGL(split_ends_kernel, dim3(grid_of(E)), dim3(kT), 0, st, E, deu.p, dev.p, touched.p);
+    check_launch("split_ends_kernel");
+    const TracksEdge edge = {deu.p, dev.p};
+    label_components(E, F, edge, p.p, changed.p, pin.h->changed, kStage, watchdog_s, st);
+    hipLaunchKernelGGL(tracks_size_kernel, dim3(grid_of(F)), dim3(kT), 0, st, F, touched.p, p.p, dfimg.p, (const uint8_t *)nullptr, size.p, regc.p);
+    check_launch("tracks_size_kernel");
+    SplitDevice ds;
+    split_on_device(n64, foff, dfoff.p, F, E, deu.p, dev.p, p.p, cflag.p, size.p, dfimg.p, std::min<int64_t>(F, E), sums, cnt.p, pin, watchdog_s, st, ds);
+    XM_HIP_CHECK(hipMemcpyAsync(hp.data(), p.p, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    XM_HIP_CHECK(hipMemcpyAsync(ht.data(), touched.p, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    wait_stream(st, watchdog_s, kStage, "the split labels");
+    split_collect(pin, ds, distinct, refused);
+    for (int g = 0; g < F; ++g) label[g] = ht[(size_t)g] ? hp[(size_t)g] : -1;
+}
+
 }  // namespace
+
+void tracks_split_stats_clear() { std::memset(t_split_stats, 0, sizeof(t_split_stats)); }
+void tracks_split_stats_get(int64_t out[8]) { std::memcpy(out, t_split_stats, sizeof(t_split_stats)); }
+
+void tracks_split_device_host(int64_t n, const int64_t *foff, int64_t nedges, const int32_t *eu, const int32_t *ev, int32_t *label, int64_t &distinct,
+                              int64_t &refused, double watchdog_s) {
+    hipStream_t st = nullptr;
+    try {
+        run_split_device(n, foff, nedges, eu, ev, label, distinct, refused, watchdog_s, st);
+    } catch (...) {
+        (void)hipStreamSynchronize(st);   // the device buffers are freed next: nothing may still be reading them
+        throw;
+    }
+}
 
 void build_tracks_host(int64_t n, const int64_t *foff, const double *xy, const uint8_t *registered, int64_t npairs, const int32_t *pi, const int32_t *pj,
                        const int64_t *moff, const int32_t *f1, const int32_t *f2, const TracksSettings &cfg, int32_t *out_cam, int32_t *out_feat,

@@ -40,7 +40,8 @@ EXPORTS = [
     "xm_ctx_dense_q", "xm_create_matrix", "xm_schur_dense_limits",
     "xm_pair_filter", "xm_pair_filter_limits",
     "xm_lift_observations", "xm_lift_limits",
-    "xm_build_tracks", "xm_tracks_limits", "xm_tracks_split_host", "xm_view_graph_filter", "xm_view_graph_limits",
+    "xm_build_tracks", "xm_tracks_limits", "xm_tracks_split_host", "xm_tracks_split_device", "xm_tracks_split_limits", "xm_tracks_split_stats",
+    "xm_view_graph_filter", "xm_view_graph_limits",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -295,7 +296,8 @@ VG_MODEL_NONE, VG_MODEL_E, VG_MODEL_F, VG_MODEL_H = 0, 1, 2, 3
 VG_MODELS = {"none": VG_MODEL_NONE, "E": VG_MODEL_E, "F": VG_MODEL_F, "H": VG_MODEL_H}
 VG_VALID, VG_INVALID_IN, VG_FEW_INLIERS, VG_LOW_RATIO, VG_ROTATION, VG_OUTSIDE = 0, 1, 2, 3, 4, 5
 TRACKS_DROP, TRACKS_GLOMAP, TRACKS_SPLIT = 0, 1, 2
-TRACKS_POLICIES = {"drop": TRACKS_DROP, "glomap": TRACKS_GLOMAP, "split": TRACKS_SPLIT}
+TRACKS_SPLIT_DEVICE = 2            # xm_tracks_options_t.flags: rule 4's split on the device (with TRACKS_SPLIT only)
+TRACKS_POLICIES = {"drop": TRACKS_DROP, "glomap": TRACKS_GLOMAP, "split": TRACKS_SPLIT, "split_device": TRACKS_SPLIT}
 TRACK_UNTOUCHED, TRACK_SHORT, TRACK_LONG, TRACK_CONFLICT, TRACK_FEW_REGISTERED, TRACK_BEYOND_MAX = -1, -2, -3, -4, -5, -6
 LIFT_MAPS_ON_DEVICE = 1
 PAIR_STAT_DTYPE = np.dtype([("n_joint", "<i4"), ("n_kept", "<i4"), ("n_flagged", "<i4"), ("status", "<i4"), ("scale1", "<f8"), ("scale2", "<f8"),
@@ -376,6 +378,9 @@ def lib():
                                           [C.POINTER(VgResult)]
         L.xm_view_graph_limits.argtypes = [C.c_void_p]
         L.xm_tracks_split_host.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.xm_tracks_split_device.argtypes = L.xm_tracks_split_host.argtypes
+        L.xm_tracks_split_limits.argtypes = [C.c_void_p]
+        L.xm_tracks_split_stats.argtypes = [C.c_void_p]
         L.xm_ctx_reprojection_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_transport.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
         L.xm_ctx_dense_q.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -991,7 +996,8 @@ def build_tracks(foff_or_counts, xy, pi, pj, matches, registered=None, min_views
     """feature tracks from pairwise matches on the device (xm_build_tracks; include/xm_amd.h has the definition and where it departs from
     the reference's fork of GLOMAP): foff_or_counts: the feature offsets (n + 1) or the feature counts (n) of the images; xy: features x 2;
     pi, pj: the images of every pair, 0-based; matches: (moff, f1, f2) or one (k, 2) array of feature indices per pair; registered: per
-    image or None; conflict: "drop", "glomap" or "split".  -> TrackTable"""
+    image or None; conflict: "drop", "glomap", "split" or "split_device" (the split policy with XM_TRACKS_SPLIT_DEVICE: the conflicted components
+    are split on the device, with the same bits).  -> TrackTable"""
     xy = np.ascontiguousarray(xy, dtype=np.float64)
     if xy.ndim != 2 or xy.shape[1] != 2:
         raise XmError("build_tracks: xy must be features x 2")
@@ -1008,7 +1014,8 @@ def build_tracks(foff_or_counts, xy, pi, pj, matches, registered=None, min_views
             raise XmError("build_tracks: registered must have one entry per image")
     if isinstance(conflict, str) and conflict not in TRACKS_POLICIES:
         raise XmError(f"build_tracks: conflict must be one of {sorted(TRACKS_POLICIES)} (or an XM_TRACKS_* number)")
-    opt = TracksOptions(int(min_views), int(max_views), int(TRACKS_POLICIES.get(conflict, conflict)), int(max_tracks), float(thres_inconsistency))
+    opt = TracksOptions(int(min_views), int(max_views), int(TRACKS_POLICIES.get(conflict, conflict)), int(max_tracks), float(thres_inconsistency),
+                        TRACKS_SPLIT_DEVICE if conflict == "split_device" else 0)
     res = TracksResult(); res.struct_size = C.sizeof(TracksResult)
     F = xy.shape[0]
     ocam = np.zeros(F, dtype=np.int32); ofeat = np.zeros(F, dtype=np.int32); otrack = np.zeros(F, dtype=np.int32); oxy = np.zeros((F, 2))
@@ -1032,6 +1039,35 @@ def split_host(foff_or_counts, nfeat, eu, ev):
     P = lambda a: a.ctypes.data_as(C.c_void_p)
     _chk(lib().xm_tracks_split_host(foff.size - 1, P(foff), eu.size, P(eu), P(ev), P(label), C.byref(d), C.byref(r)))
     return label, d.value, r.value
+
+
+def split_device(foff_or_counts, nfeat, eu, ev):
+    """the test export xm_tracks_split_device: as split_host, on the device with the split code of build_tracks(conflict="split_device");
+    every component of the edges is treated as one to split.  -> (label, distinct edges, unions refused)"""
+    foff = _tracks_foff(foff_or_counts, int(nfeat))
+    eu = np.ascontiguousarray(eu, dtype=np.int32).reshape(-1); ev = np.ascontiguousarray(ev, dtype=np.int32).reshape(-1)
+    if eu.size != ev.size:
+        raise XmError("split_device: eu and ev must have one entry per edge")
+    label = np.full(int(nfeat), -1, dtype=np.int32); d = C.c_int64(0); r = C.c_int64(0)
+    P = lambda a: a.ctypes.data_as(C.c_void_p)
+    _chk(lib().xm_tracks_split_device(foff.size - 1, P(foff), eu.size, P(eu), P(ev), P(label), C.byref(d), C.byref(r)))
+    return label, d.value, r.value
+
+
+def tracks_split_limits():
+    """-> dict(wave_endpoints, wave_edges: most endpoints and most raw (listed) edges of a conflicted component that one wavefront splits;
+    group_edges: most raw edges of one that a workgroup splits (above: the host splitter); threads: per workgroup).  Needs no device"""
+    out = np.zeros(4, dtype=np.int64)
+    _chk(lib().xm_tracks_split_limits(out.ctypes.data_as(C.c_void_p)))
+    return dict(wave_endpoints=int(out[0]), wave_edges=int(out[1]), group_edges=int(out[2]), threads=int(out[3]))
+
+
+def tracks_split_stats():
+    """what this thread's most recent build_tracks or split_device did -> dict(wave, group, host: components split in the wavefront form, in the
+    workgroup form, on the host; edges_device, edges_host: raw edges given to either; distinct, refused).  All 0 unless the device split ran"""
+    out = np.zeros(8, dtype=np.int64)
+    _chk(lib().xm_tracks_split_stats(out.ctypes.data_as(C.c_void_p)))
+    return dict(zip(("wave", "group", "host", "edges_device", "edges_host", "distinct", "refused"), (int(x) for x in out[:7])))
 
 
 class ViewGraphPlan:
