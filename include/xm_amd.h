@@ -900,6 +900,79 @@ typedef struct {
 } xm_ba_result_t;
 int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, xm_ba_result_t *res);
 int xm_ctx_reprojection_errors(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, double *sqerr);
+/* ---- Filtering tracks against a refined geometry: the TrackFilter of the reference's fork of GLOMAP
+ * (deps/glomap/glomap/processors/track_filter.cc: FilterTracksByReprojection :7-51, FilterTracksByAngle :53-89,
+ * FilterTrackTriangulationAngle :91-126), which GLOMAP alternates with its bundle adjustment (controllers/global_mapper.cc:243-317), as a
+ * query on the device over the observation lists of an XM_STORAGE_SCHUR context.  NOTHING HERE WAS COMPARED WITH THE REFERENCE'S COMPILED
+ * CODE (it needs COLMAP, Eigen and glog): parity rests on a line-cited sequential restatement (tests/xm_trackfilter_numpy.py).
+ * Input: rot (3 x 3n), t (3 x n), p (3 x n_landmarks), column-major, the layouts of xm_ctx_bundle_adjust: R_i is camera-to-world, t_i the
+ * camera centre, P_l the world point.  An observation e = (i, l) with the camera-frame point p_e is USED when its current weight is > 0
+ * and p_e2 > 0 (the bundle adjustment's rule).  Every product and sum below is rounded on its own, in the order written:
+ *   d = P_l - t_i;  q_a = (R_i[0][a] d_0 + R_i[1][a] d_1) + R_i[2][a] d_2 (q = R_i^T d);  x . y = (x_0 y_0 + x_1 y_1) + x_2 y_2;
+ *   |x| = sqrt(x . x); division and square root are IEEE.
+ *   depth          with XM_TF_REPROJECTION or XM_TF_ANGLE: q_2 < 1e-12 (GLOMAP's EPS, :20, :70) drops the observation.
+ *   reprojection   XM_TF_REPROJECTION (:27-30, :39, the normalised-image branch): u = q_0 / q_2 - p_e0 / p_e2, v = q_1 / q_2 - p_e1 / p_e2; kept
+ *                  iff sqrt(u u + v v) < max_reprojection_error (1e-2 is glomap/types.h:21).  DEPARTURE: the observed point is the bundle
+ *                  adjustment's p_e / p_e2, without the reference's + EPS in the denominator.
+ *   angle          XM_TF_ANGLE (:60-79), on what the reprojection filter left: kept iff (q / |q|) . (p_e / |p_e|) > cos(max_angle_error)
+ *                  (degrees; 1.0 is types.h:20).  DEPARTURE: every camera counts as calibrated (no has_prior_focal_length, no doubled
+ *                  threshold).
+ *   triangulation  XM_TF_TRIANGULATION (:97-121), over the SURVIVORS of a landmark: rays r_e = d / |d|; the landmark is kept iff some pair
+ *                  of survivors has r_e . r_f < cos(min_triangulation_angle) (degrees; 1.0 is types.h:22), otherwise all its observations
+ *                  are dropped; fewer than two survivors: no such pair.
+ *   min_views      > 0: a landmark that is left with fewer observations than that (and at least one) loses them all; applied last
+ *                  (the reference's bundle adjustment skips tracks below 3, bundle_adjustment.cc:65).
+ * The two cosines are computed once on the host, cos(angle * (pi / 180)), and come back in the result: the comparisons above are against
+ * those doubles.  A comparison with a NaN is false (the observation or pair does not pass).
+ * Output (host arrays): keep[nobs] (1 = used and it stays), reason[nobs] (one XM_TF_REASON_* bit for a used observation that is dropped: the
+ * first rule above that drops it; 0 where kept or unused), lm_views[n_landmarks] (observations left after all filters), lm_status
+ * [n_landmarks] (XM_TF_LM_*: KEPT = no rule dropped the landmark as a whole, also when no observation of it is left).  Result: observations
+ * used, kept and dropped per reason; tracks_total = landmarks with a used observation before the call, tracks_kept = landmarks with
+ * lm_views > 0; tracks_changed_* = GLOMAP's return value `counter` of each filter applied in the order above: the landmarks whose list the
+ * reprojection filter changed (:43-46; observations behind the camera included), then the angle filter (:81-84; those included when it
+ * runs first), the landmarks without a qualifying pair (:118-120, which counts a track that an earlier filter of the same call emptied
+ * too), and the landmarks that min_views dropped.  seconds_kernels: upload of (rot, t, p) and kernels; seconds_download: the four arrays.
+ * On the device (xm_trackfilter.h): a thread per observation, a thread per landmark of up to xm_track_filter_limits()[0] observations, a
+ * workgroup with LDS tiles of [1] rays per longer one (no limit on the length), a thread per observation again, one fixed-order
+ * reduction; no atomics.  The call reads the context and changes nothing in it; two calls give the same bits, and every output equals the
+ * restatement in numpy exactly.  XM_ERR_ARG (context unchanged and usable): not XM_STORAGE_SCHUR, several ranks or a communicator, a
+ * struct_size that is not sizeof, null arrays, non-finite input, unknown flags, min_views < 0, and for a filter that is switched on a
+ * threshold that is not finite and positive (angles: at most 180). */
+#define XM_TF_REPROJECTION  1u
+#define XM_TF_ANGLE         2u
+#define XM_TF_TRIANGULATION 4u
+#define XM_TF_REASON_DEPTH          1
+#define XM_TF_REASON_REPROJECTION   2
+#define XM_TF_REASON_ANGLE          4
+#define XM_TF_REASON_TRIANGULATION  8
+#define XM_TF_REASON_MIN_VIEWS      16
+#define XM_TF_LM_KEPT           0
+#define XM_TF_LM_UNUSED         1       /* no used observation before the call */
+#define XM_TF_LM_TRIANGULATION  2
+#define XM_TF_LM_MIN_VIEWS      3
+typedef struct {
+    uint32_t struct_size;
+    uint32_t flags;                    /* XM_TF_REPROJECTION | XM_TF_ANGLE | XM_TF_TRIANGULATION */
+    double max_reprojection_error;     /* normalised image units; GLOMAP: 1e-2 */
+    double max_angle_error;            /* degrees; GLOMAP: 1.0 */
+    double min_triangulation_angle;    /* degrees; GLOMAP: 1.0 */
+    int32_t min_views;                 /* 0 = off */
+    int32_t reserved;
+} xm_tf_options_t;
+typedef struct {
+    uint32_t struct_size;
+    uint32_t reserved;
+    int64_t tracks_total, tracks_kept, obs_used, obs_kept;
+    int64_t dropped_depth, dropped_reprojection, dropped_angle, dropped_triangulation, dropped_min_views;
+    int64_t tracks_changed_reprojection, tracks_changed_angle, tracks_changed_triangulation, tracks_changed_min_views;
+    double cos_angle, cos_triangulation;   /* the thresholds the kernels compared against (0 for a filter that is off) */
+    double seconds_kernels, seconds_download;
+} xm_tf_result_t;
+int xm_ctx_filter_tracks(xm_ctx_t *ctx, const xm_tf_options_t *opt, const double *rot, const double *t, const double *p, uint8_t *keep,
+                         uint8_t *reason, int32_t *lm_views, uint8_t *lm_status, xm_tf_result_t *res);
+/* out[0] = observations of the longest landmark that one thread walks (longer ones get a workgroup), out[1] = rays per LDS tile of the
+ * workgroup form, out[2] = threads per workgroup (host-only; tests derive their boundary cases from them) */
+int xm_track_filter_limits(int64_t out[3]);
 
 /* ================================================================== 3. kernel-level entry points (device pointers) */
 /* device memory helpers so that callers need no other GPU runtime */

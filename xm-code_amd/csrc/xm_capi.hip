@@ -10,6 +10,7 @@
 
 #include "xm_ba.h"
 #include "xm_clean.h"
+#include "xm_trackfilter.h"
 #include "xm_lift.h"
 #include "xm_tracks.h"
 #include "xm_tracks_split.h"
@@ -652,6 +653,60 @@ int xm_ctx_clean_observations(xm_ctx_t *ctx, const xm_clean_options_t *opt, uint
     xm::CleanOutcome r;
     ctx->impl->clean_observations(c, keep, cam_index, lm_index, r);
     give_clean(res, r);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_ctx_filter_tracks(xm_ctx_t *ctx, const xm_tf_options_t *opt, const double *rot, const double *t, const double *p, uint8_t *keep, uint8_t *reason,
+                         int32_t *lm_views, uint8_t *lm_status, xm_tf_result_t *res) {
+    XM_TRY
+    const std::string w("xm_ctx_filter_tracks");
+    if (!ctx || !opt || !rot || !t || !p || !keep || !reason || !lm_views || !lm_status || !res) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (opt->struct_size != sizeof(xm_tf_options_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_tf_options_t.struct_size is not sizeof(xm_tf_options_t)");
+    if (res->struct_size != sizeof(xm_tf_result_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_tf_result_t.struct_size is not sizeof(xm_tf_result_t)");
+    if (opt->flags & ~(XM_TF_REPROJECTION | XM_TF_ANGLE | XM_TF_TRIANGULATION)) throw xm::Error(XM_ERR_ARG, w + ": unknown flag");
+    if (opt->min_views < 0) throw xm::Error(XM_ERR_ARG, w + ": min_views is negative");
+    // the threshold of a filter that is switched on must be usable (one that is off is not read)
+    if ((opt->flags & XM_TF_REPROJECTION) && !(std::isfinite(opt->max_reprojection_error) && opt->max_reprojection_error > 0.0))
+        throw xm::Error(XM_ERR_ARG, w + ": max_reprojection_error must be finite and positive");
+    if ((opt->flags & XM_TF_ANGLE) && !(opt->max_angle_error > 0.0 && opt->max_angle_error <= 180.0))
+        throw xm::Error(XM_ERR_ARG, w + ": max_angle_error must be positive and at most 180 degrees");
+    if ((opt->flags & XM_TF_TRIANGULATION) && !(opt->min_triangulation_angle > 0.0 && opt->min_triangulation_angle <= 180.0))
+        throw xm::Error(XM_ERR_ARG, w + ": min_triangulation_angle must be positive and at most 180 degrees");
+    if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, w + ": single-GPU contexts only (not n_gpus > 1)");
+    if (ctx->impl->world() > 1) throw xm::Error(XM_ERR_ARG, w + ": single-rank contexts only");
+    const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks();
+    for (int64_t k = 0; k < 9 * n; ++k)
+        if (!std::isfinite(rot[k])) throw xm::Error(XM_ERR_ARG, w + ": rotations are not finite");
+    for (int64_t k = 0; k < 3 * n; ++k)
+        if (!std::isfinite(t[k])) throw xm::Error(XM_ERR_ARG, w + ": translations are not finite");
+    for (int64_t k = 0; k < 3 * m; ++k)
+        if (!std::isfinite(p[k])) throw xm::Error(XM_ERR_ARG, w + ": landmarks are not finite");
+    xm::TfSettings c;
+    c.flags = opt->flags; c.min_views = opt->min_views; c.max_reprojection_error = opt->max_reprojection_error;
+    // the cosines of the two angles, once, on the host (track_filter.cc:60, :97: cos(DegToRad(angle))); the kernels compare against these doubles
+    constexpr double kPi = 3.14159265358979323846;
+    c.cos_angle = (opt->flags & XM_TF_ANGLE) ? std::cos(opt->max_angle_error * (kPi / 180.0)) : 0.0;
+    c.cos_triangulation = (opt->flags & XM_TF_TRIANGULATION) ? std::cos(opt->min_triangulation_angle * (kPi / 180.0)) : 0.0;
+    xm::TfOutcome r;
+    ctx->impl->filter_tracks(c, rot, t, p, keep, reason, lm_views, lm_status, r);
+    xm_tf_result_t out;
+    std::memset(&out, 0, sizeof(out));
+    out.struct_size = sizeof(xm_tf_result_t);
+    out.tracks_total = r.tracks_total; out.tracks_kept = r.tracks_kept; out.obs_used = r.obs_used; out.obs_kept = r.obs_kept;
+    out.dropped_depth = r.dropped_depth; out.dropped_reprojection = r.dropped_reprojection; out.dropped_angle = r.dropped_angle;
+    out.dropped_triangulation = r.dropped_triangulation; out.dropped_min_views = r.dropped_min_views;
+    out.tracks_changed_reprojection = r.changed_reprojection; out.tracks_changed_angle = r.changed_angle;
+    out.tracks_changed_triangulation = r.changed_triangulation; out.tracks_changed_min_views = r.changed_min_views;
+    out.cos_angle = c.cos_angle; out.cos_triangulation = c.cos_triangulation;
+    out.seconds_kernels = r.seconds_kernels; out.seconds_download = r.seconds_download;
+    *res = out;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_track_filter_limits(int64_t out[3]) {
+    XM_TRY
+    if (!out) throw xm::Error(XM_ERR_ARG, "xm_track_filter_limits: null argument");
+    out[0] = xm::kSchurHeavy; out[1] = xm::kTfTile; out[2] = xm::kTfThreads;
     return XM_OK;
     XM_CATCH
 }

@@ -34,6 +34,8 @@ constexpr int kSchurDenseQWinCams = 512;   // column window of the assembly kern
                                            // 160 KB.  Every window walks the camera's list again; measured at 8000 cameras / 5.4 M observations:
                                            // 1024 cameras (one wavefront per CU) 113 ms, 512 cameras 66 ms
 constexpr int kSchurAbarPanel = 2048;      // landmark rows of Abar are produced and copied out this many at a time (a panel of 3N doubles per landmark)
+constexpr int kSchurHeavy = 64;            // landmarks with more observations get a workgroup of their own (a thread per landmark serialises
+                                           // them: 963 us per product with three landmarks seen by all 1778 cameras, 122 us once split)
 constexpr int kSchurAggCams = 64;          // two-level preconditioner of the CG form: cameras per aggregate (one wavefront, a lane per camera)
 constexpr int64_t kSchurMaxAggregates = 4096;   // ... and its coarse operator: the n_c x n_c inverse is at most 134 MB
 

@@ -19,8 +19,7 @@ namespace xm {
 // ------------------------------------------------------------------------------------------------------------------
 // device kernels
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int kSchurHeavy = 64;   // landmarks with more observations get a workgroup of their own (a thread per landmark serialises
-                                  // them: 963 us per product with three landmarks seen by all 1778 cameras, 122 us once split)
+// kSchurHeavy (xm_schur.h): landmarks with more observations get a workgroup of their own
 
 // h_l = -(1/Q3_l) sum_{obs of l} w (p . W_i)      a light landmark: one thread | a heavy one: a 1024-thread workgroup (a landmark
 // seen by all 13 682 cameras: 14 strided steps instead of 13 682 serial ones; thread-strided order, DPP tree per wavefront, the 16

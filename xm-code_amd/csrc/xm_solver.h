@@ -120,6 +120,8 @@ struct BaOutcome;
 struct BaProbe;
 struct CleanSettings;  // xm_clean.h
 struct CleanOutcome;
+struct TfSettings;     // xm_trackfilter.h
+struct TfOutcome;
 
 struct PointState {  // everything the gradient epilogue writes for one point (R, s)
     DevBuf<double> G, egs, S0, rgR, rgs;
@@ -166,6 +168,9 @@ public:
     void schur_probe(xm_schur_probe_t &q);   // test export (xm_ctx_schur_probe): the matrix-free Q's factors, chain stages and inner-CG pieces
     void cert_probe(xm_cert_probe_t &q); // test export (xm_ctx_cert_probe): the certificate's Lanczos eigen-solver
     void reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr);   // per observation, input order (xm_ba.h)
+    // GLOMAP's track filters at (rot, t, p) with the current weights (xm_trackfilter.h); cfg.watchdog_s is the context's
+    void filter_tracks(const TfSettings &cfg, const double *rot, const double *t, const double *p, uint8_t *keep, uint8_t *reason,
+                       int32_t *lm_views, uint8_t *lm_status, TfOutcome &out);
     // which observations, cameras and landmarks of the list survive cleaning at the current weights (xm_clean.h); changes nothing here
     void clean_observations(const CleanSettings &cfg, uint8_t *keep, int32_t *cam_index, int32_t *lm_index, CleanOutcome &out);
     // XM^2 with the reference's residual definition (3_test_colmap_glomap.py:305-316): squared distance per edge / observation of the

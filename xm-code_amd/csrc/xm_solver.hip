@@ -15,6 +15,7 @@
 #include "xm_schur.h"
 #include "xm_ba.h"
 #include "xm_clean.h"
+#include "xm_trackfilter.h"
 
 #include <algorithm>
 #include <chrono>
@@ -2388,6 +2389,15 @@ void Context::reprojection_errors(const double *rot, const double *t, const doub
         throw Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
     if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: single-rank contexts only");
     xm::reprojection_errors(*schur_, rot, t, p, sqerr, cfg_.watchdog_s, st_);
+}
+void Context::filter_tracks(const TfSettings &cfg, const double *rot, const double *t, const double *p, uint8_t *keep, uint8_t *reason, int32_t *lm_views,
+                            uint8_t *lm_status, TfOutcome &out) {
+    if (!schur_)
+        throw Error(XM_ERR_ARG, "xm_ctx_filter_tracks: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_filter_tracks: single-rank contexts only");
+    TfSettings c = cfg;
+    c.watchdog_s = cfg_.watchdog_s;
+    xm::filter_tracks(*schur_, c, rot, t, p, keep, reason, lm_views, lm_status, out, st_);
 }
 void Context::clean_observations(const CleanSettings &cfg, uint8_t *keep, int32_t *cam_index, int32_t *lm_index, CleanOutcome &out) {
     if (!schur_)

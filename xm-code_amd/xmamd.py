@@ -42,6 +42,7 @@ EXPORTS = [
     "xm_lift_observations", "xm_lift_limits",
     "xm_build_tracks", "xm_tracks_limits", "xm_tracks_split_host", "xm_tracks_split_device", "xm_tracks_split_limits", "xm_tracks_split_stats",
     "xm_view_graph_filter", "xm_view_graph_limits",
+    "xm_ctx_filter_tracks", "xm_track_filter_limits",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -223,6 +224,20 @@ class CleanResult(C.Structure):    # xm_clean_result_t
                                          "cams_off_component", "lms_off_component")] + [("first_camera", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TfOptions(C.Structure):      # xm_tf_options_t
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("max_reprojection_error", C.c_double), ("max_angle_error", C.c_double),
+                ("min_triangulation_angle", C.c_double), ("min_views", C.c_int32), ("reserved", C.c_int32)]
+
+
+TF_COUNTS = ("tracks_total", "tracks_kept", "obs_used", "obs_kept", "dropped_depth", "dropped_reprojection", "dropped_angle", "dropped_triangulation",
+             "dropped_min_views", "tracks_changed_reprojection", "tracks_changed_angle", "tracks_changed_triangulation", "tracks_changed_min_views")
+
+
+class TfResult(C.Structure):       # xm_tf_result_t
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_int64) for k in TF_COUNTS] + \
+               [(k, C.c_double) for k in ("cos_angle", "cos_triangulation", "seconds_kernels", "seconds_download")]
+
+
 class PairOptions(C.Structure):    # xm_pair_options_t; the defaults are the reference's constants (XM_PAIR_OPTIONS_INIT)
     _fields_ = [("struct_size", C.c_uint32), ("min_joint", C.c_int32), ("min_flags", C.c_int32), ("flags", C.c_uint32), ("trim", C.c_double),
                 ("dist_pct", C.c_double), ("err_pct", C.c_double), ("mad_factor", C.c_double)]
@@ -305,6 +320,9 @@ PAIR_STAT_DTYPE = np.dtype([("n_joint", "<i4"), ("n_kept", "<i4"), ("n_flagged",
 PAIR_SKIP_ROW0 = 1
 PAIR_USED, PAIR_TOO_FEW, PAIR_DEGENERATE = 0, 1, 2
 CLEAN_NO_SWAP = 1
+TF_REPROJECTION, TF_ANGLE, TF_TRIANGULATION = 1, 2, 4                     # xm_tf_options_t.flags
+TF_REASON_DEPTH, TF_REASON_REPROJECTION, TF_REASON_ANGLE, TF_REASON_TRIANGULATION, TF_REASON_MIN_VIEWS = 1, 2, 4, 8, 16   # reason[e]
+TF_LM_KEPT, TF_LM_UNUSED, TF_LM_TRIANGULATION, TF_LM_MIN_VIEWS = 0, 1, 2, 3   # lm_status[l]
 BA_PROBE_DENSE_MAX_ROWS = 4096
 BA_FIX_ROTATIONS = 1
 BA_NONMONOTONIC = 2
@@ -381,6 +399,8 @@ def lib():
         L.xm_tracks_split_device.argtypes = L.xm_tracks_split_host.argtypes
         L.xm_tracks_split_limits.argtypes = [C.c_void_p]
         L.xm_tracks_split_stats.argtypes = [C.c_void_p]
+        L.xm_ctx_filter_tracks.argtypes = [C.c_void_p, C.POINTER(TfOptions)] + [C.c_void_p] * 7 + [C.POINTER(TfResult)]
+        L.xm_track_filter_limits.argtypes = [C.c_void_p]
         L.xm_ctx_reprojection_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_transport.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
         L.xm_ctx_dense_q.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -770,6 +790,47 @@ def clean_observations(cam, lm, w=None, n=None, m=None, min_cam_obs=10, min_lm_o
                                      None if w is None else w.ctypes.data_as(C.c_void_p), C.byref(opt), keep.ctypes.data_as(C.c_void_p),
                                      ci.ctypes.data_as(C.c_void_p), li.ctypes.data_as(C.c_void_p), C.byref(res)))
     return _clean_plan(keep, ci, li, res)
+
+
+class TrackFilterPlan:
+    """what Context.filter_tracks found: keep (bool per observation: used and it stays), reason (uint8 per observation: one TF_REASON_* bit
+    where a used observation is dropped, 0 where kept or unused), lm_views (int32 per landmark: observations left), lm_status (uint8 per
+    landmark: TF_LM_*) and info, the fields of xm_tf_result_t"""
+
+    def __init__(self, keep, reason, lm_views, lm_status, info):
+        self.keep, self.reason, self.lm_views, self.lm_status, self.info = keep, reason, lm_views, lm_status, info
+
+    @property
+    def dropped(self):
+        """bool per observation: used before the call and dropped by it"""
+        return self.reason != 0
+
+    def weights(self, w):
+        """w (one weight per observation) with zeros where the call dropped the observation: the argument of Context.set_edge_weights"""
+        w = np.array(w, dtype=np.float64).reshape(-1)
+        if w.shape != self.reason.shape:
+            raise XmError("TrackFilterPlan.weights: w must have one entry per observation of the filtered list")
+        w[self.reason != 0] = 0.0
+        return w
+
+    def apply(self, *per_observation):
+        """the rows of the kept observations, in input order, of every array given (cam, lm, p, w, ...)"""
+        k = self.keep
+        out = []
+        for a in per_observation:
+            a = np.asarray(a)
+            if a.shape[:1] != k.shape:
+                raise XmError("TrackFilterPlan.apply: a per-observation array has another length than the filtered list")
+            out.append(a[k])
+        return tuple(out)
+
+
+def track_filter_limits():
+    """-> dict(light_max: observations of the longest landmark that one thread walks (longer ones get a workgroup), tile: rays per LDS tile
+    of the workgroup form, threads: per workgroup)"""
+    out = np.zeros(3, dtype=np.int64)
+    _chk(lib().xm_track_filter_limits(out.ctypes.data_as(C.c_void_p)))
+    return dict(light_max=int(out[0]), tile=int(out[1]), threads=int(out[2]))
 
 
 class PairFilterPlan:
@@ -1318,6 +1379,7 @@ class Context:
             p.obs_cam, p.obs_lm, p.obs_p, p.obs_w = (a.ctypes.data_as(C.c_void_p) for a in (cam, lm, pts, w))
             self._keep += [cam, lm, pts, w]
             self.ne = cam.size                      # residuals / weights of the XM^2 loop are per observation
+            self._w = w.copy()                      # the current weights, as far as this object set them (refine_filtered)
         elif dq is not None:                      # dense Q already on the device in the solver's layout (borrowed)
             self.n = int(n)
             p.n, p.storage, p.q_on_device, p.q, p.ldq = self.n, STORAGE_DENSE, 1, dq.ptr, dense_ld(self.n)
@@ -1705,6 +1767,112 @@ class Context:
                                               out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def filter_tracks(self, rot, t, P, reprojection=1e-2, angle=None, triangulation=None, min_views=0):
+        """GLOMAP's TrackFilter (track_filter.cc:7-126) at the geometry (rot, t, P) -- the layouts of bundle_adjust -- over this context's
+        observations at their CURRENT weights, on the device (xm_ctx_filter_tracks; include/xm_amd.h has the contract); matrix-free
+        contexts only, nothing in the context changes.  reprojection: largest reprojection error in normalised image units (GLOMAP:
+        1e-2), angle: largest angle between the observed and the predicted ray in degrees (GLOMAP: 1.0), triangulation: smallest
+        triangulation angle of a landmark in degrees (GLOMAP: 1.0); None switches a filter off.  min_views > 0: a landmark left with
+        fewer observations loses them all.  -> TrackFilterPlan; ctx.set_edge_weights(plan.weights(w)) takes what it dropped out of the
+        next solve or bundle_adjust."""
+        flags = (TF_REPROJECTION if reprojection is not None else 0) | (TF_ANGLE if angle is not None else 0) | \
+                (TF_TRIANGULATION if triangulation is not None else 0)
+        for name, v in (("reprojection", reprojection), ("angle", angle), ("triangulation", triangulation)):
+            if v is not None and not (np.isfinite(v) and float(v) > 0.0):
+                raise XmError(f"filter_tracks: {name} must be finite and positive (None switches the filter off)")
+        if int(min_views) < 0:
+            raise XmError("filter_tracks: min_views is negative")
+        rot = np.asfortranarray(np.asarray(rot, dtype=np.float64)); t = np.asfortranarray(np.asarray(t, dtype=np.float64))
+        P = np.asfortranarray(np.asarray(P, dtype=np.float64))
+        m = getattr(self, "n_landmarks", 0)   # (a context of another storage has no landmarks: sized for nothing, the library refuses it)
+        assert rot.shape == (3, 3 * self.n) and t.shape == (3, self.n) and P.shape == (3, m)
+        opt = TfOptions(); res = TfResult()
+        opt.struct_size, res.struct_size = C.sizeof(TfOptions), C.sizeof(TfResult)
+        opt.flags, opt.min_views = flags, int(min_views)
+        opt.max_reprojection_error = float(reprojection or 0.0); opt.max_angle_error = float(angle or 0.0)
+        opt.min_triangulation_angle = float(triangulation or 0.0)
+        nobs = getattr(self, "ne", 0)
+        keep = np.zeros(nobs, dtype=np.uint8); reason = np.zeros(nobs, dtype=np.uint8)
+        views = np.zeros(m, dtype=np.int32); status = np.zeros(m, dtype=np.uint8)
+        _chk(lib().xm_ctx_filter_tracks(self.h, C.byref(opt), rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p),
+                                        keep.ctypes.data_as(C.c_void_p), reason.ctypes.data_as(C.c_void_p), views.ctypes.data_as(C.c_void_p),
+                                        status.ctypes.data_as(C.c_void_p), C.byref(res)))
+        info = {k: getattr(res, k) for k, _ in TfResult._fields_ if k not in ("struct_size", "reserved")}
+        return TrackFilterPlan(keep.astype(bool), reason, views, status, info)
+
+    def refine_filtered(self, rot, t, P, rounds=3, reprojection=1e-2, triangulation=1.0, min_views=0, restore_weights=False, weights=None,
+                        **bundle_adjust_kwargs):
+        """GLOMAP's alternation of bundle adjustment and track filtering (controllers/global_mapper.cc:243-317) on this context:
+          for ite < rounds (:243): bundle_adjust with fix_rotations=True (:250-253), then the full one (:260-265); then (:282-297)
+            while ite < rounds: filter_tracks(reprojection = max(3 - ite, 1) * reprojection) (:285-291); the landmarks it changed add up in
+            filtered_num; more than 1e-3 * tracks_total of them: back to the adjustment (:293-294), else ite += 1 (:296) and filter again
+            with the tighter threshold; the while ending without that: stop (:298-301);
+          then the reprojection filter at 1 x reprojection (:307-312) and the triangulation-angle filter (:313-317; None: not run).
+        After every filter that dropped something the context's weights become plan.weights(w) (set_edge_weights): THIS METHOD CHANGES
+        THE CONTEXT'S WEIGHTS, so that the next adjustment (and a later solve) leaves the dropped observations out; restore_weights=True
+        puts the entry weights back before it returns.  weights: the context's current weights (default: those it was created with or
+        was last given through set_edge_weights / xm2_filter).  min_views goes to every filter call.  bundle_adjust_kwargs go to every
+        bundle_adjust (not fix_rotations).
+        Departures from the reference: no NormalizeReconstruction (:273) and no UndistortImages (:279, :305) -- the thresholds are in
+        normalised image units and in angles, both free of the scale; the 0.1 % is counted against the landmarks with a used observation
+        at that filter call (tracks_total), not against every track ever made (:293); and the departures of filter_tracks itself.
+        -> (rot, t, P, info): info["rounds"] one record per adjustment round (ba_fixed / ba_full: status and costs; filters: one record per
+        filter call with scaling, threshold, dropped, tracks_changed, tracks_total), info["final"] the records of the two closing
+        filters, info["keep"] the kept observations of the last filter call, info["weights"] the weights it ends with (before a
+        restore), info["stopped_early"] whether the 0.1 % rule ended the loop."""
+        if "fix_rotations" in bundle_adjust_kwargs:
+            raise XmError("refine_filtered: fix_rotations is set by the loop itself (a fixed-rotation adjustment, then the full one)")
+        if int(rounds) < 0:
+            raise XmError("refine_filtered: rounds is negative")
+        w0 = getattr(self, "_w", None) if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w0 is None:
+            raise XmError("refine_filtered: the context's current weights are not known here (xm2_round filters inside the library): pass weights=")
+        if w0.size != self.ne:
+            raise XmError("refine_filtered: weights must have one entry per observation")
+        state = {"w": w0.copy(), "changed": False, "keep": None}
+
+        def run_filter(rep, tri, scaling):
+            plan = self.filter_tracks(rot, t, P, reprojection=rep, angle=None, triangulation=tri, min_views=min_views)
+            dropped = int(np.count_nonzero(plan.reason))
+            if dropped:
+                state["w"] = plan.weights(state["w"]); state["changed"] = True
+                self.set_edge_weights(state["w"])
+            state["keep"] = plan.keep
+            changed = plan.info["tracks_changed_reprojection"] if rep is not None else plan.info["tracks_changed_triangulation"]
+            return dict(scaling=scaling, reprojection=rep, triangulation=tri, dropped=dropped, tracks_changed=int(changed),
+                        tracks_total=int(plan.info["tracks_total"]), info=plan.info)
+
+        def ba_record(i):
+            return {k: i[k] for k in ("status", "status_name", "iters", "initial_cost", "final_cost", "n_used")}
+        records, stopped = [], False
+        ite = 0
+        while ite < int(rounds):                                                        # :243
+            rot, t, P, i1 = self.bundle_adjust(rot, t, P, fix_rotations=True, **bundle_adjust_kwargs)    # :250-253
+            rot, t, P, i2 = self.bundle_adjust(rot, t, P, fix_rotations=False, **bundle_adjust_kwargs)   # :260-265
+            rec = dict(ite=ite, ba_fixed=ba_record(i1), ba_full=ba_record(i2), filters=[])
+            records.append(rec)
+            status, filtered_num = True, 0                                              # :282-283
+            while status and ite < int(rounds):                                         # :284
+                scaling = max(3 - ite, 1)                                               # :285
+                f = run_filter(scaling * reprojection, None, scaling)                   # :286-291
+                rec["filters"].append(f)
+                filtered_num += f["tracks_changed"]
+                if filtered_num > 1e-3 * f["tracks_total"]:                             # :293
+                    status = False                                                      # :294
+                else:
+                    ite += 1                                                            # :296
+            if status:                                                                  # :298-301
+                stopped = True
+                break
+            ite += 1                                                                    # :243, the for's increment
+        final = [run_filter(reprojection, None, 1)]                                     # :307-312
+        if triangulation is not None:
+            final.append(run_filter(None, triangulation, 1))                            # :313-317
+        info = dict(rounds=records, final=final, keep=state["keep"], weights=state["w"], stopped_early=stopped)
+        if restore_weights and state["changed"]:
+            self.set_edge_weights(w0)
+        return rot, t, P, info
+
     def clean_observations(self, min_cam_obs=10, min_lm_obs=1, swap_first=True):
         """the reference's checklandmarks for this context's list at its CURRENT weights (after xm2_filter / set_edge_weights: the filtered
         list; xm_ctx_clean_observations), matrix-free contexts only; nothing in the context changes.  -> CleanPlan; plan.apply(cam, lm, p, w)
@@ -1730,6 +1898,7 @@ class Context:
         thr = C.c_double(); rm = C.c_int64(); w = np.zeros(self.ne)
         _chk(lib().xm_ctx_xm2_filter(self.h, rot.ctypes.data_as(C.c_void_p), scale.ctypes.data_as(C.c_void_p), percentile, C.byref(thr), C.byref(rm),
                                      w.ctypes.data_as(C.c_void_p)))
+        self._w = w.copy()
         return thr.value, rm.value, w
 
     def xm2_round(self, R, s, max_rank, tol, max_time=1000.0, percentile=90.0, flags=0):
@@ -1744,6 +1913,7 @@ class Context:
         inf.percentile = percentile
         res.R = Ro.ctypes.data_as(C.c_void_p); res.s = so.ctypes.data_as(C.c_void_p)
         _chk(lib().xm_ctx_xm2_round(self.h, R.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p), R.shape[1], C.byref(opt), C.byref(inf), C.byref(res)))
+        self._w = None   # the round filtered inside the library: the weights are no longer known here
         info = {k: getattr(res, k) for k, _ in Result._fields_ if k not in ("R", "s", "struct_size")}
         x2 = {k: getattr(inf, k) for k, _ in Xm2Info._fields_ if k != "struct_size"}
         return np.ascontiguousarray(Ro[:, : res.rank]), so, info, x2
@@ -1752,6 +1922,7 @@ class Context:
         w = np.ascontiguousarray(w, dtype=np.float64)
         assert w.size == self.ne
         _chk(lib().xm_ctx_set_edge_weights(self.h, w.ctypes.data_as(C.c_void_p)))
+        self._w = w.reshape(-1).copy()
 
     def solve(self, max_rank, tol, lam, max_time=1000.0, mode=MODE_SOLVE, flags=0, s_ini=None, trace=0, R_ini=None, retraction=RETRACT_QR,
               grouping=0):
