@@ -762,6 +762,48 @@ def test_qw_dense_symmetric_kernel_with_a_forced_finer_cut(xmamd, n, o, k, kf):
         xmamd._chk(L.xm_bench_symv_k(0, 1, 0))
 
 
+@pytest.mark.parametrize("n,o,cut", [(1, 3, None), (2, 3, None), (7, 3, None), (42, 3, None), (43, 3, None), (85, 3, None), (86, 4, None),
+                                     (87, 5, None), (128, 3, None), (171, 5, None), (343, 4, (5, 1, 1))])
+def test_dense_products_of_small_integers_are_exact(xmamd, n, o, cut):
+    """symmetric Q and W with integer entries in [-8, 8], alpha = 2: every product and partial sum is an integer far below 2^53 and Q is
+    exact in fp32, so the general and the symmetric product, from the f64 matrix and from its fp32 copy, the sweeps top-down (functional
+    entry) and bottom-up (the timing hook's last launch, alpha 1), equal numpy's 2 Q W exactly whatever their summation orders -- a wrong
+    mask, a swapped column pair or a wrong partial-sum offset shows at zero tolerance.  Shapes: a half strip, a full strip, an odd camera
+    count, two strips with a half second strip, an odd strip count whose middle strip has no fold partner; one forced finer cut"""
+    rng = np.random.default_rng(13 * n + o)
+    A = np.triu(rng.integers(-8, 9, (3 * n, 3 * n)).astype(np.float64))
+    Q = A + np.triu(A, 1).T
+    W = rng.integers(-8, 9, (3 * n, o)).astype(np.float64)
+    ref = 2.0 * (Q @ W)
+    L = xmamd.lib()
+    ld = xmamd.dense_ld(n)
+    dq = xmamd.dense_upload(Q); d32 = xmamd.dense_to_f32(dq, n)
+    dW = xmamd.DevArray(xmamd.to_rm(W, rows=ld)); ms = C.c_double()
+    def run(fn, mat, *tail):
+        dO = xmamd.DevArray(np.full(3 * n * xmamd.pitch_of(o), np.nan))
+        try:
+            xmamd._chk(fn(mat.ptr, n, o, dW.ptr, dO.ptr, *tail)); xmamd._chk(L.xm_dev_sync())
+            return xmamd.from_rm(dO.get(), 3 * n, o)
+        finally:
+            dO.free()
+    try:
+        if cut:
+            xmamd._chk(L.xm_bench_symv_k(*cut))
+        got = {"general f64": run(L.xm_qw_dense, dq, 2.0, None),
+               "symmetric f64 top-down": run(L.xm_qw_dense_sym, dq, 2.0, None),
+               "symmetric f64 bottom-up": 2.0 * run(L.xm_qw_dense_sym_time, dq, 1, C.byref(ms)),
+               "general fp32": run(L.xm_qw_dense_f32, d32, 2.0, None),
+               "symmetric fp32 top-down": run(L.xm_qw_dense_sym_f32, d32, 2.0, None),
+               "symmetric fp32 bottom-up": 2.0 * run(L.xm_qw_dense_sym_f32_time, d32, 1, C.byref(ms))}
+    finally:
+        xmamd._chk(L.xm_bench_symv_k(0, 1, 0))
+        for b in (dq, d32, dW):
+            b.free()
+    for what, out in got.items():
+        bad = np.flatnonzero((out != ref).any(axis=1))
+        assert np.array_equal(out, ref), f"{what}: {bad.size} rows differ, first {int(bad[0]) if bad.size else -1}"
+
+
 def test_new_products_are_bit_reproducible(xmamd):
     """fixed summation orders everywhere: the half-traffic symmetric product (per-strip row sums through LDS, per-chunk column sums,
     list-ordered reducer) and the matrix-free chain (degree-sorted landmark groups, hub landmarks in the same launch) give the same

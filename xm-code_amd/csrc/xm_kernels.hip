@@ -29,6 +29,7 @@
 
 #include "xm_common.h"
 #include "xm_device.h"
+#include "xm_symv_step.h"
 
 namespace xm {
 
@@ -336,27 +337,10 @@ __global__ __launch_bounds__(256) void qw_dense_ks_kernel(const double *__restri
 }
 
 // ----------------------------------------------------------------------------------------------------------------
-// Half-traffic product for SYMMETRIC dense Q (single GPU, o <= 5): only the upper block triangle is read, every Q fragment is used
-// twice.  A WORKGROUP owns a strip of 256 columns and 4 K consecutive steps of it; each of its four wavefronts (lane: 2 + 2 adjacent
-// columns, W of its columns in registers for the whole sweep) walks K steps of two cameras (6 rows x 256 columns = 12 KB per step):
-//   column direction  y_cols += Q_step^T w_rows : per-lane accumulators that live in registers for the whole chunk; the four
-//                     wavefronts' sums are added in LDS (wavefront order 0..3: fixed) and written ONCE per workgroup;
-//   row direction     y_rows  = Q_step w_cols   : 6 * o per-lane partial sums per step, summed over the 64 lanes through LDS
-//                     (transposed write, 16-lane DPP row sums) and written as 6 * o doubles per step.
-// Element (r, c) of step j (rows [6j, 6j+6)): used both ways when c >= 6j + 6, in the row direction only when 6j <= c < 6j + 6
-// (the 6 x 6 diagonal block is read in full), not at all when c < 6j (its mirror image serves it).
-// Round 6 (profiles/r06_kbench_symv.txt; Venice size, o = 3 / 4, pair of launches, us): workgroup on four strips with one chunk each and a
-// select behind every load 29.8 / 34.0 -> workgroup on one strip, column sums combined in LDS (Pcol / 4: ~35 instead of ~100 partial records
-// per camera), loads without a select and a peeled loop so that the next step's twelve requests stay in flight while the current step is
-// multiplied (s_waitcnt vmcnt(12), not 0) 28.1 / 32.5 -> alternating sweep direction (rev) 27.4 / 31.9 -> K = 6 (one residency round of
-// ~420 workgroups) 26.5 / 29.6.  The per-wavefront timestamps (TRACE) say where the time of the launch goes: all wavefronts start within
-// 1 us, the first step completes after ~5-6 us (every wavefront asks for 20 KB at once: 25 MB at the ~7 TB/s the fabric delivers), every
-// further step 2.1-2.5 us (= 7 TB/s over all wavefronts: the loop runs at the chip's saturation), the median wavefront ends at 20 us, the last at 24.
-// The loads carry no select: a row past the end re-reads the last row and meets w_row = 0 in the column direction (its row sums land in
-// rows of Prow nobody reads), the absent second half of the last strip re-reads the first half and meets w_col = 0.
+// Half-traffic product for SYMMETRIC dense Q: the design, its measurements and the shared pieces of the sweep are in xm_symv_step.h.
+// A lane holds columns c0 + 2 lane, + 1 (pair 0) and the same 128 further right (pair 1): two double2 per row and step.
 // TRACE (micro-benchmark only): 100 MHz timestamps per wavefront -- entry, after the status word, after every step, end.
 // ----------------------------------------------------------------------------------------------------------------
-constexpr int kSvStrip = 256;
 constexpr int kSvTraceSlots = 24;
 template <int O, bool TRACE = false>
 __global__ __launch_bounds__(256) void qw_symv_kernel(const double *__restrict__ Q, int64_t ld, const double *__restrict__ W, int nloc, int Kc, int Kf, int ysplit, int nt_step0,
@@ -365,26 +349,8 @@ __global__ __launch_bounds__(256) void qw_symv_kernel(const double *__restrict__
     constexpr int OP = pitch_of(O), V = 6 * O;
     __shared__ __attribute__((aligned(16))) double lds[4][V * 64];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // The live (strip, group) pairs form a staircase -- strip s has ~ (s + 1) * 42.7 / (4 K) groups -- and block b runs on XCD b mod 8: a grid of
-    // strips x groups is half empty and its live blocks land on the XCDs unevenly (K = 11 at 2 560 cameras: 180 ... 272 live wavefronts per XCD,
-    // one XCD beyond its 64 resident workgroups, a second dispatch round: 66.7 us instead of 48).  FOLDED grid: row y holds strip y and, behind
-    // it, strip S - 1 - y -- every row has about the same number of live blocks, (nearly) every block of the grid is live, and consecutive
-    // blocks are consecutive XCDs.
-    const int nsteps = (nloc + 1) >> 1, nrows = 3 * nloc;
-    const int nstrips = (int)((ld + kSvStrip - 1) / kSvStrip);
-    const int K = ((int)blockIdx.y >= ysplit) ? Kf : Kc;         // the rows dispatched last are cut finer: they are the launch's tail
-    int s = blockIdx.y, sc = blockIdx.x;
-    {
-        int jA = (int)(((int64_t)s * kSvStrip + kSvStrip + 5) / 6);
-        if (jA > nsteps) jA = nsteps;
-        const int nA = (jA + 4 * K - 1) / (4 * K);
-        if (sc >= nA) {
-            if (nstrips - 1 - s == s) return;                    // the middle strip of an odd count has no partner (uniform over the workgroup)
-            s = nstrips - 1 - s; sc -= nA;
-        }
-    }
     unsigned long long *tr = nullptr;
-    if constexpr (TRACE) {
+    if constexpr (TRACE) {   // every wavefront of the grid stamps its entry, with work or without
         tr = trace + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * kSvTraceSlots;
         if (lane == 0) {
             unsigned int hw, xcc;
@@ -394,177 +360,84 @@ __global__ __launch_bounds__(256) void qw_symv_kernel(const double *__restrict__
             tr[kSvTraceSlots - 1] = ((unsigned long long)xcc << 32) | hw;
         }
     }
-    const int64_t c0 = (int64_t)s * kSvStrip;
-    int jend = (int)((c0 + kSvStrip + 5) / 6);                   // steps whose rows start above the end of the strip
-    if (jend > nsteps) jend = nsteps;
-    if (sc * 4 * K >= jend) return;                              // uniform over the workgroup
-    const int jb = (sc * 4 + wave) * K;                          // this wavefront's chunk [jb, je): may be empty at the foot of the strip
-    const int je = (jb + K < jend) ? jb + K : jend;
-    const int jfull = (int)(c0 / 6);                             // steps j < jfull lie entirely above the diagonal: no masks
-    const bool half1 = c0 + 128 < ld;                            // ld is a multiple of 128: the strip may end after its first half
-    const int64_t R = (int64_t)6 * nsteps;
+    const SymvChunk ch = symv_chunk(blockIdx.x, blockIdx.y, nloc, ld, Kc, Kf, ysplit, wave);
+    if (ch.empty) return;                                        // uniform over the workgroup
+    const int nrows = 3 * nloc, jb = ch.jb, je = ch.je;
+    const bool half1 = ch.c0 + 128 < ld;                         // ld is a multiple of 128: the strip may end after its first half
     double *L = lds[wave];
-    const int64_t cA = c0 + 2 * lane, cB = half1 ? cA + 128 : cA;
+    const int64_t cA = ch.c0 + 2 * lane, cB = half1 ? cA + 128 : cA;
 
     double wc[2][2][O], ca[2][2][O];
+    struct Slot { double2 q[6][2]; double wl; } slot[2];
 
-    // chunks that start at a step >= nt_step0 stream non-temporally (a matrix beyond the Infinity Cache keeps its top rows resident:
-    // symv_nt_step0).  The policy is a compile-time property of the sweep loop (two copies under one wave-uniform branch, see qw_dense_kernel).
-    // W of the step's six rows travels with the step's Q: lane l requests element l of the 6 * OP contiguous doubles (one more request behind
-    // the twelve), and the multiply reads w_row out of that register with v_readlane.  Scalar loads at the point of use (round 5) were waited
-    // for one by one inside the step -- up to six exposed round trips to L2 per step at o = 4, where a row's four values are a load of their own.
-    const int64_t wlim = (int64_t)nrows * OP - 1;
-    auto load_q = [&](int j, double2 (&q)[6][2], double &wl, auto ntag) __attribute__((always_inline)) {
-        constexpr bool NT = decltype(ntag)::value;
+    int nrun = 0;
+    auto run = [&](int j, auto sl) __attribute__((always_inline)) {
+        const Slot &b = slot[decltype(sl)::value];
         const int64_t r0 = (int64_t)6 * j;
-        {
-            const int64_t wi = r0 * OP + (lane < 6 * OP ? lane : 0);
-            wl = W[wi < wlim ? wi : wlim];
-        }
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            const int64_t rr = (r0 + r < nrows) ? r0 + r : nrows - 1;   // wave-uniform clamp (odd camera count: three rows of the last step)
-            const double *row = Q + (size_t)rr * (size_t)ld;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const double2 *qp = reinterpret_cast<const double2 *>(row + (h ? cB : cA));
-                if (NT) q[r][h] = nt_load16(qp);
-                else q[r][h] = *qp;
-            }
-        }
-    };
-    auto step = [&](int j, const double2 (&q)[6][2], const double wl, auto masked) __attribute__((always_inline)) {
-        constexpr bool MASK = decltype(masked)::value;
-        const int64_t r0 = (int64_t)6 * j;
+        auto qat = [&](int r, int h, int e) __attribute__((always_inline)) { return e ? b.q[r][h].y : b.q[r][h].x; };
+        auto wrow = [&](int r, double (&wr)[O]) __attribute__((always_inline)) { symv_wrow_read<O>(b.wl, r, r0 + r < nrows, wr); };
+        double *prow = Prow + ((size_t)ch.s * (size_t)ch.R + (size_t)r0) * O;
         double mr[2] = {1.0, 1.0}, mc[2] = {1.0, 1.0};
-        if constexpr (MASK) {
+        if (j < ch.jfull) symv_step<O, false>(qat, mr, mc, wrow, wc, ca, L, lane, prow);
+        else {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {   // both columns of a pair fall on the same side (all bounds are even)
                 mr[h] = (cA + 128 * h >= r0) ? 1.0 : 0.0;
                 mc[h] = (cA + 128 * h >= r0 + 6) ? 1.0 : 0.0;
             }
+            symv_step<O, true>(qat, mr, mc, wrow, wc, ca, L, lane, prow);
         }
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            double wr[O];
-            const bool ok = r0 + r < nrows;                              // wave-uniform: scalar select
-#pragma unroll
-            for (int k = 0; k < O; ++k) {
-                const int lo = __builtin_amdgcn_readlane(__double2loint(wl), r * OP + k), hi = __builtin_amdgcn_readlane(__double2hiint(wl), r * OP + k);
-                wr[k] = ok ? __hiloint2double(hi, lo) : 0.0;
-            }
-            double qr[2][2], qc[2][2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                qr[h][0] = MASK ? q[r][h].x * mr[h] : q[r][h].x; qr[h][1] = MASK ? q[r][h].y * mr[h] : q[r][h].y;
-                qc[h][0] = MASK ? q[r][h].x * mc[h] : q[r][h].x; qc[h][1] = MASK ? q[r][h].y * mc[h] : q[r][h].y;
-            }
-#pragma unroll
-            for (int k = 0; k < O; ++k) {
-                double t = qr[0][0] * wc[0][0][k];
-                t = fma(qr[0][1], wc[0][1][k], t);
-                t = fma(qr[1][0], wc[1][0][k], t);
-                t = fma(qr[1][1], wc[1][1][k], t);
-                L[(r * O + k) * 64 + lane] = t;
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) ca[h][e][k] = fma(qc[h][e], wr[k], ca[h][e][k]);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        // 64 addends per value: a 16-lane row takes value v = 4 i + (lane / 16), each lane four addends, DPP row sum
-        const int g = lane >> 4, jl = lane & 15;
-#pragma unroll
-        for (int v0 = 0; v0 < V; v0 += 4) {
-            const int v = v0 + g;
-            double t = 0.0;
-            if (v < V) {
-                const double2 a = *reinterpret_cast<const double2 *>(L + v * 64 + 4 * jl), b = *reinterpret_cast<const double2 *>(L + v * 64 + 4 * jl + 2);
-                t = (a.x + a.y) + (b.x + b.y);
-            }
-            t = group_sum<16>(t);
-            if (jl == 0 && v < V) Prow[((size_t)s * (size_t)R + (size_t)r0) * O + v] = t;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-    int nrun = 0;
-    auto run = [&](int j, const double2 (&q)[6][2], const double wl) __attribute__((always_inline)) {
-        if (j < jfull) step(j, q, wl, std::false_type{});
-        else step(j, q, wl, std::true_type{});
         if constexpr (TRACE) {
             if (lane == 0 && 2 + nrun < kSvTraceSlots - 3) tr[2 + nrun] = wall_clock64();
             ++nrun;
         }
     };
-
-    double2 qA[6][2], qB[6][2];
-    double wA = 0.0, wB = 0.0;
+    // chunks that start at a step >= nt_step0 stream non-temporally (a matrix beyond the Infinity Cache keeps its top rows resident:
+    // symv_nt_step0).  The policy is a compile-time property of the sweep loop (two copies under one wave-uniform branch, see qw_dense_kernel).
     auto sweep = [&](auto ntag) __attribute__((always_inline)) -> bool {
-    if (jb < je) load_q(rev ? je - 1 : jb, qA, wA, ntag);                // wave-uniform
+        constexpr bool NT = decltype(ntag)::value;
+        auto load = [&](int j, auto sl) __attribute__((always_inline)) {
+            Slot &b = slot[decltype(sl)::value];
+            b.wl = symv_wrow_request<O>(W, j, nrows, lane);
+            const int64_t r0 = (int64_t)6 * j;
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
+            for (int r = 0; r < 6; ++r) {
+                const int64_t rr = (r0 + r < nrows) ? r0 + r : nrows - 1;   // wave-uniform clamp (odd camera count: three rows of the last step)
+                const double *row = Q + (size_t)rr * (size_t)ld;
 #pragma unroll
-        for (int e = 0; e < 2; ++e)
-#pragma unroll
-            for (int k = 0; k < O; ++k) {
-                const double t = W[(size_t)((h ? cB : cA) + e) * OP + k];   // unconditional request (a predicated one is a branch per element)
-                wc[h][e][k] = (h == 0 || half1) ? t : 0.0;
-                ca[h][e][k] = 0.0;
+                for (int h = 0; h < 2; ++h) {
+                    const double2 *qp = reinterpret_cast<const double2 *>(row + (h ? cB : cA));
+                    if (NT) b.q[r][h] = nt_load16(qp);
+                    else b.q[r][h] = *qp;
+                }
             }
-    // the tCG's status word (written by the previous launch on another XCD: an L2 miss) is looked at only now, with the columns of W and the
-    // first step of Q already requested: one round trip at the head of every wavefront instead of two
-    if (scal != nullptr) {   // by_phase (device-driven outer iteration): live in the phases PH_TCG and PH_CAND, whatever the tCG's status says
-        if (by_phase ? (scal->phase >= PH_STOP) : (scal->status != 0)) return false;
-    }
-    if constexpr (TRACE) { if (lane == 0) tr[1] = wall_clock64(); }
-    // rev: the chunk is walked bottom-up (position i <-> step je - 1 - i).  Launches alternate the direction, so that a launch starts with
-    // the steps the previous one ended with: they are still in this XCD's L2 (4 MB; block b runs on XCD b mod 8 in every launch)
-    auto at = [&](int i) __attribute__((always_inline)) { return rev ? je - 1 - i : jb + i; };
-    const int cnt = je - jb;
-    if (cnt > 0) {
-        int i = 0;
-        while (i + 2 < cnt) {          // two more steps follow: both requests below are unconditional
-            load_q(at(i + 1), qB, wB, ntag);
-            run(at(i), qA, wA);
-            load_q(at(i + 2), qA, wA, ntag);
-            run(at(i + 1), qB, wB);
-            i += 2;
+        };
+        if (jb < je) load(symv_walk_at(jb, je, rev, 0), std::integral_constant<int, 0>{});   // wave-uniform
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+#pragma unroll
+                for (int k = 0; k < O; ++k) {
+                    const double t = W[(size_t)((h ? cB : cA) + e) * OP + k];   // unconditional request (a predicated one is a branch per element)
+                    wc[h][e][k] = (h == 0 || half1) ? t : 0.0;
+                    ca[h][e][k] = 0.0;
+                }
+        // the tCG's status word (written by the previous launch on another XCD: an L2 miss) is looked at only now, with the columns of W and the
+        // first step of Q already requested: one round trip at the head of every wavefront instead of two
+        if (scal != nullptr) {   // by_phase (device-driven outer iteration): live in the phases PH_TCG and PH_CAND, whatever the tCG's status says
+            if (by_phase ? (scal->phase >= PH_STOP) : (scal->status != 0)) return false;
         }
-        if (i + 1 < cnt) {
-            load_q(at(i + 1), qB, wB, ntag);
-            run(at(i), qA, wA);
-            run(at(i + 1), qB, wB);
-        } else {
-            run(at(i), qA, wA);
-        }
-    }
-    return true;
+        if constexpr (TRACE) { if (lane == 0) tr[1] = wall_clock64(); }
+        symv_walk(jb, je, rev, load, run);
+        return true;
     };
     const bool alive = (jb >= nt_step0) ? sweep(std::true_type{}) : sweep(std::false_type{});
     if (!alive) return;
     if constexpr (TRACE) { if (lane == 0) tr[kSvTraceSlots - 3] = wall_clock64(); }
 
-    // column sums of the four chunks, added in wavefront order; wavefront h writes the h-th half of the strip (2 O contiguous doubles per lane)
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-#pragma unroll
-            for (int k = 0; k < O; ++k) L[((h * 2 + e) * O + k) * 64 + lane] = ca[h][e][k];
-    __syncthreads();
-    if (wave < 2 && (wave == 0 || half1)) {
-        double *pc = Pcol + ((size_t)sc * (size_t)ld + (size_t)(cA + 128 * wave)) * O;
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-#pragma unroll
-            for (int k = 0; k < O; ++k) {
-                const int idx = ((wave * 2 + e) * O + k) * 64 + lane;
-                pc[e * O + k] = ((lds[0][idx] + lds[1][idx]) + lds[2][idx]) + lds[3][idx];
-            }
-    }
+    // wavefront h writes the h-th half of the strip
+    symv_colsum<O>(ca, lds, wave, lane, wave == 0 || half1, Pcol + ((size_t)ch.sc * (size_t)ld + (size_t)(cA + 128 * wave)) * O);
     if constexpr (TRACE) { if (lane == 0) tr[kSvTraceSlots - 2] = wall_clock64(); }
 }
 
@@ -3151,9 +3024,10 @@ __global__ __launch_bounds__(256) void qw_dense_f32_kernel(const float *__restri
 }
 
 // Symmetric half-traffic sweep from the fp32 copy: qw_symv_kernel's strips, chunks, folded grid and partial-sum layout (Prow / Pcol, read by
-// symv_reduce_kernel), with a lane on four adjacent columns c0 + 4 lane .. + 3 of its strip -- column pair h (0, 1) = columns c0 + 4 lane + 2 h,
-// + 1 -- and one float4 per row and step.  A strip that ends after its first 128 columns: lanes 32..63 re-read the first half and meet
-// w_col = 0; their column sums are not written.  EPI_AUTO (by_phase): PH_TCG streams the fp32 copy, PH_CAND the f64 matrix (two double2 per row).
+// symv_reduce_kernel) and its pieces (xm_symv_step.h), with a lane on four adjacent columns c0 + 4 lane .. + 3 of its strip -- column pair
+// h (0, 1) = columns c0 + 4 lane + 2 h, + 1 -- and one float4 per row and step.  A strip that ends after its first 128 columns: lanes 32..63
+// re-read the first half and meet w_col = 0; their column sums are not written.  EPI_AUTO (by_phase): PH_TCG streams the fp32 copy, PH_CAND
+// the f64 matrix (two double2 per row).  Load policy and the place of the status word: as in qw_symv_kernel.
 template <int O, bool AUTO>
 __global__ __launch_bounds__(256) void qw_symv_f32_kernel(const float *__restrict__ Qf, const double *__restrict__ Qd, int64_t ld, const double *__restrict__ W,
                                                            int nloc, int Kc, int Kf, int ysplit, int nt_step0, const TcgScal *__restrict__ scal,
@@ -3161,114 +3035,46 @@ __global__ __launch_bounds__(256) void qw_symv_f32_kernel(const float *__restric
     constexpr int OP = pitch_of(O), V = 6 * O;
     __shared__ __attribute__((aligned(16))) double lds[4][V * 64];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int nsteps = (nloc + 1) >> 1, nrows = 3 * nloc;
-    const int nstrips = (int)((ld + kSvStrip - 1) / kSvStrip);
-    const int K = ((int)blockIdx.y >= ysplit) ? Kf : Kc;
-    int s = blockIdx.y, sc = blockIdx.x;
-    {
-        int jA = (int)(((int64_t)s * kSvStrip + kSvStrip + 5) / 6);
-        if (jA > nsteps) jA = nsteps;
-        const int nA = (jA + 4 * K - 1) / (4 * K);
-        if (sc >= nA) {
-            if (nstrips - 1 - s == s) return;
-            s = nstrips - 1 - s; sc -= nA;
-        }
-    }
-    const int64_t c0 = (int64_t)s * kSvStrip;
-    int jend = (int)((c0 + kSvStrip + 5) / 6);
-    if (jend > nsteps) jend = nsteps;
-    if (sc * 4 * K >= jend) return;
-    const int jb = (sc * 4 + wave) * K;
-    const int je = (jb + K < jend) ? jb + K : jend;
-    const int jfull = (int)(c0 / 6);
-    const bool lane_ok = (c0 + 4 * lane) < ld;                   // false only in the absent half of a half strip
-    const int64_t R = (int64_t)6 * nsteps;
+    const SymvChunk ch = symv_chunk(blockIdx.x, blockIdx.y, nloc, ld, Kc, Kf, ysplit, wave);
+    if (ch.empty) return;                                        // uniform over the workgroup
+    const int nrows = 3 * nloc, jb = ch.jb, je = ch.je;
+    const bool lane_ok = (ch.c0 + 4 * lane) < ld;                // false only in the absent half of a half strip
     double *L = lds[wave];
-    const int64_t cA = lane_ok ? c0 + 4 * lane : c0 + 4 * (lane - 32);
-    const int64_t wlim = (int64_t)nrows * OP - 1;
+    const int64_t cA = lane_ok ? ch.c0 + 4 * lane : ch.c0 + 4 * (lane - 32);
 
     double wc[2][2][O], ca[2][2][O];
     auto sweep = [&](const auto *Q, auto ntag) __attribute__((always_inline)) -> bool {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(Q)>>;
         constexpr bool NT = decltype(ntag)::value;
-        auto load_q = [&](int j, QFrag4<T> (&q)[6], double &wl) __attribute__((always_inline)) {
+        struct Slot { QFrag4<T> q[6]; double wl; } slot[2];
+        auto load = [&](int j, auto sl) __attribute__((always_inline)) {
+            Slot &b = slot[decltype(sl)::value];
+            b.wl = symv_wrow_request<O>(W, j, nrows, lane);
             const int64_t r0 = (int64_t)6 * j;
-            {
-                const int64_t wi = r0 * OP + (lane < 6 * OP ? lane : 0);
-                wl = W[wi < wlim ? wi : wlim];
-            }
 #pragma unroll
             for (int r = 0; r < 6; ++r) {
                 const int64_t rr = (r0 + r < nrows) ? r0 + r : nrows - 1;
-                q[r].template load<NT>(Q + (size_t)rr * (size_t)ld + cA);
+                b.q[r].template load<NT>(Q + (size_t)rr * (size_t)ld + cA);
             }
         };
-        auto step = [&](int j, const QFrag4<T> (&q)[6], const double wl, auto masked) __attribute__((always_inline)) {
-            constexpr bool MASK = decltype(masked)::value;
+        auto run = [&](int j, auto sl) __attribute__((always_inline)) {
+            const Slot &b = slot[decltype(sl)::value];
             const int64_t r0 = (int64_t)6 * j;
+            auto qat = [&](int r, int h, int e) __attribute__((always_inline)) { return b.q[r].at(2 * h + e); };
+            auto wrow = [&](int r, double (&wr)[O]) __attribute__((always_inline)) { symv_wrow_read<O>(b.wl, r, r0 + r < nrows, wr); };
+            double *prow = Prow + ((size_t)ch.s * (size_t)ch.R + (size_t)r0) * O;
             double mr[2] = {1.0, 1.0}, mc[2] = {1.0, 1.0};
-            if constexpr (MASK) {
+            if (j < ch.jfull) symv_step<O, false>(qat, mr, mc, wrow, wc, ca, L, lane, prow);
+            else {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {   // both columns of a pair fall on the same side (all bounds are even)
                     mr[h] = (cA + 2 * h >= r0) ? 1.0 : 0.0;
                     mc[h] = (cA + 2 * h >= r0 + 6) ? 1.0 : 0.0;
                 }
+                symv_step<O, true>(qat, mr, mc, wrow, wc, ca, L, lane, prow);
             }
-#pragma unroll
-            for (int r = 0; r < 6; ++r) {
-                double wr[O];
-                const bool ok = r0 + r < nrows;
-#pragma unroll
-                for (int k = 0; k < O; ++k) {
-                    const int lo = __builtin_amdgcn_readlane(__double2loint(wl), r * OP + k), hi = __builtin_amdgcn_readlane(__double2hiint(wl), r * OP + k);
-                    wr[k] = ok ? __hiloint2double(hi, lo) : 0.0;
-                }
-                double qr[2][2], qc[2][2];
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const double x = q[r].at(2 * h + e);
-                        qr[h][e] = MASK ? x * mr[h] : x;
-                        qc[h][e] = MASK ? x * mc[h] : x;
-                    }
-#pragma unroll
-                for (int k = 0; k < O; ++k) {
-                    double t = qr[0][0] * wc[0][0][k];
-                    t = fma(qr[0][1], wc[0][1][k], t);
-                    t = fma(qr[1][0], wc[1][0][k], t);
-                    t = fma(qr[1][1], wc[1][1][k], t);
-                    L[(r * O + k) * 64 + lane] = t;
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                        for (int e = 0; e < 2; ++e) ca[h][e][k] = fma(qc[h][e], wr[k], ca[h][e][k]);
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const int g = lane >> 4, jl = lane & 15;
-#pragma unroll
-            for (int v0 = 0; v0 < V; v0 += 4) {
-                const int v = v0 + g;
-                double t = 0.0;
-                if (v < V) {
-                    const double2 x = *reinterpret_cast<const double2 *>(L + v * 64 + 4 * jl), y = *reinterpret_cast<const double2 *>(L + v * 64 + 4 * jl + 2);
-                    t = (x.x + x.y) + (y.x + y.y);
-                }
-                t = group_sum<16>(t);
-                if (jl == 0 && v < V) Prow[((size_t)s * (size_t)R + (size_t)r0) * O + v] = t;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
         };
-        auto run = [&](int j, const QFrag4<T> (&q)[6], const double wl) __attribute__((always_inline)) {
-            if (j < jfull) step(j, q, wl, std::false_type{});
-            else step(j, q, wl, std::true_type{});
-        };
-        QFrag4<T> qA[6], qB[6];
-        double wA = 0.0, wB = 0.0;
-        if (jb < je) load_q(rev ? je - 1 : jb, qA, wA);
+        if (jb < je) load(symv_walk_at(jb, je, rev, 0), std::integral_constant<int, 0>{});
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -3282,25 +3088,7 @@ __global__ __launch_bounds__(256) void qw_symv_f32_kernel(const float *__restric
         if (!AUTO && scal != nullptr) {
             if (scal->status != 0) return false;
         }
-        auto at = [&](int i) __attribute__((always_inline)) { return rev ? je - 1 - i : jb + i; };
-        const int cnt = je - jb;
-        if (cnt > 0) {
-            int i = 0;
-            while (i + 2 < cnt) {
-                load_q(at(i + 1), qB, wB);
-                run(at(i), qA, wA);
-                load_q(at(i + 2), qA, wA);
-                run(at(i + 1), qB, wB);
-                i += 2;
-            }
-            if (i + 1 < cnt) {
-                load_q(at(i + 1), qB, wB);
-                run(at(i), qA, wA);
-                run(at(i + 1), qB, wB);
-            } else {
-                run(at(i), qA, wA);
-            }
-        }
+        symv_walk(jb, je, rev, load, run);
         return true;
     };
     bool alive;
@@ -3314,23 +3102,8 @@ __global__ __launch_bounds__(256) void qw_symv_f32_kernel(const float *__restric
         alive = nt ? sweep(Qf, std::true_type{}) : sweep(Qf, std::false_type{});
     }
     if (!alive) return;
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-#pragma unroll
-            for (int k = 0; k < O; ++k) L[((h * 2 + e) * O + k) * 64 + lane] = ca[h][e][k];
-    __syncthreads();
-    if (wave < 2 && lane_ok) {   // wavefront h writes the column pair h of every lane
-        double *pc = Pcol + ((size_t)sc * (size_t)ld + (size_t)(cA + 2 * wave)) * O;
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-#pragma unroll
-            for (int k = 0; k < O; ++k) {
-                const int idx = ((wave * 2 + e) * O + k) * 64 + lane;
-                pc[e * O + k] = ((lds[0][idx] + lds[1][idx]) + lds[2][idx]) + lds[3][idx];
-            }
-    }
+    // wavefront h writes the column pair h of every lane
+    symv_colsum<O>(ca, lds, wave, lane, lane_ok, Pcol + ((size_t)ch.sc * (size_t)ld + (size_t)(cA + 2 * wave)) * O);
 }
 
 // bad: device counter of elements that are not finite in fp32, zeroed here; the caller reads it after the stream has run

@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "xm_device.h"
+#include "xm_symv_step.h"
 
 namespace xm {
 
@@ -54,6 +55,7 @@ size_t symw_csum_count(int64_t ntot, int o) { return (size_t)3 * (size_t)ntot * 
 
 // ------------------------------------------------------------------------------------------------------------------
 // device: the sweep.  One wavefront per work item (strip of 256 columns x up to K steps of 6 rows of this rank's strip of Q).
+// The step is the triangular sweep's (xm_symv_step.h:symv_step) under this kernel's masks, with the six rows of W from scalar loads.
 // ------------------------------------------------------------------------------------------------------------------
 template <int O, bool NT>
 __global__ __launch_bounds__(256) void qw_symw_kernel(const double *__restrict__ Q, int64_t ld, const double *__restrict__ W, SymwGeom g,
@@ -111,12 +113,18 @@ __global__ __launch_bounds__(256) void qw_symw_kernel(const double *__restrict__
             }
         }
     };
-    auto step = [&](int j, const double2 (&q)[6][2], auto masked) {
-        constexpr bool MASK = decltype(masked)::value;
+    auto run = [&](int j, const double2 (&q)[6][2]) {
         const int t = g.t0 + j;
         const int64_t r0 = (int64_t)6 * j;
+        auto qat = [&](int r, int h, int e) __attribute__((always_inline)) { return e ? q[r][h].y : q[r][h].x; };
+        auto wrow = [&](int r, double (&wr)[O]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int k = 0; k < O; ++k) wr[k] = W[(size_t)(R0 + r0 + r) * OP + k];   // wave-uniform: scalar loads
+        };
+        double *prow = Prow + ((size_t)s * (size_t)R + (size_t)r0) * O;
         double mr[2] = {1.0, 1.0}, mc[2] = {1.0, 1.0};
-        if constexpr (MASK) {
+        if (symw_full(g, t, s)) symv_step<O, false>(qat, mr, mc, wrow, wc, ca, L, lane, prow);   // wave-uniform
+        else {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const bool real = ucol[h] >= 0;
@@ -125,52 +133,8 @@ __global__ __launch_bounds__(256) void qw_symw_kernel(const double *__restrict__
                 mr[h] = (use || diag) ? 1.0 : 0.0;   // row direction: the used blocks and the whole diagonal block
                 mc[h] = use ? 1.0 : 0.0;             // column direction: the used blocks only
             }
+            symv_step<O, true>(qat, mr, mc, wrow, wc, ca, L, lane, prow);
         }
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            double wr[O];
-#pragma unroll
-            for (int k = 0; k < O; ++k) wr[k] = W[(size_t)(R0 + r0 + r) * OP + k];   // wave-uniform: scalar loads
-            double qr[2][2], qc[2][2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                qr[h][0] = MASK ? q[r][h].x * mr[h] : q[r][h].x; qr[h][1] = MASK ? q[r][h].y * mr[h] : q[r][h].y;
-                qc[h][0] = MASK ? q[r][h].x * mc[h] : q[r][h].x; qc[h][1] = MASK ? q[r][h].y * mc[h] : q[r][h].y;
-            }
-#pragma unroll
-            for (int k = 0; k < O; ++k) {
-                double tt = qr[0][0] * wc[0][0][k];
-                tt = fma(qr[0][1], wc[0][1][k], tt);
-                tt = fma(qr[1][0], wc[1][0][k], tt);
-                tt = fma(qr[1][1], wc[1][1][k], tt);
-                L[(r * O + k) * 64 + lane] = tt;
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) ca[h][e][k] = fma(qc[h][e], wr[k], ca[h][e][k]);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        // 64 addends per value: a 16-lane row takes value v = 4 i + (lane / 16), each lane four addends, DPP row sum (as qw_symv_kernel)
-        const int gq = lane >> 4, jl = lane & 15;
-#pragma unroll
-        for (int v0 = 0; v0 < V; v0 += 4) {
-            const int v = v0 + gq;
-            double tt = 0.0;
-            if (v < V) {
-                const double2 a = *reinterpret_cast<const double2 *>(L + v * 64 + 4 * jl), b = *reinterpret_cast<const double2 *>(L + v * 64 + 4 * jl + 2);
-                tt = (a.x + a.y) + (b.x + b.y);
-            }
-            tt = group_sum<16>(tt);
-            if (jl == 0 && v < V) Prow[((size_t)s * (size_t)R + (size_t)r0) * O + v] = tt;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-    auto run = [&](int j, const double2 (&q)[6][2]) {
-        if (symw_full(g, g.t0 + j, s)) step(j, q, std::false_type{});   // wave-uniform
-        else step(j, q, std::true_type{});
     };
 
     double2 qA[6][2], qB[6][2];
