@@ -973,6 +973,82 @@ int xm_ctx_filter_tracks(xm_ctx_t *ctx, const xm_tf_options_t *opt, const double
 /* out[0] = observations of the longest landmark that one thread walks (longer ones get a workgroup), out[1] = rays per LDS tile of the
  * workgroup form, out[2] = threads per workgroup (host-only; tests derive their boundary cases from them) */
 int xm_track_filter_limits(int64_t out[3]);
+/* ---- Pruning weakly connected images by covisibility clusters: step 8 of the reference's fork of GLOMAP, PruneWeaklyConnectedImages
+ * (deps/glomap/glomap/processors/reconstruction_pruning.cc:6-84) with ViewGraphManipulater::EstablishStrongClusters
+ * (processors/view_graph_manipulation.cc:68-168) and ViewGraph::KeepLargestConnectedComponents / MarkConnectedComponents
+ * (scene/view_graph.cc:9-90), as a query on the device over an observation list.  NOTHING HERE WAS COMPARED WITH THE REFERENCE'S COMPILED
+ * CODE (it needs COLMAP, Eigen and glog): parity rests on a line-cited sequential restatement (tests/xm_prune_numpy.py).
+ * Input: n cameras (the reference's images), m landmarks (its tracks), nobs observations (cam[e], lm[e]), 0-based.  An observation is
+ * USED when its weight is > 0 (w == NULL: all; the rule of xm_clean_observations).  L_l = used observations of landmark l; landmarks with
+ * L_l <= 2 are skipped (:14).  A (camera, landmark) pair named twice counts twice, as in the reference's loops.  a_l(i) = used
+ * observations of camera i in the landmark l that is not skipped.
+ *   1 observation count  obs_count[i] = sum over l of a_l(i) (:17).
+ *   2 covisibility       for i < j: covis(i, j) = sum over l of a_l(i) a_l(j) (:16-31, with its image_id1 == image_id2 skip).
+ *   3 visibility graph   pairs_covisible = pairs with covis >= min_covisibility (5, :41; the reference's `counter`); the EDGES are those of
+ *                        them with obs_count >= min_num_observations at both ends (:46-48); an edge's weight is its covis.
+ *   4 threshold          median = element E / 2 (integer division) of the sorted edge weights, mad = element E / 2 of the sorted
+ *                        |weight - median| (:61-70), threshold = max(median - mad, min_threshold) (20.0, :80): integers held exactly in a
+ *                        double.  DEPARTURE: E = 0 is undefined behaviour in the reference (pair_count[0] of an empty vector); here every
+ *                        cluster_id = -1, n_clusters = 0, threshold = 0, rounds = 0 and XM_OK.
+ *   5 largest component  of the edges (view_graph.cc:9-46); edges outside it become invalid.  DEPARTURE: of several largest ones the
+ *                        component with the smallest image index stays (the reference: the first in hash order).
+ *   6 strong clusters    union over the valid edges with weight > threshold (view_graph_manipulation.cc:79-90); an image without such an
+ *                        edge is a cluster of its own.  strong_clusters counts the clusters among the images of the largest component.
+ *   7 merge rounds       (:95-149) in a round every valid edge that is not `weight < 0.75 threshold` (the product computed once, in double)
+ *                        and whose ends lie in different clusters counts once for its unordered pair of clusters; all cluster pairs with
+ *                        count >= 2 are united at once: the new clusters are the components of that cluster graph, so the order of the
+ *                        unions cannot matter.  Rounds repeat while a round united anything; the body runs at most 10 times
+ *                        (`iteration > 10` breaks in front of the 11th).  rounds = bodies run; weak_edges = the edges the first round
+ *                        looked at.
+ *   8 final marking      (:151-161, view_graph.cc:66-90) valid edges whose ends differ in cluster become invalid; the components of what
+ *                        is left are sorted by size, descending; DEPARTURE: equal sizes go by smallest image index first (the reference
+ *                        sorts (size, index into a hash-ordered vector)).  Components get cluster_id 0, 1, ... while their size is
+ *                        >= min_num_images (2); every other image, every image without a valid edge included, gets -1.
+ * Output (host arrays): cluster_id[n], obs_count[n]; pairs (optional): the visibility graph in (i, j) order, i < j, into host arrays of
+ * `capacity` entries each; with a capacity below n_edges nothing is written, and n_edges says what is needed.  seconds_kernels: from the
+ * call to the final labels on the host; seconds_download: the pairs.
+ * On the device (xm_prune.h): a workgroup per camera with an LDS histogram of xm_prune_limits()[0] camera bins at a time (integer LDS
+ * atomics: a sum has one value in any order), a prefix sum for the positions of the edges, a two-level histogram select for the two order
+ * statistics, and three component labellings.  No floating-point atomic, and no atomic decides an order or a position.  The merge rounds
+ * run on the host over the downloaded edges that step 7 looks at; the final ranking of the components too.  The call changes nothing it is
+ * given; two calls give the same bits, and every output equals the restatement in numpy exactly.
+ * Limits: n, m, nobs and n_edges below 2^31 each and every covis below 2^31 (XM_ERR_ARG where the call can see it).
+ * xm_prune_weakly_connected: host arrays, uploaded inside the call.  xm_ctx_prune_weakly_connected: the lists an XM_STORAGE_SCHUR
+ * context holds on the device at its CURRENT weights, with no upload of the list.  XM_ERR_ARG (context unchanged and usable): another
+ * storage, several ranks or a communicator, a struct_size that is not sizeof, null outputs, a negative option, a min_threshold that is
+ * not finite, a pairs struct with capacity < 0 or with a null array at capacity > 0, an index out of range. */
+typedef struct {
+    uint32_t struct_size;
+    int32_t min_covisibility;      /* GLOMAP: 5 */
+    int32_t min_num_images;        /* GLOMAP: 2 */
+    int32_t min_num_observations;  /* GLOMAP: 0 */
+    double min_threshold;          /* GLOMAP: 20.0 */
+} xm_prune_options_t;
+#define XM_PRUNE_OPTIONS_INIT {(uint32_t)sizeof(xm_prune_options_t), 5, 2, 0, 20.0}
+typedef struct {
+    int64_t capacity;
+    int32_t *i, *j, *count;
+} xm_prune_pairs_t;
+typedef struct {
+    uint32_t struct_size;
+    int32_t rounds;                /* bodies of the merge loop that ran (0: empty graph) */
+    int64_t pairs_covisible, n_edges;
+    double median, mad, threshold;
+    int64_t component_images;      /* images of the largest component */
+    int64_t strong_clusters;       /* clusters of step 6 among them */
+    int64_t weak_edges;            /* edges the first merge round looked at */
+    int64_t n_clusters, images_clustered;
+    double seconds_kernels, seconds_download;
+} xm_prune_result_t;
+int xm_prune_weakly_connected(int64_t n, int64_t m, int64_t nobs, const int32_t *cam, const int32_t *lm, const double *w /* NULL: all used */,
+                              const xm_prune_options_t *opt, int32_t *cluster_id, int32_t *obs_count, const xm_prune_pairs_t *pairs /* may be NULL */,
+                              xm_prune_result_t *res);
+int xm_ctx_prune_weakly_connected(xm_ctx_t *ctx, const xm_prune_options_t *opt, int32_t *cluster_id, int32_t *obs_count,
+                                  const xm_prune_pairs_t *pairs /* may be NULL */, xm_prune_result_t *res);
+/* out[0] = camera bins per LDS tile of the covisibility histogram, out[1] = threads per workgroup, out[2] = entries of the longest landmark
+ * list that a group of out[3] lanes walks (longer ones: the whole workgroup), out[4] = low bits of the order statistics' second level
+ * (host-only; tests derive their boundary cases from them) */
+int xm_prune_limits(int64_t out[5]);
 
 /* ================================================================== 3. kernel-level entry points (device pointers) */
 /* device memory helpers so that callers need no other GPU runtime */

@@ -11,6 +11,7 @@
 #include "xm_ba.h"
 #include "xm_clean.h"
 #include "xm_trackfilter.h"
+#include "xm_prune.h"
 #include "xm_lift.h"
 #include "xm_tracks.h"
 #include "xm_tracks_split.h"
@@ -707,6 +708,74 @@ int xm_track_filter_limits(int64_t out[3]) {
     XM_TRY
     if (!out) throw xm::Error(XM_ERR_ARG, "xm_track_filter_limits: null argument");
     out[0] = xm::kSchurHeavy; out[1] = xm::kTfTile; out[2] = xm::kTfThreads;
+    return XM_OK;
+    XM_CATCH
+}
+namespace {
+void prune_settings(const char *who, const xm_prune_options_t *opt, const int32_t *cluster_id, const int32_t *obs_count, const xm_prune_pairs_t *pairs,
+                    const xm_prune_result_t *res, xm::PruneSettings &c, xm::PrunePairs &pp) {
+    const std::string w(who);
+    if (!opt || !cluster_id || !obs_count || !res) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (opt->struct_size != sizeof(xm_prune_options_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_prune_options_t.struct_size is not sizeof(xm_prune_options_t)");
+    if (res->struct_size != sizeof(xm_prune_result_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_prune_result_t.struct_size is not sizeof(xm_prune_result_t)");
+    if (opt->min_covisibility < 0 || opt->min_num_images < 0 || opt->min_num_observations < 0) throw xm::Error(XM_ERR_ARG, w + ": negative option");
+    if (!std::isfinite(opt->min_threshold)) throw xm::Error(XM_ERR_ARG, w + ": min_threshold is not finite");
+    if (pairs) {
+        if (pairs->capacity < 0) throw xm::Error(XM_ERR_ARG, w + ": xm_prune_pairs_t.capacity is negative");
+        if (pairs->capacity > 0 && (!pairs->i || !pairs->j || !pairs->count)) throw xm::Error(XM_ERR_ARG, w + ": null array in xm_prune_pairs_t");
+        pp.capacity = pairs->capacity; pp.i = pairs->i; pp.j = pairs->j; pp.count = pairs->count;
+    }
+    c.min_covisibility = opt->min_covisibility; c.min_num_images = opt->min_num_images; c.min_num_observations = opt->min_num_observations;
+    c.min_threshold = opt->min_threshold;
+}
+void give_prune(xm_prune_result_t *res, const xm::PruneOutcome &r) {
+    xm_prune_result_t out;
+    std::memset(&out, 0, sizeof(out));
+    out.struct_size = sizeof(xm_prune_result_t);
+    out.rounds = r.rounds; out.pairs_covisible = r.pairs_covisible; out.n_edges = r.n_edges; out.median = r.median; out.mad = r.mad;
+    out.threshold = r.threshold; out.component_images = r.component_images; out.strong_clusters = r.strong_clusters; out.weak_edges = r.weak_edges;
+    out.n_clusters = r.n_clusters; out.images_clustered = r.images_clustered; out.seconds_kernels = r.seconds_kernels;
+    out.seconds_download = r.seconds_download;
+    *res = out;
+}
+}  // namespace
+int xm_prune_weakly_connected(int64_t n, int64_t m, int64_t nobs, const int32_t *cam, const int32_t *lm, const double *w, const xm_prune_options_t *opt,
+                              int32_t *cluster_id, int32_t *obs_count, const xm_prune_pairs_t *pairs, xm_prune_result_t *res) {
+    XM_TRY
+    xm::PruneSettings c;
+    xm::PrunePairs pp;
+    prune_settings("xm_prune_weakly_connected", opt, cluster_id, obs_count, pairs, res, c, pp);
+    if (n < 0 || m < 0 || nobs < 0) throw xm::Error(XM_ERR_ARG, "xm_prune_weakly_connected: negative size");
+    if (n >= ((int64_t)1 << 31) || m >= ((int64_t)1 << 31) || nobs >= ((int64_t)1 << 31))
+        throw xm::Error(XM_ERR_ARG, "xm_prune_weakly_connected: cameras, landmarks and observations must each stay below 2^31");
+    if (nobs > 0 && (!cam || !lm)) throw xm::Error(XM_ERR_ARG, "xm_prune_weakly_connected: null observation arrays");
+    require_device();
+    if (const char *e = std::getenv("XM_WATCHDOG_S")) { const double v = std::atof(e); if (v > 0) c.watchdog_s = v; }
+    xm::PruneOutcome r;
+    xm::prune_host(n, m, nobs, cam, lm, w, c, cluster_id, obs_count, pairs ? &pp : nullptr, r);
+    give_prune(res, r);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_ctx_prune_weakly_connected(xm_ctx_t *ctx, const xm_prune_options_t *opt, int32_t *cluster_id, int32_t *obs_count, const xm_prune_pairs_t *pairs,
+                                  xm_prune_result_t *res) {
+    XM_TRY
+    if (!ctx) throw xm::Error(XM_ERR_ARG, "xm_ctx_prune_weakly_connected: null argument");
+    xm::PruneSettings c;
+    xm::PrunePairs pp;
+    prune_settings("xm_ctx_prune_weakly_connected", opt, cluster_id, obs_count, pairs, res, c, pp);
+    if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_prune_weakly_connected: single-GPU contexts only (not n_gpus > 1)");
+    if (ctx->impl->world() > 1) throw xm::Error(XM_ERR_ARG, "xm_ctx_prune_weakly_connected: single-rank contexts only");
+    xm::PruneOutcome r;
+    ctx->impl->prune_weakly_connected(c, cluster_id, obs_count, pairs ? &pp : nullptr, r);
+    give_prune(res, r);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_prune_limits(int64_t out[5]) {
+    XM_TRY
+    if (!out) throw xm::Error(XM_ERR_ARG, "xm_prune_limits: null argument");
+    out[0] = xm::kPruneTile; out[1] = xm::kPruneThreads; out[2] = xm::kPruneHeavy; out[3] = xm::kPruneGroup; out[4] = xm::kPruneSelBits;
     return XM_OK;
     XM_CATCH
 }

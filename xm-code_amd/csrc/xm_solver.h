@@ -122,6 +122,9 @@ struct CleanSettings;  // xm_clean.h
 struct CleanOutcome;
 struct TfSettings;     // xm_trackfilter.h
 struct TfOutcome;
+struct PruneSettings;  // xm_prune.h
+struct PrunePairs;
+struct PruneOutcome;
 
 struct PointState {  // everything the gradient epilogue writes for one point (R, s)
     DevBuf<double> G, egs, S0, rgR, rgs;
@@ -171,6 +174,8 @@ public:
     // GLOMAP's track filters at (rot, t, p) with the current weights (xm_trackfilter.h); cfg.watchdog_s is the context's
     void filter_tracks(const TfSettings &cfg, const double *rot, const double *t, const double *p, uint8_t *keep, uint8_t *reason,
                        int32_t *lm_views, uint8_t *lm_status, TfOutcome &out);
+    // covisibility clusters of the cameras at the current weights (xm_prune.h); changes nothing here
+    void prune_weakly_connected(const PruneSettings &cfg, int32_t *cluster_id, int32_t *obs_count, const PrunePairs *pairs, PruneOutcome &out);
     // which observations, cameras and landmarks of the list survive cleaning at the current weights (xm_clean.h); changes nothing here
     void clean_observations(const CleanSettings &cfg, uint8_t *keep, int32_t *cam_index, int32_t *lm_index, CleanOutcome &out);
     // XM^2 with the reference's residual definition (3_test_colmap_glomap.py:305-316): squared distance per edge / observation of the

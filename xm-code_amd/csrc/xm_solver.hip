@@ -16,6 +16,7 @@
 #include "xm_ba.h"
 #include "xm_clean.h"
 #include "xm_trackfilter.h"
+#include "xm_prune.h"
 
 #include <algorithm>
 #include <chrono>
@@ -2398,6 +2399,14 @@ void Context::filter_tracks(const TfSettings &cfg, const double *rot, const doub
     TfSettings c = cfg;
     c.watchdog_s = cfg_.watchdog_s;
     xm::filter_tracks(*schur_, c, rot, t, p, keep, reason, lm_views, lm_status, out, st_);
+}
+void Context::prune_weakly_connected(const PruneSettings &cfg, int32_t *cluster_id, int32_t *obs_count, const PrunePairs *pairs, PruneOutcome &out) {
+    if (!schur_)
+        throw Error(XM_ERR_ARG, "xm_ctx_prune_weakly_connected: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no observations");
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_prune_weakly_connected: single-rank contexts only");
+    PruneSettings c = cfg;
+    c.watchdog_s = cfg_.watchdog_s;
+    xm::prune(*schur_, c, cluster_id, obs_count, pairs, out, st_);
 }
 void Context::clean_observations(const CleanSettings &cfg, uint8_t *keep, int32_t *cam_index, int32_t *lm_index, CleanOutcome &out) {
     if (!schur_)

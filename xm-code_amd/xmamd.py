@@ -43,6 +43,7 @@ EXPORTS = [
     "xm_build_tracks", "xm_tracks_limits", "xm_tracks_split_host", "xm_tracks_split_device", "xm_tracks_split_limits", "xm_tracks_split_stats",
     "xm_view_graph_filter", "xm_view_graph_limits",
     "xm_ctx_filter_tracks", "xm_track_filter_limits",
+    "xm_prune_weakly_connected", "xm_ctx_prune_weakly_connected", "xm_prune_limits",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -238,6 +239,22 @@ class TfResult(C.Structure):       # xm_tf_result_t
                [(k, C.c_double) for k in ("cos_angle", "cos_triangulation", "seconds_kernels", "seconds_download")]
 
 
+class PruneOptions(C.Structure):   # xm_prune_options_t; the defaults are GLOMAP's (XM_PRUNE_OPTIONS_INIT)
+    _fields_ = [("struct_size", C.c_uint32), ("min_covisibility", C.c_int32), ("min_num_images", C.c_int32), ("min_num_observations", C.c_int32),
+                ("min_threshold", C.c_double)]
+
+
+class PrunePairs(C.Structure):     # xm_prune_pairs_t
+    _fields_ = [("capacity", C.c_int64), ("i", C.c_void_p), ("j", C.c_void_p), ("count", C.c_void_p)]
+
+
+class PruneResult(C.Structure):    # xm_prune_result_t
+    _fields_ = [("struct_size", C.c_uint32), ("rounds", C.c_int32), ("pairs_covisible", C.c_int64), ("n_edges", C.c_int64), ("median", C.c_double),
+                ("mad", C.c_double), ("threshold", C.c_double), ("component_images", C.c_int64), ("strong_clusters", C.c_int64),
+                ("weak_edges", C.c_int64), ("n_clusters", C.c_int64), ("images_clustered", C.c_int64), ("seconds_kernels", C.c_double),
+                ("seconds_download", C.c_double)]
+
+
 class PairOptions(C.Structure):    # xm_pair_options_t; the defaults are the reference's constants (XM_PAIR_OPTIONS_INIT)
     _fields_ = [("struct_size", C.c_uint32), ("min_joint", C.c_int32), ("min_flags", C.c_int32), ("flags", C.c_uint32), ("trim", C.c_double),
                 ("dist_pct", C.c_double), ("err_pct", C.c_double), ("mad_factor", C.c_double)]
@@ -401,6 +418,10 @@ def lib():
         L.xm_tracks_split_stats.argtypes = [C.c_void_p]
         L.xm_ctx_filter_tracks.argtypes = [C.c_void_p, C.POINTER(TfOptions)] + [C.c_void_p] * 7 + [C.POINTER(TfResult)]
         L.xm_track_filter_limits.argtypes = [C.c_void_p]
+        L.xm_prune_weakly_connected.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PruneOptions), C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.POINTER(PruneResult)]
+        L.xm_ctx_prune_weakly_connected.argtypes = [C.c_void_p, C.POINTER(PruneOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PruneResult)]
+        L.xm_prune_limits.argtypes = [C.c_void_p]
         L.xm_ctx_reprojection_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_transport.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
         L.xm_ctx_dense_q.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -831,6 +852,113 @@ def track_filter_limits():
     out = np.zeros(3, dtype=np.int64)
     _chk(lib().xm_track_filter_limits(out.ctypes.data_as(C.c_void_p)))
     return dict(light_max=int(out[0]), tile=int(out[1]), threads=int(out[2]))
+
+
+class PrunePlan:
+    """what prune_weakly_connected / Context.prune_weakly_connected found: cluster_id (int32 per camera: 0 is the largest cluster, -1 a
+    pruned image), obs_count (int32 per camera), info (the fields of xm_prune_result_t) and pairs -- the visibility graph as (i, j, count),
+    three int32 arrays in (i, j) order, or None when it was not asked for"""
+
+    def __init__(self, cluster_id, obs_count, info, pairs=None, cam=None):
+        self.cluster_id, self.obs_count, self.info, self.pairs = cluster_id, obs_count, info, pairs
+        self._cam = cam   # camera of every observation of the list the call was made on
+
+    def keep(self, cluster=0):
+        """bool per observation of the pruned list: its camera lies in `cluster`"""
+        if self._cam is None:
+            raise XmError("PrunePlan: the observations' cameras are not known here")
+        return self.cluster_id[self._cam] == int(cluster)
+
+    def weights(self, w, cluster=0):
+        """w (one weight per observation) with zeros for the observations of cameras outside `cluster`: the w of the
+        clean_observations call that drops and renumbers those cameras for the next context"""
+        w = np.array(w, dtype=np.float64).reshape(-1)
+        k = self.keep(cluster)
+        if w.shape != k.shape:
+            raise XmError("PrunePlan.weights: w must have one entry per observation of the pruned list")
+        w[~k] = 0.0
+        return w
+
+    def apply(self, *per_observation, cluster=0):
+        """the rows of the observations whose camera lies in `cluster`, in input order, of every array given (cam, lm, p, w, ...)"""
+        k = self.keep(cluster)
+        out = []
+        for a in per_observation:
+            a = np.asarray(a)
+            if a.shape[:1] != k.shape:
+                raise XmError("PrunePlan.apply: a per-observation array has another length than the pruned list")
+            out.append(a[k])
+        return tuple(out)
+
+
+def prune_limits():
+    """-> dict(tile: camera bins per LDS tile of the covisibility histogram, threads: per workgroup, group_max: entries of the longest
+    landmark list that a group of `group` lanes walks (longer ones: the whole workgroup), select_bits: low bits of the second level of the
+    order statistics)"""
+    out = np.zeros(5, dtype=np.int64)
+    _chk(lib().xm_prune_limits(out.ctypes.data_as(C.c_void_p)))
+    return dict(tile=int(out[0]), threads=int(out[1]), group_max=int(out[2]), group=int(out[3]), select_bits=int(out[4]))
+
+
+def _prune_options(min_covisibility, min_num_images, min_num_observations, min_threshold):
+    if int(min_covisibility) < 0 or int(min_num_images) < 0 or int(min_num_observations) < 0:
+        raise XmError("prune_weakly_connected: negative option")
+    if not np.isfinite(min_threshold):
+        raise XmError("prune_weakly_connected: min_threshold is not finite")
+    opt = PruneOptions(); res = PruneResult()
+    opt.struct_size, res.struct_size = C.sizeof(PruneOptions), C.sizeof(PruneResult)
+    opt.min_covisibility, opt.min_num_images, opt.min_num_observations = int(min_covisibility), int(min_num_images), int(min_num_observations)
+    opt.min_threshold = float(min_threshold)
+    return opt, res
+
+
+def _prune_call(call, n, pairs, cam):
+    """call(cluster_id, obs_count, pairs struct or None, result) -> rc; with pairs a second call sized by the first one's n_edges"""
+    cid = np.full(max(n, 0), -1, dtype=np.int32); cnt = np.zeros(max(n, 0), dtype=np.int32)
+    res = PruneResult(); res.struct_size = C.sizeof(PruneResult)
+    got = None
+    if pairs:
+        cap = 0 if pairs is True else int(pairs)          # True: ask for the size first; a number: the capacity to try
+        pi, pj, pc = (np.zeros(cap, dtype=np.int32) for _ in range(3))
+        pp = PrunePairs(cap, pi.ctypes.data_as(C.c_void_p), pj.ctypes.data_as(C.c_void_p), pc.ctypes.data_as(C.c_void_p))
+        _chk(call(cid, cnt, C.byref(pp), res))
+        if res.n_edges > cap and pairs is True:
+            cap = int(res.n_edges)
+            pi, pj, pc = (np.zeros(cap, dtype=np.int32) for _ in range(3))
+            pp = PrunePairs(cap, pi.ctypes.data_as(C.c_void_p), pj.ctypes.data_as(C.c_void_p), pc.ctypes.data_as(C.c_void_p))
+            _chk(call(cid, cnt, C.byref(pp), res))
+        if res.n_edges <= cap:
+            e = int(res.n_edges)
+            got = (pi[:e], pj[:e], pc[:e])
+    else:
+        _chk(call(cid, cnt, None, res))
+    info = {k: getattr(res, k) for k, _ in PruneResult._fields_ if k != "struct_size"}
+    return PrunePlan(cid, cnt, info, got, cam)
+
+
+def prune_weakly_connected(cam, lm, n=None, m=None, w=None, min_covisibility=5, min_num_images=2, min_num_observations=0, min_threshold=20.0,
+                           pairs=False):
+    """GLOMAP's PruneWeaklyConnectedImages (reconstruction_pruning.cc:6-84) on the device for a host list (xm_prune_weakly_connected;
+    include/xm_amd.h has the definition): cam, lm 0-based per observation, w: weights (an observation with w <= 0 is not used; None: all),
+    n / m: cameras / landmarks (None: largest index + 1).  pairs: True also returns the visibility graph (a second call sized by the
+    first), a number tries that capacity only (too small: plan.pairs is None and plan.info["n_edges"] says what is needed).  -> PrunePlan"""
+    cam = np.ascontiguousarray(cam, dtype=np.int32).reshape(-1); lm = np.ascontiguousarray(lm, dtype=np.int32).reshape(-1)
+    if cam.size != lm.size:
+        raise XmError("prune_weakly_connected: cam and lm must have one entry per observation")
+    if w is not None:
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if w.size != cam.size:
+            raise XmError("prune_weakly_connected: w must have one entry per observation")
+    n = (int(cam.max()) + 1 if cam.size else 0) if n is None else int(n)
+    m = (int(lm.max()) + 1 if lm.size else 0) if m is None else int(m)
+    opt, _ = _prune_options(min_covisibility, min_num_images, min_num_observations, min_threshold)
+    require_gpu()
+
+    def call(cid, cnt, pp, res):
+        return lib().xm_prune_weakly_connected(n, m, cam.size, cam.ctypes.data_as(C.c_void_p), lm.ctypes.data_as(C.c_void_p),
+                                               None if w is None else w.ctypes.data_as(C.c_void_p), C.byref(opt), cid.ctypes.data_as(C.c_void_p),
+                                               cnt.ctypes.data_as(C.c_void_p), pp, C.byref(res))
+    return _prune_call(call, n, pairs, cam)
 
 
 class PairFilterPlan:
@@ -1380,6 +1508,7 @@ class Context:
             self._keep += [cam, lm, pts, w]
             self.ne = cam.size                      # residuals / weights of the XM^2 loop are per observation
             self._w = w.copy()                      # the current weights, as far as this object set them (refine_filtered)
+            self._cam = cam.copy()                  # the camera of every observation (prune_weakly_connected's plan)
         elif dq is not None:                      # dense Q already on the device in the solver's layout (borrowed)
             self.n = int(n)
             p.n, p.storage, p.q_on_device, p.q, p.ldq = self.n, STORAGE_DENSE, 1, dq.ptr, dense_ld(self.n)
@@ -1800,8 +1929,21 @@ class Context:
         info = {k: getattr(res, k) for k, _ in TfResult._fields_ if k not in ("struct_size", "reserved")}
         return TrackFilterPlan(keep.astype(bool), reason, views, status, info)
 
+    def prune_weakly_connected(self, min_covisibility=5, min_num_images=2, min_num_observations=0, min_threshold=20.0, pairs=False):
+        """GLOMAP's PruneWeaklyConnectedImages (reconstruction_pruning.cc:6-84) over this context's observations at their CURRENT weights,
+        on the device and with no upload of the list (xm_ctx_prune_weakly_connected; include/xm_amd.h has the contract); matrix-free
+        contexts only, nothing in the context changes.  pairs: as in xmamd.prune_weakly_connected.  -> PrunePlan;
+        clean_observations(cam, lm, w=plan.weights(w)) gives the list of the next context without the images outside cluster 0 (this
+        context cannot take those weights: set_edge_weights refuses a camera without a weighted observation)."""
+        opt, _ = _prune_options(min_covisibility, min_num_images, min_num_observations, min_threshold)
+
+        def call(cid, cnt, pp, res):
+            return lib().xm_ctx_prune_weakly_connected(self.h, C.byref(opt), cid.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p), pp,
+                                                       C.byref(res))
+        return _prune_call(call, self.n, pairs, getattr(self, "_cam", None))
+
     def refine_filtered(self, rot, t, P, rounds=3, reprojection=1e-2, triangulation=1.0, min_views=0, restore_weights=False, weights=None,
-                        **bundle_adjust_kwargs):
+                        prune=False, **bundle_adjust_kwargs):
         """GLOMAP's alternation of bundle adjustment and track filtering (controllers/global_mapper.cc:243-317) on this context:
           for ite < rounds (:243): bundle_adjust with fix_rotations=True (:250-253), then the full one (:260-265); then (:282-297)
             while ite < rounds: filter_tracks(reprojection = max(3 - ite, 1) * reprojection) (:285-291); the landmarks it changed add up in
@@ -1819,7 +1961,12 @@ class Context:
         -> (rot, t, P, info): info["rounds"] one record per adjustment round (ba_fixed / ba_full: status and costs; filters: one record per
         filter call with scaling, threshold, dropped, tracks_changed, tracks_total), info["final"] the records of the two closing
         filters, info["keep"] the kept observations of the last filter call, info["weights"] the weights it ends with (before a
-        restore), info["stopped_early"] whether the 0.1 % rule ended the loop."""
+        restore), info["stopped_early"] whether the 0.1 % rule ended the loop.
+        prune=True runs prune_weakly_connected (GLOMAP's defaults) behind the closing filters: info["prune"] is its PrunePlan, and
+        info["weights"] has zeros for the observations of every camera with cluster_id != 0.  The CONTEXT keeps the weights of the closing
+        filters: set_edge_weights refuses a camera without a weighted observation, which is what every pruned camera becomes, so the
+        pruned list goes into the next context through clean_observations(cam, lm, w=info["weights"]), which drops and renumbers them.
+        The default, False, runs nothing more than before."""
         if "fix_rotations" in bundle_adjust_kwargs:
             raise XmError("refine_filtered: fix_rotations is set by the loop itself (a fixed-rotation adjustment, then the full one)")
         if int(rounds) < 0:
@@ -1868,7 +2015,13 @@ class Context:
         final = [run_filter(reprojection, None, 1)]                                     # :307-312
         if triangulation is not None:
             final.append(run_filter(None, triangulation, 1))                            # :313-317
+        plan = None
+        if prune:                                                                       # global_mapper.cc step 8: PruneWeaklyConnectedImages
+            plan = self.prune_weakly_connected()
+            state["w"] = plan.weights(state["w"])            # (not given to the context: it cannot hold a camera without a weight)
         info = dict(rounds=records, final=final, keep=state["keep"], weights=state["w"], stopped_early=stopped)
+        if plan is not None:
+            info["prune"] = plan
         if restore_weights and state["changed"]:
             self.set_edge_weights(w0)
         return rot, t, P, info
