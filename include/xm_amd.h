@@ -1147,6 +1147,94 @@ typedef struct {
     double *dP, *rot1, *t1, *p1;
 } xm_ba_probe_t;
 int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_ba_probe_t *probe);
+
+/* ---- Global positioning: camera centres and points from rotations and 2-D tracks, without an initial value.  Step 5 of GLOMAP's pipeline
+ * (controllers/global_mapper.cc:188-231), estimators/global_positioning.cc in its default ONLY_POINTS form, on the device over the observation
+ * lists of an XM_STORAGE_SCHUR context.  NOTHING HERE WAS COMPARED WITH THE REFERENCE'S COMPILED CODE (it needs Ceres, COLMAP, Eigen and glog):
+ * parity rests on a line-cited restatement (tests/xm_gp_numpy.py).
+ *   input       rot (3 x 3n column-major, R_i camera-to-world, READ ONLY), t (3 x n, camera centres), p (3 x n_landmarks, world points): the
+ *               layouts of xm_ctx_bundle_adjust.  t and p are host arrays; the call starts from them and updates them in place (xmamd.py's
+ *               gp_random_start gives the reference's 100 U(-1, 1)^3, .cc:141, :235).  Of an observation's camera-frame point p_e only the
+ *               bearing p_e / |p_e| is read.
+ *   used        an observation e = (i, l) is used when its current weight is > 0, p_e2 > 0 (the bundle adjustment's rule) and landmark l has
+ *               at least min_views observations that pass these two tests (0 = 3, global_positioning.h:33, .cc:119, :231).  Cameras,
+ *               landmarks and scales that are not used come back bit-identical (scales: -1).
+ *   residual    r_e = d_e - s_e (P_l - c_i) with d_e = R_i p_e / |p_e| (.cc:265-267, cost_function.h:26-29) and one scale s_e per used
+ *               observation: 1 at the start (.cc:273), bounded below by 1e-5 (.cc:297).  No camera is held fixed (.cc:337-338).
+ *   cost        F = 1/2 sum rho(|r_e|^2); loss, loss_scale as in xm_ba_options_t (the reference: XM_BA_LOSS_HUBER with 0.1,
+ *               global_positioning.h:44-45); definitions, the clamp of rho' and the Corrector convention are those of xm_ctx_bundle_adjust.
+ *   step        the Levenberg-Marquardt rules of xm_ctx_bundle_adjust word for word (radius, D = diag(J^T J) clamped to [1e-6, 1e32],
+ *               acceptance at rho > 1e-3, radius updates, stops, trace record) over x = (c, P, s); |x|^2 of the parameter test is
+ *               sum |c|^2 + sum |P|^2 + sum s^2 over what is used.  Elimination in Ceres's order (.cc:310-331): the scales in closed form
+ *               (with w = rho', v = P_l - c_i, h* = w |v|^2 + mu clamp(w |v|^2), g_s = -w r.v:  M_e = w s^2 I - (w s)^2 v v^T / h*,
+ *               q_e = w s (r + v g_s / h*)), then the landmarks (V_l = sum M_e, W_e = -M_e), then the cameras (U_i = sum M_e) by PCG from
+ *               zero with the inverted 3 x 3 blocks of S to relative residual eta or 500 iterations; the damping of c and P is
+ *               mu clamp(sum w s^2), the diagonal of the full J^T J.  ds_e = -(g_s - w s v.dc + w s v.dP) / h*.
+ *   bound       DEPARTURE from Ceres (which projects the step and runs a line search): a scale with s_e <= 1e-5 whose gradient points
+ *               outward (g_s > 0) is frozen for that iteration (its column of J is zero: M_e = w s^2 I, q_e = w s r, ds_e = 0), and the
+ *               candidate is s <- max(s + ds, 1e-5).
+ *   departures  the start is the caller's (the reference draws it from std::mt19937 in hash-map order); every camera counts as calibrated (no
+ *               has_prior_focal_length down-weighting); only ONLY_POINTS (no camera-to-camera constraints); no NormalizeReconstruction;
+ *               no Jacobi column scaling (as xm_ctx_bundle_adjust).
+ * Options: struct_size = sizeof(xm_gp_options_t); max_iters, max_time, function_tol, gradient_tol, parameter_tol, min_views: 0 = the defaults
+ * (100 and 1e-5: optimization_base.h:23, :25; 300 s, 1e-10, 1e-8, 3); eta is required and lies in (0, 1).  trace as in xm_ba_options_t.  scales
+ * (may be NULL): nobs doubles in input order, -1 for an observation that is not used.
+ * XM_ERR_ARG (context unchanged and usable): not XM_STORAGE_SCHUR, several ranks or GPUs, a wrong struct_size, null arrays, non-finite
+ * input, eta outside (0, 1), negative settings, an unknown loss, a robust loss whose loss_scale is not finite and > 0, loss_scale != 0 with
+ * the trivial loss, a non-finite initial cost.  The call reads the context and changes nothing in it (Q, weights, solver workspace).  The
+ * workspace is allocated inside the call and freed before it returns.  Every sum over observations has a fixed order and no atomics are
+ * used: two calls give the same bits. */
+typedef struct {
+    uint32_t struct_size;
+    int32_t max_iters;
+    double max_time, eta, function_tol, gradient_tol, parameter_tol;
+    int32_t min_views;
+    int32_t trace_cap;
+    double *trace;
+    int32_t loss;              /* XM_BA_LOSS_* */
+    int32_t pad;
+    double loss_scale;
+} xm_gp_options_t;
+typedef struct {
+    uint32_t struct_size;
+    int32_t status;            /* XM_BA_* */
+    int32_t iters, accepted;
+    int64_t pcg_iters, n_used;
+    double initial_cost, final_cost, gradient_max, seconds;
+    int32_t trace_len, pad;
+} xm_gp_result_t;
+int xm_ctx_global_positioning(xm_ctx_t *ctx, const xm_gp_options_t *opt, const double *rot, double *t, double *p, double *scales_or_null,
+                              xm_gp_result_t *res);
+/* One linearisation of xm_ctx_global_positioning, a test export (tests/test_gpu_gp_stages.py): at the point (t, p, s) (s: nobs scales in
+ * input order, read where the observation is used; NULL = all 1) and the damping mu > 0 it writes the records and runs the landmark and
+ * camera passes with the kernels, grids and arguments of the LM loop (one workspace class serves both) and fills the scalars and every
+ * array whose pointer is not null; arrays per observation and per landmark come by input index.
+ *   cost, n_used, gmax                       the state word after the passes (gmax: |J^T r|_inf over c, P and the scales that are not frozen)
+ *   M (6 nobs: the entries 00 01 02 11 12 22 of M_e), q (3 nobs), frozen, oused (nobs)
+ *   vinv (6 m: (V + mu D)^-1), g_l (3 m), ustar, sinv (9 n, row-major blocks), b (3 n), cused (n), lused (m)
+ *   X (3n x k, column-major, input) -> SX = S X by the matrix-free product
+ *   dc (3n, input) -> dP (3 m), ds (nobs), the candidate t1, p1, s1 in the caller's layouts (what is not used: the input bits, s1: -1), cost1,
+ *                                            model = sum r.(J d) + |J d|^2 / 2, step2, x2 (cameras, landmarks, scales)
+ * min_views, loss, loss_scale as in xm_gp_options_t.  The context is only read.  Allocates and frees its workspace per call. */
+typedef struct {
+    uint32_t struct_size;
+    int32_t min_views;
+    int32_t loss, pad;
+    double loss_scale, mu;
+    int64_t k;
+    const double *s, *X, *dc;
+    double cost, gmax, cost1, model, step2[3], x2[3];
+    int64_t n_used;
+    double *M, *q;
+    int32_t *frozen, *oused;
+    double *vinv, *g_l, *ustar, *sinv, *b;
+    int32_t *cused, *lused;
+    double *SX, *dP, *ds, *t1, *p1, *s1;
+} xm_gp_probe_t;
+int xm_ctx_gp_probe(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_gp_probe_t *probe);
+/* constants of the kernels, host-only (the tests size their edge cases from them): out[0] = a landmark with more observations than this
+ * has a workgroup of its own, out[1] = observations a wavefront takes from a camera's list in one pass, out[2] = threads of that workgroup */
+int xm_gp_limits(int64_t out[3]);
 /* The trust region's kernels stage by stage, a test export (tests/test_gpu_rtr_stages.py): at the point (R: 3n x o column-major, s: n; s[0] is
  * forced to 1 as in a solve) and with lam, the stages below run through the context's own setup for rank o, its product dispatch and the
  * launchers, grids and arguments of a solve -- the kernels are those the storage and xm_tuning_t select (product_kind: XM_PRODUCT_*; split_k: slices of

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "xm_device.h"
+#include "xm_lm_shared.h"
 #include "xm_schur.h"
 #include "xm_stage.h"
 
@@ -17,115 +18,13 @@ namespace xm {
 
 namespace {
 
-constexpr int kBaHeavyThreads = 1024;   // a landmark with more than 64 observations: a workgroup of its own (as schur_lm_*)
-constexpr int kBaMaxPcgIters = 500;     // Ceres's max_linear_solver_iterations
-
 // per-observation record, one plane of `stride` doubles per entry: J_c (2 x CD, row-major), J_P (2 x 3), r (2)
 template <int CD> constexpr int ba_planes() { return 2 * CD + 8; }
 template <int CD> constexpr int ba_jp() { return 2 * CD; }
 template <int CD> constexpr int ba_res() { return 2 * CD + 6; }
 
-struct BaState {              // device-resident; the host reads it whole
-    int32_t done, iters;      // PCG: 1 = reached the tolerance; iterations performed
-    double relres;            // PCG: |r| / |b| when it stopped
-    double cost, used, gmax;  // at the current point: F, used observations, |J^T r|_inf
-    double cost_new, model;   // candidate: F, sum r.Jd + |Jd|^2 / 2
-    double step2[2], x2[2];   // |d|^2, |x|^2: cameras, landmarks
-    double res2[2];           // dense Schur: |b - S dc|^2, |b|^2
-    int32_t fail, pad;        // dense Schur: 1 = the factorisation or a substitution failed (cleared before each factorisation)
-};
-
-__device__ __forceinline__ double clamp_diag(double d) { return fmin(fmax(d, 1e-6), 1e32); }
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-template <int T>
-__device__ __forceinline__ double block_max(double v, double *sh) {   // result valid in thread 0
-    v = wave_max(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double m = 0.0;
-    if (threadIdx.x == 0)
-        for (int q = 0; q < T / 64; ++q) m = fmax(m, sh[q]);
-    return m;
-}
-// sum of K values over a heavy landmark's workgroup: DPP tree per wavefront, the 16 wavefront sums in a fixed order; valid in thread 0
-template <int K>
-__device__ __forceinline__ bool heavy_sum(double (&acc)[K]) {
-    __shared__ double part[kBaHeavyThreads / 64][K];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = wave_sum(acc[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) part[wv][k] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return false;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double t = 0.0;
-        for (int q = 0; q < kBaHeavyThreads / 64; ++q) t += part[q][k];
-        acc[k] = t;
-    }
-    return true;
-}
-// the observations of landmark slot l in the by-landmark lists (heavy: workgroup-strided, light: the packed 64-wide group)
-struct LmRange {
-    int64_t l, e, e_end, step;
-    bool heavy, active;
-};
-__device__ __forceinline__ LmRange lm_range(const SchurLists &S) {
-    LmRange r;
-    r.heavy = (int64_t)blockIdx.x < S.nheavy;
-    r.active = true;
-    if (r.heavy) {
-        r.l = blockIdx.x; r.e = S.lm_ptr[r.l] + threadIdx.x; r.e_end = S.lm_ptr[r.l + 1]; r.step = kBaHeavyThreads;
-    } else {
-        const int64_t t = ((int64_t)blockIdx.x - S.nheavy) * kBaHeavyThreads + threadIdx.x;
-        r.l = S.nheavy + t; r.step = 64;
-        r.active = r.l < S.m;
-        r.e = r.active ? S.gbase[t >> 6] + (t & 63) : 0;
-        r.e_end = r.active ? r.e + (int64_t)64 * S.deg[r.l] : 0;
-    }
-    return r;
-}
 __device__ __forceinline__ bool obs_used(const double (&v)[6]) { return v[0] != 0.0 || v[1] != 0.0 || v[2] != 0.0; }   // J_P row 0 (never 0 when used)
 
-// ---- robust losses: Ceres's definitions (loss_function.cc) of rho(s) and rho'(s) at s = |r|^2 for the scale a, rho' clamped below at the
-// smallest normal double as Ceres does.  rho'' <= 0 everywhere for these four, so Ceres's Corrector reduces to scaling r and J by
-// sqrt(rho'(s)): the eval kernel stores the scaled records and every later pass reads them as they are.  Since rho' >= DBL_MIN, sqrt(rho')
-// >= 2^-511 and the first row of a used observation's J_P (of norm >= 1 / |X2|) stays non-zero: obs_used does not depend on the loss.
-template <int LOSS>
-__device__ __forceinline__ double ba_rho(double s, double a, double &rho1) {
-    constexpr double kMinNormal = 2.2250738585072014e-308;
-    if constexpr (LOSS == XM_BA_LOSS_HUBER) {
-        const double b = a * a;
-        if (s > b) {
-            const double r = sqrt(s);
-            rho1 = fmax(kMinNormal, a / r);
-            return 2.0 * a * r - b;
-        }
-        rho1 = 1.0;
-        return s;
-    } else if constexpr (LOSS == XM_BA_LOSS_SOFT_L1) {
-        const double b = a * a, sum = 1.0 + s * (1.0 / b), tmp = sqrt(sum);
-        rho1 = fmax(kMinNormal, 1.0 / tmp);
-        return 2.0 * b * (tmp - 1.0);
-    } else if constexpr (LOSS == XM_BA_LOSS_CAUCHY) {
-        const double b = a * a, sum = 1.0 + s * (1.0 / b);
-        rho1 = fmax(kMinNormal, 1.0 / sum);
-        return b * log(sum);
-    } else {
-        static_assert(LOSS == XM_BA_LOSS_ARCTAN, "unknown loss");
-        const double sum = 1.0 + s * s * (1.0 / (a * a));
-        rho1 = fmax(kMinNormal, 1.0 / sum);
-        return a * atan2(s, a);
-    }
-}
 // Scale: the loss scale a (one double) for a robust LOSS, nothing for the trivial one, whose argument list and code are those it had before
 template <int LOSS, class... Scale>
 constexpr bool ba_loss_args() { return sizeof...(Scale) == (LOSS == XM_BA_LOSS_TRIVIAL ? 0 : 1); }
@@ -249,60 +148,6 @@ __global__ __launch_bounds__(kBaHeavyThreads) void ba_lm_kernel(SchurLists S, co
     if (threadIdx.x == 0) gpart[blockIdx.x] = m;
 }
 
-__device__ __forceinline__ void sym3(const double *vi, double (&V)[3][3]) {
-    V[0][0] = vi[0]; V[0][1] = V[1][0] = vi[1]; V[0][2] = V[2][0] = vi[2];
-    V[1][1] = vi[3]; V[1][2] = V[2][1] = vi[4]; V[2][2] = vi[5];
-}
-__device__ __forceinline__ constexpr int tri(int a, int b) { return a <= b ? b * (b + 1) / 2 + a : a * (a + 1) / 2 + b; }
-
-// A (CD x CD, symmetric positive definite) -> its inverse by Cholesky; not positive definite: the inverse of the diagonal
-template <int CD>
-__device__ void chol_inverse(const double (&A)[CD][CD], double *out) {
-    double L[CD][CD], Li[CD][CD];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < CD; ++j) {
-        double s = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
-        if (!(s > 0.0)) { ok = false; s = 1.0; }
-        L[j][j] = sqrt(s);
-#pragma unroll
-        for (int i = j + 1; i < CD; ++i) {
-            double t = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k];
-            L[i][j] = t / L[j][j];
-        }
-    }
-    if (!ok) {
-#pragma unroll
-        for (int i = 0; i < CD; ++i)
-#pragma unroll
-            for (int j = 0; j < CD; ++j) out[CD * i + j] = (i == j && A[i][i] > 0.0) ? 1.0 / A[i][i] : 0.0;
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < CD; ++j) {
-        Li[j][j] = 1.0 / L[j][j];
-#pragma unroll
-        for (int i = j + 1; i < CD; ++i) {
-            double t = 0.0;
-#pragma unroll
-            for (int k = j; k < i; ++k) t += L[i][k] * Li[k][j];
-            Li[i][j] = -t / L[i][i];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < CD; ++i)
-#pragma unroll
-        for (int j = 0; j < CD; ++j) {
-            double t = 0.0;
-#pragma unroll
-            for (int k = (i > j ? i : j); k < CD; ++k) t += Li[k][i] * Li[k][j];
-            out[CD * i + j] = t;
-        }
-}
 
 // ---- camera pass (a wavefront per camera): U_i, g_i; S_ii = U*_i - sum_l (sum_e W_e) V*_l^-1 (sum_f W_f)^T over the observations e, f of
 // (i, l) and its inverse; b_i = -g_i + sum W V*^-1 g_l
@@ -403,66 +248,6 @@ __global__ __launch_bounds__(256) void ba_cam_kernel(SchurLists S, const double 
     }
 }
 
-// ---- PCG on S dc = b (vectors: CD per camera).  Same scheme as SchurOp::pcg_solve: per-workgroup partials, every workgroup of the flat
-// kernels sums them in the same fixed order, the direction kernel decides convergence and publishes it through the state word
-struct BaPcg {
-    int64_t n;
-    int grid, cgrid;
-    double tol2;
-    const double *b, *sinv, *ustar;
-    double *x, *r, *z, *p, *Ap;
-    double *prz[2], *prr, *pbb, *ppap;
-    BaState *st;
-};
-template <int CD>
-__device__ __forceinline__ void block_matvec(const double *M, const double *v, double (&out)[CD]) {
-#pragma unroll
-    for (int j = 0; j < CD; ++j) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < CD; ++k) t += M[CD * j + k] * v[k];
-        out[j] = t;
-    }
-}
-template <int CD>
-__global__ __launch_bounds__(256) void ba_pcg_init_kernel(BaPcg a) {
-    __shared__ double sh[4];
-    double rz = 0.0, bb = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
-        double v[CD], z[CD];
-#pragma unroll
-        for (int k = 0; k < CD; ++k) v[k] = a.b[CD * i + k];
-        block_matvec<CD>(a.sinv + (size_t)CD * CD * i, v, z);
-#pragma unroll
-        for (int k = 0; k < CD; ++k) {
-            a.x[CD * i + k] = 0.0; a.r[CD * i + k] = v[k]; a.z[CD * i + k] = z[k]; a.p[CD * i + k] = z[k];
-            rz += v[k] * z[k]; bb += v[k] * v[k];
-        }
-    }
-    rz = block_sum256(rz, sh);
-    bb = block_sum256(bb, sh);
-    if (threadIdx.x == 0) { a.prz[0][blockIdx.x] = rz; a.pbb[blockIdx.x] = bb; a.prr[blockIdx.x] = bb; }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { a.st->done = 0; a.st->iters = 0; a.st->relres = 1.0; }
-}
-// iteration it >= 1: convergence test of the last update, else beta = <r,z>_new / <r,z>_old and p = z + beta p
-template <int CD>
-__global__ __launch_bounds__(256) void ba_pcg_dir_kernel(BaPcg a, int it) {
-    __shared__ double sh[4];
-    __shared__ int was_done;
-    if (threadIdx.x == 0) was_done = a.st->done;
-    __syncthreads();
-    if (was_done) return;
-    const double rzn = sum_partials256(a.prz[it & 1], a.grid, sh), rzo = sum_partials256(a.prz[(it & 1) ^ 1], a.grid, sh);
-    const double rr = sum_partials256(a.prr, a.grid, sh), bb = sum_partials256(a.pbb, a.grid, sh);
-    const double q = bb > 0.0 ? rr / bb : 0.0;
-    if (q <= a.tol2) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) { a.st->done = 1; a.st->iters = it; a.st->relres = sqrt(q); }
-        return;
-    }
-    const double beta = rzo > 0.0 ? rzn / rzo : 0.0;
-    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < a.n * CD; j += (int64_t)gridDim.x * 256) a.p[j] = a.z[j] + beta * a.p[j];
-    if (blockIdx.x == 0 && threadIdx.x == 0) { a.st->iters = it; a.st->relres = sqrt(q); }
-}
 // landmark side of S x (and of the back-substitution): y_l = sgn V*_l^-1 (g_l + sum_{obs of l} J_P^T J_c x_i)   (g: optional)
 template <int CD>
 __global__ __launch_bounds__(kBaHeavyThreads) void ba_lmx_kernel(SchurLists S, const double *__restrict__ Jl, const double *__restrict__ vinv,
@@ -544,34 +329,6 @@ __global__ __launch_bounds__(256) void ba_camx_kernel(SchurLists S, const double
         for (int q = 0; q < kQwWaves; ++q) t += red[q];
         a.ppap[blockIdx.x] = t;
     }
-}
-// alpha = <r,z> / <p,Ap>; x += alpha p, r -= alpha Ap, z = S_ii^-1 r; partials of the new <r,z> (other parity) and |r|^2
-template <int CD>
-__global__ __launch_bounds__(256) void ba_pcg_upd_kernel(BaPcg a, int it) {
-    __shared__ double sh[4];
-    if (a.st->done) return;
-    const double rz = sum_partials256(a.prz[it & 1], a.grid, sh), pap = sum_partials256(a.ppap, a.cgrid, sh);
-    const double alpha = (pap > 0.0 && rz > 0.0) ? rz / pap : 0.0;
-    double rzn = 0.0, rr = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
-        double rn[CD], z[CD];
-#pragma unroll
-        for (int k = 0; k < CD; ++k) {
-            const size_t j = (size_t)CD * i + k;
-            a.x[j] += alpha * a.p[j];
-            rn[k] = a.r[j] - alpha * a.Ap[j];
-            a.r[j] = rn[k];
-        }
-        block_matvec<CD>(a.sinv + (size_t)CD * CD * i, rn, z);
-#pragma unroll
-        for (int k = 0; k < CD; ++k) {
-            a.z[CD * i + k] = z[k];
-            rzn += rn[k] * z[k]; rr += rn[k] * rn[k];
-        }
-    }
-    rzn = block_sum256(rzn, sh);
-    rr = block_sum256(rr, sh);
-    if (threadIdx.x == 0) { a.prz[(it & 1) ^ 1][blockIdx.x] = rzn; a.prr[blockIdx.x] = rr; }
 }
 
 // ---- dense reduced camera system (XM_BA_DENSE_SCHUR): the lower block triangle of
@@ -790,31 +547,6 @@ __global__ __launch_bounds__(256) void ba_sqerr_kernel(SchurLists S, const doubl
             sq = r0 * r0 + r1 * r1;
         }
         sqerr[e] = sq;
-    }
-}
-// scalars of the state word from the partials, in a fixed order (one workgroup): up to 6 sums and one max
-constexpr int kBaSums = 6;
-struct BaReduce {
-    const double *sum_p[kBaSums];
-    int sum_n[kBaSums];
-    double *sum_out[kBaSums];
-    const double *max_p;
-    int max_n;
-    double *max_out;
-};
-__global__ __launch_bounds__(256) void ba_reduce_kernel(BaReduce r) {
-    __shared__ double sh[4];
-    __shared__ double shm[4];
-    for (int k = 0; k < kBaSums; ++k) {
-        if (r.sum_out[k] == nullptr) continue;
-        const double v = sum_partials256(r.sum_p[k], r.sum_n[k], sh);
-        if (threadIdx.x == 0) *r.sum_out[k] = v;
-    }
-    if (r.max_out != nullptr) {
-        double m = 0.0;
-        for (int i = threadIdx.x; i < r.max_n; i += 256) m = fmax(m, r.max_p[i]);
-        m = block_max<256>(m, shm);
-        if (threadIdx.x == 0) *r.max_out = m;
     }
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "xm_ba.h"
+#include "xm_gp.h"
 #include "xm_clean.h"
 #include "xm_trackfilter.h"
 #include "xm_prune.h"
@@ -198,6 +199,24 @@ int solve_path(const char *dataset_path, unsigned max_rank, double tol, double l
     }
     if (status) *status = res.status;
     return XM_OK;
+}
+// what xm_ctx_global_positioning and xm_ctx_gp_probe refuse alike
+void gp_check(const char *who, xm_ctx_t *ctx, int loss, double loss_scale, int min_views, const double *rot, const double *t, const double *p) {
+    const std::string w(who);
+    if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, w + ": single-GPU contexts only (not n_gpus > 1)");
+    if (ctx->impl->world() > 1) throw xm::Error(XM_ERR_ARG, w + ": single-rank contexts only");
+    if (loss < XM_BA_LOSS_TRIVIAL || loss > XM_BA_LOSS_ARCTAN) throw xm::Error(XM_ERR_ARG, w + ": unknown loss");
+    if (loss == XM_BA_LOSS_TRIVIAL && loss_scale != 0.0) throw xm::Error(XM_ERR_ARG, w + ": loss_scale is given but the loss is trivial");
+    if (loss != XM_BA_LOSS_TRIVIAL && !(std::isfinite(loss_scale) && loss_scale > 0.0))
+        throw xm::Error(XM_ERR_ARG, w + ": a robust loss needs a finite loss_scale > 0");
+    if (min_views < 0) throw xm::Error(XM_ERR_ARG, w + ": min_views is negative");
+    const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks();
+    for (int64_t k = 0; k < 9 * n; ++k)
+        if (!std::isfinite(rot[k])) throw xm::Error(XM_ERR_ARG, w + ": rotations are not finite");
+    for (int64_t k = 0; k < 3 * n; ++k)
+        if (!std::isfinite(t[k])) throw xm::Error(XM_ERR_ARG, w + ": centres are not finite");
+    for (int64_t k = 0; k < 3 * m; ++k)
+        if (!std::isfinite(p[k])) throw xm::Error(XM_ERR_ARG, w + ": points are not finite");
 }
 }  // namespace
 
@@ -465,6 +484,77 @@ int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const dou
     pr->cost = q.cost; pr->gmax = q.gmax; pr->cost1 = q.cost1; pr->model = q.model; pr->n_used = q.n_used;
     pr->step2[0] = q.step2[0]; pr->step2[1] = q.step2[1]; pr->x2[0] = q.x2[0]; pr->x2[1] = q.x2[1];
     pr->nagg = q.nagg; pr->ncoarse = q.ncoarse; pr->coarse_ok = q.coarse_ok;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_ctx_global_positioning(xm_ctx_t *ctx, const xm_gp_options_t *opt, const double *rot, double *t, double *p, double *scales, xm_gp_result_t *res) {
+    XM_TRY
+    if (!ctx || !opt || !res || !rot || !t || !p) throw xm::Error(XM_ERR_ARG, "xm_ctx_global_positioning: null argument");
+    if (opt->struct_size != sizeof(xm_gp_options_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_global_positioning: xm_gp_options_t.struct_size is not sizeof(xm_gp_options_t)");
+    if (res->struct_size != sizeof(xm_gp_result_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_global_positioning: xm_gp_result_t.struct_size is not sizeof(xm_gp_result_t)");
+    const xm_gp_options_t &o = *opt;
+    auto bad = [](double v) { return !(v >= 0.0) || !std::isfinite(v); };
+    if (!(o.eta > 0.0 && o.eta < 1.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_global_positioning: eta must lie in (0, 1)");
+    if (o.max_iters < 0 || bad(o.max_time) || bad(o.function_tol) || bad(o.gradient_tol) || bad(o.parameter_tol))
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_global_positioning: negative or non-finite setting");
+    if (o.trace_cap < 0 || (o.trace_cap > 0 && !o.trace)) throw xm::Error(XM_ERR_ARG, "xm_ctx_global_positioning: trace_cap > 0 needs a trace array");
+    gp_check("xm_ctx_global_positioning", ctx, o.loss, o.loss_scale, o.min_views, rot, t, p);
+    xm::GpSettings c;
+    if (o.max_iters > 0) c.max_iters = o.max_iters;
+    if (o.max_time > 0.0) c.max_time = o.max_time;
+    if (o.function_tol > 0.0) c.function_tol = o.function_tol;
+    if (o.gradient_tol > 0.0) c.gradient_tol = o.gradient_tol;
+    if (o.parameter_tol > 0.0) c.parameter_tol = o.parameter_tol;
+    if (o.min_views > 0) c.min_views = o.min_views;
+    c.eta = o.eta;
+    c.loss = o.loss; c.loss_scale = o.loss_scale;
+    c.trace_cap = o.trace_cap; c.trace = o.trace;
+    xm::GpOutcome r;
+    ctx->impl->global_positioning(c, rot, t, p, scales, r);
+    xm_gp_result_t out;
+    std::memset(&out, 0, sizeof(out));
+    out.struct_size = sizeof(xm_gp_result_t);
+    out.status = r.status; out.iters = r.iters; out.accepted = r.accepted; out.pcg_iters = r.pcg_iters; out.n_used = r.n_used;
+    out.initial_cost = r.initial_cost; out.final_cost = r.final_cost; out.gradient_max = r.gradient_max; out.seconds = r.seconds;
+    out.trace_len = r.trace_len;
+    *res = out;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_ctx_gp_probe(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_gp_probe_t *pr) {
+    XM_TRY
+    if (!ctx || !rot || !t || !p || !pr) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe: null argument");
+    if (pr->struct_size != sizeof(xm_gp_probe_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe: xm_gp_probe_t.struct_size is not sizeof(xm_gp_probe_t)");
+    if (!(pr->mu > 0.0) || !std::isfinite(pr->mu)) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe: mu must be finite and > 0");
+    if (pr->k < 0 || (pr->k > 0 && !pr->X)) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe: k > 0 needs X");
+    gp_check("xm_ctx_gp_probe", ctx, pr->loss, pr->loss_scale, pr->min_views, rot, t, p);
+    const int64_t n = ctx->impl->cameras(), nobs = ctx->impl->n_observations();
+    if (pr->s)
+        for (int64_t k = 0; k < nobs; ++k)
+            if (!std::isfinite(pr->s[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe: s is not finite");
+    for (int64_t k = 0; k < 3 * n * pr->k; ++k)
+        if (!std::isfinite(pr->X[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe: X is not finite");
+    if (pr->dc)
+        for (int64_t k = 0; k < 3 * n; ++k)
+            if (!std::isfinite(pr->dc[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe: dc is not finite");
+    xm::GpSettings c;
+    if (pr->min_views > 0) c.min_views = pr->min_views;
+    c.loss = pr->loss; c.loss_scale = pr->loss_scale;
+    xm::GpProbe q;
+    q.mu = pr->mu; q.k = pr->k; q.s = pr->s; q.X = pr->X; q.dc = pr->dc;
+    q.M = pr->M; q.q = pr->q; q.frozen = pr->frozen; q.oused = pr->oused;
+    q.vinv = pr->vinv; q.g_l = pr->g_l; q.ustar = pr->ustar; q.sinv = pr->sinv; q.b = pr->b; q.cused = pr->cused; q.lused = pr->lused;
+    q.SX = pr->SX; q.dP = pr->dP; q.ds = pr->ds; q.t1 = pr->t1; q.p1 = pr->p1; q.s1 = pr->s1;
+    ctx->impl->gp_probe(c, rot, t, p, q);
+    pr->cost = q.cost; pr->gmax = q.gmax; pr->cost1 = q.cost1; pr->model = q.model; pr->n_used = q.n_used;
+    for (int k = 0; k < 3; ++k) { pr->step2[k] = q.step2[k]; pr->x2[k] = q.x2[k]; }
+    return XM_OK;
+    XM_CATCH
+}
+int xm_gp_limits(int64_t out[3]) {
+    XM_TRY
+    if (!out) throw xm::Error(XM_ERR_ARG, "xm_gp_limits: null output");
+    xm::gp_limits(out);
     return XM_OK;
     XM_CATCH
 }

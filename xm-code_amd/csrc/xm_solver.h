@@ -118,6 +118,9 @@ class SchurOp;      // xm_schur.h
 struct BaSettings;  // xm_ba.h
 struct BaOutcome;
 struct BaProbe;
+struct GpSettings;  // xm_gp.h
+struct GpOutcome;
+struct GpProbe;
 struct CleanSettings;  // xm_clean.h
 struct CleanOutcome;
 struct TfSettings;     // xm_trackfilter.h
@@ -166,6 +169,9 @@ public:
     // reprojection bundle adjustment of a recovered solution (xm_ba.h): matrix-free storage, one rank; reads the context, changes nothing in it
     void bundle_adjust(const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out);
     void ba_probe(const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q);   // test export
+    // global positioning from rotations and bearings (xm_gp.h): matrix-free storage, one rank; reads the context, changes nothing in it
+    void global_positioning(const GpSettings &cfg, const double *rot, double *t, double *p, double *scales, GpOutcome &out);
+    void gp_probe(const GpSettings &cfg, const double *rot, const double *t, const double *p, GpProbe &q);   // test export
     void outer_probe(xm_outer_probe_t &q);   // test export (xm_ctx_outer_probe): the retraction and the device-driven step launch stage by stage
     void rtr_probe(xm_rtr_probe_t &q);   // test export (include/xm_amd.h: xm_ctx_rtr_probe): the trust region's kernels stage by stage
     void schur_probe(xm_schur_probe_t &q);   // test export (xm_ctx_schur_probe): the matrix-free Q's factors, chain stages and inner-CG pieces
@@ -187,6 +193,7 @@ public:
     double xm2_filter(const double *rot, const double *scale, double pct, int64_t *removed, double *w_out);
     const std::vector<double> &weights() const { return w_cur_; }
     int64_t n_landmarks() const;
+    int64_t n_observations() const;   // matrix-free storage: observations of the list (0 otherwise)
     void dense_q(double *q, int64_t ldq);   // xm_tuning_t.schur_dense_q: the current dense Q -> host, column-major
     bool schur_info(int64_t out[3], double *relres) const;   // matrix-free storage with the CG form: products, inner iterations, products at the cap
     int schur_precond(int64_t *aggregates, int *block) const; // its preconditioner: -1 no CG form, 0 Jacobi, 1 two-level (aggregates, cameras per aggregate)

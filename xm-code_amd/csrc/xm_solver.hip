@@ -14,6 +14,7 @@
 #include "xm_symw.h"
 #include "xm_schur.h"
 #include "xm_ba.h"
+#include "xm_gp.h"
 #include "xm_clean.h"
 #include "xm_trackfilter.h"
 #include "xm_prune.h"
@@ -2379,6 +2380,22 @@ void Context::ba_probe(const BaSettings &cfg, const double *rot, const double *t
     c.watchdog_s = cfg_.watchdog_s;
     xm::ba_probe(*schur_, c, rot, t, p, q, st_);
 }
+void Context::global_positioning(const GpSettings &cfg, const double *rot, double *t, double *p, double *scales, GpOutcome &out) {
+    if (!schur_)
+        throw Error(XM_ERR_ARG, "xm_ctx_global_positioning: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_global_positioning: single-rank contexts only");
+    GpSettings c = cfg;
+    c.watchdog_s = cfg_.watchdog_s;
+    xm::global_positioning(*schur_, c, rot, t, p, scales, out, st_);
+}
+void Context::gp_probe(const GpSettings &cfg, const double *rot, const double *t, const double *p, GpProbe &q) {
+    if (!schur_)
+        throw Error(XM_ERR_ARG, "xm_ctx_gp_probe: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_gp_probe: single-rank contexts only");
+    GpSettings c = cfg;
+    c.watchdog_s = cfg_.watchdog_s;
+    xm::gp_probe(*schur_, c, rot, t, p, q, st_);
+}
 void Context::schur_probe(xm_schur_probe_t &q) {
     if (!schur_ || schur_dense_)
         throw Error(XM_ERR_ARG, "xm_ctx_schur_probe: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages keep no factors");
@@ -2425,6 +2442,7 @@ void Context::dense_q(double *q, int64_t ldq) {
     XM_HIP_CHECK(hipStreamSynchronize(st_));
 }
 int64_t Context::n_landmarks() const { return schur_ ? schur_->n_landmarks() : 0; }
+int64_t Context::n_observations() const { return schur_ ? schur_->nobs() : 0; }
 bool Context::schur_info(int64_t out[3], double *relres) const {
     if (!schur_ || !schur_->uses_pcg()) return false;
     schur_->pcg_stats(out, relres);

@@ -44,6 +44,7 @@ EXPORTS = [
     "xm_view_graph_filter", "xm_view_graph_limits",
     "xm_ctx_filter_tracks", "xm_track_filter_limits",
     "xm_prune_weakly_connected", "xm_ctx_prune_weakly_connected", "xm_prune_limits",
+    "xm_ctx_global_positioning", "xm_ctx_gp_probe", "xm_gp_limits",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -115,6 +116,28 @@ class BaProbe(C.Structure):   # xm_ba_probe_t, the test export xm_ctx_ba_probe
                 ("nagg", C.c_int32), ("ncoarse", C.c_int32), ("coarse_ok", C.c_int32), ("pad2", C.c_int32)] + \
                [(k, C.c_void_p) for k in ("b", "g_l", "vinv", "ustar", "sinv", "cused", "lused", "SX", "Sdense", "MX", "Pm", "dropped", "Ac",
                                           "dP", "rot1", "t1", "p1")]
+
+
+class GpOptions(C.Structure):   # xm_gp_options_t
+    _fields_ = [("struct_size", C.c_uint32), ("max_iters", C.c_int32), ("max_time", C.c_double), ("eta", C.c_double),
+                ("function_tol", C.c_double), ("gradient_tol", C.c_double), ("parameter_tol", C.c_double), ("min_views", C.c_int32),
+                ("trace_cap", C.c_int32), ("trace", C.c_void_p), ("loss", C.c_int32), ("pad", C.c_int32), ("loss_scale", C.c_double)]
+
+
+class GpResult(C.Structure):   # xm_gp_result_t
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_int32), ("iters", C.c_int32), ("accepted", C.c_int32),
+                ("pcg_iters", C.c_int64), ("n_used", C.c_int64), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("gradient_max", C.c_double), ("seconds", C.c_double), ("trace_len", C.c_int32), ("pad", C.c_int32)]
+
+
+GP_PROBE_OUT = ("M", "q", "frozen", "oused", "vinv", "g_l", "ustar", "sinv", "b", "cused", "lused", "SX", "dP", "ds", "t1", "p1", "s1")
+
+
+class GpProbe(C.Structure):   # xm_gp_probe_t, the test export xm_ctx_gp_probe
+    _fields_ = [("struct_size", C.c_uint32), ("min_views", C.c_int32), ("loss", C.c_int32), ("pad", C.c_int32), ("loss_scale", C.c_double),
+                ("mu", C.c_double), ("k", C.c_int64), ("s", C.c_void_p), ("X", C.c_void_p), ("dc", C.c_void_p), ("cost", C.c_double),
+                ("gmax", C.c_double), ("cost1", C.c_double), ("model", C.c_double), ("step2", C.c_double * 3), ("x2", C.c_double * 3),
+                ("n_used", C.c_int64)] + [(k, C.c_void_p) for k in GP_PROBE_OUT]
 
 
 class RtrScal(C.Structure):    # xm_rtr_scal_t: the truncated CG's scalar block as the test export xm_ctx_rtr_probe passes it
@@ -418,6 +441,9 @@ def lib():
         L.xm_tracks_split_stats.argtypes = [C.c_void_p]
         L.xm_ctx_filter_tracks.argtypes = [C.c_void_p, C.POINTER(TfOptions)] + [C.c_void_p] * 7 + [C.POINTER(TfResult)]
         L.xm_track_filter_limits.argtypes = [C.c_void_p]
+        L.xm_ctx_global_positioning.argtypes = [C.c_void_p, C.POINTER(GpOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GpResult)]
+        L.xm_ctx_gp_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GpProbe)]
+        L.xm_gp_limits.argtypes = [C.c_void_p]
         L.xm_prune_weakly_connected.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PruneOptions), C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.POINTER(PruneResult)]
         L.xm_ctx_prune_weakly_connected.argtypes = [C.c_void_p, C.POINTER(PruneOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PruneResult)]
@@ -844,6 +870,22 @@ class TrackFilterPlan:
                 raise XmError("TrackFilterPlan.apply: a per-observation array has another length than the filtered list")
             out.append(a[k])
         return tuple(out)
+
+
+def gp_limits():
+    """-> dict(light_max: observations of the longest landmark that one thread walks in Context.global_positioning (longer ones get a
+    workgroup), cam_pass: observations a wavefront takes from a camera's list in one pass, threads: of a heavy landmark's workgroup)"""
+    out = np.zeros(3, dtype=np.int64)
+    _chk(lib().xm_gp_limits(out.ctypes.data_as(C.c_void_p)))
+    return dict(light_max=int(out[0]), cam_pass=int(out[1]), threads=int(out[2]))
+
+
+def gp_random_start(n, m, seed=1):
+    """the start of GLOMAP's global positioning: 100 U(-1, 1)^3 for every camera centre (3 x n) and point (3 x m)
+    (global_positioning.cc:141, :235), cameras first, from numpy's default Generator.  DEPARTURE: the reference draws from std::mt19937 in
+    hash-map order, which has no order-independent restatement."""
+    rng = np.random.default_rng(seed)
+    return 100.0 * rng.uniform(-1.0, 1.0, (3, int(n))), 100.0 * rng.uniform(-1.0, 1.0, (3, int(m)))
 
 
 def track_filter_limits():
@@ -1637,6 +1679,76 @@ class Context:
         if tr is not None:
             info["trace"] = tr[: res.trace_len].copy()
         return rot, t, P, info
+
+    def global_positioning(self, rot, t=None, P=None, seed=1, min_views=3, loss="huber", loss_scale=0.1, max_iters=100, max_time=300.0, eta=0.1,
+                           function_tol=1e-5, gradient_tol=1e-10, parameter_tol=1e-8, trace=0):
+        """GLOMAP's global positioning (estimators/global_positioning.cc, ONLY_POINTS; xm_ctx_global_positioning, include/xm_amd.h has the
+        contract): camera centres t (3 x n) and points P (3 x m) from the rotations rot (3 x 3n, R_i camera to world, read only) and the
+        bearings p_e / |p_e| of this context's observations at their CURRENT weights; matrix-free contexts only.  t or P None: both start
+        from gp_random_start(n, m, seed).  -> (t, P, info) with info: status (BA_STATUS), iters, accepted, pcg_iters, n_used, initial_cost,
+        final_cost, gradient_max, seconds, scales (one per observation in input order, -1 = not used) and with trace > 0 "trace" (the rows
+        of bundle_adjust).  The result has a free gauge (origin and scale); bundle_adjust can start from it."""
+        n, m = self.n, self.n_landmarks
+        rot = np.asfortranarray(np.asarray(rot, dtype=np.float64))
+        if t is None or P is None:
+            t, P = gp_random_start(n, m, seed)
+        t = np.array(t, dtype=np.float64, order="F"); P = np.array(P, dtype=np.float64, order="F")
+        assert rot.shape == (3, 3 * n) and t.shape == (3, n) and P.shape == (3, m)
+        if loss not in BA_LOSS:
+            raise XmError(f"unknown loss {loss!r} (one of {', '.join(BA_LOSS)})")
+        opt = GpOptions(); res = GpResult()
+        opt.struct_size, res.struct_size = C.sizeof(GpOptions), C.sizeof(GpResult)
+        opt.max_iters, opt.max_time, opt.eta, opt.min_views = int(max_iters), float(max_time), float(eta), int(min_views)
+        opt.function_tol, opt.gradient_tol, opt.parameter_tol = float(function_tol), float(gradient_tol), float(parameter_tol)
+        opt.loss, opt.loss_scale = BA_LOSS[loss], float(loss_scale)
+        tr = None
+        if trace:
+            tr = np.zeros((int(trace), 6)); opt.trace_cap = int(trace); opt.trace = tr.ctypes.data_as(C.c_void_p)
+        scales = np.zeros(max(self.ne, 1))
+        _chk(lib().xm_ctx_global_positioning(self.h, C.byref(opt), rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                             P.ctypes.data_as(C.c_void_p), scales.ctypes.data_as(C.c_void_p), C.byref(res)))
+        info = {k: getattr(res, k) for k, _ in GpResult._fields_ if k not in ("struct_size", "pad")}
+        info["status_name"] = BA_STATUS.get(res.status, "?")
+        info["scales"] = scales[: self.ne]
+        if tr is not None:
+            info["trace"] = tr[: res.trace_len].copy()
+        return t, P, info
+
+    def gp_probe(self, rot, t, P, mu, s=None, min_views=3, loss="huber", loss_scale=0.1, X=None, dc=None):
+        """one linearisation of global_positioning at (t, P, s) with the damping mu (the test export xm_ctx_gp_probe; include/xm_amd.h): a
+        dict of cost, n_used, gmax, M (nobs x 6), q (nobs x 3), frozen, oused (nobs), vinv (m x 6), g_l (m x 3), ustar, sinv (n x 3 x 3), b
+        (n x 3), cused, lused; with X (3n x k): SX; with dc (3n): dP (m x 3), ds (nobs), t1, p1, s1, cost1, model, step2, x2.  Arrays per
+        observation and per landmark by input index."""
+        n, m, nobs = self.n, self.n_landmarks, self.ne
+        rot = np.asfortranarray(np.asarray(rot, dtype=np.float64)); t = np.asfortranarray(np.asarray(t, dtype=np.float64))
+        P = np.asfortranarray(np.asarray(P, dtype=np.float64))
+        assert rot.shape == (3, 3 * n) and t.shape == (3, n) and P.shape == (3, m)
+        if loss not in BA_LOSS:
+            raise XmError(f"unknown loss {loss!r} (one of {', '.join(BA_LOSS)})")
+        q = GpProbe()
+        q.struct_size = C.sizeof(GpProbe)
+        q.min_views, q.loss, q.loss_scale, q.mu = int(min_views), BA_LOSS[loss], float(loss_scale), float(mu)
+        i32 = lambda k: np.zeros(k, dtype=np.int32)
+        out = dict(M=np.zeros((nobs, 6)), q=np.zeros((nobs, 3)), frozen=i32(nobs), oused=i32(nobs), vinv=np.zeros((m, 6)), g_l=np.zeros((m, 3)),
+                   ustar=np.zeros((n, 3, 3)), sinv=np.zeros((n, 3, 3)), b=np.zeros((n, 3)), cused=i32(n), lused=i32(m))
+        if s is not None:
+            s = np.ascontiguousarray(np.asarray(s, dtype=np.float64).reshape(nobs))
+            q.s = s.ctypes.data_as(C.c_void_p)
+        if X is not None:
+            X = np.asfortranarray(np.asarray(X, dtype=np.float64).reshape(3 * n, -1))
+            q.k, q.X = X.shape[1], X.ctypes.data_as(C.c_void_p)
+            out["SX"] = np.zeros(X.shape, order="F")
+        if dc is not None:
+            dc = np.ascontiguousarray(np.asarray(dc, dtype=np.float64).reshape(3 * n))
+            q.dc = dc.ctypes.data_as(C.c_void_p)
+            out.update(dP=np.zeros((m, 3)), ds=np.zeros(nobs), t1=np.zeros((3, n), order="F"), p1=np.zeros((3, m), order="F"), s1=np.zeros(nobs))
+        for k, v in out.items():
+            setattr(q, k, v.ctypes.data_as(C.c_void_p))
+        _chk(lib().xm_ctx_gp_probe(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p), C.byref(q)))
+        out.update(cost=q.cost, n_used=q.n_used, gmax=q.gmax)
+        if dc is not None:
+            out.update(cost1=q.cost1, model=q.model, step2=np.array(q.step2[:]), x2=np.array(q.x2[:]))
+        return out
 
     def ba_probe(self, rot, t, P, mu, fix_rotations=False, loss="trivial", loss_scale=0.0, preconditioner="jacobi", X=None, dc=None, dense=False):
         """one linearisation of bundle_adjust at (rot, t, P) with the damping mu (the test export xm_ctx_ba_probe; include/xm_amd.h): a dict
