@@ -769,6 +769,123 @@ int xm_view_graph_filter(int64_t n, const int64_t *foff, const double *xy, const
 /* out[0]: most matches of a pair that one workgroup runs (and the chunk of the workspace form above it); out[1]: threads per workgroup;
  * out[2]: most matches of a pair that one wavefront runs; out[3]: most hooking rounds */
 int xm_view_graph_limits(int64_t out[4]);
+/* Focal lengths from the view graph on the device: step 1 of the reference's fork of GLOMAP (controllers/global_mapper.cc:37-46:
+ * ViewGraphCalibrator::Solve, estimators/view_graph_calibration.cc, estimators/cost_function.h:44-222), a robust least-squares fit of one
+ * focal length per camera to the pairs' fundamental matrices (Fetzer's cost, Cauchy loss), the rejection of wild estimates and the
+ * invalidation of the pairs that still disagree; with XM_VGC_UPDATE_CONFIG also step 0 in front of it
+ * (processors/view_graph_manipulation.cc:170-231).  Context-free like xm_view_graph_filter: host arrays in, host arrays out.  Its
+ * focal_out[cam_of_image[.]] and pair_status == XM_VGC_VALID are what xm_view_graph_filter takes as focal and valid_in.
+ *
+ * Cameras: focal0[ncams] the prior (Camera::Focal()), pp[2 ncams] the principal point, has_prior[ncams]: a camera with a prior is held
+ * constant (view_graph_calibration.cc:113-117).  Images: cam_of_image[n].  Pairs: pi, pj (image indices, image_id1 and image_id2),
+ * model[npairs] (XM_VG_MODEL_*), F[9 npairs] row-major (image_pair.F for E and F pairs alike), valid_in[npairs] or NULL, and with
+ * XM_VGC_UPDATE_CONFIG Rrel[9 npairs], trel[3 npairs] (cam2_from_cam1).  Only valid pairs of model E or F take part (:72-79).
+ *
+ * Rules:
+ *   1. Set-up, once per participating pair (cost_function.h:47-122): G = K1^T F K0 with K = [[1,0,px],[0,1,py],[0,0,1]], K0 of image_id1's
+ *      camera and K1 of image_id2's, every entry as (a*b + c*d) + e; the SVD of G with singular values descending (here a one-sided Jacobi
+ *      SVD in f64, at most xm_view_graph_calibrate_limits()[2] sweeps); ai, aj, bi, bj as there; d_01 = fetzer_d(., 1, 0) and d_12 =
+ *      fetzer_d(., 2, 1), eight doubles per pair (d_02 is computed by the reference and never read; it is not stored).  A joint sign flip of
+ *      (u_0, v_0) or of (u_1, v_1) flips all of d_01 and all of d_12 and leaves every residual unchanged: d is defined up to that sign.
+ *   2. Residual at (fi, fj), fi the focal of image_id1's camera (:132-152, :189-212): fi2 = fi*fi, fj2 = fj*fj, di = fj2*d_01[0] + d_01[1],
+ *      dj = fi2*d_12[0] + d_12[2], each replaced by 1e-6 when exactly 0; n0 = fj2*d_01[2] + d_01[3], n1 = fi2*d_12[1] + d_12[3], K0 =
+ *      -(n0/di), K1 = -(n1/dj), r = ((fi2 - K0)/fi2, (fj2 - K1)/fj2).  Every product and sum is rounded on its own (no fused multiply-add),
+ *      so with the same d and focals the residuals and the flags of rule 6 equal the numpy contract's bit for bit.  When both images have
+ *      one camera, fi = fj is one unknown (:89-94, :160-222).  The Jacobian is analytic where Ceres differentiates automatically (a
+ *      departure in rounding only); for a same-camera pair it is the sum of the two partials.
+ *   3. Loss: Ceres's CauchyLoss with scale thres_loss_function and Ceres's corrector, as xm_ctx_bundle_adjust applies XM_BA_LOSS_CAUCHY.
+ *   4. Minimiser: the Levenberg-Marquardt rules of xm_ctx_bundle_adjust (initial radius 1e4, step acceptance above 1e-3, Ceres's radius
+ *      update, the damping mu * clamp(diag(J^T J), 1e-6, 1e32)), function_tolerance as given, gradient tolerance 1e-10 and parameter
+ *      tolerance 1e-8 (Ceres's defaults).  Unknowns: one scalar per camera that takes part and has no prior.
+ *   5. Early return (:32-35): with no free camera the call succeeds and refines nothing and invalidates nothing.
+ *   6. Results (:123-186): a free camera that takes part is rejected when f_est/focal0 > thres_higher_ratio or < thres_lower_ratio:
+ *      focal_out = focal0, refined = 0, XM_VGC_CAM_REJECTED; otherwise focal_out = f_est, refined = 1.  Cameras in no participating pair
+ *      are untouched.  residual[2 npairs] is evaluated without the loss at the OPTIMISED focals, those of rejected cameras included
+ *      (problem_->Evaluate reads focals_, not the cameras); a participating pair becomes XM_VGC_TWO_VIEW_ERROR when r0*r0 + r1*r1 >
+ *      thres_two_view_error * thres_two_view_error.
+ *   7. With XM_VGC_UPDATE_CONFIG, before rule 1: per camera, over the valid pairs whose two cameras both have a prior, total counts E and F
+ *      pairs and calibrated the E pairs; a camera is "valid" when calibrated/total > 0.5; a valid F pair whose two cameras are both valid
+ *      becomes E (model_out) and its F is rewritten (F_out) as K2^-T [t]x R K1^-1 (math/two_view_geometry.cc:41-55): E row 0 = t1*R2. -
+ *      t2*R1., row 1 = t2*R0. - t0*R2., row 2 = t0*R1. - t1*R0.; with a = 1/f, x = -px/f, y = -py/f of each camera (the inverse of a pinhole K
+ *      in closed form, f = focal0), A = K2^-T E: rows a2*E0., a2*E1., (x2*E0. + y2*E1.) + E2.; F columns A.0*a1, A.1*a1, (A.0*x1 + A.1*y1) +
+ *      A.2.  Every operation rounded on its own: exact against the contract.
+ *
+ * Departures from the reference, all listed in DESIGN.md 2.21: a camera has ONE focal length (the reference writes the estimate into both
+ * of FocalLengthIdxs(); a camera with fx != fy is represented by its mean); the normal equations are solved matrix-free by
+ * Jacobi-preconditioned CG on the device (relative residual 1e-12 or xm_view_graph_calibrate_limits()[3] iterations) where Ceres
+ * factorises them; the bound f >= lower_bound is kept by projecting the candidate, without Ceres's line search; the Jacobian is analytic;
+ * the SVD is a one-sided Jacobi SVD.  Nothing here is compared with the reference's compiled code (it needs Ceres, COLMAP, Eigen and
+ * glog): tests/xm_vgcalib_numpy.py restates the C++ line by line and the device is tested against that.
+ *
+ * XM_ERR_ARG, nothing written, everything checked on the host before any device call: an index out of range, pi == pj, an unknown model
+ * or flag, a non-finite F entry of a participating pair, a non-positive or non-finite focal0 or option, thres_lower_ratio >
+ * thres_higher_ratio, XM_VGC_UPDATE_CONFIG without Rrel / trel, a wrong struct_size, a null array where its count is positive, counts >= 2^31.
+ * No floating-point atomic and no atomic at all: two calls give the same bytes. */
+#define XM_VGC_UPDATE_CONFIG 1u         /* flags: rule 7 */
+#define XM_VGC_VALID          0         /* pair_status[]: valid at input and not invalidated (whether or not it took part) */
+#define XM_VGC_INVALID_IN     1
+#define XM_VGC_TWO_VIEW_ERROR 2
+#define XM_VGC_CAM_UNUSED   0           /* cam_status[]: in no participating pair */
+#define XM_VGC_CAM_CONSTANT 1           /* takes part and has a prior (or nothing was optimised: rule 5) */
+#define XM_VGC_CAM_REFINED  2
+#define XM_VGC_CAM_REJECTED 3
+typedef struct {
+    uint32_t struct_size;
+    uint32_t flags;                    /* XM_VGC_UPDATE_CONFIG */
+    double thres_loss_function;        /* 1e-2 (view_graph_calibration.h:21-23) */
+    double thres_lower_ratio;          /* 0.1 */
+    double thres_higher_ratio;         /* 10 */
+    double thres_two_view_error;       /* 2 */
+    int32_t max_num_iterations;        /* 100 (optimization_base.h:21-26) */
+    int32_t reserved;
+    double function_tolerance;         /* 1e-5 */
+    double lower_bound;                /* 1e-3 (view_graph_calibration.cc:113) */
+} xm_vgc_options_t;
+#define XM_VGC_OPTIONS_INIT { (uint32_t)sizeof(xm_vgc_options_t), 0u, 1e-2, 0.1, 10.0, 2.0, 100, 0, 1e-5, 1e-3 }
+typedef struct {
+    uint32_t struct_size;
+    int32_t stop_reason;               /* XM_BA_* (XM_BA_NO_CONVERGENCE when nothing was optimised) */
+    int64_t pairs;                     /* participating pairs */
+    int64_t pairs_same_camera;
+    int64_t cams_free, cams_constant, cams_rejected;
+    int64_t pairs_invalidated;
+    int64_t pairs_flipped;             /* rule 7 */
+    int64_t cams_heavy;                /* free cameras above xm_view_graph_calibrate_limits()[0] incidences */
+    int64_t max_incidences;
+    int64_t pcg_iterations;            /* in total */
+    int32_t iterations, accepted;      /* Levenberg-Marquardt */
+    int32_t trace_len, reserved;       /* entries written to cost_trace: the cost at the start and after every accepted step */
+    double initial_cost, final_cost;
+    double seconds_index;              /* host: lists and upload */
+    double seconds_kernels;
+    double seconds_download;
+} xm_vgc_result_t;
+int xm_view_graph_calibrate(int64_t ncams, const double *focal0, const double *pp, const uint8_t *has_prior, int64_t n,
+                            const int32_t *cam_of_image, int64_t npairs, const int32_t *pi, const int32_t *pj, const int32_t *model,
+                            const double *F, const uint8_t *valid_in /* or NULL */, const double *Rrel /* or NULL */,
+                            const double *trel /* or NULL */, const xm_vgc_options_t *opt, double *focal_out, double *focal_est,
+                            uint8_t *refined, int32_t *cam_status, int32_t *pair_status, double *residual, double *d_out /* 8 per pair or NULL */,
+                            int32_t *model_out /* or NULL */, double *F_out /* or NULL */,
+                            double *cost_trace /* max_num_iterations + 1 or NULL */, xm_vgc_result_t *res);
+/* Test export (like xm_ctx_gp_probe): set-up, evaluation, the camera kernel and one product (J^T J + mu clamp(diag)) x, with the kernels,
+ * grids and arguments of the call, at the caller's focal[ncams] and x[ncams] (entries of cameras that are not free are ignored).  d_in
+ * (8 per pair, or NULL) replaces the set-up's result.  Every output whose pointer is not null is filled: d (8 per pair: d_01, d_12),
+ * residual (2 per pair, without the loss), record (6 per pair, corrector-scaled: r0, r1, dr0/dfi, dr0/dfj, dr1/dfi, dr1/dfj; a
+ * same-camera pair holds the summed partials in entries 2 and 4), cost (one double), gradient, diagonal and product per camera.  Pairs
+ * that take no part and cameras that are not free hold 0. */
+typedef struct {
+    uint32_t struct_size;
+    uint32_t reserved;
+    const double *focal, *x, *d_in;
+    double mu;
+    double *d, *residual, *record, *cost, *gradient, *diagonal, *product;
+} xm_vgc_probe_t;
+int xm_view_graph_calibrate_probe(int64_t ncams, const double *focal0, const double *pp, const uint8_t *has_prior, int64_t n,
+                                  const int32_t *cam_of_image, int64_t npairs, const int32_t *pi, const int32_t *pj, const int32_t *model,
+                                  const double *F, const uint8_t *valid_in, const xm_vgc_options_t *opt, xm_vgc_probe_t *probe);
+/* out[0]: most incidences of a camera that one thread walks (a camera above it gets a workgroup); out[1]: threads per workgroup;
+ * out[2]: most sweeps of the Jacobi SVD; out[3]: most PCG iterations of one solve */
+int xm_view_graph_calibrate_limits(int64_t out[4]);
 /* Translations and landmarks of a solution: the last step of utils/recoversolution.py:recover_XM (lines 77-86,
  * ybar_est = Abar @ sR_real.T; t_est = [0 | first N-1 columns], p_est = the rest) for an XM_STORAGE_SCHUR context.  The reference
  * needs the dense (N-1+M) x 3N matrix Abar.bin that create_matrix writes (creatematrix.py:283-311; 80 GB at Final-13682 with 800 k

@@ -17,6 +17,7 @@
 #include "xm_tracks.h"
 #include "xm_tracks_split.h"
 #include "xm_viewgraph.h"
+#include "xm_vgcalib.h"
 #include "xm_pair.h"
 #include "xm_schur.h"
 #include "xm_sell.h"
@@ -1166,6 +1167,121 @@ int xm_view_graph_limits(int64_t out[4]) {
     XM_TRY
     if (!out) throw xm::Error(XM_ERR_ARG, "xm_view_graph_limits: null output");
     out[0] = xm::kVgGroupMatches; out[1] = xm::kVgThreads; out[2] = xm::kVgWaveMatches; out[3] = xm::kMaxRounds;
+    return XM_OK;
+    XM_CATCH
+}
+namespace {
+// the checks xm_view_graph_calibrate and its probe share: everything on the host, before any device call
+void vgc_check(const std::string &w, const xm::VgcInput &in, const xm_vgc_options_t *opt, xm::VgcSettings &c) {
+    const int64_t lim = (int64_t)1 << 31;
+    const double dmax = 1.7976931348623157e308;
+    if (!opt) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (opt->struct_size != sizeof(xm_vgc_options_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_vgc_options_t.struct_size is not sizeof(xm_vgc_options_t)");
+    if (opt->flags & ~XM_VGC_UPDATE_CONFIG) throw xm::Error(XM_ERR_ARG, w + ": unknown flag");
+    const double v[6] = {opt->thres_loss_function, opt->thres_lower_ratio, opt->thres_higher_ratio, opt->thres_two_view_error, opt->function_tolerance,
+                         opt->lower_bound};
+    const char *name[6] = {"thres_loss_function", "thres_lower_ratio", "thres_higher_ratio", "thres_two_view_error", "function_tolerance", "lower_bound"};
+    for (int x = 0; x < 6; ++x)
+        if (!(v[x] > 0.0) || !(v[x] <= dmax)) throw xm::Error(XM_ERR_ARG, w + ": " + name[x] + " is not positive or not finite");
+    if (opt->max_num_iterations <= 0) throw xm::Error(XM_ERR_ARG, w + ": max_num_iterations is not positive");
+    if (opt->thres_lower_ratio > opt->thres_higher_ratio) throw xm::Error(XM_ERR_ARG, w + ": thres_lower_ratio is above thres_higher_ratio");
+    if (in.ncams < 0 || in.n < 0 || in.npairs < 0) throw xm::Error(XM_ERR_ARG, w + ": negative size");
+    if (in.ncams >= lim || in.n >= lim || in.npairs >= lim) throw xm::Error(XM_ERR_ARG, w + ": cameras, images and pairs must each stay below 2^31");
+    if (in.ncams > 0 && (!in.focal0 || !in.pp || !in.has_prior)) throw xm::Error(XM_ERR_ARG, w + ": null camera arrays");
+    if (in.n > 0 && !in.cam_of_image) throw xm::Error(XM_ERR_ARG, w + ": null cam_of_image");
+    if (in.npairs > 0 && (!in.pi || !in.pj || !in.model || !in.F)) throw xm::Error(XM_ERR_ARG, w + ": null pair arrays");
+    const bool update = (opt->flags & XM_VGC_UPDATE_CONFIG) != 0;
+    if (update && in.npairs > 0 && (!in.Rrel || !in.trel)) throw xm::Error(XM_ERR_ARG, w + ": XM_VGC_UPDATE_CONFIG without Rrel or trel");
+    for (int64_t c = 0; c < in.ncams; ++c) {
+        if (!(in.focal0[c] > 0.0) || !(in.focal0[c] <= dmax)) throw xm::Error(XM_ERR_ARG, w + ": focal0 of camera " + std::to_string(c) + " is not positive or not finite");
+        if (!(std::fabs(in.pp[2 * c]) <= dmax) || !(std::fabs(in.pp[2 * c + 1]) <= dmax))
+            throw xm::Error(XM_ERR_ARG, w + ": the principal point of camera " + std::to_string(c) + " is not finite");
+    }
+    for (int64_t i = 0; i < in.n; ++i)
+        if (in.cam_of_image[i] < 0 || in.cam_of_image[i] >= in.ncams) throw xm::Error(XM_ERR_ARG, w + ": camera index out of range at image " + std::to_string(i));
+    for (int64_t k = 0; k < in.npairs; ++k) {
+        if (in.pi[k] < 0 || in.pi[k] >= in.n || in.pj[k] < 0 || in.pj[k] >= in.n) throw xm::Error(XM_ERR_ARG, w + ": image index out of range at pair " + std::to_string(k));
+        if (in.pi[k] == in.pj[k]) throw xm::Error(XM_ERR_ARG, w + ": pair " + std::to_string(k) + " names one image twice");
+        if (in.model[k] < XM_VG_MODEL_NONE || in.model[k] > XM_VG_MODEL_H) throw xm::Error(XM_ERR_ARG, w + ": unknown model at pair " + std::to_string(k));
+        if ((in.valid_in && !in.valid_in[k]) || (in.model[k] != XM_VG_MODEL_E && in.model[k] != XM_VG_MODEL_F)) continue;
+        for (int e = 0; e < 9; ++e)
+            if (!(std::fabs(in.F[9 * k + e]) <= dmax)) throw xm::Error(XM_ERR_ARG, w + ": F of pair " + std::to_string(k) + " is not finite");
+        if (update)
+            for (int e = 0; e < 12; ++e) {
+                const double x = e < 9 ? in.Rrel[9 * k + e] : in.trel[3 * k + e - 9];
+                if (!(std::fabs(x) <= dmax)) throw xm::Error(XM_ERR_ARG, w + ": Rrel or trel of pair " + std::to_string(k) + " is not finite");
+            }
+    }
+    c.update_config = update;
+    c.loss_scale = opt->thres_loss_function; c.lower_ratio = opt->thres_lower_ratio; c.higher_ratio = opt->thres_higher_ratio;
+    c.two_view_error = opt->thres_two_view_error; c.max_iters = opt->max_num_iterations; c.function_tol = opt->function_tolerance;
+    c.lower_bound = opt->lower_bound;
+    if (const char *e = std::getenv("XM_WATCHDOG_S")) { const double s = std::atof(e); if (s > 0) c.watchdog_s = s; }
+}
+}  // namespace
+int xm_view_graph_calibrate(int64_t ncams, const double *focal0, const double *pp, const uint8_t *has_prior, int64_t n, const int32_t *cam_of_image,
+                            int64_t npairs, const int32_t *pi, const int32_t *pj, const int32_t *model, const double *F, const uint8_t *valid_in,
+                            const double *Rrel, const double *trel, const xm_vgc_options_t *opt, double *focal_out, double *focal_est, uint8_t *refined,
+                            int32_t *cam_status, int32_t *pair_status, double *residual, double *d_out, int32_t *model_out, double *F_out,
+                            double *cost_trace, xm_vgc_result_t *res) {
+    XM_TRY
+    const std::string w("xm_view_graph_calibrate");
+    if (!res) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (res->struct_size != sizeof(xm_vgc_result_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_vgc_result_t.struct_size is not sizeof(xm_vgc_result_t)");
+    xm::VgcInput in;
+    in.ncams = ncams; in.n = n; in.npairs = npairs; in.focal0 = focal0; in.pp = pp; in.has_prior = has_prior; in.cam_of_image = cam_of_image;
+    in.pi = pi; in.pj = pj; in.model = model; in.F = F; in.valid_in = valid_in; in.Rrel = Rrel; in.trel = trel;
+    xm::VgcSettings c;
+    vgc_check(w, in, opt, c);
+    if (ncams > 0 && (!focal_out || !focal_est || !refined || !cam_status)) throw xm::Error(XM_ERR_ARG, w + ": null camera outputs");
+    if (npairs > 0 && (!pair_status || !residual)) throw xm::Error(XM_ERR_ARG, w + ": null pair outputs");
+    xm::VgcOutput o;
+    o.focal_out = focal_out; o.focal_est = focal_est; o.refined = refined; o.cam_status = cam_status; o.pair_status = pair_status;
+    o.residual = residual; o.d_out = d_out; o.model_out = model_out; o.F_out = F_out; o.cost_trace = cost_trace;
+    if (npairs > 0) require_device();
+    xm::VgcOutcome r;
+    xm::view_graph_calibrate_host(in, c, o, r);
+    xm_vgc_result_t out;
+    std::memset(&out, 0, sizeof(out));
+    out.struct_size = sizeof(xm_vgc_result_t);
+    out.stop_reason = r.stop; out.pairs = r.pairs; out.pairs_same_camera = r.pairs_same; out.cams_free = r.cams_free; out.cams_constant = r.cams_constant;
+    out.cams_rejected = r.cams_rejected; out.pairs_invalidated = r.pairs_invalidated; out.pairs_flipped = r.pairs_flipped; out.cams_heavy = r.cams_heavy;
+    out.max_incidences = r.max_incidences; out.pcg_iterations = r.pcg_iters; out.iterations = r.iters; out.accepted = r.accepted;
+    out.trace_len = r.trace_len; out.initial_cost = r.initial_cost; out.final_cost = r.final_cost;
+    out.seconds_index = r.seconds_index; out.seconds_kernels = r.seconds_kernels; out.seconds_download = r.seconds_download;
+    *res = out;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_view_graph_calibrate_probe(int64_t ncams, const double *focal0, const double *pp, const uint8_t *has_prior, int64_t n, const int32_t *cam_of_image,
+                                  int64_t npairs, const int32_t *pi, const int32_t *pj, const int32_t *model, const double *F, const uint8_t *valid_in,
+                                  const xm_vgc_options_t *opt, xm_vgc_probe_t *probe) {
+    XM_TRY
+    const std::string w("xm_view_graph_calibrate_probe");
+    if (!probe) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (probe->struct_size != sizeof(xm_vgc_probe_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_vgc_probe_t.struct_size is not sizeof(xm_vgc_probe_t)");
+    xm::VgcInput in;
+    in.ncams = ncams; in.n = n; in.npairs = npairs; in.focal0 = focal0; in.pp = pp; in.has_prior = has_prior; in.cam_of_image = cam_of_image;
+    in.pi = pi; in.pj = pj; in.model = model; in.F = F; in.valid_in = valid_in;
+    xm::VgcSettings c;
+    vgc_check(w, in, opt, c);
+    if (opt->flags) throw xm::Error(XM_ERR_ARG, w + ": the probe takes no flag");
+    if (ncams > 0 && !probe->focal) throw xm::Error(XM_ERR_ARG, w + ": null focal");
+    if (!(probe->mu >= 0.0) || !(probe->mu <= 1.7976931348623157e308)) throw xm::Error(XM_ERR_ARG, w + ": mu is negative or not finite");
+    for (int64_t i = 0; i < ncams; ++i)
+        if (!(probe->focal[i] > 0.0) || !(probe->focal[i] <= 1.7976931348623157e308)) throw xm::Error(XM_ERR_ARG, w + ": a focal is not positive or not finite");
+    xm::VgcProbe q;
+    q.focal = probe->focal; q.x = probe->x; q.d_in = probe->d_in; q.mu = probe->mu; q.d = probe->d; q.residual = probe->residual; q.record = probe->record;
+    q.cost = probe->cost; q.gradient = probe->gradient; q.diagonal = probe->diagonal; q.product = probe->product;
+    if (npairs > 0) require_device();
+    xm::view_graph_calibrate_probe_host(in, c, q);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_view_graph_calibrate_limits(int64_t out[4]) {
+    XM_TRY
+    if (!out) throw xm::Error(XM_ERR_ARG, "xm_view_graph_calibrate_limits: null output");
+    out[0] = xm::kVgcLightIncidences; out[1] = xm::kVgcThreads; out[2] = xm::kVgcSweeps; out[3] = xm::kVgcMaxPcgIters;
     return XM_OK;
     XM_CATCH
 }

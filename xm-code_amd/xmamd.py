@@ -42,6 +42,7 @@ EXPORTS = [
     "xm_lift_observations", "xm_lift_limits",
     "xm_build_tracks", "xm_tracks_limits", "xm_tracks_split_host", "xm_tracks_split_device", "xm_tracks_split_limits", "xm_tracks_split_stats",
     "xm_view_graph_filter", "xm_view_graph_limits",
+    "xm_view_graph_calibrate", "xm_view_graph_calibrate_probe", "xm_view_graph_calibrate_limits",
     "xm_ctx_filter_tracks", "xm_track_filter_limits",
     "xm_prune_weakly_connected", "xm_ctx_prune_weakly_connected", "xm_prune_limits",
     "xm_ctx_global_positioning", "xm_ctx_gp_probe", "xm_gp_limits",
@@ -346,6 +347,33 @@ class VgResult(C.Structure):       # xm_vg_result_t
                [(k, C.c_double) for k in ("seconds_index", "seconds_kernels", "seconds_download")]
 
 
+class VgcOptions(C.Structure):     # xm_vgc_options_t; the defaults are those of view_graph_calibration.h:21-23 and optimization_base.h:21-26
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("thres_loss_function", C.c_double), ("thres_lower_ratio", C.c_double),
+                ("thres_higher_ratio", C.c_double), ("thres_two_view_error", C.c_double), ("max_num_iterations", C.c_int32), ("reserved", C.c_int32),
+                ("function_tolerance", C.c_double), ("lower_bound", C.c_double)]
+
+    def __init__(self, flags=0, thres_loss_function=1e-2, thres_lower_ratio=0.1, thres_higher_ratio=10.0, thres_two_view_error=2.0,
+                 max_num_iterations=100, function_tolerance=1e-5, lower_bound=1e-3):
+        super().__init__(C.sizeof(VgcOptions), flags, thres_loss_function, thres_lower_ratio, thres_higher_ratio, thres_two_view_error,
+                         max_num_iterations, 0, function_tolerance, lower_bound)
+
+
+class VgcResult(C.Structure):      # xm_vgc_result_t
+    _fields_ = [("struct_size", C.c_uint32), ("stop_reason", C.c_int32)] + \
+               [(k, C.c_int64) for k in ("pairs", "pairs_same_camera", "cams_free", "cams_constant", "cams_rejected", "pairs_invalidated", "pairs_flipped",
+                                         "cams_heavy", "max_incidences", "pcg_iterations")] + \
+               [(k, C.c_int32) for k in ("iterations", "accepted", "trace_len", "reserved")] + \
+               [(k, C.c_double) for k in ("initial_cost", "final_cost", "seconds_index", "seconds_kernels", "seconds_download")]
+
+
+class VgcProbe(C.Structure):       # xm_vgc_probe_t, the test export xm_view_graph_calibrate_probe
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("focal", C.c_void_p), ("x", C.c_void_p), ("d_in", C.c_void_p), ("mu", C.c_double)] + \
+               [(k, C.c_void_p) for k in ("d", "residual", "record", "cost", "gradient", "diagonal", "product")]
+
+
+VGC_UPDATE_CONFIG = 1
+VGC_VALID, VGC_INVALID_IN, VGC_TWO_VIEW_ERROR = 0, 1, 2
+VGC_CAM_UNUSED, VGC_CAM_CONSTANT, VGC_CAM_REFINED, VGC_CAM_REJECTED = 0, 1, 2, 3
 VG_SCORE = 1
 VG_MODEL_NONE, VG_MODEL_E, VG_MODEL_F, VG_MODEL_H = 0, 1, 2, 3
 VG_MODELS = {"none": VG_MODEL_NONE, "E": VG_MODEL_E, "F": VG_MODEL_F, "H": VG_MODEL_H}
@@ -435,6 +463,11 @@ def lib():
         L.xm_view_graph_filter.argtypes = [C.c_int64] + [C.c_void_p] * 5 + [C.c_int64] + [C.c_void_p] * 12 + [C.POINTER(VgOptions)] + [C.c_void_p] * 7 + \
                                           [C.POINTER(VgResult)]
         L.xm_view_graph_limits.argtypes = [C.c_void_p]
+        L.xm_view_graph_calibrate.argtypes = [C.c_int64] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + \
+                                             [C.POINTER(VgcOptions)] + [C.c_void_p] * 10 + [C.POINTER(VgcResult)]
+        L.xm_view_graph_calibrate_probe.argtypes = [C.c_int64] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + \
+                                                   [C.POINTER(VgcOptions), C.POINTER(VgcProbe)]
+        L.xm_view_graph_calibrate_limits.argtypes = [C.c_void_p]
         L.xm_tracks_split_host.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.xm_tracks_split_device.argtypes = L.xm_tracks_split_host.argtypes
         L.xm_tracks_split_limits.argtypes = [C.c_void_p]
@@ -1381,6 +1414,126 @@ def view_graph_filter(foff_or_counts, xy, pi, pj, model, matches, focal=None, Ki
     k = int(mo[-1])
     info = {f: getattr(res, f) for f, _ in VgResult._fields_ if f != "struct_size"}
     return ViewGraphPlan(inlier, pinl, pst, regout, (mo, o1[:k].copy(), o2[:k].copy()), info, pi, pj, Rrel)
+
+
+class CalibrationPlan:
+    """what view_graph_calibrate returns: per camera focal (focal_out), focal_est (the raw estimate), refined (uint8), cam_status
+    (VGC_CAM_*); per pair pair_status (VGC_VALID, VGC_INVALID_IN or VGC_TWO_VIEW_ERROR), valid (pair_status == VGC_VALID: the valid_in of
+    view_graph_filter), residual (pairs x 2, without the loss, at the optimised focals), d (pairs x 8) when asked for, model and F (as given,
+    or as rule 7 left them with update_config), cost_trace, info (the fields of xm_vgc_result_t)"""
+
+    def __init__(self, focal, focal_est, refined, cam_status, pair_status, residual, d, model, F, cost_trace, info, pp, cam_of_image):
+        self.focal, self.focal_est, self.refined, self.cam_status, self.pair_status = focal, focal_est, refined, cam_status, pair_status
+        self.residual, self.d, self.model, self.F, self.cost_trace, self.info = residual, d, model, F, cost_trace, info
+        self.valid = (pair_status == VGC_VALID).astype(np.uint8)
+        self._pp, self._cam = pp, cam_of_image
+
+    def focal_per_image(self):
+        """-> focal_out[cam_of_image]: the focal of view_graph_filter"""
+        return self.focal[self._cam]
+
+    def Kinv(self):
+        """-> images x 3 x 3: the inverse of [[f, 0, px], [0, f, py], [0, 0, 1]] per image, the Kinv of view_graph_filter"""
+        f = self.focal[self._cam]
+        K = np.zeros((self._cam.size, 3, 3))
+        K[:, 0, 0] = 1.0 / f; K[:, 1, 1] = 1.0 / f; K[:, 2, 2] = 1.0
+        K[:, 0, 2] = -self._pp[self._cam, 0] / f; K[:, 1, 2] = -self._pp[self._cam, 1] / f
+        return K
+
+
+def view_graph_calibrate_limits():
+    """-> dict(light_incidences: most incidences of a camera that one thread walks (a camera above it gets a workgroup), threads: per
+    workgroup, svd_sweeps: most sweeps of the Jacobi SVD, pcg_iterations: most PCG iterations of one solve)"""
+    out = np.zeros(4, dtype=np.int64)
+    _chk(lib().xm_view_graph_calibrate_limits(out.ctypes.data_as(C.c_void_p)))
+    return dict(light_incidences=int(out[0]), threads=int(out[1]), svd_sweeps=int(out[2]), pcg_iterations=int(out[3]))
+
+
+def _vgc_inputs(what, focal0, pp, has_prior, cam_of_image, pi, pj, model, F, valid_in):
+    focal0 = np.ascontiguousarray(focal0, dtype=np.float64).reshape(-1)
+    ncams = focal0.size
+    pp = np.ascontiguousarray(pp, dtype=np.float64)
+    if pp.size != 2 * ncams:
+        raise XmError(f"{what}: pp must be cameras x 2")
+    pp = pp.reshape(ncams, 2)
+    has_prior = np.ascontiguousarray(np.asarray(has_prior) != 0, dtype=np.uint8).reshape(-1)
+    if has_prior.size != ncams:
+        raise XmError(f"{what}: has_prior must have one entry per camera")
+    cam = np.ascontiguousarray(cam_of_image, dtype=np.int32).reshape(-1)
+    pi = np.ascontiguousarray(pi, dtype=np.int32).reshape(-1); pj = np.ascontiguousarray(pj, dtype=np.int32).reshape(-1)
+    if pi.size != pj.size:
+        raise XmError(f"{what}: pi and pj must have one entry per pair")
+    npairs = pi.size
+    try:
+        model = np.ascontiguousarray([VG_MODELS.get(v, v) if isinstance(v, str) else v for v in np.asarray(model).reshape(-1).tolist()], dtype=np.int32)
+    except (TypeError, ValueError):
+        raise XmError(f"{what}: model must hold VG_MODEL_* numbers or the names {sorted(VG_MODELS)}") from None
+    if model.size != npairs:
+        raise XmError(f"{what}: model must have one entry per pair")
+    F = np.ascontiguousarray(F, dtype=np.float64)
+    if F.size != 9 * npairs:
+        raise XmError(f"{what}: F must be pairs x 3 x 3")
+    F = F.reshape(npairs, 3, 3)
+    if valid_in is not None:
+        valid_in = np.ascontiguousarray(np.asarray(valid_in) != 0, dtype=np.uint8).reshape(-1)
+        if valid_in.size != npairs:
+            raise XmError(f"{what}: valid_in must have one entry per pair")
+    return focal0, pp, has_prior, cam, pi, pj, model, F, valid_in
+
+
+def view_graph_calibrate(focal0, pp, has_prior, cam_of_image, pi, pj, model, F, valid_in=None, Rrel=None, trel=None, update_config=False,
+                         thres_loss_function=1e-2, thres_lower_ratio=0.1, thres_higher_ratio=10.0, thres_two_view_error=2.0, max_num_iterations=100,
+                         function_tolerance=1e-5, lower_bound=1e-3, want_d=False):
+    """focal lengths from the view graph on the device (xm_view_graph_calibrate; include/xm_amd.h has the rules and the lines of the reference's
+    fork of GLOMAP they stand for): focal0, has_prior per camera, pp cameras x 2; cam_of_image per image; pi, pj, model ("E" / "F" / ... or
+    VG_MODEL_*), F (pairs x 3 x 3) per pair; valid_in per pair or None; Rrel (pairs x 3 x 3), trel (pairs x 3) with update_config.
+    -> CalibrationPlan"""
+    w = "view_graph_calibrate"
+    focal0, pp, has_prior, cam, pi, pj, model, F, valid_in = _vgc_inputs(w, focal0, pp, has_prior, cam_of_image, pi, pj, model, F, valid_in)
+    ncams, n, npairs = focal0.size, cam.size, pi.size
+    Rrel = None if Rrel is None else np.ascontiguousarray(Rrel, dtype=np.float64)
+    trel = None if trel is None else np.ascontiguousarray(trel, dtype=np.float64)
+    if (Rrel is not None and Rrel.size != 9 * npairs) or (trel is not None and trel.size != 3 * npairs):
+        raise XmError(f"{w}: Rrel must be pairs x 3 x 3 and trel pairs x 3")
+    opt = VgcOptions(VGC_UPDATE_CONFIG if update_config else 0, float(thres_loss_function), float(thres_lower_ratio), float(thres_higher_ratio),
+                     float(thres_two_view_error), int(max_num_iterations), float(function_tolerance), float(lower_bound))
+    res = VgcResult(); res.struct_size = C.sizeof(VgcResult)
+    fo = np.zeros(ncams); fe = np.zeros(ncams); refined = np.zeros(ncams, dtype=np.uint8); cst = np.zeros(ncams, dtype=np.int32)
+    pst = np.zeros(npairs, dtype=np.int32); resid = np.zeros((npairs, 2)); d = np.zeros((npairs, 8)) if want_d else None
+    mo = np.zeros(npairs, dtype=np.int32); Fo = np.zeros((npairs, 3, 3)); trace = np.zeros(max(int(max_num_iterations), 0) + 1)
+    P = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    _chk(lib().xm_view_graph_calibrate(ncams, P(focal0), P(pp), P(has_prior), n, P(cam), npairs, P(pi), P(pj), P(model), P(F), P(valid_in), P(Rrel), P(trel),
+                                       C.byref(opt), P(fo), P(fe), P(refined), P(cst), P(pst), P(resid), P(d), P(mo), P(Fo), P(trace), C.byref(res)))
+    info = {f: getattr(res, f) for f, _ in VgcResult._fields_ if f not in ("struct_size", "reserved")}
+    info["stop"] = BA_STATUS.get(res.stop_reason, str(res.stop_reason))
+    return CalibrationPlan(fo, fe, refined, cst, pst, resid, d, mo, Fo, trace[:res.trace_len].copy(), info, pp, cam)
+
+
+def view_graph_calibrate_probe(focal0, pp, has_prior, cam_of_image, pi, pj, model, F, focal, x=None, mu=0.0, d_in=None, valid_in=None,
+                               thres_loss_function=1e-2):
+    """the test export xm_view_graph_calibrate_probe: set-up (or d_in, pairs x 8), evaluation, the camera kernel and one product at the focals
+    `focal` (per camera) and the vector x (per camera) -> dict(d, residual, record, cost, gradient, diagonal, product)"""
+    w = "view_graph_calibrate_probe"
+    focal0, pp, has_prior, cam, pi, pj, model, F, valid_in = _vgc_inputs(w, focal0, pp, has_prior, cam_of_image, pi, pj, model, F, valid_in)
+    ncams, n, npairs = focal0.size, cam.size, pi.size
+    focal = np.ascontiguousarray(focal, dtype=np.float64).reshape(-1)
+    x = np.zeros(ncams) if x is None else np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    if focal.size != ncams or x.size != ncams:
+        raise XmError(f"{w}: focal and x must have one entry per camera")
+    if d_in is not None:
+        d_in = np.ascontiguousarray(d_in, dtype=np.float64)
+        if d_in.size != 8 * npairs:
+            raise XmError(f"{w}: d_in must be pairs x 8")
+    opt = VgcOptions(0, float(thres_loss_function))
+    out = dict(d=np.zeros((npairs, 8)), residual=np.zeros((npairs, 2)), record=np.zeros((npairs, 6)), cost=np.zeros(1), gradient=np.zeros(ncams),
+               diagonal=np.zeros(ncams), product=np.zeros(ncams))
+    P = lambda a: None if a is None else a.ctypes.data
+    q = VgcProbe(C.sizeof(VgcProbe), 0, P(focal), P(x), P(d_in), float(mu), *[P(out[k]) for k in ("d", "residual", "record", "cost", "gradient", "diagonal", "product")])
+    V = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    _chk(lib().xm_view_graph_calibrate_probe(ncams, V(focal0), V(pp), V(has_prior), n, V(cam), npairs, V(pi), V(pj), V(model), V(F), V(valid_in),
+                                             C.byref(opt), C.byref(q)))
+    out["cost"] = float(out["cost"][0])
+    return out
 
 
 def symw_plan(ntot, nloc, cam0, K=0):
