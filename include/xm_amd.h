@@ -1206,6 +1206,45 @@ int xm_spd_inverse(int64_t n, double *A);
  * triangle is read), by the Cholesky factorisation and the two triangular substitutions of the dense Schur solver of xm_ctx_bundle_adjust
  * (xm_dense_la.hip).  XM_ERR_ARG: n outside [1, 46000], k < 1, null arrays, a pivot that is not positive or a non-finite solution. */
 int xm_spd_solve(int64_t n, int64_t k, const double *A, double *B);
+/* Test export (the xm_ctx_*_probe pattern, without a context): ONE host function of xm-code_amd/csrc/xm_dense_la.hip on host arrays.  The
+ * arrays named for the operation are uploaded whole (padding between the rows and the leading dimension included), the function runs on
+ * the null stream, the device is synchronised, and the in/out arrays come back whole -- what was not to be touched can be looked at.
+ * Column-major unless stated.  info goes up with the caller's value and comes back (the kernels set it and never clear it).
+ *
+ *   op                       calls                    arrays
+ *   XM_LA_GEMM_SUB           gemm_sub_device          C (ldc x n; in/out) -= op(A) op(B): op(A) m x k, op(B) k x n; A: lda x k (ta = 0) or lda x m
+ *                                                     (ta = 1); B: ldb x n (tb = 0) or ldb x k (tb = 1); lower_only: the 64 x 64 tiles on and below
+ *                                                     the diagonal only, the diagonal tiles whole
+ *   XM_LA_CHOLESKY           spd_cholesky_device      A (lda x n; in/out): lower triangle read -> the factor L; zeros above the diagonal inside the
+ *                                                     64 x 64 diagonal blocks, the other upper blocks untouched; info
+ *   XM_LA_SUBSTITUTE         spd_substitute_device    A = L (lda x n; in), C = X (ldc x nrhs; in/out) <- (L L^T)^-1 X; info
+ *   XM_LA_INVERSE            spd_inverse_device       A (n x n, lda = n; in/out) -> the factor; C = X (n x n, ldc = n; in/out) <- the LOWER
+ *                                                     triangle of A^-1, scratch above the diagonal; info <- 0 when it returned true, 1 when it
+ *                                                     refused (X then comes back as it went up)
+ *   XM_LA_LAYOUT             spd_inverse_layout       A = X (n x n, lda = n; in), C = dst (ROW-major, n rows of ldc; in/out)
+ *   XM_LA_RANK1_SUB          rank1_sub_device         A (n x n, lda = n; in/out) -= q u u^T, B = u (n; in)
+ *
+ * Fields an operation does not name are ignored.  XM_ERR_ARG, nothing written: a struct_size that is not sizeof, an unknown op, a null
+ * array the operation names, m, n, k or nrhs outside [1, XM_LA_PROBE_MAX_N], ta, tb or lower_only outside {0, 1}, a leading dimension below
+ * the rows it spans or above 2 XM_LA_PROBE_MAX_N, lda or ldc other than n where the table says so. */
+#define XM_LA_PROBE_MAX_N 4096
+#define XM_LA_GEMM_SUB 0
+#define XM_LA_CHOLESKY 1
+#define XM_LA_SUBSTITUTE 2
+#define XM_LA_INVERSE 3
+#define XM_LA_LAYOUT 4
+#define XM_LA_RANK1_SUB 5
+typedef struct {
+    uint32_t struct_size;
+    int32_t op;
+    int32_t m, n, k, nrhs;
+    int32_t ta, tb, lower_only;
+    int32_t info;              /* in/out */
+    int64_t lda, ldb, ldc;
+    double q;
+    double *A, *B, *C;
+} xm_la_probe_t;
+int xm_la_probe(xm_la_probe_t *probe);
 
 /* Work decomposition of the half-traffic symmetric dense product (xm_qw_dense_sym, vertical sweep) for n cameras, host-only (CPU
  * test of the index arithmetic, tests/test_symv_layout.py): plan = { K steps (of two cameras) per chunk, Kf for the strip groups

@@ -1475,6 +1475,84 @@ int xm_spd_solve(int64_t n, int64_t k, const double *A, double *B) {
     XM_CATCH
 }
 
+// Test export: one host function of xm_dense_la.hip on host arrays (include/xm_amd.h); everything is checked before the first device call
+int xm_la_probe(xm_la_probe_t *probe) {
+    XM_TRY
+    const std::string w("xm_la_probe");
+    if (!probe) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (probe->struct_size != sizeof(xm_la_probe_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_la_probe_t.struct_size is not sizeof(xm_la_probe_t)");
+    const xm_la_probe_t p = *probe;
+    const int64_t cap = XM_LA_PROBE_MAX_N;
+    auto dim = [&](int64_t v, const char *what) { if (v < 1 || v > cap) throw xm::Error(XM_ERR_ARG, w + ": " + what + " outside [1, XM_LA_PROBE_MAX_N]"); };
+    auto ld = [&](int64_t v, int64_t rows, const char *what) { if (v < rows || v > 2 * cap) throw xm::Error(XM_ERR_ARG, w + ": " + what + " below the rows or above 2 XM_LA_PROBE_MAX_N"); };
+    auto same = [&](int64_t v, const char *what) { if (v != p.n) throw xm::Error(XM_ERR_ARG, w + ": " + what + " must be n for this operation"); };
+    auto arr = [&](const double *a, const char *what) { if (!a) throw xm::Error(XM_ERR_ARG, w + ": null " + what); };
+    size_t na = 0, nb = 0, nc = 0;   // doubles of A, B, C that travel
+    bool a_back = false, c_back = false;
+    dim(p.n, "n");
+    switch (p.op) {
+    case XM_LA_GEMM_SUB:
+        dim(p.m, "m"); dim(p.k, "k");
+        if ((p.ta | p.tb | p.lower_only) & ~1) throw xm::Error(XM_ERR_ARG, w + ": ta, tb and lower_only are 0 or 1");
+        ld(p.lda, p.ta ? p.k : p.m, "lda"); ld(p.ldb, p.tb ? p.n : p.k, "ldb"); ld(p.ldc, p.m, "ldc");
+        arr(p.A, "A"); arr(p.B, "B"); arr(p.C, "C");
+        na = (size_t)p.lda * (p.ta ? p.m : p.k); nb = (size_t)p.ldb * (p.tb ? p.k : p.n); nc = (size_t)p.ldc * p.n; c_back = true;
+        break;
+    case XM_LA_CHOLESKY:
+        ld(p.lda, p.n, "lda"); arr(p.A, "A");
+        na = (size_t)p.lda * p.n; a_back = true;
+        break;
+    case XM_LA_SUBSTITUTE:
+        dim(p.nrhs, "nrhs"); ld(p.lda, p.n, "lda"); ld(p.ldc, p.n, "ldc"); arr(p.A, "A"); arr(p.C, "C");
+        na = (size_t)p.lda * p.n; nc = (size_t)p.ldc * p.nrhs; c_back = true;
+        break;
+    case XM_LA_INVERSE:
+        same(p.lda, "lda"); same(p.ldc, "ldc"); arr(p.A, "A"); arr(p.C, "C");
+        na = nc = (size_t)p.n * p.n; a_back = c_back = true;
+        break;
+    case XM_LA_LAYOUT:
+        same(p.lda, "lda"); ld(p.ldc, p.n, "ldc"); arr(p.A, "A"); arr(p.C, "C");
+        na = (size_t)p.n * p.n; nc = (size_t)p.ldc * p.n; c_back = true;
+        break;
+    case XM_LA_RANK1_SUB:
+        same(p.lda, "lda"); arr(p.A, "A"); arr(p.B, "B");
+        na = (size_t)p.n * p.n; nb = (size_t)p.n; a_back = true;
+        break;
+    default:
+        throw xm::Error(XM_ERR_ARG, w + ": unknown op");
+    }
+    require_device();
+    xm::DevBuf<double> a, b, c, y;
+    xm::DevBuf<int> info;
+    info.alloc(1);
+    if (na) { a.alloc(na, false); XM_HIP_CHECK(hipMemcpy(a.p, p.A, na * sizeof(double), hipMemcpyHostToDevice)); }
+    if (nb) { b.alloc(nb, false); XM_HIP_CHECK(hipMemcpy(b.p, p.B, nb * sizeof(double), hipMemcpyHostToDevice)); }
+    if (nc) { c.alloc(nc, false); XM_HIP_CHECK(hipMemcpy(c.p, p.C, nc * sizeof(double), hipMemcpyHostToDevice)); }
+    XM_HIP_CHECK(hipMemcpy(info.p, &p.info, sizeof(int), hipMemcpyHostToDevice));
+    int h = p.info;
+    bool info_back = false;
+    switch (p.op) {
+    case XM_LA_GEMM_SUB: xm::gemm_sub_device(p.m, p.n, p.k, a.p, p.lda, p.ta, b.p, p.ldb, p.tb, c.p, p.ldc, p.lower_only, nullptr); break;
+    case XM_LA_CHOLESKY: xm::spd_cholesky_device(p.n, a.p, p.lda, info.p, nullptr); xm::check_launch("la_probe(cholesky)"); info_back = true; break;
+    case XM_LA_SUBSTITUTE:
+        y.alloc(nc);
+        xm::spd_substitute_device(p.n, a.p, p.lda, c.p, y.p, p.ldc, p.nrhs, info.p, nullptr);
+        xm::check_launch("la_probe(substitute)");
+        info_back = true;
+        break;
+    case XM_LA_INVERSE: h = xm::spd_inverse_device(p.n, a.p, c.p, nullptr) ? 0 : 1; break;
+    case XM_LA_LAYOUT: xm::spd_inverse_layout(p.n, a.p, c.p, p.ldc, nullptr); break;
+    case XM_LA_RANK1_SUB: xm::rank1_sub_device(p.n, a.p, b.p, p.q, nullptr); break;
+    }
+    XM_HIP_CHECK(hipDeviceSynchronize());
+    if (info_back) XM_HIP_CHECK(hipMemcpy(&h, info.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (a_back) XM_HIP_CHECK(hipMemcpy(p.A, a.p, na * sizeof(double), hipMemcpyDeviceToHost));
+    if (c_back) XM_HIP_CHECK(hipMemcpy(p.C, c.p, nc * sizeof(double), hipMemcpyDeviceToHost));
+    probe->info = h;
+    return XM_OK;
+    XM_CATCH
+}
+
 int xm_symv_plan(int64_t n, int32_t plan[4]) {
     XM_TRY
     if (n < 1 || !plan) throw xm::Error(XM_ERR_ARG, "bad argument");

@@ -35,7 +35,7 @@ EXPORTS = [
     "xm_ctx_attach_edges", "xm_ctx_edge_residuals", "xm_ctx_edge_residuals_recovered", "xm_ctx_xm2_filter", "xm_ctx_xm2_round", "xm_ctx_set_edge_weights", "xm_ctx_recover_tp", "xm_ctx_schur_info", "xm_ctx_qw", "xm_spd_inverse", "xm_ctx_transport", "xm_ctx_sell_wpad", "xm_ctx_product_kind", "xm_symw_plan", "xm_symw_use",
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
-    "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_ba_aggregate_plan", "xm_ctx_ba_probe",
+    "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_la_probe", "xm_ba_aggregate_plan", "xm_ctx_ba_probe",
     "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe", "xm_ctx_outer_probe", "xm_ctx_cert_probe", "xm_tridiag_min", "xm_ctx_schur_probe",
     "xm_ctx_dense_q", "xm_create_matrix", "xm_schur_dense_limits",
     "xm_pair_filter", "xm_pair_filter_limits",
@@ -371,6 +371,13 @@ class VgcProbe(C.Structure):       # xm_vgc_probe_t, the test export xm_view_gra
                [(k, C.c_void_p) for k in ("d", "residual", "record", "cost", "gradient", "diagonal", "product")]
 
 
+class LaProbe(C.Structure):        # xm_la_probe_t, the test export xm_la_probe
+    _fields_ = [("struct_size", C.c_uint32)] + [(k, C.c_int32) for k in ("op", "m", "n", "k", "nrhs", "ta", "tb", "lower_only", "info")] + \
+               [(k, C.c_int64) for k in ("lda", "ldb", "ldc")] + [("q", C.c_double)] + [(k, C.c_void_p) for k in ("A", "B", "C")]
+
+
+LA_PROBE_MAX_N = 4096
+LA_OPS = {"gemm_sub": 0, "cholesky": 1, "substitute": 2, "inverse": 3, "layout": 4, "rank1_sub": 5}
 VGC_UPDATE_CONFIG = 1
 VGC_VALID, VGC_INVALID_IN, VGC_TWO_VIEW_ERROR = 0, 1, 2
 VGC_CAM_UNUSED, VGC_CAM_CONSTANT, VGC_CAM_REFINED, VGC_CAM_REJECTED = 0, 1, 2, 3
@@ -433,6 +440,7 @@ def lib():
         L.xm_ctx_destroy.restype = None
         L.xm_spd_inverse.argtypes = [C.c_int64, C.c_void_p]
         L.xm_spd_solve.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+        L.xm_la_probe.argtypes = [C.POINTER(LaProbe)]
         L.xm_ctx_qw.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double]
         L.xm_ctx_attach_edges.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_edge_residuals.argtypes = [C.c_void_p, C.c_void_p]
@@ -751,6 +759,22 @@ def spd_solve(A, B):
     assert A.ndim == 2 and A.shape[0] == A.shape[1] == X.shape[0]
     _chk(lib().xm_spd_solve(A.shape[0], X.shape[1], A.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p)))
     return X[:, 0].copy() if vec else np.ascontiguousarray(X)
+
+
+def la_probe(op, a=None, b=None, c=None, m=0, n=0, k=0, nrhs=0, ta=0, tb=0, lower_only=0, info=0, lda=0, ldb=0, ldc=0, q=0.0):
+    """one host function of xm_dense_la.hip on host arrays (the test export xm_la_probe, include/xm_amd.h): op is a key of LA_OPS; a, b, c (the
+    struct's A, B, C) are contiguous float64 arrays holding the buffers exactly as the device sees them (leading dimensions and padding included), the
+    in/out ones are overwritten in place.  Returns info."""
+    if op not in LA_OPS:
+        raise XmError(f"la_probe: unknown op {op!r}")
+    for x in (a, b, c):
+        if x is not None and not (isinstance(x, np.ndarray) and x.dtype == np.float64 and (x.flags.c_contiguous or x.flags.f_contiguous) and x.flags.writeable):
+            raise XmError("la_probe: the arrays are contiguous writable float64 numpy arrays")
+    ptr = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
+    p = LaProbe(struct_size=C.sizeof(LaProbe), op=LA_OPS[op], m=m, n=n, k=k, nrhs=nrhs, ta=ta, tb=tb, lower_only=lower_only, info=info, lda=lda,
+                ldb=ldb, ldc=ldc, q=q, A=ptr(a), B=ptr(b), C=ptr(c))
+    _chk(lib().xm_la_probe(C.byref(p)))
+    return int(p.info)
 
 
 def quat_roundtrip(block):
