@@ -886,6 +886,109 @@ int xm_view_graph_calibrate_probe(int64_t ncams, const double *focal0, const dou
 /* out[0]: most incidences of a camera that one thread walks (a camera above it gets a workgroup); out[1]: threads per workgroup;
  * out[2]: most sweeps of the Jacobi SVD; out[3]: most PCG iterations of one solve */
 int xm_view_graph_calibrate_limits(int64_t out[4]);
+/* Robust rotation averaging over the view graph on the device: the IRLS stage of step 3 of the reference's fork of GLOMAP
+ * (controllers/global_mapper.cc:76-111: RotationEstimator::EstimateRotations, estimators/global_rotation_averaging.cc, math/rigid3d.cc
+ * :41-71) with the reference's own options skip_initialization = true and max_num_l1_iterations = 0: iteratively re-weighted least squares
+ * on the tangent space from rotations the caller supplies (those of a view-graph solve), so that a pair with a wrong relative rotation
+ * ends with a vanishing weight before xm_view_graph_filter's rotation test.  Context-free like xm_view_graph_filter and in its
+ * conventions, so nothing is transposed between the calls: registered[n] or NULL (all), rot0[9n] cam_from_world row-major (the start),
+ * pi, pj (image_id1, image_id2), Rrel[9 npairs] cam2_from_cam1 row-major, valid_in[npairs] or NULL.
+ *
+ * Rules (lines of global_rotation_averaging.cc unless a file is named):
+ *   1. Participation: a pair takes part when it is valid and both ends are registered (:163-164).  The fixed camera is fixed_image; with
+ *      -1 the smallest registered index (a departure: :150-156 takes the first entry in hash order).
+ *   2. State: one angle-axis vector per registered image (rotation_estimated_), Log of rot0 by rule 4, kept as angle-axis across the
+ *      iterations as the reference does (:143-144, :425-430).
+ *   3. AngleAxisToRotation (rigid3d.cc:53-71): n = sqrt((a0*a0 + a1*a1) + a2*a2).  Above n = 1e-12, Eigen's AngleAxis(n, a/n)
+ *      .toRotationMatrix(): u = a/n, s = sin n, c = cos n, su = s*u, cu = (1 - c)*u; R01 = cu0*u1 - su2, R10 = cu0*u1 + su2, R02 = cu0*u2 +
+ *      su1, R20 = cu0*u2 - su1, R12 = cu1*u2 - su0, R21 = cu1*u2 + su0, Rkk = cuk*uk + c.  At or below 1e-12 the first-order matrix of
+ *      :59-69, [[1, -a2, a1], [a2, 1, -a0], [-a1, a0, 1]], which is not orthogonal, on purpose.
+ *   4. RotationToAngleAxis (rigid3d.cc:47-51) is Eigen's AngleAxis(Matrix3d), which the reference does not contain; in full: matrix ->
+ *      quaternion by the four-branch rule: t = (R00 + R11) + R22; when t > 0: t' = sqrt(t + 1), w = t'/2, f = 0.5/t', vec = ((R21 - R12) f,
+ *      (R02 - R20) f, (R10 - R01) f); otherwise i the index of the largest diagonal entry (i = 1 when R11 > R00, then i = 2 when R22 > Rii),
+ *      j = (i+1)%3, k = (j+1)%3: t' = sqrt(((Rii - Rjj) - Rkk) + 1), vec_i = t'/2, f = 0.5/t', w = (Rkj - Rjk) f, vec_j = (Rji + Rij) f,
+ *      vec_k = (Rki + Rik) f.  Then nrm = |vec|, angle = 2 atan2(nrm, |w|), the axis is vec/nrm with nrm negated when w < 0, the result
+ *      angle * axis, and the zero vector when nrm == 0.
+ *   5. Residual (:453-469): r_e = -Log(R_2^T (Rrel_e R_1)), R_1 of image_id1; every entry of a 3x3 product as (p0 + p1) + p2.
+ *   6. Gauge residual (:478-482): Log(Exp(fixed0)^T R_fixed), fixed0 the fixed camera's state at the start.
+ *   7. Weights (:362-393): e2 = (r0*r0 + r1*r1) + r2*r2; XM_VGR_GEMAN_MCCLURE: w = s2/((e2 + s2)*(e2 + s2)) with s2 the square of sigma in
+ *      radians (sigma * pi / 180, rigid3d.cc:37); XM_VGR_HALF_NORM: w = pow(e2, -0.75).  The three gauge rows have weight 1.  A weight that
+ *      is not finite ends the call with XM_VGR_STOP_NONFINITE and the rotations, residuals and weights of the last completed iteration
+ *      (weights 0 when there is none); a departure: the reference tests for NaN only and an infinite weight would poison its system.
+ *   8. Linear system (:396-402): without gravity A^T W A = (L_w + e_f e_f^T) (x) I_3, L_w the weighted Laplacian of the participating
+ *      pairs; the right-hand side at camera i is the sum of +w r over the pairs where i is image_id2, of -w r where it is image_id1 (a
+ *      camera's pairs in input order), plus the gauge residual at the fixed camera.  It is solved matrix-free as ONE system of
+ *      3 * registered unknowns by conjugate gradients preconditioned with the diagonal (weighted degree, + 1 at the fixed camera), from
+ *      zero to a relative residual of 1e-12 or xm_view_graph_rotations_limits()[2] iterations; a capped solve is counted and its iterate
+ *      used.  A departure: the reference factorises with CHOLMOD.
+ *   9. Update (:418-435): est_i <- Log(Exp(est_i) Exp(-x_i)) for every registered image, the fixed one included.
+ *  10. Stop (:485-499, :407-411): the sum of |x_i| over the registered images divided by their number goes to step_trace[iteration]; the
+ *      loop ends when it is < irls_step_convergence_threshold (XM_VGR_STOP_STEP) or after max_num_irls_iterations (XM_VGR_STOP_ITERATIONS).
+ *  11. XM_ERR_ARG, nothing written, everything checked on the host before any device call: an index out of range, pi == pj, an unknown
+ *      weight type, a non-finite or non-positive option, a non-finite entry of rot0 of a registered image or of Rrel of a participating
+ *      pair, a wrong struct_size, a null array where its count is positive, counts >= 2^31, fixed_image out of range or unregistered,
+ *      registered images that the participating pairs do not connect (a host union-find; the reference assumes
+ *      KeepLargestConnectedComponents ran, and a second component would make the system singular).  With no participating pair the call
+ *      succeeds, copies rot0, reports zero iterations and XM_VGR_STOP_NOTHING, and needs no device.
+ * Outputs: rot_out[9n] (Exp of the state; unregistered images keep rot0), angle_axis_out[3n] (0 when unregistered), residual[3 npairs] at
+ * the final rotations, weight[npairs] of the last iteration's solve (0 for a pair that takes no part), step_trace[max_num_irls_iterations]
+ * (0 behind the last iteration).
+ * Not built: the maximum-spanning-tree start, the L1 / ADMM stage, gravity, use_weight (a TODO in the reference too).
+ * Nothing here is compared with the reference's compiled code (it needs Eigen, SuiteSparse, COLMAP and glog): tests/xm_rotavg_numpy.py
+ * restates the C++ line by line and the device is tested against that.  All f64; sums run in a fixed order and there is no atomic at all:
+ * two calls give the same bytes. */
+#define XM_VGR_GEMAN_MCCLURE 0          /* weight_type (RotationEstimatorOptions::GEMAN_MCCLURE, the default) */
+#define XM_VGR_HALF_NORM     1
+#define XM_VGR_STOP_NOTHING    0        /* stop_reason: no participating pair */
+#define XM_VGR_STOP_STEP       1
+#define XM_VGR_STOP_ITERATIONS 2
+#define XM_VGR_STOP_NONFINITE  3
+typedef struct {
+    uint32_t struct_size;
+    int32_t weight_type;                     /* XM_VGR_GEMAN_MCCLURE (global_rotation_averaging.h) */
+    int32_t max_num_irls_iterations;         /* 100 */
+    int32_t fixed_image;                     /* -1: the smallest registered index */
+    double irls_step_convergence_threshold;  /* 1e-3 */
+    double irls_loss_parameter_sigma;        /* 5.0, degrees */
+} xm_vgr_options_t;
+#define XM_VGR_OPTIONS_INIT { (uint32_t)sizeof(xm_vgr_options_t), XM_VGR_GEMAN_MCCLURE, 100, -1, 1e-3, 5.0 }
+typedef struct {
+    uint32_t struct_size;
+    int32_t stop_reason;               /* XM_VGR_STOP_* */
+    int32_t irls_iterations;
+    int32_t reserved;
+    int64_t pcg_iterations;            /* in total */
+    int64_t pcg_capped;                /* solves that hit xm_view_graph_rotations_limits()[2] */
+    int64_t pairs;                     /* participating pairs */
+    int64_t registered;
+    int64_t fixed_image;               /* -1 when nothing is registered */
+    int64_t cams_heavy;                /* cameras above xm_view_graph_rotations_limits()[0] incidences */
+    int64_t max_incidences;
+    double seconds_index;              /* host: lists and upload */
+    double seconds_kernels;
+    double seconds_download;
+} xm_vgr_result_t;
+int xm_view_graph_rotations(int64_t n, const uint8_t *registered /* or NULL */, const double *rot0, int64_t npairs, const int32_t *pi,
+                            const int32_t *pj, const double *Rrel, const uint8_t *valid_in /* or NULL */, const xm_vgr_options_t *opt,
+                            double *rot_out, double *angle_axis_out, double *residual, double *weight, double *step_trace,
+                            xm_vgr_result_t *res);
+/* Test export (like xm_view_graph_calibrate_probe): with the kernels, grids and arguments of the call, at the caller's angle_axis[3n] (the
+ * state) and x[3n] (a step; entries of unregistered images are ignored): the camera matrices rot (9 per image), residual (3 per pair), the
+ * gauge residual (3; fixed0 comes from rot0), weight (per pair, of opt's type from those residuals), then with weight_in (per pair, or
+ * NULL: the computed weights) rhs (3 per image), diagonal (per image), product (A^T W A x, 3 per image), and angle_axis_out (rule 9 with x)
+ * and step (rule 10, one double).  Every output whose pointer is not null is filled; pairs and cameras that take no part hold 0. */
+typedef struct {
+    uint32_t struct_size;
+    uint32_t reserved;
+    const double *angle_axis, *x, *weight_in;
+    double *rot, *residual, *gauge, *weight, *rhs, *diagonal, *product, *angle_axis_out, *step;
+} xm_vgr_probe_t;
+int xm_view_graph_rotations_probe(int64_t n, const uint8_t *registered, const double *rot0, int64_t npairs, const int32_t *pi,
+                                  const int32_t *pj, const double *Rrel, const uint8_t *valid_in, const xm_vgr_options_t *opt,
+                                  xm_vgr_probe_t *probe);
+/* out[0]: most incidences of a camera that one thread walks (a camera above it gets a workgroup); out[1]: threads per workgroup;
+ * out[2]: most PCG iterations of one solve; out[3]: 0 (spare) */
+int xm_view_graph_rotations_limits(int64_t out[4]);
 /* Translations and landmarks of a solution: the last step of utils/recoversolution.py:recover_XM (lines 77-86,
  * ybar_est = Abar @ sR_real.T; t_est = [0 | first N-1 columns], p_est = the rest) for an XM_STORAGE_SCHUR context.  The reference
  * needs the dense (N-1+M) x 3N matrix Abar.bin that create_matrix writes (creatematrix.py:283-311; 80 GB at Final-13682 with 800 k

@@ -18,6 +18,7 @@
 #include "xm_tracks_split.h"
 #include "xm_viewgraph.h"
 #include "xm_vgcalib.h"
+#include "xm_rotavg.h"
 #include "xm_pair.h"
 #include "xm_schur.h"
 #include "xm_sell.h"
@@ -1282,6 +1283,124 @@ int xm_view_graph_calibrate_limits(int64_t out[4]) {
     XM_TRY
     if (!out) throw xm::Error(XM_ERR_ARG, "xm_view_graph_calibrate_limits: null output");
     out[0] = xm::kVgcLightIncidences; out[1] = xm::kVgcThreads; out[2] = xm::kVgcSweeps; out[3] = xm::kVgcMaxPcgIters;
+    return XM_OK;
+    XM_CATCH
+}
+namespace {
+// the checks xm_view_graph_rotations and its probe share (rule 11): everything on the host, before any device call.  Returns the number of
+// participating pairs.
+int64_t vgr_check(const std::string &w, const xm::RavInput &in, const xm_vgr_options_t *opt, xm::RavSettings &c) {
+    const int64_t lim = (int64_t)1 << 31;
+    const double dmax = 1.7976931348623157e308;
+    if (!opt) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (opt->struct_size != sizeof(xm_vgr_options_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_vgr_options_t.struct_size is not sizeof(xm_vgr_options_t)");
+    if (opt->weight_type != XM_VGR_GEMAN_MCCLURE && opt->weight_type != XM_VGR_HALF_NORM) throw xm::Error(XM_ERR_ARG, w + ": unknown weight type");
+    if (opt->max_num_irls_iterations <= 0) throw xm::Error(XM_ERR_ARG, w + ": max_num_irls_iterations is not positive");
+    const double v[2] = {opt->irls_step_convergence_threshold, opt->irls_loss_parameter_sigma};
+    const char *name[2] = {"irls_step_convergence_threshold", "irls_loss_parameter_sigma"};
+    for (int x = 0; x < 2; ++x)
+        if (!(v[x] > 0.0) || !(v[x] <= dmax)) throw xm::Error(XM_ERR_ARG, w + ": " + name[x] + " is not positive or not finite");
+    if (in.n < 0 || in.npairs < 0) throw xm::Error(XM_ERR_ARG, w + ": negative size");
+    if (in.n >= lim || in.npairs >= lim) throw xm::Error(XM_ERR_ARG, w + ": images and pairs must each stay below 2^31");
+    if (in.n > 0 && !in.rot0) throw xm::Error(XM_ERR_ARG, w + ": null rot0");
+    if (in.npairs > 0 && (!in.pi || !in.pj || !in.Rrel)) throw xm::Error(XM_ERR_ARG, w + ": null pair arrays");
+    if (opt->fixed_image < -1 || opt->fixed_image >= in.n) throw xm::Error(XM_ERR_ARG, w + ": fixed_image out of range");
+    int64_t fixed = opt->fixed_image, nreg = 0;
+    for (int64_t i = 0; i < in.n; ++i) {
+        if (in.registered && !in.registered[i]) continue;
+        nreg++;
+        if (fixed < 0) fixed = i;
+        for (int e = 0; e < 9; ++e)
+            if (!(std::fabs(in.rot0[9 * i + e]) <= dmax)) throw xm::Error(XM_ERR_ARG, w + ": rot0 of image " + std::to_string(i) + " is not finite");
+    }
+    if (opt->fixed_image >= 0 && in.registered && !in.registered[opt->fixed_image]) throw xm::Error(XM_ERR_ARG, w + ": fixed_image is not registered");
+    for (int64_t k = 0; k < in.npairs; ++k) {
+        if (in.pi[k] < 0 || in.pi[k] >= in.n || in.pj[k] < 0 || in.pj[k] >= in.n) throw xm::Error(XM_ERR_ARG, w + ": image index out of range at pair " + std::to_string(k));
+        if (in.pi[k] == in.pj[k]) throw xm::Error(XM_ERR_ARG, w + ": pair " + std::to_string(k) + " names one image twice");
+    }
+    // the registered images must be one component over the participating pairs
+    std::vector<int32_t> parent((size_t)in.n);
+    for (int64_t i = 0; i < in.n; ++i) parent[(size_t)i] = (int32_t)i;
+    auto find = [&](int32_t a) {
+        while (parent[(size_t)a] != a) { parent[(size_t)a] = parent[(size_t)parent[(size_t)a]]; a = parent[(size_t)a]; }
+        return a;
+    };
+    int64_t M = 0, joins = 0;
+    for (int64_t k = 0; k < in.npairs; ++k) {
+        if (!xm::rav_takes_part(in, k)) continue;
+        M++;
+        for (int e = 0; e < 9; ++e)
+            if (!(std::fabs(in.Rrel[9 * k + e]) <= dmax)) throw xm::Error(XM_ERR_ARG, w + ": Rrel of pair " + std::to_string(k) + " is not finite");
+        const int32_t a = find(in.pi[k]), b = find(in.pj[k]);
+        if (a != b) { parent[(size_t)std::max(a, b)] = std::min(a, b); joins++; }
+    }
+    if (M > 0 && joins != nreg - 1) throw xm::Error(XM_ERR_ARG, w + ": the participating pairs do not connect the registered images");
+    c.weight_type = opt->weight_type; c.max_iters = opt->max_num_irls_iterations; c.fixed_image = fixed;
+    c.step_tol = opt->irls_step_convergence_threshold; c.sigma_deg = opt->irls_loss_parameter_sigma;
+    if (const char *e = std::getenv("XM_WATCHDOG_S")) { const double s = std::atof(e); if (s > 0) c.watchdog_s = s; }
+    return M;
+}
+}  // namespace
+int xm_view_graph_rotations(int64_t n, const uint8_t *registered, const double *rot0, int64_t npairs, const int32_t *pi, const int32_t *pj,
+                            const double *Rrel, const uint8_t *valid_in, const xm_vgr_options_t *opt, double *rot_out, double *angle_axis_out,
+                            double *residual, double *weight, double *step_trace, xm_vgr_result_t *res) {
+    XM_TRY
+    const std::string w("xm_view_graph_rotations");
+    if (!res) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (res->struct_size != sizeof(xm_vgr_result_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_vgr_result_t.struct_size is not sizeof(xm_vgr_result_t)");
+    xm::RavInput in;
+    in.n = n; in.npairs = npairs; in.registered = registered; in.rot0 = rot0; in.pi = pi; in.pj = pj; in.Rrel = Rrel; in.valid_in = valid_in;
+    xm::RavSettings c;
+    const int64_t M = vgr_check(w, in, opt, c);
+    if (n > 0 && (!rot_out || !angle_axis_out)) throw xm::Error(XM_ERR_ARG, w + ": null image outputs");
+    if (npairs > 0 && (!residual || !weight)) throw xm::Error(XM_ERR_ARG, w + ": null pair outputs");
+    if (!step_trace) throw xm::Error(XM_ERR_ARG, w + ": null step_trace");
+    xm::RavOutput o;
+    o.rot_out = rot_out; o.angle_axis_out = angle_axis_out; o.residual = residual; o.weight = weight; o.step_trace = step_trace;
+    if (M > 0) require_device();
+    xm::RavOutcome r;
+    xm::view_graph_rotations_host(in, c, o, r);
+    xm_vgr_result_t out;
+    std::memset(&out, 0, sizeof(out));
+    out.struct_size = sizeof(xm_vgr_result_t);
+    out.stop_reason = r.stop; out.irls_iterations = r.iters; out.pcg_iterations = r.pcg_iters; out.pcg_capped = r.pcg_capped; out.pairs = r.pairs;
+    out.registered = r.registered; out.fixed_image = r.fixed_image; out.cams_heavy = r.cams_heavy; out.max_incidences = r.max_incidences;
+    out.seconds_index = r.seconds_index; out.seconds_kernels = r.seconds_kernels; out.seconds_download = r.seconds_download;
+    *res = out;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_view_graph_rotations_probe(int64_t n, const uint8_t *registered, const double *rot0, int64_t npairs, const int32_t *pi, const int32_t *pj,
+                                  const double *Rrel, const uint8_t *valid_in, const xm_vgr_options_t *opt, xm_vgr_probe_t *probe) {
+    XM_TRY
+    const std::string w("xm_view_graph_rotations_probe");
+    const double dmax = 1.7976931348623157e308;
+    if (!probe) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (probe->struct_size != sizeof(xm_vgr_probe_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_vgr_probe_t.struct_size is not sizeof(xm_vgr_probe_t)");
+    xm::RavInput in;
+    in.n = n; in.npairs = npairs; in.registered = registered; in.rot0 = rot0; in.pi = pi; in.pj = pj; in.Rrel = Rrel; in.valid_in = valid_in;
+    xm::RavSettings c;
+    const int64_t M = vgr_check(w, in, opt, c);
+    if (n > 0 && (!probe->angle_axis || !probe->x)) throw xm::Error(XM_ERR_ARG, w + ": null angle_axis or x");
+    for (int64_t i = 0; i < n; ++i) {
+        if (registered && !registered[i]) continue;
+        for (int e = 0; e < 3; ++e)
+            if (!(std::fabs(probe->angle_axis[3 * i + e]) <= dmax) || !(std::fabs(probe->x[3 * i + e]) <= dmax))
+                throw xm::Error(XM_ERR_ARG, w + ": angle_axis or x of image " + std::to_string(i) + " is not finite");
+    }
+    xm::RavProbe q;
+    q.angle_axis = probe->angle_axis; q.x = probe->x; q.weight_in = probe->weight_in; q.rot = probe->rot; q.residual = probe->residual;
+    q.gauge = probe->gauge; q.weight = probe->weight; q.rhs = probe->rhs; q.diagonal = probe->diagonal; q.product = probe->product;
+    q.angle_axis_out = probe->angle_axis_out; q.step = probe->step;
+    if (M > 0) require_device();
+    xm::view_graph_rotations_probe_host(in, c, q);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_view_graph_rotations_limits(int64_t out[4]) {
+    XM_TRY
+    if (!out) throw xm::Error(XM_ERR_ARG, "xm_view_graph_rotations_limits: null output");
+    out[0] = xm::kRavLightIncidences; out[1] = xm::kRavThreads; out[2] = xm::kRavMaxPcgIters; out[3] = 0;
     return XM_OK;
     XM_CATCH
 }

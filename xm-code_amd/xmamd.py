@@ -43,6 +43,7 @@ EXPORTS = [
     "xm_build_tracks", "xm_tracks_limits", "xm_tracks_split_host", "xm_tracks_split_device", "xm_tracks_split_limits", "xm_tracks_split_stats",
     "xm_view_graph_filter", "xm_view_graph_limits",
     "xm_view_graph_calibrate", "xm_view_graph_calibrate_probe", "xm_view_graph_calibrate_limits",
+    "xm_view_graph_rotations", "xm_view_graph_rotations_probe", "xm_view_graph_rotations_limits",
     "xm_ctx_filter_tracks", "xm_track_filter_limits",
     "xm_prune_weakly_connected", "xm_ctx_prune_weakly_connected", "xm_prune_limits",
     "xm_ctx_global_positioning", "xm_ctx_gp_probe", "xm_gp_limits",
@@ -371,6 +372,28 @@ class VgcProbe(C.Structure):       # xm_vgc_probe_t, the test export xm_view_gra
                [(k, C.c_void_p) for k in ("d", "residual", "record", "cost", "gradient", "diagonal", "product")]
 
 
+class VgrOptions(C.Structure):     # xm_vgr_options_t; the defaults are those of global_rotation_averaging.h
+    _fields_ = [("struct_size", C.c_uint32), ("weight_type", C.c_int32), ("max_num_irls_iterations", C.c_int32), ("fixed_image", C.c_int32),
+                ("irls_step_convergence_threshold", C.c_double), ("irls_loss_parameter_sigma", C.c_double)]
+
+    def __init__(self, weight_type=0, max_num_irls_iterations=100, fixed_image=-1, irls_step_convergence_threshold=1e-3,
+                 irls_loss_parameter_sigma=5.0):
+        super().__init__(C.sizeof(VgrOptions), weight_type, max_num_irls_iterations, fixed_image, irls_step_convergence_threshold,
+                         irls_loss_parameter_sigma)
+
+
+class VgrResult(C.Structure):      # xm_vgr_result_t
+    _fields_ = [("struct_size", C.c_uint32), ("stop_reason", C.c_int32), ("irls_iterations", C.c_int32), ("reserved", C.c_int32)] + \
+               [(k, C.c_int64) for k in ("pcg_iterations", "pcg_capped", "pairs", "registered", "fixed_image", "cams_heavy", "max_incidences")] + \
+               [(k, C.c_double) for k in ("seconds_index", "seconds_kernels", "seconds_download")]
+
+
+class VgrProbe(C.Structure):       # xm_vgr_probe_t, the test export xm_view_graph_rotations_probe
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + \
+               [(k, C.c_void_p) for k in ("angle_axis", "x", "weight_in", "rot", "residual", "gauge", "weight", "rhs", "diagonal", "product",
+                                          "angle_axis_out", "step")]
+
+
 class LaProbe(C.Structure):        # xm_la_probe_t, the test export xm_la_probe
     _fields_ = [("struct_size", C.c_uint32)] + [(k, C.c_int32) for k in ("op", "m", "n", "k", "nrhs", "ta", "tb", "lower_only", "info")] + \
                [(k, C.c_int64) for k in ("lda", "ldb", "ldc")] + [("q", C.c_double)] + [(k, C.c_void_p) for k in ("A", "B", "C")]
@@ -381,6 +404,10 @@ LA_OPS = {"gemm_sub": 0, "cholesky": 1, "substitute": 2, "inverse": 3, "layout":
 VGC_UPDATE_CONFIG = 1
 VGC_VALID, VGC_INVALID_IN, VGC_TWO_VIEW_ERROR = 0, 1, 2
 VGC_CAM_UNUSED, VGC_CAM_CONSTANT, VGC_CAM_REFINED, VGC_CAM_REJECTED = 0, 1, 2, 3
+VGR_GEMAN_MCCLURE, VGR_HALF_NORM = 0, 1
+VGR_WEIGHT_TYPES = {"geman_mcclure": VGR_GEMAN_MCCLURE, "half_norm": VGR_HALF_NORM}
+VGR_STOP_NOTHING, VGR_STOP_STEP, VGR_STOP_ITERATIONS, VGR_STOP_NONFINITE = 0, 1, 2, 3
+VGR_STOP = {0: "nothing", 1: "step_tolerance", 2: "max_iterations", 3: "nonfinite_weight"}
 VG_SCORE = 1
 VG_MODEL_NONE, VG_MODEL_E, VG_MODEL_F, VG_MODEL_H = 0, 1, 2, 3
 VG_MODELS = {"none": VG_MODEL_NONE, "E": VG_MODEL_E, "F": VG_MODEL_F, "H": VG_MODEL_H}
@@ -476,6 +503,11 @@ def lib():
         L.xm_view_graph_calibrate_probe.argtypes = [C.c_int64] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + \
                                                    [C.POINTER(VgcOptions), C.POINTER(VgcProbe)]
         L.xm_view_graph_calibrate_limits.argtypes = [C.c_void_p]
+        L.xm_view_graph_rotations.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.POINTER(VgrOptions)] + \
+                                             [C.c_void_p] * 5 + [C.POINTER(VgrResult)]
+        L.xm_view_graph_rotations_probe.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + \
+                                                   [C.POINTER(VgrOptions), C.POINTER(VgrProbe)]
+        L.xm_view_graph_rotations_limits.argtypes = [C.c_void_p]
         L.xm_tracks_split_host.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.xm_tracks_split_device.argtypes = L.xm_tracks_split_host.argtypes
         L.xm_tracks_split_limits.argtypes = [C.c_void_p]
@@ -1557,6 +1589,101 @@ def view_graph_calibrate_probe(focal0, pp, has_prior, cam_of_image, pi, pj, mode
     _chk(lib().xm_view_graph_calibrate_probe(ncams, V(focal0), V(pp), V(has_prior), n, V(cam), npairs, V(pi), V(pj), V(model), V(F), V(valid_in),
                                              C.byref(opt), C.byref(q)))
     out["cost"] = float(out["cost"][0])
+    return out
+
+
+class RotationPlan:
+    """what view_graph_rotations returns: rot (n x 3 x 3, cam_from_world: the rot of view_graph_filter's pass B as it is; unregistered images
+    keep rot0), angle_axis (n x 3), residual (pairs x 3, at the final rotations), weight (per pair, of the last iteration's solve; 0 for a
+    pair that takes no part), step_trace (the average step of every iteration), info (the fields of xm_vgr_result_t and stop, its name)"""
+
+    def __init__(self, rot, angle_axis, residual, weight, step_trace, info):
+        self.rot, self.angle_axis, self.residual, self.weight, self.step_trace, self.info = rot, angle_axis, residual, weight, step_trace, info
+
+
+def view_graph_rotations_limits():
+    """-> dict(light_incidences: most incidences of a camera that one thread walks (a camera above it gets a workgroup), threads: per
+    workgroup, pcg_iterations: most PCG iterations of one solve).  Needs no device"""
+    out = np.zeros(4, dtype=np.int64)
+    _chk(lib().xm_view_graph_rotations_limits(out.ctypes.data_as(C.c_void_p)))
+    return dict(light_incidences=int(out[0]), threads=int(out[1]), pcg_iterations=int(out[2]))
+
+
+def _vgr_inputs(what, rot0, pi, pj, Rrel, registered, valid_in, weight_type):
+    rot0 = np.ascontiguousarray(rot0, dtype=np.float64)
+    if rot0.size % 9:
+        raise XmError(f"{what}: rot0 must be images x 3 x 3")
+    rot0 = rot0.reshape(-1, 3, 3)
+    n = rot0.shape[0]
+    pi = np.ascontiguousarray(pi, dtype=np.int32).reshape(-1); pj = np.ascontiguousarray(pj, dtype=np.int32).reshape(-1)
+    if pi.size != pj.size:
+        raise XmError(f"{what}: pi and pj must have one entry per pair")
+    npairs = pi.size
+    Rrel = np.ascontiguousarray(Rrel, dtype=np.float64)
+    if Rrel.size != 9 * npairs:
+        raise XmError(f"{what}: Rrel must be pairs x 3 x 3")
+    Rrel = Rrel.reshape(npairs, 3, 3)
+    if registered is not None:
+        registered = np.ascontiguousarray(np.asarray(registered) != 0, dtype=np.uint8).reshape(-1)
+        if registered.size != n:
+            raise XmError(f"{what}: registered must have one entry per image")
+    if valid_in is not None:
+        valid_in = np.ascontiguousarray(np.asarray(valid_in) != 0, dtype=np.uint8).reshape(-1)
+        if valid_in.size != npairs:
+            raise XmError(f"{what}: valid_in must have one entry per pair")
+    if isinstance(weight_type, str):
+        if weight_type not in VGR_WEIGHT_TYPES:
+            raise XmError(f"{what}: weight_type must be a VGR_* number or one of {sorted(VGR_WEIGHT_TYPES)}")
+        weight_type = VGR_WEIGHT_TYPES[weight_type]
+    return rot0, pi, pj, Rrel, registered, valid_in, int(weight_type)
+
+
+def view_graph_rotations(rot0, pi, pj, Rrel, registered=None, valid_in=None, weight_type=VGR_GEMAN_MCCLURE, max_num_irls_iterations=100,
+                         irls_step_convergence_threshold=1e-3, irls_loss_parameter_sigma=5.0, fixed_image=-1):
+    """robust rotation averaging over the view graph on the device (xm_view_graph_rotations; include/xm_amd.h has the rules and the lines of
+    the reference's fork of GLOMAP they stand for): rot0 (n x 3 x 3, cam_from_world, the start: the rotations of a view-graph solve), pi, pj,
+    Rrel (pairs x 3 x 3, cam2_from_cam1) as view_graph_filter takes them; registered per image and valid_in per pair or None; weight_type
+    VGR_GEMAN_MCCLURE / VGR_HALF_NORM or "geman_mcclure" / "half_norm"; sigma in degrees.  -> RotationPlan"""
+    w = "view_graph_rotations"
+    rot0, pi, pj, Rrel, registered, valid_in, wt = _vgr_inputs(w, rot0, pi, pj, Rrel, registered, valid_in, weight_type)
+    n, npairs = rot0.shape[0], pi.size
+    opt = VgrOptions(wt, int(max_num_irls_iterations), int(fixed_image), float(irls_step_convergence_threshold), float(irls_loss_parameter_sigma))
+    res = VgrResult(); res.struct_size = C.sizeof(VgrResult)
+    rot = np.zeros((n, 3, 3)); aa = np.zeros((n, 3)); resid = np.zeros((npairs, 3)); weight = np.zeros(npairs)
+    trace = np.zeros(max(int(max_num_irls_iterations), 1))
+    P = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    _chk(lib().xm_view_graph_rotations(n, P(registered), P(rot0), npairs, P(pi), P(pj), P(Rrel), P(valid_in), C.byref(opt), P(rot), P(aa), P(resid),
+                                       P(weight), P(trace), C.byref(res)))
+    info = {f: getattr(res, f) for f, _ in VgrResult._fields_ if f not in ("struct_size", "reserved")}
+    info["stop"] = VGR_STOP.get(res.stop_reason, str(res.stop_reason))
+    return RotationPlan(rot, aa, resid, weight, trace[:res.irls_iterations].copy(), info)
+
+
+def view_graph_rotations_probe(rot0, pi, pj, Rrel, angle_axis, x=None, weight_in=None, registered=None, valid_in=None,
+                               weight_type=VGR_GEMAN_MCCLURE, irls_loss_parameter_sigma=5.0, fixed_image=-1):
+    """the test export xm_view_graph_rotations_probe: the camera matrices, residuals, gauge residual and weights at the state angle_axis (n x 3),
+    then with weight_in (per pair, or None: the computed weights) the right-hand side, the diagonal and the product with x (n x 3), and the
+    update by x with its average step -> dict(rot, residual, gauge, weight, rhs, diagonal, product, angle_axis_out, step)"""
+    w = "view_graph_rotations_probe"
+    rot0, pi, pj, Rrel, registered, valid_in, wt = _vgr_inputs(w, rot0, pi, pj, Rrel, registered, valid_in, weight_type)
+    n, npairs = rot0.shape[0], pi.size
+    angle_axis = np.ascontiguousarray(angle_axis, dtype=np.float64)
+    x = np.zeros((n, 3)) if x is None else np.ascontiguousarray(x, dtype=np.float64)
+    if angle_axis.size != 3 * n or x.size != 3 * n:
+        raise XmError(f"{w}: angle_axis and x must be images x 3")
+    if weight_in is not None:
+        weight_in = np.ascontiguousarray(weight_in, dtype=np.float64).reshape(-1)
+        if weight_in.size != npairs:
+            raise XmError(f"{w}: weight_in must have one entry per pair")
+    opt = VgrOptions(wt, 100, int(fixed_image), 1e-3, float(irls_loss_parameter_sigma))
+    out = dict(rot=np.zeros((n, 3, 3)), residual=np.zeros((npairs, 3)), gauge=np.zeros(3), weight=np.zeros(npairs), rhs=np.zeros((n, 3)),
+               diagonal=np.zeros(n), product=np.zeros((n, 3)), angle_axis_out=np.zeros((n, 3)), step=np.zeros(1))
+    P = lambda a: None if a is None else a.ctypes.data
+    q = VgrProbe(C.sizeof(VgrProbe), 0, P(angle_axis), P(x), P(weight_in),
+                 *[P(out[k]) for k in ("rot", "residual", "gauge", "weight", "rhs", "diagonal", "product", "angle_axis_out", "step")])
+    V = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    _chk(lib().xm_view_graph_rotations_probe(n, V(registered), V(rot0), npairs, V(pi), V(pj), V(Rrel), V(valid_in), C.byref(opt), C.byref(q)))
+    out["step"] = float(out["step"][0])
     return out
 
 
