@@ -118,6 +118,19 @@ def test_two_calls_give_the_same_bytes(gpu, kind):
     assert all(np.asarray(out[0][k]).tobytes() == np.asarray(out[1][k]).tobytes() for k in out[0])
 
 
+def test_chain_caps_the_pcg(gpu):
+    """a chain of 600 cameras, two IRLS iterations: both solves stop at the PCG's cap of 500 iterations (tests/test_rotavg_numpy.py: the
+    contract's relative residual there is far above the tolerance), and the call goes on with what the capped solves gave"""
+    g = rn.chain(600, 3)
+    b = rn.irls_contract(g, max_iters=2)
+    plan = gpu.view_graph_rotations(**rn.call_inputs(g), max_num_irls_iterations=2)
+    i = plan.info
+    print(f"chain of 600: {i['irls_iterations']} IRLS iterations, {i['pcg_iterations']} PCG iterations, {i['pcg_capped']} capped, stop {i['stop']}")
+    assert i["irls_iterations"] == 2 and i["pcg_iterations"] == 1000 == b["pcg_iters"] and i["pcg_capped"] == 2 == b["pcg_capped"]
+    assert i["stop_reason"] == b["stop"]
+    assert all(np.isfinite(getattr(plan, k)).all() for k in ("rot", "angle_axis", "residual", "weight", "step_trace"))
+
+
 def test_fixed_image_is_honoured(gpu):
     g = references("20/100 15 %")[0]
     a, b = rn.irls_sequential(g, LD, fixed_image=7), rn.irls_contract(g, fixed_image=7)

@@ -183,3 +183,13 @@ def test_star_ring_and_simple2_generators():
     before, after = np.median(rn.errors_deg(g["rot0"], g["truth"], p["img"])), np.median(rn.errors_deg(b["rot"], g["truth"], p["img"]))
     print(f"SIMPLE2-derived: {p['k'].size} pairs of {p['img'].size} images, median error {before:.3f} -> {after:.3f} deg in {b['iters']} iterations")
     assert b["stop"] == rn.STOP_STEP and after < before
+
+
+def test_chain_caps_the_pcg():
+    """a chain of 600 cameras: both solves of two IRLS iterations run into the PCG's cap.  The relative residual there is orders of magnitude
+    above the tolerance 1e-12, so rounding cannot turn a capped solve into one that converged (tests/test_gpu_rotavg.py asks the device for
+    the same counts)"""
+    b = rn.irls_contract(rn.chain(600, 3), max_iters=2)
+    print(f"chain of 600: relative residual of the two capped solves {b['pcg_relres'][0]:.3e}, {b['pcg_relres'][1]:.3e}")
+    assert b["iters"] == 2 and b["pcg_iters"] == 2 * rn.PCG_CAP == 1000 and b["pcg_capped"] == 2 and b["stop"] == rn.STOP_ITERATIONS
+    assert min(b["pcg_relres"]) > 1e-8

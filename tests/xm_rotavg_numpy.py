@@ -417,7 +417,8 @@ def pcg_contract(apply, b, dinv, tol2=PCG_TOL2, cap=PCG_CAP):
 
 
 def irls_contract(g, weight_type=GEMAN_MCCLURE, max_iters=100, threshold=1e-3, sigma_deg=5.0, fixed_image=-1):
-    """the device's rules in float64 (rules 5 to 10 vectorised, the camera sums in incidence order) -> as irls_sequential, and pcg_iters, pcg_capped"""
+    """the device's rules in float64 (rules 5 to 10 vectorised, the camera sums in incidence order) -> as irls_sequential, and pcg_iters, pcg_capped,
+    pcg_relres (per solve |b - A x| / |b| of what the PCG returned)"""
     if weight_type not in (GEMAN_MCCLURE, HALF_NORM) or not (max_iters > 0) or not (0 < threshold < np.inf) or not (0 < sigma_deg < np.inf):
         raise Refused("options")
     p = problem(g, fixed_image)
@@ -425,7 +426,7 @@ def irls_contract(g, weight_type=GEMAN_MCCLURE, max_iters=100, threshold=1e-3, s
     nr, M = p["img"].size, p["k"].size
     est = log_batch(p["rot0"][p["img"]])
     if M == 0:
-        return _finish(p, T, est, p["rot0"][p["img"]], np.zeros(3), None, [], STOP_NOTHING, dict(pcg_iters=0, pcg_capped=0))
+        return _finish(p, T, est, p["rot0"][p["img"]], np.zeros(3), None, [], STOP_NOTHING, dict(pcg_iters=0, pcg_capped=0, pcg_relres=[]))
     ca, cb, Rrel = p["ca"], p["cb"], p["Rrel"][p["k"]]
     f = int(p["slot"][p["fixed"]])
     R = exp_batch(est)
@@ -451,7 +452,7 @@ def irls_contract(g, weight_type=GEMAN_MCCLURE, max_iters=100, threshold=1e-3, s
         return r, w
 
     r, w = evaluate(R)
-    trace, stop, w_used, pcg_iters, pcg_capped = [], STOP_ITERATIONS, None, 0, 0
+    trace, stop, w_used, pcg_iters, pcg_capped, pcg_relres = [], STOP_ITERATIONS, None, 0, 0, []
     for _ in range(max_iters):
         if not np.isfinite(w).all():
             stop = STOP_NONFINITE
@@ -471,6 +472,7 @@ def irls_contract(g, weight_type=GEMAN_MCCLURE, max_iters=100, threshold=1e-3, s
             return o.reshape(-1)
         x, it, capped = pcg_contract(apply, b.reshape(-1), dinv)
         pcg_iters += it; pcg_capped += int(capped)
+        pcg_relres.append(float(np.linalg.norm(b.reshape(-1) - apply(x)) / np.linalg.norm(b)))
         x = x.reshape(nr, 3)
         est = log_batch(mul_batch(R, exp_batch(-x)))
         R = exp_batch(est)
@@ -480,7 +482,7 @@ def irls_contract(g, weight_type=GEMAN_MCCLURE, max_iters=100, threshold=1e-3, s
         if trace[-1] < threshold:
             stop = STOP_STEP
             break
-    return _finish(p, T, est, R, r.reshape(-1), w_used, trace, stop, dict(pcg_iters=pcg_iters, pcg_capped=pcg_capped))
+    return _finish(p, T, est, R, r.reshape(-1), w_used, trace, stop, dict(pcg_iters=pcg_iters, pcg_capped=pcg_capped, pcg_relres=pcg_relres))
 
 
 # ------------------------------------------------------------------------------------------------ measures
@@ -572,6 +574,12 @@ def make_graph(n, npairs, seed, noise_deg=1.0, outliers=0.0, start="chordal"):
         pairs.append((i, j))
     clean = np.arange(len(pairs)) < n - 1
     return build_graph(n, pairs, clean, seed, noise_deg, outliers, start)
+
+
+def chain(n, seed, noise_deg=1.0):
+    """n cameras in one chain (i, i + 1), all pairs clean, from the true rotations: a Laplacian whose condition grows with n^2, so that from
+    600 cameras on the PCG runs into its cap"""
+    return build_graph(n, [(i, i + 1) for i in range(n - 1)], np.ones(n - 1, dtype=bool), seed, noise_deg, 0.0, start="truth")
 
 
 def star(leaves, seed, noise_deg=1.0, start="chordal"):

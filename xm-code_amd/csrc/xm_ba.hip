@@ -1119,7 +1119,7 @@ struct BaWork {
         pp = parts.p;
         a.n = n; a.grid = gfc; a.cgrid = gcam; a.tol2 = cfg.eta * cfg.eta;
         a.b = b.p; a.sinv = sinv.p; a.ustar = ustar.p; a.x = x.p; a.r = r.p; a.z = z.p; a.p = pv.p; a.Ap = Ap.p;
-        a.prz[0] = pp + o_pcg; a.prz[1] = pp + o_pcg + gfc; a.prr = pp + o_pcg + 2 * gfc; a.pbb = pp + o_pcg + 3 * gfc; a.ppap = pp + o_pcg + 4 * gfc;
+        a.lay_partials(pp + o_pcg);
         a.st = dst;
         tlmode = cfg.precond != 0;
         atl = a;
@@ -1302,37 +1302,13 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
     const bool nonmono = cfg.nonmonotonic;
     std::vector<double> &hR = W.hR, &hT = W.hT, &hP = W.hP;
     int &cur = W.cur, &best = W.best;
-    BaState *const dst = W.dst;
-    const int gfc = W.gfc;
-    const dim3 b256 = W.b256;
     int pcg_last = 8;
-    // PCG from zero: batches enqueued ahead of the host (as many iterations as the last solve needed + 2, then steps of 8), one read per batch
-    auto pcg = [&](int &iters, double &relres) {
-        const BaPcg &a = W.pcg_args();
-        W.pcg_start();
-        int it = 0, dir_applied = 0;
-        auto enqueue = [&](int upto) {
-            for (; it < upto; ++it) {
-                if (it != dir_applied) hipLaunchKernelGGL((ba_pcg_dir_kernel<CD>), dim3(gfc), b256, 0, st, a, it);
-                W.sx(a, dst);
-                if (W.tlmode) W.precond(it, 0);
-                else hipLaunchKernelGGL((ba_pcg_upd_kernel<CD>), dim3(gfc), b256, 0, st, a, it);
-            }
-            hipLaunchKernelGGL((ba_pcg_dir_kernel<CD>), dim3(gfc), b256, 0, st, a, it);   // convergence test of the last update (or the next direction)
-            dir_applied = it;
-        };
-        int target = std::min(kBaMaxPcgIters, std::max(4, pcg_last + 2));
-        BaState s;
-        for (;;) {
-            enqueue(target);
-            s = W.read_state("the reduced camera PCG");
-            if (s.done || target >= kBaMaxPcgIters) break;
-            target = std::min(kBaMaxPcgIters, target + 8);
-        }
-        iters = s.done ? s.iters : target;
-        relres = s.relres;
-        if (s.done && s.iters > 0) pcg_last = s.iters;
-    };
+    // the PCG's batch driver with this solver's product; two-level: the preconditioner's kernels start and update in place of the plain ones
+    PcgHooks hooks;
+    hooks.product = [&] { W.sx(W.pcg_args(), W.dst); };
+    hooks.read = [&] { return W.read_state("the reduced camera PCG"); };
+    hooks.start = [&] { W.pcg_start(); };
+    if (W.tlmode) hooks.update = [&](int it) { W.precond(it, 0); };
 
     double radius = 1e4, nu = 2.0, F = 0.0, gmax = 0.0;
     int status = XM_BA_NO_CONVERGENCE, iters = 0, accepted = 0, trace_n = 0;
@@ -1366,7 +1342,8 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         if (cfg.dense_schur) W.dense_solve();
         else {
             if (W.tlmode) W.precond_setup();
-            pcg(pit, relres);
+            const PcgResult pr = pcg_solve_batched<CD>(W.pcg_args(), W.gfc, st, pcg_last, hooks);
+            pit = pr.iters; relres = pr.relres;
         }
         pcg_total += pit;
         int nx = 0;   // the candidate's parameter set: neither the current one nor the least-cost one (without non-monotonic steps: cur ^ 1)

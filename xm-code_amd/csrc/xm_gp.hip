@@ -502,7 +502,7 @@ struct GpWork {
         pp = parts.p;
         a.n = n; a.grid = gfc; a.cgrid = gcam; a.tol2 = cfg.eta * cfg.eta;
         a.b = b.p; a.sinv = sinv.p; a.ustar = ustar.p; a.x = x.p; a.r = r.p; a.z = z.p; a.p = pv.p; a.Ap = Ap.p;
-        a.prz[0] = pp + o_pcg; a.prz[1] = pp + o_pcg + gfc; a.prr = pp + o_pcg + 2 * gfc; a.pbb = pp + o_pcg + 3 * gfc; a.ppap = pp + o_pcg + 4 * gfc;
+        a.lay_partials(pp + o_pcg);
         a.st = &dst->b;
         // which observations, landmarks and cameras take part: fixed for the call
         hipLaunchKernelGGL(gp_setup_kernel, dim3(ge), b256, 0, st, S, (const double *)rot.p, dir.p, lflag.p);
@@ -604,36 +604,11 @@ struct GpWork {
 void run(const SchurOp &SO, const GpSettings &cfg, const double *rot, double *t, double *p, double *scales, GpOutcome &out, hipStream_t st) {
     const auto t_start = std::chrono::steady_clock::now();
     GpWork W(SO, cfg, rot, t, p, nullptr, st);
-    BaState *const pst = &W.dst->b;
-    const int gfc = W.gfc;
-    const dim3 b256 = W.b256;
     int pcg_last = 8;
-    // PCG from zero: batches enqueued ahead of the host (as many iterations as the last solve needed + 2, then steps of 8), one read per batch
-    auto pcg = [&](int &iters, double &relres) {
-        const BaPcg &a = W.a;
-        hipLaunchKernelGGL((ba_pcg_init_kernel<3>), dim3(gfc), b256, 0, st, a);
-        int it = 0, dir_applied = 0;
-        auto enqueue = [&](int upto) {
-            for (; it < upto; ++it) {
-                if (it != dir_applied) hipLaunchKernelGGL((ba_pcg_dir_kernel<3>), dim3(gfc), b256, 0, st, a, it);
-                W.sx(a, pst);
-                hipLaunchKernelGGL((ba_pcg_upd_kernel<3>), dim3(gfc), b256, 0, st, a, it);
-            }
-            hipLaunchKernelGGL((ba_pcg_dir_kernel<3>), dim3(gfc), b256, 0, st, a, it);   // convergence test of the last update (or the next direction)
-            dir_applied = it;
-        };
-        int target = std::min(kBaMaxPcgIters, std::max(4, pcg_last + 2));
-        GpState s;
-        for (;;) {
-            enqueue(target);
-            s = W.read_state("the reduced camera PCG");
-            if (s.b.done || target >= kBaMaxPcgIters) break;
-            target = std::min(kBaMaxPcgIters, target + 8);
-        }
-        iters = s.b.done ? s.b.iters : target;
-        relres = s.b.relres;
-        if (s.b.done && s.b.iters > 0) pcg_last = s.b.iters;
-    };
+    // the PCG's batch driver with this solver's product; the PCG's state word is the one GpState embeds
+    PcgHooks hooks;
+    hooks.product = [&] { W.sx(W.a, &W.dst->b); };
+    hooks.read = [&] { return W.read_state("the reduced camera PCG").b; };
 
     // the bundle adjustment's loop (xm_ba.hip), except that the records depend on mu and are written again in every iteration
     double radius = 1e4, nu = 2.0, F = 0.0, gmax = 0.0;
@@ -656,10 +631,8 @@ void run(const SchurOp &SO, const GpSettings &cfg, const double *rot, double *t,
         }
         if (iters >= cfg.max_iters) { status = XM_BA_MAX_ITERATIONS; break; }
         if (secs_since(t_start) >= cfg.max_time) { status = XM_BA_TIME_LIMIT; break; }
-        int pit = 0;
-        double relres = 0.0;
-        pcg(pit, relres);
-        pcg_total += pit;
+        const PcgResult pr = pcg_solve_batched<3>(W.a, W.gfc, st, pcg_last, hooks);
+        pcg_total += pr.iters;
         W.candidate(mu, W.x.p);
         const GpState s = W.read_state("the candidate's cost");
         iters++;
@@ -670,7 +643,7 @@ void run(const SchurOp &SO, const GpSettings &cfg, const double *rot, double *t,
         const bool accept = valid && rho > 1e-3;
         if (trace_n < cfg.trace_cap && cfg.trace) {
             double *rec = cfg.trace + (size_t)6 * trace_n++;
-            rec[0] = F; rec[1] = Fn; rec[2] = mu; rec[3] = accept ? 1.0 : 0.0; rec[4] = pit; rec[5] = relres;
+            rec[0] = F; rec[1] = Fn; rec[2] = mu; rec[3] = accept ? 1.0 : 0.0; rec[4] = pr.iters; rec[5] = pr.relres;
         }
         if (step_norm <= cfg.parameter_tol * (x_norm + cfg.parameter_tol)) { status = XM_BA_CONVERGED_PARAMETER; break; }
         if (accept) {

@@ -1,12 +1,15 @@
-// xm_lm_shared.h — what the two Levenberg-Marquardt solvers on the lists of the matrix-free storage share (xm_ba.hip: the reprojection bundle
-// adjustment; xm_gp.hip: the global positioning): the state word, the fixed-order reductions over a heavy landmark's workgroup, the walk
-// over a landmark's list, Ceres's losses, the small symmetric solves, the vector kernels of the PCG on the reduced camera system and the
-// kernel that brings partial sums into the state word.  The code is the one xm_ba.hip had: moving it here changes no bit of its outputs.
-// Everything stays in the anonymous namespace it had there: internal linkage, so each of the two translation units that include this file
-// compiles its own copy of the kernels and of the __shared__ arrays inside heavy_sum (include it in .hip files only, never in a header).
+// xm_lm_shared.h — what the solvers of sparse normal equations share (xm_ba.hip: the reprojection bundle adjustment; xm_gp.hip: the global
+// positioning; xm_vgcalib.hip: the focal lengths over the view graph; xm_rotavg.hip: the rotations over it): the state word, the
+// fixed-order reductions over a heavy landmark's workgroup, the walk over a landmark's list, Ceres's losses, the small symmetric solves,
+// the vector kernels of the PCG with the host's batch driver for them, and the kernel that brings partial sums into the state word.  The
+// device code is the one xm_ba.hip had: moving it here changes no bit of its outputs.
+// Everything stays in the anonymous namespace it had there: internal linkage, so each translation unit that includes this file compiles
+// its own copy of the kernels and of the __shared__ arrays inside heavy_sum (include it in .hip files only, never in a header).
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
+#include <functional>
 
 #include "xm_device.h"
 #include "xm_schur.h"
@@ -184,6 +187,8 @@ struct BaPcg {
     double *x, *r, *z, *p, *Ap;
     double *prz[2], *prr, *pbb, *ppap;
     BaState *st;
+    // the five partial sums behind one another in q: four of `grid` workgroups, then <p, Ap> of cgrid
+    void lay_partials(double *q) { prz[0] = q; prz[1] = q + grid; prr = q + 2 * grid; pbb = q + 3 * grid; ppap = q + 4 * grid; }
 };
 template <int CD>
 __device__ __forceinline__ void block_matvec(const double *M, const double *v, double (&out)[CD]) {
@@ -261,6 +266,49 @@ __global__ __launch_bounds__(256) void ba_pcg_upd_kernel(BaPcg a, int it) {
     rzn = block_sum256(rzn, sh);
     rr = block_sum256(rr, sh);
     if (threadIdx.x == 0) { a.prz[(it & 1) ^ 1][blockIdx.x] = rzn; a.prr[blockIdx.x] = rr; }
+}
+
+// ---- the host's side of one solve from zero: batches of iterations enqueued ahead of the host (as many as the last solve needed + 2,
+// then steps of 8, at most kBaMaxPcgIters), one read of the state word per batch.  What differs between the solvers:
+struct PcgHooks {
+    std::function<void()> product;                     // a.Ap = S a.p, gated by the state word's done flag
+    std::function<BaState()> read;                     // waits for the stream; the state word
+    std::function<void()> start;                       // empty: ba_pcg_init_kernel
+    std::function<void(int it)> update;                // empty: ba_pcg_upd_kernel
+};
+struct PcgResult {
+    int iters;
+    double relres;
+    bool capped;
+};
+// grid: the workgroups of the vector kernels (a.grid, unless the partial sums of a are laid out otherwise).  last: the iterations of the
+// last solve that reached the tolerance, kept by the caller from one solve to the next (8 before the first)
+template <int CD>
+PcgResult pcg_solve_batched(const BaPcg &a, int grid, hipStream_t st, int &last, const PcgHooks &h) {
+    const dim3 g(grid), b256(256);
+    if (h.start) h.start();
+    else hipLaunchKernelGGL((ba_pcg_init_kernel<CD>), g, b256, 0, st, a);
+    int it = 0, dir_applied = 0;
+    auto enqueue = [&](int upto) {
+        for (; it < upto; ++it) {
+            if (it != dir_applied) hipLaunchKernelGGL((ba_pcg_dir_kernel<CD>), g, b256, 0, st, a, it);
+            h.product();
+            if (h.update) h.update(it);
+            else hipLaunchKernelGGL((ba_pcg_upd_kernel<CD>), g, b256, 0, st, a, it);
+        }
+        hipLaunchKernelGGL((ba_pcg_dir_kernel<CD>), g, b256, 0, st, a, it);   // convergence test of the last update (or the next direction)
+        dir_applied = it;
+    };
+    int target = std::min(kBaMaxPcgIters, std::max(4, last + 2));
+    BaState s;
+    for (;;) {
+        enqueue(target);
+        s = h.read();
+        if (s.done || target >= kBaMaxPcgIters) break;
+        target = std::min(kBaMaxPcgIters, target + 8);
+    }
+    if (s.done && s.iters > 0) last = s.iters;
+    return {s.done ? s.iters : target, s.relres, !s.done};
 }
 
 // scalars of the state word from the partials, in a fixed order (one workgroup): up to 6 sums and one max

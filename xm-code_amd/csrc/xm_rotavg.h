@@ -3,8 +3,8 @@
 // :334-499 with skip_initialization = true and max_num_l1_iterations = 0, math/rigid3d.cc:41-71), from rotations the caller supplies.
 //
 // Host: the checks (xm_capi.hip, the union-find over the participating pairs among them), the slot of every registered image in image
-// order, the participating pairs in input order, the incidence lists camera -> (pair, side) by a stable counting sort in input order, heavy
-// cameras (more than kRavLightIncidences incidences) first.
+// order, the participating pairs in input order, the incidence lists camera -> (pair, side) of xm_pair_lists.h over the registered images,
+// every pair listed at both of its ends.
 //
 // Launches, all on the default stream and all deterministic in what they write (no atomic at all):
 //   rav_log_kernel        one thread per registered image: rot0 -> angle-axis (rule 4), the state
@@ -25,12 +25,13 @@
 #include <cstdint>
 
 #include "../../include/xm_amd.h"
+#include "xm_pair_lists.h"
 #include "xm_solver.h"
 
 namespace xm {
 
-constexpr int kRavThreads = 256;            // threads per workgroup
-constexpr int kRavLightIncidences = 64;     // most incidences of a camera that one thread walks; above: a workgroup of its own
+constexpr int kRavThreads = kPairListThreads;          // threads per workgroup
+constexpr int kRavLightIncidences = kPairListLight;    // most incidences of a camera that one thread walks
 constexpr int kRavMaxPcgIters = 500;        // most PCG iterations of one solve (xm_lm_shared.h: kBaMaxPcgIters)
 
 struct RavSettings {

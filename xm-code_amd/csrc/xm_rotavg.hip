@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "xm_lm_shared.h"
+#include "xm_pair_lists.h"
 #include "xm_stage.h"
 
 // every product and every sum of the contract is rounded on its own
@@ -21,8 +22,6 @@ namespace {
 constexpr const char *kStage = "xm_view_graph_rotations";
 constexpr int kT = kRavThreads;
 static_assert(kRavMaxPcgIters == kBaMaxPcgIters, "the limit reported is the one the PCG runs to");
-static_assert(kRavThreads == 256, "block_sum256 and the four wavefront sums are for 256 threads");
-constexpr int kFlatCap = 1024;   // most workgroups of a grid-stride launch
 
 // ---- rule 3: AngleAxisToRotation (rigid3d.cc:53-71), row-major; Eigen's AngleAxis::toRotationMatrix above the norm 1e-12
 __host__ __device__ __forceinline__ void rav_exp(double a0, double a1, double a2, double (&R)[9]) {
@@ -159,51 +158,28 @@ __global__ __launch_bounds__(kT) void rav_pair_kernel(RavPairs P, const double *
     if (threadIdx.x == 0) badp[blockIdx.x] = bad;
 }
 
-struct RavLists {   // camera -> (pair, side): side 0 the camera is image_id1 (the row holds -I there), 1 image_id2 (+I)
-    int nr, nheavy, fixed;   // fixed: the slot of the fixed camera
-    const int32_t *order;    // nr slots: the heavy ones first, each group in slot order
-    const int64_t *ptr;      // nr + 1, by slot
+// The lists of the registered images as the two kernels below take them: side 0 the camera is image_id1 (the row holds -I there), 1
+// image_id2 (+I).  PairLists's fields with the slot of the fixed camera next to the two counts: there the kernel's first scalar load brings
+// it in, and both kernels assemble to what they were before the lists were shared.  As an argument of its own the slot gets a load and a
+// wait of its own where it is used, after the walk
+struct RavLists {
+    int nr, nheavy, fixed;
+    const int32_t *order;
+    const int64_t *ptr;
     const int32_t *pair;
     const uint8_t *side;
+    RavLists(const PairLists &L, int fixed_) : nr(L.n), nheavy(L.nheavy), fixed(fixed_), order(L.order), ptr(L.ptr), pair(L.pair), side(L.side) {}
+    __device__ __forceinline__ PairLists lists() const { return {nr, nheavy, order, ptr, pair, side}; }
 };
-struct RavWalk {
-    int u;
-    int64_t e, e_end, step;
-    bool heavy;
-};
-__device__ __forceinline__ RavWalk rav_walk(const RavLists &L) {
-    RavWalk w;
-    w.heavy = (int)blockIdx.x < L.nheavy;
-    const int64_t slot = w.heavy ? (int64_t)blockIdx.x : (int64_t)L.nheavy + ((int64_t)blockIdx.x - L.nheavy) * kT + threadIdx.x;
-    w.u = slot < L.nr ? L.order[slot] : -1;
-    w.e = 0; w.e_end = 0; w.step = 1;
-    if (w.u >= 0) {
-        w.e = L.ptr[w.u] + (w.heavy ? threadIdx.x : 0); w.e_end = L.ptr[w.u + 1]; w.step = w.heavy ? kT : 1;
-    }
-    return w;
-}
-// sum of K values over a heavy camera's workgroup: DPP tree per wavefront, the four wavefront sums in a fixed order; valid in thread 0
-template <int K>
-__device__ __forceinline__ void rav_heavy_sum(double (&acc)[K], double (*part)[K]) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) part[threadIdx.x >> 6][k] = acc[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
-}
-
 // rule 8: b_i = sum of +w r over the pairs where i is image_id2 and of -w r where it is image_id1, d_i = sum of w; at the fixed camera the
 // gauge residual Log(R_fixed0^T R_fixed) (rule 6) with weight 1.  sinv holds 1 / d_i three times.
-__global__ __launch_bounds__(kT) void rav_cam_kernel(RavLists L, int M_, const double *__restrict__ res, const double *__restrict__ w,
+__global__ __launch_bounds__(kT) void rav_cam_kernel(RavLists R, int M_, const double *__restrict__ res, const double *__restrict__ w,
                                                      const double *__restrict__ Rm, const double *__restrict__ Rf0, double *__restrict__ b,
                                                      double *__restrict__ diag, double *__restrict__ sinv, double *__restrict__ gauge) {
     __shared__ double part[4][4];
     const size_t M = (size_t)M_;
-    const RavWalk k = rav_walk(L);
+    const PairLists L = R.lists();
+    const PairWalk k = pair_walk(L);
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     for (int64_t e = k.e; e < k.e_end; e += k.step) {
         const int m = L.pair[e];
@@ -211,9 +187,9 @@ __global__ __launch_bounds__(kT) void rav_cam_kernel(RavLists L, int M_, const d
         acc[0] += sw * res[m]; acc[1] += sw * res[M + m]; acc[2] += sw * res[2 * M + m];
         acc[3] += wt;
     }
-    if (k.heavy) rav_heavy_sum<4>(acc, part);
+    if (k.heavy) pair_heavy_sum<4>(acc, part);
     if (k.u >= 0 && (!k.heavy || threadIdx.x == 0)) {
-        if (k.u == L.fixed) {
+        if (k.u == R.fixed) {
             double A[9], B[9], Q[9], g0, g1, g2;
             load9(Rf0, A);
             load9(Rm + (size_t)9 * k.u, B);
@@ -231,12 +207,13 @@ __global__ __launch_bounds__(kT) void rav_cam_kernel(RavLists L, int M_, const d
 }
 
 // Ap_i = sum over i's pairs of w (p_i - p_other), + p_i at the fixed camera; <p, Ap> per workgroup.  gate: the PCG's state word
-__global__ __launch_bounds__(kT) void rav_camx_kernel(RavLists L, RavPairs P, const double *__restrict__ w, const double *__restrict__ p,
+__global__ __launch_bounds__(kT) void rav_camx_kernel(RavLists R, RavPairs P, const double *__restrict__ w, const double *__restrict__ p,
                                                       const BaState *__restrict__ gate, double *__restrict__ Ap, double *__restrict__ ppap) {
     __shared__ double part[4][3];
     __shared__ double sh[4];
     if (gate != nullptr && gate->done) return;
-    const RavWalk k = rav_walk(L);
+    const PairLists L = R.lists();
+    const PairWalk k = pair_walk(L);
     double acc[3] = {0.0, 0.0, 0.0};
     double p0 = 0.0, p1 = 0.0, p2 = 0.0;
     if (k.u >= 0) { p0 = p[3 * (size_t)k.u]; p1 = p[3 * (size_t)k.u + 1]; p2 = p[3 * (size_t)k.u + 2]; }
@@ -246,10 +223,10 @@ __global__ __launch_bounds__(kT) void rav_camx_kernel(RavLists L, RavPairs P, co
         const double wt = w[m];
         acc[0] += wt * (p0 - p[o]); acc[1] += wt * (p1 - p[o + 1]); acc[2] += wt * (p2 - p[o + 2]);
     }
-    if (k.heavy) rav_heavy_sum<3>(acc, part);
+    if (k.heavy) pair_heavy_sum<3>(acc, part);
     double pap = 0.0;
     if (k.u >= 0 && (!k.heavy || threadIdx.x == 0)) {
-        if (k.u == L.fixed) { acc[0] += p0; acc[1] += p1; acc[2] += p2; }
+        if (k.u == R.fixed) { acc[0] += p0; acc[1] += p1; acc[2] += p2; }
         const size_t o = 3 * (size_t)k.u;
         Ap[o] = acc[0]; Ap[o + 1] = acc[1]; Ap[o + 2] = acc[2];
         pap = (p0 * acc[0] + p1 * acc[1]) + p2 * acc[2];
@@ -280,15 +257,11 @@ __global__ __launch_bounds__(kT) void rav_update_kernel(int nr, const double *__
     if (threadIdx.x == 0) parts[blockIdx.x] = s;
 }
 
-inline int flat_grid_of(int64_t items) { return (int)std::max<int64_t>(1, std::min<int64_t>((items + kT - 1) / kT, kFlatCap)); }
-
 // What the host prepares from the caller's arrays: the slots, the participating pairs, the lists
 struct RavPlan {
-    int n = 0, npairs = 0, nr = 0, M = 0, nheavy = 0, fixed_slot = -1;
-    int64_t max_inc = 0;
-    std::vector<int32_t> img, slot, plist, ca, cb, order, inc_pair;
-    std::vector<uint8_t> inc_side;
-    std::vector<int64_t> inc_ptr;
+    int n = 0, npairs = 0, nr = 0, M = 0, fixed_slot = -1;
+    std::vector<int32_t> img, slot, plist, ca, cb;
+    PairListsHost lists;
     std::vector<double> rrel;
 
     RavPlan(const RavInput &in, int64_t fixed_image) {
@@ -305,24 +278,7 @@ struct RavPlan {
         M = (int)plist.size();
         rrel.resize((size_t)9 * M);
         for (int m = 0; m < M; ++m) std::memcpy(&rrel[(size_t)9 * m], in.Rrel + (size_t)9 * plist[(size_t)m], 9 * sizeof(double));
-        inc_ptr.assign((size_t)nr + 1, 0);
-        for (int m = 0; m < M; ++m) { inc_ptr[(size_t)ca[(size_t)m] + 1]++; inc_ptr[(size_t)cb[(size_t)m] + 1]++; }
-        for (int u = 0; u < nr; ++u) {
-            max_inc = std::max(max_inc, inc_ptr[(size_t)u + 1]);
-            inc_ptr[(size_t)u + 1] += inc_ptr[(size_t)u];
-        }
-        inc_pair.resize((size_t)inc_ptr[(size_t)nr]); inc_side.resize(inc_pair.size());
-        std::vector<int64_t> fill(inc_ptr.begin(), inc_ptr.end() - 1);
-        for (int m = 0; m < M; ++m) {   // stable: a camera's incidences stay in input order
-            int64_t e = fill[(size_t)ca[(size_t)m]]++; inc_pair[(size_t)e] = m; inc_side[(size_t)e] = 0;
-            e = fill[(size_t)cb[(size_t)m]]++; inc_pair[(size_t)e] = m; inc_side[(size_t)e] = 1;
-        }
-        std::vector<int32_t> light;
-        for (int u = 0; u < nr; ++u) {
-            if (inc_ptr[(size_t)u + 1] - inc_ptr[(size_t)u] > kRavLightIncidences) order.push_back(u); else light.push_back(u);
-        }
-        nheavy = (int)order.size();
-        order.insert(order.end(), light.begin(), light.end());
+        lists = build_pair_lists(nr, ca, cb, kRavLightIncidences, false);
     }
 };
 
@@ -332,16 +288,14 @@ struct RavWork {
     const RavSettings &cfg;
     hipStream_t st;
     DevBuf<double> rot0, Rrel, est, Rm, Rf0, res, w[2], b, diag, sinv, x, r, z, pv, Ap, parts, gauge;
-    DevBuf<int32_t> img, ca, cb, order, inc_pair, state_buf;
-    DevBuf<uint8_t> inc_side;
-    DevBuf<int64_t> inc_ptr;
+    DevBuf<int32_t> img, ca, cb, state_buf;
+    PairListsDev lists;
     BaState *dst = nullptr;
     Pinned<BaState> hs;
-    int ge = 1, gfc = 1, gcam = 1, gup = 1, gr = 1;
+    int ge = 1, gfc = 1, gup = 1, gr = 1;
     size_t o_bad = 0, o_pcg = 0, o_step = 0;
     double sigma2 = 0.0;
     RavPairs P{};
-    RavLists L{};
     BaPcg a{};
     const dim3 blk{kT};
 
@@ -350,8 +304,7 @@ struct RavWork {
         upload(rot0, in.rot0, (size_t)9 * pl.n, st);
         upload(Rrel, pl.rrel.data(), 9 * M, st);
         upload(img, pl.img.data(), nr, st); upload(ca, pl.ca.data(), M, st); upload(cb, pl.cb.data(), M, st);
-        upload(order, pl.order.data(), nr, st); upload(inc_ptr, pl.inc_ptr.data(), nr + 1, st);
-        upload(inc_pair, pl.inc_pair.data(), pl.inc_pair.size(), st); upload(inc_side, pl.inc_side.data(), pl.inc_side.size(), st);
+        lists.upload_from(pl.lists, pl.nr, st);
         est.alloc(3 * nr, false); Rm.alloc(9 * nr, false); Rf0.alloc(9, false); res.alloc(3 * M, false);
         fresh(w[0], M, 0, st); fresh(w[1], M, 0, st); fresh(gauge, 3, 0, st);
         diag.alloc(nr, false);
@@ -362,18 +315,16 @@ struct RavWork {
         gr = (int)std::max<size_t>(1, (nr + kT - 1) / kT);
         gfc = flat_grid_of((int64_t)(3 * nr));
         gup = flat_grid_of((int64_t)nr);
-        gcam = std::max(1, pl.nheavy + (pl.nr - pl.nheavy + kT - 1) / kT);
+        const int gcam = lists.grid;
         // partials: flag (ge) | PCG (4 gfc + gcam) | step (gup)
         o_bad = 0; o_pcg = (size_t)ge; o_step = o_pcg + 4 * (size_t)gfc + gcam;
         fresh(parts, o_step + (size_t)gup, 0, st);
         const double sigma = cfg.sigma_deg * 3.141592653589793238462643383279502884 / 180.0;   // DegToRad (rigid3d.cc:37)
         sigma2 = sigma * sigma;
         P.M = pl.M; P.ca = ca.p; P.cb = cb.p; P.Rrel = Rrel.p;
-        L.nr = pl.nr; L.nheavy = pl.nheavy; L.fixed = pl.fixed_slot; L.order = order.p; L.ptr = inc_ptr.p; L.pair = inc_pair.p; L.side = inc_side.p;
-        double *q = parts.p + o_pcg;
         a.n = 3 * (int64_t)pl.nr; a.grid = gfc; a.cgrid = gcam; a.tol2 = 1e-24;   // relative residual 1e-12
         a.b = b.p; a.sinv = sinv.p; a.ustar = nullptr; a.x = x.p; a.r = r.p; a.z = z.p; a.p = pv.p; a.Ap = Ap.p;
-        a.prz[0] = q; a.prz[1] = q + gfc; a.prr = q + 2 * gfc; a.pbb = q + 3 * gfc; a.ppap = q + 4 * gfc;
+        a.lay_partials(parts.p + o_pcg);
         a.st = dst;
     }
     // the state from rot0, its matrices, and the fixed camera's start Exp(fixed0)
@@ -397,12 +348,13 @@ struct RavWork {
         check_launch("rav_pair_kernel");
     }
     void normal_equations(int which) {
-        hipLaunchKernelGGL(rav_cam_kernel, dim3(gcam), blk, 0, st, L, pl.M, (const double *)res.p, (const double *)w[which].p, (const double *)Rm.p,
-                           (const double *)Rf0.p, b.p, diag.p, sinv.p, gauge.p);
+        hipLaunchKernelGGL(rav_cam_kernel, dim3(lists.grid), blk, 0, st, RavLists{lists.L, pl.fixed_slot}, pl.M, (const double *)res.p,
+                           (const double *)w[which].p, (const double *)Rm.p, (const double *)Rf0.p, b.p, diag.p, sinv.p, gauge.p);
         check_launch("rav_cam_kernel");
     }
     void product(int which, const double *p, const BaState *gate) {
-        hipLaunchKernelGGL(rav_camx_kernel, dim3(gcam), blk, 0, st, L, P, (const double *)w[which].p, p, gate, Ap.p, a.ppap);
+        hipLaunchKernelGGL(rav_camx_kernel, dim3(lists.grid), blk, 0, st, RavLists{lists.L, pl.fixed_slot}, P, (const double *)w[which].p, p, gate,
+                           Ap.p, a.ppap);
     }
     void update(const double *xv) {
         hipLaunchKernelGGL(rav_update_kernel, dim3(gup), blk, 0, st, pl.nr, xv, est.p, Rm.p, parts.p + o_step);
@@ -415,25 +367,9 @@ struct RavWork {
         rd.max_p = parts.p + o_bad; rd.max_n = ge; rd.max_out = &dst->gmax;
         hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, st, rd);
     }
-    BaState read_state(const char *what) {
-        check_launch(what);
-        XM_HIP_CHECK(hipMemcpyAsync(hs.h, dst, sizeof(BaState), hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, kStage, what);
-        return *hs.h;
-    }
-    template <class T>
-    void download(std::vector<T> &h, const T *dev, size_t n) {
-        h.resize(n);
-        if (n) XM_HIP_CHECK(hipMemcpyAsync(h.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost, st));
-    }
+    BaState read_state(const char *what) { return xm::read_state(dst, hs, st, cfg.watchdog_s, kStage, what); }
 };
 
-// per pair in input order from the planes of the participating pairs; what takes no part is 0
-void planes_to_pairs(const RavPlan &pl, const std::vector<double> &h, int planes, double *outp) {
-    std::memset(outp, 0, (size_t)planes * pl.npairs * sizeof(double));
-    for (int m = 0; m < pl.M; ++m)
-        for (int c = 0; c < planes; ++c) outp[(size_t)planes * pl.plist[(size_t)m] + c] = h[(size_t)c * pl.M + m];
-}
 // per image from the slots; what is not registered is 0
 void slots_to_images(const RavPlan &pl, const std::vector<double> &h, int per, double *outp) {
     std::memset(outp, 0, (size_t)per * pl.n * sizeof(double));
@@ -444,7 +380,7 @@ void run(const RavInput &in, const RavSettings &cfg, const RavOutput &out, RavOu
     const auto t_start = std::chrono::steady_clock::now();
     const RavPlan pl(in, cfg.fixed_image);
     const int n = pl.n, npairs = pl.npairs, M = pl.M, nr = pl.nr;
-    res.pairs = M; res.registered = nr; res.fixed_image = cfg.fixed_image; res.cams_heavy = pl.nheavy; res.max_incidences = pl.max_inc;
+    res.pairs = M; res.registered = nr; res.fixed_image = cfg.fixed_image; res.cams_heavy = pl.lists.nheavy; res.max_incidences = pl.lists.max_inc;
     if (n > 0) std::memcpy(out.rot_out, in.rot0, (size_t)9 * n * sizeof(double));
     for (int i = 0; i < cfg.max_iters; ++i) out.step_trace[i] = 0.0;
     if (npairs > 0) { std::memset(out.residual, 0, (size_t)3 * npairs * sizeof(double)); std::memset(out.weight, 0, (size_t)npairs * sizeof(double)); }
@@ -464,35 +400,10 @@ void run(const RavInput &in, const RavSettings &cfg, const RavOutput &out, RavOu
     res.seconds_index = secs_since(t_start);
     const auto t_kernels = std::chrono::steady_clock::now();
 
-    BaState *const pst = W.dst;
-    const int gfc = W.gfc;
-    int pcg_last = 8;
-    // PCG from zero: batches enqueued ahead of the host, one read of the state word per batch (as xm_vgcalib.hip)
-    auto pcg = [&](int which, int &iters, bool &capped) {
-        const BaPcg &a = W.a;
-        hipLaunchKernelGGL((ba_pcg_init_kernel<1>), dim3(gfc), dim3(256), 0, st, a);
-        int it = 0, dir_applied = 0;
-        auto enqueue = [&](int upto) {
-            for (; it < upto; ++it) {
-                if (it != dir_applied) hipLaunchKernelGGL((ba_pcg_dir_kernel<1>), dim3(gfc), dim3(256), 0, st, a, it);
-                W.product(which, a.p, pst);
-                hipLaunchKernelGGL((ba_pcg_upd_kernel<1>), dim3(gfc), dim3(256), 0, st, a, it);
-            }
-            hipLaunchKernelGGL((ba_pcg_dir_kernel<1>), dim3(gfc), dim3(256), 0, st, a, it);
-            dir_applied = it;
-        };
-        int target = std::min(kBaMaxPcgIters, std::max(4, pcg_last + 2));
-        BaState s;
-        for (;;) {
-            enqueue(target);
-            s = W.read_state("the PCG");
-            if (s.done || target >= kBaMaxPcgIters) break;
-            target = std::min(kBaMaxPcgIters, target + 8);
-        }
-        iters = s.done ? s.iters : target;
-        capped = !s.done;
-        if (s.done && s.iters > 0) pcg_last = s.iters;
-    };
+    int pcg_last = 8, which = 0;   // which: the weights of the current iteration, read by the PCG's product
+    PcgHooks hooks;
+    hooks.product = [&] { W.product(which, W.a.p, W.dst); };
+    hooks.read = [&] { return W.read_state("the PCG"); };
 
     W.start();
     W.evaluate(0);
@@ -502,13 +413,11 @@ void run(const RavInput &in, const RavSettings &cfg, const RavOutput &out, RavOu
     for (;;) {
         if (iters >= cfg.max_iters) { status = XM_VGR_STOP_ITERATIONS; break; }
         if (s.gmax > 0.0) { status = XM_VGR_STOP_NONFINITE; break; }   // rule 7: a weight of this iteration is not finite
-        const int which = iters & 1;
+        which = iters & 1;
         W.normal_equations(which);
-        int pit = 0;
-        bool capped = false;
-        pcg(which, pit, capped);
-        res.pcg_iters += pit;
-        if (capped) res.pcg_capped++;
+        const PcgResult pr = pcg_solve_batched<1>(W.a, W.gfc, st, pcg_last, hooks);
+        res.pcg_iters += pr.iters;
+        if (pr.capped) res.pcg_capped++;
         W.update(W.x.p);
         W.evaluate(which ^ 1);
         W.reduce();
@@ -522,14 +431,14 @@ void run(const RavInput &in, const RavSettings &cfg, const RavOutput &out, RavOu
     res.seconds_kernels = secs_since(t_kernels);
     const auto t_down = std::chrono::steady_clock::now();
     std::vector<double> hR, hest, hres, hw;
-    W.download(hR, (const double *)W.Rm.p, (size_t)9 * nr); W.download(hest, (const double *)W.est.p, (size_t)3 * nr);
-    W.download(hres, (const double *)W.res.p, (size_t)3 * M);
-    if (used >= 0) W.download(hw, (const double *)W.w[used].p, (size_t)M);
+    download(hR, (const double *)W.Rm.p, (size_t)9 * nr, st); download(hest, (const double *)W.est.p, (size_t)3 * nr, st);
+    download(hres, (const double *)W.res.p, (size_t)3 * M, st);
+    if (used >= 0) download(hw, (const double *)W.w[used].p, (size_t)M, st);
     wait_stream(st, cfg.watchdog_s, kStage, "the download");
     for (int u = 0; u < nr; ++u) std::memcpy(out.rot_out + (size_t)9 * pl.img[(size_t)u], &hR[(size_t)9 * u], 9 * sizeof(double));
     slots_to_images(pl, hest, 3, out.angle_axis_out);
-    planes_to_pairs(pl, hres, 3, out.residual);
-    if (used >= 0) planes_to_pairs(pl, hw, 1, out.weight);
+    planes_to_pairs(pl.plist, npairs, hres, 3, out.residual);
+    if (used >= 0) planes_to_pairs(pl.plist, npairs, hw, 1, out.weight);
     res.stop = status; res.iters = iters;
     res.seconds_download = secs_since(t_down);
 }
@@ -554,9 +463,9 @@ void probe(const RavInput &in, const RavSettings &cfg, const RavProbe &q, hipStr
     W.exponentiate();
     W.evaluate(0);
     std::vector<double> hR, hres, hw, hg, hb, hd, hap, hnew;
-    W.download(hR, (const double *)W.Rm.p, (size_t)9 * nr);
-    W.download(hres, (const double *)W.res.p, (size_t)3 * M);
-    W.download(hw, (const double *)W.w[0].p, (size_t)M);
+    download(hR, (const double *)W.Rm.p, (size_t)9 * nr, st);
+    download(hres, (const double *)W.res.p, (size_t)3 * M, st);
+    download(hw, (const double *)W.w[0].p, (size_t)M, st);
     if (q.weight_in) {
         hwin.resize((size_t)M);
         for (int m = 0; m < M; ++m) hwin[(size_t)m] = q.weight_in[pl.plist[(size_t)m]];
@@ -567,13 +476,13 @@ void probe(const RavInput &in, const RavSettings &cfg, const RavProbe &q, hipStr
     W.update(W.pv.p);
     W.reduce();
     const BaState s = W.read_state("the probe");
-    W.download(hg, (const double *)W.gauge.p, 3); W.download(hb, (const double *)W.b.p, (size_t)3 * nr);
-    W.download(hd, (const double *)W.diag.p, (size_t)nr); W.download(hap, (const double *)W.Ap.p, (size_t)3 * nr);
-    W.download(hnew, (const double *)W.est.p, (size_t)3 * nr);
+    download(hg, (const double *)W.gauge.p, 3, st); download(hb, (const double *)W.b.p, (size_t)3 * nr, st);
+    download(hd, (const double *)W.diag.p, (size_t)nr, st); download(hap, (const double *)W.Ap.p, (size_t)3 * nr, st);
+    download(hnew, (const double *)W.est.p, (size_t)3 * nr, st);
     wait_stream(st, cfg.watchdog_s, kStage, "the probe's download");
     if (q.rot) slots_to_images(pl, hR, 9, q.rot);
-    if (q.residual) planes_to_pairs(pl, hres, 3, q.residual);
-    if (q.weight) planes_to_pairs(pl, hw, 1, q.weight);
+    if (q.residual) planes_to_pairs(pl.plist, npairs, hres, 3, q.residual);
+    if (q.weight) planes_to_pairs(pl.plist, npairs, hw, 1, q.weight);
     if (q.gauge) std::memcpy(q.gauge, hg.data(), 3 * sizeof(double));
     if (q.rhs) slots_to_images(pl, hb, 3, q.rhs);
     if (q.diagonal) slots_to_images(pl, hd, 1, q.diagonal);

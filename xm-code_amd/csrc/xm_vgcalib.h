@@ -3,7 +3,7 @@
 // with XM_VGC_UPDATE_CONFIG, step 0 in front of it (processors/view_graph_manipulation.cc:170-231, math/two_view_geometry.cc:41-55).
 //
 // Host: the checks (xm_capi.hip), the participating pairs in input order, the unknown of every camera (-1: constant), the incidence lists
-// camera -> (pair, side) by a stable counting sort in input order, heavy cameras (more than kVgcLightIncidences incidences) first.
+// camera -> (pair, side) of xm_pair_lists.h over the free cameras, a same-camera pair listed once.
 //
 // Launches, all on the default stream and all deterministic in what they write (no floating-point atomic, no atomic at all):
 //   vgc_config_kernel     XM_VGC_UPDATE_CONFIG: one thread per pair that flips from F to E: F = K2^-T [t]x R K1^-1 (rule 7)
@@ -26,12 +26,13 @@
 #include <cstdint>
 
 #include "../../include/xm_amd.h"
+#include "xm_pair_lists.h"
 #include "xm_solver.h"
 
 namespace xm {
 
-constexpr int kVgcThreads = 256;            // threads per workgroup
-constexpr int kVgcLightIncidences = 64;     // most incidences of a camera that one thread walks; above: a workgroup of its own
+constexpr int kVgcThreads = kPairListThreads;          // threads per workgroup
+constexpr int kVgcLightIncidences = kPairListLight;    // most incidences of a camera that one thread walks
 constexpr int kVgcMaxPcgIters = 500;         // most PCG iterations of one solve (xm_lm_shared.h: kBaMaxPcgIters)
 constexpr int kVgcSweeps = 30;              // most sweeps of the one-sided Jacobi SVD (a 3 x 3 matrix converges in 5 to 8)
 

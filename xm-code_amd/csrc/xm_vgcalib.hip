@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "xm_lm_shared.h"
+#include "xm_pair_lists.h"
 #include "xm_stage.h"
 
 // every product and every sum of the contract is rounded on its own
@@ -21,7 +22,6 @@ namespace {
 constexpr const char *kStage = "xm_view_graph_calibrate";
 constexpr int kT = kVgcThreads;
 static_assert(kVgcMaxPcgIters == kBaMaxPcgIters, "the limit reported is the one the PCG runs to");
-constexpr int kFlatCap = 1024;   // most workgroups of a grid-stride launch
 
 // ---- rule 7: F = K2^-T [t]x R K1^-1 for the pairs that flip, the inverse of a pinhole K in closed form
 __global__ __launch_bounds__(kT) void vgc_config_kernel(int nflip, const int32_t *__restrict__ flip, const int32_t *__restrict__ ca,
@@ -221,52 +221,15 @@ __global__ __launch_bounds__(kT) void vgc_cand_kernel(VgcPairs P, const double *
     if (threadIdx.x == 0) { parts[blockIdx.x] = cost; parts[gridDim.x + blockIdx.x] = model; }
 }
 
-struct VgcLists {   // camera -> (pair, side) of the free cameras: side 0 the camera is fi's, 1 fj's, 2 both (a same-camera pair)
-    int nfree, nheavy;
-    const int32_t *order;    // nfree unknowns: the heavy ones first, each group in camera order
-    const int64_t *ptr;      // nfree + 1, by unknown
-    const int32_t *pair;
-    const uint8_t *side;
-};
-// which unknown this thread works on and which of its incidences: a workgroup per heavy camera, a thread per light one
-struct VgcWalk {
-    int u;
-    int64_t e, e_end, step;
-    bool heavy;
-};
-__device__ __forceinline__ VgcWalk vgc_walk(const VgcLists &L) {
-    VgcWalk w;
-    w.heavy = (int)blockIdx.x < L.nheavy;
-    const int64_t slot = w.heavy ? (int64_t)blockIdx.x : (int64_t)L.nheavy + ((int64_t)blockIdx.x - L.nheavy) * kT + threadIdx.x;
-    w.u = slot < L.nfree ? L.order[slot] : -1;
-    w.e = 0; w.e_end = 0; w.step = 1;
-    if (w.u >= 0) {
-        w.e = L.ptr[w.u] + (w.heavy ? threadIdx.x : 0); w.e_end = L.ptr[w.u + 1]; w.step = w.heavy ? kT : 1;
-    }
-    return w;
-}
-// sum of K values over a heavy camera's workgroup: DPP tree per wavefront, the four wavefront sums in a fixed order; valid in thread 0
-template <int K>
-__device__ __forceinline__ void vgc_heavy_sum(double (&acc)[K], double (*part)[K]) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) part[threadIdx.x >> 6][k] = acc[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
-}
-
+// the lists of the free cameras (xm_pair_lists.h): side 0 the camera is fi's, 1 fj's, 2 both (a same-camera pair)
 // gradient g = J^T r and diagonal of J^T J per free camera; b = -g, sinv = 1 / (diag + mu clamp(diag)); |g|_inf per workgroup
-__global__ __launch_bounds__(kT) void vgc_cam_kernel(VgcLists L, int M_, const double *__restrict__ rec, double mu, double *__restrict__ grad,
+__global__ __launch_bounds__(kT) void vgc_cam_kernel(PairLists L, int M_, const double *__restrict__ rec, double mu, double *__restrict__ grad,
                                                      double *__restrict__ diag, double *__restrict__ b, double *__restrict__ sinv,
                                                      double *__restrict__ gmaxp) {
     __shared__ double part[4][2];
     __shared__ double shm[4];
     const size_t M = (size_t)M_;
-    const VgcWalk w = vgc_walk(L);
+    const PairWalk w = pair_walk(L);
     double acc[2] = {0.0, 0.0};
     for (int64_t e = w.e; e < w.e_end; e += w.step) {
         const int m = L.pair[e];
@@ -275,7 +238,7 @@ __global__ __launch_bounds__(kT) void vgc_cam_kernel(VgcLists L, int M_, const d
         acc[0] += c0 * rec[m] + c1 * rec[M + m];
         acc[1] += c0 * c0 + c1 * c1;
     }
-    if (w.heavy) vgc_heavy_sum<2>(acc, part);
+    if (w.heavy) pair_heavy_sum<2>(acc, part);
     const bool writer = w.u >= 0 && (!w.heavy || threadIdx.x == 0);
     if (writer) {
         const double dd = acc[1] + mu * clamp_diag(acc[1]);
@@ -286,14 +249,14 @@ __global__ __launch_bounds__(kT) void vgc_cam_kernel(VgcLists L, int M_, const d
 }
 
 // Ap = (J^T J + mu clamp(diag)) p in one pass over the incidence lists; <p, Ap> per workgroup.  gate: the PCG's state word (done: nothing to do)
-__global__ __launch_bounds__(kT) void vgc_camx_kernel(VgcLists L, VgcPairs P, const double *__restrict__ rec, const double *__restrict__ diag, double mu,
+__global__ __launch_bounds__(kT) void vgc_camx_kernel(PairLists L, VgcPairs P, const double *__restrict__ rec, const double *__restrict__ diag, double mu,
                                                       const double *__restrict__ p, const BaState *__restrict__ gate, double *__restrict__ Ap,
                                                       double *__restrict__ ppap) {
     __shared__ double part[4][1];
     __shared__ double sh[4];
     if (gate != nullptr && gate->done) return;
     const size_t M = (size_t)P.M;
-    const VgcWalk w = vgc_walk(L);
+    const PairWalk w = pair_walk(L);
     double acc[1] = {0.0};
     for (int64_t e = w.e; e < w.e_end; e += w.step) {
         const int m = L.pair[e];
@@ -304,7 +267,7 @@ __global__ __launch_bounds__(kT) void vgc_camx_kernel(VgcLists L, VgcPairs P, co
         const double t0 = j00 * xa + j01 * xb, t1 = j10 * xa + j11 * xb;
         acc[0] += (second ? j01 : j00) * t0 + (second ? j11 : j10) * t1;
     }
-    if (w.heavy) vgc_heavy_sum<1>(acc, part);
+    if (w.heavy) pair_heavy_sum<1>(acc, part);
     double pap = 0.0;
     if (w.u >= 0 && (!w.heavy || threadIdx.x == 0)) {
         const double v = acc[0] + (mu * clamp_diag(diag[w.u])) * p[w.u];
@@ -357,15 +320,13 @@ __global__ __launch_bounds__(kT) void vgc_finish_kernel(int ncams, const int32_t
     }
 }
 
-inline int flat_grid_of(int64_t items) { return (int)std::max<int64_t>(1, std::min<int64_t>((items + kT - 1) / kT, kFlatCap)); }
-
 // What the host prepares from the caller's arrays: the effective models (rule 7), the participating pairs, the unknowns, the lists
 struct VgcPlan {
-    int ncams = 0, npairs = 0, M = 0, nfree = 0, nheavy = 0;
-    int64_t same = 0, constant = 0, max_inc = 0;
-    std::vector<int32_t> model, flip, flip_ca, flip_cb, plist, ca, cb, ua, ub, uslot, cam_of, order, inc_pair;
-    std::vector<uint8_t> touched, inc_side;
-    std::vector<int64_t> inc_ptr;
+    int ncams = 0, npairs = 0, M = 0, nfree = 0;
+    int64_t same = 0, constant = 0;
+    std::vector<int32_t> model, flip, flip_ca, flip_cb, plist, ca, cb, ua, ub, uslot, cam_of;
+    std::vector<uint8_t> touched;
+    PairListsHost lists;
 
     VgcPlan(const VgcInput &in, bool update_config) {
         ncams = (int)in.ncams; npairs = (int)in.npairs;
@@ -406,29 +367,8 @@ struct VgcPlan {
         }
         nfree = (int)cam_of.size();
         ua.resize((size_t)M); ub.resize((size_t)M);
-        inc_ptr.assign((size_t)nfree + 1, 0);
-        for (int m = 0; m < M; ++m) {
-            ua[(size_t)m] = uslot[(size_t)ca[(size_t)m]]; ub[(size_t)m] = uslot[(size_t)cb[(size_t)m]];
-            if (ua[(size_t)m] >= 0) inc_ptr[(size_t)ua[(size_t)m] + 1]++;
-            if (ub[(size_t)m] >= 0 && ca[(size_t)m] != cb[(size_t)m]) inc_ptr[(size_t)ub[(size_t)m] + 1]++;
-        }
-        for (int u = 0; u < nfree; ++u) {
-            max_inc = std::max(max_inc, inc_ptr[(size_t)u + 1]);
-            inc_ptr[(size_t)u + 1] += inc_ptr[(size_t)u];
-        }
-        inc_pair.resize((size_t)inc_ptr[(size_t)nfree]); inc_side.resize(inc_pair.size());
-        std::vector<int64_t> fill(inc_ptr.begin(), inc_ptr.end() - 1);
-        for (int m = 0; m < M; ++m) {   // stable: a camera's incidences stay in input order
-            const bool sm = ca[(size_t)m] == cb[(size_t)m];
-            if (ua[(size_t)m] >= 0) { const int64_t e = fill[(size_t)ua[(size_t)m]]++; inc_pair[(size_t)e] = m; inc_side[(size_t)e] = sm ? 2 : 0; }
-            if (ub[(size_t)m] >= 0 && !sm) { const int64_t e = fill[(size_t)ub[(size_t)m]]++; inc_pair[(size_t)e] = m; inc_side[(size_t)e] = 1; }
-        }
-        std::vector<int32_t> light;
-        for (int u = 0; u < nfree; ++u) {
-            if (inc_ptr[(size_t)u + 1] - inc_ptr[(size_t)u] > kVgcLightIncidences) order.push_back(u); else light.push_back(u);
-        }
-        nheavy = (int)order.size();
-        order.insert(order.end(), light.begin(), light.end());
+        for (int m = 0; m < M; ++m) { ua[(size_t)m] = uslot[(size_t)ca[(size_t)m]]; ub[(size_t)m] = uslot[(size_t)cb[(size_t)m]]; }
+        lists = build_pair_lists(nfree, ua, ub, kVgcLightIncidences, true);
     }
 };
 
@@ -438,17 +378,16 @@ struct VgcWork {
     const VgcSettings &cfg;
     hipStream_t st;
     DevBuf<double> F, pp, focal0, d, f[2], rraw, rec, grad, diag, b, sinv, x, r, z, pv, Ap, parts, fout, fest;
-    DevBuf<int32_t> plist, ca, cb, ua, ub, uslot, cam_of, order, inc_pair, flip, flip_ca, flip_cb, cstat, pbad, state_buf;
-    DevBuf<uint8_t> inc_side, touched;
-    DevBuf<int64_t> inc_ptr;
+    DevBuf<int32_t> plist, ca, cb, ua, ub, uslot, cam_of, flip, flip_ca, flip_cb, cstat, pbad, state_buf;
+    DevBuf<uint8_t> touched;
+    PairListsDev lists;
     DevBuf<double> Rrel, trel;   // rule 7 only
     const double *rrel_p = nullptr, *trel_p = nullptr;
     BaState *dst = nullptr;
     Pinned<BaState> hs;
-    int ge = 1, gfc = 1, gcam = 1, cur = 0;
+    int ge = 1, gfc = 1, cur = 0;
     size_t o_eval = 0, o_gmax = 0, o_pcg = 0, o_step = 0, o_cand = 0;
     VgcPairs P{};
-    VgcLists L{};
     BaPcg a{};
     const dim3 blk{kT};
 
@@ -462,9 +401,8 @@ struct VgcWork {
         upload(plist, pl.plist.data(), M, st); upload(ca, pl.ca.data(), M, st); upload(cb, pl.cb.data(), M, st);
         upload(ua, pl.ua.data(), M, st); upload(ub, pl.ub.data(), M, st);
         upload(uslot, pl.uslot.data(), nc, st); upload(touched, pl.touched.data(), nc, st);
-        upload(cam_of, pl.cam_of.data(), nf, st); upload(order, pl.order.data(), nf, st);
-        upload(inc_ptr, pl.inc_ptr.data(), nf + 1, st);
-        upload(inc_pair, pl.inc_pair.data(), pl.inc_pair.size(), st); upload(inc_side, pl.inc_side.data(), pl.inc_side.size(), st);
+        upload(cam_of, pl.cam_of.data(), nf, st);
+        lists.upload_from(pl.lists, pl.nfree, st);
         upload(flip, pl.flip.data(), pl.flip.size(), st); upload(flip_ca, pl.flip_ca.data(), pl.flip.size(), st);
         upload(flip_cb, pl.flip_cb.data(), pl.flip.size(), st);
         d.alloc(8 * M, false); rraw.alloc(2 * M, false); rec.alloc(6 * M, false);
@@ -474,16 +412,14 @@ struct VgcWork {
         dst = reinterpret_cast<BaState *>(state_buf.p);
         ge = (int)std::max<size_t>(1, (M + kT - 1) / kT);
         gfc = flat_grid_of((int64_t)nf);
-        gcam = std::max(1, pl.nheavy + (pl.nfree - pl.nheavy + kT - 1) / kT);
+        const int gcam = lists.grid;
         // partials: eval (ge) | gmax (gcam) | PCG (4 gfc + gcam) | step (2 gfc) | candidate (2 ge)
         o_eval = 0; o_gmax = (size_t)ge; o_pcg = o_gmax + gcam; o_step = o_pcg + 4 * (size_t)gfc + gcam; o_cand = o_step + 2 * (size_t)gfc;
         fresh(parts, o_cand + 2 * (size_t)ge, 0, st);
         P.M = pl.M; P.ca = ca.p; P.cb = cb.p; P.ua = ua.p; P.ub = ub.p; P.d = d.p;
-        L.nfree = pl.nfree; L.nheavy = pl.nheavy; L.order = order.p; L.ptr = inc_ptr.p; L.pair = inc_pair.p; L.side = inc_side.p;
-        double *q = parts.p + o_pcg;
         a.n = pl.nfree; a.grid = gfc; a.cgrid = gcam; a.tol2 = 1e-24;   // relative residual 1e-12
         a.b = b.p; a.sinv = sinv.p; a.ustar = nullptr; a.x = x.p; a.r = r.p; a.z = z.p; a.p = pv.p; a.Ap = Ap.p;
-        a.prz[0] = q; a.prz[1] = q + gfc; a.prr = q + 2 * gfc; a.pbb = q + 3 * gfc; a.ppap = q + 4 * gfc;
+        a.lay_partials(parts.p + o_pcg);
         a.st = dst;
     }
     void config() {
@@ -504,23 +440,20 @@ struct VgcWork {
         check_launch("vgc_setup_kernel");
     }
     void reduce(const BaReduce &rd) { hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, st, rd); }
-    BaState read_state(const char *what) {
-        check_launch(what);
-        XM_HIP_CHECK(hipMemcpyAsync(hs.h, dst, sizeof(BaState), hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, kStage, what);
-        return *hs.h;
-    }
+    BaState read_state(const char *what) { return xm::read_state(dst, hs, st, cfg.watchdog_s, kStage, what); }
     // records, gradient and diagonal at the current focals for the damping mu; cost and |J^T r|_inf to the state word
     void linearise(double mu) {
         hipLaunchKernelGGL(vgc_eval_kernel, dim3(ge), blk, 0, st, P, (const double *)f[cur].p, cfg.loss_scale, rraw.p, rec.p, parts.p + o_eval);
-        hipLaunchKernelGGL(vgc_cam_kernel, dim3(gcam), blk, 0, st, L, pl.M, (const double *)rec.p, mu, grad.p, diag.p, b.p, sinv.p, parts.p + o_gmax);
+        hipLaunchKernelGGL(vgc_cam_kernel, dim3(lists.grid), blk, 0, st, lists.L, pl.M, (const double *)rec.p, mu, grad.p, diag.p, b.p, sinv.p,
+                           parts.p + o_gmax);
         BaReduce rd{};
         rd.sum_p[0] = parts.p + o_eval; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->cost;
-        rd.max_p = parts.p + o_gmax; rd.max_n = gcam; rd.max_out = &dst->gmax;
+        rd.max_p = parts.p + o_gmax; rd.max_n = lists.grid; rd.max_out = &dst->gmax;
         reduce(rd);
     }
     void product(const double *p, const BaState *gate, double mu) {
-        hipLaunchKernelGGL(vgc_camx_kernel, dim3(gcam), blk, 0, st, L, P, (const double *)rec.p, (const double *)diag.p, mu, p, gate, Ap.p, a.ppap);
+        hipLaunchKernelGGL(vgc_camx_kernel, dim3(lists.grid), blk, 0, st, lists.L, P, (const double *)rec.p, (const double *)diag.p, mu, p, gate, Ap.p,
+                           a.ppap);
     }
     void candidate() {
         const int nx = cur ^ 1;
@@ -535,26 +468,14 @@ struct VgcWork {
         rd.sum_p[3] = parts.p + o_step + gfc; rd.sum_n[3] = gfc; rd.sum_out[3] = &dst->x2[0];
         reduce(rd);
     }
-    template <class T>
-    void download(std::vector<T> &h, const T *dev, size_t n) {
-        h.resize(n);
-        if (n) XM_HIP_CHECK(hipMemcpyAsync(h.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost, st));
-    }
 };
-
-// per pair in input order from the planes of the participating pairs; what takes no part is 0
-void planes_to_pairs(const VgcPlan &pl, const std::vector<double> &h, int planes, double *outp) {
-    std::memset(outp, 0, (size_t)planes * pl.npairs * sizeof(double));
-    for (int m = 0; m < pl.M; ++m)
-        for (int c = 0; c < planes; ++c) outp[(size_t)planes * pl.plist[(size_t)m] + c] = h[(size_t)c * pl.M + m];
-}
 
 void run(const VgcInput &in, const VgcSettings &cfg, const VgcOutput &out, VgcOutcome &res, hipStream_t st) {
     const auto t_start = std::chrono::steady_clock::now();
     const VgcPlan pl(in, cfg.update_config);
     const int ncams = pl.ncams, npairs = pl.npairs, M = pl.M;
     res.pairs = M; res.pairs_same = pl.same; res.cams_free = pl.nfree; res.cams_constant = pl.constant; res.pairs_flipped = (int64_t)pl.flip.size();
-    res.cams_heavy = pl.nheavy; res.max_incidences = pl.max_inc;
+    res.cams_heavy = pl.lists.nheavy; res.max_incidences = pl.lists.max_inc;
     // what holds whether or not anything is optimised
     auto write_inputs_through = [&](const double *F_now) {
         for (int c = 0; c < ncams; ++c) {
@@ -584,7 +505,7 @@ void run(const VgcInput &in, const VgcSettings &cfg, const VgcOutput &out, VgcOu
     W.config();
     std::vector<double> hF;
     if (pl.nfree == 0) {   // rule 5 behind rule 7: the pairs are rewritten, nothing is refined, no pair is invalidated
-        W.download(hF, (const double *)W.F.p, (size_t)9 * npairs);
+        download(hF, (const double *)W.F.p, (size_t)9 * npairs, st);
         wait_stream(st, cfg.watchdog_s, kStage, "the rewritten pairs");
         res.seconds_kernels = secs_since(t_kernels);
         write_inputs_through(hF.data());
@@ -593,34 +514,11 @@ void run(const VgcInput &in, const VgcSettings &cfg, const VgcOutput &out, VgcOu
     }
     W.setup();
 
-    BaState *const pst = W.dst;
-    const int gfc = W.gfc;
     int pcg_last = 8;
-    // PCG from zero: batches enqueued ahead of the host, one read of the state word per batch (as xm_gp.hip)
-    auto pcg = [&](double mu, int &iters) {
-        const BaPcg &a = W.a;
-        hipLaunchKernelGGL((ba_pcg_init_kernel<1>), dim3(gfc), dim3(256), 0, st, a);
-        int it = 0, dir_applied = 0;
-        auto enqueue = [&](int upto) {
-            for (; it < upto; ++it) {
-                if (it != dir_applied) hipLaunchKernelGGL((ba_pcg_dir_kernel<1>), dim3(gfc), dim3(256), 0, st, a, it);
-                W.product(a.p, pst, mu);
-                hipLaunchKernelGGL((ba_pcg_upd_kernel<1>), dim3(gfc), dim3(256), 0, st, a, it);
-            }
-            hipLaunchKernelGGL((ba_pcg_dir_kernel<1>), dim3(gfc), dim3(256), 0, st, a, it);
-            dir_applied = it;
-        };
-        int target = std::min(kBaMaxPcgIters, std::max(4, pcg_last + 2));
-        BaState s;
-        for (;;) {
-            enqueue(target);
-            s = W.read_state("the PCG");
-            if (s.done || target >= kBaMaxPcgIters) break;
-            target = std::min(kBaMaxPcgIters, target + 8);
-        }
-        iters = s.done ? s.iters : target;
-        if (s.done && s.iters > 0) pcg_last = s.iters;
-    };
+    double mu = 0.0;   // the damping of the current linearisation: the PCG's product reads it
+    PcgHooks hooks;
+    hooks.product = [&] { W.product(W.a.p, W.dst, mu); };
+    hooks.read = [&] { return W.read_state("the PCG"); };
 
     // Ceres's Levenberg-Marquardt rules as xm_ba.hip and xm_gp.hip implement them
     double radius = 1e4, nu = 2.0, Fc = 0.0, gmax = 0.0;
@@ -629,7 +527,7 @@ void run(const VgcInput &in, const VgcSettings &cfg, const VgcOutput &out, VgcOu
     int64_t pcg_total = 0;
     bool fresh_pt = true, first = true;
     for (;;) {
-        const double mu = 1.0 / radius;
+        mu = 1.0 / radius;
         W.linearise(mu);
         if (fresh_pt) {
             const BaState s = W.read_state("the cost and gradient");
@@ -645,9 +543,7 @@ void run(const VgcInput &in, const VgcSettings &cfg, const VgcOutput &out, VgcOu
             if (gmax <= cfg.gradient_tol) { status = XM_BA_CONVERGED_GRADIENT; break; }
         }
         if (iters >= cfg.max_iters) { status = XM_BA_MAX_ITERATIONS; break; }
-        int pit = 0;
-        pcg(mu, pit);
-        pcg_total += pit;
+        pcg_total += pcg_solve_batched<1>(W.a, W.gfc, st, pcg_last, hooks).iters;
         W.candidate();
         const BaState s = W.read_state("the candidate's cost");
         iters++;
@@ -688,11 +584,11 @@ void run(const VgcInput &in, const VgcSettings &cfg, const VgcOutput &out, VgcOu
     const auto t_down = std::chrono::steady_clock::now();
     std::vector<double> hfout, hfest, hr, hd;
     std::vector<int32_t> hcs, hbad;
-    W.download(hfout, (const double *)W.fout.p, (size_t)ncams); W.download(hfest, (const double *)W.fest.p, (size_t)ncams);
-    W.download(hcs, (const int32_t *)W.cstat.p, (size_t)ncams); W.download(hbad, (const int32_t *)W.pbad.p, (size_t)M);
-    W.download(hr, (const double *)W.rraw.p, 2 * (size_t)M);
-    if (out.d_out) W.download(hd, (const double *)W.d.p, 8 * (size_t)M);
-    if (out.F_out) W.download(hF, (const double *)W.F.p, (size_t)9 * npairs);
+    download(hfout, (const double *)W.fout.p, (size_t)ncams, st); download(hfest, (const double *)W.fest.p, (size_t)ncams, st);
+    download(hcs, (const int32_t *)W.cstat.p, (size_t)ncams, st); download(hbad, (const int32_t *)W.pbad.p, (size_t)M, st);
+    download(hr, (const double *)W.rraw.p, 2 * (size_t)M, st);
+    if (out.d_out) download(hd, (const double *)W.d.p, 8 * (size_t)M, st);
+    if (out.F_out) download(hF, (const double *)W.F.p, (size_t)9 * npairs, st);
     wait_stream(st, cfg.watchdog_s, kStage, "the download");
     write_inputs_through(out.F_out ? hF.data() : in.F);
     for (int c = 0; c < ncams; ++c) {
@@ -700,8 +596,8 @@ void run(const VgcInput &in, const VgcSettings &cfg, const VgcOutput &out, VgcOu
         out.refined[c] = hcs[(size_t)c] == XM_VGC_CAM_REFINED ? 1 : 0;
         if (hcs[(size_t)c] == XM_VGC_CAM_REJECTED) res.cams_rejected++;
     }
-    planes_to_pairs(pl, hr, 2, out.residual);
-    if (out.d_out) planes_to_pairs(pl, hd, 8, out.d_out);
+    planes_to_pairs(pl.plist, npairs, hr, 2, out.residual);
+    if (out.d_out) planes_to_pairs(pl.plist, npairs, hd, 8, out.d_out);
     for (int m = 0; m < M; ++m)
         if (hbad[(size_t)m]) { out.pair_status[pl.plist[(size_t)m]] = XM_VGC_TWO_VIEW_ERROR; res.pairs_invalidated++; }
     res.stop = status; res.iters = iters; res.accepted = accepted; res.pcg_iters = pcg_total; res.final_cost = Fc; res.trace_len = trace_n;
@@ -733,13 +629,13 @@ void probe(const VgcInput &in, const VgcSettings &cfg, const VgcProbe &q, hipStr
     W.product(W.pv.p, nullptr, q.mu);
     const BaState s = W.read_state("the probe");
     std::vector<double> hd, hr, hrec, hg, hdg, hap;
-    W.download(hd, (const double *)W.d.p, 8 * (size_t)M); W.download(hr, (const double *)W.rraw.p, 2 * (size_t)M);
-    W.download(hrec, (const double *)W.rec.p, 6 * (size_t)M); W.download(hg, (const double *)W.grad.p, (size_t)pl.nfree);
-    W.download(hdg, (const double *)W.diag.p, (size_t)pl.nfree); W.download(hap, (const double *)W.Ap.p, (size_t)pl.nfree);
+    download(hd, (const double *)W.d.p, 8 * (size_t)M, st); download(hr, (const double *)W.rraw.p, 2 * (size_t)M, st);
+    download(hrec, (const double *)W.rec.p, 6 * (size_t)M, st); download(hg, (const double *)W.grad.p, (size_t)pl.nfree, st);
+    download(hdg, (const double *)W.diag.p, (size_t)pl.nfree, st); download(hap, (const double *)W.Ap.p, (size_t)pl.nfree, st);
     wait_stream(st, cfg.watchdog_s, kStage, "the probe's download");
-    if (q.d) planes_to_pairs(pl, hd, 8, q.d);
-    if (q.residual) planes_to_pairs(pl, hr, 2, q.residual);
-    if (q.record) planes_to_pairs(pl, hrec, 6, q.record);
+    if (q.d) planes_to_pairs(pl.plist, npairs, hd, 8, q.d);
+    if (q.residual) planes_to_pairs(pl.plist, npairs, hr, 2, q.residual);
+    if (q.record) planes_to_pairs(pl.plist, npairs, hrec, 6, q.record);
     if (q.cost) *q.cost = s.cost;
     for (int u = 0; u < pl.nfree; ++u) {
         const int32_t c = pl.cam_of[(size_t)u];
