@@ -202,6 +202,10 @@ typedef struct {
                                      * loop's round trips are hidden behind the speculative start of the next tCG: 41.7 against 42.4 us per tCG iteration on
                                      * the Venice-1778-size problem); in block-CSR storage the device-driven form is the faster one (34.7 against 35.5 us at
                                      * 13 682 cameras) and the default.  XM_FLAG_HOST_OUTER wins over this flag */
+#define XM_FLAG_TCG_THREE_LAUNCH 256u /* keep the truncated CG's iteration at three launches (product sweep, per-camera sums, step) where the default is two:
+                                     * on one GPU with the host-driven outer iteration and the f64 symmetric dense pair at ranks 3 and 4, the sweep of
+                                     * iteration i carries the step of iteration i - 1 in its own launch and forms its product input itself.  Same bits
+                                     * either way (xm_ctx_tcg_two_launch says which form a solve ran) */
 #define XM_FLAG_WARM_R        16u   /* XM_MODE_REBUTTLE: start the rank-3 stage from opt.R_ini instead of the identity stack.  The reference
                                        reads R_ini.bin and then overwrites it with the identity (XM_main.cu:41,95-103); this flag honours it,
                                        which is what makes the second solve of the XM^2 loop cheap */
@@ -1014,6 +1018,9 @@ int xm_schur_dense_limits(int64_t out[3]);
  * preconditioned CG on the matrix-free VT (no N^2 array) -- and, for the CG form, stats = {products so far, inner CG iterations
  * so far, products that stopped at the iteration cap instead of at the tolerance 1e-13} and the relative residual of the last product. */
 int xm_ctx_schur_info(xm_ctx_t *ctx, int *uses_cg, int64_t stats[3], double *last_relres);
+/* *count = trust regions (rank levels) of the context's LAST xm_ctx_solve whose truncated CG ran in the two-launch form (XM_FLAG_TCG_THREE_LAUNCH,
+ * or a configuration that form does not cover: 0).  Single-GPU contexts; XM_ERR_ARG otherwise.  (A getter, not a field: xm_result_t keeps its size.) */
+int xm_ctx_tcg_two_launch(xm_ctx_t *ctx, int *count);
 /* ... and the preconditioner of the CG form: *kind = -1 no CG form (dense inverse, or not a matrix-free context), 0 Jacobi (schur_solver 2 or
  * auto), 1 two-level (schur_solver 3; *aggregates = their number n_c, *block = cameras per aggregate).  aggregates / block may be NULL. */
 int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int *block);

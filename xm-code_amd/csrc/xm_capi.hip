@@ -343,6 +343,13 @@ int xm_schur_dense_limits(int64_t out[3]) {
     return XM_OK;
     XM_CATCH
 }
+int xm_ctx_tcg_two_launch(xm_ctx_t *ctx, int *count) {
+    XM_TRY
+    if (!ctx || !ctx->impl || !count) throw xm::Error(XM_ERR_ARG, "xm_ctx_tcg_two_launch: single-GPU context and a non-null output needed");
+    *count = ctx->impl->tcg_two_launch_count();
+    return XM_OK;
+    XM_CATCH
+}
 int xm_ctx_schur_info(xm_ctx_t *ctx, int *uses_cg, int64_t stats[3], double *last_relres) {
     XM_TRY
     if (!ctx || !ctx->impl || !uses_cg) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_info: single-GPU context and a non-null output needed");

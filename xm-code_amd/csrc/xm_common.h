@@ -253,6 +253,8 @@ void launch_outer_step(int o, int polar, const OuterStepArgs &A, int grid, hipSt
 struct TcgParity {
     TcgScal *scal_cur, *scal_next;
     double *ps_cur, *ps_next, *rs_cur, *rs_next;
+    double *pR_cur, *pR_next, *rR_cur, *rR_next;   // p and r of the step that ends this iteration: read at cur, written at next (one buffer where the
+                                                   // device drives the outer iteration: its step launch updates them in place)
     size_t chunk, b_off;
     double *pcur;         // gather base of this parity: what cg_step reads its sums from
     double *parts;        // this rank's [3 nA | nB] inside it: the Hessian epilogue writes the first part
@@ -275,10 +277,10 @@ struct TcgInitArgs {
 };
 struct CgStepArgs {
     int nloc;
-    TcgParity v;                       // scal, ps, rs cur -> next; sums read at v.pcur, |r|^2 partials written to v.partsB_out
+    TcgParity v;                       // scal, p, r cur -> next; sums read at v.pcur, |r|^2 partials written to v.partsB_out
     int nA, nB, world;                 // partial counts per rank; grid = nB
     const double *HpR, *Hps, *R, *s;
-    double *pR, *vR, *vs, *HvR, *Hvs, *rR;   // HvR == nullptr: XM_FLAG_MODEL_RECURRENCE
+    double *vR, *vs, *HvR, *Hvs;       // HvR == nullptr: XM_FLAG_MODEL_RECURRENCE
     double *Wloc, *Wpad;               // Wpad: single rank only
     unsigned long long *hstat;
     int64_t mat;
@@ -286,6 +288,20 @@ struct CgStepArgs {
     int grouping;
     PeerXchg xchg;
 };
+
+// Step i - 1 of a truncated CG as the symmetric sweep of iteration i carries it (two-launch form, launch_qw_sym with a step): the step's
+// workgroups are the grid rows behind the sweep's gy, and every sweep workgroup forms its part of the product input from the same vectors.
+struct TcgFuse {
+    int gy, nA, nB, grp;
+    const TcgScal *scal_cur;
+    TcgScal *scal_next;
+    const double *parts;               // [3 nA | nB] partial sums of iteration i - 1
+    const double *HpR, *Hps, *R, *s, *pR_cur, *ps_cur, *rR_cur, *rs_cur;
+    double *pR_next, *ps_next, *rR_next, *rs_next, *vR, *vs, *HvR, *Hvs, *Wloc, *partsB_out;
+    unsigned long long *hstat;
+};
+// doubles of the product input a sweep workgroup derives for its 4 K steps (LDS): a plan with longer chunks keeps the three-launch form
+constexpr int kSvDeriveRows = 768;
 
 // ---- launchers implemented in xm_kernels.hip -------------------------------------------------------------------
 // Q*W products.  grid = ceil(nloc / kQwWaves).  Q rows are the local cameras' rows; W has `ld` rows (all cameras).
@@ -326,7 +342,10 @@ struct SymvWork {
 // symmetric half-traffic products.  Every launcher throws XM_ERR_ARG unless `work` is allocated for a.nloc, ld and a rank >= o.
 void launch_qw_sym_traced(int o, const double *Q, int64_t ld, const double *W, const CamArgs &a, SymvWork &work, unsigned long long *trace, hipStream_t st);
 void launch_qw_sym(int o, int epi, const double *Q, int64_t ld, const double *W, double alpha, const CamArgs &a, SymvWork &work, hipStream_t st,
-                   int rev = 0);   // rev: sweep direction, alternated by the caller between consecutive products
+                   int rev = 0, const CgStepArgs *step = nullptr);   // rev: sweep direction, alternated by the caller between consecutive products
+                   // step (EPI_HESS, o = 3 / 4, symv_derives(work, o)): the previous iteration's cg_step runs in the sweep's launch and the
+                   // sweep derives its product input instead of reading W (TcgFuse)
+bool symv_derives(const SymvWork &work, int o);   // may a sweep on this workspace carry a step?
 void launch_asym(const double *Q, int64_t ld, int64_t m, double *out, int grid, hipStream_t st);
 // fp32 copy of a dense Q for the Hessian products of the truncated CG (xm_tuning_t.hess_f32): same shape (rows x ld, ld a multiple of 4), round to
 // nearest; *bad (device) receives the number of elements that are not finite in fp32

@@ -113,29 +113,32 @@ __device__ __forceinline__ void sum_partials256_x4(const double *p0, const doubl
 // block and these partial sums from memory the previous launch wrote on another XCD (an L2 miss each): requested together they cost one
 // round trip instead of two.
 constexpr int kPre = 4;   // covers 1024 workgroups: every partial sum of a problem in the latency regime
-struct PartialsPre { double v[4][kPre]; };
+template <int KP> struct PartialsPreN { double v[4][KP]; };   // (KP < kPre: fewer registers in flight, for a kernel that has few to spare)
+using PartialsPre = PartialsPreN<kPre>;
+template <int KP>
 __device__ __forceinline__ void sum_partials_prefetch(const double *p0, const double *p1, const double *p2, int count, const double *p3, int count3,
-                                                      PartialsPre &pre, int grp) {
+                                                      PartialsPreN<KP> &pre, int grp) {
 #pragma unroll
-    for (int r = 0; r < kPre; ++r) {
+    for (int r = 0; r < KP; ++r) {
         const int i = threadIdx.x + 256 * r;
         const int j = (i < count) ? sum_perm(i, count, grp) : 0, j3 = (i < count3) ? sum_perm(i, count3, grp) : 0;
         pre.v[0][r] = (i < count) ? p0[j] : 0.0; pre.v[1][r] = (i < count) ? p1[j] : 0.0; pre.v[2][r] = (i < count) ? p2[j] : 0.0;
         pre.v[3][r] = (i < count3) ? p3[j3] : 0.0;
     }
 }
+template <int KP>
 __device__ __forceinline__ void sum_partials256_x4_pre(const double *p0, const double *p1, const double *p2, int count, const double *p3,
-                                                       int count3, bool use3, const PartialsPre &pre, double *sh16, double (&out)[4], int grp = 0) {
+                                                       int count3, bool use3, const PartialsPreN<KP> &pre, double *sh16, double (&out)[4], int grp = 0) {
     double v[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-    for (int r = 0; r < kPre; ++r) {
+    for (int r = 0; r < KP; ++r) {
         const int i = threadIdx.x + 256 * r;
         if (i < count) { v[0] += pre.v[0][r]; v[1] += pre.v[1][r]; v[2] += pre.v[2][r]; }
         if (use3 && i < count3) v[3] += pre.v[3][r];
     }
-    for (int i = threadIdx.x + 256 * kPre; i < count; i += 256) { const int j = sum_perm(i, count, grp); v[0] += p0[j]; v[1] += p1[j]; v[2] += p2[j]; }
+    for (int i = threadIdx.x + 256 * KP; i < count; i += 256) { const int j = sum_perm(i, count, grp); v[0] += p0[j]; v[1] += p1[j]; v[2] += p2[j]; }
     if (use3)
-        for (int i = threadIdx.x + 256 * kPre; i < count3; i += 256) v[3] += p3[sum_perm(i, count3, grp)];
+        for (int i = threadIdx.x + 256 * KP; i < count3; i += 256) v[3] += p3[sum_perm(i, count3, grp)];
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] = wave_sum(v[k]);
     __syncthreads();

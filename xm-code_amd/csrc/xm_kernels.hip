@@ -342,12 +342,48 @@ __global__ __launch_bounds__(256) void qw_dense_ks_kernel(const double *__restri
 // TRACE (micro-benchmark only): 100 MHz timestamps per wavefront -- entry, after the status word, after every step, end.
 // ----------------------------------------------------------------------------------------------------------------
 constexpr int kSvTraceSlots = 24;
-template <int O, bool TRACE = false>
-__global__ __launch_bounds__(256) void qw_symv_kernel(const double *__restrict__ Q, int64_t ld, const double *__restrict__ W, int nloc, int Kc, int Kf, int ysplit, int nt_step0,
-                                                        const TcgScal *__restrict__ scal, double *__restrict__ Prow,
-                                                        double *__restrict__ Pcol, unsigned long long *__restrict__ trace, int rev, int by_phase) {
+// DERIVE (two-launch form of the tCG iteration; o = 3 / 4, Hessian products i >= 1): the launch carries cg_step(i - 1) in the grid rows behind the
+// sweep's (fu.gy) -- the unchanged body of cg_step_kernel in its own workgroups, dispatched last, filling the slots the sweep's tail frees -- and the
+// sweep does not read W, which that step is only now writing: every sweep workgroup repeats the step's scalar decision from the scalar block and
+// the partial sums of iteration i - 1 (tcg_next, the routine cg_step uses), returns if it ends the tCG, and forms W of its 256 columns and of its
+// 4 K steps' rows from p, r, Hp, R, s of iteration i - 1 (tcg_w_next, the expression cg_step stores) into LDS.  Nothing in the launch waits for
+// anything else in it: both parts read only what earlier launches finished (p and r are ping-ponged for that, TcgParity).  The operand requests go
+// out behind the first step of Q, clamped and never predicated; an element past the 3 nloc rows selects zero.
+struct TcgNext;
+struct TcgSums { double pHp, rHp, HpHp, rr_prev; };
+__device__ __forceinline__ TcgNext tcg_next(const TcgScal &sc, double pHp, double rHp, double HpHp);
+__device__ __forceinline__ double tcg_w_next(double step, double beta, double pv, double rv, double hp, double psv, double rsv, double hs, double sv, double Rv);
+__device__ __forceinline__ double tcg_dir_next(double step, double beta, double pv, double rv, double hp);
+__device__ __forceinline__ double tcg_w_of(double sv, double pn, double psn, double Rv);
+constexpr int kSvDerivePre = 2;   // rounds of partial sums a deriving sweep requests ahead (512 workgroups: every plan it runs with)
+__device__ __forceinline__ bool tcg_derive_head(const TcgFuse &fu, const PartialsPreN<kSvDerivePre> &pre, double *sh16, bool lead, double &step, double &beta);
+template <int O, bool XCHG>
+__device__ __forceinline__ void cg_step_body(int bid, int nblk, int nloc, const TcgScal *__restrict__ scal_cur, TcgScal *scal_next, const double *__restrict__ parts,
+                                             int nA_loc, int nB_loc, int world, const double *__restrict__ HpR, const double *__restrict__ Hps,
+                                             const double *__restrict__ R, const double *__restrict__ s, const double *pR_cur, double *pR_next,
+                                             const double *__restrict__ ps_cur, double *ps_next, double *vR, double *vs, double *HvR, double *Hvs,
+                                             const double *rR_cur, double *rR_next, const double *__restrict__ rs_cur, double *rs_next, double *Wloc,
+                                             double *partsB_out, unsigned long long *hstat, int b_off, int64_t mat, double *Afull, double *Wfull, int grp,
+                                             const PeerXchg *xp, double *Wpad);
+template <int O, bool TRACE, bool DERIVE>
+__device__ __forceinline__ void qw_symv_body(const double *__restrict__ Q, int64_t ld, const double *__restrict__ W, int nloc, int Kc, int Kf, int ysplit, int nt_step0,
+                                             const TcgScal *__restrict__ scal, double *__restrict__ Prow,
+                                             double *__restrict__ Pcol, unsigned long long *__restrict__ trace, int rev, int by_phase, const TcgFuse &fu) {
     constexpr int OP = pitch_of(O), V = 6 * O;
+    static_assert(!(TRACE && DERIVE), "the traced sweep reads W");
     __shared__ __attribute__((aligned(16))) double lds[4][V * 64];
+    __shared__ double wcol[DERIVE ? kSvStrip * O : 1], wrws[DERIVE ? kSvDeriveRows : 1], shd[16];   // (W without the pad of its pitch)
+    __shared__ double cam_psn[DERIVE ? 256 : 1], cam_s[DERIVE ? 256 : 1];
+    if constexpr (DERIVE) {
+        if ((int)blockIdx.y >= fu.gy) {   // cg_step(i - 1): workgroup number among the fu.nB of the step
+            const int bid = ((int)blockIdx.y - fu.gy) * (int)gridDim.x + (int)blockIdx.x;
+            if (bid < fu.nB)
+                cg_step_body<O, false>(bid, fu.nB, nloc, fu.scal_cur, fu.scal_next, fu.parts, fu.nA, fu.nB, 1, fu.HpR, fu.Hps, fu.R, fu.s, fu.pR_cur, fu.pR_next,
+                                       fu.ps_cur, fu.ps_next, fu.vR, fu.vs, fu.HvR, fu.Hvs, fu.rR_cur, fu.rR_next, fu.rs_cur, fu.rs_next, fu.Wloc,
+                                       fu.partsB_out, fu.hstat, 0, (int64_t)nloc * 3 * OP, nullptr, nullptr, fu.grp, nullptr, nullptr);
+            return;
+        }
+    }
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     unsigned long long *tr = nullptr;
     if constexpr (TRACE) {   // every wavefront of the grid stamps its entry, with work or without
@@ -375,7 +411,7 @@ __global__ __launch_bounds__(256) void qw_symv_kernel(const double *__restrict__
         const Slot &b = slot[decltype(sl)::value];
         const int64_t r0 = (int64_t)6 * j;
         auto qat = [&](int r, int h, int e) __attribute__((always_inline)) { return e ? b.q[r][h].y : b.q[r][h].x; };
-        auto wrow = [&](int r, double (&wr)[O]) __attribute__((always_inline)) { symv_wrow_read<O>(b.wl, r, r0 + r < nrows, wr); };
+        auto wrow = [&](int r, double (&wr)[O]) __attribute__((always_inline)) { symv_wrow_read<O, DERIVE ? O : OP>(b.wl, r, r0 + r < nrows, wr); };
         double *prow = Prow + ((size_t)ch.s * (size_t)ch.R + (size_t)r0) * O;
         double mr[2] = {1.0, 1.0}, mc[2] = {1.0, 1.0};
         if (j < ch.jfull) symv_step<O, false>(qat, mr, mc, wrow, wc, ca, L, lane, prow);
@@ -394,11 +430,61 @@ __global__ __launch_bounds__(256) void qw_symv_kernel(const double *__restrict__
     };
     // chunks that start at a step >= nt_step0 stream non-temporally (a matrix beyond the Infinity Cache keeps its top rows resident:
     // symv_nt_step0).  The policy is a compile-time property of the sweep loop (two copies under one wave-uniform branch, see qw_dense_kernel).
+    const int j0 = jb - wave * ((int)blockIdx.y >= ysplit ? Kf : Kc);   // first step of the workgroup (DERIVE: wrws holds W of the rows from there)
+    // DERIVE: the workgroup's W out of the vectors of iteration i - 1, between the first step's requests and the rest of the sweep (below).  false:
+    // the step this launch carries ends the tCG.  Called by all 256 threads of a live workgroup: the deriving sweep has ONE copy of its loop -- it
+    // never streams non-temporally (its plans are one residency round of a matrix the Infinity Cache holds) -- so the barriers are uniform.
+    auto derive_w = [&]() __attribute__((always_inline)) -> bool {
+        // operands of the workgroup's W: thread t holds values t + 256 m of the strip's 256 x O column values and of the 4 K steps' 24 K x O row values
+        // (value e of a list: row e / O of it, element e % O -- the pad of the pitch is left out).  The scale parts are per camera: thread t < kColCams
+        // takes camera t of the strip's columns, the threads behind them the cameras of the rows, and the elements read ps+ and s out of LDS --
+        // held per element they are four more live doubles in each of the seven rounds, which the register file of two workgroups per CU has not got
+        constexpr int NC = O, NR = kSvDeriveRows / 256, kColCams = kSvStrip / 3 + 2, kRowCams = kSvDeriveRows / (3 * O);
+        static_assert(!DERIVE || kColCams + kRowCams <= 256, "one thread per camera of the workgroup's W");
+        const int64_t wtot = (int64_t)nrows * OP;
+        const int ccam0 = (int)(ch.c0 / 3), rcam0 = 2 * j0;
+        auto windex = [&](int m) __attribute__((always_inline)) -> int64_t {
+            const int e = (m < NC ? 256 * m : 256 * (m - NC)) + (int)threadIdx.x;
+            return ((m < NC ? ch.c0 : (int64_t)6 * j0) + e / O) * OP + e % O;
+        };
+        double ops[NC + NR][4];
+#pragma unroll
+        for (int m = 0; m < NC + NR; ++m) {
+            const int64_t idx = windex(m);
+            const int64_t ic = idx < wtot ? idx : wtot - 1;
+            ops[m][0] = fu.pR_cur[ic]; ops[m][1] = fu.rR_cur[ic]; ops[m][2] = fu.HpR[ic]; ops[m][3] = fu.R[ic];
+        }
+        const int tcam = (int)threadIdx.x < kColCams ? ccam0 + (int)threadIdx.x : rcam0 + (int)threadIdx.x - kColCams;
+        const int tcc = tcam < nloc ? tcam : nloc - 1;
+        const double c_ps = fu.ps_cur[tcc], c_rs = fu.rs_cur[tcc], c_hs = fu.Hps[tcc], c_s = fu.s[tcc];
+        PartialsPreN<kSvDerivePre> pre;
+        sum_partials_prefetch(fu.parts, fu.parts + fu.nA, fu.parts + 2 * fu.nA, fu.nA, fu.parts + 3 * fu.nA, fu.nB, pre, fu.grp);
+        double step, beta;
+        // (workgroup (0, 0) always has work: it publishes the progress word as early as cg_step's own launch did)
+        if (!tcg_derive_head(fu, pre, shd, blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0, step, beta)) return false;   // uniform over the grid
+        if ((int)threadIdx.x < kColCams + kRowCams) { cam_psn[threadIdx.x] = tcg_dir_next(step, beta, c_ps, c_rs, c_hs); cam_s[threadIdx.x] = c_s; }
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < NC + NR; ++m) {
+            const int64_t idx = windex(m);
+            const int64_t ic = idx < wtot ? idx : wtot - 1;
+            const int cam = (int)(ic / (3 * OP));
+            int ts = (m < NC) ? cam - ccam0 : kColCams + cam - rcam0;   // (a clamped element may lie outside the workgroup's cameras: it selects zero below)
+            ts = ts < 0 ? 0 : (ts < kColCams + kRowCams ? ts : kColCams + kRowCams - 1);
+            const double wv = tcg_w_of(cam_s[ts], tcg_dir_next(step, beta, ops[m][0], ops[m][1], ops[m][2]), cam_psn[ts], ops[m][3]);
+            (m < NC ? wcol : wrws)[threadIdx.x + 256 * (m < NC ? m : m - NC)] = idx < wtot ? wv : 0.0;
+        }
+        __syncthreads();
+        return true;
+    };
     auto sweep = [&](auto ntag) __attribute__((always_inline)) -> bool {
         constexpr bool NT = decltype(ntag)::value;
-        auto load = [&](int j, auto sl) __attribute__((always_inline)) {
+        auto loadw = [&](int j, auto sl) __attribute__((always_inline)) {
+            slot[decltype(sl)::value].wl = wrws[(j - j0) * 6 * O + (lane < 6 * O ? lane : 0)];
+        };
+        auto loadq = [&](int j, auto sl) __attribute__((always_inline)) {
             Slot &b = slot[decltype(sl)::value];
-            b.wl = symv_wrow_request<O>(W, j, nrows, lane);
+            if constexpr (!DERIVE) b.wl = symv_wrow_request<O>(W, j, nrows, lane);
             const int64_t r0 = (int64_t)6 * j;
 #pragma unroll
             for (int r = 0; r < 6; ++r) {
@@ -412,33 +498,60 @@ __global__ __launch_bounds__(256) void qw_symv_kernel(const double *__restrict__
                 }
             }
         };
-        if (jb < je) load(symv_walk_at(jb, je, rev, 0), std::integral_constant<int, 0>{});   // wave-uniform
+        auto load = [&](int j, auto sl) __attribute__((always_inline)) {
+            if constexpr (DERIVE) loadw(j, sl);
+            loadq(j, sl);
+        };
+        if (jb < je) loadq(symv_walk_at(jb, je, rev, 0), std::integral_constant<int, 0>{});   // wave-uniform
+        if constexpr (DERIVE) {
+            if (!derive_w()) return false;
+            if (jb < je) loadw(symv_walk_at(jb, je, rev, 0), std::integral_constant<int, 0>{});
+        }
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int e = 0; e < 2; ++e)
 #pragma unroll
                 for (int k = 0; k < O; ++k) {
-                    const double t = W[(size_t)((h ? cB : cA) + e) * OP + k];   // unconditional request (a predicated one is a branch per element)
-                    wc[h][e][k] = (h == 0 || half1) ? t : 0.0;
+                    if constexpr (DERIVE) {
+                        wc[h][e][k] = wcol[(128 * h + 2 * lane + e) * O + k];   // (zero beyond the 3 nloc rows: the absent half of the last strip too)
+                    } else {
+                        const double t = W[(size_t)((h ? cB : cA) + e) * OP + k];   // unconditional request (a predicated one is a branch per element)
+                        wc[h][e][k] = (h == 0 || half1) ? t : 0.0;
+                    }
                     ca[h][e][k] = 0.0;
                 }
         // the tCG's status word (written by the previous launch on another XCD: an L2 miss) is looked at only now, with the columns of W and the
         // first step of Q already requested: one round trip at the head of every wavefront instead of two
-        if (scal != nullptr) {   // by_phase (device-driven outer iteration): live in the phases PH_TCG and PH_CAND, whatever the tCG's status says
-            if (by_phase ? (scal->phase >= PH_STOP) : (scal->status != 0)) return false;
+        if constexpr (!DERIVE) {
+            if (scal != nullptr) {   // by_phase (device-driven outer iteration): live in the phases PH_TCG and PH_CAND, whatever the tCG's status says
+                if (by_phase ? (scal->phase >= PH_STOP) : (scal->status != 0)) return false;
+            }
         }
         if constexpr (TRACE) { if (lane == 0) tr[1] = wall_clock64(); }
         symv_walk(jb, je, rev, load, run);
         return true;
     };
-    const bool alive = (jb >= nt_step0) ? sweep(std::true_type{}) : sweep(std::false_type{});
+    const bool alive = DERIVE ? sweep(std::false_type{}) : ((jb >= nt_step0) ? sweep(std::true_type{}) : sweep(std::false_type{}));
     if (!alive) return;
     if constexpr (TRACE) { if (lane == 0) tr[kSvTraceSlots - 3] = wall_clock64(); }
 
     // wavefront h writes the h-th half of the strip
     symv_colsum<O>(ca, lds, wave, lane, wave == 0 || half1, Pcol + ((size_t)ch.sc * (size_t)ld + (size_t)(cA + 128 * wave)) * O);
     if constexpr (TRACE) { if (lane == 0) tr[kSvTraceSlots - 2] = wall_clock64(); }
+}
+template <int O, bool TRACE = false>
+__global__ __launch_bounds__(256) void qw_symv_kernel(const double *__restrict__ Q, int64_t ld, const double *__restrict__ W, int nloc, int Kc, int Kf, int ysplit, int nt_step0,
+                                                        const TcgScal *__restrict__ scal, double *__restrict__ Prow,
+                                                        double *__restrict__ Pcol, unsigned long long *__restrict__ trace, int rev, int by_phase) {
+    qw_symv_body<O, TRACE, false>(Q, ld, W, nloc, Kc, Kf, ysplit, nt_step0, scal, Prow, Pcol, trace, rev, by_phase, TcgFuse{});
+}
+// the sweep that carries the step: held to the registers of two workgroups per CU (the sweep's occupancy at o = 3 and 4)
+template <int O>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void qw_symv_step_kernel(const double *__restrict__ Q, int64_t ld, int nloc, int Kc, int Kf, int ysplit, int nt_step0, double *__restrict__ Prow,
+                         double *__restrict__ Pcol, int rev, TcgFuse fu) {
+    qw_symv_body<O, false, true>(Q, ld, nullptr, nloc, Kc, Kf, ysplit, nt_step0, nullptr, Prow, Pcol, nullptr, rev, 0, fu);
 }
 
 // second half: y_cam = sum_{strips s >= s_lo} Prow[s][rows of cam] + sum_{groups above} Pcol[group][rows of cam] (fixed order), fused epilogue.
@@ -926,23 +1039,97 @@ __global__ __launch_bounds__(256) void tcg_init_kernel(int nloc, const double *_
 // reduction; the directly summed |r|^2 (partsB_out) replaces that estimate as <r,r> of the NEXT iteration, so no error
 // accumulates.  Block 0 owns the scalar state (other parity buffer) and the host-mapped progress word.  The scale parts of
 // p and r are ping-ponged (cur -> next): every element thread of a camera reads them while one thread rewrites them.
-template <int O>
-__global__ __launch_bounds__(256) void cg_step_kernel(int nloc, const TcgScal *__restrict__ scal_cur, TcgScal *scal_next,
-                                                       const double *__restrict__ parts, int nA_loc, int nB_loc, int world,
-                                                       const double *__restrict__ HpR,
-                                                       const double *__restrict__ Hps, const double *__restrict__ R,
-                                                       const double *__restrict__ s, double *pR, const double *__restrict__ ps_cur,
-                                                       double *ps_next, double *vR, double *vs, double *HvR, double *Hvs, double *rR,
-                                                       const double *__restrict__ rs_cur, double *rs_next, double *Wloc,
-                                                       double *partsB_out, unsigned long long *hstat, int b_off, int64_t mat,
-                                                       double *Afull, double *Wfull, int grp, PeerXchg x, double *Wpad) {
+struct TcgNext {
+    int mode;            // tcg_decide's
+    bool cg, conv, newdir;
+    double step, beta, rr_est;
+    int status, iter;    // of the next scalar block: status != 0 ends the tCG
+};
+// From the sums of an iteration to what its step does (trustregion.h:565-644): the decision, the residual estimate, the :627 exit test, beta and the
+// next block's status.  cg_step evaluates it in every workgroup, and so does every workgroup of the sweep that carries the step (qw_symv_step_kernel,
+// DERIVE form) -- one routine, behind contract(off), so that both get the same bits.  sc.rr: the exact |r|^2 (already replaced for iter > 0).
+__device__ __forceinline__ TcgNext tcg_next(const TcgScal &sc, double pHp, double rHp, double HpHp) {
+    TcgNext n;
+    const StepDecision d = tcg_decide(sc, pHp);
+    n.mode = d.mode; n.step = d.step; n.cg = (d.mode == 0);
+    n.conv = false; n.newdir = false; n.beta = 0.0; n.rr_est = 0.0; n.status = d.mode; n.iter = sc.iter;
+    if (d.mode == 5) { n.cg = false; return n; }
+    const double step = d.step;
+    double rr_est = sc.rr + 2.0 * step * rHp + step * step * HpHp;
+    if (rr_est < 0.0) rr_est = 0.0;
+    n.rr_est = rr_est;
+    n.conv = n.cg && (sqrt(rr_est) < sc.gradnorm * fmin(sc.gradnorm, 0.1));   // trustregion.h:627
+    n.beta = rr_est / sc.rr;
+    n.newdir = n.cg && !n.conv;
+    if (n.cg) {
+        if (n.conv) n.status = 3;
+        else { n.iter = sc.iter + 1; n.status = (n.iter >= kMaxInner) ? 6 : 0; }
+    }
+    return n;
+}
+// the scalar block behind a step that is not the mode-5 stop (block 0's lead thread only)
+__device__ __forceinline__ TcgScal tcg_scal_next(const TcgScal &sc, const TcgNext &n, double pHp, bool keep_hv) {
+    TcgScal nx = sc;
+    const double step = n.step, beta = n.beta, rr_est = n.rr_est;
+    nx.last_step = step;
+    // m(v + step p) - m(v) = step <p, r> + step^2 <p,Hp> / 2 with <p, r> = -<r, r> (CG: r is orthogonal to the previous direction), for the
+    // interior step (step = rr / <p,Hp>: -step rr / 2) and for the boundary / negative-curvature step alike (trustregion.h:605-610, 667-668
+    // compute the same number from the accumulated vectors)
+    if (!keep_hv) nx.model = sc.model - step * sc.rr + 0.5 * step * step * pHp;
+    if (!n.cg) {
+        nx.status = n.mode;
+    } else {
+        nx.rr = rr_est;
+        nx.vv = sc.vv + 2.0 * step * sc.vp + step * step * sc.pp;  // trustregion.h:642-644
+        nx.vp = beta * (sc.vp + step * sc.pp);
+        nx.pp = beta * beta * sc.pp + rr_est;
+        nx.status = n.status; nx.iter = n.iter;
+    }
+    return nx;
+}
+// the next product input at one element: W+ = s p+ + ps+ R with r+ = r + step Hp, p+ = beta p - r+ (both parts, each by tcg_dir_next)
+__device__ __forceinline__ double tcg_dir_next(double step, double beta, double pv, double rv, double hp) {
+    const double rn = rv + step * hp;
+    return beta * pv - rn;
+}
+__device__ __forceinline__ double tcg_w_of(double sv, double pn, double psn, double Rv) { return sv * pn + psn * Rv; }
+__device__ __forceinline__ double tcg_w_next(double step, double beta, double pv, double rv, double hp, double psv, double rsv, double hs, double sv, double Rv) {
+    return tcg_w_of(sv, tcg_dir_next(step, beta, pv, rv, hp), tcg_dir_next(step, beta, psv, rsv, hs), Rv);
+}
+// Head of a sweep workgroup that carries the step (all 256 threads): scalar block and partial sums of the iteration before -> does the tCG go on, and
+// with which step and beta?  The sums are cg_step's (same tree, same order); `lead` publishes the outcome to the host's progress word.
+__device__ __forceinline__ bool tcg_derive_head(const TcgFuse &fu, const PartialsPreN<kSvDerivePre> &pre, double *sh16, bool lead, double &step, double &beta) {
+    const TcgScal sc0 = *fu.scal_cur;
+    step = 0.0; beta = 0.0;
+    if (sc0.status != 0) return false;
+    double t[4];
+    sum_partials256_x4_pre(fu.parts, fu.parts + fu.nA, fu.parts + 2 * fu.nA, fu.nA, fu.parts + 3 * fu.nA, fu.nB, sc0.iter > 0, pre, sh16, t, fu.grp);
+    double pHp = 0.0, rHp = 0.0, HpHp = 0.0, rr_prev = 0.0;
+    pHp += t[0]; rHp += t[1]; HpHp += t[2];
+    if (sc0.iter > 0) rr_prev += t[3];
+    TcgScal sc = sc0;
+    if (sc0.iter > 0) sc.rr = rr_prev;
+    const TcgNext n = tcg_next(sc, pHp, rHp, HpHp);
+    if (lead) publish_host(fu.hstat, pack_stat(sc.seq, n.iter, n.status));
+    step = n.step; beta = n.beta;
+    return n.status == 0;
+}
+
+template <int O, bool XCHG>
+__device__ __forceinline__ void cg_step_body(int bid, int nblk, int nloc, const TcgScal *__restrict__ scal_cur, TcgScal *scal_next, const double *__restrict__ parts,
+                                             int nA_loc, int nB_loc, int world, const double *__restrict__ HpR, const double *__restrict__ Hps,
+                                             const double *__restrict__ R, const double *__restrict__ s, const double *pR_cur, double *pR_next,
+                                             const double *__restrict__ ps_cur, double *ps_next, double *vR, double *vs, double *HvR, double *Hvs,
+                                             const double *rR_cur, double *rR_next, const double *__restrict__ rs_cur, double *rs_next, double *Wloc,
+                                             double *partsB_out, unsigned long long *hstat, int b_off, int64_t mat, double *Afull, double *Wfull, int grp,
+                                             const PeerXchg *xp, double *Wpad) {
     constexpr int OP = pitch_of(O);
     __shared__ double sh[4];
     __shared__ double sh16[16];
     __shared__ int sh_flag;
     const int64_t total = (int64_t)nloc * 3 * OP;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t stride = (int64_t)nblk * 256;
+    int64_t i = (int64_t)bid * 256 + threadIdx.x;
     // operands of the thread's first element are requested before the scalar block / partial sums are read
     const bool in0 = i < total;
     const int camf = (int)(i / (3 * OP));
@@ -951,21 +1138,23 @@ __global__ __launch_bounds__(256) void cg_step_kernel(int nloc, const TcgScal *_
     // XM_FLAG_MODEL_RECURRENCE (HvR == nullptr): H v is not accumulated -- the model value travels in the scalar block instead (below): 2 x 3 n OP
     // doubles less read and written per iteration (28.8 MB of the launch's 93 MB at 100 k cameras, o = 3)
     const bool keep_hv = HvR != nullptr;
-    if (in0) { hp = HpR[i]; pv = pR[i]; vv0 = vR[i]; if (keep_hv) hv = HvR[i]; rv = rR[i]; Rv = R[i]; hs = Hps[camf]; psv = ps_cur[camf]; rsv = rs_cur[camf]; sv = s[camf]; }
+    if (in0) { hp = HpR[i]; pv = pR_cur[i]; vv0 = vR[i]; if (keep_hv) hv = HvR[i]; rv = rR_cur[i]; Rv = R[i]; hs = Hps[camf]; psv = ps_cur[camf]; rsv = rs_cur[camf]; sv = s[camf]; }
     if (own0) { vsv = vs[camf]; if (keep_hv) hvs = Hvs[camf]; }
     // ... and so are the first rounds of rank 0's partial sums (single GPU: all of them up to 512 workgroups): scalar block and partial sums
     // were written by the previous launches on other XCDs -- one memory round trip for both instead of two in a row
     // (not with the fused peer exchange: there the peers' chunks arrive DURING this launch)
-    const bool can_pre = x.world <= 1;
+    const bool can_pre = !XCHG || xp->world <= 1;
     PartialsPre pre;
     if (can_pre) sum_partials_prefetch(parts + b_off, parts + b_off + nA_loc, parts + b_off + 2 * nA_loc, nA_loc, parts + b_off + 3 * nA_loc, nB_loc, pre, grp);
     const TcgScal sc0 = *scal_cur;
-    const bool lead = (blockIdx.x == 0 && threadIdx.x == 0);
+    const bool lead = (bid == 0 && threadIdx.x == 0);
     if (sc0.status != 0) {
         if (lead) *scal_next = sc0;
         return;
     }
-    if (x.world > 1) {
+    if constexpr (XCHG) {
+    if (xp->world > 1) {
+        const PeerXchg &x = *xp;
         // DIRECT PEER EXCHANGE fused into this launch (peer communicators, xm_comm.hip): `parts` is this rank's exchange buffer for the
         // parity of this iteration; its own chunk [rows of B | 3 nA sums of this iteration's Hessian epilogue | nB sums of the previous
         // cg_step] is complete (earlier launches of this stream).  Every workgroup stores a slice of it into the SAME place of every
@@ -984,14 +1173,14 @@ __global__ __launch_bounds__(256) void cg_step_kernel(int nloc, const TcgScal *_
             for (int p = 0; p < x.world; ++p) {
                 if (p == x.rank) continue;
                 double *dst = x.buf[p] + off;
-                for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < chunk_d; j += (size_t)stride)
+                for (size_t j = (size_t)bid * 256 + threadIdx.x; j < chunk_d; j += (size_t)stride)
                     __hip_atomic_store(dst + j, src[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             if (threadIdx.x == 0) {
                 const unsigned long long t = __hip_atomic_fetch_add(x.ticket + par, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                sh_flag = (t + 1 == gridDim.x);
+                sh_flag = (t + 1 == (unsigned)nblk);
                 if (sh_flag) __hip_atomic_store(x.ticket + par, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             __syncthreads();
@@ -1001,14 +1190,14 @@ __global__ __launch_bounds__(256) void cg_step_kernel(int nloc, const TcgScal *_
             for (int p = 0; p < x.world; ++p) {
                 if (p == x.rank) continue;
                 double *dst = x.buf[p] + off;
-                for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < chunk_d; j += (size_t)stride) dst[j] = src[j];
+                for (size_t j = (size_t)bid * 256 + threadIdx.x; j < chunk_d; j += (size_t)stride) dst[j] = src[j];
             }
             __threadfence_system();
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             if (threadIdx.x == 0) {
                 const unsigned long long t = __hip_atomic_fetch_add(x.ticket + par, 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-                sh_flag = (t + 1 == gridDim.x);
+                sh_flag = (t + 1 == (unsigned)nblk);
                 if (sh_flag) __hip_atomic_store(x.ticket + par, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             __syncthreads();
@@ -1045,6 +1234,7 @@ __global__ __launch_bounds__(256) void cg_step_kernel(int nloc, const TcgScal *_
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
     }
+    }
     // `parts` = the gathered per-rank chunks [ <p,Hp> | <r,Hp> | <Hp,Hp> (nA_loc each, from this iteration's Hessian epilogue)
     //                                          | |r|^2 partials of the PREVIOUS iteration's cg_step (nB_loc) ]
     // (multi-rank: each chunk starts with b_off doubles = that rank's rows of the image of Hp, see below)
@@ -1060,8 +1250,8 @@ __global__ __launch_bounds__(256) void cg_step_kernel(int nloc, const TcgScal *_
     }
     TcgScal sc = sc0;
     if (sc0.iter > 0) sc.rr = rr_prev;   // exact |r|^2 summed by the previous iteration
-    const StepDecision d = tcg_decide(sc, pHp);
-    if (d.mode == 5) {
+    const TcgNext nx_ = tcg_next(sc, pHp, rHp, HpHp);
+    if (nx_.mode == 5) {
         if (lead) {
             TcgScal nx = sc; nx.status = 5; nx.last_step = 0.0;
             *scal_next = nx;
@@ -1069,13 +1259,10 @@ __global__ __launch_bounds__(256) void cg_step_kernel(int nloc, const TcgScal *_
         }
         return;
     }
-    const double step = d.step;
-    const bool cg = (d.mode == 0);
-    double rr_est = sc.rr + 2.0 * step * rHp + step * step * HpHp;
-    if (rr_est < 0.0) rr_est = 0.0;
-    const bool conv = cg && (sqrt(rr_est) < sc.gradnorm * fmin(sc.gradnorm, 0.1));   // trustregion.h:627
-    const double beta = rr_est / sc.rr;
-    const bool newdir = cg && !conv;
+    const double step = nx_.step;
+    const bool cg = nx_.cg;
+    const double beta = nx_.beta;
+    const bool newdir = nx_.newdir;
     double acc = 0.0;
     if (in0) {
         vR[i] = vv0 + step * pv;
@@ -1083,14 +1270,14 @@ __global__ __launch_bounds__(256) void cg_step_kernel(int nloc, const TcgScal *_
         if (cg) {
             const double rn = rv + step * hp;
             const double rsn = rsv + step * hs;
-            rR[i] = rn;
+            rR_next[i] = rn;
             acc += rn * rn;
             if (newdir) {
                 const double pn = beta * pv - rn;
                 const double psn = beta * psv - rsn;
-                pR[i] = pn;
+                pR_next[i] = pn;
                 if (!Afull) {
-                    const double wv = sv * pn + psn * Rv;
+                    const double wv = tcg_w_next(step, beta, pv, rv, hp, psv, rsv, hs, sv, Rv);
                     if (Wloc) Wloc[i] = wv;
                     if (Wpad) Wpad[(size_t)camf * 16 + (i - (int64_t)camf * (3 * OP))] = wv;
                 }
@@ -1103,20 +1290,21 @@ __global__ __launch_bounds__(256) void cg_step_kernel(int nloc, const TcgScal *_
     for (i += stride; i < total; i += stride) {
         const int cam = (int)(i / (3 * OP));
         const bool own = (i % (3 * OP) == 0);
-        const double hpi = HpR[i], pi = pR[i], hsi = Hps[cam], psi = ps_cur[cam];
+        const double hpi = HpR[i], pi = pR_cur[i], hsi = Hps[cam], psi = ps_cur[cam];
         vR[i] += step * pi;
         if (keep_hv) HvR[i] += step * hpi;
         if (cg) {
-            const double rn = rR[i] + step * hpi;
-            const double rsn = rs_cur[cam] + step * hsi;
-            rR[i] = rn;
+            const double rri = rR_cur[i], rsi = rs_cur[cam];
+            const double rn = rri + step * hpi;
+            const double rsn = rsi + step * hsi;
+            rR_next[i] = rn;
             acc += rn * rn;
             if (newdir) {
                 const double pn = beta * pi - rn;
                 const double psn = beta * psi - rsn;
-                pR[i] = pn;
+                pR_next[i] = pn;
                 if (!Afull) {
-                    const double wv = s[cam] * pn + psn * R[i];
+                    const double wv = tcg_w_next(step, beta, pi, rri, hpi, psi, rsi, hsi, s[cam], R[i]);
                     if (Wloc) Wloc[i] = wv;
                     if (Wpad) Wpad[(size_t)cam * 16 + (i - (int64_t)cam * (3 * OP))] = wv;
                 }
@@ -1134,7 +1322,7 @@ __global__ __launch_bounds__(256) void cg_step_kernel(int nloc, const TcgScal *_
         // replicas stay bit-identical and no second all-gather (of W) is needed.  A0 = -W0 because p0 = -r0.
         const int64_t full = mat * world;
         const bool first = (sc0.iter == 0);
-        for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < full; j += stride) {
+        for (int64_t j = (int64_t)bid * 256 + threadIdx.x; j < full; j += stride) {
             const int64_t r = j / mat;
             const double b = parts[(size_t)r * chunk + (size_t)(j - r * mat)];
             const double w = Wfull[j];
@@ -1145,32 +1333,27 @@ __global__ __launch_bounds__(256) void cg_step_kernel(int nloc, const TcgScal *_
     }
     if (cg) {
         const double tot = block_sum256(acc, sh);
-        if (threadIdx.x == 0) partsB_out[blockIdx.x] = tot;
+        if (threadIdx.x == 0) partsB_out[bid] = tot;
     }
     if (lead) {
-        TcgScal nx = sc;
-        nx.last_step = step;
-        // m(v + step p) - m(v) = step <p, r> + step^2 <p,Hp> / 2 with <p, r> = -<r, r> (CG: r is orthogonal to the previous direction), for the
-        // interior step (step = rr / <p,Hp>: -step rr / 2) and for the boundary / negative-curvature step alike (trustregion.h:605-610, 667-668
-        // compute the same number from the accumulated vectors)
-        if (!keep_hv) nx.model = sc.model - step * sc.rr + 0.5 * step * step * pHp;
-        if (!cg) {
-            nx.status = d.mode;
-        } else {
-            nx.rr = rr_est;
-            nx.vv = sc.vv + 2.0 * step * sc.vp + step * step * sc.pp;  // trustregion.h:642-644
-            nx.vp = beta * (sc.vp + step * sc.pp);
-            nx.pp = beta * beta * sc.pp + rr_est;
-            if (conv) {
-                nx.status = 3;
-            } else {
-                nx.iter = sc.iter + 1;
-                nx.status = (nx.iter >= kMaxInner) ? 6 : 0;
-            }
-        }
+        const TcgScal nx = tcg_scal_next(sc, nx_, pHp, keep_hv);
         *scal_next = nx;
         publish_host(hstat, pack_stat(nx.seq, nx.iter, nx.status));
     }
+}
+
+template <int O>
+__global__ __launch_bounds__(256) void cg_step_kernel(int nloc, const TcgScal *__restrict__ scal_cur, TcgScal *scal_next,
+                                                       const double *__restrict__ parts, int nA_loc, int nB_loc, int world,
+                                                       const double *__restrict__ HpR,
+                                                       const double *__restrict__ Hps, const double *__restrict__ R,
+                                                       const double *__restrict__ s, const double *pR_cur, double *pR_next, const double *__restrict__ ps_cur,
+                                                       double *ps_next, double *vR, double *vs, double *HvR, double *Hvs, const double *rR_cur, double *rR_next,
+                                                       const double *__restrict__ rs_cur, double *rs_next, double *Wloc,
+                                                       double *partsB_out, unsigned long long *hstat, int b_off, int64_t mat,
+                                                       double *Afull, double *Wfull, int grp, PeerXchg x, double *Wpad) {
+    cg_step_body<O, true>(blockIdx.x, gridDim.x, nloc, scal_cur, scal_next, parts, nA_loc, nB_loc, world, HpR, Hps, R, s, pR_cur, pR_next, ps_cur, ps_next, vR, vs,
+                          HvR, Hvs, rR_cur, rR_next, rs_cur, rs_next, Wloc, partsB_out, hstat, b_off, mat, Afull, Wfull, grp, &x, Wpad);
 }
 
 // End of an outer iteration: one 256-thread block adds the gathered partial sums in their fixed order and hands
@@ -2496,14 +2679,30 @@ static int symv_nt_step0(int nloc, double elem_bytes) {     // elem_bytes: 8 (f6
 }
 template <int O>
 static void qw_symv_epi(int epi, const double *Q, int64_t ld, const double *W, double alpha, const CamArgs &a, SymvWork &work,
-                        hipStream_t st, int rev, unsigned long long *trace = nullptr) {
+                        hipStream_t st, int rev, unsigned long long *trace = nullptr, const CgStepArgs *step = nullptr) {
     const auto [gs, rK, rKf, ys, nstrips] = symv_geom(work, a.nloc, ld, O);
     const SymvPlan &pl = work.plan;
     double *const Prow = work.prow.p, *const Pcol = work.pcol.p;
     const TcgScal *sc = (epi == EPI_HESS || epi == EPI_AUTO) ? a.scal : (const TcgScal *)nullptr;
     const int by_phase = (epi == EPI_AUTO) ? 1 : 0;
     const int nt0 = symv_nt_step0(a.nloc, sizeof(double));
-    if (trace) {
+    if (step) {
+        // two-launch form: cg_step of the iteration before in the grid rows behind the sweep's, W derived by the sweep (qw_symv_step_kernel)
+        if constexpr (O == 3 || O == 4) {
+            if (epi != EPI_HESS || trace || !symv_derives(work, O) || step->world > 1 || step->Afull || step->Wpad || step->v.b_off != 0)
+                throw Error(-2, "symmetric product: this launch cannot carry the tCG step");
+            const CgStepArgs &S = *step;
+            TcgFuse fu;
+            fu.gy = (int)gs.y; fu.nA = S.nA; fu.nB = S.nB; fu.grp = S.grouping;
+            fu.scal_cur = S.v.scal_cur; fu.scal_next = S.v.scal_next; fu.parts = S.v.pcur;
+            fu.HpR = S.HpR; fu.Hps = S.Hps; fu.R = S.R; fu.s = S.s;
+            fu.pR_cur = S.v.pR_cur; fu.ps_cur = S.v.ps_cur; fu.rR_cur = S.v.rR_cur; fu.rs_cur = S.v.rs_cur;
+            fu.pR_next = S.v.pR_next; fu.ps_next = S.v.ps_next; fu.rR_next = S.v.rR_next; fu.rs_next = S.v.rs_next;
+            fu.vR = S.vR; fu.vs = S.vs; fu.HvR = S.HvR; fu.Hvs = S.Hvs; fu.Wloc = S.Wloc; fu.partsB_out = S.v.partsB_out; fu.hstat = S.hstat;
+            const dim3 gf(gs.x, gs.y + (S.nB + gs.x - 1) / gs.x);
+            hipLaunchKernelGGL((qw_symv_step_kernel<O>), gf, dim3(256), 0, st, Q, ld, a.nloc, pl.K, pl.Kf, ys, nt0, Prow, Pcol, rev, fu);
+        } else throw Error(-2, "symmetric product: the tCG step travels with the sweep at o = 3 and 4 only");
+    } else if (trace) {
         if constexpr (O == 3 || O == 4) hipLaunchKernelGGL((qw_symv_kernel<O, true>), gs, dim3(256), 0, st, Q, ld, W, a.nloc, pl.K, pl.Kf, ys, nt0, sc, Prow, Pcol, trace, rev, by_phase);
     } else hipLaunchKernelGGL((qw_symv_kernel<O>), gs, dim3(256), 0, st, Q, ld, W, a.nloc, pl.K, pl.Kf, ys, nt0, sc, Prow, Pcol, trace, rev, by_phase);
     const dim3 g(qw_grid(a.nloc)), b(256);
@@ -2519,6 +2718,10 @@ static void qw_symv_epi(int epi, const double *Q, int64_t ld, const double *W, d
             throw Error(-2, "certificate operator needs o == 1");
         default: throw Error(-2, "bad epilogue");
     }
+}
+// the sweep's LDS holds W of a workgroup's 4 K steps (kSvDeriveRows doubles) at the ranks whose sweep has a deriving form
+bool symv_derives(const SymvWork &work, int o) {
+    return work && (o == 3 || o == 4) && o <= work.o && 4 * std::max(work.plan.K, work.plan.Kf) * 6 * o <= kSvDeriveRows;
 }
 int symv_trace_slots() { return kSvTraceSlots; }
 // micro-benchmark: one traced product (o = 3 or 4); trace = [work.plan.gy * work.plan.gx * 4 wavefronts][kSvTraceSlots] timestamps
@@ -2536,13 +2739,13 @@ void launch_qw_sym_traced(int o, const double *Q, int64_t ld, const double *W, c
 // by a number both runs of the same solve agree on (the tCG iteration, the Lanczos step), never by a launch count that run-ahead no-ops would shift:
 // the direction changes the order of the column sums, i.e. the last bits.
 void launch_qw_sym(int o, int epi, const double *Q, int64_t ld, const double *W, double alpha, const CamArgs &a, SymvWork &work, hipStream_t st,
-                   int rev) {
+                   int rev, const CgStepArgs *step) {
     if (a.nloc <= 0) return;
     switch (o) {
-        case 1: qw_symv_epi<1>(epi, Q, ld, W, alpha, a, work, st, rev & 1); break;
-        case 3: qw_symv_epi<3>(epi, Q, ld, W, alpha, a, work, st, rev & 1); break;
-        case 4: qw_symv_epi<4>(epi, Q, ld, W, alpha, a, work, st, rev & 1); break;
-        case 5: qw_symv_epi<5>(epi, Q, ld, W, alpha, a, work, st, rev & 1); break;
+        case 1: qw_symv_epi<1>(epi, Q, ld, W, alpha, a, work, st, rev & 1, nullptr, step); break;
+        case 3: qw_symv_epi<3>(epi, Q, ld, W, alpha, a, work, st, rev & 1, nullptr, step); break;
+        case 4: qw_symv_epi<4>(epi, Q, ld, W, alpha, a, work, st, rev & 1, nullptr, step); break;
+        case 5: qw_symv_epi<5>(epi, Q, ld, W, alpha, a, work, st, rev & 1, nullptr, step); break;
         default: throw Error(-2, "symmetric product is instantiated for o = 1, 3..5");
     }
     check_launch("qw_symv");
@@ -2680,8 +2883,8 @@ void launch_tcg_init(int o, const TcgInitArgs &a, hipStream_t st) {
 void launch_cg_step(int o, const CgStepArgs &a, hipStream_t st) {
     // grid = nB: one |r|^2 partial sum per workgroup (Context::tcg_blocks: capped when the launch waits for its peers inside the kernel)
     XM_DISPATCH_O(o, hipLaunchKernelGGL((cg_step_kernel<O_>), dim3(a.nB), dim3(256), 0, st, a.nloc,
-                                        a.v.scal_cur, a.v.scal_next, a.v.pcur, a.nA, a.nB, a.world, a.HpR, a.Hps, a.R, a.s, a.pR, a.v.ps_cur, a.v.ps_next, a.vR,
-                                        a.vs, a.HvR, a.Hvs, a.rR, a.v.rs_cur, a.v.rs_next, a.Wloc, a.v.partsB_out, a.hstat, (int)a.v.b_off, a.mat, a.Afull,
+                                        a.v.scal_cur, a.v.scal_next, a.v.pcur, a.nA, a.nB, a.world, a.HpR, a.Hps, a.R, a.s, a.v.pR_cur, a.v.pR_next, a.v.ps_cur, a.v.ps_next, a.vR,
+                                        a.vs, a.HvR, a.Hvs, a.v.rR_cur, a.v.rR_next, a.v.rs_cur, a.v.rs_next, a.Wloc, a.v.partsB_out, a.hstat, (int)a.v.b_off, a.mat, a.Afull,
                                         a.Wfull, a.grouping, a.xchg, a.Wpad));
     check_launch("cg_step");
 }

@@ -195,6 +195,7 @@ public:
     int64_t n_landmarks() const;
     int64_t n_observations() const;   // matrix-free storage: observations of the list (0 otherwise)
     void dense_q(double *q, int64_t ldq);   // xm_tuning_t.schur_dense_q: the current dense Q -> host, column-major
+    int tcg_two_launch_count() const { return tcg_two_launch_count_; }   // trust regions of the last solve in the two-launch form (xm_ctx_tcg_two_launch)
     bool schur_info(int64_t out[3], double *relres) const;   // matrix-free storage with the CG form: products, inner iterations, products at the cap
     int schur_precond(int64_t *aggregates, int *block) const; // its preconditioner: -1 no CG form, 0 Jacobi, 1 two-level (aggregates, cameras per aggregate)
 
@@ -253,7 +254,7 @@ private:
     const double *wpad_next_ = nullptr;   // set by the outer iteration's retraction: the NEXT gradient product finds its input in the padded copy too
     PointState ps_[2];
     int cur_ = 0;
-    DevBuf<double> rR_, rs_, rsB_, pR_, psA_, psB_, vR_, vs_, HvR_, Hvs_, HpR_, Hps_;
+    DevBuf<double> rR_, rRB_, rs_, rsB_, pR_, pRB_, psA_, psB_, vR_, vs_, HvR_, Hvs_, HpR_, Hps_;   // p and r: two copies by iteration parity (tcg_parity)
     DevBuf<double> partsA_, partsB_, partsM_;
     SymvWork symv_;                            // symmetric product: its chunk plan, row results and per-workgroup column partials
     DevBuf<double> ksum_;                      // column-split dense product of a small strip: partial sums per (slice, camera)
@@ -307,7 +308,10 @@ private:
     double sum_parts(const double *dparts, int count);
     int run_tcg(double rr, double delta, int adopted = 0);   // adopted: iterations of THIS tCG already enqueued speculatively (enqueue_spec_tcg)
     int enqueue_spec_tcg();      // single GPU: tcg_init + the first iteration(s) of the next tCG from the CANDIDATE point, gated on the device (SpecCtl)
-    void tcg_enqueue_iteration(int i, bool profile);   // one iteration = Hessian product (+ exchange) + cg_step
+    void tcg_enqueue_iteration(int i, bool profile);   // one iteration = Hessian product (+ exchange) + cg_step | two-launch form: (cg_step(i - 1) + sweep, reducer)
+    bool tcg_two_launch() const;                       // does the host-driven tCG of the current rank run in the two-launch form?
+    const CgStepArgs *fuse_step_ = nullptr;            // set around the product that carries a step (tcg_enqueue_iteration)
+    int tcg_two_launch_count_ = 0;                     // trust regions of the last solve that ran in the two-launch form (xm_ctx_tcg_two_launch)
     // What the solver's two forms AND the test exports (rtr_probe, outer_probe) launch the tCG's kernels with: a probe overrides single fields, never rebuilds.
     TcgParity tcg_parity(int par) const;   // single rank on partsB_ | communicator with a lockstep gather | fused peer exchange on partsB_peer_
     void cand_role(CamArgs &a, const PointState &P, const double *R, const double *s) const;   // CamArgs::cand: the gradient role of an EPI_AUTO product at (R, s)

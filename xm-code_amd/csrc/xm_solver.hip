@@ -514,7 +514,7 @@ void Context::setup_rank(int o) {
     // rank level and every later solve of the context
     const int o_top = std::max(o, (int)std::min<unsigned>(opt_ ? opt_->max_rank : 0u, (unsigned)kMaxRank));
     const size_t mat_top = (size_t)nloc_ * 3 * pitch_of(o_top);
-    for (DevBuf<double> *b : {&R_, &Rc_, &D_, &rR_, &pR_, &vR_, &HvR_, &HpR_}) b->ensure(mat, st_, mat_top);
+    for (DevBuf<double> *b : {&R_, &Rc_, &D_, &rR_, &rRB_, &pR_, &pRB_, &vR_, &HvR_, &HpR_}) b->ensure(mat, st_, mat_top);
     for (DevBuf<double> *b : {&s_, &sc_, &rs_, &rsB_, &psA_, &psB_, &vs_, &Hvs_, &Hps_}) b->ensure(vec, st_);
     for (int k = 0; k < 2; ++k) {
         ps_[k].G.ensure(mat, st_, mat_top); ps_[k].rgR.ensure(mat, st_, mat_top); ps_[k].egs.ensure(vec, st_); ps_[k].rgs.ensure(vec, st_); ps_[k].S0.ensure(vec * 9, st_);
@@ -681,7 +681,7 @@ void Context::product(int epi, int o, double alpha, const CamArgs &a) {
         else { CamArgs ar = a; ar.rev = sym_rev_; launch_qw_dense_f32(o, epi, dQ32_, dQ_, ld_, W_.p, alpha, ar, st_); }
     } else if (storage_ == XM_STORAGE_DENSE) {
         if (symw_ && o == o_ && o >= 3 && o <= sym_max_o_ && epi != EPI_CERT) product_symw(epi, o, alpha, a);
-        else if (sym_ok_ && o == o_ && o >= 3 && o <= sym_max_o_ && epi != EPI_CERT && symv_) launch_qw_sym(o, epi, dQ_, ld_, W_.p, alpha, a, symv_, st_, sym_rev_);
+        else if (sym_ok_ && o == o_ && o >= 3 && o <= sym_max_o_ && epi != EPI_CERT && symv_) launch_qw_sym(o, epi, dQ_, ld_, W_.p, alpha, a, symv_, st_, sym_rev_, fuse_step_);
         else { CamArgs ar = a; ar.rev = sym_rev_; launch_qw_dense(o, epi, dQ_, ld_, W_.p, alpha, ar, st_); }
     } else if (storage_ == XM_STORAGE_SCHUR) {
         schur_->product(o, epi, W_.p, alpha, a, st_);
@@ -838,12 +838,32 @@ void Context::finish_profile() {
 // ------------------------------------------------------------------------------------------------------------------
 // truncated CG (trustregion.h:559-664): enqueue-ahead with a host-mapped progress word, no host sync per iteration
 // ------------------------------------------------------------------------------------------------------------------
-// one tCG iteration on the stream: the Hessian product of iteration i, the lockstep all-gather when the exchange is not fused, cg_step
+// one tCG iteration on the stream: the Hessian product of iteration i, the lockstep all-gather when the exchange is not fused, cg_step.
+// Two-launch form (tcg_two_launch): the symmetric sweep of iteration i >= 1 carries cg_step(i - 1) in its own launch and derives its product
+// input, the reducer follows; iteration 0 reads W as tcg_init wrote it and carries nothing.  The step of the LAST iteration T therefore runs in
+// launch pair T + 1 -- the pair the host learns the end of the tCG from (run_tcg).
 void Context::tcg_enqueue_iteration(int i, bool profile) {
+    if (tcg_two_launch()) {
+        const CgStepArgs P = (i > 0) ? cg_step_args(i - 1) : CgStepArgs();
+        fuse_step_ = (i > 0) ? &P : nullptr;
+        struct Clear { const CgStepArgs *&p; ~Clear() { p = nullptr; } } clear{fuse_step_};
+        tcg_product(EPI_HESS, tcg_cam_args(tcg_parity(i & 1), false), i & 1, profile);
+        return;
+    }
     const CgStepArgs S = cg_step_args(i);
     tcg_product(EPI_HESS, tcg_cam_args(S.v, false), i & 1, profile);
     if (comm_->active() && xchg_.world <= 1) comm_->allgather(S.v.pcur, S.v.chunk, st_);   // lockstep: the exchange is not fused into cg_step
     launch_cg_step(o_, S, st_);
+}
+
+// Two launches per iteration: one GPU, host-driven outer iteration with run-ahead polling, the f64 symmetric pair at a rank whose sweep can derive its
+// input (o = 3, 4 and a chunk plan whose rows fit the sweep's LDS).  Everything else -- several ranks, XM_FLAG_HOST_STEPPED, the device-driven outer
+// iteration, hess_f32, rank 5 and up, the other storages -- and XM_FLAG_TCG_THREE_LAUNCH keep the three launches.
+bool Context::tcg_two_launch() const {
+    if (!opt_ || (opt_->flags & (XM_FLAG_HOST_STEPPED | XM_FLAG_TCG_THREE_LAUNCH))) return false;
+    if (comm_->active() || comm_->world > 1 || storage_ != XM_STORAGE_DENSE || dQ32_ || symw_ || !sym_ok_ || !symv_ || wpad()) return false;
+    if (o_ < 3 || o_ > sym_max_o_ || !symv_derives(symv_, o_)) return false;
+    return !device_outer_applies(o_);
 }
 
 // tCG partial sums travel in ONE all-gather per iteration: chunk = [Hessian-epilogue partials of this iteration | |r|^2 partials the previous
@@ -855,6 +875,10 @@ TcgParity Context::tcg_parity(int par) const {
     v.scal_cur = scal_.p + par; v.scal_next = scal_.p + (par ^ 1);
     v.ps_cur = par ? psB_.p : psA_.p; v.ps_next = par ? psA_.p : psB_.p;
     v.rs_cur = par ? rsB_.p : rs_.p; v.rs_next = par ? rs_.p : rsB_.p;
+    // (the device-driven outer iteration starts its truncated CGs inside its step launch, whatever the slot's parity: p and r stay in one buffer there)
+    const bool one = opt_ && device_outer_applies(o_);
+    v.pR_cur = (par && !one) ? pRB_.p : pR_.p; v.pR_next = (par || one) ? pR_.p : pRB_.p;
+    v.rR_cur = (par && !one) ? rRB_.p : rR_.p; v.rR_next = (par || one) ? rR_.p : rRB_.p;
     v.b_off = comm_->active() ? (size_t)nloc_ * 3 * OP_ : 0;
     v.chunk = v.b_off + 3 * nA + (size_t)tcg_blocks();
     double *pB = xchg_.world > 1 ? partsB_peer_ : partsB_.p;   // fused peer exchange: the sums live in peer-addressable memory
@@ -871,7 +895,7 @@ void Context::cand_role(CamArgs &a, const PointState &P, const double *R, const 
 
 CamArgs Context::tcg_cam_args(const TcgParity &v, bool cand) const {
     CamArgs a = cam_args(cur_);
-    a.scal = v.scal_cur; a.ps = v.ps_cur; a.rs = v.rs_cur;
+    a.scal = v.scal_cur; a.pR = v.pR_cur; a.ps = v.ps_cur; a.rR = v.rR_cur; a.rs = v.rs_cur;
     a.partials = v.parts; a.Bout = v.Bout;
     if (cand) cand_role(a, ps_[cur_ ^ 1], Rc_.p, sc_.p);
     return a;
@@ -909,7 +933,7 @@ CgStepArgs Context::cg_step_args(int i) const {
     a.nloc = nloc_; a.v = tcg_parity(i & 1);
     a.nA = prod_grid(); a.nB = tcg_blocks(); a.world = comm_->world;
     a.HpR = HpR_.p; a.Hps = Hps_.p; a.R = R_.p; a.s = s_.p;
-    a.pR = pR_.p; a.vR = vR_.p; a.vs = vs_.p; a.HvR = model_rec ? nullptr : HvR_.p; a.Hvs = model_rec ? nullptr : Hvs_.p; a.rR = rR_.p;
+    a.vR = vR_.p; a.vs = vs_.p; a.HvR = model_rec ? nullptr : HvR_.p; a.Hvs = model_rec ? nullptr : Hvs_.p;
     a.Wloc = wpad() ? nullptr : W_.p + (size_t)cam0_ * 3 * OP_; a.Wpad = wpad();
     a.hstat = hstat_dev_; a.mat = (int64_t)nloc_ * 3 * OP_;
     a.Afull = comm_->active() ? Afull_.p : nullptr; a.Wfull = W_.p;
@@ -943,6 +967,10 @@ int Context::enqueue_spec_tcg() {
     return n_spec;
 }
 
+#ifndef XM_TCG_PAIRS_AHEAD
+#define XM_TCG_PAIRS_AHEAD 3   // (a build-time constant so that a variant build can measure the alternative)
+#endif
+constexpr int kTcgPairsAhead = XM_TCG_PAIRS_AHEAD;   // launch pairs the two-launch tCG keeps ahead of the progress word
 int Context::run_tcg(double rr, double delta, int adopted) {
     const bool stepped = (opt_->flags & XM_FLAG_HOST_STEPPED) != 0;
     const bool profile = (opt_->flags & XM_FLAG_PROFILE_QW) != 0;
@@ -963,9 +991,17 @@ int Context::run_tcg(double rr, double delta, int adopted) {
     if (fused) xchg_.epoch_base = (++tcg_runs_) << 12;
     const bool lockstep = comm_->active() && !fused;
     // (single GPU: two iterations ahead, three for the smallest problems, whose iteration is shorter than the host's two launches)
-    const int run_ahead = (lockstep || prod_grid() >= 64) ? 2 : 3;
+    // TWO-LAUNCH FORM: launch pair j carries the step of iteration j - 1, so the pair the host learns the end of the tCG from -- its sweep's first
+    // workgroup publishes the outcome at its head, the step's lead thread again -- is the one that takes the last step: it is always in the queue
+    // already, and the cap is one pair more (pair kMaxInner carries the step that reports status 6).  The final scalar block is the one the last
+    // enqueued pair wrote, scal_[(it - 1) & 1]: pairs behind the end copy it along like the no-op steps of the three-launch form.  Pairs ahead
+    // (kTcgPairsAhead): measured at 3 and at 2 on the headline.
+    const bool two = tcg_two_launch();
+    const int cap = two ? kMaxInner + 1 : kMaxInner;
+    const int run_ahead = two ? kTcgPairsAhead : ((lockstep || prod_grid() >= 64) ? 2 : 3);
     int fin_status = 0, fin_iter = 0;
     int it = adopted;  // iterations enqueued
+    auto fin_par = [&]() { return (two ? std::max(it - 1, 0) : it) & 1; };
     auto enqueue = [&](int i) { tcg_enqueue_iteration(i, profile); };
     auto read_scal = [&](int par) {
         TcgScal sc;
@@ -992,15 +1028,15 @@ int Context::run_tcg(double rr, double delta, int adopted) {
             const int status = valid ? (int)(v & 0xff) : 0;
             const int done = valid ? (int)((v >> 8) & 0xffffff) : 0;
             if (status != 0) { fin_status = status; fin_iter = done; break; }
-            if (it < kMaxInner && it - done < run_ahead) { enqueue(it++); continue; }
+            if (it < cap && it - done < run_ahead) { enqueue(it++); continue; }
             __builtin_ia32_pause();
             if (secs_since(last_progress) > 200e-6) {
                 // Nothing new for a while: if the stream has drained the progress word is stale (or this platform does not
                 // make device writes to mapped host memory visible promptly) -> read the truth from the device.
                 if (stream_idle(last_change, "the truncated-CG progress word")) {
-                    TcgScal sc = read_scal(it & 1);
+                    TcgScal sc = read_scal(fin_par());
                     if (sc.status != 0) { fin_status = sc.status; fin_iter = sc.iter; break; }
-                    if (it >= kMaxInner) { fin_status = 6; fin_iter = kMaxInner; break; }
+                    if (it >= cap) { fin_status = 6; fin_iter = kMaxInner; break; }
                     *hstat_ = ((unsigned long long)tcg_seq_ << 32) | ((unsigned long long)(unsigned)sc.iter << 8);
                     if (it - sc.iter >= run_ahead) enqueue(it++);  // cannot happen, but never stall
                 }
@@ -1014,7 +1050,7 @@ int Context::run_tcg(double rr, double delta, int adopted) {
         const int T = (fin_status == 6) ? fin_iter - 1 : fin_iter;   // iteration in which the tCG ended
         while (it < std::min(kMaxInner, T + 2)) enqueue(it++);      // no-ops, but the same collectives on every rank
     }
-    return it;  // the final scalar block is scal_[it & 1]; the caller fetches it together with the other results
+    return two ? std::max(it - 1, 0) : it;  // the final scalar block is scal_[(return value) & 1]; the caller fetches it together with the other results
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1074,6 +1110,7 @@ TrResult Context::trust_region(int o, double &gradtol, double linesearch_step, c
     }
     eval_point(cur_, R_.p, s_.p, f, rr);  // loss[0] and the gradient state of the first outer iteration
     if (device_outer_applies(o)) return trust_region_device(o, gradtol, f, rr, delta, delta_bar, max_time);
+    if (tcg_two_launch()) tcg_two_launch_count_++;
     double loss = f;
 
     int endreason = 6, trstatus = 4, shrink_count = 0, inner_print = 1, k = 0;
@@ -1845,8 +1882,8 @@ void Context::rtr_probe(xm_rtr_probe_t &q) {
         I.rgR = D_.p; I.rgs = sc_.p;    // "rg" = -p
         I.hstat = nullptr; I.seq = 0;   // no host progress word (nor a run number for it)
         launch_tcg_init(o, I, st_);
-        up_mat(pR_.p, q.pR, 1.0); up_vec(v.ps_cur, q.ps, 1.0, false);   // the vectors as given: what they hold at the anchor must not get through
-        up_mat(rR_.p, q.rR, 1.0); up_vec(v.rs_cur, q.rs, 1.0, false);
+        up_mat(v.pR_cur, q.pR, 1.0); up_vec(v.ps_cur, q.ps, 1.0, false);   // the vectors as given: what they hold at the anchor must not get through
+        up_mat(v.rR_cur, q.rR, 1.0); up_vec(v.rs_cur, q.rs, 1.0, false);
         TcgScal sc;
         std::memset(&sc, 0, sizeof(sc));
         if (want_step) {
@@ -1867,6 +1904,7 @@ void Context::rtr_probe(xm_rtr_probe_t &q) {
             up_mat(vR_.p, q.vR, 1.0); up_vec(vs_.p, q.vs, 1.0, false);
             if (!model_rec) { up_mat(HvR_.p, q.HvR, 1.0); up_vec(Hvs_.p, q.Hvs, 1.0, false); }
             up_vec(v.ps_next, q.ps, 1.0, false); up_vec(v.rs_next, q.rs, 1.0, false);   // a branch that leaves them alone returns the input
+            if (v.pR_next != v.pR_cur) { up_mat(v.pR_next, q.pR, 1.0); up_mat(v.rR_next, q.rR, 1.0); }
             if (q.scal_in.iter > 0) to_dev(v.parts + (size_t)3 * nA, q.partsB_in, (size_t)nB * sizeof(double));
             XM_HIP_CHECK(hipMemsetAsync(v.partsB_out, 0, (size_t)nB * sizeof(double), st_));
             CgStepArgs S = cg_step_args(iter);
@@ -1882,7 +1920,7 @@ void Context::rtr_probe(xm_rtr_probe_t &q) {
             scal_out(nx, q.scal_out);
             down_mat(q.out_vR, vR_.p); down_vec(q.out_vs, vs_.p);
             if (!model_rec) { down_mat(q.out_HvR, HvR_.p); down_vec(q.out_Hvs, Hvs_.p); }
-            down_mat(q.out_rR, rR_.p); down_vec(q.out_rs, v.rs_next); down_mat(q.out_pR, pR_.p); down_vec(q.out_ps, v.ps_next);
+            down_mat(q.out_rR, v.rR_next); down_vec(q.out_rs, v.rs_next); down_mat(q.out_pR, v.pR_next); down_vec(q.out_ps, v.ps_next);
             if (Wtcg) down_mat(q.out_W, Wloc);
             if (wpad()) down_vec(q.out_Wpad, wpad(), 16);
             if (q.partsB_out) to_host(q.partsB_out, v.partsB_out, (size_t)nB * sizeof(double));
@@ -2095,8 +2133,8 @@ void Context::outer_probe(xm_outer_probe_t &q) {
             I.Wloc = Wloc; I.Wpad = nullptr;   // the native-pitch input only, as outer_step_args() (the device-driven form keeps no padded copy)
             launch_tcg_init(o, I, st_);
         }
-        up_mat(pR_.p, q.pR, 1.0); up_vec(v.ps_cur, q.ps, 1.0, false); up_vec(v.ps_next, q.ps, 1.0, false);
-        up_mat(rR_.p, q.rR, 1.0); up_vec(v.rs_cur, q.rs, 1.0, false); up_vec(v.rs_next, q.rs, 1.0, false);
+        up_mat(v.pR_cur, q.pR, 1.0); up_vec(v.ps_cur, q.ps, 1.0, false); up_vec(v.ps_next, q.ps, 1.0, false);
+        up_mat(v.rR_cur, q.rR, 1.0); up_vec(v.rs_cur, q.rs, 1.0, false); up_vec(v.rs_next, q.rs, 1.0, false);
         up_mat(vR_.p, q.vR, 1.0); up_vec(vs_.p, q.vs, 1.0, false);
         up_mat(HvR_.p, q.HvR, 1.0); up_vec(Hvs_.p, q.Hvs, 1.0, false);
         if (q.Rc && q.sc) { up_mat(Rc_.p, q.Rc, 1.0); up_vec(sc_.p, q.sc, 1.0, false); }
@@ -2166,7 +2204,7 @@ void Context::outer_probe(xm_outer_probe_t &q) {
         }
         down_mat(q.out_R, R_.p); down_vec(q.out_s, s_.p); down_mat(q.out_Rc, Rc_.p); down_vec(q.out_sc, sc_.p);
         down_mat(q.out_vR, vR_.p); down_vec(q.out_vs, vs_.p); down_mat(q.out_HvR, HvR_.p); down_vec(q.out_Hvs, Hvs_.p);
-        down_mat(q.out_rR, rR_.p); down_vec(q.out_rs, v.rs_next); down_mat(q.out_pR, pR_.p); down_vec(q.out_ps, v.ps_next);
+        down_mat(q.out_rR, v.rR_next); down_vec(q.out_rs, v.rs_next); down_mat(q.out_pR, v.pR_next); down_vec(q.out_ps, v.ps_next);
         down_mat(q.out_W, Wloc);
         if (wpad()) down_vec(q.out_Wpad, wpad(), 16);
         if (q.out_partsB) to_host(q.out_partsB, v.partsB_out, (size_t)nB * sizeof(double));
@@ -2502,6 +2540,7 @@ void Context::solve(const xm_options_t &opt, xm_result_t &res) {
     if (opt.sum_grouping < 0 || opt.sum_grouping > 2) throw Error(XM_ERR_ARG, "sum_grouping must be 0, 1 or 2");
     retraction_ = opt.retraction;
     grouping_ = opt.sum_grouping;
+    tcg_two_launch_count_ = 0;
     double *Rout = res.R, *sout = res.s;
     std::memset(&res, 0, sizeof(res));
     res.R = Rout; res.s = sout;

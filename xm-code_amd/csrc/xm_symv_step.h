@@ -85,9 +85,10 @@ __device__ __forceinline__ double symv_wrow_request(const double *__restrict__ W
     return W[wi < wlim ? wi : wlim];
 }
 // row r of the step out of the requested lane values; ok (wave-uniform: scalar select) is false for a row past the end (odd camera count)
-template <int O>
+// (P: pitch of a row among the lanes -- OP as requested from memory; O where a sweep that derives W keeps the rows without their pad, qw_symv_kernel)
+template <int O, int P = pitch_of(O)>
 __device__ __forceinline__ void symv_wrow_read(double wl, int r, bool ok, double (&wr)[O]) {
-    constexpr int OP = pitch_of(O);
+    constexpr int OP = P;
 #pragma unroll
     for (int k = 0; k < O; ++k) {
         const int lo = __builtin_amdgcn_readlane(__double2loint(wl), r * OP + k), hi = __builtin_amdgcn_readlane(__double2hiint(wl), r * OP + k);
