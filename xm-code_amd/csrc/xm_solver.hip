@@ -968,7 +968,7 @@ int Context::enqueue_spec_tcg() {
 }
 
 #ifndef XM_TCG_PAIRS_AHEAD
-#define XM_TCG_PAIRS_AHEAD 3   // (a build-time constant so that a variant build can measure the alternative)
+#define XM_TCG_PAIRS_AHEAD 2   // (a build-time constant so that a variant build can measure the alternative)
 #endif
 constexpr int kTcgPairsAhead = XM_TCG_PAIRS_AHEAD;   // launch pairs the two-launch tCG keeps ahead of the progress word
 int Context::run_tcg(double rr, double delta, int adopted) {
@@ -995,7 +995,8 @@ int Context::run_tcg(double rr, double delta, int adopted) {
     // workgroup publishes the outcome at its head, the step's lead thread again -- is the one that takes the last step: it is always in the queue
     // already, and the cap is one pair more (pair kMaxInner carries the step that reports status 6).  The final scalar block is the one the last
     // enqueued pair wrote, scal_[(it - 1) & 1]: pairs behind the end copy it along like the no-op steps of the three-launch form.  Pairs ahead
-    // (kTcgPairsAhead): measured at 3 and at 2 on the headline.
+    // (kTcgPairsAhead): 2 -- the pair behind the one that runs is in the queue, a third only adds a no-op pair per truncated CG; measured against 3
+    // on the headline in two rounds, 0.5 us per iteration ahead in every run (profiles/r32_pairs_ahead.txt, r33_pairs_ahead.txt).
     const bool two = tcg_two_launch();
     const int cap = two ? kMaxInner + 1 : kMaxInner;
     const int run_ahead = two ? kTcgPairsAhead : ((lockstep || prod_grid() >= 64) ? 2 : 3);
