@@ -289,7 +289,12 @@ int64_t xm_dense_ld(int64_t n);                                       /* padded 
  *   attach:    edges e = (ei[e], ej[e]), ei != ej, M: ne x 9 row-major; the stored pattern must hold both blocks of every edge and
  *              every diagonal block.  Does not change Q.
  *   residuals: res[e] = |Y_i - M_e Y_j|_F^2 with Y = s.*R of the LAST solve (the edge's share of <Q, Y Y^T> per unit weight)
- *   weights:   rewrites every edge block and every diagonal block from w (w[e] = 0 removes an observation).
+ *   weights:   rewrites every edge block and every diagonal block from w: each off-diagonal entry is the one product (-w[e]) * M_e[k], each
+ *              diagonal block (the f64 sum of the incident weights in edge order) * I.  w[e] = 0 removes an observation, and -0.0 IS 0
+ *              everywhere: the same Q (up to the sign of a zero), the same filter.  On dense and BSR3 storage the rewrite is linear,
+ *              so a negative weight is legal there; on a context whose sliced-ELL copy uses the quaternion codec (XM_STORAGE_VIEWGRAPH, or
+ *              sell_codec = 2) the weight is read back as a norm, so a negative or NaN weight is XM_ERR_ARG, with Q and the context's
+ *              weights unchanged.
  * XM_STORAGE_SCHUR contexts need no attach: their observations ARE the edges -- residuals: one per observation in input order,
  * |p^T U_i + t_i - P_l|^2 with the eliminated translations / landmarks of the last solution (what the reference computes from
  * recover_XM's p_est / t_est, 3_test_colmap_glomap.py:305-316); weights: one per observation (Q1, V1, Q3 and the reduced camera
@@ -301,11 +306,19 @@ int xm_ctx_set_edge_weights(xm_ctx_t *ctx, const double *w);
  *   residuals_recovered: res[e] = squared distance of edge / observation e for the RECOVERED solution -- rot: 3 x 3n column-major anchored
  *              rotations and scale: n, as xm_recover_rotations returns them (the reference's R_real / s_real, :295-316).  Matrix-free
  *              contexts: |s_i R_i p + t_i - P_l|^2 with t, P eliminated (== the reference's landmarks_transformed vs p_est); view-graph
- *              contexts: |s_i R_i - M_e s_j R_j|_F^2.  Host array, input order.  Single-GPU contexts.
- *   xm2_filter: error = w .* res on the device, threshold = np.percentile(error, pct) (linear interpolation between two order
- *              statistics found by a device radix select, :321), weights of everything above it set to 0 and Q rebuilt (:323-338,
- *              without the reference's re-indexing of emptied landmarks / cameras: that is xm_ctx_clean_observations below, which
- *              answers for the filtered list without an upload).
+ *              contexts: |s_i R_i - M_e s_j R_j|_F^2 with R_i the camera's 3 x 3 record of the solution, the TRANSPOSE of its anchored
+ *              block rot[:, 3i .. 3i+2].  Host array, input order.  Single-GPU contexts.
+ *   xm2_filter: error = w .* res on the device over the LIVE edges (w != 0; an edge with w = +0.0 or -0.0 has been removed, has error +0.0
+ *              and takes no part).  threshold = the value at the EXACT position h = (nlive - 1) * pct / 100 of the sorted live errors:
+ *              x[floor h] + (h - floor h) (x[floor h + 1] - x[floor h]), the two order statistics found by a device radix select (:321);
+ *              with h integral, or two equal neighbours, it is that order statistic bit for bit.  This is np.percentile's "linear" rule
+ *              with the position computed exactly; numpy computes it as (nlive - 1) * (pct / 100) and so lands one element lower
+ *              at some (nlive, pct), e.g. nlive = 91, pct = 70: 62.99999999999999 for 63 (pct = 70, 35 and 57 do this, the reference's
+ *              90 and 95, 50, 10, 30, 99, 0.1, 99.9 do not).  Every live edge with error > threshold gets weight +0.0 (an error equal to
+ *              the threshold stays), and Q is rebuilt (:323-338, without the reference's re-indexing of emptied landmarks / cameras:
+ *              that is xm_ctx_clean_observations below, which answers for the filtered list without an upload).  The select is defined
+ *              for non-negative errors: XM_ERR_ARG, with Q and the weights unchanged, for a negative or NaN current weight, pct outside
+ *              [0, 100] or NaN, no live edge left, or a dense / BSR3 context before xm_ctx_set_edge_weights.
  *   xm2_round: filter at `percentile` (0 -> 90), then the reference's second pass (:339-351): solve_rank3 at lam = 0, statistics of its
  *              scales; |mean(s[1:]) - 1| > 2 std(s[1:]) or more than 10 scales < 0.1  ->  lam = kept edges / n, else lam = 0; final solve
  *              with opt->max_rank / tol / max_time / flags (XM_FLAG_WARM_R in opt->flags: start it from the rank-3 result instead of the

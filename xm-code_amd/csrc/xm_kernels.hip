@@ -2434,10 +2434,11 @@ __global__ __launch_bounds__(256) void edge_residual_kernel(int64_t ne, const in
 }
 
 // ---- XM^2 outlier filter on the device (reference: np.percentile(error, 90) and the index filter, 3_test_colmap_glomap.py:316-324) ----
-// err = w .* res
+// err = w .* res; a removed edge (w = +0.0 or -0.0) has error +0.0 whatever its residual: -0.0 * res = -0.0 would sort BEHIND every
+// positive double in the select below, which counts on the removed edges in front
 __global__ __launch_bounds__(256) void xm2_error_kernel(int64_t n, const double *__restrict__ w, const double *__restrict__ res, double *__restrict__ err) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e < n) err[e] = w[e] * res[e];
+    if (e < n) err[e] = (w[e] == 0.0) ? 0.0 : w[e] * res[e];
 }
 // One pass of a most-significant-digit radix SELECT over non-negative doubles (their bit patterns order like unsigned integers):
 // histogram of the 16 bits at `shift` over the elements whose higher bits equal `prefix`.  Integer atomics: exact and order-free.
@@ -2449,13 +2450,13 @@ __global__ __launch_bounds__(256) void radix_hist_kernel(int64_t n, const double
         atomicAdd(hist + ((k >> shift) & 0xffffull), 1u);
     }
 }
-// wout = err > thr ? 0 : w ; per-block counts of the removed entries (integers)
+// wout = err > thr ? 0 : w (a removed edge comes out as +0.0, also one that came in as -0.0); count of the newly removed entries
 __global__ __launch_bounds__(256) void xm2_filter_kernel(int64_t n, const double *__restrict__ err, const double *__restrict__ w, double thr,
                                                           double *__restrict__ wout, unsigned int *__restrict__ removed) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= n) return;
     const bool rm = err[e] > thr;
-    wout[e] = rm ? 0.0 : w[e];
+    wout[e] = (rm || w[e] == 0.0) ? 0.0 : w[e];
     if (rm && w[e] != 0.0) atomicAdd(removed, 1u);
 }
 

@@ -2359,10 +2359,31 @@ static double radix_select(const double *x, int64_t n, int64_t k, unsigned int *
     return v;
 }
 
+// Position h = (nlive - 1) * pct / 100 of a percentile: floor(h) exactly (the return value) and frac(h) to two roundings.  The plain
+// (double)(nlive - 1) * pct / 100.0 has the right floor, but its fractional part carries the rounding of h itself: nlive * eps of the gap
+// between the two order statistics, which is far more than the threshold's own round-off where they are decades apart.
+static int64_t percentile_position(int64_t nlive, double pct, double &frac) {
+    const double a = (double)(nlive - 1);
+    const double hi = a * pct, lo = std::fma(a, pct, -hi);   // a * pct == hi + lo exactly
+    int64_t k = (int64_t)std::floor(hi / 100.0);
+    double r = (hi - 100.0 * (double)k) + lo;                // the difference is exact (k is within one of hi / 100); one rounding
+    while (r < 0.0) { --k; r += 100.0; }                     // rounding keeps the sign and the side of 100: the floor is exact
+    while (r >= 100.0) { ++k; r -= 100.0; }
+    frac = r / 100.0;
+    return k;
+}
+
 double Context::xm2_filter(const double *rot, const double *scale, double pct, int64_t *removed, double *w_out) {
     if (!(pct >= 0.0 && pct <= 100.0)) throw Error(XM_ERR_ARG, "xm2_filter: percentile must be in [0, 100]");
     const int64_t ne = schur_ ? schur_->nobs() : ne_;
     if ((int64_t)w_cur_.size() != ne || ne < 1) throw Error(XM_ERR_ARG, "xm2_filter: the context does not know its edge weights (view-graph / matrix-free storage, or call xm_ctx_set_edge_weights first)");
+    // the select orders bit patterns, which is the order of the values for non-negative doubles only
+    for (int64_t e = 0; e < ne; ++e)
+        if (!(w_cur_[(size_t)e] >= 0.0)) throw Error(XM_ERR_ARG, "xm2_filter: a negative or NaN weight (edge " + std::to_string(e) + ")");
+    int64_t nz = 0;
+    for (int64_t e = 0; e < ne; ++e) nz += (w_cur_[(size_t)e] == 0.0);   // -0.0 counts: a weight of -0.0 is a weight of 0
+    const int64_t nlive = ne - nz;
+    if (nlive < 1) throw Error(XM_ERR_ARG, "xm2_filter: every edge has been removed already");
     const double *res = residuals_recovered_device(rot, scale);
     if (ew_.count < (size_t)ne) ew_.alloc((size_t)ne);
     if (eerr_.count < (size_t)ne) eerr_.alloc((size_t)ne);
@@ -2370,19 +2391,15 @@ double Context::xm2_filter(const double *rot, const double *scale, double pct, i
     launch_xm2_error(ne, ew_.p, res, eerr_.p, st_);
     DevBuf<unsigned int> hist;
     hist.alloc(65536 + 1);
-    // numpy.percentile, method "linear": h = (n - 1) q; x[floor h] + (h - floor h) (x[floor h + 1] - x[floor h]) -- over the edges that are
-    // still THERE: the reference deletes the removed ones before the next round's percentile (3_test_colmap_glomap.py:321-328).  Here a
-    // removed edge keeps its place with weight 0, hence error 0: the nz zeros sort in front of every live error (>= 0), so the k-th order
-    // statistic of the survivors is entry k + nz of the whole array.
-    int64_t nz = 0;
-    for (int64_t e = 0; e < ne; ++e) nz += (w_cur_[(size_t)e] == 0.0);
-    const int64_t nlive = ne - nz;
-    if (nlive < 1) throw Error(XM_ERR_ARG, "xm2_filter: every edge has been removed already");
-    const double hq = (double)(nlive - 1) * pct / 100.0;
-    const int64_t k0 = (int64_t)std::floor(hq), k1 = std::min<int64_t>(k0 + 1, nlive - 1);
+    // numpy.percentile's "linear" rule at the exact position h = (n - 1) q / 100: x[floor h] + (h - floor h) (x[floor h + 1] - x[floor h])
+    // -- over the edges that are still THERE: the reference deletes the removed ones before the next round's percentile
+    // (3_test_colmap_glomap.py:321-328).  Here a removed edge keeps its place with weight 0 and error +0.0 (xm2_error_kernel): the nz zeros
+    // sort in front of every live error (>= 0), so the k-th order statistic of the survivors is entry k + nz of the whole array.
+    double frac = 0.0;
+    const int64_t k0 = std::min<int64_t>(percentile_position(nlive, pct, frac), nlive - 1), k1 = std::min<int64_t>(k0 + 1, nlive - 1);
     const double x0 = radix_select(eerr_.p, ne, k0 + nz, hist.p, st_);
-    const double x1 = (k1 == k0) ? x0 : radix_select(eerr_.p, ne, k1 + nz, hist.p, st_);
-    const double thr = x0 + (hq - (double)k0) * (x1 - x0);
+    const double x1 = (k1 == k0 || frac == 0.0) ? x0 : radix_select(eerr_.p, ne, k1 + nz, hist.p, st_);   // an integral position: the order statistic itself
+    const double thr = x0 + frac * (x1 - x0);
     XM_HIP_CHECK(hipMemsetAsync(hist.p + 65536, 0, sizeof(unsigned int), st_));
     DevBuf<double> wn;
     wn.alloc((size_t)ne, false);
@@ -2520,6 +2537,9 @@ void Context::set_edge_weights(const double *w) {
     }
     if (!ei_.p) throw Error(XM_ERR_ARG, "set_edge_weights: no edges attached");
     if (ne_ > 0 && !w) throw Error(XM_ERR_ARG, "set_edge_weights: null weights");
+    if (sell_ && sell_->codec() == SELL_CODEC_QUAT)   // the codec reads the weight back as the norm of the block: -w M_e would come back as w M_e
+        for (int64_t e = 0; e < ne_; ++e)
+            if (!(w[e] >= 0.0)) throw Error(XM_ERR_ARG, "set_edge_weights: a negative or NaN weight (edge " + std::to_string(e) + ") under the view-graph codec");
     w_cur_.assign(w, w + ne_);
     if (ne_ > 0) to_dev(ew_.p, w, (size_t)ne_ * sizeof(double));
     const bool dense = (storage_ == XM_STORAGE_DENSE);

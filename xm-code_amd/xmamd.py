@@ -2464,7 +2464,9 @@ class Context:
         return res
 
     def xm2_filter(self, rot, scale, percentile=90.0):
-        """the reference's percentile filter on the device -> (threshold, newly removed, new weights); Q is rebuilt"""
+        """the reference's percentile filter on the device -> (threshold, newly removed, new weights); Q is rebuilt.  The threshold sits at the
+        exact position (nlive - 1) * percentile / 100 of the live errors; a weight of -0.0 is a removed edge like 0, removed edges come back
+        as +0.0; a negative or NaN current weight is refused (xm_ctx_xm2_filter)"""
         rot = np.asfortranarray(np.asarray(rot, dtype=np.float64)); scale = np.ascontiguousarray(np.asarray(scale, dtype=np.float64).reshape(-1))
         thr = C.c_double(); rm = C.c_int64(); w = np.zeros(self.ne)
         _chk(lib().xm_ctx_xm2_filter(self.h, rot.ctypes.data_as(C.c_void_p), scale.ctypes.data_as(C.c_void_p), percentile, C.byref(thr), C.byref(rm),
