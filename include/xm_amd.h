@@ -1379,6 +1379,47 @@ int xm_symv_plan(int64_t n, int32_t plan[4]);
  * predicate "row step t uses block (t, u)" of a matrix of T steps. */
 int xm_symw_plan(int64_t ntot, int nloc, int cam0, int K, int32_t geom[8], int32_t *items);
 int xm_symw_use(int T, int t, int u);
+/* Test export (the xm_la_probe pattern: no context, host arrays that go up and come back whole): ONE rank's share of the multi-rank symmetric
+ * product, kernel by kernel -- qw_symw_kernel + symw_colsum_kernel (SymwProduct::sweep), then symw_reduce_kernel with the plain epilogue
+ * (SymwProduct::reduce) -- with every stage returned (tests/test_gpu_symw_stages.py).  The rank is cam0 / nloc of world ranks with
+ * world * nloc == ntot, as a context sets them up; cameras in the padded numbering (ntot, nloc, cam0 even).
+ *   in   o            1, 3, 4 or 5
+ *        K            <= 0: the automatic chunk length, else the chunk length of the plan (xm_symw_plan); comes back as used
+ *        nt           -1: the load policy the solver would choose, 0 / 1: the cached / non-temporal instantiation; comes back as used (0 / 1)
+ *        scal_status  -1: no status word (null), 0: a status word that says "running", 1: one that says "stopped" -- the sweep and the
+ *                     column sums then write nothing
+ *        Q            this rank's strip, 3 nloc x 3 ntot, row-major, compact.  The probe lays it out at the leading dimension of the solver
+ *                     (the next multiple of 128) and fills the padding columns with pad_value
+ *        pad_value    FINITE.  The kernels mask a padding column by a product with zero (x * 0), never by a select, so whatever pads
+ *                     a dense Q on the device must be finite: a NaN or an infinity there would reach every row of the strip
+ *        W            3 ntot x o, row-major, compact
+ *        cs_all       world x 3 ntot x o (in/out): the other ranks' column-sum vectors as the all-gather would deliver them; the slot of
+ *                     this rank is overwritten by the device result
+ *   out  (each filled when its pointer is not null; Prow, Pcol and this rank's slot of cs_all hold a quiet-NaN sentinel before the
+ *        sweep, so a record that was never written shows)
+ *        Prow         nstrips x 6 nsteps x o: the row-direction partial sums per (strip, local row)
+ *        Pcol         max(items, 1) x 256 x o: the column sums per work item
+ *        csum         3 ntot x o: this rank's column sums (the slot of cs_all)
+ *        Y            3 nloc x o, compact: alpha * (row sums + every rank's column sums)
+ *        nitems, nfull  work items of the plan; (item, step) pairs that take the unmasked path (symw_full)
+ * XM_ERR_ARG, nothing written, before any device call: a struct_size that is not sizeof, o outside {1, 3, 4, 5}, ntot, nloc or cam0 odd or
+ * out of order (cam0 + nloc > ntot, cam0 no multiple of nloc, world * nloc != ntot), ntot above XM_SYMW_PROBE_MAX_NTOT, nt outside
+ * {-1, 0, 1}, scal_status outside {-1, 0, 1}, alpha or pad_value not finite, a null Q, W or cs_all. */
+#define XM_SYMW_PROBE_MAX_NTOT 4096
+typedef struct {
+    uint32_t struct_size;
+    int32_t ntot, nloc, cam0, world;
+    int32_t o;
+    int32_t K;                 /* in/out */
+    int32_t nt;                /* in/out */
+    int32_t scal_status;
+    int32_t nitems, nfull;     /* out */
+    double alpha, pad_value;
+    const double *Q, *W;
+    double *cs_all;            /* in/out */
+    double *Prow, *Pcol, *csum, *Y;
+} xm_symw_probe_t;
+int xm_symw_probe(xm_symw_probe_t *probe);
 /* Aggregates of the two-level preconditioner (xm_tuning_t.schur_solver = 3) for an observation list, host-only (CPU test): the cameras
  * 1..n-1 in breadth-first order over the camera-landmark graph from camera 0 (landmarks seen more than 64 times are not expanded), unreached
  * cameras appended, cut into runs of B (1..64; the solver uses 64).  agg_of_camera[n]: aggregate of every camera, -1 for camera 0.  More

@@ -354,6 +354,9 @@ def _team_worker_code():
         elif case == "dense_sym":                                 # symmetric window product of the row partition (tuning sym = 1), rank escalation
             P = tl.gen_vg(41, deg=3, sigma=1.5, seed=40)
             ctx = xmamd.Context(Q=P["Q"], **kw); args = (6, 1e-9, 3.0)
+        elif case == "dense_sym300" or case == "dense300":        # the same beyond one strip of 256 columns: four strips, whole strips inside the
+            P = tl.gen_vg(300, deg=3, sigma=0.3, seed=300)       # window (unmasked path); certifies at rank 5, so o = 4, 5 run through the window too
+            ctx = xmamd.Context(Q=P["Q"], **kw); args = (6, 1e-9, 3.0)
         elif case == "rome_dense":                                # BASELINE config 5 in the reference's dense storage: 13.5 GB, every rank expands its rows
             P = tl.gen_vg(13682, deg=30, sigma=0.05, seed=13682, dense=False)
             ctx = xmamd.Context(bsr=(P["rowptr"], P["colidx"], P["blocks"]), densify=True, **kw); args = (5, 1e-6, 1000.0)
@@ -491,30 +494,33 @@ def test_eight_virtual_gpus(xmamd, tmp_path, case):
         assert float(t["primal2"]) == pytest.approx(float(a["primal2"]), rel=1e-8)
 
 
-@pytest.mark.parametrize("world", [2, 3, 4])
-def test_symmetric_window_product_under_the_row_partition(xmamd, tmp_path, world):
+@pytest.mark.parametrize("world,cams", [(2, 41), (3, 41), (4, 41), (2, 300), (4, 300)], ids=["2", "3", "4", "2-300cams", "4-300cams"])
+def test_symmetric_window_product_under_the_row_partition(xmamd, tmp_path, world, cams):
     """Dense symmetric Q on `world` ranks through the cyclic half window (xm_symw.h; forced on a test-sized problem with tuning sym = 1): every
     rank streams about half of its row strip, the ranks all-gather their column sums between the two launches of a product.  The
     single-process team must reproduce the `world`-process run over the shared-memory transport BIT FOR BIT (same partition, same
     arithmetic, fixed summation orders) and both the single-GPU optimum (rank escalation included: o = 4, 5, 6 fall back to the general
-    kernel above sym_max_o)."""
+    kernel above sym_max_o).  41 cameras are one strip of 256 columns; 300 are four, with whole strips inside the window (the sweep's
+    unmasked path), blocks cut by strip boundaries and a staircase that ends at rank 5 (o = 4, 5 and the fused gradient and Hessian
+    epilogues of the reducer beyond one strip; the kernels themselves: tests/test_gpu_symw_stages.py)."""
     code = _team_worker_code()
+    sym_case, one_case = ("dense_sym", "dense") if cams == 41 else ("dense_sym300", "dense300")
     env = dict(os.environ, XM_SHM_TIMEOUT="60", XM_WATCHDOG_S="60", XMT_TUNING='{"sym": 1}')
     name = "/xm_t4s_" + uuid.uuid4().hex[:12]
     outs = [str(tmp_path / f"shm{r}.npz") for r in range(world)]
-    procs = [subprocess.Popen([sys.executable, "-c", code, f"shm{r}", str(world), outs[r], "dense_sym", name], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    procs = [subprocess.Popen([sys.executable, "-c", code, f"shm{r}", str(world), outs[r], sym_case, name], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
              for r in range(world)]
     logs = [p.communicate(timeout=600)[0].decode() for p in procs]
     assert all(p.returncode == 0 for p in procs), "\n".join(l[-1500:] for l in logs)
     team, one = str(tmp_path / "team.npz"), str(tmp_path / "one.npz")
-    _run(code, ["team", world, team, "dense_sym"], env)
-    _run(code, ["single", 1, one, "dense"], dict(env, XMT_TUNING='{"sym": -1}'))
+    _run(code, ["team", world, team, sym_case], env)
+    _run(code, ["single", 1, one, one_case], dict(env, XMT_TUNING='{"sym": -1}'))
     t, a = np.load(team), np.load(one)
     for o_ in outs:
         b = np.load(o_)
         assert int(b["sym"]) == 1 and np.array_equal(t["R"], b["R"]) and np.array_equal(t["s"], b["s"]) and np.array_equal(t["trace"], b["trace"])
     assert int(t["sym"]) == 1 and int(t["exchange"]) == 1                      # all-gather between the launches (no fused exchange on this path)
-    assert int(t["rank"]) == int(a["rank"]) and int(t["status"]) == int(a["status"]) == 1
+    assert int(t["rank"]) == int(a["rank"]) and int(t["status"]) == int(a["status"]) == 1 and (cams == 41 or int(t["rank"]) == 5)
     assert float(t["primal"]) == pytest.approx(float(a["primal"]), rel=1e-9)
     assert tl.rotation_parity(t["R"], t["s"], a["R"], a["s"]) < 1e-6
 

@@ -4,6 +4,8 @@ strip, and a numpy restatement of the sweep + all-gather + per-camera sum reprod
 import numpy as np
 import pytest
 
+import xm_symw_stages as st
+
 
 @pytest.mark.parametrize("T", [1, 2, 3, 4, 7, 8, 21, 22])
 def test_window_uses_exactly_one_block_of_every_mirror_pair(xmamd, T):
@@ -15,12 +17,7 @@ def test_window_uses_exactly_one_block_of_every_mirror_pair(xmamd, T):
     assert set(use.sum(axis=1).tolist()) <= {(T - 1) // 2, T // 2}
 
 
-def _any(g, t, s):
-    lo, hi = (s * 256) // 6, min((s * 256 + 255) // 6, g["T"] - 1)
-    if lo > g["T"] - 1:
-        return False
-    dlo, dhi = (lo - t) % g["T"], (hi - t) % g["T"]
-    return dlo > dhi or dlo <= g["Th"]
+_any = st.any_pair
 
 
 @pytest.mark.parametrize("ntot,world", [(44, 2), (176, 4), (1024, 8), (700, 2), (13696, 8)])
@@ -58,31 +55,9 @@ def test_window_product_model_reproduces_the_symmetric_product(xmamd, ntot, worl
     lib = xmamd.lib()
     plans = [xmamd.symw_plan(ntot, nloc, r * nloc, K=3) for r in range(world)]
     T = plans[0]["T"]
-    use = np.array([[lib.xm_symw_use(T, t, u) for u in range(T)] for t in range(T)], dtype=bool)
-    csum = np.zeros((world, M, o)); prow = [dict() for _ in range(world)]
-    for r, g in enumerate(plans):
-        Qr = Q[3 * r * nloc:3 * (r + 1) * nloc]                      # this rank's strip
-        for s, jb, je in g["items"]:
-            c0, c1 = s * 256, min(s * 256 + 256, M)
-            ucol = np.arange(c0, c1) // 6
-            for j in range(jb, je):
-                t = g["t0"] + j
-                B = Qr[6 * j:6 * j + 6, c0:c1]
-                mc = use[t, ucol]; mr = mc | (ucol == t)
-                prow[r][(int(s), j)] = (B * mr) @ W[c0:c1]            # row direction -> this rank's rows
-                csum[r, c0:c1] += (B * mc).T @ W[6 * t:6 * t + 6]     # column direction -> whoever owns those cameras
-    out = np.zeros((M, o))
-    for r, g in enumerate(plans):
-        for cam in range(nloc):
-            j, t = cam // 2, g["t0"] + cam // 2
-            acc = np.zeros((3, o))
-            for s in range(g["nstrips"]):
-                if _any(g, t, s):
-                    acc += prow[r][(s, j)][3 * (cam & 1):3 * (cam & 1) + 3]
-            grow = 3 * (r * nloc + cam)
-            for r2 in range(world):
-                acc += csum[r2, grow:grow + 3]
-            out[grow:grow + 3] = acc
+    use = np.array([[lib.xm_symw_use(T, t, u) for u in range(T)] for t in range(T)], dtype=bool)      # the library's predicate, not the restatement
+    assert np.array_equal(use, st.use_matrix(T))
+    out, _, _ = st.whole_model(Q, W, world, plans, use)
     assert np.linalg.norm(out - Q @ W) <= 1e-12 * np.linalg.norm(Q @ W)
 
 
@@ -94,6 +69,7 @@ def _symw_rank_worker(rank, world, port, ntot, o, out_dir):
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, here); sys.path.insert(0, os.path.join(os.path.dirname(here), "xm-code_amd"))
     import xmamd
+    import xm_symw_stages as st
     os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     rng = np.random.default_rng(ntot)                      # the same seed everywhere: every rank could build Q, but keeps its strip only
@@ -105,29 +81,13 @@ def _symw_rank_worker(rank, world, port, ntot, o, out_dir):
     g = xmamd.symw_plan(ntot, nloc, rank * nloc, K=4)
     lib = xmamd.lib()
     T = g["T"]
-    prow, csum = {}, np.zeros((M, o))
-    for s, jb, je in g["items"]:
-        c0, c1 = s * 256, min(s * 256 + 256, M)
-        ucol = np.arange(c0, c1) // 6
-        for j in range(jb, je):
-            t = g["t0"] + j
-            mc = np.array([bool(lib.xm_symw_use(T, t, int(u))) and u != t for u in ucol]); mr = mc | (ucol == t)
-            B = Qr[6 * j:6 * j + 6, c0:c1]
-            prow[(int(s), j)] = (B * mr) @ W[c0:c1]
-            csum[c0:c1] += (B * mc).T @ W[6 * t:6 * t + 6]
+    use = np.array([[lib.xm_symw_use(T, t, u) for u in range(T)] for t in range(T)], dtype=bool)
+    geom = {k: g[k] for k in ("T", "Th", "tie", "t0", "nsteps", "nstrips")}
+    mine = st.rank_stages(st.rank_pairs(Qr, W, geom, use), geom, g["items"], o, M)
     gathered = [torch.zeros(M, o, dtype=torch.float64) for _ in range(world)]
-    dist.all_gather(gathered, torch.from_numpy(csum))       # the one collective of a product
-    out = np.zeros((3 * nloc, o))
-    for cam in range(nloc):
-        j, t = cam // 2, g["t0"] + cam // 2
-        acc = np.zeros((3, o))
-        for s in range(g["nstrips"]):
-            if _any(g, t, s):
-                acc += prow[(s, j)][3 * (cam & 1):3 * (cam & 1) + 3]
-        grow = 3 * (rank * nloc + cam)
-        for r2 in range(world):                             # rank order: the same sum on every run
-            acc += gathered[r2][grow:grow + 3].numpy()
-        out[3 * cam:3 * cam + 3] = acc
+    dist.all_gather(gathered, torch.from_numpy(mine["csum"]))       # the one collective of a product
+    cs_all = np.stack([x.numpy() for x in gathered])                 # rank order: the same sum on every run
+    out, _ = st.rank_y(mine, geom, cs_all, np.zeros_like(cs_all), rank * nloc, nloc, 1.0)
     np.save(os.path.join(out_dir, f"y{rank}.npy"), out)
     dist.destroy_process_group()
 

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <mutex>
 #include <vector>
 
@@ -1986,6 +1987,75 @@ int xm_symw_plan(int64_t ntot, int nloc, int cam0, int K, int32_t geom[8], int32
     }
     if (items)
         for (size_t i = 0; i < p.items.size(); ++i) { items[3 * i] = p.items[i].s; items[3 * i + 1] = p.items[i].jb; items[3 * i + 2] = p.items[i].je; }
+    return XM_OK;
+    XM_CATCH
+}
+// Test export: one rank's share of the multi-rank symmetric product with every stage returned (include/xm_amd.h); everything is checked
+// before the first device call.  The calls are those of Context::product_symw with the all-gather replaced by the caller's vectors.
+int xm_symw_probe(xm_symw_probe_t *probe) {
+    XM_TRY
+    const std::string w("xm_symw_probe");
+    if (!probe) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (probe->struct_size != sizeof(xm_symw_probe_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_symw_probe_t.struct_size is not sizeof(xm_symw_probe_t)");
+    const xm_symw_probe_t p = *probe;
+    if (!(p.o == 1 || (p.o >= 3 && p.o <= 5))) throw xm::Error(XM_ERR_ARG, w + ": o must be 1, 3, 4 or 5");
+    if (p.ntot < 2 || p.ntot > XM_SYMW_PROBE_MAX_NTOT || (p.ntot & 1)) throw xm::Error(XM_ERR_ARG, w + ": ntot must be even, in [2, XM_SYMW_PROBE_MAX_NTOT]");
+    if (p.nloc < 2 || (p.nloc & 1) || p.cam0 < 0 || (p.cam0 & 1) || (int64_t)p.cam0 + p.nloc > p.ntot)
+        throw xm::Error(XM_ERR_ARG, w + ": nloc and cam0 must be even, with cam0 + nloc <= ntot");
+    if (p.world < 1 || (int64_t)p.world * p.nloc != p.ntot || p.cam0 % p.nloc != 0) throw xm::Error(XM_ERR_ARG, w + ": world * nloc must be ntot and cam0 a multiple of nloc");
+    if (p.nt < -1 || p.nt > 1 || p.scal_status < -1 || p.scal_status > 1) throw xm::Error(XM_ERR_ARG, w + ": nt and scal_status are -1, 0 or 1");
+    if (!std::isfinite(p.alpha) || !std::isfinite(p.pad_value)) throw xm::Error(XM_ERR_ARG, w + ": alpha and pad_value must be finite (a padding column is masked by x * 0)");
+    if (!p.Q || !p.W || !p.cs_all) throw xm::Error(XM_ERR_ARG, w + ": null Q, W or cs_all");
+    require_device();
+    const int o = p.o, OP = xm::pitch_of(o), rank = p.cam0 / p.nloc;
+    const int64_t ld = xm::dense_ld(p.ntot), M = (int64_t)3 * p.ntot, rows = (int64_t)3 * p.nloc;
+    xm::SymwProduct sp(p.ntot, p.nloc, p.cam0, ld, nullptr, p.K);
+    sp.ensure(o, p.world);
+    const xm::SymwPlan &pl = sp.plan();
+    int nfull = 0;
+    for (const xm::SymwItem &it : pl.items)
+        for (int j = it.jb; j < it.je; ++j) nfull += xm::symw_full(pl.g, pl.g.t0 + j, it.s) ? 1 : 0;
+    // Q at the solver's leading dimension, W at the solver's pitch
+    std::vector<double> hq((size_t)rows * (size_t)ld, p.pad_value), hw((size_t)ld * OP + 16, 0.0);
+    for (int64_t r = 0; r < rows; ++r) std::copy(p.Q + (size_t)r * M, p.Q + (size_t)(r + 1) * M, hq.begin() + (size_t)r * ld);
+    for (int64_t c = 0; c < M; ++c)
+        for (int k = 0; k < o; ++k) hw[(size_t)c * OP + k] = p.W[(size_t)c * o + k];
+    xm::DevBuf<double> Q, W, out;
+    xm::DevBuf<xm::TcgScal> scal;
+    Q.alloc(hq.size(), false); W.alloc(hw.size(), false); out.alloc((size_t)rows * OP);
+    XM_HIP_CHECK(hipMemcpy(Q.p, hq.data(), hq.size() * sizeof(double), hipMemcpyHostToDevice));
+    XM_HIP_CHECK(hipMemcpy(W.p, hw.data(), hw.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (p.scal_status >= 0) {
+        xm::TcgScal hs;
+        std::memset(&hs, 0, sizeof(hs));
+        hs.status = p.scal_status ? 2 : 0;
+        scal.alloc(1);
+        XM_HIP_CHECK(hipMemcpy(scal.p, &hs, sizeof(hs), hipMemcpyHostToDevice));
+    }
+    const size_t nprow = xm::symw_prow_count(pl, o), npcol = xm::symw_pcol_count(pl, o), ncs = sp.csum_count(o);
+    std::vector<double> nan(std::max(std::max(nprow, npcol), ncs), std::numeric_limits<double>::quiet_NaN());
+    XM_HIP_CHECK(hipMemcpy(sp.prow(), nan.data(), nprow * sizeof(double), hipMemcpyHostToDevice));
+    XM_HIP_CHECK(hipMemcpy(sp.pcol(), nan.data(), npcol * sizeof(double), hipMemcpyHostToDevice));
+    XM_HIP_CHECK(hipMemcpy(sp.csum_all(), p.cs_all, ncs * (size_t)p.world * sizeof(double), hipMemcpyHostToDevice));
+    XM_HIP_CHECK(hipMemcpy(sp.csum_all() + (size_t)rank * ncs, nan.data(), ncs * sizeof(double), hipMemcpyHostToDevice));
+    const int nt = (p.nt < 0) ? (xm::symw_nt_auto(p.nloc, ld) ? 1 : 0) : p.nt;
+    sp.sweep(o, Q.p, W.p, scal.p, rank, nullptr, nt);
+    xm::CamArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.nloc = p.nloc; a.cam0 = p.cam0; a.out = out.p;
+    sp.reduce(o, xm::EPI_PLAIN, p.alpha, a, p.world, nullptr);
+    XM_HIP_CHECK(hipDeviceSynchronize());
+    if (p.Prow) XM_HIP_CHECK(hipMemcpy(p.Prow, sp.prow(), nprow * sizeof(double), hipMemcpyDeviceToHost));
+    if (p.Pcol) XM_HIP_CHECK(hipMemcpy(p.Pcol, sp.pcol(), npcol * sizeof(double), hipMemcpyDeviceToHost));
+    XM_HIP_CHECK(hipMemcpy(p.cs_all + (size_t)rank * ncs, sp.csum_all() + (size_t)rank * ncs, ncs * sizeof(double), hipMemcpyDeviceToHost));
+    if (p.csum) std::copy(p.cs_all + (size_t)rank * ncs, p.cs_all + (size_t)(rank + 1) * ncs, p.csum);
+    if (p.Y) {
+        std::vector<double> hy((size_t)rows * OP);
+        XM_HIP_CHECK(hipMemcpy(hy.data(), out.p, hy.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < rows; ++r)
+            for (int k = 0; k < o; ++k) p.Y[(size_t)r * o + k] = hy[(size_t)r * OP + k];
+    }
+    probe->K = pl.K; probe->nt = nt; probe->nitems = (int32_t)pl.items.size(); probe->nfull = nfull;
     return XM_OK;
     XM_CATCH
 }

@@ -82,17 +82,21 @@ void symw_plan_build(int64_t ntot, int nloc, int cam0, int K, SymwPlan &out);
 size_t symw_prow_count(const SymwPlan &p, int o);    // doubles of the row-direction partial sums
 size_t symw_pcol_count(const SymwPlan &p, int o);    // doubles of the per-item column sums
 size_t symw_csum_count(int64_t ntot, int o);         // doubles of one rank's column-sum vector (the all-gathered message)
+bool symw_nt_auto(int nloc, int64_t ld);             // does the sweep of a strip of nloc cameras load past the cache (non-temporal)?
 
 // device-resident plan + buffers of one rank
 class SymwProduct {
 public:
-    SymwProduct(int64_t ntot, int nloc, int cam0, int64_t ld, hipStream_t st);
+    SymwProduct(int64_t ntot, int nloc, int cam0, int64_t ld, hipStream_t st, int K = 0);   // K <= 0: automatic chunk length
     void ensure(int omax, int world);                  // buffers for every rank o <= omax (grow-only: no free between two collectives)
     // main sweep + column sums of this rank -> csum_all() + rank * csum_count(o)
-    void sweep(int o, const double *Q, const double *W, const TcgScal *scal, int rank, hipStream_t st);
+    // nt: load policy of the sweep -- -1 by the size of the strip (symw_nt_auto), 0 cached, 1 non-temporal (the test export xm_symw_probe)
+    void sweep(int o, const double *Q, const double *W, const TcgScal *scal, int rank, hipStream_t st, int nt = -1);
     // per-camera sum (row partials + every rank's column sums, fixed order) + fused epilogue
     void reduce(int o, int epi, double alpha, const CamArgs &a, int world, hipStream_t st);
     double *csum_all() { return csum_.p; }
+    double *prow() { return prow_.p; }                 // row-direction partial sums, [strip][local row][k] (the test export looks at them)
+    double *pcol() { return pcol_.p; }                 // per-item column sums, [item][column in strip][k]
     size_t csum_count(int o) const { return symw_csum_count(ntot_, o); }
     const SymwPlan &plan() const { return plan_; }
     int64_t stream_bytes() const;                      // bytes of Q one product of this rank reads

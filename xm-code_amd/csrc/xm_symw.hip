@@ -223,8 +223,8 @@ __global__ __launch_bounds__(256) void symw_reduce_kernel(SymwGeom g, const doub
 // ------------------------------------------------------------------------------------------------------------------
 // host: the per-rank object
 // ------------------------------------------------------------------------------------------------------------------
-SymwProduct::SymwProduct(int64_t ntot, int nloc, int cam0, int64_t ld, hipStream_t st) : ntot_(ntot), ld_(ld), nloc_(nloc) {
-    symw_plan_build(ntot, nloc, cam0, 0, plan_);
+SymwProduct::SymwProduct(int64_t ntot, int nloc, int cam0, int64_t ld, hipStream_t st, int K) : ntot_(ntot), ld_(ld), nloc_(nloc) {
+    symw_plan_build(ntot, nloc, cam0, K, plan_);
     if (ld < (int64_t)6 * plan_.g.T || (ld % 128) != 0) throw Error(-2, "symmetric window product: bad leading dimension");
     items_.alloc(std::max<size_t>(plan_.items.size(), 1), false);
     strip_ptr_.alloc(plan_.strip_ptr.size(), false);
@@ -249,29 +249,30 @@ int64_t SymwProduct::stream_bytes() const {
     return steps * 6 * kSwStrip * 8;
 }
 
-static bool symw_nt(int nloc, int64_t ld) { return (size_t)nloc * 3 * (size_t)ld * sizeof(double) / 2 > ((size_t)240 << 20); }
+bool symw_nt_auto(int nloc, int64_t ld) { return (size_t)nloc * 3 * (size_t)ld * sizeof(double) / 2 > ((size_t)240 << 20); }
 
 template <int O>
 static void symw_sweep_o(const SymwPlan &pl, const double *Q, int64_t ld, const double *W, const TcgScal *scal, const SymwItem *items,
-                         const int32_t *strip_ptr, double *prow, double *pcol, double *csum, int nloc, hipStream_t st) {
+                         const int32_t *strip_ptr, double *prow, double *pcol, double *csum, bool nt, hipStream_t st) {
     const int nitems = (int)pl.items.size();
     if (nitems > 0) {
         const dim3 g((nitems + 3) / 4), b(256);
-        if (symw_nt(nloc, ld)) hipLaunchKernelGGL((qw_symw_kernel<O, true>), g, b, 0, st, Q, ld, W, pl.g, items, nitems, scal, prow, pcol);
+        if (nt) hipLaunchKernelGGL((qw_symw_kernel<O, true>), g, b, 0, st, Q, ld, W, pl.g, items, nitems, scal, prow, pcol);
         else hipLaunchKernelGGL((qw_symw_kernel<O, false>), g, b, 0, st, Q, ld, W, pl.g, items, nitems, scal, prow, pcol);
     }
     const int64_t n = (int64_t)6 * pl.g.T * O;
     hipLaunchKernelGGL((symw_colsum_kernel<O>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pl.g, strip_ptr, pcol, scal, csum);
 }
 
-void SymwProduct::sweep(int o, const double *Q, const double *W, const TcgScal *scal, int rank, hipStream_t st) {
+void SymwProduct::sweep(int o, const double *Q, const double *W, const TcgScal *scal, int rank, hipStream_t st, int nt) {
     if (o > omax_) throw Error(-2, "symmetric window product: ensure() was not called for this rank");
     double *cs = csum_.p + (size_t)rank * csum_count(o);
+    const bool ntl = (nt < 0) ? symw_nt_auto(nloc_, ld_) : nt != 0;
     switch (o) {
-        case 1: symw_sweep_o<1>(plan_, Q, ld_, W, scal, items_.p, strip_ptr_.p, prow_.p, pcol_.p, cs, nloc_, st); break;
-        case 3: symw_sweep_o<3>(plan_, Q, ld_, W, scal, items_.p, strip_ptr_.p, prow_.p, pcol_.p, cs, nloc_, st); break;
-        case 4: symw_sweep_o<4>(plan_, Q, ld_, W, scal, items_.p, strip_ptr_.p, prow_.p, pcol_.p, cs, nloc_, st); break;
-        case 5: symw_sweep_o<5>(plan_, Q, ld_, W, scal, items_.p, strip_ptr_.p, prow_.p, pcol_.p, cs, nloc_, st); break;
+        case 1: symw_sweep_o<1>(plan_, Q, ld_, W, scal, items_.p, strip_ptr_.p, prow_.p, pcol_.p, cs, ntl, st); break;
+        case 3: symw_sweep_o<3>(plan_, Q, ld_, W, scal, items_.p, strip_ptr_.p, prow_.p, pcol_.p, cs, ntl, st); break;
+        case 4: symw_sweep_o<4>(plan_, Q, ld_, W, scal, items_.p, strip_ptr_.p, prow_.p, pcol_.p, cs, ntl, st); break;
+        case 5: symw_sweep_o<5>(plan_, Q, ld_, W, scal, items_.p, strip_ptr_.p, prow_.p, pcol_.p, cs, ntl, st); break;
         default: throw Error(-2, "symmetric window product is instantiated for o = 1, 3, 4, 5");
     }
     check_launch("qw_symw");

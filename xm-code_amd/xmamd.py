@@ -33,7 +33,7 @@ EXPORTS = [
     "xm_dev_sync", "xm_dense_upload", "xm_dense_from_bsr3", "xm_qw_dense", "xm_qw_dense_sym", "xm_qw_bsr3", "xm_retract", "xm_retract_polar", "xm_recover_rotations",
     "xm_comm_unique_id", "xm_comm_init", "xm_comm_init_shm", "xm_comm_init_ipc", "xm_comm_finalize", "xm_partition", "xm_partition_blocks",
     "xm_symv_plan", "xm_sell_layout", "xm_sell_locality", "xm_sell_create", "xm_sell_create2", "xm_sell_quat_roundtrip", "xm_sell_destroy", "xm_qw_sell", "xm_qw_sell_padded",
-    "xm_ctx_attach_edges", "xm_ctx_edge_residuals", "xm_ctx_edge_residuals_recovered", "xm_ctx_xm2_filter", "xm_ctx_xm2_round", "xm_ctx_set_edge_weights", "xm_ctx_recover_tp", "xm_ctx_schur_info", "xm_ctx_tcg_two_launch", "xm_ctx_qw", "xm_spd_inverse", "xm_ctx_transport", "xm_ctx_sell_wpad", "xm_ctx_product_kind", "xm_symw_plan", "xm_symw_use",
+    "xm_ctx_attach_edges", "xm_ctx_edge_residuals", "xm_ctx_edge_residuals_recovered", "xm_ctx_xm2_filter", "xm_ctx_xm2_round", "xm_ctx_set_edge_weights", "xm_ctx_recover_tp", "xm_ctx_schur_info", "xm_ctx_tcg_two_launch", "xm_ctx_qw", "xm_spd_inverse", "xm_ctx_transport", "xm_ctx_sell_wpad", "xm_ctx_product_kind", "xm_symw_plan", "xm_symw_use", "xm_symw_probe",
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
     "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_la_probe", "xm_ba_aggregate_plan", "xm_ctx_ba_probe",
@@ -400,7 +400,13 @@ class LaProbe(C.Structure):        # xm_la_probe_t, the test export xm_la_probe
                [(k, C.c_int64) for k in ("lda", "ldb", "ldc")] + [("q", C.c_double)] + [(k, C.c_void_p) for k in ("A", "B", "C")]
 
 
+class SymwProbe(C.Structure):      # xm_symw_probe_t, the test export xm_symw_probe
+    _fields_ = [("struct_size", C.c_uint32)] + [(k, C.c_int32) for k in ("ntot", "nloc", "cam0", "world", "o", "K", "nt", "scal_status", "nitems", "nfull")] + \
+               [(k, C.c_double) for k in ("alpha", "pad_value")] + [(k, C.c_void_p) for k in ("Q", "W", "cs_all", "Prow", "Pcol", "csum", "Y")]
+
+
 LA_PROBE_MAX_N = 4096
+SYMW_PROBE_MAX_NTOT = 4096
 LA_OPS = {"gemm_sub": 0, "cholesky": 1, "substitute": 2, "inverse": 3, "layout": 4, "rank1_sub": 5}
 VGC_UPDATE_CONFIG = 1
 VGC_VALID, VGC_INVALID_IN, VGC_TWO_VIEW_ERROR = 0, 1, 2
@@ -537,6 +543,7 @@ def lib():
         L.xm_bench_last_error.restype = C.c_char_p
         L.xm_symw_plan.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.xm_symw_use.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.xm_symw_probe.argtypes = [C.POINTER(SymwProbe)]
         L.xm_qw_symw_time.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
         L.xm_bench_grid_barrier.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.xm_dev_count.argtypes = [C.POINTER(C.c_int)]
@@ -1699,6 +1706,51 @@ def symw_plan(ntot, nloc, cam0, K=0):
     out = {k: int(v) for k, v in zip(keys, geom)}
     out["items"] = items[: out["nitems"]]
     return out
+
+
+def symw_probe(Q, W, ntot, nloc, cam0, world, o, alpha=1.0, K=0, nt=-1, scal_status=-1, pad_value=0.0, cs_all=None):
+    """one rank's share of the multi-rank symmetric product, kernel by kernel (the test export xm_symw_probe, include/xm_amd.h): Q is the rank's
+    strip (3 nloc x 3 ntot), W 3 ntot x o, cs_all (world x 3 ntot x o, float64, contiguous; zeros when None) the ranks' column sums as the
+    all-gather would deliver them -- the slot of this rank is overwritten in place.  Returns Prow (nstrips, 6 nsteps, o), Pcol (items, 256, o),
+    csum (3 ntot, o), Y (3 nloc, o), cs_all and K, nt, nitems, nfull as used."""
+    Q = np.ascontiguousarray(Q, dtype=np.float64); W = np.ascontiguousarray(W, dtype=np.float64).reshape(-1, max(int(o), 1))
+    if Q.shape != (3 * nloc, 3 * ntot) or W.shape[0] != 3 * ntot:
+        raise XmError("symw_probe: Q is 3 nloc x 3 ntot and W 3 ntot x o")
+    if cs_all is None:
+        cs_all = np.zeros((max(world, 1), 3 * ntot, o))
+    if not (isinstance(cs_all, np.ndarray) and cs_all.dtype == np.float64 and cs_all.flags.c_contiguous and cs_all.flags.writeable
+            and cs_all.shape == (world, 3 * ntot, o)):
+        raise XmError("symw_probe: cs_all is a contiguous writable float64 array of world x 3 ntot x o")
+    try:
+        g = symw_plan(ntot, nloc, cam0, K)
+    except XmError:
+        g = dict(nstrips=1, nsteps=1, nitems=1)       # (the export refuses what the plan refuses)
+    out = dict(Prow=np.zeros((g["nstrips"], 6 * g["nsteps"], o)), Pcol=np.zeros((max(g["nitems"], 1), 256, o)), csum=np.zeros((3 * ntot, o)),
+               Y=np.zeros((3 * nloc, o)))
+    V = lambda a: a.ctypes.data_as(C.c_void_p)
+    p = SymwProbe(struct_size=C.sizeof(SymwProbe), ntot=ntot, nloc=nloc, cam0=cam0, world=world, o=o, K=K, nt=nt, scal_status=scal_status,
+                  alpha=alpha, pad_value=pad_value, Q=V(Q), W=V(W), cs_all=V(cs_all), **{k: V(v) for k, v in out.items()})
+    _chk(lib().xm_symw_probe(C.byref(p)))
+    out.update(cs_all=cs_all, K=int(p.K), nt=int(p.nt), nitems=int(p.nitems), nfull=int(p.nfull))
+    out["Pcol"] = out["Pcol"][:out["nitems"]]
+    return out
+
+
+def symw_product(Q, W, world, o, alpha=1.0, K=0, nt=-1, scal_status=-1, pad_value=0.0):
+    """alpha * Q W of a whole symmetric Q (3 ntot x 3 ntot) by the multi-rank window product on `world` equal row strips, one xm_symw_probe call
+    per rank for the column sums and one more per rank with all of them (the all-gather is a copy here).  Returns (Y, stages): Y 3 ntot x o and
+    the per-rank results of the second round of calls."""
+    Q = np.ascontiguousarray(Q, dtype=np.float64)
+    ntot = Q.shape[0] // 3
+    if Q.shape != (3 * ntot, 3 * ntot) or world < 1 or ntot % world:
+        raise XmError("symw_product: Q is 3 ntot x 3 ntot and world divides ntot")
+    nloc = ntot // world
+    cs_all = np.zeros((world, 3 * ntot, o))
+    kw = dict(alpha=alpha, K=K, nt=nt, scal_status=scal_status, pad_value=pad_value)
+    for r in range(world):
+        symw_probe(Q[3 * r * nloc:3 * (r + 1) * nloc], W, ntot, nloc, r * nloc, world, o, cs_all=cs_all, **kw)
+    stages = [symw_probe(Q[3 * r * nloc:3 * (r + 1) * nloc], W, ntot, nloc, r * nloc, world, o, cs_all=cs_all.copy(), **kw) for r in range(world)]
+    return np.concatenate([s["Y"] for s in stages], axis=0), stages
 
 
 class SellMatrix:
