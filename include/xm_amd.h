@@ -1432,6 +1432,16 @@ int xm_schur_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const i
  * middle on two -- the members never reached appended in index order, cut into runs of B (1..64; the solver uses XM_BA_AGG_CAMS).  agg_of_camera[n]: the
  * aggregate of every camera, -1 for one without a used observation.  More than XM_BA_MAX_AGGREGATES aggregates: XM_ERR_ARG. */
 int xm_ba_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int32_t *lm, const uint8_t *used, int B, int32_t *agg_of_camera);
+/* The Levenberg-Marquardt loop that xm_ctx_bundle_adjust, xm_ctx_global_positioning and xm_view_graph_calibrate share, run over a script
+ * in place of a device, host-only (CPU test, tests/test_lm_loop.py); no time limit.  points (2 npoints): cost and |J^T r|_inf of every
+ * point the loop reads, one consumed per read; steps (5 nsteps): cost_new, model (sum r.Jd + |Jd|^2 / 2: negative for a decrease), |d|^2,
+ * |x|^2 and solved (0: the linear solve failed) of every candidate, one consumed per iteration.  mu and accepted (nsteps each): the
+ * damping and the verdict of every iteration.  info[7]: status (XM_BA_*), iterations, accepted steps, points consumed, steps consumed,
+ * which accepted step's point is the current one at the end and which one is returned (0: the start; they differ only with non-monotonic
+ * steps).  radius: the trust-region radius at the end.  A script that runs out, or a null array: XM_ERR_ARG. */
+int xm_lm_replay(int max_iters, double function_tol, double gradient_tol, double parameter_tol, int nonmonotonic, int max_nonmonotonic,
+                 int64_t npoints, const double *points, int64_t nsteps, const double *steps, double *mu, uint8_t *accepted, int32_t info[7],
+                 double *radius);
 /* One linearisation of xm_ctx_bundle_adjust, a test export (tests/test_gpu_ba_stages.py): at the point (rot, t, p) (the layouts, context and
  * refusals of xm_ctx_bundle_adjust) and the damping mu > 0 it runs one eval + landmark pass + camera pass with the kernels, grids and
  * arguments of the LM loop (one workspace class serves both) and fills the scalars and every array whose pointer is not null; arrays per

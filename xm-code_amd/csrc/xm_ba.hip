@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "xm_device.h"
+#include "xm_lm_loop.h"
 #include "xm_lm_shared.h"
 #include "xm_schur.h"
 #include "xm_stage.h"
@@ -474,22 +475,7 @@ __global__ __launch_bounds__(256) void ba_cand_cam_kernel(int64_t n, const doubl
     x2 = block_sum256(x2, sh);
     if (threadIdx.x == 0) { parts[blockIdx.x] = s2; parts[gridDim.x + blockIdx.x] = x2; }
 }
-__global__ __launch_bounds__(256) void ba_cand_lm_kernel(int64_t m, const double *__restrict__ P, const double *__restrict__ dP,
-                                                         const int32_t *__restrict__ lused, double *__restrict__ Pn, double *__restrict__ parts) {
-    __shared__ double sh[4];
-    double s2 = 0.0, x2 = 0.0;
-    for (int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x; l < m; l += (int64_t)gridDim.x * 256) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const double v = P[3 * l + k];
-            if (lused[l]) { Pn[3 * l + k] = v + dP[3 * l + k]; s2 += dP[3 * l + k] * dP[3 * l + k]; x2 += v * v; }
-            else Pn[3 * l + k] = v;
-        }
-    }
-    s2 = block_sum256(s2, sh);
-    x2 = block_sum256(x2, sh);
-    if (threadIdx.x == 0) { parts[blockIdx.x] = s2; parts[gridDim.x + blockIdx.x] = x2; }
-}
+// (the landmarks' candidate: ba_cand_vec_kernel of xm_lm_shared.h)
 // cost 1/2 sum rho(|r|^2) at the candidate (the eval kernel's expression) and the linear model's terms sum r.(J d) + |J d|^2 / 2 (J, r: the
 // stored records of the current point, by-camera order)
 template <int CD, int LOSS = XM_BA_LOSS_TRIVIAL, class... Scale>
@@ -1010,32 +996,6 @@ __global__ __launch_bounds__(256) void ba_tl_apply_coarse_kernel(BaPcg a, BaTl t
 
 constexpr const char *kStage = "bundle adjustment";
 
-// the eval and cost kernels of the chosen loss (the trivial instantiations take no scale)
-template <int CD>
-void launch_eval(int loss, double a, int grid, hipStream_t st, const SchurLists &S, const double *R, const double *T, const double *P, double *Jc,
-                 double *Jl, double *parts) {
-    const dim3 g(grid), b(256);
-    switch (loss) {
-    case XM_BA_LOSS_HUBER: hipLaunchKernelGGL((ba_eval_kernel<CD, XM_BA_LOSS_HUBER, double>), g, b, 0, st, S, R, T, P, Jc, Jl, parts, a); break;
-    case XM_BA_LOSS_SOFT_L1: hipLaunchKernelGGL((ba_eval_kernel<CD, XM_BA_LOSS_SOFT_L1, double>), g, b, 0, st, S, R, T, P, Jc, Jl, parts, a); break;
-    case XM_BA_LOSS_CAUCHY: hipLaunchKernelGGL((ba_eval_kernel<CD, XM_BA_LOSS_CAUCHY, double>), g, b, 0, st, S, R, T, P, Jc, Jl, parts, a); break;
-    case XM_BA_LOSS_ARCTAN: hipLaunchKernelGGL((ba_eval_kernel<CD, XM_BA_LOSS_ARCTAN, double>), g, b, 0, st, S, R, T, P, Jc, Jl, parts, a); break;
-    default: hipLaunchKernelGGL((ba_eval_kernel<CD>), g, b, 0, st, S, R, T, P, Jc, Jl, parts);
-    }
-}
-template <int CD>
-void launch_cost(int loss, double a, int grid, hipStream_t st, const SchurLists &S, const double *Rn, const double *Tn, const double *Pn,
-                 const double *Jc, const double *dc, const double *dP, double *parts) {
-    const dim3 g(grid), b(256);
-    switch (loss) {
-    case XM_BA_LOSS_HUBER: hipLaunchKernelGGL((ba_cost_kernel<CD, XM_BA_LOSS_HUBER, double>), g, b, 0, st, S, Rn, Tn, Pn, Jc, dc, dP, parts, a); break;
-    case XM_BA_LOSS_SOFT_L1: hipLaunchKernelGGL((ba_cost_kernel<CD, XM_BA_LOSS_SOFT_L1, double>), g, b, 0, st, S, Rn, Tn, Pn, Jc, dc, dP, parts, a); break;
-    case XM_BA_LOSS_CAUCHY: hipLaunchKernelGGL((ba_cost_kernel<CD, XM_BA_LOSS_CAUCHY, double>), g, b, 0, st, S, Rn, Tn, Pn, Jc, dc, dP, parts, a); break;
-    case XM_BA_LOSS_ARCTAN: hipLaunchKernelGGL((ba_cost_kernel<CD, XM_BA_LOSS_ARCTAN, double>), g, b, 0, st, S, Rn, Tn, Pn, Jc, dc, dP, parts, a); break;
-    default: hipLaunchKernelGGL((ba_cost_kernel<CD>), g, b, 0, st, S, Rn, Tn, Pn, Jc, dc, dP, parts);
-    }
-}
-
 // the caller's parameters in the device layouts: Rcw = R_i^T (row-major), tcw = -R_i^T t_i, P by landmark slot
 void to_device_layout(const SchurOp &SO, const double *rot, const double *t, const double *p, std::vector<double> &hR, std::vector<double> &hT,
                       std::vector<double> &hP) {
@@ -1180,14 +1140,13 @@ struct BaWork {
         atl.prz[0] = tl_parts.p; atl.prz[1] = tl_parts.p + ncoarse; atl.prr = tl_parts.p + 2 * ncoarse; atl.pbb = tl_parts.p + 3 * ncoarse;
     }
     void reduce(BaReduce rd) { hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), b256, 0, st, rd); }
-    BaState read_state(const char *what) {
-        check_launch(what);
-        XM_HIP_CHECK(hipMemcpyAsync(hs.h, dst, sizeof(BaState), hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, kStage, what);
-        return *hs.h;
-    }
+    BaState read_state(const char *what) { return xm::read_state(dst, hs, st, cfg.watchdog_s, kStage, what); }
     void eval() {
-        launch_eval<CD>(cfg.loss, cfg.loss_scale, ge, st, S, R[cur].p, T[cur].p, P[cur].p, Jc.p, Jl.p, pp + o_eval);
+        with_loss(cfg.loss, [&](auto L) {   // the trivial instantiation takes no scale
+            const double *Rc = R[cur].p, *Tc = T[cur].p, *Pc = P[cur].p;
+            if constexpr (L.value == XM_BA_LOSS_TRIVIAL) hipLaunchKernelGGL((ba_eval_kernel<CD>), dim3(ge), b256, 0, st, S, Rc, Tc, Pc, Jc.p, Jl.p, pp + o_eval);
+            else hipLaunchKernelGGL((ba_eval_kernel<CD, L.value, double>), dim3(ge), b256, 0, st, S, Rc, Tc, Pc, Jc.p, Jl.p, pp + o_eval, cfg.loss_scale);
+        });
         BaReduce rd{};
         rd.sum_p[0] = pp + o_eval; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->cost;
         rd.sum_p[1] = pp + o_eval + ge; rd.sum_n[1] = ge; rd.sum_out[1] = &dst->used;
@@ -1279,17 +1238,14 @@ struct BaWork {
                            (const int32_t *)lused.p, dc, (const BaState *)nullptr, dP.p);
         hipLaunchKernelGGL((ba_cand_cam_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p, dc,
                            (const int32_t *)cused.p, R[nx].p, T[nx].p, pp + o_cand);
-        hipLaunchKernelGGL(ba_cand_lm_kernel, dim3(gfl), b256, 0, st, m, (const double *)P[cur].p, (const double *)dP.p, (const int32_t *)lused.p,
+        hipLaunchKernelGGL(ba_cand_vec_kernel<3>, dim3(gfl), b256, 0, st, m, (const double *)P[cur].p, (const double *)dP.p, (const int32_t *)lused.p,
                            P[nx].p, pp + o_cand + 2 * (size_t)gfc);
-        launch_cost<CD>(cfg.loss, cfg.loss_scale, ge, st, S, R[nx].p, T[nx].p, P[nx].p, Jc.p, dc, dP.p, pp + o_cost);
-        BaReduce rd{};
-        rd.sum_p[0] = pp + o_cost; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->cost_new;
-        rd.sum_p[1] = pp + o_cost + ge; rd.sum_n[1] = ge; rd.sum_out[1] = &dst->model;
-        rd.sum_p[2] = pp + o_cand; rd.sum_n[2] = gfc; rd.sum_out[2] = &dst->step2[0];
-        rd.sum_p[3] = pp + o_cand + gfc; rd.sum_n[3] = gfc; rd.sum_out[3] = &dst->x2[0];
-        rd.sum_p[4] = pp + o_cand + 2 * (size_t)gfc; rd.sum_n[4] = gfl; rd.sum_out[4] = &dst->step2[1];
-        rd.sum_p[5] = pp + o_cand + 2 * (size_t)gfc + gfl; rd.sum_n[5] = gfl; rd.sum_out[5] = &dst->x2[1];
-        reduce(rd);
+        with_loss(cfg.loss, [&](auto L) {
+            const double *Rn = R[nx].p, *Tn = T[nx].p, *Pn = P[nx].p, *J = Jc.p, *dl = dP.p;
+            if constexpr (L.value == XM_BA_LOSS_TRIVIAL) hipLaunchKernelGGL((ba_cost_kernel<CD>), dim3(ge), b256, 0, st, S, Rn, Tn, Pn, J, dc, dl, pp + o_cost);
+            else hipLaunchKernelGGL((ba_cost_kernel<CD, L.value, double>), dim3(ge), b256, 0, st, S, Rn, Tn, Pn, J, dc, dl, pp + o_cost, cfg.loss_scale);
+        });
+        reduce(candidate_sums(pp + o_cost, ge, pp + o_cand, gfc, gfl, dst));
     }
 };
 
@@ -1299,7 +1255,6 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
     BaWork<CD> W(SO, cfg, rot, t, p, st, cfg.dense_schur);
     const std::vector<int32_t> &slot_of = SO.slot_of();
     const int64_t n = W.n, m = W.m;
-    const bool nonmono = cfg.nonmonotonic;
     std::vector<double> &hR = W.hR, &hT = W.hT, &hP = W.hP;
     int &cur = W.cur, &best = W.best;
     int pcg_last = 8;
@@ -1310,100 +1265,47 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
     hooks.start = [&] { W.pcg_start(); };
     if (W.tlmode) hooks.update = [&](int it) { W.precond(it, 0); };
 
-    double radius = 1e4, nu = 2.0, F = 0.0, gmax = 0.0;
-    int status = XM_BA_NO_CONVERGENCE, iters = 0, accepted = 0, trace_n = 0;
-    // non-monotonic steps: Ceres's TrustRegionStepEvaluator (Conn, Gould & Toint, Trust-Region Methods, Algorithm 10.1.2).  Costs of the
-    // minimum, the reference and the candidate point, the model decreases accumulated since the reference and the candidate, and the
-    // accepted steps since the last new minimum
-    double ev_min = 0.0, ev_ref = 0.0, ev_cand = 0.0, ev_dm_ref = 0.0, ev_dm_cand = 0.0;
-    int ev_steps = 0;
-    int64_t pcg_total = 0;
-    bool fresh = true, first = true;   // fresh: the point changed and its cost / gradient have not been read yet
-    W.eval();
-    for (;;) {
-        const double mu = 1.0 / radius;
+    // the LM loop (xm_lm_loop.h) over this solver's launches and reads
+    const LmRules rules{cfg.max_iters, cfg.function_tol, cfg.gradient_tol, cfg.parameter_tol, cfg.nonmonotonic, cfg.max_nonmonotonic};
+    int nx = 0;   // the candidate's parameter set: neither the current one nor the least-cost one (without non-monotonic steps: cur ^ 1)
+    LmHooks lm;
+    lm.linearise = [&](double mu, bool point_changed) {
+        if (point_changed) W.eval();
         W.passes(mu);
-        if (fresh) {
-            const BaState s = W.read_state("the cost and gradient");
-            F = s.cost; gmax = s.gmax;
-            if (first) {
-                if (!std::isfinite(F)) throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: the initial reprojection cost is not finite (a point on a camera's focal plane?)");
-                out.initial_cost = F; out.n_used = (int64_t)s.used;
-                ev_min = ev_ref = ev_cand = F;
-                first = false;
-            }
-            fresh = false;
-            if (gmax <= cfg.gradient_tol) { status = XM_BA_CONVERGED_GRADIENT; break; }
-        }
-        if (iters >= cfg.max_iters) { status = XM_BA_MAX_ITERATIONS; break; }
-        if (secs_since(t_start) >= cfg.max_time) { status = XM_BA_TIME_LIMIT; break; }
-        int pit = 0;
-        double relres = 0.0;
-        if (cfg.dense_schur) W.dense_solve();
-        else {
-            if (W.tlmode) W.precond_setup();
-            const PcgResult pr = pcg_solve_batched<CD>(W.pcg_args(), W.gfc, st, pcg_last, hooks);
-            pit = pr.iters; relres = pr.relres;
-        }
-        pcg_total += pit;
-        int nx = 0;   // the candidate's parameter set: neither the current one nor the least-cost one (without non-monotonic steps: cur ^ 1)
+    };
+    lm.read_point = [&](LmRead which) {
+        const BaState s = W.read_state(which == kLmReadFinal ? "the final gradient" : "the cost and gradient");
+        if (which == kLmReadFirst && !std::isfinite(s.cost))
+            throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: the initial reprojection cost is not finite (a point on a camera's focal plane?)");
+        return LmPoint{s.cost, s.gmax, s.used};
+    };
+    lm.solve = [&]() -> LmSolve {
+        if (cfg.dense_schur) { W.dense_solve(); return {0, 0.0}; }
+        if (W.tlmode) W.precond_setup();
+        const PcgResult pr = pcg_solve_batched<CD>(W.pcg_args(), W.gfc, st, pcg_last, hooks);
+        return {pr.iters, pr.relres};
+    };
+    lm.read_candidate = [&](double) {
+        nx = 0;
         while (nx == cur || nx == best) ++nx;
         W.candidate(nx, W.x.p);
         const BaState s = W.read_state("the candidate's cost");
-        iters++;
-        const double step_norm = std::sqrt(s.step2[0] + s.step2[1]), x_norm = std::sqrt(s.x2[0] + s.x2[1]);
-        const double Fn = s.cost_new, model_dec = -s.model;
-        const bool solved = !(cfg.dense_schur && s.fail);   // a failed factorisation: an invalid step, as one without a model decrease
-        if (cfg.dense_schur) relres = solved ? (s.res2[1] > 0.0 ? std::sqrt(s.res2[0] / s.res2[1]) : 0.0) : -1.0;
-        const bool valid = solved && std::isfinite(Fn) && model_dec > 0.0;
-        double rho = valid ? (F - Fn) / model_dec : -1.0;
-        if (valid && nonmono) rho = std::max(rho, (ev_ref - Fn) / (ev_dm_ref + model_dec));   // Ceres's StepQuality
-        const bool accept = valid && rho > 1e-3;
-        if (trace_n < cfg.trace_cap && cfg.trace) {
-            double *rec = cfg.trace + (size_t)6 * trace_n++;
-            rec[0] = F; rec[1] = Fn; rec[2] = mu; rec[3] = accept ? 1.0 : 0.0; rec[4] = pit; rec[5] = relres;
+        LmCandidate c{s.cost_new, s.model, s.step2[0] + s.step2[1], s.x2[0] + s.x2[1]};
+        if (cfg.dense_schur) {   // a failed factorisation: an invalid step
+            c.solved = !s.fail;
+            c.relres = c.solved ? (s.res2[1] > 0.0 ? std::sqrt(s.res2[0] / s.res2[1]) : 0.0) : -1.0;
         }
-        if (solved && step_norm <= cfg.parameter_tol * (x_norm + cfg.parameter_tol)) { status = XM_BA_CONVERGED_PARAMETER; break; }
-        if (accept) {
-            accepted++;
-            radius = std::min(1e16, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3)));
-            nu = 2.0;
-            cur = nx;
-            W.basis_stale = true;
-            if (!nonmono) {
-                best = cur;
-            } else {   // Ceres's StepAccepted
-                ev_dm_cand += model_dec; ev_dm_ref += model_dec;
-                if (Fn < ev_min) {
-                    ev_min = ev_cand = Fn; ev_dm_cand = 0.0; ev_steps = 0;
-                    best = cur;
-                } else {
-                    ++ev_steps;
-                    if (Fn > ev_cand) { ev_cand = Fn; ev_dm_cand = 0.0; }
-                }
-                if (ev_steps == cfg.max_nonmonotonic) { ev_ref = ev_cand; ev_dm_ref = ev_dm_cand; }
-            }
-            const double Fold = F;
-            F = Fn;
-            W.eval();
-            fresh = true;
-            if (std::fabs(Fold - Fn) <= cfg.function_tol * Fold) { status = XM_BA_CONVERGED_FUNCTION; break; }
-        } else {
-            radius /= nu;
-            nu *= 2.0;
-            if (radius < 1e-32) { status = XM_BA_NO_PROGRESS; break; }
-        }
-    }
-    if (best != cur) {   // non-monotonic steps: the caller gets the point of least cost, and its cost and gradient
-        cur = best;
-        W.eval();
-        fresh = true;
-    }
-    if (fresh) {   // the last accepted point: its gradient
-        W.passes(1.0 / radius);
-        const BaState s = W.read_state("the final gradient");
-        F = s.cost; gmax = s.gmax;
-    }
+        return c;
+    };
+    lm.accept = [&](bool new_best) {
+        cur = nx;
+        W.basis_stale = true;
+        if (new_best) best = cur;
+    };
+    lm.to_best = [&] { cur = best; };
+    lm.out_of_time = [&] { return secs_since(t_start) >= cfg.max_time; };
+    const LmResult res = lm_loop(rules, lm);
+    out.initial_cost = res.initial_cost; out.n_used = (int64_t)res.n_used;
     // ---- back to the caller's layouts; cameras / landmarks without a used observation are left as they came
     std::vector<int32_t> cu((size_t)n), lu((size_t)m);
     XM_HIP_CHECK(hipMemcpyAsync(hR.data(), W.R[cur].p, hR.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1425,8 +1327,8 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         if (!lu[(size_t)sl]) continue;
         for (int a = 0; a < 3; ++a) p[(size_t)3 * l + a] = hP[(size_t)3 * sl + a];
     }
-    out.status = status; out.iters = iters; out.accepted = accepted; out.pcg_iters = pcg_total;
-    out.final_cost = F; out.gradient_max = gmax; out.trace_len = trace_n;
+    out.status = res.status; out.iters = res.iters; out.accepted = res.accepted; out.pcg_iters = res.pcg_total;
+    out.final_cost = res.final_cost; out.gradient_max = res.gmax; out.trace_len = lm_copy_trace(res, cfg.trace, cfg.trace_cap);
     out.coarse_fallbacks = W.coarse_fallbacks;
     out.seconds = secs_since(t_start);
 }

@@ -11,6 +11,7 @@
 
 #include "xm_ba.h"
 #include "xm_gp.h"
+#include "xm_lm_loop.h"
 #include "xm_clean.h"
 #include "xm_trackfilter.h"
 #include "xm_prune.h"
@@ -2079,6 +2080,38 @@ int xm_ba_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int3
     xm::ba_aggregate_plan(n, nobs, cam, lm, used, B, order);
     for (int64_t i = 0; i < n; ++i) agg_of_camera[i] = -1;
     for (size_t k = 0; k < order.size(); ++k) agg_of_camera[order[k]] = (int32_t)(k / (size_t)B);
+    return XM_OK;
+    XM_CATCH
+}
+// host-only run of the solvers' LM loop (xm_lm_loop.h) over a script of points and candidates, for the CPU test
+int xm_lm_replay(int max_iters, double function_tol, double gradient_tol, double parameter_tol, int nonmonotonic, int max_nonmonotonic,
+                 int64_t npoints, const double *points, int64_t nsteps, const double *steps, double *mu, uint8_t *accepted, int32_t info[7],
+                 double *radius) {
+    XM_TRY
+    if (!points || !steps || !mu || !accepted || !info || !radius) throw xm::Error(XM_ERR_ARG, "xm_lm_replay: null array");
+    const xm::LmRules rules{max_iters, function_tol, gradient_tol, parameter_tol, nonmonotonic != 0, max_nonmonotonic};
+    int64_t ip = 0, is = 0;
+    xm::LmHooks h;
+    h.linearise = [](double, bool) {};
+    h.read_point = [&](xm::LmRead) {
+        if (ip >= npoints) throw xm::Error(XM_ERR_ARG, "xm_lm_replay: the script has no point left");
+        const double *p = points + 2 * ip++;
+        return xm::LmPoint{p[0], p[1], 0.0};
+    };
+    h.solve = [] { return xm::LmSolve{0, 0.0}; };
+    h.read_candidate = [&](double) {
+        if (is >= nsteps) throw xm::Error(XM_ERR_ARG, "xm_lm_replay: the script has no step left");
+        const double *s = steps + 5 * is++;
+        xm::LmCandidate c{s[0], s[1], s[2], s[3]};
+        c.solved = s[4] != 0.0;
+        return c;
+    };
+    h.accept = [](bool) {};
+    h.to_best = [] {};
+    const xm::LmResult r = xm::lm_loop(rules, h);
+    for (size_t k = 0; k < r.trace.size(); ++k) { mu[k] = r.trace[k].mu; accepted[k] = r.trace[k].accepted ? 1 : 0; }
+    info[0] = r.status; info[1] = r.iters; info[2] = r.accepted; info[3] = (int32_t)ip; info[4] = (int32_t)is; info[5] = r.current; info[6] = r.returned;
+    *radius = r.radius;
     return XM_OK;
     XM_CATCH
 }

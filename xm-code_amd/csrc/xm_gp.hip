@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "xm_device.h"
+#include "xm_lm_loop.h"
 #include "xm_lm_shared.h"
 #include "xm_schur.h"
 #include "xm_stage.h"
@@ -361,23 +362,7 @@ __global__ __launch_bounds__(256) void gp_camx_kernel(SchurLists S, const double
     }
 }
 
-// ---- candidate point.  Centres or points: x + d where the item is used, a copy elsewhere; partials of |d|^2 and |x|^2 over the used ones
-__global__ __launch_bounds__(256) void gp_cand_vec_kernel(int64_t n, const double *__restrict__ x, const double *__restrict__ d,
-                                                          const int32_t *__restrict__ used, double *__restrict__ xn, double *__restrict__ parts) {
-    __shared__ double sh[4];
-    double s2 = 0.0, x2 = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const double v = x[3 * i + k];
-            if (used[i]) { xn[3 * i + k] = v + d[3 * i + k]; s2 += d[3 * i + k] * d[3 * i + k]; x2 += v * v; }
-            else xn[3 * i + k] = v;
-        }
-    }
-    s2 = block_sum256(s2, sh);
-    x2 = block_sum256(x2, sh);
-    if (threadIdx.x == 0) { parts[blockIdx.x] = s2; parts[gridDim.x + blockIdx.x] = x2; }
-}
+// ---- candidate point.  Centres and points: ba_cand_vec_kernel of xm_lm_shared.h.
 // scales: ds_e = -(g_s - w s v.(dc - dP)) / h* (0 for a frozen one) from the linearisation at the current point (the eval kernel's
 // expression), s <- max(s + ds, 1e-5); the cost 1/2 sum rho(|r|^2) at the candidate, the linear model's terms sum r.(J d) + |J d|^2 / 2 with
 // J d = sqrt(w) (s (dc - dP) - v ds), and partials of |ds|^2 and |s|^2
@@ -423,29 +408,6 @@ __global__ __launch_bounds__(256) void gp_cand_obs_kernel(SchurLists S, const in
     if (threadIdx.x == 0) {
         const size_t g = gridDim.x;
         parts[blockIdx.x] = cost; parts[g + blockIdx.x] = model; parts[2 * g + blockIdx.x] = s2; parts[3 * g + blockIdx.x] = x2;
-    }
-}
-
-template <class... A>
-void launch_eval(int loss, int grid, hipStream_t st, A... args) {
-    const dim3 g(grid), b(256);
-    switch (loss) {
-    case XM_BA_LOSS_HUBER: hipLaunchKernelGGL((gp_eval_kernel<XM_BA_LOSS_HUBER>), g, b, 0, st, args...); break;
-    case XM_BA_LOSS_SOFT_L1: hipLaunchKernelGGL((gp_eval_kernel<XM_BA_LOSS_SOFT_L1>), g, b, 0, st, args...); break;
-    case XM_BA_LOSS_CAUCHY: hipLaunchKernelGGL((gp_eval_kernel<XM_BA_LOSS_CAUCHY>), g, b, 0, st, args...); break;
-    case XM_BA_LOSS_ARCTAN: hipLaunchKernelGGL((gp_eval_kernel<XM_BA_LOSS_ARCTAN>), g, b, 0, st, args...); break;
-    default: hipLaunchKernelGGL((gp_eval_kernel<XM_BA_LOSS_TRIVIAL>), g, b, 0, st, args...);
-    }
-}
-template <class... A>
-void launch_cand_obs(int loss, int grid, hipStream_t st, A... args) {
-    const dim3 g(grid), b(256);
-    switch (loss) {
-    case XM_BA_LOSS_HUBER: hipLaunchKernelGGL((gp_cand_obs_kernel<XM_BA_LOSS_HUBER>), g, b, 0, st, args...); break;
-    case XM_BA_LOSS_SOFT_L1: hipLaunchKernelGGL((gp_cand_obs_kernel<XM_BA_LOSS_SOFT_L1>), g, b, 0, st, args...); break;
-    case XM_BA_LOSS_CAUCHY: hipLaunchKernelGGL((gp_cand_obs_kernel<XM_BA_LOSS_CAUCHY>), g, b, 0, st, args...); break;
-    case XM_BA_LOSS_ARCTAN: hipLaunchKernelGGL((gp_cand_obs_kernel<XM_BA_LOSS_ARCTAN>), g, b, 0, st, args...); break;
-    default: hipLaunchKernelGGL((gp_cand_obs_kernel<XM_BA_LOSS_TRIVIAL>), g, b, 0, st, args...);
     }
 }
 
@@ -513,16 +475,13 @@ struct GpWork {
         check_launch("the used observations");
     }
     void reduce(BaReduce rd) { hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), b256, 0, st, rd); }
-    GpState read_state(const char *what) {
-        check_launch(what);
-        XM_HIP_CHECK(hipMemcpyAsync(hs.h, dst, sizeof(GpState), hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, kStage, what);
-        return *hs.h;
-    }
+    GpState read_state(const char *what) { return xm::read_state(dst, hs, st, cfg.watchdog_s, kStage, what); }
     // the records, the landmark pass and the camera pass at the current point for the damping mu; cost, used and |J^T r|_inf to the state word
     void linearise(double mu) {
-        launch_eval(cfg.loss, ge, st, S, (const int32_t *)oused.p, (const double *)dir.p, (const double *)C[cur].p, (const double *)P[cur].p,
-                    (const double *)Sc[cur].p, cfg.loss_scale, mu, Jc.p, Jl.p, frozen.p, pp + o_eval);
+        with_loss(cfg.loss, [&](auto L) {
+            hipLaunchKernelGGL((gp_eval_kernel<L.value>), dim3(ge), b256, 0, st, S, (const int32_t *)oused.p, (const double *)dir.p, (const double *)C[cur].p,
+                               (const double *)P[cur].p, (const double *)Sc[cur].p, cfg.loss_scale, mu, Jc.p, Jl.p, frozen.p, pp + o_eval);
+        });
         hipLaunchKernelGGL(gp_lm_kernel, dim3(glm), blm, 0, st, S, (const double *)Jl.p, mu, vinv.p, gl.p, pp + o_gmax);
         hipLaunchKernelGGL(gp_cam_kernel, dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)vinv.p, (const double *)gl.p, mu, ustar.p,
                            sinv.p, b.p, pp + o_gmax + glm);
@@ -546,20 +505,15 @@ struct GpWork {
         const int nx = cur ^ 1;
         hipLaunchKernelGGL(gp_lmx_kernel, dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)gl.p, -1.0,
                            (const int32_t *)lused.p, dc, (const BaState *)nullptr, dP.p);
-        hipLaunchKernelGGL(gp_cand_vec_kernel, dim3(gfc), b256, 0, st, n, (const double *)C[cur].p, dc, (const int32_t *)cused.p, C[nx].p, pp + o_cand);
-        hipLaunchKernelGGL(gp_cand_vec_kernel, dim3(gfl), b256, 0, st, m, (const double *)P[cur].p, (const double *)dP.p, (const int32_t *)lused.p, P[nx].p,
+        hipLaunchKernelGGL(ba_cand_vec_kernel<3>, dim3(gfc), b256, 0, st, n, (const double *)C[cur].p, dc, (const int32_t *)cused.p, C[nx].p, pp + o_cand);
+        hipLaunchKernelGGL(ba_cand_vec_kernel<3>, dim3(gfl), b256, 0, st, m, (const double *)P[cur].p, (const double *)dP.p, (const int32_t *)lused.p, P[nx].p,
                            pp + o_cand + 2 * (size_t)gfc);
-        launch_cand_obs(cfg.loss, ge, st, S, (const int32_t *)oused.p, (const double *)dir.p, (const double *)C[cur].p, (const double *)P[cur].p,
-                        (const double *)Sc[cur].p, dc, (const double *)dP.p, (const double *)C[nx].p, (const double *)P[nx].p, cfg.loss_scale, mu,
-                        Sc[nx].p, ds.p, pp + o_cost);
-        BaReduce rd{};
-        rd.sum_p[0] = pp + o_cost; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->b.cost_new;
-        rd.sum_p[1] = pp + o_cost + ge; rd.sum_n[1] = ge; rd.sum_out[1] = &dst->b.model;
-        rd.sum_p[2] = pp + o_cand; rd.sum_n[2] = gfc; rd.sum_out[2] = &dst->b.step2[0];
-        rd.sum_p[3] = pp + o_cand + gfc; rd.sum_n[3] = gfc; rd.sum_out[3] = &dst->b.x2[0];
-        rd.sum_p[4] = pp + o_cand + 2 * (size_t)gfc; rd.sum_n[4] = gfl; rd.sum_out[4] = &dst->b.step2[1];
-        rd.sum_p[5] = pp + o_cand + 2 * (size_t)gfc + gfl; rd.sum_n[5] = gfl; rd.sum_out[5] = &dst->b.x2[1];
-        reduce(rd);
+        with_loss(cfg.loss, [&](auto L) {
+            hipLaunchKernelGGL((gp_cand_obs_kernel<L.value>), dim3(ge), b256, 0, st, S, (const int32_t *)oused.p, (const double *)dir.p,
+                               (const double *)C[cur].p, (const double *)P[cur].p, (const double *)Sc[cur].p, dc, (const double *)dP.p,
+                               (const double *)C[nx].p, (const double *)P[nx].p, cfg.loss_scale, mu, Sc[nx].p, ds.p, pp + o_cost);
+        });
+        reduce(candidate_sums(pp + o_cost, ge, pp + o_cand, gfc, gfl, &dst->b));
         BaReduce rs{};
         rs.sum_p[0] = pp + o_cost + 2 * (size_t)ge; rs.sum_n[0] = ge; rs.sum_out[0] = &dst->step2s;
         rs.sum_p[1] = pp + o_cost + 3 * (size_t)ge; rs.sum_n[1] = ge; rs.sum_out[1] = &dst->x2s;
@@ -610,65 +564,31 @@ void run(const SchurOp &SO, const GpSettings &cfg, const double *rot, double *t,
     hooks.product = [&] { W.sx(W.a, &W.dst->b); };
     hooks.read = [&] { return W.read_state("the reduced camera PCG").b; };
 
-    // the bundle adjustment's loop (xm_ba.hip), except that the records depend on mu and are written again in every iteration
-    double radius = 1e4, nu = 2.0, F = 0.0, gmax = 0.0;
-    int status = XM_BA_NO_CONVERGENCE, iters = 0, accepted = 0, trace_n = 0;
-    int64_t pcg_total = 0;
-    bool fresh = true, first = true;   // fresh: the point changed and its cost / gradient have not been read yet
-    for (;;) {
-        const double mu = 1.0 / radius;
-        W.linearise(mu);
-        if (fresh) {
-            const GpState s = W.read_state("the cost and gradient");
-            F = s.b.cost; gmax = std::max(s.b.gmax, s.gsmax);
-            if (first) {
-                if (!std::isfinite(F)) throw Error(XM_ERR_ARG, "xm_ctx_global_positioning: the initial cost is not finite");
-                out.initial_cost = F; out.n_used = (int64_t)s.b.used;
-                first = false;
-            }
-            fresh = false;
-            if (gmax <= cfg.gradient_tol) { status = XM_BA_CONVERGED_GRADIENT; break; }
-        }
-        if (iters >= cfg.max_iters) { status = XM_BA_MAX_ITERATIONS; break; }
-        if (secs_since(t_start) >= cfg.max_time) { status = XM_BA_TIME_LIMIT; break; }
+    // the LM loop (xm_lm_loop.h) over this solver's launches and reads; the records depend on mu and are written again in every iteration
+    const LmRules rules{cfg.max_iters, cfg.function_tol, cfg.gradient_tol, cfg.parameter_tol};
+    LmHooks lm;
+    lm.linearise = [&](double mu, bool) { W.linearise(mu); };
+    lm.read_point = [&](LmRead which) {
+        const GpState s = W.read_state(which == kLmReadFinal ? "the final gradient" : "the cost and gradient");
+        if (which == kLmReadFirst && !std::isfinite(s.b.cost)) throw Error(XM_ERR_ARG, "xm_ctx_global_positioning: the initial cost is not finite");
+        return LmPoint{s.b.cost, std::max(s.b.gmax, s.gsmax), s.b.used};
+    };
+    lm.solve = [&] {
         const PcgResult pr = pcg_solve_batched<3>(W.a, W.gfc, st, pcg_last, hooks);
-        pcg_total += pr.iters;
+        return LmSolve{pr.iters, pr.relres};
+    };
+    lm.read_candidate = [&](double mu) {
         W.candidate(mu, W.x.p);
         const GpState s = W.read_state("the candidate's cost");
-        iters++;
-        const double step_norm = std::sqrt(s.b.step2[0] + s.b.step2[1] + s.step2s), x_norm = std::sqrt(s.b.x2[0] + s.b.x2[1] + s.x2s);
-        const double Fn = s.b.cost_new, model_dec = -s.b.model;
-        const bool valid = std::isfinite(Fn) && model_dec > 0.0;
-        const double rho = valid ? (F - Fn) / model_dec : -1.0;
-        const bool accept = valid && rho > 1e-3;
-        if (trace_n < cfg.trace_cap && cfg.trace) {
-            double *rec = cfg.trace + (size_t)6 * trace_n++;
-            rec[0] = F; rec[1] = Fn; rec[2] = mu; rec[3] = accept ? 1.0 : 0.0; rec[4] = pr.iters; rec[5] = pr.relres;
-        }
-        if (step_norm <= cfg.parameter_tol * (x_norm + cfg.parameter_tol)) { status = XM_BA_CONVERGED_PARAMETER; break; }
-        if (accept) {
-            accepted++;
-            radius = std::min(1e16, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3)));
-            nu = 2.0;
-            W.cur ^= 1;
-            const double Fold = F;
-            F = Fn;
-            fresh = true;
-            if (std::fabs(Fold - Fn) <= cfg.function_tol * Fold) { status = XM_BA_CONVERGED_FUNCTION; break; }
-        } else {
-            radius /= nu;
-            nu *= 2.0;
-            if (radius < 1e-32) { status = XM_BA_NO_PROGRESS; break; }
-        }
-    }
-    if (fresh) {   // the last accepted point: its gradient
-        W.linearise(1.0 / radius);
-        const GpState s = W.read_state("the final gradient");
-        F = s.b.cost; gmax = std::max(s.b.gmax, s.gsmax);
-    }
+        return LmCandidate{s.b.cost_new, s.b.model, s.b.step2[0] + s.b.step2[1] + s.step2s, s.b.x2[0] + s.b.x2[1] + s.x2s};
+    };
+    lm.accept = [&](bool) { W.cur ^= 1; };
+    lm.out_of_time = [&] { return secs_since(t_start) >= cfg.max_time; };
+    const LmResult res = lm_loop(rules, lm);
     W.to_caller(W.cur, t, p, scales);
-    out.status = status; out.iters = iters; out.accepted = accepted; out.pcg_iters = pcg_total;
-    out.final_cost = F; out.gradient_max = gmax; out.trace_len = trace_n;
+    out.initial_cost = res.initial_cost; out.n_used = (int64_t)res.n_used;
+    out.status = res.status; out.iters = res.iters; out.accepted = res.accepted; out.pcg_iters = res.pcg_total;
+    out.final_cost = res.final_cost; out.gradient_max = res.gmax; out.trace_len = lm_copy_trace(res, cfg.trace, cfg.trace_cap);
     out.seconds = secs_since(t_start);
 }
 

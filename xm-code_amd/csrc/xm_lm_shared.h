@@ -1,8 +1,9 @@
 // xm_lm_shared.h — what the solvers of sparse normal equations share (xm_ba.hip: the reprojection bundle adjustment; xm_gp.hip: the global
 // positioning; xm_vgcalib.hip: the focal lengths over the view graph; xm_rotavg.hip: the rotations over it): the state word, the
 // fixed-order reductions over a heavy landmark's workgroup, the walk over a landmark's list, Ceres's losses, the small symmetric solves,
-// the vector kernels of the PCG with the host's batch driver for them, and the kernel that brings partial sums into the state word.  The
-// device code is the one xm_ba.hip had: moving it here changes no bit of its outputs.
+// the vector kernels of the PCG with the host's batch driver for them, the kernel that brings partial sums into the state word and the
+// host's read of it, the candidate's vector kernel and the dispatch on the loss.  The device code is the one xm_ba.hip and xm_gp.hip
+// had: moving it here changes no bit of its outputs.  (The LM loop above all this: xm_lm_loop.h.)
 // Everything stays in the anonymous namespace it had there: internal linkage, so each translation unit that includes this file compiles
 // its own copy of the kernels and of the __shared__ arrays inside heavy_sum (include it in .hip files only, never in a header).
 #pragma once
@@ -10,9 +11,11 @@
 #include <algorithm>
 #include <cstdint>
 #include <functional>
+#include <type_traits>
 
 #include "xm_device.h"
 #include "xm_schur.h"
+#include "xm_stage.h"
 
 namespace xm {
 
@@ -119,6 +122,17 @@ __device__ __forceinline__ double ba_rho(double s, double a, double &rho1) {
         const double sum = 1.0 + s * s * (1.0 / (a * a));
         rho1 = fmax(kMinNormal, 1.0 / sum);
         return a * atan2(s, a);
+    }
+}
+// the host's choice of a kernel's loss: f(std::integral_constant<int, LOSS>), the loss a compile-time constant
+template <class F>
+void with_loss(int loss, F &&f) {
+    switch (loss) {
+    case XM_BA_LOSS_HUBER: f(std::integral_constant<int, XM_BA_LOSS_HUBER>{}); break;
+    case XM_BA_LOSS_SOFT_L1: f(std::integral_constant<int, XM_BA_LOSS_SOFT_L1>{}); break;
+    case XM_BA_LOSS_CAUCHY: f(std::integral_constant<int, XM_BA_LOSS_CAUCHY>{}); break;
+    case XM_BA_LOSS_ARCTAN: f(std::integral_constant<int, XM_BA_LOSS_ARCTAN>{}); break;
+    default: f(std::integral_constant<int, XM_BA_LOSS_TRIVIAL>{});
     }
 }
 
@@ -335,6 +349,47 @@ __global__ __launch_bounds__(256) void ba_reduce_kernel(BaReduce r) {
         m = block_max<256>(m, shm);
         if (threadIdx.x == 0) *r.max_out = m;
     }
+}
+
+// the candidate's six sums into the state word s: cost and model (ge partials each, at cost), then |d|^2 and |x|^2 of the cameras (gfc
+// each, at cand) and of the landmarks (gfl each, behind them)
+inline BaReduce candidate_sums(const double *cost, int ge, const double *cand, int gfc, int gfl, BaState *s) {
+    BaReduce rd{};
+    rd.sum_p[0] = cost; rd.sum_n[0] = ge; rd.sum_out[0] = &s->cost_new;
+    rd.sum_p[1] = cost + ge; rd.sum_n[1] = ge; rd.sum_out[1] = &s->model;
+    rd.sum_p[2] = cand; rd.sum_n[2] = gfc; rd.sum_out[2] = &s->step2[0];
+    rd.sum_p[3] = cand + gfc; rd.sum_n[3] = gfc; rd.sum_out[3] = &s->x2[0];
+    rd.sum_p[4] = cand + 2 * (size_t)gfc; rd.sum_n[4] = gfl; rd.sum_out[4] = &s->step2[1];
+    rd.sum_p[5] = cand + 2 * (size_t)gfc + gfl; rd.sum_n[5] = gfl; rd.sum_out[5] = &s->x2[1];
+    return rd;
+}
+// the host's read of a state word: waits for the stream
+template <class State>
+State read_state(const State *dev, Pinned<State> &hs, hipStream_t st, double watchdog_s, const char *stage, const char *what) {
+    check_launch(what);
+    XM_HIP_CHECK(hipMemcpyAsync(hs.h, dev, sizeof(State), hipMemcpyDeviceToHost, st));
+    wait_stream(st, watchdog_s, stage, what);
+    return *hs.h;
+}
+
+// ---- candidate point.  Centres or points (K = 3 per item): x + d where the item is used, a copy elsewhere; partials of |d|^2 and |x|^2
+// over the used ones.  (A template, so that only the files that launch it compile it.)
+template <int K>
+__global__ __launch_bounds__(256) void ba_cand_vec_kernel(int64_t n, const double *__restrict__ x, const double *__restrict__ d,
+                                                          const int32_t *__restrict__ used, double *__restrict__ xn, double *__restrict__ parts) {
+    __shared__ double sh[4];
+    double s2 = 0.0, x2 = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const double v = x[K * i + k];
+            if (used[i]) { xn[K * i + k] = v + d[K * i + k]; s2 += d[K * i + k] * d[K * i + k]; x2 += v * v; }
+            else xn[K * i + k] = v;
+        }
+    }
+    s2 = block_sum256(s2, sh);
+    x2 = block_sum256(x2, sh);
+    if (threadIdx.x == 0) { parts[blockIdx.x] = s2; parts[gridDim.x + blockIdx.x] = x2; }
 }
 
 }  // namespace

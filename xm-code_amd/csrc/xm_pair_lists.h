@@ -136,13 +136,6 @@ void download(std::vector<T> &h, const T *dev, size_t n, hipStream_t st) {   // 
     h.resize(n);
     if (n) XM_HIP_CHECK(hipMemcpyAsync(h.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost, st));
 }
-template <class State>
-State read_state(const State *dev, Pinned<State> &hs, hipStream_t st, double watchdog_s, const char *stage, const char *what) {
-    check_launch(what);
-    XM_HIP_CHECK(hipMemcpyAsync(hs.h, dev, sizeof(State), hipMemcpyDeviceToHost, st));
-    wait_stream(st, watchdog_s, stage, what);
-    return *hs.h;
-}
 
 }  // namespace
 

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "xm_lm_loop.h"
 #include "xm_lm_shared.h"
 #include "xm_pair_lists.h"
 #include "xm_stage.h"
@@ -520,61 +521,26 @@ void run(const VgcInput &in, const VgcSettings &cfg, const VgcOutput &out, VgcOu
     hooks.product = [&] { W.product(W.a.p, W.dst, mu); };
     hooks.read = [&] { return W.read_state("the PCG"); };
 
-    // Ceres's Levenberg-Marquardt rules as xm_ba.hip and xm_gp.hip implement them
-    double radius = 1e4, nu = 2.0, Fc = 0.0, gmax = 0.0;
-    int status = XM_BA_NO_CONVERGENCE, iters = 0, accepted = 0, trace_n = 0;
-    const int trace_cap = cfg.max_iters + 1;
-    int64_t pcg_total = 0;
-    bool fresh_pt = true, first = true;
-    for (;;) {
-        mu = 1.0 / radius;
-        W.linearise(mu);
-        if (fresh_pt) {
-            const BaState s = W.read_state("the cost and gradient");
-            Fc = s.cost; gmax = s.gmax;
-            if (first) {
-                if (!std::isfinite(Fc)) throw Error(XM_ERR_ARG, "xm_view_graph_calibrate: the initial cost is not finite");
-                res.initial_cost = Fc;
-                first = false;
-            }
-            if (out.cost_trace && trace_n < trace_cap) out.cost_trace[trace_n] = Fc;
-            if (trace_n < trace_cap) trace_n++;
-            fresh_pt = false;
-            if (gmax <= cfg.gradient_tol) { status = XM_BA_CONVERGED_GRADIENT; break; }
-        }
-        if (iters >= cfg.max_iters) { status = XM_BA_MAX_ITERATIONS; break; }
-        pcg_total += pcg_solve_batched<1>(W.a, W.gfc, st, pcg_last, hooks).iters;
+    // the LM loop (xm_lm_loop.h) over this solver's launches and reads; no time limit
+    const LmRules rules{cfg.max_iters, cfg.function_tol, cfg.gradient_tol, cfg.parameter_tol};
+    LmHooks lm;
+    lm.linearise = [&](double m, bool) { mu = m; W.linearise(mu); };
+    lm.read_point = [&](LmRead which) {   // the last accepted point is read for its residuals and cost
+        const BaState s = W.read_state(which == kLmReadFinal ? "the final cost" : "the cost and gradient");
+        if (which == kLmReadFirst && !std::isfinite(s.cost)) throw Error(XM_ERR_ARG, "xm_view_graph_calibrate: the initial cost is not finite");
+        return LmPoint{s.cost, s.gmax, 0.0};
+    };
+    lm.solve = [&] { return LmSolve{pcg_solve_batched<1>(W.a, W.gfc, st, pcg_last, hooks).iters, 0.0}; };
+    lm.read_candidate = [&](double) {
         W.candidate();
         const BaState s = W.read_state("the candidate's cost");
-        iters++;
-        const double step_norm = std::sqrt(s.step2[0]), x_norm = std::sqrt(s.x2[0]);
-        const double Fn = s.cost_new, model_dec = -s.model;
-        const bool valid = std::isfinite(Fn) && model_dec > 0.0;
-        const double rho = valid ? (Fc - Fn) / model_dec : -1.0;
-        const bool accept = valid && rho > 1e-3;
-        if (step_norm <= cfg.parameter_tol * (x_norm + cfg.parameter_tol)) { status = XM_BA_CONVERGED_PARAMETER; break; }
-        if (accept) {
-            accepted++;
-            radius = std::min(1e16, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3)));
-            nu = 2.0;
-            W.cur ^= 1;
-            const double Fold = Fc;
-            Fc = Fn;
-            fresh_pt = true;
-            if (std::fabs(Fold - Fn) <= cfg.function_tol * Fold) { status = XM_BA_CONVERGED_FUNCTION; break; }
-        } else {
-            radius /= nu;
-            nu *= 2.0;
-            if (radius < 1e-32) { status = XM_BA_NO_PROGRESS; break; }
-        }
-    }
-    if (fresh_pt) {   // the last accepted point: its residuals and cost
-        W.linearise(1.0 / radius);
-        const BaState s = W.read_state("the final cost");
-        Fc = s.cost;
-        if (out.cost_trace && trace_n < trace_cap) out.cost_trace[trace_n] = Fc;
-        if (trace_n < trace_cap) trace_n++;
-    }
+        return LmCandidate{s.cost_new, s.model, s.step2[0], s.x2[0]};
+    };
+    lm.accept = [&](bool) { W.cur ^= 1; };
+    const LmResult lr = lm_loop(rules, lm);
+    const int trace_n = (int)std::min<size_t>(lr.point_costs.size(), (size_t)std::max(cfg.max_iters + 1, 0));   // the cost at every point read
+    if (out.cost_trace) std::copy_n(lr.point_costs.begin(), trace_n, out.cost_trace);
+    res.initial_cost = lr.initial_cost;
     hipLaunchKernelGGL(vgc_finish_kernel, dim3((unsigned)((std::max(ncams, M) + kT - 1) / kT)), dim3(kT), 0, st, ncams, (const int32_t *)W.uslot.p,
                        (const uint8_t *)W.touched.p, (const double *)W.focal0.p, (const double *)W.f[W.cur].p, cfg.lower_ratio, cfg.higher_ratio, W.fout.p,
                        W.fest.p, W.cstat.p, M, (const double *)W.rraw.p, cfg.two_view_error * cfg.two_view_error, W.pbad.p);
@@ -600,7 +566,7 @@ void run(const VgcInput &in, const VgcSettings &cfg, const VgcOutput &out, VgcOu
     if (out.d_out) planes_to_pairs(pl.plist, npairs, hd, 8, out.d_out);
     for (int m = 0; m < M; ++m)
         if (hbad[(size_t)m]) { out.pair_status[pl.plist[(size_t)m]] = XM_VGC_TWO_VIEW_ERROR; res.pairs_invalidated++; }
-    res.stop = status; res.iters = iters; res.accepted = accepted; res.pcg_iters = pcg_total; res.final_cost = Fc; res.trace_len = trace_n;
+    res.stop = lr.status; res.iters = lr.iters; res.accepted = lr.accepted; res.pcg_iters = lr.pcg_total; res.final_cost = lr.final_cost; res.trace_len = trace_n;
     res.seconds_download = secs_since(t_down);
 }
 

@@ -36,7 +36,7 @@ EXPORTS = [
     "xm_ctx_attach_edges", "xm_ctx_edge_residuals", "xm_ctx_edge_residuals_recovered", "xm_ctx_xm2_filter", "xm_ctx_xm2_round", "xm_ctx_set_edge_weights", "xm_ctx_recover_tp", "xm_ctx_schur_info", "xm_ctx_tcg_two_launch", "xm_ctx_qw", "xm_spd_inverse", "xm_ctx_transport", "xm_ctx_sell_wpad", "xm_ctx_product_kind", "xm_symw_plan", "xm_symw_use", "xm_symw_probe",
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
-    "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_la_probe", "xm_ba_aggregate_plan", "xm_ctx_ba_probe",
+    "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_la_probe", "xm_ba_aggregate_plan", "xm_ctx_ba_probe", "xm_lm_replay",
     "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe", "xm_ctx_outer_probe", "xm_ctx_cert_probe", "xm_tridiag_min", "xm_ctx_schur_probe",
     "xm_ctx_dense_q", "xm_create_matrix", "xm_schur_dense_limits",
     "xm_pair_filter", "xm_pair_filter_limits",
@@ -538,6 +538,7 @@ def lib():
         L.xm_ctx_schur_precond_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
         L.xm_schur_aggregate_plan.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.xm_ba_aggregate_plan.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.xm_lm_replay.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 5
         L.xm_ctx_sell_wpad.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.xm_ctx_product_kind.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.xm_bench_last_error.restype = C.c_char_p
@@ -877,6 +878,24 @@ def ba_aggregate_plan(cam, lm, n=None, used=None, B=BA_AGG_CAMS):
     _chk(lib().xm_ba_aggregate_plan(n, cam.size, cam.ctypes.data_as(C.c_void_p), lm.ctypes.data_as(C.c_void_p),
                                     None if u is None else u.ctypes.data_as(C.c_void_p), int(B), out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+def lm_replay(points, steps, max_iters=50, function_tol=1e-6, gradient_tol=1e-10, parameter_tol=1e-8, nonmonotonic=False, max_nonmonotonic=5):
+    """the solvers' Levenberg-Marquardt loop over a script: points (k, 2) = (cost, gmax) per point read, steps (k, 5) = (cost_new, model,
+    step2, x2, solved) per candidate -- host only.  Returns a dict: mu and accepted per iteration, status (BA_STATUS name), iters,
+    n_accepted, points_read, steps_read, current, returned (accepted step whose point is current / returned, 0 = the start), radius"""
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+    stp = np.ascontiguousarray(steps, dtype=np.float64).reshape(-1, 5)
+    npts, nstp = len(pts), len(stp)
+    pts = pts if npts else np.zeros((1, 2)); stp = stp if nstp else np.zeros((1, 5))   # an empty script still passes an address
+    mu = np.zeros(len(stp)); acc = np.zeros(len(stp), dtype=np.uint8)
+    info = np.zeros(7, dtype=np.int32); radius = C.c_double(0.0)
+    _chk(lib().xm_lm_replay(int(max_iters), float(function_tol), float(gradient_tol), float(parameter_tol), int(bool(nonmonotonic)), int(max_nonmonotonic),
+                            npts, pts.ctypes.data_as(C.c_void_p), nstp, stp.ctypes.data_as(C.c_void_p), mu.ctypes.data_as(C.c_void_p),
+                            acc.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p), C.cast(C.byref(radius), C.c_void_p)))
+    k = int(info[1])
+    return dict(mu=mu[:k].copy(), accepted=acc[:k].astype(bool), status=BA_STATUS[int(info[0])], iters=k, n_accepted=int(info[2]),
+                points_read=int(info[3]), steps_read=int(info[4]), current=int(info[5]), returned=int(info[6]), radius=radius.value)
 
 
 class CleanPlan:
