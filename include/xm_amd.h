@@ -1096,12 +1096,37 @@ int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int
  * xm_ctx_reprojection_errors: sqerr[e] = |r_e|^2 (unrobustified) of every observation e in input order at (rot, t, p) (the layouts, context
  * and refusals of xm_ctx_bundle_adjust), -1 for an observation the adjustment does not use (current weight <= 0 or p_e2 <= 0); computed on
  * the device with the context's current weights, nothing in the context changes.  For choosing the loss scale before an adjustment and for
- * finding the outliers after it (xm_ctx_set_edge_weights can then drop them before the next solve). */
+ * finding the outliers after it (xm_ctx_set_edge_weights can then drop them before the next solve).
+ *
+ * Focal refinement (XM_BA_REFINE_FOCAL, xm_ctx_bundle_adjust_focal): GLOMAP's bundle adjustment optimises the intrinsics by default
+ * (estimators/bundle_adjustment.h:16) and holds only the principal point constant (bundle_adjustment.cc:163-175).  Here:
+ *   model       one focal scale g_i > 0 per camera, g_i = f_i / f_prior_i, f_prior_i the focal with which the observations were normalised
+ *               (focal: n, host, in-out).  r_e = g_i pi(Rcw_i P_l + tcw_i) - (p_e0 / p_e2, p_e1 / p_e2): with g = 1 the residual above; GLOMAP's
+ *               pixel residual divided by f_prior, principal point constant.  Update g_i += dg_i.
+ *   tangent     camera block (dtheta, dt, dg), CD = 7; (dt, dg), CD = 4, with XM_BA_FIX_ROTATIONS: the focal is the last column, the
+ *               leading ones are those of the forms above.  d r / d g = pi(X); the pose and point Jacobians are those above times g_i;
+ *               a robust loss's corrector scales the whole record as before.
+ *   mask        focal_free (n, uint8; NULL = all free): a camera with focal_free = 0 has a zero focal column, so its diagonal entry is
+ *               mu 1e-6 by the clamp of D and its right-hand side 0: its step is exactly 0 and its g_i comes back bit-identical.  The
+ *               same holds for cameras without a used observation.
+ *   g <= 0      a candidate with g_i + dg_i <= 0 for a used camera with a free focal is an invalid step: rejected exactly as a step
+ *               without model decrease (radius /= nu, nu *= 2).  A returned focal is always > 0.
+ *   stops       |x|^2 adds g_i^2 per used camera with a free focal, |d|^2 adds dg_i^2, gradient_tol sees the focal gradient.
+ * Everything else is that of xm_ctx_bundle_adjust word for word: the LM rules, D = diag(J^T J) clamped, the PCG and its stop, non-monotonic
+ * steps, losses, which observations are used, XM_BA_DENSE_SCHUR (XM_BA_DENSE_MAX_ROWS applies to 7 n / 4 n), determinism (two calls give
+ * the same bytes).  xm_ctx_bundle_adjust_focal requires XM_BA_REFINE_FOCAL in opt->flags; xm_ctx_bundle_adjust refuses the flag as unknown.
+ * The aggregate preconditioners are not available with a focal column (their coarse space, LDS block size and compensated assembly are
+ * tuned to CD = 6 / 3): XM_BA_REFINE_FOCAL with XM_BA_PRECOND_TWO_LEVEL or XM_BA_PRECOND_BLOCKS is XM_ERR_ARG.  Also XM_ERR_ARG (context
+ * unchanged and usable): focal NULL, a focal that is not finite or not positive, the flag missing, and every refusal above.
+ * Departures from the reference: one focal per image (GLOMAP shares a Camera among images, which would couple camera blocks); no
+ * distortion parameters; fx = fy.
+ * xm_ctx_reprojection_errors_focal: sqerr[e] = |g_i pi(X) - z_e|^2, -1 where the observation is unused. */
 #define XM_BA_FIX_ROTATIONS 1u          /* the reference's only_landmarks = True: rotations constant (bit-identical), t and P free */
 #define XM_BA_NONMONOTONIC  2u          /* Ceres's non-monotonic steps (see above) */
 #define XM_BA_DENSE_SCHUR   16u         /* Ceres's DENSE_SCHUR (see below) instead of ITERATIVE_SCHUR; 4 and 8 are not flags */
 #define XM_BA_PRECOND_TWO_LEVEL 32u     /* PCG preconditioner: aggregate blocks + rigid-motion coarse operator (see below) */
 #define XM_BA_PRECOND_BLOCKS    64u     /* PCG preconditioner: the aggregate blocks alone (the ablation of the above) */
+#define XM_BA_REFINE_FOCAL      128u    /* a focal scale per camera joins the camera block (xm_ctx_bundle_adjust_focal only; see above) */
 #define XM_BA_AGG_CAMS          16      /* cameras per aggregate */
 #define XM_BA_MAX_AGGREGATES    4096    /* at most this many aggregates (65 536 cameras): A_c has up to 28 672 rows */
 #define XM_BA_DENSE_MAX_ROWS 32768      /* XM_BA_DENSE_SCHUR: largest CD n (CD = 6, or 3 with XM_BA_FIX_ROTATIONS): an 8.6 GB matrix */
@@ -1140,6 +1165,9 @@ typedef struct {
 } xm_ba_result_t;
 int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, xm_ba_result_t *res);
 int xm_ctx_reprojection_errors(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, double *sqerr);
+int xm_ctx_bundle_adjust_focal(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, double *focal /* n, in-out */,
+                               const uint8_t *focal_free /* n or NULL */, xm_ba_result_t *res);
+int xm_ctx_reprojection_errors_focal(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, const double *focal, double *sqerr);
 /* ---- Filtering tracks against a refined geometry: the TrackFilter of the reference's fork of GLOMAP
  * (deps/glomap/glomap/processors/track_filter.cc: FilterTracksByReprojection :7-51, FilterTracksByAngle :53-89,
  * FilterTrackTriangulationAngle :91-126), which GLOMAP alternates with its bundle adjustment (controllers/global_mapper.cc:243-317), as a
@@ -1477,6 +1505,12 @@ typedef struct {
     double *dP, *rot1, *t1, *p1;
 } xm_ba_probe_t;
 int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_ba_probe_t *probe);
+/* The same with focal scales (xm_ctx_bundle_adjust_focal; tests/test_gpu_ba_focal_stages.py): probe->flags must hold XM_BA_REFINE_FOCAL and
+ * may hold XM_BA_FIX_ROTATIONS (a preconditioner flag: XM_ERR_ARG); the arrays are sized by CD = 7, or 4 with fixed rotations.  focal (n, > 0),
+ * focal_free (n or NULL) as there.  focal1 (n or NULL): the candidate's focal scales when probe->dc is given; a candidate focal that is
+ * not positive is reported as cost1 = NaN (the loop rejects that step as invalid). */
+int xm_ctx_ba_probe_focal(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, const double *focal, const uint8_t *focal_free,
+                          xm_ba_probe_t *probe, double *focal1);
 
 /* ---- Global positioning: camera centres and points from rotations and 2-D tracks, without an initial value.  Step 5 of GLOMAP's pipeline
  * (controllers/global_mapper.cc:188-231), estimators/global_positioning.cc in its default ONLY_POINTS form, on the device over the observation

@@ -15,7 +15,11 @@ time and final cost of a run to function_tol 1e-8 (at most 200 iterations or 120
    python scripts/kbench_ba.py --precond {jacobi,blocks,two_level} [--seq 500,1000,...] [--sphere] [--no-simple2] [--iters K] [--no-converge] [--out ...]
 the same comparison for one preconditioner of the PCG (Context.bundle_adjust(preconditioner=...)) at eta 0.1 and 1e-6, with the PCG
 iterations of every step; --sphere adds the Final-13682-size sphere scene.  Without --seq / --sphere the option only selects the
-preconditioner of the default benchmark above."""
+preconditioner of the default benchmark above.
+   python scripts/kbench_ba.py --refine-focal [--out ...]
+runs the default benchmark on each scene twice in turn in one process -- without and with focal scales (Context.bundle_adjust(
+refine_focal=True): camera blocks of 7 instead of 6, records of 22 doubles per observation instead of 20) -- and prints the ratios per LM
+iteration and per PCG iteration."""
 import os
 import sys
 import time
@@ -77,7 +81,10 @@ def pcg_bytes(n, m, nobs, cd=6):
     return nobs * per_obs + n * per_cam + m * (6 + 3) * 8
 
 
-def bench(name, obs, n, m, rot0, t0, P0):
+def bench(name, obs, n, m, rot0, t0, P0, cd=6):
+    """returns (ms per LM iteration at eta 0.1, seconds per PCG iteration or None when it is not resolved); cd = 7: with focal scales"""
+    LOSS = dict(globals()["LOSS"], refine_focal=True) if cd == 7 else globals()["LOSS"]
+    name = f"{name}, focal scales (CD = 7)" if cd == 7 else name
     ctx = xmamd.Context(obs=obs, n=n)
     ctx.bundle_adjust(rot0, t0, P0, max_iters=1, **LOSS)      # warm-up: code objects, allocations
     r = {}
@@ -99,7 +106,7 @@ def bench(name, obs, n, m, rot0, t0, P0):
     (ta, ia), (tb, ib) = one[0.1], one[1e-10]
     nobs = obs[0].size
     per_pcg = (tb - ta) / max(1, ib["pcg_iters"] - ia["pcg_iters"])
-    by = pcg_bytes(n, m, nobs)
+    by = pcg_bytes(n, m, nobs, cd)
     log(f"{name}: {n} cameras, {m} landmarks, {nobs} observations ({ia['n_used']} used)")
     for eta, (tt, inf) in r.items():
         log(f"  eta {eta:g}: {inf['iters']} LM iterations ({inf['accepted']} accepted), {inf['pcg_iters']} PCG iterations, {tt * 1e3:9.2f} ms wall, "
@@ -110,6 +117,21 @@ def bench(name, obs, n, m, rot0, t0, P0):
         log(f"  per PCG iteration: not resolved (the two single iterations differ by {(tb - ta) * 1e3:.2f} ms, less than a tenth of either)")
     else:
         log(f"  per PCG iteration: {per_pcg * 1e6:9.1f} us; modelled traffic {by / 1e6:9.1f} MB -> {by / per_pcg / 1e9:7.1f} GB/s")
+    return r[0.1][1]["seconds"] * 1e3 / max(1, r[0.1][1]["iters"]), (None if tb - ta < 0.1 * ta else per_pcg)
+
+
+def bench_both(name, *a):
+    """the scene without and, with --refine-focal, with focal scales, alternating, two rounds (the second shows the spread); the ratios"""
+    if "--refine-focal" not in sys.argv:
+        bench(name, *a)
+        return
+    by = pcg_bytes(a[1], a[2], a[0][0].size, 7) / pcg_bytes(a[1], a[2], a[0][0].size, 6)
+    for rnd in (1, 2):
+        lm6, pcg6 = bench(f"{name}, round {rnd}", *a)
+        lm7, pcg7 = bench(f"{name}, round {rnd}", *a, cd=7)
+        log(f"  round {rnd}, focal scales / without: {lm7 / lm6:.3f} x per LM iteration (eta 0.1)" +
+            (f", {pcg7 / pcg6:.3f} x per PCG iteration" if pcg6 and pcg7 else ", per PCG iteration not resolved") +
+            f"; modelled PCG traffic {by:.3f} x")
 
 
 SOLVERS = [("dense", dict(linear_solver="dense_schur")), ("eta 0.1", dict(eta=0.1)), ("eta 1e-6", dict(eta=1e-6))]
@@ -164,13 +186,13 @@ if arg("--solver", "iterative") == "dense" or PRECOND_MODE:
         with open(out_path, "w") as f:
             f.write("\n".join(lines) + "\n")
     sys.exit(0)
-bench("SIMPLE2 (the reference's R_real, t_est, p_est)", (Z["cam"], Z["lm"], Z["p"], Z["w"].reshape(-1)), ref["t_est"].shape[1], ref["p_est"].shape[1],
+bench_both("SIMPLE2 (the reference's R_real, t_est, p_est)", (Z["cam"], Z["lm"], Z["p"], Z["w"].reshape(-1)), ref["t_est"].shape[1], ref["p_est"].shape[1],
       ref["R_real"], ref["t_est"], ref["p_est"])
 t = time.time()
 S = sphere_scene(13682, 800000, 8, seed=13682)
 rot0, t0, P0 = ba.perturb(S["rot"], S["t"], S["P"], seed=1, deg=0.5, rel=1e-3)
 log(f"(scene generated in {time.time() - t:.1f} s)")
-bench("sphere scene of Final-13682 size", (S["cam"], S["lm"], S["p"], S["w"]), S["n"], S["m"], rot0, t0, P0)
+bench_both("sphere scene of Final-13682 size", (S["cam"], S["lm"], S["p"], S["w"]), S["n"], S["m"], rot0, t0, P0)
 if out_path:
     with open(out_path, "w") as f:
         f.write("\n".join(lines) + "\n")

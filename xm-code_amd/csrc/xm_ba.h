@@ -34,6 +34,14 @@
 // clamp of D and the norm of the PCG's stop test).  The rotation is the left-multiplied rotation vector (Ceres's quaternion Plus turns by
 // 2|delta|: only the meaning of gradient_tol differs).  |x| in the parameter tolerance counts 1 per free rotation (a unit quaternion) plus
 // |tcw|^2 and |P|^2.
+//
+// Focal scales (XM_BA_REFINE_FOCAL, xm_ctx_bundle_adjust_focal; the model: include/xm_amd.h): one g_i > 0 per camera, r_e = g_i pi(X) - z_e,
+// the last column of the camera block (CD = 7, or 4 with fixed rotations): d r / d g = pi(X), the pose and point Jacobians times g_i.  The
+// eval, candidate and cost kernels read the focal scales of their parameter set (three sets beside R / T / P); every pass between them reads
+// the stored records and is the CD-generic code of the 6 / 3 forms.  A held focal (focal_free[i] = 0) has a zero column: its diagonal entry
+// is mu 1e-6 by the clamp, its right-hand side 0, its step exactly 0; the candidate kernel copies it.  A candidate focal <= 0 sets
+// bad_focal in the state word and the host rejects the step as it rejects a failed factorisation.  |x|^2 adds g_i^2 per used camera with
+// a free focal.  The aggregate preconditioners are not instantiated for CD = 7 / 4 (refused at the entry point).
 #pragma once
 
 #include <cstdint>
@@ -54,6 +62,9 @@ struct BaSettings {
     bool nonmonotonic = false;    // XM_BA_NONMONOTONIC
     int max_nonmonotonic = 5;     // Ceres's max_consecutive_nonmonotonic_steps
     bool dense_schur = false;     // XM_BA_DENSE_SCHUR: the reduced camera system assembled densely and solved by Cholesky (eta unused)
+    bool refine_focal = false;    // XM_BA_REFINE_FOCAL: a focal scale per camera, the last column of the camera block (CD = 7 / 4)
+    double *focal = nullptr;      // n focal scales > 0 (host; bundle_adjust updates them in place, ba_probe only reads them)
+    const uint8_t *focal_free = nullptr;   // n, 0 = held; null: all free
     int precond = 0;              // PCG preconditioner: 0 the inverted camera blocks | 1 XM_BA_PRECOND_BLOCKS | 2 XM_BA_PRECOND_TWO_LEVEL
     int trace_cap = 0;
     double *trace = nullptr;      // trace_cap x 6 row-major: cost, candidate cost, mu, accepted, PCG iterations, PCG relative residual
@@ -88,13 +99,16 @@ struct BaProbe {
     int32_t *cused = nullptr, *lused = nullptr;
     double *SX = nullptr, *Sdense = nullptr, *MX = nullptr, *Pm = nullptr, *dropped = nullptr, *Ac = nullptr;
     double *dP = nullptr, *rot1 = nullptr, *t1 = nullptr, *p1 = nullptr;
+    double *focal1 = nullptr;   // refine_focal: the candidate's focal scales (n); cost1 is NaN when one of them is not positive
 };
 
 // rot: 3 x 3n column-major (R_i, camera-to-world), t: 3 x n, p: 3 x m (host, updated in place).  The SchurOp is only read.
 void bundle_adjust(const SchurOp &S, const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out, hipStream_t st);
 // cfg: fix_rotations, loss, loss_scale, precond and watchdog_s are read.  The launches are those of bundle_adjust (one workspace class serves both).
 void ba_probe(const SchurOp &S, const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q, hipStream_t st);
-// sqerr[e] = |r_e|^2 (unrobustified) of observation e in input order at (rot, t, p), -1 where it is not used (weight <= 0 or p_e2 <= 0)
-void reprojection_errors(const SchurOp &S, const double *rot, const double *t, const double *p, double *sqerr, double watchdog_s, hipStream_t st);
+// sqerr[e] = |r_e|^2 (unrobustified) of observation e in input order at (rot, t, p), -1 where it is not used (weight <= 0 or p_e2 <= 0);
+// focal: n focal scales, or null for g = 1 (the kernel without them)
+void reprojection_errors(const SchurOp &S, const double *rot, const double *t, const double *p, const double *focal, double *sqerr, double watchdog_s,
+                         hipStream_t st);
 
 }  // namespace xm

@@ -1,5 +1,6 @@
 // xm_ba.hip — reprojection bundle adjustment on the lists of the matrix-free storage (design: xm_ba.h).  CD = 6 (rotation vector +
-// translation per camera) or 3 (XM_BA_FIX_ROTATIONS: translation only).
+// translation per camera) or 3 (XM_BA_FIX_ROTATIONS: translation only); with XM_BA_REFINE_FOCAL one focal scale more, the last column
+// of the camera block: CD = 7 or 4.
 #include "xm_ba.h"
 
 #include <algorithm>
@@ -24,6 +25,12 @@ template <int CD> constexpr int ba_planes() { return 2 * CD + 8; }
 template <int CD> constexpr int ba_jp() { return 2 * CD; }
 template <int CD> constexpr int ba_res() { return 2 * CD + 6; }
 
+// the camera block's columns: (dtheta, dt), (dt), (dtheta, dt, dg), (dt, dg)
+template <int CD> constexpr bool ba_has_rot() { return CD >= 6; }
+template <int CD> constexpr bool ba_has_focal() { return CD == 7 || CD == 4; }
+template <int CD> constexpr int ba_toff() { return ba_has_rot<CD>() ? 3 : 0; }   // first translation column
+template <int CD> constexpr int ba_fidx() { return CD - 1; }                       // the focal column (where there is one)
+
 __device__ __forceinline__ bool obs_used(const double (&v)[6]) { return v[0] != 0.0 || v[1] != 0.0 || v[2] != 0.0; }   // J_P row 0 (never 0 when used)
 
 // Scale: the loss scale a (one double) for a robust LOSS, nothing for the trivial one, whose argument list and code are those it had before
@@ -42,10 +49,12 @@ __device__ __forceinline__ void ba_point(const double *R, const double *T, const
 
 // ---- residuals and Jacobians at (Rcw, tcw, P), written in both list orders (scaled by sqrt(rho') under a robust loss); partial sums of
 // the cost 1/2 sum rho(|r|^2) and of the used observations
-template <int CD, int LOSS = XM_BA_LOSS_TRIVIAL, class... Scale>
-__global__ __launch_bounds__(256) void ba_eval_kernel(SchurLists S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
-                                                      const double *__restrict__ P, double *__restrict__ Jc, double *__restrict__ Jl,
-                                                      double *__restrict__ parts, Scale... scale) {
+// (the body of ba_eval_kernel and ba_eval_focal_kernel.  G, gfree: the focal scales of the parameter set and the mask of the free ones
+// (null: all), read only where the camera block has a focal column: r = g pi(X) - z, J_pose and J_P times g, d r / d g = pi(X) or 0)
+template <int CD, int LOSS, class... Scale>
+__device__ __forceinline__ void ba_eval_body(const SchurLists &S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
+                                             const double *__restrict__ P, const double *__restrict__ G, const uint8_t *__restrict__ gfree,
+                                             double *__restrict__ Jc, double *__restrict__ Jl, double *__restrict__ parts, Scale... scale) {
     static_assert(ba_loss_args<LOSS, Scale...>(), "a robust loss takes its scale, the trivial one nothing");
     constexpr int NP = ba_planes<CD>(), JP = ba_jp<CD>(), RS = ba_res<CD>();
     __shared__ double sh[4];
@@ -70,19 +79,28 @@ __global__ __launch_bounds__(256) void ba_eval_kernel(SchurLists S, const double
             for (int r = 0; r < 2; ++r) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) v[JP + 3 * r + k] = d[r][0] * R[k] + d[r][1] * R[3 + k] + d[r][2] * R[6 + k];   // d pi / dX . Rcw
-                if constexpr (CD == 6) {   // X = Exp(th) Y + t: dX / dth = -[Y]x
-                    v[6 * r + 0] = -d[r][1] * Y[2] + d[r][2] * Y[1];
-                    v[6 * r + 1] = d[r][0] * Y[2] - d[r][2] * Y[0];
-                    v[6 * r + 2] = -d[r][0] * Y[1] + d[r][1] * Y[0];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) v[6 * r + 3 + k] = d[r][k];
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) v[3 * r + k] = d[r][k];
+                if constexpr (ba_has_rot<CD>()) {   // X = Exp(th) Y + t: dX / dth = -[Y]x
+                    v[CD * r + 0] = -d[r][1] * Y[2] + d[r][2] * Y[1];
+                    v[CD * r + 1] = d[r][0] * Y[2] - d[r][2] * Y[0];
+                    v[CD * r + 2] = -d[r][0] * Y[1] + d[r][1] * Y[0];
                 }
+#pragma unroll
+                for (int k = 0; k < 3; ++k) v[CD * r + ba_toff<CD>() + k] = d[r][k];
             }
-            v[RS] = u0 - q0 / q2;
-            v[RS + 1] = u1 - q1 / q2;
+            if constexpr (ba_has_focal<CD>()) {
+                const int64_t i = S.obs_cam[e];
+                const double g = G[i];
+#pragma unroll
+                for (int k = 0; k < RS; ++k) v[k] *= g;   // the focal column is still 0
+                const bool fr = gfree == nullptr || gfree[i] != 0;
+                v[ba_fidx<CD>()] = fr ? u0 : 0.0;
+                v[CD + ba_fidx<CD>()] = fr ? u1 : 0.0;
+                v[RS] = g * u0 - q0 / q2;
+                v[RS + 1] = g * u1 - q1 / q2;
+            } else {
+                v[RS] = u0 - q0 / q2;
+                v[RS + 1] = u1 - q1 / q2;
+            }
             if constexpr (LOSS == XM_BA_LOSS_TRIVIAL) {
                 cost += 0.5 * (v[RS] * v[RS] + v[RS + 1] * v[RS + 1]);
             } else {
@@ -103,6 +121,21 @@ __global__ __launch_bounds__(256) void ba_eval_kernel(SchurLists S, const double
     cost = block_sum256(cost, sh);
     used = block_sum256(used, sh);
     if (threadIdx.x == 0) { parts[blockIdx.x] = cost; parts[gridDim.x + blockIdx.x] = used; }
+}
+template <int CD, int LOSS = XM_BA_LOSS_TRIVIAL, class... Scale>
+__global__ __launch_bounds__(256) void ba_eval_kernel(SchurLists S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
+                                                      const double *__restrict__ P, double *__restrict__ Jc, double *__restrict__ Jl,
+                                                      double *__restrict__ parts, Scale... scale) {
+    static_assert(!ba_has_focal<CD>(), "a focal column: ba_eval_focal_kernel");
+    ba_eval_body<CD, LOSS>(S, Rcw, tcw, P, nullptr, nullptr, Jc, Jl, parts, scale...);
+}
+template <int CD, int LOSS = XM_BA_LOSS_TRIVIAL, class... Scale>
+__global__ __launch_bounds__(256) void ba_eval_focal_kernel(SchurLists S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
+                                                            const double *__restrict__ P, const double *__restrict__ G,
+                                                            const uint8_t *__restrict__ gfree, double *__restrict__ Jc, double *__restrict__ Jl,
+                                                            double *__restrict__ parts, Scale... scale) {
+    static_assert(ba_has_focal<CD>(), "no focal column: ba_eval_kernel");
+    ba_eval_body<CD, LOSS>(S, Rcw, tcw, P, G, gfree, Jc, Jl, parts, scale...);
 }
 
 // ---- landmark pass: V_l, g_l, (V_l + mu D_l)^-1 (6 entries of the symmetric inverse), used flag; per-workgroup max of |g_l|_inf
@@ -430,10 +463,13 @@ __global__ __launch_bounds__(256) void ba_dense_res_kernel(int64_t n, const doub
 }
 
 // ---- candidate point.  Cameras: Rcw <- Exp(dtheta) Rcw (Rodrigues), tcw += dt; cameras without a used observation are copied.
+// With a focal column (G, gfree, Gn, st given): g += dg for a used camera whose focal is free, a copy elsewhere; g^2 joins |x|^2; a candidate
+// focal that is not positive sets the state word's bad_focal (cleared before the launch; every writer stores the same 1).
 template <int CD>
-__global__ __launch_bounds__(256) void ba_cand_cam_kernel(int64_t n, const double *__restrict__ Rcw, const double *__restrict__ tcw,
-                                                          const double *__restrict__ dc, const int32_t *__restrict__ cused, double *__restrict__ Rn,
-                                                          double *__restrict__ tn, double *__restrict__ parts) {
+__device__ __forceinline__ void ba_cand_cam_body(int64_t n, const double *__restrict__ Rcw, const double *__restrict__ tcw,
+                                                 const double *__restrict__ G, const uint8_t *__restrict__ gfree, const double *__restrict__ dc,
+                                                 const int32_t *__restrict__ cused, double *__restrict__ Rn, double *__restrict__ tn,
+                                                 double *__restrict__ Gn, BaState *__restrict__ st, double *__restrict__ parts) {
     __shared__ double sh[4];
     double s2 = 0.0, x2 = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -443,14 +479,26 @@ __global__ __launch_bounds__(256) void ba_cand_cam_kernel(int64_t n, const doubl
             for (int k = 0; k < 9; ++k) Rn[9 * i + k] = R[k];
 #pragma unroll
             for (int k = 0; k < 3; ++k) tn[3 * i + k] = T[k];
+            if constexpr (ba_has_focal<CD>()) Gn[i] = G[i];
             continue;
         }
-        const double *dt = d + (CD == 6 ? 3 : 0);
+        const double *dt = d + ba_toff<CD>();
 #pragma unroll
         for (int k = 0; k < 3; ++k) { tn[3 * i + k] = T[k] + dt[k]; x2 += T[k] * T[k]; }
 #pragma unroll
         for (int k = 0; k < CD; ++k) s2 += d[k] * d[k];
-        if constexpr (CD == 6) {
+        if constexpr (ba_has_focal<CD>()) {
+            const double g = G[i];
+            if (gfree == nullptr || gfree[i] != 0) {
+                const double gn = g + d[ba_fidx<CD>()];
+                Gn[i] = gn;
+                x2 += g * g;
+                if (!(gn > 0.0)) st->bad_focal = 1;
+            } else {
+                Gn[i] = g;
+            }
+        }
+        if constexpr (ba_has_rot<CD>()) {
             x2 += 1.0;   // the unit quaternion of the rotation
             const double w0 = d[0], w1 = d[1], w2 = d[2], th2 = w0 * w0 + w1 * w1 + w2 * w2;
             double A, B;
@@ -475,13 +523,31 @@ __global__ __launch_bounds__(256) void ba_cand_cam_kernel(int64_t n, const doubl
     x2 = block_sum256(x2, sh);
     if (threadIdx.x == 0) { parts[blockIdx.x] = s2; parts[gridDim.x + blockIdx.x] = x2; }
 }
+template <int CD>
+__global__ __launch_bounds__(256) void ba_cand_cam_kernel(int64_t n, const double *__restrict__ Rcw, const double *__restrict__ tcw,
+                                                          const double *__restrict__ dc, const int32_t *__restrict__ cused, double *__restrict__ Rn,
+                                                          double *__restrict__ tn, double *__restrict__ parts) {
+    static_assert(!ba_has_focal<CD>(), "a focal column: ba_cand_cam_focal_kernel");
+    ba_cand_cam_body<CD>(n, Rcw, tcw, nullptr, nullptr, dc, cused, Rn, tn, nullptr, nullptr, parts);
+}
+template <int CD>
+__global__ __launch_bounds__(256) void ba_cand_cam_focal_kernel(int64_t n, const double *__restrict__ Rcw, const double *__restrict__ tcw,
+                                                                const double *__restrict__ G, const uint8_t *__restrict__ gfree,
+                                                                const double *__restrict__ dc, const int32_t *__restrict__ cused,
+                                                                double *__restrict__ Rn, double *__restrict__ tn, double *__restrict__ Gn,
+                                                                BaState *__restrict__ st, double *__restrict__ parts) {
+    static_assert(ba_has_focal<CD>(), "no focal column: ba_cand_cam_kernel");
+    ba_cand_cam_body<CD>(n, Rcw, tcw, G, gfree, dc, cused, Rn, tn, Gn, st, parts);
+}
 // (the landmarks' candidate: ba_cand_vec_kernel of xm_lm_shared.h)
 // cost 1/2 sum rho(|r|^2) at the candidate (the eval kernel's expression) and the linear model's terms sum r.(J d) + |J d|^2 / 2 (J, r: the
 // stored records of the current point, by-camera order)
-template <int CD, int LOSS = XM_BA_LOSS_TRIVIAL, class... Scale>
-__global__ __launch_bounds__(256) void ba_cost_kernel(SchurLists S, const double *__restrict__ Rn, const double *__restrict__ tn,
-                                                      const double *__restrict__ Pn, const double *__restrict__ Jc, const double *__restrict__ dc,
-                                                      const double *__restrict__ dP, double *__restrict__ parts, Scale... scale) {
+// (Gn: the candidate's focal scales, read only where the camera block has a focal column)
+template <int CD, int LOSS, class... Scale>
+__device__ __forceinline__ void ba_cost_body(const SchurLists &S, const double *__restrict__ Rn, const double *__restrict__ tn,
+                                             const double *__restrict__ Pn, const double *__restrict__ Gn, const double *__restrict__ Jc,
+                                             const double *__restrict__ dc, const double *__restrict__ dP, double *__restrict__ parts,
+                                             Scale... scale) {
     static_assert(ba_loss_args<LOSS, Scale...>(), "a robust loss takes its scale, the trivial one nothing");
     constexpr int JP = ba_jp<CD>(), RS = ba_res<CD>();
     __shared__ double sh[4];
@@ -495,7 +561,9 @@ __global__ __launch_bounds__(256) void ba_cost_kernel(SchurLists S, const double
         double X[3];
 #pragma unroll
         for (int a = 0; a < 3; ++a) X[a] = R[3 * a] * X3[0] + R[3 * a + 1] * X3[1] + R[3 * a + 2] * X3[2] + T[a];
-        const double e0 = X[0] / X[2] - q0 / q2, e1 = X[1] / X[2] - q1 / q2;
+        double e0, e1;
+        if constexpr (ba_has_focal<CD>()) { e0 = Gn[i] * (X[0] / X[2]) - q0 / q2; e1 = Gn[i] * (X[1] / X[2]) - q1 / q2; }
+        else { e0 = X[0] / X[2] - q0 / q2; e1 = X[1] / X[2] - q1 / q2; }
         if constexpr (LOSS == XM_BA_LOSS_TRIVIAL) {
             cost += 0.5 * (e0 * e0 + e1 * e1);
         } else {
@@ -520,6 +588,21 @@ __global__ __launch_bounds__(256) void ba_cost_kernel(SchurLists S, const double
     model = block_sum256(model, sh);
     if (threadIdx.x == 0) { parts[blockIdx.x] = cost; parts[gridDim.x + blockIdx.x] = model; }
 }
+template <int CD, int LOSS = XM_BA_LOSS_TRIVIAL, class... Scale>
+__global__ __launch_bounds__(256) void ba_cost_kernel(SchurLists S, const double *__restrict__ Rn, const double *__restrict__ tn,
+                                                      const double *__restrict__ Pn, const double *__restrict__ Jc, const double *__restrict__ dc,
+                                                      const double *__restrict__ dP, double *__restrict__ parts, Scale... scale) {
+    static_assert(!ba_has_focal<CD>(), "a focal column: ba_cost_focal_kernel");
+    ba_cost_body<CD, LOSS>(S, Rn, tn, Pn, nullptr, Jc, dc, dP, parts, scale...);
+}
+template <int CD, int LOSS = XM_BA_LOSS_TRIVIAL, class... Scale>
+__global__ __launch_bounds__(256) void ba_cost_focal_kernel(SchurLists S, const double *__restrict__ Rn, const double *__restrict__ tn,
+                                                            const double *__restrict__ Pn, const double *__restrict__ Gn,
+                                                            const double *__restrict__ Jc, const double *__restrict__ dc,
+                                                            const double *__restrict__ dP, double *__restrict__ parts, Scale... scale) {
+    static_assert(ba_has_focal<CD>(), "no focal column: ba_cost_kernel");
+    ba_cost_body<CD, LOSS>(S, Rn, tn, Pn, Gn, Jc, dc, dP, parts, scale...);
+}
 // |r_e|^2 per observation in input order at (Rcw, tcw, P) (the eval kernel's projection, unrobustified); -1 where the observation is not used
 __global__ __launch_bounds__(256) void ba_sqerr_kernel(SchurLists S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
                                                        const double *__restrict__ P, double *__restrict__ sqerr) {
@@ -530,6 +613,22 @@ __global__ __launch_bounds__(256) void ba_sqerr_kernel(SchurLists S, const doubl
             double Y[3], X[3];
             ba_point(Rcw + (size_t)9 * S.obs_cam[e], tcw + (size_t)3 * S.obs_cam[e], P + (size_t)3 * S.obs_lm[e], Y, X);
             const double r0 = X[0] / X[2] - q0 / q2, r1 = X[1] / X[2] - q1 / q2;
+            sq = r0 * r0 + r1 * r1;
+        }
+        sqerr[e] = sq;
+    }
+}
+// the same at the focal scales G: |g_i pi(X) - z|^2
+__global__ __launch_bounds__(256) void ba_sqerr_focal_kernel(SchurLists S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
+                                                             const double *__restrict__ P, const double *__restrict__ G,
+                                                             double *__restrict__ sqerr) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < S.nobs; e += (int64_t)gridDim.x * 256) {
+        const double w = S.cam_w[S.pos_c[e]], q0 = S.obs_p[3 * e], q1 = S.obs_p[3 * e + 1], q2 = S.obs_p[3 * e + 2];
+        double sq = -1.0;
+        if (w > 0.0 && q2 > 0.0) {
+            double Y[3], X[3];
+            ba_point(Rcw + (size_t)9 * S.obs_cam[e], tcw + (size_t)3 * S.obs_cam[e], P + (size_t)3 * S.obs_lm[e], Y, X);
+            const double g = G[S.obs_cam[e]], r0 = g * (X[0] / X[2]) - q0 / q2, r1 = g * (X[1] / X[2]) - q1 / q2;
             sq = r0 * r0 + r1 * r1;
         }
         sqerr[e] = sq;
@@ -1029,6 +1128,8 @@ struct BaWork {
     std::vector<double> hR, hT, hP;
     // ---- parameters on the device; three sets with non-monotonic steps (current, candidate, least cost so far), two otherwise
     DevBuf<double> R[3], T[3], P[3];
+    DevBuf<double> G[3];        // with a focal column: the focal scales of each set
+    DevBuf<uint8_t> gfree;      // the mask of the free focals (not allocated: all free)
     // ---- workspace (zero: the padding of the packed landmark lists stays 0 in every plane)
     DevBuf<double> Jc, Jl, vinv, gl, ustar, sinv, b, x, r, z, pv, Ap, y, dP, parts;
     DevBuf<int32_t> lused, cused, state_buf;
@@ -1063,6 +1164,14 @@ struct BaWork {
         XM_HIP_CHECK(hipMemcpyAsync(R[0].p, hR.data(), hR.size() * sizeof(double), hipMemcpyHostToDevice, st));
         XM_HIP_CHECK(hipMemcpyAsync(T[0].p, hT.data(), hT.size() * sizeof(double), hipMemcpyHostToDevice, st));
         XM_HIP_CHECK(hipMemcpyAsync(P[0].p, hP.data(), hP.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        if constexpr (ba_has_focal<CD>()) {
+            for (int k = 0; k < (nonmono ? 3 : 2); ++k) G[k].alloc((size_t)n, false);
+            XM_HIP_CHECK(hipMemcpyAsync(G[0].p, cfg.focal, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+            if (cfg.focal_free) {
+                gfree.alloc((size_t)n, false);
+                XM_HIP_CHECK(hipMemcpyAsync(gfree.p, cfg.focal_free, (size_t)n, hipMemcpyHostToDevice, st));
+            }
+        }
         Jc.alloc((size_t)NP * nobs); Jl.alloc((size_t)NP * S.lm_total);
         vinv.alloc((size_t)6 * m); gl.alloc((size_t)3 * m); y.alloc((size_t)3 * m); dP.alloc((size_t)3 * m); lused.alloc((size_t)m);
         ustar.alloc((size_t)CD * CD * n); sinv.alloc((size_t)CD * CD * n); cused.alloc((size_t)n);
@@ -1144,7 +1253,15 @@ struct BaWork {
     void eval() {
         with_loss(cfg.loss, [&](auto L) {   // the trivial instantiation takes no scale
             const double *Rc = R[cur].p, *Tc = T[cur].p, *Pc = P[cur].p;
-            if constexpr (L.value == XM_BA_LOSS_TRIVIAL) hipLaunchKernelGGL((ba_eval_kernel<CD>), dim3(ge), b256, 0, st, S, Rc, Tc, Pc, Jc.p, Jl.p, pp + o_eval);
+            if constexpr (ba_has_focal<CD>()) {
+                const double *Gc = G[cur].p;
+                const uint8_t *fr = gfree.p;
+                if constexpr (L.value == XM_BA_LOSS_TRIVIAL)
+                    hipLaunchKernelGGL((ba_eval_focal_kernel<CD>), dim3(ge), b256, 0, st, S, Rc, Tc, Pc, Gc, fr, Jc.p, Jl.p, pp + o_eval);
+                else
+                    hipLaunchKernelGGL((ba_eval_focal_kernel<CD, L.value, double>), dim3(ge), b256, 0, st, S, Rc, Tc, Pc, Gc, fr, Jc.p, Jl.p, pp + o_eval,
+                                       cfg.loss_scale);
+            } else if constexpr (L.value == XM_BA_LOSS_TRIVIAL) hipLaunchKernelGGL((ba_eval_kernel<CD>), dim3(ge), b256, 0, st, S, Rc, Tc, Pc, Jc.p, Jl.p, pp + o_eval);
             else hipLaunchKernelGGL((ba_eval_kernel<CD, L.value, double>), dim3(ge), b256, 0, st, S, Rc, Tc, Pc, Jc.p, Jl.p, pp + o_eval, cfg.loss_scale);
         });
         BaReduce rd{};
@@ -1163,6 +1280,10 @@ struct BaWork {
     // every LM iteration (S changes with mu): the block inverses; two-level: A_c = P^T S P and its inverse.  A_c that cannot be inverted (a
     // pivot that is not positive, an entry that is not finite): this iteration's PCG runs with the blocks alone
     void precond_setup() {
+        if constexpr (ba_has_focal<CD>()) return;   // refused before the workspace is made: the ba_tl_* kernels are not instantiated for CD = 7 / 4
+        else precond_setup_launches();
+    }
+    void precond_setup_launches() {
         hipLaunchKernelGGL((ba_tl_block_kernel<CD>), dim3((unsigned)tl.nagg), b256, 0, st, S, tl, (const double *)Jc.p, (const double *)Jl.p,
                            (const double *)vinv.p, (const double *)ustar.p, tl_binv.p);
         tl.use_coarse = 0;
@@ -1224,8 +1345,10 @@ struct BaWork {
     const BaPcg &pcg_args() const { return tlmode ? atl : a; }
     // the update of iteration it (or the start) with M^-1 = blocks [+ coarse]
     void precond(int it, int init) {
-        hipLaunchKernelGGL((ba_tl_apply_block_kernel<CD>), dim3((unsigned)tl.nagg), b256, 0, st, atl, tl, it, init);
-        hipLaunchKernelGGL((ba_tl_apply_coarse_kernel<CD>), dim3((unsigned)tl.ncoarse), b256, 0, st, atl, tl, it, init);
+        if constexpr (!ba_has_focal<CD>()) {
+            hipLaunchKernelGGL((ba_tl_apply_block_kernel<CD>), dim3((unsigned)tl.nagg), b256, 0, st, atl, tl, it, init);
+            hipLaunchKernelGGL((ba_tl_apply_coarse_kernel<CD>), dim3((unsigned)tl.ncoarse), b256, 0, st, atl, tl, it, init);
+        }
     }
     // the PCG's start: x = 0, r = b, z = M^-1 b, p = z and the first partial sums
     void pcg_start() {
@@ -1236,13 +1359,26 @@ struct BaWork {
     void candidate(int nx, const double *dc) {
         hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)gl.p, -1.0,
                            (const int32_t *)lused.p, dc, (const BaState *)nullptr, dP.p);
-        hipLaunchKernelGGL((ba_cand_cam_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p, dc,
-                           (const int32_t *)cused.p, R[nx].p, T[nx].p, pp + o_cand);
+        if constexpr (ba_has_focal<CD>()) {
+            XM_HIP_CHECK(hipMemsetAsync(&dst->bad_focal, 0, sizeof(int32_t), st));
+            hipLaunchKernelGGL((ba_cand_cam_focal_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p,
+                               (const double *)G[cur].p, (const uint8_t *)gfree.p, dc, (const int32_t *)cused.p, R[nx].p, T[nx].p, G[nx].p, dst,
+                               pp + o_cand);
+        } else
+            hipLaunchKernelGGL((ba_cand_cam_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p, dc,
+                               (const int32_t *)cused.p, R[nx].p, T[nx].p, pp + o_cand);
         hipLaunchKernelGGL(ba_cand_vec_kernel<3>, dim3(gfl), b256, 0, st, m, (const double *)P[cur].p, (const double *)dP.p, (const int32_t *)lused.p,
                            P[nx].p, pp + o_cand + 2 * (size_t)gfc);
         with_loss(cfg.loss, [&](auto L) {
             const double *Rn = R[nx].p, *Tn = T[nx].p, *Pn = P[nx].p, *J = Jc.p, *dl = dP.p;
-            if constexpr (L.value == XM_BA_LOSS_TRIVIAL) hipLaunchKernelGGL((ba_cost_kernel<CD>), dim3(ge), b256, 0, st, S, Rn, Tn, Pn, J, dc, dl, pp + o_cost);
+            if constexpr (ba_has_focal<CD>()) {
+                const double *Gn = G[nx].p;
+                if constexpr (L.value == XM_BA_LOSS_TRIVIAL)
+                    hipLaunchKernelGGL((ba_cost_focal_kernel<CD>), dim3(ge), b256, 0, st, S, Rn, Tn, Pn, Gn, J, dc, dl, pp + o_cost);
+                else
+                    hipLaunchKernelGGL((ba_cost_focal_kernel<CD, L.value, double>), dim3(ge), b256, 0, st, S, Rn, Tn, Pn, Gn, J, dc, dl, pp + o_cost,
+                                       cfg.loss_scale);
+            } else if constexpr (L.value == XM_BA_LOSS_TRIVIAL) hipLaunchKernelGGL((ba_cost_kernel<CD>), dim3(ge), b256, 0, st, S, Rn, Tn, Pn, J, dc, dl, pp + o_cost);
             else hipLaunchKernelGGL((ba_cost_kernel<CD, L.value, double>), dim3(ge), b256, 0, st, S, Rn, Tn, Pn, J, dc, dl, pp + o_cost, cfg.loss_scale);
         });
         reduce(candidate_sums(pp + o_cost, ge, pp + o_cand, gfc, gfl, dst));
@@ -1295,6 +1431,7 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
             c.solved = !s.fail;
             c.relres = c.solved ? (s.res2[1] > 0.0 ? std::sqrt(s.res2[0] / s.res2[1]) : 0.0) : -1.0;
         }
+        if constexpr (ba_has_focal<CD>()) c.solved = c.solved && !s.bad_focal;   // a candidate focal that is not positive: an invalid step
         return c;
     };
     lm.accept = [&](bool new_best) {
@@ -1326,6 +1463,10 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         const int32_t sl = slot_of[(size_t)l];
         if (!lu[(size_t)sl]) continue;
         for (int a = 0; a < 3; ++a) p[(size_t)3 * l + a] = hP[(size_t)3 * sl + a];
+    }
+    if constexpr (ba_has_focal<CD>()) {   // held focals and those of cameras without a used observation were copied from set to set
+        XM_HIP_CHECK(hipMemcpyAsync(cfg.focal, W.G[cur].p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+        wait_stream(st, cfg.watchdog_s, kStage, "the refined focal scales");
     }
     out.status = res.status; out.iters = res.iters; out.accepted = res.accepted; out.pcg_iters = res.pcg_total;
     out.final_cost = res.final_cost; out.gradient_max = res.gmax; out.trace_len = lm_copy_trace(res, cfg.trace, cfg.trace_cap);
@@ -1416,6 +1557,10 @@ void probe(const SchurOp &SO, const BaSettings &cfg, const double *rot, const do
         const BaState s = W.read_state("the probe's candidate");
         q.cost1 = s.cost_new; q.model = s.model;
         q.step2[0] = s.step2[0]; q.step2[1] = s.step2[1]; q.x2[0] = s.x2[0]; q.x2[1] = s.x2[1];
+        if constexpr (ba_has_focal<CD>()) {
+            if (s.bad_focal) q.cost1 = std::nan("");   // the candidate the loop rejects as invalid
+            if (q.focal1) { d2h(q.focal1, W.G[1].p, (size_t)n * sizeof(double)); sync("the candidate focal scales"); }
+        }
         lm_out(W.dP.p, 3, q.dP);
         lm_out(W.P[1].p, 3, q.p1);
         if (q.rot1 || q.t1) {   // as the loop returns them: cameras without a used observation keep the caller's bits
@@ -1507,26 +1652,47 @@ void ba_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int32_
 
 void bundle_adjust(const SchurOp &S, const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out, hipStream_t st) {
     out = BaOutcome();
+    if (cfg.refine_focal) {
+        if (cfg.precond != 0 || !cfg.focal) throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust_focal: needs the focal scales and the default preconditioner");
+        if (cfg.fix_rotations) run<4>(S, cfg, rot, t, p, out, st);
+        else run<7>(S, cfg, rot, t, p, out, st);
+        return;
+    }
     if (cfg.fix_rotations) run<3>(S, cfg, rot, t, p, out, st);
     else run<6>(S, cfg, rot, t, p, out, st);
 }
 
 void ba_probe(const SchurOp &S, const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q, hipStream_t st) {
+    if (cfg.refine_focal) {
+        if (cfg.precond != 0 || !cfg.focal) throw Error(XM_ERR_ARG, "xm_ctx_ba_probe_focal: needs the focal scales and the default preconditioner");
+        if (cfg.fix_rotations) probe<4>(S, cfg, rot, t, p, q, st);
+        else probe<7>(S, cfg, rot, t, p, q, st);
+        return;
+    }
     if (cfg.fix_rotations) probe<3>(S, cfg, rot, t, p, q, st);
     else probe<6>(S, cfg, rot, t, p, q, st);
 }
 
-void reprojection_errors(const SchurOp &SO, const double *rot, const double *t, const double *p, double *sqerr, double watchdog_s, hipStream_t st) {
+void reprojection_errors(const SchurOp &SO, const double *rot, const double *t, const double *p, const double *focal, double *sqerr, double watchdog_s,
+                         hipStream_t st) {
     const SchurLists S = SO.lists();
     std::vector<double> hR, hT, hP;
     to_device_layout(SO, rot, t, p, hR, hT, hP);
-    DevBuf<double> R, T, P, out;
+    DevBuf<double> R, T, P, G, out;
+    if (focal) {
+        G.alloc((size_t)S.n, false);
+        XM_HIP_CHECK(hipMemcpyAsync(G.p, focal, (size_t)S.n * sizeof(double), hipMemcpyHostToDevice, st));
+    }
     R.alloc(hR.size(), false); T.alloc(hT.size(), false); P.alloc(hP.size(), false); out.alloc((size_t)std::max<int64_t>(S.nobs, 1), false);
     XM_HIP_CHECK(hipMemcpyAsync(R.p, hR.data(), hR.size() * sizeof(double), hipMemcpyHostToDevice, st));
     XM_HIP_CHECK(hipMemcpyAsync(T.p, hT.data(), hT.size() * sizeof(double), hipMemcpyHostToDevice, st));
     XM_HIP_CHECK(hipMemcpyAsync(P.p, hP.data(), hP.size() * sizeof(double), hipMemcpyHostToDevice, st));
     if (S.nobs > 0) {
-        hipLaunchKernelGGL(ba_sqerr_kernel, dim3(flat_grid(S.nobs)), dim3(256), 0, st, S, (const double *)R.p, (const double *)T.p, (const double *)P.p, out.p);
+        if (focal)
+            hipLaunchKernelGGL(ba_sqerr_focal_kernel, dim3(flat_grid(S.nobs)), dim3(256), 0, st, S, (const double *)R.p, (const double *)T.p,
+                               (const double *)P.p, (const double *)G.p, out.p);
+        else
+            hipLaunchKernelGGL(ba_sqerr_kernel, dim3(flat_grid(S.nobs)), dim3(256), 0, st, S, (const double *)R.p, (const double *)T.p, (const double *)P.p, out.p);
         check_launch("the reprojection errors");
         XM_HIP_CHECK(hipMemcpyAsync(sqerr, out.p, (size_t)S.nobs * sizeof(double), hipMemcpyDeviceToHost, st));
     }

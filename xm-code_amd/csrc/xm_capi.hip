@@ -374,9 +374,10 @@ int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int
     return XM_OK;
     XM_CATCH
 }
-int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, xm_ba_result_t *res) {
-    XM_TRY
-    if (!ctx || !opt || !res || !rot || !t || !p) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: null argument");
+// xm_ctx_bundle_adjust (with_focal = false: XM_BA_REFINE_FOCAL is an unknown flag) and xm_ctx_bundle_adjust_focal (it is required)
+static void ba_entry(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, bool with_focal, double *focal,
+                     const uint8_t *focal_free, xm_ba_result_t *res) {
+    if (!ctx || !opt || !res || !rot || !t || !p || (with_focal && !focal)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: null argument");
     static_assert(offsetof(xm_ba_options_t, loss) == XM_BA_OPTIONS_SIZE_V1, "the first version of xm_ba_options_t ends at trace");
     if (opt->struct_size != sizeof(xm_ba_options_t) && opt->struct_size != XM_BA_OPTIONS_SIZE_V1)
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: xm_ba_options_t.struct_size is neither sizeof(xm_ba_options_t) nor XM_BA_OPTIONS_SIZE_V1");
@@ -390,8 +391,12 @@ int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot,
     if (!(o.eta > 0.0 && o.eta < 1.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: eta must lie in (0, 1)");
     if (o.max_iters < 0 || bad(o.max_time) || bad(o.function_tol) || bad(o.gradient_tol) || bad(o.parameter_tol))
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: negative or non-finite setting");
-    if (o.flags & ~(XM_BA_FIX_ROTATIONS | XM_BA_NONMONOTONIC | XM_BA_DENSE_SCHUR | XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS))
+    if (o.flags & ~(XM_BA_FIX_ROTATIONS | XM_BA_NONMONOTONIC | XM_BA_DENSE_SCHUR | XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS |
+                    (with_focal ? XM_BA_REFINE_FOCAL : 0u)))
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: unknown flag");
+    if (with_focal && !(o.flags & XM_BA_REFINE_FOCAL)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust_focal: XM_BA_REFINE_FOCAL is not set");
+    if (with_focal && (o.flags & (XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS)))
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust_focal: the aggregate preconditioners have no focal column (use the default preconditioner)");
     if ((o.flags & XM_BA_PRECOND_TWO_LEVEL) && (o.flags & XM_BA_PRECOND_BLOCKS))
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: XM_BA_PRECOND_TWO_LEVEL and XM_BA_PRECOND_BLOCKS exclude each other");
     if ((o.flags & XM_BA_DENSE_SCHUR) && (o.flags & (XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS)))
@@ -404,7 +409,7 @@ int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot,
     if (o.max_nonmonotonic < 0) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: max_nonmonotonic is negative");
     if (o.trace_cap < 0 || (o.trace_cap > 0 && !o.trace)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: trace_cap > 0 needs a trace array");
     const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks();
-    if ((o.flags & XM_BA_DENSE_SCHUR) && ((o.flags & XM_BA_FIX_ROTATIONS) ? 3 : 6) * n > XM_BA_DENSE_MAX_ROWS)
+    if ((o.flags & XM_BA_DENSE_SCHUR) && (((o.flags & XM_BA_FIX_ROTATIONS) ? 3 : 6) + (with_focal ? 1 : 0)) * n > XM_BA_DENSE_MAX_ROWS)
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: XM_BA_DENSE_SCHUR with more than XM_BA_DENSE_MAX_ROWS rows in the reduced camera system");
     for (int64_t k = 0; k < 9 * n; ++k)
         if (!std::isfinite(rot[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: rotations are not finite");
@@ -412,7 +417,11 @@ int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot,
         if (!std::isfinite(t[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: translations are not finite");
     for (int64_t k = 0; k < 3 * m; ++k)
         if (!std::isfinite(p[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: landmarks are not finite");
+    if (with_focal)
+        for (int64_t k = 0; k < n; ++k)
+            if (!std::isfinite(focal[k]) || !(focal[k] > 0.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust_focal: a focal scale is not finite and > 0");
     xm::BaSettings c;
+    c.refine_focal = with_focal; c.focal = focal; c.focal_free = focal_free;
     if (o.max_iters > 0) c.max_iters = o.max_iters;
     if (o.max_time > 0.0) c.max_time = o.max_time;
     if (o.function_tol > 0.0) c.function_tol = o.function_tol;
@@ -435,12 +444,22 @@ int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot,
     out.initial_cost = r.initial_cost; out.final_cost = r.final_cost; out.gradient_max = r.gradient_max; out.seconds = r.seconds;
     out.trace_len = r.trace_len; out.coarse_fallbacks = r.coarse_fallbacks;
     *res = out;
+}
+int xm_ctx_bundle_adjust(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, xm_ba_result_t *res) {
+    XM_TRY
+    ba_entry(ctx, opt, rot, t, p, false, nullptr, nullptr, res);
     return XM_OK;
     XM_CATCH
 }
-int xm_ctx_reprojection_errors(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, double *sqerr) {
+int xm_ctx_bundle_adjust_focal(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, double *focal, const uint8_t *focal_free,
+                               xm_ba_result_t *res) {
     XM_TRY
-    if (!ctx || !rot || !t || !p || !sqerr) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: null argument");
+    ba_entry(ctx, opt, rot, t, p, true, focal, focal_free, res);
+    return XM_OK;
+    XM_CATCH
+}
+static void sqerr_entry(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, bool with_focal, const double *focal, double *sqerr) {
+    if (!ctx || !rot || !t || !p || !sqerr || (with_focal && !focal)) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: null argument");
     if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: single-GPU contexts only (not n_gpus > 1)");
     if (ctx->impl->world() > 1) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: single-rank contexts only");
     const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks();
@@ -450,18 +469,35 @@ int xm_ctx_reprojection_errors(xm_ctx_t *ctx, const double *rot, const double *t
         if (!std::isfinite(t[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: translations are not finite");
     for (int64_t k = 0; k < 3 * m; ++k)
         if (!std::isfinite(p[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: landmarks are not finite");
-    ctx->impl->reprojection_errors(rot, t, p, sqerr);
+    if (with_focal)
+        for (int64_t k = 0; k < n; ++k)
+            if (!std::isfinite(focal[k]) || !(focal[k] > 0.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors_focal: a focal scale is not finite and > 0");
+    ctx->impl->reprojection_errors(rot, t, p, sqerr, with_focal ? focal : nullptr);
+}
+int xm_ctx_reprojection_errors(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, double *sqerr) {
+    XM_TRY
+    sqerr_entry(ctx, rot, t, p, false, nullptr, sqerr);
     return XM_OK;
     XM_CATCH
 }
-int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_ba_probe_t *pr) {
+int xm_ctx_reprojection_errors_focal(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, const double *focal, double *sqerr) {
     XM_TRY
-    if (!ctx || !rot || !t || !p || !pr) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: null argument");
+    sqerr_entry(ctx, rot, t, p, true, focal, sqerr);
+    return XM_OK;
+    XM_CATCH
+}
+static void probe_entry(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, bool with_focal, const double *focal,
+                        const uint8_t *focal_free, xm_ba_probe_t *pr, double *focal1) {
+    if (!ctx || !rot || !t || !p || !pr || (with_focal && !focal)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: null argument");
     if (pr->struct_size != sizeof(xm_ba_probe_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: xm_ba_probe_t.struct_size is not sizeof(xm_ba_probe_t)");
     if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: single-GPU contexts only (not n_gpus > 1)");
     if (ctx->impl->world() > 1) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: single-rank contexts only");
     if (!(pr->mu > 0.0) || !std::isfinite(pr->mu)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: mu must be finite and > 0");
-    if (pr->flags & ~(XM_BA_FIX_ROTATIONS | XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: unknown flag");
+    if (pr->flags & ~(XM_BA_FIX_ROTATIONS | XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS | (with_focal ? XM_BA_REFINE_FOCAL : 0u)))
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: unknown flag");
+    if (with_focal && !(pr->flags & XM_BA_REFINE_FOCAL)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe_focal: XM_BA_REFINE_FOCAL is not set");
+    if (with_focal && (pr->flags & (XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS)))
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe_focal: the aggregate preconditioners have no focal column");
     if ((pr->flags & XM_BA_PRECOND_TWO_LEVEL) && (pr->flags & XM_BA_PRECOND_BLOCKS))
         throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: XM_BA_PRECOND_TWO_LEVEL and XM_BA_PRECOND_BLOCKS exclude each other");
     if (pr->loss < XM_BA_LOSS_TRIVIAL || pr->loss > XM_BA_LOSS_ARCTAN) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: unknown loss");
@@ -469,7 +505,7 @@ int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const dou
     if (pr->loss != XM_BA_LOSS_TRIVIAL && !(std::isfinite(pr->loss_scale) && pr->loss_scale > 0.0))
         throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: a robust loss needs a finite loss_scale > 0");
     if (pr->k < 0 || (pr->k > 0 && !pr->X)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: k > 0 needs X");
-    const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks(), cd = (pr->flags & XM_BA_FIX_ROTATIONS) ? 3 : 6;
+    const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks(), cd = ((pr->flags & XM_BA_FIX_ROTATIONS) ? 3 : 6) + (with_focal ? 1 : 0);
     if (pr->Sdense && cd * n > XM_BA_PROBE_DENSE_MAX_ROWS) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: Sdense with more than XM_BA_PROBE_DENSE_MAX_ROWS rows");
     for (int64_t k = 0; k < 9 * n; ++k)
         if (!std::isfinite(rot[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: rotations are not finite");
@@ -482,7 +518,11 @@ int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const dou
     if (pr->dc)
         for (int64_t k = 0; k < cd * n; ++k)
             if (!std::isfinite(pr->dc[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: dc is not finite");
+    if (with_focal)
+        for (int64_t k = 0; k < n; ++k)
+            if (!std::isfinite(focal[k]) || !(focal[k] > 0.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe_focal: a focal scale is not finite and > 0");
     xm::BaSettings c;
+    c.refine_focal = with_focal; c.focal = const_cast<double *>(focal); c.focal_free = focal_free;   // the probe only reads them
     c.fix_rotations = (pr->flags & XM_BA_FIX_ROTATIONS) != 0;
     c.loss = pr->loss; c.loss_scale = pr->loss_scale;
     c.precond = (pr->flags & XM_BA_PRECOND_TWO_LEVEL) ? 2 : (pr->flags & XM_BA_PRECOND_BLOCKS) ? 1 : 0;
@@ -490,11 +530,22 @@ int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const dou
     q.mu = pr->mu; q.k = pr->k; q.X = pr->X; q.dc = pr->dc;
     q.b = pr->b; q.g_l = pr->g_l; q.vinv = pr->vinv; q.ustar = pr->ustar; q.sinv = pr->sinv; q.cused = pr->cused; q.lused = pr->lused;
     q.SX = pr->SX; q.Sdense = pr->Sdense; q.MX = pr->MX; q.Pm = pr->Pm; q.dropped = pr->dropped; q.Ac = pr->Ac;
-    q.dP = pr->dP; q.rot1 = pr->rot1; q.t1 = pr->t1; q.p1 = pr->p1;
+    q.dP = pr->dP; q.rot1 = pr->rot1; q.t1 = pr->t1; q.p1 = pr->p1; q.focal1 = with_focal ? focal1 : nullptr;
     ctx->impl->ba_probe(c, rot, t, p, q);
     pr->cost = q.cost; pr->gmax = q.gmax; pr->cost1 = q.cost1; pr->model = q.model; pr->n_used = q.n_used;
     pr->step2[0] = q.step2[0]; pr->step2[1] = q.step2[1]; pr->x2[0] = q.x2[0]; pr->x2[1] = q.x2[1];
     pr->nagg = q.nagg; pr->ncoarse = q.ncoarse; pr->coarse_ok = q.coarse_ok;
+}
+int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_ba_probe_t *pr) {
+    XM_TRY
+    probe_entry(ctx, rot, t, p, false, nullptr, nullptr, pr, nullptr);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_ctx_ba_probe_focal(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, const double *focal, const uint8_t *focal_free,
+                          xm_ba_probe_t *pr, double *focal1) {
+    XM_TRY
+    probe_entry(ctx, rot, t, p, true, focal, focal_free, pr, focal1);
     return XM_OK;
     XM_CATCH
 }

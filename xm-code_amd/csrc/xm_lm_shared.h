@@ -31,7 +31,8 @@ struct BaState {              // device-resident; the host reads it whole
     double cost_new, model;   // candidate: F, sum r.Jd + |Jd|^2 / 2
     double step2[2], x2[2];   // |d|^2, |x|^2: cameras, landmarks
     double res2[2];           // dense Schur: |b - S dc|^2, |b|^2
-    int32_t fail, pad;        // dense Schur: 1 = the factorisation or a substitution failed (cleared before each factorisation)
+    int32_t fail, bad_focal;  // dense Schur: 1 = the factorisation or a substitution failed (cleared before each factorisation); bundle
+                              // adjustment with focal scales: 1 = a candidate focal is not positive (cleared before each candidate)
 };
 
 __device__ __forceinline__ double clamp_diag(double d) { return fmin(fmax(d, 1e-6), 1e32); }

@@ -37,6 +37,7 @@ EXPORTS = [
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
     "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_la_probe", "xm_ba_aggregate_plan", "xm_ctx_ba_probe", "xm_lm_replay",
+    "xm_ctx_bundle_adjust_focal", "xm_ctx_reprojection_errors_focal", "xm_ctx_ba_probe_focal",
     "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe", "xm_ctx_outer_probe", "xm_ctx_cert_probe", "xm_tridiag_min", "xm_ctx_schur_probe",
     "xm_ctx_dense_q", "xm_create_matrix", "xm_schur_dense_limits",
     "xm_pair_filter", "xm_pair_filter_limits",
@@ -442,6 +443,7 @@ BA_PRECOND_TWO_LEVEL = 32      # PCG preconditioner: aggregate blocks + rigid-mo
 BA_PRECOND_BLOCKS = 64         # ... the aggregate blocks alone
 BA_AGG_CAMS = 16               # cameras per aggregate
 BA_MAX_AGGREGATES = 4096
+BA_REFINE_FOCAL = 128          # a focal scale per camera in the camera block (xm_ctx_bundle_adjust_focal; the default preconditioner only)
 BA_PRECONDITIONERS = {"jacobi": 0, "blocks": BA_PRECOND_BLOCKS, "two_level": BA_PRECOND_TWO_LEVEL}
 BA_LOSS = {"trivial": 0, "huber": 1, "soft_l1": 2, "cauchy": 3, "arctan": 4}
 BA_OPTIONS_SIZE_V1 = 64        # struct_size of callers built before loss, max_nonmonotonic and loss_scale (include/xm_amd.h)
@@ -485,6 +487,10 @@ def lib():
         L.xm_ctx_recover_tp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_bundle_adjust.argtypes = [C.c_void_p, C.POINTER(BaOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaResult)]
         L.xm_ctx_ba_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaProbe)]
+        L.xm_ctx_bundle_adjust_focal.argtypes = [C.c_void_p, C.POINTER(BaOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(BaResult)]
+        L.xm_ctx_reprojection_errors_focal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.xm_ctx_ba_probe_focal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaProbe), C.c_void_p]
         L.xm_ctx_rtr_probe.argtypes = [C.c_void_p, C.POINTER(RtrProbe)]
         L.xm_ctx_outer_probe.argtypes = [C.c_void_p, C.POINTER(OuterProbe)]
         L.xm_ctx_cert_probe.argtypes = [C.c_void_p, C.POINTER(CertProbe)]
@@ -864,6 +870,41 @@ def schur_aggregate_plan(cam, lm, n=None, B=64):
     _chk(lib().xm_schur_aggregate_plan(n, cam.size, cam.ctypes.data_as(C.c_void_p), lm.ctypes.data_as(C.c_void_p), int(B),
                                        out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+def _focal_args(n, focal, focal_free, preconditioner="jacobi"):
+    """the focal scales (ones when None) and the mask of the free ones (None = all) of a call with focal scales, refused here, before
+    the device, as the C entry points refuse them: a preconditioner other than "jacobi", a wrong length, a focal that is not finite and > 0"""
+    if preconditioner != "jacobi":
+        raise XmError(f"refine_focal: the preconditioner {preconditioner!r} has no focal column (only 'jacobi')")
+    focal = np.ones(n) if focal is None else np.array(focal, dtype=np.float64).reshape(-1)
+    if focal.shape != (n,):
+        raise XmError(f"focal: {focal.size} values for {n} cameras")
+    if not (np.isfinite(focal).all() and (focal > 0.0).all()):
+        raise XmError("focal: every focal scale must be finite and > 0")
+    if focal_free is not None:
+        focal_free = np.ascontiguousarray(np.asarray(focal_free).reshape(-1) != 0, dtype=np.uint8)
+        if focal_free.shape != (n,):
+            raise XmError(f"focal_free: {focal_free.size} values for {n} cameras")
+    return focal, focal_free
+
+
+def rescale_observations(p, cam, focal):
+    """the observations (3 x nobs or nobs x 3 as given, p_e = (p0, p1, p2)) of the cameras cam (nobs) as the refined focal scales normalise
+    them: (p0 / g, p1 / g, p2) with g = focal[cam].  A Context built from them carries the refined calibration at g = 1: everything
+    that has no focal argument (filter_tracks, refine_filtered, global_positioning, a second solve) then uses it."""
+    p = np.array(p, dtype=np.float64)
+    cam = np.asarray(cam).reshape(-1)
+    g = np.asarray(focal, dtype=np.float64).reshape(-1)[cam]
+    if not (np.isfinite(g).all() and (g > 0.0).all()):
+        raise XmError("rescale_observations: every focal scale must be finite and > 0")
+    if p.ndim == 2 and p.shape[0] == 3 and p.shape[1] == cam.size:
+        p[0] /= g; p[1] /= g
+    elif p.ndim == 2 and p.shape == (cam.size, 3):
+        p[:, 0] /= g; p[:, 1] /= g
+    else:
+        raise XmError("rescale_observations: p must be 3 x nobs or nobs x 3")
+    return p
 
 
 def ba_aggregate_plan(cam, lm, n=None, used=None, B=BA_AGG_CAMS):
@@ -2017,7 +2058,7 @@ class Context:
 
     def bundle_adjust(self, rot, t, P, fix_rotations=False, max_iters=1000, max_time=300.0, eta=0.1, function_tol=1e-6,
                       gradient_tol=1e-10, parameter_tol=1e-8, trace=0, loss="trivial", loss_scale=0.0, nonmonotonic=False, max_nonmonotonic=0,
-                      linear_solver="iterative_schur", preconditioner="jacobi"):
+                      linear_solver="iterative_schur", preconditioner="jacobi", refine_focal=False, focal=None, focal_free=None):
         """reprojection bundle adjustment of a recovered solution (the reference's Ceres refinement, xm_ctx_bundle_adjust): rot 3 x 3n
         (R_i), t 3 x n, P 3 x m as recover_rotations / recover_tp return them -> refined (rot, t, P, info); matrix-free contexts only.
         loss: a BA_LOSS name with its scale loss_scale (Ceres's a, in normalised image units: pixels / focal length); nonmonotonic=True:
@@ -2030,7 +2071,14 @@ class Context:
         whose coarse operator could not be inverted and that ran with the blocks alone.
         info: status (BA_STATUS), iters, accepted, pcg_iters, n_used, initial_cost, final_cost, gradient_max, seconds, and with trace > 0
         "trace": one row per LM iteration (cost, candidate cost, mu, accepted, PCG iterations, PCG relative residual); costs are
-        1/2 sum rho(|r|^2)"""
+        1/2 sum rho(|r|^2).
+        refine_focal=True (xm_ctx_bundle_adjust_focal): one focal scale g_i > 0 per camera joins its block, r = g_i pi(X) - z; focal (n;
+        None = ones) is the start, focal_free (n; None = all) holds the cameras with 0 at their value; info["focal"] is the refined
+        array.  preconditioner must be "jacobi"."""
+        if refine_focal:   # refused before the device
+            focal, focal_free = _focal_args(self.n, focal, focal_free, preconditioner)
+        elif focal is not None or focal_free is not None:
+            raise XmError("focal / focal_free are given but refine_focal is not set")
         rot = np.array(rot, dtype=np.float64, order="F"); t = np.array(t, dtype=np.float64, order="F"); P = np.array(P, dtype=np.float64, order="F")
         assert rot.shape == (3, 3 * self.n) and t.shape == (3, self.n) and P.shape == (3, self.n_landmarks)
         if loss not in BA_LOSS:
@@ -2049,9 +2097,17 @@ class Context:
         tr = None
         if trace:
             tr = np.zeros((int(trace), 6)); opt.trace_cap = int(trace); opt.trace = tr.ctypes.data_as(C.c_void_p)
-        _chk(lib().xm_ctx_bundle_adjust(self.h, C.byref(opt), rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
-                                        P.ctypes.data_as(C.c_void_p), C.byref(res)))
+        if refine_focal:
+            opt.flags |= BA_REFINE_FOCAL
+            _chk(lib().xm_ctx_bundle_adjust_focal(self.h, C.byref(opt), rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                                  P.ctypes.data_as(C.c_void_p), focal.ctypes.data_as(C.c_void_p),
+                                                  None if focal_free is None else focal_free.ctypes.data_as(C.c_void_p), C.byref(res)))
+        else:
+            _chk(lib().xm_ctx_bundle_adjust(self.h, C.byref(opt), rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                            P.ctypes.data_as(C.c_void_p), C.byref(res)))
         info = {k: getattr(res, k) for k, _ in BaResult._fields_ if k != "struct_size"}
+        if refine_focal:
+            info["focal"] = focal
         info["status_name"] = BA_STATUS.get(res.status, "?")
         if tr is not None:
             info["trace"] = tr[: res.trace_len].copy()
@@ -2133,6 +2189,17 @@ class Context:
         (M^-1 X for the preconditioner); dense=True: Sdense (the lower block triangle); preconditioner "two_level": Pm (CD n x NC), dropped,
         Ac (lower block triangle), coarse_ok, nagg, ncoarse; with dc (CD n): dP (m x 3), rot1, t1, p1, cost1, model, step2, x2.  Landmark
         arrays by input index."""
+        return self._ba_probe(rot, t, P, mu, fix_rotations, loss, loss_scale, preconditioner, X, dc, dense, False, None, None)
+
+    def ba_probe_focal(self, rot, t, P, mu, focal=None, focal_free=None, fix_rotations=False, loss="trivial", loss_scale=0.0, X=None, dc=None,
+                       dense=False, preconditioner="jacobi"):
+        """ba_probe for bundle_adjust(refine_focal=True) (the test export xm_ctx_ba_probe_focal): focal, focal_free as there; the same dict
+        with CD = 7, or 4 with fixed rotations, the focal the last entry of a camera's block; with dc also focal1 (n), the candidate's focal
+        scales, and cost1 is NaN when one of them is not positive.  preconditioner: only "jacobi" (the others are refused here)."""
+        focal, focal_free = _focal_args(self.n, focal, focal_free, preconditioner)
+        return self._ba_probe(rot, t, P, mu, fix_rotations, loss, loss_scale, preconditioner, X, dc, dense, True, focal, focal_free)
+
+    def _ba_probe(self, rot, t, P, mu, fix_rotations, loss, loss_scale, preconditioner, X, dc, dense, refine_focal, focal, focal_free):
         rot = np.asfortranarray(np.asarray(rot, dtype=np.float64)); t = np.asfortranarray(np.asarray(t, dtype=np.float64))
         P = np.asfortranarray(np.asarray(P, dtype=np.float64))
         n, m = self.n, self.n_landmarks
@@ -2142,10 +2209,11 @@ class Context:
         if preconditioner not in BA_PRECONDITIONERS:
             raise XmError(f"unknown preconditioner {preconditioner!r} (one of {', '.join(BA_PRECONDITIONERS)})")
         cd, nc = (3, 4) if fix_rotations else (6, 7)
+        cd += 1 if refine_focal else 0
         nd = cd * n
         q = BaProbe()
         q.struct_size = C.sizeof(BaProbe)
-        q.flags = (BA_FIX_ROTATIONS if fix_rotations else 0) | BA_PRECONDITIONERS[preconditioner]
+        q.flags = (BA_FIX_ROTATIONS if fix_rotations else 0) | BA_PRECONDITIONERS[preconditioner] | (BA_REFINE_FOCAL if refine_focal else 0)
         q.loss, q.loss_scale, q.mu = BA_LOSS[loss], float(loss_scale), float(mu)
         out = dict(b=np.zeros((n, cd)), g_l=np.zeros((m, 3)), vinv=np.zeros((m, 6)), ustar=np.zeros((n, cd, cd)), sinv=np.zeros((n, cd, cd)),
                    cused=np.zeros(n, dtype=np.int32), lused=np.zeros(m, dtype=np.int32))
@@ -2166,7 +2234,15 @@ class Context:
             out.update(dP=np.zeros((m, 3)), rot1=np.zeros((3, 3 * n), order="F"), t1=np.zeros((3, n), order="F"), p1=np.zeros((3, m), order="F"))
         for k, v in out.items():
             setattr(q, k, v.ctypes.data_as(C.c_void_p))
-        _chk(lib().xm_ctx_ba_probe(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p), C.byref(q)))
+        if refine_focal:
+            focal1 = np.zeros(n) if dc is not None else None
+            _chk(lib().xm_ctx_ba_probe_focal(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p),
+                                             focal.ctypes.data_as(C.c_void_p), None if focal_free is None else focal_free.ctypes.data_as(C.c_void_p),
+                                             C.byref(q), None if focal1 is None else focal1.ctypes.data_as(C.c_void_p)))
+            if focal1 is not None:
+                out["focal1"] = focal1
+        else:
+            _chk(lib().xm_ctx_ba_probe(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p), C.byref(q)))
         out.update(cost=q.cost, n_used=q.n_used, gmax=q.gmax, nagg=q.nagg, ncoarse=q.ncoarse, coarse_ok=q.coarse_ok)
         if preconditioner == "two_level":
             k = nc * q.ncoarse
@@ -2374,13 +2450,20 @@ class Context:
                 out.update(f_cand=q.f_cand, rr_cand=q.rr_cand, m_cand=q.m_cand)
         return {k: (np.ascontiguousarray(val) if isinstance(val, np.ndarray) else val) for k, val in out.items()}
 
-    def reprojection_errors(self, rot, t, P):
+    def reprojection_errors(self, rot, t, P, focal=None):
         """|r_e|^2 (unrobustified) of every observation in input order at (rot, t, P) -- the layouts of bundle_adjust -- with the
-        context's current weights, -1 where the adjustment does not use the observation (weight <= 0 or p_e2 <= 0): an (nobs,) array"""
+        context's current weights, -1 where the adjustment does not use the observation (weight <= 0 or p_e2 <= 0): an (nobs,) array.
+        focal (n): the residual with focal scales, g_i pi(X) - z (xm_ctx_reprojection_errors_focal)"""
+        if focal is not None:
+            focal, _ = _focal_args(self.n, focal, None)
         rot = np.asfortranarray(np.asarray(rot, dtype=np.float64)); t = np.asfortranarray(np.asarray(t, dtype=np.float64))
         P = np.asfortranarray(np.asarray(P, dtype=np.float64))
         assert rot.shape == (3, 3 * self.n) and t.shape == (3, self.n) and P.shape == (3, self.n_landmarks)
         out = np.zeros(self.ne)
+        if focal is not None:
+            _chk(lib().xm_ctx_reprojection_errors_focal(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                                        P.ctypes.data_as(C.c_void_p), focal.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+            return out
         _chk(lib().xm_ctx_reprojection_errors(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p),
                                               out.ctypes.data_as(C.c_void_p)))
         return out
