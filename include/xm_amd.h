@@ -1118,9 +1118,32 @@ int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int
  * The aggregate preconditioners are not available with a focal column (their coarse space, LDS block size and compensated assembly are
  * tuned to CD = 6 / 3): XM_BA_REFINE_FOCAL with XM_BA_PRECOND_TWO_LEVEL or XM_BA_PRECOND_BLOCKS is XM_ERR_ARG.  Also XM_ERR_ARG (context
  * unchanged and usable): focal NULL, a focal that is not finite or not positive, the flag missing, and every refusal above.
- * Departures from the reference: one focal per image (GLOMAP shares a Camera among images, which would couple camera blocks); no
- * distortion parameters; fx = fy.
- * xm_ctx_reprojection_errors_focal: sqerr[e] = |g_i pi(X) - z_e|^2, -1 where the observation is unused. */
+ * Departures from the reference: no distortion parameters; fx = fy; no aggregate preconditioners with a focal column.
+ * xm_ctx_reprojection_errors_focal: sqerr[e] = |g_i pi(X) - z_e|^2, -1 where the observation is unused.
+ *
+ * Focal groups (xm_ctx_bundle_adjust_focal_groups): GLOMAP shares a Camera among images -- every residual block takes
+ * cameras[image.camera_id].params (estimators/bundle_adjustment.cc:72-84), so the focal belongs to the camera, not to the image.  Here:
+ *   model       G groups; group_of (n, int32, in [0, G)) names every camera's group; focal (G, host, in-out, > 0), focal_free (G, uint8, or
+ *               NULL = all free).  r_e = g_{group_of[i]} pi(Rcw_i P_l + tcw_i) - z_e.
+ *   tangent     CP = CD - 1 columns per camera (6, or 3 with XM_BA_FIX_ROTATIONS), then the G focal entries: CP n + G in all (the order of
+ *               the probe's vectors).  With E the 0/1 matrix that copies a group's unknown into the focal column of each member,
+ *               J_shared = J_7 E; the reduced camera system is E^T S_7 E, its right-hand side E^T b_7.
+ *   damping     Ceres's rule on the shared parameter: D_c = clamp(sum_{i in c} (J_7^T J_7)_ff,i, 1e-6, 1e32), mu D_c on the group's diagonal
+ *               (not the sum of the members' clamped terms).
+ *   held        a group with focal_free[c] = 0, and a group none of whose members has a used observation (an empty group among them): zero
+ *               columns, right-hand side 0, diagonal mu 1e-6, a step of exactly 0; its focal comes back bit-identical.
+ *   g <= 0      a candidate g_c + dg_c <= 0 of a moving group is an invalid step, as above.
+ *   stops       |x|^2 adds g_c^2 and |d|^2 adds dg_c^2 once per moving group, not per member.
+ *   PCG         preconditioner blockdiag(the cameras' pose blocks of S, F).  G <= XM_BA_FOCAL_GROUPS_EXACT: F = S_shared[focal, focal], the
+ *               exact G x G block, from G products with indicator vectors once per LM iteration, inverted on the device; a factorisation
+ *               that fails leaves that iteration with the rule for larger G and is counted in xm_ba_result_t.coarse_fallbacks.  Larger G:
+ *               F = diag(sum_{i in c} S_7,ii[f, f] + mu D_c).  Both are SPD: principal blocks of an SPD matrix, or positive scalars.
+ *   dense       XM_BA_DENSE_SCHUR solves the (CP n + G)-row system exactly: the CD n matrix is assembled as before and its focal rows and
+ *               columns are contracted by group in a fixed order; XM_BA_DENSE_MAX_ROWS applies to CD n.
+ * Everything else is xm_ctx_bundle_adjust_focal word for word: the LM rules, losses, non-monotonic steps, stops, which observations are
+ * used, determinism (the sums over a group's members are taken in a fixed order without atomics: two calls give the same bytes).
+ * XM_ERR_ARG with the context unchanged: XM_BA_REFINE_FOCAL missing, G < 1 or G > n, a group_of entry out of range, a focal that is not
+ * positive or not finite, an aggregate preconditioner flag, and every refusal of the per-image form.  xm_ctx_reprojection_errors_focal takes per-image scales: pass focal[group_of[i]]. */
 #define XM_BA_FIX_ROTATIONS 1u          /* the reference's only_landmarks = True: rotations constant (bit-identical), t and P free */
 #define XM_BA_NONMONOTONIC  2u          /* Ceres's non-monotonic steps (see above) */
 #define XM_BA_DENSE_SCHUR   16u         /* Ceres's DENSE_SCHUR (see below) instead of ITERATIVE_SCHUR; 4 and 8 are not flags */
@@ -1128,6 +1151,7 @@ int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int
 #define XM_BA_PRECOND_BLOCKS    64u     /* PCG preconditioner: the aggregate blocks alone (the ablation of the above) */
 #define XM_BA_REFINE_FOCAL      128u    /* a focal scale per camera joins the camera block (xm_ctx_bundle_adjust_focal only; see above) */
 #define XM_BA_AGG_CAMS          16      /* cameras per aggregate */
+#define XM_BA_FOCAL_GROUPS_EXACT 16     /* focal groups: up to this many, the preconditioner's focal block is the exact G x G one */
 #define XM_BA_MAX_AGGREGATES    4096    /* at most this many aggregates (65 536 cameras): A_c has up to 28 672 rows */
 #define XM_BA_DENSE_MAX_ROWS 32768      /* XM_BA_DENSE_SCHUR: largest CD n (CD = 6, or 3 with XM_BA_FIX_ROTATIONS): an 8.6 GB matrix */
 #define XM_BA_LOSS_TRIVIAL  0
@@ -1168,6 +1192,9 @@ int xm_ctx_reprojection_errors(xm_ctx_t *ctx, const double *rot, const double *t
 int xm_ctx_bundle_adjust_focal(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, double *focal /* n, in-out */,
                                const uint8_t *focal_free /* n or NULL */, xm_ba_result_t *res);
 int xm_ctx_reprojection_errors_focal(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, const double *focal, double *sqerr);
+int xm_ctx_bundle_adjust_focal_groups(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, int64_t ngroups,
+                                      const int32_t *group_of /* n */, double *focal /* ngroups, in-out */,
+                                      const uint8_t *focal_free /* ngroups or NULL */, xm_ba_result_t *res);
 /* ---- Filtering tracks against a refined geometry: the TrackFilter of the reference's fork of GLOMAP
  * (deps/glomap/glomap/processors/track_filter.cc: FilterTracksByReprojection :7-51, FilterTracksByAngle :53-89,
  * FilterTrackTriangulationAngle :91-126), which GLOMAP alternates with its bundle adjustment (controllers/global_mapper.cc:243-317), as a
@@ -1511,6 +1538,17 @@ int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const dou
  * not positive is reported as cost1 = NaN (the loop rejects that step as invalid). */
 int xm_ctx_ba_probe_focal(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, const double *focal, const uint8_t *focal_free,
                           xm_ba_probe_t *probe, double *focal1);
+/* The same with focal groups (xm_ctx_bundle_adjust_focal_groups; tests/test_gpu_ba_groups_stages.py): ngroups, group_of, focal (ngroups),
+ * focal_free (ngroups or NULL) as there.  b, the columns of X, SX and MX, and dc have CP n + G entries: CP = CD - 1 per camera, then the G
+ * focal entries (0 comes back for an empty group).  ustar and sinv (CD CD n) are the blocks the device holds: U* with the focal diagonal
+ * undamped; the inverse of the pose block of S_ii with the preconditioner's 1 / F_c in the focal slot of the group's first member and 0 in
+ * the other members'.  The aggregate arrays have no meaning here and the struct keeps its size, so two of their pointers serve the groups:
+ * dropped (G or NULL) receives D_c; Ac (or NULL) receives F: the exact block as assembled, G x G column-major, for G <=
+ * XM_BA_FOCAL_GROUPS_EXACT (coarse_ok = 1 when it was inverted and the preconditioner uses it), else the G diagonal entries; Pm is ignored.
+ * focal1 (G or NULL): the groups' candidate scales.  gmax sees the groups' gradient entries sum_i g_if.  Sdense (CP n + G square,
+ * column-major): the lower triangle of the contracted matrix, the rest 0; CD n > XM_BA_PROBE_DENSE_MAX_ROWS: XM_ERR_ARG. */
+int xm_ctx_ba_probe_focal_groups(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, int64_t ngroups, const int32_t *group_of,
+                                 const double *focal, const uint8_t *focal_free, xm_ba_probe_t *probe, double *focal1);
 
 /* ---- Global positioning: camera centres and points from rotations and 2-D tracks, without an initial value.  Step 5 of GLOMAP's pipeline
  * (controllers/global_mapper.cc:188-231), estimators/global_positioning.cc in its default ONLY_POINTS form, on the device over the observation

@@ -42,6 +42,15 @@
 // is mu 1e-6 by the clamp, its right-hand side 0, its step exactly 0; the candidate kernel copies it.  A candidate focal <= 0 sets
 // bad_focal in the state word and the host rejects the step as it rejects a failed factorisation.  |x|^2 adds g_i^2 per used camera with
 // a free focal.  The aggregate preconditioners are not instantiated for CD = 7 / 4 (refused at the entry point).
+//
+// Focal groups (xm_ctx_bundle_adjust_focal_groups): one focal scale per group of cameras, GLOMAP's Camera shared among images.  With E the
+// 0/1 matrix that copies a group's unknown into the focal column of each member, J_shared = J_7 E and, as the landmark elimination commutes
+// with E, S_shared = E^T S_7 E, b_shared = E^T b_7: the CD = 7 / 4 kernels run unchanged on expanded vectors.  New around them: an expand
+// before the product (and before the back-substitution), a fixed-order sum by group after it, a set-up pass per LM iteration (D_c, b_c, the
+// preconditioner's F_c, which groups move) and the group's candidate.  The camera pass leaves the members' focal diagonal undamped
+// (summing mu clamp(U_ff,i) is not mu clamp(sum U_ff,i) once a member's clamp is active); mu D_c x_c joins in the group sum.  The PCG runs
+// on CD n vectors whose focal slots are 0 but for each group's representative, with M = blockdiag(inverted pose blocks, F): the exact G x G
+// focal block for G <= XM_BA_FOCAL_GROUPS_EXACT, its diagonal rule above.  XM_BA_DENSE_SCHUR: the CD n matrix contracted by group in place.
 #pragma once
 
 #include <cstdint>
@@ -65,6 +74,8 @@ struct BaSettings {
     bool refine_focal = false;    // XM_BA_REFINE_FOCAL: a focal scale per camera, the last column of the camera block (CD = 7 / 4)
     double *focal = nullptr;      // n focal scales > 0 (host; bundle_adjust updates them in place, ba_probe only reads them)
     const uint8_t *focal_free = nullptr;   // n, 0 = held; null: all free
+    int64_t ngroups = 0;          // > 0 (xm_ctx_bundle_adjust_focal_groups): one focal scale per group of cameras; focal and focal_free have
+    const int32_t *group_of = nullptr;     // ngroups entries then, group_of (n, host) names every camera's group
     int precond = 0;              // PCG preconditioner: 0 the inverted camera blocks | 1 XM_BA_PRECOND_BLOCKS | 2 XM_BA_PRECOND_TWO_LEVEL
     int trace_cap = 0;
     double *trace = nullptr;      // trace_cap x 6 row-major: cost, candidate cost, mu, accepted, PCG iterations, PCG relative residual
@@ -100,6 +111,10 @@ struct BaProbe {
     double *SX = nullptr, *Sdense = nullptr, *MX = nullptr, *Pm = nullptr, *dropped = nullptr, *Ac = nullptr;
     double *dP = nullptr, *rot1 = nullptr, *t1 = nullptr, *p1 = nullptr;
     double *focal1 = nullptr;   // refine_focal: the candidate's focal scales (n); cost1 is NaN when one of them is not positive
+    // focal groups: b, X, SX, MX and dc are vectors of CP n + G entries (CP = CD - 1 columns per camera, then the G focal entries); focal1
+    // has G entries; ustar and sinv are the blocks the device holds (the focal diagonal of U* undamped; the inverted pose block with the
+    // preconditioner's 1 / F_c in the representative's focal slot)
+    double *group_D = nullptr, *group_F = nullptr;   // D_c = clamp(sum U_ff,i) (G); F: G x G column-major for G <= XM_BA_FOCAL_GROUPS_EXACT, else G
 };
 
 // rot: 3 x 3n column-major (R_i, camera-to-world), t: 3 x n, p: 3 x m (host, updated in place).  The SchurOp is only read.

@@ -185,10 +185,15 @@ __global__ __launch_bounds__(kBaHeavyThreads) void ba_lm_kernel(SchurLists S, co
 
 // ---- camera pass (a wavefront per camera): U_i, g_i; S_ii = U*_i - sum_l (sum_e W_e) V*_l^-1 (sum_f W_f)^T over the observations e, f of
 // (i, l) and its inverse; b_i = -g_i + sum W V*^-1 g_l
-template <int CD>
+// (GR, focal groups: the focal diagonal of U*_i stays undamped -- the damping mu D_c of the shared parameter joins where the group sum is
+// taken --, sinv is the inverse of the leading pose block with 1 in the focal slot (ba_group_setup_kernel puts 1 / F_c or 0 there), the
+// focal gradient is left out of the maximum and goes with the undamped S_ii[f, f] to fstat (2 per camera))
+template <int CD, bool GR = false>
 __global__ __launch_bounds__(256) void ba_cam_kernel(SchurLists S, const double *__restrict__ Jc, const double *__restrict__ vinv,
                                                      const double *__restrict__ gl, double mu, double *__restrict__ ustar, double *__restrict__ sinv,
-                                                     double *__restrict__ b, int32_t *__restrict__ cused, double *__restrict__ gpart) {
+                                                     double *__restrict__ b, int32_t *__restrict__ cused, double *__restrict__ gpart,
+                                                     double *__restrict__ fstat = nullptr) {
+    static_assert(!GR || ba_has_focal<CD>(), "focal groups need a focal column");
     constexpr int JP = ba_jp<CD>(), RS = ba_res<CD>(), NU = CD * (CD + 1) / 2, NA = 2 * NU + 2 * CD + 1;
     __shared__ double red[kQwWaves];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -257,9 +262,16 @@ __global__ __launch_bounds__(256) void ba_cam_kernel(SchurLists S, const double 
 #pragma unroll
             for (int k = 0; k < CD; ++k) {
                 const double u = acc[tri(k, j)];
-                Us[j][k] = (j == k) ? u + mu * clamp_diag(u) : u;
+                if constexpr (GR) Us[j][k] = (j == k && j != ba_fidx<CD>()) ? u + mu * clamp_diag(u) : u;
+                else Us[j][k] = (j == k) ? u + mu * clamp_diag(u) : u;
                 Sm[j][k] = Us[j][k] - acc[NU + tri(k, j)];
             }
+        if constexpr (GR) {
+            constexpr int F = ba_fidx<CD>();
+            fstat[2 * cam] = Sm[F][F]; fstat[2 * cam + 1] = acc[2 * NU + F];
+#pragma unroll
+            for (int k = 0; k < CD; ++k) Sm[F][k] = Sm[k][F] = (k == F) ? 1.0 : 0.0;
+        }
         double *us = ustar + (size_t)CD * CD * cam;
 #pragma unroll
         for (int j = 0; j < CD; ++j)
@@ -269,7 +281,7 @@ __global__ __launch_bounds__(256) void ba_cam_kernel(SchurLists S, const double 
 #pragma unroll
         for (int k = 0; k < CD; ++k) {
             b[(size_t)CD * cam + k] = -acc[2 * NU + k] + acc[2 * NU + CD + k];
-            gabs = fmax(gabs, fabs(acc[2 * NU + k]));
+            if (!(GR && k == ba_fidx<CD>())) gabs = fmax(gabs, fabs(acc[2 * NU + k]));
         }
         cused[cam] = acc[NA - 1] > 0.0 ? 1 : 0;
     }
@@ -465,11 +477,15 @@ __global__ __launch_bounds__(256) void ba_dense_res_kernel(int64_t n, const doub
 // ---- candidate point.  Cameras: Rcw <- Exp(dtheta) Rcw (Rodrigues), tcw += dt; cameras without a used observation are copied.
 // With a focal column (G, gfree, Gn, st given): g += dg for a used camera whose focal is free, a copy elsewhere; g^2 joins |x|^2; a candidate
 // focal that is not positive sets the state word's bad_focal (cleared before the launch; every writer stores the same 1).
-template <int CD>
+// (GR, focal groups: dc is the expanded step; the focal entry is the group's -- ba_group_cand_kernel takes the step, the norms and the
+// sign test once per group --, every member reads its group's candidate gnew[group_of[i]]; |x|^2 partials at parts[xoff + workgroup])
+template <int CD, bool GR = false>
 __device__ __forceinline__ void ba_cand_cam_body(int64_t n, const double *__restrict__ Rcw, const double *__restrict__ tcw,
                                                  const double *__restrict__ G, const uint8_t *__restrict__ gfree, const double *__restrict__ dc,
                                                  const int32_t *__restrict__ cused, double *__restrict__ Rn, double *__restrict__ tn,
-                                                 double *__restrict__ Gn, BaState *__restrict__ st, double *__restrict__ parts) {
+                                                 double *__restrict__ Gn, BaState *__restrict__ st, double *__restrict__ parts,
+                                                 const int32_t *__restrict__ group_of = nullptr, const double *__restrict__ gnew = nullptr,
+                                                 int xoff = 0) {
     __shared__ double sh[4];
     double s2 = 0.0, x2 = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -479,15 +495,18 @@ __device__ __forceinline__ void ba_cand_cam_body(int64_t n, const double *__rest
             for (int k = 0; k < 9; ++k) Rn[9 * i + k] = R[k];
 #pragma unroll
             for (int k = 0; k < 3; ++k) tn[3 * i + k] = T[k];
-            if constexpr (ba_has_focal<CD>()) Gn[i] = G[i];
+            if constexpr (GR) Gn[i] = gnew[group_of[i]];
+            else if constexpr (ba_has_focal<CD>()) Gn[i] = G[i];
             continue;
         }
         const double *dt = d + ba_toff<CD>();
 #pragma unroll
         for (int k = 0; k < 3; ++k) { tn[3 * i + k] = T[k] + dt[k]; x2 += T[k] * T[k]; }
 #pragma unroll
-        for (int k = 0; k < CD; ++k) s2 += d[k] * d[k];
-        if constexpr (ba_has_focal<CD>()) {
+        for (int k = 0; k < (GR ? CD - 1 : CD); ++k) s2 += d[k] * d[k];
+        if constexpr (GR) {
+            Gn[i] = gnew[group_of[i]];
+        } else if constexpr (ba_has_focal<CD>()) {
             const double g = G[i];
             if (gfree == nullptr || gfree[i] != 0) {
                 const double gn = g + d[ba_fidx<CD>()];
@@ -521,7 +540,11 @@ __device__ __forceinline__ void ba_cand_cam_body(int64_t n, const double *__rest
     }
     s2 = block_sum256(s2, sh);
     x2 = block_sum256(x2, sh);
-    if (threadIdx.x == 0) { parts[blockIdx.x] = s2; parts[gridDim.x + blockIdx.x] = x2; }
+    if constexpr (GR) {
+        if (threadIdx.x == 0) { parts[blockIdx.x] = s2; parts[xoff + blockIdx.x] = x2; }
+    } else {
+        if (threadIdx.x == 0) { parts[blockIdx.x] = s2; parts[gridDim.x + blockIdx.x] = x2; }
+    }
 }
 template <int CD>
 __global__ __launch_bounds__(256) void ba_cand_cam_kernel(int64_t n, const double *__restrict__ Rcw, const double *__restrict__ tcw,
@@ -538,6 +561,243 @@ __global__ __launch_bounds__(256) void ba_cand_cam_focal_kernel(int64_t n, const
                                                                 BaState *__restrict__ st, double *__restrict__ parts) {
     static_assert(ba_has_focal<CD>(), "no focal column: ba_cand_cam_kernel");
     ba_cand_cam_body<CD>(n, Rcw, tcw, G, gfree, dc, cused, Rn, tn, Gn, st, parts);
+}
+// ---- focal groups (xm_ctx_bundle_adjust_focal_groups): one focal scale per group of cameras.  With E the 0/1 matrix that copies a group's
+// focal unknown into the focal column of each member, J_shared = J_7 E, so S_shared = E^T S_7 E and b_shared = E^T b_7: the kernels above
+// run as they are (CD = 7 / 4) on expanded vectors, and the kernels below expand before them and sum by group after them.  A vector of
+// the shared space lives in a CD n array: the pose slots of every camera, the group's entry in the focal slot of its representative (its
+// first member), 0 in the focal slots of the other members -- so the PCG's vector kernels run unchanged on it.  An empty group has no slot:
+// it is held.  The sums over a group's members are taken in member order by one thread (up to 64 members) or lane-strided by one workgroup
+// with the DPP tree of block_sum256 behind it (more): a fixed order, no atomics.
+struct BaGroups {
+    int32_t ng, nsmall, nsb;   // groups; those of at most 64 members (the first nsmall of list); the workgroups that take these, a thread each
+    const int32_t *off, *mem;  // the members of group c: mem[off[c] .. off[c + 1]), ascending
+    const int32_t *rep;        // its representative, -1: empty
+    const int32_t *list;       // the groups in the order the workgroups take them: the small ones, then one workgroup for each other
+    const uint8_t *free;       // 0 = held; null: all free
+};
+constexpr int kBaGroupThread = 64;   // a group of up to this many members: one thread
+// the group of this thread (small groups; -1: none) or of this workgroup; K sums over its members, valid in `writer` (the thread itself, or
+// every thread of the workgroup); sh: 4 doubles
+template <int K, class Load>
+__device__ __forceinline__ int group_reduce(const BaGroups &g, double (&acc)[K], double *sh, bool &big, Load &&load) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = 0.0;
+    big = (int)blockIdx.x >= g.nsb;
+    if (!big) {
+        const int q = blockIdx.x * 256 + threadIdx.x;
+        if (q >= g.nsmall) return -1;
+        const int c = g.list[q];
+        for (int k = g.off[c]; k < g.off[c + 1]; ++k) load(g.mem[k], acc);
+        return c;
+    }
+    const int c = g.list[g.nsmall + ((int)blockIdx.x - g.nsb)];
+    for (int k = g.off[c] + threadIdx.x; k < g.off[c + 1]; k += 256) load(g.mem[k], acc);
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = block_sum256(acc[k], sh);
+    return c;
+}
+// f(member) for every member of group c but its representative, by the threads that summed it
+template <class F>
+__device__ __forceinline__ void group_others(const BaGroups &g, int c, bool big, F &&f) {
+    if (c < 0) return;
+    const int first = g.off[c] + 1;   // the representative is the first member
+    if (!big) { for (int k = first; k < g.off[c + 1]; ++k) f(g.mem[k]); }
+    else { for (int k = first + threadIdx.x; k < g.off[c + 1]; k += 256) f(g.mem[k]); }
+}
+// per LM iteration, after the camera pass: D_c = clamp(sum U_ff,i), b_c = sum b_7,if into the representative's slot (0 in the others'),
+// F_c = sum S_7,ii[f, f] (undamped) + mu D_c and 1 / F_c into the representative's focal slot of sinv (0 in the others'), moving_c = free and
+// a member with a used observation; per-workgroup max of |sum g_if| for the gradient's maximum
+template <int CD>
+__global__ __launch_bounds__(256) void ba_group_setup_kernel(BaGroups g, const double *__restrict__ ustar, const double *__restrict__ fstat,
+                                                             const int32_t *__restrict__ cused, double mu, double *__restrict__ b,
+                                                             double *__restrict__ sinv, double *__restrict__ D, double *__restrict__ F,
+                                                             int32_t *__restrict__ moving, double *__restrict__ gpart) {
+    constexpr int FI = ba_fidx<CD>(), FF = CD * FI + FI;
+    __shared__ double sh[4];
+    __shared__ double shm[4];
+    double acc[5];
+    bool big;
+    const int c = group_reduce<5>(g, acc, sh, big, [&](int i, double (&a)[5]) {
+        a[0] += ustar[(size_t)CD * CD * i + FF]; a[1] += b[(size_t)CD * i + FI]; a[2] += fstat[2 * (size_t)i + 1]; a[3] += fstat[2 * (size_t)i];
+        a[4] += cused[i] ? 1.0 : 0.0;
+    });
+    double gabs = 0.0;
+    group_others(g, c, big, [&](int i) { b[(size_t)CD * i + FI] = 0.0; sinv[(size_t)CD * CD * i + FF] = 0.0; });
+    if (c >= 0 && (!big || threadIdx.x == 0)) {
+        const double d = clamp_diag(acc[0]);
+        double f = acc[3] + mu * d;
+        if (!(f > 0.0)) f = mu * d;
+        D[c] = d; F[c] = f;
+        moving[c] = ((g.free == nullptr || g.free[c] != 0) && acc[4] > 0.0) ? 1 : 0;
+        const int r = g.rep[c];
+        if (r >= 0) { b[(size_t)CD * r + FI] = acc[1]; sinv[(size_t)CD * CD * r + FF] = 1.0 / f; }
+        gabs = fabs(acc[2]);
+    }
+    const double m = block_max<256>(gabs, shm);
+    if (threadIdx.x == 0) gpart[blockIdx.x] = m;
+}
+// dst = E src: the pose slots copied, every member's focal slot from its group's representative (rep_of: per camera)
+template <int CD>
+__global__ __launch_bounds__(256) void ba_group_expand_kernel(int64_t n, const int32_t *__restrict__ rep_of, const double *__restrict__ src,
+                                                              double *__restrict__ dst, const BaState *__restrict__ gate) {
+    if (gate != nullptr && gate->done) return;
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n * CD; j += (int64_t)gridDim.x * 256) {
+        const int64_t i = j / CD;
+        const int k = (int)(j - i * CD);
+        dst[j] = (k == ba_fidx<CD>()) ? src[(size_t)CD * rep_of[i] + k] : src[j];
+    }
+}
+// Ap <- E^T Ap + mu D x in the focal slots: the members' entries summed into the representative's, plus mu D_c x_c (x: the vector before
+// the expansion); 0 in the other members' slots; per-workgroup partials of mu D_c x_c^2, the part of <x, A x> the camera kernel has not seen
+template <int CD>
+__global__ __launch_bounds__(256) void ba_group_sum_kernel(BaGroups g, const double *__restrict__ D, double mu, const double *__restrict__ x,
+                                                           double *__restrict__ Ap, double *__restrict__ ppap, const BaState *__restrict__ gate) {
+    constexpr int FI = ba_fidx<CD>();
+    __shared__ double sh[4];
+    if (gate != nullptr && gate->done) return;
+    double acc[1];
+    bool big;
+    const int c = group_reduce<1>(g, acc, sh, big, [&](int i, double (&a)[1]) { a[0] += Ap[(size_t)CD * i + FI]; });
+    group_others(g, c, big, [&](int i) { Ap[(size_t)CD * i + FI] = 0.0; });
+    double pap = 0.0;
+    if (c >= 0 && (!big || threadIdx.x == 0) && g.rep[c] >= 0) {
+        const size_t at = (size_t)CD * g.rep[c] + FI;
+        const double xc = x[at], dx = mu * D[c] * xc;
+        Ap[at] = acc[0] + dx;
+        pap = dx * xc;
+    }
+    pap = block_sum256(pap, sh);
+    if (threadIdx.x == 0) ppap[blockIdx.x] = pap;
+}
+// the groups' candidate: g_c + dg_c for a moving group (dc: the step before the expansion), a copy elsewhere; dg_c^2 and g_c^2 once per
+// moving group into the partials of |d|^2 and |x|^2 (at parts[workgroup] and parts[xoff + workgroup]); a candidate that is not positive
+// sets bad_focal
+template <int CD>
+__global__ __launch_bounds__(256) void ba_group_cand_kernel(BaGroups g, const double *__restrict__ G, const double *__restrict__ dc,
+                                                            const int32_t *__restrict__ moving, double *__restrict__ gnew,
+                                                            BaState *__restrict__ st, double *__restrict__ parts, int xoff) {
+    __shared__ double sh[4];
+    double s2 = 0.0, x2 = 0.0;
+    for (int c = blockIdx.x * 256 + threadIdx.x; c < g.ng; c += gridDim.x * 256) {
+        const int r = g.rep[c];
+        if (r < 0) { gnew[c] = 1.0; continue; }   // empty: nobody reads it
+        const double g0 = G[r];
+        if (moving[c]) {
+            const double d = dc[(size_t)CD * r + ba_fidx<CD>()], gn = g0 + d;
+            gnew[c] = gn;
+            s2 += d * d; x2 += g0 * g0;
+            if (!(gn > 0.0)) st->bad_focal = 1;
+        } else {
+            gnew[c] = g0;
+        }
+    }
+    s2 = block_sum256(s2, sh);
+    x2 = block_sum256(x2, sh);
+    if (threadIdx.x == 0) { parts[blockIdx.x] = s2; parts[xoff + blockIdx.x] = x2; }
+}
+template <int CD>
+__global__ __launch_bounds__(256) void ba_cand_cam_groups_kernel(int64_t n, const double *__restrict__ Rcw, const double *__restrict__ tcw,
+                                                                 const double *__restrict__ dc, const int32_t *__restrict__ cused,
+                                                                 const int32_t *__restrict__ group_of, const double *__restrict__ gnew,
+                                                                 double *__restrict__ Rn, double *__restrict__ tn, double *__restrict__ Gn,
+                                                                 double *__restrict__ parts, int xoff) {
+    ba_cand_cam_body<CD, true>(n, Rcw, tcw, nullptr, nullptr, dc, cused, Rn, tn, Gn, nullptr, parts, group_of, gnew, xoff);
+}
+// ---- the exact focal block of the preconditioner (at most XM_BA_FOCAL_GROUPS_EXACT groups): F = S_shared[focal, focal], column d from the
+// product with the indicator of group d.  v <- e_slot
+__global__ __launch_bounds__(256) void ba_group_unit_kernel(int64_t count, int64_t slot, double *__restrict__ v) {
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < count; j += (int64_t)gridDim.x * 256) v[j] = j == slot ? 1.0 : 0.0;
+}
+// column d of F (column-major G x G) from A p = S_shared e_d; an empty group (it has no slot): mu D_c on its diagonal, as the held groups have
+template <int CD>
+__global__ __launch_bounds__(256) void ba_group_col_kernel(BaGroups g, int d, const double *__restrict__ Ap, const double *__restrict__ D, double mu,
+                                                           double *__restrict__ Fm) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= g.ng) return;
+    const int r = g.rep[c];
+    Fm[c + (size_t)g.ng * d] = (r >= 0 && g.rep[d] >= 0) ? Ap[(size_t)CD * r + ba_fidx<CD>()] : (c == d ? mu * D[c] : 0.0);
+}
+// F was inverted: the focal slots of the block-Jacobi inverse give way to it (z_f = 0 from the vector kernels)
+template <int CD>
+__global__ __launch_bounds__(256) void ba_group_exact_on_kernel(BaGroups g, double *__restrict__ sinv) {
+    constexpr int FI = ba_fidx<CD>();
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < g.ng && g.rep[c] >= 0) sinv[(size_t)CD * CD * g.rep[c] + CD * FI + FI] = 0.0;
+}
+// behind the PCG's start or update (one workgroup): z_focal = F^-1 r_focal (Finv: the full symmetric inverse), p = z at the start, and
+// <r_focal, z_focal> into the partial behind the vector kernels' (slot a.grid - 1).  exact = 0 (the factorisation failed this iteration and
+// the diagonal stands): that partial is 0
+template <int CD>
+__global__ __launch_bounds__(256) void ba_group_precond_kernel(BaGroups g, const double *__restrict__ Finv, BaPcg a, int it, int init, int exact) {
+    constexpr int FI = ba_fidx<CD>();
+    __shared__ double sh[4];
+    if (!init && a.st->done) return;
+    const int c = threadIdx.x;
+    double rz = 0.0;
+    if (exact && c < g.ng && g.rep[c] >= 0) {
+        double z = 0.0;
+        for (int d = 0; d < g.ng; ++d)
+            if (g.rep[d] >= 0) z += Finv[(size_t)c * g.ng + d] * a.r[(size_t)CD * g.rep[d] + FI];
+        const size_t at = (size_t)CD * g.rep[c] + FI;
+        a.z[at] = z;
+        if (init) a.p[at] = z;
+        rz = a.r[at] * z;
+    }
+    rz = block_sum256(rz, sh);
+    if (threadIdx.x == 0) a.prz[init ? 0 : (it & 1) ^ 1][a.grid - 1] = rz;
+}
+
+// ---- XM_BA_DENSE_SCHUR with focal groups: the CD n matrix of ba_schur_dense_kernel (the members' focal diagonal undamped) contracted by
+// group in place, S_shared = E^T S_7 E + mu D in the layout of the vectors: the group's row and column in its representative's focal slot,
+// the other members' focal slots a unit row and column.  Only the lower triangle is read and written (what the factorisation reads).
+__device__ __forceinline__ double &dense_low(double *Sd, int64_t ld, int64_t a, int64_t b) { return a >= b ? Sd[a + b * ld] : Sd[b + a * ld]; }
+// T[c nd + k] = sum_{i in c} S_7[f_i, k] over the members in order, every column k
+template <int CD>
+__global__ __launch_bounds__(256) void ba_group_dense_rows_kernel(BaGroups g, double *__restrict__ Sd, int64_t ld, int64_t nd, double *__restrict__ T) {
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < g.ng * nd; q += (int64_t)gridDim.x * 256) {
+        const int c = (int)(q / nd);
+        const int64_t k = q - c * nd;
+        double s = 0.0;
+        for (int m = g.off[c]; m < g.off[c + 1]; ++m) s += dense_low(Sd, ld, (int64_t)CD * g.mem[m] + ba_fidx<CD>(), k);
+        T[q] = s;
+    }
+}
+// U[c + G d] = sum_{j in d} T[c, f_j]
+template <int CD>
+__global__ __launch_bounds__(256) void ba_group_dense_cols_kernel(BaGroups g, int64_t nd, const double *__restrict__ T, double *__restrict__ U) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= g.ng * g.ng) return;
+    const int c = q % g.ng, d = q / g.ng;
+    double s = 0.0;
+    for (int m = g.off[d]; m < g.off[d + 1]; ++m) s += T[(size_t)c * nd + (size_t)CD * g.mem[m] + ba_fidx<CD>()];
+    U[q] = s;
+}
+// every focal row and column becomes a unit one ...
+template <int CD>
+__global__ __launch_bounds__(256) void ba_group_dense_clear_kernel(int64_t n, double *__restrict__ Sd, int64_t ld, int64_t nd) {
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n * nd; q += (int64_t)gridDim.x * 256) {
+        const int64_t i = q / nd, k = q - i * nd, f = CD * i + ba_fidx<CD>();
+        dense_low(Sd, ld, f, k) = k == f ? 1.0 : 0.0;
+    }
+}
+// ... and the representatives' take the contracted entries: T against the pose columns, U (its lower triangle) + mu D among the groups
+template <int CD>
+__global__ __launch_bounds__(256) void ba_group_dense_write_kernel(BaGroups g, double *__restrict__ Sd, int64_t ld, int64_t nd, const double *__restrict__ T,
+                                                                   const double *__restrict__ U, const double *__restrict__ D, double mu) {
+    constexpr int FI = ba_fidx<CD>();
+    const int64_t nt = g.ng * nd;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nt + (int64_t)g.ng * g.ng; q += (int64_t)gridDim.x * 256) {
+        if (q < nt) {
+            const int c = (int)(q / nd);
+            const int64_t k = q - c * nd;
+            if (g.rep[c] >= 0 && k % CD != FI) dense_low(Sd, ld, (int64_t)CD * g.rep[c] + FI, k) = T[q];
+        } else {
+            const int c = (int)((q - nt) % g.ng), d = (int)((q - nt) / g.ng);
+            if (d <= c && g.rep[c] >= 0 && g.rep[d] >= 0)
+                dense_low(Sd, ld, (int64_t)CD * g.rep[c] + FI, (int64_t)CD * g.rep[d] + FI) = U[c + (size_t)g.ng * d] + (c == d ? mu * D[c] : 0.0);
+        }
+    }
 }
 // (the landmarks' candidate: ba_cand_vec_kernel of xm_lm_shared.h)
 // cost 1/2 sum rho(|r|^2) at the candidate (the eval kernel's expression) and the linear model's terms sum r.(J d) + |J d|^2 / 2 (J, r: the
@@ -1130,6 +1390,22 @@ struct BaWork {
     DevBuf<double> R[3], T[3], P[3];
     DevBuf<double> G[3];        // with a focal column: the focal scales of each set
     DevBuf<uint8_t> gfree;      // the mask of the free focals (not allocated: all free)
+    // ---- focal groups (cfg.ngroups > 0): G[] and gfree above are the groups' values copied to every member, so that the eval, candidate and
+    // cost kernels read them as they read per-camera ones; the member lists (host counting sort, once per call) and the groups' arrays
+    const bool grouped;
+    const int64_t ng;
+    std::vector<int32_t> h_rep;   // group -> representative, -1: empty
+    BaGroups grp{};
+    DevBuf<int32_t> grp_off, grp_mem, grp_rep, grp_list, grp_of, grp_repof, grp_moving;
+    DevBuf<uint8_t> grp_free;
+    DevBuf<double> grp_D, grp_F, grp_new, fstat, pe;   // pe: an expanded vector (the product's E p, the candidate's E dc)
+    int ggrp = 0, ggf = 0;        // workgroups of the group sums; of the flat kernel over the groups
+    // at most XM_BA_FOCAL_GROUPS_EXACT groups: the preconditioner's focal block is the exact F = S_shared[focal, focal] (G products per LM
+    // iteration), inverted by spd_inverse_device; a failed factorisation leaves that iteration with diag F and is counted in
+    // coarse_fallbacks
+    bool f_small = false, f_exact = false;
+    DevBuf<double> grp_Fm, grp_Fx, grp_Fcopy, grp_T, grp_U;   // F -> F^-1, the inverse's scratch, F as assembled; the dense contraction's sums
+    DevBuf<int32_t> grp_flag;
     // ---- workspace (zero: the padding of the packed landmark lists stays 0 in every plane)
     DevBuf<double> Jc, Jl, vinv, gl, ustar, sinv, b, x, r, z, pv, Ap, y, dP, parts;
     DevBuf<int32_t> lused, cused, state_buf;
@@ -1157,7 +1433,8 @@ struct BaWork {
     DevBuf<double> Sd, ysub;
 
     BaWork(const SchurOp &SO_, const BaSettings &cfg_, const double *rot, const double *t, const double *p, hipStream_t st_, bool dense)
-        : SO(SO_), cfg(cfg_), st(st_), S(SO_.lists()), n(S.n), m(S.m), nobs(S.nobs), nd((int64_t)CD * S.n) {
+        : SO(SO_), cfg(cfg_), st(st_), S(SO_.lists()), n(S.n), m(S.m), nobs(S.nobs), grouped(ba_has_focal<CD>() && cfg_.ngroups > 0),
+          ng(grouped ? cfg_.ngroups : 0), nd((int64_t)CD * S.n) {
         to_device_layout(SO, rot, t, p, hR, hT, hP);
         const bool nonmono = cfg.nonmonotonic;
         for (int k = 0; k < (nonmono ? 3 : 2); ++k) { R[k].alloc((size_t)9 * n, false); T[k].alloc((size_t)3 * n, false); P[k].alloc((size_t)3 * m, false); }
@@ -1166,10 +1443,14 @@ struct BaWork {
         XM_HIP_CHECK(hipMemcpyAsync(P[0].p, hP.data(), hP.size() * sizeof(double), hipMemcpyHostToDevice, st));
         if constexpr (ba_has_focal<CD>()) {
             for (int k = 0; k < (nonmono ? 3 : 2); ++k) G[k].alloc((size_t)n, false);
-            XM_HIP_CHECK(hipMemcpyAsync(G[0].p, cfg.focal, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-            if (cfg.focal_free) {
-                gfree.alloc((size_t)n, false);
-                XM_HIP_CHECK(hipMemcpyAsync(gfree.p, cfg.focal_free, (size_t)n, hipMemcpyHostToDevice, st));
+            if (grouped) {
+                plan_groups();
+            } else {
+                XM_HIP_CHECK(hipMemcpyAsync(G[0].p, cfg.focal, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+                if (cfg.focal_free) {
+                    gfree.alloc((size_t)n, false);
+                    XM_HIP_CHECK(hipMemcpyAsync(gfree.p, cfg.focal_free, (size_t)n, hipMemcpyHostToDevice, st));
+                }
             }
         }
         Jc.alloc((size_t)NP * nobs); Jl.alloc((size_t)NP * S.lm_total);
@@ -1181,12 +1462,15 @@ struct BaWork {
         ge = flat_grid(nobs); gfc = flat_grid(n); gfl = flat_grid(m); gcam = qw_grid((int)n);
         glm = (int)(S.nheavy + (m - S.nheavy + kBaHeavyThreads - 1) / kBaHeavyThreads);
         // partials: eval (2 ge) | gmax (glm + gcam) | PCG (4 gfc + gcam) | candidate step / |x| (cameras then landmarks, 2 x (gfc + gfl)) | cost (2 ge)
-        o_eval = 0; o_gmax = o_eval + 2 * (size_t)ge; o_pcg = o_gmax + glm + gcam; o_cand = o_pcg + 4 * (size_t)gfc + gcam;
-        o_cost = o_cand + 2 * ((size_t)gfc + gfl);
+        // (focal groups: ggrp more behind the cameras' gmax and <p, Ap> partials, ggf more behind each of the cameras' candidate sums)
+        // (and one more partial behind each of the PCG's four sums: <r, z> of the exact focal block; the others stay 0)
+        const int gx = grouped ? 1 : 0;
+        o_eval = 0; o_gmax = o_eval + 2 * (size_t)ge; o_pcg = o_gmax + glm + gcam + ggrp; o_cand = o_pcg + 4 * ((size_t)gfc + gx) + gcam + ggrp;
+        o_cost = o_cand + 2 * ((size_t)gfc + ggf + gfl);
         const size_t n_parts = o_cost + 2 * (size_t)ge;
         parts.alloc(n_parts);
         pp = parts.p;
-        a.n = n; a.grid = gfc; a.cgrid = gcam; a.tol2 = cfg.eta * cfg.eta;
+        a.n = n; a.grid = gfc + gx; a.cgrid = gcam + ggrp; a.tol2 = cfg.eta * cfg.eta;
         a.b = b.p; a.sinv = sinv.p; a.ustar = ustar.p; a.x = x.p; a.r = r.p; a.z = z.p; a.p = pv.p; a.Ap = Ap.p;
         a.lay_partials(pp + o_pcg);
         a.st = dst;
@@ -1203,6 +1487,59 @@ struct BaWork {
             }
             Sd.count = Sd.capacity = elems;
             ysub.alloc((size_t)nd);
+            if (grouped) { grp_T.alloc((size_t)ng * nd, false); grp_U.alloc((size_t)ng * ng, false); }
+        }
+    }
+    // the member lists by a counting sort (members ascending, the first one the representative), the groups' values and mask copied to the
+    // members, the order in which the workgroups of the group sums take the groups
+    void plan_groups() {
+        std::vector<int32_t> off((size_t)ng + 1, 0), mem((size_t)n), repof((size_t)n), list;
+        for (int64_t i = 0; i < n; ++i) off[(size_t)cfg.group_of[i] + 1]++;
+        for (int64_t c = 0; c < ng; ++c) off[(size_t)c + 1] += off[(size_t)c];
+        {
+            std::vector<int32_t> at(off.begin(), off.end() - 1);
+            for (int64_t i = 0; i < n; ++i) mem[(size_t)at[(size_t)cfg.group_of[i]]++] = (int32_t)i;
+        }
+        h_rep.assign((size_t)ng, -1);
+        for (int64_t c = 0; c < ng; ++c)
+            if (off[(size_t)c + 1] > off[(size_t)c]) h_rep[(size_t)c] = mem[(size_t)off[(size_t)c]];
+        int64_t nsmall = 0;
+        for (int pass = 0; pass < 2; ++pass) {
+            for (int64_t c = 0; c < ng; ++c)
+                if ((off[(size_t)c + 1] - off[(size_t)c] <= kBaGroupThread) == (pass == 0)) list.push_back((int32_t)c);
+            if (pass == 0) nsmall = (int64_t)list.size();
+        }
+        std::vector<double> hG((size_t)n);
+        std::vector<uint8_t> hfree((size_t)n, 1);
+        for (int64_t i = 0; i < n; ++i) {
+            const int32_t c = cfg.group_of[i];
+            repof[(size_t)i] = h_rep[(size_t)c];
+            hG[(size_t)i] = cfg.focal[c];
+            if (cfg.focal_free) hfree[(size_t)i] = cfg.focal_free[c];
+        }
+        auto up = [&](auto &buf, const auto &v) {
+            buf.alloc(v.size(), false);
+            XM_HIP_CHECK(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, st));
+        };
+        up(grp_off, off); up(grp_mem, mem); up(grp_rep, h_rep); up(grp_list, list); up(grp_repof, repof); up(G[0], hG);
+        grp_of.alloc((size_t)n, false);
+        XM_HIP_CHECK(hipMemcpyAsync(grp_of.p, cfg.group_of, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (cfg.focal_free) {
+            up(gfree, hfree);
+            grp_free.alloc((size_t)ng, false);
+            XM_HIP_CHECK(hipMemcpyAsync(grp_free.p, cfg.focal_free, (size_t)ng, hipMemcpyHostToDevice, st));
+        }
+        wait_stream(st, cfg.watchdog_s, kStage, "the focal groups");   // the host vectors above end with this function
+        grp_D.alloc((size_t)ng); grp_F.alloc((size_t)ng); grp_new.alloc((size_t)ng); grp_moving.alloc((size_t)ng);
+        fstat.alloc((size_t)2 * n); pe.alloc((size_t)CD * n);
+        const int nsb = (int)((nsmall + 255) / 256);
+        grp.ng = (int32_t)ng; grp.nsmall = (int32_t)nsmall; grp.nsb = nsb;
+        grp.off = grp_off.p; grp.mem = grp_mem.p; grp.rep = grp_rep.p; grp.list = grp_list.p; grp.free = grp_free.p;
+        ggrp = nsb + (int)(ng - nsmall);
+        ggf = flat_grid(ng);
+        f_small = ng <= XM_BA_FOCAL_GROUPS_EXACT;
+        if (ng <= XM_BA_FOCAL_GROUPS_EXACT) {
+            grp_Fm.alloc((size_t)ng * ng); grp_Fx.alloc((size_t)ng * ng); grp_Fcopy.alloc((size_t)ng * ng); grp_flag.alloc(1);
         }
     }
     void plan_aggregates() {
@@ -1271,11 +1608,72 @@ struct BaWork {
     }
     void passes(double mu) {
         hipLaunchKernelGGL((ba_lm_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, mu, vinv.p, gl.p, lused.p, pp + o_gmax);
-        hipLaunchKernelGGL((ba_cam_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)vinv.p, (const double *)gl.p, mu,
-                           ustar.p, sinv.p, b.p, cused.p, pp + o_gmax + glm);
+        if constexpr (ba_has_focal<CD>()) {
+            if (grouped) {   // the camera pass in its grouped form, then the groups' pass: their gradient entries join the maximum
+                hipLaunchKernelGGL((ba_cam_kernel<CD, true>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)vinv.p,
+                                   (const double *)gl.p, mu, ustar.p, sinv.p, b.p, cused.p, pp + o_gmax + glm, fstat.p);
+                hipLaunchKernelGGL((ba_group_setup_kernel<CD>), dim3(ggrp), b256, 0, st, grp, (const double *)ustar.p, (const double *)fstat.p,
+                                   (const int32_t *)cused.p, mu, b.p, sinv.p, grp_D.p, grp_F.p, grp_moving.p, pp + o_gmax + glm + gcam);
+                cur_mu = mu;
+            }
+        }
+        if (!grouped) {
+            hipLaunchKernelGGL((ba_cam_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)vinv.p, (const double *)gl.p, mu,
+                               ustar.p, sinv.p, b.p, cused.p, pp + o_gmax + glm);
+        }
         BaReduce rd{};
-        rd.max_p = pp + o_gmax; rd.max_n = glm + gcam; rd.max_out = &dst->gmax;
+        rd.max_p = pp + o_gmax; rd.max_n = glm + gcam + ggrp; rd.max_out = &dst->gmax;   // (ggrp = 0 without groups)
         reduce(rd);
+        f_exact = false;
+        if (grouped && f_small && !dense_mode) exact_focal_block();
+    }
+    double cur_mu = 0.0;   // focal groups: the damping of the last passes (mu D_c x_c joins in the group sum)
+    bool dense_mode = false;   // the dense solver runs no PCG: no preconditioner to set up
+    // F by G products with indicator vectors (through the PCG's direction and product vectors, which the PCG's start fills anew), its inverse
+    void exact_focal_block() {
+        if constexpr (ba_has_focal<CD>()) {
+            XM_HIP_CHECK(hipMemsetAsync(&dst->done, 0, sizeof(int32_t), st));   // the last solve's flag would skip the camera side of the product
+            const int G = (int)ng;
+            for (int d = 0; d < G; ++d) {
+                if (h_rep[(size_t)d] >= 0) {
+                    hipLaunchKernelGGL(ba_group_unit_kernel, dim3(flat_grid(nd)), b256, 0, st, nd, (int64_t)CD * h_rep[(size_t)d] + ba_fidx<CD>(), pv.p);
+                    sx(a, nullptr);
+                }
+                hipLaunchKernelGGL((ba_group_col_kernel<CD>), dim3(ggf), b256, 0, st, grp, d, (const double *)Ap.p, (const double *)grp_D.p, cur_mu, grp_Fm.p);
+            }
+            XM_HIP_CHECK(hipMemcpyAsync(grp_Fcopy.p, grp_Fm.p, grp_Fm.count * sizeof(double), hipMemcpyDeviceToDevice, st));
+            XM_HIP_CHECK(hipMemsetAsync(grp_flag.p, 0, sizeof(int32_t), st));
+            check_launch("the exact focal block");
+            bool ok = spd_inverse_device(G, grp_Fm.p, grp_Fx.p, st);
+            if (ok) {
+                spd_inverse_layout(G, grp_Fx.p, grp_Fm.p, G, st);
+                hipLaunchKernelGGL(ba_tl_finite_kernel, dim3(1), b256, 0, st, (int64_t)G * G, (const double *)grp_Fm.p, grp_flag.p);
+                int32_t bad = 0;
+                XM_HIP_CHECK(hipMemcpyAsync(&bad, grp_flag.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+                wait_stream(st, cfg.watchdog_s, kStage, "the focal block's inverse");
+                ok = bad == 0;
+            }
+            if (ok) {
+                hipLaunchKernelGGL((ba_group_exact_on_kernel<CD>), dim3(ggf), b256, 0, st, grp, sinv.p);
+                f_exact = true;
+            } else {
+                coarse_fallbacks++;
+            }
+        }
+    }
+    // behind the PCG's start (init) or the update of iteration it: the exact focal block's part of z
+    void focal_precond(int it, int init) {
+        if constexpr (ba_has_focal<CD>())
+            hipLaunchKernelGGL((ba_group_precond_kernel<CD>), dim3(1), b256, 0, st, grp, (const double *)grp_Fm.p, a, it, init, f_exact ? 1 : 0);
+    }
+    void pcg_update(int it) {
+        hipLaunchKernelGGL((ba_pcg_upd_kernel<CD>), dim3(gfc), b256, 0, st, a, it);
+        focal_precond(it, 0);
+    }
+    // pe = E src
+    void expand(const double *src, const BaState *gate) {
+        if constexpr (ba_has_focal<CD>())
+            hipLaunchKernelGGL((ba_group_expand_kernel<CD>), dim3(flat_grid(n * CD)), b256, 0, st, n, (const int32_t *)grp_repof.p, src, pe.p, gate);
     }
     // every LM iteration (S changes with mu): the block inverses; two-level: A_c = P^T S P and its inverse.  A_c that cannot be inverted (a
     // pivot that is not positive, an entry that is not finite): this iteration's PCG runs with the blocks alone
@@ -1315,9 +1713,17 @@ struct BaWork {
     }
     // ar.Ap = S ar.p through the two lists (the PCG's product; gate: the state word whose done flag skips the landmark side, or null)
     void sx(const BaPcg &ar, const BaState *gate) {
+        BaPcg ae = ar;   // focal groups: S_shared x = E^T S_7 (E x) + mu D x -- the two list passes read E x
+        if (grouped) { expand(ar.p, gate); ae.p = pe.p; }
         hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)nullptr, 1.0,
-                           (const int32_t *)lused.p, (const double *)ar.p, gate, y.p);
-        hipLaunchKernelGGL((ba_camx_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)y.p, ar);
+                           (const int32_t *)lused.p, (const double *)ae.p, gate, y.p);
+        hipLaunchKernelGGL((ba_camx_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)y.p, ae);
+        if constexpr (ba_has_focal<CD>()) {
+            if (grouped) {
+                hipLaunchKernelGGL((ba_group_sum_kernel<CD>), dim3(ggrp), b256, 0, st, grp, (const double *)grp_D.p, cur_mu, (const double *)ar.p,
+                                   ar.Ap, ar.ppap + gcam, gate);
+            }
+        }
     }
     // the dense lower block triangle of S into Sd (zeroed here), the failure flag cleared
     void dense_assemble() {
@@ -1325,6 +1731,16 @@ struct BaWork {
         XM_HIP_CHECK(hipMemsetAsync(&dst->fail, 0, sizeof(int32_t), st));
         hipLaunchKernelGGL((ba_schur_dense_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)Jl.p, (const double *)vinv.p,
                            (const double *)ustar.p, Sd.p, nd);
+        if constexpr (ba_has_focal<CD>()) {
+            if (grouped) {   // S_shared = E^T S_7 E + mu D in place
+                hipLaunchKernelGGL((ba_group_dense_rows_kernel<CD>), dim3(flat_grid(ng * nd)), b256, 0, st, grp, Sd.p, nd, nd, grp_T.p);
+                hipLaunchKernelGGL((ba_group_dense_cols_kernel<CD>), dim3((unsigned)((ng * ng + 255) / 256)), b256, 0, st, grp, nd, (const double *)grp_T.p,
+                                   grp_U.p);
+                hipLaunchKernelGGL((ba_group_dense_clear_kernel<CD>), dim3(flat_grid(n * nd)), b256, 0, st, n, Sd.p, nd, nd);
+                hipLaunchKernelGGL((ba_group_dense_write_kernel<CD>), dim3(flat_grid(ng * nd + ng * ng)), b256, 0, st, grp, Sd.p, nd, nd,
+                                   (const double *)grp_T.p, (const double *)grp_U.p, (const double *)grp_D.p, cur_mu);
+            }
+        }
     }
     // S dc = b exactly: assembly, Cholesky, substitutions (dc -> x); then |b - S dc|^2 and |b|^2 with S applied through the matrix-free
     // kernels of the PCG (the state word's done flag is never set on this path).  Nothing is read by the host here.
@@ -1354,21 +1770,34 @@ struct BaWork {
     void pcg_start() {
         if (tlmode) precond(0, 1);
         else hipLaunchKernelGGL((ba_pcg_init_kernel<CD>), dim3(gfc), b256, 0, st, a);
+        if (grouped && f_small) focal_precond(0, 1);
     }
     // back-substitution dP = -V*^-1 (g + W^T dc), candidate (parameter set nx), its cost and the model decrease; the scalars to the state word
     void candidate(int nx, const double *dc) {
+        const double *dshared = dc;   // focal groups: the step before the expansion; every kernel below but the groups' reads E dc
+        if (grouped) { expand(dc, nullptr); dc = pe.p; }
+        const int gfg = gfc + ggf;
         hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)gl.p, -1.0,
                            (const int32_t *)lused.p, dc, (const BaState *)nullptr, dP.p);
         if constexpr (ba_has_focal<CD>()) {
             XM_HIP_CHECK(hipMemsetAsync(&dst->bad_focal, 0, sizeof(int32_t), st));
-            hipLaunchKernelGGL((ba_cand_cam_focal_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p,
-                               (const double *)G[cur].p, (const uint8_t *)gfree.p, dc, (const int32_t *)cused.p, R[nx].p, T[nx].p, G[nx].p, dst,
-                               pp + o_cand);
-        } else
+            if (grouped) {
+                hipLaunchKernelGGL((ba_group_cand_kernel<CD>), dim3(ggf), b256, 0, st, grp, (const double *)G[cur].p, dshared,
+                                   (const int32_t *)grp_moving.p, grp_new.p, dst, pp + o_cand + gfc, gfg);
+                hipLaunchKernelGGL((ba_cand_cam_groups_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p, dc,
+                                   (const int32_t *)cused.p, (const int32_t *)grp_of.p, (const double *)grp_new.p, R[nx].p, T[nx].p, G[nx].p,
+                                   pp + o_cand, gfg);
+            } else {
+                hipLaunchKernelGGL((ba_cand_cam_focal_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p,
+                                   (const double *)G[cur].p, (const uint8_t *)gfree.p, dc, (const int32_t *)cused.p, R[nx].p, T[nx].p, G[nx].p, dst,
+                                   pp + o_cand);
+            }
+        } else {
             hipLaunchKernelGGL((ba_cand_cam_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p, dc,
                                (const int32_t *)cused.p, R[nx].p, T[nx].p, pp + o_cand);
+        }
         hipLaunchKernelGGL(ba_cand_vec_kernel<3>, dim3(gfl), b256, 0, st, m, (const double *)P[cur].p, (const double *)dP.p, (const int32_t *)lused.p,
-                           P[nx].p, pp + o_cand + 2 * (size_t)gfc);
+                           P[nx].p, pp + o_cand + 2 * (size_t)gfg);
         with_loss(cfg.loss, [&](auto L) {
             const double *Rn = R[nx].p, *Tn = T[nx].p, *Pn = P[nx].p, *J = Jc.p, *dl = dP.p;
             if constexpr (ba_has_focal<CD>()) {
@@ -1381,7 +1810,7 @@ struct BaWork {
             } else if constexpr (L.value == XM_BA_LOSS_TRIVIAL) hipLaunchKernelGGL((ba_cost_kernel<CD>), dim3(ge), b256, 0, st, S, Rn, Tn, Pn, J, dc, dl, pp + o_cost);
             else hipLaunchKernelGGL((ba_cost_kernel<CD, L.value, double>), dim3(ge), b256, 0, st, S, Rn, Tn, Pn, J, dc, dl, pp + o_cost, cfg.loss_scale);
         });
-        reduce(candidate_sums(pp + o_cost, ge, pp + o_cand, gfc, gfl, dst));
+        reduce(candidate_sums(pp + o_cost, ge, pp + o_cand, gfg, gfl, dst));
     }
 };
 
@@ -1400,6 +1829,8 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
     hooks.read = [&] { return W.read_state("the reduced camera PCG"); };
     hooks.start = [&] { W.pcg_start(); };
     if (W.tlmode) hooks.update = [&](int it) { W.precond(it, 0); };
+    if (W.grouped && W.f_small) hooks.update = [&](int it) { W.pcg_update(it); };
+    W.dense_mode = cfg.dense_schur;
 
     // the LM loop (xm_lm_loop.h) over this solver's launches and reads
     const LmRules rules{cfg.max_iters, cfg.function_tol, cfg.gradient_tol, cfg.parameter_tol, cfg.nonmonotonic, cfg.max_nonmonotonic};
@@ -1465,8 +1896,16 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
         for (int a = 0; a < 3; ++a) p[(size_t)3 * l + a] = hP[(size_t)3 * sl + a];
     }
     if constexpr (ba_has_focal<CD>()) {   // held focals and those of cameras without a used observation were copied from set to set
-        XM_HIP_CHECK(hipMemcpyAsync(cfg.focal, W.G[cur].p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-        wait_stream(st, cfg.watchdog_s, kStage, "the refined focal scales");
+        if (W.grouped) {   // a group's value: its representative's (every member holds it); an empty group keeps the caller's
+            std::vector<double> hG((size_t)n);
+            XM_HIP_CHECK(hipMemcpyAsync(hG.data(), W.G[cur].p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+            wait_stream(st, cfg.watchdog_s, kStage, "the refined focal scales");
+            for (int64_t c = 0; c < W.ng; ++c)
+                if (W.h_rep[(size_t)c] >= 0) cfg.focal[c] = hG[(size_t)W.h_rep[(size_t)c]];
+        } else {
+            XM_HIP_CHECK(hipMemcpyAsync(cfg.focal, W.G[cur].p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+            wait_stream(st, cfg.watchdog_s, kStage, "the refined focal scales");
+        }
     }
     out.status = res.status; out.iters = res.iters; out.accepted = res.accepted; out.pcg_iters = res.pcg_total;
     out.final_cost = res.final_cost; out.gradient_max = res.gmax; out.trace_len = lm_copy_trace(res, cfg.trace, cfg.trace_cap);
@@ -1494,11 +1933,42 @@ void probe(const SchurOp &SO, const BaSettings &cfg, const double *rot, const do
         for (int64_t l = 0; l < m; ++l)
             for (int k = 0; k < w; ++k) outp[(size_t)w * l + k] = tmp[(size_t)w * slot_of[(size_t)l] + k];
     };
+    // focal groups: the caller's vectors have CP n + G entries (CP = CD - 1 columns per camera, then the groups' focal entries); the device's
+    // have CD n (the group's entry in its representative's focal slot).  An empty group has no slot: 0 comes back for it
+    constexpr int CP = CD - 1;
+    const bool grouped = W.grouped;
+    const int64_t ns = grouped ? CP * n + W.ng : nd;
+    std::vector<double> hin, hout;
+    auto to_dev = [&](const double *v, double *dev) {   // a caller's vector -> the device array
+        if (!grouped) { XM_HIP_CHECK(hipMemcpyAsync(dev, v, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st)); return; }
+        hin.assign((size_t)nd, 0.0);
+        for (int64_t i = 0; i < n; ++i)
+            for (int k = 0; k < CP; ++k) hin[(size_t)CD * i + k] = v[(size_t)CP * i + k];
+        for (int64_t c = 0; c < W.ng; ++c)
+            if (W.h_rep[(size_t)c] >= 0) hin[(size_t)CD * W.h_rep[(size_t)c] + CP] = v[(size_t)CP * n + c];
+        XM_HIP_CHECK(hipMemcpyAsync(dev, hin.data(), (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
+        wait_stream(st, cfg.watchdog_s, kStage, "a probe vector");
+    };
+    auto from_dev = [&](double *v, const double *dev, const char *what) {   // and back (waits)
+        if (!grouped) { d2h(v, dev, (size_t)nd * sizeof(double)); sync(what); return; }
+        hout.resize((size_t)nd);
+        d2h(hout.data(), dev, (size_t)nd * sizeof(double));
+        sync(what);
+        for (int64_t i = 0; i < n; ++i)
+            for (int k = 0; k < CP; ++k) v[(size_t)CP * i + k] = hout[(size_t)CD * i + k];
+        for (int64_t c = 0; c < W.ng; ++c) v[(size_t)CP * n + c] = W.h_rep[(size_t)c] >= 0 ? hout[(size_t)CD * W.h_rep[(size_t)c] + CP] : 0.0;
+    };
     W.eval();
     W.passes(q.mu);
     const BaState s0 = W.read_state("the probe's passes");
     q.cost = s0.cost; q.n_used = (int64_t)s0.used; q.gmax = s0.gmax;
-    if (q.b) d2h(q.b, W.b.p, (size_t)nd * sizeof(double));
+    if (q.b) from_dev(q.b, W.b.p, "the right-hand side");
+    if (grouped && q.group_D) d2h(q.group_D, W.grp_D.p, (size_t)W.ng * sizeof(double));
+    if (grouped && q.group_F) {   // the exact block (G x G, column-major, as assembled) where the rule builds it, else the diagonal (G)
+        if (W.f_small) d2h(q.group_F, W.grp_Fcopy.p, (size_t)W.ng * W.ng * sizeof(double));
+        else d2h(q.group_F, W.grp_F.p, (size_t)W.ng * sizeof(double));
+        q.coarse_ok = W.f_exact ? 1 : 0;
+    }
     if (q.ustar) d2h(q.ustar, W.ustar.p, (size_t)CD * nd * sizeof(double));
     if (q.sinv) d2h(q.sinv, W.sinv.p, (size_t)CD * nd * sizeof(double));
     if (q.cused) d2h(q.cused, W.cused.p, (size_t)n * sizeof(int32_t));
@@ -1514,12 +1984,29 @@ void probe(const SchurOp &SO, const BaSettings &cfg, const double *rot, const do
     // S X: column j into the PCG's direction vector, the product pair, A p back (the state word's done flag is 0: nothing has set it)
     if (q.SX)
         for (int64_t j = 0; j < q.k; ++j) {
-            XM_HIP_CHECK(hipMemcpyAsync(W.pv.p, q.X + (size_t)nd * j, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
+            to_dev(q.X + (size_t)ns * j, W.pv.p);
             W.sx(W.pcg_args(), W.dst);
-            d2h(q.SX + (size_t)nd * j, W.Ap.p, (size_t)nd * sizeof(double));
-            sync("the product S x");
+            from_dev(q.SX + (size_t)ns * j, W.Ap.p, "the product S x");
         }
-    if (q.Sdense) {
+    if (q.Sdense && grouped) {   // the lower triangle of the (CP n + G)-row matrix, the rest 0
+        W.dense_assemble();
+        std::vector<double> hS((size_t)nd * nd);
+        d2h(hS.data(), W.Sd.p, hS.size() * sizeof(double));
+        sync("the dense Schur matrix");
+        std::vector<int64_t> to((size_t)nd, -1);   // device index -> the caller's; -1: a pinned focal slot
+        for (int64_t i = 0; i < n; ++i)
+            for (int k = 0; k < CP; ++k) to[(size_t)CD * i + k] = CP * i + k;
+        for (int64_t c = 0; c < W.ng; ++c)
+            if (W.h_rep[(size_t)c] >= 0) to[(size_t)CD * W.h_rep[(size_t)c] + CP] = CP * n + c;
+        std::fill(q.Sdense, q.Sdense + (size_t)ns * ns, 0.0);
+        for (int64_t c = 0; c < W.ng; ++c)   // an empty group has no slot on the device: its row of the system is mu clamp(0) on the diagonal
+            if (W.h_rep[(size_t)c] < 0) q.Sdense[(size_t)(CP * n + c) * (ns + 1)] = q.mu * 1e-6;
+        for (int64_t bcol = 0; bcol < nd; ++bcol)
+            for (int64_t arow = bcol; arow < nd; ++arow) {
+                const int64_t sa = to[(size_t)arow], sb = to[(size_t)bcol];
+                if (sa >= 0 && sb >= 0) q.Sdense[(size_t)std::max(sa, sb) + (size_t)std::min(sa, sb) * ns] = hS[(size_t)arow + (size_t)bcol * nd];
+            }
+    } else if (q.Sdense) {
         W.dense_assemble();
         d2h(q.Sdense, W.Sd.p, (size_t)nd * nd * sizeof(double));
         sync("the dense Schur matrix");
@@ -1542,24 +2029,28 @@ void probe(const SchurOp &SO, const BaSettings &cfg, const double *rot, const do
         keep.alloc((size_t)nd, false);
         XM_HIP_CHECK(hipMemcpyAsync(keep.p, W.b.p, (size_t)nd * sizeof(double), hipMemcpyDeviceToDevice, st));
         for (int64_t j = 0; j < q.k; ++j) {
-            XM_HIP_CHECK(hipMemcpyAsync(W.b.p, q.X + (size_t)nd * j, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
+            to_dev(q.X + (size_t)ns * j, W.b.p);
             XM_HIP_CHECK(hipMemsetAsync(W.z.p, 0, (size_t)nd * sizeof(double), st));   // as the loop's first start finds it: cameras that are no members keep 0
             W.pcg_start();
-            d2h(q.MX + (size_t)nd * j, W.z.p, (size_t)nd * sizeof(double));
-            sync("the preconditioner");
+            from_dev(q.MX + (size_t)ns * j, W.z.p, "the preconditioner");
         }
         XM_HIP_CHECK(hipMemcpyAsync(W.b.p, keep.p, (size_t)nd * sizeof(double), hipMemcpyDeviceToDevice, st));
         wait_stream(st, cfg.watchdog_s, kStage, "the right-hand side");
     }
     if (q.dc) {
-        XM_HIP_CHECK(hipMemcpyAsync(W.x.p, q.dc, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
+        to_dev(q.dc, W.x.p);
         W.candidate(1, W.x.p);
         const BaState s = W.read_state("the probe's candidate");
         q.cost1 = s.cost_new; q.model = s.model;
         q.step2[0] = s.step2[0]; q.step2[1] = s.step2[1]; q.x2[0] = s.x2[0]; q.x2[1] = s.x2[1];
         if constexpr (ba_has_focal<CD>()) {
             if (s.bad_focal) q.cost1 = std::nan("");   // the candidate the loop rejects as invalid
-            if (q.focal1) { d2h(q.focal1, W.G[1].p, (size_t)n * sizeof(double)); sync("the candidate focal scales"); }
+            if (q.focal1 && grouped) {
+                std::vector<double> hG((size_t)n);
+                d2h(hG.data(), W.G[1].p, (size_t)n * sizeof(double));
+                sync("the candidate focal scales");
+                for (int64_t c = 0; c < W.ng; ++c) q.focal1[c] = W.h_rep[(size_t)c] >= 0 ? hG[(size_t)W.h_rep[(size_t)c]] : cfg.focal[c];
+            } else if (q.focal1) { d2h(q.focal1, W.G[1].p, (size_t)n * sizeof(double)); sync("the candidate focal scales"); }
         }
         lm_out(W.dP.p, 3, q.dP);
         lm_out(W.P[1].p, 3, q.p1);
@@ -1654,6 +2145,7 @@ void bundle_adjust(const SchurOp &S, const BaSettings &cfg, double *rot, double 
     out = BaOutcome();
     if (cfg.refine_focal) {
         if (cfg.precond != 0 || !cfg.focal) throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust_focal: needs the focal scales and the default preconditioner");
+        if (cfg.ngroups > 0 && !cfg.group_of) throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust_focal_groups: needs group_of");
         if (cfg.fix_rotations) run<4>(S, cfg, rot, t, p, out, st);
         else run<7>(S, cfg, rot, t, p, out, st);
         return;
@@ -1665,6 +2157,7 @@ void bundle_adjust(const SchurOp &S, const BaSettings &cfg, double *rot, double 
 void ba_probe(const SchurOp &S, const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q, hipStream_t st) {
     if (cfg.refine_focal) {
         if (cfg.precond != 0 || !cfg.focal) throw Error(XM_ERR_ARG, "xm_ctx_ba_probe_focal: needs the focal scales and the default preconditioner");
+        if (cfg.ngroups > 0 && !cfg.group_of) throw Error(XM_ERR_ARG, "xm_ctx_ba_probe_focal_groups: needs group_of");
         if (cfg.fix_rotations) probe<4>(S, cfg, rot, t, p, q, st);
         else probe<7>(S, cfg, rot, t, p, q, st);
         return;

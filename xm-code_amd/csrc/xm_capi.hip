@@ -375,8 +375,15 @@ int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int
     XM_CATCH
 }
 // xm_ctx_bundle_adjust (with_focal = false: XM_BA_REFINE_FOCAL is an unknown flag) and xm_ctx_bundle_adjust_focal (it is required)
+// (groups: xm_ctx_bundle_adjust_focal_groups -- focal and focal_free have ngroups entries, group_of names every camera's group)
+static void check_focal_groups(const std::string &w, int64_t n, int64_t ngroups, const int32_t *group_of) {
+    if (!group_of) throw xm::Error(XM_ERR_ARG, w + ": group_of is null");
+    if (ngroups < 1 || ngroups > n) throw xm::Error(XM_ERR_ARG, w + ": ngroups must lie in [1, n]");
+    for (int64_t i = 0; i < n; ++i)
+        if (group_of[i] < 0 || group_of[i] >= ngroups) throw xm::Error(XM_ERR_ARG, w + ": group_of[" + std::to_string(i) + "] is out of range");
+}
 static void ba_entry(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, bool with_focal, double *focal,
-                     const uint8_t *focal_free, xm_ba_result_t *res) {
+                     const uint8_t *focal_free, xm_ba_result_t *res, bool groups = false, int64_t ngroups = 0, const int32_t *group_of = nullptr) {
     if (!ctx || !opt || !res || !rot || !t || !p || (with_focal && !focal)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: null argument");
     static_assert(offsetof(xm_ba_options_t, loss) == XM_BA_OPTIONS_SIZE_V1, "the first version of xm_ba_options_t ends at trace");
     if (opt->struct_size != sizeof(xm_ba_options_t) && opt->struct_size != XM_BA_OPTIONS_SIZE_V1)
@@ -409,6 +416,9 @@ static void ba_entry(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, dou
     if (o.max_nonmonotonic < 0) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: max_nonmonotonic is negative");
     if (o.trace_cap < 0 || (o.trace_cap > 0 && !o.trace)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: trace_cap > 0 needs a trace array");
     const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks();
+    if (groups) {
+        check_focal_groups("xm_ctx_bundle_adjust_focal_groups", n, ngroups, group_of);
+    }
     if ((o.flags & XM_BA_DENSE_SCHUR) && (((o.flags & XM_BA_FIX_ROTATIONS) ? 3 : 6) + (with_focal ? 1 : 0)) * n > XM_BA_DENSE_MAX_ROWS)
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: XM_BA_DENSE_SCHUR with more than XM_BA_DENSE_MAX_ROWS rows in the reduced camera system");
     for (int64_t k = 0; k < 9 * n; ++k)
@@ -418,10 +428,11 @@ static void ba_entry(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, dou
     for (int64_t k = 0; k < 3 * m; ++k)
         if (!std::isfinite(p[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: landmarks are not finite");
     if (with_focal)
-        for (int64_t k = 0; k < n; ++k)
+        for (int64_t k = 0; k < (groups ? ngroups : n); ++k)
             if (!std::isfinite(focal[k]) || !(focal[k] > 0.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust_focal: a focal scale is not finite and > 0");
     xm::BaSettings c;
     c.refine_focal = with_focal; c.focal = focal; c.focal_free = focal_free;
+    if (groups) { c.ngroups = ngroups; c.group_of = group_of; }
     if (o.max_iters > 0) c.max_iters = o.max_iters;
     if (o.max_time > 0.0) c.max_time = o.max_time;
     if (o.function_tol > 0.0) c.function_tol = o.function_tol;
@@ -458,6 +469,13 @@ int xm_ctx_bundle_adjust_focal(xm_ctx_t *ctx, const xm_ba_options_t *opt, double
     return XM_OK;
     XM_CATCH
 }
+int xm_ctx_bundle_adjust_focal_groups(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, int64_t ngroups,
+                                      const int32_t *group_of, double *focal, const uint8_t *focal_free, xm_ba_result_t *res) {
+    XM_TRY
+    ba_entry(ctx, opt, rot, t, p, true, focal, focal_free, res, true, ngroups, group_of);
+    return XM_OK;
+    XM_CATCH
+}
 static void sqerr_entry(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, bool with_focal, const double *focal, double *sqerr) {
     if (!ctx || !rot || !t || !p || !sqerr || (with_focal && !focal)) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: null argument");
     if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: single-GPU contexts only (not n_gpus > 1)");
@@ -487,7 +505,8 @@ int xm_ctx_reprojection_errors_focal(xm_ctx_t *ctx, const double *rot, const dou
     XM_CATCH
 }
 static void probe_entry(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, bool with_focal, const double *focal,
-                        const uint8_t *focal_free, xm_ba_probe_t *pr, double *focal1) {
+                        const uint8_t *focal_free, xm_ba_probe_t *pr, double *focal1, bool groups = false, int64_t ngroups = 0,
+                        const int32_t *group_of = nullptr) {
     if (!ctx || !rot || !t || !p || !pr || (with_focal && !focal)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: null argument");
     if (pr->struct_size != sizeof(xm_ba_probe_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: xm_ba_probe_t.struct_size is not sizeof(xm_ba_probe_t)");
     if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: single-GPU contexts only (not n_gpus > 1)");
@@ -507,22 +526,27 @@ static void probe_entry(xm_ctx_t *ctx, const double *rot, const double *t, const
     if (pr->k < 0 || (pr->k > 0 && !pr->X)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: k > 0 needs X");
     const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks(), cd = ((pr->flags & XM_BA_FIX_ROTATIONS) ? 3 : 6) + (with_focal ? 1 : 0);
     if (pr->Sdense && cd * n > XM_BA_PROBE_DENSE_MAX_ROWS) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: Sdense with more than XM_BA_PROBE_DENSE_MAX_ROWS rows");
+    if (groups) {
+        check_focal_groups("xm_ctx_ba_probe_focal_groups", n, ngroups, group_of);
+    }
+    const int64_t nvec = groups ? (cd - 1) * n + ngroups : cd * n;   // entries of b, a column of X, dc
     for (int64_t k = 0; k < 9 * n; ++k)
         if (!std::isfinite(rot[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: rotations are not finite");
     for (int64_t k = 0; k < 3 * n; ++k)
         if (!std::isfinite(t[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: translations are not finite");
     for (int64_t k = 0; k < 3 * m; ++k)
         if (!std::isfinite(p[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: landmarks are not finite");
-    for (int64_t k = 0; k < cd * n * pr->k; ++k)
+    for (int64_t k = 0; k < nvec * pr->k; ++k)
         if (!std::isfinite(pr->X[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: X is not finite");
     if (pr->dc)
-        for (int64_t k = 0; k < cd * n; ++k)
+        for (int64_t k = 0; k < nvec; ++k)
             if (!std::isfinite(pr->dc[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: dc is not finite");
     if (with_focal)
-        for (int64_t k = 0; k < n; ++k)
+        for (int64_t k = 0; k < (groups ? ngroups : n); ++k)
             if (!std::isfinite(focal[k]) || !(focal[k] > 0.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe_focal: a focal scale is not finite and > 0");
     xm::BaSettings c;
     c.refine_focal = with_focal; c.focal = const_cast<double *>(focal); c.focal_free = focal_free;   // the probe only reads them
+    if (groups) { c.ngroups = ngroups; c.group_of = group_of; }
     c.fix_rotations = (pr->flags & XM_BA_FIX_ROTATIONS) != 0;
     c.loss = pr->loss; c.loss_scale = pr->loss_scale;
     c.precond = (pr->flags & XM_BA_PRECOND_TWO_LEVEL) ? 2 : (pr->flags & XM_BA_PRECOND_BLOCKS) ? 1 : 0;
@@ -531,10 +555,11 @@ static void probe_entry(xm_ctx_t *ctx, const double *rot, const double *t, const
     q.b = pr->b; q.g_l = pr->g_l; q.vinv = pr->vinv; q.ustar = pr->ustar; q.sinv = pr->sinv; q.cused = pr->cused; q.lused = pr->lused;
     q.SX = pr->SX; q.Sdense = pr->Sdense; q.MX = pr->MX; q.Pm = pr->Pm; q.dropped = pr->dropped; q.Ac = pr->Ac;
     q.dP = pr->dP; q.rot1 = pr->rot1; q.t1 = pr->t1; q.p1 = pr->p1; q.focal1 = with_focal ? focal1 : nullptr;
+    if (groups) { q.group_D = pr->dropped; q.group_F = pr->Ac; q.Pm = q.dropped = q.Ac = nullptr; }   // no aggregates here: their pointers serve the groups
     ctx->impl->ba_probe(c, rot, t, p, q);
     pr->cost = q.cost; pr->gmax = q.gmax; pr->cost1 = q.cost1; pr->model = q.model; pr->n_used = q.n_used;
     pr->step2[0] = q.step2[0]; pr->step2[1] = q.step2[1]; pr->x2[0] = q.x2[0]; pr->x2[1] = q.x2[1];
-    pr->nagg = q.nagg; pr->ncoarse = q.ncoarse; pr->coarse_ok = q.coarse_ok;
+    pr->nagg = q.nagg; pr->ncoarse = q.ncoarse; pr->coarse_ok = q.coarse_ok;   // (focal groups: coarse_ok = the exact focal block was inverted)
 }
 int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_ba_probe_t *pr) {
     XM_TRY
@@ -546,6 +571,13 @@ int xm_ctx_ba_probe_focal(xm_ctx_t *ctx, const double *rot, const double *t, con
                           xm_ba_probe_t *pr, double *focal1) {
     XM_TRY
     probe_entry(ctx, rot, t, p, true, focal, focal_free, pr, focal1);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_ctx_ba_probe_focal_groups(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, int64_t ngroups, const int32_t *group_of,
+                                 const double *focal, const uint8_t *focal_free, xm_ba_probe_t *pr, double *focal1) {
+    XM_TRY
+    probe_entry(ctx, rot, t, p, true, focal, focal_free, pr, focal1, true, ngroups, group_of);
     return XM_OK;
     XM_CATCH
 }

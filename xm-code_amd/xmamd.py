@@ -38,6 +38,7 @@ EXPORTS = [
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
     "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_la_probe", "xm_ba_aggregate_plan", "xm_ctx_ba_probe", "xm_lm_replay",
     "xm_ctx_bundle_adjust_focal", "xm_ctx_reprojection_errors_focal", "xm_ctx_ba_probe_focal",
+    "xm_ctx_bundle_adjust_focal_groups", "xm_ctx_ba_probe_focal_groups",
     "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe", "xm_ctx_outer_probe", "xm_ctx_cert_probe", "xm_tridiag_min", "xm_ctx_schur_probe",
     "xm_ctx_dense_q", "xm_create_matrix", "xm_schur_dense_limits",
     "xm_pair_filter", "xm_pair_filter_limits",
@@ -443,6 +444,7 @@ BA_PRECOND_TWO_LEVEL = 32      # PCG preconditioner: aggregate blocks + rigid-mo
 BA_PRECOND_BLOCKS = 64         # ... the aggregate blocks alone
 BA_AGG_CAMS = 16               # cameras per aggregate
 BA_MAX_AGGREGATES = 4096
+BA_FOCAL_GROUPS_EXACT = 16     # focal groups: up to this many, the preconditioner's focal block is the exact G x G one
 BA_REFINE_FOCAL = 128          # a focal scale per camera in the camera block (xm_ctx_bundle_adjust_focal; the default preconditioner only)
 BA_PRECONDITIONERS = {"jacobi": 0, "blocks": BA_PRECOND_BLOCKS, "two_level": BA_PRECOND_TWO_LEVEL}
 BA_LOSS = {"trivial": 0, "huber": 1, "soft_l1": 2, "cauchy": 3, "arctan": 4}
@@ -491,6 +493,10 @@ def lib():
                                                  C.POINTER(BaResult)]
         L.xm_ctx_reprojection_errors_focal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_ctx_ba_probe_focal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaProbe), C.c_void_p]
+        L.xm_ctx_bundle_adjust_focal_groups.argtypes = [C.c_void_p, C.POINTER(BaOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.POINTER(BaResult)]
+        L.xm_ctx_ba_probe_focal_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(BaProbe), C.c_void_p]
         L.xm_ctx_rtr_probe.argtypes = [C.c_void_p, C.POINTER(RtrProbe)]
         L.xm_ctx_outer_probe.argtypes = [C.c_void_p, C.POINTER(OuterProbe)]
         L.xm_ctx_cert_probe.argtypes = [C.c_void_p, C.POINTER(CertProbe)]
@@ -887,6 +893,21 @@ def _focal_args(n, focal, focal_free, preconditioner="jacobi"):
         if focal_free.shape != (n,):
             raise XmError(f"focal_free: {focal_free.size} values for {n} cameras")
     return focal, focal_free
+
+
+def _focal_group_args(n, focal_group, focal, focal_free, preconditioner="jacobi", linear_solver="iterative_schur"):
+    """the arguments of a call with focal groups, refused here as the C entry points refuse them: group_of (n, int32, in [0, G)), focal
+    (G; None: ones, with G = max(group_of) + 1), focal_free (G or None); G < 1 or G > n, an entry out of range"""
+    group_of = np.asarray(focal_group).reshape(-1)
+    if group_of.shape != (n,) or not np.issubdtype(group_of.dtype, np.integer):
+        raise XmError(f"focal_group: one integer per camera ({n}) is needed")
+    G = (int(group_of.max()) + 1 if n else 0) if focal is None else np.asarray(focal).size
+    if G < 1 or G > n:
+        raise XmError(f"focal_group: {G} groups for {n} cameras (must lie in [1, n])")
+    if group_of.min() < 0 or group_of.max() >= G:
+        raise XmError(f"focal_group: an entry lies outside [0, {G})")
+    focal, focal_free = _focal_args(G, focal, focal_free, preconditioner)
+    return np.ascontiguousarray(group_of, dtype=np.int32), focal, focal_free
 
 
 def rescale_observations(p, cam, focal):
@@ -2058,7 +2079,8 @@ class Context:
 
     def bundle_adjust(self, rot, t, P, fix_rotations=False, max_iters=1000, max_time=300.0, eta=0.1, function_tol=1e-6,
                       gradient_tol=1e-10, parameter_tol=1e-8, trace=0, loss="trivial", loss_scale=0.0, nonmonotonic=False, max_nonmonotonic=0,
-                      linear_solver="iterative_schur", preconditioner="jacobi", refine_focal=False, focal=None, focal_free=None):
+                      linear_solver="iterative_schur", preconditioner="jacobi", refine_focal=False, focal=None, focal_free=None,
+                      focal_group=None):
         """reprojection bundle adjustment of a recovered solution (the reference's Ceres refinement, xm_ctx_bundle_adjust): rot 3 x 3n
         (R_i), t 3 x n, P 3 x m as recover_rotations / recover_tp return them -> refined (rot, t, P, info); matrix-free contexts only.
         loss: a BA_LOSS name with its scale loss_scale (Ceres's a, in normalised image units: pixels / focal length); nonmonotonic=True:
@@ -2074,8 +2096,18 @@ class Context:
         1/2 sum rho(|r|^2).
         refine_focal=True (xm_ctx_bundle_adjust_focal): one focal scale g_i > 0 per camera joins its block, r = g_i pi(X) - z; focal (n;
         None = ones) is the start, focal_free (n; None = all) holds the cameras with 0 at their value; info["focal"] is the refined
-        array.  preconditioner must be "jacobi"."""
-        if refine_focal:   # refused before the device
+        array.  preconditioner must be "jacobi".
+        focal_group (n integers in [0, G); xm_ctx_bundle_adjust_focal_groups): the cameras of a group share ONE focal scale, as the images
+        of one physical camera do; focal and focal_free then have G entries (focal None: ones, G = max(focal_group) + 1) and
+        info["focal"] has shape (G,); pass info["focal"][focal_group] where per-image scales are taken (reprojection_errors,
+        rescale_observations).  With at most BA_FOCAL_GROUPS_EXACT groups the PCG's preconditioner holds the exact focal block
+        (info["coarse_fallbacks"]: LM iterations in which it could not be factored).  None: the per-image call, unchanged."""
+        group_of = None
+        if focal_group is not None:
+            if not refine_focal:
+                raise XmError("focal_group is given but refine_focal is not set")
+            group_of, focal, focal_free = _focal_group_args(self.n, focal_group, focal, focal_free, preconditioner, linear_solver)
+        elif refine_focal:   # refused before the device
             focal, focal_free = _focal_args(self.n, focal, focal_free, preconditioner)
         elif focal is not None or focal_free is not None:
             raise XmError("focal / focal_free are given but refine_focal is not set")
@@ -2097,7 +2129,13 @@ class Context:
         tr = None
         if trace:
             tr = np.zeros((int(trace), 6)); opt.trace_cap = int(trace); opt.trace = tr.ctypes.data_as(C.c_void_p)
-        if refine_focal:
+        if group_of is not None:
+            opt.flags |= BA_REFINE_FOCAL
+            _chk(lib().xm_ctx_bundle_adjust_focal_groups(self.h, C.byref(opt), rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                                         P.ctypes.data_as(C.c_void_p), focal.size, group_of.ctypes.data_as(C.c_void_p),
+                                                         focal.ctypes.data_as(C.c_void_p),
+                                                         None if focal_free is None else focal_free.ctypes.data_as(C.c_void_p), C.byref(res)))
+        elif refine_focal:
             opt.flags |= BA_REFINE_FOCAL
             _chk(lib().xm_ctx_bundle_adjust_focal(self.h, C.byref(opt), rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
                                                   P.ctypes.data_as(C.c_void_p), focal.ctypes.data_as(C.c_void_p),
@@ -2192,14 +2230,22 @@ class Context:
         return self._ba_probe(rot, t, P, mu, fix_rotations, loss, loss_scale, preconditioner, X, dc, dense, False, None, None)
 
     def ba_probe_focal(self, rot, t, P, mu, focal=None, focal_free=None, fix_rotations=False, loss="trivial", loss_scale=0.0, X=None, dc=None,
-                       dense=False, preconditioner="jacobi"):
+                       dense=False, preconditioner="jacobi", focal_group=None):
         """ba_probe for bundle_adjust(refine_focal=True) (the test export xm_ctx_ba_probe_focal): focal, focal_free as there; the same dict
         with CD = 7, or 4 with fixed rotations, the focal the last entry of a camera's block; with dc also focal1 (n), the candidate's focal
-        scales, and cost1 is NaN when one of them is not positive.  preconditioner: only "jacobi" (the others are refused here)."""
+        scales, and cost1 is NaN when one of them is not positive.  preconditioner: only "jacobi" (the others are refused here).
+        focal_group (xm_ctx_ba_probe_focal_groups): focal, focal_free per group (G); b (CP n + G), X, SX, MX (CP n + G rows) and dc
+        (CP n + G) are vectors of the shared space -- CP = CD - 1 entries per camera, then the G focal entries --, focal1 has G entries,
+        and the dict also holds D (G: D_c) and F (the preconditioner's focal block: G x G for G <= BA_FOCAL_GROUPS_EXACT, with coarse_ok =
+        1 when it was inverted, else its G diagonal entries); dense=True: Sdense is the lower triangle of the (CP n + G)-row matrix."""
+        if focal_group is not None:
+            group_of, focal, focal_free = _focal_group_args(self.n, focal_group, focal, focal_free, preconditioner)
+            return self._ba_probe(rot, t, P, mu, fix_rotations, loss, loss_scale, preconditioner, X, dc, dense, True, focal, focal_free, group_of)
         focal, focal_free = _focal_args(self.n, focal, focal_free, preconditioner)
         return self._ba_probe(rot, t, P, mu, fix_rotations, loss, loss_scale, preconditioner, X, dc, dense, True, focal, focal_free)
 
-    def _ba_probe(self, rot, t, P, mu, fix_rotations, loss, loss_scale, preconditioner, X, dc, dense, refine_focal, focal, focal_free):
+    def _ba_probe(self, rot, t, P, mu, fix_rotations, loss, loss_scale, preconditioner, X, dc, dense, refine_focal, focal, focal_free,
+                  group_of=None):
         rot = np.asfortranarray(np.asarray(rot, dtype=np.float64)); t = np.asfortranarray(np.asarray(t, dtype=np.float64))
         P = np.asfortranarray(np.asarray(P, dtype=np.float64))
         n, m = self.n, self.n_landmarks
@@ -2211,30 +2257,42 @@ class Context:
         cd, nc = (3, 4) if fix_rotations else (6, 7)
         cd += 1 if refine_focal else 0
         nd = cd * n
+        nvec = nd if group_of is None else (cd - 1) * n + focal.size   # entries of b, of a column of X and of dc
         q = BaProbe()
         q.struct_size = C.sizeof(BaProbe)
         q.flags = (BA_FIX_ROTATIONS if fix_rotations else 0) | BA_PRECONDITIONERS[preconditioner] | (BA_REFINE_FOCAL if refine_focal else 0)
         q.loss, q.loss_scale, q.mu = BA_LOSS[loss], float(loss_scale), float(mu)
-        out = dict(b=np.zeros((n, cd)), g_l=np.zeros((m, 3)), vinv=np.zeros((m, 6)), ustar=np.zeros((n, cd, cd)), sinv=np.zeros((n, cd, cd)),
+        out = dict(b=np.zeros((n, cd) if group_of is None else nvec), g_l=np.zeros((m, 3)), vinv=np.zeros((m, 6)), ustar=np.zeros((n, cd, cd)), sinv=np.zeros((n, cd, cd)),
                    cused=np.zeros(n, dtype=np.int32), lused=np.zeros(m, dtype=np.int32))
         if X is not None:
-            X = np.asfortranarray(np.asarray(X, dtype=np.float64).reshape(nd, -1))
+            X = np.asfortranarray(np.asarray(X, dtype=np.float64).reshape(nvec, -1))
             q.k, q.X = X.shape[1], X.ctypes.data_as(C.c_void_p)
             out["SX"] = np.zeros(X.shape, order="F"); out["MX"] = np.zeros(X.shape, order="F")
         if dense:
             if nd > BA_PROBE_DENSE_MAX_ROWS:
                 raise XmError("ba_probe: Sdense with more than BA_PROBE_DENSE_MAX_ROWS rows")
-            out["Sdense"] = np.zeros((nd, nd), order="F")
+            out["Sdense"] = np.zeros((nvec, nvec), order="F")
         ncmax = nc * ((n + BA_AGG_CAMS - 1) // BA_AGG_CAMS)
         if preconditioner == "two_level":
             out["Pm"] = np.zeros((nd, nc)); out["dropped"] = np.zeros(ncmax); out["Ac"] = np.zeros(ncmax * ncmax)
         if dc is not None:
-            dc = np.ascontiguousarray(np.asarray(dc, dtype=np.float64).reshape(nd))
+            dc = np.ascontiguousarray(np.asarray(dc, dtype=np.float64).reshape(nvec))
             q.dc = dc.ctypes.data_as(C.c_void_p)
             out.update(dP=np.zeros((m, 3)), rot1=np.zeros((3, 3 * n), order="F"), t1=np.zeros((3, n), order="F"), p1=np.zeros((3, m), order="F"))
         for k, v in out.items():
             setattr(q, k, v.ctypes.data_as(C.c_void_p))
-        if refine_focal:
+        if group_of is not None:   # the aggregates' pointers serve the groups (include/xm_amd.h): dropped <- D_c, Ac <- F_c
+            G = focal.size
+            out["D"] = np.zeros(G); out["F"] = np.zeros((G, G), order="F") if G <= BA_FOCAL_GROUPS_EXACT else np.zeros(G)
+            q.dropped, q.Ac = out["D"].ctypes.data_as(C.c_void_p), out["F"].ctypes.data_as(C.c_void_p)
+            focal1 = np.zeros(focal.size) if dc is not None else None
+            _chk(lib().xm_ctx_ba_probe_focal_groups(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p),
+                                                    focal.size, group_of.ctypes.data_as(C.c_void_p), focal.ctypes.data_as(C.c_void_p),
+                                                    None if focal_free is None else focal_free.ctypes.data_as(C.c_void_p), C.byref(q),
+                                                    None if focal1 is None else focal1.ctypes.data_as(C.c_void_p)))
+            if focal1 is not None:
+                out["focal1"] = focal1
+        elif refine_focal:
             focal1 = np.zeros(n) if dc is not None else None
             _chk(lib().xm_ctx_ba_probe_focal(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p),
                                              focal.ctypes.data_as(C.c_void_p), None if focal_free is None else focal_free.ctypes.data_as(C.c_void_p),
