@@ -1575,9 +1575,9 @@ int xm_ctx_ba_probe_focal_groups(xm_ctx_t *ctx, const double *rot, const double 
  *   bound       DEPARTURE from Ceres (which projects the step and runs a line search): a scale with s_e <= 1e-5 whose gradient points
  *               outward (g_s > 0) is frozen for that iteration (its column of J is zero: M_e = w s^2 I, q_e = w s r, ds_e = 0), and the
  *               candidate is s <- max(s + ds, 1e-5).
- *   departures  the start is the caller's (the reference draws it from std::mt19937 in hash-map order); every camera counts as calibrated (no
- *               has_prior_focal_length down-weighting); only ONLY_POINTS (no camera-to-camera constraints); no NormalizeReconstruction;
- *               no Jacobi column scaling (as xm_ctx_bundle_adjust).
+ *   departures  the start is the caller's (the reference draws it from std::mt19937 in hash-map order); no NormalizeReconstruction; no Jacobi column
+ *               scaling (as xm_ctx_bundle_adjust).  This entry is the ONLY_POINTS form with every camera calibrated; the other constraint
+ *               types, the has_prior_focal_length down-weighting and the fixed-centre pass: xm_ctx_global_positioning_pairs below.
  * Options: struct_size = sizeof(xm_gp_options_t); max_iters, max_time, function_tol, gradient_tol, parameter_tol, min_views: 0 = the defaults
  * (100 and 1e-5: optimization_base.h:23, :25; 300 s, 1e-10, 1e-8, 3); eta is required and lies in (0, 1).  trace as in xm_ba_options_t.  scales
  * (may be NULL): nobs doubles in input order, -1 for an observation that is not used.
@@ -1637,6 +1637,79 @@ int xm_ctx_gp_probe(xm_ctx_t *ctx, const double *rot, const double *t, const dou
 /* constants of the kernels, host-only (the tests size their edge cases from them): out[0] = a landmark with more observations than this
  * has a workgroup of its own, out[1] = observations a wavefront takes from a camera's list in one pass, out[2] = threads of that workgroup */
 int xm_gp_limits(int64_t out[3]);
+
+/* ---- Global positioning with camera-to-camera constraints, per-camera weights and a fixed-centre point pass: the other three constraint
+ * types of estimators/global_positioning.cc (ONLY_CAMERAS, POINTS_AND_CAMERAS, POINTS_AND_CAMERAS_BALANCED, .cc:53-60) and the second pass
+ * of controllers/global_mapper.cc:205-217 (optimize_positions = false).  Everything xm_ctx_global_positioning states holds word for word
+ * (input layouts, used observations, loss, LM rules, bound, PCG, stops, trace, refusals, fixed-order sums, f64); what is added:
+ *   pairs       pi, pj (image_id1, image_id2), trel (3 npairs: the translation of cam2_from_cam1, used as given), valid (npairs bytes, NULL =
+ *               all valid): the conventions of xm_view_graph_filter and xm_view_graph_rotations.  A pair takes part when it is valid
+ *               (.cc:152).  pi == pj or an index outside [0, n) is XM_ERR_ARG, for every pair named.
+ *   residual    r_m = tau_m - sigma_m (c_j - c_i) with tau_m = -R_j trel_m (.cc:165-175; R_j = rot of image_id2, camera-to-world; position1 =
+ *               c_i, position2 = c_j) and one scale sigma_m per participating pair: 1 at the start, bounded below by 1e-5 (.cc:163, :177) by
+ *               the active-set rule of the observation scales.  Loss: the plain loss of the options (.cc:172), never weighted.
+ *   weights     of the observation terms (.cc:201-228, :283-295): rho and rho' are multiplied by a_e (Ceres's ScaledLoss).
+ *               weight_scale_pt = reweight_scale * (participating pairs) / (landmarks of the context) for BALANCED with at least one
+ *               participating pair, else 1.  The divisor is ALL landmarks of the context, as the reference divides by tracks.size()
+ *               (.cc:193), not the used ones.  a_e = weight_scale_pt for a calibrated camera (1 unless BALANCED) and 0.5 weight_scale_pt for
+ *               one with calibrated[i] == 0, in every type that has observation terms.  calibrated: n bytes, NULL = all calibrated.
+ *   terms       XM_GP_ONLY_POINTS: observations; XM_GP_ONLY_CAMERAS: pairs -- no observation is used, p comes back bit-identical and every
+ *               scale -1; the two mixed types: both.  A type with pair terms and no participating pair is XM_ERR_ARG (.cc:32-36).
+ *   used        a camera is used when it has a used observation (where observation terms exist) or a participating pair (where pair terms
+ *               exist), .cc:108-127.  Everything else comes back with the caller's bits.
+ *   elimination pair scales in closed form like observation scales: with v = c_j - c_i, w = rho', h* = w |v|^2 + mu clamp(w |v|^2),
+ *               g_sigma = -w r.v:  M_m = w sigma^2 I - (w sigma)^2 v v^T / h*,  q_m = w sigma (r + v g_sigma / h*).  M_m enters the reduced
+ *               camera system directly: S_ii += M_m, S_jj += M_m, S_ij = S_ji = -M_m; q_m enters the gradient of i with the camera's sign
+ *               and of j with the point's.  Camera damping mu clamp(sum_obs a w s^2 + sum_pairs w sigma^2): one clamp of the whole diagonal.
+ *               d sigma_m = -(g_sigma - w sigma v.dc_i + w sigma v.dc_j) / h*.  |x|^2 and |step|^2 add sigma^2 and d sigma^2; the gradient
+ *               test sees g_sigma of the pairs that are not frozen.  The PCG's 3 x 3 blocks of S_ii include the pair terms.
+ *   fixed       XM_GP_FIX_CENTRES (with XM_GP_ONLY_POINTS only, anything else is XM_ERR_ARG): the centres are constants, t is read only and
+ *               comes back bit-identical; no camera pass and no PCG, dP_l = -V*_l^-1 g_l; |x|^2 and |step|^2 count points and scales only;
+ *               the gradient test sees points and scales.
+ * With XM_GP_ONLY_POINTS, no flag and calibrated NULL the call launches what xm_ctx_global_positioning launches and returns its bytes.
+ * xm_gp_pairs_t: struct_size = sizeof; reweight_scale 0 = 1.0 (negative or non-finite: XM_ERR_ARG); sigma (out, may be NULL): npairs doubles,
+ * -1 for a pair that takes no part.  Outputs: pairs_used, cams_heavy (cameras whose incidence list a workgroup walks), max_incidences,
+ * weight_scale_pt.  NOTHING HERE WAS COMPARED WITH THE REFERENCE'S COMPILED CODE: parity rests on tests/xm_gp_pairs_numpy.py. */
+#define XM_GP_ONLY_POINTS                  0
+#define XM_GP_ONLY_CAMERAS                 1
+#define XM_GP_POINTS_AND_CAMERAS_BALANCED  2
+#define XM_GP_POINTS_AND_CAMERAS           3
+#define XM_GP_FIX_CENTRES                  1u
+typedef struct {
+    uint32_t struct_size;
+    int32_t constraint;        /* XM_GP_ONLY_POINTS ... */
+    uint32_t flags;            /* XM_GP_FIX_CENTRES */
+    int32_t pad;
+    int64_t npairs;
+    const int32_t *pi, *pj;
+    const double *trel;
+    const uint8_t *valid, *calibrated;
+    double reweight_scale;
+    double *sigma;
+    int64_t pairs_used, cams_heavy, max_incidences;
+    double weight_scale_pt;
+} xm_gp_pairs_t;
+int xm_ctx_global_positioning_pairs(xm_ctx_t *ctx, const xm_gp_options_t *opt, xm_gp_pairs_t *pairs, const double *rot, double *t, double *p,
+                                    double *scales_or_null, xm_gp_result_t *res);
+/* One linearisation of xm_ctx_global_positioning_pairs, a test export (tests/test_gpu_gp_pairs_stages.py): xm_ctx_gp_probe with the terms
+ * that `pairs` selects, through the workspace class and the launches of the LM loop.  probe is filled as by xm_ctx_gp_probe: cost, cost1,
+ * model, step2 and x2 from the observation terms alone, gmax over everything the loop's gradient test sees, ustar / sinv / b / SX with the
+ * pair terms in them; with XM_GP_FIX_CENTRES dc is taken as 0 and k must be 0.  pair_probe: sigma_in (npairs, read where the pair takes
+ * part, NULL = all 1) -> the pairs' cost, gsmax (max |g_sigma| over the pairs that are not frozen), cost1, model, step2, x2, and per pair in
+ * input order Mp (6 npairs: 00 01 02 11 12 22), qp (3 npairs), pfrozen, pused, dsigma and sigma1 (-1 where the pair takes no part). */
+typedef struct {
+    uint32_t struct_size;
+    int32_t pad;
+    const double *sigma_in;
+    double cost, gsmax, cost1, model, step2, x2;
+    double *Mp, *qp;
+    int32_t *pfrozen, *pused;
+    double *dsigma, *sigma1;
+} xm_gp_pair_probe_t;
+int xm_ctx_gp_probe_pairs(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_gp_probe_t *probe, xm_gp_pairs_t *pairs,
+                          xm_gp_pair_probe_t *pair_probe);
+/* out[0] = a camera with more incidences (ends of participating pairs) than this has a workgroup of its own, out[1] = threads of it */
+int xm_gp_pair_limits(int64_t out[2]);
 /* The trust region's kernels stage by stage, a test export (tests/test_gpu_rtr_stages.py): at the point (R: 3n x o column-major, s: n; s[0] is
  * forced to 1 as in a solve) and with lam, the stages below run through the context's own setup for rank o, its product dispatch and the
  * launchers, grids and arguments of a solve -- the kernels are those the storage and xm_tuning_t select (product_kind: XM_PRODUCT_*; split_k: slices of

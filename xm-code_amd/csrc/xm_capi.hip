@@ -222,6 +222,74 @@ void gp_check(const char *who, xm_ctx_t *ctx, int loss, double loss_scale, int m
     for (int64_t k = 0; k < 3 * m; ++k)
         if (!std::isfinite(p[k])) throw xm::Error(XM_ERR_ARG, w + ": points are not finite");
 }
+// xm_gp_options_t -> the solver's settings, with the refusals the two positioning entries share
+xm::GpSettings gp_settings(const char *who, xm_ctx_t *ctx, const xm_gp_options_t *opt, const xm_gp_result_t *res, const double *rot, const double *t,
+                           const double *p) {
+    const std::string w(who);
+    if (!ctx || !opt || !res || !rot || !t || !p) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (opt->struct_size != sizeof(xm_gp_options_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_gp_options_t.struct_size is not sizeof(xm_gp_options_t)");
+    if (res->struct_size != sizeof(xm_gp_result_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_gp_result_t.struct_size is not sizeof(xm_gp_result_t)");
+    const xm_gp_options_t &o = *opt;
+    auto bad = [](double v) { return !(v >= 0.0) || !std::isfinite(v); };
+    if (!(o.eta > 0.0 && o.eta < 1.0)) throw xm::Error(XM_ERR_ARG, w + ": eta must lie in (0, 1)");
+    if (o.max_iters < 0 || bad(o.max_time) || bad(o.function_tol) || bad(o.gradient_tol) || bad(o.parameter_tol))
+        throw xm::Error(XM_ERR_ARG, w + ": negative or non-finite setting");
+    if (o.trace_cap < 0 || (o.trace_cap > 0 && !o.trace)) throw xm::Error(XM_ERR_ARG, w + ": trace_cap > 0 needs a trace array");
+    gp_check(who, ctx, o.loss, o.loss_scale, o.min_views, rot, t, p);
+    xm::GpSettings c;
+    if (o.max_iters > 0) c.max_iters = o.max_iters;
+    if (o.max_time > 0.0) c.max_time = o.max_time;
+    if (o.function_tol > 0.0) c.function_tol = o.function_tol;
+    if (o.gradient_tol > 0.0) c.gradient_tol = o.gradient_tol;
+    if (o.parameter_tol > 0.0) c.parameter_tol = o.parameter_tol;
+    if (o.min_views > 0) c.min_views = o.min_views;
+    c.eta = o.eta;
+    c.loss = o.loss; c.loss_scale = o.loss_scale;
+    c.trace_cap = o.trace_cap; c.trace = o.trace;
+    return c;
+}
+void gp_result_out(const xm::GpOutcome &r, xm_gp_result_t *res) {
+    xm_gp_result_t out;
+    std::memset(&out, 0, sizeof(out));
+    out.struct_size = sizeof(xm_gp_result_t);
+    out.status = r.status; out.iters = r.iters; out.accepted = r.accepted; out.pcg_iters = r.pcg_iters; out.n_used = r.n_used;
+    out.initial_cost = r.initial_cost; out.final_cost = r.final_cost; out.gradient_max = r.gradient_max; out.seconds = r.seconds;
+    out.trace_len = r.trace_len;
+    *res = out;
+}
+// xm_gp_pairs_t -> the solver's view of it, with the refusals of the contract (the context is known to be a single one: gp_check came first)
+xm::GpPairsIn gp_pairs_in(const char *who, xm_ctx_t *ctx, const xm_gp_pairs_t *pr) {
+    const std::string w(who);
+    if (pr->struct_size != sizeof(xm_gp_pairs_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_gp_pairs_t.struct_size is not sizeof(xm_gp_pairs_t)");
+    if (pr->constraint < XM_GP_ONLY_POINTS || pr->constraint > XM_GP_POINTS_AND_CAMERAS) throw xm::Error(XM_ERR_ARG, w + ": unknown constraint type");
+    if (pr->flags & ~XM_GP_FIX_CENTRES) throw xm::Error(XM_ERR_ARG, w + ": unknown flag");
+    const bool fix = (pr->flags & XM_GP_FIX_CENTRES) != 0;
+    if (fix && pr->constraint != XM_GP_ONLY_POINTS) throw xm::Error(XM_ERR_ARG, w + ": XM_GP_FIX_CENTRES goes with XM_GP_ONLY_POINTS only");
+    if (pr->npairs < 0 || pr->npairs > INT32_MAX) throw xm::Error(XM_ERR_ARG, w + ": npairs is negative or too large");
+    if (pr->npairs > 0 && (!pr->pi || !pr->pj || !pr->trel)) throw xm::Error(XM_ERR_ARG, w + ": npairs > 0 needs pi, pj and trel");
+    if (!(pr->reweight_scale >= 0.0) || !std::isfinite(pr->reweight_scale)) throw xm::Error(XM_ERR_ARG, w + ": reweight_scale is negative or not finite");
+    const int64_t n = ctx->impl->cameras();
+    int64_t part = 0;
+    for (int64_t k = 0; k < pr->npairs; ++k) {
+        const int64_t i = pr->pi[k], j = pr->pj[k];
+        if (i < 0 || i >= n || j < 0 || j >= n || i == j) throw xm::Error(XM_ERR_ARG, w + ": a pair names a camera outside [0, n) or one camera twice");
+        if (pr->valid && !pr->valid[k]) continue;
+        ++part;
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(pr->trel[3 * k + c])) throw xm::Error(XM_ERR_ARG, w + ": trel of a participating pair is not finite");
+    }
+    if (pr->constraint != XM_GP_ONLY_POINTS && part == 0)
+        throw xm::Error(XM_ERR_ARG, w + ": the constraint type has pair terms but no pair takes part");
+    xm::GpPairsIn in;
+    in.constraint = pr->constraint; in.fix_centres = fix; in.npairs = pr->npairs;
+    in.pi = pr->pi; in.pj = pr->pj; in.trel = pr->trel; in.valid = pr->valid; in.calibrated = pr->calibrated;
+    in.reweight_scale = pr->reweight_scale > 0.0 ? pr->reweight_scale : 1.0;
+    in.sigma = pr->sigma;
+    return in;
+}
+void gp_pairs_out(const xm::GpPairsIn &in, xm_gp_pairs_t *pr) {
+    pr->pairs_used = in.pairs_used; pr->cams_heavy = in.cams_heavy; pr->max_incidences = in.max_incidences; pr->weight_scale_pt = in.weight_scale_pt;
+}
 }  // namespace
 
 extern "C" {
@@ -583,54 +651,43 @@ int xm_ctx_ba_probe_focal_groups(xm_ctx_t *ctx, const double *rot, const double 
 }
 int xm_ctx_global_positioning(xm_ctx_t *ctx, const xm_gp_options_t *opt, const double *rot, double *t, double *p, double *scales, xm_gp_result_t *res) {
     XM_TRY
-    if (!ctx || !opt || !res || !rot || !t || !p) throw xm::Error(XM_ERR_ARG, "xm_ctx_global_positioning: null argument");
-    if (opt->struct_size != sizeof(xm_gp_options_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_global_positioning: xm_gp_options_t.struct_size is not sizeof(xm_gp_options_t)");
-    if (res->struct_size != sizeof(xm_gp_result_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_global_positioning: xm_gp_result_t.struct_size is not sizeof(xm_gp_result_t)");
-    const xm_gp_options_t &o = *opt;
-    auto bad = [](double v) { return !(v >= 0.0) || !std::isfinite(v); };
-    if (!(o.eta > 0.0 && o.eta < 1.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_global_positioning: eta must lie in (0, 1)");
-    if (o.max_iters < 0 || bad(o.max_time) || bad(o.function_tol) || bad(o.gradient_tol) || bad(o.parameter_tol))
-        throw xm::Error(XM_ERR_ARG, "xm_ctx_global_positioning: negative or non-finite setting");
-    if (o.trace_cap < 0 || (o.trace_cap > 0 && !o.trace)) throw xm::Error(XM_ERR_ARG, "xm_ctx_global_positioning: trace_cap > 0 needs a trace array");
-    gp_check("xm_ctx_global_positioning", ctx, o.loss, o.loss_scale, o.min_views, rot, t, p);
-    xm::GpSettings c;
-    if (o.max_iters > 0) c.max_iters = o.max_iters;
-    if (o.max_time > 0.0) c.max_time = o.max_time;
-    if (o.function_tol > 0.0) c.function_tol = o.function_tol;
-    if (o.gradient_tol > 0.0) c.gradient_tol = o.gradient_tol;
-    if (o.parameter_tol > 0.0) c.parameter_tol = o.parameter_tol;
-    if (o.min_views > 0) c.min_views = o.min_views;
-    c.eta = o.eta;
-    c.loss = o.loss; c.loss_scale = o.loss_scale;
-    c.trace_cap = o.trace_cap; c.trace = o.trace;
+    const xm::GpSettings c = gp_settings("xm_ctx_global_positioning", ctx, opt, res, rot, t, p);
     xm::GpOutcome r;
     ctx->impl->global_positioning(c, rot, t, p, scales, r);
-    xm_gp_result_t out;
-    std::memset(&out, 0, sizeof(out));
-    out.struct_size = sizeof(xm_gp_result_t);
-    out.status = r.status; out.iters = r.iters; out.accepted = r.accepted; out.pcg_iters = r.pcg_iters; out.n_used = r.n_used;
-    out.initial_cost = r.initial_cost; out.final_cost = r.final_cost; out.gradient_max = r.gradient_max; out.seconds = r.seconds;
-    out.trace_len = r.trace_len;
-    *res = out;
+    gp_result_out(r, res);
     return XM_OK;
     XM_CATCH
 }
-int xm_ctx_gp_probe(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_gp_probe_t *pr) {
+int xm_ctx_global_positioning_pairs(xm_ctx_t *ctx, const xm_gp_options_t *opt, xm_gp_pairs_t *pairs, const double *rot, double *t, double *p,
+                                    double *scales, xm_gp_result_t *res) {
     XM_TRY
-    if (!ctx || !rot || !t || !p || !pr) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe: null argument");
-    if (pr->struct_size != sizeof(xm_gp_probe_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe: xm_gp_probe_t.struct_size is not sizeof(xm_gp_probe_t)");
-    if (!(pr->mu > 0.0) || !std::isfinite(pr->mu)) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe: mu must be finite and > 0");
-    if (pr->k < 0 || (pr->k > 0 && !pr->X)) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe: k > 0 needs X");
-    gp_check("xm_ctx_gp_probe", ctx, pr->loss, pr->loss_scale, pr->min_views, rot, t, p);
+    if (!pairs) throw xm::Error(XM_ERR_ARG, "xm_ctx_global_positioning_pairs: null argument");
+    const xm::GpSettings c = gp_settings("xm_ctx_global_positioning_pairs", ctx, opt, res, rot, t, p);
+    xm::GpPairsIn in = gp_pairs_in("xm_ctx_global_positioning_pairs", ctx, pairs);
+    xm::GpOutcome r;
+    ctx->impl->global_positioning_pairs(c, in, rot, t, p, scales, r);
+    gp_result_out(r, res);
+    gp_pairs_out(in, pairs);
+    return XM_OK;
+    XM_CATCH
+}
+static void gp_probe_entry(const char *who, xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_gp_probe_t *pr, xm_gp_pairs_t *pairs,
+                           xm_gp_pair_probe_t *pp) {
+    const std::string w(who);
+    if (!ctx || !rot || !t || !p || !pr) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (pr->struct_size != sizeof(xm_gp_probe_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_gp_probe_t.struct_size is not sizeof(xm_gp_probe_t)");
+    if (!(pr->mu > 0.0) || !std::isfinite(pr->mu)) throw xm::Error(XM_ERR_ARG, w + ": mu must be finite and > 0");
+    if (pr->k < 0 || (pr->k > 0 && !pr->X)) throw xm::Error(XM_ERR_ARG, w + ": k > 0 needs X");
+    gp_check(who, ctx, pr->loss, pr->loss_scale, pr->min_views, rot, t, p);
     const int64_t n = ctx->impl->cameras(), nobs = ctx->impl->n_observations();
     if (pr->s)
         for (int64_t k = 0; k < nobs; ++k)
-            if (!std::isfinite(pr->s[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe: s is not finite");
+            if (!std::isfinite(pr->s[k])) throw xm::Error(XM_ERR_ARG, w + ": s is not finite");
     for (int64_t k = 0; k < 3 * n * pr->k; ++k)
-        if (!std::isfinite(pr->X[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe: X is not finite");
+        if (!std::isfinite(pr->X[k])) throw xm::Error(XM_ERR_ARG, w + ": X is not finite");
     if (pr->dc)
         for (int64_t k = 0; k < 3 * n; ++k)
-            if (!std::isfinite(pr->dc[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe: dc is not finite");
+            if (!std::isfinite(pr->dc[k])) throw xm::Error(XM_ERR_ARG, w + ": dc is not finite");
     xm::GpSettings c;
     if (pr->min_views > 0) c.min_views = pr->min_views;
     c.loss = pr->loss; c.loss_scale = pr->loss_scale;
@@ -639,9 +696,37 @@ int xm_ctx_gp_probe(xm_ctx_t *ctx, const double *rot, const double *t, const dou
     q.M = pr->M; q.q = pr->q; q.frozen = pr->frozen; q.oused = pr->oused;
     q.vinv = pr->vinv; q.g_l = pr->g_l; q.ustar = pr->ustar; q.sinv = pr->sinv; q.b = pr->b; q.cused = pr->cused; q.lused = pr->lused;
     q.SX = pr->SX; q.dP = pr->dP; q.ds = pr->ds; q.t1 = pr->t1; q.p1 = pr->p1; q.s1 = pr->s1;
-    ctx->impl->gp_probe(c, rot, t, p, q);
+    if (pairs) {
+        if (!pp) throw xm::Error(XM_ERR_ARG, w + ": null argument");
+        if (pp->struct_size != sizeof(xm_gp_pair_probe_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_gp_pair_probe_t.struct_size is not sizeof(xm_gp_pair_probe_t)");
+        xm::GpPairsIn in = gp_pairs_in(who, ctx, pairs);
+        if (in.fix_centres && pr->k > 0) throw xm::Error(XM_ERR_ARG, w + ": fixed centres have no reduced camera system (k must be 0)");
+        if (pp->sigma_in)
+            for (int64_t k = 0; k < in.npairs; ++k)
+                if (!std::isfinite(pp->sigma_in[k])) throw xm::Error(XM_ERR_ARG, w + ": sigma_in is not finite");
+        xm::GpPairProbe pq;
+        pq.sigma_in = pp->sigma_in; pq.Mp = pp->Mp; pq.qp = pp->qp; pq.pfrozen = pp->pfrozen; pq.pused = pp->pused; pq.dsigma = pp->dsigma;
+        pq.sigma1 = pp->sigma1;
+        ctx->impl->gp_probe_pairs(c, in, rot, t, p, q, pq);
+        pp->cost = pq.cost; pp->gsmax = pq.gsmax; pp->cost1 = pq.cost1; pp->model = pq.model; pp->step2 = pq.step2; pp->x2 = pq.x2;
+        gp_pairs_out(in, pairs);
+    } else {
+        ctx->impl->gp_probe(c, rot, t, p, q);
+    }
     pr->cost = q.cost; pr->gmax = q.gmax; pr->cost1 = q.cost1; pr->model = q.model; pr->n_used = q.n_used;
     for (int k = 0; k < 3; ++k) { pr->step2[k] = q.step2[k]; pr->x2[k] = q.x2[k]; }
+}
+int xm_ctx_gp_probe(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_gp_probe_t *pr) {
+    XM_TRY
+    gp_probe_entry("xm_ctx_gp_probe", ctx, rot, t, p, pr, nullptr, nullptr);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_ctx_gp_probe_pairs(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, xm_gp_probe_t *pr, xm_gp_pairs_t *pairs,
+                          xm_gp_pair_probe_t *pp) {
+    XM_TRY
+    if (!pairs) throw xm::Error(XM_ERR_ARG, "xm_ctx_gp_probe_pairs: null argument");
+    gp_probe_entry("xm_ctx_gp_probe_pairs", ctx, rot, t, p, pr, pairs, pp);
     return XM_OK;
     XM_CATCH
 }
@@ -649,6 +734,13 @@ int xm_gp_limits(int64_t out[3]) {
     XM_TRY
     if (!out) throw xm::Error(XM_ERR_ARG, "xm_gp_limits: null output");
     xm::gp_limits(out);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_gp_pair_limits(int64_t out[2]) {
+    XM_TRY
+    if (!out) throw xm::Error(XM_ERR_ARG, "xm_gp_pair_limits: null output");
+    xm::gp_pair_limits(out);
     return XM_OK;
     XM_CATCH
 }

@@ -70,13 +70,50 @@ struct GpProbe {
     double *SX = nullptr, *dP = nullptr, *ds = nullptr, *t1 = nullptr, *p1 = nullptr, *s1 = nullptr;
 };
 
+// Camera-to-camera terms and the fixed-centre pass (xm_ctx_global_positioning_pairs, include/xm_amd.h): the view graph's relative translations
+// in the same residual, r_m = tau_m - sigma_m (c_j - c_i) with tau_m = -R_j trel_m and one scale sigma_m >= 1e-5 per participating pair
+// (global_positioning.cc:149-183).  A pair is an observation whose "point" is the other camera: the record, the closed-form elimination of
+// sigma, the freezing rule and the candidate are the observations' (gp_lin), with camera i in the camera's role and camera j in the
+// point's.  Pairs touch no landmark: sum M_m, sum w sigma^2 and the gradient parts are summed per camera over the incidence lists of
+// xm_pair_lists.h (thread per light camera, workgroup per heavy one) and enter U*_i, S_ii, b_i and the damping inside the camera pass;
+// the product adds -sum M_m p_other to the camera side (sum M_m p_i is in U*_i p_i) before <p, Ap> is taken.  Fixed centres: no camera pass and no PCG, dc = 0.
+struct GpPairsIn {
+    int constraint = XM_GP_ONLY_POINTS;
+    bool fix_centres = false;
+    int64_t npairs = 0;
+    const int32_t *pi = nullptr, *pj = nullptr;   // image_id1, image_id2
+    const double *trel = nullptr;                 // 3 npairs: translation of cam2_from_cam1
+    const uint8_t *valid = nullptr, *calibrated = nullptr;   // npairs (null: all valid); n (null: all calibrated)
+    double reweight_scale = 1.0;
+    double *sigma = nullptr;                      // out (may be null): npairs, -1 for a pair that takes no part
+    int64_t pairs_used = 0, cams_heavy = 0, max_incidences = 0;   // out
+    double weight_scale_pt = 1.0;                 // out
+};
+// the pairs' side of one linearisation for xm_ctx_gp_probe_pairs: per pair in input order, 0 (sigma1: -1) where it takes no part
+struct GpPairProbe {
+    const double *sigma_in = nullptr;             // npairs (null: all 1)
+    double cost = 0, gsmax = 0, cost1 = 0, model = 0, step2 = 0, x2 = 0;
+    double *Mp = nullptr, *qp = nullptr;          // npairs x 6, npairs x 3
+    int32_t *pfrozen = nullptr, *pused = nullptr;
+    double *dsigma = nullptr, *sigma1 = nullptr;
+};
+
 // rot: 3 x 3n column-major (R_i, camera-to-world, read only), t: 3 x n (centres), p: 3 x m (host, the start, updated in place); scales (may be
 // null): nobs in input order, -1 for an observation that is not used.  The SchurOp is only read.
 void global_positioning(const SchurOp &S, const GpSettings &cfg, const double *rot, double *t, double *p, double *scales, GpOutcome &out, hipStream_t st);
+// the same with camera-to-camera terms, per-camera weights of the observation terms or fixed centres; with XM_GP_ONLY_POINTS, no flag and
+// calibrated null it launches what global_positioning launches
+void global_positioning_pairs(const SchurOp &S, const GpSettings &cfg, GpPairsIn &pairs, const double *rot, double *t, double *p, double *scales,
+                              GpOutcome &out, hipStream_t st);
 // cfg: min_views, loss, loss_scale and watchdog_s are read.  The launches are those of global_positioning (one workspace class serves both).
 void gp_probe(const SchurOp &S, const GpSettings &cfg, const double *rot, const double *t, const double *p, GpProbe &q, hipStream_t st);
+// q is filled as by gp_probe from the observation terms (its gmax: over everything the loop's gradient test sees); the pairs' shares go to pq
+void gp_probe_pairs(const SchurOp &S, const GpSettings &cfg, GpPairsIn &pairs, const double *rot, const double *t, const double *p, GpProbe &q,
+                    GpPairProbe &pq, hipStream_t st);
 // out[0]: a landmark with more observations than this has a workgroup of its own; out[1]: observations a wavefront takes from a camera's
 // list in one pass; out[2]: threads of a heavy landmark's workgroup (host-only; the tests size their edge cases from them)
 void gp_limits(int64_t out[3]);
+// out[0]: a camera with more incidences (participating pair ends) than this has a workgroup of its own; out[1]: threads of that workgroup
+void gp_pair_limits(int64_t out[2]);
 
 }  // namespace xm

@@ -11,6 +11,7 @@
 #include "xm_device.h"
 #include "xm_lm_loop.h"
 #include "xm_lm_shared.h"
+#include "xm_pair_lists.h"
 #include "xm_schur.h"
 #include "xm_stage.h"
 
@@ -25,11 +26,15 @@ constexpr const char *kStage = "global positioning";
 // and the padding of the packed landmark lists, is 0 in every plane and adds nothing to any sum.
 constexpr int kGpPlanes = 8;
 enum { GA = 0, GU = 1, GQ = 4, GK = 7 };
+// per camera over its participating pairs: sum M_m (6, in tri() order), sum w sigma^2, the reduced gradient's part (3), the full gradient's (3)
+constexpr int kGpPairSums = 13;
 
 struct GpState {        // device-resident; the host reads it whole
     BaState b;          // the PCG's words and the scalars the bundle adjustment has too (step2 / x2: cameras, landmarks)
     double step2s, x2s; // |ds|^2 and |s|^2 over the used observations
     double gsmax;       // max |g_s| over the scales that are not frozen
+    // the pairs' shares (0 without pair terms): cost and max |g_sigma| at the current point; the candidate's cost, model, |d sigma|^2, |sigma|^2
+    double pcost, pgsmax, pcost_new, pmodel, pstep2, px2;
 };
 
 // what one observation contributes at (c_i, P_l, s_e): v = P - c, r = d - s v, w = rho'(|r|^2) (1 for the trivial loss), g_s = -w r.v, and
@@ -38,14 +43,16 @@ struct GpLin {
     double v[3], r[3], w, gs, hs;
     bool frozen;
 };
-template <int LOSS>
-__device__ __forceinline__ double gp_lin(const double *c, const double *P, const double *d, double s, double a, double mu, GpLin &o) {
+// AW: the loss is Ceres's ScaledLoss with the factor ae (rho and rho' times ae); without it ae is not read
+template <int LOSS, bool AW = false>
+__device__ __forceinline__ double gp_lin(const double *c, const double *P, const double *d, double s, double a, double mu, GpLin &o, double ae = 1.0) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) { o.v[k] = P[k] - c[k]; o.r[k] = d[k] - s * o.v[k]; }
     const double sq = o.r[0] * o.r[0] + o.r[1] * o.r[1] + o.r[2] * o.r[2];
     double rho = sq;
     o.w = 1.0;
     if constexpr (LOSS != XM_BA_LOSS_TRIVIAL) rho = ba_rho<LOSS>(sq, a, o.w);
+    if constexpr (AW) { rho *= ae; o.w *= ae; }
     o.gs = -o.w * (o.r[0] * o.v[0] + o.r[1] * o.v[1] + o.r[2] * o.v[2]);
     o.frozen = s <= kGpMinScale && o.gs > 0.0;
     const double h = o.w * (o.v[0] * o.v[0] + o.v[1] * o.v[1] + o.v[2] * o.v[2]);
@@ -103,11 +110,11 @@ __global__ __launch_bounds__(256) void gp_cam_count_kernel(SchurLists S, const d
 
 // ---- the records at (c, P, s) for the damping mu, written in both list orders; partial sums of the cost 1/2 sum rho(|r|^2) and of the
 // used observations, per-workgroup max of |g_s|
-template <int LOSS>
+template <int LOSS, bool AW>
 __global__ __launch_bounds__(256) void gp_eval_kernel(SchurLists S, const int32_t *__restrict__ oused, const double *__restrict__ dir,
                                                       const double *__restrict__ C, const double *__restrict__ P, const double *__restrict__ sc, double a,
-                                                      double mu, double *__restrict__ Jc, double *__restrict__ Jl, int32_t *__restrict__ frozen,
-                                                      double *__restrict__ parts) {
+                                                      double mu, const double *__restrict__ cam_a, double *__restrict__ Jc, double *__restrict__ Jl,
+                                                      int32_t *__restrict__ frozen, double *__restrict__ parts) {
     __shared__ double sh[4];
     __shared__ double shm[4];
     double cost = 0.0, used = 0.0, gsm = 0.0;
@@ -119,7 +126,8 @@ __global__ __launch_bounds__(256) void gp_eval_kernel(SchurLists S, const int32_
         if (oused[e]) {
             GpLin o;
             const double s = sc[e];
-            cost += 0.5 * gp_lin<LOSS>(C + (size_t)3 * S.obs_cam[e], P + (size_t)3 * S.obs_lm[e], dir + (size_t)3 * e, s, a, mu, o);
+            cost += 0.5 * gp_lin<LOSS, AW>(C + (size_t)3 * S.obs_cam[e], P + (size_t)3 * S.obs_lm[e], dir + (size_t)3 * e, s, a, mu, o,
+                                           AW ? cam_a[S.obs_cam[e]] : 1.0);
             const double ws = o.w * s;
             v[GA] = ws * s;
             if (o.frozen) {
@@ -211,9 +219,13 @@ __device__ __forceinline__ void gp_load(const double *J, size_t stride, int64_t 
 
 // ---- camera pass (a wavefront per camera): U*_i; S_ii = U*_i - sum_l (sum_e M_e) V*_l^-1 (sum_f M_f) over the observations e, f of (i, l)
 // and its inverse; b_i = -sum q_e - sum M_e V*_l^-1 g_l (W_e = -M_e); per-workgroup max of the FULL gradient's camera part
+// PAIRS: the camera's sums over its pairs (gp_pair_cam_kernel: psum) join U_i, the damped diagonal, the gradient parts and so S_ii^-1, b_i and
+// the gradient's max; obs_on = 0 (no observation terms): the observation list is not walked
+template <bool PAIRS>
 __global__ __launch_bounds__(256) void gp_cam_kernel(SchurLists S, const double *__restrict__ Jc, const double *__restrict__ vinv,
-                                                     const double *__restrict__ gl, double mu, double *__restrict__ ustar, double *__restrict__ sinv,
-                                                     double *__restrict__ b, double *__restrict__ gpart) {
+                                                     const double *__restrict__ gl, double mu, const double *__restrict__ psum, int obs_on,
+                                                     double *__restrict__ ustar, double *__restrict__ sinv, double *__restrict__ b,
+                                                     double *__restrict__ gpart) {
     constexpr int NU = 6, NA = 2 * NU + 10;   // U, the landmarks' term, sum q (3), sum M V^-1 g (3), the full gradient (3), sum a
     __shared__ double red[kQwWaves];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -222,7 +234,7 @@ __global__ __launch_bounds__(256) void gp_cam_kernel(SchurLists S, const double 
     double acc[NA];
 #pragma unroll
     for (int k = 0; k < NA; ++k) acc[k] = 0.0;
-    if (on)
+    if (on && (!PAIRS || obs_on))
         for (int64_t e = S.cam_ptr[cam] + lane; e < S.cam_ptr[cam + 1]; e += 64) {
             double v[kGpPlanes], M[3][3], V[3][3], MV[3][3];
             gp_load(Jc, (size_t)S.nobs, e, v);
@@ -266,6 +278,14 @@ __global__ __launch_bounds__(256) void gp_cam_kernel(SchurLists S, const double 
     double gabs = 0.0;
     if (on && lane == 0) {
         double Us[3][3], Sm[3][3];
+        if constexpr (PAIRS) {
+            const double *ps = psum + (size_t)kGpPairSums * cam;
+#pragma unroll
+            for (int k = 0; k < NU; ++k) acc[k] += ps[k];
+            acc[NA - 1] += ps[6];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { acc[2 * NU + k] += ps[7 + k]; acc[2 * NU + 6 + k] += ps[10 + k]; }
+        }
         const double dmp = mu * clamp_diag(acc[NA - 1]);
 #pragma unroll
         for (int j = 0; j < 3; ++j)
@@ -324,14 +344,17 @@ __global__ __launch_bounds__(kBaHeavyThreads) void gp_lmx_kernel(SchurLists S, c
     for (int c = 0; c < 3; ++c) y[3 * l + c] = sgn * (V[c][0] * acc[0] + V[c][1] * acc[1] + V[c][2] * acc[2]);
 }
 // camera side: Ap_i = U*_i p_i - sum_{obs of i} W_e y_l = U*_i p_i + sum M_e y_l (a wavefront per camera); per-workgroup partials of <p, Ap>
-__global__ __launch_bounds__(256) void gp_camx_kernel(SchurLists S, const double *__restrict__ Jc, const double *__restrict__ y, BaPcg a) {
+// PAIRS: plus the pairs' off-diagonal part yp_i = -sum M_m p_other (gp_pairx_kernel), added before <p, Ap> is taken
+template <bool PAIRS>
+__global__ __launch_bounds__(256) void gp_camx_kernel(SchurLists S, const double *__restrict__ Jc, const double *__restrict__ y,
+                                                      const double *__restrict__ yp, int obs_on, BaPcg a) {
     __shared__ double red[kQwWaves];
     if (a.st->done) return;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t cam = (int64_t)blockIdx.x * kQwWaves + wv;
     const bool on = cam < S.n;
     double acc[3] = {0.0, 0.0, 0.0};
-    if (on)
+    if (on && (!PAIRS || obs_on))
         for (int64_t e = S.cam_ptr[cam] + lane; e < S.cam_ptr[cam + 1]; e += 64) {
             const double av = Jc[(size_t)GA * S.nobs + e], u0 = Jc[(size_t)GU * S.nobs + e], u1 = Jc[(size_t)(GU + 1) * S.nobs + e],
                          u2 = Jc[(size_t)(GU + 2) * S.nobs + e];
@@ -347,7 +370,8 @@ __global__ __launch_bounds__(256) void gp_camx_kernel(SchurLists S, const double
         block_matvec<3>(a.ustar + (size_t)9 * cam, a.p + (size_t)3 * cam, up);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const double v = up[k] + acc[k];
+            double v = up[k] + acc[k];
+            if constexpr (PAIRS) v += yp[3 * cam + k];
             a.Ap[3 * cam + k] = v;
             pap += a.p[3 * cam + k] * v;
         }
@@ -366,12 +390,12 @@ __global__ __launch_bounds__(256) void gp_camx_kernel(SchurLists S, const double
 // scales: ds_e = -(g_s - w s v.(dc - dP)) / h* (0 for a frozen one) from the linearisation at the current point (the eval kernel's
 // expression), s <- max(s + ds, 1e-5); the cost 1/2 sum rho(|r|^2) at the candidate, the linear model's terms sum r.(J d) + |J d|^2 / 2 with
 // J d = sqrt(w) (s (dc - dP) - v ds), and partials of |ds|^2 and |s|^2
-template <int LOSS>
+template <int LOSS, bool AW>
 __global__ __launch_bounds__(256) void gp_cand_obs_kernel(SchurLists S, const int32_t *__restrict__ oused, const double *__restrict__ dir,
                                                           const double *__restrict__ C, const double *__restrict__ P, const double *__restrict__ sc,
                                                           const double *__restrict__ dc, const double *__restrict__ dP, const double *__restrict__ Cn,
-                                                          const double *__restrict__ Pn, double a, double mu, double *__restrict__ sn,
-                                                          double *__restrict__ dsv, double *__restrict__ parts) {
+                                                          const double *__restrict__ Pn, double a, double mu, const double *__restrict__ cam_a,
+                                                          double *__restrict__ sn, double *__restrict__ dsv, double *__restrict__ parts) {
     __shared__ double sh[4];
     double cost = 0.0, model = 0.0, s2 = 0.0, x2 = 0.0;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < S.nobs; e += (int64_t)gridDim.x * 256) {
@@ -380,7 +404,8 @@ __global__ __launch_bounds__(256) void gp_cand_obs_kernel(SchurLists S, const in
         if (oused[e]) {
             const int64_t i = S.obs_cam[e], l = S.obs_lm[e];
             GpLin o;
-            (void)gp_lin<LOSS>(C + 3 * i, P + 3 * l, dir + (size_t)3 * e, s, a, mu, o);
+            const double ae = AW ? cam_a[i] : 1.0;
+            (void)gp_lin<LOSS, AW>(C + 3 * i, P + 3 * l, dir + (size_t)3 * e, s, a, mu, o, ae);
             double dd[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) dd[k] = dc[3 * i + k] - dP[3 * l + k];
@@ -395,11 +420,168 @@ __global__ __launch_bounds__(256) void gp_cand_obs_kernel(SchurLists S, const in
             }
             model += o.w * (rj + 0.5 * jj);
             GpLin o1;
-            cost += 0.5 * gp_lin<LOSS>(Cn + 3 * i, Pn + 3 * l, dir + (size_t)3 * e, s1, a, mu, o1);
+            cost += 0.5 * gp_lin<LOSS, AW>(Cn + 3 * i, Pn + 3 * l, dir + (size_t)3 * e, s1, a, mu, o1, ae);
             s2 += ds * ds; x2 += s * s;
         }
         sn[e] = s1;
         dsv[e] = ds;
+    }
+    cost = block_sum256(cost, sh);
+    model = block_sum256(model, sh);
+    s2 = block_sum256(s2, sh);
+    x2 = block_sum256(x2, sh);
+    if (threadIdx.x == 0) {
+        const size_t g = gridDim.x;
+        parts[blockIdx.x] = cost; parts[g + blockIdx.x] = model; parts[2 * g + blockIdx.x] = s2; parts[3 * g + blockIdx.x] = x2;
+    }
+}
+
+// ---- camera-to-camera terms (design: xm_gp.h).  The M participating pairs in input order; a pair is an observation of camera ci whose
+// point is camera cj and whose direction is tau, so gp_lin, the record's eight planes (stride M) and the candidate's expressions are the
+// observations'.
+struct GpPairs {
+    int64_t M;
+    const int32_t *ci, *cj;
+    const double *tau;   // 3 per pair
+};
+// once per call: tau_m = -R_j trel_m
+__global__ __launch_bounds__(256) void gp_pair_setup_kernel(int64_t M, const int32_t *__restrict__ cj, const double *__restrict__ rot,
+                                                            const double *__restrict__ trel, double *__restrict__ tau) {
+    for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < M; m += (int64_t)gridDim.x * 256) {
+        const double *R = rot + (size_t)9 * cj[m];   // column-major: R[a + 3 c]
+        const double t0 = trel[3 * m], t1 = trel[3 * m + 1], t2 = trel[3 * m + 2];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) tau[3 * m + a] = -(R[a] * t0 + R[3 + a] * t1 + R[6 + a] * t2);
+    }
+}
+// cused |= the camera has a participating pair
+__global__ __launch_bounds__(256) void gp_pair_used_kernel(int n, const int64_t *__restrict__ ptr, int32_t *__restrict__ cused) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+        if (ptr[i + 1] > ptr[i]) cused[i] = 1;
+}
+// the records at (c, sigma) for the damping mu (a thread per pair); per-workgroup partials of the cost and of max |g_sigma|
+template <int LOSS>
+__global__ __launch_bounds__(256) void gp_pair_eval_kernel(GpPairs Q, const double *__restrict__ C, const double *__restrict__ sg, double a, double mu,
+                                                           double *__restrict__ rec, int32_t *__restrict__ pfrozen, double *__restrict__ parts) {
+    __shared__ double sh[4];
+    __shared__ double shm[4];
+    double cost = 0.0, gsm = 0.0;
+    for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < Q.M; m += (int64_t)gridDim.x * 256) {
+        double v[kGpPlanes];
+#pragma unroll
+        for (int k = 0; k < kGpPlanes; ++k) v[k] = 0.0;
+        GpLin o;
+        const double s = sg[m];
+        cost += 0.5 * gp_lin<LOSS>(C + (size_t)3 * Q.ci[m], C + (size_t)3 * Q.cj[m], Q.tau + (size_t)3 * m, s, a, mu, o);
+        const double ws = o.w * s;
+        v[GA] = ws * s;
+        if (o.frozen) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[GQ + k] = ws * o.r[k];
+        } else {
+            const double ih = 1.0 / sqrt(o.hs);
+            v[GK] = o.gs * ih;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                v[GU + k] = ws * ih * o.v[k];
+                v[GQ + k] = ws * o.r[k] + v[GU + k] * v[GK];
+            }
+            gsm = fmax(gsm, fabs(o.gs));
+        }
+#pragma unroll
+        for (int k = 0; k < kGpPlanes; ++k) rec[(size_t)k * Q.M + m] = v[k];
+        pfrozen[m] = o.frozen ? 1 : 0;
+    }
+    cost = block_sum256(cost, sh);
+    const double mx = block_max<256>(gsm, shm);
+    if (threadIdx.x == 0) { parts[blockIdx.x] = cost; parts[gridDim.x + blockIdx.x] = mx; }
+}
+// per camera over its incidence list, in list order: kGpPairSums values (side 0: the camera is the pair's ci and takes +q, side 1: its cj, -q)
+__global__ __launch_bounds__(kPairListThreads) void gp_pair_cam_kernel(PairLists L, int64_t M, const double *__restrict__ rec, double *__restrict__ psum) {
+    __shared__ double part[kPairListThreads / 64][10];
+    __shared__ double part3[kPairListThreads / 64][3];
+    const PairWalk k = pair_walk(L);
+    double acc[10], gf[3] = {0.0, 0.0, 0.0};   // M (6), sum a, the reduced gradient's part (3); the full gradient's part
+#pragma unroll
+    for (int c = 0; c < 10; ++c) acc[c] = 0.0;
+    for (int64_t e = k.e; e < k.e_end; e += k.step) {
+        const int64_t m = L.pair[e];
+        const double sg = L.side[e] == 0 ? 1.0 : -1.0;
+        double v[kGpPlanes];
+        gp_load(rec, (size_t)M, m, v);
+        acc[0] += v[GA] - v[GU] * v[GU]; acc[1] -= v[GU] * v[GU + 1]; acc[2] += v[GA] - v[GU + 1] * v[GU + 1];
+        acc[3] -= v[GU] * v[GU + 2]; acc[4] -= v[GU + 1] * v[GU + 2]; acc[5] += v[GA] - v[GU + 2] * v[GU + 2];
+        acc[6] += v[GA];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { acc[7 + c] += sg * v[GQ + c]; gf[c] += sg * (v[GQ + c] - v[GK] * v[GU + c]); }
+    }
+    if (k.heavy) {   // two reductions, as gp_lm_kernel: fewer wavefront sums in flight
+        pair_heavy_sum<3>(gf, part3);
+        pair_heavy_sum<10>(acc, part);
+    }
+    if (k.u >= 0 && (!k.heavy || threadIdx.x == 0)) {
+        double *ps = psum + (size_t)kGpPairSums * k.u;
+#pragma unroll
+        for (int c = 0; c < 10; ++c) ps[c] = acc[c];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ps[10 + c] = gf[c];
+    }
+}
+// the pairs' off-diagonal part of S x: yp_i = -sum M_m x_other over the camera's incidence list, gathering the other camera's x (the
+// diagonal part sum M_m x_i is in U*_i)
+__global__ __launch_bounds__(kPairListThreads) void gp_pairx_kernel(PairLists L, GpPairs Q, const double *__restrict__ rec, const double *__restrict__ x,
+                                                                    const BaState *__restrict__ st, double *__restrict__ yp) {
+    __shared__ double part[kPairListThreads / 64][3];
+    if (st != nullptr && st->done) return;
+    const PairWalk k = pair_walk(L);
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int64_t e = k.e; e < k.e_end; e += k.step) {
+        const int64_t m = L.pair[e];
+        const size_t o = 3 * (size_t)(L.side[e] == 0 ? Q.cj[m] : Q.ci[m]);
+        const double av = rec[(size_t)GA * Q.M + m], u0 = rec[(size_t)GU * Q.M + m], u1 = rec[(size_t)(GU + 1) * Q.M + m],
+                     u2 = rec[(size_t)(GU + 2) * Q.M + m];
+        const double d0 = x[o], d1 = x[o + 1], d2 = x[o + 2];
+        const double ud = u0 * d0 + u1 * d1 + u2 * d2;
+        acc[0] -= av * d0 - u0 * ud; acc[1] -= av * d1 - u1 * ud; acc[2] -= av * d2 - u2 * ud;
+    }
+    if (k.heavy) pair_heavy_sum<3>(acc, part);
+    if (k.u >= 0 && (!k.heavy || threadIdx.x == 0)) {
+        const size_t o = 3 * (size_t)k.u;
+        yp[o] = acc[0]; yp[o + 1] = acc[1]; yp[o + 2] = acc[2];
+    }
+}
+// candidate: d sigma_m = -(g_sigma - w sigma v.(dc_i - dc_j)) / h* (0 for a frozen one), sigma <- max(sigma + d sigma, 1e-5); the pairs'
+// cost at the candidate, model terms, |d sigma|^2 and |sigma|^2 (gp_cand_obs_kernel with camera j in the point's place)
+template <int LOSS>
+__global__ __launch_bounds__(256) void gp_cand_pair_kernel(GpPairs Q, const double *__restrict__ C, const double *__restrict__ sg,
+                                                           const double *__restrict__ dc, const double *__restrict__ Cn, double a, double mu,
+                                                           double *__restrict__ sgn, double *__restrict__ dsg, double *__restrict__ parts) {
+    __shared__ double sh[4];
+    double cost = 0.0, model = 0.0, s2 = 0.0, x2 = 0.0;
+    for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < Q.M; m += (int64_t)gridDim.x * 256) {
+        const double s = sg[m];
+        const int64_t i = Q.ci[m], j = Q.cj[m];
+        GpLin o;
+        (void)gp_lin<LOSS>(C + 3 * i, C + 3 * j, Q.tau + (size_t)3 * m, s, a, mu, o);
+        double dd[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dd[k] = dc[3 * i + k] - dc[3 * j + k];
+        const double vd = o.v[0] * dd[0] + o.v[1] * dd[1] + o.v[2] * dd[2];
+        double ds = 0.0;
+        if (!o.frozen) ds = -(o.gs - o.w * s * vd) / o.hs;
+        const double s1 = fmax(s + ds, kGpMinScale);
+        double rj = 0.0, jj = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double jd = s * dd[k] - o.v[k] * ds;
+            rj += o.r[k] * jd; jj += jd * jd;
+        }
+        model += o.w * (rj + 0.5 * jj);
+        GpLin o1;
+        cost += 0.5 * gp_lin<LOSS>(Cn + 3 * i, Cn + 3 * j, Q.tau + (size_t)3 * m, s1, a, mu, o1);
+        s2 += ds * ds; x2 += s * s;
+        sgn[m] = s1;
+        dsg[m] = ds;
     }
     cost = block_sum256(cost, sh);
     model = block_sum256(model, sh);
@@ -431,11 +613,66 @@ struct GpWork {
     const dim3 b256{256}, blm{kBaHeavyThreads};
     int cur = 0;
     BaPcg a;
+    // which terms (xm_gp.h): observation terms, pair terms, fixed centres, weighted observation terms.  Without pairs_in: observations only
+    bool has_obs = true, has_pairs = false, fix = false, aw = false;
+    std::vector<int32_t> plist;   // the participating pairs' input indices
+    int64_t M = 0;
+    PairListsDev lists;
+    DevBuf<int32_t> ci, cj, pfrozen;
+    DevBuf<double> trel, tau, prec, psum, yp, Sg[2], dsg, cam_a;
+    GpPairs Q{};
+    int gp = 1;
+    size_t o_pe = 0, o_pc = 0;
 
-    GpWork(const SchurOp &SO_, const GpSettings &cfg_, const double *rot_h, const double *t, const double *p, const double *s0, hipStream_t st_)
+    // the pair terms' host side: which pairs take part, the incidence lists, the weights a_e per camera; fills the outputs of pin
+    void setup_pairs(GpPairsIn &pin, const double *sigma0) {
+        has_obs = pin.constraint != XM_GP_ONLY_CAMERAS;
+        has_pairs = pin.constraint != XM_GP_ONLY_POINTS;
+        fix = pin.fix_centres;
+        pin.pairs_used = pin.cams_heavy = pin.max_incidences = 0;
+        pin.weight_scale_pt = 1.0;
+        if (has_pairs) {
+            std::vector<int32_t> ua, ub;
+            std::vector<double> ht, hs;
+            for (int64_t k = 0; k < pin.npairs; ++k) {
+                if (pin.valid && !pin.valid[k]) continue;
+                plist.push_back((int32_t)k); ua.push_back(pin.pi[k]); ub.push_back(pin.pj[k]);
+                for (int c = 0; c < 3; ++c) ht.push_back(pin.trel[3 * k + c]);
+                hs.push_back(sigma0 ? sigma0[k] : 1.0);
+            }
+            M = (int64_t)plist.size();
+            if (M < 1) throw Error(XM_ERR_ARG, "xm_ctx_global_positioning_pairs: the constraint type has pair terms but no pair takes part");
+            const PairListsHost h = build_pair_lists((int)n, ua, ub, kPairListLight, false);
+            lists.upload_from(h, (int)n, st);
+            upload(ci, ua.data(), (size_t)M, st); upload(cj, ub.data(), (size_t)M, st); upload(trel, ht.data(), ht.size(), st);
+            upload(Sg[0], hs.data(), (size_t)M, st);
+            wait_stream(st, cfg.watchdog_s, kStage, "the pair lists");   // the host vectors above end with this scope
+            Sg[1].alloc((size_t)M); dsg.alloc((size_t)M); pfrozen.alloc((size_t)M); tau.alloc((size_t)3 * M);
+            prec.alloc((size_t)kGpPlanes * M); psum.alloc((size_t)kGpPairSums * n); yp.alloc((size_t)3 * n);
+            Q.M = M; Q.ci = ci.p; Q.cj = cj.p; Q.tau = tau.p;
+            gp = flat_grid(M);
+            pin.pairs_used = M; pin.cams_heavy = h.nheavy; pin.max_incidences = h.max_inc;
+            if (pin.constraint == XM_GP_POINTS_AND_CAMERAS_BALANCED) pin.weight_scale_pt = pin.reweight_scale * (double)M / (double)m;
+        }
+        if (has_obs) {
+            std::vector<double> ha((size_t)n, pin.weight_scale_pt);
+            aw = pin.weight_scale_pt != 1.0;
+            if (pin.calibrated)
+                for (int64_t i = 0; i < n; ++i)
+                    if (!pin.calibrated[i]) { ha[(size_t)i] = 0.5 * pin.weight_scale_pt; aw = true; }
+            if (aw) {
+                upload(cam_a, ha.data(), (size_t)n, st);
+                wait_stream(st, cfg.watchdog_s, kStage, "the observation weights");
+            }
+        }
+    }
+
+    GpWork(const SchurOp &SO_, const GpSettings &cfg_, const double *rot_h, const double *t, const double *p, const double *s0, hipStream_t st_,
+           GpPairsIn *pin = nullptr, const double *sigma0 = nullptr)
         : SO(SO_), cfg(cfg_), st(st_), S(SO_.lists()), n(S.n), m(S.m), nobs(S.nobs) {
         if (n < 1 || m < 1 || nobs < 1)   // no launch below has an empty grid
             throw Error(XM_ERR_ARG, "xm_ctx_global_positioning: the context holds no camera, landmark or observation");
+        if (pin) setup_pairs(*pin, sigma0);
         const std::vector<int32_t> &slot_of = SO.slot_of();
         std::vector<double> hP((size_t)3 * m), hS((size_t)std::max<int64_t>(nobs, 1), 1.0);
         for (int64_t l = 0; l < m; ++l)
@@ -445,6 +682,7 @@ struct GpWork {
         rot.alloc((size_t)9 * n, false);
         XM_HIP_CHECK(hipMemcpyAsync(rot.p, rot_h, (size_t)9 * n * sizeof(double), hipMemcpyHostToDevice, st));
         XM_HIP_CHECK(hipMemcpyAsync(C[0].p, t, (size_t)3 * n * sizeof(double), hipMemcpyHostToDevice, st));
+        if (fix) XM_HIP_CHECK(hipMemcpyAsync(C[1].p, t, (size_t)3 * n * sizeof(double), hipMemcpyHostToDevice, st));   // no launch writes a centre
         XM_HIP_CHECK(hipMemcpyAsync(P[0].p, hP.data(), hP.size() * sizeof(double), hipMemcpyHostToDevice, st));
         XM_HIP_CHECK(hipMemcpyAsync(Sc[0].p, hS.data(), hS.size() * sizeof(double), hipMemcpyHostToDevice, st));
         // workspace (zero: the padding of the packed landmark lists stays 0 in every plane and in the flags)
@@ -460,31 +698,59 @@ struct GpWork {
         // partials: eval (3 ge) | gmax (glm + gcam) | PCG (4 gfc + gcam) | candidate step / |x| (cameras then landmarks, 2 x (gfc + gfl)) | cost (4 ge)
         o_eval = 0; o_gmax = o_eval + 3 * (size_t)ge; o_pcg = o_gmax + glm + gcam; o_cand = o_pcg + 4 * (size_t)gfc + gcam;
         o_cost = o_cand + 2 * ((size_t)gfc + gfl);
-        parts.alloc(o_cost + 4 * (size_t)ge);
+        // behind them, with pair terms: the pairs' eval (2 gp) | the pairs' candidate (4 gp)
+        o_pe = o_cost + 4 * (size_t)ge; o_pc = o_pe + (has_pairs ? 2 * (size_t)gp : 0);
+        parts.alloc(o_pc + (has_pairs ? 4 * (size_t)gp : 0));
         pp = parts.p;
         a.n = n; a.grid = gfc; a.cgrid = gcam; a.tol2 = cfg.eta * cfg.eta;
         a.b = b.p; a.sinv = sinv.p; a.ustar = ustar.p; a.x = x.p; a.r = r.p; a.z = z.p; a.p = pv.p; a.Ap = Ap.p;
         a.lay_partials(pp + o_pcg);
         a.st = &dst->b;
-        // which observations, landmarks and cameras take part: fixed for the call
-        hipLaunchKernelGGL(gp_setup_kernel, dim3(ge), b256, 0, st, S, (const double *)rot.p, dir.p, lflag.p);
-        hipLaunchKernelGGL(gp_lm_count_kernel, dim3(glm), blm, 0, st, S, (const double *)lflag.p, (double)std::max(cfg.min_views, 1), lm_ok.p);
-        hipLaunchKernelGGL(gp_used_kernel, dim3(ge), b256, 0, st, S, (const int32_t *)lm_ok.p, oused.p, cflag.p, lflag.p);
-        hipLaunchKernelGGL(gp_lm_count_kernel, dim3(glm), blm, 0, st, S, (const double *)lflag.p, 1.0, lused.p);
-        hipLaunchKernelGGL(gp_cam_count_kernel, dim3(gcam), b256, 0, st, S, (const double *)cflag.p, cused.p);
+        // which observations, landmarks and cameras take part: fixed for the call (without observation terms every flag stays 0)
+        if (has_obs) {
+            hipLaunchKernelGGL(gp_setup_kernel, dim3(ge), b256, 0, st, S, (const double *)rot.p, dir.p, lflag.p);
+            hipLaunchKernelGGL(gp_lm_count_kernel, dim3(glm), blm, 0, st, S, (const double *)lflag.p, (double)std::max(cfg.min_views, 1), lm_ok.p);
+            hipLaunchKernelGGL(gp_used_kernel, dim3(ge), b256, 0, st, S, (const int32_t *)lm_ok.p, oused.p, cflag.p, lflag.p);
+            hipLaunchKernelGGL(gp_lm_count_kernel, dim3(glm), blm, 0, st, S, (const double *)lflag.p, 1.0, lused.p);
+            hipLaunchKernelGGL(gp_cam_count_kernel, dim3(gcam), b256, 0, st, S, (const double *)cflag.p, cused.p);
+        }
+        if (has_pairs) {
+            hipLaunchKernelGGL(gp_pair_setup_kernel, dim3(gp), b256, 0, st, M, (const int32_t *)cj.p, (const double *)rot.p, (const double *)trel.p, tau.p);
+            hipLaunchKernelGGL(gp_pair_used_kernel, dim3(gfc), b256, 0, st, (int)n, (const int64_t *)lists.ptr.p, cused.p);
+        }
         check_launch("the used observations");
     }
     void reduce(BaReduce rd) { hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), b256, 0, st, rd); }
     GpState read_state(const char *what) { return xm::read_state(dst, hs, st, cfg.watchdog_s, kStage, what); }
     // the records, the landmark pass and the camera pass at the current point for the damping mu; cost, used and |J^T r|_inf to the state word
     void linearise(double mu) {
-        with_loss(cfg.loss, [&](auto L) {
-            hipLaunchKernelGGL((gp_eval_kernel<L.value>), dim3(ge), b256, 0, st, S, (const int32_t *)oused.p, (const double *)dir.p, (const double *)C[cur].p,
-                               (const double *)P[cur].p, (const double *)Sc[cur].p, cfg.loss_scale, mu, Jc.p, Jl.p, frozen.p, pp + o_eval);
-        });
-        hipLaunchKernelGGL(gp_lm_kernel, dim3(glm), blm, 0, st, S, (const double *)Jl.p, mu, vinv.p, gl.p, pp + o_gmax);
-        hipLaunchKernelGGL(gp_cam_kernel, dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)vinv.p, (const double *)gl.p, mu, ustar.p,
-                           sinv.p, b.p, pp + o_gmax + glm);
+        if (has_obs) {
+            with_loss(cfg.loss, [&](auto L) {
+                auto launch = [&](auto AW) {
+                    hipLaunchKernelGGL((gp_eval_kernel<decltype(L)::value, decltype(AW)::value>), dim3(ge), b256, 0, st, S, (const int32_t *)oused.p, (const double *)dir.p,
+                                       (const double *)C[cur].p, (const double *)P[cur].p, (const double *)Sc[cur].p, cfg.loss_scale, mu,
+                                       (const double *)cam_a.p, Jc.p, Jl.p, frozen.p, pp + o_eval);
+                };
+                if (aw) launch(std::true_type{}); else launch(std::false_type{});
+            });
+            hipLaunchKernelGGL(gp_lm_kernel, dim3(glm), blm, 0, st, S, (const double *)Jl.p, mu, vinv.p, gl.p, pp + o_gmax);
+        }
+        if (has_pairs) {   // the pairs' records and the per-camera sums the camera pass reads
+            with_loss(cfg.loss, [&](auto L) {
+                hipLaunchKernelGGL((gp_pair_eval_kernel<L.value>), dim3(gp), b256, 0, st, Q, (const double *)C[cur].p, (const double *)Sg[cur].p,
+                                   cfg.loss_scale, mu, prec.p, pfrozen.p, pp + o_pe);
+            });
+            hipLaunchKernelGGL(gp_pair_cam_kernel, dim3(lists.grid), dim3(kPairListThreads), 0, st, lists.L, M, (const double *)prec.p, psum.p);
+            hipLaunchKernelGGL(gp_cam_kernel<true>, dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)vinv.p, (const double *)gl.p, mu,
+                               (const double *)psum.p, has_obs ? 1 : 0, ustar.p, sinv.p, b.p, pp + o_gmax + glm);
+            BaReduce rp{};
+            rp.sum_p[0] = pp + o_pe; rp.sum_n[0] = gp; rp.sum_out[0] = &dst->pcost;
+            rp.max_p = pp + o_pe + gp; rp.max_n = gp; rp.max_out = &dst->pgsmax;
+            reduce(rp);
+        } else if (!fix) {
+            hipLaunchKernelGGL(gp_cam_kernel<false>, dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)vinv.p, (const double *)gl.p, mu,
+                               (const double *)nullptr, 1, ustar.p, sinv.p, b.p, pp + o_gmax + glm);
+        }
         BaReduce rd{};
         rd.sum_p[0] = pp + o_eval; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->b.cost;
         rd.sum_p[1] = pp + o_eval + ge; rd.sum_n[1] = ge; rd.sum_out[1] = &dst->b.used;
@@ -496,23 +762,50 @@ struct GpWork {
     }
     // ar.Ap = S ar.p through the two lists (gate: the state word whose done flag skips the landmark side, or null)
     void sx(const BaPcg &ar, const BaState *gate) {
-        hipLaunchKernelGGL(gp_lmx_kernel, dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)nullptr, 1.0,
-                           (const int32_t *)lused.p, (const double *)ar.p, gate, y.p);
-        hipLaunchKernelGGL(gp_camx_kernel, dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)y.p, ar);
+        if (has_obs)
+            hipLaunchKernelGGL(gp_lmx_kernel, dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)nullptr, 1.0,
+                               (const int32_t *)lused.p, (const double *)ar.p, gate, y.p);
+        if (has_pairs) {
+            hipLaunchKernelGGL(gp_pairx_kernel, dim3(lists.grid), dim3(kPairListThreads), 0, st, lists.L, Q, (const double *)prec.p, (const double *)ar.p,
+                               gate, yp.p);
+            hipLaunchKernelGGL(gp_camx_kernel<true>, dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)y.p, (const double *)yp.p,
+                               has_obs ? 1 : 0, ar);
+        } else {
+            hipLaunchKernelGGL(gp_camx_kernel<false>, dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)y.p, (const double *)nullptr, 1, ar);
+        }
     }
     // back-substitution, candidate (the other parameter set), its cost and the model decrease; the scalars to the state word
     void candidate(double mu, const double *dc) {
         const int nx = cur ^ 1;
-        hipLaunchKernelGGL(gp_lmx_kernel, dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)gl.p, -1.0,
-                           (const int32_t *)lused.p, dc, (const BaState *)nullptr, dP.p);
-        hipLaunchKernelGGL(ba_cand_vec_kernel<3>, dim3(gfc), b256, 0, st, n, (const double *)C[cur].p, dc, (const int32_t *)cused.p, C[nx].p, pp + o_cand);
-        hipLaunchKernelGGL(ba_cand_vec_kernel<3>, dim3(gfl), b256, 0, st, m, (const double *)P[cur].p, (const double *)dP.p, (const int32_t *)lused.p, P[nx].p,
-                           pp + o_cand + 2 * (size_t)gfc);
-        with_loss(cfg.loss, [&](auto L) {
-            hipLaunchKernelGGL((gp_cand_obs_kernel<L.value>), dim3(ge), b256, 0, st, S, (const int32_t *)oused.p, (const double *)dir.p,
-                               (const double *)C[cur].p, (const double *)P[cur].p, (const double *)Sc[cur].p, dc, (const double *)dP.p,
-                               (const double *)C[nx].p, (const double *)P[nx].p, cfg.loss_scale, mu, Sc[nx].p, ds.p, pp + o_cost);
-        });
+        // fixed centres: dc is the zero vector, no centre is written (both sets hold the caller's) and the cameras' partials stay 0
+        if (has_obs)
+            hipLaunchKernelGGL(gp_lmx_kernel, dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)gl.p, -1.0,
+                               (const int32_t *)lused.p, dc, (const BaState *)nullptr, dP.p);
+        if (!fix)
+            hipLaunchKernelGGL(ba_cand_vec_kernel<3>, dim3(gfc), b256, 0, st, n, (const double *)C[cur].p, dc, (const int32_t *)cused.p, C[nx].p, pp + o_cand);
+        if (has_obs) {
+            hipLaunchKernelGGL(ba_cand_vec_kernel<3>, dim3(gfl), b256, 0, st, m, (const double *)P[cur].p, (const double *)dP.p, (const int32_t *)lused.p,
+                               P[nx].p, pp + o_cand + 2 * (size_t)gfc);
+            with_loss(cfg.loss, [&](auto L) {
+                auto launch = [&](auto AW) {
+                    hipLaunchKernelGGL((gp_cand_obs_kernel<decltype(L)::value, decltype(AW)::value>), dim3(ge), b256, 0, st, S, (const int32_t *)oused.p, (const double *)dir.p,
+                                       (const double *)C[cur].p, (const double *)P[cur].p, (const double *)Sc[cur].p, dc, (const double *)dP.p,
+                                       (const double *)C[nx].p, (const double *)P[nx].p, cfg.loss_scale, mu, (const double *)cam_a.p, Sc[nx].p, ds.p,
+                                       pp + o_cost);
+                };
+                if (aw) launch(std::true_type{}); else launch(std::false_type{});
+            });
+        }
+        if (has_pairs) {
+            with_loss(cfg.loss, [&](auto L) {
+                hipLaunchKernelGGL((gp_cand_pair_kernel<L.value>), dim3(gp), b256, 0, st, Q, (const double *)C[cur].p, (const double *)Sg[cur].p, dc,
+                                   (const double *)C[nx].p, cfg.loss_scale, mu, Sg[nx].p, dsg.p, pp + o_pc);
+            });
+            BaReduce rp{};
+            for (int k = 0; k < 4; ++k) { rp.sum_p[k] = pp + o_pc + (size_t)k * gp; rp.sum_n[k] = gp; }
+            rp.sum_out[0] = &dst->pcost_new; rp.sum_out[1] = &dst->pmodel; rp.sum_out[2] = &dst->pstep2; rp.sum_out[3] = &dst->px2;
+            reduce(rp);
+        }
         reduce(candidate_sums(pp + o_cost, ge, pp + o_cand, gfc, gfl, &dst->b));
         BaReduce rs{};
         rs.sum_p[0] = pp + o_cost + 2 * (size_t)ge; rs.sum_n[0] = ge; rs.sum_out[0] = &dst->step2s;
@@ -542,7 +835,7 @@ struct GpWork {
             XM_HIP_CHECK(hipMemcpyAsync(ou.data(), oused.p, ou.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         }
         wait_stream(st, cfg.watchdog_s, kStage, "the positions");
-        for (int64_t i = 0; i < n; ++i)
+        for (int64_t i = 0; i < n && !fix; ++i)
             if (cu[(size_t)i])
                 for (int c = 0; c < 3; ++c) t[(size_t)3 * i + c] = hC[(size_t)3 * i + c];
         for (int64_t l = 0; l < m; ++l) {
@@ -555,9 +848,19 @@ struct GpWork {
     }
 };
 
-void run(const SchurOp &SO, const GpSettings &cfg, const double *rot, double *t, double *p, double *scales, GpOutcome &out, hipStream_t st) {
+// sigma of the participating pairs from parameter set k, by input index; -1 for a pair that takes no part
+void pairs_to_caller(GpWork &W, int k, int64_t npairs, double *sigma) {
+    std::vector<double> hs;
+    download(hs, (const double *)W.Sg[k].p, (size_t)W.M, W.st);
+    wait_stream(W.st, W.cfg.watchdog_s, kStage, "the pair scales");
+    std::fill(sigma, sigma + npairs, -1.0);
+    for (size_t q = 0; q < W.plist.size(); ++q) sigma[W.plist[q]] = hs[q];
+}
+
+void run(const SchurOp &SO, const GpSettings &cfg, GpPairsIn *pin, const double *rot, double *t, double *p, double *scales, GpOutcome &out,
+         hipStream_t st) {
     const auto t_start = std::chrono::steady_clock::now();
-    GpWork W(SO, cfg, rot, t, p, nullptr, st);
+    GpWork W(SO, cfg, rot, t, p, nullptr, st, pin);
     int pcg_last = 8;
     // the PCG's batch driver with this solver's product; the PCG's state word is the one GpState embeds
     PcgHooks hooks;
@@ -571,21 +874,27 @@ void run(const SchurOp &SO, const GpSettings &cfg, const double *rot, double *t,
     lm.read_point = [&](LmRead which) {
         const GpState s = W.read_state(which == kLmReadFinal ? "the final gradient" : "the cost and gradient");
         if (which == kLmReadFirst && !std::isfinite(s.b.cost)) throw Error(XM_ERR_ARG, "xm_ctx_global_positioning: the initial cost is not finite");
+        if (W.has_pairs) return LmPoint{s.b.cost + s.pcost, std::max(std::max(s.b.gmax, s.gsmax), s.pgsmax), s.b.used};
         return LmPoint{s.b.cost, std::max(s.b.gmax, s.gsmax), s.b.used};
     };
     lm.solve = [&] {
+        if (W.fix) return LmSolve{0, 0.0};   // dc = 0: the PCG's solution vector is never written
         const PcgResult pr = pcg_solve_batched<3>(W.a, W.gfc, st, pcg_last, hooks);
         return LmSolve{pr.iters, pr.relres};
     };
     lm.read_candidate = [&](double mu) {
         W.candidate(mu, W.x.p);
         const GpState s = W.read_state("the candidate's cost");
+        if (W.has_pairs)
+            return LmCandidate{s.b.cost_new + s.pcost_new, s.b.model + s.pmodel, s.b.step2[0] + s.b.step2[1] + s.step2s + s.pstep2,
+                               s.b.x2[0] + s.b.x2[1] + s.x2s + s.px2};
         return LmCandidate{s.b.cost_new, s.b.model, s.b.step2[0] + s.b.step2[1] + s.step2s, s.b.x2[0] + s.b.x2[1] + s.x2s};
     };
     lm.accept = [&](bool) { W.cur ^= 1; };
     lm.out_of_time = [&] { return secs_since(t_start) >= cfg.max_time; };
     const LmResult res = lm_loop(rules, lm);
     W.to_caller(W.cur, t, p, scales);
+    if (W.has_pairs && pin->sigma) pairs_to_caller(W, W.cur, pin->npairs, pin->sigma);
     out.initial_cost = res.initial_cost; out.n_used = (int64_t)res.n_used;
     out.status = res.status; out.iters = res.iters; out.accepted = res.accepted; out.pcg_iters = res.pcg_total;
     out.final_cost = res.final_cost; out.gradient_max = res.gmax; out.trace_len = lm_copy_trace(res, cfg.trace, cfg.trace_cap);
@@ -596,13 +905,21 @@ void run(const SchurOp &SO, const GpSettings &cfg, const double *rot, double *t,
 
 void global_positioning(const SchurOp &S, const GpSettings &cfg, const double *rot, double *t, double *p, double *scales, GpOutcome &out, hipStream_t st) {
     out = GpOutcome();
-    run(S, cfg, rot, t, p, scales, out, st);
+    run(S, cfg, nullptr, rot, t, p, scales, out, st);
+}
+void global_positioning_pairs(const SchurOp &S, const GpSettings &cfg, GpPairsIn &pairs, const double *rot, double *t, double *p, double *scales,
+                              GpOutcome &out, hipStream_t st) {
+    out = GpOutcome();
+    run(S, cfg, &pairs, rot, t, p, scales, out, st);
+    if (pairs.constraint == XM_GP_ONLY_POINTS && pairs.sigma) std::fill(pairs.sigma, pairs.sigma + pairs.npairs, -1.0);
 }
 
 // The test export xm_ctx_gp_probe: one linearisation at (t, p, s) with the damping mu, then whatever the caller asked for, every array
 // brought back in the caller's index order.  Only GpWork's members launch kernels here.
-void gp_probe(const SchurOp &SO, const GpSettings &cfg, const double *rot, const double *t, const double *p, GpProbe &q, hipStream_t st) {
-    GpWork W(SO, cfg, rot, t, p, q.s, st);
+namespace {
+void probe(const SchurOp &SO, const GpSettings &cfg, GpPairsIn *pin, const double *rot, const double *t, const double *p, GpProbe &q, GpPairProbe *pq,
+           hipStream_t st) {
+    GpWork W(SO, cfg, rot, t, p, q.s, st, pin, pq ? pq->sigma_in : nullptr);
     const int64_t n = W.n, m = W.m, nobs = W.nobs, nd = 3 * n;
     auto d2h = [&](void *dstp, const void *src, size_t bytes) { XM_HIP_CHECK(hipMemcpyAsync(dstp, src, bytes, hipMemcpyDeviceToHost, st)); };
     auto sync = [&](const char *what) { check_launch(what); wait_stream(st, cfg.watchdog_s, kStage, what); };
@@ -610,6 +927,33 @@ void gp_probe(const SchurOp &SO, const GpSettings &cfg, const double *rot, const
     W.linearise(q.mu);
     const GpState s0 = W.read_state("the probe's passes");
     q.cost = s0.b.cost; q.n_used = (int64_t)s0.b.used; q.gmax = std::max(s0.b.gmax, s0.gsmax);
+    const int64_t np = pin ? pin->npairs : 0;
+    if (W.has_pairs) {   // the pairs' records and flags, by input index
+        q.gmax = std::max(q.gmax, s0.pgsmax);
+        pq->cost = s0.pcost; pq->gsmax = s0.pgsmax;
+        std::vector<double> rec;
+        std::vector<int32_t> fz;
+        download(rec, (const double *)W.prec.p, (size_t)kGpPlanes * W.M, st);
+        download(fz, (const int32_t *)W.pfrozen.p, (size_t)W.M, st);
+        sync("the pairs' records");
+        if (pq->Mp) std::fill(pq->Mp, pq->Mp + 6 * np, 0.0);
+        if (pq->qp) std::fill(pq->qp, pq->qp + 3 * np, 0.0);
+        if (pq->pfrozen) std::fill(pq->pfrozen, pq->pfrozen + np, 0);
+        if (pq->pused) std::fill(pq->pused, pq->pused + np, 0);
+        for (int64_t k = 0; k < W.M; ++k) {
+            const int64_t e = W.plist[(size_t)k];
+            auto pl = [&](int c) { return rec[(size_t)c * W.M + (size_t)k]; };
+            const double a = pl(GA), u[3] = {pl(GU), pl(GU + 1), pl(GU + 2)};
+            if (pq->Mp) {
+                double *Mm = pq->Mp + (size_t)6 * e;
+                Mm[0] = a - u[0] * u[0]; Mm[1] = -u[0] * u[1]; Mm[2] = -u[0] * u[2]; Mm[3] = a - u[1] * u[1]; Mm[4] = -u[1] * u[2]; Mm[5] = a - u[2] * u[2];
+            }
+            if (pq->qp)
+                for (int c = 0; c < 3; ++c) pq->qp[(size_t)3 * e + c] = pl(GQ + c);
+            if (pq->pfrozen) pq->pfrozen[e] = fz[(size_t)k];
+            if (pq->pused) pq->pused[e] = 1;
+        }
+    }
     if (q.M || q.q) {   // records by camera position -> input order; M_e = a I - u u^T
         std::vector<double> rec((size_t)kGpPlanes * nobs);
         std::vector<int64_t> pos((size_t)nobs);
@@ -644,7 +988,7 @@ void gp_probe(const SchurOp &SO, const GpSettings &cfg, const double *rot, const
         for (int64_t l = 0; l < m; ++l) q.lused[l] = lu[(size_t)slot_of[(size_t)l]];
     }
     // S X: column j into the PCG's direction vector, the product pair, A p back (the state word's done flag is 0: nothing has set it)
-    if (q.SX)
+    if (q.SX && !W.fix)
         for (int64_t j = 0; j < q.k; ++j) {
             XM_HIP_CHECK(hipMemcpyAsync(W.pv.p, q.X + (size_t)nd * j, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
             W.sx(W.a, &W.dst->b);
@@ -652,7 +996,7 @@ void gp_probe(const SchurOp &SO, const GpSettings &cfg, const double *rot, const
             sync("the product S x");
         }
     if (q.dc) {
-        XM_HIP_CHECK(hipMemcpyAsync(W.x.p, q.dc, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
+        if (!W.fix) XM_HIP_CHECK(hipMemcpyAsync(W.x.p, q.dc, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));   // fixed centres: x stays 0
         W.candidate(q.mu, W.x.p);
         const GpState s = W.read_state("the probe's candidate");
         q.cost1 = s.b.cost_new; q.model = s.b.model;
@@ -667,11 +1011,43 @@ void gp_probe(const SchurOp &SO, const GpSettings &cfg, const double *rot, const
             if (q.p1) std::memcpy(q.p1, p1.data(), p1.size() * sizeof(double));
             if (q.s1) std::memcpy(q.s1, s1.data(), s1.size() * sizeof(double));
         }
+        if (W.has_pairs) {
+            pq->cost1 = s.pcost_new; pq->model = s.pmodel; pq->step2 = s.pstep2; pq->x2 = s.px2;
+            if (pq->sigma1) pairs_to_caller(W, 1, np, pq->sigma1);
+            if (pq->dsigma) {
+                std::vector<double> hd;
+                download(hd, (const double *)W.dsg.p, (size_t)W.M, st);
+                sync("the pair scale steps");
+                std::fill(pq->dsigma, pq->dsigma + np, 0.0);
+                for (int64_t k = 0; k < W.M; ++k) pq->dsigma[W.plist[(size_t)k]] = hd[(size_t)k];
+            }
+        }
     }
+    if (pq && !W.has_pairs) {   // no pair terms: nothing takes part
+        if (pq->Mp) std::fill(pq->Mp, pq->Mp + 6 * np, 0.0);
+        if (pq->qp) std::fill(pq->qp, pq->qp + 3 * np, 0.0);
+        if (pq->pfrozen) std::fill(pq->pfrozen, pq->pfrozen + np, 0);
+        if (pq->pused) std::fill(pq->pused, pq->pused + np, 0);
+        if (pq->dsigma) std::fill(pq->dsigma, pq->dsigma + np, 0.0);
+        if (pq->sigma1) std::fill(pq->sigma1, pq->sigma1 + np, -1.0);
+    }
+}
+}  // namespace
+
+void gp_probe(const SchurOp &SO, const GpSettings &cfg, const double *rot, const double *t, const double *p, GpProbe &q, hipStream_t st) {
+    probe(SO, cfg, nullptr, rot, t, p, q, nullptr, st);
+}
+void gp_probe_pairs(const SchurOp &SO, const GpSettings &cfg, GpPairsIn &pairs, const double *rot, const double *t, const double *p, GpProbe &q,
+                    GpPairProbe &pq, hipStream_t st) {
+    pq.cost = pq.gsmax = pq.cost1 = pq.model = pq.step2 = pq.x2 = 0.0;
+    probe(SO, cfg, &pairs, rot, t, p, q, &pq, st);
 }
 
 void gp_limits(int64_t out[3]) {
     out[0] = kSchurHeavy; out[1] = 64; out[2] = kBaHeavyThreads;
+}
+void gp_pair_limits(int64_t out[2]) {
+    out[0] = kPairListLight; out[1] = kPairListThreads;
 }
 
 }  // namespace xm

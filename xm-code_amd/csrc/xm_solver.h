@@ -121,6 +121,8 @@ struct BaProbe;
 struct GpSettings;  // xm_gp.h
 struct GpOutcome;
 struct GpProbe;
+struct GpPairsIn;
+struct GpPairProbe;
 struct CleanSettings;  // xm_clean.h
 struct CleanOutcome;
 struct TfSettings;     // xm_trackfilter.h
@@ -172,6 +174,8 @@ public:
     // global positioning from rotations and bearings (xm_gp.h): matrix-free storage, one rank; reads the context, changes nothing in it
     void global_positioning(const GpSettings &cfg, const double *rot, double *t, double *p, double *scales, GpOutcome &out);
     void gp_probe(const GpSettings &cfg, const double *rot, const double *t, const double *p, GpProbe &q);   // test export
+    void global_positioning_pairs(const GpSettings &cfg, GpPairsIn &pairs, const double *rot, double *t, double *p, double *scales, GpOutcome &out);
+    void gp_probe_pairs(const GpSettings &cfg, GpPairsIn &pairs, const double *rot, const double *t, const double *p, GpProbe &q, GpPairProbe &pq);   // test export
     void outer_probe(xm_outer_probe_t &q);   // test export (xm_ctx_outer_probe): the retraction and the device-driven step launch stage by stage
     void rtr_probe(xm_rtr_probe_t &q);   // test export (include/xm_amd.h: xm_ctx_rtr_probe): the trust region's kernels stage by stage
     void schur_probe(xm_schur_probe_t &q);   // test export (xm_ctx_schur_probe): the matrix-free Q's factors, chain stages and inner-CG pieces

@@ -2452,6 +2452,24 @@ void Context::gp_probe(const GpSettings &cfg, const double *rot, const double *t
     c.watchdog_s = cfg_.watchdog_s;
     xm::gp_probe(*schur_, c, rot, t, p, q, st_);
 }
+void Context::global_positioning_pairs(const GpSettings &cfg, GpPairsIn &pairs, const double *rot, double *t, double *p, double *scales,
+                                       GpOutcome &out) {
+    if (!schur_)
+        throw Error(XM_ERR_ARG, "xm_ctx_global_positioning_pairs: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_global_positioning_pairs: single-rank contexts only");
+    GpSettings c = cfg;
+    c.watchdog_s = cfg_.watchdog_s;
+    xm::global_positioning_pairs(*schur_, c, pairs, rot, t, p, scales, out, st_);
+}
+void Context::gp_probe_pairs(const GpSettings &cfg, GpPairsIn &pairs, const double *rot, const double *t, const double *p, GpProbe &q,
+                             GpPairProbe &pq) {
+    if (!schur_)
+        throw Error(XM_ERR_ARG, "xm_ctx_gp_probe_pairs: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_gp_probe_pairs: single-rank contexts only");
+    GpSettings c = cfg;
+    c.watchdog_s = cfg_.watchdog_s;
+    xm::gp_probe_pairs(*schur_, c, pairs, rot, t, p, q, pq, st_);
+}
 void Context::schur_probe(xm_schur_probe_t &q) {
     if (!schur_ || schur_dense_)
         throw Error(XM_ERR_ARG, "xm_ctx_schur_probe: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages keep no factors");

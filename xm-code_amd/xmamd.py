@@ -50,6 +50,7 @@ EXPORTS = [
     "xm_ctx_filter_tracks", "xm_track_filter_limits",
     "xm_prune_weakly_connected", "xm_ctx_prune_weakly_connected", "xm_prune_limits",
     "xm_ctx_global_positioning", "xm_ctx_gp_probe", "xm_gp_limits",
+    "xm_ctx_global_positioning_pairs", "xm_ctx_gp_probe_pairs", "xm_gp_pair_limits",
 ]
 # include/xm_bench.h: timing hooks of the micro-benchmarks (same library, not part of the product ABI)
 BENCH_EXPORTS = ["xm_bench_last_error", "xm_qw_dense_time", "xm_qw_dense_sym_time", "xm_qw_dense_f32_time", "xm_qw_dense_sym_f32_time", "xm_bench_symv_k", "xm_bench_dense_policy", "xm_qw_dense_sym_trace", "xm_qw_dense_strip_time", "xm_qw_dense_strip_ks", "xm_qw_bsr3_time", "xm_bench_bsr_binned", "xm_qw_sell_time",
@@ -143,6 +144,23 @@ class GpProbe(C.Structure):   # xm_gp_probe_t, the test export xm_ctx_gp_probe
                 ("mu", C.c_double), ("k", C.c_int64), ("s", C.c_void_p), ("X", C.c_void_p), ("dc", C.c_void_p), ("cost", C.c_double),
                 ("gmax", C.c_double), ("cost1", C.c_double), ("model", C.c_double), ("step2", C.c_double * 3), ("x2", C.c_double * 3),
                 ("n_used", C.c_int64)] + [(k, C.c_void_p) for k in GP_PROBE_OUT]
+
+
+GP_CONSTRAINT = {"only_points": 0, "only_cameras": 1, "points_and_cameras_balanced": 2, "points_and_cameras": 3}   # XM_GP_*
+GP_FIX_CENTRES = 1
+GP_PAIR_PROBE_OUT = ("Mp", "qp", "pfrozen", "pused", "dsigma", "sigma1")
+
+
+class GpPairs(C.Structure):   # xm_gp_pairs_t
+    _fields_ = [("struct_size", C.c_uint32), ("constraint", C.c_int32), ("flags", C.c_uint32), ("pad", C.c_int32), ("npairs", C.c_int64),
+                ("pi", C.c_void_p), ("pj", C.c_void_p), ("trel", C.c_void_p), ("valid", C.c_void_p), ("calibrated", C.c_void_p),
+                ("reweight_scale", C.c_double), ("sigma", C.c_void_p), ("pairs_used", C.c_int64), ("cams_heavy", C.c_int64),
+                ("max_incidences", C.c_int64), ("weight_scale_pt", C.c_double)]
+
+
+class GpPairProbe(C.Structure):   # xm_gp_pair_probe_t, the test export xm_ctx_gp_probe_pairs
+    _fields_ = [("struct_size", C.c_uint32), ("pad", C.c_int32), ("sigma_in", C.c_void_p)] + \
+               [(k, C.c_double) for k in ("cost", "gsmax", "cost1", "model", "step2", "x2")] + [(k, C.c_void_p) for k in GP_PAIR_PROBE_OUT]
 
 
 class RtrScal(C.Structure):    # xm_rtr_scal_t: the truncated CG's scalar block as the test export xm_ctx_rtr_probe passes it
@@ -536,6 +554,10 @@ def lib():
         L.xm_ctx_global_positioning.argtypes = [C.c_void_p, C.POINTER(GpOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GpResult)]
         L.xm_ctx_gp_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GpProbe)]
         L.xm_gp_limits.argtypes = [C.c_void_p]
+        L.xm_ctx_global_positioning_pairs.argtypes = [C.c_void_p, C.POINTER(GpOptions), C.POINTER(GpPairs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.POINTER(GpResult)]
+        L.xm_ctx_gp_probe_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GpProbe), C.POINTER(GpPairs), C.POINTER(GpPairProbe)]
+        L.xm_gp_pair_limits.argtypes = [C.c_void_p]
         L.xm_prune_weakly_connected.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PruneOptions), C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.POINTER(PruneResult)]
         L.xm_ctx_prune_weakly_connected.argtypes = [C.c_void_p, C.POINTER(PruneOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PruneResult)]
@@ -1057,6 +1079,40 @@ def gp_limits():
     out = np.zeros(3, dtype=np.int64)
     _chk(lib().xm_gp_limits(out.ctypes.data_as(C.c_void_p)))
     return dict(light_max=int(out[0]), cam_pass=int(out[1]), threads=int(out[2]))
+
+
+def gp_pair_limits():
+    """-> dict(light_max: incidences (ends of participating pairs) of a camera that one thread walks in Context.global_positioning with
+    pairs (a camera with more gets a workgroup), threads: of that workgroup)"""
+    out = np.zeros(2, dtype=np.int64)
+    _chk(lib().xm_gp_pair_limits(out.ctypes.data_as(C.c_void_p)))
+    return dict(light_max=int(out[0]), threads=int(out[1]))
+
+
+def _gp_pairs_struct(n, pairs, constraint, calibrated, reweight_scale, fix_centres, want_sigma=True):
+    """xm_gp_pairs_t from the Python arguments -> (struct, arrays kept alive, sigma or None)"""
+    if constraint not in GP_CONSTRAINT:
+        raise XmError(f"unknown constraint {constraint!r} (one of {', '.join(GP_CONSTRAINT)})")
+    g = GpPairs()
+    g.struct_size = C.sizeof(GpPairs)
+    g.constraint, g.flags, g.reweight_scale = GP_CONSTRAINT[constraint], (GP_FIX_CENTRES if fix_centres else 0), float(reweight_scale)
+    keep, sigma = [], None
+    if pairs is not None:
+        pi = np.ascontiguousarray(pairs[0], dtype=np.int32); pj = np.ascontiguousarray(pairs[1], dtype=np.int32)
+        trel = np.ascontiguousarray(np.asarray(pairs[2], dtype=np.float64).reshape(pi.size, 3))
+        assert pj.shape == pi.shape
+        keep += [pi, pj, trel]
+        g.npairs, g.pi, g.pj, g.trel = pi.size, pi.ctypes.data_as(C.c_void_p), pj.ctypes.data_as(C.c_void_p), trel.ctypes.data_as(C.c_void_p)
+        if len(pairs) > 3 and pairs[3] is not None:
+            valid = np.ascontiguousarray(np.asarray(pairs[3]).reshape(pi.size) != 0, dtype=np.uint8)
+            keep.append(valid); g.valid = valid.ctypes.data_as(C.c_void_p)
+        if want_sigma:
+            sigma = np.zeros(max(pi.size, 1)); g.sigma = sigma.ctypes.data_as(C.c_void_p)
+            sigma = sigma[: pi.size]
+    if calibrated is not None:
+        cal = np.ascontiguousarray(np.asarray(calibrated).reshape(n) != 0, dtype=np.uint8)
+        keep.append(cal); g.calibrated = cal.ctypes.data_as(C.c_void_p)
+    return g, keep, sigma
 
 
 def gp_random_start(n, m, seed=1):
@@ -2152,13 +2208,19 @@ class Context:
         return rot, t, P, info
 
     def global_positioning(self, rot, t=None, P=None, seed=1, min_views=3, loss="huber", loss_scale=0.1, max_iters=100, max_time=300.0, eta=0.1,
-                           function_tol=1e-5, gradient_tol=1e-10, parameter_tol=1e-8, trace=0):
+                           function_tol=1e-5, gradient_tol=1e-10, parameter_tol=1e-8, trace=0, pairs=None, constraint="only_points",
+                           calibrated=None, reweight_scale=1.0, fix_centres=False, points=True):
         """GLOMAP's global positioning (estimators/global_positioning.cc, ONLY_POINTS; xm_ctx_global_positioning, include/xm_amd.h has the
         contract): camera centres t (3 x n) and points P (3 x m) from the rotations rot (3 x 3n, R_i camera to world, read only) and the
         bearings p_e / |p_e| of this context's observations at their CURRENT weights; matrix-free contexts only.  t or P None: both start
         from gp_random_start(n, m, seed).  -> (t, P, info) with info: status (BA_STATUS), iters, accepted, pcg_iters, n_used, initial_cost,
         final_cost, gradient_max, seconds, scales (one per observation in input order, -1 = not used) and with trace > 0 "trace" (the rows
-        of bundle_adjust).  The result has a free gauge (origin and scale); bundle_adjust can start from it."""
+        of bundle_adjust).  The result has a free gauge (origin and scale); bundle_adjust can start from it.
+        pairs = (pi, pj, trel[, valid]), constraint ("only_points", "only_cameras", "points_and_cameras_balanced", "points_and_cameras"),
+        calibrated (n flags), reweight_scale, fix_centres: xm_ctx_global_positioning_pairs (with the defaults of all five the old entry
+        point is called).  constraint="only_cameras" with points=True then makes the second call of global_mapper.cc:205-217, "only_points"
+        with the centres fixed, so that P is placed against the centres just found; info is the first call's, with "points" the second's.
+        info gains sigma (one per pair, -1 = takes no part), pairs_used, weight_scale_pt, cams_heavy, max_incidences."""
         n, m = self.n, self.n_landmarks
         rot = np.asfortranarray(np.asarray(rot, dtype=np.float64))
         if t is None or P is None:
@@ -2176,16 +2238,60 @@ class Context:
         if trace:
             tr = np.zeros((int(trace), 6)); opt.trace_cap = int(trace); opt.trace = tr.ctypes.data_as(C.c_void_p)
         scales = np.zeros(max(self.ne, 1))
-        _chk(lib().xm_ctx_global_positioning(self.h, C.byref(opt), rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
-                                             P.ctypes.data_as(C.c_void_p), scales.ctypes.data_as(C.c_void_p), C.byref(res)))
+        plain = pairs is None and constraint == "only_points" and calibrated is None and reweight_scale == 1.0 and not fix_centres
+        if plain:
+            _chk(lib().xm_ctx_global_positioning(self.h, C.byref(opt), rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                                 P.ctypes.data_as(C.c_void_p), scales.ctypes.data_as(C.c_void_p), C.byref(res)))
+        else:
+            g, keep, sigma = _gp_pairs_struct(n, pairs, constraint, calibrated, reweight_scale, fix_centres)
+            _chk(lib().xm_ctx_global_positioning_pairs(self.h, C.byref(opt), C.byref(g), rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                                       P.ctypes.data_as(C.c_void_p), scales.ctypes.data_as(C.c_void_p), C.byref(res)))
         info = {k: getattr(res, k) for k, _ in GpResult._fields_ if k not in ("struct_size", "pad")}
         info["status_name"] = BA_STATUS.get(res.status, "?")
         info["scales"] = scales[: self.ne]
         if tr is not None:
             info["trace"] = tr[: res.trace_len].copy()
+        if not plain:
+            info.update(sigma=sigma, pairs_used=g.pairs_used, weight_scale_pt=g.weight_scale_pt, cams_heavy=g.cams_heavy, max_incidences=g.max_incidences)
+            if constraint == "only_cameras" and points:
+                _, P, info["points"] = self.global_positioning(rot, t, P, min_views=min_views, loss=loss, loss_scale=loss_scale, max_iters=max_iters,
+                                                               max_time=max_time, eta=eta, function_tol=function_tol, gradient_tol=gradient_tol,
+                                                               parameter_tol=parameter_tol, calibrated=calibrated, fix_centres=True)
+                info["scales"] = info["points"]["scales"]
         return t, P, info
 
-    def gp_probe(self, rot, t, P, mu, s=None, min_views=3, loss="huber", loss_scale=0.1, X=None, dc=None):
+    def gp_probe_pairs(self, rot, t, P, mu, pairs=None, constraint="only_points", calibrated=None, reweight_scale=1.0, fix_centres=False, s=None,
+                       sigma=None, min_views=3, loss="huber", loss_scale=0.1, X=None, dc=None):
+        """gp_probe with the terms of global_positioning(pairs=..., constraint=..., ...) (the test export xm_ctx_gp_probe_pairs;
+        include/xm_amd.h): gp_probe's dict -- cost, cost1, model, step2, x2 from the observation terms alone -- plus, per pair in input
+        order, Mp (npairs x 6), qp (npairs x 3), pfrozen, pused, and with dc: dsigma, sigma1 (-1 = takes no part); the pairs' scalars
+        pcost, pgsmax, and with dc pcost1, pmodel, pstep2, px2; pairs_used, cams_heavy, max_incidences, weight_scale_pt.  sigma: npairs
+        scales read where the pair takes part (None: all 1)."""
+        n = self.n
+        g, keep, _ = _gp_pairs_struct(n, pairs, constraint, calibrated, reweight_scale, fix_centres, want_sigma=False)
+        npairs = int(g.npairs)
+        pq = GpPairProbe()
+        pq.struct_size = C.sizeof(GpPairProbe)
+        if sigma is not None:
+            sigma = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(npairs))
+            pq.sigma_in = sigma.ctypes.data_as(C.c_void_p)
+        k1 = max(npairs, 1)
+        pout = dict(Mp=np.zeros((k1, 6)), qp=np.zeros((k1, 3)), pfrozen=np.zeros(k1, dtype=np.int32), pused=np.zeros(k1, dtype=np.int32))
+        if dc is not None or fix_centres:
+            pout.update(dsigma=np.zeros(k1), sigma1=np.zeros(k1))
+        for k, v in pout.items():
+            setattr(pq, k, v.ctypes.data_as(C.c_void_p))
+        if fix_centres and dc is None:
+            dc = np.zeros(3 * n)
+        out = self.gp_probe(rot, t, P, mu, s=s, min_views=min_views, loss=loss, loss_scale=loss_scale, X=X, dc=dc, _pairs=(g, pq))
+        out.update({k: v[:npairs] for k, v in pout.items()})
+        out.update(pcost=pq.cost, pgsmax=pq.gsmax, pairs_used=g.pairs_used, cams_heavy=g.cams_heavy, max_incidences=g.max_incidences,
+                   weight_scale_pt=g.weight_scale_pt)
+        if dc is not None:
+            out.update(pcost1=pq.cost1, pmodel=pq.model, pstep2=pq.step2, px2=pq.x2)
+        return out
+
+    def gp_probe(self, rot, t, P, mu, s=None, min_views=3, loss="huber", loss_scale=0.1, X=None, dc=None, _pairs=None):
         """one linearisation of global_positioning at (t, P, s) with the damping mu (the test export xm_ctx_gp_probe; include/xm_amd.h): a
         dict of cost, n_used, gmax, M (nobs x 6), q (nobs x 3), frozen, oused (nobs), vinv (m x 6), g_l (m x 3), ustar, sinv (n x 3 x 3), b
         (n x 3), cused, lused; with X (3n x k): SX; with dc (3n): dP (m x 3), ds (nobs), t1, p1, s1, cost1, model, step2, x2.  Arrays per
@@ -2215,7 +2321,11 @@ class Context:
             out.update(dP=np.zeros((m, 3)), ds=np.zeros(nobs), t1=np.zeros((3, n), order="F"), p1=np.zeros((3, m), order="F"), s1=np.zeros(nobs))
         for k, v in out.items():
             setattr(q, k, v.ctypes.data_as(C.c_void_p))
-        _chk(lib().xm_ctx_gp_probe(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p), C.byref(q)))
+        if _pairs is not None:   # gp_probe_pairs: the same arrays through xm_ctx_gp_probe_pairs
+            _chk(lib().xm_ctx_gp_probe_pairs(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p),
+                                             C.byref(q), C.byref(_pairs[0]), C.byref(_pairs[1])))
+        else:
+            _chk(lib().xm_ctx_gp_probe(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p), C.byref(q)))
         out.update(cost=q.cost, n_used=q.n_used, gmax=q.gmax)
         if dc is not None:
             out.update(cost1=q.cost1, model=q.model, step2=np.array(q.step2[:]), x2=np.array(q.x2[:]))
