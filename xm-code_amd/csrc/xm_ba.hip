@@ -33,12 +33,8 @@ template <int CD> constexpr int ba_fidx() { return CD - 1; }                    
 
 __device__ __forceinline__ bool obs_used(const double (&v)[6]) { return v[0] != 0.0 || v[1] != 0.0 || v[2] != 0.0; }   // J_P row 0 (never 0 when used)
 
-// Scale: the loss scale a (one double) for a robust LOSS, nothing for the trivial one, whose argument list and code are those it had before
-template <int LOSS, class... Scale>
-constexpr bool ba_loss_args() { return sizeof...(Scale) == (LOSS == XM_BA_LOSS_TRIVIAL ? 0 : 1); }
-
-// Y = Rcw P, X = Y + tcw: the camera-frame point of an observation, the eval kernel's expression (written out there, so that its trivial
-// instantiations keep the code they had before the losses)
+// Y = Rcw P, X = Y + tcw: the camera-frame point of an observation.  The eval and cost bodies write the same expression out: called from
+// them, this function changes the order of their vector instructions (profiles/r40_ba_one_kernel_per_stage.txt)
 __device__ __forceinline__ void ba_point(const double *R, const double *T, const double *X3, double (&Y)[3], double (&X)[3]) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -49,13 +45,16 @@ __device__ __forceinline__ void ba_point(const double *R, const double *T, const
 
 // ---- residuals and Jacobians at (Rcw, tcw, P), written in both list orders (scaled by sqrt(rho') under a robust loss); partial sums of
 // the cost 1/2 sum rho(|r|^2) and of the used observations
-// (the body of ba_eval_kernel and ba_eval_focal_kernel.  G, gfree: the focal scales of the parameter set and the mask of the free ones
-// (null: all), read only where the camera block has a focal column: r = g pi(X) - z, J_pose and J_P times g, d r / d g = pi(X) or 0)
-template <int CD, int LOSS, class... Scale>
+// (G, gfree: the focal scales of the parameter set and the mask of the free ones (null: all), read only where the camera block has a focal
+// column and null elsewhere: r = g pi(X) - z, J_pose and J_P times g, d r / d g = pi(X) or 0.  scale: the loss scale a, not read under
+// XM_BA_LOSS_TRIVIAL)
+// The eval, cost and camera-candidate kernels each forward to a __forceinline__ body whose pointer parameters are __restrict__: with the
+// body written into the kernel the __restrict__ of the kernel's own parameters alone gives other instruction streams and register counts
+// (profiles/r40_ba_one_kernel_per_stage.txt), so the bodies stay functions.
+template <int CD, int LOSS>
 __device__ __forceinline__ void ba_eval_body(const SchurLists &S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
                                              const double *__restrict__ P, const double *__restrict__ G, const uint8_t *__restrict__ gfree,
-                                             double *__restrict__ Jc, double *__restrict__ Jl, double *__restrict__ parts, Scale... scale) {
-    static_assert(ba_loss_args<LOSS, Scale...>(), "a robust loss takes its scale, the trivial one nothing");
+                                             double *__restrict__ Jc, double *__restrict__ Jl, double *__restrict__ parts, double scale) {
     constexpr int NP = ba_planes<CD>(), JP = ba_jp<CD>(), RS = ba_res<CD>();
     __shared__ double sh[4];
     double cost = 0.0, used = 0.0;
@@ -105,7 +104,7 @@ __device__ __forceinline__ void ba_eval_body(const SchurLists &S, const double *
                 cost += 0.5 * (v[RS] * v[RS] + v[RS + 1] * v[RS + 1]);
             } else {
                 double rho1;
-                cost += 0.5 * ba_rho<LOSS>(v[RS] * v[RS] + v[RS + 1] * v[RS + 1], scale..., rho1);
+                cost += 0.5 * ba_rho<LOSS>(v[RS] * v[RS] + v[RS + 1] * v[RS + 1], scale, rho1);
                 const double c = sqrt(rho1);
 #pragma unroll
                 for (int k = 0; k < NP; ++k) v[k] *= c;
@@ -122,20 +121,12 @@ __device__ __forceinline__ void ba_eval_body(const SchurLists &S, const double *
     used = block_sum256(used, sh);
     if (threadIdx.x == 0) { parts[blockIdx.x] = cost; parts[gridDim.x + blockIdx.x] = used; }
 }
-template <int CD, int LOSS = XM_BA_LOSS_TRIVIAL, class... Scale>
+template <int CD, int LOSS>
 __global__ __launch_bounds__(256) void ba_eval_kernel(SchurLists S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
-                                                      const double *__restrict__ P, double *__restrict__ Jc, double *__restrict__ Jl,
-                                                      double *__restrict__ parts, Scale... scale) {
-    static_assert(!ba_has_focal<CD>(), "a focal column: ba_eval_focal_kernel");
-    ba_eval_body<CD, LOSS>(S, Rcw, tcw, P, nullptr, nullptr, Jc, Jl, parts, scale...);
-}
-template <int CD, int LOSS = XM_BA_LOSS_TRIVIAL, class... Scale>
-__global__ __launch_bounds__(256) void ba_eval_focal_kernel(SchurLists S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
-                                                            const double *__restrict__ P, const double *__restrict__ G,
-                                                            const uint8_t *__restrict__ gfree, double *__restrict__ Jc, double *__restrict__ Jl,
-                                                            double *__restrict__ parts, Scale... scale) {
-    static_assert(ba_has_focal<CD>(), "no focal column: ba_eval_kernel");
-    ba_eval_body<CD, LOSS>(S, Rcw, tcw, P, G, gfree, Jc, Jl, parts, scale...);
+                                                      const double *__restrict__ P, const double *__restrict__ G,
+                                                      const uint8_t *__restrict__ gfree, double *__restrict__ Jc, double *__restrict__ Jl,
+                                                      double *__restrict__ parts, double scale) {
+    ba_eval_body<CD, LOSS>(S, Rcw, tcw, P, G, gfree, Jc, Jl, parts, scale);
 }
 
 // ---- landmark pass: V_l, g_l, (V_l + mu D_l)^-1 (6 entries of the symmetric inverse), used flag; per-workgroup max of |g_l|_inf
@@ -188,11 +179,11 @@ __global__ __launch_bounds__(kBaHeavyThreads) void ba_lm_kernel(SchurLists S, co
 // (GR, focal groups: the focal diagonal of U*_i stays undamped -- the damping mu D_c of the shared parameter joins where the group sum is
 // taken --, sinv is the inverse of the leading pose block with 1 in the focal slot (ba_group_setup_kernel puts 1 / F_c or 0 there), the
 // focal gradient is left out of the maximum and goes with the undamped S_ii[f, f] to fstat (2 per camera))
-template <int CD, bool GR = false>
+template <int CD, bool GR>
 __global__ __launch_bounds__(256) void ba_cam_kernel(SchurLists S, const double *__restrict__ Jc, const double *__restrict__ vinv,
                                                      const double *__restrict__ gl, double mu, double *__restrict__ ustar, double *__restrict__ sinv,
                                                      double *__restrict__ b, int32_t *__restrict__ cused, double *__restrict__ gpart,
-                                                     double *__restrict__ fstat = nullptr) {
+                                                     double *__restrict__ fstat) {
     static_assert(!GR || ba_has_focal<CD>(), "focal groups need a focal column");
     constexpr int JP = ba_jp<CD>(), RS = ba_res<CD>(), NU = CD * (CD + 1) / 2, NA = 2 * NU + 2 * CD + 1;
     __shared__ double red[kQwWaves];
@@ -478,14 +469,16 @@ __global__ __launch_bounds__(256) void ba_dense_res_kernel(int64_t n, const doub
 // With a focal column (G, gfree, Gn, st given): g += dg for a used camera whose focal is free, a copy elsewhere; g^2 joins |x|^2; a candidate
 // focal that is not positive sets the state word's bad_focal (cleared before the launch; every writer stores the same 1).
 // (GR, focal groups: dc is the expanded step; the focal entry is the group's -- ba_group_cand_kernel takes the step, the norms and the
-// sign test once per group --, every member reads its group's candidate gnew[group_of[i]]; |x|^2 partials at parts[xoff + workgroup])
-template <int CD, bool GR = false>
+// sign test once per group --, every member reads its group's candidate gnew[group_of[i]]; |x|^2 partials at parts[xoff + workgroup];
+// G, gfree and st are not read.  Without GR: group_of, gnew and xoff are not read.)  Without a focal column G, gfree and Gn are null and
+// st is not read.
+template <int CD, bool GR>
 __device__ __forceinline__ void ba_cand_cam_body(int64_t n, const double *__restrict__ Rcw, const double *__restrict__ tcw,
                                                  const double *__restrict__ G, const uint8_t *__restrict__ gfree, const double *__restrict__ dc,
                                                  const int32_t *__restrict__ cused, double *__restrict__ Rn, double *__restrict__ tn,
                                                  double *__restrict__ Gn, BaState *__restrict__ st, double *__restrict__ parts,
-                                                 const int32_t *__restrict__ group_of = nullptr, const double *__restrict__ gnew = nullptr,
-                                                 int xoff = 0) {
+                                                 const int32_t *__restrict__ group_of, const double *__restrict__ gnew, int xoff) {
+    static_assert(!GR || ba_has_focal<CD>(), "focal groups need a focal column");
     __shared__ double sh[4];
     double s2 = 0.0, x2 = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -546,21 +539,14 @@ __device__ __forceinline__ void ba_cand_cam_body(int64_t n, const double *__rest
         if (threadIdx.x == 0) { parts[blockIdx.x] = s2; parts[gridDim.x + blockIdx.x] = x2; }
     }
 }
-template <int CD>
+template <int CD, bool GR>
 __global__ __launch_bounds__(256) void ba_cand_cam_kernel(int64_t n, const double *__restrict__ Rcw, const double *__restrict__ tcw,
-                                                          const double *__restrict__ dc, const int32_t *__restrict__ cused, double *__restrict__ Rn,
-                                                          double *__restrict__ tn, double *__restrict__ parts) {
-    static_assert(!ba_has_focal<CD>(), "a focal column: ba_cand_cam_focal_kernel");
-    ba_cand_cam_body<CD>(n, Rcw, tcw, nullptr, nullptr, dc, cused, Rn, tn, nullptr, nullptr, parts);
-}
-template <int CD>
-__global__ __launch_bounds__(256) void ba_cand_cam_focal_kernel(int64_t n, const double *__restrict__ Rcw, const double *__restrict__ tcw,
-                                                                const double *__restrict__ G, const uint8_t *__restrict__ gfree,
-                                                                const double *__restrict__ dc, const int32_t *__restrict__ cused,
-                                                                double *__restrict__ Rn, double *__restrict__ tn, double *__restrict__ Gn,
-                                                                BaState *__restrict__ st, double *__restrict__ parts) {
-    static_assert(ba_has_focal<CD>(), "no focal column: ba_cand_cam_kernel");
-    ba_cand_cam_body<CD>(n, Rcw, tcw, G, gfree, dc, cused, Rn, tn, Gn, st, parts);
+                                                          const double *__restrict__ G, const uint8_t *__restrict__ gfree,
+                                                          const double *__restrict__ dc, const int32_t *__restrict__ cused,
+                                                          double *__restrict__ Rn, double *__restrict__ tn, double *__restrict__ Gn,
+                                                          BaState *__restrict__ st, double *__restrict__ parts,
+                                                          const int32_t *__restrict__ group_of, const double *__restrict__ gnew, int xoff) {
+    ba_cand_cam_body<CD, GR>(n, Rcw, tcw, G, gfree, dc, cused, Rn, tn, Gn, st, parts, group_of, gnew, xoff);
 }
 // ---- focal groups (xm_ctx_bundle_adjust_focal_groups): one focal scale per group of cameras.  With E the 0/1 matrix that copies a group's
 // focal unknown into the focal column of each member, J_shared = J_7 E, so S_shared = E^T S_7 E and b_shared = E^T b_7: the kernels above
@@ -696,14 +682,6 @@ __global__ __launch_bounds__(256) void ba_group_cand_kernel(BaGroups g, const do
     x2 = block_sum256(x2, sh);
     if (threadIdx.x == 0) { parts[blockIdx.x] = s2; parts[xoff + blockIdx.x] = x2; }
 }
-template <int CD>
-__global__ __launch_bounds__(256) void ba_cand_cam_groups_kernel(int64_t n, const double *__restrict__ Rcw, const double *__restrict__ tcw,
-                                                                 const double *__restrict__ dc, const int32_t *__restrict__ cused,
-                                                                 const int32_t *__restrict__ group_of, const double *__restrict__ gnew,
-                                                                 double *__restrict__ Rn, double *__restrict__ tn, double *__restrict__ Gn,
-                                                                 double *__restrict__ parts, int xoff) {
-    ba_cand_cam_body<CD, true>(n, Rcw, tcw, nullptr, nullptr, dc, cused, Rn, tn, Gn, nullptr, parts, group_of, gnew, xoff);
-}
 // ---- the exact focal block of the preconditioner (at most XM_BA_FOCAL_GROUPS_EXACT groups): F = S_shared[focal, focal], column d from the
 // product with the indicator of group d.  v <- e_slot
 __global__ __launch_bounds__(256) void ba_group_unit_kernel(int64_t count, int64_t slot, double *__restrict__ v) {
@@ -802,13 +780,12 @@ __global__ __launch_bounds__(256) void ba_group_dense_write_kernel(BaGroups g, d
 // (the landmarks' candidate: ba_cand_vec_kernel of xm_lm_shared.h)
 // cost 1/2 sum rho(|r|^2) at the candidate (the eval kernel's expression) and the linear model's terms sum r.(J d) + |J d|^2 / 2 (J, r: the
 // stored records of the current point, by-camera order)
-// (Gn: the candidate's focal scales, read only where the camera block has a focal column)
-template <int CD, int LOSS, class... Scale>
+// (Gn: the candidate's focal scales, read only where the camera block has a focal column and null elsewhere; scale: as in ba_eval_kernel)
+template <int CD, int LOSS>
 __device__ __forceinline__ void ba_cost_body(const SchurLists &S, const double *__restrict__ Rn, const double *__restrict__ tn,
                                              const double *__restrict__ Pn, const double *__restrict__ Gn, const double *__restrict__ Jc,
                                              const double *__restrict__ dc, const double *__restrict__ dP, double *__restrict__ parts,
-                                             Scale... scale) {
-    static_assert(ba_loss_args<LOSS, Scale...>(), "a robust loss takes its scale, the trivial one nothing");
+                                             double scale) {
     constexpr int JP = ba_jp<CD>(), RS = ba_res<CD>();
     __shared__ double sh[4];
     double cost = 0.0, model = 0.0;
@@ -828,7 +805,7 @@ __device__ __forceinline__ void ba_cost_body(const SchurLists &S, const double *
             cost += 0.5 * (e0 * e0 + e1 * e1);
         } else {
             double rho1;
-            cost += 0.5 * ba_rho<LOSS>(e0 * e0 + e1 * e1, scale..., rho1);
+            cost += 0.5 * ba_rho<LOSS>(e0 * e0 + e1 * e1, scale, rho1);
         }
         double jd0 = 0.0, jd1 = 0.0;
 #pragma unroll
@@ -848,47 +825,27 @@ __device__ __forceinline__ void ba_cost_body(const SchurLists &S, const double *
     model = block_sum256(model, sh);
     if (threadIdx.x == 0) { parts[blockIdx.x] = cost; parts[gridDim.x + blockIdx.x] = model; }
 }
-template <int CD, int LOSS = XM_BA_LOSS_TRIVIAL, class... Scale>
+template <int CD, int LOSS>
 __global__ __launch_bounds__(256) void ba_cost_kernel(SchurLists S, const double *__restrict__ Rn, const double *__restrict__ tn,
-                                                      const double *__restrict__ Pn, const double *__restrict__ Jc, const double *__restrict__ dc,
-                                                      const double *__restrict__ dP, double *__restrict__ parts, Scale... scale) {
-    static_assert(!ba_has_focal<CD>(), "a focal column: ba_cost_focal_kernel");
-    ba_cost_body<CD, LOSS>(S, Rn, tn, Pn, nullptr, Jc, dc, dP, parts, scale...);
-}
-template <int CD, int LOSS = XM_BA_LOSS_TRIVIAL, class... Scale>
-__global__ __launch_bounds__(256) void ba_cost_focal_kernel(SchurLists S, const double *__restrict__ Rn, const double *__restrict__ tn,
-                                                            const double *__restrict__ Pn, const double *__restrict__ Gn,
-                                                            const double *__restrict__ Jc, const double *__restrict__ dc,
-                                                            const double *__restrict__ dP, double *__restrict__ parts, Scale... scale) {
-    static_assert(ba_has_focal<CD>(), "no focal column: ba_cost_kernel");
-    ba_cost_body<CD, LOSS>(S, Rn, tn, Pn, Gn, Jc, dc, dP, parts, scale...);
+                                                      const double *__restrict__ Pn, const double *__restrict__ Gn,
+                                                      const double *__restrict__ Jc, const double *__restrict__ dc,
+                                                      const double *__restrict__ dP, double *__restrict__ parts, double scale) {
+    ba_cost_body<CD, LOSS>(S, Rn, tn, Pn, Gn, Jc, dc, dP, parts, scale);
 }
 // |r_e|^2 per observation in input order at (Rcw, tcw, P) (the eval kernel's projection, unrobustified); -1 where the observation is not used
+// (FOCAL: at the focal scales G, |g_i pi(X) - z|^2; without it G is null and not read)
+template <bool FOCAL>
 __global__ __launch_bounds__(256) void ba_sqerr_kernel(SchurLists S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
-                                                       const double *__restrict__ P, double *__restrict__ sqerr) {
+                                                       const double *__restrict__ P, const double *__restrict__ G, double *__restrict__ sqerr) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < S.nobs; e += (int64_t)gridDim.x * 256) {
         const double w = S.cam_w[S.pos_c[e]], q0 = S.obs_p[3 * e], q1 = S.obs_p[3 * e + 1], q2 = S.obs_p[3 * e + 2];
         double sq = -1.0;
         if (w > 0.0 && q2 > 0.0) {
             double Y[3], X[3];
             ba_point(Rcw + (size_t)9 * S.obs_cam[e], tcw + (size_t)3 * S.obs_cam[e], P + (size_t)3 * S.obs_lm[e], Y, X);
-            const double r0 = X[0] / X[2] - q0 / q2, r1 = X[1] / X[2] - q1 / q2;
-            sq = r0 * r0 + r1 * r1;
-        }
-        sqerr[e] = sq;
-    }
-}
-// the same at the focal scales G: |g_i pi(X) - z|^2
-__global__ __launch_bounds__(256) void ba_sqerr_focal_kernel(SchurLists S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
-                                                             const double *__restrict__ P, const double *__restrict__ G,
-                                                             double *__restrict__ sqerr) {
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < S.nobs; e += (int64_t)gridDim.x * 256) {
-        const double w = S.cam_w[S.pos_c[e]], q0 = S.obs_p[3 * e], q1 = S.obs_p[3 * e + 1], q2 = S.obs_p[3 * e + 2];
-        double sq = -1.0;
-        if (w > 0.0 && q2 > 0.0) {
-            double Y[3], X[3];
-            ba_point(Rcw + (size_t)9 * S.obs_cam[e], tcw + (size_t)3 * S.obs_cam[e], P + (size_t)3 * S.obs_lm[e], Y, X);
-            const double g = G[S.obs_cam[e]], r0 = g * (X[0] / X[2]) - q0 / q2, r1 = g * (X[1] / X[2]) - q1 / q2;
+            double r0, r1;
+            if constexpr (FOCAL) { const double g = G[S.obs_cam[e]]; r0 = g * (X[0] / X[2]) - q0 / q2; r1 = g * (X[1] / X[2]) - q1 / q2; }
+            else { r0 = X[0] / X[2] - q0 / q2; r1 = X[1] / X[2] - q1 / q2; }
             sq = r0 * r0 + r1 * r1;
         }
         sqerr[e] = sq;
@@ -1373,6 +1330,19 @@ void to_device_layout(const SchurOp &SO, const double *rot, const double *t, con
     for (int64_t l = 0; l < m; ++l)
         for (int a = 0; a < 3; ++a) hP[(size_t)3 * slot_of[(size_t)l] + a] = p[(size_t)3 * l + a];
 }
+// and the cameras back: R_i = Rcw^T, t_i = -R_i tcw for the cameras whose cused is set, the others left as they are (rot or t null: not written)
+void from_device_layout(int64_t n, const std::vector<double> &hR, const std::vector<double> &hT, const std::vector<int32_t> &cused, double *rot,
+                        double *t) {
+    for (int64_t i = 0; i < n; ++i) {
+        if (!cused[(size_t)i]) continue;
+        const double *Rc = &hR[(size_t)9 * i], *tc = &hT[(size_t)3 * i];
+        for (int a = 0; a < 3; ++a) {
+            if (rot)
+                for (int c = 0; c < 3; ++c) rot[(size_t)a + 3 * ((size_t)3 * i + c)] = Rc[3 * c + a];
+            if (t) t[(size_t)3 * i + a] = -(Rc[a] * tc[0] + Rc[3 + a] * tc[1] + Rc[6 + a] * tc[2]);
+        }
+    }
+}
 
 // One linearisation's device state and the launches on it: the workspace, the eval / landmark / camera passes, the preconditioner's
 // set-up, the product S x, the dense assembly, the PCG's start and the candidate block.  run() (the LM loop) and probe() (the test export
@@ -1587,19 +1557,18 @@ struct BaWork {
     }
     void reduce(BaReduce rd) { hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), b256, 0, st, rd); }
     BaState read_state(const char *what) { return xm::read_state(dst, hs, st, cfg.watchdog_s, kStage, what); }
+    // f(GR): `grouped` as a compile-time constant (the grouped kernels exist for a camera block with a focal column only)
+    template <class F>
+    void by_grouping(F &&f) {
+        if constexpr (ba_has_focal<CD>()) {
+            if (grouped) return f(std::true_type{});
+        }
+        f(std::false_type{});
+    }
     void eval() {
-        with_loss(cfg.loss, [&](auto L) {   // the trivial instantiation takes no scale
-            const double *Rc = R[cur].p, *Tc = T[cur].p, *Pc = P[cur].p;
-            if constexpr (ba_has_focal<CD>()) {
-                const double *Gc = G[cur].p;
-                const uint8_t *fr = gfree.p;
-                if constexpr (L.value == XM_BA_LOSS_TRIVIAL)
-                    hipLaunchKernelGGL((ba_eval_focal_kernel<CD>), dim3(ge), b256, 0, st, S, Rc, Tc, Pc, Gc, fr, Jc.p, Jl.p, pp + o_eval);
-                else
-                    hipLaunchKernelGGL((ba_eval_focal_kernel<CD, L.value, double>), dim3(ge), b256, 0, st, S, Rc, Tc, Pc, Gc, fr, Jc.p, Jl.p, pp + o_eval,
-                                       cfg.loss_scale);
-            } else if constexpr (L.value == XM_BA_LOSS_TRIVIAL) hipLaunchKernelGGL((ba_eval_kernel<CD>), dim3(ge), b256, 0, st, S, Rc, Tc, Pc, Jc.p, Jl.p, pp + o_eval);
-            else hipLaunchKernelGGL((ba_eval_kernel<CD, L.value, double>), dim3(ge), b256, 0, st, S, Rc, Tc, Pc, Jc.p, Jl.p, pp + o_eval, cfg.loss_scale);
+        with_loss(cfg.loss, [&](auto L) {   // G[] and gfree are not allocated (null) without a focal column
+            hipLaunchKernelGGL((ba_eval_kernel<CD, L.value>), dim3(ge), b256, 0, st, S, (const double *)R[cur].p, (const double *)T[cur].p,
+                               (const double *)P[cur].p, (const double *)G[cur].p, (const uint8_t *)gfree.p, Jc.p, Jl.p, pp + o_eval, cfg.loss_scale);
         });
         BaReduce rd{};
         rd.sum_p[0] = pp + o_eval; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->cost;
@@ -1608,18 +1577,16 @@ struct BaWork {
     }
     void passes(double mu) {
         hipLaunchKernelGGL((ba_lm_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, mu, vinv.p, gl.p, lused.p, pp + o_gmax);
+        by_grouping([&](auto GR) {   // fstat: allocated with the groups, null without
+            hipLaunchKernelGGL((ba_cam_kernel<CD, GR.value>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)vinv.p,
+                               (const double *)gl.p, mu, ustar.p, sinv.p, b.p, cused.p, pp + o_gmax + glm, fstat.p);
+        });
         if constexpr (ba_has_focal<CD>()) {
-            if (grouped) {   // the camera pass in its grouped form, then the groups' pass: their gradient entries join the maximum
-                hipLaunchKernelGGL((ba_cam_kernel<CD, true>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)vinv.p,
-                                   (const double *)gl.p, mu, ustar.p, sinv.p, b.p, cused.p, pp + o_gmax + glm, fstat.p);
+            if (grouped) {   // the groups' pass: their gradient entries join the maximum
                 hipLaunchKernelGGL((ba_group_setup_kernel<CD>), dim3(ggrp), b256, 0, st, grp, (const double *)ustar.p, (const double *)fstat.p,
                                    (const int32_t *)cused.p, mu, b.p, sinv.p, grp_D.p, grp_F.p, grp_moving.p, pp + o_gmax + glm + gcam);
                 cur_mu = mu;
             }
-        }
-        if (!grouped) {
-            hipLaunchKernelGGL((ba_cam_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)vinv.p, (const double *)gl.p, mu,
-                               ustar.p, sinv.p, b.p, cused.p, pp + o_gmax + glm);
         }
         BaReduce rd{};
         rd.max_p = pp + o_gmax; rd.max_n = glm + gcam + ggrp; rd.max_out = &dst->gmax;   // (ggrp = 0 without groups)
@@ -1781,34 +1748,21 @@ struct BaWork {
                            (const int32_t *)lused.p, dc, (const BaState *)nullptr, dP.p);
         if constexpr (ba_has_focal<CD>()) {
             XM_HIP_CHECK(hipMemsetAsync(&dst->bad_focal, 0, sizeof(int32_t), st));
-            if (grouped) {
+            if (grouped)
                 hipLaunchKernelGGL((ba_group_cand_kernel<CD>), dim3(ggf), b256, 0, st, grp, (const double *)G[cur].p, dshared,
                                    (const int32_t *)grp_moving.p, grp_new.p, dst, pp + o_cand + gfc, gfg);
-                hipLaunchKernelGGL((ba_cand_cam_groups_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p, dc,
-                                   (const int32_t *)cused.p, (const int32_t *)grp_of.p, (const double *)grp_new.p, R[nx].p, T[nx].p, G[nx].p,
-                                   pp + o_cand, gfg);
-            } else {
-                hipLaunchKernelGGL((ba_cand_cam_focal_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p,
-                                   (const double *)G[cur].p, (const uint8_t *)gfree.p, dc, (const int32_t *)cused.p, R[nx].p, T[nx].p, G[nx].p, dst,
-                                   pp + o_cand);
-            }
-        } else {
-            hipLaunchKernelGGL((ba_cand_cam_kernel<CD>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p, dc,
-                               (const int32_t *)cused.p, R[nx].p, T[nx].p, pp + o_cand);
         }
+        by_grouping([&](auto GR) {   // G[], gfree and the groups' arrays: null where there are none
+            hipLaunchKernelGGL((ba_cand_cam_kernel<CD, GR.value>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p,
+                               (const double *)G[cur].p, (const uint8_t *)gfree.p, dc, (const int32_t *)cused.p, R[nx].p, T[nx].p, G[nx].p,
+                               dst, pp + o_cand, (const int32_t *)grp_of.p, (const double *)grp_new.p, gfg);
+        });
         hipLaunchKernelGGL(ba_cand_vec_kernel<3>, dim3(gfl), b256, 0, st, m, (const double *)P[cur].p, (const double *)dP.p, (const int32_t *)lused.p,
                            P[nx].p, pp + o_cand + 2 * (size_t)gfg);
         with_loss(cfg.loss, [&](auto L) {
-            const double *Rn = R[nx].p, *Tn = T[nx].p, *Pn = P[nx].p, *J = Jc.p, *dl = dP.p;
-            if constexpr (ba_has_focal<CD>()) {
-                const double *Gn = G[nx].p;
-                if constexpr (L.value == XM_BA_LOSS_TRIVIAL)
-                    hipLaunchKernelGGL((ba_cost_focal_kernel<CD>), dim3(ge), b256, 0, st, S, Rn, Tn, Pn, Gn, J, dc, dl, pp + o_cost);
-                else
-                    hipLaunchKernelGGL((ba_cost_focal_kernel<CD, L.value, double>), dim3(ge), b256, 0, st, S, Rn, Tn, Pn, Gn, J, dc, dl, pp + o_cost,
-                                       cfg.loss_scale);
-            } else if constexpr (L.value == XM_BA_LOSS_TRIVIAL) hipLaunchKernelGGL((ba_cost_kernel<CD>), dim3(ge), b256, 0, st, S, Rn, Tn, Pn, J, dc, dl, pp + o_cost);
-            else hipLaunchKernelGGL((ba_cost_kernel<CD, L.value, double>), dim3(ge), b256, 0, st, S, Rn, Tn, Pn, J, dc, dl, pp + o_cost, cfg.loss_scale);
+            hipLaunchKernelGGL((ba_cost_kernel<CD, L.value>), dim3(ge), b256, 0, st, S, (const double *)R[nx].p, (const double *)T[nx].p,
+                               (const double *)P[nx].p, (const double *)G[nx].p, (const double *)Jc.p, dc, (const double *)dP.p, pp + o_cost,
+                               cfg.loss_scale);
         });
         reduce(candidate_sums(pp + o_cost, ge, pp + o_cand, gfg, gfl, dst));
     }
@@ -1882,14 +1836,7 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
     XM_HIP_CHECK(hipMemcpyAsync(cu.data(), W.cused.p, cu.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     XM_HIP_CHECK(hipMemcpyAsync(lu.data(), W.lused.p, lu.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     wait_stream(st, cfg.watchdog_s, kStage, "the refined parameters");
-    for (int64_t i = 0; i < n; ++i) {
-        if (!cu[(size_t)i]) continue;
-        const double *Rc = &hR[(size_t)9 * i], *tc = &hT[(size_t)3 * i];
-        for (int a = 0; a < 3; ++a) {
-            for (int c = 0; c < 3; ++c) rot[(size_t)a + 3 * ((size_t)3 * i + c)] = Rc[3 * c + a];   // R_i = Rcw^T
-            t[(size_t)3 * i + a] = -(Rc[a] * tc[0] + Rc[3 + a] * tc[1] + Rc[6 + a] * tc[2]);     // t_i = -R_i tcw
-        }
-    }
+    from_device_layout(n, hR, hT, cu, rot, t);
     for (int64_t l = 0; l < m; ++l) {
         const int32_t sl = slot_of[(size_t)l];
         if (!lu[(size_t)sl]) continue;
@@ -2063,17 +2010,21 @@ void probe(const SchurOp &SO, const BaSettings &cfg, const double *rot, const do
             sync("the candidate cameras");
             if (q.rot1) std::memcpy(q.rot1, rot, (size_t)9 * n * sizeof(double));
             if (q.t1) std::memcpy(q.t1, t, (size_t)3 * n * sizeof(double));
-            for (int64_t i = 0; i < n; ++i) {
-                if (!cu[(size_t)i]) continue;
-                const double *Rc = &hR[(size_t)9 * i], *tc = &hT[(size_t)3 * i];
-                for (int a = 0; a < 3; ++a) {
-                    if (q.rot1)
-                        for (int c = 0; c < 3; ++c) q.rot1[(size_t)a + 3 * ((size_t)3 * i + c)] = Rc[3 * c + a];   // R_i = Rcw^T
-                    if (q.t1) q.t1[(size_t)3 * i + a] = -(Rc[a] * tc[0] + Rc[3 + a] * tc[1] + Rc[6 + a] * tc[2]);   // t_i = -R_i tcw
-                }
-            }
+            from_device_layout(n, hR, hT, cu, q.rot1, q.t1);
         }
     }
+}
+
+// f(CD as a constant) for the camera block the settings ask for; who: the export's name up to the focal suffix, for the messages
+template <class F>
+void with_cd(const BaSettings &cfg, const std::string &who, F &&f) {
+    if (cfg.refine_focal) {
+        if (cfg.precond != 0 || !cfg.focal) throw Error(XM_ERR_ARG, who + "_focal: needs the focal scales and the default preconditioner");
+        if (cfg.ngroups > 0 && !cfg.group_of) throw Error(XM_ERR_ARG, who + "_focal_groups: needs group_of");
+        if (cfg.fix_rotations) f(std::integral_constant<int, 4>{});
+        else f(std::integral_constant<int, 7>{});
+    } else if (cfg.fix_rotations) f(std::integral_constant<int, 3>{});
+    else f(std::integral_constant<int, 6>{});
 }
 
 }  // namespace
@@ -2143,27 +2094,11 @@ void ba_aggregate_plan(int64_t n, int64_t nobs, const int32_t *cam, const int32_
 
 void bundle_adjust(const SchurOp &S, const BaSettings &cfg, double *rot, double *t, double *p, BaOutcome &out, hipStream_t st) {
     out = BaOutcome();
-    if (cfg.refine_focal) {
-        if (cfg.precond != 0 || !cfg.focal) throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust_focal: needs the focal scales and the default preconditioner");
-        if (cfg.ngroups > 0 && !cfg.group_of) throw Error(XM_ERR_ARG, "xm_ctx_bundle_adjust_focal_groups: needs group_of");
-        if (cfg.fix_rotations) run<4>(S, cfg, rot, t, p, out, st);
-        else run<7>(S, cfg, rot, t, p, out, st);
-        return;
-    }
-    if (cfg.fix_rotations) run<3>(S, cfg, rot, t, p, out, st);
-    else run<6>(S, cfg, rot, t, p, out, st);
+    with_cd(cfg, "xm_ctx_bundle_adjust", [&](auto CD) { run<CD.value>(S, cfg, rot, t, p, out, st); });
 }
 
 void ba_probe(const SchurOp &S, const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q, hipStream_t st) {
-    if (cfg.refine_focal) {
-        if (cfg.precond != 0 || !cfg.focal) throw Error(XM_ERR_ARG, "xm_ctx_ba_probe_focal: needs the focal scales and the default preconditioner");
-        if (cfg.ngroups > 0 && !cfg.group_of) throw Error(XM_ERR_ARG, "xm_ctx_ba_probe_focal_groups: needs group_of");
-        if (cfg.fix_rotations) probe<4>(S, cfg, rot, t, p, q, st);
-        else probe<7>(S, cfg, rot, t, p, q, st);
-        return;
-    }
-    if (cfg.fix_rotations) probe<3>(S, cfg, rot, t, p, q, st);
-    else probe<6>(S, cfg, rot, t, p, q, st);
+    with_cd(cfg, "xm_ctx_ba_probe", [&](auto CD) { probe<CD.value>(S, cfg, rot, t, p, q, st); });
 }
 
 void reprojection_errors(const SchurOp &SO, const double *rot, const double *t, const double *p, const double *focal, double *sqerr, double watchdog_s,
@@ -2181,11 +2116,11 @@ void reprojection_errors(const SchurOp &SO, const double *rot, const double *t, 
     XM_HIP_CHECK(hipMemcpyAsync(T.p, hT.data(), hT.size() * sizeof(double), hipMemcpyHostToDevice, st));
     XM_HIP_CHECK(hipMemcpyAsync(P.p, hP.data(), hP.size() * sizeof(double), hipMemcpyHostToDevice, st));
     if (S.nobs > 0) {
-        if (focal)
-            hipLaunchKernelGGL(ba_sqerr_focal_kernel, dim3(flat_grid(S.nobs)), dim3(256), 0, st, S, (const double *)R.p, (const double *)T.p,
+        auto launch = [&](auto FOCAL) {
+            hipLaunchKernelGGL(ba_sqerr_kernel<FOCAL.value>, dim3(flat_grid(S.nobs)), dim3(256), 0, st, S, (const double *)R.p, (const double *)T.p,
                                (const double *)P.p, (const double *)G.p, out.p);
-        else
-            hipLaunchKernelGGL(ba_sqerr_kernel, dim3(flat_grid(S.nobs)), dim3(256), 0, st, S, (const double *)R.p, (const double *)T.p, (const double *)P.p, out.p);
+        };
+        if (focal) launch(std::true_type{}); else launch(std::false_type{});
         check_launch("the reprojection errors");
         XM_HIP_CHECK(hipMemcpyAsync(sqerr, out.p, (size_t)S.nobs * sizeof(double), hipMemcpyDeviceToHost, st));
     }
