@@ -1268,6 +1268,91 @@ int xm_ctx_filter_tracks(xm_ctx_t *ctx, const xm_tf_options_t *opt, const double
 /* out[0] = observations of the longest landmark that one thread walks (longer ones get a workgroup), out[1] = rays per LDS tile of the
  * workgroup form, out[2] = threads per workgroup (host-only; tests derive their boundary cases from them) */
 int xm_track_filter_limits(int64_t out[3]);
+/* ---- Landmarks from 2-D tracks at given poses: the capability behind step 7 of the reference's fork of GLOMAP, retriangulation
+ * (deps/glomap/glomap/controllers/global_mapper.cc:322-375, controllers/track_retriangulation.cc), as a query on the device over the
+ * observation lists of an XM_STORAGE_SCHUR context.  NOTHING HERE WAS COMPARED WITH THE REFERENCE'S COMPILED CODE: the fork only calls
+ * COLMAP's IncrementalMapper::TriangulateImage and CompleteAndMergeTracks, and COLMAP's sources are not part of it.  Parity rests on
+ * the project's own contract, restated in tests/xm_triangulate_numpy.py and modelled on the structure of COLMAP's triangulator as GLOMAP
+ * configures it: create from two-view samples under an angular error, refine linearly, complete under a reprojection error, require a
+ * minimum triangulation angle.  DESIGN.md 2.23 lists the departures.
+ * Input: rot (3 x 3n), t (3 x n), p (3 x n_landmarks, in-out), column-major, the layouts of xm_ctx_bundle_adjust: R_i is camera-to-world,
+ * t_i the camera centre.  Observation e = (i, l) has the camera-frame point p_e.  The CANDIDATES of a landmark: with candidate == NULL
+ * the observations the bundle adjustment uses (current weight > 0 and p_e2 > 0); otherwise those with candidate[e] != 0 and p_e2 > 0,
+ * whatever their weight (this is how dropped observations come back).  A landmark's LIST is all its observations in input order
+ * (the order of the context's by-landmark list), positions 0 .. L-1; a position that holds no candidate takes part in nothing but keeps
+ * its place in the schedule and in the sums.  Every product and sum below is rounded on its own, in the order written:
+ *   x . y = (x_0 y_0 + x_1 y_1) + x_2 y_2;  |x| = sqrt(x . x); division and square root are IEEE; a comparison with a NaN is false.
+ *   A sum over a list is the pairwise tree over the positions padded with +0.0 to a power of two, adjacent pairs first:
+ *   ((x_0 + x_1) + (x_2 + x_3)) + ...; the term of a position that is masked out is +0.0.
+ *   1 rays        u = p_e0 / p_e2, v = p_e1 / p_e2;  g_r = (R_i[r][0] u + R_i[r][1] v) + R_i[r][2];  b_e = g / |g|;  c_e = t_i.
+ *   2 hypotheses  unordered pairs of positions in the schedule d = 1 .. L / 2 (integer), a = 0 .. L-1, pair (a, (a + d) mod L); for
+ *                 2 d = L only a < L / 2.  That is every pair once; entry h is d = h / L + 1, a = h - (d - 1) L.  The first H =
+ *                 min(max_hypotheses, L (L-1) / 2) entries are tried (counted in pairs_tested for a landmark with two candidates or
+ *                 more).  For the pair (1, 2) = (a, (a + d) mod L):  cs = b_1 . b_2;  w = c_2 - c_1;  d_1 = b_1 . w;  d_2 = b_2 . w;
+ *                 den = 1 - cs cs;  s = (d_1 - cs d_2) / den;  t = (cs d_1 - d_2) / den;  X_k = 0.5 ((c_1k + s b_1k) + (c_2k + t b_2k)),
+ *                 the midpoint of the two closest points.  The pair is a hypothesis iff both positions hold candidates,
+ *                 cs < cos(min_angle), den > 0, s > 0 and t > 0 (counted in hypotheses_scored).
+ *   3 score       the number of candidates with (dx . b_e) / |dx| > cos(create_max_angle_error), dx = X - c_e.  The highest count wins,
+ *                 among equals the earliest entry of the schedule.  lm_support is that count and lm_hypothesis that entry (0 and -1
+ *                 when there is no hypothesis).  No hypothesis, or a count below two: XM_TRI_LM_NO_HYPOTHESIS.  The supporters of the
+ *                 winner are the first members.
+ *   4 refinement and completion, refine_rounds times.  Fewer than two members: XM_TRI_LM_MIN_VIEWS.  Per member, with sc = b . c:
+ *                 A_00 += 1 - b_0 b_0, A_01 += 0 - b_0 b_1, A_02 += 0 - b_0 b_2, A_11 += 1 - b_1 b_1, A_12 += 0 - b_1 b_2,
+ *                 A_22 += 1 - b_2 b_2, r_k += (c_k - b_k sc) + 0 (nine tree sums; no term is -0.0, so the padding cannot show).
+ *                 k_00 = A_11 A_22 - A_12 A_12, k_01 = A_02 A_12 - A_01 A_22, k_02 = A_01 A_12 - A_02 A_11, k_11 = A_00 A_22 - A_02 A_02,
+ *                 k_12 = A_01 A_02 - A_00 A_12, k_22 = A_00 A_11 - A_01 A_01;  det = (A_00 k_00 + A_01 k_01) + A_02 k_02;
+ *                 det not finite and > 0: XM_TRI_LM_DEGENERATE.  X_0 = ((k_00 r_0 + k_01 r_1) + k_02 r_2) / det, X_1 = ((k_01 r_0 +
+ *                 k_11 r_1) + k_12 r_2) / det, X_2 = ((k_02 r_0 + k_12 r_1) + k_22 r_2) / det.  The members afterwards: the candidates
+ *                 with d = X - t_i, q = R_i^T d as in xm_ctx_filter_tracks, q_2 >= 1e-12 and sqrt(uu uu + vv vv) <
+ *                 complete_max_reproj_error for uu = q_0 / q_2 - u, vv = q_1 / q_2 - v (the formulas of XM_TF_REPROJECTION).
+ *   5 acceptance  fewer than max(min_views, 2) members: XM_TRI_LM_MIN_VIEWS; no pair of members with b_e . b_f < cos(min_angle):
+ *                 XM_TRI_LM_ANGLE.  Accepted: p[:, l] = X, keep = the members, lm_views = their number.  Rejected, or without a
+ *                 candidate (XM_TRI_LM_UNUSED): the landmark's column of p comes back bit for bit, keep = 0, lm_views = 0.
+ * The two cosines are computed once on the host, cos(angle * (pi / 180)), and come back in the result.
+ * Output (host arrays): p, keep[nobs], reason[nobs] (XM_TRI_REASON_*; 0 where kept), lm_views, lm_status (XM_TRI_LM_*), lm_support,
+ * lm_hypothesis [n_landmarks].  Result: landmarks per status; observations that are candidates, kept, re-admitted (kept with current
+ * weight <= 0) and lost (used by the bundle adjustment before, not kept); pairs tested and hypotheses scored; seconds_kernels: upload of
+ * (rot, t, candidate) and kernels; seconds_download: the arrays.
+ * On the device (xm_triangulate.h): a thread per observation, a wavefront per landmark of up to xm_triangulate_limits()[0] observations,
+ * a workgroup with tiles of [1] rays per longer one (no limit on the length), a thread per observation again, one fixed-order
+ * reduction; no atomics.  The call reads the context and changes nothing in it; two calls give the same bits, and every output equals the
+ * restatement in numpy exactly.  XM_ERR_ARG (context unchanged and usable): the refusals of xm_ctx_filter_tracks (not
+ * XM_STORAGE_SCHUR, several ranks or a communicator, a struct_size that is not sizeof, null arrays, non-finite input), max_hypotheses < 1, refine_rounds < 1, min_views < 0, an angle outside
+ * (0, 180], a complete_max_reproj_error that is not finite and positive, 2^31 observations or more. */
+#define XM_TRI_LM_ACCEPTED       0
+#define XM_TRI_LM_UNUSED         1       /* no candidate */
+#define XM_TRI_LM_NO_HYPOTHESIS  2
+#define XM_TRI_LM_DEGENERATE     3
+#define XM_TRI_LM_MIN_VIEWS      4
+#define XM_TRI_LM_ANGLE          5
+#define XM_TRI_REASON_NOT_CANDIDATE  1
+#define XM_TRI_REASON_NOT_MEMBER     2   /* a candidate of an accepted landmark that the completion left out */
+#define XM_TRI_REASON_LANDMARK       4   /* a candidate of a landmark that was not accepted */
+typedef struct {
+    uint32_t struct_size;
+    int32_t max_hypotheses;            /* entries of the pair schedule tried per landmark; 64 */
+    double min_angle;                  /* degrees; GLOMAP: 1.0 (track_retriangulation.h:13) */
+    double create_max_angle_error;     /* degrees; COLMAP's default, 2.0 */
+    double complete_max_reproj_error;  /* normalised image units; 1e-2, the project's max_reprojection_error */
+    int32_t min_views;                 /* members an accepted landmark needs (at least 2 are always needed); 2 */
+    int32_t refine_rounds;             /* 2 */
+} xm_tri_options_t;
+#define XM_TRI_OPTIONS_INIT { (uint32_t)sizeof(xm_tri_options_t), 64, 1.0, 2.0, 1e-2, 2, 2 }
+typedef struct {
+    uint32_t struct_size;
+    uint32_t reserved;
+    int64_t lm_accepted, lm_unused, lm_no_hypothesis, lm_degenerate, lm_min_views, lm_angle;
+    int64_t obs_candidates, obs_kept, obs_readmitted, obs_lost;
+    int64_t pairs_tested, hypotheses_scored;
+    double cos_min_angle, cos_create;      /* the thresholds the kernels compared against */
+    double seconds_kernels, seconds_download;
+} xm_tri_result_t;
+int xm_ctx_triangulate_tracks(xm_ctx_t *ctx, const xm_tri_options_t *opt, const double *rot, const double *t, double *p,
+                              const uint8_t *candidate /* nobs or NULL */, uint8_t *keep, uint8_t *reason, int32_t *lm_views,
+                              uint8_t *lm_status, int32_t *lm_support, int32_t *lm_hypothesis, xm_tri_result_t *res);
+/* out[0] = observations of the longest landmark that one wavefront holds (longer ones get a workgroup), out[1] = rays per tile and
+ * hypotheses per batch of the workgroup form, out[2] = threads per workgroup (host-only; tests derive their boundary cases from them) */
+int xm_triangulate_limits(int64_t out[3]);
 /* ---- Pruning weakly connected images by covisibility clusters: step 8 of the reference's fork of GLOMAP, PruneWeaklyConnectedImages
  * (deps/glomap/glomap/processors/reconstruction_pruning.cc:6-84) with ViewGraphManipulater::EstablishStrongClusters
  * (processors/view_graph_manipulation.cc:68-168) and ViewGraph::KeepLargestConnectedComponents / MarkConnectedComponents

@@ -14,6 +14,7 @@
 #include "xm_lm_loop.h"
 #include "xm_clean.h"
 #include "xm_trackfilter.h"
+#include "xm_triangulate.h"
 #include "xm_prune.h"
 #include "xm_lift.h"
 #include "xm_tracks.h"
@@ -984,6 +985,61 @@ int xm_track_filter_limits(int64_t out[3]) {
     XM_TRY
     if (!out) throw xm::Error(XM_ERR_ARG, "xm_track_filter_limits: null argument");
     out[0] = xm::kSchurHeavy; out[1] = xm::kTfTile; out[2] = xm::kTfThreads;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_ctx_triangulate_tracks(xm_ctx_t *ctx, const xm_tri_options_t *opt, const double *rot, const double *t, double *p, const uint8_t *candidate,
+                              uint8_t *keep, uint8_t *reason, int32_t *lm_views, uint8_t *lm_status, int32_t *lm_support, int32_t *lm_hypothesis,
+                              xm_tri_result_t *res) {
+    XM_TRY
+    const std::string w("xm_ctx_triangulate_tracks");
+    if (!ctx || !opt || !rot || !t || !p || !keep || !reason || !lm_views || !lm_status || !lm_support || !lm_hypothesis || !res)
+        throw xm::Error(XM_ERR_ARG, w + ": null argument");
+    if (opt->struct_size != sizeof(xm_tri_options_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_tri_options_t.struct_size is not sizeof(xm_tri_options_t)");
+    if (res->struct_size != sizeof(xm_tri_result_t)) throw xm::Error(XM_ERR_ARG, w + ": xm_tri_result_t.struct_size is not sizeof(xm_tri_result_t)");
+    if (opt->max_hypotheses < 1) throw xm::Error(XM_ERR_ARG, w + ": max_hypotheses must be at least 1");
+    if (opt->refine_rounds < 1) throw xm::Error(XM_ERR_ARG, w + ": refine_rounds must be at least 1");
+    if (opt->min_views < 0) throw xm::Error(XM_ERR_ARG, w + ": min_views is negative");
+    if (!(opt->min_angle > 0.0 && opt->min_angle <= 180.0)) throw xm::Error(XM_ERR_ARG, w + ": min_angle must be positive and at most 180 degrees");
+    if (!(opt->create_max_angle_error > 0.0 && opt->create_max_angle_error <= 180.0))
+        throw xm::Error(XM_ERR_ARG, w + ": create_max_angle_error must be positive and at most 180 degrees");
+    if (!(std::isfinite(opt->complete_max_reproj_error) && opt->complete_max_reproj_error > 0.0))
+        throw xm::Error(XM_ERR_ARG, w + ": complete_max_reproj_error must be finite and positive");
+    if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, w + ": single-GPU contexts only (not n_gpus > 1)");
+    if (ctx->impl->world() > 1) throw xm::Error(XM_ERR_ARG, w + ": single-rank contexts only");
+    const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks();
+    for (int64_t k = 0; k < 9 * n; ++k)
+        if (!std::isfinite(rot[k])) throw xm::Error(XM_ERR_ARG, w + ": rotations are not finite");
+    for (int64_t k = 0; k < 3 * n; ++k)
+        if (!std::isfinite(t[k])) throw xm::Error(XM_ERR_ARG, w + ": translations are not finite");
+    for (int64_t k = 0; k < 3 * m; ++k)
+        if (!std::isfinite(p[k])) throw xm::Error(XM_ERR_ARG, w + ": landmarks are not finite");
+    xm::TriSettings c;
+    c.max_hypotheses = opt->max_hypotheses; c.refine_rounds = opt->refine_rounds; c.min_views = opt->min_views;
+    c.complete_max_reproj_error = opt->complete_max_reproj_error;
+    // the cosines of the two angles, once, on the host; the kernels compare against these doubles
+    constexpr double kPi = 3.14159265358979323846;
+    c.cos_min_angle = std::cos(opt->min_angle * (kPi / 180.0));
+    c.cos_create = std::cos(opt->create_max_angle_error * (kPi / 180.0));
+    xm::TriOutcome r;
+    ctx->impl->triangulate_tracks(c, rot, t, p, candidate, keep, reason, lm_views, lm_status, lm_support, lm_hypothesis, r);
+    xm_tri_result_t out;
+    std::memset(&out, 0, sizeof(out));
+    out.struct_size = sizeof(xm_tri_result_t);
+    out.lm_accepted = r.lm[XM_TRI_LM_ACCEPTED]; out.lm_unused = r.lm[XM_TRI_LM_UNUSED]; out.lm_no_hypothesis = r.lm[XM_TRI_LM_NO_HYPOTHESIS];
+    out.lm_degenerate = r.lm[XM_TRI_LM_DEGENERATE]; out.lm_min_views = r.lm[XM_TRI_LM_MIN_VIEWS]; out.lm_angle = r.lm[XM_TRI_LM_ANGLE];
+    out.obs_candidates = r.obs_candidates; out.obs_kept = r.obs_kept; out.obs_readmitted = r.obs_readmitted; out.obs_lost = r.obs_lost;
+    out.pairs_tested = r.pairs_tested; out.hypotheses_scored = r.hypotheses_scored;
+    out.cos_min_angle = c.cos_min_angle; out.cos_create = c.cos_create;
+    out.seconds_kernels = r.seconds_kernels; out.seconds_download = r.seconds_download;
+    *res = out;
+    return XM_OK;
+    XM_CATCH
+}
+int xm_triangulate_limits(int64_t out[3]) {
+    XM_TRY
+    if (!out) throw xm::Error(XM_ERR_ARG, "xm_triangulate_limits: null argument");
+    out[0] = xm::kSchurHeavy; out[1] = xm::kTriTile; out[2] = xm::kTriThreads;
     return XM_OK;
     XM_CATCH
 }

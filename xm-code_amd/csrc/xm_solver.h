@@ -127,6 +127,8 @@ struct CleanSettings;  // xm_clean.h
 struct CleanOutcome;
 struct TfSettings;     // xm_trackfilter.h
 struct TfOutcome;
+struct TriSettings;    // xm_triangulate.h
+struct TriOutcome;
 struct PruneSettings;  // xm_prune.h
 struct PrunePairs;
 struct PruneOutcome;
@@ -184,6 +186,9 @@ public:
     // GLOMAP's track filters at (rot, t, p) with the current weights (xm_trackfilter.h); cfg.watchdog_s is the context's
     void filter_tracks(const TfSettings &cfg, const double *rot, const double *t, const double *p, uint8_t *keep, uint8_t *reason,
                        int32_t *lm_views, uint8_t *lm_status, TfOutcome &out);
+    // landmarks from the rays of their observations at (rot, t) (xm_triangulate.h); p in-out; cfg.watchdog_s is the context's
+    void triangulate_tracks(const TriSettings &cfg, const double *rot, const double *t, double *p, const uint8_t *candidate, uint8_t *keep,
+                            uint8_t *reason, int32_t *lm_views, uint8_t *lm_status, int32_t *lm_support, int32_t *lm_hypothesis, TriOutcome &out);
     // covisibility clusters of the cameras at the current weights (xm_prune.h); changes nothing here
     void prune_weakly_connected(const PruneSettings &cfg, int32_t *cluster_id, int32_t *obs_count, const PrunePairs *pairs, PruneOutcome &out);
     // which observations, cameras and landmarks of the list survive cleaning at the current weights (xm_clean.h); changes nothing here

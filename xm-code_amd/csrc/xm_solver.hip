@@ -17,6 +17,7 @@
 #include "xm_gp.h"
 #include "xm_clean.h"
 #include "xm_trackfilter.h"
+#include "xm_triangulate.h"
 #include "xm_prune.h"
 
 #include <algorithm>
@@ -2490,6 +2491,15 @@ void Context::filter_tracks(const TfSettings &cfg, const double *rot, const doub
     TfSettings c = cfg;
     c.watchdog_s = cfg_.watchdog_s;
     xm::filter_tracks(*schur_, c, rot, t, p, keep, reason, lm_views, lm_status, out, st_);
+}
+void Context::triangulate_tracks(const TriSettings &cfg, const double *rot, const double *t, double *p, const uint8_t *candidate, uint8_t *keep,
+                                 uint8_t *reason, int32_t *lm_views, uint8_t *lm_status, int32_t *lm_support, int32_t *lm_hypothesis, TriOutcome &out) {
+    if (!schur_)
+        throw Error(XM_ERR_ARG, "xm_ctx_triangulate_tracks: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
+    if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_triangulate_tracks: single-rank contexts only");
+    TriSettings c = cfg;
+    c.watchdog_s = cfg_.watchdog_s;
+    xm::triangulate_tracks(*schur_, c, rot, t, p, candidate, keep, reason, lm_views, lm_status, lm_support, lm_hypothesis, out, st_);
 }
 void Context::prune_weakly_connected(const PruneSettings &cfg, int32_t *cluster_id, int32_t *obs_count, const PrunePairs *pairs, PruneOutcome &out) {
     if (!schur_)

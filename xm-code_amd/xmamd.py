@@ -48,6 +48,7 @@ EXPORTS = [
     "xm_view_graph_calibrate", "xm_view_graph_calibrate_probe", "xm_view_graph_calibrate_limits",
     "xm_view_graph_rotations", "xm_view_graph_rotations_probe", "xm_view_graph_rotations_limits",
     "xm_ctx_filter_tracks", "xm_track_filter_limits",
+    "xm_ctx_triangulate_tracks", "xm_triangulate_limits",
     "xm_prune_weakly_connected", "xm_ctx_prune_weakly_connected", "xm_prune_limits",
     "xm_ctx_global_positioning", "xm_ctx_gp_probe", "xm_gp_limits",
     "xm_ctx_global_positioning_pairs", "xm_ctx_gp_probe_pairs", "xm_gp_pair_limits",
@@ -285,6 +286,20 @@ class TfResult(C.Structure):       # xm_tf_result_t
                [(k, C.c_double) for k in ("cos_angle", "cos_triangulation", "seconds_kernels", "seconds_download")]
 
 
+class TriOptions(C.Structure):     # xm_tri_options_t; the defaults are XM_TRI_OPTIONS_INIT
+    _fields_ = [("struct_size", C.c_uint32), ("max_hypotheses", C.c_int32), ("min_angle", C.c_double), ("create_max_angle_error", C.c_double),
+                ("complete_max_reproj_error", C.c_double), ("min_views", C.c_int32), ("refine_rounds", C.c_int32)]
+
+
+TRI_COUNTS = ("lm_accepted", "lm_unused", "lm_no_hypothesis", "lm_degenerate", "lm_min_views", "lm_angle", "obs_candidates", "obs_kept",
+              "obs_readmitted", "obs_lost", "pairs_tested", "hypotheses_scored")
+
+
+class TriResult(C.Structure):      # xm_tri_result_t
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_int64) for k in TRI_COUNTS] + \
+               [(k, C.c_double) for k in ("cos_min_angle", "cos_create", "seconds_kernels", "seconds_download")]
+
+
 class PruneOptions(C.Structure):   # xm_prune_options_t; the defaults are GLOMAP's (XM_PRUNE_OPTIONS_INIT)
     _fields_ = [("struct_size", C.c_uint32), ("min_covisibility", C.c_int32), ("min_num_images", C.c_int32), ("min_num_observations", C.c_int32),
                 ("min_threshold", C.c_double)]
@@ -452,6 +467,8 @@ CLEAN_NO_SWAP = 1
 TF_REPROJECTION, TF_ANGLE, TF_TRIANGULATION = 1, 2, 4                     # xm_tf_options_t.flags
 TF_REASON_DEPTH, TF_REASON_REPROJECTION, TF_REASON_ANGLE, TF_REASON_TRIANGULATION, TF_REASON_MIN_VIEWS = 1, 2, 4, 8, 16   # reason[e]
 TF_LM_KEPT, TF_LM_UNUSED, TF_LM_TRIANGULATION, TF_LM_MIN_VIEWS = 0, 1, 2, 3   # lm_status[l]
+TRI_LM_ACCEPTED, TRI_LM_UNUSED, TRI_LM_NO_HYPOTHESIS, TRI_LM_DEGENERATE, TRI_LM_MIN_VIEWS, TRI_LM_ANGLE = 0, 1, 2, 3, 4, 5   # lm_status[l]
+TRI_REASON_NOT_CANDIDATE, TRI_REASON_NOT_MEMBER, TRI_REASON_LANDMARK = 1, 2, 4   # reason[e]
 BA_PROBE_DENSE_MAX_ROWS = 4096
 BA_FIX_ROTATIONS = 1
 BA_NONMONOTONIC = 2
@@ -551,6 +568,8 @@ def lib():
         L.xm_tracks_split_stats.argtypes = [C.c_void_p]
         L.xm_ctx_filter_tracks.argtypes = [C.c_void_p, C.POINTER(TfOptions)] + [C.c_void_p] * 7 + [C.POINTER(TfResult)]
         L.xm_track_filter_limits.argtypes = [C.c_void_p]
+        L.xm_ctx_triangulate_tracks.argtypes = [C.c_void_p, C.POINTER(TriOptions)] + [C.c_void_p] * 10 + [C.POINTER(TriResult)]
+        L.xm_triangulate_limits.argtypes = [C.c_void_p]
         L.xm_ctx_global_positioning.argtypes = [C.c_void_p, C.POINTER(GpOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GpResult)]
         L.xm_ctx_gp_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GpProbe)]
         L.xm_gp_limits.argtypes = [C.c_void_p]
@@ -1128,6 +1147,45 @@ def track_filter_limits():
     of the workgroup form, threads: per workgroup)"""
     out = np.zeros(3, dtype=np.int64)
     _chk(lib().xm_track_filter_limits(out.ctypes.data_as(C.c_void_p)))
+    return dict(light_max=int(out[0]), tile=int(out[1]), threads=int(out[2]))
+
+
+class TriangulationPlan:
+    """what Context.triangulate_tracks found: P (3 x m: the triangulated point of every accepted landmark, the column that was given for
+    every other), keep (bool per observation: a member of an accepted landmark), reason (uint8 per observation: TRI_REASON_*, 0 where
+    kept), views (int32 per landmark: members), status (uint8 per landmark: TRI_LM_*), support and hypothesis (int32 per landmark: the
+    winning count and its entry of the pair schedule, -1 when there was none) and info, the fields of xm_tri_result_t"""
+
+    def __init__(self, P, keep, reason, views, status, support, hypothesis, info):
+        self.P, self.keep, self.reason, self.views, self.status = P, keep, reason, views, status
+        self.support, self.hypothesis, self.info = support, hypothesis, info
+
+    def weights(self, w):
+        """w (one weight per observation) where kept and 0 elsewhere: the argument of Context.set_edge_weights (give it the weights the
+        candidates had before they were dropped, so that a re-admitted observation gets its weight back)"""
+        w = np.array(w, dtype=np.float64).reshape(-1)
+        if w.shape != self.keep.shape:
+            raise XmError("TriangulationPlan.weights: w must have one entry per observation of the list")
+        w[~self.keep] = 0.0
+        return w
+
+    def apply(self, *per_observation):
+        """the rows of the kept observations, in input order, of every array given (cam, lm, p, w, ...)"""
+        k = self.keep
+        out = []
+        for a in per_observation:
+            a = np.asarray(a)
+            if a.shape[:1] != k.shape:
+                raise XmError("TriangulationPlan.apply: a per-observation array has another length than the list")
+            out.append(a[k])
+        return tuple(out)
+
+
+def triangulate_limits():
+    """-> dict(light_max: observations of the longest landmark that one wavefront holds in Context.triangulate_tracks (longer ones get a
+    workgroup), tile: rays per tile and hypotheses per batch of the workgroup form, threads: per workgroup)"""
+    out = np.zeros(3, dtype=np.int64)
+    _chk(lib().xm_triangulate_limits(out.ctypes.data_as(C.c_void_p)))
     return dict(light_max=int(out[0]), tile=int(out[1]), threads=int(out[2]))
 
 
@@ -2668,6 +2726,121 @@ class Context:
                                         status.ctypes.data_as(C.c_void_p), C.byref(res)))
         info = {k: getattr(res, k) for k, _ in TfResult._fields_ if k not in ("struct_size", "reserved")}
         return TrackFilterPlan(keep.astype(bool), reason, views, status, info)
+
+    def triangulate_tracks(self, rot, t, P=None, candidates=None, max_hypotheses=64, min_angle=1.0, create_angle=2.0, complete_reprojection=1e-2,
+                           min_views=2, refine_rounds=2):
+        """every landmark of this context from the rays of its observations at the poses (rot, t) -- the layouts of bundle_adjust -- on the
+        device (xm_ctx_triangulate_tracks; include/xm_amd.h has the contract): a search over two-view midpoints in a fixed pair schedule
+        (at most max_hypotheses per landmark, scored by the candidates within create_angle degrees), refine_rounds of a linear multi-view
+        solve with completion under complete_reprojection (normalised image units), and acceptance with min_views members and a pair of
+        them at least min_angle degrees apart.  candidates: None -- the observations of CURRENT weight > 0; a bool mask, or weights whose
+        positive entries are the candidates, whatever the context's weights are: this is how dropped observations come back.  P: the
+        columns that rejected landmarks keep (None: zeros).  Matrix-free contexts only, nothing in the context changes.
+        -> TriangulationPlan; ctx.set_edge_weights(plan.weights(w)) makes the next bundle_adjust use exactly what it kept."""
+        rot = np.asfortranarray(np.asarray(rot, dtype=np.float64)); t = np.asfortranarray(np.asarray(t, dtype=np.float64))
+        m = getattr(self, "n_landmarks", 0)   # (a context of another storage has no landmarks: sized for nothing, the library refuses it)
+        nobs = getattr(self, "ne", 0)
+        P = np.zeros((3, m), order="F") if P is None else np.array(P, dtype=np.float64, order="F", copy=True)
+        assert rot.shape == (3, 3 * self.n) and t.shape == (3, self.n) and P.shape == (3, m)
+        for name, v in (("min_angle", min_angle), ("create_angle", create_angle), ("complete_reprojection", complete_reprojection)):
+            if not (np.isfinite(v) and float(v) > 0.0):
+                raise XmError(f"triangulate_tracks: {name} must be finite and positive")
+        if int(max_hypotheses) < 1 or int(refine_rounds) < 1 or int(min_views) < 0:
+            raise XmError("triangulate_tracks: max_hypotheses and refine_rounds must be at least 1, min_views not negative")
+        cand = None
+        if candidates is not None:
+            c = np.asarray(candidates).reshape(-1)
+            if c.size != nobs:
+                raise XmError("triangulate_tracks: candidates must have one entry per observation")
+            cand = np.ascontiguousarray(c if c.dtype == bool else c > 0, dtype=np.uint8)
+        opt = TriOptions(); res = TriResult()
+        opt.struct_size, res.struct_size = C.sizeof(TriOptions), C.sizeof(TriResult)
+        opt.max_hypotheses, opt.min_views, opt.refine_rounds = int(max_hypotheses), int(min_views), int(refine_rounds)
+        opt.min_angle, opt.create_max_angle_error, opt.complete_max_reproj_error = float(min_angle), float(create_angle), float(complete_reprojection)
+        keep = np.zeros(nobs, dtype=np.uint8); reason = np.zeros(nobs, dtype=np.uint8)
+        views = np.zeros(m, dtype=np.int32); status = np.zeros(m, dtype=np.uint8)
+        support = np.zeros(m, dtype=np.int32); hyp = np.zeros(m, dtype=np.int32)
+        _chk(lib().xm_ctx_triangulate_tracks(self.h, C.byref(opt), rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                             P.ctypes.data_as(C.c_void_p), None if cand is None else cand.ctypes.data_as(C.c_void_p),
+                                             keep.ctypes.data_as(C.c_void_p), reason.ctypes.data_as(C.c_void_p), views.ctypes.data_as(C.c_void_p),
+                                             status.ctypes.data_as(C.c_void_p), support.ctypes.data_as(C.c_void_p), hyp.ctypes.data_as(C.c_void_p),
+                                             C.byref(res)))
+        info = {k: getattr(res, k) for k, _ in TriResult._fields_ if k not in ("struct_size", "reserved")}
+        return TriangulationPlan(P, keep.astype(bool), reason, views, status, support, hyp, info)
+
+    def retriangulate(self, rot, t, P, rounds=1, weights=None, restore_weights=False, reprojection=1e-2, triangulation=1.0, min_views=0,
+                      **bundle_adjust_kwargs):
+        """GLOMAP's retriangulation step (controllers/global_mapper.cc:322-375) on this context:
+          for ite < rounds (:327): triangulate_tracks at the current poses with candidates = weights > 0 (:328-336, where the fork calls
+            COLMAP's triangulator: RetriangulateTracks), the context's weights become plan.weights(weights), bundle_adjust (:339-344),
+            filter_tracks(reprojection) (:347-354; the fork filters at its fixed threshold here, with no scaling), bundle_adjust (:355-356);
+          then the reprojection filter (:364-369) and the triangulation-angle filter (:370-374; None: not run).
+        weights: the ENTRY weights, what every observation weighs when it is used (default: the context's current weights); an
+        observation that an earlier filter set to 0 comes back when it is positive here and the triangulation at the current poses
+        takes it as a member.  THIS METHOD CHANGES THE CONTEXT'S WEIGHTS; restore_weights=True puts back the ones it had when the
+        method was called.  min_views goes to every filter call, bundle_adjust_kwargs to every bundle_adjust.
+        A round that would leave a camera without a weighted observation raises XmError naming the cameras (set_edge_weights refuses
+        such a list); the context then has the weights it had at entry.
+        Departures from the reference: those of triangulate_tracks, no NormalizeReconstruction (:358) and no
+        UndistortImages (:346).
+        -> (rot, t, P, info): info["rounds"] one record per round (triangulation: the plan's counters; ba_first / ba_second: status and
+        costs; filter: dropped, tracks_changed, tracks_total), info["final"] the records of the closing filters, info["keep"] the
+        observations it ends with, info["weights"] the weights it ends with (before a restore)."""
+        if int(rounds) < 0:
+            raise XmError("retriangulate: rounds is negative")
+        w_ctx = getattr(self, "_w", None)
+        w_in = w_ctx if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w_in is None or w_ctx is None:
+            raise XmError("retriangulate: the context's current weights are not known here (xm2_round filters inside the library): "
+                          "call set_edge_weights first")
+        if w_in.size != self.ne:
+            raise XmError("retriangulate: weights must have one entry per observation")
+        w_entry = w_ctx.copy()
+        state = {"w": w_ctx.copy(), "changed": False}
+
+        def give(w, what):
+            cam = getattr(self, "_cam", None)
+            if cam is not None:
+                empty = np.nonzero(np.bincount(np.asarray(cam)[w > 0], minlength=self.n) == 0)[0]
+                if empty.size:
+                    if state["changed"]:
+                        self.set_edge_weights(w_entry)
+                    raise XmError(f"retriangulate: {what} would leave no weighted observation for cameras {empty.tolist()}")
+            try:
+                self.set_edge_weights(w)
+            except XmError:
+                if state["changed"]:
+                    self.set_edge_weights(w_entry)
+                raise
+            state["w"] = w; state["changed"] = True
+
+        def run_filter(rep, tri):
+            plan = self.filter_tracks(rot, t, P, reprojection=rep, angle=None, triangulation=tri, min_views=min_views)
+            dropped = int(np.count_nonzero(plan.reason))
+            if dropped:
+                give(plan.weights(state["w"]), "a filter")
+            changed = plan.info["tracks_changed_reprojection"] if rep is not None else plan.info["tracks_changed_triangulation"]
+            return dict(reprojection=rep, triangulation=tri, dropped=dropped, tracks_changed=int(changed),
+                        tracks_total=int(plan.info["tracks_total"]), info=plan.info)
+
+        def ba_record(i):
+            return {k: i[k] for k in ("status", "status_name", "iters", "initial_cost", "final_cost", "n_used")}
+        records = []
+        for ite in range(int(rounds)):                                                   # :327
+            plan = self.triangulate_tracks(rot, t, P, candidates=w_in > 0)               # :328-336
+            P = plan.P
+            give(plan.weights(w_in), "the triangulation")
+            rot, t, P, i1 = self.bundle_adjust(rot, t, P, **bundle_adjust_kwargs)        # :339-344
+            f = run_filter(reprojection, None)                                           # :347-354
+            rot, t, P, i2 = self.bundle_adjust(rot, t, P, **bundle_adjust_kwargs)        # :355-356
+            records.append(dict(ite=ite, triangulation=plan.info, ba_first=ba_record(i1), filter=f, ba_second=ba_record(i2)))
+        final = [run_filter(reprojection, None)]                                         # :364-369
+        if triangulation is not None:
+            final.append(run_filter(None, triangulation))                                # :370-374
+        info = dict(rounds=records, final=final, keep=state["w"] > 0, weights=state["w"])
+        if restore_weights and state["changed"]:
+            self.set_edge_weights(w_entry)
+        return rot, t, P, info
 
     def prune_weakly_connected(self, min_covisibility=5, min_num_images=2, min_num_observations=0, min_threshold=20.0, pairs=False):
         """GLOMAP's PruneWeaklyConnectedImages (reconstruction_pruning.cc:6-84) over this context's observations at their CURRENT weights,
