@@ -206,6 +206,12 @@ typedef struct {
                                      * on one GPU with the host-driven outer iteration and the f64 symmetric dense pair at ranks 3 and 4, the sweep of
                                      * iteration i carries the step of iteration i - 1 in its own launch and forms its product input itself.  Same bits
                                      * either way (xm_ctx_tcg_two_launch says which form a solve ran) */
+#define XM_FLAG_TCG_RECOMPUTE 512u  /* recompute the truncated CG behind a rejected step.  The default, on one GPU with the host-driven outer iteration
+                                     * and every storage but the matrix-free one (not: several ranks, XM_FLAG_HOST_STEPPED, XM_FLAG_HOST_OUTER, the
+                                     * device-driven outer iteration), replays it: a rejection keeps the point, so the next truncated CG differs only
+                                     * in its radius and repeats the rejected one's iterations bit for bit up to the one at which the smaller radius
+                                     * trips.  The steps keep their direction and Hessian product (64 iterations, xm_ctx_set_tcg_history) and one launch
+                                     * rebuilds the step from them, without a product.  Same bits either way (xm_ctx_tcg_replay counts the replays) */
 #define XM_FLAG_WARM_R        16u   /* XM_MODE_REBUTTLE: start the rank-3 stage from opt.R_ini instead of the identity stack.  The reference
                                        reads R_ini.bin and then overwrites it with the identity (XM_main.cu:41,95-103); this flag honours it,
                                        which is what makes the second solve of the XM^2 loop cheap */
@@ -239,9 +245,11 @@ typedef struct {
     int32_t rank;              /* columns of R that are valid (what R.bin would hold) */
     int32_t status;            /* XM_STATUS_* */
     double primal, dual, min_eig, gap;
-    int64_t tcg_iters;         /* sum over outer iterations of (i+1) — the reference's "Total iteration" */
+    int64_t tcg_iters;         /* sum over outer iterations of (i+1) — the reference's "Total iteration".  A truncated CG that is replayed from the
+                                  history of a rejected step (XM_FLAG_TCG_RECOMPUTE) counts the i+1 iterations it stands for, although none of them ran */
     int64_t outer_iters;
-    int64_t qw_products;       /* launches of the Q*W kernel (any epilogue) */
+    int64_t qw_products;       /* launches of the Q*W kernel (any epilogue): a replayed truncated CG launches none, so this is smaller than with
+                                  XM_FLAG_TCG_RECOMPUTE while tcg_iters is the same */
     int64_t lanczos_iters;
     double seconds;            /* wall clock of the whole solve (Q already resident) */
     double tr_seconds;         /* time inside the trust-region loops */
@@ -1034,6 +1042,15 @@ int xm_ctx_schur_info(xm_ctx_t *ctx, int *uses_cg, int64_t stats[3], double *las
 /* *count = trust regions (rank levels) of the context's LAST xm_ctx_solve whose truncated CG ran in the two-launch form (XM_FLAG_TCG_THREE_LAUNCH,
  * or a configuration that form does not cover: 0).  Single-GPU contexts; XM_ERR_ARG otherwise.  (A getter, not a field: xm_result_t keeps its size.) */
 int xm_ctx_tcg_two_launch(xm_ctx_t *ctx, int *count);
+/* out[0] = truncated CGs of the context's LAST xm_ctx_solve that were replayed from the history of a rejected step instead of recomputed, out[1] = the
+ * iterations they stand for (counted in tcg_iters, not executed).  Both 0 with XM_FLAG_TCG_RECOMPUTE or where the replay does not apply.
+ * Single-GPU contexts; XM_ERR_ARG otherwise.  (A getter, not a field: xm_result_t keeps its size.) */
+int xm_ctx_tcg_replay(xm_ctx_t *ctx, int64_t out[2]);
+/* Iterations of a truncated CG whose direction and Hessian product are kept for that replay, from the context's next xm_ctx_solve on: 0 = the
+ * default (64), 1 .. 256; anything else XM_ERR_ARG.  A rejected truncated CG that needs more iterations than this at the smaller radius is
+ * recomputed, so the setting changes time and memory (2 x iterations x (3n x pitch + n) doubles), never a result.  Tests force small values.
+ * (A setter, not a field: xm_tuning_t keeps its size.)  Single-GPU contexts; XM_ERR_ARG otherwise. */
+int xm_ctx_set_tcg_history(xm_ctx_t *ctx, int32_t iterations);
 /* ... and the preconditioner of the CG form: *kind = -1 no CG form (dense inverse, or not a matrix-free context), 0 Jacobi (schur_solver 2 or
  * auto), 1 two-level (schur_solver 3; *aggregates = their number n_c, *block = cameras per aggregate).  aggregates / block may be NULL. */
 int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int *block);

@@ -421,6 +421,20 @@ int xm_ctx_tcg_two_launch(xm_ctx_t *ctx, int *count) {
     return XM_OK;
     XM_CATCH
 }
+int xm_ctx_tcg_replay(xm_ctx_t *ctx, int64_t out[2]) {
+    XM_TRY
+    if (!ctx || !ctx->impl || !out) throw xm::Error(XM_ERR_ARG, "xm_ctx_tcg_replay: single-GPU context and a non-null output needed");
+    ctx->impl->tcg_replay_counts(out);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_ctx_set_tcg_history(xm_ctx_t *ctx, int32_t iterations) {
+    XM_TRY
+    if (!ctx || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_set_tcg_history: single-GPU context needed");
+    ctx->impl->set_tcg_history(iterations);
+    return XM_OK;
+    XM_CATCH
+}
 int xm_ctx_schur_info(xm_ctx_t *ctx, int *uses_cg, int64_t stats[3], double *last_relres) {
     XM_TRY
     if (!ctx || !ctx->impl || !uses_cg) throw xm::Error(XM_ERR_ARG, "xm_ctx_schur_info: single-GPU context and a non-null output needed");

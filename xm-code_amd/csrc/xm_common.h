@@ -262,6 +262,34 @@ struct TcgParity {
     double *partsB_out;   // this rank's |r|^2 partials in the OTHER parity: written by the step that ends this iteration
 };
 
+// History of a truncated CG, for the replay of a rejected step (tcg_replay_kernel): the step of iteration j < H stores the direction p_j and its
+// Hessian product Hp_j -- it holds both in registers -- into slot j, and its lead thread the scalar block and the three sums it decided from.
+// A truncated CG that starts from the same point with a smaller radius repeats these iterations bit for bit up to the one at which the radius
+// trips, so it needs no product.  All pointers nullptr: nothing is stored (every path that does not replay).
+struct TcgRec {
+    TcgScal sc;               // as passed to tcg_next: with the exact |r|^2
+    double pHp, rHp, HpHp;
+};
+struct TcgHist {
+    double *vec = nullptr;    // H slots of [p_R | Hp_R], nloc*3*OP doubles each
+    double *cam = nullptr;    // H slots of [p_s | Hp_s], nloc doubles each
+    TcgRec *rec = nullptr;    // H records
+    int H = 0;
+};
+constexpr int kTcgHistDefault = 64, kTcgHistMax = 256;   // (a record per thread of tcg_replay_kernel's workgroup)
+constexpr int kTcgNotCovered = 10;                       // progress-word status of a replay whose records ran out before a stop
+struct TcgReplayArgs {
+    int nloc;
+    TcgHist hist;
+    int nrec;                 // records the rejected truncated CG wrote
+    double delta;             // the new radius
+    double *vR, *vs, *HvR, *Hvs;   // rebuilt from zero; HvR == nullptr: XM_FLAG_MODEL_RECURRENCE
+    TcgScal *scal_out;
+    unsigned long long *hstat;
+    int seq;
+};
+void launch_tcg_replay(int o, const TcgReplayArgs &a, hipStream_t st);
+
 // Host-side arguments of tcg_init_kernel and cg_step_kernel: Context::tcg_init_args / cg_step_args build them for a solve, the launchers unpack
 // them into the kernels' positional parameters.
 struct TcgInitArgs {
@@ -287,6 +315,7 @@ struct CgStepArgs {
     double *Afull, *Wfull;             // multi-rank: replicated image of the residual / the whole product input
     int grouping;
     PeerXchg xchg;
+    TcgHist hist;                      // where the step records itself for a replay (all nullptr: nowhere)
 };
 
 // Step i - 1 of a truncated CG as the symmetric sweep of iteration i carries it (two-launch form, launch_qw_sym with a step): the step's
@@ -299,6 +328,7 @@ struct TcgFuse {
     const double *HpR, *Hps, *R, *s, *pR_cur, *ps_cur, *rR_cur, *rs_cur;
     double *pR_next, *ps_next, *rR_next, *rs_next, *vR, *vs, *HvR, *Hvs, *Wloc, *partsB_out;
     unsigned long long *hstat;
+    TcgHist hist;
 };
 // doubles of the product input a sweep workgroup derives for its 4 K steps (LDS): a plan with longer chunks keeps the three-launch form
 constexpr int kSvDeriveRows = 768;

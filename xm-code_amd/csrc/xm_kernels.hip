@@ -364,7 +364,7 @@ __device__ __forceinline__ void cg_step_body(int bid, int nblk, int nloc, const 
                                              const double *__restrict__ ps_cur, double *ps_next, double *vR, double *vs, double *HvR, double *Hvs,
                                              const double *rR_cur, double *rR_next, const double *__restrict__ rs_cur, double *rs_next, double *Wloc,
                                              double *partsB_out, unsigned long long *hstat, int b_off, int64_t mat, double *Afull, double *Wfull, int grp,
-                                             const PeerXchg *xp, double *Wpad);
+                                             const PeerXchg *xp, double *Wpad, const TcgHist &hist);
 template <int O, bool TRACE, bool DERIVE>
 __device__ __forceinline__ void qw_symv_body(const double *__restrict__ Q, int64_t ld, const double *__restrict__ W, int nloc, int Kc, int Kf, int ysplit, int nt_step0,
                                              const TcgScal *__restrict__ scal, double *__restrict__ Prow,
@@ -380,7 +380,7 @@ __device__ __forceinline__ void qw_symv_body(const double *__restrict__ Q, int64
             if (bid < fu.nB)
                 cg_step_body<O, false>(bid, fu.nB, nloc, fu.scal_cur, fu.scal_next, fu.parts, fu.nA, fu.nB, 1, fu.HpR, fu.Hps, fu.R, fu.s, fu.pR_cur, fu.pR_next,
                                        fu.ps_cur, fu.ps_next, fu.vR, fu.vs, fu.HvR, fu.Hvs, fu.rR_cur, fu.rR_next, fu.rs_cur, fu.rs_next, fu.Wloc,
-                                       fu.partsB_out, fu.hstat, 0, (int64_t)nloc * 3 * OP, nullptr, nullptr, fu.grp, nullptr, nullptr);
+                                       fu.partsB_out, fu.hstat, 0, (int64_t)nloc * 3 * OP, nullptr, nullptr, fu.grp, nullptr, nullptr, fu.hist);
             return;
         }
     }
@@ -1122,7 +1122,7 @@ __device__ __forceinline__ void cg_step_body(int bid, int nblk, int nloc, const 
                                              const double *__restrict__ ps_cur, double *ps_next, double *vR, double *vs, double *HvR, double *Hvs,
                                              const double *rR_cur, double *rR_next, const double *__restrict__ rs_cur, double *rs_next, double *Wloc,
                                              double *partsB_out, unsigned long long *hstat, int b_off, int64_t mat, double *Afull, double *Wfull, int grp,
-                                             const PeerXchg *xp, double *Wpad) {
+                                             const PeerXchg *xp, double *Wpad, const TcgHist &hist) {
     constexpr int OP = pitch_of(O);
     __shared__ double sh[4];
     __shared__ double sh16[16];
@@ -1250,6 +1250,14 @@ __device__ __forceinline__ void cg_step_body(int bid, int nblk, int nloc, const 
     }
     TcgScal sc = sc0;
     if (sc0.iter > 0) sc.rr = rr_prev;   // exact |r|^2 summed by the previous iteration
+    // the iteration's slot of the history (TcgHist): what it decided from, and below p and Hp as they are read
+    const bool rec = hist.vec != nullptr && sc0.iter < hist.H;
+    double *const hR = rec ? hist.vec + (size_t)sc0.iter * 2 * (size_t)total : nullptr;
+    double *const hS = rec ? hist.cam + (size_t)sc0.iter * 2 * (size_t)nloc : nullptr;
+    if (lead && rec) {
+        TcgRec *q = hist.rec + sc0.iter;
+        q->sc = sc; q->pHp = pHp; q->rHp = rHp; q->HpHp = HpHp;
+    }
     const TcgNext nx_ = tcg_next(sc, pHp, rHp, HpHp);
     if (nx_.mode == 5) {
         if (lead) {
@@ -1265,6 +1273,10 @@ __device__ __forceinline__ void cg_step_body(int bid, int nblk, int nloc, const 
     const bool newdir = nx_.newdir;
     double acc = 0.0;
     if (in0) {
+        if (rec) {
+            hR[i] = pv; hR[total + i] = hp;
+            if (own0) { hS[camf] = psv; hS[nloc + camf] = hs; }
+        }
         vR[i] = vv0 + step * pv;
         if (keep_hv) HvR[i] = hv + step * hp;
         if (cg) {
@@ -1291,6 +1303,10 @@ __device__ __forceinline__ void cg_step_body(int bid, int nblk, int nloc, const 
         const int cam = (int)(i / (3 * OP));
         const bool own = (i % (3 * OP) == 0);
         const double hpi = HpR[i], pi = pR_cur[i], hsi = Hps[cam], psi = ps_cur[cam];
+        if (rec) {
+            hR[i] = pi; hR[total + i] = hpi;
+            if (own) { hS[cam] = psi; hS[nloc + cam] = hsi; }
+        }
         vR[i] += step * pi;
         if (keep_hv) HvR[i] += step * hpi;
         if (cg) {
@@ -1351,9 +1367,73 @@ __global__ __launch_bounds__(256) void cg_step_kernel(int nloc, const TcgScal *_
                                                        double *ps_next, double *vR, double *vs, double *HvR, double *Hvs, const double *rR_cur, double *rR_next,
                                                        const double *__restrict__ rs_cur, double *rs_next, double *Wloc,
                                                        double *partsB_out, unsigned long long *hstat, int b_off, int64_t mat,
-                                                       double *Afull, double *Wfull, int grp, PeerXchg x, double *Wpad) {
+                                                       double *Afull, double *Wfull, int grp, PeerXchg x, double *Wpad, TcgHist hist) {
     cg_step_body<O, true>(blockIdx.x, gridDim.x, nloc, scal_cur, scal_next, parts, nA_loc, nB_loc, world, HpR, Hps, R, s, pR_cur, pR_next, ps_cur, ps_next, vR, vs,
-                          HvR, Hvs, rR_cur, rR_next, rs_cur, rs_next, Wloc, partsB_out, hstat, b_off, mat, Afull, Wfull, grp, &x, Wpad);
+                          HvR, Hvs, rR_cur, rR_next, rs_cur, rs_next, Wloc, partsB_out, hstat, b_off, mat, Afull, Wfull, grp, &x, Wpad, hist);
+}
+
+// A truncated CG from the point, gradient state and |r|^2 of the one that wrote the history, with another radius -- without a product.  Until the
+// radius trips, that truncated CG takes the recorded iterations bit for bit: iteration j's scalar block is record j's but for delta, and its sums
+// are the record's.  Thread j evaluates record j with the step's routine (tcg_next), the first record whose next status is not 0 ends the run, and
+// v (and H v) are accumulated from zero in the step's own order and expression, v += step_j p_j.  The lead thread writes the scalar block the
+// last step would have written and the progress word.  No record ends it (the rejected run was longer than the history): kTcgNotCovered in the
+// progress word, nothing else written.
+template <int O>
+__global__ __launch_bounds__(256) void tcg_replay_kernel(TcgReplayArgs a) {
+    constexpr int OP = pitch_of(O);
+    __shared__ double sh_step[kTcgHistMax];
+    __shared__ int sh_status[kTcgHistMax];
+    const int64_t total = (int64_t)a.nloc * 3 * OP;
+    const bool keep_hv = a.HvR != nullptr;
+    const int nrec = a.nrec < kTcgHistMax ? a.nrec : kTcgHistMax;
+    if ((int)threadIdx.x < nrec) {
+        const TcgRec &q = a.hist.rec[threadIdx.x];
+        TcgScal sc = q.sc;
+        sc.delta = a.delta;
+        const TcgNext n = tcg_next(sc, q.pHp, q.rHp, q.HpHp);
+        sh_step[threadIdx.x] = n.step;
+        sh_status[threadIdx.x] = n.status;
+    }
+    __syncthreads();
+    int last = 0;
+    while (last < nrec && sh_status[last] == 0) ++last;
+    const bool lead = (blockIdx.x == 0 && threadIdx.x == 0);
+    if (last >= nrec) {
+        if (lead) publish_host(a.hstat, pack_stat(a.seq, 0, kTcgNotCovered));
+        return;
+    }
+    const int napply = (sh_status[last] == 5) ? last : last + 1;   // (the stop at |r|^2 < 1e-15 takes no step)
+    const size_t slot_v = 2 * (size_t)total, slot_c = 2 * (size_t)a.nloc;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int cam = (int)(i / (3 * OP));
+        const bool own = (i % (3 * OP) == 0);
+        double v = 0.0, hv = 0.0, vsc = 0.0, hvs = 0.0;
+        for (int j = 0; j < napply; ++j) {
+            const double step = sh_step[j];
+            const double *hR = a.hist.vec + (size_t)j * slot_v;
+            v = v + step * hR[i];
+            if (keep_hv) hv = hv + step * hR[total + i];
+            if (own) {
+                const double *hS = a.hist.cam + (size_t)j * slot_c;
+                vsc = vsc + step * hS[cam];
+                if (keep_hv) hvs = hvs + step * hS[a.nloc + cam];
+            }
+        }
+        a.vR[i] = v;
+        if (keep_hv) a.HvR[i] = hv;
+        if (own) { a.vs[cam] = vsc; if (keep_hv) a.Hvs[cam] = hvs; }
+    }
+    if (lead) {
+        const TcgRec &q = a.hist.rec[last];
+        TcgScal sc = q.sc;
+        sc.delta = a.delta; sc.seq = a.seq;
+        const TcgNext n = tcg_next(sc, q.pHp, q.rHp, q.HpHp);
+        TcgScal nx;
+        if (n.mode == 5) { nx = sc; nx.status = 5; nx.last_step = 0.0; }
+        else nx = tcg_scal_next(sc, n, q.pHp, keep_hv);
+        *a.scal_out = nx;
+        publish_host(a.hstat, pack_stat(nx.seq, nx.iter, nx.status));
+    }
 }
 
 // End of an outer iteration: one 256-thread block adds the gathered partial sums in their fixed order and hands
@@ -2700,6 +2780,7 @@ static void qw_symv_epi(int epi, const double *Q, int64_t ld, const double *W, d
             fu.pR_cur = S.v.pR_cur; fu.ps_cur = S.v.ps_cur; fu.rR_cur = S.v.rR_cur; fu.rs_cur = S.v.rs_cur;
             fu.pR_next = S.v.pR_next; fu.ps_next = S.v.ps_next; fu.rR_next = S.v.rR_next; fu.rs_next = S.v.rs_next;
             fu.vR = S.vR; fu.vs = S.vs; fu.HvR = S.HvR; fu.Hvs = S.Hvs; fu.Wloc = S.Wloc; fu.partsB_out = S.v.partsB_out; fu.hstat = S.hstat;
+            fu.hist = S.hist;
             const dim3 gf(gs.x, gs.y + (S.nB + gs.x - 1) / gs.x);
             hipLaunchKernelGGL((qw_symv_step_kernel<O>), gf, dim3(256), 0, st, Q, ld, a.nloc, pl.K, pl.Kf, ys, nt0, Prow, Pcol, rev, fu);
         } else throw Error(-2, "symmetric product: the tCG step travels with the sweep at o = 3 and 4 only");
@@ -2886,8 +2967,14 @@ void launch_cg_step(int o, const CgStepArgs &a, hipStream_t st) {
     XM_DISPATCH_O(o, hipLaunchKernelGGL((cg_step_kernel<O_>), dim3(a.nB), dim3(256), 0, st, a.nloc,
                                         a.v.scal_cur, a.v.scal_next, a.v.pcur, a.nA, a.nB, a.world, a.HpR, a.Hps, a.R, a.s, a.v.pR_cur, a.v.pR_next, a.v.ps_cur, a.v.ps_next, a.vR,
                                         a.vs, a.HvR, a.Hvs, a.v.rR_cur, a.v.rR_next, a.v.rs_cur, a.v.rs_next, a.Wloc, a.v.partsB_out, a.hstat, (int)a.v.b_off, a.mat, a.Afull,
-                                        a.Wfull, a.grouping, a.xchg, a.Wpad));
+                                        a.Wfull, a.grouping, a.xchg, a.Wpad, a.hist));
     check_launch("cg_step");
+}
+void launch_tcg_replay(int o, const TcgReplayArgs &a, hipStream_t st) {
+    if (!a.hist.vec || !a.hist.cam || !a.hist.rec || a.nrec < 1 || a.nrec > a.hist.H || a.hist.H > kTcgHistMax)
+        throw Error(-2, "tcg_replay: no history to replay");
+    XM_DISPATCH_O(o, hipLaunchKernelGGL((tcg_replay_kernel<O_>), dim3(flat_grid((int64_t)a.nloc * 3 * pitch_of(O_))), dim3(256), 0, st, a));
+    check_launch("tcg_replay");
 }
 void launch_outer_finalize(const double *partsA, int nA_loc, int world, const double *partsM, int nM, const TcgScal *scal, double *hres,
                            unsigned long long seq, int grouping, hipStream_t st, const OuterArgs *oa, SpecCtl *spec_out) {

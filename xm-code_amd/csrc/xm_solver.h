@@ -46,6 +46,7 @@ struct Settings {
     int64_t schur_dense_max = 20000;
     int schur_dense_q = 0;                // 1: a matrix-free context also builds the dense Q on the device and multiplies with it (xm_schur_dense.hip)
     int hess_f32 = 0;                     // 1: the tCG Hessian products of a dense single-rank context read an fp32 copy of Q (dQ32_)
+    int tcg_history = kTcgHistDefault;    // iterations of a truncated CG that are kept for the replay of a rejected step (TcgHist::H)
     static Settings resolve(const xm_tuning_t *t);
 };
 
@@ -205,7 +206,12 @@ public:
     int64_t n_observations() const;   // matrix-free storage: observations of the list (0 otherwise)
     void dense_q(double *q, int64_t ldq);   // xm_tuning_t.schur_dense_q: the current dense Q -> host, column-major
     int tcg_two_launch_count() const { return tcg_two_launch_count_; }   // trust regions of the last solve in the two-launch form (xm_ctx_tcg_two_launch)
-    bool schur_info(int64_t out[3], double *relres) const;   // matrix-free storage with the CG form: products, inner iterations, products at the cap
+    void set_tcg_history(int H) {   // iterations kept for the replay from the next solve on (xm_ctx_set_tcg_history); 0: the default
+        if (H < 0 || H > kTcgHistMax) throw Error(XM_ERR_ARG, "tcg history must be 0 (default) or 1.." + std::to_string(kTcgHistMax));
+        cfg_.tcg_history = H > 0 ? H : kTcgHistDefault;
+    }
+    void tcg_replay_counts(int64_t out[2]) const { out[0] = tcg_replays_; out[1] = tcg_replayed_iters_; }   // replays and replayed iterations of the last solve (xm_ctx_tcg_replay)
+    bool schur_info(int64_t out[3], double *relres) const;  // matrix-free storage with the CG form: products, inner iterations, products at the cap
     int schur_precond(int64_t *aggregates, int *block) const; // its preconditioner: -1 no CG form, 0 Jacobi, 1 two-level (aggregates, cameras per aggregate)
 
 private:
@@ -321,6 +327,17 @@ private:
     bool tcg_two_launch() const;                       // does the host-driven tCG of the current rank run in the two-launch form?
     const CgStepArgs *fuse_step_ = nullptr;            // set around the product that carries a step (tcg_enqueue_iteration)
     int tcg_two_launch_count_ = 0;                     // trust regions of the last solve that ran in the two-launch form (xm_ctx_tcg_two_launch)
+    // Replay of a rejected step's truncated CG (TcgHist, tcg_replay_kernel): the steps of a live truncated CG record themselves; when the host rejects
+    // the step and keeps the point, the next truncated CG differs only in its radius and is rebuilt from the records by one launch.
+    bool replay_applies() const;                       // one GPU, host-driven outer iteration with run-ahead polling, not matrix-free, not XM_FLAG_HOST_OUTER / XM_FLAG_TCG_RECOMPUTE
+    TcgHist tcg_hist() const;                          // the history as the step launches get it (all nullptr where replay does not apply)
+    int run_tcg_replay(double delta);                  // scalar-block index, or -1: the records do not cover this radius
+    DevBuf<double> hist_vec_, hist_cam_;
+    DevBuf<TcgRec> hist_rec_;
+    bool hist_valid_ = false;                          // the records are those of a rejected truncated CG from the current point
+    bool tcg_replayed_ = false;                        // the last run_tcg was a replay
+    int hist_n_ = 0;                                   // records that truncated CG wrote
+    int64_t tcg_replays_ = 0, tcg_replayed_iters_ = 0; // of the last solve (xm_ctx_tcg_replay)
     // What the solver's two forms AND the test exports (rtr_probe, outer_probe) launch the tCG's kernels with: a probe overrides single fields, never rebuilds.
     TcgParity tcg_parity(int par) const;   // single rank on partsB_ | communicator with a lockstep gather | fused peer exchange on partsB_peer_
     void cand_role(CamArgs &a, const PointState &P, const double *R, const double *s) const;   // CamArgs::cand: the gradient role of an EPI_AUTO product at (R, s)

@@ -569,6 +569,15 @@ void Context::setup_rank(int o) {
     }
     scal_.ensure(2, st_);
     spec_.ensure(1, st_);
+    // history of the truncated CG for the replay of a rejected step: tcg_history slots of [p | Hp].  Grow-only and not zeroed: a replay reads
+    // only what the steps of the rejected truncated CG wrote (hist_n_ records)
+    hist_valid_ = false;
+    if (replay_applies()) {
+        const size_t H = (size_t)cfg_.tcg_history;
+        if (hist_vec_.capacity < H * 2 * mat) hist_vec_.alloc(H * 2 * mat_top, false);
+        if (hist_cam_.capacity < H * 2 * vec) hist_cam_.alloc(H * 2 * vec, false);
+        if (hist_rec_.capacity < H) hist_rec_.alloc(H, false);
+    }
     // the sliced-ELL product's partial-result buffer grows with o: (re)allocate it HERE, between the two barriers -- hipFree synchronises
     // the whole device, and with several ranks of one process on one device ("virtual devices") a free between two collectives waits for
     // a peer's spinning wait kernel that waits for this rank's next push (8 virtual ranks ran into exactly that at the first o = 4 product)
@@ -939,7 +948,54 @@ CgStepArgs Context::cg_step_args(int i) const {
     a.hstat = hstat_dev_; a.mat = (int64_t)nloc_ * 3 * OP_;
     a.Afull = comm_->active() ? Afull_.p : nullptr; a.Wfull = W_.p;
     a.grouping = grouping_; a.xchg = xchg_;
+    a.hist = tcg_hist();
     return a;
+}
+
+// Replay of a rejected step's truncated CG: where the host decides the rejection and the next truncated CG starts from bit-identical inputs.
+// Several ranks, XM_FLAG_HOST_STEPPED, the device-driven outer iteration, the matrix-free storage and XM_FLAG_HOST_OUTER (the form of rounds 1-5,
+// which the device-driven form is compared with) keep recomputing, and so does XM_FLAG_TCG_RECOMPUTE.
+bool Context::replay_applies() const {
+    if (!opt_ || (opt_->flags & (XM_FLAG_HOST_STEPPED | XM_FLAG_HOST_OUTER | XM_FLAG_TCG_RECOMPUTE))) return false;
+    if (comm_->active() || comm_->world > 1 || storage_ == XM_STORAGE_SCHUR || o_ < 3) return false;
+    return !device_outer_applies(o_);
+}
+
+TcgHist Context::tcg_hist() const {
+    TcgHist h;
+    const size_t H = (size_t)cfg_.tcg_history;
+    if (!replay_applies() || !hist_vec_.p || !hist_cam_.p || !hist_rec_.p) return h;
+    if (hist_vec_.capacity < H * 2 * (size_t)nloc_ * 3 * OP_ || hist_cam_.capacity < H * 2 * (size_t)nloc_ || hist_rec_.capacity < H) return h;   // (not set up for this rank)
+    h.vec = hist_vec_.p; h.cam = hist_cam_.p; h.rec = hist_rec_.p; h.H = cfg_.tcg_history;
+    return h;
+}
+
+// One launch instead of tcg_init and the iterations: the progress word says how the replayed truncated CG ended, or that the records do not reach
+// the iteration at which this radius trips (the rejected one ran past the history).  The scalar block is scal_[0].
+int Context::run_tcg_replay(double delta) {
+    ++tcg_seq_;
+    TcgReplayArgs a;
+    const bool model_rec = (opt_->flags & XM_FLAG_MODEL_RECURRENCE) != 0;
+    a.nloc = nloc_; a.hist = tcg_hist(); a.nrec = hist_n_; a.delta = delta;
+    a.vR = vR_.p; a.vs = vs_.p; a.HvR = model_rec ? nullptr : HvR_.p; a.Hvs = model_rec ? nullptr : Hvs_.p;
+    a.scal_out = scal_.p; a.hstat = hstat_dev_; a.seq = (int)tcg_seq_;
+    launch_tcg_replay(o_, a, st_);
+    volatile unsigned long long *hs = hstat_;
+    const auto t_wait = clk::now();
+    auto t_check = t_wait;
+    for (;;) {
+        const unsigned long long v = *hs;
+        if ((unsigned int)(v >> 32) == tcg_seq_ && (v & 0xff) != 0) return (int)(v & 0xff) == kTcgNotCovered ? -1 : 0;
+        __builtin_ia32_pause();
+        if (secs_since(t_check) > 200e-6) {
+            if (stream_idle(t_wait, "the replayed truncated CG")) {
+                XM_HIP_CHECK(hipStreamSynchronize(st_));
+                const unsigned long long w = *hs;
+                if ((unsigned int)(w >> 32) != tcg_seq_ || (w & 0xff) == 0) throw Error(XM_ERR_HIP, "replayed truncated CG: no result reached host-mapped memory");
+            }
+            t_check = clk::now();
+        }
+    }
 }
 
 // May the start of the next truncated CG be enqueued behind outer_finalize_kernel before the host knows how the outer iteration ended?
@@ -976,6 +1032,14 @@ int Context::run_tcg(double rr, double delta, int adopted) {
     const bool stepped = (opt_->flags & XM_FLAG_HOST_STEPPED) != 0;
     const bool profile = (opt_->flags & XM_FLAG_PROFILE_QW) != 0;
     if (comm_->active()) comm_->note("tcg_start", rr, delta);
+    // the step before was rejected and the point kept: this truncated CG is the rejected one with a smaller radius (run_tcg_replay).  A live one
+    // -- this one, when the records do not cover it -- overwrites the history.
+    if (adopted == 0 && hist_valid_) {
+        const int enq = run_tcg_replay(delta);
+        if (enq >= 0) { tcg_replayed_ = true; return enq; }
+    }
+    hist_valid_ = false;
+    tcg_replayed_ = false;
     if (adopted == 0) {
         ++tcg_seq_;
         launch_tcg_init(o_, tcg_init_args(rr, delta, nullptr), st_);
@@ -1113,6 +1177,8 @@ TrResult Context::trust_region(int o, double &gradtol, double linesearch_step, c
     eval_point(cur_, R_.p, s_.p, f, rr);  // loss[0] and the gradient state of the first outer iteration
     if (device_outer_applies(o)) return trust_region_device(o, gradtol, f, rr, delta, delta_bar, max_time);
     if (tcg_two_launch()) tcg_two_launch_count_++;
+    hist_valid_ = false;
+    tcg_replayed_ = false;
     double loss = f;
 
     int endreason = 6, trstatus = 4, shrink_count = 0, inner_print = 1, k = 0;
@@ -1181,6 +1247,7 @@ TrResult Context::trust_region(int o, double &gradtol, double linesearch_step, c
         endreason = fin.status;
         inner_print = fin.iter + 1;
         totalite += fin.iter + 1;
+        if (tcg_replayed_) { tcg_replays_++; tcg_replayed_iters_ += fin.iter + 1; }   // counted like the iterations they stand for
         if (opt_->flags & XM_FLAG_PROFILE_QW) drain_events();
         if (loss_qu >= 0) { stop_reason = 12; break; }
         const double rou = (f_new - loss) / loss_qu;  // trustregion.h:680-701
@@ -1195,6 +1262,7 @@ TrResult Context::trust_region(int o, double &gradtol, double linesearch_step, c
         }
         const bool reject = (f_new > loss || rou < 0.1);  // trustregion.h:702
         if (stop_delta || !reject) {
+            hist_valid_ = false;
             std::swap(R_.p, Rc_.p);
             std::swap(s_.p, sc_.p);
             cur_ ^= 1;
@@ -1205,6 +1273,12 @@ TrResult Context::trust_region(int o, double &gradtol, double linesearch_step, c
             if (spec_go && std::memcmp(&spec_delta, &delta, sizeof(double)) == 0) adopted = n_spec;
         } else {
             trstatus = 3;  // keep point, state, loss and rr
+            // ... so the next truncated CG is this one with the smaller radius: replayed from the history its steps wrote, if the speculative
+            // start behind the result kernel stayed dormant (a live one has begun to overwrite it).  A replayed one leaves the history as it is.
+            if (replay_applies() && !spec_go && hist_vec_.p) {
+                if (!tcg_replayed_) hist_n_ = std::min(cfg_.tcg_history, fin.iter + 1);
+                hist_valid_ = true;
+            }
         }
         // Speculative launches that were not adopted found a dormant scalar block and returned at once: they are no products.
         // Invariant for the ones that WERE adopted when the loop is left right after (time limit, |grad| < gradtol by a rounding of the sqrt): a live
@@ -2590,6 +2664,7 @@ void Context::solve(const xm_options_t &opt, xm_result_t &res) {
     retraction_ = opt.retraction;
     grouping_ = opt.sum_grouping;
     tcg_two_launch_count_ = 0;
+    tcg_replays_ = tcg_replayed_iters_ = 0;
     double *Rout = res.R, *sout = res.s;
     std::memset(&res, 0, sizeof(res));
     res.R = Rout; res.s = sout;

@@ -26,6 +26,7 @@ FLAG_HOST_OUTER = 64           # outer iteration of the trust region on the host
 FLAG_DEVICE_OUTER = 128        # ... on the device also with dense products, where the host-driven form is the (faster) default (xm_amd.h)
 FLAG_MODEL_RECURRENCE = 32     # model decrease of a tCG from its recurrences instead of from accumulated H v (xm_amd.h)
 FLAG_TCG_THREE_LAUNCH = 256    # three launches per tCG iteration where the default is two (symmetric dense pair, one GPU; xm_amd.h): same bits
+FLAG_TCG_RECOMPUTE = 512       # recompute the truncated CG behind a rejected step where the default replays it from the rejected one's history (xm_amd.h): same bits
 
 EXPORTS = [
     "xm_last_error", "xm_version", "xm_abi_revision", "xm_solve", "xm_solve_rank3", "xm_solve_rebuttle", "xm_ctx_create", "xm_ctx_solve",
@@ -33,7 +34,7 @@ EXPORTS = [
     "xm_dev_sync", "xm_dense_upload", "xm_dense_from_bsr3", "xm_qw_dense", "xm_qw_dense_sym", "xm_qw_bsr3", "xm_retract", "xm_retract_polar", "xm_recover_rotations",
     "xm_comm_unique_id", "xm_comm_init", "xm_comm_init_shm", "xm_comm_init_ipc", "xm_comm_finalize", "xm_partition", "xm_partition_blocks",
     "xm_symv_plan", "xm_sell_layout", "xm_sell_locality", "xm_sell_create", "xm_sell_create2", "xm_sell_quat_roundtrip", "xm_sell_destroy", "xm_qw_sell", "xm_qw_sell_padded",
-    "xm_ctx_attach_edges", "xm_ctx_edge_residuals", "xm_ctx_edge_residuals_recovered", "xm_ctx_xm2_filter", "xm_ctx_xm2_round", "xm_ctx_set_edge_weights", "xm_ctx_recover_tp", "xm_ctx_schur_info", "xm_ctx_tcg_two_launch", "xm_ctx_qw", "xm_spd_inverse", "xm_ctx_transport", "xm_ctx_sell_wpad", "xm_ctx_product_kind", "xm_symw_plan", "xm_symw_use", "xm_symw_probe",
+    "xm_ctx_attach_edges", "xm_ctx_edge_residuals", "xm_ctx_edge_residuals_recovered", "xm_ctx_xm2_filter", "xm_ctx_xm2_round", "xm_ctx_set_edge_weights", "xm_ctx_recover_tp", "xm_ctx_schur_info", "xm_ctx_tcg_two_launch", "xm_ctx_tcg_replay", "xm_ctx_set_tcg_history", "xm_ctx_qw", "xm_spd_inverse", "xm_ctx_transport", "xm_ctx_sell_wpad", "xm_ctx_product_kind", "xm_symw_plan", "xm_symw_use", "xm_symw_probe",
     "xm_ctx_schur_precond_info", "xm_schur_aggregate_plan",
     "xm_dense_to_f32", "xm_qw_dense_f32", "xm_qw_dense_sym_f32",
     "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_la_probe", "xm_ba_aggregate_plan", "xm_ctx_ba_probe", "xm_lm_replay",
@@ -587,6 +588,8 @@ def lib():
         L.xm_create_matrix.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.xm_schur_dense_limits.argtypes = [C.c_void_p]
         L.xm_ctx_tcg_two_launch.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.xm_ctx_tcg_replay.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.xm_ctx_set_tcg_history.argtypes = [C.c_void_p, C.c_int32]
         L.xm_ctx_schur_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_double)]
         L.xm_ctx_schur_precond_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
         L.xm_schur_aggregate_plan.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -3018,9 +3021,17 @@ class Context:
         # trust regions of this solve whose tCG iteration was two launches (0: all three -- FLAG_TCG_THREE_LAUNCH or a form it does not cover)
         cnt = C.c_int(0)
         info["tcg_two_launch"] = cnt.value if lib().xm_ctx_tcg_two_launch(self.h, C.byref(cnt)) == 0 else 0
+        # truncated CGs behind a rejected step that were replayed from the rejected one's history, and the iterations they stand for (in tcg_iters)
+        rp = (C.c_int64 * 2)(0, 0)
+        ok = lib().xm_ctx_tcg_replay(self.h, rp) == 0
+        info["tcg_replays"], info["tcg_replayed_iters"] = (int(rp[0]), int(rp[1])) if ok else (0, 0)
         if tr is not None:
             info["trace"] = tr[: res.trace_len].copy()
         return np.ascontiguousarray(R[:, : res.rank]), s, info
+
+    def set_tcg_history(self, iterations):
+        """iterations of a truncated CG kept for the replay of a rejected step, from the next solve on (0 = default 64, 1 .. 256; xm_ctx_set_tcg_history)"""
+        _chk(lib().xm_ctx_set_tcg_history(self.h, int(iterations)))
 
     def close(self):
         if self.h:
