@@ -1135,8 +1135,37 @@ int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int
  * The aggregate preconditioners are not available with a focal column (their coarse space, LDS block size and compensated assembly are
  * tuned to CD = 6 / 3): XM_BA_REFINE_FOCAL with XM_BA_PRECOND_TWO_LEVEL or XM_BA_PRECOND_BLOCKS is XM_ERR_ARG.  Also XM_ERR_ARG (context
  * unchanged and usable): focal NULL, a focal that is not finite or not positive, the flag missing, and every refusal above.
- * Departures from the reference: no distortion parameters; fx = fy; no aggregate preconditioners with a focal column.
+ * Departures from the reference: of the distortion parameters only one radial coefficient (xm_ctx_bundle_adjust_radial below: no second
+ * coefficient, no tangential terms, none shared by focal group); fx = fy; no aggregate preconditioners with a focal column.
  * xm_ctx_reprojection_errors_focal: sqerr[e] = |g_i pi(X) - z_e|^2, -1 where the observation is unused.
+ *
+ * Radial distortion (XM_BA_REFINE_RADIAL, xm_ctx_bundle_adjust_radial): GLOMAP builds colmap::CreateCameraCostFunction<ReprojErrorCostFunctor>
+ * over the camera's whole parameter vector (estimators/bundle_adjustment.cc:72-84) and with optimize_intrinsics holds only the principal
+ * point (:163-175), so a radial coefficient moves with the focal.  Here:
+ *   model       one radial coefficient k_i per camera beside the focal scale g_i (dist: n, host, in-out; dimensionless, either sign).  With
+ *               u = pi(Rcw_i P_l + tcw_i), rho^2 = u0^2 + u1^2, s = 1 + k_i rho^2:  r_e = g_i s u - (p_e0 / p_e2, p_e1 / p_e2).  COLMAP's
+ *               SIMPLE_RADIAL and BAL's model with k2 = 0, in pixels divided by the focal prior, principal point removed and held.  With
+ *               k = 0 the residual of xm_ctx_bundle_adjust_focal.  Update g_i += dg_i, k_i += dk_i.
+ *   tangent     camera block (dtheta, dt, dg, dk), CD = 8; (dt, dg, dk), CD = 5, with XM_BA_FIX_ROTATIONS: the leading columns and the focal
+ *               column where they are at CD = 7 / 4, the distortion column last.  d r / d g = s u, d r / d k = g rho^2 u,
+ *               d r / d u = g (s I + 2 k u u^T) in front of the pose and point Jacobians of the pinhole form; a robust loss's corrector scales
+ *               the whole record as before.
+ *   masks       focal_free and dist_free (n, uint8; NULL = all free), independent.  A held column is zero: diagonal mu 1e-6 by the clamp of D,
+ *               right-hand side 0, a step of exactly 0, the value comes back bit-identical; the same for cameras without a used observation.
+ *               An observation with rho = 0 contributes a zero distortion column, by the formula.
+ *   invalid     a candidate with g_i <= 0 for a moving focal, or with 1 + 3 k_i rho^2 <= 0 at some used observation (there rho -> rho (1 +
+ *               k rho^2) folds and stops being invertible), is rejected exactly as a step without model decrease (radius /= nu, nu *= 2).
+ *               The caller's start is not checked.
+ *   stops       |x|^2 adds g_i^2 and k_i^2 per used camera with the respective column free, |d|^2 adds dg_i^2 and dk_i^2, gradient_tol sees
+ *               both gradients.
+ * Everything else is xm_ctx_bundle_adjust_focal word for word: the LM rules, the block-Jacobi PCG with the inverted 8 x 8 / 5 x 5 blocks,
+ * XM_BA_DENSE_SCHUR (XM_BA_DENSE_MAX_ROWS applies to 8 n / 5 n), losses, non-monotonic steps, which observations are used, determinism (no
+ * atomics, fixed-order sums: two calls give the same bytes).  XM_BA_REFINE_RADIAL is valid only together with XM_BA_REFINE_FOCAL and only
+ * in xm_ctx_bundle_adjust_radial and xm_ctx_ba_probe_radial; every other entry point refuses it as unknown.  XM_ERR_ARG (context unchanged
+ * and usable): dist NULL or not finite, the flag without XM_BA_REFINE_FOCAL, either aggregate preconditioner flag, and every refusal of
+ * the focal form.  Not built: a second radial coefficient (BAL's k2, COLMAP's RADIAL), distortion shared by focal group, aggregate
+ * preconditioners, tangential terms, fx != fy.
+ * xm_ctx_reprojection_errors_radial: sqerr[e] = |g_i s u - z_e|^2, -1 where the observation is unused.
  *
  * Focal groups (xm_ctx_bundle_adjust_focal_groups): GLOMAP shares a Camera among images -- every residual block takes
  * cameras[image.camera_id].params (estimators/bundle_adjustment.cc:72-84), so the focal belongs to the camera, not to the image.  Here:
@@ -1167,6 +1196,7 @@ int xm_ctx_schur_precond_info(xm_ctx_t *ctx, int *kind, int64_t *aggregates, int
 #define XM_BA_PRECOND_TWO_LEVEL 32u     /* PCG preconditioner: aggregate blocks + rigid-motion coarse operator (see below) */
 #define XM_BA_PRECOND_BLOCKS    64u     /* PCG preconditioner: the aggregate blocks alone (the ablation of the above) */
 #define XM_BA_REFINE_FOCAL      128u    /* a focal scale per camera joins the camera block (xm_ctx_bundle_adjust_focal only; see above) */
+#define XM_BA_REFINE_RADIAL     256u    /* a radial coefficient per camera behind the focal scale (xm_ctx_bundle_adjust_radial only; see above) */
 #define XM_BA_AGG_CAMS          16      /* cameras per aggregate */
 #define XM_BA_FOCAL_GROUPS_EXACT 16     /* focal groups: up to this many, the preconditioner's focal block is the exact G x G one */
 #define XM_BA_MAX_AGGREGATES    4096    /* at most this many aggregates (65 536 cameras): A_c has up to 28 672 rows */
@@ -1212,6 +1242,11 @@ int xm_ctx_reprojection_errors_focal(xm_ctx_t *ctx, const double *rot, const dou
 int xm_ctx_bundle_adjust_focal_groups(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, int64_t ngroups,
                                       const int32_t *group_of /* n */, double *focal /* ngroups, in-out */,
                                       const uint8_t *focal_free /* ngroups or NULL */, xm_ba_result_t *res);
+int xm_ctx_bundle_adjust_radial(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, double *focal /* n, in-out */,
+                                const uint8_t *focal_free /* n or NULL */, double *dist /* n, in-out */, const uint8_t *dist_free /* n or NULL */,
+                                xm_ba_result_t *res);
+int xm_ctx_reprojection_errors_radial(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, const double *focal, const double *dist,
+                                      double *sqerr);
 /* ---- Filtering tracks against a refined geometry: the TrackFilter of the reference's fork of GLOMAP
  * (deps/glomap/glomap/processors/track_filter.cc: FilterTracksByReprojection :7-51, FilterTracksByAngle :53-89,
  * FilterTrackTriangulationAngle :91-126), which GLOMAP alternates with its bundle adjustment (controllers/global_mapper.cc:243-317), as a
@@ -1640,6 +1675,12 @@ int xm_ctx_ba_probe(xm_ctx_t *ctx, const double *rot, const double *t, const dou
  * not positive is reported as cost1 = NaN (the loop rejects that step as invalid). */
 int xm_ctx_ba_probe_focal(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, const double *focal, const uint8_t *focal_free,
                           xm_ba_probe_t *probe, double *focal1);
+/* The same with a radial coefficient behind the focal scale (xm_ctx_bundle_adjust_radial; tests/test_gpu_ba_radial_stages.py): probe->flags
+ * must hold XM_BA_REFINE_FOCAL | XM_BA_REFINE_RADIAL and may hold XM_BA_FIX_ROTATIONS; the arrays are sized by CD = 8, or 5 with fixed
+ * rotations.  dist (n, finite), dist_free (n or NULL) as there.  dist1 (n or NULL): the candidate's coefficients when probe->dc is given; a
+ * candidate at which the radial map folds at a used observation is reported as cost1 = NaN, as a focal that is not positive is. */
+int xm_ctx_ba_probe_radial(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, const double *focal, const uint8_t *focal_free,
+                           const double *dist, const uint8_t *dist_free, xm_ba_probe_t *probe, double *focal1, double *dist1);
 /* The same with focal groups (xm_ctx_bundle_adjust_focal_groups; tests/test_gpu_ba_groups_stages.py): ngroups, group_of, focal (ngroups),
  * focal_free (ngroups or NULL) as there.  b, the columns of X, SX and MX, and dc have CP n + G entries: CP = CD - 1 per camera, then the G
  * focal entries (0 comes back for an empty group).  ustar and sinv (CD CD n) are the blocks the device holds: U* with the focal diagonal

@@ -14,4 +14,4 @@ for line in out.splitlines():
     elif cur is not None: cur[k] = v
 for r in rows:
     if filt in r["name"]:
-        print(f'{r["name"][:110]:110s} vgpr {r.get("VGPRs"):>4} sgpr {r.get("TotalSGPRs"):>4} scratch {r.get("ScratchSize [bytes/lane]"):>5} occ {r.get("Occupancy [waves/SIMD]"):>2} lds {r.get("LDS Size [bytes/block]"):>6}')
+        print(f'{r["name"][:110]:110s} vgpr {r.get("VGPRs"):>4} agpr {r.get("AGPRs"):>3} sgpr {r.get("TotalSGPRs"):>4} scratch {r.get("ScratchSize [bytes/lane]"):>5} occ {r.get("Occupancy [waves/SIMD]"):>2} lds {r.get("LDS Size [bytes/block]"):>6}')

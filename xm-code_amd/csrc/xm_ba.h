@@ -43,6 +43,15 @@
 // bad_focal in the state word and the host rejects the step as it rejects a failed factorisation.  |x|^2 adds g_i^2 per used camera with
 // a free focal.  The aggregate preconditioners are not instantiated for CD = 7 / 4 (refused at the entry point).
 //
+// Radial distortion (XM_BA_REFINE_RADIAL, xm_ctx_bundle_adjust_radial; the model: include/xm_amd.h): one coefficient k_i per camera beside
+// the focal scale, r_e = g_i s u - z_e with u = pi(X), s = 1 + k_i |u|^2 (COLMAP's SIMPLE_RADIAL, BAL's model with k2 = 0).  The last column
+// of the camera block (CD = 8, or 5 with fixed rotations), the focal column before it: d r / d g = s u, d r / d k = g |u|^2 u, and
+// d r / d u = g (s I + 2 k u u^T) in front of the pinhole pose and point rows.  As with the focal scales only the eval, candidate and cost
+// kernels read the coefficients; every pass between them is the CD-generic code.  focal_free and dist_free are independent masks; a held
+// column is zero (diagonal mu 1e-6, right-hand side 0, step exactly 0).  A candidate with 1 + 3 k |u|^2 <= 0 at a used observation (the
+// radial map folds there) sets bad_focal from the cost kernel, which computes the candidate's projection anyway; the caller's start is not
+// checked.  |x|^2 adds k_i^2 per used camera with a free coefficient.  No focal groups and no aggregate preconditioners at CD = 8 / 5.
+//
 // Focal groups (xm_ctx_bundle_adjust_focal_groups): one focal scale per group of cameras, GLOMAP's Camera shared among images.  With E the
 // 0/1 matrix that copies a group's unknown into the focal column of each member, J_shared = J_7 E and, as the landmark elimination commutes
 // with E, S_shared = E^T S_7 E, b_shared = E^T b_7: the CD = 7 / 4 kernels run unchanged on expanded vectors.  New around them: an expand
@@ -74,6 +83,9 @@ struct BaSettings {
     bool refine_focal = false;    // XM_BA_REFINE_FOCAL: a focal scale per camera, the last column of the camera block (CD = 7 / 4)
     double *focal = nullptr;      // n focal scales > 0 (host; bundle_adjust updates them in place, ba_probe only reads them)
     const uint8_t *focal_free = nullptr;   // n, 0 = held; null: all free
+    bool refine_dist = false;     // XM_BA_REFINE_RADIAL (with refine_focal, no groups): a radial coefficient per camera, the last column (CD = 8 / 5)
+    double *dist = nullptr;       // n radial coefficients, either sign (host; bundle_adjust updates them in place, ba_probe only reads them)
+    const uint8_t *dist_free = nullptr;    // n, 0 = held; null: all free
     int64_t ngroups = 0;          // > 0 (xm_ctx_bundle_adjust_focal_groups): one focal scale per group of cameras; focal and focal_free have
     const int32_t *group_of = nullptr;     // ngroups entries then, group_of (n, host) names every camera's group
     int precond = 0;              // PCG preconditioner: 0 the inverted camera blocks | 1 XM_BA_PRECOND_BLOCKS | 2 XM_BA_PRECOND_TWO_LEVEL
@@ -111,6 +123,7 @@ struct BaProbe {
     double *SX = nullptr, *Sdense = nullptr, *MX = nullptr, *Pm = nullptr, *dropped = nullptr, *Ac = nullptr;
     double *dP = nullptr, *rot1 = nullptr, *t1 = nullptr, *p1 = nullptr;
     double *focal1 = nullptr;   // refine_focal: the candidate's focal scales (n); cost1 is NaN when one of them is not positive
+    double *dist1 = nullptr;    // refine_dist: the candidate's radial coefficients (n); cost1 is NaN too when the radial map folds at a used observation
     // focal groups: b, X, SX, MX and dc are vectors of CP n + G entries (CP = CD - 1 columns per camera, then the G focal entries); focal1
     // has G entries; ustar and sinv are the blocks the device holds (the focal diagonal of U* undamped; the inverted pose block with the
     // preconditioner's 1 / F_c in the representative's focal slot)
@@ -122,8 +135,8 @@ void bundle_adjust(const SchurOp &S, const BaSettings &cfg, double *rot, double 
 // cfg: fix_rotations, loss, loss_scale, precond and watchdog_s are read.  The launches are those of bundle_adjust (one workspace class serves both).
 void ba_probe(const SchurOp &S, const BaSettings &cfg, const double *rot, const double *t, const double *p, BaProbe &q, hipStream_t st);
 // sqerr[e] = |r_e|^2 (unrobustified) of observation e in input order at (rot, t, p), -1 where it is not used (weight <= 0 or p_e2 <= 0);
-// focal: n focal scales, or null for g = 1 (the kernel without them)
-void reprojection_errors(const SchurOp &S, const double *rot, const double *t, const double *p, const double *focal, double *sqerr, double watchdog_s,
-                         hipStream_t st);
+// focal: n focal scales, or null for g = 1 (the kernel without them); dist: n radial coefficients beside the focal scales, or null for k = 0
+void reprojection_errors(const SchurOp &S, const double *rot, const double *t, const double *p, const double *focal, const double *dist,
+                         double *sqerr, double watchdog_s, hipStream_t st);
 
 }  // namespace xm

@@ -1,6 +1,6 @@
 // xm_ba.hip — reprojection bundle adjustment on the lists of the matrix-free storage (design: xm_ba.h).  CD = 6 (rotation vector +
 // translation per camera) or 3 (XM_BA_FIX_ROTATIONS: translation only); with XM_BA_REFINE_FOCAL one focal scale more, the last column
-// of the camera block: CD = 7 or 4.
+// of the camera block: CD = 7 or 4; with XM_BA_REFINE_RADIAL a radial coefficient behind it: CD = 8 or 5.
 #include "xm_ba.h"
 
 #include <algorithm>
@@ -25,11 +25,14 @@ template <int CD> constexpr int ba_planes() { return 2 * CD + 8; }
 template <int CD> constexpr int ba_jp() { return 2 * CD; }
 template <int CD> constexpr int ba_res() { return 2 * CD + 6; }
 
-// the camera block's columns: (dtheta, dt), (dt), (dtheta, dt, dg), (dt, dg)
+// the camera block's columns: (dtheta, dt), (dt), (dtheta, dt, dg), (dt, dg), (dtheta, dt, dg, dk), (dt, dg, dk)
 template <int CD> constexpr bool ba_has_rot() { return CD >= 6; }
-template <int CD> constexpr bool ba_has_focal() { return CD == 7 || CD == 4; }
+template <int CD> constexpr bool ba_has_dist() { return CD == 8 || CD == 5; }
+template <int CD> constexpr bool ba_has_focal() { return CD == 7 || CD == 4 || ba_has_dist<CD>(); }
+template <int CD> constexpr bool ba_can_group() { return CD == 7 || CD == 4; }   // the focal groups' kernels: the focal-only blocks
 template <int CD> constexpr int ba_toff() { return ba_has_rot<CD>() ? 3 : 0; }   // first translation column
-template <int CD> constexpr int ba_fidx() { return CD - 1; }                       // the focal column (where there is one)
+template <int CD> constexpr int ba_fidx() { return ba_has_dist<CD>() ? CD - 2 : CD - 1; }   // the focal column (where there is one)
+template <int CD> constexpr int ba_kidx() { return CD - 1; }                       // the distortion column (where there is one): the last
 
 __device__ __forceinline__ bool obs_used(const double (&v)[6]) { return v[0] != 0.0 || v[1] != 0.0 || v[2] != 0.0; }   // J_P row 0 (never 0 when used)
 
@@ -54,6 +57,7 @@ __device__ __forceinline__ void ba_point(const double *R, const double *T, const
 template <int CD, int LOSS>
 __device__ __forceinline__ void ba_eval_body(const SchurLists &S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
                                              const double *__restrict__ P, const double *__restrict__ G, const uint8_t *__restrict__ gfree,
+                                             const double *__restrict__ Kd, const uint8_t *__restrict__ kfree,
                                              double *__restrict__ Jc, double *__restrict__ Jl, double *__restrict__ parts, double scale) {
     constexpr int NP = ba_planes<CD>(), JP = ba_jp<CD>(), RS = ba_res<CD>();
     __shared__ double sh[4];
@@ -67,10 +71,22 @@ __device__ __forceinline__ void ba_eval_body(const SchurLists &S, const double *
         if (w > 0.0 && q2 > 0.0) {
             const double *R = Rcw + (size_t)9 * S.obs_cam[e], *T = tcw + (size_t)3 * S.obs_cam[e], *X3 = P + (size_t)3 * S.obs_lm[e];
             double Y[3], X[3];
+            if constexpr (ba_has_dist<CD>() && ba_has_rot<CD>()) {
+                // With k = 0 held this block is the focal form's and its records are to be that form's bytes.  Which two of the three
+                // products of a row of R X3 the compiler fuses is its choice per instantiation: at CD = 7 it takes row 0 the other way
+                // round than rows 1 and 2 (and than every row at CD = 4 / 5, which agree without help), and left alone it does not
+                // here.  So the fused pairs of CD = 7 are written out (tests/test_gpu_ba_radial_stages.py, the k_zero case).
+                Y[0] = fma(X3[2], R[2], fma(X3[1], R[1], X3[0] * R[0]));
+                Y[1] = fma(X3[2], R[5], fma(X3[0], R[3], X3[1] * R[4]));
+                Y[2] = fma(X3[2], R[8], fma(X3[0], R[6], X3[1] * R[7]));
 #pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                Y[a] = R[3 * a] * X3[0] + R[3 * a + 1] * X3[1] + R[3 * a + 2] * X3[2];
-                X[a] = Y[a] + T[a];
+                for (int a = 0; a < 3; ++a) X[a] = Y[a] + T[a];
+            } else {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    Y[a] = R[3 * a] * X3[0] + R[3 * a + 1] * X3[1] + R[3 * a + 2] * X3[2];
+                    X[a] = Y[a] + T[a];
+                }
             }
             const double iz = 1.0 / X[2], u0 = X[0] / X[2], u1 = X[1] / X[2];
             const double d[2][3] = {{iz, 0.0, -u0 * iz}, {0.0, iz, -u1 * iz}};   // d pi / d X
@@ -86,7 +102,30 @@ __device__ __forceinline__ void ba_eval_body(const SchurLists &S, const double *
 #pragma unroll
                 for (int k = 0; k < 3; ++k) v[CD * r + ba_toff<CD>() + k] = d[r][k];
             }
-            if constexpr (ba_has_focal<CD>()) {
+            if constexpr (ba_has_dist<CD>()) {   // r = g s u - z, s = 1 + k |u|^2: d r / d u = g (s I + 2 k u u^T) in front of the pinhole rows
+                const int64_t i = S.obs_cam[e];
+                const double g = G[i], kd = Kd[i], rho2 = u0 * u0 + u1 * u1, s = 1.0 + kd * rho2;
+                const double m00 = g * (s + 2.0 * kd * u0 * u0), m01 = g * (2.0 * kd * u0 * u1), m11 = g * (s + 2.0 * kd * u1 * u1);
+#pragma unroll
+                for (int k = 0; k < CD - 2; ++k) {   // the focal and distortion columns are still 0
+                    const double a0 = v[k], a1 = v[CD + k];
+                    v[k] = m00 * a0 + m01 * a1;
+                    v[CD + k] = m01 * a0 + m11 * a1;
+                }
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const double a0 = v[JP + k], a1 = v[JP + 3 + k];
+                    v[JP + k] = m00 * a0 + m01 * a1;
+                    v[JP + 3 + k] = m01 * a0 + m11 * a1;
+                }
+                const bool fr = gfree == nullptr || gfree[i] != 0, kr = kfree == nullptr || kfree[i] != 0;
+                v[ba_fidx<CD>()] = fr ? s * u0 : 0.0;
+                v[CD + ba_fidx<CD>()] = fr ? s * u1 : 0.0;
+                v[ba_kidx<CD>()] = kr ? g * rho2 * u0 : 0.0;
+                v[CD + ba_kidx<CD>()] = kr ? g * rho2 * u1 : 0.0;
+                v[RS] = g * s * u0 - q0 / q2;
+                v[RS + 1] = g * s * u1 - q1 / q2;
+            } else if constexpr (ba_has_focal<CD>()) {
                 const int64_t i = S.obs_cam[e];
                 const double g = G[i];
 #pragma unroll
@@ -124,9 +163,10 @@ __device__ __forceinline__ void ba_eval_body(const SchurLists &S, const double *
 template <int CD, int LOSS>
 __global__ __launch_bounds__(256) void ba_eval_kernel(SchurLists S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
                                                       const double *__restrict__ P, const double *__restrict__ G,
-                                                      const uint8_t *__restrict__ gfree, double *__restrict__ Jc, double *__restrict__ Jl,
+                                                      const uint8_t *__restrict__ gfree, const double *__restrict__ Kd,
+                                                      const uint8_t *__restrict__ kfree, double *__restrict__ Jc, double *__restrict__ Jl,
                                                       double *__restrict__ parts, double scale) {
-    ba_eval_body<CD, LOSS>(S, Rcw, tcw, P, G, gfree, Jc, Jl, parts, scale);
+    ba_eval_body<CD, LOSS>(S, Rcw, tcw, P, G, gfree, Kd, kfree, Jc, Jl, parts, scale);
 }
 
 // ---- landmark pass: V_l, g_l, (V_l + mu D_l)^-1 (6 entries of the symmetric inverse), used flag; per-workgroup max of |g_l|_inf
@@ -477,7 +517,8 @@ __device__ __forceinline__ void ba_cand_cam_body(int64_t n, const double *__rest
                                                  const double *__restrict__ G, const uint8_t *__restrict__ gfree, const double *__restrict__ dc,
                                                  const int32_t *__restrict__ cused, double *__restrict__ Rn, double *__restrict__ tn,
                                                  double *__restrict__ Gn, BaState *__restrict__ st, double *__restrict__ parts,
-                                                 const int32_t *__restrict__ group_of, const double *__restrict__ gnew, int xoff) {
+                                                 const int32_t *__restrict__ group_of, const double *__restrict__ gnew, int xoff,
+                                                 const double *__restrict__ Kd, const uint8_t *__restrict__ kfree, double *__restrict__ Kn) {
     static_assert(!GR || ba_has_focal<CD>(), "focal groups need a focal column");
     __shared__ double sh[4];
     double s2 = 0.0, x2 = 0.0;
@@ -490,6 +531,7 @@ __device__ __forceinline__ void ba_cand_cam_body(int64_t n, const double *__rest
             for (int k = 0; k < 3; ++k) tn[3 * i + k] = T[k];
             if constexpr (GR) Gn[i] = gnew[group_of[i]];
             else if constexpr (ba_has_focal<CD>()) Gn[i] = G[i];
+            if constexpr (ba_has_dist<CD>()) Kn[i] = Kd[i];
             continue;
         }
         const double *dt = d + ba_toff<CD>();
@@ -508,6 +550,15 @@ __device__ __forceinline__ void ba_cand_cam_body(int64_t n, const double *__rest
                 if (!(gn > 0.0)) st->bad_focal = 1;
             } else {
                 Gn[i] = g;
+            }
+        }
+        if constexpr (ba_has_dist<CD>()) {   // k += dk for a free coefficient (either sign is a value), a copy elsewhere; k^2 joins |x|^2
+            const double kd = Kd[i];
+            if (kfree == nullptr || kfree[i] != 0) {
+                Kn[i] = kd + d[ba_kidx<CD>()];
+                x2 += kd * kd;
+            } else {
+                Kn[i] = kd;
             }
         }
         if constexpr (ba_has_rot<CD>()) {
@@ -545,8 +596,10 @@ __global__ __launch_bounds__(256) void ba_cand_cam_kernel(int64_t n, const doubl
                                                           const double *__restrict__ dc, const int32_t *__restrict__ cused,
                                                           double *__restrict__ Rn, double *__restrict__ tn, double *__restrict__ Gn,
                                                           BaState *__restrict__ st, double *__restrict__ parts,
-                                                          const int32_t *__restrict__ group_of, const double *__restrict__ gnew, int xoff) {
-    ba_cand_cam_body<CD, GR>(n, Rcw, tcw, G, gfree, dc, cused, Rn, tn, Gn, st, parts, group_of, gnew, xoff);
+                                                          const int32_t *__restrict__ group_of, const double *__restrict__ gnew, int xoff,
+                                                          const double *__restrict__ Kd, const uint8_t *__restrict__ kfree,
+                                                          double *__restrict__ Kn) {
+    ba_cand_cam_body<CD, GR>(n, Rcw, tcw, G, gfree, dc, cused, Rn, tn, Gn, st, parts, group_of, gnew, xoff, Kd, kfree, Kn);
 }
 // ---- focal groups (xm_ctx_bundle_adjust_focal_groups): one focal scale per group of cameras.  With E the 0/1 matrix that copies a group's
 // focal unknown into the focal column of each member, J_shared = J_7 E, so S_shared = E^T S_7 E and b_shared = E^T b_7: the kernels above
@@ -785,7 +838,7 @@ template <int CD, int LOSS>
 __device__ __forceinline__ void ba_cost_body(const SchurLists &S, const double *__restrict__ Rn, const double *__restrict__ tn,
                                              const double *__restrict__ Pn, const double *__restrict__ Gn, const double *__restrict__ Jc,
                                              const double *__restrict__ dc, const double *__restrict__ dP, double *__restrict__ parts,
-                                             double scale) {
+                                             double scale, const double *__restrict__ Kn, BaState *__restrict__ st) {
     constexpr int JP = ba_jp<CD>(), RS = ba_res<CD>();
     __shared__ double sh[4];
     double cost = 0.0, model = 0.0;
@@ -799,7 +852,11 @@ __device__ __forceinline__ void ba_cost_body(const SchurLists &S, const double *
 #pragma unroll
         for (int a = 0; a < 3; ++a) X[a] = R[3 * a] * X3[0] + R[3 * a + 1] * X3[1] + R[3 * a + 2] * X3[2] + T[a];
         double e0, e1;
-        if constexpr (ba_has_focal<CD>()) { e0 = Gn[i] * (X[0] / X[2]) - q0 / q2; e1 = Gn[i] * (X[1] / X[2]) - q1 / q2; }
+        if constexpr (ba_has_dist<CD>()) {   // past 1 + 3 k |u|^2 = 0 the radial map folds: an invalid candidate, as a focal that is not positive
+            const double u0 = X[0] / X[2], u1 = X[1] / X[2], g = Gn[i], kd = Kn[i], rho2 = u0 * u0 + u1 * u1, s = 1.0 + kd * rho2;
+            e0 = g * s * u0 - q0 / q2; e1 = g * s * u1 - q1 / q2;
+            if (!(1.0 + 3.0 * kd * rho2 > 0.0)) st->bad_focal = 1;
+        } else if constexpr (ba_has_focal<CD>()) { e0 = Gn[i] * (X[0] / X[2]) - q0 / q2; e1 = Gn[i] * (X[1] / X[2]) - q1 / q2; }
         else { e0 = X[0] / X[2] - q0 / q2; e1 = X[1] / X[2] - q1 / q2; }
         if constexpr (LOSS == XM_BA_LOSS_TRIVIAL) {
             cost += 0.5 * (e0 * e0 + e1 * e1);
@@ -829,8 +886,9 @@ template <int CD, int LOSS>
 __global__ __launch_bounds__(256) void ba_cost_kernel(SchurLists S, const double *__restrict__ Rn, const double *__restrict__ tn,
                                                       const double *__restrict__ Pn, const double *__restrict__ Gn,
                                                       const double *__restrict__ Jc, const double *__restrict__ dc,
-                                                      const double *__restrict__ dP, double *__restrict__ parts, double scale) {
-    ba_cost_body<CD, LOSS>(S, Rn, tn, Pn, Gn, Jc, dc, dP, parts, scale);
+                                                      const double *__restrict__ dP, double *__restrict__ parts, double scale,
+                                                      const double *__restrict__ Kn, BaState *__restrict__ st) {
+    ba_cost_body<CD, LOSS>(S, Rn, tn, Pn, Gn, Jc, dc, dP, parts, scale, Kn, st);
 }
 // |r_e|^2 per observation in input order at (Rcw, tcw, P) (the eval kernel's projection, unrobustified); -1 where the observation is not used
 // (FOCAL: at the focal scales G, |g_i pi(X) - z|^2; without it G is null and not read)
@@ -846,6 +904,24 @@ __global__ __launch_bounds__(256) void ba_sqerr_kernel(SchurLists S, const doubl
             double r0, r1;
             if constexpr (FOCAL) { const double g = G[S.obs_cam[e]]; r0 = g * (X[0] / X[2]) - q0 / q2; r1 = g * (X[1] / X[2]) - q1 / q2; }
             else { r0 = X[0] / X[2] - q0 / q2; r1 = X[1] / X[2] - q1 / q2; }
+            sq = r0 * r0 + r1 * r1;
+        }
+        sqerr[e] = sq;
+    }
+}
+
+// the same at the focal scales G and the radial coefficients Kd: |g_i (1 + k_i |u|^2) u - z|^2, u = pi(X)
+__global__ __launch_bounds__(256) void ba_sqerr_radial_kernel(SchurLists S, const double *__restrict__ Rcw, const double *__restrict__ tcw,
+                                                              const double *__restrict__ P, const double *__restrict__ G,
+                                                              const double *__restrict__ Kd, double *__restrict__ sqerr) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < S.nobs; e += (int64_t)gridDim.x * 256) {
+        const double w = S.cam_w[S.pos_c[e]], q0 = S.obs_p[3 * e], q1 = S.obs_p[3 * e + 1], q2 = S.obs_p[3 * e + 2];
+        double sq = -1.0;
+        if (w > 0.0 && q2 > 0.0) {
+            double Y[3], X[3];
+            ba_point(Rcw + (size_t)9 * S.obs_cam[e], tcw + (size_t)3 * S.obs_cam[e], P + (size_t)3 * S.obs_lm[e], Y, X);
+            const double u0 = X[0] / X[2], u1 = X[1] / X[2], g = G[S.obs_cam[e]], s = 1.0 + Kd[S.obs_cam[e]] * (u0 * u0 + u1 * u1);
+            const double r0 = g * s * u0 - q0 / q2, r1 = g * s * u1 - q1 / q2;
             sq = r0 * r0 + r1 * r1;
         }
         sqerr[e] = sq;
@@ -1360,6 +1436,8 @@ struct BaWork {
     DevBuf<double> R[3], T[3], P[3];
     DevBuf<double> G[3];        // with a focal column: the focal scales of each set
     DevBuf<uint8_t> gfree;      // the mask of the free focals (not allocated: all free)
+    DevBuf<double> Kd[3];       // with a distortion column: the radial coefficients of each set
+    DevBuf<uint8_t> kfree;      // the mask of the free coefficients (not allocated: all free)
     // ---- focal groups (cfg.ngroups > 0): G[] and gfree above are the groups' values copied to every member, so that the eval, candidate and
     // cost kernels read them as they read per-camera ones; the member lists (host counting sort, once per call) and the groups' arrays
     const bool grouped;
@@ -1403,7 +1481,7 @@ struct BaWork {
     DevBuf<double> Sd, ysub;
 
     BaWork(const SchurOp &SO_, const BaSettings &cfg_, const double *rot, const double *t, const double *p, hipStream_t st_, bool dense)
-        : SO(SO_), cfg(cfg_), st(st_), S(SO_.lists()), n(S.n), m(S.m), nobs(S.nobs), grouped(ba_has_focal<CD>() && cfg_.ngroups > 0),
+        : SO(SO_), cfg(cfg_), st(st_), S(SO_.lists()), n(S.n), m(S.m), nobs(S.nobs), grouped(ba_can_group<CD>() && cfg_.ngroups > 0),
           ng(grouped ? cfg_.ngroups : 0), nd((int64_t)CD * S.n) {
         to_device_layout(SO, rot, t, p, hR, hT, hP);
         const bool nonmono = cfg.nonmonotonic;
@@ -1421,6 +1499,14 @@ struct BaWork {
                     gfree.alloc((size_t)n, false);
                     XM_HIP_CHECK(hipMemcpyAsync(gfree.p, cfg.focal_free, (size_t)n, hipMemcpyHostToDevice, st));
                 }
+            }
+        }
+        if constexpr (ba_has_dist<CD>()) {
+            for (int k = 0; k < (nonmono ? 3 : 2); ++k) Kd[k].alloc((size_t)n, false);
+            XM_HIP_CHECK(hipMemcpyAsync(Kd[0].p, cfg.dist, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+            if (cfg.dist_free) {
+                kfree.alloc((size_t)n, false);
+                XM_HIP_CHECK(hipMemcpyAsync(kfree.p, cfg.dist_free, (size_t)n, hipMemcpyHostToDevice, st));
             }
         }
         Jc.alloc((size_t)NP * nobs); Jl.alloc((size_t)NP * S.lm_total);
@@ -1560,15 +1646,16 @@ struct BaWork {
     // f(GR): `grouped` as a compile-time constant (the grouped kernels exist for a camera block with a focal column only)
     template <class F>
     void by_grouping(F &&f) {
-        if constexpr (ba_has_focal<CD>()) {
+        if constexpr (ba_can_group<CD>()) {
             if (grouped) return f(std::true_type{});
         }
         f(std::false_type{});
     }
     void eval() {
-        with_loss(cfg.loss, [&](auto L) {   // G[] and gfree are not allocated (null) without a focal column
+        with_loss(cfg.loss, [&](auto L) {   // G[] and gfree are not allocated (null) without a focal column, Kd[] and kfree without a distortion column
             hipLaunchKernelGGL((ba_eval_kernel<CD, L.value>), dim3(ge), b256, 0, st, S, (const double *)R[cur].p, (const double *)T[cur].p,
-                               (const double *)P[cur].p, (const double *)G[cur].p, (const uint8_t *)gfree.p, Jc.p, Jl.p, pp + o_eval, cfg.loss_scale);
+                               (const double *)P[cur].p, (const double *)G[cur].p, (const uint8_t *)gfree.p, (const double *)Kd[cur].p,
+                               (const uint8_t *)kfree.p, Jc.p, Jl.p, pp + o_eval, cfg.loss_scale);
         });
         BaReduce rd{};
         rd.sum_p[0] = pp + o_eval; rd.sum_n[0] = ge; rd.sum_out[0] = &dst->cost;
@@ -1581,7 +1668,7 @@ struct BaWork {
             hipLaunchKernelGGL((ba_cam_kernel<CD, GR.value>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)vinv.p,
                                (const double *)gl.p, mu, ustar.p, sinv.p, b.p, cused.p, pp + o_gmax + glm, fstat.p);
         });
-        if constexpr (ba_has_focal<CD>()) {
+        if constexpr (ba_can_group<CD>()) {
             if (grouped) {   // the groups' pass: their gradient entries join the maximum
                 hipLaunchKernelGGL((ba_group_setup_kernel<CD>), dim3(ggrp), b256, 0, st, grp, (const double *)ustar.p, (const double *)fstat.p,
                                    (const int32_t *)cused.p, mu, b.p, sinv.p, grp_D.p, grp_F.p, grp_moving.p, pp + o_gmax + glm + gcam);
@@ -1598,7 +1685,7 @@ struct BaWork {
     bool dense_mode = false;   // the dense solver runs no PCG: no preconditioner to set up
     // F by G products with indicator vectors (through the PCG's direction and product vectors, which the PCG's start fills anew), its inverse
     void exact_focal_block() {
-        if constexpr (ba_has_focal<CD>()) {
+        if constexpr (ba_can_group<CD>()) {
             XM_HIP_CHECK(hipMemsetAsync(&dst->done, 0, sizeof(int32_t), st));   // the last solve's flag would skip the camera side of the product
             const int G = (int)ng;
             for (int d = 0; d < G; ++d) {
@@ -1630,7 +1717,7 @@ struct BaWork {
     }
     // behind the PCG's start (init) or the update of iteration it: the exact focal block's part of z
     void focal_precond(int it, int init) {
-        if constexpr (ba_has_focal<CD>())
+        if constexpr (ba_can_group<CD>())
             hipLaunchKernelGGL((ba_group_precond_kernel<CD>), dim3(1), b256, 0, st, grp, (const double *)grp_Fm.p, a, it, init, f_exact ? 1 : 0);
     }
     void pcg_update(int it) {
@@ -1639,7 +1726,7 @@ struct BaWork {
     }
     // pe = E src
     void expand(const double *src, const BaState *gate) {
-        if constexpr (ba_has_focal<CD>())
+        if constexpr (ba_can_group<CD>())
             hipLaunchKernelGGL((ba_group_expand_kernel<CD>), dim3(flat_grid(n * CD)), b256, 0, st, n, (const int32_t *)grp_repof.p, src, pe.p, gate);
     }
     // every LM iteration (S changes with mu): the block inverses; two-level: A_c = P^T S P and its inverse.  A_c that cannot be inverted (a
@@ -1685,7 +1772,7 @@ struct BaWork {
         hipLaunchKernelGGL((ba_lmx_kernel<CD>), dim3(glm), blm, 0, st, S, (const double *)Jl.p, (const double *)vinv.p, (const double *)nullptr, 1.0,
                            (const int32_t *)lused.p, (const double *)ae.p, gate, y.p);
         hipLaunchKernelGGL((ba_camx_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)y.p, ae);
-        if constexpr (ba_has_focal<CD>()) {
+        if constexpr (ba_can_group<CD>()) {
             if (grouped) {
                 hipLaunchKernelGGL((ba_group_sum_kernel<CD>), dim3(ggrp), b256, 0, st, grp, (const double *)grp_D.p, cur_mu, (const double *)ar.p,
                                    ar.Ap, ar.ppap + gcam, gate);
@@ -1698,7 +1785,7 @@ struct BaWork {
         XM_HIP_CHECK(hipMemsetAsync(&dst->fail, 0, sizeof(int32_t), st));
         hipLaunchKernelGGL((ba_schur_dense_kernel<CD>), dim3(gcam), b256, 0, st, S, (const double *)Jc.p, (const double *)Jl.p, (const double *)vinv.p,
                            (const double *)ustar.p, Sd.p, nd);
-        if constexpr (ba_has_focal<CD>()) {
+        if constexpr (ba_can_group<CD>()) {
             if (grouped) {   // S_shared = E^T S_7 E + mu D in place
                 hipLaunchKernelGGL((ba_group_dense_rows_kernel<CD>), dim3(flat_grid(ng * nd)), b256, 0, st, grp, Sd.p, nd, nd, grp_T.p);
                 hipLaunchKernelGGL((ba_group_dense_cols_kernel<CD>), dim3((unsigned)((ng * ng + 255) / 256)), b256, 0, st, grp, nd, (const double *)grp_T.p,
@@ -1748,21 +1835,24 @@ struct BaWork {
                            (const int32_t *)lused.p, dc, (const BaState *)nullptr, dP.p);
         if constexpr (ba_has_focal<CD>()) {
             XM_HIP_CHECK(hipMemsetAsync(&dst->bad_focal, 0, sizeof(int32_t), st));
-            if (grouped)
-                hipLaunchKernelGGL((ba_group_cand_kernel<CD>), dim3(ggf), b256, 0, st, grp, (const double *)G[cur].p, dshared,
-                                   (const int32_t *)grp_moving.p, grp_new.p, dst, pp + o_cand + gfc, gfg);
+            if constexpr (ba_can_group<CD>()) {
+                if (grouped)
+                    hipLaunchKernelGGL((ba_group_cand_kernel<CD>), dim3(ggf), b256, 0, st, grp, (const double *)G[cur].p, dshared,
+                                       (const int32_t *)grp_moving.p, grp_new.p, dst, pp + o_cand + gfc, gfg);
+            }
         }
-        by_grouping([&](auto GR) {   // G[], gfree and the groups' arrays: null where there are none
+        by_grouping([&](auto GR) {   // G[], gfree, Kd[], kfree and the groups' arrays: null where there are none
             hipLaunchKernelGGL((ba_cand_cam_kernel<CD, GR.value>), dim3(gfc), b256, 0, st, n, (const double *)R[cur].p, (const double *)T[cur].p,
                                (const double *)G[cur].p, (const uint8_t *)gfree.p, dc, (const int32_t *)cused.p, R[nx].p, T[nx].p, G[nx].p,
-                               dst, pp + o_cand, (const int32_t *)grp_of.p, (const double *)grp_new.p, gfg);
+                               dst, pp + o_cand, (const int32_t *)grp_of.p, (const double *)grp_new.p, gfg, (const double *)Kd[cur].p,
+                               (const uint8_t *)kfree.p, Kd[nx].p);
         });
         hipLaunchKernelGGL(ba_cand_vec_kernel<3>, dim3(gfl), b256, 0, st, m, (const double *)P[cur].p, (const double *)dP.p, (const int32_t *)lused.p,
                            P[nx].p, pp + o_cand + 2 * (size_t)gfg);
         with_loss(cfg.loss, [&](auto L) {
             hipLaunchKernelGGL((ba_cost_kernel<CD, L.value>), dim3(ge), b256, 0, st, S, (const double *)R[nx].p, (const double *)T[nx].p,
                                (const double *)P[nx].p, (const double *)G[nx].p, (const double *)Jc.p, dc, (const double *)dP.p, pp + o_cost,
-                               cfg.loss_scale);
+                               cfg.loss_scale, (const double *)Kd[nx].p, dst);
         });
         reduce(candidate_sums(pp + o_cost, ge, pp + o_cand, gfg, gfl, dst));
     }
@@ -1853,6 +1943,10 @@ void run(const SchurOp &SO, const BaSettings &cfg, double *rot, double *t, doubl
             XM_HIP_CHECK(hipMemcpyAsync(cfg.focal, W.G[cur].p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
             wait_stream(st, cfg.watchdog_s, kStage, "the refined focal scales");
         }
+    }
+    if constexpr (ba_has_dist<CD>()) {   // held coefficients and those of cameras without a used observation: copied from set to set
+        XM_HIP_CHECK(hipMemcpyAsync(cfg.dist, W.Kd[cur].p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+        wait_stream(st, cfg.watchdog_s, kStage, "the refined radial coefficients");
     }
     out.status = res.status; out.iters = res.iters; out.accepted = res.accepted; out.pcg_iters = res.pcg_total;
     out.final_cost = res.final_cost; out.gradient_max = res.gmax; out.trace_len = lm_copy_trace(res, cfg.trace, cfg.trace_cap);
@@ -1999,6 +2093,9 @@ void probe(const SchurOp &SO, const BaSettings &cfg, const double *rot, const do
                 for (int64_t c = 0; c < W.ng; ++c) q.focal1[c] = W.h_rep[(size_t)c] >= 0 ? hG[(size_t)W.h_rep[(size_t)c]] : cfg.focal[c];
             } else if (q.focal1) { d2h(q.focal1, W.G[1].p, (size_t)n * sizeof(double)); sync("the candidate focal scales"); }
         }
+        if constexpr (ba_has_dist<CD>()) {
+            if (q.dist1) { d2h(q.dist1, W.Kd[1].p, (size_t)n * sizeof(double)); sync("the candidate radial coefficients"); }
+        }
         lm_out(W.dP.p, 3, q.dP);
         lm_out(W.P[1].p, 3, q.p1);
         if (q.rot1 || q.t1) {   // as the loop returns them: cameras without a used observation keep the caller's bits
@@ -2021,7 +2118,11 @@ void with_cd(const BaSettings &cfg, const std::string &who, F &&f) {
     if (cfg.refine_focal) {
         if (cfg.precond != 0 || !cfg.focal) throw Error(XM_ERR_ARG, who + "_focal: needs the focal scales and the default preconditioner");
         if (cfg.ngroups > 0 && !cfg.group_of) throw Error(XM_ERR_ARG, who + "_focal_groups: needs group_of");
-        if (cfg.fix_rotations) f(std::integral_constant<int, 4>{});
+        if (cfg.refine_dist) {
+            if (!cfg.dist || cfg.ngroups > 0) throw Error(XM_ERR_ARG, who + "_radial: needs the radial coefficients and no focal groups");
+            if (cfg.fix_rotations) f(std::integral_constant<int, 5>{});
+            else f(std::integral_constant<int, 8>{});
+        } else if (cfg.fix_rotations) f(std::integral_constant<int, 4>{});
         else f(std::integral_constant<int, 7>{});
     } else if (cfg.fix_rotations) f(std::integral_constant<int, 3>{});
     else f(std::integral_constant<int, 6>{});
@@ -2101,12 +2202,17 @@ void ba_probe(const SchurOp &S, const BaSettings &cfg, const double *rot, const 
     with_cd(cfg, "xm_ctx_ba_probe", [&](auto CD) { probe<CD.value>(S, cfg, rot, t, p, q, st); });
 }
 
-void reprojection_errors(const SchurOp &SO, const double *rot, const double *t, const double *p, const double *focal, double *sqerr, double watchdog_s,
-                         hipStream_t st) {
+void reprojection_errors(const SchurOp &SO, const double *rot, const double *t, const double *p, const double *focal, const double *dist,
+                         double *sqerr, double watchdog_s, hipStream_t st) {
     const SchurLists S = SO.lists();
     std::vector<double> hR, hT, hP;
     to_device_layout(SO, rot, t, p, hR, hT, hP);
-    DevBuf<double> R, T, P, G, out;
+    DevBuf<double> R, T, P, G, K, out;
+    if (dist) {
+        if (!focal) throw Error(XM_ERR_ARG, "xm_ctx_reprojection_errors_radial: needs the focal scales");
+        K.alloc((size_t)S.n, false);
+        XM_HIP_CHECK(hipMemcpyAsync(K.p, dist, (size_t)S.n * sizeof(double), hipMemcpyHostToDevice, st));
+    }
     if (focal) {
         G.alloc((size_t)S.n, false);
         XM_HIP_CHECK(hipMemcpyAsync(G.p, focal, (size_t)S.n * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2120,7 +2226,11 @@ void reprojection_errors(const SchurOp &SO, const double *rot, const double *t, 
             hipLaunchKernelGGL(ba_sqerr_kernel<FOCAL.value>, dim3(flat_grid(S.nobs)), dim3(256), 0, st, S, (const double *)R.p, (const double *)T.p,
                                (const double *)P.p, (const double *)G.p, out.p);
         };
-        if (focal) launch(std::true_type{}); else launch(std::false_type{});
+        if (dist)
+            hipLaunchKernelGGL(ba_sqerr_radial_kernel, dim3(flat_grid(S.nobs)), dim3(256), 0, st, S, (const double *)R.p, (const double *)T.p,
+                               (const double *)P.p, (const double *)G.p, (const double *)K.p, out.p);
+        else if (focal) launch(std::true_type{});
+        else launch(std::false_type{});
         check_launch("the reprojection errors");
         XM_HIP_CHECK(hipMemcpyAsync(sqerr, out.p, (size_t)S.nobs * sizeof(double), hipMemcpyDeviceToHost, st));
     }

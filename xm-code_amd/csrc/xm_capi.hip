@@ -466,8 +466,10 @@ static void check_focal_groups(const std::string &w, int64_t n, int64_t ngroups,
         if (group_of[i] < 0 || group_of[i] >= ngroups) throw xm::Error(XM_ERR_ARG, w + ": group_of[" + std::to_string(i) + "] is out of range");
 }
 static void ba_entry(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, bool with_focal, double *focal,
-                     const uint8_t *focal_free, xm_ba_result_t *res, bool groups = false, int64_t ngroups = 0, const int32_t *group_of = nullptr) {
-    if (!ctx || !opt || !res || !rot || !t || !p || (with_focal && !focal)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: null argument");
+                     const uint8_t *focal_free, xm_ba_result_t *res, bool groups = false, int64_t ngroups = 0, const int32_t *group_of = nullptr,
+                     bool with_dist = false, double *dist = nullptr, const uint8_t *dist_free = nullptr) {
+    if (!ctx || !opt || !res || !rot || !t || !p || (with_focal && !focal) || (with_dist && !dist))
+        throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: null argument");
     static_assert(offsetof(xm_ba_options_t, loss) == XM_BA_OPTIONS_SIZE_V1, "the first version of xm_ba_options_t ends at trace");
     if (opt->struct_size != sizeof(xm_ba_options_t) && opt->struct_size != XM_BA_OPTIONS_SIZE_V1)
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: xm_ba_options_t.struct_size is neither sizeof(xm_ba_options_t) nor XM_BA_OPTIONS_SIZE_V1");
@@ -482,9 +484,10 @@ static void ba_entry(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, dou
     if (o.max_iters < 0 || bad(o.max_time) || bad(o.function_tol) || bad(o.gradient_tol) || bad(o.parameter_tol))
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: negative or non-finite setting");
     if (o.flags & ~(XM_BA_FIX_ROTATIONS | XM_BA_NONMONOTONIC | XM_BA_DENSE_SCHUR | XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS |
-                    (with_focal ? XM_BA_REFINE_FOCAL : 0u)))
+                    (with_focal ? XM_BA_REFINE_FOCAL : 0u) | (with_dist ? XM_BA_REFINE_RADIAL : 0u)))
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: unknown flag");
     if (with_focal && !(o.flags & XM_BA_REFINE_FOCAL)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust_focal: XM_BA_REFINE_FOCAL is not set");
+    if (with_dist && !(o.flags & XM_BA_REFINE_RADIAL)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust_radial: XM_BA_REFINE_RADIAL is not set");
     if (with_focal && (o.flags & (XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS)))
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust_focal: the aggregate preconditioners have no focal column (use the default preconditioner)");
     if ((o.flags & XM_BA_PRECOND_TWO_LEVEL) && (o.flags & XM_BA_PRECOND_BLOCKS))
@@ -502,7 +505,7 @@ static void ba_entry(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, dou
     if (groups) {
         check_focal_groups("xm_ctx_bundle_adjust_focal_groups", n, ngroups, group_of);
     }
-    if ((o.flags & XM_BA_DENSE_SCHUR) && (((o.flags & XM_BA_FIX_ROTATIONS) ? 3 : 6) + (with_focal ? 1 : 0)) * n > XM_BA_DENSE_MAX_ROWS)
+    if ((o.flags & XM_BA_DENSE_SCHUR) && (((o.flags & XM_BA_FIX_ROTATIONS) ? 3 : 6) + (with_focal ? 1 : 0) + (with_dist ? 1 : 0)) * n > XM_BA_DENSE_MAX_ROWS)
         throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: XM_BA_DENSE_SCHUR with more than XM_BA_DENSE_MAX_ROWS rows in the reduced camera system");
     for (int64_t k = 0; k < 9 * n; ++k)
         if (!std::isfinite(rot[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust: rotations are not finite");
@@ -513,8 +516,12 @@ static void ba_entry(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, dou
     if (with_focal)
         for (int64_t k = 0; k < (groups ? ngroups : n); ++k)
             if (!std::isfinite(focal[k]) || !(focal[k] > 0.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust_focal: a focal scale is not finite and > 0");
+    if (with_dist)
+        for (int64_t k = 0; k < n; ++k)
+            if (!std::isfinite(dist[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_bundle_adjust_radial: a radial coefficient is not finite");
     xm::BaSettings c;
     c.refine_focal = with_focal; c.focal = focal; c.focal_free = focal_free;
+    c.refine_dist = with_dist; c.dist = dist; c.dist_free = dist_free;
     if (groups) { c.ngroups = ngroups; c.group_of = group_of; }
     if (o.max_iters > 0) c.max_iters = o.max_iters;
     if (o.max_time > 0.0) c.max_time = o.max_time;
@@ -559,8 +566,16 @@ int xm_ctx_bundle_adjust_focal_groups(xm_ctx_t *ctx, const xm_ba_options_t *opt,
     return XM_OK;
     XM_CATCH
 }
-static void sqerr_entry(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, bool with_focal, const double *focal, double *sqerr) {
-    if (!ctx || !rot || !t || !p || !sqerr || (with_focal && !focal)) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: null argument");
+int xm_ctx_bundle_adjust_radial(xm_ctx_t *ctx, const xm_ba_options_t *opt, double *rot, double *t, double *p, double *focal, const uint8_t *focal_free,
+                                double *dist, const uint8_t *dist_free, xm_ba_result_t *res) {
+    XM_TRY
+    ba_entry(ctx, opt, rot, t, p, true, focal, focal_free, res, false, 0, nullptr, true, dist, dist_free);
+    return XM_OK;
+    XM_CATCH
+}
+static void sqerr_entry(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, bool with_focal, const double *focal, double *sqerr,
+                        bool with_dist = false, const double *dist = nullptr) {
+    if (!ctx || !rot || !t || !p || !sqerr || (with_focal && !focal) || (with_dist && !dist)) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: null argument");
     if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: single-GPU contexts only (not n_gpus > 1)");
     if (ctx->impl->world() > 1) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: single-rank contexts only");
     const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks();
@@ -573,7 +588,17 @@ static void sqerr_entry(xm_ctx_t *ctx, const double *rot, const double *t, const
     if (with_focal)
         for (int64_t k = 0; k < n; ++k)
             if (!std::isfinite(focal[k]) || !(focal[k] > 0.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors_focal: a focal scale is not finite and > 0");
-    ctx->impl->reprojection_errors(rot, t, p, sqerr, with_focal ? focal : nullptr);
+    if (with_dist)
+        for (int64_t k = 0; k < n; ++k)
+            if (!std::isfinite(dist[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_reprojection_errors_radial: a radial coefficient is not finite");
+    ctx->impl->reprojection_errors(rot, t, p, sqerr, with_focal ? focal : nullptr, with_dist ? dist : nullptr);
+}
+int xm_ctx_reprojection_errors_radial(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, const double *focal, const double *dist,
+                                      double *sqerr) {
+    XM_TRY
+    sqerr_entry(ctx, rot, t, p, true, focal, sqerr, true, dist);
+    return XM_OK;
+    XM_CATCH
 }
 int xm_ctx_reprojection_errors(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, double *sqerr) {
     XM_TRY
@@ -589,14 +614,17 @@ int xm_ctx_reprojection_errors_focal(xm_ctx_t *ctx, const double *rot, const dou
 }
 static void probe_entry(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, bool with_focal, const double *focal,
                         const uint8_t *focal_free, xm_ba_probe_t *pr, double *focal1, bool groups = false, int64_t ngroups = 0,
-                        const int32_t *group_of = nullptr) {
-    if (!ctx || !rot || !t || !p || !pr || (with_focal && !focal)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: null argument");
+                        const int32_t *group_of = nullptr, bool with_dist = false, const double *dist = nullptr, const uint8_t *dist_free = nullptr,
+                        double *dist1 = nullptr) {
+    if (!ctx || !rot || !t || !p || !pr || (with_focal && !focal) || (with_dist && !dist)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: null argument");
     if (pr->struct_size != sizeof(xm_ba_probe_t)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: xm_ba_probe_t.struct_size is not sizeof(xm_ba_probe_t)");
     if (ctx->team || !ctx->impl) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: single-GPU contexts only (not n_gpus > 1)");
     if (ctx->impl->world() > 1) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: single-rank contexts only");
     if (!(pr->mu > 0.0) || !std::isfinite(pr->mu)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: mu must be finite and > 0");
-    if (pr->flags & ~(XM_BA_FIX_ROTATIONS | XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS | (with_focal ? XM_BA_REFINE_FOCAL : 0u)))
+    if (pr->flags & ~(XM_BA_FIX_ROTATIONS | XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS | (with_focal ? XM_BA_REFINE_FOCAL : 0u) |
+                      (with_dist ? XM_BA_REFINE_RADIAL : 0u)))
         throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: unknown flag");
+    if (with_dist && !(pr->flags & XM_BA_REFINE_RADIAL)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe_radial: XM_BA_REFINE_RADIAL is not set");
     if (with_focal && !(pr->flags & XM_BA_REFINE_FOCAL)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe_focal: XM_BA_REFINE_FOCAL is not set");
     if (with_focal && (pr->flags & (XM_BA_PRECOND_TWO_LEVEL | XM_BA_PRECOND_BLOCKS)))
         throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe_focal: the aggregate preconditioners have no focal column");
@@ -607,7 +635,7 @@ static void probe_entry(xm_ctx_t *ctx, const double *rot, const double *t, const
     if (pr->loss != XM_BA_LOSS_TRIVIAL && !(std::isfinite(pr->loss_scale) && pr->loss_scale > 0.0))
         throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: a robust loss needs a finite loss_scale > 0");
     if (pr->k < 0 || (pr->k > 0 && !pr->X)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: k > 0 needs X");
-    const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks(), cd = ((pr->flags & XM_BA_FIX_ROTATIONS) ? 3 : 6) + (with_focal ? 1 : 0);
+    const int64_t n = ctx->impl->cameras(), m = ctx->impl->n_landmarks(), cd = ((pr->flags & XM_BA_FIX_ROTATIONS) ? 3 : 6) + (with_focal ? 1 : 0) + (with_dist ? 1 : 0);
     if (pr->Sdense && cd * n > XM_BA_PROBE_DENSE_MAX_ROWS) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe: Sdense with more than XM_BA_PROBE_DENSE_MAX_ROWS rows");
     if (groups) {
         check_focal_groups("xm_ctx_ba_probe_focal_groups", n, ngroups, group_of);
@@ -627,8 +655,12 @@ static void probe_entry(xm_ctx_t *ctx, const double *rot, const double *t, const
     if (with_focal)
         for (int64_t k = 0; k < (groups ? ngroups : n); ++k)
             if (!std::isfinite(focal[k]) || !(focal[k] > 0.0)) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe_focal: a focal scale is not finite and > 0");
+    if (with_dist)
+        for (int64_t k = 0; k < n; ++k)
+            if (!std::isfinite(dist[k])) throw xm::Error(XM_ERR_ARG, "xm_ctx_ba_probe_radial: a radial coefficient is not finite");
     xm::BaSettings c;
     c.refine_focal = with_focal; c.focal = const_cast<double *>(focal); c.focal_free = focal_free;   // the probe only reads them
+    c.refine_dist = with_dist; c.dist = const_cast<double *>(dist); c.dist_free = dist_free;
     if (groups) { c.ngroups = ngroups; c.group_of = group_of; }
     c.fix_rotations = (pr->flags & XM_BA_FIX_ROTATIONS) != 0;
     c.loss = pr->loss; c.loss_scale = pr->loss_scale;
@@ -638,6 +670,7 @@ static void probe_entry(xm_ctx_t *ctx, const double *rot, const double *t, const
     q.b = pr->b; q.g_l = pr->g_l; q.vinv = pr->vinv; q.ustar = pr->ustar; q.sinv = pr->sinv; q.cused = pr->cused; q.lused = pr->lused;
     q.SX = pr->SX; q.Sdense = pr->Sdense; q.MX = pr->MX; q.Pm = pr->Pm; q.dropped = pr->dropped; q.Ac = pr->Ac;
     q.dP = pr->dP; q.rot1 = pr->rot1; q.t1 = pr->t1; q.p1 = pr->p1; q.focal1 = with_focal ? focal1 : nullptr;
+    q.dist1 = with_dist ? dist1 : nullptr;
     if (groups) { q.group_D = pr->dropped; q.group_F = pr->Ac; q.Pm = q.dropped = q.Ac = nullptr; }   // no aggregates here: their pointers serve the groups
     ctx->impl->ba_probe(c, rot, t, p, q);
     pr->cost = q.cost; pr->gmax = q.gmax; pr->cost1 = q.cost1; pr->model = q.model; pr->n_used = q.n_used;
@@ -654,6 +687,13 @@ int xm_ctx_ba_probe_focal(xm_ctx_t *ctx, const double *rot, const double *t, con
                           xm_ba_probe_t *pr, double *focal1) {
     XM_TRY
     probe_entry(ctx, rot, t, p, true, focal, focal_free, pr, focal1);
+    return XM_OK;
+    XM_CATCH
+}
+int xm_ctx_ba_probe_radial(xm_ctx_t *ctx, const double *rot, const double *t, const double *p, const double *focal, const uint8_t *focal_free,
+                           const double *dist, const uint8_t *dist_free, xm_ba_probe_t *pr, double *focal1, double *dist1) {
+    XM_TRY
+    probe_entry(ctx, rot, t, p, true, focal, focal_free, pr, focal1, false, 0, nullptr, true, dist, dist_free, dist1);
     return XM_OK;
     XM_CATCH
 }

@@ -183,7 +183,7 @@ public:
     void rtr_probe(xm_rtr_probe_t &q);   // test export (include/xm_amd.h: xm_ctx_rtr_probe): the trust region's kernels stage by stage
     void schur_probe(xm_schur_probe_t &q);   // test export (xm_ctx_schur_probe): the matrix-free Q's factors, chain stages and inner-CG pieces
     void cert_probe(xm_cert_probe_t &q); // test export (xm_ctx_cert_probe): the certificate's Lanczos eigen-solver
-    void reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr, const double *focal = nullptr);   // per observation, input order (xm_ba.h)
+    void reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr, const double *focal = nullptr, const double *dist = nullptr);   // per observation, input order (xm_ba.h)
     // GLOMAP's track filters at (rot, t, p) with the current weights (xm_trackfilter.h); cfg.watchdog_s is the context's
     void filter_tracks(const TfSettings &cfg, const double *rot, const double *t, const double *p, uint8_t *keep, uint8_t *reason,
                        int32_t *lm_views, uint8_t *lm_status, TfOutcome &out);

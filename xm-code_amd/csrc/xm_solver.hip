@@ -2551,11 +2551,11 @@ void Context::schur_probe(xm_schur_probe_t &q) {
     if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_schur_probe: single-rank contexts only");
     schur_->probe(q, st_);
 }
-void Context::reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr, const double *focal) {
+void Context::reprojection_errors(const double *rot, const double *t, const double *p, double *sqerr, const double *focal, const double *dist) {
     if (!schur_)
         throw Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: needs a matrix-free context (XM_STORAGE_SCHUR): the other storages hold no landmarks");
     if (comm_->active()) throw Error(XM_ERR_ARG, "xm_ctx_reprojection_errors: single-rank contexts only");
-    xm::reprojection_errors(*schur_, rot, t, p, focal, sqerr, cfg_.watchdog_s, st_);
+    xm::reprojection_errors(*schur_, rot, t, p, focal, dist, sqerr, cfg_.watchdog_s, st_);
 }
 void Context::filter_tracks(const TfSettings &cfg, const double *rot, const double *t, const double *p, uint8_t *keep, uint8_t *reason, int32_t *lm_views,
                             uint8_t *lm_status, TfOutcome &out) {

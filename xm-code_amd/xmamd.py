@@ -40,6 +40,7 @@ EXPORTS = [
     "xm_ctx_bundle_adjust", "xm_ctx_reprojection_errors", "xm_spd_solve", "xm_la_probe", "xm_ba_aggregate_plan", "xm_ctx_ba_probe", "xm_lm_replay",
     "xm_ctx_bundle_adjust_focal", "xm_ctx_reprojection_errors_focal", "xm_ctx_ba_probe_focal",
     "xm_ctx_bundle_adjust_focal_groups", "xm_ctx_ba_probe_focal_groups",
+    "xm_ctx_bundle_adjust_radial", "xm_ctx_reprojection_errors_radial", "xm_ctx_ba_probe_radial",
     "xm_clean_observations", "xm_ctx_clean_observations", "xm_ctx_rtr_probe", "xm_ctx_outer_probe", "xm_ctx_cert_probe", "xm_tridiag_min", "xm_ctx_schur_probe",
     "xm_ctx_dense_q", "xm_create_matrix", "xm_schur_dense_limits",
     "xm_pair_filter", "xm_pair_filter_limits",
@@ -482,6 +483,7 @@ BA_AGG_CAMS = 16               # cameras per aggregate
 BA_MAX_AGGREGATES = 4096
 BA_FOCAL_GROUPS_EXACT = 16     # focal groups: up to this many, the preconditioner's focal block is the exact G x G one
 BA_REFINE_FOCAL = 128          # a focal scale per camera in the camera block (xm_ctx_bundle_adjust_focal; the default preconditioner only)
+BA_REFINE_RADIAL = 256         # a radial coefficient per camera behind the focal scale (xm_ctx_bundle_adjust_radial; with BA_REFINE_FOCAL only)
 BA_PRECONDITIONERS = {"jacobi": 0, "blocks": BA_PRECOND_BLOCKS, "two_level": BA_PRECOND_TWO_LEVEL}
 BA_LOSS = {"trivial": 0, "huber": 1, "soft_l1": 2, "cauchy": 3, "arctan": 4}
 BA_OPTIONS_SIZE_V1 = 64        # struct_size of callers built before loss, max_nonmonotonic and loss_scale (include/xm_amd.h)
@@ -528,6 +530,9 @@ def lib():
         L.xm_ctx_bundle_adjust_focal.argtypes = [C.c_void_p, C.POINTER(BaOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.POINTER(BaResult)]
         L.xm_ctx_reprojection_errors_focal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.xm_ctx_bundle_adjust_radial.argtypes = [C.c_void_p, C.POINTER(BaOptions)] + [C.c_void_p] * 7 + [C.POINTER(BaResult)]
+        L.xm_ctx_reprojection_errors_radial.argtypes = [C.c_void_p] * 7
+        L.xm_ctx_ba_probe_radial.argtypes = [C.c_void_p] * 8 + [C.POINTER(BaProbe), C.c_void_p, C.c_void_p]
         L.xm_ctx_ba_probe_focal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BaProbe), C.c_void_p]
         L.xm_ctx_bundle_adjust_focal_groups.argtypes = [C.c_void_p, C.POINTER(BaOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.POINTER(BaResult)]
@@ -952,6 +957,64 @@ def _focal_group_args(n, focal_group, focal, focal_free, preconditioner="jacobi"
         raise XmError(f"focal_group: an entry lies outside [0, {G})")
     focal, focal_free = _focal_args(G, focal, focal_free, preconditioner)
     return np.ascontiguousarray(group_of, dtype=np.int32), focal, focal_free
+
+
+def _dist_args(n, dist, dist_free):
+    """the radial coefficients (zeros when None) and the mask of the free ones (None = all) of a call with a distortion column, refused
+    here, before the device, as the C entry points refuse them: a wrong length, a coefficient that is not finite"""
+    dist = np.zeros(n) if dist is None else np.array(dist, dtype=np.float64).reshape(-1)
+    if dist.shape != (n,):
+        raise XmError(f"distortion: {dist.size} values for {n} cameras")
+    if not np.isfinite(dist).all():
+        raise XmError("distortion: every radial coefficient must be finite")
+    if dist_free is not None:
+        dist_free = np.ascontiguousarray(np.asarray(dist_free).reshape(-1) != 0, dtype=np.uint8)
+        if dist_free.shape != (n,):
+            raise XmError(f"distortion_free: {dist_free.size} values for {n} cameras")
+    return dist, dist_free
+
+
+def undistort_observations(p, cam, focal, distortion):
+    """the observations (3 x nobs or nobs x 3 as given) of the cameras cam (nobs) as a pinhole camera at g = 1, k = 0 sees them, from the
+    refined focal scales and radial coefficients of bundle_adjust(refine_distortion=True): z = (p0, p1) / p2 = g s u with s = 1 + k rho^2,
+    rho = |u|, so rho solves rho (1 + k rho^2) = |z| / g on the monotone branch (Newton from |z| / g, at most 50 iterations, stopped when
+    the iterate no longer changes) and the result is (p0 / (g s), p1 / (g s), p2).  With k = 0 the bytes of rescale_observations.
+    -> (p, no_root): no_root (nobs, bool) flags the observations that have no root on that branch (beyond the fold of a negative k);
+    they are left as given.  A Context built from the result carries the refined calibration: filter_tracks, refine_filtered,
+    global_positioning, triangulate_tracks and a second solve then use it.  Host numpy."""
+    p = np.array(p, dtype=np.float64)
+    cam = np.asarray(cam).reshape(-1)
+    g = np.asarray(focal, dtype=np.float64).reshape(-1)[cam]
+    k = np.asarray(distortion, dtype=np.float64).reshape(-1)[cam]
+    if not (np.isfinite(g).all() and (g > 0.0).all()):
+        raise XmError("undistort_observations: every focal scale must be finite and > 0")
+    if not np.isfinite(k).all():
+        raise XmError("undistort_observations: every radial coefficient must be finite")
+    if p.ndim == 2 and p.shape[0] == 3 and p.shape[1] == cam.size:
+        rows = p
+    elif p.ndim == 2 and p.shape == (cam.size, 3):
+        rows = p.T
+    else:
+        raise XmError("undistort_observations: p must be 3 x nobs or nobs x 3")
+    with np.errstate(all="ignore"):
+        c = np.hypot(rows[0] / rows[2], rows[1] / rows[2]) / g          # |z| / g
+        # k < 0: rho (1 + k rho^2) rises up to the fold rho_f = 1 / sqrt(-3 k), where it is 2 rho_f / 3: beyond that no root
+        fold = np.where(k < 0.0, 1.0 / np.sqrt(-3.0 * np.where(k < 0.0, k, -1.0)), np.inf)
+        no_root = (~np.isfinite(c) & (k != 0.0)) | ((k < 0.0) & ~(c < 2.0 * fold / 3.0))   # k = 0: nothing to solve, whatever c is
+        rho = np.where(no_root, 0.0, c)
+        live = ~no_root & (k != 0.0)
+        for _ in range(50):
+            f = rho * (1.0 + k * rho * rho) - c
+            nxt = np.where(live, rho - f / (1.0 + 3.0 * k * rho * rho), rho)
+            same = nxt == rho
+            rho = nxt
+            if same.all():
+                break
+        s = 1.0 + k * rho * rho
+        no_root |= (k != 0.0) & (~np.isfinite(rho) | ~(1.0 + 3.0 * k * rho * rho > 0.0) | ~(rho >= 0.0))
+    gs = np.where(no_root, 1.0, np.where(k != 0.0, g * s, g))
+    rows[0] /= gs; rows[1] /= gs
+    return p, no_root
 
 
 def rescale_observations(p, cam, focal):
@@ -2197,7 +2260,7 @@ class Context:
     def bundle_adjust(self, rot, t, P, fix_rotations=False, max_iters=1000, max_time=300.0, eta=0.1, function_tol=1e-6,
                       gradient_tol=1e-10, parameter_tol=1e-8, trace=0, loss="trivial", loss_scale=0.0, nonmonotonic=False, max_nonmonotonic=0,
                       linear_solver="iterative_schur", preconditioner="jacobi", refine_focal=False, focal=None, focal_free=None,
-                      focal_group=None):
+                      focal_group=None, refine_distortion=False, distortion=None, distortion_free=None):
         """reprojection bundle adjustment of a recovered solution (the reference's Ceres refinement, xm_ctx_bundle_adjust): rot 3 x 3n
         (R_i), t 3 x n, P 3 x m as recover_rotations / recover_tp return them -> refined (rot, t, P, info); matrix-free contexts only.
         loss: a BA_LOSS name with its scale loss_scale (Ceres's a, in normalised image units: pixels / focal length); nonmonotonic=True:
@@ -2218,8 +2281,21 @@ class Context:
         of one physical camera do; focal and focal_free then have G entries (focal None: ones, G = max(focal_group) + 1) and
         info["focal"] has shape (G,); pass info["focal"][focal_group] where per-image scales are taken (reprojection_errors,
         rescale_observations).  With at most BA_FOCAL_GROUPS_EXACT groups the PCG's preconditioner holds the exact focal block
-        (info["coarse_fallbacks"]: LM iterations in which it could not be factored).  None: the per-image call, unchanged."""
+        (info["coarse_fallbacks"]: LM iterations in which it could not be factored).  None: the per-image call, unchanged.
+        refine_distortion=True (xm_ctx_bundle_adjust_radial; implies refine_focal=True): one radial coefficient k_i per camera joins the
+        block behind the focal scale, r = g_i (1 + k_i |u|^2) u - z with u = pi(X) (COLMAP's SIMPLE_RADIAL); distortion (n; None = zeros) is
+        the start, distortion_free (n; None = all) holds the cameras with 0; info["distortion"] is the refined array (n,).  A candidate
+        at which the radial map folds at a used observation (1 + 3 k |u|^2 <= 0) is rejected like one with a focal <= 0.  Not with
+        focal_group.  undistort_observations carries the result to everything that has no distortion argument."""
         group_of = None
+        dist = dist_free = None
+        if refine_distortion:   # refused before the device
+            if focal_group is not None:
+                raise XmError("refine_distortion: a radial coefficient shared by focal group is not built (no focal_group)")
+            refine_focal = True
+            dist, dist_free = _dist_args(self.n, distortion, distortion_free)
+        elif distortion is not None or distortion_free is not None:
+            raise XmError("distortion / distortion_free are given but refine_distortion is not set")
         if focal_group is not None:
             if not refine_focal:
                 raise XmError("focal_group is given but refine_focal is not set")
@@ -2252,6 +2328,10 @@ class Context:
                                                          P.ctypes.data_as(C.c_void_p), focal.size, group_of.ctypes.data_as(C.c_void_p),
                                                          focal.ctypes.data_as(C.c_void_p),
                                                          None if focal_free is None else focal_free.ctypes.data_as(C.c_void_p), C.byref(res)))
+        elif refine_distortion:
+            opt.flags |= BA_REFINE_FOCAL | BA_REFINE_RADIAL
+            V = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+            _chk(lib().xm_ctx_bundle_adjust_radial(self.h, C.byref(opt), V(rot), V(t), V(P), V(focal), V(focal_free), V(dist), V(dist_free), C.byref(res)))
         elif refine_focal:
             opt.flags |= BA_REFINE_FOCAL
             _chk(lib().xm_ctx_bundle_adjust_focal(self.h, C.byref(opt), rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
@@ -2263,6 +2343,8 @@ class Context:
         info = {k: getattr(res, k) for k, _ in BaResult._fields_ if k != "struct_size"}
         if refine_focal:
             info["focal"] = focal
+        if refine_distortion:
+            info["distortion"] = dist
         info["status_name"] = BA_STATUS.get(res.status, "?")
         if tr is not None:
             info["trace"] = tr[: res.trace_len].copy()
@@ -2415,8 +2497,19 @@ class Context:
         focal, focal_free = _focal_args(self.n, focal, focal_free, preconditioner)
         return self._ba_probe(rot, t, P, mu, fix_rotations, loss, loss_scale, preconditioner, X, dc, dense, True, focal, focal_free)
 
+    def ba_probe_radial(self, rot, t, P, mu, focal=None, focal_free=None, distortion=None, distortion_free=None, fix_rotations=False,
+                        loss="trivial", loss_scale=0.0, X=None, dc=None, dense=False, preconditioner="jacobi"):
+        """ba_probe for bundle_adjust(refine_distortion=True) (the test export xm_ctx_ba_probe_radial): focal, focal_free, distortion,
+        distortion_free as there; the same dict with CD = 8, or 5 with fixed rotations, the focal and then the radial coefficient the last
+        entries of a camera's block; with dc also focal1 and dist1 (n), the candidate's values, and cost1 is NaN when a focal is not
+        positive or the radial map folds at a used observation.  preconditioner: only "jacobi"."""
+        focal, focal_free = _focal_args(self.n, focal, focal_free, preconditioner)
+        dist, dist_free = _dist_args(self.n, distortion, distortion_free)
+        return self._ba_probe(rot, t, P, mu, fix_rotations, loss, loss_scale, preconditioner, X, dc, dense, True, focal, focal_free,
+                              dist=dist, dist_free=dist_free)
+
     def _ba_probe(self, rot, t, P, mu, fix_rotations, loss, loss_scale, preconditioner, X, dc, dense, refine_focal, focal, focal_free,
-                  group_of=None):
+                  group_of=None, dist=None, dist_free=None):
         rot = np.asfortranarray(np.asarray(rot, dtype=np.float64)); t = np.asfortranarray(np.asarray(t, dtype=np.float64))
         P = np.asfortranarray(np.asarray(P, dtype=np.float64))
         n, m = self.n, self.n_landmarks
@@ -2427,11 +2520,13 @@ class Context:
             raise XmError(f"unknown preconditioner {preconditioner!r} (one of {', '.join(BA_PRECONDITIONERS)})")
         cd, nc = (3, 4) if fix_rotations else (6, 7)
         cd += 1 if refine_focal else 0
+        cd += 1 if dist is not None else 0
         nd = cd * n
         nvec = nd if group_of is None else (cd - 1) * n + focal.size   # entries of b, of a column of X and of dc
         q = BaProbe()
         q.struct_size = C.sizeof(BaProbe)
         q.flags = (BA_FIX_ROTATIONS if fix_rotations else 0) | BA_PRECONDITIONERS[preconditioner] | (BA_REFINE_FOCAL if refine_focal else 0)
+        q.flags |= BA_REFINE_RADIAL if dist is not None else 0
         q.loss, q.loss_scale, q.mu = BA_LOSS[loss], float(loss_scale), float(mu)
         out = dict(b=np.zeros((n, cd) if group_of is None else nvec), g_l=np.zeros((m, 3)), vinv=np.zeros((m, 6)), ustar=np.zeros((n, cd, cd)), sinv=np.zeros((n, cd, cd)),
                    cused=np.zeros(n, dtype=np.int32), lused=np.zeros(m, dtype=np.int32))
@@ -2463,6 +2558,13 @@ class Context:
                                                     None if focal1 is None else focal1.ctypes.data_as(C.c_void_p)))
             if focal1 is not None:
                 out["focal1"] = focal1
+        elif dist is not None:
+            focal1 = np.zeros(n) if dc is not None else None
+            dist1 = np.zeros(n) if dc is not None else None
+            V = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+            _chk(lib().xm_ctx_ba_probe_radial(self.h, V(rot), V(t), V(P), V(focal), V(focal_free), V(dist), V(dist_free), C.byref(q), V(focal1), V(dist1)))
+            if dc is not None:
+                out["focal1"] = focal1; out["dist1"] = dist1
         elif refine_focal:
             focal1 = np.zeros(n) if dc is not None else None
             _chk(lib().xm_ctx_ba_probe_focal(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p),
@@ -2679,16 +2781,23 @@ class Context:
                 out.update(f_cand=q.f_cand, rr_cand=q.rr_cand, m_cand=q.m_cand)
         return {k: (np.ascontiguousarray(val) if isinstance(val, np.ndarray) else val) for k, val in out.items()}
 
-    def reprojection_errors(self, rot, t, P, focal=None):
+    def reprojection_errors(self, rot, t, P, focal=None, distortion=None):
         """|r_e|^2 (unrobustified) of every observation in input order at (rot, t, P) -- the layouts of bundle_adjust -- with the
         context's current weights, -1 where the adjustment does not use the observation (weight <= 0 or p_e2 <= 0): an (nobs,) array.
-        focal (n): the residual with focal scales, g_i pi(X) - z (xm_ctx_reprojection_errors_focal)"""
-        if focal is not None:
+        focal (n): the residual with focal scales, g_i pi(X) - z (xm_ctx_reprojection_errors_focal); distortion (n; focal None = ones):
+        the residual g_i (1 + k_i |u|^2) u - z of bundle_adjust(refine_distortion=True) (xm_ctx_reprojection_errors_radial)"""
+        if focal is not None or distortion is not None:
             focal, _ = _focal_args(self.n, focal, None)
+        if distortion is not None:
+            distortion, _ = _dist_args(self.n, distortion, None)
         rot = np.asfortranarray(np.asarray(rot, dtype=np.float64)); t = np.asfortranarray(np.asarray(t, dtype=np.float64))
         P = np.asfortranarray(np.asarray(P, dtype=np.float64))
         assert rot.shape == (3, 3 * self.n) and t.shape == (3, self.n) and P.shape == (3, self.n_landmarks)
         out = np.zeros(self.ne)
+        if distortion is not None:
+            V = lambda a: a.ctypes.data_as(C.c_void_p)
+            _chk(lib().xm_ctx_reprojection_errors_radial(self.h, V(rot), V(t), V(P), V(focal), V(distortion), V(out)))
+            return out
         if focal is not None:
             _chk(lib().xm_ctx_reprojection_errors_focal(self.h, rot.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
                                                         P.ctypes.data_as(C.c_void_p), focal.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
